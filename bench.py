@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the ISTVT hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]       (N > 1: starts its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                              (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W     (the same ranks, started by the caller)
 
@@ -15,10 +16,24 @@ the per-GPU batch is fixed, so `value` = N * B * K / max-over-ranks(time).
 Other modes: --frames 16 (C4), --batch 64 --attn-fp8 (C5), --eval (forward only, a different
 metric), --torch-optimizer, --no-wgrad-overlap, --no-early-allreduce (the plain variants).
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (the MFMA GEMM: 97 % of
-the model's FLOPs): algorithmic FLOPs of its launches / their duration measured with events on
-the launch stream in an instrumented extra step.  `cpu_baseline` times the oracle (the CPU
-restatement of the reference, parity-pinned to it) on the host cores on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); everything else
+runs only with --full, after the timed steps: the extra legs (dead-row elimination, host
+boundary, captured HIP graphs; N > 1: the other all-reduce schedule and the steps without
+collectives), the instrumented step behind `roofline` / `kernels`, `other_configs` (C4 / C5 /
+C1 / native), `cpu_baseline` and the N = 1 record for later N > 1 runs.  `roofline` describes
+the dominant kernel (the MFMA GEMM: 97 % of the model's FLOPs): algorithmic FLOPs of its
+launches / their duration measured with events on the launch stream in an instrumented extra
+step.  `cpu_baseline` times the oracle (the CPU restatement of the reference, parity-pinned to
+it) on the host cores on a bounded sample.
+
+--dump-outputs DIR (rank 0) writes what the last timed step computed, as float32 .npy files:
+logits.npy (B,), and for a training step loss.npy (1,), params_sample.npy and one
+<state>_sample.npy per optimizer state (momentum_buffer for SGD; exp_avg, exp_avg_sq for Adam)
+-- the updated parameters and optimizer state at the same 2^21 fixed positions of the flat
+parameter order (numpy default_rng(0), sorted; all of them if there are fewer).  Weights
+(torch.manual_seed(0)) and inputs (generator seed 1 + rank) are the same in every run with
+the same arguments.
 """
 import argparse
 import json
@@ -54,6 +69,11 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every extra measurement (legs, instrumented step, other_configs, '
+                         'cpu_baseline); a plain run times the headline steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (float32; see the module docstring)')
     ap.add_argument('--batch', type=int, default=32, help='clips per GPU')
     ap.add_argument('--frames', type=int, default=8)
     ap.add_argument('--size', type=int, default=224)
@@ -70,7 +90,7 @@ def parse():
                     help='torch.optim.SGD + a separate zero-grad pass instead of the fused HIP optimizer step')
     ap.add_argument('--dead-row-elimination', action='store_true',
                     help='opt-in: skip the rows of the last layer that cannot reach the logits (identical results; '
-                         'STTransformer.dead_row_elimination).  Without the flag the default run still reports this '
+                         'STTransformer.dead_row_elimination).  Without the flag a --full run still reports this '
                          'variant\'s step time as an extra field')
     ap.add_argument('--no-dre-extra', action='store_true',
                     help='skip the extra K steps that fill the with_dead_row_elimination field (profiled runs: one kind of step in the trace)')
@@ -80,7 +100,7 @@ def parse():
                     help='a BASELINE.json configuration by name: C1 1-clip T=4 96^2 depth-2 float32, C2 (default) B=32 T=8 224^2 bf16, '
                          'C3 = C2 per GPU on 8 GPUs (use with --gpus 8), C4 T=16, C5 B=64 with fp8 spatial-attention operands')
     ap.add_argument('--host-boundary', action='store_true', default=True,
-                    help='(default) extra field with_host_boundary: the same K steps with the reference loop\'s host side in the '
+                    help='(default with --full) extra field with_host_boundary: the same K steps with the reference loop\'s host side in the '
                          'timed region (train_CNN.py:506,512,534-536): per-step H2D copy of the (B,T,3,S,S) batch from pinned '
                          'memory (double-buffered on a copy stream), loss.item() and the accuracy count; NOT the headline value')
     ap.add_argument('--no-host-boundary', dest='host_boundary', action='store_false', help='skip the with_host_boundary leg')
@@ -117,7 +137,7 @@ def parse():
                     help='run the HEADLINE steps through the captured HIP graphs too (default: launch by launch; the graphs are '
                          'reported as the extra field with_step_graphs)')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the short C4 / C5 / C1 legs that fill the other_configs field of the default run')
+                    help='skip the short C4 / C5 / C1 legs that fill the other_configs field of a --full run')
     ap.add_argument('--self-launch', action='store_true',
                     help='start the rank(s) through the self-launcher even for --gpus 1 (what --gpus N > 1 does without '
                          'WORLD_SIZE in the environment): the launcher path of the multi-GPU run, testable on a one-GPU box')
@@ -576,6 +596,34 @@ def make_optimizer(a, parallel, bucket, live):
     return parallel.FusedSGD(bucket, lr=a.learning_rate, momentum=0.9, weight_decay=a.weight_decay, zero_grad=True)
 
 
+DUMP_SAMPLE = 1 << 21           # positions of the flat parameter order written by --dump-outputs (8 MiB per array)
+
+
+def dump_outputs(a, logits, loss, opt, bucket, live, dev):
+    """--dump-outputs: the last timed step's logits, loss, updated parameters and optimizer state (the latter two at a fixed,
+    seeded sample of positions of the flat parameter order) as DIR/<name>.npy, float32"""
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    arrays = {'logits': logits.detach().float().view(-1)}
+    if loss is not None:
+        arrays['loss'] = loss.detach().float().view(1)
+        if bucket.flat_params is not None:
+            flat = {'params': bucket.flat_params}
+            flat.update({name: getattr(opt, name) for name in getattr(opt, '_state_names', ())})
+        else:                               # --torch-optimizer: per-parameter tensors, concatenated in the bucket's order
+            flat = {'params': torch.cat([p.detach().reshape(-1) for p in live])}
+            names = sorted({k for st in opt.state.values() for k, v in st.items() if torch.is_tensor(v) and v.numel() > 1})
+            for name in names:
+                flat[name] = torch.cat([opt.state[p][name].reshape(-1) for p in live])
+        n = flat['params'].numel()
+        idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, size=DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(dev)
+        for name, t in flat.items():
+            arrays[name + '_sample'] = t.detach().reshape(-1)[idx].float()
+    for name, t in arrays.items():
+        np.save(os.path.join(a.dump_outputs, name + '.npy'), t.cpu().numpy().astype(np.float32))
+
+
 def headline(a, world, rank, local_rank, multi):
     """the timed run of the configuration `a` names; returns the JSON dict on rank 0 (None elsewhere)"""
     dev = torch.device('cuda', local_rank)
@@ -616,17 +664,22 @@ def headline(a, world, rank, local_rank, multi):
     if a.step_graphs:
         model.enable_step_graphs(True)
 
+    last = {}                               # the logits of the latest step (--dump-outputs)
+
     def step(reduce=True, xin=None, lab=None, want_logits=False, after_loss=None):
         xin = x if xin is None else xin
         lab = labels if lab is None else lab
         if a.eval:
             with torch.no_grad():
-                return model(xin).sum()
+                logits = model(xin)
+                last['logits'] = logits
+                return logits.sum()
         if a.torch_optimizer:
             bucket.zero()
         else:
             opt.zero_grad()                 # a pass only before the first step: the fused step re-zeroes the gradients
         logits = model(xin)
+        last['logits'] = logits
         loss = crit(logits.view(-1), lab)
         if after_loss is not None:
             after_loss(loss, logits)
@@ -669,12 +722,14 @@ def headline(a, world, rank, local_rank, multi):
         per_rank = [round(float(t.item()) / a.steps * 1e3, 3) for t in allt]
         elapsed = max(float(t.item()) for t in allt)
     loss_val = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, last['logits'], None if a.eval else loss, opt, bucket, live, dev)
 
     # ---- N > 1: the same K steps under the OTHER collective schedule, so that one run decides between them: the default
     # starts the transformer's 98.8 % of the bucket from inside backward (two collectives per step: that slice, then the
     # stem's 4.4 MB), the alternative is north_star's single blocking all-reduce after backward.
     schedules = None
-    if multi and not a.eval:
+    if multi and not a.eval and a.full:
         def timed(k):
             sync()
             t1 = time.perf_counter()
@@ -713,7 +768,7 @@ def headline(a, world, rank, local_rank, multi):
     # ---- N > 1: the same K steps on every rank with NO collective (what each GPU does alone, in this very job: same
     # clocks, same host load), so that one line separates "the GPUs are slower together" from "the all-reduce costs".
     alone = None
-    if multi and not a.eval:
+    if multi and not a.eval and a.full:
         was_early = bucket._early is not None
         first_vit = next(i for i, (n, _) in enumerate(live_named) if n.startswith('vit.'))
         bucket.disable_early_all_reduce()
@@ -756,7 +811,7 @@ def headline(a, world, rank, local_rank, multi):
 
     # ---- extra field: the same K steps with the opt-in dead-row elimination (identical logits / gradients, fewer FLOPs)
     dre = None
-    if not a.eval and not a.dead_row_elimination and not a.no_dre_extra and a.depth > 1:
+    if a.full and not a.eval and not a.dead_row_elimination and not a.no_dre_extra and a.depth > 1:
         model.set_dead_row_elimination(True)
         step(); step()
         sync()
@@ -776,7 +831,7 @@ def headline(a, world, rank, local_rank, multi):
 
     # ---- extra field: the reference loop's host boundary inside the timed region (train_CNN.py:506,512,534-536)
     hostb = None
-    if a.host_boundary and not a.eval:
+    if a.full and a.host_boundary and not a.eval:
         shape = (a.batch, a.frames, 3, a.size, a.size)
         pin = [torch.randn(shape, generator=g).pin_memory() for _ in range(2)]
         pin_l = [(torch.rand((a.batch,), generator=g) > 0.5).float().pin_memory() for _ in range(2)]
@@ -847,7 +902,7 @@ def headline(a, world, rank, local_rank, multi):
 
     # ---- extra field: the same K steps with forward and backward replayed as two captured HIP graphs (parallel.StepGraphs)
     graphs = None
-    if not (multi or a.eval or a.torch_optimizer or a.no_step_graphs or a.step_graphs):
+    if a.full and not (multi or a.eval or a.torch_optimizer or a.no_step_graphs or a.step_graphs):
         model.enable_step_graphs(True)
         for _ in range(4):                  # two launch-by-launch warm-up calls, the capture, one replay
             step()
@@ -876,7 +931,7 @@ def headline(a, world, rank, local_rank, multi):
     # ---- instrumented extra step: every GEMM launch bracketed by events on its stream
     roof = None
     kern = None
-    if rank == 0 and not a.no_kernel_profile:
+    if a.full and rank == 0 and not a.no_kernel_profile:
         ops.gemm_profile = []
         ops.kernel_profile = []
         Fn.set_wgrad_overlap(False)         # one stream: a kernel's duration is then its own, not its neighbour's
@@ -1095,14 +1150,14 @@ def main():
         elif 'WORLD_SIZE' in os.environ:
             out['launcher'] = {'self_launched': False, 'note': 'ranks started by the caller (torch.distributed.run)'}
         default_c2 = (a.batch, a.frames, a.size, a.depth, a.dtype, bool(a.attn_fp8)) == (32, 8, 224, 12, 'bf16', False)
-        if world == 1 and default_c2 and not (a.eval or a.no_other_configs or a.rccl_rehearsal):
+        if a.full and world == 1 and default_c2 and not (a.eval or a.no_other_configs or a.rccl_rehearsal):
             # BASELINE.json's other single-GPU configurations, short legs after the headline (its model is freed)
             out['other_configs'] = other_configs(a, local_rank)
-        if world == 1 and not a.no_cpu_baseline and not a.eval:
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.eval:
             out['cpu_baseline'] = cpu_baseline(a.frames, a.size, a.depth)
-        if world == 1 and default_c2 and not (a.eval or a.rccl_rehearsal or a.dead_row_elimination):
+        if a.full and world == 1 and default_c2 and not (a.eval or a.rccl_rehearsal or a.dead_row_elimination):
             n1_cache_write(out)
-        if world > 1:
+        if a.full and world > 1:
             # cpu_baseline is measured at N = 1 only (bounded sample on rank 0); the N > 1 line carries the newest N = 1
             # record of this host, if a run left one, so SCALE can be cross-checked against BENCH from one line
             ref = n1_cache_read()

@@ -775,7 +775,7 @@ def test_bench_two_rank_path_rehearsal():
     env = dict(os.environ, ISTVT_BENCH_REHEARSAL='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29541', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-           '--frames', '4', '--size', '96', '--depth', '2', '--no-cpu-baseline']
+           '--frames', '4', '--size', '96', '--depth', '2', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -869,7 +869,7 @@ def test_bench_gpus_n_self_launch_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['ISTVT_BENCH_REHEARSAL'] = '1'
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-           '--frames', '4', '--size', '96', '--depth', '2', '--no-cpu-baseline', '--host-boundary']
+           '--frames', '4', '--size', '96', '--depth', '2', '--no-cpu-baseline', '--host-boundary', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -894,7 +894,7 @@ def test_bench_real_self_launch_parent_on_this_box():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'ISTVT_BENCH_REHEARSAL')}
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--self-launch', '--gpus', '1', '--rccl-rehearsal', '--steps', '2',
            '--warmup', '1', '--batch', '2', '--frames', '4', '--size', '96', '--depth', '2', '--no-cpu-baseline',
-           '--no-kernel-profile', '--no-dre-extra', '--no-host-boundary']
+           '--no-kernel-profile', '--no-dre-extra', '--no-host-boundary', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

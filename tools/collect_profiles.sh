@@ -8,9 +8,9 @@ tag=${1:-r04}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py > $out/bench.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_single -- python3 bench.py --no-cpu-baseline --no-dre-extra --no-other-configs --no-host-boundary --no-step-graphs --no-wgrad-overlap > $out/bench_prof_single.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_overlap -- python3 bench.py --no-cpu-baseline --no-dre-extra --no-other-configs --no-host-boundary --no-step-graphs > $out/bench_prof_overlap.log 2>&1
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_single -- python3 bench.py --full --no-cpu-baseline --no-dre-extra --no-other-configs --no-host-boundary --no-step-graphs --no-wgrad-overlap > $out/bench_prof_single.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_overlap -- python3 bench.py --full --no-cpu-baseline --no-dre-extra --no-other-configs --no-host-boundary --no-step-graphs > $out/bench_prof_overlap.log 2>&1
 cp $(ls $out/trace_single/*/*_kernel_stats.csv | head -1) $out/kernel_stats.csv
 cp $(ls $out/trace_overlap/*/*_kernel_stats.csv | head -1) $out/overlap_kernel_stats.csv
 B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-profile --no-dre-extra --no-other-configs --no-wgrad-overlap --no-host-boundary --no-step-graphs"
