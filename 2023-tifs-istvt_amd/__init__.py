@@ -10,5 +10,6 @@ Layout
     functional.py  torch.autograd.Function glue (autograd plumbing only)
     network/       nn.Modules mirroring the reference's constructor/forward signatures
     parallel.py    data-parallel gradient bucket (one RCCL all-reduce per step)
+    explain.py     relevance maps (gradient-weighted attention rollout)
 """
-__all__ = ['ops', 'functional', 'network', 'parallel']
+__all__ = ['ops', 'functional', 'network', 'parallel', 'explain']

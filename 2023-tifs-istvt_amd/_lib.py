@@ -28,6 +28,9 @@ SIGNATURES = {
     'istvt_attn_spatial_bwd_fp8': [P, L, P, P, L, P, P, P, I, I, I, I, F, I, P],
     'istvt_attn_temporal_fwd': [P, L, P, L, P, L, I, I, I, I, I, F, I, I, P],
     'istvt_attn_temporal_bwd': [P, L, P, L, P, L, P, P, I, I, I, I, I, F, I, I, P],
+    'istvt_attn_spatial_relevance': [P, L, P, L, P, P, P, I, I, I, I, F, I, P],
+    'istvt_attn_temporal_relevance': [P, L, P, L, P, P, I, I, I, I, I, F, I, I, P],
+    'istvt_relevance_heatmap': [P, P, I, I, I, P],
     'istvt_tokens_fwd': [P, P, P, P, P, L, I, I, I, I, I, I, P],
     'istvt_tokens_bwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],
     'istvt_frame_diff': [P, P, I, I, I, I, I, I, P],

@@ -1,0 +1,120 @@
+"""Relevance maps of ISTVT: gradient-weighted attention rollout (Chefer, Gur, Wolf, ICCV 2021, "Generic Attention-model
+Explainability"), the interpretable half of the reference (visualize_rel.py:206-294) on the HIP path.
+
+    res = istvt_amd.explain.relevance(model, clips, index=0)      # or model.relevance(clips)
+    maps = istvt_amd.explain.heatmaps(res.cam_s, scale=16)        # (B, T, g*16, g*16), min-max normalised per map
+
+Definition (DESIGN.md "Relevance maps"): y = sum_b logits[b, index]; per layer and head A = softmax output, G = dy/dA;
+Abar_l = (1/H) sum_h max(0, A_{l,h} * G_{l,h}); r = e_0, r <- r + r Abar_l for l = L-1 .. 0, one spatial rollout per
+(clip, frame) over tokens and one temporal rollout per (clip, position) over frames.  No row normalisation (the 2021b
+"generic" rule, not the LRP rules of the reference's `tfe` package).
+
+The call leaves the model as it found it: eval mode for the call (BatchNorm statistics do not move), the stem under
+no_grad, a backward pass to the token input only, no parameter gradient computed (p.grad, the fused bucket and any
+data-parallel hook see nothing), eager even when step graphs are on (the graph cache is not touched), fp8 attention
+operands off (the recomputed probabilities must match the forward's statistics), and every flag restored in a
+``finally``.
+"""
+from __future__ import annotations
+
+import contextlib
+
+import torch
+
+from . import functional as Fn
+from . import ops
+
+
+class Relevance:
+    """cam_s, cam_t (B, T, P-1): the per-frame spatial and temporal maps (the reference's cam_s and cam_t after its
+    transpose(0, 1), visualize_rel.py:259); r_s (B, F, P), r_t (B, P, F): the raw rollouts; logits (B, num_classes)."""
+    __slots__ = ('cam_s', 'cam_t', 'r_s', 'r_t', 'logits')
+
+    def __init__(self, r_s, r_t, logits):
+        self.r_s, self.r_t, self.logits = r_s, r_t, logits
+        self.cam_s = r_s[:, 1:, 1:]                           # cam_s[b, t, n-1] = r_s[b, t+1, n]
+        self.cam_t = r_t[:, 1:, 1:].transpose(1, 2)           # cam_t[b, t, n-1] = r_t[b, n, t+1]
+
+    def __repr__(self):
+        return 'Relevance(cam_s=%s, cam_t=%s)' % (tuple(self.cam_s.shape), tuple(self.cam_t.shape))
+
+
+def _attention_modules(model):
+    from .network.vivit.module import SpatialOnlyAttention
+    return [m for m in model.modules() if isinstance(m, SpatialOnlyAttention)]
+
+
+@contextlib.contextmanager
+def _explaining(model):
+    """eval mode, fp8 attention operands off and every parameter frozen for the call; all restored afterwards"""
+    modes = [(m, m.training) for m in model.modules()]
+    fp8 = [(m, m.attn_fp8) for m in _attention_modules(model)]
+    req = [(p, p.requires_grad) for p in model.parameters()]
+    try:
+        for m, _ in modes:
+            m.training = False
+        for m, _ in fp8:
+            m.attn_fp8 = False
+        for p, _ in req:
+            p.requires_grad_(False)
+        yield
+    finally:
+        for p, on in req:
+            p.requires_grad_(on)
+        for m, on in fp8:
+            m.attn_fp8 = on
+        for m, on in modes:
+            m.training = on
+
+
+def _rollouts(dsttr, feats, index):
+    """feats (b, t, hw, c) -> Relevance; the caller has put the model in _explaining"""
+    if feats.dim() != 4:
+        raise RuntimeError('relevance: features must be (b, t, h*w, c), got %s' % (tuple(feats.shape),))
+    b, t, hw, _ = feats.shape
+    f, p = t + 1, hw + 1
+    with torch.no_grad():
+        x = Fn.TokensFn.apply(ops.cast(feats, dsttr.compute_dtype), dsttr.space_token, dsttr.temporal_token,
+                              dsttr.pos_embedding)
+    x = x.detach().requires_grad_(True)                       # the backward pass ends at the tokens
+    rel = Fn.RelevanceContext(b, f, p, x.device)
+    with torch.enable_grad(), Fn.relevance_mode(rel):
+        logits = dsttr.forward_tokens(x, b, f, p)
+    if not 0 <= index < logits.shape[1]:
+        raise IndexError('relevance: index %d out of range for %d outputs' % (index, logits.shape[1]))
+    torch.autograd.grad(logits[:, index].sum(), x)
+    return Relevance(rel.r_s.view(b, f, p), rel.r_t.view(b, p, f), logits.detach())
+
+
+def relevance_features(dsttr, feats, index=0) -> Relevance:
+    """Relevance maps of a DSTTr from its input features (b, t, h*w, c)."""
+    with _explaining(dsttr):
+        return _rollouts(dsttr, feats, index)
+
+
+def relevance(model, x, index=0) -> Relevance:
+    """Relevance maps of an XceptionVidTr for the clips x (b, t, 3, S, S) and output `index` (a DSTTr takes its features
+    (b, t, h*w, c) instead, as relevance_features)."""
+    from .network.vivit.vivit import DSTTr, XceptionVidTr
+    if isinstance(model, DSTTr):
+        return relevance_features(model, x, index)
+    if not isinstance(model, XceptionVidTr):
+        raise TypeError('relevance: expected an XceptionVidTr or a DSTTr, got %s' % type(model).__name__)
+    with _explaining(model):
+        b, t = x.shape[:2]
+        with torch.no_grad():
+            feats = model.xcep.model.low_level_features_nhwc(x.flatten(0, 1), model.compute_dtype)
+        n, h, w, c = feats.shape
+        return _rollouts(model.vit, feats.view(b, t, h * w, c), index)
+
+
+def heatmaps(cam, scale: int = 16):
+    """The reference's post-processing of one map (visualize_rel.py:262-265) for every map at once: bilinear upsampling
+    by `scale` (align_corners=False) and (x - min) / (max - min) per map.  cam: (B, T, g, g), or (B, T, g*g) as
+    Relevance.cam_s / cam_t hold it -> (B, T, g*scale, g*scale) float32."""
+    if cam.dim() == 3:
+        g = int(round(cam.shape[-1] ** 0.5))
+        if g * g != cam.shape[-1]:
+            raise RuntimeError('heatmaps: %d tokens per map is not a square grid' % cam.shape[-1])
+        cam = cam.reshape(*cam.shape[:-1], g, g)
+    return ops.relevance_heatmap(cam, scale)

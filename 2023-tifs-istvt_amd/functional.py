@@ -9,7 +9,9 @@ returns ``None`` for it, which removes one zero-fill and one add pass per parame
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import threading
 
 import torch
 from torch.autograd import Function
@@ -28,6 +30,65 @@ def _target(p):
         return p.grad, None
     z = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
     return z, z
+
+
+# Relevance context (gradient-weighted attention rollout, explain.py; DESIGN.md "Relevance maps").  Thread-local and
+# inactive by default.  A Function whose forward runs while one is active keeps a reference to it (ctx.rel): the
+# backward pass runs on the autograd engine's device thread, where the caller's thread-local state is not visible.
+# With ctx.rel set, the attention backwards also launch one rollout step each (an extra launch: the training kernels are
+# unchanged), and the LayerNorm / FeedForward backwards compute no parameter gradients.  With it None (every call outside
+# relevance_mode) the backward path is the training path, unchanged.
+_rel_tls = threading.local()
+
+
+class RelevanceContext:
+    """The two rollouts of one relevance() call, updated in place by the attention backwards from the last layer to
+    the first: r_s [B*F, P] (one vector per (clip, frame)) and r_t [B*P, F] (one per (clip, position)), both starting
+    at e_0 (the space class token, the temporal class frame)."""
+
+    def __init__(self, B: int, F: int, P: int, device):
+        self.geom = (B, F, P)
+        self.r_s = torch.zeros((B * F, P), dtype=torch.float32, device=device)
+        self.r_s[:, 0] = 1.0
+        self.r_t = torch.zeros((B * P, F), dtype=torch.float32, device=device)
+        self.r_t[:, 0] = 1.0
+
+    def spatial_step(self, qkv, dout, lse, BF, P, heads, dh):
+        B, F, P0 = self.geom
+        if P != P0:
+            raise RuntimeError('relevance: spatial attention over %d tokens, the context expects %d' % (P, P0))
+        if BF == B * F:
+            self.r_s = ops.attn_spatial_relevance(qkv, dout, lse, self.r_s, BF, P, heads, dh)
+        elif BF == B:
+            # dead-row elimination's last layer attends frame 0 of every clip only; the other frames' outputs are dead
+            # there (dA = 0), so their rollout vectors do not move
+            r0 = ops.attn_spatial_relevance(qkv, dout, lse, self.r_s.view(B, F, P)[:, 0], BF, P, heads, dh)
+            r_s = self.r_s.clone()
+            r_s.view(B, F, P)[:, 0] = r0
+            self.r_s = r_s
+        else:
+            raise RuntimeError('relevance: spatial attention over %d frames, the context has B=%d F=%d' % (BF, B, F))
+
+    def temporal_step(self, qkv, dout, B, F, P, heads, dh, diff):
+        if (B, F, P) != self.geom:
+            raise RuntimeError('relevance: temporal attention geometry %s, the context expects %s' % ((B, F, P), self.geom))
+        self.r_t = ops.attn_temporal_relevance(qkv, dout, self.r_t, B, F, P, heads, dh, diff)
+
+
+def relevance_context():
+    """the active RelevanceContext of this thread, or None"""
+    return getattr(_rel_tls, 'ctx', None)
+
+
+@contextlib.contextmanager
+def relevance_mode(ctx):
+    """make `ctx` the active relevance context of this thread for the forwards run inside the block"""
+    prev = getattr(_rel_tls, 'ctx', None)
+    _rel_tls.ctx = ctx
+    try:
+        yield ctx
+    finally:
+        _rel_tls.ctx = prev
 
 
 class BiasSink:
@@ -49,6 +110,12 @@ class BiasSink:
         return self.bias.grad
 
 
+def _ln_input_grad(dy, x, mean, rstd, gamma, dres):
+    """LayerNorm backward inside a relevance call: the row kernel alone (dx); the fold of its partial rows into the
+    parameter gradients is never launched"""
+    return ops.layernorm_bwd(dy, x, mean, rstd, gamma, None, None, dres=dres, pad=True, defer=lambda *a: None)
+
+
 class LayerNormFn(Function):
     """nn.LayerNorm over the last dim (reference module.py:15-21).  fork=True also returns the input itself: a
     caller that uses x both as the LayerNorm input and as a residual takes the second output for the residual, and
@@ -60,6 +127,7 @@ class LayerNormFn(Function):
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.set_materialize_grads(False)
         ctx.sink = sink
+        ctx.rel = relevance_context()
         return (y, x.view_as(x)) if fork else y
 
     @staticmethod
@@ -71,6 +139,8 @@ class LayerNormFn(Function):
             if dcol is not None and dres is not None:
                 ops.colsum(dres.reshape(-1, dres.shape[-1]), out=dcol)
             return dres, None, None, None, None, None
+        if ctx.rel is not None:
+            return _ln_input_grad(dy, x, mean, rstd, gamma, dres), None, None, None, None, None
         dg, rg = _target(gamma)
         db, rb = _target(beta)
         dx = ops.layernorm_bwd(dy, x, mean, rstd, gamma, dg, db, dres=dres, pad=True, dcol=dcol, defer=_ln_defer(dy, (rg, rb)))
@@ -93,6 +163,7 @@ class LayerNormDiffFn(Function):
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.set_materialize_grads(False)
         ctx.sink = sink
+        ctx.rel = relevance_context()
         y, yd = y.view(*x.shape), yd.view(*x.shape)
         ctx.mark_non_differentiable(yd)         # the tensor that is RETURNED (a view made after the mark would not carry it)
         return (y, yd, x.view_as(x)) if fork else (y, yd)
@@ -111,6 +182,8 @@ class LayerNormDiffFn(Function):
             if dcol is not None and dres is not None:
                 ops.colsum(dres.reshape(-1, dres.shape[-1]), out=dcol)
             return dres, None, None, None, None, None, None
+        if ctx.rel is not None:
+            return _ln_input_grad(dy, x, mean, rstd, gamma, dres), None, None, None, None, None, None
         dg, rg = _target(gamma)
         db, rb = _target(beta)
         dx = ops.layernorm_bwd(dy, x, mean, rstd, gamma, dg, db, dres=dres, pad=True, dcol=dcol, defer=_ln_defer(dy, (rg, rb)))
@@ -472,12 +545,17 @@ class FeedForwardFn(Function):
         ctx.save_for_backward(x, u, g, w1, b1, w2, b2)
         ctx.has_res = residual is not None
         ctx.defer_bias = bool(defer_bias)           # b2's gradient comes from the next LayerNorm's backward (BiasSink)
+        ctx.rel = relevance_context()
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         x, u, g, w1, b1, w2, b2 = ctx.saved_tensors
+        if ctx.rel is not None:                 # relevance call: the input gradient only
+            du = ops.linear_dgrad(dy, ops.weight_as(w2, dy.dtype, pad=True), gelu_u=u, pad=True, gelu_d=ctx.gelu_d)
+            dx = ops.linear_dgrad(du, ops.weight_as(w1, dy.dtype, pad=True), pad=True)
+            return dx, None, None, None, None, (dy if ctx.has_res else None), None
         # (dy W2) * gelu'(u); the hidden layer's bias gradient = its column sums, taken in that GEMM's epilogue
         buf1, db1 = _target(b1)
         du = ops.linear_dgrad(dy, ops.weight_as(w2, dy.dtype, pad=True), gelu_u=u, pad=True, csum=buf1, gelu_d=ctx.gelu_d)
@@ -497,12 +575,15 @@ class SpatialAttnFn(Function):
         ctx.save_for_backward(qkv, out, lse)
         ctx.geom = (BF, P, heads, dh)
         ctx.fp8 = fp8
+        ctx.rel = relevance_context()
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
+        if ctx.rel is not None:
+            ctx.rel.spatial_step(qkv, dout, lse, *ctx.geom)
         return ops.attn_spatial_bwd(qkv, out, dout, lse, *ctx.geom, fp8=ctx.fp8), None, None, None, None, None
 
 
@@ -518,6 +599,7 @@ class TemporalAttnFn(Function):
         out = ops.attn_temporal_fwd(qkv[:, :2 * inner], qkv[:, 2 * inner:], B, F, P, heads, dh, diff=diff)
         ctx.save_for_backward(qkv)
         ctx.geom = (B, F, P, heads, dh, int(diff))
+        ctx.rel = relevance_context()
         return out
 
     @staticmethod
@@ -526,6 +608,8 @@ class TemporalAttnFn(Function):
         (qkv,) = ctx.saved_tensors
         B, F, P, heads, dh, diff = ctx.geom
         inner = heads * dh
+        if ctx.rel is not None:
+            ctx.rel.temporal_step(qkv, dout, B, F, P, heads, dh, diff)
         dqkv, _ = ops.attn_temporal_bwd(qkv[:, :2 * inner], qkv[:, 2 * inner:], dout, B, F, P, heads, dh, diff=diff, packed=True)
         return dqkv, None, None, None, None, None, None
 

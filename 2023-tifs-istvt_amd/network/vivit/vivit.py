@@ -123,12 +123,20 @@ class DSTTr(nn.Module):
         b, t, hw, c = feats.shape
         feats = ops.cast(feats, self.compute_dtype)
         x = Fn.TokensFn.apply(feats, self.space_token, self.temporal_token, self.pos_embedding)
-        p = hw + 1
-        cls = self.transformer(x, hw=p, cls_of=(b, t + 1, p))     # (b, c): temporal-token frame, space-token slot
+        return self.forward_tokens(x, b, t + 1, hw + 1)
+
+    def forward_tokens(self, x, b, f, p):
+        """x: the assembled tokens (b, f*p, dim) -> (b, num_classes) float32 logits"""
+        cls = self.transformer(x, hw=p, cls_of=(b, f, p))         # (b, c): temporal-token frame, space-token slot
         ln, fc = self.mlp_head[0], self.mlp_head[1]
         y = Fn.layer_norm(cls, ln.weight, ln.bias, ln.eps)
         y = Fn.LinearFn.apply(y, fc.weight, fc.bias, None)
         return y.float()
+
+    def relevance_features(self, feats, index=0):
+        """Relevance maps of the clips behind the features (b, t, h*w, c): istvt_amd.explain.relevance on this module"""
+        from istvt_amd import explain
+        return explain.relevance_features(self, feats, index)
 
     def forward(self, x):
         """x: (b, t, c, h, w) as in the reference (vivit.py:132)."""
@@ -190,6 +198,11 @@ class XceptionVidTr(nn.Module):
         if g is not None:
             return g(x)
         return self._forward_eager(x)
+
+    def relevance(self, x, index=0):
+        """Spatial and temporal relevance maps of the clips x (b, t, c, h, w) for output `index`: istvt_amd.explain.relevance"""
+        from istvt_amd import explain
+        return explain.relevance(self, x, index)
 
     def _forward_eager(self, x):
         b, t = x.shape[:2]

@@ -955,6 +955,85 @@ def attn_temporal_bwd(qk: Tensor, v: Tensor, dout: Tensor, B: int, F: int, P: in
 
 
 # ------------------------------------------------------------------------------------------
+# Relevance maps (gradient-weighted attention rollout, DESIGN.md "Relevance maps"): one rollout step per attention call,
+# r_out = r + (1/H) sum_h r E_h, E_h = max(0, A_h * dA_h).  r / r_out fp32, a new r_out per call.
+def _rollout_vec(r: Tensor, rows_: int, n: int, what: str) -> Tensor:
+    _req(r, what)
+    if r.dtype != torch.float32 or r.numel() != rows_ * n:
+        raise RuntimeError('%s: r must be float32 with %d x %d elements, got %s %s' % (what, rows_, n, r.dtype, tuple(r.shape)))
+    return _c(r)
+
+
+def attn_spatial_relevance(qkv: Tensor, dout: Tensor, lse: Tensor, r: Tensor, BF: int, P: int, heads: int, dh: int) -> Tensor:
+    """qkv / lse as attn_spatial_fwd used and returned them, dout [BF*P, heads*dh], r [BF, P] fp32 -> r_out [BF, P]"""
+    inner = heads * dh
+    qkv, ldq = rows(_req(qkv))
+    dout, ldd = rows(_req(dout))
+    if tuple(qkv.shape) != (BF * P, 3 * inner) or tuple(dout.shape) != (BF * P, inner):
+        raise RuntimeError('attn_spatial_relevance: qkv %s / dout %s do not match BF=%d P=%d heads=%d dh=%d'
+                           % (tuple(qkv.shape), tuple(dout.shape), BF, P, heads, dh))
+    if dout.dtype != qkv.dtype:
+        raise TypeError('attn_spatial_relevance: dout is %s, qkv %s' % (dout.dtype, qkv.dtype))
+    if lse.dtype != torch.float32 or lse.numel() != BF * P * heads * 2 or not lse.is_contiguous():
+        raise RuntimeError('attn_spatial_relevance: lse must be the forward\'s contiguous float32 (BF*P, heads, 2) statistics')
+    if dh not in (32, 64):
+        raise RuntimeError('attn_spatial_relevance: dim_head must be 32 or 64, got %d' % dh)
+    r = _rollout_vec(r, BF, P, 'attn_spatial_relevance')
+    out = torch.empty((BF, P), dtype=torch.float32, device=qkv.device)
+    # q, k, v and dO once per key tile (ceil(P / 64) tiles); two P x P x dh products per (frame, head)
+    ntile = (P + 63) // 64
+    with prof('attn_spatial_relevance', (3 * ntile + 1) * BF * P * inner * qkv.element_size(), 4.0 * BF * heads * P * P * dh):
+        _lib.check(_lib.lib().istvt_attn_spatial_relevance(qkv.data_ptr(), ldq, dout.data_ptr(), ldd, lse.data_ptr(),
+                                                           r.data_ptr(), out.data_ptr(), BF, P, heads, dh, dh ** -0.5,
+                                                           dtype_code(qkv), _stream()), 'istvt_attn_spatial_relevance')
+    return out
+
+
+def attn_temporal_relevance(qkv: Tensor, dout: Tensor, r: Tensor, B: int, F: int, P: int, heads: int, dh: int,
+                            diff: int = 0) -> Tensor:
+    """qkv [B*F*P, 3*heads*dh] (the packed q|k|v TemporalAttnFn saved), dout [B*F*P, heads*dh], r [B*P, F] fp32 ->
+    r_out [B*P, F]; diff: the forward's code (0 plain, 1 q / k differenced in the kernel, 2 q / k arrived differenced)"""
+    inner = heads * dh
+    qkv, ldq = rows(_req(qkv))
+    dout, ldd = rows(_req(dout))
+    if F > 17:
+        raise RuntimeError('attn_temporal_relevance: at most 17 frames are supported, got F=%d' % F)
+    if tuple(qkv.shape) != (B * F * P, 3 * inner) or tuple(dout.shape) != (B * F * P, inner):
+        raise RuntimeError('attn_temporal_relevance: qkv %s / dout %s do not match B=%d F=%d P=%d heads=%d dh=%d'
+                           % (tuple(qkv.shape), tuple(dout.shape), B, F, P, heads, dh))
+    if dout.dtype != qkv.dtype:
+        raise TypeError('attn_temporal_relevance: dout is %s, qkv %s' % (dout.dtype, qkv.dtype))
+    if dh not in (32, 64) or int(diff) not in (0, 1, 2):
+        raise RuntimeError('attn_temporal_relevance: dim_head must be 32 or 64 and diff 0, 1 or 2 (got %d, %r)' % (dh, diff))
+    r = _rollout_vec(r, B * P, F, 'attn_temporal_relevance')
+    out = torch.empty((B * P, F), dtype=torch.float32, device=qkv.device)
+    M = B * F * P
+    with prof('attn_temporal_relevance', (4 + (int(diff) == 1)) * M * inner * qkv.element_size(), 4.0 * B * P * heads * F * F * dh):
+        _lib.check(_lib.lib().istvt_attn_temporal_relevance(qkv.data_ptr(), ldq, dout.data_ptr(), ldd, r.data_ptr(),
+                                                            out.data_ptr(), B, F, P, heads, dh, dh ** -0.5, int(diff),
+                                                            dtype_code(qkv), _stream()), 'istvt_attn_temporal_relevance')
+    return out
+
+
+def relevance_heatmap(cam: Tensor, scale: int = 16) -> Tensor:
+    """cam (..., g, g) fp32 -> (..., g*scale, g*scale): bilinear upsampling (align_corners=False) and per-map min-max"""
+    cam = _c(_req(cam, 'cam'))
+    if cam.dtype != torch.float32 or cam.dim() < 2 or cam.shape[-1] != cam.shape[-2]:
+        raise RuntimeError('relevance_heatmap: cam must be float32 (..., g, g), got %s %s' % (cam.dtype, tuple(cam.shape)))
+    g, s = cam.shape[-1], int(scale)
+    if not 1 <= g <= 64 or s < 1 or g * s > 8192:
+        raise RuntimeError('relevance_heatmap: need 1 <= g <= 64 and 1 <= g*scale <= 8192 (g=%d, scale=%d)' % (g, s))
+    maps = cam.numel() // (g * g)
+    out = torch.empty((*cam.shape[:-2], g * s, g * s), dtype=torch.float32, device=cam.device)
+    if maps == 0:
+        return out
+    with prof('relevance_heatmap', 4 * maps * (g * g + g * s * g * s)):
+        _lib.check(_lib.lib().istvt_relevance_heatmap(cam.data_ptr(), out.data_ptr(), maps, g, s, _stream()),
+                   'istvt_relevance_heatmap')
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 def tokens_fwd(feats: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad: bool = False) -> Tensor:
     """feats [B,T,hw,D] -> x [B,(T+1)*(hw+1),D]; pos is the full (1,T,P_decl,D) parameter."""
     feats = _c(_req(feats))

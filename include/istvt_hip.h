@@ -160,6 +160,20 @@ int istvt_attn_temporal_bwd(const void* qk, long ldqk, const void* v, long ldv, 
                             void* dv, int B, int F, int P, int heads, int dh, float scale, int diff, int dtype,
                             istvt_stream_t stream);
 
+/* ---- relevance maps: gradient-weighted attention rollout (DESIGN.md "Relevance maps") -------------------------
+ * One rollout step r_out[j] = r[j] + (1/H) sum_h sum_i r[i] max(0, A_h[i, j] dA_h[i, j]) with A the softmax output and
+ * dA = dO V^T its gradient; fp32 r / r_out, r_out != r.  Spatial: per frame (r, r_out [BF][P]); qkv / ldqkv / lse as
+ * istvt_attn_spatial_fwd wrote them, dout [BF*P][heads*dh] with row stride ldo; P recomputed from lse.  Temporal: per
+ * (clip, position) (r, r_out [B*P][F], F <= 17); qkv [B*F*P][3*heads*dh] (q|k|v), the softmax recomputed in full with
+ * the forward's diff code (0, 1, 2).  dh in {32, 64}. */
+int istvt_attn_spatial_relevance(const void* qkv, long ldqkv, const void* dout, long ldo, const float* lse, const float* r,
+                                 float* r_out, int BF, int P, int heads, int dh, float scale, int dtype, istvt_stream_t stream);
+int istvt_attn_temporal_relevance(const void* qkv, long ldqkv, const void* dout, long ldo, const float* r, float* r_out, int B,
+                                  int F, int P, int heads, int dh, float scale, int diff, int dtype, istvt_stream_t stream);
+/* cam [maps][g][g] fp32 -> out [maps][g*s][g*s] fp32: bilinear upsampling (align_corners=False) by the integer factor s,
+ * then (x - min) / (max - min) per map (visualize_rel.py:262-265).  g <= 64. */
+int istvt_relevance_heatmap(const float* cam, float* out, int maps, int g, int s, istvt_stream_t stream);
+
 /* ---- token assembly (DSTTr.forward, vivit.py:133-142) -------------------------------------- */
 int istvt_tokens_fwd(const void* feats, const float* space, const float* temporal, const float* pos, void* x, long ldx,
                      int B, int F, int P, int D, int pos_rows, int dtype, istvt_stream_t stream);
