@@ -11,5 +11,6 @@ Layout
     network/       nn.Modules mirroring the reference's constructor/forward signatures
     parallel.py    data-parallel gradient bucket (one RCCL all-reduce per step)
     explain.py     relevance maps (gradient-weighted attention rollout)
+    video.py       whole-video scoring: uint8 frames, sliding windows, the stem once per frame
 """
-__all__ = ['ops', 'functional', 'network', 'parallel', 'explain']
+__all__ = ['ops', 'functional', 'network', 'parallel', 'explain', 'video']

@@ -32,6 +32,7 @@ SIGNATURES = {
     'istvt_attn_temporal_relevance': [P, L, P, L, P, P, I, I, I, I, I, F, I, I, P],
     'istvt_relevance_heatmap': [P, P, I, I, I, P],
     'istvt_tokens_fwd': [P, P, P, P, P, L, I, I, I, I, I, I, P],
+    'istvt_tokens_gather_fwd': [P, P, P, P, P, P, L, I, I, I, I, I, I, I, P],
     'istvt_tokens_bwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],
     'istvt_frame_diff': [P, P, I, I, I, I, I, I, P],
     'istvt_stats_replicas': [],
@@ -45,6 +46,7 @@ SIGNATURES = {
     'istvt_bn_add_fwd': [P, P, P, P, P, L, I, I, P],
     'istvt_im2col_conv1': [P, P, I, I, I, P],
     'istvt_conv1_fwd': [P, P, P, I, I, I, P],
+    'istvt_conv1_fwd_u8': [P, P, P, P, P, I, I, I, P],
     'istvt_conv1_wgrad': [P, P, P, P, I, I, I, P],
     'istvt_conv1_wgrad_slabs': [],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],

@@ -61,6 +61,85 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------ conv1 forward from bytes
+// The inference entry of conv1: the frames as a decoder delivers them, uint8 [frames][S][S][3], normalised on the fly as
+// torchvision's ToTensor + Normalize do it, v = (float(u) / 255 - mean[c]) / std[c] with each operation rounded on its own
+// (the explicitly rounded intrinsics: nothing for -ffp-contract=fast to fuse or reassociate).  A byte has 256 values, so
+// the three channels' normalised values are a 3 x 256 float table each workgroup fills in LDS from those expressions; the
+// 27 x 32 multiply-adds then run in conv1_fwd_kernel's order on the same float values, so the output is bit-identical to
+// conv1_fwd_kernel on the float32 NCHW tensor torch makes from the same bytes.
+// Work item = (frame, R output rows): their 2R + 1 input rows are ONE contiguous byte range of the frame, staged in LDS
+// with 16-byte loads (from the enclosing 16-byte-aligned range; pieces that stick out of the tensor are read byte by
+// byte, so any view of a frame batch is accepted and nothing outside [x, x + total) is touched).  Neighbouring outputs
+// share a column and two of three rows: every input byte comes from HBM once per work item (plus one shared row in 2R + 1).
+template <typename T>
+__global__ __launch_bounds__(256) void conv1_fwd_u8(const uint8_t* __restrict__ x, const float* __restrict__ mean,
+                                                    const float* __restrict__ stdv, const float* __restrict__ w,
+                                                    T* __restrict__ u1, long total, int S, int Ho, int R, int ngroups) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* lut = reinterpret_cast<float*>(smem);                  // [3][256]
+    unsigned char* sb = smem + 3 * 256 * sizeof(float);           // staged bytes, sb[j] = byte at aligned address a0 + j
+    const int tid = threadIdx.x;
+    const int grp = (int)(blockIdx.x % ngroups);
+    const long f = blockIdx.x / ngroups;
+    const int y0 = grp * R;
+    const int rows = min(R, Ho - y0);
+    for (int i = tid; i < 3 * 256; i += 256) {
+        const int c = i >> 8;
+        lut[i] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)(i & 255), 255.0f), mean[c]), stdv[c]);
+    }
+    const long g0 = (f * S + 2 * y0) * (long)S * 3;               // first byte of input row 2 y0 of frame f
+    const int len = (2 * rows + 1) * S * 3;                       // rows 2 y0 .. 2 (y0 + rows): 2 (Ho - 1) + 2 <= S - 1
+    const uintptr_t base = reinterpret_cast<uintptr_t>(x);
+    const int lead = (int)((base + (uintptr_t)g0) & 15);
+    const long c0 = g0 - lead;                                    // offset (from x) of the aligned range's first byte
+    const int nchunks = (lead + len + 15) >> 4;
+    for (int c = tid; c < nchunks; c += 256) {
+        const long o = c0 + 16L * c;
+        uint4 v;
+        if (o >= 0 && o + 16 <= total) {
+            v = *reinterpret_cast<const uint4*>(x + o);
+        } else {
+            unsigned char b[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) b[j] = (o + j >= 0 && o + j < total) ? x[o + j] : (unsigned char)0;
+            v = *reinterpret_cast<const uint4*>(b);
+        }
+        *reinterpret_cast<uint4*>(sb + 16 * c) = v;
+    }
+    __syncthreads();
+    const int nout = rows * Ho;
+    for (int o = tid; o < nout; o += 256) {
+        const int yl = o / Ho, xo = o - yl * Ho;
+        float v[27];                                     // [ci][dy][dx]: the order of conv1.weight[co]
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const unsigned char* row = sb + lead + ((2 * yl + dy) * S + 2 * xo) * 3;    // 9 bytes: 3 pixels x RGB
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci) v[ci * 9 + dy * 3 + dx] = lut[ci * 256 + row[dx * 3 + ci]];
+        }
+        const long m = (f * Ho + y0) * (long)Ho + o;
+        int w0 = 0;
+        asm volatile("" : "+s"(w0));                     // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
+        const float* wl = w + w0;
+#pragma unroll
+        for (int c8 = 0; c8 < 4; ++c8) {
+            float acc[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float* wc = wl + (c8 * 8 + j) * 27;    // uniform address: scalar loads
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < 27; ++k) a = fmaf(wc[k], v[k], a);
+                acc[j] = a;
+            }
+            store8(u1 + m * 32 + c8 * 8, acc);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ conv2 forward
 // wf[tap][nt]: row operand fragments; MFMA row rho of n-tile nt is output channel 16 (rho >> 2) + 4 nt + (rho & 3)
 // so that lane (r, g) accumulates channels 16g .. 16g+15 of pixel r over its four n-tiles.
@@ -441,6 +520,30 @@ extern "C" int istvt_conv1_fwd(const float* x, const float* w, void* u1, int Fr,
     const long Mo = (long)Fr * Ho * Ho;
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_kernel<T>), dim3((unsigned)((Mo + 255) / 256)), dim3(256), 0,
                                              stream, x, w, (T*)u1, Mo, S, Ho, Ho));
+    return istvt_check_launch();
+}
+
+// conv1 forward from bytes: x uint8 [frames][S][S][3], mean / std float [3], w as above -> the same u1
+extern "C" int istvt_conv1_fwd_u8(const void* x, const float* mean, const float* stdv, const float* w, void* u1, int Fr,
+                                  int S, int dtype, hipStream_t stream) {
+    if (Fr <= 0 || S < 3 || S > 4096 || !x || !mean || !stdv) return ISTVT_ERR_SHAPE;
+    const int Ho = (S - 3) / 2 + 1;
+    // R output rows per workgroup (2R + 1 staged input rows, at most 48 KiB; one always fits: 3 * 4096 * 3 bytes): of
+    // 4..16, the one that wastes the fewest lanes of the 256-thread passes over its R * Ho outputs
+    int R = 1;
+    double best = 0.0;
+    for (int r = 1; r <= 16 && r <= Ho; ++r) {
+        if ((2L * r + 1) * S * 3 > 48 * 1024) break;
+        const double eff = r < 4 ? 0.0 : (double)(r * Ho) / (double)(((r * Ho + 255) / 256) * 256);
+        if (r < 4 || eff > best + 1e-9) best = eff, R = r;
+    }
+    const int ngroups = (Ho + R - 1) / R;
+    const long nblocks = (long)Fr * ngroups;
+    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const long total = (long)Fr * S * S * 3;
+    const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * S * 3 + 32;
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_u8<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
+                                             (const uint8_t*)x, mean, stdv, w, (T*)u1, total, S, Ho, R, ngroups));
     return istvt_check_launch();
 }
 

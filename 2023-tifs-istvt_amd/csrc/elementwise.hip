@@ -143,6 +143,47 @@ __global__ __launch_bounds__(128) void tokens_fwd_kernel(const T* __restrict__ f
     }
 }
 
+// The same assembly for sliding windows over one video (inference): the frames of window w are slots of a per-frame
+// feature bank [cap][hw][D], named by idx [W][T]; windows that overlap share bank slots instead of being copied out as
+// clips.  Element for element the arithmetic of tokens_fwd_kernel (one float add, one rounding), so on windows
+// materialised as clips the two agree bit for bit.  A slot outside [0, cap) -- the host validates the table -- reads
+// nothing and contributes zero.
+template <typename T>
+__global__ __launch_bounds__(128) void tokens_gather_fwd_kernel(const T* __restrict__ bank, const int* __restrict__ idx,
+                                                                const float* __restrict__ space,
+                                                                const float* __restrict__ temporal,
+                                                                const float* __restrict__ pos, T* __restrict__ x, int W,
+                                                                int F, int P, int D, int pos_rows, int cap, long ldx) {
+    const long row = blockIdx.x;                 // over W*F*P
+    const int p = (int)(row % P);
+    const int f = (int)((row / P) % F);
+    const long w = row / ((long)P * F);
+    const int hw = P - 1, Tn = F - 1;
+    for (int e = threadIdx.x * 8; e < D; e += 128 * 8) {
+        float o[8];
+        if (f == 0) {
+            load8(temporal + e, o);
+        } else {
+            float pe[8];
+            load8(pos + ((long)(f - 1) * pos_rows + p) * D + e, pe);
+            if (p == 0) {
+                load8(space + e, o);
+            } else {
+                const int slot = idx[w * Tn + (f - 1)];
+                if (slot >= 0 && slot < cap) {
+                    load8(bank + (((long)slot * hw) + (p - 1)) * D + e, o);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) o[i] = 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o[i] += pe[i];
+        }
+        store8(x + row * ldx + e, o);
+    }
+}
+
 // backward of the assembly.  grid (P, F); loops over b.
 //   dfeats[b,t,i] = dx[b,1+t,1+i];  dpos[t][p] += sum_b dx[b,1+t,p];
 //   dspace += sum_{b,t} dx[b,1+t,0];  dtemporal += sum_{b,p} dx[b,0,p]   (per-block partial rows + the fixed-order reduce)
@@ -184,6 +225,18 @@ extern "C" int istvt_tokens_fwd(const void* feats, const float* space, const flo
     dim3 grid((unsigned)((long)B * F * P)), block(128);
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((tokens_fwd_kernel<T>), grid, block, 0, stream, (const T*)feats, space,
                                              temporal, pos, (T*)x, B, F, P, D, pos_rows, ldx));
+    return istvt_check_launch();
+}
+
+extern "C" int istvt_tokens_gather_fwd(const void* bank, const int* idx, const float* space, const float* temporal,
+                                       const float* pos, void* x, long ldx, int W, int F, int P, int D, int pos_rows,
+                                       int cap, int dtype, hipStream_t stream) {
+    if (W <= 0 || F < 2 || P < 2 || D % 8 != 0 || pos_rows < P || ldx < D || ldx % 8 || cap <= 0 || !idx)
+        return ISTVT_ERR_SHAPE;
+    if ((long)W * F * P > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    dim3 grid((unsigned)((long)W * F * P)), block(128);
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((tokens_gather_fwd_kernel<T>), grid, block, 0, stream, (const T*)bank, idx,
+                                             space, temporal, pos, (T*)x, W, F, P, D, pos_rows, cap, ldx));
     return istvt_check_launch();
 }
 

@@ -204,6 +204,12 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import explain
         return explain.relevance(self, x, index)
 
+    def score_video(self, frames, **kw):
+        """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S):
+        istvt_amd.video.VideoScorer(self, **kw).score(frames)"""
+        from istvt_amd import video
+        return video.VideoScorer(self, **kw).score(frames)
+
     def _forward_eager(self, x):
         b, t = x.shape[:2]
         feats = self.xcep.model.low_level_features_nhwc(x.flatten(0, 1), self.compute_dtype)   # (b*t, h, w, c)

@@ -140,9 +140,11 @@ class Xception(nn.Module):
         self.fc = nn.Linear(2048, num_classes)
         self.compute_dtype = torch.float32
 
-    def low_level_features_nhwc(self, input, dtype=None):
-        """(n,3,S,S) float32 -> (n,h,w,728) channels-last features in the compute dtype."""
-        return _stem.stem_forward(input, self, dtype or self.compute_dtype)
+    def low_level_features_nhwc(self, input, dtype=None, mean=None, std=None, inference=False):
+        """(n,3,S,S) float32 -> (n,h,w,728) channels-last features in the compute dtype.  Inference entry (eval mode under
+        torch.no_grad() only): decoded frames, uint8 (n,S,S,3), with the per-channel mean / std that conv1 normalises
+        them by; inference=True sends float input through the same entry (stem.stem_forward)."""
+        return _stem.stem_forward(input, self, dtype or self.compute_dtype, mean, std, inference)
 
     def low_level_features(self, input):
         """Reference signature (xception.py:193-206): (n,3,S,S) -> (n,728,h,w)."""

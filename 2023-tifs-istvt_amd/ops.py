@@ -1052,6 +1052,73 @@ def tokens_fwd(feats: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad:
     return x.view(B, F * P, D)
 
 
+def tokens_gather_fwd(bank: Tensor, idx: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad: bool = False) -> Tensor:
+    """Token assembly for sliding windows: bank [cap,hw,D] per-frame features, idx int32 [W,T] bank slots of every window's
+    frames -> x [W,(T+1)*(hw+1),D], bit-identical to tokens_fwd(bank[idx]).  The table is validated here, on the host: pass
+    it as a host tensor (it is uploaded on the current stream); a device table costs one synchronisation to check."""
+    bank = _c(_req(bank, 'feature bank'))
+    if bank.dim() != 3:
+        raise RuntimeError('tokens_gather_fwd: bank must be (cap, h*w, D), got %s' % (tuple(bank.shape),))
+    if idx.dim() != 2 or idx.dtype != torch.int32:
+        raise RuntimeError('tokens_gather_fwd: idx must be an int32 (windows, frames) table, got %s %s'
+                           % (idx.dtype, tuple(idx.shape)))
+    cap, hw, D = bank.shape
+    W, T = idx.shape
+    if W == 0:
+        raise RuntimeError('tokens_gather_fwd: no windows')
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= cap:
+        raise IndexError('tokens_gather_fwd: slots span [%d, %d], the bank has %d' % (lo, hi, cap))
+    idx = _c(idx)
+    if not idx.is_cuda:
+        idx = idx.to(bank.device, non_blocking=True)
+    elif idx.device != bank.device:
+        raise RuntimeError('tokens_gather_fwd: idx is on %s, the bank on %s' % (idx.device, bank.device))
+    F, P = T + 1, hw + 1
+    if pos.shape[1] != T:
+        raise RuntimeError('The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension 1'
+                           % (T, pos.shape[1]))          # as tokens_fwd
+    if pos.shape[2] < P:
+        raise RuntimeError('pos_embedding has %d tokens per frame, input needs %d' % (pos.shape[2], P))
+    if pos.shape[-1] != D or space.shape[-1] != D or temporal.shape[-1] != D:
+        raise RuntimeError('tokens_gather_fwd: bank has %d channels, the tokens %d' % (D, pos.shape[-1]))
+    x = empty_rows(W * F * P, D, bank.dtype, bank.device, pad)
+    with prof('tokens_gather_fwd', (W * T * hw + W * F * P) * D * bank.element_size() + W * T * 4):
+        _lib.check(_lib.lib().istvt_tokens_gather_fwd(bank.data_ptr(), idx.data_ptr(), space.data_ptr(), temporal.data_ptr(),
+                                                      pos.data_ptr(), x.data_ptr(), x.stride(0), W, F, P, D, pos.shape[2],
+                                                      cap, dtype_code(bank), _stream()), 'istvt_tokens_gather_fwd')
+    return x.view(W, F * P, D)
+
+
+def conv1_fwd_u8(frames: Tensor, mean: Tensor, std: Tensor, weight: Tensor, dtype: torch.dtype) -> Tensor:
+    """conv1 of the Xception stem straight from decoded frames: frames uint8 [Fr,S,S,3] (channels last), mean / std float32
+    [3] on the device, weight conv1.weight (32,3,3,3) float32 -> u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to
+    istvt_conv1_fwd on ((frames.float() / 255 - mean) / std).permute(0, 3, 1, 2).  Inference only (no weight gradient)."""
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('conv1_fwd_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[1] != frames.shape[2]:
+        raise RuntimeError('conv1_fwd_u8 expects channels-last (frames, S, S, 3) uint8 input, got %s' % (tuple(frames.shape),))
+    if dtype not in _DT:
+        raise TypeError('istvt_amd supports float32 and bfloat16 activations, got %s' % dtype)
+    for t, n in ((mean, 'mean'), (std, 'std')):
+        if t.dtype != torch.float32 or t.numel() != 3 or t.device != frames.device:
+            raise RuntimeError('conv1_fwd_u8: %s must be 3 float32 values on %s' % (n, frames.device))
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (32, 3, 3, 3) or weight.device != frames.device:
+        raise RuntimeError('conv1_fwd_u8: weight must be conv1.weight, float32 (32, 3, 3, 3) on %s' % frames.device)
+    frames = _c(frames)
+    Fr, S = frames.shape[0], frames.shape[1]
+    if Fr == 0 or S < 3:
+        raise RuntimeError('conv1_fwd_u8: empty input %s' % (tuple(frames.shape),))
+    Ho = (S - 3) // 2 + 1
+    u1 = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=frames.device)
+    with prof('conv1_fwd_u8', Fr * S * S * 3 + u1.numel() * u1.element_size(), 2.0 * 27 * u1.numel()):
+        _lib.check(_lib.lib().istvt_conv1_fwd_u8(frames.data_ptr(), _c(mean).data_ptr(), _c(std).data_ptr(),
+                                                 _c(weight.detach()).data_ptr(), u1.data_ptr(), Fr, S, _DT[dtype], _stream()),
+                   'istvt_conv1_fwd_u8')
+    return u1
+
+
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,
                need_dfeats: bool) -> Optional[Tensor]:
     dx, lddx = rows(_req(dx))

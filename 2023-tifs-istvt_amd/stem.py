@@ -248,17 +248,35 @@ def bn_names() -> List[str]:
 class StemFn(Function):
     """y = Xception.low_level_features(x).  x: (Fr,3,S,S) float32 NCHW; y: (Fr,h,w,728) NHWC in
     `dtype`.  `buffers` = [running_mean, running_var] * 11 in bn_names() order (updated in place
-    when training)."""
+    when training).  `infer`: None, or the inference entry's (mean, std): x is then either decoded
+    frames, uint8 (Fr,S,S,3) normalised inside conv1 with the float32 [3] device tensors mean / std,
+    or the float clip with (None, None); conv1 runs as the direct kernel in both compute dtypes (so
+    the two kinds of input agree bit for bit) and there is no backward."""
 
     @staticmethod
-    def forward(ctx, x, dtype, training, buffers, *params):
+    def forward(ctx, x, dtype, training, buffers, infer, *params):
         _req(x, 'input clip')
-        if x.dtype != torch.float32:
-            raise TypeError('stem input must be float32, got %s' % x.dtype)
-        x = _c(x)
-        Fr, cin, S, S2 = x.shape
-        if cin != 3 or S != S2:
-            raise RuntimeError('stem expects (frames, 3, S, S) input, got %s' % (tuple(x.shape),))
+        if infer is not None and training:          # (stem_forward also refuses it with gradients enabled)
+            raise RuntimeError('the stem\'s inference entry needs eval mode: it has no backward')
+        u8 = x.dtype == torch.uint8
+        if u8:
+            if infer is None or infer[0] is None:
+                raise RuntimeError('uint8 frames need mean and std (Xception.low_level_features_nhwc(x, dtype, mean, std))')
+            if x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
+                raise RuntimeError('stem expects channels-last (frames, S, S, 3) uint8 input, got %s' % (tuple(x.shape),))
+            x = _c(x)
+            Fr, S = x.shape[0], x.shape[1]
+        else:
+            if x.dtype != torch.float32:
+                raise TypeError('stem input must be float32, got %s' % x.dtype)
+            if infer is not None and infer[0] is not None:
+                raise RuntimeError('mean / std apply to uint8 frames; float input is taken as already normalised')
+            if x.dim() != 4:
+                raise RuntimeError('stem expects (frames, 3, S, S) input, got %s' % (tuple(x.shape),))
+            x = _c(x)
+            Fr, cin, S, S2 = x.shape
+            if cin != 3 or S != S2:
+                raise RuntimeError('stem expects (frames, 3, S, S) input, got %s' % (tuple(x.shape),))
         L = _lib.lib()
         dev = x.device
         P = dict(zip(param_names(), params))
@@ -278,7 +296,9 @@ class StemFn(Function):
         M1 = Fr * H1 * H1
         # conv1 directly from the fp32 NCHW clip (one thread per output pixel); w1 is the GEMM form for the backward
         w1 = _conv1_weight(P['conv1.weight'], dtype)
-        if dtype == torch.bfloat16:
+        if u8:
+            u1 = ops.conv1_fwd_u8(x, infer[0], infer[1], P['conv1.weight'], dtype)
+        elif dtype == torch.bfloat16 or infer is not None:
             u1 = torch.empty((M1, 32), dtype=dtype, device=dev)
             _lib.check(L.istvt_conv1_fwd(x.data_ptr(), P['conv1.weight'].detach().contiguous().data_ptr(), u1.data_ptr(),
                                          Fr, S, ops._DT[dtype], _stream()), 'istvt_conv1_fwd')
@@ -527,11 +547,40 @@ class StemFn(Function):
                 q.grad.add_(grads[n].view(q.shape))
                 grads[n] = None
         out = [None if grads[n] is None else grads[n].view(P[n].shape) for n in param_names()]
-        return (dx, None, None, None, *out)
+        return (dx, None, None, None, None, *out)
 
 
-def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype) -> Tensor:
-    """Run the HIP stem with the parameters/buffers of an ``Xception`` module (network/xception.py)."""
+def _norm_vec(v, name: str, device) -> Tensor:
+    """mean / std of the byte entry as 3 float32 values on the device (a device tensor passes through: no copy per call)"""
+    if isinstance(v, Tensor) and v.device == device and v.dtype == torch.float32 and v.numel() == 3:
+        return v.reshape(3)
+    t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+    if t.numel() != 3:
+        raise ValueError('%s must have 3 values (one per channel), got %d' % (name, t.numel()))
+    if name == 'std' and bool((t == 0).any()):
+        raise ValueError('std must be non-zero')
+    return t.to(device)
+
+
+def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None, std=None, inference: bool = False) -> Tensor:
+    """Run the HIP stem with the parameters/buffers of an ``Xception`` module (network/xception.py).
+
+    x float32 (frames, 3, S, S): the training / evaluation path.  x uint8 (frames, S, S, 3) with mean and std (3 values
+    each): the inference entry, conv1 normalises the bytes itself (istvt_conv1_fwd_u8); it needs eval mode and
+    torch.no_grad().  inference=True puts float input through the same entry (the direct conv1 kernel in either compute
+    dtype), which is what makes byte and float input of one video agree bit for bit (video.VideoScorer)."""
+    infer = None
+    if x.dtype == torch.uint8:
+        if mean is None or std is None:
+            raise RuntimeError('uint8 frames need mean and std (3 values each)')
+        infer = (_norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device))
+    elif mean is not None or std is not None:
+        raise RuntimeError('mean / std apply to uint8 frames; float input is taken as already normalised')
+    elif inference:
+        infer = (None, None)
+    if infer is not None and (xcep.training or torch.is_grad_enabled()):
+        raise RuntimeError('the stem\'s inference entry (uint8 frames / VideoScorer) needs eval mode and torch.no_grad(): '
+                           'it has no backward (no conv1 weight gradient from bytes)')
     # The tensors are looked up through their owning submodules every call (a load_state_dict / .to() may have replaced
     # them): the owners are cached on the module and re-validated by identity (get_submodule per distinct owner), the
     # parameters / buffers then come straight out of the owners' dicts.  get_parameter / get_buffer by dotted name, 55 per
@@ -553,7 +602,7 @@ def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype) -> Tensor
     if x.is_cuda:
         stats_arena_reset(x.device)          # one fill for every statistics accumulator of this step
         ops.refresh_stale_operands()         # one grouped cast for every bf16 weight operand the optimizer invalidated
-    y = StemFn.apply(x, dtype, xcep.training, buffers, *params)
+    y = StemFn.apply(x, dtype, xcep.training, buffers, infer, *params)
     if xcep.training:
         torch._foreach_add_([owner._buffers['num_batches_tracked'] for owner in refs[2]], 1)     # one launch, not 11
     return y

@@ -1,0 +1,314 @@
+"""Scoring whole videos (DESIGN.md "Video scoring"): decoded frames in, one logit per sliding window and one score per
+video out.
+
+    scorer = VideoScorer(model, stride=1)
+    res = scorer.score(frames)                       # uint8 (N, S, S, 3), host or device; or float32 (N, 3, S, S)
+    scorer.reset()
+    for chunk in stream:                             # the same windows, as the frames arrive
+        logits, starts = scorer.push(chunk)
+    logits, starts = scorer.flush()                  # the window that covers the tail, if one is due
+
+What `model(clips)` would pay for this and the scorer does not: the Xception stem runs once per frame instead of once per
+(window, frame) -- in eval mode a frame's feature map does not depend on the clip around it --, conv1 reads the decoder's
+bytes (istvt_conv1_fwd_u8) instead of a host-normalised float32 copy four times the size, and overlapping windows are
+never copied out as clips: the per-frame features sit in a device ring and istvt_tokens_gather_fwd assembles each
+window's tokens from its slots.
+
+The schedule (which frames go through the stem when, which windows run when, which ring slot holds which frame) is host
+logic with no tensor in it: RingPlan, testable without a device.
+"""
+from __future__ import annotations
+
+import contextlib
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from . import ops
+
+Tensor = torch.Tensor
+# the reference's preprocessing (network/xception.py:12 of the reference: Normalize([0.5] * 3, [0.5] * 3))
+DEFAULT_MEAN = (0.5, 0.5, 0.5)
+DEFAULT_STD = (0.5, 0.5, 0.5)
+
+
+def window_starts(n: int, T: int, stride: int = 1, cover_tail: bool = True) -> List[int]:
+    """First frames of the T-frame windows over an n-frame video: 0, stride, 2 stride, ... while the window fits, and with
+    cover_tail one more at n - T when the last of those does not end at the last frame."""
+    if T < 1 or stride < 1:
+        raise ValueError('window_starts: T and stride must be positive, got T=%d stride=%d' % (T, stride))
+    if n < T:
+        raise ValueError('a video of %d frames is shorter than one window of %d' % (n, T))
+    starts = list(range(0, n - T + 1, stride))
+    if cover_tail and starts[-1] != n - T:
+        starts.append(n - T)
+    return starts
+
+
+def check_frames(frames) -> str:
+    """'u8' for decoded frames uint8 (N, S, S, 3), 'f32' for normalised float32 (N, 3, S, S); ValueError otherwise."""
+    if not torch.is_tensor(frames):
+        raise ValueError('frames must be a torch tensor, got %s' % type(frames).__name__)
+    if frames.dim() != 4:
+        raise ValueError('frames must be uint8 (N, S, S, 3) or float32 (N, 3, S, S), got rank %d: %s'
+                         % (frames.dim(), tuple(frames.shape)))
+    if frames.dtype == torch.uint8:
+        if frames.shape[3] != 3 or frames.shape[1] != frames.shape[2]:
+            raise ValueError('uint8 frames must be channels-last (N, S, S, 3) as a decoder delivers them, got %s'
+                             % (tuple(frames.shape),))
+        return 'u8'
+    if frames.dtype == torch.float32:
+        if frames.shape[1] != 3 or frames.shape[2] != frames.shape[3]:
+            raise ValueError('float frames must be normalised (N, 3, S, S), got %s' % (tuple(frames.shape),))
+        return 'f32'
+    raise ValueError('frames must be uint8 or float32, got %s' % frames.dtype)
+
+
+class Step(NamedTuple):
+    """One unit of work of a RingPlan.  kind 'frames': frames [first, first + count) go through the stem into ring slots
+    `slots` (one per frame).  kind 'windows': the windows starting at `starts` run; idx[w][t] is the slot of frame
+    starts[w] + t."""
+    kind: str
+    first: int
+    count: int
+    slots: Tuple[int, ...]
+    starts: Tuple[int, ...]
+    idx: Optional[Tensor]
+
+
+class RingPlan:
+    """The order of work for a stream of frames whose features live in a ring of `capacity` slots (frame i in slot
+    i mod capacity).  push(k) plans k more frames, flush() the tail window.  Frames go through the stem at most
+    frame_batch at a time, windows run window_batch at a time as they complete, and every window completed by the frames
+    of a push has run when the push returns.
+
+    The invariant: a slot is overwritten only when no window that is pending or still to come, the tail window of a later
+    flush() included, reads the frame in it.  Everything still to come reads only the last T frames, so a batch of k new
+    frames -- which overwrites frames up to seen + k - 1 - capacity -- is cut to k <= capacity - T (no cut while the ring
+    has never been full), and windows that are complete but still queued for a full batch run first when they read a
+    slot the batch is about to take."""
+
+    def __init__(self, T: int, stride: int, capacity: int, frame_batch: int, window_batch: int):
+        if T < 1 or stride < 1 or frame_batch < 1 or window_batch < 1:
+            raise ValueError('RingPlan: T, stride, frame_batch and window_batch must be positive')
+        if capacity < T:
+            raise ValueError('a ring of %d frames cannot hold one window of %d' % (capacity, T))
+        self.T, self.stride, self.capacity = T, stride, capacity
+        self.frame_batch, self.window_batch = frame_batch, window_batch
+        self.seen = 0                      # frames planned so far (absolute index of the next one)
+        self.next_start = 0                # first regular window that is not complete yet
+        self.last_start = -1               # start of the last window planned
+        self.pending: List[int] = []       # complete, not yet planned into a 'windows' step
+        self.flushed = False
+
+    def _windows(self, steps: List[Step], count: int):
+        starts, self.pending = self.pending[:count], self.pending[count:]
+        idx = torch.tensor([[(s + t) % self.capacity for t in range(self.T)] for s in starts], dtype=torch.int32)
+        steps.append(Step('windows', starts[0], len(starts), (), tuple(starts), idx))
+        self.last_start = starts[-1]
+
+    def _drain(self, steps: List[Step]):
+        while self.pending:
+            self._windows(steps, min(len(self.pending), self.window_batch))
+
+    def push(self, k: int, drain: bool = True) -> List[Step]:
+        """drain=False leaves the last, partial batch of complete windows queued (for a flush() that follows at once)."""
+        if self.flushed:
+            raise RuntimeError('this stream has been flushed: reset() starts a new one')
+        steps: List[Step] = []
+        C, T = self.capacity, self.T
+        while k > 0:
+            room = max(C - self.seen, C - T)
+            if room < 1:
+                raise ValueError('a ring of %d frames holds one window of %d and nothing more: streaming needs capacity > T'
+                                 % (C, T))
+            kb = min(k, self.frame_batch, room)
+            if self.pending and self.pending[0] <= self.seen + kb - 1 - C:
+                self._drain(steps)         # they read slots this batch overwrites
+            steps.append(Step('frames', self.seen, kb, tuple((self.seen + i) % C for i in range(kb)), (), None))
+            self.seen += kb
+            k -= kb
+            while self.next_start + T <= self.seen:
+                self.pending.append(self.next_start)
+                self.next_start += self.stride
+            while len(self.pending) >= self.window_batch:
+                self._windows(steps, self.window_batch)
+        if drain:
+            self._drain(steps)
+        return steps
+
+    def flush(self, cover_tail: bool = True) -> List[Step]:
+        """The end of the stream: the window at seen - T when cover_tail asks for it and no window ends at the last frame."""
+        if self.flushed:
+            return []
+        if self.seen < self.T:
+            raise ValueError('a video of %d frames is shorter than one window of %d' % (self.seen, self.T))
+        self.flushed = True
+        steps: List[Step] = []
+        last = self.pending[-1] if self.pending else self.last_start
+        if cover_tail and last != self.seen - self.T:
+            self.pending.append(self.seen - self.T)
+        self._drain(steps)
+        return steps
+
+
+class VideoScore(NamedTuple):
+    """Result of VideoScorer.score: device tensors, complete when score() returns."""
+    window_logits: Tensor      # (W, num_classes) float32
+    starts: Tensor             # (W,) int64: first frame of every window
+    logit_mean: Tensor         # (num_classes,) mean of the window logits
+    prob_mean: Tensor          # (num_classes,) mean of the windows' sigmoids
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """eval mode for the call; every module's own train / eval flag comes back afterwards (as explain.relevance does)"""
+    on = [m for m in model.modules() if m.training]         # one walk; a model already in eval mode costs nothing more
+    try:
+        for m in on:
+            m.training = False
+        yield
+    finally:
+        for m in on:
+            m.training = True
+
+
+class VideoScorer:
+    """Sliding-window scores of an XceptionVidTr over decoded video frames.
+
+    model         the XceptionVidTr; its compute_dtype, attn_fp8 and dead_row_elimination settings are used as they are.
+                  It is put in eval mode for each call and handed back with its train / eval flags as they were; running
+                  statistics and num_batches_tracked are not touched.
+    stride        frames between window starts.
+    frame_batch   frames per stem pass.        window_batch   windows per transformer pass.
+    capacity      frames of features the device ring holds (default: the whole video for score(), T + frame_batch
+                  rounded up to a multiple of 8 for push()).
+    mean, std     per-channel normalisation of uint8 frames, (u / 255 - mean) / std; float input is taken as normalised.
+    cover_tail    score() / flush() add the window at N - T when the strided windows leave the last frames uncovered.
+    """
+
+    def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
+                 capacity: Optional[int] = None, mean: Sequence[float] = DEFAULT_MEAN, std: Sequence[float] = DEFAULT_STD,
+                 cover_tail: bool = True):
+        vit = getattr(model, 'vit', None)
+        if vit is None or not hasattr(model, 'xcep') or not hasattr(vit, 'forward_tokens'):
+            raise TypeError('VideoScorer: expected an XceptionVidTr, got %s' % type(model).__name__)
+        if stride < 1 or frame_batch < 1 or window_batch < 1:
+            raise ValueError('VideoScorer: stride, frame_batch and window_batch must be positive')
+        self.model = model
+        self.T = int(vit.pos_embedding.shape[1])
+        if capacity is not None and capacity <= self.T:
+            raise ValueError('VideoScorer: capacity %d must exceed the window length %d' % (capacity, self.T))
+        if len(mean) != 3 or len(std) != 3 or any(float(s) == 0.0 for s in std):
+            raise ValueError('VideoScorer: mean and std take 3 values each, std non-zero')
+        self.stride, self.frame_batch, self.window_batch = int(stride), int(frame_batch), int(window_batch)
+        self.capacity = capacity
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.cover_tail = bool(cover_tail)
+        self._norm = None                  # (device, mean tensor, std tensor)
+        self.reset()
+
+    # ---------------------------------------------------------------------------------------- streaming state
+    def reset(self):
+        """Forget the stream: the next push() is frame 0 of a new video."""
+        self._plan: Optional[RingPlan] = None
+        self._ring: Optional[Tensor] = None
+        self._kind: Optional[str] = None
+        return self
+
+    def _device(self):
+        dev = next(self.model.parameters()).device
+        if dev.type != 'cuda':
+            raise RuntimeError('VideoScorer: the model must be on a ROCm device (no CPU fallback exists for the ISTVT hot path)')
+        return dev
+
+    def _stem(self, x: Tensor, kind: str, dev) -> Tensor:
+        if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
+            x = x.contiguous().pin_memory().to(dev, non_blocking=True)
+        xcep = self.model.xcep.model
+        if kind == 'u8':
+            if self._norm is None or self._norm[0] != dev:
+                self._norm = (dev, torch.tensor(self.mean, dtype=torch.float32, device=dev),
+                              torch.tensor(self.std, dtype=torch.float32, device=dev))
+            feats = xcep.low_level_features_nhwc(x, self.model.compute_dtype, self._norm[1], self._norm[2])
+        else:
+            feats = xcep.low_level_features_nhwc(x, self.model.compute_dtype, inference=True)
+        n, h, w, c = feats.shape
+        return feats.view(n, h * w, c)
+
+    def _store(self, feats: Tensor, slots: Tuple[int, ...]):
+        C = self._ring.shape[0]
+        k, s0 = len(slots), slots[0]
+        head = min(k, C - s0)              # slots are consecutive modulo the capacity: at most two pieces
+        self._ring[s0:s0 + head].copy_(feats[:head])
+        if head < k:
+            self._ring[:k - head].copy_(feats[head:])
+
+    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev):
+        """-> (logits (W, num_classes) float32 on the device, list of starts) of the windows the steps ran"""
+        vit = self.model.vit
+        outs, starts = [], []
+        with _eval_mode(self.model), torch.no_grad():
+            for st in steps:
+                if st.kind == 'frames':
+                    feats = self._stem(frames[st.first - base:st.first - base + st.count], kind, dev)
+                    if self._ring is None:
+                        self._ring = torch.empty((self._plan.capacity,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
+                    elif tuple(self._ring.shape[1:]) != tuple(feats.shape[1:]) or self._ring.dtype != feats.dtype:
+                        raise RuntimeError('VideoScorer: the frames of one stream must share one size and compute dtype '
+                                           '(reset() starts a new stream)')
+                    self._store(feats, st.slots)
+                else:
+                    hw = self._ring.shape[1]
+                    x = ops.tokens_gather_fwd(self._ring, st.idx, vit.space_token, vit.temporal_token, vit.pos_embedding,
+                                              pad=True)
+                    outs.append(vit.forward_tokens(x, st.count, self.T + 1, hw + 1))
+                    starts.extend(st.starts)
+        nc = vit.mlp_head[1].out_features
+        logits = torch.cat(outs) if outs else torch.empty((0, nc), dtype=torch.float32, device=dev)
+        return logits, starts
+
+    def push(self, frames: Tensor):
+        """The next frames of the stream -> (logits (W, num_classes) float32 on the device, starts (W,) int64 on the host)
+        of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation."""
+        kind = check_frames(frames)
+        if self._kind is not None and kind != self._kind:
+            raise ValueError('VideoScorer: a stream is either uint8 or float frames, not both (reset() starts a new one)')
+        dev = self._device()
+        if self._plan is None:
+            cap = self.capacity if self.capacity is not None else -(-(self.T + self.frame_batch) // 8) * 8
+            self._plan = RingPlan(self.T, self.stride, cap, self.frame_batch, self.window_batch)
+        self._kind = kind
+        base = self._plan.seen
+        logits, starts = self._run(self._plan.push(int(frames.shape[0])), frames, base, kind, dev)
+        return logits, torch.tensor(starts, dtype=torch.int64)
+
+    def flush(self):
+        """End of the stream -> (logits, starts) of the tail window (empty when none is due).  ValueError if the stream
+        was shorter than one window."""
+        if self._plan is None:
+            raise ValueError('a video of 0 frames is shorter than one window of %d' % self.T)
+        logits, starts = self._run(self._plan.flush(self.cover_tail), None, 0, None, self._device())
+        return logits, torch.tensor(starts, dtype=torch.int64)
+
+    # ---------------------------------------------------------------------------------------- whole video
+    def score(self, frames: Tensor) -> VideoScore:
+        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own)."""
+        kind = check_frames(frames)
+        n = int(frames.shape[0])
+        if n < self.T:
+            raise ValueError('a video of %d frames is shorter than one window of %d' % (n, self.T))
+        dev = self._device()
+        saved = (self._plan, self._ring, self._kind)
+        try:
+            self._plan = RingPlan(self.T, self.stride, self.capacity if self.capacity is not None else n,
+                                  self.frame_batch, self.window_batch)
+            self._ring = None
+            steps = self._plan.push(n, drain=False) + self._plan.flush(self.cover_tail)
+            logits, starts = self._run(steps, frames, 0, kind, dev)
+        finally:
+            self._plan, self._ring, self._kind = saved
+        res = VideoScore(logits, torch.tensor(starts, dtype=torch.int64).to(dev, non_blocking=True), logits.mean(0),
+                         torch.sigmoid(logits).mean(0))
+        torch.cuda.current_stream(dev).synchronize()
+        return res

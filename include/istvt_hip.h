@@ -177,6 +177,12 @@ int istvt_relevance_heatmap(const float* cam, float* out, int maps, int g, int s
 /* ---- token assembly (DSTTr.forward, vivit.py:133-142) -------------------------------------- */
 int istvt_tokens_fwd(const void* feats, const float* space, const float* temporal, const float* pos, void* x, long ldx,
                      int B, int F, int P, int D, int pos_rows, int dtype, istvt_stream_t stream);
+/* The same assembly for W sliding windows over one video (inference, forward only): bank [cap][P-1][D] (dtype) holds one
+ * feature map per frame, idx int32 [W][F-1] names the bank slot of every frame of every window (0 <= idx < cap, validated by
+ * the caller; a slot outside the bank contributes zero).  Bit-identical to istvt_tokens_fwd on the windows copied out. */
+int istvt_tokens_gather_fwd(const void* bank, const int* idx, const float* space, const float* temporal, const float* pos,
+                            void* x, long ldx, int W, int F, int P, int D, int pos_rows, int cap, int dtype,
+                            istvt_stream_t stream);
 /* dspace / dtemporal / dpos accumulate; ws = float scratch of (P + F - 1) * D elements (per-workgroup partial rows of the
  * two token gradients, folded in a fixed order: no floating-point atomics) */
 int istvt_tokens_bwd(const void* dx, long lddx, void* dfeats, float* dspace, float* dtemporal, float* dpos, float* ws,
@@ -236,6 +242,12 @@ int istvt_col2im3x3(const void* dcol, const void* u, const float* bnp, void* dz,
  * relu'(bn1(u1)); wgrad: dw float [64][(dy,dx,ci)] += sum over pixels, slabs = caller-owned float workspace of
  * istvt_conv2_wgrad_slabs() * 64 * 288 elements. */
 int istvt_conv1_fwd(const float* x, const float* w, void* u1, int frames, int S, int dtype, istvt_stream_t stream);
+/* conv1 forward from decoded frames (inference, no weight gradient): x uint8 [frames][S][S][3], mean / std float [3];
+ * every byte is normalised as v = (float(u) / 255 - mean[c]) / std[c], each operation rounded on its own, and the sums run in
+ * istvt_conv1_fwd's order: u1 is bit-identical to istvt_conv1_fwd on the float tensor torch makes from the same bytes.
+ * S <= 4096. */
+int istvt_conv1_fwd_u8(const void* x, const float* mean, const float* std, const float* w, void* u1, int frames, int S,
+                       int dtype, istvt_stream_t stream);
 /* conv1 weight gradient: du1 [frames*Ho*Wo][32] (dtype; rounded to bf16 for the MFMA), x as above ->
  * dw float [32][32] +=, column k = ci*9 + dy*3 + dx (conv1.weight's own order; columns 27..31 unused);
  * slabs = caller-owned float workspace of istvt_conv1_wgrad_slabs() * 1024 elements.  Ho <= 128. */

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""Video scoring (DESIGN.md "Video scoring") against the clip path it replaces, on one GPU in one process.
+
+    python tools/video_bench.py [--frames 256] [--size 224] [--T 8] [--depth 12] [--strides 1,2,4,8] [--json out.json]
+    python tools/video_bench.py --conv1-only        # the two conv1 kernels alone, for a kernel trace
+
+(a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
+float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
+code path that exists without the scorer (its host-side normalisation and 4x larger upload are NOT charged to it).
+Each repeat times (a) then (b), the device synchronised on both sides of each; the figures are medians over the repeats
+after the warm-up, with the min-max spread of both.  The split of (a) into stem / token assembly / transformer comes from
+ops.prof events in one further, instrumented run.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+import istvt_pkg  # noqa: E402
+
+istvt_pkg.load()
+from istvt_amd import _lib, ops, video  # noqa: E402
+from istvt_amd.network.vivit.vivit import XceptionVidTr  # noqa: E402
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3              # ms
+
+
+def stats(ts):
+    s = sorted(ts)
+    return {'median_ms': s[len(s) // 2], 'min_ms': s[0], 'max_ms': s[-1]}
+
+
+def conv1_only(a):
+    """both conv1 kernels on the same frames, `reps` launches each (run under a kernel trace)"""
+    g = torch.Generator().manual_seed(0)
+    u8 = torch.randint(0, 256, (a.frames, a.size, a.size, 3), generator=g, dtype=torch.uint8).cuda()
+    mean, std = torch.tensor(video.DEFAULT_MEAN).cuda(), torch.tensor(video.DEFAULT_STD).cuda()
+    x = (((u8.float() / 255) - mean) / std).permute(0, 3, 1, 2).contiguous()
+    w = torch.randn((32, 3, 3, 3), generator=g).cuda()
+    Ho = (a.size - 3) // 2 + 1
+    ref = torch.empty((a.frames * Ho * Ho, 32), dtype=torch.bfloat16, device='cuda')
+    for _ in range(a.reps + a.warmup):
+        out = ops.conv1_fwd_u8(u8, mean, std, w, torch.bfloat16)
+        _lib.check(_lib.lib().istvt_conv1_fwd(x.data_ptr(), w.data_ptr(), ref.data_ptr(), a.frames, a.size, 1, ops._stream()),
+                   'istvt_conv1_fwd')
+    torch.cuda.synchronize()
+    # (x was normalised on the device here, where torch divides by multiplying with a reciprocal: close, not equal bits)
+    print('conv1_only: %d launches each, max abs diff %.3e' % (a.reps + a.warmup, float((out.float() - ref.float()).abs().max())))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=256)
+    ap.add_argument('--size', type=int, default=224)
+    ap.add_argument('--T', type=int, default=8)
+    ap.add_argument('--depth', type=int, default=12)
+    ap.add_argument('--strides', default='1,2,4,8')
+    ap.add_argument('--frame-batch', type=int, default=64)
+    ap.add_argument('--window-batch', type=int, default=32)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
+    ap.add_argument('--conv1-only', action='store_true')
+    ap.add_argument('--json', default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('video_bench.py measures on a GPU; none is visible')
+    if a.conv1_only:
+        return conv1_only(a)
+    from oracle import istvt_ref as R
+    grid = R.stem_out_side(a.size)
+    dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
+    torch.manual_seed(0)
+    model = XceptionVidTr(num_frames=a.T, grid=grid, depth=a.depth, compute_dtype=dt).cuda().eval()
+    g = torch.Generator().manual_seed(1)
+    u8 = torch.randint(0, 256, (a.frames, a.size, a.size, 3), generator=g, dtype=torch.uint8)
+    xn = (((u8.float() / 255) - torch.tensor(video.DEFAULT_MEAN)) / torch.tensor(video.DEFAULT_STD)).permute(0, 3, 1, 2).contiguous()
+    u8, xn = u8.cuda(), xn.cuda()
+    out = {'frames': a.frames, 'size': a.size, 'T': a.T, 'depth': a.depth, 'dtype': a.dtype, 'frame_batch': a.frame_batch,
+           'window_batch': a.window_batch, 'reps': a.reps, 'warmup': a.warmup, 'strides': {}}
+    for stride in [int(s) for s in a.strides.split(',')]:
+        scorer = video.VideoScorer(model, stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch)
+        starts = video.window_starts(a.frames, a.T, stride, True)
+        W = len(starts)
+        tab = (torch.tensor(starts).view(-1, 1) + torch.arange(a.T).view(1, -1)).cuda()
+        res = {}
+
+        def run_scorer():
+            res['a'] = scorer.score(u8).window_logits
+
+        def run_clips():
+            with torch.no_grad():
+                res['b'] = torch.cat([model(xn[tab[i:i + a.window_batch]]) for i in range(0, W, a.window_batch)])
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_scorer), timed(run_clips)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        diff = float((res['a'] - res['b']).abs().max())
+        # one instrumented run of (a): events around the three phases and the two new kernels (ops.prof)
+        ops.kernel_profile = []
+        stem0, gather0, ft0 = scorer._stem, ops.tokens_gather_fwd, model.vit.forward_tokens
+
+        def wrap(name, fn):
+            def f(*p, **k):
+                with ops.prof(name):
+                    return fn(*p, **k)
+            return f
+        try:
+            scorer._stem = wrap('phase:stem', stem0)
+            ops.tokens_gather_fwd = wrap('phase:tokens', gather0)
+            model.vit.forward_tokens = wrap('phase:transformer', ft0)
+            run_scorer()
+            torch.cuda.synchronize()
+            split = {}
+            for name, e0, e1, nbytes, flops in ops.kernel_profile:
+                if name.startswith('phase:') or name in ('conv1_fwd_u8', 'tokens_gather_fwd'):
+                    d = split.setdefault(name.replace('phase:', ''), {'ms': 0.0, 'bytes': 0})
+                    d['ms'] += e0.elapsed_time(e1)
+                    d['bytes'] += nbytes
+        finally:
+            ops.kernel_profile = None
+            scorer._stem, ops.tokens_gather_fwd = stem0, gather0
+            del model.vit.forward_tokens                   # the instance attribute; the method is back
+        sa, sb = stats(ta), stats(tb)
+        rec = {'windows': W, 'scorer': sa, 'clip_path': sb, 'scorer_windows_per_s': W / sa['median_ms'] * 1e3,
+               'clip_path_windows_per_s': W / sb['median_ms'] * 1e3, 'speedup': sb['median_ms'] / sa['median_ms'],
+               'clip_path_spread': (sb['max_ms'] - sb['min_ms']) / sb['median_ms'],
+               'scorer_spread': (sa['max_ms'] - sa['min_ms']) / sa['median_ms'], 'max_abs_logit_diff': diff, 'split_ms': split}
+        out['strides'][str(stride)] = rec
+        print('stride %d: %d windows | scorer %.1f ms (%.1f-%.1f) = %.1f windows/s | clip path %.1f ms (%.1f-%.1f) = %.1f windows/s'
+              ' | x%.2f | max |logit diff| %.2e' % (stride, W, sa['median_ms'], sa['min_ms'], sa['max_ms'], rec['scorer_windows_per_s'],
+                                                   sb['median_ms'], sb['min_ms'], sb['max_ms'], rec['clip_path_windows_per_s'],
+                                                   rec['speedup'], diff), flush=True)
+        print('          split of one instrumented scorer run: ' +
+              ', '.join('%s %.2f ms' % (k, v['ms']) for k, v in split.items()), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, 'w') as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps({'video_bench': {k: {'scorer_windows_per_s': v['scorer_windows_per_s'],
+                                          'clip_path_windows_per_s': v['clip_path_windows_per_s']}
+                                      for k, v in out['strides'].items()}}))
+
+
+if __name__ == '__main__':
+    main()
