@@ -6,6 +6,8 @@ package through ``istvt_pkg.load()`` at the repo root, which registers it as ``i
 Layout
     csrc/          hand-written HIP kernels + the C ABI (libistvt_hip.so, see include/istvt_hip.h)
     _lib.py        ctypes binding of the C ABI (fails loudly when the library is missing)
+    _common.py     dtype codes, stream handle, row-strided layout, cast: what ops.py and weights.py both stand on
+    weights.py     the one cache of every copy derived from a parameter (operands, transposes, stem layouts)
     ops.py         tensor-level launch wrappers (shape checks, stream, dtype codes)
     functional.py  torch.autograd.Function glue (autograd plumbing only)
     network/       nn.Modules mirroring the reference's constructor/forward signatures

@@ -244,7 +244,7 @@ def no_data_parallel(self):
     """``nn.Module._replicate_for_data_parallel`` of every module in network/: the reference loop wraps the model in
     single-process ``nn.DataParallel`` when ``-d`` names more than one device (train_CNN.py:185-186).  That mode cannot
     work here -- replicas are shallow copies made per forward on worker THREADS, while the weight-operand cache
-    (ops._wcache), the side-stream join state and the flat gradient bucket are per process and keyed by the original
+    (weights.cache), the side-stream join state and the flat gradient bucket are per process and keyed by the original
     parameters -- so it fails at the first replication with the way out, instead of training on stale operands."""
     raise RuntimeError(
         '%s: torch.nn.DataParallel is not supported by the HIP path (per-process operand caches, side streams and the '

@@ -8,415 +8,19 @@ device: there is deliberately no CPU path.
 from __future__ import annotations
 
 import os
-import sys
-import weakref
-from typing import Optional, Tuple
+from typing import Optional
 
 import torch
 
 from . import _lib
-
-Tensor = torch.Tensor
-_DT = {torch.float32: 0, torch.bfloat16: 1}
-
-
-def dtype_code(t: Tensor) -> int:
-    try:
-        return _DT[t.dtype]
-    except KeyError:
-        raise TypeError('istvt_amd supports float32 and bfloat16 activations, got %s' % t.dtype) from None
-
-
-def _req(t: Tensor, name: str = 'tensor') -> Tensor:
-    if not t.is_cuda:
-        raise RuntimeError('istvt_amd: %s must be on a ROCm device (no CPU fallback exists for the ISTVT hot path)' % name)
-    return t
-
-
-def _c(t: Tensor) -> Tensor:
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _stream() -> int:
-    # the raw handle of torch's current stream; torch.cuda.current_stream() builds a Stream object through three
-    # Python layers (10 us x ~1500 launches per step)
-    return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-
-
-# ------------------------------------------------------------------------------------------
-# Row-strided activations.  The GEMMs stage their operands with LDS-DMA, which is priced per cache
-# line touched: a [M][728] bf16 tensor has 1456-byte rows, so every 128-byte piece of a row straddles
-# two lines.  Transformer activations (and the bf16 operand copies of the weights) are therefore
-# allocated with rows padded to a multiple of 64 elements and handed around as [M, D] VIEWS of the
-# [M, ld] buffer; every kernel takes the row stride.  Pad columns are never read and never written.
-ROW_ALIGN = 64
-
-
-def _parse_pad_mod(spec: str) -> Tuple[int, int]:
-    try:
-        m, r = (int(v) for v in spec.split(','))
-    except ValueError:
-        raise ValueError("ISTVT_PAD_MOD must be 'm,r' (lines per row = r mod m), got %r" % (spec,)) from None
-    if m < 1 or not 0 <= r < m:
-        raise ValueError('ISTVT_PAD_MOD=%r: need m >= 1 and 0 <= r < m' % (spec,))
-    return m, r
-
-
-_PAD_MOD = _parse_pad_mod(os.environ.get('ISTVT_PAD_MOD', '2,1'))   # (m, r): 64-element units per row = r mod m
-
-
-def pad_ld(n: int) -> int:
-    q = (n + ROW_ALIGN - 1) // ROW_ALIGN
-    m, r = _PAD_MOD
-    return (q + ((r - q) % m)) * ROW_ALIGN
-
-
-def empty_rows(M: int, D: int, dtype, device, pad: bool = True) -> Tensor:
-    ld = pad_ld(D) if pad else D
-    buf = torch.empty((M, ld), dtype=dtype, device=device)
-    return buf if ld == D else buf[:, :D]
-
-
-def zeros_rows(M: int, D: int, dtype, device, pad: bool = True) -> Tensor:
-    ld = pad_ld(D) if pad else D
-    buf = torch.zeros((M, ld), dtype=dtype, device=device)
-    return buf if ld == D else buf[:, :D]
-
-
-def rows(t: Tensor) -> Tuple[Tensor, int]:
-    """(2-D view [M, D] with unit column stride, row stride in elements); copies only if the layout is not that."""
-    t2 = t if t.dim() == 2 else t.reshape(-1, t.shape[-1])
-    M, D = t2.shape
-    if M == 1:
-        return (t2 if t2.stride(1) == 1 else t2.contiguous()), D
-    if t2.stride(1) != 1 or t2.stride(0) < D or t2.stride(0) % 8 != 0 or t2.data_ptr() % 16 != 0:
-        t2 = t2.contiguous()
-    return t2, t2.stride(0)
-
-
-# ------------------------------------------------------------------------------------------
-# fp32 master weight -> compute-dtype operand, cached per parameter version
-_wcache: dict = {}
-_wepoch = [0]          # bumped by writers that modify parameters behind autograd's back (parallel.FusedSGD / FusedAdamW)
-
-
-def invalidate_weight_cache():
-    """A kernel wrote parameters through raw pointers (no ``_version`` bump): drop every cached operand copy."""
-    _wepoch[0] += 1
-
-
-# bf16 GEMM operands that come out of the fused cast + transpose pass (weight_as(pad=True) / weight_cat_as):
-# cache key -> (weakrefs of the fp32 parameters stacked in the operand, operand [sum R, C], transpose [C, sum R]).
-# refresh_stale_operands() re-casts every one whose parameters have changed in ONE grouped launch.
-_operands: dict = {}
-
-
-def _versions(ws) -> tuple:
-    return tuple(w._version for w in ws) + (_wepoch[0],)
-
-
-def _holders(t: Tensor) -> tuple:
-    """(Python references, C++ references to the TensorImpl -- autograd SavedVariables --, tensors sharing the storage --
-    views and slices) of `t`, each including what THIS call adds.  Only differences between two calls made the same way
-    mean anything: _operand_holders() is the one place that calls it."""
-    try:
-        return (sys.getrefcount(t), t._use_count(), torch._C._storage_Use_Count(t.untyped_storage()._cdata))
-    except AttributeError:
-        # private torch APIs (Tensor._use_count, torch._C._storage_Use_Count) gone in this build: report "held by somebody",
-        # so that no operand is ever rewritten in place (it is re-made instead: correct, one launch per weight slower)
-        global _holders_warned
-        if not _holders_warned:
-            _holders_warned = True
-            import warnings
-            warnings.warn('istvt_amd.ops: torch lacks the reference-count introspection used to refresh bf16 operand copies in '
-                          'place; falling back to re-making them (slower, still correct)')
-        return (1 << 30, 1 << 30, 1 << 30)
-
-
-_holders_warned = False
-
-
-def _operand_holders(key) -> tuple:
-    _refs, out, wt = _operands[key]
-    return _holders(out) + _holders(wt)
-
-
-def _idle_holder_counts(view: bool) -> tuple:
-    """what _operand_holders() returns for an operand pair that NOTHING but the two caches holds: measured, not assumed --
-    a throw-away pair is put through the same dict / tuple structure and the same call (so another Python version's
-    reference accounting, or a refactor of the cache entries, moves the baseline and the check together)."""
-    if view not in _idle_counts:
-        saved = (dict(_operands), dict(_wcache))
-        try:
-            key = ('calibration', view)
-            mk = (lambda: torch.empty((2, 16))[:, :8]) if view else (lambda: torch.empty((2, 8)))
-            # Under the mode real operands are made in (a normal forward): the first stale refresh now runs inside the
-            # optimizer step, possibly under torch.inference_mode() / no_grad, where a slice carries no ._base and its storage
-            # has one holder fewer -- a baseline taken there made every later refresh look "held" and silently fell back to 84
-            # lazy casts per step (ADVICE r5).
-            with torch.inference_mode(False), torch.enable_grad():
-                out, wt = mk(), mk()
-            if (out._base is not None) != bool(view) or (wt._base is not None) != bool(view):
-                raise RuntimeError('istvt_amd.ops: calibration operand is %sa view (expected view=%r)'
-                                   % ('' if out._base is not None else 'not ', view))
-            _operands[key] = ((), out, wt)
-            _wcache[key] = (None, None, out)
-            _wcache[(id(out), 'T')] = (None, 0, wt)
-            del out, wt
-            _idle_counts[view] = _operand_holders(key)
-        finally:
-            _operands.clear(); _operands.update(saved[0])
-            _wcache.clear(); _wcache.update(saved[1])
-    return _idle_counts[view]
-
-
-_idle_counts: dict = {}
-
-
-def refresh_stale_operands() -> int:
-    """Re-cast, in one grouped launch (istvt_cast_transpose_group), the bf16 operand copies (W and W^T) of every weight
-    that changed since they were made -- i.e. of all of them after an optimizer step.  The models call this at the start
-    of a forward pass; without it the same work happens lazily, one launch per weight (84 per step at depth 12, each far
-    shorter than the ~5 us a launch occupies the queue for).  Returns the number of weights re-cast."""
-    import ctypes as C
-    _refresh_derived()
-    static = static_addresses()
-    if static:
-        _refresh_plain_copies()
-    todo = []
-    for key, (refs, out, wt) in list(_operands.items()):
-        ws = [r() for r in refs]
-        hit = _wcache.get(key)
-        if any(w is None for w in ws) or hit is None or hit[2] is not out:
-            _operands.pop(key, None)
-            continue
-        ver = _versions(ws)
-        if hit[1] != ver:
-            # Rewritten IN PLACE only when nothing but the two caches (and this loop) holds the operand or its transpose.  A
-            # live autograd graph that saved them (ctx attributes or save_for_backward of RepChainFn / StemFn / LinearFn:
-            # forward A -> optimizer step -> forward B -> backward A) must still find forward A's weights: those copies are
-            # left alone -- dropped from the caches, so the next use makes fresh ones -- and die with the graph.
-            # Holders are counted three ways (_holders: Python references, C++ references such as SavedVariable, tensors
-            # sharing the storage such as views / slices) and compared with the counts of an operand pair that only the
-            # caches hold, measured once through the same structures (_idle_holder_counts).
-            del out, wt, hit
-            idle = (_idle_holder_counts(_operands[key][1]._base is not None)[:3]
-                    + _idle_holder_counts(_operands[key][2]._base is not None)[3:])
-            if not static and any(a > b for a, b in zip(_operand_holders(key), idle)):
-                _refs, out, _wt = _operands[key]
-                _operands.pop(key, None)
-                _wcache.pop(key, None)
-                _wcache.pop((id(out), 'T'), None)
-                continue
-            _refs, out, wt = _operands[key]
-            todo.append((key, ws, out, wt, ver, _wcache[key]))
-    if not todo:
-        return 0
-    srcs, ins, ldi, outs, ldo, outts, ldt, Rs, Cs = [], [], [], [], [], [], [], [], []
-    for key, ws, out, wt, ver, hit in todo:
-        es, r0 = out.element_size(), 0
-        for w in ws:
-            w2 = _c(w.detach().reshape(w.shape[0], -1))
-            srcs.append(w2)                       # kept alive until the launch is enqueued
-            n, K = w2.shape
-            ins.append(w2.data_ptr()); ldi.append(K)
-            outs.append(out.data_ptr() + r0 * out.stride(0) * es); ldo.append(out.stride(0))
-            outts.append(wt.data_ptr() + r0 * es); ldt.append(wt.stride(0))
-            Rs.append(n); Cs.append(K)
-            r0 += n
-    n = len(ins)
-    PA, LA, IA = C.c_void_p * n, C.c_long * n, C.c_int * n
-    _lib.check(_lib.lib().istvt_cast_transpose_group(n, PA(*ins), LA(*ldi), PA(*outs), LA(*ldo), PA(*outts), LA(*ldt),
-                                                     IA(*Rs), IA(*Cs), _stream()), 'istvt_cast_transpose_group')
-    for key, ws, out, wt, ver, hit in todo:
-        _wcache[key] = (hit[0], ver, out)
-    return n
-
-# ------------------------------------------------------------------------------------------
-# Derived weight layouts that are built with a few torch ops (the stem's tap-major depthwise weights, conv1 / conv2 in
-# GEMM form): cached per parameter version like the operand copies, and -- like them -- rebuilt by
-# refresh_stale_operands(), i.e. right behind the optimizer step when a fused optimizer drives the loop, instead of at
-# the head of the next forward pass (where a loop that syncs every step has the GPU waiting for the host).
-_derived: dict = {}
-
-
-def derived(key, w: Tensor, builder):
-    """builder(w) -> Tensor, cached until `w` changes (its version counter, or a raw-pointer writer's epoch)"""
-    hit = _derived.get(key)
-    ver = _versions((w,))
-    if hit is not None and hit[0]() is w and hit[1] == ver:
-        return hit[2]
-    out = builder(w)
-    _derived[key] = (weakref.ref(w, lambda _r, k=key, c=_derived: c.pop(k, None)), ver, out, builder)
-    return out
-
-
-def _refresh_derived() -> int:
-    n = 0
-    for key, (ref, ver, _out, builder) in list(_derived.items()):
-        w = ref()
-        if w is None:
-            _derived.pop(key, None)
-        elif ver != _versions((w,)):
-            if static_addresses():
-                # captured HIP graphs hold the ADDRESS of the layout (parallel.StepGraphs): rebuilt in place
-                _out.copy_(builder(w))
-                _derived[key] = (ref, _versions((w,)), _out, builder)
-            else:
-                # a FRESH tensor (never in place): whatever a live autograd graph still holds of the old layout stays intact
-                _derived[key] = (ref, _versions((w,)), builder(w), builder)
-            n += 1
-    return n
-
-
-# Static-address mode (parallel.StepGraphs: the forward / backward launch sequences captured as HIP graphs hold raw
-# pointers): every cached copy derived from a parameter -- bf16 operand pairs, plain casts, stacked operands, derived
-# layouts -- is then refreshed IN PLACE, always, by refresh_stale_operands(); nothing is ever re-made at a new address.
-# The price is the guarantee the eager mode gives a live autograd graph (its saved operand copies stay intact when the
-# parameter changes before backward): with graphs on, parameters must not be modified between a forward and its backward
-# -- which the graphs' own static activations forbid anyway.
-_static = [False]
-_static_holders = weakref.WeakSet()     # parallel.StepGraphs objects: the mode is on while any of them holds a captured graph
-
-
-def set_static_addresses(on: bool) -> bool:
-    """explicit switch (beside the automatic one: on while a parallel.StepGraphs holds captured graphs)"""
-    prev = _static[0]
-    _static[0] = bool(on)
-    return prev
-
-
-def static_addresses() -> bool:
-    return _static[0] or any(h.entries for h in _static_holders)
-
-
-def _refresh_plain_copies() -> int:
-    """static-address mode: the cached copies that are NOT (operand, transpose) pairs of the grouped refresh -- plain casts
-    (weight_as without padding or of a narrow weight), padded casts without a fused transpose, stacked operands without one,
-    weight_t_as transposes, and the lazily made transposes of such copies (_transposed_operand) -- re-made into the buffers
-    they already live in.  A handful per model (the head's Linear, narrow 1x1 convolutions)."""
-    n = 0
-    for key, hit in list(_wcache.items()):
-        kind = key[1] if isinstance(key, tuple) and len(key) == 2 else None
-        if kind == 'T' or key in _operands:
-            continue                                    # transposes follow their source; pairs: the grouped refresh
-        refs, ver, out = hit
-        ws = [r() for r in (refs if isinstance(refs, tuple) else (refs,))]
-        if any(w is None for w in ws) or _versions(ws) == tuple(ver):
-            continue
-        if kind == 'cat':
-            r0 = 0
-            for w in ws:
-                out[r0:r0 + w.shape[0]].copy_(w.detach())
-                r0 += w.shape[0]
-        else:
-            w2 = ws[0].detach()
-            if w2.dim() != 2:
-                w2 = w2.reshape(w2.shape[0], -1)
-            out.copy_(w2.t() if kind == 't' else w2)    # casts on the way; `out` may be a row-padded view
-        tr = _wcache.get((id(out), 'T'))
-        if tr is not None and tr[0]() is out:
-            tr[2].copy_(out.t())
-        _wcache[key] = (refs, _versions(ws), out)
-        n += 1
-    return n
-
-
-G256_MIN = 64          # smallest output edge routed to the 256x256 DMA GEMM (mirrors ISTVT_G256_MIN in gemm.hip)
-
-
-def cast(t: Tensor, dtype: torch.dtype) -> Tensor:
-    _req(t)
-    if t.dtype == dtype:
-        return t
-    t = _c(t)
-    out = torch.empty(t.shape, dtype=dtype, device=t.device)
-    if t.numel():
-        _lib.check(_lib.lib().istvt_cast(t.data_ptr(), dtype_code(t), out.data_ptr(), _DT[dtype], t.numel(), _stream()),
-                   'istvt_cast')
-    return out
-
-
-def weight_as(w: Tensor, dtype: torch.dtype, pad: bool = False) -> Tensor:
-    """2-D view of a (fp32) parameter in the compute dtype; bf16 copies are cached until the parameter is modified
-    in place (optimizer step bumps ``_version``).  pad=True: the copy has line-aligned rows (a [N, K] view of a
-    [N, pad_ld(K)] buffer), the layout the DMA-staged GEMMs want for their B operand."""
-    w2 = w.detach()
-    if w2.dim() != 2:
-        w2 = w2.reshape(w2.shape[0], -1)
-    if w2.dtype == dtype:
-        return _c(w2)
-    pad = pad and w2.shape[1] % 8 == 0 and pad_ld(w2.shape[1]) != w2.shape[1]
-    key = (id(w), 'p') if pad else id(w)    # id-keyed: Tensor.__eq__ is elementwise, so tensors cannot be dict keys
-    hit = _wcache.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == _versions((w,)) and hit[2].dtype == dtype:
-        return hit[2]
-    if pad:
-        w2 = _c(w2)
-        R, C = w2.shape
-        out = empty_rows(R, C, dtype, w2.device)
-        if w2.dtype == torch.float32 and dtype == torch.bfloat16 and R % 8 == 0 and R >= G256_MIN and C >= G256_MIN:
-            # the operand of the input-gradient GEMM (W^T, k-contiguous) comes out of the same pass over the fp32 weight
-            wt = empty_rows(C, R, dtype, w2.device)
-            _lib.check(_lib.lib().istvt_cast_transpose(w2.data_ptr(), C, out.data_ptr(), out.stride(0), wt.data_ptr(),
-                                                       wt.stride(0), R, C, _stream()), 'istvt_cast_transpose')
-            tkey = (id(out), 'T')
-            _wcache[tkey] = (weakref.ref(out, lambda _r, k=tkey, c=_wcache: c.pop(k, None)), 0, wt)
-            _operands[key] = ((weakref.ref(w),), out, wt)          # refreshed in place by refresh_stale_operands()
-        else:
-            _lib.check(_lib.lib().istvt_cast2d(w2.data_ptr(), dtype_code(w2), C, out.data_ptr(), _DT[dtype],
-                                               out.stride(0), R, C, _stream()), 'istvt_cast2d')
-    else:
-        out = cast(w2, dtype)
-    # (the parameter's death drops the operand copies at once, not at the next refresh_stale_operands())
-    _wcache[key] = (weakref.ref(w, lambda _r, k=key, c=_wcache, o=_operands: (c.pop(k, None), o.pop(k, None))), _versions((w,)), out)
-    return out
-
-
-def weight_cat_as(ws, dtype: torch.dtype) -> Tensor:
-    """[w_0; w_1; ...] stacked along the output dimension as ONE line-aligned GEMM operand in the compute dtype: the
-    parameters stay separate (state dict, optimizer), the operand copy is cached until one of them is modified.
-    TemporalResidualAttention's [to_qk | to_v] (module.py:182-183): one 728 -> 1536 GEMM instead of two.  For bf16 the
-    operand of the input-gradient GEMM ([K, sum N_i], k-contiguous W^T) comes out of the same passes over the fp32
-    weights."""
-    ws = tuple(ws)
-    key = (tuple(id(w) for w in ws), 'cat')
-    ver = _versions(ws)
-    hit = _wcache.get(key)
-    if hit is not None and all(r() is w for r, w in zip(hit[0], ws)) and hit[1] == ver and hit[2].dtype == dtype:
-        return hit[2]
-    K = ws[0].shape[1]
-    if any(w.dim() != 2 or w.shape[1] != K for w in ws):
-        raise RuntimeError('weight_cat_as: the weights must be 2-D with one input width')
-    R = sum(w.shape[0] for w in ws)
-    dev = ws[0].device
-    out = empty_rows(R, K, dtype, dev, K % 8 == 0)
-    fused_t = (dtype == torch.bfloat16 and all(w.dtype == torch.float32 and w.shape[0] % 8 == 0 and w.shape[0] >= G256_MIN
-                                                for w in ws) and K >= G256_MIN and K % 8 == 0)
-    wt = empty_rows(K, R, dtype, dev) if fused_t else None
-    r0 = 0
-    for w in ws:
-        w2 = _c(w.detach())
-        n = w2.shape[0]
-        if fused_t:
-            es = out.element_size()
-            _lib.check(_lib.lib().istvt_cast_transpose(w2.data_ptr(), K, out.data_ptr() + r0 * out.stride(0) * es, out.stride(0),
-                                                       wt.data_ptr() + r0 * es, wt.stride(0), n, K, _stream()),
-                       'istvt_cast_transpose')
-        else:
-            out[r0:r0 + n].copy_(w2)
-        r0 += n
-    if wt is not None:
-        tkey = (id(out), 'T')
-        _wcache[tkey] = (weakref.ref(out, lambda _r, k=tkey, c=_wcache: c.pop(k, None)), 0, wt)
-        _operands[key] = (tuple(weakref.ref(w) for w in ws), out, wt)
-    drop = lambda _r, k=key, c=_wcache, o=_operands: (c.pop(k, None), o.pop(k, None))
-    _wcache[key] = (tuple(weakref.ref(w, drop) for w in ws), ver, out)
-    return out
+# dtype codes, the stream handle, the row-strided activation layout (pad_ld / empty_rows / rows) and the cast launch
+from ._common import (G256_MIN, ROW_ALIGN, Tensor, _DT, _c, _ptr, _req, _stream, cast, dtype_code,  # noqa: F401
+                      empty_rows, pad_ld, rows, zeros_rows)
+# Every copy derived from a parameter (the compute-dtype operand, its transpose, the stacked operand, the stem's layouts):
+# cached, refreshed and released by weights.py; the names below are the live cache's.
+from .weights import (_refresh_derived, _refresh_plain_copies, _static_holders, _transposed_operand,  # noqa: F401
+                      _versions, derived, invalidate_weight_cache, refresh_stale_operands, set_static_addresses,
+                      static_addresses, weight_as, weight_cat_as)
 
 
 # ------------------------------------------------------------------------------------------
@@ -588,35 +192,6 @@ def linear_fwd(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, residual: Op
     gemm_raw(x, lda, True, w, ldb, True, y, ldc, M, N, K, bias=bias, residual=residual, ldr=ldr, stats=stats, blocked=blocked,
              a_sel_col=a_sel_col)
     return y
-
-
-def weight_t_as(w: Tensor, dtype: torch.dtype) -> Tensor:
-    """W^T ([K,N] contiguous) of a [N,K] parameter in the compute dtype, cached per parameter
-    version.  With it the input gradient dx = dy W is the same k-contiguous ("NT") GEMM as the
-    forward, i.e. it runs on the DMA-staged 256x256 kernel; transposing 88 M weights once per
-    optimizer step is noise next to transposing activations."""
-    key = (id(w), 't')
-    hit = _wcache.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == (w._version, _wepoch[0]) and hit[2].dtype == dtype:
-        return hit[2]
-    wt = weight_as(w, dtype).t()
-    out = empty_rows(wt.shape[0], wt.shape[1], dtype, w.device)
-    out.copy_(wt)
-    _wcache[key] = (weakref.ref(w, lambda _r, k=key, c=_wcache: c.pop(k, None)), (w._version, _wepoch[0]), out)
-    return out
-
-
-def _transposed_operand(w: Tensor) -> Tensor:
-    """w^T of an already-cast GEMM operand (the per-version cached bf16 weight copy), cached for
-    as long as that operand tensor lives."""
-    key = (id(w), 'T')
-    hit = _wcache.get(key)
-    if hit is not None and hit[0]() is w:
-        return hit[2]
-    wt = empty_rows(w.shape[1], w.shape[0], w.dtype, w.device)        # line-aligned rows for the DMA-staged GEMM
-    wt.copy_(w.t())
-    _wcache[key] = (weakref.ref(w, lambda _r, k=key, c=_wcache: c.pop(k, None)), 0, wt)
-    return wt
 
 
 def linear_dgrad(dy: Tensor, w: Tensor, gelu_u: Optional[Tensor] = None, wt: Optional[Tensor] = None,

@@ -498,7 +498,7 @@ class StepGraphs:
       * the previous graphed forward of this entry has had its backward (or was dropped): an entry owns ONE set of saved
         activations.
     Addresses: parameters, gradients and every cached operand copy must stay where they were at capture; the cached copies are
-    refreshed in place (ops.set_static_addresses), parameters and gradients are fingerprinted (data_ptr of each) and a change
+    refreshed in place (the static-address mode of weights.py), parameters and gradients are fingerprinted (data_ptr of each) and a change
     drops the graphs and captures again.  The first ``warmup`` calls of an entry run launch by launch (they fill the operand
     caches, the statistics arena, the side stream, the kernels' one-time attribute calls).  Every entry has a memory pool of
     its own: replaying one never touches what another saved for its backward."""
@@ -627,6 +627,7 @@ class StepGraphs:
         from . import functional as Fn
         from . import ops
         from . import stem as stem_mod
+        from . import weights
         Fn.flush_stale_joins()
         if self.anchor is None or self.anchor.device != x.device:
             self.anchor = torch.zeros((), device=x.device, requires_grad=True)
@@ -655,8 +656,7 @@ class StepGraphs:
             stem_mod._arena.clear()
             stem_mod._arena.update(arena_saved)
         # everything outside the graphs' pool whose ADDRESS they captured stays alive with them
-        ent.keep = ([h[2] for h in ops._wcache.values()] + [d[2] for d in ops._derived.values()]
-                    + [arena_private] + [v[1:] for v in ops._operands.values()])
+        ent.keep = weights.cache.tensors() + [arena_private]
         self.entries[key] = ent
         self.stats['captures'] += 1
         return ent

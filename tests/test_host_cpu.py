@@ -538,7 +538,8 @@ def test_derived_weight_layouts_follow_the_parameter(pkg):
     assert c is not b and len(calls) == 3
     del w
     gc.collect()
-    assert key not in ops._derived
+    from istvt_amd import weights
+    assert weights.cache.entry('derived', key) is None
 
 
 def test_fused_zero_grad_recovers_from_an_aborted_backward(pkg):
@@ -570,61 +571,102 @@ def test_fused_zero_grad_recovers_from_an_aborted_backward(pkg):
 def test_operand_refresh_baseline_is_mode_independent(pkg):
     """the idle-holder baseline of ops.refresh_stale_operands() is taken under grad mode whatever mode the first
     stale refresh runs in (the optimizer step: possibly torch.inference_mode())."""
-    from istvt_amd import ops
-    ops._idle_counts.clear()
+    from istvt_amd.weights import WeightCache
+    WeightCache._idle.clear()
     with torch.inference_mode():
-        a = (ops._idle_holder_counts(True), ops._idle_holder_counts(False))
-    ops._idle_counts.clear()
-    b = (ops._idle_holder_counts(True), ops._idle_holder_counts(False))
+        a = (WeightCache._idle_holders(True), WeightCache._idle_holders(False))
+    WeightCache._idle.clear()
+    b = (WeightCache._idle_holders(True), WeightCache._idle_holders(False))
     assert a == b
 
 
-def test_static_address_refresh_rewrites_cached_copies_in_place(pkg):
-    """parallel.StepGraphs relies on ops' static-address mode: every cached copy derived from a parameter is refreshed INTO
-    the buffer it lives in (captured HIP graphs hold its address).  The host logic, on CPU tensors: a plain cast, a weight_t_as
-    transpose, a stacked operand, the lazily made transpose of a cast copy and a derived layout -- all rewritten in place
-    after the parameters change; with the mode off, derived layouts are re-made (a live autograd graph keeps the old one)."""
-    import weakref
-    from istvt_amd import ops
-    saved = (dict(ops._wcache), dict(ops._operands), dict(ops._derived))
-    ops._wcache.clear(); ops._operands.clear(); ops._derived.clear()
+def test_operand_refresh_baseline_leaves_the_live_cache_alone(pkg):
+    """The idle-holder baseline is measured on a private cache: the live one holds the same entry objects afterwards, and a
+    parameter that dies between two calibrations is still dropped from the live cache by its weakref callback."""
+    import gc
+    from istvt_amd import weights
+    cache, WeightCache = weights.cache, weights.WeightCache
+    w = torch.nn.Parameter(torch.zeros(2, 8))
+    v = torch.nn.Parameter(torch.ones(2, 8))
+    for p in (w, v):
+        cache.insert(cache.key('padded', p), (p,), weights._versions((p,)), torch.empty(2, 8), torch.empty(8, 2), grouped=True)
+    kw, kv = cache.key('padded', w), cache.key('padded', v)
     try:
-        w = torch.nn.Parameter(torch.arange(12, dtype=torch.float32).reshape(3, 4))
-        v = torch.nn.Parameter(torch.ones(2, 4))
-        plain = w.detach().to(torch.bfloat16).clone()
-        plain_t = plain.t().contiguous().clone()
-        wt = w.detach().t().to(torch.bfloat16).contiguous().clone()
-        cat = torch.cat((w.detach(), v.detach())).to(torch.bfloat16).clone()
-        ver = ops._versions((w,))
-        ops._wcache[id(w)] = (weakref.ref(w), ver, plain)
-        ops._wcache[(id(plain), 'T')] = (weakref.ref(plain), 0, plain_t)
-        ops._wcache[(id(w), 't')] = (weakref.ref(w), ver, wt)
-        ops._wcache[((id(w), id(v)), 'cat')] = ((weakref.ref(w), weakref.ref(v)), ops._versions((w, v)), cat)
-        der = ops.derived((id(w), 'tap'), w, lambda q: q.detach().t().contiguous())
-        ptrs = [t.data_ptr() for t in (plain, plain_t, wt, cat, der)]
-        with torch.no_grad():
-            w.mul_(2.0)
-            v.add_(1.0)
-        # mode off: the derived layout is re-made at a new address, the plain copies are left to their lazy paths
-        assert not ops.static_addresses()
-        assert ops._refresh_derived() == 1 and ops._derived[(id(w), 'tap')][2].data_ptr() != ptrs[4]
-        with torch.no_grad():
-            w.add_(1.0)
-        prev = ops.set_static_addresses(True)
-        try:
-            der2 = ops._derived[(id(w), 'tap')][2]
-            p_der2 = der2.data_ptr()
-            assert ops._refresh_derived() == 1 and ops._derived[(id(w), 'tap')][2].data_ptr() == p_der2
-            assert torch.equal(der2, w.detach().t())
-            assert ops._refresh_plain_copies() == 3
-        finally:
-            ops.set_static_addresses(prev)
-        assert [t.data_ptr() for t in (plain, plain_t, wt, cat)] == ptrs[:4]
-        assert torch.equal(plain, w.detach().to(torch.bfloat16)) and torch.equal(plain_t, plain.t())
-        assert torch.equal(wt, w.detach().t().to(torch.bfloat16))
-        assert torch.equal(cat, torch.cat((w.detach(), v.detach())).to(torch.bfloat16))
-        assert ops._refresh_plain_copies() == 0                     # nothing stale any more
+        before = dict(cache.entries)
+        index = dict(cache.by_out)
+        WeightCache._idle.clear()
+        WeightCache._idle_holders(True)
+        assert cache.entries.keys() == before.keys() and all(cache.entries[k] is e for k, e in before.items())
+        assert cache.by_out.keys() == index.keys() and all(cache.by_out[k] is e for k, e in index.items())
+        del before, index
+        assert not cache.held(cache.entries[kw])            # (and the baseline fits entries made by the real insert)
+        extra = cache.entries[kw].wt[:1]
+        assert cache.held(cache.entries[kw])
+        del extra
+        del w
+        gc.collect()
+        WeightCache._idle_holders(False)
+        assert kw not in cache.entries and cache.entries[kv].refs[0]() is v
     finally:
-        ops._wcache.clear(); ops._wcache.update(saved[0])
-        ops._operands.clear(); ops._operands.update(saved[1])
-        ops._derived.clear(); ops._derived.update(saved[2])
+        cache.drop(kw)
+        cache.drop(kv)
+
+
+def test_operand_refresh_without_introspection_counts_everything_as_held(pkg, monkeypatch):
+    """where torch lacks the private reference-count introspection, every pair counts as held by somebody (never rewritten in
+    place), with one warning"""
+    import warnings
+    from istvt_amd import weights
+
+    def gone(t):
+        raise AttributeError('_use_count')
+    monkeypatch.setattr(weights, '_holders', gone)
+    monkeypatch.setattr(weights.WeightCache, '_idle', {})
+    monkeypatch.setattr(weights.WeightCache, '_introspection_warned', False)
+    c = weights.WeightCache()
+    e = c.insert(('padded', 0), (), None, torch.empty(2, 8), torch.empty(8, 2), grouped=True)
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter('always')
+        assert c.held(e) and c.held(e)
+    assert len(caught) == 1 and 'introspection' in str(caught[0].message)
+
+
+def test_static_address_refresh_rewrites_cached_copies_in_place(pkg):
+    """parallel.StepGraphs relies on the static-address mode of weights.py: every cached copy derived from a parameter is
+    refreshed INTO the buffer it lives in (captured HIP graphs hold its address).  The host logic, on CPU tensors put into a
+    private cache through its insert(): a plain cast, the lazily made transpose of that cast, a stacked operand and a derived
+    layout -- all rewritten in place after the parameters change; with the mode off, derived layouts are re-made (a live
+    autograd graph keeps the old one)."""
+    from istvt_amd import ops, weights
+    c = weights.WeightCache()
+    w = torch.nn.Parameter(torch.arange(12, dtype=torch.float32).reshape(3, 4))
+    v = torch.nn.Parameter(torch.ones(2, 4))
+    plain = w.detach().to(torch.bfloat16).clone()
+    plain_t = plain.t().contiguous().clone()
+    cat = torch.cat((w.detach(), v.detach())).to(torch.bfloat16).clone()
+    c.insert(c.key('plain', w), (w,), ops._versions((w,)), plain, plain_t)
+    c.insert(c.key('cat', (w, v)), (w, v), ops._versions((w, v)), cat)
+    assert c._transposed_operand(plain) is plain_t
+    der = c.derived((id(w), 'tap'), w, lambda q: q.detach().t().contiguous())
+    ptrs = [t.data_ptr() for t in (plain, plain_t, cat, der)]
+    with torch.no_grad():
+        w.mul_(2.0)
+        v.add_(1.0)
+    # mode off: the derived layout is re-made at a new address, the plain copies are left to their lazy paths
+    assert not ops.static_addresses()
+    assert c._refresh_derived() == 1 and c.entry('derived', (id(w), 'tap')).out.data_ptr() != ptrs[3]
+    with torch.no_grad():
+        w.add_(1.0)
+    prev = ops.set_static_addresses(True)
+    try:
+        der2 = c.entry('derived', (id(w), 'tap')).out
+        p_der2 = der2.data_ptr()
+        assert c._refresh_derived() == 1 and c.entry('derived', (id(w), 'tap')).out.data_ptr() == p_der2
+        assert torch.equal(der2, w.detach().t())
+        assert c._refresh_plain_copies() == 2
+    finally:
+        ops.set_static_addresses(prev)
+    assert [t.data_ptr() for t in (plain, plain_t, cat)] == ptrs[:3]
+    assert torch.equal(plain, w.detach().to(torch.bfloat16)) and torch.equal(plain_t, plain.t())
+    assert torch.equal(cat, torch.cat((w.detach(), v.detach())).to(torch.bfloat16))
+    assert c._refresh_plain_copies() == 0                       # nothing stale any more

@@ -264,19 +264,21 @@ def test_operand_refresh_spares_operands_held_by_a_live_graph():
     launch; a dead parameter releases its copies at once."""
     import istvt_pkg
     istvt_pkg.load()
-    from istvt_amd import ops
+    from istvt_amd import ops, weights
+    cache = weights.cache
     w = torch.nn.Parameter(torch.randn(256, 728, device='cuda'))
     op = ops.weight_as(w, torch.bfloat16, pad=True)
     opt = ops._transposed_operand(op)
-    key = (id(w), 'p')
-    assert key in ops._operands and ops._operands[key][1] is op and ops._operands[key][2] is opt
+    ent = cache.entry('padded', w)
+    assert ent is not None and ent.grouped and ent.out is op and ent.wt is opt
+    del ent
     before = op.clone()
     with torch.no_grad():
         w.add_(1.0)                                    # "optimizer step": bumps _version
     del op, opt
     assert ops.refresh_stale_operands() == 1           # steady state: rewritten in place by the grouped launch
     op = ops.weight_as(w, torch.bfloat16, pad=True)
-    assert ops._operands[key][1] is op and not torch.equal(op, before)
+    assert cache.entry('padded', w).out is op and not torch.equal(op, before)
     assert torch.equal(op, w.detach().to(torch.bfloat16))
 
     class Hold(torch.autograd.Function):              # a Function that keeps the operand for its backward
@@ -295,7 +297,7 @@ def test_operand_refresh_spares_operands_held_by_a_live_graph():
         w.add_(1.0)
     held = op
     del op
-    assert ops.refresh_stale_operands() == 0 and key not in ops._operands      # not rewritten: dropped from the caches
+    assert ops.refresh_stale_operands() == 0 and cache.entry('padded', w) is None      # not rewritten: dropped from the caches
     torch.cuda.synchronize()
     assert torch.equal(held, snap)                                              # forward A's operand is intact
     fresh = ops.weight_as(w, torch.bfloat16, pad=True)
@@ -309,20 +311,20 @@ def test_operand_refresh_spares_operands_held_by_a_live_graph():
     del op
     with torch.no_grad():
         w.add_(1.0)
-    assert ops.refresh_stale_operands() == 0 and key not in ops._operands
+    assert ops.refresh_stale_operands() == 0 and cache.entry('padded', w) is None
     (held,) = y.grad_fn.saved_tensors
     torch.cuda.synchronize()
     assert torch.equal(held, snap)
     y.sum().backward()
     del y, held
     # (b) ONLY a view / slice of the operand (it shares the storage) is held, and (c) only a slice of its transpose
-    for which in (1, 2):
+    for which in ('out', 'wt'):
         ops.weight_as(w, torch.bfloat16, pad=True)
-        part = ops._operands[key][which][:8]
+        part = getattr(cache.entry('padded', w), which)[:8]
         snap = part.clone()
         with torch.no_grad():
             w.add_(1.0)
-        assert ops.refresh_stale_operands() == 0 and key not in ops._operands, which
+        assert ops.refresh_stale_operands() == 0 and cache.entry('padded', w) is None, which
         torch.cuda.synchronize()
         assert torch.equal(part, snap), which
         del part
@@ -330,13 +332,14 @@ def test_operand_refresh_spares_operands_held_by_a_live_graph():
     ops.weight_as(w, torch.bfloat16, pad=True)
     with torch.no_grad():
         w.add_(1.0)
-    assert ops.refresh_stale_operands() == 1 and torch.equal(ops._operands[key][1], w.detach().to(torch.bfloat16))
-    n0 = len(ops._operands)
-    assert key in ops._operands
+    assert ops.refresh_stale_operands() == 1 and torch.equal(cache.entry('padded', w).out, w.detach().to(torch.bfloat16))
+    n0 = cache.grouped_count()
+    key = cache.key('padded', w)
+    assert key in cache.entries and cache.entries[key].grouped
     del w
     import gc
     gc.collect()
-    assert key not in ops._operands and len(ops._operands) == n0 - 1            # the parameter died: copies released
+    assert key not in cache.entries and cache.grouped_count() == n0 - 1         # the parameter died: copies released
 
 
 

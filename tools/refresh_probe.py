@@ -6,7 +6,7 @@ import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, istvt_pkg
 istvt_pkg.load()
-from istvt_amd import ops, parallel
+from istvt_amd import ops, parallel, weights
 from istvt_amd.network.vivit import vivit
 counts = []
 orig = ops.refresh_stale_operands
@@ -30,4 +30,4 @@ for i in range(4):
         with torch.no_grad():
             for p in live: p.add_(p.grad, alpha=-1e-3)
 torch.cuda.synchronize()
-print('refresh counts per call:', counts, ' operands cached:', len(ops._operands))
+print('refresh counts per call:', counts, ' operands cached:', weights.cache.grouped_count())
