@@ -31,6 +31,8 @@ SIGNATURES = {
     'istvt_attn_spatial_relevance': [P, L, P, L, P, P, P, I, I, I, I, F, I, P],
     'istvt_attn_temporal_relevance': [P, L, P, L, P, P, I, I, I, I, I, F, I, I, P],
     'istvt_relevance_heatmap': [P, P, I, I, I, P],
+    'istvt_relevance_fuse_windows': [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    'istvt_relevance_overlay_u8': [P, P, P, P, P, I, I, I, I, P],
     'istvt_tokens_fwd': [P, P, P, P, P, L, I, I, I, I, I, I, P],
     'istvt_tokens_gather_fwd': [P, P, P, P, P, P, L, I, I, I, I, I, I, I, P],
     'istvt_tokens_bwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],

@@ -227,6 +227,16 @@ __device__ __forceinline__ void heat_src(int o, float inv_s, int g, int& i0, int
     l1 = src - (float)i0;
 }
 
+// the upsampled map at output pixel (oy, ox); x: the g x g map
+__device__ __forceinline__ float heat_value(const float* x, int g, float inv_s, int oy, int ox) {
+    int y0, y1, x0, x1;
+    float ly, lx;
+    heat_src(oy, inv_s, g, y0, y1, ly);
+    heat_src(ox, inv_s, g, x0, x1, lx);
+    return (1.f - ly) * ((1.f - lx) * x[y0 * g + x0] + lx * x[y0 * g + x1]) +
+           ly * ((1.f - lx) * x[y1 * g + x0] + lx * x[y1 * g + x1]);
+}
+
 __global__ void __launch_bounds__(256) heatmap_kernel(const float* __restrict__ cam, float* __restrict__ out, int g, int s) {
     __shared__ float x[HEAT_GMAX * HEAT_GMAX];
     __shared__ float rmin[4], rmax[4];
@@ -242,13 +252,7 @@ __global__ void __launch_bounds__(256) heatmap_kernel(const float* __restrict__ 
         float lo = 0.f, den = 1.f;
         if (pass == 1) { lo = mn; den = mx - mn; }
         for (int t = threadIdx.x; t < G * G; t += 256) {
-            const int oy = t / G, ox = t % G;
-            int y0, y1, x0, x1;
-            float ly, lx;
-            heat_src(oy, inv_s, g, y0, y1, ly);
-            heat_src(ox, inv_s, g, x0, x1, lx);
-            const float v = (1.f - ly) * ((1.f - lx) * x[y0 * g + x0] + lx * x[y0 * g + x1]) +
-                            ly * ((1.f - lx) * x[y1 * g + x0] + lx * x[y1 * g + x1]);
+            const float v = heat_value(x, g, inv_s, t / G, t % G);
             if (pass == 0) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
             else dst[t] = (v - lo) / den;
         }
@@ -265,5 +269,229 @@ __global__ void __launch_bounds__(256) heatmap_kernel(const float* __restrict__ 
 extern "C" int istvt_relevance_heatmap(const float* cam, float* out, int maps, int g, int s, hipStream_t stream) {
     if (maps <= 0 || g <= 0 || g > HEAT_GMAX || s <= 0 || (long)g * s > 8192) return ISTVT_ERR_SHAPE;
     hipLaunchKernelGGL(heatmap_kernel, dim3((unsigned)maps), dim3(256), 0, stream, cam, out, g, s);
+    return istvt_check_launch();
+}
+
+// ---- whole videos: the per-window rollouts fused into per-frame maps (DESIGN.md "Explaining whole videos") -----------
+// Window w starts at frame starts[w] (ascending) and covers frame n as its frame t = n - starts[w] when 0 <= t < T.  Per
+// frame: the plain mean over the covering windows, in ascending window order, of cam_s[w][t][j] = r_s[w][t+1][j+1],
+// cam_t[w][t][j] = r_t[w][j+1][t+1], the temporal rollout at the space-class position r_t[w][0][t+1] and logits[w][index];
+// and the number of covering windows.  One workgroup per frame, one thread per output element: every sum has one writer
+// and a fixed order (no atomics), so two runs give the same bits.  A frame no window covers gets zeros.
+__global__ void __launch_bounds__(256) fuse_windows_kernel(const float* __restrict__ r_s, const float* __restrict__ r_t,
+                                                           const float* __restrict__ logits, const int* __restrict__ starts,
+                                                           float* __restrict__ frame_s, float* __restrict__ frame_t,
+                                                           float* __restrict__ frame_weight, float* __restrict__ frame_logit,
+                                                           int* __restrict__ count, int W, int T, int P, int nc, int index) {
+    const int n = blockIdx.x;
+    const int F = T + 1, hw = P - 1;
+    // first window with starts[w] > n - T (uniform binary search), then every window up to the first with starts[w] > n
+    int lo = 0, hi = W;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] > n - T) hi = mid; else lo = mid + 1;
+    }
+    const int w0 = lo;
+    int w1 = w0;
+    while (w1 < W && starts[w1] <= n && starts[w1] > n - T) ++w1;       // the second test holds for ascending starts
+    const int cnt = w1 - w0;
+    const float inv = cnt > 0 ? 1.f / (float)cnt : 0.f;
+    for (int j = threadIdx.x; j < hw; j += 256) {
+        float as = 0.f, at = 0.f;
+        for (int w = w0; w < w1; ++w) {
+            const int t = n - starts[w];
+            as += r_s[((long)w * F + t + 1) * P + j + 1];
+            at += r_t[((long)w * P + j + 1) * F + t + 1];
+        }
+        frame_s[(long)n * hw + j] = as * inv;
+        frame_t[(long)n * hw + j] = at * inv;
+    }
+    if (threadIdx.x == 0) {
+        float aw = 0.f, al = 0.f;
+        for (int w = w0; w < w1; ++w) {
+            aw += r_t[(long)w * P * F + (n - starts[w]) + 1];
+            al += logits[(long)w * nc + index];
+        }
+        frame_weight[n] = aw * inv;
+        frame_logit[n] = al * inv;
+        count[n] = cnt;
+    }
+}
+
+extern "C" int istvt_relevance_fuse_windows(const float* r_s, const float* r_t, const float* logits, const int* starts,
+                                            float* frame_s, float* frame_t, float* frame_weight, float* frame_logit, int* count,
+                                            int W, int T, int P, int nc, int index, int N, hipStream_t stream) {
+    if (W <= 0 || T <= 0 || P < 2 || nc <= 0 || index < 0 || index >= nc || N < T) return ISTVT_ERR_SHAPE;
+    hipLaunchKernelGGL(fuse_windows_kernel, dim3((unsigned)N), dim3(256), 0, stream, r_s, r_t, logits, starts, frame_s, frame_t,
+                       frame_weight, frame_logit, count, W, T, P, nc, index);
+    return istvt_check_launch();
+}
+
+// ---- overlay: the heat map on the frame, bytes in and bytes out (the reference's show_cam_on_image, ----------------------
+// visualize_rel.py:39-44, for a batch of frames).  Per frame: m = the map upsampled by s and min-max normalised (the
+// arithmetic of heatmap_kernel), k = trunc(255 m) (a constant map's 0 / 0 takes k = 0), heat = lut[k] / 255,
+// img = frame / 255 at the output pixel (read directly when S == g s, sampled bilinearly with half-pixel centres
+// otherwise), cam = heat + img, out = trunc(255 cam / max(cam over the frame)).
+// Three launches on one stream: the map's min / max (one workgroup per frame), the frame's max of cam, the write.  The two
+// later ones are one kernel (the same cam arithmetic), a thread takes 16 consecutive pixels: 48 bytes, three 16-byte
+// accesses when the frame size and the pointers allow.  The maximum crosses workgroups as an integer atomic max on the
+// bits of a non-negative float: exact, so the order does not matter.  ws: 4 floats per frame (min, max, max of cam, pad).
+__global__ void __launch_bounds__(256) overlay_minmax_kernel(const float* __restrict__ maps, float* __restrict__ ws, int g, int s) {
+    __shared__ float x[HEAT_GMAX * HEAT_GMAX];
+    __shared__ float rmin[4], rmax[4];
+    const int n = blockIdx.x;
+    const int G = g * s;
+    const float inv_s = 1.f / (float)s;
+    for (int t = threadIdx.x; t < g * g; t += 256) x[t] = maps[(long)n * g * g + t];
+    __syncthreads();
+    float mn = INFINITY, mx = -INFINITY;
+    for (int t = threadIdx.x; t < G * G; t += 256) {
+        const float v = heat_value(x, g, inv_s, t / G, t % G);
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+    }
+    const float a = -wave_max(-mn), b = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = a; rmax[threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ws[4 * n + 0] = fminf(fminf(rmin[0], rmin[1]), fminf(rmin[2], rmin[3]));
+        ws[4 * n + 1] = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+        ws[4 * n + 2] = 0.f;
+        ws[4 * n + 3] = 0.f;
+    }
+}
+
+constexpr int OVL_PIX = 16;                     // pixels per thread
+
+// source taps of F.interpolate(mode='bilinear', align_corners=False) from S to So samples: ratio = S / So
+__device__ __forceinline__ void resample_src(int o, float ratio, int S, int& i0, int& i1, float& l1) {
+    float src = ((float)o + 0.5f) * ratio - 0.5f;
+    src = src < 0.f ? 0.f : src;
+    i0 = (int)src;
+    i0 = i0 < S - 1 ? i0 : S - 1;
+    i1 = i0 < S - 1 ? i0 + 1 : i0;
+    l1 = src - (float)i0;
+}
+
+template <bool WRITE>
+__global__ void __launch_bounds__(256) overlay_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ maps,
+                                                      const uint8_t* __restrict__ lut, float* __restrict__ ws,
+                                                      uint8_t* __restrict__ out, int S, int g, int s, int vec_in, int vec_out) {
+    __shared__ float x[HEAT_GMAX * HEAT_GMAX];
+    __shared__ float heat[256 * 3];
+    __shared__ float rmax[4];
+    const int n = blockIdx.y;
+    const int So = g * s;
+    const long npix = (long)So * So;
+    const float inv_s = 1.f / (float)s;
+    for (int t = threadIdx.x; t < g * g; t += 256) x[t] = maps[(long)n * g * g + t];
+    for (int t = threadIdx.x; t < 256 * 3; t += 256) heat[t] = (float)lut[t] / 255.f;
+    __syncthreads();
+    const float lo = ws[4 * n + 0], den = ws[4 * n + 1] - lo;
+    const float top = WRITE ? ws[4 * n + 2] : 1.f;
+    const uint8_t* frame = frames + (long)n * S * S * 3;
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * OVL_PIX;
+    const bool direct = S == So;
+    const float ratio = (float)S / (float)So;
+
+    uint32_t in[12], o[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) { in[i] = 0u; o[i] = 0u; }
+    if (direct && p0 < npix) {
+        if (vec_in) {                           // npix is a multiple of 16 then: the 16 pixels are all inside
+            const uint4* q = reinterpret_cast<const uint4*>(frame + p0 * 3);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const uint4 v = q[i];
+                in[4 * i] = v.x; in[4 * i + 1] = v.y; in[4 * i + 2] = v.z; in[4 * i + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 48; ++b)
+                if (p0 * 3 + b < npix * 3) in[b >> 2] |= (uint32_t)frame[p0 * 3 + b] << (8 * (b & 3));
+        }
+    }
+    float mx = 0.f;
+    int oy = (int)(p0 / So), ox = (int)(p0 % So);
+#pragma unroll
+    for (int i = 0; i < OVL_PIX; ++i) {
+        if (p0 + i < npix) {
+            const float m = (heat_value(x, g, inv_s, oy, ox) - lo) / den;
+            int k = m >= 0.f ? (int)(255.f * m) : 0;        // NaN (a constant map) compares false
+            k = k < 255 ? k : 255;
+            float img[3];
+            if (direct) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int b = 3 * i + c;
+                    img[c] = (float)((in[b >> 2] >> (8 * (b & 3))) & 0xffu) / 255.f;
+                }
+            } else {
+                int y0, y1, x0, x1;
+                float ly, lx;
+                resample_src(oy, ratio, S, y0, y1, ly);
+                resample_src(ox, ratio, S, x0, x1, lx);
+                const uint8_t* a = frame + ((long)y0 * S + x0) * 3;
+                const uint8_t* b = frame + ((long)y0 * S + x1) * 3;
+                const uint8_t* c2 = frame + ((long)y1 * S + x0) * 3;
+                const uint8_t* d = frame + ((long)y1 * S + x1) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    img[c] = ((1.f - ly) * ((1.f - lx) * (float)a[c] + lx * (float)b[c]) +
+                              ly * ((1.f - lx) * (float)c2[c] + lx * (float)d[c])) / 255.f;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float cam = heat[3 * k + c] + img[c];
+                if (WRITE) {
+                    int v = top > 0.f ? (int)(255.f * (cam / top)) : 0;
+                    v = v < 255 ? v : 255;
+                    const int b = 3 * i + c;
+                    o[b >> 2] |= (uint32_t)v << (8 * (b & 3));
+                } else {
+                    mx = fmaxf(mx, cam);
+                }
+            }
+        }
+        if (++ox == So) { ox = 0; ++oy; }
+    }
+    if (WRITE) {
+        if (p0 < npix) {
+            uint8_t* dst = out + ((long)n * npix + p0) * 3;
+            if (vec_out) {
+                uint4* q = reinterpret_cast<uint4*>(dst);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) q[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 48; ++b)
+                    if (p0 * 3 + b < npix * 3) dst[b] = (uint8_t)((o[b >> 2] >> (8 * (b & 3))) & 0xffu);
+            }
+        }
+    } else {
+        mx = wave_max(mx);
+        if ((threadIdx.x & 63) == 0) rmax[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            mx = fmaxf(fmaxf(rmax[0], rmax[1]), fmaxf(rmax[2], rmax[3]));
+            atomicMax(reinterpret_cast<unsigned*>(ws + 4 * n + 2), __float_as_uint(mx));       // cam >= 0: bits order as values
+        }
+    }
+}
+
+extern "C" int istvt_relevance_overlay_u8(const void* frames, const float* maps, const void* lut, float* ws, void* out,
+                                          int N, int S, int g, int s, hipStream_t stream) {
+    if (N <= 0 || N > 65535 || S <= 0 || g <= 0 || g > HEAT_GMAX || s <= 0 || (long)g * s > 8192) return ISTVT_ERR_SHAPE;
+    const long npix = (long)g * s * g * s;
+    const unsigned chunks = (unsigned)((npix + 256 * OVL_PIX - 1) / (256 * OVL_PIX));
+    const bool whole = npix % OVL_PIX == 0;
+    const int vec_in = whole && S == g * s && (uintptr_t)frames % 16 == 0 && ((long)S * S * 3) % 16 == 0;
+    const int vec_out = whole && (uintptr_t)out % 16 == 0 && (npix * 3) % 16 == 0;
+    const uint8_t* f = static_cast<const uint8_t*>(frames);
+    const uint8_t* l = static_cast<const uint8_t*>(lut);
+    uint8_t* o = static_cast<uint8_t*>(out);
+    hipLaunchKernelGGL(overlay_minmax_kernel, dim3((unsigned)N), dim3(256), 0, stream, maps, ws, g, s);
+    hipLaunchKernelGGL(overlay_kernel<false>, dim3(chunks, (unsigned)N), dim3(256), 0, stream, f, maps, l, ws, o, S, g, s, vec_in, vec_out);
+    hipLaunchKernelGGL(overlay_kernel<true>, dim3(chunks, (unsigned)N), dim3(256), 0, stream, f, maps, l, ws, o, S, g, s, vec_in, vec_out);
     return istvt_check_launch();
 }

@@ -3,6 +3,8 @@ Explainability"), the interpretable half of the reference (visualize_rel.py:206-
 
     res = istvt_amd.explain.relevance(model, clips, index=0)      # or model.relevance(clips)
     maps = istvt_amd.explain.heatmaps(res.cam_s, scale=16)        # (B, T, g*16, g*16), min-max normalised per map
+    ex = model.explain_video(frames)                              # a whole video: video.VideoScorer.explain
+    shown = istvt_amd.explain.overlay(frames, ex.frame_s)         # (N, g*16, g*16, 3) uint8, the maps on the frames
 
 Definition (DESIGN.md "Relevance maps"): y = sum_b logits[b, index]; per layer and head A = softmax output, G = dy/dA;
 Abar_l = (1/H) sum_h max(0, A_{l,h} * G_{l,h}); r = e_0, r <- r + r Abar_l for l = L-1 .. 0, one spatial rollout per
@@ -67,23 +69,28 @@ def _explaining(model):
             m.training = on
 
 
+def _rollouts_tokens(dsttr, x, b, f, p, index):
+    """x: the assembled tokens (b, f*p, dim) of b clips -> Relevance; the caller has put the model in _explaining"""
+    x = x.detach().requires_grad_(True)                       # the backward pass ends at the tokens
+    rel = Fn.RelevanceContext(b, f, p, x.device)
+    with torch.enable_grad(), Fn.relevance_mode(rel):
+        logits = dsttr.forward_tokens(x, b, f, p)
+        if not 0 <= index < logits.shape[1]:
+            raise IndexError('relevance: index %d out of range for %d outputs' % (index, logits.shape[1]))
+        y = logits[:, index].sum()                            # inside enable_grad: VideoScorer.explain calls under no_grad
+    torch.autograd.grad(y, x)
+    return Relevance(rel.r_s.view(b, f, p), rel.r_t.view(b, p, f), logits.detach())
+
+
 def _rollouts(dsttr, feats, index):
     """feats (b, t, hw, c) -> Relevance; the caller has put the model in _explaining"""
     if feats.dim() != 4:
         raise RuntimeError('relevance: features must be (b, t, h*w, c), got %s' % (tuple(feats.shape),))
     b, t, hw, _ = feats.shape
-    f, p = t + 1, hw + 1
     with torch.no_grad():
         x = Fn.TokensFn.apply(ops.cast(feats, dsttr.compute_dtype), dsttr.space_token, dsttr.temporal_token,
                               dsttr.pos_embedding)
-    x = x.detach().requires_grad_(True)                       # the backward pass ends at the tokens
-    rel = Fn.RelevanceContext(b, f, p, x.device)
-    with torch.enable_grad(), Fn.relevance_mode(rel):
-        logits = dsttr.forward_tokens(x, b, f, p)
-    if not 0 <= index < logits.shape[1]:
-        raise IndexError('relevance: index %d out of range for %d outputs' % (index, logits.shape[1]))
-    torch.autograd.grad(logits[:, index].sum(), x)
-    return Relevance(rel.r_s.view(b, f, p), rel.r_t.view(b, p, f), logits.detach())
+    return _rollouts_tokens(dsttr, x, b, t + 1, hw + 1, index)
 
 
 def relevance_features(dsttr, feats, index=0) -> Relevance:
@@ -113,8 +120,39 @@ def heatmaps(cam, scale: int = 16):
     by `scale` (align_corners=False) and (x - min) / (max - min) per map.  cam: (B, T, g, g), or (B, T, g*g) as
     Relevance.cam_s / cam_t hold it -> (B, T, g*scale, g*scale) float32."""
     if cam.dim() == 3:
-        g = int(round(cam.shape[-1] ** 0.5))
-        if g * g != cam.shape[-1]:
-            raise RuntimeError('heatmaps: %d tokens per map is not a square grid' % cam.shape[-1])
+        g = _grid(cam, 'heatmaps')
         cam = cam.reshape(*cam.shape[:-1], g, g)
     return ops.relevance_heatmap(cam, scale)
+
+
+def _grid(cam, what):
+    g = int(round(cam.shape[-1] ** 0.5))
+    if g * g != cam.shape[-1]:
+        raise RuntimeError('%s: %d tokens per map is not a square grid' % (what, cam.shape[-1]))
+    return g
+
+
+def jet_lut(device=None):
+    """The default colour table of overlay(): (256, 3) uint8, a closed-form piecewise-linear jet.  Entry i of the channel
+    with centre c is round(255 * clip(1.5 - |4 i / 255 - 4 c|, 0, 1)), c = 0.75, 0.5, 0.25 for red, green, blue (columns
+    0, 1, 2).  It is NOT pinned to OpenCV's COLORMAP_JET (a sampled table that differs from this formula by a few levels
+    in places), and its channel order is RGB where the reference's cv2 frames are BGR: the order of `lut`'s columns and
+    of the frames' channels is the caller's."""
+    i = torch.arange(256, dtype=torch.float64).view(256, 1)
+    c = torch.tensor([0.75, 0.5, 0.25], dtype=torch.float64).view(1, 3)
+    lut = torch.round(255 * (1.5 - (4 * i / 255 - 4 * c).abs()).clamp(0, 1)).to(torch.uint8)
+    return lut if device is None else lut.to(device)
+
+
+def overlay(frames_u8, maps, scale: int = 16, lut=None):
+    """The reference's show_cam_on_image (visualize_rel.py:39-44) for a batch of frames, decoder bytes in and displayable
+    bytes out: frames_u8 (N, S, S, 3) uint8, maps (N, g, g) or (N, g*g) float32 (VideoExplanation.frame_s, say), lut
+    (256, 3) uint8 (default jet_lut()) -> (N, g*scale, g*scale, 3) uint8.  Per frame: the map upsampled and min-max
+    normalised as heatmaps() does, coloured through the table, added to the frame (resampled bilinearly to g*scale when
+    S differs: 300 -> 304 at the native geometry), and the sum divided by its maximum over the frame."""
+    if maps.dim() == 2:
+        g = _grid(maps, 'overlay')
+        maps = maps.reshape(maps.shape[0], g, g)
+    if lut is None:
+        lut = jet_lut(frames_u8.device)
+    return ops.relevance_overlay_u8(frames_u8, maps, lut, scale)

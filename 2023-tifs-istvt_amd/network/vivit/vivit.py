@@ -210,6 +210,12 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score(frames)
 
+    def explain_video(self, frames, index=0, **kw):
+        """Per-frame relevance maps of one video (frames as score_video takes them) for output `index`:
+        istvt_amd.video.VideoScorer(self, **kw).explain(frames, index)"""
+        from istvt_amd import video
+        return video.VideoScorer(self, **kw).explain(frames, index)
+
     def _forward_eager(self, x):
         b, t = x.shape[:2]
         feats = self.xcep.model.low_level_features_nhwc(x.flatten(0, 1), self.compute_dtype)   # (b*t, h, w, c)

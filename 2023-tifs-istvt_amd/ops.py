@@ -608,6 +608,87 @@ def relevance_heatmap(cam: Tensor, scale: int = 16) -> Tensor:
     return out
 
 
+def check_window_starts(starts, n: int, T: int):
+    """The window starts of an n-frame video as a list of ints: ascending and 0 <= s <= n - T, ValueError otherwise."""
+    starts = [int(v) for v in (starts.tolist() if torch.is_tensor(starts) else starts)]
+    if not starts:
+        raise ValueError('window starts: no windows')
+    if any(b < a for a, b in zip(starts, starts[1:])):
+        raise ValueError('window starts must ascend, got %s' % (starts,))
+    if starts[0] < 0 or starts[-1] > n - T:
+        raise ValueError('window starts span [%d, %d]: %d-frame windows of a %d-frame video start in [0, %d]'
+                         % (starts[0], starts[-1], T, n, n - T))
+    return starts
+
+
+def relevance_fuse_windows(r_s: Tensor, r_t: Tensor, logits: Tensor, starts, n: int, index: int = 0):
+    """The rollouts of W sliding windows fused per frame.  r_s (W, T+1, P), r_t (W, P, T+1), logits (W, nc) fp32; starts:
+    the W first frames (a host tensor or a list, validated here and uploaded on the current stream) -> frame_s, frame_t
+    (n, P-1), frame_weight, frame_logit (n,) fp32 and count (n,) int32: plain means over the windows that cover a frame,
+    in window order; zeros where none does."""
+    for t, what in ((r_s, 'r_s'), (r_t, 'r_t'), (logits, 'logits')):
+        _req(t, what)
+        if t.dtype != torch.float32:
+            raise TypeError('relevance_fuse_windows: %s must be float32, got %s' % (what, t.dtype))
+    if r_s.dim() != 3 or r_t.dim() != 3 or logits.dim() != 2:
+        raise RuntimeError('relevance_fuse_windows: r_s (W, T+1, P), r_t (W, P, T+1) and logits (W, nc) expected, got %s %s %s'
+                           % (tuple(r_s.shape), tuple(r_t.shape), tuple(logits.shape)))
+    W, F, P = r_s.shape
+    T, nc = F - 1, logits.shape[1]
+    if tuple(r_t.shape) != (W, P, F) or logits.shape[0] != W or T < 1 or P < 2:
+        raise RuntimeError('relevance_fuse_windows: r_s %s, r_t %s and logits %s do not describe the same windows'
+                           % (tuple(r_s.shape), tuple(r_t.shape), tuple(logits.shape)))
+    if not 0 <= index < nc:
+        raise IndexError('relevance_fuse_windows: index %d out of range for %d outputs' % (index, nc))
+    starts = check_window_starts(starts, n, T)
+    if len(starts) != W:
+        raise RuntimeError('relevance_fuse_windows: %d starts for %d windows' % (len(starts), W))
+    dev = r_s.device
+    st = torch.tensor(starts, dtype=torch.int32).to(dev, non_blocking=True)
+    r_s, r_t, logits = _c(r_s), _c(r_t), _c(logits)
+    frame_s = torch.empty((n, P - 1), dtype=torch.float32, device=dev)
+    frame_t = torch.empty((n, P - 1), dtype=torch.float32, device=dev)
+    weight = torch.empty((n,), dtype=torch.float32, device=dev)
+    logit = torch.empty((n,), dtype=torch.float32, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    with prof('relevance_fuse_windows', 4 * (2 * W * F * P + 2 * n * (P - 1))):
+        _lib.check(_lib.lib().istvt_relevance_fuse_windows(r_s.data_ptr(), r_t.data_ptr(), logits.data_ptr(), st.data_ptr(),
+                                                           frame_s.data_ptr(), frame_t.data_ptr(), weight.data_ptr(),
+                                                           logit.data_ptr(), count.data_ptr(), W, T, P, nc, int(index), int(n),
+                                                           _stream()), 'istvt_relevance_fuse_windows')
+    return frame_s, frame_t, weight, logit, count
+
+
+def relevance_overlay_u8(frames: Tensor, maps: Tensor, lut: Tensor, scale: int = 16) -> Tensor:
+    """frames uint8 (N, S, S, 3) (any view: a non-contiguous one is copied), maps fp32 (N, g, g), lut uint8 (256, 3) ->
+    uint8 (N, g*scale, g*scale, 3): the colour-mapped, min-max normalised heat map added to the frame and the sum scaled
+    to the frame's maximum (the reference's show_cam_on_image)."""
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[1] != frames.shape[2]:
+        raise RuntimeError('relevance_overlay_u8: frames must be channels-last uint8 (N, S, S, 3), got %s %s'
+                           % (frames.dtype, tuple(frames.shape)))
+    if maps.dtype != torch.float32 or maps.dim() != 3 or maps.shape[1] != maps.shape[2]:
+        raise RuntimeError('relevance_overlay_u8: maps must be float32 (N, g, g), got %s %s' % (maps.dtype, tuple(maps.shape)))
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise RuntimeError('relevance_overlay_u8: lut must be uint8 (256, 3), got %s %s' % (lut.dtype, tuple(lut.shape)))
+    if maps.shape[0] != frames.shape[0]:
+        raise RuntimeError('relevance_overlay_u8: %d maps for %d frames' % (maps.shape[0], frames.shape[0]))
+    if maps.device != frames.device or lut.device != frames.device:
+        raise RuntimeError('relevance_overlay_u8: frames, maps and lut must share one device')
+    N, S, g, s = frames.shape[0], frames.shape[1], maps.shape[1], int(scale)
+    if not 1 <= g <= 64 or s < 1 or g * s > 8192 or not 1 <= N <= 65535 or S < 1:
+        raise RuntimeError('relevance_overlay_u8: need 1 <= g <= 64, 1 <= g*scale <= 8192 and 1 <= N <= 65535 '
+                           '(g=%d, scale=%d, N=%d)' % (g, s, N))
+    frames, maps, lut = _c(frames), _c(maps), _c(lut)
+    So = g * s
+    out = torch.empty((N, So, So, 3), dtype=torch.uint8, device=frames.device)
+    ws = torch.empty((N, 4), dtype=torch.float32, device=frames.device)
+    with prof('relevance_overlay_u8', N * S * S * 3 + N * So * So * 3):
+        _lib.check(_lib.lib().istvt_relevance_overlay_u8(frames.data_ptr(), maps.data_ptr(), lut.data_ptr(), ws.data_ptr(),
+                                                         out.data_ptr(), N, S, g, s, _stream()), 'istvt_relevance_overlay_u8')
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 def tokens_fwd(feats: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad: bool = False) -> Tensor:
     """feats [B,T,hw,D] -> x [B,(T+1)*(hw+1),D]; pos is the full (1,T,P_decl,D) parameter."""

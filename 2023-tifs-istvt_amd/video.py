@@ -3,6 +3,7 @@ video out.
 
     scorer = VideoScorer(model, stride=1)
     res = scorer.score(frames)                       # uint8 (N, S, S, 3), host or device; or float32 (N, 3, S, S)
+    ex = scorer.explain(frames)                      # the same windows through the relevance rollout, fused per frame
     scorer.reset()
     for chunk in stream:                             # the same windows, as the frames arrive
         logits, starts = scorer.push(chunk)
@@ -160,6 +161,17 @@ class VideoScore(NamedTuple):
     prob_mean: Tensor          # (num_classes,) mean of the windows' sigmoids
 
 
+class VideoExplanation(NamedTuple):
+    """Result of VideoScorer.explain: device tensors, complete when explain() returns.  P - 1 = g * g map positions."""
+    score: VideoScore          # as score(frames) returns it, for the same windows
+    windows: object            # explain.Relevance: every window's own maps, cam_s / cam_t (W, T, P-1), in window order
+    frame_s: Tensor            # (N, P-1) float32: mean over the covering windows of cam_s[w, n - start_w]
+    frame_t: Tensor            # (N, P-1) float32: the same of cam_t
+    frame_weight: Tensor       # (N,) float32: mean of r_t[w, 0, n - start_w + 1], how much the verdict rests on the frame
+    frame_logit: Tensor        # (N,) float32: mean of logits[w, index] over the covering windows
+    count: Tensor              # (N,) int32: number of windows that cover the frame (0: zeros in the other fields)
+
+
 @contextlib.contextmanager
 def _eval_mode(model):
     """eval mode for the call; every module's own train / eval flag comes back afterwards (as explain.relevance does)"""
@@ -244,8 +256,9 @@ class VideoScorer:
         if head < k:
             self._ring[:k - head].copy_(feats[head:])
 
-    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev):
-        """-> (logits (W, num_classes) float32 on the device, list of starts) of the windows the steps ran"""
+    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev, rollout=None):
+        """-> (logits (W, num_classes) float32 on the device, list of starts) of the windows the steps ran.  rollout:
+        what runs a batch of windows instead of the plain forward, (tokens, windows, h*w) -> logits (explain())."""
         vit = self.model.vit
         outs, starts = [], []
         with _eval_mode(self.model), torch.no_grad():
@@ -262,7 +275,8 @@ class VideoScorer:
                     hw = self._ring.shape[1]
                     x = ops.tokens_gather_fwd(self._ring, st.idx, vit.space_token, vit.temporal_token, vit.pos_embedding,
                                               pad=True)
-                    outs.append(vit.forward_tokens(x, st.count, self.T + 1, hw + 1))
+                    outs.append(vit.forward_tokens(x, st.count, self.T + 1, hw + 1) if rollout is None
+                                else rollout(x, st.count, hw))
                     starts.extend(st.starts)
         nc = vit.mlp_head[1].out_features
         logits = torch.cat(outs) if outs else torch.empty((0, nc), dtype=torch.float32, device=dev)
@@ -292,8 +306,8 @@ class VideoScorer:
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     # ---------------------------------------------------------------------------------------- whole video
-    def score(self, frames: Tensor) -> VideoScore:
-        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own)."""
+    def _whole_video(self, frames: Tensor, rollout=None):
+        """every window of one video on a ring of its own -> (logits, list of starts, device)"""
         kind = check_frames(frames)
         n = int(frames.shape[0])
         if n < self.T:
@@ -305,10 +319,40 @@ class VideoScorer:
                                   self.frame_batch, self.window_batch)
             self._ring = None
             steps = self._plan.push(n, drain=False) + self._plan.flush(self.cover_tail)
-            logits, starts = self._run(steps, frames, 0, kind, dev)
+            logits, starts = self._run(steps, frames, 0, kind, dev, rollout)
         finally:
             self._plan, self._ring, self._kind = saved
-        res = VideoScore(logits, torch.tensor(starts, dtype=torch.int64).to(dev, non_blocking=True), logits.mean(0),
-                         torch.sigmoid(logits).mean(0))
+        return logits, starts, dev
+
+    @staticmethod
+    def _video_score(logits: Tensor, starts: List[int], dev) -> VideoScore:
+        return VideoScore(logits, torch.tensor(starts, dtype=torch.int64).to(dev, non_blocking=True), logits.mean(0),
+                          torch.sigmoid(logits).mean(0))
+
+    def score(self, frames: Tensor) -> VideoScore:
+        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own)."""
+        logits, starts, dev = self._whole_video(frames)
+        res = self._video_score(logits, starts, dev)
+        torch.cuda.current_stream(dev).synchronize()
+        return res
+
+    def explain(self, frames: Tensor, index: int = 0) -> VideoExplanation:
+        """Relevance maps of one video for output `index` (DESIGN.md "Explaining whole videos"): the windows, frames and
+        stem pass of score(), every window batch through the gradient-weighted attention rollout of explain.relevance
+        instead of the plain forward, and the windows' maps fused per frame (ops.relevance_fuse_windows).  The model is in
+        explain.relevance's state for the call and comes back as it was; a stream in progress is not disturbed."""
+        from . import explain as _explain
+        vit = self.model.vit
+        rels = []
+
+        def rollout(x, count, hw):
+            rels.append(_explain._rollouts_tokens(vit, x, count, self.T + 1, hw + 1, index))
+            return rels[-1].logits
+
+        with _explain._explaining(self.model):
+            logits, starts, dev = self._whole_video(frames, rollout)
+            windows = _explain.Relevance(torch.cat([r.r_s for r in rels]), torch.cat([r.r_t for r in rels]), logits)
+            fused = ops.relevance_fuse_windows(windows.r_s, windows.r_t, logits, starts, int(frames.shape[0]), index)
+        res = VideoExplanation(self._video_score(logits, starts, dev), windows, *fused)
         torch.cuda.current_stream(dev).synchronize()
         return res

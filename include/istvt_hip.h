@@ -173,6 +173,21 @@ int istvt_attn_temporal_relevance(const void* qkv, long ldqkv, const void* dout,
 /* cam [maps][g][g] fp32 -> out [maps][g*s][g*s] fp32: bilinear upsampling (align_corners=False) by the integer factor s,
  * then (x - min) / (max - min) per map (visualize_rel.py:262-265).  g <= 64. */
 int istvt_relevance_heatmap(const float* cam, float* out, int maps, int g, int s, istvt_stream_t stream);
+/* Whole videos (DESIGN.md "Explaining whole videos"): the rollouts of W sliding windows, r_s [W][T+1][P], r_t [W][P][T+1],
+ * logits [W][nc], fused per frame.  starts int32 [W] on the device: first frame of every window, ascending, 0 <= s <= N - T
+ * (validated by the caller).  Window w covers frame n as its frame t = n - starts[w] when 0 <= t < T.  Per frame, the plain
+ * mean over the covering windows in ascending window order of r_s[w][t+1][1..] (frame_s [N][P-1]), r_t[w][1..][t+1]
+ * (frame_t [N][P-1]), r_t[w][0][t+1] (frame_weight [N]) and logits[w][index] (frame_logit [N]); count int32 [N] the number
+ * of covering windows, a frame without one gets zeros.  One writer per element, fixed order, no atomics. */
+int istvt_relevance_fuse_windows(const float* r_s, const float* r_t, const float* logits, const int* starts, float* frame_s,
+                                 float* frame_t, float* frame_weight, float* frame_logit, int* count, int W, int T, int P,
+                                 int nc, int index, int N, istvt_stream_t stream);
+/* The heat map on the frame (visualize_rel.py:39-44) for N frames: frames uint8 [N][S][S][3], maps fp32 [N][g][g], lut uint8
+ * [256][3] -> out uint8 [N][g*s][g*s][3].  m = istvt_relevance_heatmap's value, k = trunc(255 m) (k = 0 for a constant
+ * map), cam = lut[k] / 255 + frame / 255 (the frame sampled bilinearly with half-pixel centres when S != g*s),
+ * out = trunc(255 cam / max of cam over the frame).  ws: 4 floats of scratch per frame.  g <= 64, N <= 65535. */
+int istvt_relevance_overlay_u8(const void* frames, const float* maps, const void* lut, float* ws, void* out, int N, int S,
+                               int g, int s, istvt_stream_t stream);
 
 /* ---- token assembly (DSTTr.forward, vivit.py:133-142) -------------------------------------- */
 int istvt_tokens_fwd(const void* feats, const float* space, const float* temporal, const float* pos, void* x, long ldx,

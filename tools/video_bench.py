@@ -3,6 +3,7 @@
 
     python tools/video_bench.py [--frames 256] [--size 224] [--T 8] [--depth 12] [--strides 1,2,4,8] [--json out.json]
     python tools/video_bench.py --conv1-only        # the two conv1 kernels alone, for a kernel trace
+    python tools/video_bench.py --explain           # VideoScorer.explain against model.relevance on materialised windows
 
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
 float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
@@ -10,6 +11,13 @@ code path that exists without the scorer (its host-side normalisation and 4x lar
 Each repeat times (a) then (b), the device synchronised on both sides of each; the figures are medians over the repeats
 after the warm-up, with the min-max spread of both.  The split of (a) into stem / token assembly / transformer comes from
 ops.prof events in one further, instrumented run.
+
+--explain (DESIGN.md "Explaining whole videos"), strides 1 and 8 unless --strides says otherwise: (a) VideoScorer.explain
+on the device-resident uint8 video; (b) the loop a user writes without it: model.relevance on the windows gathered from the
+normalised float32 video, window_batch at a time (normalisation and upload again not charged; the fusion over windows,
+which that user would still have to write, is not part of (b) either).  Alternating, medians as above.  One further,
+instrumented explain() and one explain.overlay() of the whole video give the device time of the fuse and overlay kernels
+(events around the launches) and the overlay's rate against its algorithmic bytes.
 """
 import argparse
 import json
@@ -58,21 +66,77 @@ def conv1_only(a):
     print('conv1_only: %d launches each, max abs diff %.3e' % (a.reps + a.warmup, float((out.float() - ref.float()).abs().max())))
 
 
+def explain_bench(a, model, u8, xn):
+    from istvt_amd import explain
+    out = {}
+    for stride in [int(s) for s in a.strides.split(',')]:
+        scorer = video.VideoScorer(model, stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch)
+        starts = video.window_starts(a.frames, a.T, stride, True)
+        W = len(starts)
+        tab = (torch.tensor(starts).view(-1, 1) + torch.arange(a.T).view(1, -1)).cuda()
+        res = {}
+
+        def run_explain():
+            res['a'] = scorer.explain(u8)
+
+        def run_loop():
+            res['b'] = [model.relevance(xn[tab[i:i + a.window_batch]]) for i in range(0, W, a.window_batch)]
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_explain), timed(run_loop)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        cam = torch.cat([r.cam_s for r in res['b']]).double()
+        diff = float((res['a'].windows.cam_s.double() - cam).norm() / cam.norm())
+        ops.kernel_profile = []
+        try:
+            run_explain()
+            shown = explain.overlay(u8, res['a'].frame_s)
+            torch.cuda.synchronize()
+            kern = {}
+            for name, e0, e1, nbytes, flops in ops.kernel_profile:
+                if name in ('relevance_fuse_windows', 'relevance_overlay_u8'):
+                    d = kern.setdefault(name, {'ms': 0.0, 'bytes': 0})
+                    d['ms'] += e0.elapsed_time(e1)
+                    d['bytes'] += nbytes
+        finally:
+            ops.kernel_profile = None
+        sa, sb = stats(ta), stats(tb)
+        for d in kern.values():
+            d['GB_per_s'] = d['bytes'] / d['ms'] * 1e-6
+            d['share_of_explain'] = d['ms'] / sa['median_ms']
+        rec = {'windows': W, 'explain': sa, 'relevance_loop': sb, 'loop_over_explain': sb['median_ms'] / sa['median_ms'],
+               'explain_spread': (sa['max_ms'] - sa['min_ms']) / sa['median_ms'],
+               'loop_spread': (sb['max_ms'] - sb['min_ms']) / sb['median_ms'], 'cam_s_relerr': diff, 'kernels': kern,
+               'overlay_shape': list(shown.shape)}
+        out[str(stride)] = rec
+        print('explain stride %d: %d windows | explain %.1f ms (%.1f-%.1f) | model.relevance loop %.1f ms (%.1f-%.1f) | loop / '
+              'explain x%.3f | cam_s relerr %.2e' % (stride, W, sa['median_ms'], sa['min_ms'], sa['max_ms'], sb['median_ms'],
+                                                    sb['min_ms'], sb['max_ms'], rec['loop_over_explain'], diff), flush=True)
+        for k, d in kern.items():
+            print('          %s: %.3f ms on the device, %.1f GB/s of %.1f MB algorithmic, %.3f %% of one explain()'
+                  % (k, d['ms'], d['GB_per_s'], d['bytes'] * 1e-6, 100 * d['share_of_explain']), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--T', type=int, default=8)
     ap.add_argument('--depth', type=int, default=12)
-    ap.add_argument('--strides', default='1,2,4,8')
+    ap.add_argument('--strides', default=None)
     ap.add_argument('--frame-batch', type=int, default=64)
     ap.add_argument('--window-batch', type=int, default=32)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     ap.add_argument('--conv1-only', action='store_true')
+    ap.add_argument('--explain', action='store_true')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
+    a.strides = a.strides or ('1,8' if a.explain else '1,2,4,8')
     if not torch.cuda.is_available():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
@@ -86,6 +150,15 @@ def main():
     u8 = torch.randint(0, 256, (a.frames, a.size, a.size, 3), generator=g, dtype=torch.uint8)
     xn = (((u8.float() / 255) - torch.tensor(video.DEFAULT_MEAN)) / torch.tensor(video.DEFAULT_STD)).permute(0, 3, 1, 2).contiguous()
     u8, xn = u8.cuda(), xn.cuda()
+    if a.explain:
+        out = {'frames': a.frames, 'size': a.size, 'T': a.T, 'depth': a.depth, 'dtype': a.dtype, 'frame_batch': a.frame_batch,
+               'window_batch': a.window_batch, 'reps': a.reps, 'warmup': a.warmup, 'explain': explain_bench(a, model, u8, xn)}
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_explain_bench': {k: v['loop_over_explain'] for k, v in out['explain'].items()}}))
+        return
     out = {'frames': a.frames, 'size': a.size, 'T': a.T, 'depth': a.depth, 'dtype': a.dtype, 'frame_batch': a.frame_batch,
            'window_batch': a.window_batch, 'reps': a.reps, 'warmup': a.warmup, 'strides': {}}
     for stride in [int(s) for s in a.strides.split(',')]:
