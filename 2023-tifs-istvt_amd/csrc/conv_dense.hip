@@ -15,6 +15,8 @@
 // These maps are the largest of the network (111 x 111 x 32 and 109 x 109 x 64 per frame) and every pass over them is
 // HBM-bound; algorithmic bytes per frame at S = 224 (bf16): conv2 forward 0.79 MB in + 1.52 MB out.
 #include "common.h"
+#include "u8_view.h"
+#include <type_traits>
 
 namespace {
 
@@ -84,10 +86,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_u8(const uint8_t* __restrict__ 
     const long f = blockIdx.x / ngroups;
     const int y0 = grp * R;
     const int rows = min(R, Ho - y0);
-    for (int i = tid; i < 3 * 256; i += 256) {
-        const int c = i >> 8;
-        lut[i] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)(i & 255), 255.0f), mean[c]), stdv[c]);
-    }
+    u8_fill_lut(lut, mean, stdv, tid, 256);
     const long g0 = (f * S + 2 * y0) * (long)S * 3;               // first byte of input row 2 y0 of frame f
     const int len = (2 * rows + 1) * S * 3;                       // rows 2 y0 .. 2 (y0 + rows): 2 (Ho - 1) + 2 <= S - 1
     const uintptr_t base = reinterpret_cast<uintptr_t>(x);
@@ -121,6 +120,66 @@ __global__ __launch_bounds__(256) void conv1_fwd_u8(const uint8_t* __restrict__ 
                 for (int ci = 0; ci < 3; ++ci) v[ci * 9 + dy * 3 + dx] = lut[ci * 256 + row[dx * 3 + ci]];
         }
         const long m = (f * Ho + y0) * (long)Ho + o;
+        int w0 = 0;
+        asm volatile("" : "+s"(w0));                     // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
+        const float* wl = w + w0;
+#pragma unroll
+        for (int c8 = 0; c8 < 4; ++c8) {
+            float acc[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float* wc = wl + (c8 * 8 + j) * 27;    // uniform address: scalar loads
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < 27; ++k) a = fmaf(wc[k], v[k], a);
+                acc[j] = a;
+            }
+            store8(u1 + m * 32 + c8 * 8, acc);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ conv1 forward from a view
+// The training entry of conv1: the S x S view (crop window + horizontal flip, u8_view.h) of a larger decoded frame, uint8
+// [frames][Hs][Ws][3].  Work item = (frame, R output rows) as in conv1_fwd_u8; with a crop its 2R + 1 input rows are no
+// longer one contiguous range, so they are staged row by row (u8_stage_rows), and a flipped view looks its pixels up
+// mirrored.  The 27 x 32 multiply-adds run in conv1_fwd_kernel's order on the same float values: bit-identical to
+// conv1_fwd_kernel on the float32 NCHW tensor the host makes of the view.
+template <typename T>
+__global__ __launch_bounds__(256) void conv1_fwd_u8_view(const uint8_t* __restrict__ x, const int* __restrict__ view,
+                                                         const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                         const float* __restrict__ w, T* __restrict__ u1, long total,
+                                                         int Hs, int Ws, int S, int Ho, int R, int ngroups) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    float* lut = reinterpret_cast<float*>(smem);                  // [3][256]
+    unsigned char* sb = smem + 3 * 256 * sizeof(float);           // staged rows, pitch bytes each
+    const int tid = threadIdx.x;
+    const int grp = (int)(blockIdx.x % ngroups);
+    const long f = blockIdx.x / ngroups;
+    const int yb = grp * R;
+    const int rows = min(R, Ho - yb);
+    const U8View vw = u8_view_of(view, f, Hs, Ws, S);
+    u8_fill_lut(lut, mean, stdv, tid, 256);
+    const int pitch = u8_row_pitch(S), rstride = Ws * 3;
+    const long g0 = ((f * Hs + vw.y0 + 2 * yb) * (long)Ws + vw.x0) * 3;     // view row 2 yb of frame f
+    const int lead0 = u8_stage_rows(x, total, g0, rstride, 2 * rows + 1, S, sb, pitch, tid, 256);
+    __syncthreads();
+    const int nout = rows * Ho;
+    for (int o = tid; o < nout; o += 256) {
+        const int yl = o / Ho, xo = o - yl * Ho;
+        float v[27];                                     // [ci][dy][dx]: the order of conv1.weight[co]
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const int rr = 2 * yl + dy;
+            const unsigned char* row = sb + rr * pitch + u8_row_lead(lead0, rr, rstride);
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const unsigned char* px = row + u8_view_px(2 * xo + dx, S, vw.flip);
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci) v[ci * 9 + dy * 3 + dx] = lut[ci * 256 + px[ci]];
+            }
+        }
+        const long m = (f * Ho + yb) * (long)Ho + o;
         int w0 = 0;
         asm volatile("" : "+s"(w0));                     // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
         const float* wl = w + w0;
@@ -505,6 +564,109 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const TD* __restrict__
     for (int i = 0; i < 4; ++i) out[(16 * mt + 4 * g + i) * 32 + 16 * nt + r] = acc[i];
 }
 
+// ------------------------------------------------------------------------------------------ conv1 weight gradient from bytes
+// conv1_wgrad_kernel with the patches gathered from a view of the decoded frames (u8_view.h) instead of the fp32 clip:
+// the same chunks (one output row), grid and row walk, the same bf16 rounding of du1 and of the patches, the same four
+// k-steps and slabs -- the float values the patches are rounded from are the table's, i.e. the host-made tensor's, so dW1
+// has conv1_wgrad_kernel's bits.  The three source rows of a chunk (at most 258 pixels of them: Wo <= 128) travel as
+// bytes: prefetched into registers one 16-byte piece per thread while the previous chunk is in the MFMAs, stored to LDS,
+// and each patch thread looks its 16 values up there: three runs of 9 contiguous bytes per pixel (descending pixels when
+// the view is flipped) instead of 27 scattered NCHW loads.
+constexpr int C1B_MAXS = 2 * C1_PX + 2;                      // largest S with Ho <= C1_PX
+constexpr int C1B_CPR = (C1B_MAXS * 3 + 30) >> 4;            // 16-byte pieces of a staged row (u8_row_pitch)
+constexpr int C1B_PITCH = C1B_CPR * 16;
+static_assert(3 * C1B_CPR <= 256, "one 16-byte piece per thread");
+
+template <typename TD>
+__global__ __launch_bounds__(256) void conv1_wgrad_u8_kernel(const TD* __restrict__ du1, const uint8_t* __restrict__ x,
+                                                             const int* __restrict__ view, const float* __restrict__ mean,
+                                                             const float* __restrict__ stdv, float* __restrict__ slabs,
+                                                             long total, int Hs, int Ws, int S, int Ho, int Wo, int nrows) {
+    __shared__ __attribute__((aligned(16))) char dimg[C1_PX * C1_PITCH];
+    __shared__ __attribute__((aligned(16))) char pimg[C1_PX * C1_PITCH];
+    __shared__ __attribute__((aligned(16))) unsigned char sb[3 * C1B_PITCH];
+    __shared__ float lut[3 * 256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int mt = wave >> 1, nt = wave & 1;
+    const int ppx = tid & (C1_PX - 1), pk0 = (tid >> 7) * 16;    // patch role: pixel, first of 16 k (the same in a wavefront)
+    const int brow = tid / C1B_CPR, bc = tid - brow * C1B_CPR;   // byte role: source row of the chunk, 16-byte piece
+    const int rstride = Ws * 3, len = S * 3;
+    u8_fill_lut(lut, mean, stdv, tid, 256);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 dreg[2];
+    uint4 breg = make_uint4(0u, 0u, 0u, 0u);
+    int lead0 = 0, flip = 0, lead0n = 0, flipn = 0;          // of the chunk in LDS / of the prefetched one
+    auto gload = [&](int row) {
+        const int yo = row % Ho;
+        const long f = row / Ho;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {                        // 128 px x 4 pieces of 8 channels
+            const int i = tid + 256 * k;
+            const int px = i >> 2, pc = i & 3;
+            dreg[k] = zero_frag();
+            if (px < Wo) {
+                float v[8];
+                load8(du1 + ((f * Ho + yo) * Wo + px) * 32 + pc * 8, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) dreg[k][j] = (bf16_t)v[j];
+            }
+        }
+        const U8View vw = u8_view_of(view, f, Hs, Ws, S);
+        const long g0 = ((f * Hs + vw.y0 + 2 * yo) * (long)Ws + vw.x0) * 3;
+        lead0n = (int)((reinterpret_cast<uintptr_t>(x) + (uintptr_t)g0) & 15);
+        flipn = vw.flip;
+        if (brow < 3) {
+            const int lead = u8_row_lead(lead0n, brow, rstride);
+            if (16 * bc < lead + len) breg = u8_load16(x, g0 + (long)brow * rstride - lead + 16L * bc, total);
+        }
+    };
+    // the 16 patch values k = K0 .. K0 + 15 of pixel ppx: k = (ci, dy, dx) is known at compile time
+    auto patch = [&](auto k0) {
+        constexpr int K0 = decltype(k0)::value;
+        int rowoff[3], pxoff[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            rowoff[d] = d * C1B_PITCH + u8_row_lead(lead0, d, rstride);
+            pxoff[d] = u8_view_px(2 * ppx + d, S, flip);
+        }
+        bf16x8 p[2];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int k = K0 + j;
+            const int ci = k / 9, dy = (k % 9) / 3, dx = k % 3;
+            float v = 0.f;
+            if (k < 27 && ppx < Wo) v = lut[ci * 256 + sb[rowoff[dy] + pxoff[dx] + ci]];
+            p[j >> 3][j & 7] = (bf16_t)v;
+        }
+        *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + K0 * 2) = p[0];
+        *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + K0 * 2 + 16) = p[1];
+    };
+    int row = blockIdx.x;
+    if (row < nrows) gload(row);
+    for (; row < nrows; row += gridDim.x) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int i = tid + 256 * k;
+            *reinterpret_cast<bf16x8*>(dimg + (i >> 2) * C1_PITCH + (i & 3) * 16) = dreg[k];
+        }
+        if (brow < 3) *reinterpret_cast<uint4*>(sb + brow * C1B_PITCH + 16 * bc) = breg;
+        lead0 = lead0n, flip = flipn;
+        __syncthreads();
+        if (pk0 == 0) patch(std::integral_constant<int, 0>()); else patch(std::integral_constant<int, 16>());
+        if (row + (int)gridDim.x < nrows) gload(row + gridDim.x);
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < C1_PX / 32; ++ks)
+            acc = mma16(tr_frag(dimg, C1_PITCH, 32 * ks + 8 * g, 16 * mt, r),
+                        tr_frag(pimg, C1_PITCH, 32 * ks + 8 * g, 16 * nt, r), acc);
+        __syncthreads();
+    }
+    float* out = slabs + (long)blockIdx.x * 32 * 32;         // rows co = 16 mt + 4g + i, column k = 16 nt + r
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[(16 * mt + 4 * g + i) * 32 + 16 * nt + r] = acc[i];
+}
+
 inline int wave_grid(int ngroups, int per_cu) {
     const int need = (ngroups + 3) / 4;
     const int cap = 256 * per_cu;
@@ -544,6 +706,41 @@ extern "C" int istvt_conv1_fwd_u8(const void* x, const float* mean, const float*
     const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * S * 3 + 32;
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_u8<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
                                              (const uint8_t*)x, mean, stdv, w, (T*)u1, total, S, Ho, R, ngroups));
+    return istvt_check_launch();
+}
+
+// Common argument check of the entry points that read a view of decoded frames (u8_view.h)
+static inline bool u8_view_args_ok(const void* x, long total, int Hs, int Ws, const float* mean, const float* stdv, int Fr,
+                                   int S) {
+    if (Fr <= 0 || S < 3 || !x || !mean || !stdv) return false;
+    if (Hs < S || Ws < S || Hs > 16384 || Ws > 16384) return false;
+    return total >= (long)Fr * Hs * Ws * 3;
+}
+
+// conv1 forward from a view of decoded frames: x uint8 [frames][Hs][Ws][3] (total bytes readable at x), view int32
+// [frames][3] = (y0, x0, flip) on the device or null, crop side S -> the u1 istvt_conv1_fwd gives on the float tensor
+// of the view
+extern "C" int istvt_conv1_fwd_u8_view(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
+                                       const float* stdv, const float* w, void* u1, int Fr, int S, int dtype,
+                                       hipStream_t stream) {
+    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || S > 4096 || !w || !u1) return ISTVT_ERR_SHAPE;
+    const int Ho = (S - 3) / 2 + 1;
+    const int pitch = u8_row_pitch(S);
+    // R output rows per workgroup as istvt_conv1_fwd_u8 chooses them (2R + 1 staged rows, at most 48 KiB)
+    int R = 1;
+    double best = 0.0;
+    for (int r = 1; r <= 16 && r <= Ho; ++r) {
+        if ((2L * r + 1) * pitch > 48 * 1024) break;
+        const double eff = r < 4 ? 0.0 : (double)(r * Ho) / (double)(((r * Ho + 255) / 256) * 256);
+        if (r < 4 || eff > best + 1e-9) best = eff, R = r;
+    }
+    const int ngroups = (Ho + R - 1) / R;
+    const long nblocks = (long)Fr * ngroups;
+    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * pitch;
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_u8_view<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
+                                             (const uint8_t*)x, view, mean, stdv, w, (T*)u1, total, Hs, Ws, S, Ho, R,
+                                             ngroups));
     return istvt_check_launch();
 }
 
@@ -610,6 +807,26 @@ extern "C" int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, 
     const int grid = nrows < cap ? (int)nrows : cap;
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1, x,
                                              slabs, S, Ho, Ho, (int)nrows));
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    return istvt_rows_reduce_add(slabs, grid, 1, 1024, dw, nullptr, nullptr, stream);
+}
+
+// conv1 weight gradient from a view of decoded frames (source and view as istvt_conv1_fwd_u8_view): dw float [32][32] +=
+// with istvt_conv1_wgrad's bits on the float tensor of the view; same slabs workspace, same limit (Ho <= 128)
+extern "C" int istvt_conv1_wgrad_u8(const void* du1, const void* x, long total, int Hs, int Ws, const int* view,
+                                    const float* mean, const float* stdv, float* slabs, float* dw, int Fr, int S, int dtype,
+                                    hipStream_t stream) {
+    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || !du1 || !slabs || !dw) return ISTVT_ERR_SHAPE;
+    const int Ho = (S - 3) / 2 + 1;
+    if (Ho > C1_PX) return ISTVT_ERR_SHAPE;
+    const long nrows = (long)Fr * Ho;
+    if (nrows > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const int cap = istvt_conv1_wgrad_slabs();
+    const int grid = nrows < cap ? (int)nrows : cap;
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_u8_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1,
+                                             (const uint8_t*)x, view, mean, stdv, slabs, total, Hs, Ws, S, Ho, Ho,
+                                             (int)nrows));
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     return istvt_rows_reduce_add(slabs, grid, 1, 1024, dw, nullptr, nullptr, stream);

@@ -159,6 +159,8 @@ class XceptionVidTr(nn.Module):
         self.compute_dtype = compute_dtype
         self.set_attn_fp8(attn_fp8)
         self._step_graphs = None
+        self.set_input_normalisation()
+        self.set_crop_side(300 if grid == 19 else None)
         if os.environ.get('ISTVT_STEP_GRAPHS', '0') == '1':
             self.enable_step_graphs(True)
 
@@ -170,6 +172,27 @@ class XceptionVidTr(nn.Module):
             if isinstance(m, SpatialOnlyAttention):
                 m.attn_fp8 = bool(on)
         return self
+
+    def set_input_normalisation(self, mean=None, std=None):
+        """Per-channel mean / std that uint8 clips are normalised by inside conv1 (``model(u8, view=...)``): 3 values each,
+        default the reference's preprocessing (video.DEFAULT_MEAN / DEFAULT_STD).  Float input is taken as normalised."""
+        from istvt_amd import video
+        mean = tuple(float(v) for v in (video.DEFAULT_MEAN if mean is None else mean))
+        std = tuple(float(v) for v in (video.DEFAULT_STD if std is None else std))
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError('mean and std must have 3 values (one per channel), got %d and %d' % (len(mean), len(std)))
+        if any(v == 0 for v in std):
+            raise ValueError('std must be non-zero')
+        self._input_norm = (mean, std)
+        self._input_norm_dev = {}           # device -> (mean, std) float32 [3] tensors
+        return self
+
+    def _input_norm_on(self, device):
+        got = self._input_norm_dev.get(device)
+        if got is None:
+            got = tuple(torch.tensor(v, dtype=torch.float32, device=device) for v in self._input_norm)
+            self._input_norm_dev[device] = got
+        return got
 
     def set_compute_dtype(self, dtype):
         self.compute_dtype = dtype
@@ -193,7 +216,19 @@ class XceptionVidTr(nn.Module):
             self._step_graphs = None
         return self
 
-    def forward(self, x):
+    def forward(self, x, view=None, crop=None):
+        """x float32 (b, t, 3, S, S), already normalised: the reference's call.  x uint8 (b, t, Hs, Ws, 3), the clips as
+        decoded (istvt_amd.clips): conv1 normalises the bytes (set_input_normalisation) and reads them through `view`,
+        int32 (b, 3) = one (y0, x0, flip) per clip shared by its t frames -- a host tensor, validated before any launch --,
+        with crop side `crop` (default: the side the model's token grid stands for).  Without a view the frames must
+        already be crop-sized.  A uint8 step runs launch by launch also with step graphs on."""
+        if x.dtype == torch.uint8:
+            g = self._step_graphs
+            if g is not None:
+                g.note_eager('uint8 input: the byte path is not captured')
+            return self._forward_eager(x, view, crop)
+        if view is not None or crop is not None:
+            raise RuntimeError('view / crop apply to uint8 clips; float input is taken as already cropped and normalised')
         g = self._step_graphs
         if g is not None:
             return g(x)
@@ -216,8 +251,36 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import video
         return video.VideoScorer(self, **kw).explain(frames, index)
 
-    def _forward_eager(self, x):
+    def set_crop_side(self, S):
+        """The side S of the crops a view cuts out of larger uint8 source frames.  A token grid does not name it (sixteen
+        input sides end at the same grid), so it is a setting: 300 for the reference's 19 x 19 grid, otherwise to be
+        given here or per call (``model(u8, view=view, crop=S)``)."""
+        self.crop_side = None if S is None else int(S)
+        return self
+
+    def _crop_side(self):
+        if self.crop_side is None:
+            raise ValueError('a view needs the crop side: model(x, view=view, crop=S) or model.set_crop_side(S)')
+        return self.crop_side
+
+    def _forward_eager(self, x, view=None, crop=None):
         b, t = x.shape[:2]
+        if x.dtype == torch.uint8:
+            from istvt_amd import clips
+            ops._req(x, 'input clip')
+            if x.dim() != 5 or x.shape[4] != 3:
+                raise RuntimeError('uint8 clips must be channels-last (b, t, Hs, Ws, 3), got %s' % (tuple(x.shape),))
+            Hs, Ws = x.shape[2], x.shape[3]
+            if crop is None:
+                crop = self._crop_side() if view is not None else Hs
+            v = clips.check_views(view, b, Hs, Ws, crop)
+            if v is not None:               # one small upload, expanded to the per-frame table on the device
+                v = clips.per_frame_views(v.contiguous().to(x.device, non_blocking=True), t)
+            mean, std = self._input_norm_on(x.device)
+            feats = self.xcep.model.low_level_features_nhwc(x.flatten(0, 1), self.compute_dtype, mean, std,
+                                                            train_bytes=True, view=v, crop=crop)
+            n, h, w, c = feats.shape
+            return self.vit.forward_features(feats.view(b, t, h * w, c))
         feats = self.xcep.model.low_level_features_nhwc(x.flatten(0, 1), self.compute_dtype)   # (b*t, h, w, c)
         n, h, w, c = feats.shape
         return self.vit.forward_features(feats.view(b, t, h * w, c))

@@ -140,11 +140,14 @@ class Xception(nn.Module):
         self.fc = nn.Linear(2048, num_classes)
         self.compute_dtype = torch.float32
 
-    def low_level_features_nhwc(self, input, dtype=None, mean=None, std=None, inference=False):
+    def low_level_features_nhwc(self, input, dtype=None, mean=None, std=None, inference=False, train_bytes=False,
+                                view=None, crop=None):
         """(n,3,S,S) float32 -> (n,h,w,728) channels-last features in the compute dtype.  Inference entry (eval mode under
         torch.no_grad() only): decoded frames, uint8 (n,S,S,3), with the per-channel mean / std that conv1 normalises
-        them by; inference=True sends float input through the same entry (stem.stem_forward)."""
-        return _stem.stem_forward(input, self, dtype or self.compute_dtype, mean, std, inference)
+        them by; inference=True sends float input through the same entry (stem.stem_forward).  Training byte entry
+        (train_bytes=True, any mode): uint8 (n,Hs,Ws,3) source frames with mean / std, read through view (int32 (n,3) =
+        (y0, x0, flip) per frame) with crop side `crop` (istvt_amd.clips)."""
+        return _stem.stem_forward(input, self, dtype or self.compute_dtype, mean, std, inference, train_bytes, view, crop)
 
     def low_level_features(self, input):
         """Reference signature (xception.py:193-206): (n,3,S,S) -> (n,728,h,w)."""

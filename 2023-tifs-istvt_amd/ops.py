@@ -775,6 +775,89 @@ def conv1_fwd_u8(frames: Tensor, mean: Tensor, std: Tensor, weight: Tensor, dtyp
     return u1
 
 
+def _u8_source(what: str, src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, dtype, checked: bool):
+    """Arguments common to the kernels that read a view of decoded frames: src uint8 [Fr,Hs,Ws,3], view int32 [Fr,3] =
+    (y0, x0, flip) or None, crop side S (None: the frames' own side).  A view is validated on the host (clips.check_views)
+    before any launch and then uploaded; checked=True takes a device table the caller has validated already (the stem:
+    one table, checked once, read by the forward and the backward).  -> (src, Fr, Hs, Ws, S, device table or None)"""
+    from . import clips
+    _req(src, 'frames')
+    if src.dtype != torch.uint8:
+        raise TypeError('%s: frames must be uint8, got %s' % (what, src.dtype))
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise RuntimeError('%s expects channels-last (frames, Hs, Ws, 3) uint8 input, got %s' % (what, tuple(src.shape)))
+    if dtype not in _DT:
+        raise TypeError('istvt_amd supports float32 and bfloat16 activations, got %s' % dtype)
+    for t, n in ((mean, 'mean'), (std, 'std')):
+        if t.dtype != torch.float32 or t.numel() != 3 or t.device != src.device:
+            raise RuntimeError('%s: %s must be 3 float32 values on %s' % (what, n, src.device))
+    Fr, Hs, Ws = src.shape[0], src.shape[1], src.shape[2]
+    if Fr == 0:
+        raise RuntimeError('%s: empty input %s' % (what, tuple(src.shape)))
+    if checked:
+        if S is None or S < 3 or S > min(Hs, Ws) or (view is None and (Hs != S or Ws != S)):
+            raise ValueError('%s: crop side %r does not fit %d x %d frames' % (what, S, Hs, Ws))
+        if view is not None and (view.dtype != torch.int32 or tuple(view.shape) != (Fr, 3) or view.device != src.device):
+            raise RuntimeError('%s: a checked view table is int32 (%d, 3) on %s' % (what, Fr, src.device))
+        vdev = None if view is None else _c(view)
+    else:
+        v = clips.check_views(view, Fr, Hs, Ws, S)
+        S = Hs if S is None else S
+        vdev = None if v is None else v.contiguous().to(src.device)
+    return _c(src), Fr, Hs, Ws, S, vdev
+
+
+def conv1_fwd_u8_view(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, weight: Tensor, dtype: torch.dtype,
+                      checked: bool = False) -> Tensor:
+    """conv1 from a view of decoded frames (clips.py): src uint8 [Fr,Hs,Ws,3], view int32 [Fr,3] or None, crop side S ->
+    u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to istvt_conv1_fwd on clips.to_float(src, mean, std, view, S) made on the
+    host."""
+    src, Fr, Hs, Ws, S, vdev = _u8_source('conv1_fwd_u8_view', src, view, S, mean, std, dtype, checked)
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (32, 3, 3, 3) or weight.device != src.device:
+        raise RuntimeError('conv1_fwd_u8_view: weight must be conv1.weight, float32 (32, 3, 3, 3) on %s' % src.device)
+    Ho = (S - 3) // 2 + 1
+    u1 = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=src.device)
+    with prof('conv1_fwd_u8_view', Fr * S * S * 3 + u1.numel() * u1.element_size(), 2.0 * 27 * u1.numel()):
+        _lib.check(_lib.lib().istvt_conv1_fwd_u8_view(src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev), _c(mean).data_ptr(),
+                                                      _c(std).data_ptr(), _c(weight.detach()).data_ptr(), u1.data_ptr(),
+                                                      Fr, S, _DT[dtype], _stream()), 'istvt_conv1_fwd_u8_view')
+    return u1
+
+
+def conv1_wgrad_u8(du1: Tensor, src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor,
+                   checked: bool = False) -> Tensor:
+    """conv1's weight gradient from a view of decoded frames: du1 [Fr*Ho*Ho, 32] (float32 or bfloat16), source and view as
+    conv1_fwd_u8_view -> dW float32 [32, 32], column k = ci*9 + dy*3 + dx (27..31 zero), bit-identical to
+    istvt_conv1_wgrad on clips.to_float(...).  Needs Ho <= 128 (S <= 258), as the float kernel."""
+    src, Fr, Hs, Ws, S, vdev = _u8_source('conv1_wgrad_u8', src, view, S, mean, std, du1.dtype, checked)
+    Ho = (S - 3) // 2 + 1
+    if du1.device != src.device or du1.dim() != 2 or tuple(du1.shape) != (Fr * Ho * Ho, 32):
+        raise RuntimeError('conv1_wgrad_u8: du1 must be (%d, 32) on %s, got %s' % (Fr * Ho * Ho, src.device, tuple(du1.shape)))
+    du1 = _c(du1)
+    L = _lib.lib()
+    dW = torch.zeros((32, 32), dtype=torch.float32, device=src.device)
+    slabs = torch.empty((L.istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=src.device)
+    with prof('conv1_wgrad_u8', du1.numel() * du1.element_size() + Fr * S * S * 3, 2.0 * 32 * du1.numel()):
+        _lib.check(L.istvt_conv1_wgrad_u8(du1.data_ptr(), src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev),
+                                          _c(mean).data_ptr(), _c(std).data_ptr(), slabs.data_ptr(), dW.data_ptr(), Fr, S,
+                                          _DT[du1.dtype], _stream()), 'istvt_conv1_wgrad_u8')
+    return dW
+
+
+def im2col_conv1_u8(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, dtype: torch.dtype,
+                    checked: bool = False) -> Tensor:
+    """conv1's im2col from a view of decoded frames -> col [Fr*Ho*Ho, 32] in `dtype` ((dy,dx,ci) + 5 zero columns),
+    bit-identical to istvt_im2col_conv1 on clips.to_float(...)."""
+    src, Fr, Hs, Ws, S, vdev = _u8_source('im2col_conv1_u8', src, view, S, mean, std, dtype, checked)
+    Ho = (S - 3) // 2 + 1
+    col = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=src.device)
+    with prof('im2col_conv1_u8', Fr * S * S * 3 + col.numel() * col.element_size()):
+        _lib.check(_lib.lib().istvt_im2col_conv1_u8(src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev), _c(mean).data_ptr(),
+                                                    _c(std).data_ptr(), col.data_ptr(), Fr, S, _DT[dtype], _stream()),
+                   'istvt_im2col_conv1_u8')
+    return col
+
+
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,
                need_dfeats: bool) -> Optional[Tensor]:
     dx, lddx = rows(_req(dx))

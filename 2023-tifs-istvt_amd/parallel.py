@@ -524,6 +524,11 @@ class StepGraphs:
     def forward_eager(self, x):
         return self._fwd()(x)
 
+    def note_eager(self, reason: str):
+        """a call the model runs launch by launch without asking (an input kind no graph is captured for)"""
+        self.last_reason = reason
+        self.stats['eager'] += 1
+
     def _config(self, m):
         from . import functional as Fn
         if m is None:

@@ -251,15 +251,25 @@ class StemFn(Function):
     when training).  `infer`: None, or the inference entry's (mean, std): x is then either decoded
     frames, uint8 (Fr,S,S,3) normalised inside conv1 with the float32 [3] device tensors mean / std,
     or the float clip with (None, None); conv1 runs as the direct kernel in both compute dtypes (so
-    the two kinds of input agree bit for bit) and there is no backward."""
+    the two kinds of input agree bit for bit) and there is no backward.  `bytesrc`: None, or the training byte
+    entry's (mean, std, view, S): x is uint8 (Fr,Hs,Ws,3) source frames read through the validated device table view
+    (int32 (Fr,3) or None) with crop side S; conv1 takes the routes of the float path (direct kernels in bfloat16,
+    im2col + GEMM in float32 and for the weight gradient when Ho > 128) through the byte kernels, the bytes and the
+    table are what the backward keeps, and there is no input gradient."""
 
     @staticmethod
-    def forward(ctx, x, dtype, training, buffers, infer, *params):
+    def forward(ctx, x, dtype, training, buffers, infer, bytesrc, *params):
         _req(x, 'input clip')
         if infer is not None and training:          # (stem_forward also refuses it with gradients enabled)
             raise RuntimeError('the stem\'s inference entry needs eval mode: it has no backward')
         u8 = x.dtype == torch.uint8
-        if u8:
+        if bytesrc is not None:
+            if not u8 or x.dim() != 4 or x.shape[3] != 3:
+                raise RuntimeError('the stem\'s byte entry expects channels-last (frames, Hs, Ws, 3) uint8 input, got %s %s'
+                                   % (x.dtype, tuple(x.shape)))
+            x = _c(x)
+            Fr, S = x.shape[0], bytesrc[3]
+        elif u8:
             if infer is None or infer[0] is None:
                 raise RuntimeError('uint8 frames need mean and std (Xception.low_level_features_nhwc(x, dtype, mean, std))')
             if x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
@@ -296,7 +306,15 @@ class StemFn(Function):
         M1 = Fr * H1 * H1
         # conv1 directly from the fp32 NCHW clip (one thread per output pixel); w1 is the GEMM form for the backward
         w1 = _conv1_weight(P['conv1.weight'], dtype)
-        if u8:
+        if bytesrc is not None:
+            bmean, bstd, bview = bytesrc[0], bytesrc[1], bytesrc[2]
+            if dtype == torch.bfloat16:
+                u1 = ops.conv1_fwd_u8_view(x, bview, S, bmean, bstd, P['conv1.weight'], dtype, checked=True)
+            else:                           # fp32 parity mode: im2col + GEMM, as the float path below
+                col1 = ops.im2col_conv1_u8(x, bview, S, bmean, bstd, dtype, checked=True)
+                u1 = ops.linear_fwd(col1, w1, blocked=False)
+                del col1
+        elif u8:
             u1 = ops.conv1_fwd_u8(x, infer[0], infer[1], P['conv1.weight'], dtype)
         elif dtype == torch.bfloat16 or infer is not None:
             u1 = torch.empty((M1, 32), dtype=dtype, device=dev)
@@ -329,7 +347,7 @@ class StemFn(Function):
         # block1's first depthwise convolution applies bn2 + ReLU as it stages its input tile -- rounded to the storage type
         # there, exactly where the separate pass rounded it --, its weight gradient takes the same pair on load, and the
         # stride-2 skip path applies them to the quarter of the pixels it keeps.
-        sv.update(x=x, S=S, Fr=Fr, H1=H1, H2=H2, u1=u1, bn1=bn1, u2=u2, bn2=bn2, w1=w1, w2=w2)
+        sv.update(x=x, bytesrc=bytesrc, S=S, Fr=Fr, H1=H1, H2=H2, u1=u1, bn1=bn1, u2=u2, bn2=bn2, w1=w1, w2=w2)
 
         fuse_in = os.environ.get('ISTVT_STEM_MATERIALISE_A2', '0') != '1'     # (1: the separate bn_apply pass, for A/B runs)
         X, H = (u2 if fuse_in else bn_apply(u2, bn2, M2, 64, True)), H2
@@ -370,7 +388,7 @@ class StemFn(Function):
         sv['training'] = training
         sv['dtype'] = dtype
         ctx.sv = sv
-        ctx.need_dx = x.requires_grad
+        ctx.need_dx = x.requires_grad and bytesrc is None
         return X.view(Fr, H, H, 728)
 
     @staticmethod
@@ -517,7 +535,16 @@ class StemFn(Function):
             grads['conv2.weight'] = dW2 if dtype == torch.bfloat16 else dW2.view(64, 3, 3, 32).permute(0, 3, 1, 2).contiguous()
         du1 = bn_bwd(dz1, sv['u1'], sv['bn1'], 'bn1', M1, 32)
         del dz1
-        if dtype == torch.bfloat16 and H1 <= 128:
+        bsrc = sv['bytesrc']
+        if bsrc is not None and dtype == torch.bfloat16 and H1 <= 128:
+            dW1 = ops.conv1_wgrad_u8(du1.contiguous(), sv['x'], bsrc[2], S, bsrc[0], bsrc[1], checked=True)
+            grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).contiguous()
+        elif bsrc is not None:
+            col1 = ops.im2col_conv1_u8(sv['x'], bsrc[2], S, bsrc[0], bsrc[1], dtype, checked=True)
+            dW1 = ops.linear_wgrad(du1, col1)                                    # [32][(dy,dx,ci) + 5 zero columns]
+            grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+            del col1
+        elif dtype == torch.bfloat16 and H1 <= 128:
             du1 = du1.contiguous()
             dW1 = torch.zeros((32, 32), dtype=torch.float32, device=du1.device)      # [co][(ci,dy,dx) + 5 unused]
             slabs = torch.empty((L.istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=du1.device)
@@ -547,7 +574,7 @@ class StemFn(Function):
                 q.grad.add_(grads[n].view(q.shape))
                 grads[n] = None
         out = [None if grads[n] is None else grads[n].view(P[n].shape) for n in param_names()]
-        return (dx, None, None, None, None, *out)
+        return (dx, None, None, None, None, None, *out)
 
 
 def _norm_vec(v, name: str, device) -> Tensor:
@@ -562,15 +589,50 @@ def _norm_vec(v, name: str, device) -> Tensor:
     return t.to(device)
 
 
-def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None, std=None, inference: bool = False) -> Tensor:
+def byte_source(x: Tensor, mean, std, view, crop):
+    """StemFn's `bytesrc` for uint8 (frames, Hs, Ws, 3) on the device: (mean, std, view table on the device or None, S).
+    A host view is validated (clips.check_views) and uploaded; a device view is taken as validated by the caller."""
+    from . import clips
+    Fr, Hs, Ws = x.shape[0], x.shape[1], x.shape[2]
+    if view is not None and torch.is_tensor(view) and view.is_cuda:
+        if crop is None:
+            raise ValueError('a view needs the crop side S')
+        vdev = view
+    else:
+        v = clips.check_views(view, Fr, Hs, Ws, crop)
+        vdev = None if v is None else v.contiguous().to(x.device, non_blocking=True)
+    S = Hs if crop is None else int(crop)
+    return (_norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device), vdev, S)
+
+
+def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None, std=None, inference: bool = False,
+                 train_bytes: bool = False, view=None, crop=None) -> Tensor:
     """Run the HIP stem with the parameters/buffers of an ``Xception`` module (network/xception.py).
 
     x float32 (frames, 3, S, S): the training / evaluation path.  x uint8 (frames, S, S, 3) with mean and std (3 values
     each): the inference entry, conv1 normalises the bytes itself (istvt_conv1_fwd_u8); it needs eval mode and
     torch.no_grad().  inference=True puts float input through the same entry (the direct conv1 kernel in either compute
-    dtype), which is what makes byte and float input of one video agree bit for bit (video.VideoScorer)."""
-    infer = None
-    if x.dtype == torch.uint8:
+    dtype), which is what makes byte and float input of one video agree bit for bit (video.VideoScorer).
+
+    train_bytes=True: the training byte entry (clips.py), in train or eval mode, with or without gradients.  x uint8
+    (frames, Hs, Ws, 3) with mean and std; view: int32 (frames, 3) = (y0, x0, flip) per frame, a host tensor (validated
+    here, before any launch) or None; crop: the side S of the view (default: the frames' own side, which then must be
+    square).  conv1 and its weight gradient read the bytes through the view, with the bits of the float path on
+    clips.to_float(x, mean, std, view, crop) made on the host; there is no input gradient."""
+    infer = bytesrc = None
+    if train_bytes:
+        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+            raise RuntimeError('train_bytes expects channels-last (frames, Hs, Ws, 3) uint8 input, got %s %s'
+                               % (x.dtype, tuple(x.shape)))
+        if mean is None or std is None:
+            raise RuntimeError('uint8 frames need mean and std (3 values each)')
+        if inference:
+            raise RuntimeError('train_bytes and inference are two different entries')
+        _req(x, 'input clip')
+        bytesrc = byte_source(x, mean, std, view, crop)
+    elif view is not None or crop is not None:
+        raise RuntimeError('view / crop belong to the training byte entry (train_bytes=True)')
+    elif x.dtype == torch.uint8:
         if mean is None or std is None:
             raise RuntimeError('uint8 frames need mean and std (3 values each)')
         infer = (_norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device))
@@ -602,7 +664,7 @@ def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None
     if x.is_cuda:
         stats_arena_reset(x.device)          # one fill for every statistics accumulator of this step
         ops.refresh_stale_operands()         # one grouped cast for every bf16 weight operand the optimizer invalidated
-    y = StemFn.apply(x, dtype, xcep.training, buffers, infer, *params)
+    y = StemFn.apply(x, dtype, xcep.training, buffers, infer, bytesrc, *params)
     if xcep.training:
         torch._foreach_add_([owner._buffers['num_batches_tracked'] for owner in refs[2]], 1)     # one launch, not 11
     return y

@@ -269,6 +269,18 @@ int istvt_conv1_fwd_u8(const void* x, const float* mean, const float* std, const
 int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, float* dw, int frames, int S, int dtype,
                       istvt_stream_t stream);
 int istvt_conv1_wgrad_slabs(void);
+/* conv1 from a VIEW of decoded frames (the training entry): x uint8 [frames][Hs][Ws][3], `total` bytes readable at x
+ * (>= frames*Hs*Ws*3; nothing outside [x, x + total) is read, x needs no alignment); view int32 [frames][3] = (y0, x0,
+ * flip) on the device, or null for (0, 0, 0): output pixel (y, x) of frame f is source pixel (y0 + y, x0 + (flip ?
+ * S-1-x : x)), 3 <= S <= min(Hs, Ws), channel order kept.  Bytes are normalised as in istvt_conv1_fwd_u8.  Each gives the
+ * bits of its float twin (istvt_conv1_fwd / istvt_conv1_wgrad / istvt_im2col_conv1) on the float32 NCHW tensor the host
+ * makes of the view, ((u / 255) - mean) / std.  conv1_wgrad_u8: slabs and limit (Ho <= 128) as istvt_conv1_wgrad. */
+int istvt_conv1_fwd_u8_view(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
+                            const float* std, const float* w, void* u1, int frames, int S, int dtype, istvt_stream_t stream);
+int istvt_conv1_wgrad_u8(const void* du1, const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
+                         const float* std, float* slabs, float* dw, int frames, int S, int dtype, istvt_stream_t stream);
+int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* view, const float* mean, const float* std,
+                          void* col, int frames, int S, int dtype, istvt_stream_t stream);
 int istvt_conv2_fwd(const void* u1, const float* bnp, const void* w, void* u2, int frames, int H, int W,
                     istvt_stream_t stream);
 int istvt_conv2_dgrad(const void* du2, const void* w, const void* u1, const float* bnp, void* dz1, int frames, int H,
