@@ -32,22 +32,10 @@ __device__ __forceinline__ f32x4 mma16(const bf16x8& a, const bf16x8& b, const f
 }
 
 // ------------------------------------------------------------------------------------------ conv1 forward
+// One output pixel: its 27 patch values v[k], k = (ci, dy, dx) as conv1.weight[co] stores them, times the 32 filters.
+// Every output's bits depend on this fmaf chain (k ascending from 0): it is written once, for the float and the byte kernel.
 template <typename T>
-__global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        T* __restrict__ u1, long Mo, int S, int Ho, int Wo) {
-    const long m = (long)blockIdx.x * 256 + threadIdx.x;
-    if (m >= Mo) return;
-    const int xo = (int)(m % Wo), yo = (int)((m / Wo) % Ho);
-    const long f = m / ((long)Wo * Ho);
-    float v[27];                                     // [ci][dy][dx]: the order of conv1.weight[co]
-#pragma unroll
-    for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const float* row = x + ((f * 3 + ci) * S + 2 * yo + dy) * S + 2 * xo;
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) v[ci * 9 + dy * 3 + dx] = row[dx];
-        }
+__device__ __forceinline__ void conv1_mac_store(const float* v, const float* __restrict__ w, T* __restrict__ out) {
 #pragma unroll
     for (int c8 = 0; c8 < 4; ++c8) {
         float o[8];
@@ -59,97 +47,67 @@ __global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict_
             for (int k = 0; k < 27; ++k) a = fmaf(wc[k], v[k], a);
             o[j] = a;
         }
-        store8(u1 + m * 32 + c8 * 8, o);
+        store8(out + c8 * 8, o);
     }
 }
 
-// ------------------------------------------------------------------------------------------ conv1 forward from bytes
-// The inference entry of conv1: the frames as a decoder delivers them, uint8 [frames][S][S][3], normalised on the fly as
-// torchvision's ToTensor + Normalize do it, v = (float(u) / 255 - mean[c]) / std[c] with each operation rounded on its own
-// (the explicitly rounded intrinsics: nothing for -ffp-contract=fast to fuse or reassociate).  A byte has 256 values, so
-// the three channels' normalised values are a 3 x 256 float table each workgroup fills in LDS from those expressions; the
-// 27 x 32 multiply-adds then run in conv1_fwd_kernel's order on the same float values, so the output is bit-identical to
-// conv1_fwd_kernel on the float32 NCHW tensor torch makes from the same bytes.
-// Work item = (frame, R output rows): their 2R + 1 input rows are ONE contiguous byte range of the frame, staged in LDS
-// with 16-byte loads (from the enclosing 16-byte-aligned range; pieces that stick out of the tensor are read byte by
-// byte, so any view of a frame batch is accepted and nothing outside [x, x + total) is touched).  Neighbouring outputs
-// share a column and two of three rows: every input byte comes from HBM once per work item (plus one shared row in 2R + 1).
 template <typename T>
-__global__ __launch_bounds__(256) void conv1_fwd_u8(const uint8_t* __restrict__ x, const float* __restrict__ mean,
-                                                    const float* __restrict__ stdv, const float* __restrict__ w,
-                                                    T* __restrict__ u1, long total, int S, int Ho, int R, int ngroups) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* lut = reinterpret_cast<float*>(smem);                  // [3][256]
-    unsigned char* sb = smem + 3 * 256 * sizeof(float);           // staged bytes, sb[j] = byte at aligned address a0 + j
-    const int tid = threadIdx.x;
-    const int grp = (int)(blockIdx.x % ngroups);
-    const long f = blockIdx.x / ngroups;
-    const int y0 = grp * R;
-    const int rows = min(R, Ho - y0);
-    u8_fill_lut(lut, mean, stdv, tid, 256);
-    const long g0 = (f * S + 2 * y0) * (long)S * 3;               // first byte of input row 2 y0 of frame f
-    const int len = (2 * rows + 1) * S * 3;                       // rows 2 y0 .. 2 (y0 + rows): 2 (Ho - 1) + 2 <= S - 1
-    const uintptr_t base = reinterpret_cast<uintptr_t>(x);
-    const int lead = (int)((base + (uintptr_t)g0) & 15);
-    const long c0 = g0 - lead;                                    // offset (from x) of the aligned range's first byte
-    const int nchunks = (lead + len + 15) >> 4;
-    for (int c = tid; c < nchunks; c += 256) {
-        const long o = c0 + 16L * c;
-        uint4 v;
-        if (o >= 0 && o + 16 <= total) {
-            v = *reinterpret_cast<const uint4*>(x + o);
-        } else {
-            unsigned char b[16];
+__global__ __launch_bounds__(256) void conv1_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                        T* __restrict__ u1, long Mo, int S, int Ho, int Wo) {
+    const long m = (long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= Mo) return;
+    const int xo = (int)(m % Wo), yo = (int)((m / Wo) % Ho);
+    const long f = m / ((long)Wo * Ho);
+    float v[27];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) b[j] = (o + j >= 0 && o + j < total) ? x[o + j] : (unsigned char)0;
-            v = *reinterpret_cast<const uint4*>(b);
-        }
-        *reinterpret_cast<uint4*>(sb + 16 * c) = v;
-    }
-    __syncthreads();
-    const int nout = rows * Ho;
-    for (int o = tid; o < nout; o += 256) {
-        const int yl = o / Ho, xo = o - yl * Ho;
-        float v[27];                                     // [ci][dy][dx]: the order of conv1.weight[co]
+    for (int ci = 0; ci < 3; ++ci)
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
-            const unsigned char* row = sb + lead + ((2 * yl + dy) * S + 2 * xo) * 3;    // 9 bytes: 3 pixels x RGB
+            const float* row = x + ((f * 3 + ci) * S + 2 * yo + dy) * S + 2 * xo;
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) v[ci * 9 + dy * 3 + dx] = lut[ci * 256 + row[dx * 3 + ci]];
+            for (int dx = 0; dx < 3; ++dx) v[ci * 9 + dy * 3 + dx] = row[dx];
         }
-        const long m = (f * Ho + y0) * (long)Ho + o;
-        int w0 = 0;
-        asm volatile("" : "+s"(w0));                     // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
-        const float* wl = w + w0;
-#pragma unroll
-        for (int c8 = 0; c8 < 4; ++c8) {
-            float acc[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float* wc = wl + (c8 * 8 + j) * 27;    // uniform address: scalar loads
-                float a = 0.f;
-#pragma unroll
-                for (int k = 0; k < 27; ++k) a = fmaf(wc[k], v[k], a);
-                acc[j] = a;
-            }
-            store8(u1 + m * 32 + c8 * 8, acc);
-        }
-    }
+    conv1_mac_store(v, w, u1 + m * 32);
 }
 
-// ------------------------------------------------------------------------------------------ conv1 forward from a view
-// The training entry of conv1: the S x S view (crop window + horizontal flip, u8_view.h) of a larger decoded frame, uint8
-// [frames][Hs][Ws][3].  Work item = (frame, R output rows) as in conv1_fwd_u8; with a crop its 2R + 1 input rows are no
-// longer one contiguous range, so they are staged row by row (u8_stage_rows), and a flipped view looks its pixels up
-// mirrored.  The 27 x 32 multiply-adds run in conv1_fwd_kernel's order on the same float values: bit-identical to
-// conv1_fwd_kernel on the float32 NCHW tensor the host makes of the view.
-template <typename T>
-__global__ __launch_bounds__(256) void conv1_fwd_u8_view(const uint8_t* __restrict__ x, const int* __restrict__ view,
-                                                         const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                         const float* __restrict__ w, T* __restrict__ u1, long total,
-                                                         int Hs, int Ws, int S, int Ho, int R, int ngroups) {
+// ------------------------------------------------------------------------------------------ conv1 from bytes
+// conv1's input as decoded frames, uint8 [frames][Hs][Ws][3], read through a view (crop window + horizontal flip,
+// u8_view.h; a null table is the identity) and normalised on the fly: a byte has 256 values, so the three channels'
+// normalised values are a 3 x 256 float table each workgroup fills in LDS from the host's expressions (u8_normalise).
+// Work item = (frame, R output rows): their 2R + 1 view rows are staged in LDS row by row (u8_stage_rows), so every input
+// byte comes from HBM once per work item (plus one shared row in 2R + 1); a flipped view looks its pixels up mirrored.
+// What is done with an output pixel's 27 values is the Sink: both give the bits of their float twin on the float32 NCHW
+// tensor the host makes of the view, because the values are the same floats and so is every operation after the gather.
+struct Conv1Mac {                           // conv1_fwd_kernel: (ci, dy, dx) order, 27 x 32 multiply-adds -> u1
+    static __device__ __forceinline__ int slot(int dy, int dx, int ci) { return ci * 9 + dy * 3 + dx; }
+    template <typename T>
+    static __device__ __forceinline__ void emit(const float* v, const float* __restrict__ w, T* __restrict__ out) {
+        int w0 = 0;
+        asm volatile("" : "+s"(w0));        // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
+        conv1_mac_store(v, w + w0, out);
+    }
+};
+
+struct Conv1Col {                           // im2col_c3s2_kernel (stem.hip): (dy, dx, ci) order + 5 zero columns -> col
+    static __device__ __forceinline__ int slot(int dy, int dx, int ci) { return (dy * 3 + dx) * 3 + ci; }
+    template <typename T>
+    static __device__ __forceinline__ void emit(const float* v, const float*, T* __restrict__ out) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float t[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) t[i] = c * 8 + i < 27 ? v[c * 8 + i] : 0.f;
+            store8(out + c * 8, t);
+        }
+    }
+};
+
+// out [frames*Ho*Ho][32]: u1 or col; w: conv1.weight as stored (Conv1Mac only)
+template <typename Sink, typename T>
+__global__ __launch_bounds__(256) void conv1_u8_kernel(const uint8_t* __restrict__ x, const int* __restrict__ view,
+                                                       const float* __restrict__ mean, const float* __restrict__ stdv,
+                                                       const float* __restrict__ w, T* __restrict__ out, long total,
+                                                       int Hs, int Ws, int S, int Ho, int R, int ngroups) {
     extern __shared__ __align__(16) unsigned char smem[];
     float* lut = reinterpret_cast<float*>(smem);                  // [3][256]
     unsigned char* sb = smem + 3 * 256 * sizeof(float);           // staged rows, pitch bytes each
@@ -167,7 +125,7 @@ __global__ __launch_bounds__(256) void conv1_fwd_u8_view(const uint8_t* __restri
     const int nout = rows * Ho;
     for (int o = tid; o < nout; o += 256) {
         const int yl = o / Ho, xo = o - yl * Ho;
-        float v[27];                                     // [ci][dy][dx]: the order of conv1.weight[co]
+        float v[27];
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int rr = 2 * yl + dy;
@@ -176,26 +134,10 @@ __global__ __launch_bounds__(256) void conv1_fwd_u8_view(const uint8_t* __restri
             for (int dx = 0; dx < 3; ++dx) {
                 const unsigned char* px = row + u8_view_px(2 * xo + dx, S, vw.flip);
 #pragma unroll
-                for (int ci = 0; ci < 3; ++ci) v[ci * 9 + dy * 3 + dx] = lut[ci * 256 + px[ci]];
+                for (int ci = 0; ci < 3; ++ci) v[Sink::slot(dy, dx, ci)] = lut[ci * 256 + px[ci]];
             }
         }
-        const long m = (f * Ho + yb) * (long)Ho + o;
-        int w0 = 0;
-        asm volatile("" : "+s"(w0));                     // the 864 weights are re-read per pass, not hoisted into SGPRs and spilled
-        const float* wl = w + w0;
-#pragma unroll
-        for (int c8 = 0; c8 < 4; ++c8) {
-            float acc[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float* wc = wl + (c8 * 8 + j) * 27;    // uniform address: scalar loads
-                float a = 0.f;
-#pragma unroll
-                for (int k = 0; k < 27; ++k) a = fmaf(wc[k], v[k], a);
-                acc[j] = a;
-            }
-            store8(u1 + m * 32 + c8 * 8, acc);
-        }
+        Sink::emit(v, w, out + ((f * Ho + yb) * (long)Ho + o) * 32);
     }
 }
 
@@ -501,67 +443,96 @@ __global__ __launch_bounds__(256) void conv2_wgrad_kernel(const bf16_t* __restri
 constexpr int C1_PX = 128;
 constexpr int C1_PITCH = 32 * 2 + 16;
 
+// What the two kernels below share.  Chunk `row` = (frame f, output row yo); dreg: the row of du1, pixel (tid + 256 k) >> 2,
+// channels 8 ((tid + 256 k) & 3) .. + 7, rounded to bf16 (zero past the row end)
+struct C1Row {
+    long f;
+    int yo;
+};
+
+template <typename TD>
+__device__ __forceinline__ C1Row c1_load_du1(const TD* __restrict__ du1, int row, int Ho, int Wo, int tid, bf16x8 (&dreg)[2]) {
+    const C1Row c{row / Ho, row % Ho};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {                            // 128 px x 4 pieces of 8 channels
+        const int i = tid + 256 * k;
+        const int px = i >> 2, pc = i & 3;
+        dreg[k] = zero_frag();
+        if (px < Wo) {
+            float v[8];
+            load8(du1 + ((c.f * Ho + c.yo) * Wo + px) * 32 + pc * 8, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) dreg[k][j] = (bf16_t)v[j];
+        }
+    }
+    return c;
+}
+
+__device__ __forceinline__ void c1_store_du1(char* dimg, int tid, const bf16x8 (&dreg)[2]) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int i = tid + 256 * k;
+        *reinterpret_cast<bf16x8*>(dimg + (i >> 2) * C1_PITCH + (i & 3) * 16) = dreg[k];
+    }
+}
+
+// 16 patch values k0 .. k0 + 15 of pixel px, rounded to bf16, into the patch image
+__device__ __forceinline__ void c1_store_patch(char* pimg, int px, int k0, const float (&v)[16]) {
+    bf16x8 p0, p1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { p0[j] = (bf16_t)v[j]; p1[j] = (bf16_t)v[8 + j]; }
+    *reinterpret_cast<bf16x8*>(pimg + px * C1_PITCH + k0 * 2) = p0;
+    *reinterpret_cast<bf16x8*>(pimg + px * C1_PITCH + k0 * 2 + 16) = p1;
+}
+
+// wave (mt, nt) owns the 16 x 16 tile (co tile mt, k tile nt): four k-steps of 32 pixels
+__device__ __forceinline__ f32x4 c1_mma(const char* dimg, const char* pimg, int tid, f32x4 acc) {
+    const int lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int ks = 0; ks < C1_PX / 32; ++ks)
+        acc = mma16(tr_frag(dimg, C1_PITCH, 32 * ks + 8 * g, 16 * (wave >> 1), r),
+                    tr_frag(pimg, C1_PITCH, 32 * ks + 8 * g, 16 * (wave & 1), r), acc);
+    return acc;
+}
+
+__device__ __forceinline__ void c1_store_slab(float* __restrict__ slabs, int tid, const f32x4& acc) {
+    const int lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+    float* out = slabs + (long)blockIdx.x * 32 * 32;         // rows co = 16 mt + 4g + i, column k = 16 nt + r
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[(16 * (wave >> 1) + 4 * g + i) * 32 + 16 * (wave & 1) + r] = acc[i];
+}
+
 template <typename TD>
 __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const TD* __restrict__ du1, const float* __restrict__ x,
                                                           float* __restrict__ slabs, int S, int Ho, int Wo, int nrows) {
     __shared__ __attribute__((aligned(16))) char dimg[C1_PX * C1_PITCH];
     __shared__ __attribute__((aligned(16))) char pimg[C1_PX * C1_PITCH];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    const int mt = wave >> 1, nt = wave & 1;
+    const int tid = threadIdx.x;
     const int ppx = tid >> 1, pk0 = (tid & 1) * 16;          // patch role: pixel, first of 16 k
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 dreg[2];
     float xreg[16];
     auto gload = [&](int row) {
-        const int yo = row % Ho;
-        const long f = row / Ho;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {                        // 128 px x 4 pieces of 8 channels
-            const int i = tid + 256 * k;
-            const int px = i >> 2, pc = i & 3;
-            dreg[k] = zero_frag();
-            if (px < Wo) {
-                float v[8];
-                load8(du1 + ((f * Ho + yo) * Wo + px) * 32 + pc * 8, v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dreg[k][j] = (bf16_t)v[j];
-            }
-        }
+        const C1Row c = c1_load_du1(du1, row, Ho, Wo, tid, dreg);
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int k = pk0 + j;                           // (ci, dy, dx)
             const int ci = k / 9, dy = (k % 9) / 3, dx = k % 3;
             xreg[j] = 0.f;
-            if (k < 27 && ppx < Wo) xreg[j] = x[((f * 3 + ci) * S + 2 * yo + dy) * S + 2 * ppx + dx];
+            if (k < 27 && ppx < Wo) xreg[j] = x[((c.f * 3 + ci) * S + 2 * c.yo + dy) * S + 2 * ppx + dx];
         }
     };
     int row = blockIdx.x;
     if (row < nrows) gload(row);
     for (; row < nrows; row += gridDim.x) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int i = tid + 256 * k;
-            *reinterpret_cast<bf16x8*>(dimg + (i >> 2) * C1_PITCH + (i & 3) * 16) = dreg[k];
-        }
-        {
-            bf16x8 p0, p1;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { p0[j] = (bf16_t)xreg[j]; p1[j] = (bf16_t)xreg[8 + j]; }
-            *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + pk0 * 2) = p0;
-            *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + pk0 * 2 + 16) = p1;
-        }
+        c1_store_du1(dimg, tid, dreg);
+        c1_store_patch(pimg, ppx, pk0, xreg);
         __syncthreads();
         if (row + (int)gridDim.x < nrows) gload(row + gridDim.x);
-#pragma unroll
-        for (int ks = 0; ks < C1_PX / 32; ++ks)
-            acc = mma16(tr_frag(dimg, C1_PITCH, 32 * ks + 8 * g, 16 * mt, r),
-                        tr_frag(pimg, C1_PITCH, 32 * ks + 8 * g, 16 * nt, r), acc);
+        acc = c1_mma(dimg, pimg, tid, acc);
         __syncthreads();
     }
-    float* out = slabs + (long)blockIdx.x * 32 * 32;         // rows co = 16 mt + 4g + i, column k = 16 nt + r
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[(16 * mt + 4 * g + i) * 32 + 16 * nt + r] = acc[i];
+    c1_store_slab(slabs, tid, acc);
 }
 
 // ------------------------------------------------------------------------------------------ conv1 weight gradient from bytes
@@ -586,9 +557,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_u8_kernel(const TD* __restric
     __shared__ __attribute__((aligned(16))) char pimg[C1_PX * C1_PITCH];
     __shared__ __attribute__((aligned(16))) unsigned char sb[3 * C1B_PITCH];
     __shared__ float lut[3 * 256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, g = lane >> 4;
-    const int mt = wave >> 1, nt = wave & 1;
+    const int tid = threadIdx.x;
     const int ppx = tid & (C1_PX - 1), pk0 = (tid >> 7) * 16;    // patch role: pixel, first of 16 k (the same in a wavefront)
     const int brow = tid / C1B_CPR, bc = tid - brow * C1B_CPR;   // byte role: source row of the chunk, 16-byte piece
     const int rstride = Ws * 3, len = S * 3;
@@ -598,22 +567,9 @@ __global__ __launch_bounds__(256) void conv1_wgrad_u8_kernel(const TD* __restric
     uint4 breg = make_uint4(0u, 0u, 0u, 0u);
     int lead0 = 0, flip = 0, lead0n = 0, flipn = 0;          // of the chunk in LDS / of the prefetched one
     auto gload = [&](int row) {
-        const int yo = row % Ho;
-        const long f = row / Ho;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {                        // 128 px x 4 pieces of 8 channels
-            const int i = tid + 256 * k;
-            const int px = i >> 2, pc = i & 3;
-            dreg[k] = zero_frag();
-            if (px < Wo) {
-                float v[8];
-                load8(du1 + ((f * Ho + yo) * Wo + px) * 32 + pc * 8, v);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dreg[k][j] = (bf16_t)v[j];
-            }
-        }
-        const U8View vw = u8_view_of(view, f, Hs, Ws, S);
-        const long g0 = ((f * Hs + vw.y0 + 2 * yo) * (long)Ws + vw.x0) * 3;
+        const C1Row c = c1_load_du1(du1, row, Ho, Wo, tid, dreg);
+        const U8View vw = u8_view_of(view, c.f, Hs, Ws, S);
+        const long g0 = ((c.f * Hs + vw.y0 + 2 * c.yo) * (long)Ws + vw.x0) * 3;
         lead0n = (int)((reinterpret_cast<uintptr_t>(x) + (uintptr_t)g0) & 15);
         flipn = vw.flip;
         if (brow < 3) {
@@ -630,41 +586,30 @@ __global__ __launch_bounds__(256) void conv1_wgrad_u8_kernel(const TD* __restric
             rowoff[d] = d * C1B_PITCH + u8_row_lead(lead0, d, rstride);
             pxoff[d] = u8_view_px(2 * ppx + d, S, flip);
         }
-        bf16x8 p[2];
+        float v[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int k = K0 + j;
             const int ci = k / 9, dy = (k % 9) / 3, dx = k % 3;
-            float v = 0.f;
-            if (k < 27 && ppx < Wo) v = lut[ci * 256 + sb[rowoff[dy] + pxoff[dx] + ci]];
-            p[j >> 3][j & 7] = (bf16_t)v;
+            v[j] = 0.f;
+            if (k < 27 && ppx < Wo) v[j] = lut[ci * 256 + sb[rowoff[dy] + pxoff[dx] + ci]];
         }
-        *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + K0 * 2) = p[0];
-        *reinterpret_cast<bf16x8*>(pimg + ppx * C1_PITCH + K0 * 2 + 16) = p[1];
+        c1_store_patch(pimg, ppx, K0, v);
     };
     int row = blockIdx.x;
     if (row < nrows) gload(row);
     for (; row < nrows; row += gridDim.x) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int i = tid + 256 * k;
-            *reinterpret_cast<bf16x8*>(dimg + (i >> 2) * C1_PITCH + (i & 3) * 16) = dreg[k];
-        }
+        c1_store_du1(dimg, tid, dreg);
         if (brow < 3) *reinterpret_cast<uint4*>(sb + brow * C1B_PITCH + 16 * bc) = breg;
         lead0 = lead0n, flip = flipn;
-        __syncthreads();
+        __syncthreads();                                     // the bytes are in LDS before any patch is gathered from them
         if (pk0 == 0) patch(std::integral_constant<int, 0>()); else patch(std::integral_constant<int, 16>());
         if (row + (int)gridDim.x < nrows) gload(row + gridDim.x);
         __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < C1_PX / 32; ++ks)
-            acc = mma16(tr_frag(dimg, C1_PITCH, 32 * ks + 8 * g, 16 * mt, r),
-                        tr_frag(pimg, C1_PITCH, 32 * ks + 8 * g, 16 * nt, r), acc);
+        acc = c1_mma(dimg, pimg, tid, acc);
         __syncthreads();
     }
-    float* out = slabs + (long)blockIdx.x * 32 * 32;         // rows co = 16 mt + 4g + i, column k = 16 nt + r
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[(16 * mt + 4 * g + i) * 32 + 16 * nt + r] = acc[i];
+    c1_store_slab(slabs, tid, acc);
 }
 
 inline int wave_grid(int ngroups, int per_cu) {
@@ -685,30 +630,6 @@ extern "C" int istvt_conv1_fwd(const float* x, const float* w, void* u1, int Fr,
     return istvt_check_launch();
 }
 
-// conv1 forward from bytes: x uint8 [frames][S][S][3], mean / std float [3], w as above -> the same u1
-extern "C" int istvt_conv1_fwd_u8(const void* x, const float* mean, const float* stdv, const float* w, void* u1, int Fr,
-                                  int S, int dtype, hipStream_t stream) {
-    if (Fr <= 0 || S < 3 || S > 4096 || !x || !mean || !stdv) return ISTVT_ERR_SHAPE;
-    const int Ho = (S - 3) / 2 + 1;
-    // R output rows per workgroup (2R + 1 staged input rows, at most 48 KiB; one always fits: 3 * 4096 * 3 bytes): of
-    // 4..16, the one that wastes the fewest lanes of the 256-thread passes over its R * Ho outputs
-    int R = 1;
-    double best = 0.0;
-    for (int r = 1; r <= 16 && r <= Ho; ++r) {
-        if ((2L * r + 1) * S * 3 > 48 * 1024) break;
-        const double eff = r < 4 ? 0.0 : (double)(r * Ho) / (double)(((r * Ho + 255) / 256) * 256);
-        if (r < 4 || eff > best + 1e-9) best = eff, R = r;
-    }
-    const int ngroups = (Ho + R - 1) / R;
-    const long nblocks = (long)Fr * ngroups;
-    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const long total = (long)Fr * S * S * 3;
-    const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * S * 3 + 32;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_u8<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
-                                             (const uint8_t*)x, mean, stdv, w, (T*)u1, total, S, Ho, R, ngroups));
-    return istvt_check_launch();
-}
-
 // Common argument check of the entry points that read a view of decoded frames (u8_view.h)
 static inline bool u8_view_args_ok(const void* x, long total, int Hs, int Ws, const float* mean, const float* stdv, int Fr,
                                    int S) {
@@ -717,16 +638,16 @@ static inline bool u8_view_args_ok(const void* x, long total, int Hs, int Ws, co
     return total >= (long)Fr * Hs * Ws * 3;
 }
 
-// conv1 forward from a view of decoded frames: x uint8 [frames][Hs][Ws][3] (total bytes readable at x), view int32
-// [frames][3] = (y0, x0, flip) on the device or null, crop side S -> the u1 istvt_conv1_fwd gives on the float tensor
-// of the view
-extern "C" int istvt_conv1_fwd_u8_view(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
-                                       const float* stdv, const float* w, void* u1, int Fr, int S, int dtype,
-                                       hipStream_t stream) {
-    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || S > 4096 || !w || !u1) return ISTVT_ERR_SHAPE;
+// Launch of conv1_u8_kernel<Sink, .>.  R output rows per workgroup: 2R + 1 staged rows of u8_row_pitch(S) bytes, at most
+// 48 KiB (one always fits: 3 rows of 4096 pixels); of 4..16, the R that wastes the fewest lanes of the 256-thread passes
+// over its R * Ho outputs.  (The contiguous entry used to budget (2R + 1) * S * 3 bytes: at sides near 500 and above the
+// two budgets can differ by one R, which regroups the rows and changes no bits.)
+template <typename Sink>
+static int conv1_u8_launch(const void* x, long total, int Hs, int Ws, const int* view, const float* mean, const float* stdv,
+                           const float* w, void* out, int Fr, int S, int dtype, hipStream_t stream) {
+    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || S > 4096 || !out) return ISTVT_ERR_SHAPE;
     const int Ho = (S - 3) / 2 + 1;
     const int pitch = u8_row_pitch(S);
-    // R output rows per workgroup as istvt_conv1_fwd_u8 chooses them (2R + 1 staged rows, at most 48 KiB)
     int R = 1;
     double best = 0.0;
     for (int r = 1; r <= 16 && r <= Ho; ++r) {
@@ -738,10 +659,32 @@ extern "C" int istvt_conv1_fwd_u8_view(const void* x, long total, int Hs, int Ws
     const long nblocks = (long)Fr * ngroups;
     if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
     const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * pitch;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_fwd_u8_view<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
-                                             (const uint8_t*)x, view, mean, stdv, w, (T*)u1, total, Hs, Ws, S, Ho, R,
-                                             ngroups));
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_u8_kernel<Sink, T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
+                                             (const uint8_t*)x, view, mean, stdv, w, (T*)out, total, Hs, Ws, S, Ho, R, ngroups));
     return istvt_check_launch();
+}
+
+// conv1 forward from a view of decoded frames: x uint8 [frames][Hs][Ws][3] (total bytes readable at x), view int32
+// [frames][3] = (y0, x0, flip) on the device or null, crop side S -> the u1 istvt_conv1_fwd gives on the float tensor
+// of the view
+extern "C" int istvt_conv1_fwd_u8_view(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
+                                       const float* stdv, const float* w, void* u1, int Fr, int S, int dtype,
+                                       hipStream_t stream) {
+    if (!w) return ISTVT_ERR_SHAPE;
+    return conv1_u8_launch<Conv1Mac>(x, total, Hs, Ws, view, mean, stdv, w, u1, Fr, S, dtype, stream);
+}
+
+// conv1 forward from bytes, the inference entry: x uint8 [frames][S][S][3] whole, i.e. the identity view of S x S frames
+extern "C" int istvt_conv1_fwd_u8(const void* x, const float* mean, const float* stdv, const float* w, void* u1, int Fr,
+                                  int S, int dtype, hipStream_t stream) {
+    return istvt_conv1_fwd_u8_view(x, (long)Fr * S * S * 3, S, S, nullptr, mean, stdv, w, u1, Fr, S, dtype, stream);
+}
+
+// conv1's im2col from a view of decoded frames (source and view as istvt_conv1_fwd_u8_view) -> col [frames*Ho*Ho][32] as
+// istvt_im2col_conv1 (stem.hip) makes it of the float tensor of the view
+extern "C" int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
+                                     const float* stdv, void* col, int Fr, int S, int dtype, hipStream_t stream) {
+    return conv1_u8_launch<Conv1Col>(x, total, Hs, Ws, view, mean, stdv, nullptr, col, Fr, S, dtype, stream);
 }
 
 // conv2 forward (bf16): u1 [frames][H][W][32] raw conv1 output, bnp = bn1's pack (relu applied), w [64][(dy,dx,ci)]
@@ -793,11 +736,13 @@ extern "C" int istvt_conv2_wgrad(const void* du2, const void* u1, const float* b
 
 // conv1 weight gradient: du1 [frames*Ho*Wo][32] (dtype), x float [frames][3][S][S] -> dw float [32][32] +=, column
 // k = ci*9 + dy*3 + dx (the order of conv1.weight[co]; columns 27..31 stay untouched zeros of the patches);
-// slabs = caller-owned float workspace of istvt_conv1_wgrad_slabs() * 1024 elements.  Needs Wo <= 128 (S <= 257).
+// slabs = caller-owned float workspace of istvt_conv1_wgrad_slabs() * 1024 elements.  Needs Wo <= 128 (S <= 258).
 extern "C" int istvt_conv1_wgrad_slabs() { return 1024; }
 
-extern "C" int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, float* dw, int Fr, int S, int dtype,
-                                 hipStream_t stream) {
+// One chunk per output row over at most istvt_conv1_wgrad_slabs() workgroups, then the slabs summed in index order;
+// launch(grid, Ho, nrows) starts the float or the byte kernel
+template <typename Launch>
+static int conv1_wgrad_launch(float* slabs, float* dw, int Fr, int S, hipStream_t stream, Launch launch) {
     if (Fr <= 0 || S < 3 || !slabs) return ISTVT_ERR_SHAPE;
     const int Ho = (S - 3) / 2 + 1;
     if (Ho > C1_PX) return ISTVT_ERR_SHAPE;
@@ -805,11 +750,19 @@ extern "C" int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, 
     if (nrows > 0x7fffffffL) return ISTVT_ERR_SHAPE;
     const int cap = istvt_conv1_wgrad_slabs();
     const int grid = nrows < cap ? (int)nrows : cap;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1, x,
-                                             slabs, S, Ho, Ho, (int)nrows));
-    int rc = istvt_check_launch();
+    int rc = launch(grid, Ho, (int)nrows);
+    if (rc == ISTVT_OK) rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     return istvt_rows_reduce_add(slabs, grid, 1, 1024, dw, nullptr, nullptr, stream);
+}
+
+extern "C" int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, float* dw, int Fr, int S, int dtype,
+                                 hipStream_t stream) {
+    return conv1_wgrad_launch(slabs, dw, Fr, S, stream, [&](int grid, int Ho, int nrows) {
+        DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1, x,
+                                                 slabs, S, Ho, Ho, nrows));
+        return ISTVT_OK;
+    });
 }
 
 // conv1 weight gradient from a view of decoded frames (source and view as istvt_conv1_fwd_u8_view): dw float [32][32] +=
@@ -817,17 +770,10 @@ extern "C" int istvt_conv1_wgrad(const void* du1, const float* x, float* slabs, 
 extern "C" int istvt_conv1_wgrad_u8(const void* du1, const void* x, long total, int Hs, int Ws, const int* view,
                                     const float* mean, const float* stdv, float* slabs, float* dw, int Fr, int S, int dtype,
                                     hipStream_t stream) {
-    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || !du1 || !slabs || !dw) return ISTVT_ERR_SHAPE;
-    const int Ho = (S - 3) / 2 + 1;
-    if (Ho > C1_PX) return ISTVT_ERR_SHAPE;
-    const long nrows = (long)Fr * Ho;
-    if (nrows > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const int cap = istvt_conv1_wgrad_slabs();
-    const int grid = nrows < cap ? (int)nrows : cap;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_u8_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1,
-                                             (const uint8_t*)x, view, mean, stdv, slabs, total, Hs, Ws, S, Ho, Ho,
-                                             (int)nrows));
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    return istvt_rows_reduce_add(slabs, grid, 1, 1024, dw, nullptr, nullptr, stream);
+    if (!u8_view_args_ok(x, total, Hs, Ws, mean, stdv, Fr, S) || !du1 || !dw) return ISTVT_ERR_SHAPE;
+    return conv1_wgrad_launch(slabs, dw, Fr, S, stream, [&](int grid, int Ho, int nrows) {
+        DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv1_wgrad_u8_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)du1,
+                                                 (const uint8_t*)x, view, mean, stdv, slabs, total, Hs, Ws, S, Ho, Ho, nrows));
+        return ISTVT_OK;
+    });
 }

@@ -14,7 +14,6 @@
 //
 // All of these are HBM-bound (AI <= 4.5 flop/B): coalesced 16-byte accesses along C.
 #include "common.h"
-#include "u8_view.h"
 #include <cstdlib>
 
 // A finalized BatchNorm is passed around as ONE pointer `bnp` to a float [4][C] pack:
@@ -378,56 +377,6 @@ __global__ __launch_bounds__(256) void im2col_c3s2_kernel(const float* __restric
     }
 }
 
-// conv1's im2col from a view of decoded frames (u8_view.h): uint8 [Fr][Hs][Ws][3] -> the col im2col_c3s2_kernel makes of
-// the float32 tensor of the view, bit for bit (the table holds the host's float values; the rounding to T is store8's in
-// both).  Work item = (frame, R output rows), their 2R + 1 view rows staged in LDS as in conv1_fwd_u8_view.
-template <typename T>
-__global__ __launch_bounds__(256) void im2col_c3s2_u8_kernel(const uint8_t* __restrict__ x, const int* __restrict__ view,
-                                                             const float* __restrict__ mean, const float* __restrict__ stdv,
-                                                             T* __restrict__ col, long total, int Hs, int Ws, int S, int Ho,
-                                                             int R, int ngroups) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    float* lut = reinterpret_cast<float*>(smem);                  // [3][256]
-    unsigned char* sb = smem + 3 * 256 * sizeof(float);           // staged rows, pitch bytes each
-    const int tid = threadIdx.x;
-    const int grp = (int)(blockIdx.x % ngroups);
-    const long f = blockIdx.x / ngroups;
-    const int yb = grp * R;
-    const int rows = min(R, Ho - yb);
-    const U8View vw = u8_view_of(view, f, Hs, Ws, S);
-    u8_fill_lut(lut, mean, stdv, tid, 256);
-    const int pitch = u8_row_pitch(S), rstride = Ws * 3;
-    const long g0 = ((f * Hs + vw.y0 + 2 * yb) * (long)Ws + vw.x0) * 3;
-    const int lead0 = u8_stage_rows(x, total, g0, rstride, 2 * rows + 1, S, sb, pitch, tid, 256);
-    __syncthreads();
-    const int nout = rows * Ho;
-    for (int o = tid; o < nout; o += 256) {
-        const int yl = o / Ho, xo = o - yl * Ho;
-        float v[32];
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int rr = 2 * yl + dy;
-            const unsigned char* row = sb + rr * pitch + u8_row_lead(lead0, rr, rstride);
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const unsigned char* px = row + u8_view_px(2 * xo + dx, S, vw.flip);
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci) v[(dy * 3 + dx) * 3 + ci] = lut[ci * 256 + px[ci]];
-            }
-        }
-#pragma unroll
-        for (int i = 27; i < 32; ++i) v[i] = 0.f;
-        const long m = (f * Ho + yb) * (long)Ho + o;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float t[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) t[i] = v[c * 8 + i];
-            store8(col + m * 32 + c * 8, t);
-        }
-    }
-}
-
 // NHWC source, stride 1, pad 0, optional BatchNorm pack (+ReLU) applied on load
 template <typename T>
 __global__ __launch_bounds__(256) void im2col3x3_kernel(const T* __restrict__ src, const float* __restrict__ bnp,
@@ -531,31 +480,6 @@ extern "C" int istvt_im2col_conv1(const float* x, void* col, int Fr, int S, int 
     const long Mo = (long)Fr * Ho * Ho;
     DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((im2col_c3s2_kernel<T>), dim3((unsigned)((Mo + 255) / 256)), dim3(256), 0,
                                              stream, x, (T*)col, Mo, S, Ho, Ho));
-    return istvt_check_launch();
-}
-
-// conv1's im2col from a view of decoded frames: x uint8 [frames][Hs][Ws][3] (total bytes readable at x), view int32
-// [frames][3] = (y0, x0, flip) on the device or null, crop side S -> col [frames*Ho*Ho][32] as istvt_im2col_conv1
-extern "C" int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* view, const float* mean,
-                                     const float* stdv, void* col, int Fr, int S, int dtype, hipStream_t stream) {
-    if (Fr <= 0 || S < 3 || S > 4096 || !x || !mean || !stdv || !col) return ISTVT_ERR_SHAPE;
-    if (Hs < S || Ws < S || Hs > 16384 || Ws > 16384 || total < (long)Fr * Hs * Ws * 3) return ISTVT_ERR_SHAPE;
-    const int Ho = (S - 3) / 2 + 1;
-    const int pitch = u8_row_pitch(S);
-    // R output rows per workgroup (2R + 1 staged rows, at most 48 KiB): the choice of istvt_conv1_fwd_u8
-    int R = 1;
-    double best = 0.0;
-    for (int r = 1; r <= 16 && r <= Ho; ++r) {
-        if ((2L * r + 1) * pitch > 48 * 1024) break;
-        const double eff = r < 4 ? 0.0 : (double)(r * Ho) / (double)(((r * Ho + 255) / 256) * 256);
-        if (r < 4 || eff > best + 1e-9) best = eff, R = r;
-    }
-    const int ngroups = (Ho + R - 1) / R;
-    const long nblocks = (long)Fr * ngroups;
-    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const size_t lds = 3 * 256 * sizeof(float) + (size_t)(2 * R + 1) * pitch;
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((im2col_c3s2_u8_kernel<T>), dim3((unsigned)nblocks), dim3(256), lds, stream,
-                                             (const uint8_t*)x, view, mean, stdv, (T*)col, total, Hs, Ws, S, Ho, R, ngroups));
     return istvt_check_launch();
 }
 

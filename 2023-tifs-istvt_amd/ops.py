@@ -746,33 +746,69 @@ def tokens_gather_fwd(bank: Tensor, idx: Tensor, space: Tensor, temporal: Tensor
     return x.view(W, F * P, D)
 
 
-def conv1_fwd_u8(frames: Tensor, mean: Tensor, std: Tensor, weight: Tensor, dtype: torch.dtype) -> Tensor:
-    """conv1 of the Xception stem straight from decoded frames: frames uint8 [Fr,S,S,3] (channels last), mean / std float32
-    [3] on the device, weight conv1.weight (32,3,3,3) float32 -> u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to
-    istvt_conv1_fwd on ((frames.float() / 255 - mean) / std).permute(0, 3, 1, 2).  Inference only (no weight gradient)."""
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('conv1_fwd_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[1] != frames.shape[2]:
-        raise RuntimeError('conv1_fwd_u8 expects channels-last (frames, S, S, 3) uint8 input, got %s' % (tuple(frames.shape),))
+# ---- conv1 of the Xception stem (3 -> 32, 3x3, stride 2, no padding) from its two kinds of input: the float32 NCHW clip, or
+# decoded frames (uint8, channels last) read through a view and normalised in the kernel.  Every byte routine gives the bits of
+# its float twin on clips.to_float(src, mean, std, view, S) made on the host.
+def _float_clip(what: str, x: Tensor):
+    _req(x, 'input clip')
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[0] == 0:
+        raise RuntimeError('%s expects a float32 (frames, 3, S, S) clip, got %s %s' % (what, x.dtype, tuple(x.shape)))
+    return _c(x), x.shape[0], x.shape[2]
+
+
+def _conv1_out(Fr: int, S: int, dtype, device) -> Tensor:
     if dtype not in _DT:
         raise TypeError('istvt_amd supports float32 and bfloat16 activations, got %s' % dtype)
-    for t, n in ((mean, 'mean'), (std, 'std')):
-        if t.dtype != torch.float32 or t.numel() != 3 or t.device != frames.device:
-            raise RuntimeError('conv1_fwd_u8: %s must be 3 float32 values on %s' % (n, frames.device))
-    if weight.dtype != torch.float32 or tuple(weight.shape) != (32, 3, 3, 3) or weight.device != frames.device:
-        raise RuntimeError('conv1_fwd_u8: weight must be conv1.weight, float32 (32, 3, 3, 3) on %s' % frames.device)
-    frames = _c(frames)
-    Fr, S = frames.shape[0], frames.shape[1]
-    if Fr == 0 or S < 3:
-        raise RuntimeError('conv1_fwd_u8: empty input %s' % (tuple(frames.shape),))
     Ho = (S - 3) // 2 + 1
-    u1 = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=frames.device)
-    with prof('conv1_fwd_u8', Fr * S * S * 3 + u1.numel() * u1.element_size(), 2.0 * 27 * u1.numel()):
-        _lib.check(_lib.lib().istvt_conv1_fwd_u8(frames.data_ptr(), _c(mean).data_ptr(), _c(std).data_ptr(),
-                                                 _c(weight.detach()).data_ptr(), u1.data_ptr(), Fr, S, _DT[dtype], _stream()),
-                   'istvt_conv1_fwd_u8')
+    return torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=device)
+
+
+def _conv1_w(what: str, weight: Tensor, device) -> Tensor:
+    if weight.dtype != torch.float32 or tuple(weight.shape) != (32, 3, 3, 3) or weight.device != device:
+        raise RuntimeError('%s: weight must be conv1.weight, float32 (32, 3, 3, 3) on %s' % (what, device))
+    return _c(weight.detach())
+
+
+def _conv1_du1(what: str, du1: Tensor, Fr: int, S: int, device) -> Tensor:
+    Ho = (S - 3) // 2 + 1
+    if du1.device != device or du1.dim() != 2 or tuple(du1.shape) != (Fr * Ho * Ho, 32):
+        raise RuntimeError('%s: du1 must be (%d, 32) on %s, got %s' % (what, Fr * Ho * Ho, device, tuple(du1.shape)))
+    return _c(du1)
+
+
+def _conv1_wgrad_ws(device):
+    """(dW float32 [32, 32] zeroed, the kernel's slab workspace)"""
+    return (torch.zeros((32, 32), dtype=torch.float32, device=device),
+            torch.empty((_lib.lib().istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=device))
+
+
+def conv1_fwd(x: Tensor, weight: Tensor, dtype: torch.dtype) -> Tensor:
+    """x float32 [Fr,3,S,S], weight conv1.weight (32,3,3,3) float32 -> u1 [Fr*Ho*Ho, 32] in `dtype` (the direct kernel)."""
+    x, Fr, S = _float_clip('conv1_fwd', x)
+    w = _conv1_w('conv1_fwd', weight, x.device)
+    u1 = _conv1_out(Fr, S, dtype, x.device)
+    _lib.check(_lib.lib().istvt_conv1_fwd(x.data_ptr(), w.data_ptr(), u1.data_ptr(), Fr, S, _DT[dtype], _stream()),
+               'istvt_conv1_fwd')
     return u1
+
+
+def conv1_wgrad(du1: Tensor, x: Tensor) -> Tensor:
+    """du1 [Fr*Ho*Ho, 32] (float32 or bfloat16), x float32 [Fr,3,S,S] -> dW float32 [32, 32], column k = ci*9 + dy*3 + dx
+    (27..31 zero).  Needs Ho <= 128 (S <= 258)."""
+    x, Fr, S = _float_clip('conv1_wgrad', x)
+    du1 = _conv1_du1('conv1_wgrad', du1, Fr, S, x.device)
+    dW, slabs = _conv1_wgrad_ws(x.device)
+    _lib.check(_lib.lib().istvt_conv1_wgrad(du1.data_ptr(), x.data_ptr(), slabs.data_ptr(), dW.data_ptr(), Fr, S,
+                                            dtype_code(du1), _stream()), 'istvt_conv1_wgrad')
+    return dW
+
+
+def im2col_conv1(x: Tensor, dtype: torch.dtype) -> Tensor:
+    """x float32 [Fr,3,S,S] -> col [Fr*Ho*Ho, 32] in `dtype`: columns (dy,dx,ci) + 5 zero columns."""
+    x, Fr, S = _float_clip('im2col_conv1', x)
+    col = _conv1_out(Fr, S, dtype, x.device)
+    _lib.check(_lib.lib().istvt_im2col_conv1(x.data_ptr(), col.data_ptr(), Fr, S, _DT[dtype], _stream()), 'istvt_im2col_conv1')
+    return col
 
 
 def _u8_source(what: str, src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, dtype, checked: bool):
@@ -807,50 +843,57 @@ def _u8_source(what: str, src: Tensor, view, S: Optional[int], mean: Tensor, std
     return _c(src), Fr, Hs, Ws, S, vdev
 
 
+def conv1_fwd_u8(frames: Tensor, mean: Tensor, std: Tensor, weight: Tensor, dtype: torch.dtype) -> Tensor:
+    """conv1 straight from decoded frames, the inference entry: frames uint8 [Fr,S,S,3] whole (the identity view), mean / std
+    float32 [3] on the device -> u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to conv1_fwd on
+    ((frames.float() / 255 - mean) / std).permute(0, 3, 1, 2)."""
+    # (the one refusal kept here: _u8_source's check_views answers a non-square frame with ValueError, this entry always
+    # answered RuntimeError; a wrong dtype stays _u8_source's TypeError)
+    if frames.dtype == torch.uint8 and frames.dim() == 4 and (frames.shape[1] != frames.shape[2] or frames.shape[1] < 3):
+        raise RuntimeError('conv1_fwd_u8 expects channels-last (frames, S, S, 3) uint8 input, got %s' % (tuple(frames.shape),))
+    frames, Fr, _, _, S, _ = _u8_source('conv1_fwd_u8', frames, None, None, mean, std, dtype, False)
+    w = _conv1_w('conv1_fwd_u8', weight, frames.device)
+    u1 = _conv1_out(Fr, S, dtype, frames.device)
+    with prof('conv1_fwd_u8', Fr * S * S * 3 + u1.numel() * u1.element_size(), 2.0 * 27 * u1.numel()):
+        _lib.check(_lib.lib().istvt_conv1_fwd_u8(frames.data_ptr(), _c(mean).data_ptr(), _c(std).data_ptr(), w.data_ptr(),
+                                                 u1.data_ptr(), Fr, S, _DT[dtype], _stream()), 'istvt_conv1_fwd_u8')
+    return u1
+
+
 def conv1_fwd_u8_view(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, weight: Tensor, dtype: torch.dtype,
                       checked: bool = False) -> Tensor:
     """conv1 from a view of decoded frames (clips.py): src uint8 [Fr,Hs,Ws,3], view int32 [Fr,3] or None, crop side S ->
-    u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to istvt_conv1_fwd on clips.to_float(src, mean, std, view, S) made on the
-    host."""
+    u1 [Fr*Ho*Ho, 32] in `dtype`, bit-identical to conv1_fwd on clips.to_float(src, mean, std, view, S) made on the host."""
     src, Fr, Hs, Ws, S, vdev = _u8_source('conv1_fwd_u8_view', src, view, S, mean, std, dtype, checked)
-    if weight.dtype != torch.float32 or tuple(weight.shape) != (32, 3, 3, 3) or weight.device != src.device:
-        raise RuntimeError('conv1_fwd_u8_view: weight must be conv1.weight, float32 (32, 3, 3, 3) on %s' % src.device)
-    Ho = (S - 3) // 2 + 1
-    u1 = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=src.device)
+    w = _conv1_w('conv1_fwd_u8_view', weight, src.device)
+    u1 = _conv1_out(Fr, S, dtype, src.device)
     with prof('conv1_fwd_u8_view', Fr * S * S * 3 + u1.numel() * u1.element_size(), 2.0 * 27 * u1.numel()):
         _lib.check(_lib.lib().istvt_conv1_fwd_u8_view(src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev), _c(mean).data_ptr(),
-                                                      _c(std).data_ptr(), _c(weight.detach()).data_ptr(), u1.data_ptr(),
-                                                      Fr, S, _DT[dtype], _stream()), 'istvt_conv1_fwd_u8_view')
+                                                      _c(std).data_ptr(), w.data_ptr(), u1.data_ptr(), Fr, S, _DT[dtype],
+                                                      _stream()), 'istvt_conv1_fwd_u8_view')
     return u1
 
 
 def conv1_wgrad_u8(du1: Tensor, src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor,
                    checked: bool = False) -> Tensor:
-    """conv1's weight gradient from a view of decoded frames: du1 [Fr*Ho*Ho, 32] (float32 or bfloat16), source and view as
-    conv1_fwd_u8_view -> dW float32 [32, 32], column k = ci*9 + dy*3 + dx (27..31 zero), bit-identical to
-    istvt_conv1_wgrad on clips.to_float(...).  Needs Ho <= 128 (S <= 258), as the float kernel."""
+    """conv1's weight gradient from a view of decoded frames: du1 as conv1_wgrad takes it, source and view as
+    conv1_fwd_u8_view -> dW float32 [32, 32], bit-identical to conv1_wgrad on clips.to_float(...); the same limit."""
     src, Fr, Hs, Ws, S, vdev = _u8_source('conv1_wgrad_u8', src, view, S, mean, std, du1.dtype, checked)
-    Ho = (S - 3) // 2 + 1
-    if du1.device != src.device or du1.dim() != 2 or tuple(du1.shape) != (Fr * Ho * Ho, 32):
-        raise RuntimeError('conv1_wgrad_u8: du1 must be (%d, 32) on %s, got %s' % (Fr * Ho * Ho, src.device, tuple(du1.shape)))
-    du1 = _c(du1)
-    L = _lib.lib()
-    dW = torch.zeros((32, 32), dtype=torch.float32, device=src.device)
-    slabs = torch.empty((L.istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=src.device)
+    du1 = _conv1_du1('conv1_wgrad_u8', du1, Fr, S, src.device)
+    dW, slabs = _conv1_wgrad_ws(src.device)
     with prof('conv1_wgrad_u8', du1.numel() * du1.element_size() + Fr * S * S * 3, 2.0 * 32 * du1.numel()):
-        _lib.check(L.istvt_conv1_wgrad_u8(du1.data_ptr(), src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev),
-                                          _c(mean).data_ptr(), _c(std).data_ptr(), slabs.data_ptr(), dW.data_ptr(), Fr, S,
-                                          _DT[du1.dtype], _stream()), 'istvt_conv1_wgrad_u8')
+        _lib.check(_lib.lib().istvt_conv1_wgrad_u8(du1.data_ptr(), src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev),
+                                                   _c(mean).data_ptr(), _c(std).data_ptr(), slabs.data_ptr(), dW.data_ptr(),
+                                                   Fr, S, _DT[du1.dtype], _stream()), 'istvt_conv1_wgrad_u8')
     return dW
 
 
 def im2col_conv1_u8(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tensor, dtype: torch.dtype,
                     checked: bool = False) -> Tensor:
-    """conv1's im2col from a view of decoded frames -> col [Fr*Ho*Ho, 32] in `dtype` ((dy,dx,ci) + 5 zero columns),
-    bit-identical to istvt_im2col_conv1 on clips.to_float(...)."""
+    """conv1's im2col from a view of decoded frames -> col [Fr*Ho*Ho, 32] in `dtype`, bit-identical to im2col_conv1 on
+    clips.to_float(...)."""
     src, Fr, Hs, Ws, S, vdev = _u8_source('im2col_conv1_u8', src, view, S, mean, std, dtype, checked)
-    Ho = (S - 3) // 2 + 1
-    col = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device=src.device)
+    col = _conv1_out(Fr, S, dtype, src.device)
     with prof('im2col_conv1_u8', Fr * S * S * 3 + col.numel() * col.element_size()):
         _lib.check(_lib.lib().istvt_im2col_conv1_u8(src.data_ptr(), src.numel(), Hs, Ws, _ptr(vdev), _c(mean).data_ptr(),
                                                     _c(std).data_ptr(), col.data_ptr(), Fr, S, _DT[dtype], _stream()),

@@ -245,48 +245,67 @@ def bn_names() -> List[str]:
     return names
 
 
-class StemFn(Function):
-    """y = Xception.low_level_features(x).  x: (Fr,3,S,S) float32 NCHW; y: (Fr,h,w,728) NHWC in
-    `dtype`.  `buffers` = [running_mean, running_var] * 11 in bn_names() order (updated in place
-    when training).  `infer`: None, or the inference entry's (mean, std): x is then either decoded
-    frames, uint8 (Fr,S,S,3) normalised inside conv1 with the float32 [3] device tensors mean / std,
-    or the float clip with (None, None); conv1 runs as the direct kernel in both compute dtypes (so
-    the two kinds of input agree bit for bit) and there is no backward.  `bytesrc`: None, or the training byte
-    entry's (mean, std, view, S): x is uint8 (Fr,Hs,Ws,3) source frames read through the validated device table view
-    (int32 (Fr,3) or None) with crop side S; conv1 takes the routes of the float path (direct kernels in bfloat16,
-    im2col + GEMM in float32 and for the weight gradient when Ho > 128) through the byte kernels, the bytes and the
-    table are what the backward keeps, and there is no input gradient."""
+class Conv1Input:
+    """What conv1 reads and the three ways the stem reads it.  Either the float32 NCHW clip (frames, 3, S, S); or decoded
+    frames, uint8 (frames, Hs, Ws, 3), with mean / std (float32 [3] on the device), a validated device view table (int32
+    (frames, 3) = (y0, x0, flip); None: whole S x S frames) and the crop side S (clips.py), normalised inside the kernels:
+    every byte route then has the bits of the float route on clips.to_float(x, mean, std, view, S) made on the host.
+    inference: the no-backward entry (video.VideoScorer); conv1 runs as the direct kernel in either compute dtype, which is
+    what makes byte and float input of one video agree bit for bit."""
+    __slots__ = ('x', 'mean', 'std', 'view', 'S', 'inference')
 
-    @staticmethod
-    def forward(ctx, x, dtype, training, buffers, infer, bytesrc, *params):
+    def __init__(self, x, mean=None, std=None, view=None, S=None, inference=False):
         _req(x, 'input clip')
-        if infer is not None and training:          # (stem_forward also refuses it with gradients enabled)
-            raise RuntimeError('the stem\'s inference entry needs eval mode: it has no backward')
-        u8 = x.dtype == torch.uint8
-        if bytesrc is not None:
-            if not u8 or x.dim() != 4 or x.shape[3] != 3:
+        if mean is not None:
+            if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
                 raise RuntimeError('the stem\'s byte entry expects channels-last (frames, Hs, Ws, 3) uint8 input, got %s %s'
                                    % (x.dtype, tuple(x.shape)))
-            x = _c(x)
-            Fr, S = x.shape[0], bytesrc[3]
-        elif u8:
-            if infer is None or infer[0] is None:
-                raise RuntimeError('uint8 frames need mean and std (Xception.low_level_features_nhwc(x, dtype, mean, std))')
-            if x.dim() != 4 or x.shape[3] != 3 or x.shape[1] != x.shape[2]:
+            S = x.shape[1] if S is None else S
+            if view is None and (x.shape[1] != S or x.shape[2] != S):
                 raise RuntimeError('stem expects channels-last (frames, S, S, 3) uint8 input, got %s' % (tuple(x.shape),))
-            x = _c(x)
-            Fr, S = x.shape[0], x.shape[1]
         else:
+            if x.dtype == torch.uint8:
+                raise RuntimeError('uint8 frames need mean and std (Xception.low_level_features_nhwc(x, dtype, mean, std))')
             if x.dtype != torch.float32:
                 raise TypeError('stem input must be float32, got %s' % x.dtype)
-            if infer is not None and infer[0] is not None:
-                raise RuntimeError('mean / std apply to uint8 frames; float input is taken as already normalised')
-            if x.dim() != 4:
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
                 raise RuntimeError('stem expects (frames, 3, S, S) input, got %s' % (tuple(x.shape),))
-            x = _c(x)
-            Fr, cin, S, S2 = x.shape
-            if cin != 3 or S != S2:
-                raise RuntimeError('stem expects (frames, 3, S, S) input, got %s' % (tuple(x.shape),))
+            S = x.shape[2]
+        self.x, self.mean, self.std, self.view, self.S, self.inference = _c(x), mean, std, view, S, inference
+
+    def forward(self, weight, dtype):
+        """-> u1 (frames * Ho * Ho, 32), the direct kernel"""
+        if self.mean is None:
+            return ops.conv1_fwd(self.x, weight, dtype)
+        if self.inference:
+            return ops.conv1_fwd_u8(self.x, self.mean, self.std, weight, dtype)
+        return ops.conv1_fwd_u8_view(self.x, self.view, self.S, self.mean, self.std, weight, dtype, checked=True)
+
+    def im2col(self, dtype):
+        """-> col (frames * Ho * Ho, 32): columns (dy, dx, ci) + 5 zero columns, the GEMM route's operand"""
+        if self.mean is None:
+            return ops.im2col_conv1(self.x, dtype)
+        return ops.im2col_conv1_u8(self.x, self.view, self.S, self.mean, self.std, dtype, checked=True)
+
+    def wgrad(self, du1):
+        """-> dW float32 (32, 32), column k = ci*9 + dy*3 + dx (27..31 zero), the direct kernel (Ho <= 128)"""
+        if self.mean is None:
+            return ops.conv1_wgrad(du1, self.x)
+        return ops.conv1_wgrad_u8(du1, self.x, self.view, self.S, self.mean, self.std, checked=True)
+
+
+class StemFn(Function):
+    """y = Xception.low_level_features(x); y: (Fr,h,w,728) NHWC in `dtype`.  `src` = Conv1Input of x (x itself is an argument
+    for autograd's sake).  `buffers` = [running_mean, running_var] * 11 in bn_names() order (updated in place when
+    training).  conv1 and its weight gradient run as the direct kernels in bfloat16 and on the inference entry, as im2col +
+    GEMM in float32 and for the weight gradient when Ho > 128, on whichever input `src` describes; the backward keeps
+    `src` (the bytes and the view table, or the float clip), and only a float clip has an input gradient."""
+
+    @staticmethod
+    def forward(ctx, x, dtype, training, buffers, src, *params):
+        if src.inference and training:              # (stem_forward also refuses it with gradients enabled)
+            raise RuntimeError('the stem\'s inference entry needs eval mode: it has no backward')
+        Fr, S = src.x.shape[0], src.S
         L = _lib.lib()
         dev = x.device
         P = dict(zip(param_names(), params))
@@ -301,32 +320,16 @@ class StemFn(Function):
             rm, rv = bufs[name]
             return pointwise_bn(xin, w, M, C, P[name + '.weight'], P[name + '.bias'], rm, rv, training)
 
-        # conv1 (3->32, 3x3, s2, p0) as im2col + GEMM
+        # conv1 (3->32, 3x3, s2, p0); w1 is the GEMM form, for the float32 route and the input gradient
         H1 = (S - 3) // 2 + 1
         M1 = Fr * H1 * H1
-        # conv1 directly from the fp32 NCHW clip (one thread per output pixel); w1 is the GEMM form for the backward
         w1 = _conv1_weight(P['conv1.weight'], dtype)
-        if bytesrc is not None:
-            bmean, bstd, bview = bytesrc[0], bytesrc[1], bytesrc[2]
-            if dtype == torch.bfloat16:
-                u1 = ops.conv1_fwd_u8_view(x, bview, S, bmean, bstd, P['conv1.weight'], dtype, checked=True)
-            else:                           # fp32 parity mode: im2col + GEMM, as the float path below
-                col1 = ops.im2col_conv1_u8(x, bview, S, bmean, bstd, dtype, checked=True)
-                u1 = ops.linear_fwd(col1, w1, blocked=False)
-                del col1
-        elif u8:
-            u1 = ops.conv1_fwd_u8(x, infer[0], infer[1], P['conv1.weight'], dtype)
-        elif dtype == torch.bfloat16 or infer is not None:
-            u1 = torch.empty((M1, 32), dtype=dtype, device=dev)
-            _lib.check(L.istvt_conv1_fwd(x.data_ptr(), P['conv1.weight'].detach().contiguous().data_ptr(), u1.data_ptr(),
-                                         Fr, S, ops._DT[dtype], _stream()), 'istvt_conv1_fwd')
+        if dtype == torch.bfloat16 or src.inference:
+            u1 = src.forward(P['conv1.weight'], dtype)
         else:
             # fp32 parity mode keeps im2col + GEMM: with the golden recipe's structured weights a different fp32
             # summation order flips ReLU masks at |z| ~ 1e-7 and moves early-layer gradients by 1e-2
-            col1 = torch.empty((M1, 32), dtype=dtype, device=dev)
-            _lib.check(L.istvt_im2col_conv1(x.data_ptr(), col1.data_ptr(), Fr, S, ops._DT[dtype], _stream()), 'istvt_im2col_conv1')
-            u1 = ops.linear_fwd(col1, w1, blocked=False)
-            del col1
+            u1 = ops.linear_fwd(src.im2col(dtype), w1, blocked=False)
         bn1 = bn('bn1', u1, M1, 32)
         # conv2 (32->64, 3x3, p0): im2col applies bn1 + ReLU on load
         H2 = H1 - 2
@@ -347,7 +350,7 @@ class StemFn(Function):
         # block1's first depthwise convolution applies bn2 + ReLU as it stages its input tile -- rounded to the storage type
         # there, exactly where the separate pass rounded it --, its weight gradient takes the same pair on load, and the
         # stride-2 skip path applies them to the quarter of the pixels it keeps.
-        sv.update(x=x, bytesrc=bytesrc, S=S, Fr=Fr, H1=H1, H2=H2, u1=u1, bn1=bn1, u2=u2, bn2=bn2, w1=w1, w2=w2)
+        sv.update(src=src, S=S, Fr=Fr, H1=H1, H2=H2, u1=u1, bn1=bn1, u2=u2, bn2=bn2, w1=w1, w2=w2)
 
         fuse_in = os.environ.get('ISTVT_STEM_MATERIALISE_A2', '0') != '1'     # (1: the separate bn_apply pass, for A/B runs)
         X, H = (u2 if fuse_in else bn_apply(u2, bn2, M2, 64, True)), H2
@@ -388,7 +391,7 @@ class StemFn(Function):
         sv['training'] = training
         sv['dtype'] = dtype
         ctx.sv = sv
-        ctx.need_dx = x.requires_grad and bytesrc is None
+        ctx.need_dx = x.requires_grad and src.mean is None
         return X.view(Fr, H, H, 728)
 
     @staticmethod
@@ -535,33 +538,17 @@ class StemFn(Function):
             grads['conv2.weight'] = dW2 if dtype == torch.bfloat16 else dW2.view(64, 3, 3, 32).permute(0, 3, 1, 2).contiguous()
         du1 = bn_bwd(dz1, sv['u1'], sv['bn1'], 'bn1', M1, 32)
         del dz1
-        bsrc = sv['bytesrc']
-        if bsrc is not None and dtype == torch.bfloat16 and H1 <= 128:
-            dW1 = ops.conv1_wgrad_u8(du1.contiguous(), sv['x'], bsrc[2], S, bsrc[0], bsrc[1], checked=True)
+        src = sv['src']
+        if dtype == torch.bfloat16 and H1 <= 128:
+            dW1 = src.wgrad(du1.contiguous())                                    # [32][(ci,dy,dx) + 5 unused]
             grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).contiguous()
-        elif bsrc is not None:
-            col1 = ops.im2col_conv1_u8(sv['x'], bsrc[2], S, bsrc[0], bsrc[1], dtype, checked=True)
-            dW1 = ops.linear_wgrad(du1, col1)                                    # [32][(dy,dx,ci) + 5 zero columns]
-            grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
-            del col1
-        elif dtype == torch.bfloat16 and H1 <= 128:
-            du1 = du1.contiguous()
-            dW1 = torch.zeros((32, 32), dtype=torch.float32, device=du1.device)      # [co][(ci,dy,dx) + 5 unused]
-            slabs = torch.empty((L.istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=du1.device)
-            _lib.check(L.istvt_conv1_wgrad(du1.data_ptr(), sv['x'].data_ptr(), slabs.data_ptr(), dW1.data_ptr(), Fr, S, dtc,
-                                           _stream()), 'istvt_conv1_wgrad')
-            grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).contiguous()
-            del slabs
         else:
-            col1 = torch.empty((M1, 32), dtype=dtype, device=du1.device)
-            _lib.check(L.istvt_im2col_conv1(sv['x'].data_ptr(), col1.data_ptr(), Fr, S, dtc, _stream()), 'istvt_im2col_conv1')
-            dW1 = ops.linear_wgrad(du1, col1)                                    # [32][(dy,dx,ci) + 5 zero columns]
+            dW1 = ops.linear_wgrad(du1, src.im2col(dtype))                       # [32][(dy,dx,ci) + 5 zero columns]
             grads['conv1.weight'] = dW1[:, :27].reshape(32, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
-            del col1
         dx = None
         if ctx.need_dx:
             dcol1 = ops.linear_dgrad(du1, sv['w1'], blocked=False)
-            dx = torch.empty_like(sv['x'])
+            dx = torch.empty_like(src.x)
             _lib.check(L.istvt_col2im_conv1(dcol1.data_ptr(), dx.data_ptr(), Fr, S, dtc, _stream()), 'istvt_col2im_conv1')
         ctx.sv = None
         # The two dense convolutions' weight gradients come out of a slab reduce as fresh tensors.  With the fused bucket they
@@ -574,7 +561,7 @@ class StemFn(Function):
                 q.grad.add_(grads[n].view(q.shape))
                 grads[n] = None
         out = [None if grads[n] is None else grads[n].view(P[n].shape) for n in param_names()]
-        return (dx, None, None, None, None, None, *out)
+        return (dx, None, None, None, None, *out)
 
 
 def _norm_vec(v, name: str, device) -> Tensor:
@@ -589,20 +576,18 @@ def _norm_vec(v, name: str, device) -> Tensor:
     return t.to(device)
 
 
-def byte_source(x: Tensor, mean, std, view, crop):
-    """StemFn's `bytesrc` for uint8 (frames, Hs, Ws, 3) on the device: (mean, std, view table on the device or None, S).
-    A host view is validated (clips.check_views) and uploaded; a device view is taken as validated by the caller."""
+def byte_source(x: Tensor, mean, std, view=None, crop=None, inference: bool = False) -> Conv1Input:
+    """StemFn's `src` for uint8 (frames, Hs, Ws, 3) on the device.  A host view is validated (clips.check_views) and
+    uploaded; a device view is taken as validated by the caller."""
     from . import clips
-    Fr, Hs, Ws = x.shape[0], x.shape[1], x.shape[2]
     if view is not None and torch.is_tensor(view) and view.is_cuda:
         if crop is None:
             raise ValueError('a view needs the crop side S')
-        vdev = view
-    else:
-        v = clips.check_views(view, Fr, Hs, Ws, crop)
-        vdev = None if v is None else v.contiguous().to(x.device, non_blocking=True)
-    S = Hs if crop is None else int(crop)
-    return (_norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device), vdev, S)
+    elif not inference:
+        view = clips.check_views(view, x.shape[0], x.shape[1], x.shape[2], crop)
+        view = None if view is None else view.contiguous().to(x.device, non_blocking=True)
+    return Conv1Input(x, _norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device), view,
+                      None if crop is None else int(crop), inference)
 
 
 def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None, std=None, inference: bool = False,
@@ -619,30 +604,28 @@ def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None
     here, before any launch) or None; crop: the side S of the view (default: the frames' own side, which then must be
     square).  conv1 and its weight gradient read the bytes through the view, with the bits of the float path on
     clips.to_float(x, mean, std, view, crop) made on the host; there is no input gradient."""
-    infer = bytesrc = None
+    u8 = x.dtype == torch.uint8
     if train_bytes:
-        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        if not u8 or x.dim() != 4 or x.shape[3] != 3:
             raise RuntimeError('train_bytes expects channels-last (frames, Hs, Ws, 3) uint8 input, got %s %s'
                                % (x.dtype, tuple(x.shape)))
-        if mean is None or std is None:
-            raise RuntimeError('uint8 frames need mean and std (3 values each)')
         if inference:
             raise RuntimeError('train_bytes and inference are two different entries')
-        _req(x, 'input clip')
-        bytesrc = byte_source(x, mean, std, view, crop)
     elif view is not None or crop is not None:
         raise RuntimeError('view / crop belong to the training byte entry (train_bytes=True)')
-    elif x.dtype == torch.uint8:
-        if mean is None or std is None:
-            raise RuntimeError('uint8 frames need mean and std (3 values each)')
-        infer = (_norm_vec(mean, 'mean', x.device), _norm_vec(std, 'std', x.device))
-    elif mean is not None or std is not None:
+    if u8 and (mean is None or std is None):
+        raise RuntimeError('uint8 frames need mean and std (3 values each)')
+    if not u8 and (mean is not None or std is not None):
         raise RuntimeError('mean / std apply to uint8 frames; float input is taken as already normalised')
-    elif inference:
-        infer = (None, None)
-    if infer is not None and (xcep.training or torch.is_grad_enabled()):
+    inference = inference or (u8 and not train_bytes)
+    if inference and (xcep.training or torch.is_grad_enabled()):
         raise RuntimeError('the stem\'s inference entry (uint8 frames / VideoScorer) needs eval mode and torch.no_grad(): '
                            'it has no backward (no conv1 weight gradient from bytes)')
+    if u8:
+        _req(x, 'input clip')
+        src = byte_source(x, mean, std, view, crop, inference)
+    else:
+        src = Conv1Input(x, inference=inference)
     # The tensors are looked up through their owning submodules every call (a load_state_dict / .to() may have replaced
     # them): the owners are cached on the module and re-validated by identity (get_submodule per distinct owner), the
     # parameters / buffers then come straight out of the owners' dicts.  get_parameter / get_buffer by dotted name, 55 per
@@ -664,7 +647,7 @@ def stem_forward(x: Tensor, xcep: torch.nn.Module, dtype: torch.dtype, mean=None
     if x.is_cuda:
         stats_arena_reset(x.device)          # one fill for every statistics accumulator of this step
         ops.refresh_stale_operands()         # one grouped cast for every bf16 weight operand the optimizer invalidated
-    y = StemFn.apply(x, dtype, xcep.training, buffers, infer, bytesrc, *params)
+    y = StemFn.apply(src.x, dtype, xcep.training, buffers, src, *params)
     if xcep.training:
         torch._foreach_add_([owner._buffers['num_batches_tracked'] for owner in refs[2]], 1)     # one launch, not 11
     return y

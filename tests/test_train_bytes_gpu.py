@@ -44,39 +44,6 @@ def _norm_dev(norm):
     return torch.tensor(norm[0]).cuda(), torch.tensor(norm[1]).cuda()
 
 
-def _raw(name, *args):
-    from istvt_amd import _lib
-    return getattr(_lib.lib(), name)(*args)
-
-
-def _conv1_fwd(x, w, dtype):
-    from istvt_amd import _lib, ops
-    Fr, S = x.shape[0], x.shape[2]
-    Ho = (S - 3) // 2 + 1
-    ref = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device='cuda')
-    _lib.check(_raw('istvt_conv1_fwd', x.data_ptr(), w.data_ptr(), ref.data_ptr(), Fr, S, ops._DT[dtype], ops._stream()), 'istvt_conv1_fwd')
-    return ref
-
-
-def _conv1_wgrad(du1, x):
-    from istvt_amd import _lib, ops
-    Fr, S = x.shape[0], x.shape[2]
-    dW = torch.zeros((32, 32), dtype=torch.float32, device='cuda')
-    slabs = torch.empty((_lib.lib().istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device='cuda')
-    _lib.check(_raw('istvt_conv1_wgrad', du1.data_ptr(), x.data_ptr(), slabs.data_ptr(), dW.data_ptr(), Fr, S, ops._DT[du1.dtype],
-                    ops._stream()), 'istvt_conv1_wgrad')
-    return dW
-
-
-def _im2col(x, dtype):
-    from istvt_amd import _lib, ops
-    Fr, S = x.shape[0], x.shape[2]
-    Ho = (S - 3) // 2 + 1
-    col = torch.empty((Fr * Ho * Ho, 32), dtype=dtype, device='cuda')
-    _lib.check(_raw('istvt_im2col_conv1', x.data_ptr(), col.data_ptr(), Fr, S, ops._DT[dtype], ops._stream()), 'istvt_im2col_conv1')
-    return col
-
-
 # ---- kernels ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('dtype', DTYPES, ids=IDS)
 @pytest.mark.parametrize('side', [96, 139, 224, 300])
@@ -87,7 +54,7 @@ def test_conv1_fwd_from_a_view_bit_identical(pkg, side, dtype):
     w = torch.randn((32, 3, 3, 3), generator=torch.Generator().manual_seed(side + 1)).cuda()
     Ho = (side - 3) // 2 + 1
     for name, u8, view in _cases(side):
-        ref = _conv1_fwd(clips.to_float(u8, norm[0], norm[1], view, side).cuda(), w, dtype)
+        ref = ops.conv1_fwd(clips.to_float(u8, norm[0], norm[1], view, side).cuda(), w, dtype)
         assert torch.isfinite(ref.float()).all() and float(ref.float().abs().max()) > 0
         dev = u8.cuda()
         out = ops.conv1_fwd_u8_view(dev, view, side, m, s, w, dtype)
@@ -117,14 +84,14 @@ def test_conv1_wgrad_from_bytes_bit_identical(pkg, side, dtype):
         n = u8.shape[0]
         du1 = torch.randn((n * Ho * Ho, 32), generator=torch.Generator().manual_seed(side)).cuda().to(dtype)
         x = clips.to_float(u8, norm[0], norm[1], view, side)
-        ref = _conv1_wgrad(du1, x.cuda())
+        ref = ops.conv1_wgrad(du1, x.cuda())
         dev = u8.cuda()
         out = ops.conv1_wgrad_u8(du1, dev, view, side, m, s)
         assert float(ref.abs().max()) > 0
         assert torch.equal(out, ref), name
         assert float(out[:, 27:].abs().max()) == 0.0
         out1 = ops.conv1_wgrad_u8(du1[Ho * Ho:], dev[1:], None if view is None else view[1:].contiguous(), side, m, s)
-        assert torch.equal(out1, _conv1_wgrad(du1[Ho * Ho:], x[1:].cuda())), name
+        assert torch.equal(out1, ops.conv1_wgrad(du1[Ho * Ho:], x[1:].cuda())), name
         # float64 conv2d backward on bf16-rounded patches and du1 (what the MFMA is fed), as gpu_checks.conv_dense_check
         xq = x.to(torch.bfloat16).double()
         wd = torch.zeros((32, 3, 3, 3), dtype=torch.float64, requires_grad=True)
@@ -153,7 +120,7 @@ def test_im2col_from_bytes_bit_identical(pkg, side, dtype):
     m, s = _norm_dev(norm)
     Ho = (side - 3) // 2 + 1
     for name, u8, view in _cases(side):
-        ref = _im2col(clips.to_float(u8, norm[0], norm[1], view, side).cuda(), dtype)
+        ref = ops.im2col_conv1(clips.to_float(u8, norm[0], norm[1], view, side).cuda(), dtype)
         dev = u8.cuda()
         out = ops.im2col_conv1_u8(dev, view, side, m, s, dtype)
         assert torch.equal(out, ref), name

@@ -46,19 +46,26 @@ def _windows(x, starts, T):
 
 
 # ---- kernels ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
-@pytest.mark.parametrize('norm', [IMAGENET, HALF], ids=['imagenet', 'half'])
-@pytest.mark.parametrize('side', [96, 139, 224, 300])
-def test_conv1_from_bytes_bit_identical(pkg, side, norm, dtype):
-    from istvt_amd import _lib, ops
+# Row-by-row staging above side 300, 2 frames each, bf16.  Side 1001: odd, so every staged row has another lead; a row pitch of
+# 3024 bytes lets at most 7 output rows into the 48 KiB budget and the chooser takes R = 4 (Ho = 500: 4..7 fill the 256-thread
+# passes equally).  Side 525: the budget itself decides, R = 14 (31 rows of pitch 1600 do not fit; the contiguous budget took
+# 15), and the last group of a frame has 10 of its 14 rows.
+CONV1_CASES = [pytest.param(side, norm, dtype, 3, id='%d-%s-%s' % (side, nid, did))
+               for dtype, did in ((torch.float32, 'f32'), (torch.bfloat16, 'bf16'))
+               for norm, nid in ((IMAGENET, 'imagenet'), (HALF, 'half')) for side in (96, 139, 224, 300)]
+CONV1_CASES.append(pytest.param(1001, IMAGENET, torch.bfloat16, 2, id='1001-imagenet-bf16'))
+CONV1_CASES.append(pytest.param(525, HALF, torch.bfloat16, 2, id='525-half-bf16'))
+
+
+@pytest.mark.parametrize('side,norm,dtype,n', CONV1_CASES)
+def test_conv1_from_bytes_bit_identical(pkg, side, norm, dtype, n):
+    from istvt_amd import ops
     mean, std = norm
-    u8 = _video(3, side, side)
+    u8 = _video(n, side, side)
     w = torch.randn((32, 3, 3, 3), generator=torch.Generator().manual_seed(side + 1)).cuda()
     x = _normalise(u8, mean, std).cuda()
     Ho = (side - 3) // 2 + 1
-    ref = torch.empty((3 * Ho * Ho, 32), dtype=dtype, device='cuda')
-    _lib.check(_lib.lib().istvt_conv1_fwd(x.data_ptr(), w.data_ptr(), ref.data_ptr(), 3, side, ops._DT[dtype],
-                                          ops._stream()), 'istvt_conv1_fwd')
+    ref = ops.conv1_fwd(x, w, dtype)
     m, s = torch.tensor(mean).cuda(), torch.tensor(std).cuda()
     dev = u8.cuda()
     out = ops.conv1_fwd_u8(dev, m, s, w, dtype)
@@ -67,10 +74,32 @@ def test_conv1_from_bytes_bit_identical(pkg, side, norm, dtype):
     # a view that starts in the middle of the allocation (frame 1 on: an odd byte offset at odd sides)
     out1 = ops.conv1_fwd_u8(dev[1:], m, s, w, dtype)
     assert torch.equal(out1, ref[Ho * Ho:])
+    # the inference entry is the identity view of the training entry
+    assert torch.equal(out, ops.conv1_fwd_u8_view(dev, None, side, m, s, w, dtype))
     with pytest.raises(RuntimeError):
         ops.conv1_fwd_u8(dev.permute(0, 3, 1, 2), m, s, w, dtype)
     with pytest.raises(TypeError):
         ops.conv1_fwd_u8(x, m, s, w, dtype)
+
+
+def test_byte_entries_refuse_sides_past_4096(pkg):
+    """side 4097: the shape error from all three byte entries that stage rows, before any launch (the buffers are whole, so a
+    launch would be a wrong answer here, not a fault)"""
+    from istvt_amd import _lib, ops
+    L, S = _lib.lib(), 4097
+    Ho = (S - 3) // 2 + 1
+    x = torch.zeros((1, S, S, 3), dtype=torch.uint8, device='cuda')
+    out = torch.empty((Ho * Ho, 32), dtype=torch.bfloat16, device='cuda')
+    m, s = torch.tensor(HALF[0]).cuda(), torch.tensor(HALF[1]).cuda()
+    w = torch.zeros((32, 3, 3, 3), device='cuda')
+    st, bf16 = ops._stream(), ops._DT[torch.bfloat16]
+    assert L.istvt_conv1_fwd_u8(x.data_ptr(), m.data_ptr(), s.data_ptr(), w.data_ptr(), out.data_ptr(), 1, S, bf16, st) == -3
+    assert L.istvt_conv1_fwd_u8_view(x.data_ptr(), x.numel(), S, S, None, m.data_ptr(), s.data_ptr(), w.data_ptr(),
+                                     out.data_ptr(), 1, S, bf16, st) == -3
+    assert L.istvt_im2col_conv1_u8(x.data_ptr(), x.numel(), S, S, None, m.data_ptr(), s.data_ptr(), out.data_ptr(), 1, S, bf16,
+                                   st) == -3
+    with pytest.raises(RuntimeError, match='invalid shape'):
+        ops.conv1_fwd_u8(x, m, s, w, torch.bfloat16)
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
