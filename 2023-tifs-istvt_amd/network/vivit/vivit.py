@@ -239,17 +239,18 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import explain
         return explain.relevance(self, x, index)
 
-    def score_video(self, frames, **kw):
-        """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S):
-        istvt_amd.video.VideoScorer(self, **kw).score(frames)"""
+    def score_video(self, frames, boxes=None, **kw):
+        """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S), or whole uint8
+        frames (N, Hs, Ws, 3) with one face box (y0, x0, h, w) each in `boxes`, int32 (N, 4):
+        istvt_amd.video.VideoScorer(self, **kw).score(frames, boxes)"""
         from istvt_amd import video
-        return video.VideoScorer(self, **kw).score(frames)
+        return video.VideoScorer(self, **kw).score(frames, boxes=boxes)
 
-    def explain_video(self, frames, index=0, **kw):
-        """Per-frame relevance maps of one video (frames as score_video takes them) for output `index`:
-        istvt_amd.video.VideoScorer(self, **kw).explain(frames, index)"""
+    def explain_video(self, frames, index=0, boxes=None, **kw):
+        """Per-frame relevance maps of one video (frames and boxes as score_video takes them) for output `index`:
+        istvt_amd.video.VideoScorer(self, **kw).explain(frames, index, boxes)"""
         from istvt_amd import video
-        return video.VideoScorer(self, **kw).explain(frames, index)
+        return video.VideoScorer(self, **kw).explain(frames, index, boxes=boxes)
 
     def set_crop_side(self, S):
         """The side S of the crops a view cuts out of larger uint8 source frames.  A token grid does not name it (sixteen

@@ -901,6 +901,50 @@ def im2col_conv1_u8(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tens
     return col
 
 
+def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
+    """Frames and boxes (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, boxes int32 [n,4] = (y0, x0, h,
+    w) per frame or, for clips, [B,4] spread over the T frames of a clip -> uint8 [n,S,S,3] / [B,T,S,S,3]: every box cut out
+    and resized with the antialiased bilinear filter of clips.crop_resize_host.  Boxes are validated on the host
+    (clips.check_boxes) before any launch and then uploaded; checked=True takes a per-frame device table the caller has
+    validated already.  `out` (uint8, contiguous, of the result's shape) is written when given."""
+    from . import clips
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('crop_resize_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
+        raise RuntimeError('crop_resize_u8 expects channels-last (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3) uint8 input, got %s'
+                           % (tuple(frames.shape),))
+    if frames.numel() == 0:
+        raise RuntimeError('crop_resize_u8: empty input %s' % (tuple(frames.shape),))
+    S = int(S)
+    lead = tuple(frames.shape[:-3])
+    Hs, Ws = frames.shape[-3], frames.shape[-2]
+    if S < 1 or S > 480:
+        raise ValueError('crop_resize_u8: the output side must lie in [1, 480], got %d' % S)
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('crop_resize_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
+    src = _c(frames).view((-1, Hs, Ws, 3))
+    n = src.shape[0]
+    if checked:
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != src.device:
+            raise RuntimeError('crop_resize_u8: a checked box table is int32 (%d, 4) on %s' % (n, src.device))
+        bdev = _c(boxes)
+    else:
+        b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
+        if frames.dim() == 5:
+            b = clips.per_frame_boxes(b, frames.shape[1])
+        bdev = b.contiguous().to(src.device)
+    shape = lead + (S, S, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != src.device or not out.is_contiguous():
+        raise RuntimeError('crop_resize_u8: out must be contiguous uint8 %s on %s' % (shape, src.device))
+    with prof('crop_resize_u8', n * S * S * 3):        # + the boxes' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_crop_resize_u8(src.data_ptr(), src.numel(), Hs, Ws, bdev.data_ptr(), out.data_ptr(), n, S,
+                                                   _stream()), 'istvt_crop_resize_u8')
+    return out
+
+
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,
                need_dfeats: bool) -> Optional[Tensor]:
     dx, lddx = rows(_req(dx))

@@ -4,6 +4,8 @@ video out.
     scorer = VideoScorer(model, stride=1)
     res = scorer.score(frames)                       # uint8 (N, S, S, 3), host or device; or float32 (N, 3, S, S)
     ex = scorer.explain(frames)                      # the same windows through the relevance rollout, fused per frame
+    res = scorer.score(full, boxes=boxes)            # whole frames uint8 (N, Hs, Ws, 3) and one face box per frame, int32
+                                                     # (N, 4) = (y0, x0, h, w): cropped and resized on the device
     scorer.reset()
     for chunk in stream:                             # the same windows, as the frames arrive
         logits, starts = scorer.push(chunk)
@@ -63,6 +65,20 @@ def check_frames(frames) -> str:
             raise ValueError('float frames must be normalised (N, 3, S, S), got %s' % (tuple(frames.shape),))
         return 'f32'
     raise ValueError('frames must be uint8 or float32, got %s' % frames.dtype)
+
+
+def check_boxed_frames(frames, boxes, side: Optional[int]):
+    """Whole frames with one face box each (DESIGN.md "Frames and boxes"): frames uint8 (N, Hs, Ws, 3) of any size, boxes
+    int32 (N, 4) = (y0, x0, h, w) inside the frame with 1 <= h, w <= 8 side.  -> the validated box table on the host."""
+    from . import clips
+    if side is None:
+        raise ValueError('boxes need the side of the crops: VideoScorer(model, side=S) or model.set_crop_side(S)')
+    if not torch.is_tensor(frames):
+        raise ValueError('frames must be a torch tensor, got %s' % type(frames).__name__)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError('with boxes, frames must be uint8 channels-last (N, Hs, Ws, 3) as a decoder delivers them, got %s %s'
+                         % (frames.dtype, tuple(frames.shape)))
+    return clips.check_boxes(boxes, int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]), int(side))
 
 
 class Step(NamedTuple):
@@ -197,11 +213,12 @@ class VideoScorer:
                   rounded up to a multiple of 8 for push()).
     mean, std     per-channel normalisation of uint8 frames, (u / 255 - mean) / std; float input is taken as normalised.
     cover_tail    score() / flush() add the window at N - T when the strided windows leave the last frames uncovered.
+    side          the side of the crops made of whole frames when a call passes `boxes` (default: the model's crop_side).
     """
 
     def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
                  capacity: Optional[int] = None, mean: Sequence[float] = DEFAULT_MEAN, std: Sequence[float] = DEFAULT_STD,
-                 cover_tail: bool = True):
+                 cover_tail: bool = True, side: Optional[int] = None):
         vit = getattr(model, 'vit', None)
         if vit is None or not hasattr(model, 'xcep') or not hasattr(vit, 'forward_tokens'):
             raise TypeError('VideoScorer: expected an XceptionVidTr, got %s' % type(model).__name__)
@@ -217,6 +234,9 @@ class VideoScorer:
         self.capacity = capacity
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.cover_tail = bool(cover_tail)
+        if side is not None and int(side) < 3:
+            raise ValueError('VideoScorer: side must be at least 3, got %r' % (side,))
+        self.side = None if side is None else int(side)
         self._norm = None                  # (device, mean tensor, std tensor)
         self.reset()
 
@@ -234,9 +254,21 @@ class VideoScorer:
             raise RuntimeError('VideoScorer: the model must be on a ROCm device (no CPU fallback exists for the ISTVT hot path)')
         return dev
 
-    def _stem(self, x: Tensor, kind: str, dev) -> Tensor:
+    def _side(self) -> Optional[int]:
+        return self.side if self.side is not None else getattr(self.model, 'crop_side', None)
+
+    def _boxed(self, frames: Tensor, boxes):
+        """-> (validated boxes on the device, side) of a call with boxes; raises before anything is launched"""
+        side = self._side()
+        b = check_boxed_frames(frames, boxes, side)
+        dev = self._device()
+        return b.contiguous().to(dev, non_blocking=True), side
+
+    def _stem(self, x: Tensor, kind: str, dev, boxes: Optional[Tensor] = None, side: Optional[int] = None) -> Tensor:
         if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
             x = x.contiguous().pin_memory().to(dev, non_blocking=True)
+        if boxes is not None:              # whole frames: this batch's crops, made where the frames are
+            x = ops.crop_resize_u8(x, boxes, side, checked=True)
         xcep = self.model.xcep.model
         if kind == 'u8':
             if self._norm is None or self._norm[0] != dev:
@@ -256,15 +288,19 @@ class VideoScorer:
         if head < k:
             self._ring[:k - head].copy_(feats[head:])
 
-    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev, rollout=None):
+    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev, rollout=None,
+             boxes: Optional[Tensor] = None, side: Optional[int] = None):
         """-> (logits (W, num_classes) float32 on the device, list of starts) of the windows the steps ran.  rollout:
-        what runs a batch of windows instead of the plain forward, (tokens, windows, h*w) -> logits (explain())."""
+        what runs a batch of windows instead of the plain forward, (tokens, windows, h*w) -> logits (explain()).
+        boxes: the validated device table of `frames` (row i for frames[i]); each stem batch is cropped to side x side."""
         vit = self.model.vit
         outs, starts = [], []
         with _eval_mode(self.model), torch.no_grad():
             for st in steps:
                 if st.kind == 'frames':
-                    feats = self._stem(frames[st.first - base:st.first - base + st.count], kind, dev)
+                    lo = st.first - base
+                    feats = (self._stem(frames[lo:lo + st.count], kind, dev) if boxes is None else
+                             self._stem(frames[lo:lo + st.count], 'u8', dev, boxes[lo:lo + st.count], side))
                     if self._ring is None:
                         self._ring = torch.empty((self._plan.capacity,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
                     elif tuple(self._ring.shape[1:]) != tuple(feats.shape[1:]) or self._ring.dtype != feats.dtype:
@@ -282,19 +318,30 @@ class VideoScorer:
         logits = torch.cat(outs) if outs else torch.empty((0, nc), dtype=torch.float32, device=dev)
         return logits, starts
 
-    def push(self, frames: Tensor):
+    def push(self, frames: Tensor, boxes=None):
         """The next frames of the stream -> (logits (W, num_classes) float32 on the device, starts (W,) int64 on the host)
-        of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation."""
-        kind = check_frames(frames)
+        of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation.
+        boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); a stream keeps one mode."""
+        bdev = side = None
+        if boxes is None:
+            kind = check_frames(frames)
+        else:
+            side = self._side()
+            bhost = check_boxed_frames(frames, boxes, side)
+            kind = 'u8+boxes'
         if self._kind is not None and kind != self._kind:
+            if 'u8+boxes' in (kind, self._kind):
+                raise ValueError('VideoScorer: a stream takes boxes with every push or with none (reset() starts a new one)')
             raise ValueError('VideoScorer: a stream is either uint8 or float frames, not both (reset() starts a new one)')
         dev = self._device()
+        if boxes is not None:
+            bdev = bhost.contiguous().to(dev, non_blocking=True)
         if self._plan is None:
             cap = self.capacity if self.capacity is not None else -(-(self.T + self.frame_batch) // 8) * 8
             self._plan = RingPlan(self.T, self.stride, cap, self.frame_batch, self.window_batch)
         self._kind = kind
         base = self._plan.seen
-        logits, starts = self._run(self._plan.push(int(frames.shape[0])), frames, base, kind, dev)
+        logits, starts = self._run(self._plan.push(int(frames.shape[0])), frames, base, kind, dev, boxes=bdev, side=side)
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     def flush(self):
@@ -306,20 +353,28 @@ class VideoScorer:
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     # ---------------------------------------------------------------------------------------- whole video
-    def _whole_video(self, frames: Tensor, rollout=None):
+    def _whole_video(self, frames: Tensor, rollout=None, boxes=None):
         """every window of one video on a ring of its own -> (logits, list of starts, device)"""
-        kind = check_frames(frames)
+        bdev = side = None
+        if boxes is None:
+            kind = check_frames(frames)
+        else:
+            side = self._side()
+            bhost = check_boxed_frames(frames, boxes, side)
+            kind = 'u8+boxes'
         n = int(frames.shape[0])
         if n < self.T:
             raise ValueError('a video of %d frames is shorter than one window of %d' % (n, self.T))
         dev = self._device()
+        if boxes is not None:
+            bdev = bhost.contiguous().to(dev, non_blocking=True)
         saved = (self._plan, self._ring, self._kind)
         try:
             self._plan = RingPlan(self.T, self.stride, self.capacity if self.capacity is not None else n,
                                   self.frame_batch, self.window_batch)
             self._ring = None
             steps = self._plan.push(n, drain=False) + self._plan.flush(self.cover_tail)
-            logits, starts = self._run(steps, frames, 0, kind, dev, rollout)
+            logits, starts = self._run(steps, frames, 0, kind, dev, rollout, bdev, side)
         finally:
             self._plan, self._ring, self._kind = saved
         return logits, starts, dev
@@ -329,18 +384,21 @@ class VideoScorer:
         return VideoScore(logits, torch.tensor(starts, dtype=torch.int64).to(dev, non_blocking=True), logits.mean(0),
                           torch.sigmoid(logits).mean(0))
 
-    def score(self, frames: Tensor) -> VideoScore:
-        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own)."""
-        logits, starts, dev = self._whole_video(frames)
+    def score(self, frames: Tensor, boxes=None) -> VideoScore:
+        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own).  boxes: one
+        (y0, x0, h, w) per frame, int32 (N, 4), for whole frames uint8 (N, Hs, Ws, 3): each stem batch is cropped and resized
+        to side x side on the device (ops.crop_resize_u8) just before the stem -- the bits of score() on those crops."""
+        logits, starts, dev = self._whole_video(frames, boxes=boxes)
         res = self._video_score(logits, starts, dev)
         torch.cuda.current_stream(dev).synchronize()
         return res
 
-    def explain(self, frames: Tensor, index: int = 0) -> VideoExplanation:
+    def explain(self, frames: Tensor, index: int = 0, boxes=None) -> VideoExplanation:
         """Relevance maps of one video for output `index` (DESIGN.md "Explaining whole videos"): the windows, frames and
         stem pass of score(), every window batch through the gradient-weighted attention rollout of explain.relevance
         instead of the plain forward, and the windows' maps fused per frame (ops.relevance_fuse_windows).  The model is in
-        explain.relevance's state for the call and comes back as it was; a stream in progress is not disturbed."""
+        explain.relevance's state for the call and comes back as it was; a stream in progress is not disturbed.  With
+        boxes (as score() takes them) the maps are in crop coordinates."""
         from . import explain as _explain
         vit = self.model.vit
         rels = []
@@ -350,7 +408,7 @@ class VideoScorer:
             return rels[-1].logits
 
         with _explain._explaining(self.model):
-            logits, starts, dev = self._whole_video(frames, rollout)
+            logits, starts, dev = self._whole_video(frames, rollout, boxes)
             windows = _explain.Relevance(torch.cat([r.r_s for r in rels]), torch.cat([r.r_t for r in rels]), logits)
             fused = ops.relevance_fuse_windows(windows.r_s, windows.r_t, logits, starts, int(frames.shape[0]), index)
         res = VideoExplanation(self._video_score(logits, starts, dev), windows, *fused)

@@ -281,6 +281,15 @@ int istvt_conv1_wgrad_u8(const void* du1, const void* x, long total, int Hs, int
                          const float* std, float* slabs, float* dw, int frames, int S, int dtype, istvt_stream_t stream);
 int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* view, const float* mean, const float* std,
                           void* col, int frames, int S, int dtype, istvt_stream_t stream);
+/* Frames and boxes: frames uint8 [n][Hs][Ws][3] (`total` bytes readable at frames, >= n*Hs*Ws*3; nothing outside
+ * [frames, frames + total) is read, no alignment needed), boxes int32 [n][4] = (y0, x0, h, w) on the device, every box
+ * inside its frame with 1 <= h, w <= 8 S (the kernel forces a box that is not) -> out uint8 [n][S][S][3]: the box cut out
+ * and resized as torch's interpolate(mode='bilinear', align_corners=False, antialias=True) resizes the cropped image --
+ * per axis scale = n_in / S, sup = max(scale, 1), c = (i + 0.5) * scale, taps j in [max(int(c - sup + 0.5), 0),
+ * min(int(c + sup + 0.5), n_in)) with w_j = max(0, 1 - |(j - c + 0.5) / sup|) divided by their sum; horizontal pass first,
+ * kept in fp32, then vertical; byte = clamp(floor(v + 0.5), 0, 255).  h = w = S reproduces the slice.  S <= 480 (LDS). */
+int istvt_crop_resize_u8(const void* frames, long total, int Hs, int Ws, const int* boxes, void* out, int n, int S,
+                         istvt_stream_t stream);
 int istvt_conv2_fwd(const void* u1, const float* bnp, const void* w, void* u2, int frames, int H, int W,
                     istvt_stream_t stream);
 int istvt_conv2_dgrad(const void* du2, const void* w, const void* u1, const float* bnp, void* dz1, int frames, int H,

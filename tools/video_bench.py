@@ -4,6 +4,7 @@
     python tools/video_bench.py [--frames 256] [--size 224] [--T 8] [--depth 12] [--strides 1,2,4,8] [--json out.json]
     python tools/video_bench.py --conv1-only        # the two conv1 kernels alone, for a kernel trace
     python tools/video_bench.py --explain           # VideoScorer.explain against model.relevance on materialised windows
+    python tools/video_bench.py --boxes             # whole 1080 x 1920 frames and face boxes (DESIGN.md "Frames and boxes")
 
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
 float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
@@ -18,6 +19,14 @@ normalised float32 video, window_batch at a time (normalisation and upload again
 which that user would still have to write, is not part of (b) either).  Alternating, medians as above.  One further,
 instrumented explain() and one explain.overlay() of the whole video give the device time of the fuse and overlay kernels
 (events around the launches) and the overlay's rate against its algorithmic bytes.
+
+--boxes (DESIGN.md "Frames and boxes"): --frames whole frames of --full-size on the device, one random box of side
+--box-sides per frame.  Alternating, medians and spread as above: (a) score(frames, boxes=...); (b) score on the crops the
+same kernel made beforehand -- (a) - (b) is what the crop costs inside a call; (c) the host loop it replaces,
+clips.crop_resize_host on host frames + upload of the crops, twice on its own (it takes seconds: this project's plain
+torch restatement of the definition, not a tuned image library); (d) the kernel alone on all frames (events around the launch)
+against (e) a device-to-device copy that moves the same algorithmic bytes (box areas * 3 in, S * S * 3 out per frame: a
+copy of half their sum reads and writes that many).
 """
 import argparse
 import json
@@ -120,6 +129,87 @@ def explain_bench(a, model, u8, xn):
     return out
 
 
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def boxes_bench(a, model):
+    from istvt_amd import clips
+    Hs, Ws = (int(v) for v in a.full_size.split('x'))
+    lo, hi = (int(v) for v in a.box_sides.split('-'))
+    S, n = a.size, a.frames
+    g = torch.Generator().manual_seed(2)
+    host = torch.randint(0, 256, (n, Hs, Ws, 3), generator=g, dtype=torch.uint8)
+    h = torch.randint(lo, hi + 1, (n,), generator=g)
+    w = torch.randint(lo, hi + 1, (n,), generator=g)
+    y0 = torch.minimum((torch.rand(n, generator=g) * (Hs - h + 1)).long(), Hs - h)
+    x0 = torch.minimum((torch.rand(n, generator=g) * (Ws - w + 1)).long(), Ws - w)
+    boxes = torch.stack([y0, x0, h, w], dim=1).to(torch.int32)
+    frames = host.cuda()
+    bdev = boxes.cuda()
+    crops = ops.crop_resize_u8(frames, boxes, S)
+    bytes_in, bytes_out = int((h * w).sum()) * 3, n * S * S * 3
+    half = (bytes_in + bytes_out) // 2
+    src, dst = torch.empty(half, dtype=torch.uint8, device='cuda'), torch.empty(half, dtype=torch.uint8, device='cuda')
+    out = {'frames': n, 'full_size': [Hs, Ws], 'box_sides': [lo, hi], 'size': S, 'bytes_in': bytes_in, 'bytes_out': bytes_out,
+           'strides': {}}
+    tk, tc = [], []
+    for r in range(a.warmup + a.reps):
+        x = event_ms(lambda: ops.crop_resize_u8(frames, bdev, S, out=crops, checked=True))
+        y = event_ms(lambda: dst.copy_(src))
+        if r >= a.warmup:
+            tk.append(x)
+            tc.append(y)
+    sk, sc = stats(tk), stats(tc)
+    out['kernel'] = dict(sk, GB_per_s=(bytes_in + bytes_out) / sk['median_ms'] * 1e-6)
+    out['copy'] = dict(sc, GB_per_s=(bytes_in + bytes_out) / sc['median_ms'] * 1e-6)
+    print('crop_resize_u8: %d frames, %.1f MB in + %.1f MB out | kernel %.3f ms (%.3f-%.3f) = %.0f GB/s | device copy of the '
+          'same bytes %.3f ms (%.3f-%.3f) = %.0f GB/s | kernel / copy x%.2f'
+          % (n, bytes_in * 1e-6, bytes_out * 1e-6, sk['median_ms'], sk['min_ms'], sk['max_ms'], out['kernel']['GB_per_s'],
+             sc['median_ms'], sc['min_ms'], sc['max_ms'], out['copy']['GB_per_s'], sk['median_ms'] / sc['median_ms']), flush=True)
+    for stride in [int(s) for s in a.strides.split(',')]:
+        scorer = video.VideoScorer(model, stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch, side=S)
+        res = {}
+
+        def run_boxed():
+            res['a'] = scorer.score(frames, boxes=boxes).window_logits
+
+        def run_crops():
+            res['b'] = scorer.score(crops).window_logits
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_boxed), timed(run_crops)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        sa, sb = stats(ta), stats(tb)
+        rec = {'boxed': sa, 'crops': sb, 'equal_bits': bool(torch.equal(res['a'], res['b'])),
+               'crop_cost_ms': sa['median_ms'] - sb['median_ms'],
+               'crop_cost_share': (sa['median_ms'] - sb['median_ms']) / sb['median_ms']}
+        out['strides'][str(stride)] = rec
+        print('boxes stride %d: score(frames, boxes) %.2f ms (%.2f-%.2f) | score(crops) %.2f ms (%.2f-%.2f) | difference %.2f ms = '
+              '%.2f %% | equal bits %s' % (stride, sa['median_ms'], sa['min_ms'], sa['max_ms'], sb['median_ms'], sb['min_ms'],
+                                          sb['max_ms'], rec['crop_cost_ms'], 100 * rec['crop_cost_share'], rec['equal_bits']),
+              flush=True)
+    res = {}
+
+    def run_host():
+        res['c'] = clips.crop_resize_host(host, boxes, S).pin_memory().cuda()
+    clips.crop_resize_host(host[:4], boxes[:4], S)
+    th = [timed(run_host) for _ in range(2)]
+    differ = int((res['c'] != crops).sum())
+    out['host_loop'] = {'ms': th, 'bytes_differing_from_the_kernel': differ, 'of': crops.numel(),
+                        'max_abs_byte_diff': int((res['c'].int() - crops.int()).abs().max())}
+    print('host loop (crop_resize_host + upload): %.0f and %.0f ms | %d of %d bytes differ from the kernel, by at most %d'
+          % (th[0], th[1], differ, crops.numel(), out['host_loop']['max_abs_byte_diff']), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=256)
@@ -134,9 +224,12 @@ def main():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     ap.add_argument('--conv1-only', action='store_true')
     ap.add_argument('--explain', action='store_true')
+    ap.add_argument('--boxes', action='store_true')
+    ap.add_argument('--full-size', default='1080x1920')
+    ap.add_argument('--box-sides', default='150-600')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    a.strides = a.strides or ('1,8' if a.explain else '1,2,4,8')
+    a.strides = a.strides or ('1,8' if a.explain or a.boxes else '1,2,4,8')
     if not torch.cuda.is_available():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
@@ -146,6 +239,17 @@ def main():
     dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
     torch.manual_seed(0)
     model = XceptionVidTr(num_frames=a.T, grid=grid, depth=a.depth, compute_dtype=dt).cuda().eval()
+    if a.boxes:
+        out = dict(boxes_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
+                   window_batch=a.window_batch, reps=a.reps, warmup=a.warmup)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_boxes_bench': {'kernel_ms': out['kernel']['median_ms'], 'kernel_GB_per_s': out['kernel']['GB_per_s'],
+                                                'copy_GB_per_s': out['copy']['GB_per_s'],
+                                                'crop_cost_share': {k: v['crop_cost_share'] for k, v in out['strides'].items()}}}))
+        return
     g = torch.Generator().manual_seed(1)
     u8 = torch.randint(0, 256, (a.frames, a.size, a.size, 3), generator=g, dtype=torch.uint8)
     xn = (((u8.float() / 255) - torch.tensor(video.DEFAULT_MEAN)) / torch.tensor(video.DEFAULT_STD)).permute(0, 3, 1, 2).contiguous()
