@@ -90,6 +90,10 @@ SIGNATURES = {
     'istvt_add': [P, L, P, L, P, L, L, I, I, P],
     'istvt_sgd_momentum': [P, P, P, L, F, F, F, F, I, I, I, F, P],
     'istvt_adamw': [P, P, P, P, L, F, F, F, F, F, L, I, F, P],
+    'istvt_grad_norm': [P, L, F, F, I, P, L, P, P],
+    'istvt_grad_norm_ws_elems': [L],
+    'istvt_sgd_momentum_groups': [P, P, P, L, P, P, I, P, P, I, F, F, I, I, I, F, P, I, P],
+    'istvt_adamw_groups': [P, P, P, P, L, P, P, I, P, P, I, F, F, F, L, I, F, P, I, P],
 }
 
 _lib = None

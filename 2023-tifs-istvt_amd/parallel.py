@@ -193,9 +193,11 @@ class GradBucket:
         """sum over ranks then divide by world size (== DataParallel's global-batch mean).
 
         With a fused optimizer attached (``defer_scale``) the division happens inside its step kernel: between this call
-        and ``optimizer.step()`` every ``p.grad`` holds the cross-rank SUM (``world`` times the mean).  Code that reads
-        gradients in between -- ``clip_grad_norm_``, gradient-norm logging, a non-fused optimizer over ``bucket.params``
-        -- must call ``apply_deferred_scale()`` first."""
+        and ``optimizer.step()`` every ``p.grad`` holds the cross-rank SUM (``world`` times the mean).  Gradient clipping
+        and gradient-norm logging need nothing in between: ``FusedSGD / FusedAdamW(..., max_grad_norm=...)`` clip against,
+        and ``optimizer.grad_norm()`` reports, the norm of the global-batch MEAN gradient (the pending ``grad_scale`` is
+        part of the norm kernel).  Only code that reads ``p.grad`` itself -- torch's ``clip_grad_norm_``, a non-fused
+        optimizer over ``bucket.params`` -- must call ``apply_deferred_scale()`` first."""
         if not (dist.is_available() and dist.is_initialized()):
             return
         world = dist.get_world_size(group)
@@ -292,31 +294,166 @@ def shard_batch(x: torch.Tensor, rank: int, world: int) -> torch.Tensor:
     return x[rank * per:(rank + 1) * per]
 
 
+MAX_PARAM_GROUPS = 8            # the by-value {lr, weight_decay} table of the grouped step kernels
+GRAD_NORM_CHUNK = 16384         # elements one workgroup of istvt_grad_norm reduces (istvt_grad_norm_ws_elems(n) = chunks of n)
+
+
+def segment_table(params, groups):
+    """The segment table of the grouped step kernels, on the host (no GPU needed).
+
+    ``params``: the bucket's parameters in bucket order; ``groups``: one list of parameters per named group, in any order
+    and not necessarily contiguous in the bucket.  Parameters no group names form a last group of their own.  Returns
+    ``(ends, group_ids, group_of)``: the sorted end offsets of the segments (the last one is the bucket's size), the group of
+    each segment -- consecutive parameters of one group are merged into one segment -- and the group index of every parameter.
+    ValueError: a parameter in two groups, a parameter that is not in the bucket, more than MAX_PARAM_GROUPS groups."""
+    params = list(params)
+    index = {id(p): i for i, p in enumerate(params)}
+    group_of = [None] * len(params)
+    groups = [list(g) for g in groups]
+    for gi, members in enumerate(groups):
+        for q in members:
+            i = index.get(id(q))
+            if i is None:
+                raise ValueError('param group %d names a parameter that is not in the bucket' % gi)
+            if group_of[i] is not None:
+                raise ValueError('parameter %d of the bucket appears in more than one param group' % i)
+            group_of[i] = gi
+    count = len(groups)
+    if any(g is None for g in group_of):
+        group_of = [count if g is None else g for g in group_of]
+        count += 1
+    if count > MAX_PARAM_GROUPS:
+        raise ValueError('%d param groups (the default group included): the fused optimizers take at most %d'
+                         % (count, MAX_PARAM_GROUPS))
+    ends, gids, off = [], [], 0
+    for q, gi in zip(params, group_of):
+        if q.numel() == 0:
+            continue
+        off += q.numel()
+        if gids and gids[-1] == gi:
+            ends[-1] = off
+        else:
+            ends.append(off)
+            gids.append(gi)
+    return ends, gids, group_of
+
+
 class _FusedOptimizer(torch.optim.Optimizer):
     """Common part of the fused optimizers: one HIP launch over GradBucket's flat parameter / gradient buffers
     (reference optimizers: train_CNN.py:196-201).  ``zero_grad=True`` makes the step kernel
     write zeros over the gradients it has just consumed, so the training loop needs no zero-grad pass.
 
-    They are torch.optim.Optimizer objects: ONE param group over the bucket's parameters whose hyper-parameters
-    (``lr`` ...) are read at every step, so ``lr_scheduler.CosineAnnealingLR(optimizer, ...)`` (train_CNN.py:202)
-    works; ``state_dict()`` / ``load_state_dict()`` carry the step count and the flat state buffers."""
+    They are torch.optim.Optimizer objects with real ``param_groups`` whose hyper-parameters (``lr`` ...) are read at every
+    step, so ``lr_scheduler.CosineAnnealingLR(optimizer, ...)`` (train_CNN.py:202) works; ``state_dict()`` /
+    ``load_state_dict()`` carry the step count and the flat state buffers.
+
+    ``param_groups``: a list of dicts as torch takes them (``{'params': [...], 'lr': ..., 'weight_decay': ...}``), at most
+    MAX_PARAM_GROUPS with the default group that collects every parameter no dict names.  ``lr`` and ``weight_decay`` are
+    per group; the other hyper-parameters must agree.  ``max_grad_norm``: clip the global L2 norm of the global-batch mean
+    gradient, as ``clip_grad_norm_(params, max_grad_norm)`` in front of the step would (the pending ``bucket.grad_scale``
+    is included: no ``apply_deferred_scale()``).  ``skip_nonfinite``: a step whose gradient norm is inf / NaN changes no
+    parameter and no state, and is not counted (SGD's first-step rule and AdamW's bias corrections follow the applied
+    steps).  Either of the two adds one pass that reads the bucket (istvt_grad_norm); ``step()`` still never synchronises
+    and never copies to the host -- ``grad_norm()`` / ``skipped_steps()`` hand out HostScalars.  With none of the three the
+    optimizer launches exactly the one-group kernel it always launched."""
 
     _state_names: Tuple[str, ...] = ()
+    _shared_keys: Tuple[str, ...] = ()      # hyper-parameters the kernels take once: they must agree across the groups
 
-    def __init__(self, bucket: GradBucket, defaults: dict, zero_grad: bool):
+    def __init__(self, bucket: GradBucket, defaults: dict, zero_grad: bool, param_groups=None, max_grad_norm=None,
+                 skip_nonfinite: bool = False):
         if bucket.flat_params is None:
             raise ValueError('the fused optimizers need GradBucket(..., flatten_params=True)')
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError('max_grad_norm must be positive (None: no clipping)')
+        table = None
+        if param_groups is not None:
+            param_groups = [dict(g) for g in param_groups]
+            for g in param_groups:
+                g['params'] = list(g['params']) if not isinstance(g['params'], torch.Tensor) else [g['params']]
+            table = segment_table(bucket.params, [g['params'] for g in param_groups])
+            rest = [q for q, gi in zip(bucket.params, table[2]) if gi == len(param_groups)]
+            if rest:
+                param_groups = param_groups + [{'params': rest}]
+            self._check_shared([dict(defaults, **g) for g in param_groups])
         if not bucket.flat.is_cuda:
             raise RuntimeError('the fused optimizers run on the GPU only (no CPU fallback)')
-        super().__init__(bucket.params, defaults)
+        super().__init__(bucket.params if param_groups is None else param_groups, defaults)
         self.bucket = bucket
         bucket.defer_scale = True           # all_reduce() leaves the sum; step() applies 1 / world size
         self.fused_zero_grad = bool(zero_grad)
-        self.steps = 0
+        self.steps = 0                      # step() calls (what zero_grad() goes by); skip mode: see applied_steps()
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        # torch numbers parameters group by group: _order[torch index] = bucket index
+        index = {id(q): i for i, q in enumerate(bucket.params)}
+        self._order = [index[id(q)] for g in self.param_groups for q in g['params']]
+        self._seg = self._info = self._norm_ws = None
+        dev = bucket.flat.device
+        if len(self.param_groups) > 1 or self._uses_info():
+            ends, gids, _ = table if table is not None else segment_table(bucket.params, [])
+            self._seg = (torch.tensor(ends, dtype=torch.int64, device=dev), torch.tensor(gids, dtype=torch.int32, device=dev))
+        if self._uses_info():
+            from . import _lib
+            self._info = torch.zeros(8, dtype=torch.int32, device=dev)          # the step-info block (include/istvt_hip.h)
+            self._norm_ws = torch.empty(_lib.lib().istvt_grad_norm_ws_elems(bucket.numel), dtype=torch.float64, device=dev)
 
     @property
     def hyper(self) -> dict:
         return self.param_groups[0]
+
+    def _uses_info(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _check_shared(self, groups):
+        def same(a, b):
+            return tuple(a) == tuple(b) if isinstance(a, (list, tuple)) else a == b
+        for g in groups[1:]:
+            for k in self._shared_keys:
+                if not same(g[k], groups[0][k]):
+                    raise ValueError('fused optimizer: %r must be the same in every param group (%r in group 0, %r in group '
+                                     '%d); only lr and weight_decay are per group' % (k, groups[0][k], g[k], groups.index(g)))
+
+    def _group_args(self):
+        """the kernels' by-value {lr, weight_decay} table, read from the param groups at every step"""
+        from ctypes import c_float
+        groups = self.param_groups
+        if len(groups) > MAX_PARAM_GROUPS:
+            raise ValueError('the fused optimizers take at most %d param groups' % MAX_PARAM_GROUPS)
+        self._check_shared(groups)
+        arr = c_float * len(groups)
+        return arr(*[g['lr'] for g in groups]), arr(*[g['weight_decay'] for g in groups]), len(groups)
+
+    def _norm_pass(self):
+        """istvt_grad_norm over the bucket when clipping or skipping is on: the address of the step-info block the
+        step kernel then reads its gradient scale (and, in skip mode, its step count) from; otherwise None"""
+        if self._info is None:
+            return None
+        from . import _lib, ops
+        b = self.bucket
+        _lib.check(_lib.lib().istvt_grad_norm(b.flat.data_ptr(), b.numel, float(b.grad_scale), self.max_grad_norm or 0.0,
+                                              int(self.skip_nonfinite), self._norm_ws.data_ptr(), self._norm_ws.numel(),
+                                              self._info.data_ptr(), ops._stream()), 'istvt_grad_norm')
+        return self._info.data_ptr()
+
+    def _info_scalar(self, word: int, dtype) -> 'HostScalar':
+        if self._info is None:
+            raise RuntimeError('needs max_grad_norm=... or skip_nonfinite=True: without them no norm is computed')
+        # a copy on the current stream: the next step's norm kernel overwrites the block
+        return HostScalar(self._info[word:word + 1].view(dtype).clone())
+
+    def grad_norm(self) -> 'HostScalar':
+        """L2 norm of the last step's global-batch mean gradient (before clipping), without a sync in the loop: take it
+        after ``step()``, call ``.item()`` where the number is needed"""
+        return self._info_scalar(0, torch.float32)
+
+    def skipped_steps(self) -> 'HostScalar':
+        """how many steps ``skip_nonfinite`` has skipped so far (the device counter)"""
+        return self._info_scalar(4, torch.int32)
+
+    def applied_steps(self) -> int:
+        """steps that changed the parameters.  In skip mode the count lives on the device: reading it synchronises."""
+        return int(self._info[3].item()) if self.skip_nonfinite else self.steps
 
     def zero_grad(self, set_to_none: bool = False):
         if set_to_none:
@@ -342,37 +479,50 @@ class _FusedOptimizer(torch.optim.Optimizer):
         ops.refresh_stale_operands()
 
     def _slices(self):
-        off = 0
-        for i, p in enumerate(self.bucket.params):
-            n = p.numel()
-            yield i, p, off, n
-            off += n
+        """(torch's parameter index, parameter, offset in the flat buffers, elements), in torch's order"""
+        offs, off = [], 0
+        for q in self.bucket.params:
+            offs.append(off)
+            off += q.numel()
+        for i, bi in enumerate(self._order):
+            q = self.bucket.params[bi]
+            yield i, q, offs[bi], q.numel()
 
-    def _extra_state(self, i) -> dict:      # per-parameter entries beside the flat buffers (AdamW's step count)
+    def _extra_state(self, steps) -> dict:  # per-parameter entries beside the flat buffers (AdamW's step count)
         return {}
 
     def state_dict(self):
         """torch.optim's format -- ``{'state': {index: {name: tensor}}, 'param_groups': [{..., 'params': [indices]}]}``
-        -- with the per-parameter tensors cut out of the flat state buffers, so a checkpoint written here loads into
-        torch.optim.SGD / AdamW over the same parameters and the other way round.  ``fused_steps`` (ignored by torch)
-        keeps the step count for SGD, whose torch state has none."""
+        -- with the per-parameter tensors cut out of the flat state buffers and the parameters numbered group by group as
+        torch numbers them, so a checkpoint written here loads into torch.optim.SGD / AdamW built with the same groups and
+        the other way round.  ``fused_steps`` (ignored by torch) keeps the step count for SGD, whose torch state has none;
+        in skip mode it is the applied count."""
+        steps = self.applied_steps()
         state = {}
-        if self.steps > 0:                  # torch optimizers have no state before their first step either
+        if steps > 0:                       # torch optimizers have no state before their first step either
             for i, p, off, n in self._slices():
                 st = {name: getattr(self, name)[off:off + n].view_as(p).detach().clone() for name in self._state_names}
-                st.update(self._extra_state(i))
+                st.update(self._extra_state(steps))
                 state[i] = st
-        group = {k: v for k, v in self.hyper.items() if k != 'params'}
-        group['params'] = list(range(len(self.bucket.params)))
-        return {'state': state, 'param_groups': [group], 'fused_steps': self.steps}
+        groups, first = [], 0
+        for g in self.param_groups:
+            out = {k: v for k, v in g.items() if k != 'params'}
+            out['params'] = list(range(first, first + len(g['params'])))
+            first += len(g['params'])
+            groups.append(out)
+        return {'state': state, 'param_groups': groups, 'fused_steps': steps}
 
     def load_state_dict(self, sd):
         groups = sd['param_groups']
-        if len(groups) != 1 or len(groups[0]['params']) != len(self.bucket.params):
-            raise ValueError('fused optimizer: expected ONE param group over %d parameters' % len(self.bucket.params))
+        if len(groups) != len(self.param_groups) or \
+                any(len(g['params']) != len(mine['params']) for g, mine in zip(groups, self.param_groups)):
+            raise ValueError('fused optimizer: expected %d param group(s) over %s parameters, the checkpoint has %s'
+                             % (len(self.param_groups), [len(g['params']) for g in self.param_groups],
+                                [len(g['params']) for g in groups]))
         # every saved key, as torch.optim does (a checkpoint written with an LR scheduler attached carries
         # 'initial_lr', which CosineAnnealingLR(last_epoch=E) needs on resume); the kernels read only the keys they know
-        self.hyper.update({k: v for k, v in groups[0].items() if k != 'params'})
+        for g, mine in zip(groups, self.param_groups):
+            mine.update({k: v for k, v in g.items() if k != 'params'})
         state = sd['state']
         steps = 0
         for i, p, off, n in self._slices():
@@ -389,29 +539,43 @@ class _FusedOptimizer(torch.optim.Optimizer):
             if st is not None:
                 steps = max(steps, int(float(st['step'])) if 'step' in st else 1)
         self.steps = int(sd.get('fused_steps', steps))
+        if self.skip_nonfinite:
+            self._info[3:4].fill_(self.steps)       # the device's applied-step count goes on from the checkpoint's
 
 
 class FusedSGD(_FusedOptimizer):
     """torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov) over the flat buffers."""
 
     _state_names = ('momentum_buffer',)
+    _shared_keys = ('momentum', 'dampening', 'nesterov')
 
     def __init__(self, bucket: GradBucket, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False, zero_grad: bool = False):
+                 weight_decay: float = 0.0, nesterov: bool = False, zero_grad: bool = False, param_groups=None,
+                 max_grad_norm=None, skip_nonfinite: bool = False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError('Nesterov momentum requires a momentum and zero dampening')
         super().__init__(bucket, dict(lr=float(lr), momentum=float(momentum), dampening=float(dampening),
-                                      weight_decay=float(weight_decay), nesterov=bool(nesterov)), zero_grad)
+                                      weight_decay=float(weight_decay), nesterov=bool(nesterov)), zero_grad,
+                         param_groups, max_grad_norm, skip_nonfinite)
         self.momentum_buffer = torch.zeros_like(bucket.flat)
 
     @torch.no_grad()
     def step(self, closure=None):
         from . import _lib, ops
         b, h = self.bucket, self.hyper
-        _lib.check(_lib.lib().istvt_sgd_momentum(b.flat_params.data_ptr(), b.flat.data_ptr(), self.momentum_buffer.data_ptr(),
-                                                 b.numel, h['lr'], h['momentum'], h['dampening'], h['weight_decay'],
-                                                 int(h['nesterov']), int(self.steps == 0), int(self.fused_zero_grad),
-                                                 float(b.grad_scale), ops._stream()), 'istvt_sgd_momentum')
+        if len(self.param_groups) == 1 and self._info is None:
+            _lib.check(_lib.lib().istvt_sgd_momentum(b.flat_params.data_ptr(), b.flat.data_ptr(), self.momentum_buffer.data_ptr(),
+                                                     b.numel, h['lr'], h['momentum'], h['dampening'], h['weight_decay'],
+                                                     int(h['nesterov']), int(self.steps == 0), int(self.fused_zero_grad),
+                                                     float(b.grad_scale), ops._stream()), 'istvt_sgd_momentum')
+        else:
+            lrs, wds, count = self._group_args()
+            info = self._norm_pass()
+            _lib.check(_lib.lib().istvt_sgd_momentum_groups(
+                b.flat_params.data_ptr(), b.flat.data_ptr(), self.momentum_buffer.data_ptr(), b.numel,
+                self._seg[0].data_ptr(), self._seg[1].data_ptr(), self._seg[0].numel(), lrs, wds, count, h['momentum'],
+                h['dampening'], int(h['nesterov']), int(self.steps == 0), int(self.fused_zero_grad), float(b.grad_scale),
+                info, int(self.skip_nonfinite), ops._stream()), 'istvt_sgd_momentum_groups')
         self._done()
 
 
@@ -419,14 +583,17 @@ class FusedAdamW(_FusedOptimizer):
     """torch.optim.AdamW(params, lr, betas, eps, weight_decay) (amsgrad off) over the flat buffers."""
 
     _state_names = ('exp_avg', 'exp_avg_sq')
+    _shared_keys = ('betas', 'eps')
 
-    def _extra_state(self, i):
-        return {'step': torch.tensor(float(self.steps))}
+    def _extra_state(self, steps):
+        return {'step': torch.tensor(float(steps))}
 
     def __init__(self, bucket: GradBucket, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, zero_grad: bool = False):
+                 weight_decay: float = 1e-2, zero_grad: bool = False, param_groups=None, max_grad_norm=None,
+                 skip_nonfinite: bool = False):
         super().__init__(bucket, dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
-                                      weight_decay=float(weight_decay)), zero_grad)
+                                      weight_decay=float(weight_decay)), zero_grad, param_groups, max_grad_norm,
+                         skip_nonfinite)
         self.exp_avg = torch.zeros_like(bucket.flat)
         self.exp_avg_sq = torch.zeros_like(bucket.flat)
 
@@ -434,10 +601,19 @@ class FusedAdamW(_FusedOptimizer):
     def step(self, closure=None):
         from . import _lib, ops
         b, h = self.bucket, self.hyper
-        _lib.check(_lib.lib().istvt_adamw(b.flat_params.data_ptr(), b.flat.data_ptr(), self.exp_avg.data_ptr(),
-                                          self.exp_avg_sq.data_ptr(), b.numel, h['lr'], h['betas'][0], h['betas'][1],
-                                          h['eps'], h['weight_decay'], self.steps + 1, int(self.fused_zero_grad),
-                                          float(b.grad_scale), ops._stream()), 'istvt_adamw')
+        if len(self.param_groups) == 1 and self._info is None:
+            _lib.check(_lib.lib().istvt_adamw(b.flat_params.data_ptr(), b.flat.data_ptr(), self.exp_avg.data_ptr(),
+                                              self.exp_avg_sq.data_ptr(), b.numel, h['lr'], h['betas'][0], h['betas'][1],
+                                              h['eps'], h['weight_decay'], self.steps + 1, int(self.fused_zero_grad),
+                                              float(b.grad_scale), ops._stream()), 'istvt_adamw')
+        else:
+            lrs, wds, count = self._group_args()
+            info = self._norm_pass()
+            _lib.check(_lib.lib().istvt_adamw_groups(
+                b.flat_params.data_ptr(), b.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), b.numel,
+                self._seg[0].data_ptr(), self._seg[1].data_ptr(), self._seg[0].numel(), lrs, wds, count, h['betas'][0],
+                h['betas'][1], h['eps'], self.steps + 1, int(self.fused_zero_grad), float(b.grad_scale), info,
+                int(self.skip_nonfinite), ops._stream()), 'istvt_adamw_groups')
         self._done()
 
 

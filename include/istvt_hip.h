@@ -393,6 +393,39 @@ int istvt_sgd_momentum(float* p, float* g, float* buf, long n, float lr, float m
 int istvt_adamw(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                 float weight_decay, long step, int zero_grad, float grad_scale, istvt_stream_t stream);
 
+/* ---- around the fused step: global gradient norm (clipping, non-finite skip) and per-group hyper-parameters ----
+ * istvt_grad_norm: total_norm = || grad_scale * g ||_2 over the n floats of g (16-byte aligned), two stages in a fixed
+ * order: every workgroup reduces one contiguous chunk (fp32 per lane over 16 elements, fp64 from there on) into one double
+ * of ws (>= istvt_grad_norm_ws_elems(n) doubles), one workgroup sums those.  Chunk and grid depend on n alone and there are
+ * no atomics: the same bucket gives the same bits on every rank and in every run.  The second stage writes the STEP-INFO
+ * BLOCK `info` (device memory, 8 x 32-bit words):
+ *   [0] float total_norm
+ *   [1] float scale: what the step multiplies g by -- grad_scale x min(1, max_norm / (total_norm + 1e-6)), torch's
+ *       clip_grad_norm_ coefficient; just grad_scale with max_norm <= 0; 0 for a skipped step
+ *   [2] int finite: total_norm is finite
+ *   [3] int applied_steps, [4] int skipped_steps: touched only with skip_nonfinite != 0 -- a non-finite norm counts as a
+ *       skipped step, any other as an applied one (the caller zeroes the block once, or sets [3] when it resumes a run)
+ *   [5..7] reserved */
+int istvt_grad_norm(const float* g, long n, float grad_scale, float max_norm, int skip_nonfinite, double* ws,
+                    long ws_elems, void* info, istvt_stream_t stream);
+int istvt_grad_norm_ws_elems(long n);
+/* The steps above with {lr, weight_decay} per parameter group (at most 8).  seg_end / seg_group: DEVICE arrays of nseg
+ * entries -- sorted end offsets (the last one is n) and the group of the elements [seg_end[i-1], seg_end[i]); boundaries
+ * fall at any offset.  group_lr / group_wd: HOST arrays of ngroups floats, passed on to the kernel by value (a scheduler's
+ * change costs no copy to the device).  The arithmetic is that of the plain entry points, bit for bit.
+ * info (nullable): a step-info block written by istvt_grad_norm on the same stream; its `scale` then replaces grad_scale.
+ * skip_nonfinite != 0 (needs info): with finite == 0 parameters and state stay untouched (g is still zeroed when zero_grad
+ * is set), and which step this is -- sgd's first-step rule, adamw's bias corrections -- comes from the block's
+ * applied_steps instead of first_step / step, so a skipped step leaves no trace. */
+int istvt_sgd_momentum_groups(float* p, float* g, float* buf, long n, const long* seg_end, const int* seg_group, int nseg,
+                              const float* group_lr, const float* group_wd, int ngroups, float momentum, float dampening,
+                              int nesterov, int first_step, int zero_grad, float grad_scale, const void* info,
+                              int skip_nonfinite, istvt_stream_t stream);
+int istvt_adamw_groups(float* p, float* g, float* m, float* v, long n, const long* seg_end, const int* seg_group, int nseg,
+                       const float* group_lr, const float* group_wd, int ngroups, float beta1, float beta2, float eps,
+                       long step, int zero_grad, float grad_scale, const void* info, int skip_nonfinite,
+                       istvt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
