@@ -33,6 +33,8 @@ SIGNATURES = {
     'istvt_relevance_heatmap': [P, P, I, I, I, P],
     'istvt_relevance_fuse_windows': [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     'istvt_relevance_overlay_u8': [P, P, P, P, P, I, I, I, I, P],
+    'istvt_windows_reduce': [P, P, P, P, I, I, I, P],
+    'istvt_auc_pairs': [P, P, F, P, L, P, P, I, P],
     'istvt_tokens_fwd': [P, P, P, P, P, L, I, I, I, I, I, I, P],
     'istvt_tokens_gather_fwd': [P, P, P, P, P, P, L, I, I, I, I, I, I, I, P],
     'istvt_tokens_bwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],

@@ -246,6 +246,13 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score(frames, boxes=boxes)
 
+    def score_videos(self, videos, boxes=None, labels=None, **kw):
+        """Sliding-window scores of a set of videos in one pass (a list of tensors as score_video takes them, one box table
+        per video in `boxes`), with accuracy counts and the AUC over the set when `labels` gives one 0 / 1 per video:
+        istvt_amd.video.VideoScorer(self, **kw).score_videos(videos, boxes, labels)"""
+        from istvt_amd import video
+        return video.VideoScorer(self, **kw).score_videos(videos, boxes=boxes, labels=labels)
+
     def explain_video(self, frames, index=0, boxes=None, **kw):
         """Per-frame relevance maps of one video (frames and boxes as score_video takes them) for output `index`:
         istvt_amd.video.VideoScorer(self, **kw).explain(frames, index, boxes)"""

@@ -659,6 +659,83 @@ def relevance_fuse_windows(r_s: Tensor, r_t: Tensor, logits: Tensor, starts, n: 
     return frame_s, frame_t, weight, logit, count
 
 
+def check_window_offsets(offsets, W: int):
+    """The window ranges of V videos as a list of V + 1 ints: 0 = o[0] < o[1] < ... < o[V] = W (every video has a window),
+    ValueError otherwise."""
+    off = [int(v) for v in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
+    if len(off) < 2:
+        raise ValueError('window offsets: no videos')
+    if off[0] != 0 or off[-1] != W:
+        raise ValueError('window offsets span [%d, %d], the %d windows [0, %d]' % (off[0], off[-1], W, W))
+    if any(b <= a for a, b in zip(off, off[1:])):
+        raise ValueError('window offsets must ascend strictly (a video without a window cannot be scored), got %s'
+                         % (off if len(off) <= 16 else off[:16] + ['...'],))
+    return off
+
+
+def windows_reduce(logits: Tensor, offsets, checked: bool = False):
+    """The windows of V videos reduced per video.  logits (W, nc) fp32, video v owns the rows [offsets[v], offsets[v+1]);
+    offsets: V + 1 ints as a host tensor or a list, validated here (check_window_offsets) and uploaded on the current stream;
+    checked=True takes an int32 device table the caller has validated already -> logit_mean, prob_mean (V, nc) fp32: the mean
+    logit and the mean of 1 / (1 + exp(-logit)), each an fp64 sum in a fixed order rounded once."""
+    _req(logits, 'logits')
+    if logits.dtype != torch.float32:
+        raise TypeError('windows_reduce: logits must be float32, got %s' % logits.dtype)
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise RuntimeError('windows_reduce: logits (W, nc) with W, nc >= 1 expected, got %s' % (tuple(logits.shape),))
+    W, nc = logits.shape
+    if checked:
+        if (not torch.is_tensor(offsets) or offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.shape[0] < 2
+                or offsets.device != logits.device):
+            raise RuntimeError('windows_reduce: a checked offset table is int32 (V + 1,) on %s' % logits.device)
+        off = _c(offsets)
+        V = off.shape[0] - 1
+    else:
+        if torch.is_tensor(offsets) and offsets.dim() != 1:
+            raise RuntimeError('windows_reduce: offsets must be (V + 1,), got %s' % (tuple(offsets.shape),))
+        host = check_window_offsets(offsets, W)
+        V = len(host) - 1
+        off = torch.tensor(host, dtype=torch.int32).to(logits.device, non_blocking=True)
+    if V > W:
+        raise ValueError('windows_reduce: %d videos for %d windows' % (V, W))
+    logits = _c(logits)
+    logit_mean = torch.empty((V, nc), dtype=torch.float32, device=logits.device)
+    prob_mean = torch.empty((V, nc), dtype=torch.float32, device=logits.device)
+    with prof('windows_reduce', 4 * (W * nc + 2 * V * nc + V + 1)):
+        _lib.check(_lib.lib().istvt_windows_reduce(logits.data_ptr(), off.data_ptr(), logit_mean.data_ptr(), prob_mean.data_ptr(),
+                                                   W, V, nc, _stream()), 'istvt_windows_reduce')
+    return logit_mean, prob_mean
+
+
+AUC_COUNTS = ('greater', 'equal', 'positives', 'negatives', 'nonfinite', 'correct')
+
+
+def auc_pairs(scores: Tensor, labels: Tensor, threshold: float = 0.0):
+    """scores fp32 (V,), labels int32 (V,) of 0 / 1, both on the device -> counts int64 (6,) in the order of AUC_COUNTS and auc
+    float64 (1,) = (greater + equal / 2) / (positives * negatives) over the (positive, negative) pairs, NaN when a class is
+    empty.  A non-finite score is in no pair, never correct, and counted in nonfinite.  Nothing here synchronises."""
+    _req(scores, 'scores')
+    _req(labels, 'labels')
+    if scores.dtype != torch.float32:
+        raise TypeError('auc_pairs: scores must be float32, got %s' % scores.dtype)
+    if labels.dtype != torch.int32:
+        raise TypeError('auc_pairs: labels must be int32, got %s' % labels.dtype)
+    if scores.dim() != 1 or scores.shape[0] < 1 or tuple(labels.shape) != tuple(scores.shape):
+        raise RuntimeError('auc_pairs: scores (V,) and labels (V,) with V >= 1 expected, got %s and %s'
+                           % (tuple(scores.shape), tuple(labels.shape)))
+    if labels.device != scores.device:
+        raise RuntimeError('auc_pairs: scores are on %s, labels on %s' % (scores.device, labels.device))
+    V = scores.shape[0]
+    scores, labels = _c(scores), _c(labels)
+    ws = torch.empty((-(-V // 256), len(AUC_COUNTS)), dtype=torch.int64, device=scores.device)
+    counts = torch.empty((len(AUC_COUNTS),), dtype=torch.int64, device=scores.device)
+    auc = torch.empty((1,), dtype=torch.float64, device=scores.device)
+    with prof('auc_pairs', 8 * V):
+        _lib.check(_lib.lib().istvt_auc_pairs(scores.data_ptr(), labels.data_ptr(), float(threshold), ws.data_ptr(), ws.numel(),
+                                              counts.data_ptr(), auc.data_ptr(), V, _stream()), 'istvt_auc_pairs')
+    return counts, auc
+
+
 def relevance_overlay_u8(frames: Tensor, maps: Tensor, lut: Tensor, scale: int = 16) -> Tensor:
     """frames uint8 (N, S, S, 3) (any view: a non-contiguous one is copied), maps fp32 (N, g, g), lut uint8 (256, 3) ->
     uint8 (N, g*scale, g*scale, 3): the colour-mapped, min-max normalised heat map added to the frame and the sum scaled
@@ -708,10 +785,13 @@ def tokens_fwd(feats: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad:
     return x.view(B, F * P, D)
 
 
-def tokens_gather_fwd(bank: Tensor, idx: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad: bool = False) -> Tensor:
+def tokens_gather_fwd(bank: Tensor, idx: Tensor, space: Tensor, temporal: Tensor, pos: Tensor, pad: bool = False,
+                      checked: bool = False) -> Tensor:
     """Token assembly for sliding windows: bank [cap,hw,D] per-frame features, idx int32 [W,T] bank slots of every window's
     frames -> x [W,(T+1)*(hw+1),D], bit-identical to tokens_fwd(bank[idx]).  The table is validated here, on the host: pass
-    it as a host tensor (it is uploaded on the current stream); a device table costs one synchronisation to check."""
+    it as a host tensor (it is uploaded on the current stream); a device table costs one synchronisation to check.
+    checked=True takes a device table whose range the caller has validated on the host already (video.SetPlan's tables,
+    uploaded once per call): no synchronisation."""
     bank = _c(_req(bank, 'feature bank'))
     if bank.dim() != 3:
         raise RuntimeError('tokens_gather_fwd: bank must be (cap, h*w, D), got %s' % (tuple(bank.shape),))
@@ -722,9 +802,13 @@ def tokens_gather_fwd(bank: Tensor, idx: Tensor, space: Tensor, temporal: Tensor
     W, T = idx.shape
     if W == 0:
         raise RuntimeError('tokens_gather_fwd: no windows')
-    lo, hi = int(idx.min()), int(idx.max())
-    if lo < 0 or hi >= cap:
-        raise IndexError('tokens_gather_fwd: slots span [%d, %d], the bank has %d' % (lo, hi, cap))
+    if checked:
+        if not idx.is_cuda:
+            raise RuntimeError('tokens_gather_fwd: a checked table is on the device already')
+    else:
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= cap:
+            raise IndexError('tokens_gather_fwd: slots span [%d, %d], the bank has %d' % (lo, hi, cap))
     idx = _c(idx)
     if not idx.is_cuda:
         idx = idx.to(bank.device, non_blocking=True)

@@ -10,6 +10,8 @@ video out.
     for chunk in stream:                             # the same windows, as the frames arrive
         logits, starts = scorer.push(chunk)
     logits, starts = scorer.flush()                  # the window that covers the tail, if one is due
+    res = scorer.score_videos(videos, labels=labels)  # a test set: stem and window batches assembled across the videos, one
+                                                     # synchronisation, per-video means and accuracy / AUC on the device
 
 What `model(clips)` would pay for this and the scorer does not: the Xception stem runs once per frame instead of once per
 (window, frame) -- in eval mode a frame's feature map does not depend on the clip around it --, conv1 reads the decoder's
@@ -18,11 +20,13 @@ never copied out as clips: the per-frame features sit in a device ring and istvt
 window's tokens from its slots.
 
 The schedule (which frames go through the stem when, which windows run when, which ring slot holds which frame) is host
-logic with no tensor in it: RingPlan, testable without a device.
+logic with no tensor in it: RingPlan for one stream, SetPlan for a set of videos that share one bank, both testable
+without a device.
 """
 from __future__ import annotations
 
 import contextlib
+import heapq
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -169,6 +173,129 @@ class RingPlan:
         return steps
 
 
+class SetPlan:
+    """The order of work for a set of V videos of n_0 ... n_{V-1} frames whose features share one bank of `capacity` slots
+    (DESIGN.md "Scoring a set of videos").  The frames of all videos form one sequence (video after video; frame i of video v
+    is number frame_offsets[v] + i) and so do the windows (those of video v are window_starts(n_v, T, stride, cover_tail), in
+    that order; video v owns the windows [offsets[v], offsets[v + 1])).
+
+    steps           the Steps VideoScorer runs, in order.  'frames': frames [first, first + count) of the sequence go through
+                    the stem into the bank slots `slots`; a batch may cross a video boundary.  'windows': the windows
+                    [first, first + count) of the window sequence run; `starts` are their first frames inside their own
+                    videos and idx[w][t] is the slot that holds frame t of window first + w.  Windows of several videos share a
+                    batch: every batch is full except the last one of the plan.
+    window_video    the video of every window;  starts: its first frame inside that video.
+    capacity        slots of the bank (default: frame_batch + window_batch * T rounded up to a multiple of 8, where no batch is
+                    ever cut); slots_used: the highest slot named, plus one -- what has to be allocated.
+    full_batches, partial_batches   window batches of window_batch windows, and of fewer.
+
+    The bank is a pool: a frame takes the lowest free slot, and the slot returns to the pool when the last window that reads
+    the frame has been planned into a step (a frame no window reads returns its slot with its own stem batch).  The device
+    runs the steps in order, so a slot handed out again is written only after every window that read its previous frame.
+    When the next frame batch would find too few free slots, the complete windows that are still queued for a full batch
+    are issued first, as a partial batch: they then hold nothing, and what remains held are the at most T - 1 frames of the
+    one window that is not complete yet.  Hence the smallest capacity, frame_batch + T."""
+
+    def __init__(self, counts: Sequence[int], T: int, stride: int = 1, cover_tail: bool = True, frame_batch: int = 64,
+                 window_batch: int = 32, capacity: Optional[int] = None):
+        if T < 1 or stride < 1 or frame_batch < 1 or window_batch < 1:
+            raise ValueError('SetPlan: T, stride, frame_batch and window_batch must be positive')
+        counts = [int(n) for n in counts]
+        if not counts:
+            raise ValueError('SetPlan: no videos')
+        for v, n in enumerate(counts):
+            if n < T:
+                raise ValueError('video %d has %d frames: shorter than one window of %d' % (v, n, T))
+        if capacity is None:
+            capacity = self.default_capacity(T, frame_batch, window_batch)
+        if capacity < frame_batch + T:
+            raise ValueError('a bank of %d slots is too small for a frame batch of %d and one window of %d: %d at least'
+                             % (capacity, frame_batch, T, frame_batch + T))
+        self.T, self.stride, self.cover_tail = T, stride, bool(cover_tail)
+        self.frame_batch, self.window_batch, self.capacity = frame_batch, window_batch, int(capacity)
+        self.counts = counts
+        self.frame_offsets, self.offsets = [0], [0]
+        self.window_video: List[int] = []
+        self.starts: List[int] = []
+        for v, n in enumerate(counts):
+            st = window_starts(n, T, stride, cover_tail)
+            self.window_video += [v] * len(st)
+            self.starts += st
+            self.frame_offsets.append(self.frame_offsets[-1] + n)
+            self.offsets.append(self.offsets[-1] + len(st))
+        self.steps: List[Step] = []
+        self.full_batches = self.partial_batches = 0
+        self.slots_used = 0
+        self._build()
+
+    @staticmethod
+    def default_capacity(T: int, frame_batch: int, window_batch: int) -> int:
+        return -(-(frame_batch + window_batch * T) // 8) * 8
+
+    def _build(self):
+        T, G, W = self.T, self.frame_offsets[-1], len(self.starts)
+        first = [self.frame_offsets[v] + s for v, s in zip(self.window_video, self.starts)]   # first frame, in the sequence
+        readers = [0] * G                  # windows not yet planned that read the frame
+        for f in first:
+            for t in range(T):
+                readers[f + t] += 1
+        slot_of = [-1] * G
+        free = list(range(self.capacity))  # a heap: the lowest free slot first
+        pending: List[int] = []            # windows whose frames are all in the bank, not yet planned
+        done = 0                           # windows [0, done) are complete (all their frames planned); they complete in order
+
+        def windows(count):
+            ws, pending[:] = pending[:count], pending[count:]
+            idx = torch.tensor([[slot_of[first[w] + t] for t in range(T)] for w in ws], dtype=torch.int32)
+            self.steps.append(Step('windows', ws[0], len(ws), (), tuple(self.starts[w] for w in ws), idx))
+            if len(ws) == self.window_batch:
+                self.full_batches += 1
+            else:
+                self.partial_batches += 1
+            for w in ws:
+                for t in range(T):
+                    f = first[w] + t
+                    readers[f] -= 1
+                    if readers[f] == 0:
+                        heapq.heappush(free, slot_of[f])
+
+        g = 0
+        while g < G:
+            kb = min(self.frame_batch, G - g)
+            if len(free) < kb and pending:
+                windows(len(pending))      # early and partial: the bank has no room for the next frame batch otherwise
+            assert len(free) >= kb, 'SetPlan: the bank ran out of slots'          # capacity >= frame_batch + T rules it out
+            slots = tuple(heapq.heappop(free) for _ in range(kb))
+            self.slots_used = max(self.slots_used, max(slots) + 1)
+            self.steps.append(Step('frames', g, kb, slots, (), None))
+            for i, sl in enumerate(slots):
+                slot_of[g + i] = sl
+                if readers[g + i] == 0:    # a frame between two windows (stride > T) or past the last one (no cover_tail)
+                    heapq.heappush(free, sl)
+            g += kb
+            while done < W and first[done] + T <= g:
+                pending.append(done)
+                done += 1
+            while len(pending) >= self.window_batch:
+                windows(self.window_batch)
+        while pending:
+            windows(min(len(pending), self.window_batch))
+
+    def pieces(self, first: int, count: int) -> List[Tuple[int, int, int]]:
+        """the frames [first, first + count) of the sequence as (video, lo, hi) pieces, frames [lo, hi) of that video"""
+        out = []
+        v = 0
+        while self.frame_offsets[v + 1] <= first:
+            v += 1
+        end = first + count
+        while first < end:
+            hi = min(end, self.frame_offsets[v + 1])
+            out.append((v, first - self.frame_offsets[v], hi - self.frame_offsets[v]))
+            first = hi
+            v += 1
+        return out
+
+
 class VideoScore(NamedTuple):
     """Result of VideoScorer.score: device tensors, complete when score() returns."""
     window_logits: Tensor      # (W, num_classes) float32
@@ -186,6 +313,81 @@ class VideoExplanation(NamedTuple):
     frame_weight: Tensor       # (N,) float32: mean of r_t[w, 0, n - start_w + 1], how much the verdict rests on the frame
     frame_logit: Tensor        # (N,) float32: mean of logits[w, index] over the covering windows
     count: Tensor              # (N,) int32: number of windows that cover the frame (0: zeros in the other fields)
+
+
+class SetMetrics(NamedTuple):
+    """Result of set_metrics: 0-dim device tensors; nothing has been synchronised."""
+    correct: Tensor            # int64: videos with a finite score and (score > threshold) == (label == 1)
+    positives: Tensor          # int64: videos labelled 1
+    negatives: Tensor          # int64: videos labelled 0
+    nonfinite: Tensor          # int64: videos whose score is NaN or infinite (in no pair, never correct)
+    auc: Tensor                # float64: (greater + equal / 2) / (positives * negatives); NaN when a class is empty
+    greater: Tensor            # int64: (positive, negative) pairs with s_p > s_n
+    equal: Tensor              # int64: pairs with s_p == s_n
+
+
+class VideoSetScore(NamedTuple):
+    """Result of VideoScorer.score_videos: device tensors, complete when score_videos() returns.  The windows of video v are
+    the rows [offsets[v], offsets[v + 1])."""
+    window_logits: Tensor      # (W, num_classes) float32, video after video
+    window_video: Tensor       # (W,) int32: the video of every window
+    starts: Tensor             # (W,) int64: first frame of every window inside its video
+    offsets: Tensor            # (V + 1,) int32
+    logit_mean: Tensor         # (V, num_classes) mean of each video's window logits
+    prob_mean: Tensor          # (V, num_classes) mean of each video's windows' sigmoids
+    metrics: Optional[SetMetrics]      # set_metrics(logit_mean[:, 0], labels) when labels were given
+
+
+def _check_labels(labels, V: int, dev) -> Tensor:
+    """labels of 0 / 1 -> int32 (V,) on dev.  A host tensor or a list is validated; a device tensor is taken as it is
+    (checking it would synchronise): anything but 0 counts as 1."""
+    if not torch.is_tensor(labels):
+        labels = torch.as_tensor(labels)
+    if labels.dim() != 1 or labels.shape[0] != V:
+        raise ValueError('labels: one 0 / 1 per video expected, (%d,), got %s' % (V, tuple(labels.shape)))
+    if not labels.is_cuda:
+        if not bool(((labels == 0) | (labels == 1)).all()):
+            raise ValueError('labels must be 0 or 1')
+        return labels.to(torch.int32).to(dev, non_blocking=True)
+    return labels.to(device=dev, dtype=torch.int32)
+
+
+def set_metrics(scores: Tensor, labels, threshold: float = 0.0) -> SetMetrics:
+    """Accuracy counts and the pairwise AUC of V video scores on the device (ops.auc_pairs), without a synchronisation.
+    scores (V,) float32 on the device, labels (V,) of 0 / 1 (host or device)."""
+    if not torch.is_tensor(scores) or scores.dim() != 1 or scores.shape[0] < 1:
+        raise ValueError('scores: one per video expected, (V,), got %s'
+                         % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
+    ops._req(scores, 'scores')
+    lab = _check_labels(labels, int(scores.shape[0]), scores.device)
+    counts, auc = ops.auc_pairs(scores.float(), lab, threshold)
+    c = dict(zip(ops.AUC_COUNTS, counts.unbind(0)))
+    return SetMetrics(c['correct'], c['positives'], c['negatives'], c['nonfinite'], auc[0], c['greater'], c['equal'])
+
+
+def windows_reduce_ref(logits: Tensor, offsets) -> Tuple[Tensor, Tensor]:
+    """ops.windows_reduce restated in float64 on the host: (logit_mean, prob_mean), float64 (V, nc)"""
+    x = logits.detach().cpu().double()
+    off = [int(v) for v in (offsets.tolist() if torch.is_tensor(offsets) else offsets)]
+    lm = torch.stack([x[a:b].sum(0) / (b - a) for a, b in zip(off, off[1:])])
+    pm = torch.stack([(1.0 / (1.0 + torch.exp(-x[a:b]))).sum(0) / (b - a) for a, b in zip(off, off[1:])])
+    return lm, pm
+
+
+def set_metrics_ref(scores, labels, threshold: float = 0.0) -> dict:
+    """set_metrics restated on the host with sorted ranks instead of pairs: Python ints and a Python float (auc)"""
+    s = torch.as_tensor(scores).detach().cpu().float()
+    lab = torch.as_tensor(labels).detach().cpu() != 0
+    fin = torch.isfinite(s)
+    neg = torch.sort(s[~lab & fin].double()).values
+    pos = s[lab & fin].double()
+    below = torch.searchsorted(neg, pos, right=False)      # negatives strictly below every positive
+    upto = torch.searchsorted(neg, pos, right=True)
+    greater, equal = int(below.sum()), int((upto - below).sum())
+    P, N = int(lab.sum()), int((~lab).sum())
+    auc = (float(greater) + 0.5 * float(equal)) / (float(P) * float(N)) if P and N else float('nan')
+    correct = int((fin & ((s > threshold) == lab)).sum())
+    return dict(correct=correct, positives=P, negatives=N, nonfinite=int((~fin).sum()), auc=auc, greater=greater, equal=equal)
 
 
 @contextlib.contextmanager
@@ -392,6 +594,100 @@ class VideoScorer:
         res = self._video_score(logits, starts, dev)
         torch.cuda.current_stream(dev).synchronize()
         return res
+
+    # ---------------------------------------------------------------------------------------- a set of videos
+    def _check_set(self, videos, boxes):
+        """-> (kind, list of validated host box tables or None, side); every ValueError of a call, before anything is launched"""
+        if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
+            raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
+        if boxes is None:
+            kinds = [check_frames(v) for v in videos]
+            if len(set(kinds)) != 1:
+                raise ValueError('the videos of one call are all uint8 or all float, not both (video %d differs from video 0)'
+                                 % next(i for i, k in enumerate(kinds) if k != kinds[0]))
+            sides = [int(v.shape[2]) for v in videos]
+            if len(set(sides)) != 1:
+                raise ValueError('the videos of one call share one crop side, got %s' % sorted(set(sides)))
+            return kinds[0], None, None
+        if not isinstance(boxes, (list, tuple)) or len(boxes) != len(videos):
+            raise ValueError('boxes: one table per video expected (%d)' % len(videos))
+        side = self._side()
+        return 'u8', [check_boxed_frames(v, b, side) for v, b in zip(videos, boxes)], side
+
+    def score_videos(self, videos, boxes=None, labels=None) -> VideoSetScore:
+        """All windows of a set of videos in one pass (DESIGN.md "Scoring a set of videos"): the windows of score(video) for
+        every video, but stem batches and window batches are assembled across the videos (SetPlan), the per-video means are
+        one kernel (ops.windows_reduce), and the call synchronises once.  videos: a list of tensors as score() takes them --
+        all uint8 or all float, one crop side, host or device in any mix.  boxes: one table per video, for whole uint8
+        frames; each video may have its own frame size.  labels: one 0 / 1 per video -> metrics = set_metrics(logit_mean[:, 0],
+        labels).  A stream in progress is not disturbed."""
+        kind, bhost, side = self._check_set(videos, boxes)
+        plan = SetPlan([int(v.shape[0]) for v in videos], self.T, self.stride, self.cover_tail, self.frame_batch,
+                       self.window_batch, self.capacity)
+        V = len(videos)
+        if labels is not None and (torch.as_tensor(labels).dim() != 1 or len(labels) != V):
+            raise ValueError('labels: one 0 / 1 per video expected, (%d,)' % V)
+        dev = self._device()
+        vit = self.model.vit
+        # every table of the call in two uploads: the slots of the frame batches (int64, for index_copy_) and the windows' idx
+        fsteps = [st for st in plan.steps if st.kind == 'frames']
+        wsteps = [st for st in plan.steps if st.kind == 'windows']
+        slots = torch.tensor([s for st in fsteps for s in st.slots], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        idx = torch.cat([st.idx for st in wsteps]).pin_memory().to(dev, non_blocking=True)      # SetPlan names slots < capacity
+        bdev = None if bhost is None else [b.contiguous().to(dev, non_blocking=True) for b in bhost]
+        bank, outs, fpos, wpos = None, [], 0, 0
+        with _eval_mode(self.model), torch.no_grad():
+            for st in plan.steps:
+                if st.kind == 'frames':
+                    feats = self._stem(self._frame_batch(videos, plan.pieces(st.first, st.count), bdev, side, dev), kind, dev)
+                    if bank is None:
+                        bank = torch.empty((plan.slots_used,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
+                    s0 = st.slots[0]
+                    if st.slots == tuple(range(s0, s0 + st.count)):
+                        bank[s0:s0 + st.count].copy_(feats)
+                    else:
+                        bank.index_copy_(0, slots[fpos:fpos + st.count], feats)
+                    fpos += st.count
+                else:
+                    x = ops.tokens_gather_fwd(bank, idx[wpos:wpos + st.count], vit.space_token, vit.temporal_token,
+                                              vit.pos_embedding, pad=True, checked=True)
+                    outs.append(vit.forward_tokens(x, st.count, self.T + 1, bank.shape[1] + 1))
+                    wpos += st.count
+            logits = torch.cat(outs) if len(outs) > 1 else outs[0]
+            tab = torch.tensor(plan.offsets + plan.window_video, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            offsets, window_video = tab[:V + 1], tab[V + 1:]
+            starts = torch.tensor(plan.starts, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            ops.check_window_offsets(plan.offsets, int(logits.shape[0]))
+            logit_mean, prob_mean = ops.windows_reduce(logits, offsets, checked=True)
+            metrics = None if labels is None else set_metrics(logit_mean[:, 0].contiguous(), labels)
+        res = VideoSetScore(logits, window_video, starts, offsets, logit_mean, prob_mean, metrics)
+        torch.cuda.current_stream(dev).synchronize()
+        return res
+
+    @staticmethod
+    def _frame_batch(videos, pieces, bdev, side, dev) -> Tensor:
+        """One stem batch on the device from (video, lo, hi) pieces.  Without boxes a single device piece is used where it is;
+        otherwise the pieces are copied into one staging batch (host pieces pinned first).  With boxes every piece is cropped
+        by ops.crop_resize_u8 into its slice of one crop batch."""
+        if bdev is None and len(pieces) == 1:
+            v, lo, hi = pieces[0]
+            x = videos[v][lo:hi]
+            return x if x.is_cuda else x.contiguous().pin_memory().to(dev, non_blocking=True)
+        n = sum(hi - lo for _, lo, hi in pieces)
+        first = videos[pieces[0][0]]
+        shape = (n, side, side, 3) if bdev is not None else (n,) + tuple(first.shape[1:])
+        batch = torch.empty(shape, dtype=first.dtype, device=dev)
+        at = 0
+        for v, lo, hi in pieces:
+            x = videos[v][lo:hi]
+            if bdev is None:
+                batch[at:at + hi - lo].copy_(x if x.is_cuda else x.contiguous().pin_memory(), non_blocking=True)
+            else:
+                if not x.is_cuda:
+                    x = x.contiguous().pin_memory().to(dev, non_blocking=True)
+                ops.crop_resize_u8(x, bdev[v][lo:hi], side, out=batch[at:at + hi - lo], checked=True)
+            at += hi - lo
+        return batch
 
     def explain(self, frames: Tensor, index: int = 0, boxes=None) -> VideoExplanation:
         """Relevance maps of one video for output `index` (DESIGN.md "Explaining whole videos"): the windows, frames and

@@ -188,6 +188,23 @@ int istvt_relevance_fuse_windows(const float* r_s, const float* r_t, const float
  * out = trunc(255 cam / max of cam over the frame).  ws: 4 floats of scratch per frame.  g <= 64, N <= 65535. */
 int istvt_relevance_overlay_u8(const void* frames, const float* maps, const void* lut, float* ws, void* out, int N, int S,
                                int g, int s, istvt_stream_t stream);
+/* A set of videos (DESIGN.md "Scoring a set of videos").  logits fp32 [W][nc], the windows of V videos one after the other;
+ * offsets int32 [V+1] on the device: video v owns the windows [offsets[v], offsets[v+1]), 0 = offsets[0] < ... <
+ * offsets[V] = W (validated by the caller; the kernel forces the table into [0, W]) -> logit_mean, prob_mean fp32 [V][nc]:
+ * the mean of the video's logits and of 1 / (1 + exp(-logit)) (fp32).  One workgroup per video, every lane sums a strided
+ * share of the windows in ascending order in fp64, the lane partials are added in lane order and the mean is rounded once
+ * to fp32.  One writer per element, no atomics. */
+int istvt_windows_reduce(const float* logits, const int* offsets, float* logit_mean, float* prob_mean, int W, int V, int nc,
+                         istvt_stream_t stream);
+/* scores fp32 [V], labels int32 [V] (0: negative, anything else: positive) -> counts int64 [6] = greater, equal, positives,
+ * negatives, nonfinite, correct and auc fp64 [1] = (greater + equal / 2) / (positives * negatives), NaN when a class is
+ * empty.  greater / equal: the (positive, negative) pairs with s_p > s_n / s_p == s_n in which both scores are finite; a
+ * video with a NaN or infinite score is in `nonfinite`, in its class's count, in no pair and never correct.  correct:
+ * (score > threshold) == positive.  Two launches: 256 videos per workgroup against all videos, six 64-bit counts per
+ * workgroup into ws (ws_elems >= 6 * ceil(V / 256) 8-byte elements of caller-owned scratch), then one workgroup sums them.
+ * Integer counts: exact, independent of order, no atomics. */
+int istvt_auc_pairs(const float* scores, const int* labels, float threshold, void* ws, long ws_elems, long long* counts,
+                    double* auc, int V, istvt_stream_t stream);
 
 /* ---- token assembly (DSTTr.forward, vivit.py:133-142) -------------------------------------- */
 int istvt_tokens_fwd(const void* feats, const float* space, const float* temporal, const float* pos, void* x, long ldx,

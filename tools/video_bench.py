@@ -6,6 +6,8 @@
     python tools/video_bench.py --explain           # VideoScorer.explain against model.relevance on materialised windows
     python tools/video_bench.py --boxes             # whole 1080 x 1920 frames and face boxes (DESIGN.md "Frames and boxes")
 
+    python tools/video_bench.py --videos            # a set of 64 videos of 32 frames (DESIGN.md "Scoring a set of videos")
+
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
 float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
 code path that exists without the scorer (its host-side normalisation and 4x larger upload are NOT charged to it).
@@ -27,6 +29,12 @@ clips.crop_resize_host on host frames + upload of the crops, twice on its own (i
 torch restatement of the definition, not a tuned image library); (d) the kernel alone on all frames (events around the launch)
 against (e) a device-to-device copy that moves the same algorithmic bytes (box areas * 3 in, S * S * 3 out per frame: a
 copy of half their sum reads and writes that many).
+
+--videos (DESIGN.md "Scoring a set of videos"), strides 8 and 1 unless --strides says otherwise: --set-size device-resident
+uint8 videos of --video-frames frames.  Alternating, medians and spread as above: (a) score_videos(videos, labels=...);
+(b) the loop that exists without it, score(video) for every video.  One further, instrumented run of each gives the device
+time of the phases (stem, token assembly, transformer) and of the two new kernels (ops.prof events); the plan's full and
+partial window batches are reported with them.
 """
 import argparse
 import json
@@ -210,6 +218,85 @@ def boxes_bench(a, model):
     return out
 
 
+def _phases(scorer, model, fn, extra=()):
+    """one instrumented run of fn: device ms between the events around the three phases and the kernels named in `extra`"""
+    ops.kernel_profile = []
+    stem0, gather0, ft0 = scorer._stem, ops.tokens_gather_fwd, model.vit.forward_tokens
+
+    def wrap(name, f0):
+        def f(*p, **k):
+            with ops.prof(name):
+                return f0(*p, **k)
+        return f
+    try:
+        scorer._stem = wrap('phase:stem', stem0)
+        ops.tokens_gather_fwd = wrap('phase:tokens', gather0)
+        model.vit.forward_tokens = wrap('phase:transformer', ft0)
+        fn()
+        torch.cuda.synchronize()
+        split = {}
+        for name, e0, e1, nbytes, flops in ops.kernel_profile:
+            if name.startswith('phase:') or name in extra:
+                d = split.setdefault(name.replace('phase:', ''), {'ms': 0.0, 'launches': 0})
+                d['ms'] += e0.elapsed_time(e1)
+                d['launches'] += 1
+    finally:
+        ops.kernel_profile = None
+        scorer._stem, ops.tokens_gather_fwd = stem0, gather0
+        del model.vit.forward_tokens                       # the instance attribute; the method is back
+    return split
+
+
+def videos_bench(a, model):
+    g = torch.Generator().manual_seed(3)
+    V, n = a.set_size, a.video_frames
+    vids = [torch.randint(0, 256, (n, a.size, a.size, 3), generator=g, dtype=torch.uint8).cuda() for _ in range(V)]
+    labels = torch.randint(0, 2, (V,), generator=g)
+    out = {}
+    for stride in [int(s) for s in a.strides.split(',')]:
+        scorer = video.VideoScorer(model, stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch)
+        plan = video.SetPlan([n] * V, a.T, stride, True, a.frame_batch, a.window_batch)
+        W = len(plan.starts)
+        res = {}
+
+        def run_set():
+            res['a'] = scorer.score_videos(vids, labels=labels)
+
+        def run_loop():
+            res['b'] = [scorer.score(v) for v in vids]
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_set), timed(run_loop)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        ref = torch.cat([r.window_logits for r in res['b']])
+        diff = float((res['a'].window_logits - ref).abs().max())
+        mdiff = float((res['a'].logit_mean - torch.stack([r.logit_mean for r in res['b']])).abs().max())
+        split_a = _phases(scorer, model, run_set, ('windows_reduce', 'auc_pairs'))
+        split_b = _phases(scorer, model, run_loop)
+        sa, sb = stats(ta), stats(tb)
+        m = res['a'].metrics
+        rec = {'videos': V, 'frames_per_video': n, 'windows': W, 'score_videos': sa, 'score_loop': sb,
+               'loop_over_set': sb['median_ms'] / sa['median_ms'], 'set_ms_per_32_windows': sa['median_ms'] * 32 / W,
+               'loop_ms_per_32_windows': sb['median_ms'] * 32 / W, 'set_spread_ms': sa['max_ms'] - sa['min_ms'],
+               'loop_spread_ms': sb['max_ms'] - sb['min_ms'], 'max_abs_logit_diff': diff, 'max_abs_logit_mean_diff': mdiff,
+               'equal_bits': bool(torch.equal(res['a'].window_logits, ref)), 'full_window_batches': plan.full_batches,
+               'partial_window_batches': plan.partial_batches, 'bank_slots': plan.slots_used, 'split_set_ms': split_a,
+               'split_loop_ms': split_b, 'auc': float(m.auc), 'correct': int(m.correct)}
+        out[str(stride)] = rec
+        print('videos stride %d: %d videos, %d windows (%d full + %d partial batches, %d bank slots) | score_videos %.1f ms '
+              '(%.1f-%.1f) = %.2f ms / 32 windows | loop of score %.1f ms (%.1f-%.1f) = %.2f ms / 32 windows | loop / set x%.3f | '
+              'max |logit diff| %.2e, equal bits %s' % (stride, V, W, plan.full_batches, plan.partial_batches, plan.slots_used,
+                                                       sa['median_ms'], sa['min_ms'], sa['max_ms'], rec['set_ms_per_32_windows'],
+                                                       sb['median_ms'], sb['min_ms'], sb['max_ms'], rec['loop_ms_per_32_windows'],
+                                                       rec['loop_over_set'], diff, rec['equal_bits']), flush=True)
+        for what, split in (('score_videos', split_a), ('loop', split_b)):
+            print('          %s, one instrumented run: ' % what +
+                  ', '.join('%s %.3f ms in %d' % (k, v['ms'], v['launches']) for k, v in split.items()), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=256)
@@ -225,11 +312,14 @@ def main():
     ap.add_argument('--conv1-only', action='store_true')
     ap.add_argument('--explain', action='store_true')
     ap.add_argument('--boxes', action='store_true')
+    ap.add_argument('--videos', action='store_true')
+    ap.add_argument('--set-size', type=int, default=64)
+    ap.add_argument('--video-frames', type=int, default=32)
     ap.add_argument('--full-size', default='1080x1920')
     ap.add_argument('--box-sides', default='150-600')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    a.strides = a.strides or ('1,8' if a.explain or a.boxes else '1,2,4,8')
+    a.strides = a.strides or ('8,1' if a.videos else '1,8' if a.explain or a.boxes else '1,2,4,8')
     if not torch.cuda.is_available():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
@@ -239,6 +329,17 @@ def main():
     dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
     torch.manual_seed(0)
     model = XceptionVidTr(num_frames=a.T, grid=grid, depth=a.depth, compute_dtype=dt).cuda().eval()
+    if a.videos:
+        out = {'size': a.size, 'T': a.T, 'depth': a.depth, 'dtype': a.dtype, 'frame_batch': a.frame_batch,
+               'window_batch': a.window_batch, 'reps': a.reps, 'warmup': a.warmup, 'strides': videos_bench(a, model)}
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_set_bench': {k: {'loop_over_set': v['loop_over_set'],
+                                                  'set_ms_per_32_windows': v['set_ms_per_32_windows']}
+                                              for k, v in out['strides'].items()}}))
+        return
     if a.boxes:
         out = dict(boxes_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
                    window_batch=a.window_batch, reps=a.reps, warmup=a.warmup)
