@@ -14,5 +14,6 @@ Layout
     parallel.py    data-parallel gradient bucket (one RCCL all-reduce per step)
     explain.py     relevance maps (gradient-weighted attention rollout)
     video.py       whole-video scoring: uint8 frames, sliding windows, the stem once per frame
+    loss.py        the criterion: BCE with logits, accuracy and epoch meters in one launch
 """
-__all__ = ['ops', 'functional', 'network', 'parallel', 'explain', 'video']
+__all__ = ['ops', 'functional', 'network', 'parallel', 'explain', 'video', 'loss']

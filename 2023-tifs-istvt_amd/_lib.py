@@ -96,6 +96,8 @@ SIGNATURES = {
     'istvt_grad_norm_ws_elems': [L],
     'istvt_sgd_momentum_groups': [P, P, P, L, P, P, I, P, P, I, F, F, I, I, I, F, P, I, P],
     'istvt_adamw_groups': [P, P, P, P, L, P, P, I, P, P, I, F, F, F, L, I, F, P, I, P],
+    'istvt_bce_logits': [P, L, P, I, P, F, F, I, F, L, P, P, P, P, P],
+    'istvt_bce_logits_bwd': [P, P, I, P, L, P],
 }
 
 _lib = None

@@ -1051,3 +1051,85 @@ def frame_diff(x: Tensor, B: int, F: int, P: int, adjoint: bool = False) -> Tens
     _lib.check(_lib.lib().istvt_frame_diff(x.data_ptr(), out.data_ptr(), B, F, P, D, int(adjoint), dtype_code(x),
                                            _stream()), 'istvt_frame_diff')
     return out
+
+
+# ---- the criterion (include/istvt_hip.h istvt_bce_logits) ------------------------------------------
+BCE_TARGET_KINDS = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.uint8: 3}
+BCE_REDUCTIONS = {'none': 0, 'mean': 1, 'sum': 2}
+METER_WORDS = 10                   # istvt_loss_meter: two float64 sums and eight int64 words
+
+
+def check_meter_block(meter: Tensor, device) -> Tensor:
+    if (not torch.is_tensor(meter) or meter.dtype != torch.int64 or tuple(meter.shape) != (METER_WORDS,)
+            or not meter.is_contiguous() or meter.device != device):
+        raise RuntimeError('bce_logits: a meter block is a contiguous int64 (%d,) tensor on %s' % (METER_WORDS, device))
+    return meter
+
+
+def bce_logits(z: Tensor, y: Tensor, weight: Optional[Tensor] = None, pos_weight: float = 1.0, label_smoothing: float = 0.0,
+               reduction: str = 'mean', threshold: float = 0.0, want_loss: bool = False, want_reduced: bool = True,
+               want_grad: bool = True, meter: Optional[Tensor] = None):
+    """BCE with logits on z (n,) float32 (any positive stride) against y (n,) float32 / int64 / int32 / uint8 / bool, in one
+    launch -> (loss (n,) or None, reduced (1,) or None, d (n,) or None): the per-sample losses, their sum or mean (the sum with
+    reduction 'none') and the unscaled logit gradient of the reduced value; `meter` (a raw block, TrainMeter.tensor) is added
+    to.  Shapes and dtypes are checked before the device is, so a host tensor of the wrong kind says what is wrong with it."""
+    if z.dtype != torch.float32:
+        raise TypeError('bce_logits: logits must be float32, got %s' % z.dtype)
+    if y.dtype == torch.bool:
+        y = y.view(torch.uint8)
+    if y.dtype not in BCE_TARGET_KINDS:
+        raise TypeError('bce_logits: targets must be float32, int64, int32, uint8 or bool, got %s' % y.dtype)
+    if z.dim() != 1 or z.shape[0] < 1:
+        raise RuntimeError('bce_logits: logits (n,) with n >= 1 expected, got %s (pass outputs.view(-1))' % (tuple(z.shape),))
+    n = z.shape[0]
+    if tuple(y.shape) != (n,):
+        raise RuntimeError('bce_logits: %d logits, targets %s' % (n, tuple(y.shape)))
+    if weight is not None:
+        if weight.dtype != torch.float32:
+            raise TypeError('bce_logits: weight must be float32, got %s' % weight.dtype)
+        if tuple(weight.shape) != (n,):
+            raise RuntimeError('bce_logits: %d logits, per-sample weight %s' % (n, tuple(weight.shape)))
+    if reduction not in BCE_REDUCTIONS:
+        raise ValueError("bce_logits: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError('bce_logits: label_smoothing must be in [0, 1), got %r' % (label_smoothing,))
+    if n > 1 << 30:
+        raise RuntimeError('bce_logits: at most 2^30 logits per call, got %d' % n)
+    _req(z, 'logits')
+    for t, name in ((y, 'targets'), (weight, 'weight')):
+        if t is not None and t.device != z.device:
+            raise RuntimeError('bce_logits: logits are on %s, %s on %s' % (z.device, name, t.device))
+    if meter is not None:
+        check_meter_block(meter, z.device)
+    stride = z.stride(0) if n > 1 else 1
+    if stride < 1:
+        z, stride = z.contiguous(), 1
+    y = _c(y)
+    weight = None if weight is None else _c(weight)
+    loss = torch.empty((n,), dtype=torch.float32, device=z.device) if want_loss else None
+    reduced = torch.empty((1,), dtype=torch.float32, device=z.device) if want_reduced else None
+    d = torch.empty((n,), dtype=torch.float32, device=z.device) if want_grad else None
+    with prof('bce_logits', 4 * n * (2 + (weight is not None) + want_loss + want_grad)):
+        _lib.check(_lib.lib().istvt_bce_logits(z.data_ptr(), stride, y.data_ptr(), BCE_TARGET_KINDS[y.dtype], _ptr(weight),
+                                               float(pos_weight), float(label_smoothing), BCE_REDUCTIONS[reduction],
+                                               float(threshold), n, _ptr(loss), _ptr(reduced), _ptr(d), _ptr(meter), _stream()),
+                   'istvt_bce_logits')
+    return loss, reduced, d
+
+
+def bce_logits_bwd(d: Tensor, g: Tensor) -> Tensor:
+    """d (n,) from bce_logits times the incoming gradient g -- one element (mean / sum) or (n,) ('none'), read on the device"""
+    _req(d, 'd')
+    _req(g, 'grad_output')
+    if d.dtype != torch.float32 or g.dtype != torch.float32:
+        raise TypeError('bce_logits_bwd: float32 expected, got %s and %s' % (d.dtype, g.dtype))
+    n = d.shape[0]
+    if d.dim() != 1 or g.numel() not in (1, n) or g.device != d.device:
+        raise RuntimeError('bce_logits_bwd: d %s, grad_output %s on %s / %s' % (tuple(d.shape), tuple(g.shape), d.device, g.device))
+    per_sample = n > 1 and g.numel() == n
+    d, g = _c(d), _c(g)
+    grad = torch.empty_like(d)
+    with prof('bce_logits_bwd', 12 * n):
+        _lib.check(_lib.lib().istvt_bce_logits_bwd(d.data_ptr(), g.data_ptr(), int(per_sample), grad.data_ptr(), n, _stream()),
+                   'istvt_bce_logits_bwd')
+    return grad

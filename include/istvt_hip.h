@@ -443,6 +443,48 @@ int istvt_adamw_groups(float* p, float* g, float* m, float* v, long n, const lon
                        long step, int zero_grad, float grad_scale, const void* info, int skip_nonfinite,
                        istvt_stream_t stream);
 
+/* ---- the criterion: nn.BCEWithLogitsLoss, the accuracy count and the epoch meters (train_CNN.py:148,526-536) ----
+ * THE METER BLOCK: ten 8-byte words of device memory that istvt_bce_logits ADDS one call to.  One lane updates it with a
+ * plain read-modify-write: calls that share a block run on one stream (single writer, stream-ordered, no atomics).  The
+ * caller zeroes it (one fill) where an epoch starts. */
+typedef struct istvt_loss_meter {
+    double loss_sum;       /* sum of the per-sample losses, fp64 */
+    double batch_loss_sum; /* sum of the reduced values the calls returned (each rounded to fp32 once): what
+                              `train_loss += loss.item()` accumulates; with reduction none, the call's sum */
+    long long seen;        /* samples */
+    long long correct;     /* tp + tn */
+    long long tp, tn, fp, fn; /* prediction z > threshold against y > 0.5 (the unsmoothed target) */
+    long long calls;
+    long long reserved;
+} istvt_loss_meter;
+#define ISTVT_TARGET_F32 0
+#define ISTVT_TARGET_I64 1
+#define ISTVT_TARGET_I32 2
+#define ISTVT_TARGET_U8 3
+#define ISTVT_REDUCE_NONE 0
+#define ISTVT_REDUCE_MEAN 1
+#define ISTVT_REDUCE_SUM 2
+/* One launch, one workgroup.  z: float logits, sample i at z[i * stride] (stride >= 1 elements: a column of a (B, nc)
+ * tensor needs no copy); y: n targets of the type y_kind names, contiguous; w: float[n] per-sample weights or NULL.
+ *   y' = y (1 - label_smoothing) + label_smoothing / 2                                 0 <= label_smoothing < 1
+ *   l_i = w_i [ (1 - y') z + (1 + (pos_weight - 1) y') (log1p(exp(-|z|)) + max(-z, 0)) ]     (torch's formula; computed as
+ *         w_i [ (1 - y') softplus(z) + pos_weight y' softplus(-z) ], the same function without the cancellation)
+ *   reduced = sum_i l_i (ISTVT_REDUCE_SUM, and _NONE) or that sum / n (ISTVT_REDUCE_MEAN: by n, as torch, not by sum w)
+ *   d_i = d reduced / d z_i = w_i [ (1 - y') sigmoid(z) - pos_weight y' sigmoid(-z) ], times 1 / n for the mean
+ * Outputs, each nullable: loss float[n] (per sample), reduced float[1], d float[n] (the UNSCALED logit gradient:
+ * istvt_bce_logits_bwd multiplies it by the incoming gradient), meter (an istvt_loss_meter, added to).
+ * Per-sample arithmetic is fp32.  The sum is fp64 in a fixed order -- lane t of T = min(1024, max(64, 2^ceil(log2 n)))
+ * adds samples t, t + T, ... in ascending order, a binary tree in LDS folds the lanes -- and is rounded to fp32 once; counts
+ * are integers.  Two calls give the same bits.  A NaN logit predicts negative (NaN > threshold is false), as the
+ * reference's (outputs > 0) does, and makes the sums NaN.  1 <= n <= 2^30; the one workgroup walks n samples in
+ * ceil(n / 1024) rounds (DESIGN.md section 16 has the times). */
+int istvt_bce_logits(const float* z, long stride, const void* y, int y_kind, const float* w, float pos_weight,
+                     float label_smoothing, int reduction, float threshold, long n, float* loss, float* reduced, float* d,
+                     void* meter, istvt_stream_t stream);
+/* grad[i] = d[i] * (g_per_sample ? g[i] : g[0]); g in DEVICE memory (the gradient autograd hands the criterion: one
+ * element for mean / sum, n for none), so (loss * s).backward() needs no host read. */
+int istvt_bce_logits_bwd(const float* d, const float* g, int g_per_sample, float* grad, long n, istvt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
