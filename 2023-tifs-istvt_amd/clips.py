@@ -11,6 +11,11 @@ the float path on that tensor (DESIGN.md "Training from bytes").
 
 Whole frames and face boxes (DESIGN.md "Frames and boxes") are the second half of this file: ``check_boxes``,
 ``resize_weights``, ``crop_resize_host`` (the definition of ops.crop_resize_u8) and ``random_boxes``.
+
+JPEG recompression (DESIGN.md "JPEG round trip") is the third part: ``jpeg_quant_tables``, ``check_qualities``,
+``jpeg_roundtrip_host`` (the definition of ops.jpeg_roundtrip_u8, integers only) and ``random_qualities``.  Training needs no
+new model code: a loader yields ``(u8, boxes, qualities, flips)`` and the step is
+``model(ops.jpeg_roundtrip_u8(ops.crop_resize_u8(u8, boxes, S), q), view=flips)``.
 """
 from typing import Optional
 
@@ -218,3 +223,200 @@ def random_boxes(B: int, Hs: int, Ws: int, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3
     y0 = torch.minimum(y0, Hs - h)
     x0 = torch.minimum(x0, Ws - w)
     return torch.stack([y0, x0, h, w], dim=1).to(torch.int32).contiguous()
+
+
+# ------------------------------------------------------------------------------------------ JPEG round trip
+# DESIGN.md "JPEG round trip": the uint8 RGB a baseline JPEG encoder and decoder hand back at quality q, bytes to bytes and
+# without a bitstream (entropy coding is lossless: quantising and de-quantising the DCT coefficients is the whole lossy
+# part).  The pipeline is libjpeg's, in int32 from end to end: 16-bit fixed-point colour transforms, the 13-bit fixed-point
+# "slow integer" 8-point DCT and IDCT (Loeffler, Ligtenberg and Moschytz; two passes with 2 extra bits between them, the
+# forward result scaled by 8), integer quantisation.  ops.jpeg_roundtrip_u8 is the device kernel and gives these bits.
+JPEG_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+             14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+             49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)           # ITU-T T.81 Annex K.1
+JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+               47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32                                    # Annex K.2
+JPEG_SUBSAMPLINGS = {'420': 2, '444': 1}   # chroma step per axis; the MCU is 8 * step pixels square
+
+
+def jpeg_quant_tables(q: int) -> Tensor:
+    """The two quantisation tables of quality q in 1..100 as libjpeg scales Annex K: s = 5000 // q for q < 50, else
+    200 - 2 q; entry = (base * s + 50) // 100 clamped to 1..255.  int32 (2, 8, 8): luminance, chrominance; row = vertical
+    frequency."""
+    q = int(q)
+    if not 1 <= q <= 100:
+        raise ValueError('jpeg_quant_tables: the quality must lie in [1, 100], got %d' % q)
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    base = torch.tensor([JPEG_LUMA, JPEG_CHROMA], dtype=torch.int32)
+    return ((base * s + 50) // 100).clamp_(1, 255).reshape(2, 8, 8)
+
+
+def check_qualities(quality, n: int) -> Tensor:
+    """Host validation of a quality table before any launch: int32 (n,) with every entry <= 100; 1..100 compress, an entry
+    <= 0 leaves its frame (or clip) unchanged.  A Python int stands for that quality everywhere.  Returns the table on the
+    host (a device tensor is copied back, which waits for the device: hand over the loader's host tensor)."""
+    if isinstance(quality, int) and not isinstance(quality, bool):
+        quality = torch.full((n,), quality, dtype=torch.int32)
+    if not torch.is_tensor(quality):
+        raise TypeError('quality must be an int or an int32 tensor (n,), got %s' % type(quality).__name__)
+    if quality.dtype != torch.int32:
+        raise TypeError('quality must be int32, got %s' % quality.dtype)
+    if quality.dim() != 1 or quality.shape[0] != n:
+        raise ValueError('quality must have shape (%d,), one entry per frame or clip, got %s' % (n, tuple(quality.shape)))
+    q = quality.detach().cpu()
+    if bool((q > 100).any()):
+        raise ValueError('quality: entries must be at most 100 (1..100 compress, <= 0 copies), got up to %d' % int(q.max()))
+    return q
+
+
+def _jpeg_sub(subsampling) -> int:
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("subsampling must be '420' or '444', got %r" % (subsampling,))
+    return JPEG_SUBSAMPLINGS[subsampling]
+
+
+def _descale(x: Tensor, n: int) -> Tensor:
+    return (x + (1 << (n - 1))) >> n
+
+
+def _fdct8(d, first: bool):
+    """One pass of the forward DCT over 8 int32 tensors.  The first pass leaves its results scaled up by 4, the second takes
+    that out again; together they give 8 x the DCT."""
+    t0, t7, t1, t6 = d[0] + d[7], d[0] - d[7], d[1] + d[6], d[1] - d[6]
+    t2, t5, t3, t4 = d[2] + d[5], d[2] - d[5], d[3] + d[4], d[3] - d[4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    n = 11 if first else 15
+    o = [None] * 8
+    o[0] = (t10 + t11) * 4 if first else _descale(t10 + t11, 2)
+    o[4] = (t10 - t11) * 4 if first else _descale(t10 - t11, 2)
+    z1 = (t12 + t13) * 4433
+    o[2] = _descale(z1 + t13 * 6270, n)
+    o[6] = _descale(z1 - t12 * 15137, n)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * 9633
+    t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+    z1, z2 = z1 * -7373, z2 * -20995
+    z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
+    o[7] = _descale(t4 + z1 + z3, n)
+    o[5] = _descale(t5 + z2 + z4, n)
+    o[3] = _descale(t6 + z2 + z3, n)
+    o[1] = _descale(t7 + z1 + z4, n)
+    return o
+
+
+def _idct8(d, first: bool):
+    """One pass of the inverse DCT over 8 int32 tensors: the first keeps 2 extra bits, the second removes them and the
+    forward transform's factor 8."""
+    z1 = (d[2] + d[6]) * 4433
+    t2, t3 = z1 - d[6] * 15137, z1 + d[2] * 6270
+    t0, t1 = (d[0] + d[4]) * 8192, (d[0] - d[4]) * 8192
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = d[7], d[5], d[3], d[1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * 9633
+    t0, t1, t2, t3 = t0 * 2446, t1 * 16819, t2 * 25172, t3 * 12299
+    z1, z2 = z1 * -7373, z2 * -20995
+    z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    n = 11 if first else 18
+    return [_descale(t10 + t3, n), _descale(t11 + t2, n), _descale(t12 + t1, n), _descale(t13 + t0, n),
+            _descale(t13 - t0, n), _descale(t12 - t1, n), _descale(t11 - t2, n), _descale(t10 - t3, n)]
+
+
+def _jpeg_plane(p: Tensor, qt: Tensor) -> Tensor:
+    """One component through its 8 x 8 blocks: p int32 (n, Hp, Wp) samples 0..255 with Hp, Wp multiples of 8, qt int32
+    (n, 8, 8) -> the reconstructed samples, int32 0..255.  Level shift, rows then columns forward, quantise (half away from
+    zero) and multiply back, columns then rows inverse, + 128, clamp."""
+    n, Hp, Wp = p.shape
+    b = (p - 128).reshape(n, Hp // 8, 8, Wp // 8, 8)                           # (frame, block row, v, block column, u)
+    b = torch.stack(_fdct8(b.unbind(4), True), dim=4)
+    b = torch.stack(_fdct8(b.unbind(2), False), dim=2)                        # 8 x the coefficients
+    q = qt[:, None, :, None, :]
+    k = (b.abs() + q * 4) // (q * 8)                                          # (|c| + q / 2) / q in the units of the table
+    b = torch.where(b < 0, -k, k) * q
+    b = torch.stack(_idct8(b.unbind(2), True), dim=2)
+    b = torch.stack(_idct8(b.unbind(4), False), dim=4)
+    return (b + 128).clamp_(0, 255).reshape(n, Hp, Wp)
+
+
+def _jpeg_upsample(c: Tensor, H: int, W: int) -> Tensor:
+    """libjpeg's "fancy" 2 x 2 upsampling of a chroma plane int32 (n, Hc, Wc), Hc = ceil(H / 2), Wc = ceil(W / 2) -> (n, H,
+    W): 3/4 of the nearer and 1/4 of the farther sample per axis, vertically first and unrounded, then horizontally with
+    + 8 (even columns) or + 7 (odd ones) and >> 4; the plane's edges replicate."""
+    Hc, Wc = c.shape[1], c.shape[2]
+    y, x = torch.arange(H), torch.arange(W)
+    near, far = y >> 1, ((y >> 1) + (y & 1) * 2 - 1).clamp_(0, Hc - 1)
+    col = 3 * c[:, near] + c[:, far]
+    this, other = x >> 1, ((x >> 1) + (x & 1) * 2 - 1).clamp_(0, Wc - 1)
+    return (3 * col[:, :, this] + col[:, :, other] + (8 - (x & 1)).to(torch.int32)) >> 4
+
+
+def jpeg_roundtrip_host(u8: Tensor, quality, subsampling: str = '420') -> Tensor:
+    """The definition on the host: uint8 (n, H, W, 3) or (B, T, H, W, 3), any H, W >= 1, and quality int32 (n,) / (B,) (one
+    entry per frame, or per clip and shared by its T frames; an int for all) -> the uint8 RGB of the same shape that a
+    baseline JPEG encoder and decoder would hand back.  Entries 1..100 compress, an entry <= 0 copies the frame.  int32
+    arithmetic only:
+
+      colour in    Y = (19595 R + 38470 G + 7471 B + 32768) >> 16;  Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767)
+                   >> 16;  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+      padding      to whole MCUs (16 x 16 pixels for '420', 8 x 8 for '444') by edge replication
+      downsample   '420': 2 x 2 box, (sum + bias) >> 2, bias 1, 2, 1, 2, ... along a row; chroma rows below the frame's
+                   ceil(H / 2) repeat the last of those (libjpeg pads the width and an odd height before the downsample,
+                   the rest of the height after it)
+      blocks       _jpeg_plane with jpeg_quant_tables(q): luminance table for Y, chrominance table for Cb and Cr
+      upsample     '420': _jpeg_upsample on the ceil(H / 2) x ceil(W / 2) chroma samples that belong to the frame
+      colour out   R = Y + ((91881 Cr' + 32768) >> 16);  G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16);  B = Y +
+                   ((116130 Cb' + 32768) >> 16) with Cb' = Cb - 128, Cr' = Cr - 128; clamp to 0..255; crop to H x W
+
+    No product or sum leaves int32: the samples have 8 bits, the colour constants 17, the DCT constants 15 with at most 13
+    bits of headroom used by the passes (libjpeg's own argument for its 32-bit "slow integer" transforms)."""
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError('jpeg_roundtrip_host expects non-empty uint8 (n, H, W, 3) or (B, T, H, W, 3), got %s %s'
+                         % (u8.dtype, tuple(u8.shape)))
+    sub = _jpeg_sub(subsampling)
+    q = check_qualities(quality, u8.shape[0])
+    if u8.dim() == 5:
+        q = q.repeat_interleave(u8.shape[1])
+    H, W = u8.shape[-3], u8.shape[-2]
+    src = u8.reshape((-1, H, W, 3)).cpu()
+    mcu = 8 * sub
+    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
+    rgb = src[:, torch.arange(Hp).clamp_(max=H - 1)][:, :, torch.arange(Wp).clamp_(max=W - 1)].to(torch.int32)
+    R, G, B = rgb.unbind(3)
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    tables = torch.stack([jpeg_quant_tables(min(max(int(v), 1), 100)) for v in q])       # (n, 2, 8, 8); unused where q <= 0
+    if sub == 2:
+        bias = torch.tensor([1, 2], dtype=torch.int32).repeat(Wp // 4)
+        Cb, Cr = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + bias) >> 2 for c in (Cb, Cr))
+        rows = torch.arange(Hp // 2).clamp_(max=(H + 1) // 2 - 1)              # below the frame: the last chroma row again
+        Cb, Cr = Cb[:, rows], Cr[:, rows]
+    Y = _jpeg_plane(Y, tables[:, 0])[:, :H, :W]
+    Cb, Cr = _jpeg_plane(Cb, tables[:, 1]), _jpeg_plane(Cr, tables[:, 1])
+    if sub == 2:
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        Cb, Cr = _jpeg_upsample(Cb[:, :Hc, :Wc], H, W), _jpeg_upsample(Cr[:, :Hc, :Wc], H, W)
+    else:
+        Cb, Cr = Cb[:, :H, :W], Cr[:, :H, :W]
+    Cb, Cr = Cb - 128, Cr - 128
+    out = torch.stack([Y + ((91881 * Cr + 32768) >> 16), Y + ((-22554 * Cb - 46802 * Cr + 32768) >> 16),
+                       Y + ((116130 * Cb + 32768) >> 16)], dim=3).clamp_(0, 255).to(torch.uint8)
+    keep = q <= 0
+    out[keep] = src[keep]
+    return out.reshape(u8.shape).to(u8.device)
+
+
+def random_qualities(n: int, p: float = 0.5, lo: int = 30, hi: int = 95, generator: Optional[torch.Generator] = None) -> Tensor:
+    """One random quality per frame or clip for compression augmentation: 0 (leave it alone) with probability 1 - p, otherwise
+    uniform in [lo, hi].  Returns an int32 (n,) host tensor (contiguous: ready for pin_memory()), reproducible from
+    `generator`."""
+    if n < 1:
+        raise ValueError('random_qualities: need n >= 1, got %d' % n)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('random_qualities: p must be a probability, got %r' % (p,))
+    if not 1 <= lo <= hi <= 100:
+        raise ValueError('random_qualities: need 1 <= lo <= hi <= 100, got lo=%r hi=%r' % (lo, hi))
+    on = torch.rand((n,), generator=generator) < p
+    q = torch.randint(lo, hi + 1, (n,), generator=generator)
+    return torch.where(on, q, torch.zeros_like(q)).to(torch.int32).contiguous()

@@ -1,0 +1,320 @@
+// JPEG round trip (DESIGN.md "JPEG round trip"): frames uint8 [n][H][W][3] -> the uint8 RGB a baseline JPEG encoder and
+// decoder hand back at each frame's quality, bytes to bytes and without a bitstream.  clips.jpeg_roundtrip_host is the
+// definition and this file gives its bits: int32 arithmetic only (libjpeg's fixed-point colour transforms and its 13-bit
+// "slow integer" DCT / IDCT), no floating point, no atomics, one writer per byte.
+//
+//   colour in    Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb / Cr likewise around 128
+//   padding      to whole MCUs (16 x 16 pixels at 4:2:0, 8 x 8 at 4:4:4) by edge replication: every source read goes through
+//                clamped coordinates
+//   downsample   4:2:0: 2 x 2 box, (sum + 1 or 2) >> 2; chroma rows below the frame's ceil(H / 2) repeat the last of those
+//   blocks       - 128, rows then columns forward (8 x the DCT), k = (|c| + 4 q) / (8 q) with the sign of c, k * q, columns
+//                then rows inverse, + 128, clamp.  q = the Annex K entry scaled by the frame's quality
+//   upsample     4:2:0: 3/4 + 1/4 vertically, then horizontally with + 8 / + 7 and >> 4; the chroma plane's edges replicate
+//   colour out   R = Y + ((91881 Cr' + 32768) >> 16), ... ; clamp
+//
+// Two launches.  jpeg_planes_kernel: a workgroup takes a tile of one MCU row x 64 pixels of a frame, stages its source bytes
+// in LDS with 16-byte loads (u8_stage_rows), converts them into 24 blocks of 8 x 8 samples in LDS -- 16 Y + 4 Cb + 4 Cr at
+// 4:2:0, 8 + 8 + 8 at 4:4:4 -- and runs the 192 row and column transforms of a pass one per lane: forward rows | forward
+// columns, quantise, multiply back, inverse columns (all in the lane's registers) | inverse rows, whose 8 bytes leave as one
+// store into the caller's scratch planes (per frame Y [Hp][Wp], then Cb and Cr [Hp / s][Wp / s], s = 2 or 1; Hp, Wp = H, W
+// rounded up to whole MCUs).  jpeg_rgb_kernel: a lane takes 4 consecutive pixels of the batch, reads Y and the (up to 4 + 4)
+// chroma samples around each from the planes, and stores their 12 bytes as three dwords.  A frame whose quality is <= 0 is
+// skipped by the first kernel and copied by the second.
+#include "u8_view.h"
+
+namespace {
+
+constexpr int JP_TILE_W = 64;               // pixels per tile row: 8 blocks of Y
+constexpr int JP_BLOCKS = 24;               // 8 x 8 blocks of a tile, either subsampling
+constexpr int JP_BLOCK_LD = 72;             // ints between blocks in LDS: 64 + 8, so a column pass meets no bank twice
+constexpr int JP_PITCH = 208;               // u8_row_pitch(JP_TILE_W)
+
+// ITU-T T.81 Annex K.1 (luminance) and K.2 (chrominance), row = vertical frequency
+__constant__ unsigned char JP_BASE[128] = {
+    16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+    14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+    49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99,
+    17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+    47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+    99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+__device__ __forceinline__ int jp_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+__device__ __forceinline__ int jp_byte(int v) { return min(max(v, 0), 255); }
+
+// One pass of the forward DCT (clips._fdct8): the first leaves 2 extra bits, the second takes them out; 8 x the DCT
+template <bool FIRST> __device__ __forceinline__ void jp_fdct8(int (&d)[8]) {
+    int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    constexpr int N = FIRST ? 11 : 15;
+    d[0] = FIRST ? (t10 + t11) * 4 : jp_descale(t10 + t11, 2);
+    d[4] = FIRST ? (t10 - t11) * 4 : jp_descale(t10 - t11, 2);
+    int z1 = (t12 + t13) * 4433;
+    d[2] = jp_descale(z1 + t13 * 6270, N);
+    d[6] = jp_descale(z1 - t12 * 15137, N);
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;
+    z1 *= -7373, z2 *= -20995;
+    z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    d[7] = jp_descale(t4 + z1 + z3, N);
+    d[5] = jp_descale(t5 + z2 + z4, N);
+    d[3] = jp_descale(t6 + z2 + z3, N);
+    d[1] = jp_descale(t7 + z1 + z4, N);
+}
+
+// One pass of the inverse DCT (clips._idct8): the first keeps 2 extra bits, the second removes them and the factor 8
+template <bool FIRST> __device__ __forceinline__ void jp_idct8(int (&d)[8]) {
+    int z1 = (d[2] + d[6]) * 4433;
+    int t2 = z1 - d[6] * 15137, t3 = z1 + d[2] * 6270;
+    int t0 = (d[0] + d[4]) * 8192, t1 = (d[0] - d[4]) * 8192;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    t0 = d[7], t1 = d[5], t2 = d[3], t3 = d[1];
+    z1 = t0 + t3;
+    int z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
+    const int z5 = (z3 + z4) * 9633;
+    t0 *= 2446, t1 *= 16819, t2 *= 25172, t3 *= 12299;
+    z1 *= -7373, z2 *= -20995;
+    z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    t0 += z1 + z3, t1 += z2 + z4, t2 += z2 + z3, t3 += z1 + z4;
+    constexpr int N = FIRST ? 11 : 18;
+    d[0] = jp_descale(t10 + t3, N), d[7] = jp_descale(t10 - t3, N);
+    d[1] = jp_descale(t11 + t2, N), d[6] = jp_descale(t11 - t2, N);
+    d[2] = jp_descale(t12 + t1, N), d[5] = jp_descale(t12 - t1, N);
+    d[3] = jp_descale(t13 + t0, N), d[4] = jp_descale(t13 - t0, N);
+}
+
+struct JpYcc {
+    int y, cb, cr;
+};
+
+__device__ __forceinline__ JpYcc jp_ycc(const unsigned char* px) {
+    const int r = px[0], g = px[1], b = px[2];
+    JpYcc v;
+    v.y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    v.cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    v.cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+    return v;
+}
+
+// bytes of one frame's planes in the scratch: Hp, Wp are whole MCUs, so every plane starts on an 8-byte boundary
+template <int SUB> __host__ __device__ __forceinline__ long jp_frame_bytes(int Hp, int Wp) {
+    return SUB == 2 ? (long)Hp * Wp / 2 * 3 : (long)Hp * Wp * 3;
+}
+
+// SUB = chroma step per axis: 2 (4:2:0, MCU 16 x 16) or 1 (4:4:4, MCU 8 x 8).  A tile is one MCU row x JP_TILE_W pixels.
+template <int SUB>
+__global__ __launch_bounds__(256) void jpeg_planes_kernel(const uint8_t* __restrict__ x, long total,
+                                                          const int* __restrict__ quality, uint8_t* __restrict__ planes,
+                                                          int H, int W, int Hp, int Wp, int tiles_y, int tiles_x) {
+    constexpr int TH = 8 * SUB;
+    __shared__ int ws[JP_BLOCKS * JP_BLOCK_LD];
+    __shared__ int qt[128];
+    __shared__ __align__(16) unsigned char stage[TH * JP_PITCH];
+
+    const int tid = threadIdx.x;
+    const int per = tiles_y * tiles_x;
+    const long f = blockIdx.x / per;
+    const int rem = (int)(blockIdx.x - f * per);
+    const int y0 = (rem / tiles_x) * TH, x0 = (rem % tiles_x) * JP_TILE_W;
+    const int q = min(quality[f], 100);
+    if (q <= 0) return;                                          // the whole workgroup: jpeg_rgb_kernel copies this frame
+
+    if (tid < 128) {
+        const int s = q < 50 ? 5000 / q : 200 - 2 * q;
+        qt[tid] = min(max((JP_BASE[tid] * s + 50) / 100, 1), 255);
+    }
+    // the tile's part of the frame (y0 < H and x0 < W: padding adds less than one MCU); pixels past it replicate its edge
+    const int rows = min(TH, H - y0), cols = min(JP_TILE_W, W - x0);
+    const int rstride = W * 3;
+    const int lead0 = u8_stage_rows(x, total, ((f * H + y0) * (long)W + x0) * 3, rstride, rows, cols, stage, JP_PITCH, tid, 256);
+    __syncthreads();
+
+    auto pixel = [&](int r, int c) -> const unsigned char* {
+        r = min(r, rows - 1);
+        return stage + r * JP_PITCH + u8_row_lead(lead0, r, rstride) + min(c, cols - 1) * 3;
+    };
+    if (SUB == 2) {                                              // one 2 x 2 quad per lane: 8 x 32 quads
+        const int qy = tid >> 5, qx = tid & 31;
+        // chroma row y0 / 2 + qy of the frame, or the last one the frame has (its two source rows lie in this tile)
+        const int cr0 = 2 * min(y0 / 2 + qy, (H + 1) / 2 - 1) - y0;
+        int cb = 0, cr = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int dy = j >> 1, dx = j & 1;
+            const int ty = 2 * qy + dy, tx = 2 * qx + dx;
+            ws[((ty >> 3) * 8 + (tx >> 3)) * JP_BLOCK_LD + (ty & 7) * 8 + (tx & 7)] = jp_ycc(pixel(ty, tx)).y - 128;
+            const JpYcc c = jp_ycc(pixel(cr0 + dy, tx));
+            cb += c.cb, cr += c.cr;
+        }
+        const int bias = 1 + (qx & 1);
+        const int at = (qx >> 3) * JP_BLOCK_LD + qy * 8 + (qx & 7);
+        ws[16 * JP_BLOCK_LD + at] = ((cb + bias) >> 2) - 128;
+        ws[20 * JP_BLOCK_LD + at] = ((cr + bias) >> 2) - 128;
+    } else {                                                     // 8 x 64 pixels, two per lane
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int p = tid + 256 * j;
+            const int ty = p >> 6, tx = p & 63;
+            const JpYcc c = jp_ycc(pixel(ty, tx));
+            const int at = (tx >> 3) * JP_BLOCK_LD + ty * 8 + (tx & 7);
+            ws[at] = c.y - 128;
+            ws[8 * JP_BLOCK_LD + at] = c.cb - 128;
+            ws[16 * JP_BLOCK_LD + at] = c.cr - 128;
+        }
+    }
+    __syncthreads();
+
+    const int b = tid >> 3, k = tid & 7;                         // block and its row (passes 1, 3) or column (pass 2)
+    const bool on = tid < JP_BLOCKS * 8;
+    int d[8];
+    if (on) {                                                    // forward, rows
+        int* row = ws + b * JP_BLOCK_LD + k * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        jp_fdct8<true>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[i] = d[i];
+    }
+    __syncthreads();
+    if (on) {                                                    // forward columns, quantise, multiply back, inverse columns
+        int* col = ws + b * JP_BLOCK_LD + k;
+        const int* qc = qt + (b < (SUB == 2 ? 16 : 8) ? 0 : 64) + k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = col[i * 8];
+        jp_fdct8<false>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int qv = qc[i * 8];
+            const int n = (abs(d[i]) + 4 * qv) / (8 * qv);
+            d[i] = (d[i] < 0 ? -n : n) * qv;
+        }
+        jp_idct8<true>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) col[i * 8] = d[i];
+    }
+    __syncthreads();
+    if (on) {                                                    // inverse rows -> 8 bytes of a plane
+        const int* row = ws + b * JP_BLOCK_LD + k * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        jp_idct8<false>(d);
+        int comp, py, px, pw;                                    // component, row and first column in its plane, plane width
+        if (SUB == 2) {
+            if (b < 16) comp = 0, py = y0 + (b >> 3) * 8 + k, px = x0 + (b & 7) * 8, pw = Wp;
+            else comp = 1 + ((b - 16) >> 2), py = y0 / 2 + k, px = x0 / 2 + ((b - 16) & 3) * 8, pw = Wp / 2;
+        } else {
+            comp = b >> 3, py = y0 + k, px = x0 + (b & 7) * 8, pw = Wp;
+        }
+        if (px < pw) {                                           // a tile may reach past the last MCU of the row
+            const long plane = (long)Hp * Wp;                    // Y; a chroma plane has plane / (SUB * SUB) bytes
+            uint8_t* dst = planes + f * jp_frame_bytes<SUB>(Hp, Wp) + (comp ? plane + (comp - 1) * (plane / (SUB * SUB)) : 0) +
+                           (long)py * pw + px;
+            uint2 v;
+            v.x = jp_byte(d[0] + 128) | jp_byte(d[1] + 128) << 8 | jp_byte(d[2] + 128) << 16 | jp_byte(d[3] + 128) << 24;
+            v.y = jp_byte(d[4] + 128) | jp_byte(d[5] + 128) << 8 | jp_byte(d[6] + 128) << 16 | jp_byte(d[7] + 128) << 24;
+            *reinterpret_cast<uint2*>(dst) = v;
+        }
+    }
+}
+
+// chroma at pixel (y, x) of the frame from a plane of the frame's Hc x Wc samples (row pitch pw)
+template <int SUB> __device__ __forceinline__ int jp_chroma(const uint8_t* __restrict__ c, int pw, int Hc, int Wc, int y, int x) {
+    if (SUB == 1) return c[(long)y * pw + x];
+    const int cy = y >> 1, cx = x >> 1;
+    const uint8_t* near = c + (long)cy * pw;
+    const uint8_t* far = c + (long)min(max(cy + (y & 1) * 2 - 1, 0), Hc - 1) * pw;
+    const int ox = min(max(cx + (x & 1) * 2 - 1, 0), Wc - 1);
+    return (3 * (3 * near[cx] + far[cx]) + 3 * near[ox] + far[ox] + 8 - (x & 1)) >> 4;
+}
+
+// 4 consecutive pixels of the batch per lane; out4 = the output may be written as dwords
+template <int SUB>
+__global__ __launch_bounds__(256) void jpeg_rgb_kernel(const uint8_t* __restrict__ x, const int* __restrict__ quality,
+                                                       const uint8_t* __restrict__ planes, uint8_t* __restrict__ out, long npix,
+                                                       int H, int W, int Hp, int Wp, int out4) {
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= npix) return;
+    const long hw = (long)H * W;
+    long f = p0 / hw;
+    int rest = (int)(p0 - f * hw);
+    int y = rest / W, xx = rest - y * W;
+    const long plane = (long)Hp * Wp, cplane = plane / (SUB * SUB);
+    const int pw = Wp / SUB, Hc = (H + SUB - 1) / SUB, Wc = (W + SUB - 1) / SUB;
+    unsigned char o[12];
+    const int cnt = (int)min(4L, npix - p0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < cnt) {
+            const long g = (p0 + j) * 3;
+            if (quality[f] <= 0) {
+                o[3 * j] = x[g], o[3 * j + 1] = x[g + 1], o[3 * j + 2] = x[g + 2];
+            } else {
+                const uint8_t* fp = planes + f * jp_frame_bytes<SUB>(Hp, Wp);
+                const int yv = fp[(long)y * Wp + xx];
+                const int cb = jp_chroma<SUB>(fp + plane, pw, Hc, Wc, y, xx) - 128;
+                const int cr = jp_chroma<SUB>(fp + plane + cplane, pw, Hc, Wc, y, xx) - 128;
+                o[3 * j] = (unsigned char)jp_byte(yv + ((91881 * cr + 32768) >> 16));
+                o[3 * j + 1] = (unsigned char)jp_byte(yv + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+                o[3 * j + 2] = (unsigned char)jp_byte(yv + ((116130 * cb + 32768) >> 16));
+            }
+            if (++xx == W) {
+                xx = 0;
+                if (++y == H) y = 0, ++f;
+            }
+        } else {
+            o[3 * j] = o[3 * j + 1] = o[3 * j + 2] = 0;
+        }
+    }
+    uint8_t* dst = out + p0 * 3;
+    if (out4 && cnt == 4) {
+        unsigned* d4 = reinterpret_cast<unsigned*>(dst);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) d4[j] = o[4 * j] | o[4 * j + 1] << 8 | o[4 * j + 2] << 16 | (unsigned)o[4 * j + 3] << 24;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (j < 3 * cnt) dst[j] = o[j];
+    }
+}
+
+template <int SUB>
+int jpeg_launch(const uint8_t* x, long total, int n, int H, int W, const int* quality, uint8_t* scratch, long scratch_bytes,
+                uint8_t* out, hipStream_t stream) {
+    constexpr int MCU = 8 * SUB;
+    const int Hp = (H + MCU - 1) / MCU * MCU, Wp = (W + MCU - 1) / MCU * MCU;
+    if (scratch_bytes < n * jp_frame_bytes<SUB>(Hp, Wp)) return ISTVT_ERR_SHAPE;
+    const int tiles_y = Hp / MCU, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
+    const long tiles = (long)n * tiles_y * tiles_x;
+    const long npix = (long)n * H * W;
+    const long groups = (npix + 1023) / 1024;
+    if (tiles > 0x7fffffffL || groups > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    hipLaunchKernelGGL(jpeg_planes_kernel<SUB>, dim3((unsigned)tiles), dim3(256), 0, stream, x, total, quality, scratch, H, W,
+                       Hp, Wp, tiles_y, tiles_x);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_rgb_kernel<SUB>, dim3((unsigned)groups), dim3(256), 0, stream, x, quality, scratch, out, npix, H, W,
+                       Hp, Wp, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
+}  // namespace
+
+// frames uint8 [n][H][W][3] (total bytes readable at frames; no alignment needed), quality int32 [n] on the device (1..100
+// compress, larger counts as 100, <= 0 copies the frame), subsampling 2 (4:2:0) or 0 (4:4:4) as JPEG libraries number them
+// -> out uint8 [n][H][W][3], which must not overlap frames.  scratch: the planes, 8-byte aligned, n * Hp * Wp * 3 / 2 bytes
+// at 4:2:0 and n * Hp * Wp * 3 at 4:4:4 with Hp, Wp = H, W rounded up to multiples of 16 / 8.
+extern "C" int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W, const int* quality,
+                                       int subsampling, void* scratch, long scratch_bytes, void* out, hipStream_t stream) {
+    if (n <= 0 || !frames || !quality || !scratch || !out) return ISTVT_ERR_SHAPE;
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return ISTVT_ERR_SHAPE;
+    if (subsampling != 0 && subsampling != 2) return ISTVT_ERR_SHAPE;
+    const long bytes = (long)n * H * W * 3;
+    if (total < bytes || (reinterpret_cast<uintptr_t>(scratch) & 7)) return ISTVT_ERR_SHAPE;
+    const uint8_t* a = (const uint8_t*)frames;
+    const uint8_t* o = (const uint8_t*)out;
+    if (o < a + bytes && a < o + bytes) return ISTVT_ERR_SHAPE;              // in place: the upsample reads its neighbours
+    if (subsampling == 2) return jpeg_launch<2>(a, total, n, H, W, quality, (uint8_t*)scratch, scratch_bytes, (uint8_t*)out, stream);
+    return jpeg_launch<1>(a, total, n, H, W, quality, (uint8_t*)scratch, scratch_bytes, (uint8_t*)out, stream);
+}

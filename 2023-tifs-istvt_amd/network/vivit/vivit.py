@@ -242,7 +242,9 @@ class XceptionVidTr(nn.Module):
     def score_video(self, frames, boxes=None, **kw):
         """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S), or whole uint8
         frames (N, Hs, Ws, 3) with one face box (y0, x0, h, w) each in `boxes`, int32 (N, 4):
-        istvt_amd.video.VideoScorer(self, **kw).score(frames, boxes)"""
+        istvt_amd.video.VideoScorer(self, **kw).score(frames, boxes).  jpeg_quality=q (1..100) among the keywords scores the
+        crops as a JPEG codec would hand them back at that quality (ops.jpeg_roundtrip_u8); score_videos and explain_video
+        take it too."""
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score(frames, boxes=boxes)
 

@@ -1029,6 +1029,64 @@ def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] 
     return out
 
 
+def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
+                      checked: bool = False) -> Tensor:
+    """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for
+    clips, [B] shared by the T frames of a clip (or an int for all) -> uint8 of the same shape: what a baseline JPEG encoder
+    and decoder hand back at that quality ('420' or '444' chroma), the bits of clips.jpeg_roundtrip_host.  Entries 1..100
+    compress, an entry <= 0 copies its frame.  A host table is validated (clips.check_qualities) before any launch and
+    uploaded without blocking; checked=True takes a per-frame device table the caller has validated already and reads nothing
+    back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.  `out` (uint8, contiguous, of the input's shape) is written when given; it may not share memory
+    with the input, whose neighbouring blocks the chroma upsample reads."""
+    from . import clips
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('jpeg_roundtrip_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
+        raise RuntimeError('jpeg_roundtrip_u8 expects channels-last (n, H, W, 3) or (B, T, H, W, 3) uint8 input, got %s'
+                           % (tuple(frames.shape),))
+    if frames.numel() == 0:
+        raise RuntimeError('jpeg_roundtrip_u8: empty input %s' % (tuple(frames.shape),))
+    if not frames.is_contiguous():
+        raise RuntimeError('jpeg_roundtrip_u8: frames must be contiguous, got strides %s for %s'
+                           % (tuple(frames.stride()), tuple(frames.shape)))
+    sub = clips._jpeg_sub(subsampling)
+    H, W = frames.shape[-3], frames.shape[-2]
+    if H > 16384 or W > 16384:
+        raise ValueError('jpeg_roundtrip_u8: frames of at most 16384 x 16384, got %d x %d' % (H, W))
+    src = frames.view((-1, H, W, 3))
+    n = src.shape[0]
+    if checked:
+        if (not torch.is_tensor(quality) or quality.dtype != torch.int32 or tuple(quality.shape) != (n,)
+                or quality.device != src.device):
+            raise RuntimeError('jpeg_roundtrip_u8: a checked quality table is int32 (%d,) on %s' % (n, src.device))
+        qdev = _c(quality)
+    else:
+        if torch.is_tensor(quality) and quality.is_cuda:
+            raise RuntimeError('jpeg_roundtrip_u8: a device quality table is taken with checked=True only (int32, one entry per '
+                               'frame, validated by the caller); hand over the host table otherwise')
+        q = clips.check_qualities(quality, frames.shape[0])
+        if frames.dim() == 5:
+            q = q.repeat_interleave(frames.shape[1])
+        qdev = q.contiguous().to(src.device, non_blocking=True)
+    if out is None:
+        out = torch.empty_like(frames)
+    elif (out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape) or out.device != src.device
+          or not out.is_contiguous()):
+        raise RuntimeError('jpeg_roundtrip_u8: out must be contiguous uint8 %s on %s' % (tuple(frames.shape), src.device))
+    nbytes = src.numel()
+    if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
+        raise RuntimeError('jpeg_roundtrip_u8: out may not share memory with the input (the round trip is not done in place)')
+    mcu = 8 * sub
+    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
+    planes = torch.empty((n * Hp * Wp * 3 // (2 if sub == 2 else 1),), dtype=torch.uint8, device=src.device)
+    with prof('jpeg_roundtrip_u8', 2 * nbytes + 2 * planes.numel()):
+        _lib.check(_lib.lib().istvt_jpeg_roundtrip_u8(src.data_ptr(), nbytes, n, H, W, qdev.data_ptr(), 2 if sub == 2 else 0,
+                                                      planes.data_ptr(), planes.numel(), out.data_ptr(), _stream()),
+                   'istvt_jpeg_roundtrip_u8')
+    return out
+
+
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,
                need_dfeats: bool) -> Optional[Tensor]:
     dx, lddx = rows(_req(dx))

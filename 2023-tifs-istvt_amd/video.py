@@ -416,11 +416,15 @@ class VideoScorer:
     mean, std     per-channel normalisation of uint8 frames, (u / 255 - mean) / std; float input is taken as normalised.
     cover_tail    score() / flush() add the window at N - T when the strided windows leave the last frames uncovered.
     side          the side of the crops made of whole frames when a call passes `boxes` (default: the model's crop_side).
+    jpeg_quality  None, or an int in 1..100: every uint8 stem batch goes through ops.jpeg_roundtrip_u8 at that quality (4:2:0)
+                  just before the stem, after the crop when a call passes `boxes` -- the S x S crops the stem reads are
+                  recompressed, not the whole frames.  score(), push(), score_videos() and explain() then give the bits they
+                  give on ops.jpeg_roundtrip_u8(crops, jpeg_quality); float frames raise TypeError.
     """
 
     def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
                  capacity: Optional[int] = None, mean: Sequence[float] = DEFAULT_MEAN, std: Sequence[float] = DEFAULT_STD,
-                 cover_tail: bool = True, side: Optional[int] = None):
+                 cover_tail: bool = True, side: Optional[int] = None, jpeg_quality: Optional[int] = None):
         vit = getattr(model, 'vit', None)
         if vit is None or not hasattr(model, 'xcep') or not hasattr(vit, 'forward_tokens'):
             raise TypeError('VideoScorer: expected an XceptionVidTr, got %s' % type(model).__name__)
@@ -439,7 +443,12 @@ class VideoScorer:
         if side is not None and int(side) < 3:
             raise ValueError('VideoScorer: side must be at least 3, got %r' % (side,))
         self.side = None if side is None else int(side)
+        if jpeg_quality is not None and (isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int)
+                                         or not 1 <= jpeg_quality <= 100):
+            raise ValueError('VideoScorer: jpeg_quality must be None or an int in [1, 100], got %r' % (jpeg_quality,))
+        self.jpeg_quality = jpeg_quality
         self._norm = None                  # (device, mean tensor, std tensor)
+        self._jpeg = None                  # the device quality table of a stem batch: jpeg_quality, frame_batch times
         self.reset()
 
     # ---------------------------------------------------------------------------------------- streaming state
@@ -466,11 +475,21 @@ class VideoScorer:
         dev = self._device()
         return b.contiguous().to(dev, non_blocking=True), side
 
+    def _check_kind(self, kind: str) -> str:
+        if self.jpeg_quality is not None and kind == 'f32':
+            raise TypeError('VideoScorer: jpeg_quality recompresses decoded uint8 frames; normalised float frames cannot take it')
+        return kind
+
     def _stem(self, x: Tensor, kind: str, dev, boxes: Optional[Tensor] = None, side: Optional[int] = None) -> Tensor:
         if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
             x = x.contiguous().pin_memory().to(dev, non_blocking=True)
         if boxes is not None:              # whole frames: this batch's crops, made where the frames are
             x = ops.crop_resize_u8(x, boxes, side, checked=True)
+        if self.jpeg_quality is not None:  # the bytes the stem reads, as a JPEG codec would hand them back
+            n = int(x.shape[0])
+            if self._jpeg is None or self._jpeg.device != dev or self._jpeg.shape[0] < n:
+                self._jpeg = torch.full((max(n, self.frame_batch),), self.jpeg_quality, dtype=torch.int32, device=dev)
+            x = ops.jpeg_roundtrip_u8(x.contiguous(), self._jpeg[:n], checked=True)
         xcep = self.model.xcep.model
         if kind == 'u8':
             if self._norm is None or self._norm[0] != dev:
@@ -526,7 +545,7 @@ class VideoScorer:
         boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); a stream keeps one mode."""
         bdev = side = None
         if boxes is None:
-            kind = check_frames(frames)
+            kind = self._check_kind(check_frames(frames))
         else:
             side = self._side()
             bhost = check_boxed_frames(frames, boxes, side)
@@ -559,7 +578,7 @@ class VideoScorer:
         """every window of one video on a ring of its own -> (logits, list of starts, device)"""
         bdev = side = None
         if boxes is None:
-            kind = check_frames(frames)
+            kind = self._check_kind(check_frames(frames))
         else:
             side = self._side()
             bhost = check_boxed_frames(frames, boxes, side)
@@ -601,7 +620,7 @@ class VideoScorer:
         if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
             raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
         if boxes is None:
-            kinds = [check_frames(v) for v in videos]
+            kinds = [self._check_kind(check_frames(v)) for v in videos]
             if len(set(kinds)) != 1:
                 raise ValueError('the videos of one call are all uint8 or all float, not both (video %d differs from video 0)'
                                  % next(i for i, k in enumerate(kinds) if k != kinds[0]))

@@ -307,6 +307,17 @@ int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* 
  * kept in fp32, then vertical; byte = clamp(floor(v + 0.5), 0, 255).  h = w = S reproduces the slice.  S <= 480 (LDS). */
 int istvt_crop_resize_u8(const void* frames, long total, int Hs, int Ws, const int* boxes, void* out, int n, int S,
                          istvt_stream_t stream);
+/* JPEG round trip: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
+ * alignment needed), quality int32 [n] on the device -> out uint8 [n][H][W][3] (no overlap with frames: ISTVT_ERR_SHAPE), the
+ * RGB a baseline JPEG encoder and decoder hand back: libjpeg's 16-bit fixed-point colour transforms, edge replication to whole
+ * MCUs, 2x2 box chroma downsample (subsampling = 2, 4:2:0) or none (0, 4:4:4), the 13-bit "slow integer" DCT, Annex K tables
+ * scaled by the frame's quality (s = 5000 / q below 50, else 200 - 2 q; entry (base * s + 50) / 100 in 1..255), quantisation
+ * half away from zero, the inverse DCT, the "fancy" triangle chroma upsample, clamp.  Quality 1..100 compresses (larger counts
+ * as 100), <= 0 copies the frame.  int32 arithmetic only: the bits of clips.jpeg_roundtrip_host.  scratch: 8-byte aligned
+ * planes, n * Hp * Wp * 3 / 2 bytes at 4:2:0 (Hp, Wp = H, W rounded up to multiples of 16) and n * Hp * Wp * 3 at 4:4:4
+ * (multiples of 8).  Two launches, no synchronisation, no atomics.  H, W <= 16384. */
+int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W, const int* quality, int subsampling,
+                            void* scratch, long scratch_bytes, void* out, istvt_stream_t stream);
 int istvt_conv2_fwd(const void* u1, const float* bnp, const void* w, void* u2, int frames, int H, int W,
                     istvt_stream_t stream);
 int istvt_conv2_dgrad(const void* du2, const void* w, const void* u1, const float* bnp, void* dz1, int frames, int H,
