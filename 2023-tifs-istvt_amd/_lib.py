@@ -57,6 +57,8 @@ SIGNATURES = {
     'istvt_conv1_wgrad_u8': [P, P, L, I, I, P, P, P, P, P, I, I, I, P],
     'istvt_im2col_conv1_u8': [P, L, I, I, P, P, P, P, I, I, I, P],
     'istvt_crop_resize_u8': [P, L, I, I, P, P, I, I, P],
+    'istvt_crop_resize_nv12': [P, L, I, I, L, L, P, P, P, I, I, P],
+    'istvt_nv12_to_rgb_u8': [P, L, I, I, L, L, P, P, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],

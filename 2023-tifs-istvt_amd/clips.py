@@ -16,7 +16,13 @@ JPEG recompression (DESIGN.md "JPEG round trip") is the third part: ``jpeg_quant
 ``jpeg_roundtrip_host`` (the definition of ops.jpeg_roundtrip_u8, integers only) and ``random_qualities``.  Training needs no
 new model code: a loader yields ``(u8, boxes, qualities, flips)`` and the step is
 ``model(ops.jpeg_roundtrip_u8(ops.crop_resize_u8(u8, boxes, S), q), view=flips)``.
+
+NV12 frames (DESIGN.md "NV12 frames") are the fourth: ``nv12_coefficients``, ``check_nv12``, ``nv12_to_rgb_host`` (the
+definition of ops.nv12_to_rgb_u8, integers only), ``crop_resize_nv12_host`` (of ops.crop_resize_nv12) and ``rgb_to_nv12_host``,
+a plain float encoder that makes NV12 fixtures.  ``ops.crop_resize_nv12(clips_nv12, boxes, S)`` stands where
+``ops.crop_resize_u8(u8, boxes, S)`` stands above.
 """
+from fractions import Fraction
 from typing import Optional
 
 import torch
@@ -239,6 +245,24 @@ JPEG_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 2
 JPEG_SUBSAMPLINGS = {'420': 2, '444': 1}   # chroma step per axis; the MCU is 8 * step pixels square
 
 
+JFIF_COEFFICIENTS = (65536, 0, 91881, 22554, 46802, 116130)     # libjpeg's decoder: ky, yoff, krv, kgu, kgv, kbu
+
+
+def _ycc_to_rgb(Y: Tensor, Cb: Tensor, Cr: Tensor, coef) -> Tensor:
+    """The colour-out expression the JPEG decoder and the NV12 reader share, int32 only: Y and the centred Cb' = Cb - 128,
+    Cr' = Cr - 128 as int32 tensors of one shape, coef = (ky, yoff, krv, kgu, kgv, kbu) -> uint8 (..., 3):
+
+        yy = ky (Y - yoff);  R = clamp((yy + krv Cr' + 32768) >> 16);  G = clamp((yy - kgu Cb' - kgv Cr' + 32768) >> 16);
+        B = clamp((yy + kbu Cb' + 32768) >> 16)
+
+    with arithmetic shifts and the clamp to 0..255.  With ky = 65536 and yoff = 0, yy is a multiple of 65536 and the three
+    lines are Y + ((k C' + 32768) >> 16), libjpeg's own."""
+    ky, yoff, krv, kgu, kgv, kbu = coef
+    yy = ky * (Y - yoff) + 32768
+    return torch.stack([(yy + krv * Cr) >> 16, (yy - kgu * Cb - kgv * Cr) >> 16, (yy + kbu * Cb) >> 16],
+                       dim=-1).clamp_(0, 255).to(torch.uint8)
+
+
 def jpeg_quant_tables(q: int) -> Tensor:
     """The two quantisation tables of quality q in 1..100 as libjpeg scales Annex K: s = 5000 // q for q < 50, else
     200 - 2 q; entry = (base * s + 50) // 100 clamped to 1..255.  int32 (2, 8, 8): luminance, chrominance; row = vertical
@@ -399,9 +423,7 @@ def jpeg_roundtrip_host(u8: Tensor, quality, subsampling: str = '420') -> Tensor
         Cb, Cr = _jpeg_upsample(Cb[:, :Hc, :Wc], H, W), _jpeg_upsample(Cr[:, :Hc, :Wc], H, W)
     else:
         Cb, Cr = Cb[:, :H, :W], Cr[:, :H, :W]
-    Cb, Cr = Cb - 128, Cr - 128
-    out = torch.stack([Y + ((91881 * Cr + 32768) >> 16), Y + ((-22554 * Cb - 46802 * Cr + 32768) >> 16),
-                       Y + ((116130 * Cb + 32768) >> 16)], dim=3).clamp_(0, 255).to(torch.uint8)
+    out = _ycc_to_rgb(Y, Cb - 128, Cr - 128, JFIF_COEFFICIENTS)
     keep = q <= 0
     out[keep] = src[keep]
     return out.reshape(u8.shape).to(u8.device)
@@ -420,3 +442,102 @@ def random_qualities(n: int, p: float = 0.5, lo: int = 30, hi: int = 95, generat
     on = torch.rand((n,), generator=generator) < p
     q = torch.randint(lo, hi + 1, (n,), generator=generator)
     return torch.where(on, q, torch.zeros_like(q)).to(torch.int32).contiguous()
+
+
+# ------------------------------------------------------------------------------------------ NV12 frames
+# DESIGN.md "NV12 frames": what a video decoder hands back.  A frame is Hs rows of Y followed by Hs / 2 rows of Ws / 2
+# interleaved (Cb, Cr) pairs: uint8 (N, 3 * Hs / 2, Ws) or, for clips, (B, T, 3 * Hs / 2, Ws), Hs and Ws even.  The last
+# dimension is contiguous; the row stride (a decoder's pitch >= Ws) and the frame stride are whatever the tensor's strides
+# say.  Pixel (y, x) takes the chroma pair (y >> 1, x >> 1): nearest chroma, no interpolation.
+NV12_MATRICES = {'bt601': (Fraction(299, 1000), Fraction(114, 1000)), 'bt709': (Fraction(2126, 10000), Fraction(722, 10000))}
+YUV_MATRICES = ('bt601', 'bt709', 'jfif')
+
+
+def nv12_coefficients(matrix: str):
+    """(ky, yoff, krv, kgu, kgv, kbu) of _ycc_to_rgb for `matrix`.  'bt601' and 'bt709' are limited range (Y 16..235, chroma
+    16..240): with Kg = 1 - Kr - Kb the exact rationals are ky = 255 / 219, krv = 255 / 224 * 2 (1 - Kr), kgu = 255 / 224 *
+    2 Kb (1 - Kb) / Kg, kgv = 255 / 224 * 2 Kr (1 - Kr) / Kg, kbu = 255 / 224 * 2 (1 - Kb); each becomes round(65536 c).
+    'jfif' is full range with the JPEG decoder's own integers."""
+    if matrix == 'jfif':
+        return JFIF_COEFFICIENTS
+    if matrix not in NV12_MATRICES:
+        raise ValueError("matrix must be 'bt601', 'bt709' or 'jfif', got %r" % (matrix,))
+    kr, kb = NV12_MATRICES[matrix]
+    kg = 1 - kr - kb
+    c = Fraction(255, 224)
+    exact = (Fraction(255, 219), c * 2 * (1 - kr), c * 2 * kb * (1 - kb) / kg, c * 2 * kr * (1 - kr) / kg, c * 2 * (1 - kb))
+    ky, krv, kgu, kgv, kbu = ((v * 65536 + Fraction(1, 2)).__floor__() for v in exact)
+    return (ky, 16, krv, kgu, kgv, kbu)
+
+
+def check_nv12(frames):
+    """(Hs, Ws) of an NV12 batch uint8 (N, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws).  TypeError for anything but a uint8
+    tensor; ValueError for a wrong rank, a row count that is no multiple of 3, odd Hs or Ws, or a last dimension that is
+    not contiguous."""
+    if not torch.is_tensor(frames):
+        raise TypeError('NV12 frames must be a uint8 tensor, got %s' % type(frames).__name__)
+    if frames.dtype != torch.uint8:
+        raise TypeError('NV12 frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() not in (3, 4):
+        raise ValueError('NV12 frames must be (N, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws), got %s' % (tuple(frames.shape),))
+    rows, Ws = int(frames.shape[-2]), int(frames.shape[-1])
+    if rows < 3 or rows % 3 != 0:
+        raise ValueError('NV12 frames have 3 * Hs / 2 rows (Hs of Y, Hs / 2 of CbCr), got %d' % rows)
+    Hs = rows // 3 * 2
+    if Hs % 2 != 0 or Ws < 2 or Ws % 2 != 0:
+        raise ValueError('NV12 frames need even sizes, got Hs=%d Ws=%d' % (Hs, Ws))
+    if frames.stride(-1) != 1:
+        raise ValueError('NV12 frames need a contiguous last dimension (a row of bytes), got strides %s' % (tuple(frames.stride()),))
+    return Hs, Ws
+
+
+def nv12_to_rgb_host(frames: Tensor, matrix: str = 'bt709') -> Tensor:
+    """The definition on the host: NV12 uint8 (N, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws) -> packed RGB uint8 (N, Hs, Ws, 3)
+    / (B, T, Hs, Ws, 3) through _ycc_to_rgb with nv12_coefficients(matrix); int32 arithmetic only.  Input bytes outside the
+    nominal range are legal and clamp."""
+    Hs, Ws = check_nv12(frames)
+    coef = nv12_coefficients(matrix)
+    src = frames.cpu()
+    Y = src[..., :Hs, :].to(torch.int32)
+    cbcr = src[..., Hs:, :].to(torch.int32)
+    yi, xi = torch.arange(Hs) >> 1, torch.arange(Ws) >> 1
+    Cb = cbcr[..., 0::2][..., yi, :][..., xi]
+    Cr = cbcr[..., 1::2][..., yi, :][..., xi]
+    return _ycc_to_rgb(Y, Cb - 128, Cr - 128, coef).contiguous().to(frames.device)
+
+
+def crop_resize_nv12_host(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709') -> Tensor:
+    """The definition of ops.crop_resize_nv12: crop_resize_host(nv12_to_rgb_host(frames, matrix), boxes, S)"""
+    return crop_resize_host(nv12_to_rgb_host(frames, matrix), boxes, S)
+
+
+def rgb_to_nv12_host(u8: Tensor, matrix: str = 'bt709') -> Tensor:
+    """A plain float64 encoder, to make NV12 from RGB fixtures: uint8 (..., Hs, Ws, 3) with Hs, Ws even -> NV12 uint8
+    (..., 3 * Hs / 2, Ws), contiguous.  Y' = Kr R + Kg G + Kb B, Pb = (B - Y') / (2 (1 - Kb)), Pr = (R - Y') / (2 (1 - Kr));
+    limited range: Y = 16 + 219 Y' / 255, C = 128 + 224 P / 255; 'jfif': Y = Y', C = 128 + P (BT.601 weights); chroma is the
+    mean of its 2 x 2 pixels; round half up, clamp to 0..255.  Runs where u8 lives.  It promises nothing bit-wise: nv12_to_rgb_host of its result
+    is close to the input where the 2 x 2 blocks are flat, no more."""
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() < 3 or u8.shape[-1] != 3:
+        raise ValueError('rgb_to_nv12_host expects uint8 (..., Hs, Ws, 3)')
+    Hs, Ws = int(u8.shape[-3]), int(u8.shape[-2])
+    if Hs < 2 or Ws < 2 or Hs % 2 or Ws % 2:
+        raise ValueError('NV12 frames need even sizes, got Hs=%d Ws=%d' % (Hs, Ws))
+    if matrix not in YUV_MATRICES:
+        raise ValueError("matrix must be 'bt601', 'bt709' or 'jfif', got %r" % (matrix,))
+    kr, kb = (float(v) for v in NV12_MATRICES['bt601' if matrix == 'jfif' else matrix])
+    ys, cs = (1.0, 1.0) if matrix == 'jfif' else (219.0 / 255.0, 224.0 / 255.0)
+    R, G, B = u8.to(torch.float64).unbind(-1)
+    yp = kr * R + (1.0 - kr - kb) * G + kb * B
+    lead = tuple(u8.shape[:-3])
+
+    def pool(p):
+        return p.reshape(lead + (Hs // 2, 2, Ws // 2, 2)).mean(dim=(-3, -1))
+
+    Y = (0.0 if matrix == 'jfif' else 16.0) + ys * yp
+    Cb = 128.0 + cs * pool((B - yp) / (2.0 * (1.0 - kb)))
+    Cr = 128.0 + cs * pool((R - yp) / (2.0 * (1.0 - kr)))
+    out = torch.empty(lead + (Hs + Hs // 2, Ws), dtype=torch.uint8, device=u8.device)
+    out[..., :Hs, :] = torch.floor(Y + 0.5).clamp_(0, 255).to(torch.uint8)
+    out[..., Hs:, 0::2] = torch.floor(Cb + 0.5).clamp_(0, 255).to(torch.uint8)
+    out[..., Hs:, 1::2] = torch.floor(Cr + 0.5).clamp_(0, 255).to(torch.uint8)
+    return out

@@ -58,11 +58,102 @@ __device__ __forceinline__ void resize_taps(int i, int n_in, int n_out, int* lo_
     *cnt_out = hi - lo;
 }
 
+// ---- where the bytes of a box come from ----------------------------------------------------------------------------------
+// The kernel below is written once and instantiated per source.  A source says how many rows of a box one chunk stages
+// (chunk_rows), fills the stage with the packed RGB bytes of `ch` box rows from s0 on (fill: row rr at stage + rr * pitch +
+// lead(rr), lead(rr) = u8_row_lead(fill's result, rr, lead_stride())), and nothing else: the tap tables, the passes, the
+// two filters and the output path do not know which source they read.
+
+// Packed RGB frames, uint8 [n][Hs][Ws][3]: a box row is one contiguous piece of the source and is staged as it lies
+struct RgbSource {
+    const uint8_t* x;
+    long total;
+    int Hs, Ws;
+    __device__ __forceinline__ int lead_stride() const { return Ws * 3; }
+    __device__ __forceinline__ int chunk_rows(int stage_bytes, int pitch, int) const { return max(stage_bytes / pitch, 1); }
+    __device__ __forceinline__ int fill(long f, const CropBox& b, int s0, int ch, unsigned char* stage, int pitch,
+                                        unsigned char*, int tid) const {
+        const long g0 = ((f * Hs + b.y0 + s0) * (long)Ws + b.x0) * 3;
+        return u8_stage_rows(x, total, g0, Ws * 3, ch, b.w, stage, pitch, tid, 256);
+    }
+};
+
+// NV12 (DESIGN.md "NV12 frames"): per frame Hs rows of Y, then Hs / 2 rows of Ws / 2 interleaved (Cb, Cr) pairs, `pitch`
+// bytes from row to row and `fstride` from frame to frame; pixel (y, x) takes the pair (y >> 1, x >> 1).  One integer
+// expression for every matrix, int32 only (|k| < 2^20 and 8-bit samples: no sum leaves 2^30):
+//   yy = ky (Y - yoff);  R = clamp((yy + krv Cr' + 32768) >> 16);  G = clamp((yy - kgu Cb' - kgv Cr' + 32768) >> 16);
+//   B = clamp((yy + kbu Cb' + 32768) >> 16);  Cb' = Cb - 128, Cr' = Cr - 128; arithmetic shifts, clamp to 0..255
+struct Nv12Matrix {
+    int ky, yoff, krv, kgu, kgv, kbu;
+};
+
+__device__ __forceinline__ int nv12_byte(int v) { return min(max(v >> 16, 0), 255); }
+
+// channel c of a pixel
+__device__ __forceinline__ int nv12_channel(const Nv12Matrix& m, int c, int y, int cb, int cr) {
+    const int yy = m.ky * (y - m.yoff) + 32768;
+    cb -= 128, cr -= 128;
+    return nv12_byte(c == 0 ? yy + m.krv * cr : c == 1 ? yy - m.kgu * cb - m.kgv * cr : yy + m.kbu * cb);
+}
+
+// pitch of a staged raw row piece of a box of width w: lead (<= 15) + at most w + 2 bytes (the chroma pairs of w columns
+// from an odd origin), in whole 16-byte pieces
+__host__ __device__ __forceinline__ int nv12_raw_pitch(int w) { return ((w + 32) >> 4) << 4; }
+
+struct Nv12Source {
+    const uint8_t* x;
+    long total, fstride;
+    int Hs, Ws, pitch;
+    Nv12Matrix m;
+    int raw_bytes;
+    __device__ __forceinline__ int lead_stride() const { return 0; }          // converted rows start at their pitch
+    // ch box rows need ch raw Y pieces and at most ch / 2 + 1 chroma pieces: 3 ch / 2 + 1 <= the raw area's rows
+    __device__ __forceinline__ int chunk_rows(int stage_bytes, int pitch_, int w) const {
+        const int nr = raw_bytes / nv12_raw_pitch(w);
+        return max(min(stage_bytes / pitch_, (nr - 1) * 2 / 3), 1);
+    }
+    __device__ __forceinline__ int fill(long f, const CropBox& b, int s0, int ch, unsigned char* stage, int spitch,
+                                        unsigned char* raw, int tid) const {
+        const int rp = nv12_raw_pitch(b.w);
+        const int y0 = b.y0 + s0;                                  // first frame row of the chunk
+        const int c0 = y0 >> 1, nc = ((y0 + ch - 1) >> 1) - c0 + 1;  // its chroma rows: two box rows share one
+        const int cx0 = b.x0 >> 1, clen = 2 * (((b.x0 + b.w - 1) >> 1) - cx0 + 1);
+        unsigned char* const rawc = raw + ch * rp;
+        const int ly = u8_stage_byte_rows(x, total, f * fstride + (long)y0 * pitch + b.x0, pitch, ch, b.w, raw, rp, tid, 256);
+        const int lc = u8_stage_byte_rows(x, total, f * fstride + (long)(Hs + c0) * pitch + 2 * cx0, pitch, nc, clen, rawc, rp,
+                                          tid, 256);
+        __syncthreads();
+        const int q4 = (b.w + 3) >> 2;                             // four pixels = three dwords of the stage per thread
+        for (int e = tid; e < ch * q4; e += 256) {
+            const int rr = e / q4, q = e - rr * q4;
+            const unsigned char* yrow = raw + rr * rp + u8_row_lead(ly, rr, pitch);
+            const int cr_ = ((y0 + rr) >> 1) - c0;
+            const unsigned char* crow = rawc + cr_ * rp + u8_row_lead(lc, cr_, pitch);
+            unsigned o[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int px = 4 * q + j;
+                if (px >= b.w) continue;
+                const int p = 2 * (((b.x0 + px) >> 1) - cx0);
+                const int yv = yrow[px], cb = crow[p], cr = crow[p + 1];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[(3 * j + c) >> 2] |= (unsigned)nv12_channel(m, c, yv, cb, cr) << (8 * ((3 * j + c) & 3));
+            }
+            unsigned* dst = reinterpret_cast<unsigned*>(stage + rr * spitch + 12 * q);
+            dst[0] = o[0], dst[1] = o[1], dst[2] = o[2];
+        }
+        return 0;
+    }
+};
+
 // LDS: col_lo[S] col_n[S] row_lo[R] row_n[R] (int) | col_w[S][17] row_w[R][17] (float) | tile[TR][S * 3] (float) |
-// stage[stage_bytes]: the staged source rows of a chunk, then the output bytes of a pass
-__global__ __launch_bounds__(256) void crop_resize_u8_kernel(const uint8_t* __restrict__ x, const int* __restrict__ boxes,
-                                                             uint8_t* __restrict__ out, long total, int Hs, int Ws, int S,
-                                                             int R, int ngroups, int TR, int stage_bytes) {
+// stage[stage_bytes]: the staged source rows of a chunk, then the output bytes of a pass | raw[src.raw_bytes] (NV12 only):
+// the Y and chroma pieces of a chunk before their conversion into the stage
+template <typename Src>
+__global__ __launch_bounds__(256) void crop_resize_u8_kernel(const Src src, const int* __restrict__ boxes,
+                                                             uint8_t* __restrict__ out, int S, int R, int ngroups, int TR,
+                                                             int stage_bytes) {
+    const int Hs = src.Hs, Ws = src.Ws;
     extern __shared__ __align__(16) unsigned char smem[];
     const int S3 = S * 3;
     int* col_lo = reinterpret_cast<int*>(smem);
@@ -88,8 +179,8 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const uint8_t* __re
     }
     __syncthreads();
 
-    const int pitch = u8_row_pitch(b.w), rstride = Ws * 3;
-    const int CH = max(stage_bytes / pitch, 1);                  // the host sizes the stage for one widest row at least
+    const int pitch = u8_row_pitch(b.w), rstride = src.lead_stride();
+    const int CH = src.chunk_rows(stage_bytes, pitch, b.w);      // the host sizes the stage for one widest row at least
     uint8_t* const obase = out + (f * S + yb) * (long)S3;         // first output byte of this work item
 
     for (int y = 0; y < rows;) {
@@ -101,8 +192,7 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const uint8_t* __re
 
         for (int s0 = s_lo; s0 < s_hi; s0 += CH) {
             const int ch = min(CH, s_hi - s0);
-            const long g0 = ((f * Hs + b.y0 + s0) * (long)Ws + b.x0) * 3;
-            const int lead0 = u8_stage_rows(x, total, g0, rstride, ch, b.w, stage, pitch, tid, 256);
+            const int lead0 = src.fill(f, b, s0, ch, stage, pitch, stage + stage_bytes, tid);
             __syncthreads();
             for (int e = tid; e < ch * S3; e += 256) {            // horizontal: (source row, output column, channel)
                 const int rr = e / S3, xc = e - rr * S3;
@@ -153,24 +243,77 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const uint8_t* __re
     }
 }
 
-}  // namespace
+// Whole NV12 frames -> packed RGB.  Work item = (frame, row pair, tile of NV_TW columns): the two Y pieces and the chroma
+// piece they share are staged with 16-byte loads, then every thread makes one 16-byte piece of one of the two output rows
+// (a contiguous range of `out` each) and stores it whole where the range allows, byte by byte at its ends.
+constexpr int NV_TW = 640;                                       // 2 rows x 1920 output bytes = 240 pieces: one per thread
+constexpr int NV_RP = ((NV_TW + 32) >> 4) << 4;                  // nv12_raw_pitch(NV_TW)
 
-// frames uint8 [n][Hs][Ws][3] (total bytes readable at frames; no alignment needed), boxes int32 [n][4] = (y0, x0, h, w)
-// on the device -> out uint8 [n][S][S][3].  LDS: the tables (76 bytes per column and per row), 17 tile rows at least, and a
-// stage of two widest source rows or one pass of output bytes; spare room up to 64 KiB becomes more tile rows (fewer
-// passes and fewer source rows filtered twice at small scales), and only a side whose 17 rows do not fit gets more, up to
-// the CU's 160 KiB (S = 224 from wide frames: 72 KiB, two workgroups per CU; any S <= 480 fits).
-extern "C" int istvt_crop_resize_u8(const void* frames, long total, int Hs, int Ws, const int* boxes, void* out, int n,
-                                    int S, hipStream_t stream) {
-    if (n <= 0 || S < 1 || S > 4096 || !frames || !boxes || !out) return ISTVT_ERR_SHAPE;
-    if (Hs < 1 || Ws < 1 || Hs > 16384 || Ws > 16384) return ISTVT_ERR_SHAPE;
-    if (total < (long)n * Hs * Ws * 3) return ISTVT_ERR_SHAPE;
+__global__ __launch_bounds__(256) void nv12_to_rgb_u8_kernel(const Nv12Source src, uint8_t* __restrict__ out, int tiles) {
+    __shared__ __align__(16) unsigned char raw[3 * NV_RP];
+    const int tid = threadIdx.x;
+    const int tile = (int)(blockIdx.x % tiles);
+    const long t = blockIdx.x / tiles;
+    const int pr = (int)(t % (src.Hs >> 1));
+    const long f = t / (src.Hs >> 1);
+    const int xa = tile * NV_TW, tw = min(NV_TW, src.Ws - xa);   // both even
+    const int ly = u8_stage_byte_rows(src.x, src.total, f * src.fstride + (long)(2 * pr) * src.pitch + xa, src.pitch, 2, tw, raw,
+                                      NV_RP, tid, 256);
+    const int lc = u8_stage_byte_rows(src.x, src.total, f * src.fstride + (long)(src.Hs + pr) * src.pitch + xa, src.pitch, 1, tw,
+                                      raw + 2 * NV_RP, NV_RP, tid, 256);
+    __syncthreads();
+    const int rr = tid >> 7, ck = tid & 127;                     // a row has at most (15 + 1920 + 15) / 16 = 121 pieces
+    uint8_t* const o0 = out + ((f * src.Hs + 2 * pr + rr) * (long)src.Ws + xa) * 3;
+    const int lead = (int)(reinterpret_cast<uintptr_t>(o0) & 15);
+    const int len = tw * 3, a = 16 * ck;
+    if (a >= lead + len) return;
+    const unsigned char* yrow = raw + rr * NV_RP + u8_row_lead(ly, rr, src.pitch);
+    const unsigned char* crow = raw + 2 * NV_RP + lc;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int q = a + j - lead;
+        if (q < 0 || q >= len) continue;
+        const int px = q / 3, c = q - px * 3;
+        w[j >> 2] |= (unsigned)nv12_channel(src.m, c, yrow[px], crow[px & ~1], crow[(px & ~1) + 1]) << (8 * (j & 3));
+    }
+    if (a >= lead && a + 16 <= lead + len) {
+        *reinterpret_cast<uint4*>(o0 - lead + a) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (a + j >= lead && a + j < lead + len) o0[a + j - lead] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+    }
+}
+
+// What both NV12 entries check of their source: even sizes, a pitch and a frame stride that keep every row inside `total`
+static int nv12_source_of(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, int n, const int* coef,
+                          Nv12Source* src) {
+    if (n <= 0 || !frames || !coef) return ISTVT_ERR_SHAPE;
+    if (Hs < 2 || Ws < 2 || (Hs & 1) || (Ws & 1) || Hs > 16384 || Ws > 16384) return ISTVT_ERR_SHAPE;
+    if (pitch < 0 || pitch > (1L << 20) || fstride < 0) return ISTVT_ERR_SHAPE;
+    if (total < (long)(n - 1) * fstride + (long)(Hs + Hs / 2 - 1) * pitch + Ws) return ISTVT_ERR_SHAPE;
+    if (coef[1] < 0 || coef[1] > 255) return ISTVT_ERR_SHAPE;
+    for (int i = 0; i < 6; ++i)
+        if (coef[i] < 0 || coef[i] >= (1 << 20)) return ISTVT_ERR_SHAPE;      // int32 holds every sum
+    *src = Nv12Source{(const uint8_t*)frames, total, fstride, Hs, Ws, (int)pitch,
+                      Nv12Matrix{coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]}, 0};
+    return ISTVT_OK;
+}
+
+// The launch both crop entries share.  LDS: the tables (76 bytes per column and per row), 17 tile rows at least, a stage of
+// `srows` widest source rows or one pass of output bytes, and `raw_bytes` more for a source that converts into the stage;
+// spare room up to 64 KiB becomes more tile rows (fewer passes and fewer source rows filtered twice at small scales), and
+// only a side whose 17 rows do not fit gets more, up to the CU's 160 KiB.  -> ISTVT_ERR_SHAPE when that does not suffice.
+template <typename Src>
+static int crop_resize_launch(const Src& src, const int* boxes, void* out, int n, int S, int srows, int raw_bytes,
+                              hipStream_t stream) {
     const int R = S < CR_ROWS ? S : CR_ROWS;
     const int S3 = S * 3;
-    const int wmax = Ws < 8 * S ? Ws : 8 * S;
-    int stage_bytes = 2 * u8_row_pitch(wmax);
+    const int wmax = src.Ws < 8 * S ? src.Ws : 8 * S;
+    int stage_bytes = srows * u8_row_pitch(wmax);
     if (stage_bytes < ((R * S3 + 47) & ~15)) stage_bytes = (R * S3 + 47) & ~15;     // lead <= 15, whole dwords
-    const long fixed = (long)(S + R) * (8 + 4 * CR_TAPS) + 16 + stage_bytes;
+    const long fixed = (long)(S + R) * (8 + 4 * CR_TAPS) + 16 + stage_bytes + raw_bytes;
     const long tile_row = (long)S3 * 4;
     int TR = CR_TAPS;
     if (fixed + TR * tile_row < CR_LDS_TARGET) TR = (int)((CR_LDS_TARGET - fixed) / tile_row);
@@ -181,11 +324,59 @@ extern "C" int istvt_crop_resize_u8(const void* frames, long total, int Hs, int 
     const long nblocks = (long)n * ngroups;
     if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
     if (lds > 64 * 1024) {
-        static std::atomic<unsigned long long> lds_raised{0};
-        if (istvt_raise_lds_limit(lds_raised, reinterpret_cast<const void*>(crop_resize_u8_kernel), CR_LDS_MAX) != ISTVT_OK)
+        static std::atomic<unsigned long long> lds_raised{0};              // one per instantiation
+        if (istvt_raise_lds_limit(lds_raised, reinterpret_cast<const void*>(crop_resize_u8_kernel<Src>), CR_LDS_MAX) != ISTVT_OK)
             return ISTVT_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)nblocks), dim3(256), (size_t)lds, stream,
-                       (const uint8_t*)frames, boxes, (uint8_t*)out, total, Hs, Ws, S, R, ngroups, TR, stage_bytes);
+    hipLaunchKernelGGL(crop_resize_u8_kernel<Src>, dim3((unsigned)nblocks), dim3(256), (size_t)lds, stream, src, boxes,
+                       (uint8_t*)out, S, R, ngroups, TR, stage_bytes);
+    return istvt_check_launch();
+}
+
+}  // namespace
+
+// frames uint8 [n][Hs][Ws][3] (total bytes readable at frames; no alignment needed), boxes int32 [n][4] = (y0, x0, h, w)
+// on the device -> out uint8 [n][S][S][3].  LDS as crop_resize_launch says, with a stage of two widest source rows and no
+// raw area (S = 224 from wide frames: 72 KiB, two workgroups per CU; any S <= 480 fits).
+extern "C" int istvt_crop_resize_u8(const void* frames, long total, int Hs, int Ws, const int* boxes, void* out, int n,
+                                    int S, hipStream_t stream) {
+    if (n <= 0 || S < 1 || S > 4096 || !frames || !boxes || !out) return ISTVT_ERR_SHAPE;
+    if (Hs < 1 || Ws < 1 || Hs > 16384 || Ws > 16384) return ISTVT_ERR_SHAPE;
+    if (total < (long)n * Hs * Ws * 3) return ISTVT_ERR_SHAPE;
+    return crop_resize_launch(RgbSource{(const uint8_t*)frames, total, Hs, Ws}, boxes, out, n, S, 2, 0, stream);
+}
+
+// The same from NV12 frames (n frames of Hs + Hs / 2 rows of Ws bytes, `pitch` bytes from row to row, `fstride` from frame
+// to frame, `total` bytes readable at frames; Hs, Ws even, no alignment needed; coef = ky, yoff, krv, kgu, kgv, kbu on the
+// host): the bits of istvt_crop_resize_u8 on istvt_nv12_to_rgb_u8's frames, which are never made.  LDS: the RGB entry's,
+// plus a raw area of three row pieces of nv12_raw_pitch(widest box) = min(Ws, 8 S) + 32 bytes (two Y rows and the chroma
+// row they share; narrower boxes stage more rows per chunk): S = 224 from wide frames 77.7 KiB, still two workgroups per
+// CU.  Where that does not fit the CU (S > 440 from frames wider than 8 S), the stage and the raw area shrink to one source
+// row each (one Y and one chroma piece), so any S <= 480 fits here too.
+extern "C" int istvt_crop_resize_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
+                                      const int* boxes, void* out, int n, int S, hipStream_t stream) {
+    if (S < 1 || S > 4096 || !boxes || !out) return ISTVT_ERR_SHAPE;
+    Nv12Source src;
+    const int rc = nv12_source_of(frames, total, Hs, Ws, pitch, fstride, n, coef, &src);
+    if (rc != ISTVT_OK) return rc;
+    const int rp = nv12_raw_pitch(Ws < 8 * S ? Ws : 8 * S);
+    src.raw_bytes = 3 * rp;
+    const int r3 = crop_resize_launch(src, boxes, out, n, S, 2, src.raw_bytes, stream);
+    if (r3 != ISTVT_ERR_SHAPE) return r3;
+    src.raw_bytes = 2 * rp;
+    return crop_resize_launch(src, boxes, out, n, S, 1, src.raw_bytes, stream);
+}
+
+// NV12 frames as above -> out uint8 [n][Hs][Ws][3], contiguous, no alignment needed, no overlap with the frames
+extern "C" int istvt_nv12_to_rgb_u8(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
+                                    void* out, int n, hipStream_t stream) {
+    if (!out) return ISTVT_ERR_SHAPE;
+    Nv12Source src;
+    const int rc = nv12_source_of(frames, total, Hs, Ws, pitch, fstride, n, coef, &src);
+    if (rc != ISTVT_OK) return rc;
+    const int tiles = (Ws + NV_TW - 1) / NV_TW;
+    const long nblocks = (long)n * (Hs / 2) * tiles;
+    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    hipLaunchKernelGGL(nv12_to_rgb_u8_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream, src, (uint8_t*)out, tiles);
     return istvt_check_launch();
 }

@@ -55,12 +55,13 @@ __device__ __forceinline__ uint4 u8_load16(const uint8_t* __restrict__ x, long o
 // pitch of a staged row of S pixels: lead (<= 15) + S * 3 bytes, in whole 16-byte pieces
 __host__ __device__ __forceinline__ int u8_row_pitch(int S) { return ((S * 3 + 30) >> 4) << 4; }
 
-// Stage rows [0, nrows) of a work item: row r is the S * 3 bytes at g0 + r * rstride (offsets from x).  Returns lead(0);
-// lead(r) = (lead(0) + r * rstride) & 15 (u8_row_lead).  The caller synchronises.
-__device__ __forceinline__ int u8_stage_rows(const uint8_t* __restrict__ x, long total, long g0, int rstride, int nrows,
-                                             int S, unsigned char* sb, int pitch, int tid, int nthreads) {
+// Stage rows [0, nrows) of a work item, `len` bytes each: row r is the bytes at g0 + r * rstride (offsets from x), laid down
+// at sb + r * pitch + lead(r); pitch >= 15 + len in whole 16-byte pieces.  Returns lead(0); lead(r) = (lead(0) + r *
+// rstride) & 15 (u8_row_lead).  The caller synchronises.
+__device__ __forceinline__ int u8_stage_byte_rows(const uint8_t* __restrict__ x, long total, long g0, int rstride, int nrows,
+                                                  int len, unsigned char* sb, int pitch, int tid, int nthreads) {
     const int lead0 = (int)((reinterpret_cast<uintptr_t>(x) + (uintptr_t)g0) & 15);
-    const int cpr = pitch >> 4, len = S * 3;
+    const int cpr = pitch >> 4;
     for (int i = tid; i < nrows * cpr; i += nthreads) {
         const int rr = i / cpr, c = i - rr * cpr;
         const int lead = (lead0 + rr * rstride) & 15;
@@ -69,6 +70,12 @@ __device__ __forceinline__ int u8_stage_rows(const uint8_t* __restrict__ x, long
         *reinterpret_cast<uint4*>(sb + rr * pitch + 16 * c) = u8_load16(x, o, total);
     }
     return lead0;
+}
+
+// The same for rows of S packed RGB pixels (S * 3 bytes, pitch = u8_row_pitch(S))
+__device__ __forceinline__ int u8_stage_rows(const uint8_t* __restrict__ x, long total, long g0, int rstride, int nrows,
+                                             int S, unsigned char* sb, int pitch, int tid, int nthreads) {
+    return u8_stage_byte_rows(x, total, g0, rstride, nrows, S * 3, sb, pitch, tid, nthreads);
 }
 
 __device__ __forceinline__ int u8_row_lead(int lead0, int r, int rstride) { return (lead0 + r * rstride) & 15; }

@@ -243,8 +243,9 @@ class XceptionVidTr(nn.Module):
         """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S), or whole uint8
         frames (N, Hs, Ws, 3) with one face box (y0, x0, h, w) each in `boxes`, int32 (N, 4):
         istvt_amd.video.VideoScorer(self, **kw).score(frames, boxes).  jpeg_quality=q (1..100) among the keywords scores the
-        crops as a JPEG codec would hand them back at that quality (ops.jpeg_roundtrip_u8); score_videos and explain_video
-        take it too."""
+        crops as a JPEG codec would hand them back at that quality (ops.jpeg_roundtrip_u8); pixel_format='nv12' (with
+        yuv_matrix='bt601' | 'bt709' | 'jfif') takes NV12 frames uint8 (N, 3 * Hs / 2, Ws) and needs boxes; score_videos and
+        explain_video take both too."""
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score(frames, boxes=boxes)
 

@@ -1029,6 +1029,103 @@ def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] 
     return out
 
 
+def _nv12_source(what: str, frames: Tensor, matrix: str):
+    """Arguments common to the kernels that read NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws]
+    on the device.  The row pitch and the frame stride are the tensor's strides; only a non-contiguous last dimension is
+    copied.  -> (Hs, Ws, coefficients as a C array, launches), launches = [(tensor that keeps the memory alive, data_ptr,
+    readable bytes, pitch, frame stride, first frame, frames)]: one launch, or one per clip when the clip stride of a 4-D
+    batch is not T frame strides."""
+    import ctypes
+    from . import clips
+    if torch.is_tensor(frames) and frames.dtype != torch.uint8:
+        raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
+        raise RuntimeError('%s expects NV12 (n, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws) uint8 input, got %s'
+                           % (what, tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__))
+    if frames.numel() == 0:
+        raise RuntimeError('%s: empty input %s' % (what, tuple(frames.shape)))
+    if frames.stride(-1) != 1:
+        frames = frames.contiguous()
+    Hs, Ws = clips.check_nv12(frames)
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('%s: frames of at most 16384 x 16384, got %d x %d' % (what, Hs, Ws))
+    coef = (ctypes.c_int * 6)(*clips.nv12_coefficients(matrix))
+    _req(frames, 'frames')             # after the argument errors, which need no device
+    rows, pitch = Hs + Hs // 2, int(frames.stride(-2))
+    if pitch > (1 << 20):
+        raise ValueError('%s: a row pitch of at most 2^20 bytes, got %d' % (what, pitch))
+
+    def launch(t, first):              # t: 3-D
+        n, fs = int(t.shape[0]), int(t.stride(0)) if t.shape[0] > 1 else 0
+        return (t, t.data_ptr(), (n - 1) * fs + (rows - 1) * pitch + Ws, pitch, fs, first, n)
+
+    if frames.dim() == 3:
+        return Hs, Ws, coef, [launch(frames, 0)]
+    B, T = int(frames.shape[0]), int(frames.shape[1])
+    if B == 1 or T == 1 or frames.stride(0) == T * frames.stride(1):
+        flat = frames[0] if B == 1 else frames[:, 0] if T == 1 else frames.as_strided((B * T, rows, Ws), (frames.stride(1), pitch, 1))
+        return Hs, Ws, coef, [launch(flat, 0)]
+    return Hs, Ws, coef, [launch(frames[b], b * T) for b in range(B)]
+
+
+def _nv12_out(what: str, frames: Tensor, shape, out: Optional[Tensor]) -> Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device or not out.is_contiguous():
+        raise RuntimeError('%s: out must be contiguous uint8 %s on %s' % (what, tuple(shape), frames.device))
+    return out
+
+
+def nv12_to_rgb_u8(frames: Tensor, matrix: str = 'bt709', out: Optional[Tensor] = None) -> Tensor:
+    """NV12 frames (clips.py) -> packed RGB: frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device, the row
+    pitch and the frame stride taken from the tensor's strides (a decoder surface wrapped with as_strided is read where it
+    lies) -> uint8 [n, Hs, Ws, 3] / [B, T, Hs, Ws, 3], the bits of clips.nv12_to_rgb_host.  matrix: 'bt601', 'bt709' (limited
+    range) or 'jfif' (full range).  `out` (uint8, contiguous, of the result's shape, no overlap with the frames) is written
+    when given."""
+    Hs, Ws, coef, launches = _nv12_source('nv12_to_rgb_u8', frames, matrix)
+    out = _nv12_out('nv12_to_rgb_u8', frames, tuple(frames.shape[:-2]) + (Hs, Ws, 3), out)
+    flat = out.view((-1, Hs, Ws, 3))
+    for t, ptr, total, pitch, fs, first, n in launches:
+        if out.data_ptr() < ptr + total and ptr < out.data_ptr() + out.numel():
+            raise RuntimeError('nv12_to_rgb_u8: out may not share memory with the frames')
+        with prof('nv12_to_rgb_u8', n * Hs * Ws * 9 // 2):
+            _lib.check(_lib.lib().istvt_nv12_to_rgb_u8(ptr, total, Hs, Ws, pitch, fs, coef, flat[first:first + n].data_ptr(), n,
+                                                       _stream()), 'istvt_nv12_to_rgb_u8')
+    return out
+
+
+def crop_resize_nv12(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
+                     checked: bool = False) -> Tensor:
+    """crop_resize_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device (pitch
+    and frame stride from the tensor's strides, nothing copied unless the last dimension is not contiguous), boxes, S, `out`
+    and `checked` as crop_resize_u8 takes them, the boxes in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] /
+    [B, T, S, S, 3]: the bits of crop_resize_u8(nv12_to_rgb_u8(frames, matrix), boxes, S) without the RGB frames -- the colour
+    conversion runs on the rows of the box only, inside the crop kernel."""
+    from . import clips
+    Hs, Ws, coef, launches = _nv12_source('crop_resize_nv12', frames, matrix)
+    S = int(S)
+    if S < 1 or S > 480:
+        raise ValueError('crop_resize_nv12: the output side must lie in [1, 480], got %d' % S)
+    n = frames.numel() // (frames.shape[-2] * frames.shape[-1])
+    if checked:
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != frames.device:
+            raise RuntimeError('crop_resize_nv12: a checked box table is int32 (%d, 4) on %s' % (n, frames.device))
+        bdev = _c(boxes)
+    else:
+        b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
+        if frames.dim() == 4:
+            b = clips.per_frame_boxes(b, frames.shape[1])
+        bdev = b.contiguous().to(frames.device)
+    out = _nv12_out('crop_resize_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
+    flat = out.view((-1, S, S, 3))
+    for t, ptr, total, pitch, fs, first, k in launches:
+        with prof('crop_resize_nv12', k * S * S * 3):  # + the boxes' areas * 3 / 2, which live on the device
+            _lib.check(_lib.lib().istvt_crop_resize_nv12(ptr, total, Hs, Ws, pitch, fs, coef, bdev[first:first + k].data_ptr(),
+                                                         flat[first:first + k].data_ptr(), k, S, _stream()),
+                       'istvt_crop_resize_nv12')
+    return out
+
+
 def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
                       checked: bool = False) -> Tensor:
     """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for

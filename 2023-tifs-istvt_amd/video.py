@@ -71,14 +71,21 @@ def check_frames(frames) -> str:
     raise ValueError('frames must be uint8 or float32, got %s' % frames.dtype)
 
 
-def check_boxed_frames(frames, boxes, side: Optional[int]):
+def check_boxed_frames(frames, boxes, side: Optional[int], pixel_format: str = 'rgb24'):
     """Whole frames with one face box each (DESIGN.md "Frames and boxes"): frames uint8 (N, Hs, Ws, 3) of any size, boxes
-    int32 (N, 4) = (y0, x0, h, w) inside the frame with 1 <= h, w <= 8 side.  -> the validated box table on the host."""
+    int32 (N, 4) = (y0, x0, h, w) inside the frame with 1 <= h, w <= 8 side.  pixel_format 'nv12' (DESIGN.md "NV12 frames"):
+    frames uint8 (N, 3 * Hs / 2, Ws), the boxes in pixels of the Hs x Ws picture.  -> the validated box table on the host."""
     from . import clips
     if side is None:
         raise ValueError('boxes need the side of the crops: VideoScorer(model, side=S) or model.set_crop_side(S)')
     if not torch.is_tensor(frames):
         raise ValueError('frames must be a torch tensor, got %s' % type(frames).__name__)
+    if pixel_format == 'nv12':
+        if frames.dtype != torch.uint8 or frames.dim() != 3:
+            raise ValueError('NV12 frames must be uint8 (N, 3 * Hs / 2, Ws) as a decoder delivers them, got %s %s'
+                             % (frames.dtype, tuple(frames.shape)))
+        Hs, Ws = clips.check_nv12(frames)
+        return clips.check_boxes(boxes, int(frames.shape[0]), Hs, Ws, int(side))
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError('with boxes, frames must be uint8 channels-last (N, Hs, Ws, 3) as a decoder delivers them, got %s %s'
                          % (frames.dtype, tuple(frames.shape)))
@@ -420,11 +427,17 @@ class VideoScorer:
                   just before the stem, after the crop when a call passes `boxes` -- the S x S crops the stem reads are
                   recompressed, not the whole frames.  score(), push(), score_videos() and explain() then give the bits they
                   give on ops.jpeg_roundtrip_u8(crops, jpeg_quality); float frames raise TypeError.
+    pixel_format  'rgb24' (packed RGB, the default) or 'nv12': every call then takes NV12 frames uint8 (N, 3 * Hs / 2, Ws) and
+                  needs `boxes` (ValueError without; frames that already are the crops take identity boxes).  The crop reads
+                  the NV12 bytes itself (ops.crop_resize_nv12): the bits of the 'rgb24' scorer on
+                  ops.crop_resize_nv12(frames, boxes, side, yuv_matrix), and everything after the crop is the same code.
+    yuv_matrix    'bt601', 'bt709' (limited range) or 'jfif' (full range): how 'nv12' frames become RGB.
     """
 
     def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
                  capacity: Optional[int] = None, mean: Sequence[float] = DEFAULT_MEAN, std: Sequence[float] = DEFAULT_STD,
-                 cover_tail: bool = True, side: Optional[int] = None, jpeg_quality: Optional[int] = None):
+                 cover_tail: bool = True, side: Optional[int] = None, jpeg_quality: Optional[int] = None,
+                 pixel_format: str = 'rgb24', yuv_matrix: str = 'bt709'):
         vit = getattr(model, 'vit', None)
         if vit is None or not hasattr(model, 'xcep') or not hasattr(vit, 'forward_tokens'):
             raise TypeError('VideoScorer: expected an XceptionVidTr, got %s' % type(model).__name__)
@@ -447,6 +460,12 @@ class VideoScorer:
                                          or not 1 <= jpeg_quality <= 100):
             raise ValueError('VideoScorer: jpeg_quality must be None or an int in [1, 100], got %r' % (jpeg_quality,))
         self.jpeg_quality = jpeg_quality
+        if pixel_format not in ('rgb24', 'nv12'):
+            raise ValueError("VideoScorer: pixel_format must be 'rgb24' or 'nv12', got %r" % (pixel_format,))
+        from . import clips
+        if yuv_matrix not in clips.YUV_MATRICES:
+            raise ValueError("VideoScorer: yuv_matrix must be 'bt601', 'bt709' or 'jfif', got %r" % (yuv_matrix,))
+        self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
         self._norm = None                  # (device, mean tensor, std tensor)
         self._jpeg = None                  # the device quality table of a stem batch: jpeg_quality, frame_batch times
         self.reset()
@@ -475,6 +494,18 @@ class VideoScorer:
         dev = self._device()
         return b.contiguous().to(dev, non_blocking=True), side
 
+    def _check_boxed(self, frames, boxes, side):
+        """check_boxed_frames in this scorer's pixel format; 'nv12' has no call without boxes"""
+        if boxes is None:
+            raise ValueError("VideoScorer: pixel_format='nv12' needs boxes with every call (one (y0, x0, h, w) per frame; "
+                             'frames that already are the crops take identity boxes)')
+        return check_boxed_frames(frames, boxes, side, self.pixel_format)
+
+    def _crop(self, x: Tensor, boxes: Tensor, side: int, out: Optional[Tensor] = None) -> Tensor:
+        if self.pixel_format == 'nv12':
+            return ops.crop_resize_nv12(x, boxes, side, self.yuv_matrix, out=out, checked=True)
+        return ops.crop_resize_u8(x, boxes, side, out=out, checked=True)
+
     def _check_kind(self, kind: str) -> str:
         if self.jpeg_quality is not None and kind == 'f32':
             raise TypeError('VideoScorer: jpeg_quality recompresses decoded uint8 frames; normalised float frames cannot take it')
@@ -484,7 +515,7 @@ class VideoScorer:
         if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
             x = x.contiguous().pin_memory().to(dev, non_blocking=True)
         if boxes is not None:              # whole frames: this batch's crops, made where the frames are
-            x = ops.crop_resize_u8(x, boxes, side, checked=True)
+            x = self._crop(x, boxes, side)
         if self.jpeg_quality is not None:  # the bytes the stem reads, as a JPEG codec would hand them back
             n = int(x.shape[0])
             if self._jpeg is None or self._jpeg.device != dev or self._jpeg.shape[0] < n:
@@ -544,11 +575,11 @@ class VideoScorer:
         of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation.
         boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); a stream keeps one mode."""
         bdev = side = None
-        if boxes is None:
+        if boxes is None and self.pixel_format == 'rgb24':
             kind = self._check_kind(check_frames(frames))
         else:
             side = self._side()
-            bhost = check_boxed_frames(frames, boxes, side)
+            bhost = self._check_boxed(frames, boxes, side)
             kind = 'u8+boxes'
         if self._kind is not None and kind != self._kind:
             if 'u8+boxes' in (kind, self._kind):
@@ -577,11 +608,11 @@ class VideoScorer:
     def _whole_video(self, frames: Tensor, rollout=None, boxes=None):
         """every window of one video on a ring of its own -> (logits, list of starts, device)"""
         bdev = side = None
-        if boxes is None:
+        if boxes is None and self.pixel_format == 'rgb24':
             kind = self._check_kind(check_frames(frames))
         else:
             side = self._side()
-            bhost = check_boxed_frames(frames, boxes, side)
+            bhost = self._check_boxed(frames, boxes, side)
             kind = 'u8+boxes'
         n = int(frames.shape[0])
         if n < self.T:
@@ -619,7 +650,7 @@ class VideoScorer:
         """-> (kind, list of validated host box tables or None, side); every ValueError of a call, before anything is launched"""
         if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
             raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
-        if boxes is None:
+        if boxes is None and self.pixel_format == 'rgb24':
             kinds = [self._check_kind(check_frames(v)) for v in videos]
             if len(set(kinds)) != 1:
                 raise ValueError('the videos of one call are all uint8 or all float, not both (video %d differs from video 0)'
@@ -628,10 +659,12 @@ class VideoScorer:
             if len(set(sides)) != 1:
                 raise ValueError('the videos of one call share one crop side, got %s' % sorted(set(sides)))
             return kinds[0], None, None
+        if boxes is None:
+            self._check_boxed(videos[0], None, None)
         if not isinstance(boxes, (list, tuple)) or len(boxes) != len(videos):
             raise ValueError('boxes: one table per video expected (%d)' % len(videos))
         side = self._side()
-        return 'u8', [check_boxed_frames(v, b, side) for v, b in zip(videos, boxes)], side
+        return 'u8', [self._check_boxed(v, b, side) for v, b in zip(videos, boxes)], side
 
     def score_videos(self, videos, boxes=None, labels=None) -> VideoSetScore:
         """All windows of a set of videos in one pass (DESIGN.md "Scoring a set of videos"): the windows of score(video) for
@@ -658,7 +691,8 @@ class VideoScorer:
         with _eval_mode(self.model), torch.no_grad():
             for st in plan.steps:
                 if st.kind == 'frames':
-                    feats = self._stem(self._frame_batch(videos, plan.pieces(st.first, st.count), bdev, side, dev), kind, dev)
+                    feats = self._stem(self._frame_batch(videos, plan.pieces(st.first, st.count), bdev, side, dev, self._crop),
+                                       kind, dev)
                     if bank is None:
                         bank = torch.empty((plan.slots_used,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
                     s0 = st.slots[0]
@@ -684,10 +718,10 @@ class VideoScorer:
         return res
 
     @staticmethod
-    def _frame_batch(videos, pieces, bdev, side, dev) -> Tensor:
+    def _frame_batch(videos, pieces, bdev, side, dev, crop=None) -> Tensor:
         """One stem batch on the device from (video, lo, hi) pieces.  Without boxes a single device piece is used where it is;
         otherwise the pieces are copied into one staging batch (host pieces pinned first).  With boxes every piece is cropped
-        by ops.crop_resize_u8 into its slice of one crop batch."""
+        by `crop` (the scorer's _crop; ops.crop_resize_u8 when none is given) into its slice of one crop batch."""
         if bdev is None and len(pieces) == 1:
             v, lo, hi = pieces[0]
             x = videos[v][lo:hi]
@@ -704,7 +738,10 @@ class VideoScorer:
             else:
                 if not x.is_cuda:
                     x = x.contiguous().pin_memory().to(dev, non_blocking=True)
-                ops.crop_resize_u8(x, bdev[v][lo:hi], side, out=batch[at:at + hi - lo], checked=True)
+                if crop is None:
+                    ops.crop_resize_u8(x, bdev[v][lo:hi], side, out=batch[at:at + hi - lo], checked=True)
+                else:
+                    crop(x, bdev[v][lo:hi], side, batch[at:at + hi - lo])
             at += hi - lo
         return batch
 

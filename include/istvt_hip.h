@@ -307,6 +307,19 @@ int istvt_im2col_conv1_u8(const void* x, long total, int Hs, int Ws, const int* 
  * kept in fp32, then vertical; byte = clamp(floor(v + 0.5), 0, 255).  h = w = S reproduces the slice.  S <= 480 (LDS). */
 int istvt_crop_resize_u8(const void* frames, long total, int Hs, int Ws, const int* boxes, void* out, int n, int S,
                          istvt_stream_t stream);
+/* NV12 frames: n frames of Hs rows of Y followed by Hs / 2 rows of Ws / 2 interleaved (Cb, Cr) pairs, uint8, `pitch` bytes
+ * from row to row and `fstride` bytes from frame to frame (`total` bytes readable at frames, >= (n - 1) * fstride + (3 Hs / 2
+ * - 1) * pitch + Ws; nothing outside is read, no alignment needed); Hs, Ws even, pixel (y, x) takes the pair (y >> 1,
+ * x >> 1).  coef = (ky, yoff, krv, kgu, kgv, kbu) on the host, each in [0, 2^20), yoff <= 255; with Cb' = Cb - 128, Cr' =
+ * Cr - 128 and yy = ky (Y - yoff), in int32: R = clamp((yy + krv Cr' + 32768) >> 16), G = clamp((yy - kgu Cb' - kgv Cr' +
+ * 32768) >> 16), B = clamp((yy + kbu Cb' + 32768) >> 16), arithmetic shifts, clamp to 0..255.
+ * istvt_nv12_to_rgb_u8 -> out uint8 [n][Hs][Ws][3] (contiguous, no alignment needed, no overlap with the frames).
+ * istvt_crop_resize_nv12 -> out uint8 [n][S][S][3]: istvt_crop_resize_u8 (the same boxes, the same filter code) on those
+ * RGB frames, bit for bit, without making them: only the Y and chroma bytes of the box rows are read.  S <= 480 (LDS). */
+int istvt_nv12_to_rgb_u8(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef, void* out,
+                         int n, istvt_stream_t stream);
+int istvt_crop_resize_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
+                           const int* boxes, void* out, int n, int S, istvt_stream_t stream);
 /* JPEG round trip: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), quality int32 [n] on the device -> out uint8 [n][H][W][3] (no overlap with frames: ISTVT_ERR_SHAPE), the
  * RGB a baseline JPEG encoder and decoder hand back: libjpeg's 16-bit fixed-point colour transforms, edge replication to whole

@@ -6,6 +6,7 @@
     python tools/video_bench.py --explain           # VideoScorer.explain against model.relevance on materialised windows
     python tools/video_bench.py --boxes             # whole 1080 x 1920 frames and face boxes (DESIGN.md "Frames and boxes")
 
+    python tools/video_bench.py --nv12              # NV12 frames: the fused crop against convert + crop (DESIGN.md "NV12 frames")
     python tools/video_bench.py --videos            # a set of 64 videos of 32 frames (DESIGN.md "Scoring a set of videos")
 
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
@@ -29,6 +30,12 @@ clips.crop_resize_host on host frames + upload of the crops, twice on its own (i
 torch restatement of the definition, not a tuned image library); (d) the kernel alone on all frames (events around the launch)
 against (e) a device-to-device copy that moves the same algorithmic bytes (box areas * 3 in, S * S * 3 out per frame: a
 copy of half their sum reads and writes that many).
+
+--nv12 (DESIGN.md "NV12 frames"), stride 8 unless --strides says otherwise: --frames NV12 frames of --full-size on the
+device, made once with clips.rgb_to_nv12_host, one random box of side --box-sides per frame.  Events around the launches,
+the legs of a comparison alternating, median and range of --reps: (a) ops.crop_resize_nv12 against (b) ops.nv12_to_rgb_u8
+followed by ops.crop_resize_u8; each of those two kernels on its own; then score(nv12, boxes) on an NV12 scorer against
+score(rgb, boxes) on the frames (b) converted beforehand.
 
 --videos (DESIGN.md "Scoring a set of videos"), strides 8 and 1 unless --strides says otherwise: --set-size device-resident
 uint8 videos of --video-frames frames.  Alternating, medians and spread as above: (a) score_videos(videos, labels=...);
@@ -218,6 +225,74 @@ def boxes_bench(a, model):
     return out
 
 
+def nv12_bench(a, model):
+    from istvt_amd import clips
+    Hs, Ws = (int(v) for v in a.full_size.split('x'))
+    lo, hi = (int(v) for v in a.box_sides.split('-'))
+    S, n = a.size, a.frames
+    g = torch.Generator().manual_seed(2)
+    nv = torch.empty((n, Hs + Hs // 2, Ws), dtype=torch.uint8, device='cuda')
+    for i in range(0, n, 8):                                # the float64 encoder, a few frames at a time
+        k = min(8, n - i)
+        nv[i:i + k] = clips.rgb_to_nv12_host(torch.randint(0, 256, (k, Hs, Ws, 3), generator=g, dtype=torch.uint8).cuda(), a.matrix)
+    h = torch.randint(lo, hi + 1, (n,), generator=g)
+    w = torch.randint(lo, hi + 1, (n,), generator=g)
+    y0 = torch.minimum((torch.rand(n, generator=g) * (Hs - h + 1)).long(), Hs - h)
+    x0 = torch.minimum((torch.rand(n, generator=g) * (Ws - w + 1)).long(), Ws - w)
+    boxes = torch.stack([y0, x0, h, w], dim=1).to(torch.int32)
+    bdev = boxes.cuda()
+    rgb = ops.nv12_to_rgb_u8(nv, a.matrix)
+    crops = ops.crop_resize_u8(rgb, boxes, S)
+    fused = ops.crop_resize_nv12(nv, boxes, S, a.matrix)
+    area = int((h * w).sum())
+    out = {'frames': n, 'full_size': [Hs, Ws], 'box_sides': [lo, hi], 'size': S, 'matrix': a.matrix, 'box_pixels': area,
+           'equal_bits': bool(torch.equal(fused, crops)), 'strides': {}}
+    legs = {'fused': lambda: ops.crop_resize_nv12(nv, bdev, S, a.matrix, out=fused, checked=True),
+            'convert_then_crop': lambda: ops.crop_resize_u8(ops.nv12_to_rgb_u8(nv, a.matrix, out=rgb), bdev, S, out=crops, checked=True),
+            'nv12_to_rgb_u8': lambda: ops.nv12_to_rgb_u8(nv, a.matrix, out=rgb),
+            'crop_resize_u8': lambda: ops.crop_resize_u8(rgb, bdev, S, out=crops, checked=True)}
+    ts = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        for k, fn in legs.items():                          # alternating
+            t = event_ms(fn)
+            if r >= a.warmup:
+                ts[k].append(t)
+    # algorithmic bytes: the fused kernel reads 1.5 bytes per box pixel, the conversion 1.5 per frame pixel and writes 3
+    nbytes = {'fused': area * 3 // 2 + n * S * S * 3, 'nv12_to_rgb_u8': n * Hs * Ws * 9 // 2, 'crop_resize_u8': area * 3 + n * S * S * 3}
+    for k in legs:
+        out[k] = stats(ts[k])
+        if k in nbytes:
+            out[k]['GB_per_s'] = nbytes[k] / out[k]['median_ms'] * 1e-6
+        print('nv12 %-18s %.3f ms (%.3f-%.3f)%s' % (k, out[k]['median_ms'], out[k]['min_ms'], out[k]['max_ms'],
+                                                     ' = %.0f GB/s of its algorithmic bytes' % out[k]['GB_per_s'] if k in nbytes else ''),
+              flush=True)
+    print('nv12: fused / (convert + crop) x%.3f | equal bits %s' % (out['fused']['median_ms'] / out['convert_then_crop']['median_ms'],
+                                                                  out['equal_bits']), flush=True)
+    for stride in [int(s) for s in a.strides.split(',')]:
+        kw = dict(stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch, side=S)
+        s_nv = video.VideoScorer(model, pixel_format='nv12', yuv_matrix=a.matrix, **kw)
+        s_rgb = video.VideoScorer(model, **kw)
+        res = {}
+
+        def run_nv12():
+            res['a'] = s_nv.score(nv, boxes=boxes).window_logits
+
+        def run_rgb():
+            res['b'] = s_rgb.score(rgb, boxes=boxes).window_logits
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_nv12), timed(run_rgb)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        sa, sb = stats(ta), stats(tb)
+        out['strides'][str(stride)] = {'nv12': sa, 'rgb': sb, 'equal_bits': bool(torch.equal(res['a'], res['b']))}
+        print('nv12 stride %d: score(nv12, boxes) %.2f ms (%.2f-%.2f) | score(rgb, boxes) %.2f ms (%.2f-%.2f) | equal bits %s'
+              % (stride, sa['median_ms'], sa['min_ms'], sa['max_ms'], sb['median_ms'], sb['min_ms'], sb['max_ms'],
+                 out['strides'][str(stride)]['equal_bits']), flush=True)
+    return out
+
+
 def _phases(scorer, model, fn, extra=()):
     """one instrumented run of fn: device ms between the events around the three phases and the kernels named in `extra`"""
     ops.kernel_profile = []
@@ -313,13 +388,15 @@ def main():
     ap.add_argument('--explain', action='store_true')
     ap.add_argument('--boxes', action='store_true')
     ap.add_argument('--videos', action='store_true')
+    ap.add_argument('--nv12', action='store_true')
+    ap.add_argument('--matrix', default='bt709', choices=['bt601', 'bt709', 'jfif'])
     ap.add_argument('--set-size', type=int, default=64)
     ap.add_argument('--video-frames', type=int, default=32)
     ap.add_argument('--full-size', default='1080x1920')
     ap.add_argument('--box-sides', default='150-600')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    a.strides = a.strides or ('8,1' if a.videos else '1,8' if a.explain or a.boxes else '1,2,4,8')
+    a.strides = a.strides or ('8' if a.nv12 else '8,1' if a.videos else '1,8' if a.explain or a.boxes else '1,2,4,8')
     if not torch.cuda.is_available():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
@@ -339,6 +416,17 @@ def main():
         print(json.dumps({'video_set_bench': {k: {'loop_over_set': v['loop_over_set'],
                                                   'set_ms_per_32_windows': v['set_ms_per_32_windows']}
                                               for k, v in out['strides'].items()}}))
+        return
+    if a.nv12:
+        out = dict(nv12_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
+                   window_batch=a.window_batch, reps=a.reps, warmup=a.warmup)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_nv12_bench': {'fused_ms': out['fused']['median_ms'],
+                                               'convert_then_crop_ms': out['convert_then_crop']['median_ms'],
+                                               'crop_resize_u8_ms': out['crop_resize_u8']['median_ms'], 'equal_bits': out['equal_bits']}}))
         return
     if a.boxes:
         out = dict(boxes_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
