@@ -985,13 +985,36 @@ def im2col_conv1_u8(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tens
     return col
 
 
+def _u8_out(what: str, frames: Tensor, shape, out: Optional[Tensor]) -> Tensor:
+    """the uint8 result of the byte-image routines: a new tensor of `shape` on the frames' device, or the caller's `out`"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device or not out.is_contiguous():
+        raise RuntimeError('%s: out must be contiguous uint8 %s on %s' % (what, tuple(shape), frames.device))
+    return out
+
+
+def _frame_boxes(what: str, frames: Tensor, boxes: Tensor, n: int, T: Optional[int], Hs: int, Ws: int, S: int,
+                 checked: bool) -> Tensor:
+    """the device box table of the two crops, one row for each of the n frames: a checked table as it is, or the host table
+    validated (clips.check_boxes), spread over the T frames of a clip (T None: frames, not clips) and uploaded"""
+    from . import clips
+    if checked:
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != frames.device:
+            raise RuntimeError('%s: a checked box table is int32 (%d, 4) on %s' % (what, n, frames.device))
+        return _c(boxes)
+    b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
+    if T is not None:
+        b = clips.per_frame_boxes(b, T)
+    return b.contiguous().to(frames.device)
+
+
 def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
     """Frames and boxes (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, boxes int32 [n,4] = (y0, x0, h,
     w) per frame or, for clips, [B,4] spread over the T frames of a clip -> uint8 [n,S,S,3] / [B,T,S,S,3]: every box cut out
     and resized with the antialiased bilinear filter of clips.crop_resize_host.  Boxes are validated on the host
     (clips.check_boxes) before any launch and then uploaded; checked=True takes a per-frame device table the caller has
     validated already.  `out` (uint8, contiguous, of the result's shape) is written when given."""
-    from . import clips
     _req(frames, 'frames')
     if frames.dtype != torch.uint8:
         raise TypeError('crop_resize_u8: frames must be uint8, got %s' % frames.dtype)
@@ -1009,20 +1032,8 @@ def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] 
         raise ValueError('crop_resize_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
     src = _c(frames).view((-1, Hs, Ws, 3))
     n = src.shape[0]
-    if checked:
-        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != src.device:
-            raise RuntimeError('crop_resize_u8: a checked box table is int32 (%d, 4) on %s' % (n, src.device))
-        bdev = _c(boxes)
-    else:
-        b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
-        if frames.dim() == 5:
-            b = clips.per_frame_boxes(b, frames.shape[1])
-        bdev = b.contiguous().to(src.device)
-    shape = lead + (S, S, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != src.device or not out.is_contiguous():
-        raise RuntimeError('crop_resize_u8: out must be contiguous uint8 %s on %s' % (shape, src.device))
+    bdev = _frame_boxes('crop_resize_u8', frames, boxes, n, frames.shape[1] if frames.dim() == 5 else None, Hs, Ws, S, checked)
+    out = _u8_out('crop_resize_u8', frames, lead + (S, S, 3), out)
     with prof('crop_resize_u8', n * S * S * 3):        # + the boxes' areas * 3, which live on the device
         _lib.check(_lib.lib().istvt_crop_resize_u8(src.data_ptr(), src.numel(), Hs, Ws, bdev.data_ptr(), out.data_ptr(), n, S,
                                                    _stream()), 'istvt_crop_resize_u8')
@@ -1068,14 +1079,6 @@ def _nv12_source(what: str, frames: Tensor, matrix: str):
     return Hs, Ws, coef, [launch(frames[b], b * T) for b in range(B)]
 
 
-def _nv12_out(what: str, frames: Tensor, shape, out: Optional[Tensor]) -> Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device or not out.is_contiguous():
-        raise RuntimeError('%s: out must be contiguous uint8 %s on %s' % (what, tuple(shape), frames.device))
-    return out
-
-
 def nv12_to_rgb_u8(frames: Tensor, matrix: str = 'bt709', out: Optional[Tensor] = None) -> Tensor:
     """NV12 frames (clips.py) -> packed RGB: frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device, the row
     pitch and the frame stride taken from the tensor's strides (a decoder surface wrapped with as_strided is read where it
@@ -1083,7 +1086,7 @@ def nv12_to_rgb_u8(frames: Tensor, matrix: str = 'bt709', out: Optional[Tensor] 
     range) or 'jfif' (full range).  `out` (uint8, contiguous, of the result's shape, no overlap with the frames) is written
     when given."""
     Hs, Ws, coef, launches = _nv12_source('nv12_to_rgb_u8', frames, matrix)
-    out = _nv12_out('nv12_to_rgb_u8', frames, tuple(frames.shape[:-2]) + (Hs, Ws, 3), out)
+    out = _u8_out('nv12_to_rgb_u8', frames, tuple(frames.shape[:-2]) + (Hs, Ws, 3), out)
     flat = out.view((-1, Hs, Ws, 3))
     for t, ptr, total, pitch, fs, first, n in launches:
         if out.data_ptr() < ptr + total and ptr < out.data_ptr() + out.numel():
@@ -1101,22 +1104,13 @@ def crop_resize_nv12(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709
     and `checked` as crop_resize_u8 takes them, the boxes in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] /
     [B, T, S, S, 3]: the bits of crop_resize_u8(nv12_to_rgb_u8(frames, matrix), boxes, S) without the RGB frames -- the colour
     conversion runs on the rows of the box only, inside the crop kernel."""
-    from . import clips
     Hs, Ws, coef, launches = _nv12_source('crop_resize_nv12', frames, matrix)
     S = int(S)
     if S < 1 or S > 480:
         raise ValueError('crop_resize_nv12: the output side must lie in [1, 480], got %d' % S)
     n = frames.numel() // (frames.shape[-2] * frames.shape[-1])
-    if checked:
-        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != frames.device:
-            raise RuntimeError('crop_resize_nv12: a checked box table is int32 (%d, 4) on %s' % (n, frames.device))
-        bdev = _c(boxes)
-    else:
-        b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
-        if frames.dim() == 4:
-            b = clips.per_frame_boxes(b, frames.shape[1])
-        bdev = b.contiguous().to(frames.device)
-    out = _nv12_out('crop_resize_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
+    bdev = _frame_boxes('crop_resize_nv12', frames, boxes, n, frames.shape[1] if frames.dim() == 4 else None, Hs, Ws, S, checked)
+    out = _u8_out('crop_resize_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
     flat = out.view((-1, S, S, 3))
     for t, ptr, total, pitch, fs, first, k in launches:
         with prof('crop_resize_nv12', k * S * S * 3):  # + the boxes' areas * 3 / 2, which live on the device
@@ -1166,11 +1160,7 @@ def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Op
         if frames.dim() == 5:
             q = q.repeat_interleave(frames.shape[1])
         qdev = q.contiguous().to(src.device, non_blocking=True)
-    if out is None:
-        out = torch.empty_like(frames)
-    elif (out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape) or out.device != src.device
-          or not out.is_contiguous()):
-        raise RuntimeError('jpeg_roundtrip_u8: out must be contiguous uint8 %s on %s' % (tuple(frames.shape), src.device))
+    out = _u8_out('jpeg_roundtrip_u8', frames, frames.shape, out)
     nbytes = src.numel()
     if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
         raise RuntimeError('jpeg_roundtrip_u8: out may not share memory with the input (the round trip is not done in place)')

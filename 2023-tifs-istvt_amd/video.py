@@ -345,16 +345,21 @@ class VideoSetScore(NamedTuple):
     metrics: Optional[SetMetrics]      # set_metrics(logit_mean[:, 0], labels) when labels were given
 
 
-def _check_labels(labels, V: int, dev) -> Tensor:
-    """labels of 0 / 1 -> int32 (V,) on dev.  A host tensor or a list is validated; a device tensor is taken as it is
-    (checking it would synchronise): anything but 0 counts as 1."""
+def _validate_labels(labels, V: int) -> Tensor:
+    """labels of 0 / 1, one per video, checked on the host -> the tensor.  A host tensor or a list is validated; a device
+    tensor is taken as it is (checking it would synchronise): anything but 0 counts as 1."""
     if not torch.is_tensor(labels):
         labels = torch.as_tensor(labels)
     if labels.dim() != 1 or labels.shape[0] != V:
         raise ValueError('labels: one 0 / 1 per video expected, (%d,), got %s' % (V, tuple(labels.shape)))
+    if not labels.is_cuda and not bool(((labels == 0) | (labels == 1)).all()):
+        raise ValueError('labels must be 0 or 1')
+    return labels
+
+
+def _upload_labels(labels: Tensor, dev) -> Tensor:
+    """validated labels -> int32 (V,) on dev"""
     if not labels.is_cuda:
-        if not bool(((labels == 0) | (labels == 1)).all()):
-            raise ValueError('labels must be 0 or 1')
         return labels.to(torch.int32).to(dev, non_blocking=True)
     return labels.to(device=dev, dtype=torch.int32)
 
@@ -366,7 +371,7 @@ def set_metrics(scores: Tensor, labels, threshold: float = 0.0) -> SetMetrics:
         raise ValueError('scores: one per video expected, (V,), got %s'
                          % (tuple(scores.shape) if torch.is_tensor(scores) else type(scores).__name__,))
     ops._req(scores, 'scores')
-    lab = _check_labels(labels, int(scores.shape[0]), scores.device)
+    lab = _upload_labels(_validate_labels(labels, int(scores.shape[0])), scores.device)
     counts, auc = ops.auc_pairs(scores.float(), lab, threshold)
     c = dict(zip(ops.AUC_COUNTS, counts.unbind(0)))
     return SetMetrics(c['correct'], c['positives'], c['negatives'], c['nonfinite'], auc[0], c['greater'], c['equal'])
@@ -395,6 +400,39 @@ def set_metrics_ref(scores, labels, threshold: float = 0.0) -> dict:
     auc = (float(greater) + 0.5 * float(equal)) / (float(P) * float(N)) if P and N else float('nan')
     correct = int((fin & ((s > threshold) == lab)).sum())
     return dict(correct=correct, positives=P, negatives=N, nonfinite=int((~fin).sum()), auc=auc, greater=greater, equal=equal)
+
+
+class VideoInput(NamedTuple):
+    """What a call hands over for one video (VideoScorer._input)."""
+    reads: str                 # what the stem reads: 'u8' decoded bytes, 'f32' normalised floats
+    boxed: bool                # whole frames with one box each: every stem batch is cropped to side x side first
+    side: Optional[int]        # the side of those crops (None without boxes)
+    boxes: Optional[Tensor]    # the validated box table on the host, int32 (N, 4) (None without boxes)
+
+
+def slot_runs(slots: Sequence[int]) -> List[Tuple[int, int]]:
+    """The slots of a frame batch as (first slot, count) runs of consecutive slots, in order: one run for a batch that lies
+    in the bank as it is, two where a ring wraps, more for slots scattered over a pool."""
+    runs = [[slots[0], 1]]
+    for s in slots[1:]:
+        if s == runs[-1][0] + runs[-1][1]:
+            runs[-1][1] += 1
+        else:
+            runs.append([s, 1])
+    return [(s0, k) for s0, k in runs]
+
+
+def _store(bank: Tensor, feats: Tensor, slots: Tuple[int, ...], dslots: Optional[Tensor] = None):
+    """feats[i] -> bank[slots[i]]: slice copies run by run, or one index_copy_ when the slots are scattered and the caller
+    has them on the device (dslots, int64)"""
+    runs = slot_runs(slots)
+    if len(runs) > 1 and dslots is not None:
+        bank.index_copy_(0, dslots, feats)
+        return
+    at = 0
+    for s0, k in runs:
+        bank[s0:s0 + k].copy_(feats[at:at + k])
+        at += k
 
 
 @contextlib.contextmanager
@@ -470,52 +508,64 @@ class VideoScorer:
         self._jpeg = None                  # the device quality table of a stem batch: jpeg_quality, frame_batch times
         self.reset()
 
-    # ---------------------------------------------------------------------------------------- streaming state
-    def reset(self):
-        """Forget the stream: the next push() is frame 0 of a new video."""
-        self._plan: Optional[RingPlan] = None
-        self._ring: Optional[Tensor] = None
-        self._kind: Optional[str] = None
-        return self
-
+    # ---------------------------------------------------------------------------------------- what a call hands over
     def _device(self):
         dev = next(self.model.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('VideoScorer: the model must be on a ROCm device (no CPU fallback exists for the ISTVT hot path)')
         return dev
 
-    def _side(self) -> Optional[int]:
-        return self.side if self.side is not None else getattr(self.model, 'crop_side', None)
-
-    def _boxed(self, frames: Tensor, boxes):
-        """-> (validated boxes on the device, side) of a call with boxes; raises before anything is launched"""
-        side = self._side()
-        b = check_boxed_frames(frames, boxes, side)
-        dev = self._device()
-        return b.contiguous().to(dev, non_blocking=True), side
-
-    def _check_boxed(self, frames, boxes, side):
-        """check_boxed_frames in this scorer's pixel format; 'nv12' has no call without boxes"""
+    def _input(self, frames, boxes) -> VideoInput:
+        """The frames (and boxes) of one video, checked: every argument error of a call, before anything is launched."""
+        if boxes is None and self.pixel_format == 'rgb24':
+            reads = check_frames(frames)
+            if self.jpeg_quality is not None and reads == 'f32':
+                raise TypeError('VideoScorer: jpeg_quality recompresses decoded uint8 frames; normalised float frames cannot '
+                                'take it')
+            return VideoInput(reads, False, None, None)
         if boxes is None:
             raise ValueError("VideoScorer: pixel_format='nv12' needs boxes with every call (one (y0, x0, h, w) per frame; "
                              'frames that already are the crops take identity boxes)')
-        return check_boxed_frames(frames, boxes, side, self.pixel_format)
+        side = self.side if self.side is not None else getattr(self.model, 'crop_side', None)
+        return VideoInput('u8', True, side, check_boxed_frames(frames, boxes, side, self.pixel_format))
 
-    def _crop(self, x: Tensor, boxes: Tensor, side: int, out: Optional[Tensor] = None) -> Tensor:
-        if self.pixel_format == 'nv12':
-            return ops.crop_resize_nv12(x, boxes, side, self.yuv_matrix, out=out, checked=True)
-        return ops.crop_resize_u8(x, boxes, side, out=out, checked=True)
+    def _fetcher(self, videos, inputs: Sequence[VideoInput], pieces, dev):
+        """-> fetch(first, count), the stem batch of frames [first, first + count) of the executor's steps;
+        pieces(first, count) names them as (video, lo, hi).  The box tables are uploaded here, once."""
+        bdev = [i.boxes.contiguous().to(dev, non_blocking=True) for i in inputs] if inputs[0].boxed else None
+        return lambda first, count: self._frame_batch(videos, pieces(first, count), bdev, inputs[0].side, dev)
 
-    def _check_kind(self, kind: str) -> str:
-        if self.jpeg_quality is not None and kind == 'f32':
-            raise TypeError('VideoScorer: jpeg_quality recompresses decoded uint8 frames; normalised float frames cannot take it')
-        return kind
+    def _frame_batch(self, videos, pieces, bdev, side, dev) -> Tensor:
+        """One stem batch from (video, lo, hi) pieces.  Without boxes a single piece is used where it lies (_stem uploads a
+        host batch); several are copied into one staging batch on the device (host pieces pinned first).  With boxes (bdev:
+        one validated device table per video) every piece is cropped into its slice of one batch of side x side crops, from
+        NV12 or packed RGB as the scorer's pixel_format says."""
+        if bdev is None and len(pieces) == 1:
+            v, lo, hi = pieces[0]
+            return videos[v][lo:hi]
+        n = sum(hi - lo for _, lo, hi in pieces)
+        first = videos[pieces[0][0]]
+        shape = (n, side, side, 3) if bdev is not None else (n,) + tuple(first.shape[1:])
+        batch = torch.empty(shape, dtype=first.dtype, device=dev)
+        at = 0
+        for v, lo, hi in pieces:
+            x, out = videos[v][lo:hi], batch[at:at + hi - lo]
+            if not x.is_cuda:
+                x = x.contiguous().pin_memory()
+            if bdev is None:
+                out.copy_(x, non_blocking=True)
+            elif self.pixel_format == 'nv12':
+                ops.crop_resize_nv12(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, self.yuv_matrix, out=out, checked=True)
+            else:
+                ops.crop_resize_u8(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, out=out, checked=True)
+            at += hi - lo
+        return batch
 
-    def _stem(self, x: Tensor, kind: str, dev, boxes: Optional[Tensor] = None, side: Optional[int] = None) -> Tensor:
+    # ---------------------------------------------------------------------------------------- the executor
+    def _stem(self, x: Tensor, kind: str, dev) -> Tensor:
+        """a stem batch ('u8' bytes or 'f32' normalised floats) -> its features (n, h * w, C)"""
         if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
             x = x.contiguous().pin_memory().to(dev, non_blocking=True)
-        if boxes is not None:              # whole frames: this batch's crops, made where the frames are
-            x = self._crop(x, boxes, side)
         if self.jpeg_quality is not None:  # the bytes the stem reads, as a JPEG codec would hand them back
             n = int(x.shape[0])
             if self._jpeg is None or self._jpeg.device != dev or self._jpeg.shape[0] < n:
@@ -532,68 +582,66 @@ class VideoScorer:
         n, h, w, c = feats.shape
         return feats.view(n, h * w, c)
 
-    def _store(self, feats: Tensor, slots: Tuple[int, ...]):
-        C = self._ring.shape[0]
-        k, s0 = len(slots), slots[0]
-        head = min(k, C - s0)              # slots are consecutive modulo the capacity: at most two pieces
-        self._ring[s0:s0 + head].copy_(feats[:head])
-        if head < k:
-            self._ring[:k - head].copy_(feats[head:])
-
-    def _run(self, steps: List[Step], frames: Optional[Tensor], base: int, kind: Optional[str], dev, rollout=None,
-             boxes: Optional[Tensor] = None, side: Optional[int] = None):
-        """-> (logits (W, num_classes) float32 on the device, list of starts) of the windows the steps ran.  rollout:
-        what runs a batch of windows instead of the plain forward, (tokens, windows, h*w) -> logits (explain()).
-        boxes: the validated device table of `frames` (row i for frames[i]); each stem batch is cropped to side x side."""
+    def _execute(self, steps: Sequence[Step], bank: Optional[Tensor], slots: int, dev, fetch=None, reads: Optional[str] = None,
+                 rollout=None, dslots: Optional[Tensor] = None):
+        """Runs the steps, in order, against the feature bank it is given -> (bank, logits (W, num_classes) float32 on the
+        device, list of starts) of the windows that ran.  A 'frames' step sends fetch(first, count) through the stem (`reads`
+        as VideoInput has it) into its slots; a 'windows' step assembles the tokens of its windows from the bank and runs
+        the transformer on them.  bank None: allocated with `slots` slots from the shape of the first stem batch.  idx of a
+        'windows' step: a host table, validated and uploaded by ops.tokens_gather_fwd, or a device table the caller has
+        validated.  rollout: what runs a batch of windows instead of the plain forward, (tokens, windows, h*w) -> logits
+        (explain()).  dslots: the slots of all 'frames' steps, one after the other, int64 on the device."""
         vit = self.model.vit
-        outs, starts = [], []
+        outs, starts, fpos = [], [], 0
         with _eval_mode(self.model), torch.no_grad():
             for st in steps:
                 if st.kind == 'frames':
-                    lo = st.first - base
-                    feats = (self._stem(frames[lo:lo + st.count], kind, dev) if boxes is None else
-                             self._stem(frames[lo:lo + st.count], 'u8', dev, boxes[lo:lo + st.count], side))
-                    if self._ring is None:
-                        self._ring = torch.empty((self._plan.capacity,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
-                    elif tuple(self._ring.shape[1:]) != tuple(feats.shape[1:]) or self._ring.dtype != feats.dtype:
+                    feats = self._stem(fetch(st.first, st.count), reads, dev)
+                    if bank is None:
+                        bank = torch.empty((slots,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
+                    elif tuple(bank.shape[1:]) != tuple(feats.shape[1:]) or bank.dtype != feats.dtype:
                         raise RuntimeError('VideoScorer: the frames of one stream must share one size and compute dtype '
                                            '(reset() starts a new stream)')
-                    self._store(feats, st.slots)
+                    _store(bank, feats, st.slots, None if dslots is None else dslots[fpos:fpos + st.count])
+                    fpos += st.count
                 else:
-                    hw = self._ring.shape[1]
-                    x = ops.tokens_gather_fwd(self._ring, st.idx, vit.space_token, vit.temporal_token, vit.pos_embedding,
-                                              pad=True)
+                    hw = bank.shape[1]
+                    x = ops.tokens_gather_fwd(bank, st.idx, vit.space_token, vit.temporal_token, vit.pos_embedding, pad=True,
+                                              checked=st.idx.is_cuda)
                     outs.append(vit.forward_tokens(x, st.count, self.T + 1, hw + 1) if rollout is None
                                 else rollout(x, st.count, hw))
                     starts.extend(st.starts)
+        if len(outs) == 1:
+            return bank, outs[0], starts
         nc = vit.mlp_head[1].out_features
-        logits = torch.cat(outs) if outs else torch.empty((0, nc), dtype=torch.float32, device=dev)
-        return logits, starts
+        return bank, torch.cat(outs) if outs else torch.empty((0, nc), dtype=torch.float32, device=dev), starts
+
+    # ---------------------------------------------------------------------------------------- a stream
+    def reset(self):
+        """Forget the stream: the next push() is frame 0 of a new video."""
+        self._plan: Optional[RingPlan] = None
+        self._ring: Optional[Tensor] = None
+        self._kind: Optional[VideoInput] = None            # what the stream's first push handed over
+        return self
 
     def push(self, frames: Tensor, boxes=None):
         """The next frames of the stream -> (logits (W, num_classes) float32 on the device, starts (W,) int64 on the host)
         of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation.
         boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); a stream keeps one mode."""
-        bdev = side = None
-        if boxes is None and self.pixel_format == 'rgb24':
-            kind = self._check_kind(check_frames(frames))
-        else:
-            side = self._side()
-            bhost = self._check_boxed(frames, boxes, side)
-            kind = 'u8+boxes'
-        if self._kind is not None and kind != self._kind:
-            if 'u8+boxes' in (kind, self._kind):
-                raise ValueError('VideoScorer: a stream takes boxes with every push or with none (reset() starts a new one)')
+        inp = self._input(frames, boxes)
+        if self._kind is not None and inp.boxed != self._kind.boxed:
+            raise ValueError('VideoScorer: a stream takes boxes with every push or with none (reset() starts a new one)')
+        if self._kind is not None and inp.reads != self._kind.reads:
             raise ValueError('VideoScorer: a stream is either uint8 or float frames, not both (reset() starts a new one)')
         dev = self._device()
-        if boxes is not None:
-            bdev = bhost.contiguous().to(dev, non_blocking=True)
         if self._plan is None:
             cap = self.capacity if self.capacity is not None else -(-(self.T + self.frame_batch) // 8) * 8
             self._plan = RingPlan(self.T, self.stride, cap, self.frame_batch, self.window_batch)
-        self._kind = kind
+        self._kind = inp._replace(boxes=None)
         base = self._plan.seen
-        logits, starts = self._run(self._plan.push(int(frames.shape[0])), frames, base, kind, dev, boxes=bdev, side=side)
+        fetch = self._fetcher([frames], [inp], lambda first, count: [(0, first - base, first - base + count)], dev)
+        self._ring, logits, starts = self._execute(self._plan.push(int(frames.shape[0])), self._ring, self._plan.capacity, dev,
+                                                   fetch, inp.reads)
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     def flush(self):
@@ -601,34 +649,22 @@ class VideoScorer:
         was shorter than one window."""
         if self._plan is None:
             raise ValueError('a video of 0 frames is shorter than one window of %d' % self.T)
-        logits, starts = self._run(self._plan.flush(self.cover_tail), None, 0, None, self._device())
+        _, logits, starts = self._execute(self._plan.flush(self.cover_tail), self._ring, self._plan.capacity, self._device())
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     # ---------------------------------------------------------------------------------------- whole video
     def _whole_video(self, frames: Tensor, rollout=None, boxes=None):
-        """every window of one video on a ring of its own -> (logits, list of starts, device)"""
-        bdev = side = None
-        if boxes is None and self.pixel_format == 'rgb24':
-            kind = self._check_kind(check_frames(frames))
-        else:
-            side = self._side()
-            bhost = self._check_boxed(frames, boxes, side)
-            kind = 'u8+boxes'
+        """every window of one video, on a plan and a bank of its own -> (logits, list of starts, device)"""
+        inp = self._input(frames, boxes)
         n = int(frames.shape[0])
         if n < self.T:
             raise ValueError('a video of %d frames is shorter than one window of %d' % (n, self.T))
         dev = self._device()
-        if boxes is not None:
-            bdev = bhost.contiguous().to(dev, non_blocking=True)
-        saved = (self._plan, self._ring, self._kind)
-        try:
-            self._plan = RingPlan(self.T, self.stride, self.capacity if self.capacity is not None else n,
-                                  self.frame_batch, self.window_batch)
-            self._ring = None
-            steps = self._plan.push(n, drain=False) + self._plan.flush(self.cover_tail)
-            logits, starts = self._run(steps, frames, 0, kind, dev, rollout, bdev, side)
-        finally:
-            self._plan, self._ring, self._kind = saved
+        plan = RingPlan(self.T, self.stride, self.capacity if self.capacity is not None else n, self.frame_batch,
+                        self.window_batch)
+        steps = plan.push(n, drain=False) + plan.flush(self.cover_tail)
+        fetch = self._fetcher([frames], [inp], lambda first, count: [(0, first, first + count)], dev)
+        _, logits, starts = self._execute(steps, None, plan.capacity, dev, fetch, inp.reads, rollout)
         return logits, starts, dev
 
     @staticmethod
@@ -637,113 +673,13 @@ class VideoScorer:
                           torch.sigmoid(logits).mean(0))
 
     def score(self, frames: Tensor, boxes=None) -> VideoScore:
-        """All windows of one video.  Does not disturb a stream in progress (it uses a ring of its own).  boxes: one
+        """All windows of one video.  Does not disturb a stream in progress (it never touches the stream's state).  boxes: one
         (y0, x0, h, w) per frame, int32 (N, 4), for whole frames uint8 (N, Hs, Ws, 3): each stem batch is cropped and resized
         to side x side on the device (ops.crop_resize_u8) just before the stem -- the bits of score() on those crops."""
         logits, starts, dev = self._whole_video(frames, boxes=boxes)
         res = self._video_score(logits, starts, dev)
         torch.cuda.current_stream(dev).synchronize()
         return res
-
-    # ---------------------------------------------------------------------------------------- a set of videos
-    def _check_set(self, videos, boxes):
-        """-> (kind, list of validated host box tables or None, side); every ValueError of a call, before anything is launched"""
-        if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
-            raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
-        if boxes is None and self.pixel_format == 'rgb24':
-            kinds = [self._check_kind(check_frames(v)) for v in videos]
-            if len(set(kinds)) != 1:
-                raise ValueError('the videos of one call are all uint8 or all float, not both (video %d differs from video 0)'
-                                 % next(i for i, k in enumerate(kinds) if k != kinds[0]))
-            sides = [int(v.shape[2]) for v in videos]
-            if len(set(sides)) != 1:
-                raise ValueError('the videos of one call share one crop side, got %s' % sorted(set(sides)))
-            return kinds[0], None, None
-        if boxes is None:
-            self._check_boxed(videos[0], None, None)
-        if not isinstance(boxes, (list, tuple)) or len(boxes) != len(videos):
-            raise ValueError('boxes: one table per video expected (%d)' % len(videos))
-        side = self._side()
-        return 'u8', [self._check_boxed(v, b, side) for v, b in zip(videos, boxes)], side
-
-    def score_videos(self, videos, boxes=None, labels=None) -> VideoSetScore:
-        """All windows of a set of videos in one pass (DESIGN.md "Scoring a set of videos"): the windows of score(video) for
-        every video, but stem batches and window batches are assembled across the videos (SetPlan), the per-video means are
-        one kernel (ops.windows_reduce), and the call synchronises once.  videos: a list of tensors as score() takes them --
-        all uint8 or all float, one crop side, host or device in any mix.  boxes: one table per video, for whole uint8
-        frames; each video may have its own frame size.  labels: one 0 / 1 per video -> metrics = set_metrics(logit_mean[:, 0],
-        labels).  A stream in progress is not disturbed."""
-        kind, bhost, side = self._check_set(videos, boxes)
-        plan = SetPlan([int(v.shape[0]) for v in videos], self.T, self.stride, self.cover_tail, self.frame_batch,
-                       self.window_batch, self.capacity)
-        V = len(videos)
-        if labels is not None and (torch.as_tensor(labels).dim() != 1 or len(labels) != V):
-            raise ValueError('labels: one 0 / 1 per video expected, (%d,)' % V)
-        dev = self._device()
-        vit = self.model.vit
-        # every table of the call in two uploads: the slots of the frame batches (int64, for index_copy_) and the windows' idx
-        fsteps = [st for st in plan.steps if st.kind == 'frames']
-        wsteps = [st for st in plan.steps if st.kind == 'windows']
-        slots = torch.tensor([s for st in fsteps for s in st.slots], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-        idx = torch.cat([st.idx for st in wsteps]).pin_memory().to(dev, non_blocking=True)      # SetPlan names slots < capacity
-        bdev = None if bhost is None else [b.contiguous().to(dev, non_blocking=True) for b in bhost]
-        bank, outs, fpos, wpos = None, [], 0, 0
-        with _eval_mode(self.model), torch.no_grad():
-            for st in plan.steps:
-                if st.kind == 'frames':
-                    feats = self._stem(self._frame_batch(videos, plan.pieces(st.first, st.count), bdev, side, dev, self._crop),
-                                       kind, dev)
-                    if bank is None:
-                        bank = torch.empty((plan.slots_used,) + tuple(feats.shape[1:]), dtype=feats.dtype, device=dev)
-                    s0 = st.slots[0]
-                    if st.slots == tuple(range(s0, s0 + st.count)):
-                        bank[s0:s0 + st.count].copy_(feats)
-                    else:
-                        bank.index_copy_(0, slots[fpos:fpos + st.count], feats)
-                    fpos += st.count
-                else:
-                    x = ops.tokens_gather_fwd(bank, idx[wpos:wpos + st.count], vit.space_token, vit.temporal_token,
-                                              vit.pos_embedding, pad=True, checked=True)
-                    outs.append(vit.forward_tokens(x, st.count, self.T + 1, bank.shape[1] + 1))
-                    wpos += st.count
-            logits = torch.cat(outs) if len(outs) > 1 else outs[0]
-            tab = torch.tensor(plan.offsets + plan.window_video, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-            offsets, window_video = tab[:V + 1], tab[V + 1:]
-            starts = torch.tensor(plan.starts, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
-            ops.check_window_offsets(plan.offsets, int(logits.shape[0]))
-            logit_mean, prob_mean = ops.windows_reduce(logits, offsets, checked=True)
-            metrics = None if labels is None else set_metrics(logit_mean[:, 0].contiguous(), labels)
-        res = VideoSetScore(logits, window_video, starts, offsets, logit_mean, prob_mean, metrics)
-        torch.cuda.current_stream(dev).synchronize()
-        return res
-
-    @staticmethod
-    def _frame_batch(videos, pieces, bdev, side, dev, crop=None) -> Tensor:
-        """One stem batch on the device from (video, lo, hi) pieces.  Without boxes a single device piece is used where it is;
-        otherwise the pieces are copied into one staging batch (host pieces pinned first).  With boxes every piece is cropped
-        by `crop` (the scorer's _crop; ops.crop_resize_u8 when none is given) into its slice of one crop batch."""
-        if bdev is None and len(pieces) == 1:
-            v, lo, hi = pieces[0]
-            x = videos[v][lo:hi]
-            return x if x.is_cuda else x.contiguous().pin_memory().to(dev, non_blocking=True)
-        n = sum(hi - lo for _, lo, hi in pieces)
-        first = videos[pieces[0][0]]
-        shape = (n, side, side, 3) if bdev is not None else (n,) + tuple(first.shape[1:])
-        batch = torch.empty(shape, dtype=first.dtype, device=dev)
-        at = 0
-        for v, lo, hi in pieces:
-            x = videos[v][lo:hi]
-            if bdev is None:
-                batch[at:at + hi - lo].copy_(x if x.is_cuda else x.contiguous().pin_memory(), non_blocking=True)
-            else:
-                if not x.is_cuda:
-                    x = x.contiguous().pin_memory().to(dev, non_blocking=True)
-                if crop is None:
-                    ops.crop_resize_u8(x, bdev[v][lo:hi], side, out=batch[at:at + hi - lo], checked=True)
-                else:
-                    crop(x, bdev[v][lo:hi], side, batch[at:at + hi - lo])
-            at += hi - lo
-        return batch
 
     def explain(self, frames: Tensor, index: int = 0, boxes=None) -> VideoExplanation:
         """Relevance maps of one video for output `index` (DESIGN.md "Explaining whole videos"): the windows, frames and
@@ -764,5 +700,54 @@ class VideoScorer:
             windows = _explain.Relevance(torch.cat([r.r_s for r in rels]), torch.cat([r.r_t for r in rels]), logits)
             fused = ops.relevance_fuse_windows(windows.r_s, windows.r_t, logits, starts, int(frames.shape[0]), index)
         res = VideoExplanation(self._video_score(logits, starts, dev), windows, *fused)
+        torch.cuda.current_stream(dev).synchronize()
+        return res
+
+    # ---------------------------------------------------------------------------------------- a set of videos
+    def _check_set(self, videos, boxes) -> List[VideoInput]:
+        """-> every video's VideoInput; every ValueError of a call about its videos and boxes, before anything is launched"""
+        if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
+            raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
+        if boxes is None:
+            inputs = [self._input(v, None) for v in videos]
+            if len({i.reads for i in inputs}) != 1:
+                raise ValueError('the videos of one call are all uint8 or all float, not both (video %d differs from video 0)'
+                                 % next(v for v, i in enumerate(inputs) if i.reads != inputs[0].reads))
+            sides = sorted({int(v.shape[2]) for v in videos})
+            if len(sides) != 1:
+                raise ValueError('the videos of one call share one crop side, got %s' % sides)
+            return inputs
+        if not isinstance(boxes, (list, tuple)) or len(boxes) != len(videos) or any(b is None for b in boxes):
+            raise ValueError('boxes: one table per video expected (%d)' % len(videos))
+        return [self._input(v, b) for v, b in zip(videos, boxes)]
+
+    def score_videos(self, videos, boxes=None, labels=None) -> VideoSetScore:
+        """All windows of a set of videos in one pass (DESIGN.md "Scoring a set of videos"): the windows of score(video) for
+        every video, but stem batches and window batches are assembled across the videos (SetPlan), the per-video means are
+        one kernel (ops.windows_reduce), and the call synchronises once.  videos: a list of tensors as score() takes them --
+        all uint8 or all float, one crop side, host or device in any mix.  boxes: one table per video, for whole uint8
+        frames; each video may have its own frame size.  labels: one 0 / 1 per video -> metrics = set_metrics(logit_mean[:, 0],
+        labels).  A stream in progress is not disturbed."""
+        inputs = self._check_set(videos, boxes)
+        plan = SetPlan([int(v.shape[0]) for v in videos], self.T, self.stride, self.cover_tail, self.frame_batch,
+                       self.window_batch, self.capacity)
+        V = len(videos)
+        if labels is not None:
+            labels = _validate_labels(labels, V)
+        dev = self._device()
+        # every table of the call in two uploads: the slots of the frame batches (int64, for index_copy_) and the windows' idx,
+        # whose slices take the place of the steps' host tables (SetPlan names slots < capacity: they are checked)
+        dslots = torch.tensor([s for st in plan.steps for s in st.slots], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        idx = torch.cat([st.idx for st in plan.steps if st.kind == 'windows']).pin_memory().to(dev, non_blocking=True)
+        steps = [st if st.kind == 'frames' else st._replace(idx=idx[st.first:st.first + st.count]) for st in plan.steps]
+        fetch = self._fetcher(videos, inputs, plan.pieces, dev)
+        _, logits, _ = self._execute(steps, None, plan.slots_used, dev, fetch, inputs[0].reads, dslots=dslots)
+        tab = torch.tensor(plan.offsets + plan.window_video, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        offsets, window_video = tab[:V + 1], tab[V + 1:]
+        starts = torch.tensor(plan.starts, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        ops.check_window_offsets(plan.offsets, int(logits.shape[0]))
+        logit_mean, prob_mean = ops.windows_reduce(logits, offsets, checked=True)
+        metrics = None if labels is None else set_metrics(logit_mean[:, 0].contiguous(), labels)
+        res = VideoSetScore(logits, window_video, starts, offsets, logit_mean, prob_mean, metrics)
         torch.cuda.current_stream(dev).synchronize()
         return res

@@ -312,3 +312,71 @@ def test_score_nv12_with_jpeg_quality(boxed):
     assert torch.equal(res.window_logits, ref.window_logits)
     plain = video.VideoScorer(boxed['model'], frame_batch=4, side=SIDE).score(boxed['crops'])
     assert not torch.equal(res.window_logits, plain.window_logits)
+
+
+# ---- every option through every entry -----------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def small_model(pkg):
+    """the `small` model of tests/test_video_set_gpu.py: depth 2, T = 4, 96 x 96 (grid 6), float32, running statistics moved by
+    one training forward, left in TRAIN mode"""
+    from oracle import istvt_ref as R
+    from istvt_amd.network.vivit.vivit import XceptionVidTr
+    T, depth = 4, 2
+    grid = R.stem_out_side(SIDE)
+    shapes = {'xcep.model.' + k: v for k, v in R.stem_param_shapes().items()}
+    shapes.update({'vit.' + k: v for k, v in R.dsttr_param_shapes(T, grid, depth=depth).items()})
+    model = XceptionVidTr(num_frames=T, grid=grid, depth=depth)
+    sd = model.state_dict()
+    sd.update(R.random_params(shapes, seed=0))
+    model.load_state_dict(sd)
+    model = model.cuda().train()
+    with torch.no_grad():
+        model(torch.randn((2, T, 3, SIDE, SIDE), generator=torch.Generator().manual_seed(1)).cuda())
+    return model
+
+
+def test_nv12_jpeg_boxes_through_every_entry(small_model):
+    """NV12 frames, boxes and JPEG recompression at once, through score_videos, score, push / flush and explain, on a bank of 8
+    slots: the bits of the plain scorer on ops.jpeg_roundtrip_u8(ops.crop_resize_nv12(...)) made beforehand.  The set's plan
+    has a frame batch made of two videos' pieces and one whose slots are scattered; the 9-frame video wraps the ring."""
+    from istvt_amd import ops, video
+    counts, sizes = [5, 9, 6], [(120, 160), (130, 110), (120, 160)]
+    plan = video.SetPlan(counts, 4, 3, True, 4, 2, 8)
+    fsteps = [st for st in plan.steps if st.kind == 'frames']
+    assert any(len(plan.pieces(st.first, st.count)) > 1 for st in fsteps)
+    assert any(st.slots != tuple(range(st.slots[0], st.slots[0] + st.count)) for st in fsteps)
+    g = torch.Generator().manual_seed(31)
+    nvs, boxes, crops = [], [], []
+    for i, (n, (Hs, Ws)) in enumerate(zip(counts, sizes)):
+        nv = _nv12(n, Hs, Ws, 40 + i)
+        h = torch.randint(40, Hs + 1, (n,), generator=g)
+        w = torch.randint(40, Ws + 1, (n,), generator=g)
+        y0 = torch.minimum((torch.rand(n, generator=g) * (Hs - h + 1).float()).long(), Hs - h)
+        x0 = torch.minimum((torch.rand(n, generator=g) * (Ws - w + 1).float()).long(), Ws - w)
+        b = torch.stack([y0, x0, h, w], dim=1).to(torch.int32)
+        crops.append(ops.jpeg_roundtrip_u8(ops.crop_resize_nv12(nv.cuda(), b, SIDE, 'bt709'), 40))
+        nvs.append(nv if i == 1 else nv.cuda())                                  # the 9-frame video stays on the host
+        boxes.append(b)
+    kw = dict(stride=3, frame_batch=4, window_batch=2, capacity=8)
+    scorer = video.VideoScorer(small_model, side=SIDE, jpeg_quality=40, pixel_format='nv12', **kw)
+    plain = video.VideoScorer(small_model, **kw)
+    res, ref = scorer.score_videos(nvs, boxes=boxes), plain.score_videos(crops)
+    assert torch.isfinite(ref.window_logits).all() and ref.window_logits.shape[0] == len(plan.starts)
+    for i in range(6):
+        assert torch.equal(res[i], ref[i]), video.VideoSetScore._fields[i]
+    nv, b, c = nvs[1], boxes[1], crops[1]
+    assert torch.equal(scorer.score(nv, boxes=b).window_logits, plain.score(c).window_logits)
+
+    def stream(s, frames, table):
+        outs = []
+        for lo in range(0, 9, 2):
+            outs.append(s.push(frames[lo:lo + 2], boxes=None if table is None else table[lo:lo + 2].contiguous()))
+        outs.append(s.flush())
+        return torch.cat([l for l, _ in outs]), torch.cat([st for _, st in outs]).tolist()
+    got, want = stream(scorer, nv, b), stream(plain, c, None)
+    assert want[1] == video.window_starts(9, 4, 3, True) and got[1] == want[1]
+    assert torch.equal(got[0], want[0])
+    ex, exr = scorer.explain(nv, boxes=b), plain.explain(c)
+    assert float(exr.frame_s.abs().max()) > 0
+    for name in ('frame_s', 'frame_t', 'frame_weight'):
+        assert torch.equal(getattr(ex, name), getattr(exr, name)), name

@@ -124,6 +124,18 @@ def test_input_errors(video):
         video.check_frames(torch.zeros((5, 3, 8, 8), dtype=torch.float64))
 
 
+@pytest.mark.parametrize('slots,runs', [((2, 3, 4, 5), 1),           # one consecutive run
+                                        ((6, 7, 0, 1), 2),           # a ring of 8 slots wraps
+                                        ((0, 3, 4), 2),              # scattered over a pool
+                                        ((0, 1, 4, 5, 2), 3),
+                                        ((5,), 1)])                  # a single slot
+def test_slot_runs_cover_every_slot_once_and_in_order(video, slots, runs):
+    got = video.slot_runs(slots)
+    assert len(got) == runs and all(k >= 1 for _, k in got)
+    assert tuple(s0 + i for s0, k in got for i in range(k)) == slots
+    assert all(a + k != b for (a, k), (b, _) in zip(got, got[1:]))   # the runs are maximal
+
+
 def test_scorer_checks_before_any_device_work(video):
     from istvt_amd.network.vivit.vivit import XceptionVidTr
     model = XceptionVidTr(num_frames=4, grid=6, depth=1)

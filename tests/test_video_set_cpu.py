@@ -139,6 +139,16 @@ def test_score_videos_refuses_bad_sets_before_any_launch(video):
     assert callable(XceptionVidTr.score_videos)
 
 
+def test_score_videos_refuses_bad_labels_before_any_launch(video):
+    """label values are checked where their shape is: on the host, before the device is asked for"""
+    from istvt_amd.network.vivit.vivit import XceptionVidTr
+    scorer = video.VideoScorer(XceptionVidTr(num_frames=T, grid=6, depth=1))     # on the host: nothing may be launched
+    u8 = torch.zeros((5, 96, 96, 3), dtype=torch.uint8)
+    for labels in ([0, 2], torch.tensor([0, 2])):
+        with pytest.raises(ValueError, match='0 or 1'):                          # not the RuntimeError about the ROCm device
+            scorer.score_videos([u8, u8], labels=labels)
+
+
 def test_entry_points_declared_and_exported(video):
     from istvt_amd import _lib, ops
     header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
