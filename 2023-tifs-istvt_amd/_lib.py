@@ -59,6 +59,8 @@ SIGNATURES = {
     'istvt_crop_resize_u8': [P, L, I, I, P, P, I, I, P],
     'istvt_crop_resize_nv12': [P, L, I, I, L, L, P, P, P, I, I, P],
     'istvt_nv12_to_rgb_u8': [P, L, I, I, L, L, P, P, I, P],
+    'istvt_warp_similarity_u8': [P, L, I, I, P, P, I, I, P],
+    'istvt_warp_similarity_nv12': [P, L, I, I, L, L, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],

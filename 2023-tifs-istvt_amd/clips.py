@@ -21,7 +21,13 @@ NV12 frames (DESIGN.md "NV12 frames") are the fourth: ``nv12_coefficients``, ``c
 definition of ops.nv12_to_rgb_u8, integers only), ``crop_resize_nv12_host`` (of ops.crop_resize_nv12) and ``rgb_to_nv12_host``,
 a plain float encoder that makes NV12 fixtures.  ``ops.crop_resize_nv12(clips_nv12, boxes, S)`` stands where
 ``ops.crop_resize_u8(u8, boxes, S)`` stands above.
+
+Aligned crops (DESIGN.md "Aligned crops") are the fifth: ``check_similarities``, ``warp_similarity_host`` (the definition of
+ops.warp_similarity_u8, float64), ``similarity_of_boxes``, ``similarity_from_landmarks``, ``similarities_of_squares`` and
+``random_similarities``.  A
+training step with rotation, scale and flip in one table is ``model(ops.warp_similarity_u8(u8, M.to(dev), S))``.
 """
+import math
 from fractions import Fraction
 from typing import Optional
 
@@ -541,3 +547,222 @@ def rgb_to_nv12_host(u8: Tensor, matrix: str = 'bt709') -> Tensor:
     out[..., Hs:, 0::2] = torch.floor(Cb + 0.5).clamp_(0, 255).to(torch.uint8)
     out[..., Hs:, 1::2] = torch.floor(Cr + 0.5).clamp_(0, 255).to(torch.uint8)
     return out
+
+
+# ------------------------------------------------------------------------------------------ aligned crops
+# DESIGN.md "Aligned crops": whole frames uint8 (n, Hs, Ws, 3) and one similarity per frame, M float32 (n, 2, 3) -> uint8
+# (n, S, S, 3).  M takes the CENTRE of output pixel (ox, oy) to continuous source coordinates; source pixel j covers
+# [j, j + 1) and has its centre at j + 0.5, the convention of resize_weights:
+#
+#     cx = m00 (ox + .5) + m01 (oy + .5) + m02        cy = m10 (ox + .5) + m11 (oy + .5) + m12
+#     u = (m00, m10), v = (m01, m11);  e1 = u / |u|, e2 = v / |v|;  s = sqrt(|det|);  sup = max(s, 1)
+#     for every integer (jx, jy):  d = (jx + .5 - cx, jy + .5 - cy)
+#         w = max(0, 1 - |d . e1| / sup) * max(0, 1 - |d . e2| / sup)
+#     value_c = sum w * frame[clamp(jy, 0, Hs - 1), clamp(jx, 0, Ws - 1), c] / sum w        (all in float64)
+#     byte = clamp(floor(value + 0.5), 0, 255)
+#
+# the antialiased triangle of crop_resize in the rotated frame of the output, with the border replicated: an aligned face
+# next to the frame's edge still gives a crop.  ops.warp_similarity_u8 is the device kernel, warp_similarity_host the
+# definition.
+MIN_SIMILARITY_SCALE = 2.0 ** -6
+MAX_SIMILARITY_SCALE = 8.0                 # about 4 sup^2 taps per pixel: some 260 at the most
+SIMILARITY_TOLERANCE = 1e-4
+
+
+def _similarity_parts(M: Tensor):
+    """float64 pieces of a table (n, 2, 3): |u|, |v|, u . v, s = sqrt |det|"""
+    m = M.detach().cpu().to(torch.float64)
+    m00, m01, m10, m11 = m[:, 0, 0], m[:, 0, 1], m[:, 1, 0], m[:, 1, 1]
+    nu = torch.sqrt(m00 * m00 + m10 * m10)
+    nv = torch.sqrt(m01 * m01 + m11 * m11)
+    return m, nu, nv, m00 * m01 + m10 * m11, torch.sqrt((m00 * m11 - m01 * m10).abs())
+
+
+def check_similarities(M, n: int, Hs: int, Ws: int, S: int) -> Tensor:
+    """Host validation of a table of similarities before any launch: float32 (n, 2, 3), every number finite; a similarity,
+    ||u| - |v|| <= 1e-4 max(|u|, |v|) and |u . v| <= 1e-4 |u| |v| for the columns u = (m00, m10), v = (m01, m11); a scale
+    s = sqrt |det| with 2^-6 <= s <= 8; and the image of the output centre (S / 2, S / 2) inside [0, Ws] x [0, Hs]
+    (IndexError otherwise).  Returns the table on the host (a device tensor is copied back, which waits for the device: hand
+    over the host tensor)."""
+    if S is None or S < 1:
+        raise ValueError('similarities need the output side S >= 1, got %r' % (S,))
+    if not torch.is_tensor(M):
+        raise TypeError('similarities must be a float32 tensor (n, 2, 3), got %s' % type(M).__name__)
+    if M.dtype != torch.float32:
+        raise TypeError('similarities must be float32, got %s' % M.dtype)
+    if M.dim() != 3 or tuple(M.shape) != (n, 2, 3):
+        raise ValueError('similarities must have shape (%d, 2, 3), one 2 x 3 map per entry, got %s' % (n, tuple(M.shape)))
+    t = M.detach().cpu()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError('similarities: every entry must be finite')
+    m, nu, nv, dot, s = _similarity_parts(t)
+    tol = SIMILARITY_TOLERANCE
+    if bool(((nu - nv).abs() > tol * torch.maximum(nu, nv)).any()) or bool((dot.abs() > tol * nu * nv).any()):
+        raise ValueError('similarities: a rotation, a uniform scale and an optional mirror expected (columns of equal length '
+                         'at right angles, to 1e-4); general affine maps are not supported')
+    if bool((s < MIN_SIMILARITY_SCALE).any()) or bool((s > MAX_SIMILARITY_SCALE).any()):
+        raise ValueError('similarities: the scale sqrt|det| (source pixels per output pixel) must lie in [2^-6, 8], got '
+                         '[%g, %g]' % (float(s.min()), float(s.max())))
+    h = 0.5 * S
+    px = (m[:, 0, 0] * h + m[:, 0, 1] * h) + m[:, 0, 2]
+    py = (m[:, 1, 0] * h + m[:, 1, 1] * h) + m[:, 1, 2]
+    if bool((px < 0).any()) or bool((px > Ws).any()) or bool((py < 0).any()) or bool((py > Hs).any()):
+        raise IndexError('similarities: the output centre (%g, %g) must land inside the frame [0, %d] x [0, %d], got x in '
+                         '[%g, %g], y in [%g, %g]' % (h, h, Ws, Hs, float(px.min()), float(px.max()), float(py.min()),
+                                                     float(py.max())))
+    return t
+
+
+def per_frame_similarities(M: Tensor, T: int) -> Tensor:
+    """(B, 2, 3) per-clip table -> (B*T, 2, 3) per-frame table (each clip's map repeated for its T frames), where `M` lives"""
+    return M.repeat_interleave(T, dim=0).contiguous()
+
+
+def warp_similarity_host(u8: Tensor, M: Tensor, S: int) -> Tensor:
+    """The definition on the host, in float64: uint8 (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3) and M float32 (n, 2, 3) / (B, 2, 3)
+    -> uint8 (n, S, S, 3) / (B, T, S, S, 3), as the comment above states it.  Every output pixel sums the (2 K + 1)^2 source
+    pixels around the pixel under its centre, K = ceil(sqrt 2 sup) + 1: all that can have a weight, one pass over the S x S
+    output per tap offset (memory does not grow with s; the passes do, 729 at s = 8).  Documentation and a
+    reference for tests: the device path is ops.warp_similarity_u8 (double sums in another order: a byte may differ by one
+    where the value lies within rounding of a half)."""
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 3:
+        raise ValueError('warp_similarity_host expects uint8 (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3), got %s %s'
+                         % (u8.dtype, tuple(u8.shape)))
+    lead = tuple(u8.shape[:-3])
+    Hs, Ws = int(u8.shape[-3]), int(u8.shape[-2])
+    t = check_similarities(M, u8.shape[0], Hs, Ws, S)
+    if u8.dim() == 5:
+        t = per_frame_similarities(t, u8.shape[1])
+    src = u8.reshape((-1, Hs, Ws, 3)).cpu()
+    m, nu, nv, _, sc = _similarity_parts(t)
+    out = torch.empty((src.shape[0], S, S, 3), dtype=torch.uint8)
+    o = torch.arange(S, dtype=torch.float64) + 0.5
+    for i in range(src.shape[0]):
+        sup = max(float(sc[i]), 1.0)
+        e1 = (float(m[i, 0, 0] / nu[i]), float(m[i, 1, 0] / nu[i]))
+        e2 = (float(m[i, 0, 1] / nv[i]), float(m[i, 1, 1] / nv[i]))
+        cx = (m[i, 0, 0] * o[None, :] + m[i, 0, 1] * o[:, None]) + m[i, 0, 2]             # (S, S): [oy, ox]
+        cy = (m[i, 1, 0] * o[None, :] + m[i, 1, 1] * o[:, None]) + m[i, 1, 2]
+        bx, by = torch.floor(cx).to(torch.int64), torch.floor(cy).to(torch.int64)
+        K = int(math.ceil(math.sqrt(2.0) * sup)) + 1
+        img = src[i].to(torch.float64)
+        num = torch.zeros((S, S, 3), dtype=torch.float64)
+        den = torch.zeros((S, S), dtype=torch.float64)
+        for ky in range(-K, K + 1):                            # one pass per tap offset: (S, S) at a time, whatever s is
+            jy = by + ky
+            dy = jy.to(torch.float64) + 0.5 - cy
+            yc = jy.clamp(0, Hs - 1)
+            for kx in range(-K, K + 1):
+                jx = bx + kx
+                dx = jx.to(torch.float64) + 0.5 - cx
+                w = (1.0 - (dx * e1[0] + dy * e1[1]).abs() / sup).clamp_(min=0.0) * \
+                    (1.0 - (dx * e2[0] + dy * e2[1]).abs() / sup).clamp_(min=0.0)
+                num += w[:, :, None] * img[yc, jx.clamp(0, Ws - 1)]
+                den += w
+        out[i] = torch.floor(num / den[:, :, None] + 0.5).clamp_(0, 255).to(torch.uint8)
+    return out.reshape(lead + (S, S, 3)).to(u8.device)
+
+
+def similarity_of_boxes(boxes: Tensor, S: int) -> Tensor:
+    """Square boxes int32 (n, 4) = (y0, x0, h, w) with h == w as similarities: M = [[s, 0, x0], [0, s, y0]], s = h / S, float32
+    (n, 2, 3) where `boxes` lives.  Away from the crop's border (output rows and columns 1 .. S - 2) the warp then weighs
+    what crop_resize weighs; in the border it sees the frame outside the box, which the crop does not.  ValueError for
+    h != w."""
+    if not torch.is_tensor(boxes) or boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise TypeError('similarity_of_boxes: boxes must be an int32 tensor (n, 4) = (y0, x0, h, w)')
+    if S is None or S < 1:
+        raise ValueError('similarity_of_boxes: the output side S >= 1, got %r' % (S,))
+    if bool((boxes[:, 2] != boxes[:, 3]).any()):
+        raise ValueError('similarity_of_boxes: a similarity has one scale: square boxes (h == w) only')
+    b = boxes.to(torch.float64)
+    M = torch.zeros((boxes.shape[0], 2, 3), dtype=torch.float64, device=boxes.device)
+    M[:, 0, 0] = M[:, 1, 1] = b[:, 2] / S
+    M[:, 0, 2], M[:, 1, 2] = b[:, 1], b[:, 0]
+    return M.to(torch.float32)
+
+
+def similarity_from_landmarks(landmarks: Tensor, template: Tensor, S: Optional[int] = None) -> Tensor:
+    """The similarity that lays a template over detected landmarks: landmarks float (n, K, 2) as (x, y) in source
+    coordinates, template (K, 2) as (x, y) in coordinates of the output crop, K >= 2 -> M float32 (n, 2, 3), output to
+    source, as ops.warp_similarity_u8 takes it.  BOTH arguments use continuous coordinates in which pixel j covers [j, j + 1)
+    and has its centre at j + 0.5: a detector that reports pixel indices adds 0.5.  The template is the caller's (none is
+    shipped); with S given it must lie inside the crop [0, S]^2.
+
+    Least squares over rotation, uniform scale and translation, without reflection, closed form in float64: with p' = p -
+    mean p (template) and q' = q - mean q (landmarks), a = sum(p' . q') / sum |p'|^2, b = sum(p'x q'y - p'y q'x) / sum |p'|^2,
+    A = [[a, -b], [b, a]], t = mean q - A mean p.  ValueError for K < 2 and for a template whose points coincide."""
+    if not torch.is_tensor(landmarks) or not torch.is_tensor(template):
+        raise TypeError('similarity_from_landmarks: landmarks and template must be tensors')
+    if not landmarks.is_floating_point() or landmarks.dim() != 3 or landmarks.shape[2] != 2:
+        raise ValueError('similarity_from_landmarks: landmarks must be float (n, K, 2), got %s %s'
+                         % (landmarks.dtype, tuple(landmarks.shape)))
+    K = int(landmarks.shape[1])
+    if K < 2:
+        raise ValueError('similarity_from_landmarks: two points at least determine a similarity, got K = %d' % K)
+    if template.dim() != 2 or tuple(template.shape) != (K, 2):
+        raise ValueError('similarity_from_landmarks: the template must be (%d, 2), got %s' % (K, tuple(template.shape)))
+    p = template.detach().cpu().to(torch.float64)
+    q = landmarks.detach().cpu().to(torch.float64)
+    if not bool(torch.isfinite(p).all()) or not bool(torch.isfinite(q).all()):
+        raise ValueError('similarity_from_landmarks: every coordinate must be finite')
+    if S is not None and (bool((p < 0).any()) or bool((p > S).any())):
+        raise ValueError('similarity_from_landmarks: the template must lie inside the crop [0, %d]^2' % S)
+    pm, qm = p.mean(0), q.mean(1)
+    pc, qc = p - pm, q - qm[:, None, :]
+    den = (pc * pc).sum()
+    if float(den) <= 1e-24 * max(1.0, float((p * p).sum())):
+        raise ValueError('similarity_from_landmarks: the points of the template coincide')
+    a = (pc[None] * qc).sum(dim=(1, 2)) / den
+    b = (pc[None, :, 0] * qc[:, :, 1] - pc[None, :, 1] * qc[:, :, 0]).sum(1) / den
+    M = torch.empty((q.shape[0], 2, 3), dtype=torch.float64)
+    M[:, 0, 0], M[:, 0, 1], M[:, 1, 0], M[:, 1, 1] = a, -b, b, a
+    M[:, 0, 2] = qm[:, 0] - (a * pm[0] - b * pm[1])
+    M[:, 1, 2] = qm[:, 1] - (b * pm[0] + a * pm[1])
+    return M.to(torch.float32).to(landmarks.device)
+
+
+def similarities_of_squares(side: Tensor, angle: Tensor, cx: Tensor, cy: Tensor, mirror: Tensor, S: int) -> Tensor:
+    """The one place that writes the matrix convention down: a source square of side `side` pixels around (cx, cy), turned
+    by `angle` (radians, counter-clockwise in (x, y) with y down the frame) and mirrored where `mirror` is true, as the map of
+    an S x S crop: M = s R(angle) with s = side / S, the first column negated for a mirror, the output centre (S / 2, S / 2)
+    taken to (cx, cy).  All arguments (n,) tensors; computed in float64 -> float32 (n, 2, 3) on the host.  A side within 1e-6
+    of S / 64 or 8 S is moved inside by that much, so that the float32 rounding of s cos and s sin cannot carry sqrt |det|
+    over a limit of check_similarities (a float32 has 6e-8)."""
+    side = side.detach().cpu().to(torch.float64).clamp(S * MIN_SIMILARITY_SCALE * (1.0 + 1e-6), S * MAX_SIMILARITY_SCALE * (1.0 - 1e-6))
+    angle, cx, cy = (t.detach().cpu().to(torch.float64) for t in (angle, cx, cy))
+    sgn = torch.where(mirror.detach().cpu().to(torch.bool), -1.0, 1.0).to(torch.float64)
+    s, cos, sin = side / S, torch.cos(angle), torch.sin(angle)
+    M = torch.empty((side.shape[0], 2, 3), dtype=torch.float64)
+    M[:, 0, 0], M[:, 0, 1] = sgn * s * cos, -s * sin
+    M[:, 1, 0], M[:, 1, 1] = sgn * s * sin, s * cos
+    M[:, 0, 2] = cx - (M[:, 0, 0] + M[:, 0, 1]) * (0.5 * S)
+    M[:, 1, 2] = cy - (M[:, 1, 0] + M[:, 1, 1]) * (0.5 * S)
+    return M.to(torch.float32).contiguous()
+
+
+def random_similarities(B: int, Hs: int, Ws: int, S: int, scale=(0.5, 1.0), degrees: float = 10.0, flip_p: float = 0.5,
+                        generator: Optional[torch.Generator] = None) -> Tensor:
+    """One random similarity per clip for rotation, scale and flip augmentation in one table: the source square has the side
+    random_boxes draws for a square (area `scale`, uniform, of min(Hs, Ws) ** 2; cut to [S / 64, 8 S]), the angle is uniform
+    in [-degrees, degrees], the mirror (probability flip_p) is folded into the matrix, and the centre is uniform over the
+    positions that keep the rotated square inside the frame (the frame's centre along an axis that has none).  Returns a
+    float32 (B, 2, 3) host tensor, reproducible from `generator`.  A training step is then
+    ``model(ops.warp_similarity_u8(u8, M.to(dev), S))``: no view is needed, the flip is in M."""
+    if B < 1 or Hs < 1 or Ws < 1 or S < 1:
+        raise ValueError('random_similarities: need B, Hs, Ws, S >= 1, got B=%d Hs=%d Ws=%d S=%d' % (B, Hs, Ws, S))
+    if not (0.0 < scale[0] <= scale[1] <= 1.0):
+        raise ValueError('random_similarities: need 0 < scale[0] <= scale[1] <= 1, got %r' % (scale,))
+    if not 0.0 <= degrees <= 180.0:
+        raise ValueError('random_similarities: degrees must lie in [0, 180], got %r' % (degrees,))
+    if not 0.0 <= flip_p <= 1.0:
+        raise ValueError('random_similarities: flip_p must be a probability, got %r' % (flip_p,))
+    u = torch.rand((5, B), generator=generator, dtype=torch.float64)
+    area = (scale[0] + (scale[1] - scale[0]) * u[0]) * float(min(Hs, Ws)) ** 2
+    # cut to the scales a similarity may have; similarities_of_squares keeps a side that lands on a limit just inside it
+    side = torch.sqrt(area).round().clamp_(1, min(Hs, Ws)).clamp_(S * MIN_SIMILARITY_SCALE, S * MAX_SIMILARITY_SCALE)
+    ang = (2.0 * u[1] - 1.0) * (degrees * math.pi / 180.0)
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    half = 0.5 * side * (cos.abs() + sin.abs())                # half the bounding box of the rotated square
+    cx = torch.where(Ws - 2.0 * half > 0, half + u[2] * (Ws - 2.0 * half), torch.full_like(half, 0.5 * Ws))
+    cy = torch.where(Hs - 2.0 * half > 0, half + u[3] * (Hs - 2.0 * half), torch.full_like(half, 0.5 * Hs))
+    return similarities_of_squares(side, ang, cx, cy, u[4] < flip_p, S)

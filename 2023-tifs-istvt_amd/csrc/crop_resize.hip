@@ -15,6 +15,10 @@
 // horizontally into the tile, and the tile is filtered vertically into bytes in LDS, which leave as whole 16-byte chunks
 // where the output range allows it.  One writer per byte, no scratch, no atomics: a second run gives the same bits, and
 // the bits do not depend on R, TR or the passes (a tile row is the same sum whichever pass makes it).
+//
+// Further down: whole NV12 frames to packed RGB (DESIGN.md "NV12 frames"), and the similarity warp (DESIGN.md "Aligned
+// crops"), a second kernel over the same two sources: one 2 x 3 map per frame instead of a box, the same triangle in the
+// rotated frame of the output, in double.
 #include "u8_view.h"
 
 namespace {
@@ -333,6 +337,205 @@ static int crop_resize_launch(const Src& src, const int* boxes, void* out, int n
     return istvt_check_launch();
 }
 
+
+// ---- similarity warp (DESIGN.md "Aligned crops") ---------------------------------------------------------------------
+// One 2 x 3 map per frame, float32 M[f] = (m00 m01 m02; m10 m11 m12), takes the centre of output pixel (ox, oy) to the
+// continuous source point c = M (ox + .5, oy + .5, 1); source pixel j covers [j, j + 1).  With u = (m00, m10), v = (m01, m11),
+// e1 = u / |u|, e2 = v / |v|, s = sqrt|det|, sup = max(s, 1) and d = (jx + .5, jy + .5) - c:
+//
+//   w(jx, jy) = max(0, 1 - |d . e1| / sup) * max(0, 1 - |d . e2| / sup)
+//   value_c = sum w * frame[clamp(jy, 0, Hs - 1)][clamp(jx, 0, Ws - 1)][c] / sum w;  byte = clamp(floor(value + .5), 0, 255)
+//
+// over every integer (jx, jy): the crop's antialiased triangle in the rotated frame of the output, the border replicated.
+// Positions, weights and the four sums are double (under rotation every output pixel has its own sub-pixel phase: no
+// per-axis table exists, and float32 sums over up to ~260 taps would be good to 4e-3 only).
+//
+// Work item = (frame, output tile), 256 threads: 16 x 16 pixels with one thread each while s <= 4, 8 x 8 with four threads
+// each above (thread q takes the tap rows jy_lo + q, + 4, ...; the four are neighbouring lanes of one wave, and lane q = 0
+// adds their partial sums, fetched with shuffles, in the order of q).  The tile's footprint -- the bounding rectangle of its pixels' tap ranges, clamped into the frame, never empty
+// and never larger than WS_SPAN x WS_SPAN for a similarity with s <= 8 -- is staged once as packed RGB through the same
+// Src::fill the crop uses (an NV12 pixel is converted once per tile, not once per tap); taps read the stage at
+// coordinates clamped into that rectangle, which for a similarity is the clamp into the frame.  A block walks the tiles of
+// its frame in a strided loop: the grid does not depend on the table.  One writer per byte, no atomics, no scratch.
+//
+// The kernel's own check of an entry (a table that was not validated reads nothing it must not): every number finite,
+// 2^-6 <= s <= 8, |u| and |v| in [2^-7, 16], the image of the output centre inside [0, Ws] x [0, Hs].  An entry that fails
+// gives a frame of zeros and nothing of that frame is read.  A sheared entry that passes gives defined garbage: its tap
+// ranges follow sup and its rectangle is cut to WS_SPAN.
+constexpr int WS_SPAN = 108;               // (7 * 8 + 2 * 8) * sqrt 2 + margins = 105 at s = 8, 100 at s = 4 with 16 x 16
+constexpr int WS_RAW_PIECES = 48;          // NV12: row pieces of the raw area (31 rectangle rows per chunk)
+
+struct WarpMap {
+    double m00, m01, m02, m10, m11, m12;   // the entry
+    double g1x, g1y, g2x, g2y;             // e1 / sup, e2 / sup
+    double Rx, Ry;                         // half width of a pixel's tap range per source axis
+    double s;
+    bool ok;
+};
+
+__device__ __forceinline__ WarpMap warp_map_of(const float* __restrict__ M, long f, int Hs, int Ws, int S) {
+    WarpMap w;
+    const float* m = M + f * 6;
+    bool fin = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) fin = fin && fabsf(m[i]) <= 3.402823466e38f;     // FLT_MAX: false for NaN and the infinities
+    w.m00 = m[0], w.m01 = m[1], w.m02 = m[2], w.m10 = m[3], w.m11 = m[4], w.m12 = m[5];
+    const double det = __dsub_rn(__dmul_rn(w.m00, w.m11), __dmul_rn(w.m01, w.m10));      // the products are exact
+    w.s = __dsqrt_rn(fabs(det));
+    const double nu = __dsqrt_rn(__dadd_rn(__dmul_rn(w.m00, w.m00), __dmul_rn(w.m10, w.m10)));
+    const double nv = __dsqrt_rn(__dadd_rn(__dmul_rn(w.m01, w.m01), __dmul_rn(w.m11, w.m11)));
+    const double h = 0.5 * (double)S;
+    const double px = __dadd_rn(__dadd_rn(__dmul_rn(w.m00, h), __dmul_rn(w.m01, h)), w.m02);
+    const double py = __dadd_rn(__dadd_rn(__dmul_rn(w.m10, h), __dmul_rn(w.m11, h)), w.m12);
+    w.ok = fin && w.s >= 0.015625 && w.s <= 8.0 && nu >= 0.0078125 && nu <= 16.0 && nv >= 0.0078125 && nv <= 16.0 &&
+           px >= 0.0 && px <= (double)Ws && py >= 0.0 && py <= (double)Hs;
+    if (!w.ok) return w;
+    const double sup = w.s > 1.0 ? w.s : 1.0;
+    const double e1x = __ddiv_rn(w.m00, nu), e1y = __ddiv_rn(w.m10, nu);
+    const double e2x = __ddiv_rn(w.m01, nv), e2y = __ddiv_rn(w.m11, nv);
+    w.g1x = __ddiv_rn(e1x, sup), w.g1y = __ddiv_rn(e1y, sup);
+    w.g2x = __ddiv_rn(e2x, sup), w.g2y = __ddiv_rn(e2y, sup);
+    // |d . e1|, |d . e2| < sup puts |dx| below sup (|e1x| + |e2x|) when e1 and e2 are orthogonal; the margin covers the
+    // 1e-4 a validated table may be off, and .5 turns pixel centres into indices
+    w.Rx = sup * (fabs(e1x) + fabs(e2x)) * 1.001 + 0.51;
+    w.Ry = sup * (fabs(e1y) + fabs(e2y)) * 1.001 + 0.51;
+    return w;
+}
+
+__device__ __forceinline__ double warp_cx(const WarpMap& w, double px, double py) {
+    return __dadd_rn(__dadd_rn(__dmul_rn(w.m00, px), __dmul_rn(w.m01, py)), w.m02);
+}
+__device__ __forceinline__ double warp_cy(const WarpMap& w, double px, double py) {
+    return __dadd_rn(__dadd_rn(__dmul_rn(w.m10, px), __dmul_rn(w.m11, py)), w.m12);
+}
+
+// LDS: the frame's WarpMap (static: thread 0 works it out -- three square roots, eight divisions -- and all read it) |
+// stage[stage_bytes]: the rectangle | raw[src.raw_bytes] (NV12 only)
+template <typename Src>
+__global__ __launch_bounds__(256) void warp_similarity_kernel(const Src src, const float* __restrict__ M,
+                                                              uint8_t* __restrict__ out, int S, int G, int stage_bytes) {
+    const int Hs = src.Hs, Ws = src.Ws;
+    extern __shared__ __align__(16) unsigned char smem[];
+    unsigned char* stage = smem;
+    __shared__ WarpMap shared_map;
+
+    const int tid = threadIdx.x;
+    const long f = blockIdx.x / G;
+    const int t0 = (int)(blockIdx.x % G);
+    if (tid == 0) shared_map = warp_map_of(M, f, Hs, Ws, S);
+    __syncthreads();
+    const WarpMap w = shared_map;
+    const bool wide = w.ok && w.s > 4.0;                         // 8 x 8 tiles, four threads per pixel
+    const int P = wide ? 8 : 16, Q = wide ? 4 : 1;
+    const int tp = (S + P - 1) / P;
+    const int pid = tid / Q, q = tid - pid * Q;
+    const int ly = pid / P, lx = pid - ly * P;
+    uint8_t* const obase = out + f * (long)S * S * 3;
+
+    for (int t = t0; t < tp * tp; t += G) {
+        const int ty = t / tp, tx = t - ty * tp;
+        const int ox0 = tx * P, oy0 = ty * P;
+        const int ox = ox0 + lx, oy = oy0 + ly;
+        const bool live = ox < S && oy < S;
+        if (!w.ok) {
+            if (live) {
+                uint8_t* o = obase + ((long)oy * S + ox) * 3;
+                o[0] = 0, o[1] = 0, o[2] = 0;
+            }
+            continue;
+        }
+        // the rectangle: the map is affine, so the centres of the tile's corner pixels bound those of all its pixels
+        const double xa = (double)ox0 + 0.5, xb = (double)min(ox0 + P, S) - 0.5;
+        const double ya = (double)oy0 + 0.5, yb = (double)min(oy0 + P, S) - 0.5;
+        const double c0 = warp_cx(w, xa, ya), c1 = warp_cx(w, xb, ya), c2 = warp_cx(w, xa, yb), c3 = warp_cx(w, xb, yb);
+        const double r0 = warp_cy(w, xa, ya), r1 = warp_cy(w, xb, ya), r2 = warp_cy(w, xa, yb), r3 = warp_cy(w, xb, yb);
+        const int x_lo = (int)floor(fmin(fmin(c0, c1), fmin(c2, c3)) - w.Rx);
+        const int x_hi = (int)floor(fmax(fmax(c0, c1), fmax(c2, c3)) + w.Rx);
+        const int y_lo = (int)floor(fmin(fmin(r0, r1), fmin(r2, r3)) - w.Ry);
+        const int y_hi = (int)floor(fmax(fmax(r0, r1), fmax(r2, r3)) + w.Ry);
+        CropBox b;
+        b.x0 = min(max(x_lo, 0), Ws - 1);
+        b.y0 = min(max(y_lo, 0), Hs - 1);
+        b.w = min(min(max(x_hi, 0), Ws - 1) - b.x0 + 1, WS_SPAN);
+        b.h = min(min(max(y_hi, 0), Hs - 1) - b.y0 + 1, WS_SPAN);
+
+        const int pitch = u8_row_pitch(b.w), rstride = src.lead_stride();
+        const int CH = src.chunk_rows(stage_bytes, pitch, b.w);  // the host sizes the stage for WS_SPAN widest rows
+        int lead0 = 0;
+        for (int s0 = 0; s0 < b.h; s0 += CH) {
+            const int l = src.fill(f, b, s0, min(CH, b.h - s0), stage + s0 * pitch, pitch, stage + stage_bytes, tid);
+            if (s0 == 0) lead0 = l;
+            __syncthreads();                                     // the next chunk converts from the same raw area
+        }
+
+        double sw = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        if (live) {
+            const double cx = warp_cx(w, (double)ox + 0.5, (double)oy + 0.5);
+            const double cy = warp_cy(w, (double)ox + 0.5, (double)oy + 0.5);
+            const int jx_lo = (int)floor(cx - w.Rx), jx_hi = (int)floor(cx + w.Rx);
+            const int jy_lo = (int)floor(cy - w.Ry), jy_hi = (int)floor(cy + w.Ry);
+            const int xe = b.x0 + b.w - 1, ye = b.y0 + b.h - 1;
+            for (int jy = jy_lo + q; jy <= jy_hi; jy += Q) {
+                const int sy = min(max(jy, b.y0), ye) - b.y0;
+                const unsigned char* row = stage + sy * pitch + u8_row_lead(lead0, sy, rstride);
+                const double dy = __dsub_rn((double)jy + 0.5, cy);
+                const double ay = __dmul_rn(dy, w.g1y), by = __dmul_rn(dy, w.g2y);
+                for (int jx = jx_lo; jx <= jx_hi; ++jx) {
+                    const double dx = __dsub_rn((double)jx + 0.5, cx);
+                    const double wa = 1.0 - fabs(__fma_rn(dx, w.g1x, ay));
+                    const double wb = 1.0 - fabs(__fma_rn(dx, w.g2x, by));
+                    if (wa <= 0.0 || wb <= 0.0) continue;
+                    const double wt = __dmul_rn(wa, wb);
+                    const unsigned char* p = row + (min(max(jx, b.x0), xe) - b.x0) * 3;
+                    sw = __dadd_rn(sw, wt);
+                    a0 = __fma_rn(wt, (double)p[0], a0);
+                    a1 = __fma_rn(wt, (double)p[1], a1);
+                    a2 = __fma_rn(wt, (double)p[2], a2);
+                }
+            }
+        }
+        if (Q == 4) {                                            // every lane shuffles; what lanes q != 0 get is not used
+            const double own[4] = {sw, a0, a1, a2};
+#pragma unroll
+            for (int k = 1; k < 4; ++k) {                        // the sums of lane q = k, fetched from the lanes' own values
+                sw = __dadd_rn(sw, __shfl_down(own[0], k));
+                a0 = __dadd_rn(a0, __shfl_down(own[1], k));
+                a1 = __dadd_rn(a1, __shfl_down(own[2], k));
+                a2 = __dadd_rn(a2, __shfl_down(own[3], k));
+            }
+        }
+        if (live && q == 0) {
+            uint8_t* o = obase + ((long)oy * S + ox) * 3;
+            const double acc[3] = {a0, a1, a2};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double v = sw > 0.0 ? __ddiv_rn(acc[c], sw) : 0.0;
+                o[c] = (uint8_t)(int)fmin(fmax(floor(v + 0.5), 0.0), 255.0);
+            }
+        }
+        __syncthreads();                                         // the next tile stages over these bytes
+    }
+}
+
+static int src_raw_bytes(const RgbSource&) { return 0; }
+static int src_raw_bytes(const Nv12Source& s) { return s.raw_bytes; }
+
+// The launch both warp entries share: n * G blocks, G = the 16 x 16 tiles of an output.  LDS: a stage of min(Hs, WS_SPAN)
+// rows of min(Ws, WS_SPAN) pixels (at most 37.1 KiB) and the source's raw area, next to the kernel's static WarpMap.
+template <typename Src>
+static int warp_similarity_launch(const Src& src, const float* M, void* out, int n, int S, hipStream_t stream) {
+    const int wcap = src.Ws < WS_SPAN ? src.Ws : WS_SPAN, hcap = src.Hs < WS_SPAN ? src.Hs : WS_SPAN;
+    const int stage_bytes = hcap * u8_row_pitch(wcap);
+    const long lds = (long)stage_bytes + src_raw_bytes(src);
+    const int tp = (S + 15) / 16;
+    const int G = tp * tp;
+    const long nblocks = (long)n * G;
+    if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    hipLaunchKernelGGL(warp_similarity_kernel<Src>, dim3((unsigned)nblocks), dim3(256), (size_t)lds, stream, src, M,
+                       (uint8_t*)out, S, G, stage_bytes);
+    return istvt_check_launch();
+}
+
 }  // namespace
 
 // frames uint8 [n][Hs][Ws][3] (total bytes readable at frames; no alignment needed), boxes int32 [n][4] = (y0, x0, h, w)
@@ -379,4 +582,27 @@ extern "C" int istvt_nv12_to_rgb_u8(const void* frames, long total, int Hs, int 
     if (nblocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
     hipLaunchKernelGGL(nv12_to_rgb_u8_kernel, dim3((unsigned)nblocks), dim3(256), 0, stream, src, (uint8_t*)out, tiles);
     return istvt_check_launch();
+}
+
+// Similarity warp: frames as istvt_crop_resize_u8 takes them, M float32 [n][2][3] on the device (the map of every frame, as
+// the comment above warp_similarity_kernel defines it) -> out uint8 [n][S][S][3].  An entry that fails the kernel's check
+// gives zeros.
+extern "C" int istvt_warp_similarity_u8(const void* frames, long total, int Hs, int Ws, const float* M, void* out, int n,
+                                        int S, hipStream_t stream) {
+    if (n <= 0 || S < 1 || S > 4096 || !frames || !M || !out) return ISTVT_ERR_SHAPE;
+    if (Hs < 1 || Ws < 1 || Hs > 16384 || Ws > 16384) return ISTVT_ERR_SHAPE;
+    if (total < (long)n * Hs * Ws * 3) return ISTVT_ERR_SHAPE;
+    return warp_similarity_launch(RgbSource{(const uint8_t*)frames, total, Hs, Ws}, M, out, n, S, stream);
+}
+
+// The same from NV12 frames as istvt_crop_resize_nv12 takes them: the bits of istvt_warp_similarity_u8 on
+// istvt_nv12_to_rgb_u8's frames, which are never made.  The raw area holds WS_RAW_PIECES row pieces of the widest rectangle.
+extern "C" int istvt_warp_similarity_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride,
+                                          const int* coef, const float* M, void* out, int n, int S, hipStream_t stream) {
+    if (S < 1 || S > 4096 || !M || !out) return ISTVT_ERR_SHAPE;
+    Nv12Source src;
+    const int rc = nv12_source_of(frames, total, Hs, Ws, pitch, fstride, n, coef, &src);
+    if (rc != ISTVT_OK) return rc;
+    src.raw_bytes = WS_RAW_PIECES * nv12_raw_pitch(Ws < WS_SPAN ? Ws : WS_SPAN);
+    return warp_similarity_launch(src, M, out, n, S, stream);
 }

@@ -239,28 +239,29 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import explain
         return explain.relevance(self, x, index)
 
-    def score_video(self, frames, boxes=None, **kw):
+    def score_video(self, frames, boxes=None, transforms=None, **kw):
         """Sliding-window scores of one video, uint8 (N, S, S, 3) frames or normalised float (N, 3, S, S), or whole uint8
         frames (N, Hs, Ws, 3) with one face box (y0, x0, h, w) each in `boxes`, int32 (N, 4):
         istvt_amd.video.VideoScorer(self, **kw).score(frames, boxes).  jpeg_quality=q (1..100) among the keywords scores the
         crops as a JPEG codec would hand them back at that quality (ops.jpeg_roundtrip_u8); pixel_format='nv12' (with
         yuv_matrix='bt601' | 'bt709' | 'jfif') takes NV12 frames uint8 (N, 3 * Hs / 2, Ws) and needs boxes; score_videos and
-        explain_video take both too."""
+        explain_video take both too.  transforms= stands in the boxes' place (never both): one similarity per frame, float32
+        (N, 2, 3), for aligned crops (ops.warp_similarity_u8; clips.similarity_from_landmarks makes them)."""
         from istvt_amd import video
-        return video.VideoScorer(self, **kw).score(frames, boxes=boxes)
+        return video.VideoScorer(self, **kw).score(frames, boxes=boxes, transforms=transforms)
 
-    def score_videos(self, videos, boxes=None, labels=None, **kw):
+    def score_videos(self, videos, boxes=None, labels=None, transforms=None, **kw):
         """Sliding-window scores of a set of videos in one pass (a list of tensors as score_video takes them, one box table
         per video in `boxes`), with accuracy counts and the AUC over the set when `labels` gives one 0 / 1 per video:
         istvt_amd.video.VideoScorer(self, **kw).score_videos(videos, boxes, labels)"""
         from istvt_amd import video
-        return video.VideoScorer(self, **kw).score_videos(videos, boxes=boxes, labels=labels)
+        return video.VideoScorer(self, **kw).score_videos(videos, boxes=boxes, labels=labels, transforms=transforms)
 
-    def explain_video(self, frames, index=0, boxes=None, **kw):
+    def explain_video(self, frames, index=0, boxes=None, transforms=None, **kw):
         """Per-frame relevance maps of one video (frames and boxes as score_video takes them) for output `index`:
         istvt_amd.video.VideoScorer(self, **kw).explain(frames, index, boxes)"""
         from istvt_amd import video
-        return video.VideoScorer(self, **kw).explain(frames, index, boxes=boxes)
+        return video.VideoScorer(self, **kw).explain(frames, index, boxes=boxes, transforms=transforms)
 
     def set_crop_side(self, S):
         """The side S of the crops a view cuts out of larger uint8 source frames.  A token grid does not name it (sixteen

@@ -1120,6 +1120,79 @@ def crop_resize_nv12(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709
     return out
 
 
+def _frame_similarities(what: str, frames: Tensor, M: Tensor, n: int, T: Optional[int], Hs: int, Ws: int, S: int,
+                        checked: bool) -> Tensor:
+    """the device table of the two warps, one 2 x 3 map for each of the n frames: a checked table as it is, or the host table
+    validated (clips.check_similarities), spread over the T frames of a clip (T None: frames, not clips) and uploaded"""
+    from . import clips
+    if checked:
+        if M.dtype != torch.float32 or tuple(M.shape) != (n, 2, 3) or M.device != frames.device:
+            raise RuntimeError('%s: a checked table of similarities is float32 (%d, 2, 3) on %s' % (what, n, frames.device))
+        return _c(M)
+    m = clips.check_similarities(M, frames.shape[0], Hs, Ws, S)
+    if T is not None:
+        m = clips.per_frame_similarities(m, T)
+    return m.contiguous().to(frames.device)
+
+
+def warp_similarity_u8(frames: Tensor, M: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
+    """Aligned crops (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, M float32 [n,2,3] per frame or, for
+    clips, [B,2,3] spread over the T frames of a clip: the similarity that takes the centre of an output pixel to source
+    coordinates (pixel j covers [j, j + 1)) -> uint8 [n,S,S,3] / [B,T,S,S,3], every frame resampled through its map with the
+    antialiased triangle of clips.warp_similarity_host, the border replicated.  The table is validated on the host
+    (clips.check_similarities) before any launch and then uploaded; checked=True takes a per-frame device table the caller
+    has validated already (an entry the kernel itself refuses gives a frame of zeros).  `out` (uint8, contiguous, of the
+    result's shape) is written when given."""
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('warp_similarity_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
+        raise RuntimeError('warp_similarity_u8 expects channels-last (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3) uint8 input, got %s'
+                           % (tuple(frames.shape),))
+    if frames.numel() == 0:
+        raise RuntimeError('warp_similarity_u8: empty input %s' % (tuple(frames.shape),))
+    S = int(S)
+    lead = tuple(frames.shape[:-3])
+    Hs, Ws = frames.shape[-3], frames.shape[-2]
+    if S < 1 or S > 480:
+        raise ValueError('warp_similarity_u8: the output side must lie in [1, 480], got %d' % S)
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('warp_similarity_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
+    src = _c(frames).view((-1, Hs, Ws, 3))
+    n = src.shape[0]
+    mdev = _frame_similarities('warp_similarity_u8', frames, M, n, frames.shape[1] if frames.dim() == 5 else None, Hs, Ws, S,
+                               checked)
+    out = _u8_out('warp_similarity_u8', frames, lead + (S, S, 3), out)
+    with prof('warp_similarity_u8', n * S * S * 3):    # + the footprints' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_warp_similarity_u8(src.data_ptr(), src.numel(), Hs, Ws, mdev.data_ptr(), out.data_ptr(), n,
+                                                       S, _stream()), 'istvt_warp_similarity_u8')
+    return out
+
+
+def warp_similarity_nv12(frames: Tensor, M: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
+                         checked: bool = False) -> Tensor:
+    """warp_similarity_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device
+    (pitch and frame stride from the tensor's strides, as crop_resize_nv12 takes them), M, S, `out` and `checked` as
+    warp_similarity_u8 takes them, the maps in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] / [B, T, S, S, 3]: the bits of
+    warp_similarity_u8(nv12_to_rgb_u8(frames, matrix), M, S) without the RGB frames -- a source pixel is converted once per
+    output tile, inside the warp kernel."""
+    Hs, Ws, coef, launches = _nv12_source('warp_similarity_nv12', frames, matrix)
+    S = int(S)
+    if S < 1 or S > 480:
+        raise ValueError('warp_similarity_nv12: the output side must lie in [1, 480], got %d' % S)
+    n = frames.numel() // (frames.shape[-2] * frames.shape[-1])
+    mdev = _frame_similarities('warp_similarity_nv12', frames, M, n, frames.shape[1] if frames.dim() == 4 else None, Hs, Ws, S,
+                               checked)
+    out = _u8_out('warp_similarity_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
+    flat = out.view((-1, S, S, 3))
+    for t, ptr, total, pitch, fs, first, k in launches:
+        with prof('warp_similarity_nv12', k * S * S * 3):
+            _lib.check(_lib.lib().istvt_warp_similarity_nv12(ptr, total, Hs, Ws, pitch, fs, coef,
+                                                             mdev[first:first + k].data_ptr(), flat[first:first + k].data_ptr(), k,
+                                                             S, _stream()), 'istvt_warp_similarity_nv12')
+    return out
+
+
 def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
                       checked: bool = False) -> Tensor:
     """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for

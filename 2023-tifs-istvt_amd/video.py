@@ -6,6 +6,8 @@ video out.
     ex = scorer.explain(frames)                      # the same windows through the relevance rollout, fused per frame
     res = scorer.score(full, boxes=boxes)            # whole frames uint8 (N, Hs, Ws, 3) and one face box per frame, int32
                                                      # (N, 4) = (y0, x0, h, w): cropped and resized on the device
+    res = scorer.score(full, transforms=M)           # or one similarity per frame, float32 (N, 2, 3): aligned crops
+                                                     # (ops.warp_similarity_u8), e.g. clips.similarity_from_landmarks
     scorer.reset()
     for chunk in stream:                             # the same windows, as the frames arrive
         logits, starts = scorer.push(chunk)
@@ -71,25 +73,40 @@ def check_frames(frames) -> str:
     raise ValueError('frames must be uint8 or float32, got %s' % frames.dtype)
 
 
-def check_boxed_frames(frames, boxes, side: Optional[int], pixel_format: str = 'rgb24'):
-    """Whole frames with one face box each (DESIGN.md "Frames and boxes"): frames uint8 (N, Hs, Ws, 3) of any size, boxes
-    int32 (N, 4) = (y0, x0, h, w) inside the frame with 1 <= h, w <= 8 side.  pixel_format 'nv12' (DESIGN.md "NV12 frames"):
-    frames uint8 (N, 3 * Hs / 2, Ws), the boxes in pixels of the Hs x Ws picture.  -> the validated box table on the host."""
+def _whole_frames(frames, side: Optional[int], pixel_format: str, word: str):
+    """(N, Hs, Ws) of whole frames that a table of `word` ('boxes' or 'transforms') cuts crops of side `side` from: uint8
+    (N, Hs, Ws, 3), or NV12 uint8 (N, 3 * Hs / 2, Ws); ValueError otherwise"""
     from . import clips
     if side is None:
-        raise ValueError('boxes need the side of the crops: VideoScorer(model, side=S) or model.set_crop_side(S)')
+        raise ValueError('%s need the side of the crops: VideoScorer(model, side=S) or model.set_crop_side(S)' % word)
     if not torch.is_tensor(frames):
         raise ValueError('frames must be a torch tensor, got %s' % type(frames).__name__)
     if pixel_format == 'nv12':
         if frames.dtype != torch.uint8 or frames.dim() != 3:
             raise ValueError('NV12 frames must be uint8 (N, 3 * Hs / 2, Ws) as a decoder delivers them, got %s %s'
                              % (frames.dtype, tuple(frames.shape)))
-        Hs, Ws = clips.check_nv12(frames)
-        return clips.check_boxes(boxes, int(frames.shape[0]), Hs, Ws, int(side))
+        return (int(frames.shape[0]),) + clips.check_nv12(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-        raise ValueError('with boxes, frames must be uint8 channels-last (N, Hs, Ws, 3) as a decoder delivers them, got %s %s'
-                         % (frames.dtype, tuple(frames.shape)))
-    return clips.check_boxes(boxes, int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2]), int(side))
+        raise ValueError('with %s, frames must be uint8 channels-last (N, Hs, Ws, 3) as a decoder delivers them, got %s %s'
+                         % (word, frames.dtype, tuple(frames.shape)))
+    return int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+
+
+def check_boxed_frames(frames, boxes, side: Optional[int], pixel_format: str = 'rgb24'):
+    """Whole frames with one face box each (DESIGN.md "Frames and boxes"): frames uint8 (N, Hs, Ws, 3) of any size, boxes
+    int32 (N, 4) = (y0, x0, h, w) inside the frame with 1 <= h, w <= 8 side.  pixel_format 'nv12' (DESIGN.md "NV12 frames"):
+    frames uint8 (N, 3 * Hs / 2, Ws), the boxes in pixels of the Hs x Ws picture.  -> the validated box table on the host."""
+    from . import clips
+    n, Hs, Ws = _whole_frames(frames, side, pixel_format, 'boxes')
+    return clips.check_boxes(boxes, n, Hs, Ws, int(side))
+
+
+def check_aligned_frames(frames, transforms, side: Optional[int], pixel_format: str = 'rgb24'):
+    """Whole frames with one similarity each (DESIGN.md "Aligned crops"): frames as check_boxed_frames takes them, transforms
+    float32 (N, 2, 3) as clips.check_similarities validates them.  -> the validated table on the host."""
+    from . import clips
+    n, Hs, Ws = _whole_frames(frames, side, pixel_format, 'transforms')
+    return clips.check_similarities(transforms, n, Hs, Ws, int(side))
 
 
 class Step(NamedTuple):
@@ -405,9 +422,12 @@ def set_metrics_ref(scores, labels, threshold: float = 0.0) -> dict:
 class VideoInput(NamedTuple):
     """What a call hands over for one video (VideoScorer._input)."""
     reads: str                 # what the stem reads: 'u8' decoded bytes, 'f32' normalised floats
-    boxed: bool                # whole frames with one box each: every stem batch is cropped to side x side first
+    boxed: bool                # whole frames with one box or one similarity each: every stem batch is cropped to side x
+                               # side first
     side: Optional[int]        # the side of those crops (None without boxes)
-    boxes: Optional[Tensor]    # the validated box table on the host, int32 (N, 4) (None without boxes)
+    table: Optional[Tensor]    # the validated table on the host: boxes int32 (N, 4), or similarities float32 (N, 2, 3) when
+                               # `aligned` (None without either)
+    aligned: bool = False      # the crops are cut through similarities (ops.warp_similarity_*), not boxes
 
 
 def slot_runs(slots: Sequence[int]) -> List[Tuple[int, int]]:
@@ -470,6 +490,11 @@ class VideoScorer:
                   the NV12 bytes itself (ops.crop_resize_nv12): the bits of the 'rgb24' scorer on
                   ops.crop_resize_nv12(frames, boxes, side, yuv_matrix), and everything after the crop is the same code.
     yuv_matrix    'bt601', 'bt709' (limited range) or 'jfif' (full range): how 'nv12' frames become RGB.
+
+    Every call that takes `boxes` takes `transforms` in their place (never both: ValueError): one similarity per frame,
+    float32 (N, 2, 3), output pixel centres to source coordinates (clips.check_similarities).  The crops are then
+    ops.warp_similarity_u8(frames, transforms, side) -- ops.warp_similarity_nv12 for 'nv12' frames -- and everything after the
+    crop is the same code; explain() gives its maps in crop coordinates.
     """
 
     def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
@@ -515,8 +540,14 @@ class VideoScorer:
             raise RuntimeError('VideoScorer: the model must be on a ROCm device (no CPU fallback exists for the ISTVT hot path)')
         return dev
 
-    def _input(self, frames, boxes) -> VideoInput:
-        """The frames (and boxes) of one video, checked: every argument error of a call, before anything is launched."""
+    def _input(self, frames, boxes, transforms=None) -> VideoInput:
+        """The frames (and boxes or transforms) of one video, checked: every argument error of a call, before anything is
+        launched."""
+        if boxes is not None and transforms is not None:
+            raise ValueError('VideoScorer: boxes and transforms are two ways to cut the same crop: pass one of them')
+        if transforms is not None:
+            side = self.side if self.side is not None else getattr(self.model, 'crop_side', None)
+            return VideoInput('u8', True, side, check_aligned_frames(frames, transforms, side, self.pixel_format), True)
         if boxes is None and self.pixel_format == 'rgb24':
             reads = check_frames(frames)
             if self.jpeg_quality is not None and reads == 'f32':
@@ -524,22 +555,25 @@ class VideoScorer:
                                 'take it')
             return VideoInput(reads, False, None, None)
         if boxes is None:
-            raise ValueError("VideoScorer: pixel_format='nv12' needs boxes with every call (one (y0, x0, h, w) per frame; "
-                             'frames that already are the crops take identity boxes)')
+            raise ValueError("VideoScorer: pixel_format='nv12' needs boxes or transforms with every call (one (y0, x0, h, w) or "
+                             'one similarity per frame; frames that already are the crops take identity boxes)')
         side = self.side if self.side is not None else getattr(self.model, 'crop_side', None)
         return VideoInput('u8', True, side, check_boxed_frames(frames, boxes, side, self.pixel_format))
 
     def _fetcher(self, videos, inputs: Sequence[VideoInput], pieces, dev):
         """-> fetch(first, count), the stem batch of frames [first, first + count) of the executor's steps;
-        pieces(first, count) names them as (video, lo, hi).  The box tables are uploaded here, once."""
-        bdev = [i.boxes.contiguous().to(dev, non_blocking=True) for i in inputs] if inputs[0].boxed else None
-        return lambda first, count: self._frame_batch(videos, pieces(first, count), bdev, inputs[0].side, dev)
+        pieces(first, count) names them as (video, lo, hi).  The tables are uploaded here, once.  The inputs of one call are
+        all of one kind (_check_set and _input see to it: boxes for every video, transforms for every video, or neither), so
+        the first one speaks for the set."""
+        bdev = [i.table.contiguous().to(dev, non_blocking=True) for i in inputs] if inputs[0].boxed else None
+        return lambda first, count: self._frame_batch(videos, pieces(first, count), bdev, inputs[0].side, dev,
+                                                      inputs[0].aligned)
 
-    def _frame_batch(self, videos, pieces, bdev, side, dev) -> Tensor:
+    def _frame_batch(self, videos, pieces, bdev, side, dev, aligned: bool = False) -> Tensor:
         """One stem batch from (video, lo, hi) pieces.  Without boxes a single piece is used where it lies (_stem uploads a
         host batch); several are copied into one staging batch on the device (host pieces pinned first).  With boxes (bdev:
         one validated device table per video) every piece is cropped into its slice of one batch of side x side crops, from
-        NV12 or packed RGB as the scorer's pixel_format says."""
+        NV12 or packed RGB as the scorer's pixel_format says; `aligned`: the tables hold similarities and the crops are warps."""
         if bdev is None and len(pieces) == 1:
             v, lo, hi = pieces[0]
             return videos[v][lo:hi]
@@ -554,6 +588,11 @@ class VideoScorer:
                 x = x.contiguous().pin_memory()
             if bdev is None:
                 out.copy_(x, non_blocking=True)
+            elif aligned and self.pixel_format == 'nv12':
+                ops.warp_similarity_nv12(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, self.yuv_matrix, out=out,
+                                         checked=True)
+            elif aligned:
+                ops.warp_similarity_u8(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, out=out, checked=True)
             elif self.pixel_format == 'nv12':
                 ops.crop_resize_nv12(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, self.yuv_matrix, out=out, checked=True)
             else:
@@ -624,20 +663,22 @@ class VideoScorer:
         self._kind: Optional[VideoInput] = None            # what the stream's first push handed over
         return self
 
-    def push(self, frames: Tensor, boxes=None):
+    def push(self, frames: Tensor, boxes=None, transforms=None):
         """The next frames of the stream -> (logits (W, num_classes) float32 on the device, starts (W,) int64 on the host)
         of the windows these frames complete, in stream order: with flush(), the windows of score() on the concatenation.
-        boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); a stream keeps one mode."""
-        inp = self._input(frames, boxes)
-        if self._kind is not None and inp.boxed != self._kind.boxed:
-            raise ValueError('VideoScorer: a stream takes boxes with every push or with none (reset() starts a new one)')
+        boxes: one (y0, x0, h, w) per frame of this push, for whole frames uint8 (k, Hs, Ws, 3); transforms: one similarity per
+        frame in their place; a stream keeps one mode."""
+        inp = self._input(frames, boxes, transforms)
+        if self._kind is not None and (inp.boxed != self._kind.boxed or inp.aligned != self._kind.aligned):
+            raise ValueError('VideoScorer: a stream takes boxes with every push, transforms with every push, or neither '
+                             '(reset() starts a new one)')
         if self._kind is not None and inp.reads != self._kind.reads:
             raise ValueError('VideoScorer: a stream is either uint8 or float frames, not both (reset() starts a new one)')
         dev = self._device()
         if self._plan is None:
             cap = self.capacity if self.capacity is not None else -(-(self.T + self.frame_batch) // 8) * 8
             self._plan = RingPlan(self.T, self.stride, cap, self.frame_batch, self.window_batch)
-        self._kind = inp._replace(boxes=None)
+        self._kind = inp._replace(table=None)
         base = self._plan.seen
         fetch = self._fetcher([frames], [inp], lambda first, count: [(0, first - base, first - base + count)], dev)
         self._ring, logits, starts = self._execute(self._plan.push(int(frames.shape[0])), self._ring, self._plan.capacity, dev,
@@ -653,9 +694,9 @@ class VideoScorer:
         return logits, torch.tensor(starts, dtype=torch.int64)
 
     # ---------------------------------------------------------------------------------------- whole video
-    def _whole_video(self, frames: Tensor, rollout=None, boxes=None):
+    def _whole_video(self, frames: Tensor, rollout=None, boxes=None, transforms=None):
         """every window of one video, on a plan and a bank of its own -> (logits, list of starts, device)"""
-        inp = self._input(frames, boxes)
+        inp = self._input(frames, boxes, transforms)
         n = int(frames.shape[0])
         if n < self.T:
             raise ValueError('a video of %d frames is shorter than one window of %d' % (n, self.T))
@@ -672,21 +713,22 @@ class VideoScorer:
         return VideoScore(logits, torch.tensor(starts, dtype=torch.int64).to(dev, non_blocking=True), logits.mean(0),
                           torch.sigmoid(logits).mean(0))
 
-    def score(self, frames: Tensor, boxes=None) -> VideoScore:
+    def score(self, frames: Tensor, boxes=None, transforms=None) -> VideoScore:
         """All windows of one video.  Does not disturb a stream in progress (it never touches the stream's state).  boxes: one
         (y0, x0, h, w) per frame, int32 (N, 4), for whole frames uint8 (N, Hs, Ws, 3): each stem batch is cropped and resized
-        to side x side on the device (ops.crop_resize_u8) just before the stem -- the bits of score() on those crops."""
-        logits, starts, dev = self._whole_video(frames, boxes=boxes)
+        to side x side on the device (ops.crop_resize_u8) just before the stem -- the bits of score() on those crops.  transforms: one similarity per
+        frame, float32 (N, 2, 3), in the boxes' place: the crops are ops.warp_similarity_u8(frames, transforms, side)."""
+        logits, starts, dev = self._whole_video(frames, boxes=boxes, transforms=transforms)
         res = self._video_score(logits, starts, dev)
         torch.cuda.current_stream(dev).synchronize()
         return res
 
-    def explain(self, frames: Tensor, index: int = 0, boxes=None) -> VideoExplanation:
+    def explain(self, frames: Tensor, index: int = 0, boxes=None, transforms=None) -> VideoExplanation:
         """Relevance maps of one video for output `index` (DESIGN.md "Explaining whole videos"): the windows, frames and
         stem pass of score(), every window batch through the gradient-weighted attention rollout of explain.relevance
         instead of the plain forward, and the windows' maps fused per frame (ops.relevance_fuse_windows).  The model is in
         explain.relevance's state for the call and comes back as it was; a stream in progress is not disturbed.  With
-        boxes (as score() takes them) the maps are in crop coordinates."""
+        boxes or transforms (as score() takes them) the maps are in crop coordinates."""
         from . import explain as _explain
         vit = self.model.vit
         rels = []
@@ -696,7 +738,7 @@ class VideoScorer:
             return rels[-1].logits
 
         with _explain._explaining(self.model):
-            logits, starts, dev = self._whole_video(frames, rollout, boxes)
+            logits, starts, dev = self._whole_video(frames, rollout, boxes, transforms)
             windows = _explain.Relevance(torch.cat([r.r_s for r in rels]), torch.cat([r.r_t for r in rels]), logits)
             fused = ops.relevance_fuse_windows(windows.r_s, windows.r_t, logits, starts, int(frames.shape[0]), index)
         res = VideoExplanation(self._video_score(logits, starts, dev), windows, *fused)
@@ -704,10 +746,17 @@ class VideoScorer:
         return res
 
     # ---------------------------------------------------------------------------------------- a set of videos
-    def _check_set(self, videos, boxes) -> List[VideoInput]:
-        """-> every video's VideoInput; every ValueError of a call about its videos and boxes, before anything is launched"""
+    def _check_set(self, videos, boxes, transforms=None) -> List[VideoInput]:
+        """-> every video's VideoInput; every ValueError of a call about its videos and boxes (or transforms), before anything
+        is launched"""
         if torch.is_tensor(videos) or not isinstance(videos, (list, tuple)) or len(videos) == 0:
             raise ValueError('videos: a non-empty list of frame tensors expected, got %s' % type(videos).__name__)
+        if boxes is not None and transforms is not None:
+            raise ValueError('VideoScorer: boxes and transforms are two ways to cut the same crop: pass one of them')
+        if transforms is not None:
+            if not isinstance(transforms, (list, tuple)) or len(transforms) != len(videos) or any(t is None for t in transforms):
+                raise ValueError('transforms: one table per video expected (%d)' % len(videos))
+            return [self._input(v, None, t) for v, t in zip(videos, transforms)]
         if boxes is None:
             inputs = [self._input(v, None) for v in videos]
             if len({i.reads for i in inputs}) != 1:
@@ -721,14 +770,14 @@ class VideoScorer:
             raise ValueError('boxes: one table per video expected (%d)' % len(videos))
         return [self._input(v, b) for v, b in zip(videos, boxes)]
 
-    def score_videos(self, videos, boxes=None, labels=None) -> VideoSetScore:
+    def score_videos(self, videos, boxes=None, labels=None, transforms=None) -> VideoSetScore:
         """All windows of a set of videos in one pass (DESIGN.md "Scoring a set of videos"): the windows of score(video) for
         every video, but stem batches and window batches are assembled across the videos (SetPlan), the per-video means are
         one kernel (ops.windows_reduce), and the call synchronises once.  videos: a list of tensors as score() takes them --
         all uint8 or all float, one crop side, host or device in any mix.  boxes: one table per video, for whole uint8
-        frames; each video may have its own frame size.  labels: one 0 / 1 per video -> metrics = set_metrics(logit_mean[:, 0],
+        frames; each video may have its own frame size.  transforms: one table of similarities per video in the boxes' place.  labels: one 0 / 1 per video -> metrics = set_metrics(logit_mean[:, 0],
         labels).  A stream in progress is not disturbed."""
-        inputs = self._check_set(videos, boxes)
+        inputs = self._check_set(videos, boxes, transforms)
         plan = SetPlan([int(v.shape[0]) for v in videos], self.T, self.stride, self.cover_tail, self.frame_batch,
                        self.window_batch, self.capacity)
         V = len(videos)

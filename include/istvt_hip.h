@@ -320,6 +320,19 @@ int istvt_nv12_to_rgb_u8(const void* frames, long total, int Hs, int Ws, long pi
                          int n, istvt_stream_t stream);
 int istvt_crop_resize_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
                            const int* boxes, void* out, int n, int S, istvt_stream_t stream);
+/* Similarity warp (aligned crops): frames as istvt_crop_resize_u8 / istvt_crop_resize_nv12 take them, M float32 [n][2][3] on
+ * the device -> out uint8 [n][S][S][3].  M[f] takes the centre of output pixel (ox, oy) to the continuous source point
+ * c = M[f] (ox + .5, oy + .5, 1), source pixel j covering [j, j + 1).  With u = (m00, m10), v = (m01, m11), e1 = u / |u|,
+ * e2 = v / |v|, s = sqrt|det|, sup = max(s, 1) and d = (jx + .5, jy + .5) - c, over every integer (jx, jy):
+ * w = max(0, 1 - |d . e1| / sup) * max(0, 1 - |d . e2| / sup), value = sum w * frame[clamp(jy)][clamp(jx)] / sum w in double,
+ * byte = clamp(floor(value + .5), 0, 255): the crop's antialiased triangle in the rotated frame of the output, the border
+ * replicated.  An entry with a non-finite number, s outside [2^-6, 8], |u| or |v| outside [2^-7, 16] or the image of the
+ * output centre (S / 2, S / 2) outside [0, Ws] x [0, Hs] gives a frame of zeros and reads nothing of its frame.
+ * istvt_warp_similarity_nv12: the bits of istvt_warp_similarity_u8 on istvt_nv12_to_rgb_u8's frames, without making them. */
+int istvt_warp_similarity_u8(const void* frames, long total, int Hs, int Ws, const float* M, void* out, int n, int S,
+                             istvt_stream_t stream);
+int istvt_warp_similarity_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
+                               const float* M, void* out, int n, int S, istvt_stream_t stream);
 /* JPEG round trip: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), quality int32 [n] on the device -> out uint8 [n][H][W][3] (no overlap with frames: ISTVT_ERR_SHAPE), the
  * RGB a baseline JPEG encoder and decoder hand back: libjpeg's 16-bit fixed-point colour transforms, edge replication to whole

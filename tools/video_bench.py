@@ -8,6 +8,7 @@
 
     python tools/video_bench.py --nv12              # NV12 frames: the fused crop against convert + crop (DESIGN.md "NV12 frames")
     python tools/video_bench.py --videos            # a set of 64 videos of 32 frames (DESIGN.md "Scoring a set of videos")
+    python tools/video_bench.py --align             # one similarity per frame: the warp against the crop (DESIGN.md "Aligned crops")
 
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
 float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
@@ -36,6 +37,12 @@ device, made once with clips.rgb_to_nv12_host, one random box of side --box-side
 the legs of a comparison alternating, median and range of --reps: (a) ops.crop_resize_nv12 against (b) ops.nv12_to_rgb_u8
 followed by ops.crop_resize_u8; each of those two kernels on its own; then score(nv12, boxes) on an NV12 scorer against
 score(rgb, boxes) on the frames (b) converted beforehand.
+
+--align (DESIGN.md "Aligned crops"), stride 8 unless --strides says otherwise: --frames frames of --full-size on the device,
+as packed RGB and as NV12, one random similarity per frame (source side --box-sides, within --degrees, half of them
+mirrored, the rotated square inside the frame).  Events around the launches, the legs alternating, median and range of
+--reps: ops.warp_similarity_u8, ops.warp_similarity_nv12, and the yardstick, ops.crop_resize_u8 on the square boxes of the
+same centres and sides; then score(frames, transforms=...) against score on the warps made beforehand.
 
 --videos (DESIGN.md "Scoring a set of videos"), strides 8 and 1 unless --strides says otherwise: --set-size device-resident
 uint8 videos of --video-frames frames.  Alternating, medians and spread as above: (a) score_videos(videos, labels=...);
@@ -293,6 +300,79 @@ def nv12_bench(a, model):
     return out
 
 
+def align_bench(a, model):
+    import math
+    from istvt_amd import clips
+    Hs, Ws = (int(v) for v in a.full_size.split('x'))
+    lo, hi = (int(v) for v in a.box_sides.split('-'))
+    S, n = a.size, a.frames
+    g = torch.Generator().manual_seed(2)
+    frames = torch.randint(0, 256, (n, Hs, Ws, 3), generator=g, dtype=torch.uint8).cuda()
+    nv = torch.empty((n, Hs + Hs // 2, Ws), dtype=torch.uint8, device='cuda')
+    for i in range(0, n, 8):
+        nv[i:i + 8] = clips.rgb_to_nv12_host(frames[i:i + 8], a.matrix)
+    side = torch.randint(lo, hi + 1, (n,), generator=g).double()
+    u = torch.rand((4, n), generator=g, dtype=torch.float64)
+    ang = (2 * u[0] - 1) * math.radians(a.degrees)
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    half = 0.5 * side * (cos.abs() + sin.abs())
+    cx, cy = half + u[1] * (Ws - 2 * half), half + u[2] * (Hs - 2 * half)
+    M = clips.check_similarities(clips.similarities_of_squares(side, ang, cx, cy, u[3] < 0.5, S), n, Hs, Ws, S)
+    # the yardstick's boxes: the same centres and sides, axis-aligned
+    isd = side.long()
+    y0 = (cy - 0.5 * side).round().long().clamp_(min=0)
+    x0 = (cx - 0.5 * side).round().long().clamp_(min=0)
+    boxes = torch.stack([torch.minimum(y0, Hs - isd), torch.minimum(x0, Ws - isd), isd, isd], dim=1).to(torch.int32)
+    mdev, bdev = M.cuda(), boxes.cuda()
+    warps = ops.warp_similarity_u8(frames, M, S)
+    warps_nv = ops.warp_similarity_nv12(nv, M, S, a.matrix)
+    crops = ops.crop_resize_u8(frames, boxes, S)
+    out = {'frames': n, 'full_size': [Hs, Ws], 'box_sides': [lo, hi], 'degrees': a.degrees, 'size': S, 'matrix': a.matrix,
+           'source_pixels': int((isd * isd).sum()), 'strides': {},
+           'nv12_equals_rgb_path': bool(torch.equal(warps_nv, ops.warp_similarity_u8(ops.nv12_to_rgb_u8(nv, a.matrix), M, S)))}
+    legs = {'warp_similarity_u8': lambda: ops.warp_similarity_u8(frames, mdev, S, out=warps, checked=True),
+            'warp_similarity_nv12': lambda: ops.warp_similarity_nv12(nv, mdev, S, a.matrix, out=warps_nv, checked=True),
+            'crop_resize_u8': lambda: ops.crop_resize_u8(frames, bdev, S, out=crops, checked=True)}
+    ts = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        for k, fn in legs.items():                          # alternating
+            t = event_ms(fn)
+            if r >= a.warmup:
+                ts[k].append(t)
+    for k in legs:
+        out[k] = stats(ts[k])
+        print('align %-22s %.3f ms (%.3f-%.3f)' % (k, out[k]['median_ms'], out[k]['min_ms'], out[k]['max_ms']), flush=True)
+    out['warp_over_crop'] = out['warp_similarity_u8']['median_ms'] / out['crop_resize_u8']['median_ms']
+    out['warp_nv12_over_crop'] = out['warp_similarity_nv12']['median_ms'] / out['crop_resize_u8']['median_ms']
+    print('align: warp / crop x%.2f (RGB), x%.2f (NV12) on the same %d faces | NV12 equals the RGB path: %s'
+          % (out['warp_over_crop'], out['warp_nv12_over_crop'], n, out['nv12_equals_rgb_path']), flush=True)
+    for stride in [int(v) for v in a.strides.split(',')]:
+        scorer = video.VideoScorer(model, stride=stride, frame_batch=a.frame_batch, window_batch=a.window_batch, side=S)
+        res = {}
+
+        def run_aligned():
+            res['a'] = scorer.score(frames, transforms=M).window_logits
+
+        def run_crops():
+            res['b'] = scorer.score(warps).window_logits
+        ta, tb = [], []
+        for r in range(a.warmup + a.reps):
+            x, y = timed(run_aligned), timed(run_crops)
+            if r >= a.warmup:
+                ta.append(x)
+                tb.append(y)
+        sa, sb = stats(ta), stats(tb)
+        rec = {'aligned': sa, 'crops': sb, 'equal_bits': bool(torch.equal(res['a'], res['b'])),
+               'warp_cost_ms': sa['median_ms'] - sb['median_ms'],
+               'warp_cost_share': (sa['median_ms'] - sb['median_ms']) / sb['median_ms']}
+        out['strides'][str(stride)] = rec
+        print('align stride %d: score(frames, transforms) %.2f ms (%.2f-%.2f) | score(warps) %.2f ms (%.2f-%.2f) | difference '
+              '%.2f ms = %.2f %% | equal bits %s' % (stride, sa['median_ms'], sa['min_ms'], sa['max_ms'], sb['median_ms'],
+                                                    sb['min_ms'], sb['max_ms'], rec['warp_cost_ms'],
+                                                    100 * rec['warp_cost_share'], rec['equal_bits']), flush=True)
+    return out
+
+
 def _phases(scorer, model, fn, extra=()):
     """one instrumented run of fn: device ms between the events around the three phases and the kernels named in `extra`"""
     ops.kernel_profile = []
@@ -389,6 +469,8 @@ def main():
     ap.add_argument('--boxes', action='store_true')
     ap.add_argument('--videos', action='store_true')
     ap.add_argument('--nv12', action='store_true')
+    ap.add_argument('--align', action='store_true')
+    ap.add_argument('--degrees', type=float, default=15.0)
     ap.add_argument('--matrix', default='bt709', choices=['bt601', 'bt709', 'jfif'])
     ap.add_argument('--set-size', type=int, default=64)
     ap.add_argument('--video-frames', type=int, default=32)
@@ -396,7 +478,7 @@ def main():
     ap.add_argument('--box-sides', default='150-600')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
-    a.strides = a.strides or ('8' if a.nv12 else '8,1' if a.videos else '1,8' if a.explain or a.boxes else '1,2,4,8')
+    a.strides = a.strides or ('8' if a.nv12 or a.align else '8,1' if a.videos else '1,8' if a.explain or a.boxes else '1,2,4,8')
     if not torch.cuda.is_available():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
@@ -416,6 +498,18 @@ def main():
         print(json.dumps({'video_set_bench': {k: {'loop_over_set': v['loop_over_set'],
                                                   'set_ms_per_32_windows': v['set_ms_per_32_windows']}
                                               for k, v in out['strides'].items()}}))
+        return
+    if a.align:
+        out = dict(align_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
+                   window_batch=a.window_batch, reps=a.reps, warmup=a.warmup)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_align_bench': {'warp_u8_ms': out['warp_similarity_u8']['median_ms'],
+                                                'warp_nv12_ms': out['warp_similarity_nv12']['median_ms'],
+                                                'crop_resize_u8_ms': out['crop_resize_u8']['median_ms'],
+                                                'warp_over_crop': out['warp_over_crop']}}))
         return
     if a.nv12:
         out = dict(nv12_bench(a, model), T=a.T, depth=a.depth, dtype=a.dtype, frame_batch=a.frame_batch,
