@@ -48,6 +48,9 @@ SIGNATURES = {
     'istvt_bn_bwd_stats': [P, P, P, P, P, L, I, I, P],
     'istvt_bn_bwd_apply': [P, P, P, P, P, P, P, P, P, L, I, I, I, P],
     'istvt_bn_add_fwd': [P, P, P, P, P, L, I, I, P],
+    'istvt_pw_bwd': [P, P, P, P, P, P, P, L, P, L, P, P, P, P, P, L, I, I, I, I, P],
+    'istvt_pw_bwd_grid': [L],
+    'istvt_pw_bwd_rows': [],
     'istvt_im2col_conv1': [P, P, I, I, I, P],
     'istvt_conv1_fwd': [P, P, P, I, I, I, P],
     'istvt_conv1_fwd_u8': [P, P, P, P, P, I, I, I, P],

@@ -14,6 +14,7 @@
 //
 // All of these are HBM-bound (AI <= 4.5 flop/B): coalesced 16-byte accesses along C.
 #include "common.h"
+#include "bn_bwd.h"
 #include <cstdlib>
 
 // A finalized BatchNorm is passed around as ONE pointer `bnp` to a float [4][C] pack:
@@ -210,8 +211,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     const long nvec = M * vpr;
     // eval mode (running statistics are constants): du = gamma * rstd * dz, no mean / projection terms
     const float invM = batch_stats ? 1.0f / (float)M : 0.0f;
-    const float* mean = bnp;
-    const float* rstd = bnp + C;
     // A thread keeps ONE channel chunk for all its vectors (the stride is a multiple of the chunks per row), so the
     // per-channel constants are loaded once: read per vector they were 224 bytes of L1 traffic beside 32 bytes of
     // payload, and the kernel ran at the rate of the load path (3.7 TB/s), not of HBM.
@@ -219,12 +218,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t < nthr) {
         const int c0 = (int)(t % vpr) * 8;
-        float mu[8], rs[8], g[8], k1[8], k2[8];
-        load8(mean + c0, mu);
-        load8(rstd + c0, rs);
-        load8(gamma + c0, g);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { k1[j] = (float)s1[c0 + j] * invM; k2[j] = (float)s2[c0 + j] * invM; }
+        BnBwdChunk k;                                            // the expression itself: bn_bwd.h (shared with pw_bwd.hip)
+        bn_bwd_chunk_load(k, bnp, gamma, s1, s2, C, c0, invM);
         long i = t;
         for (; i + nthr < nvec; i += 2 * nthr) {                 // two vectors in flight
             float d0[8], u0[8], d1[8], u1[8];
@@ -234,9 +229,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
             load8(u + (i + nthr) * 8, u1);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float x0 = (u0[j] - mu[j]) * rs[j], x1 = (u1[j] - mu[j]) * rs[j];
-                d0[j] = g[j] * rs[j] * (d0[j] - k1[j] - x0 * k2[j]);
-                d1[j] = g[j] * rs[j] * (d1[j] - k1[j] - x1 * k2[j]);
+                d0[j] = bn_bwd_du(d0[j], u0[j], k, j);
+                d1[j] = bn_bwd_du(d1[j], u1[j], k, j);
             }
             store8(du + i * 8, d0);
             store8(du + (i + nthr) * 8, d1);
@@ -246,10 +240,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
             load8(dz + i * 8, d0);
             load8(u + i * 8, u0);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float x0 = (u0[j] - mu[j]) * rs[j];
-                d0[j] = g[j] * rs[j] * (d0[j] - k1[j] - x0 * k2[j]);
-            }
+            for (int j = 0; j < 8; ++j) d0[j] = bn_bwd_du(d0[j], u0[j], k, j);
             store8(du + i * 8, d0);
         }
     }

@@ -288,6 +288,60 @@ def linear_wgrad(dy: Tensor, x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# Fused backward of a separable unit's 1x1 convolution and the BatchNorm behind it (csrc/pw_bwd.hip)
+PW_BWD_PAIRS = ((64, 128), (128, 128))          # (Cin, Cout) the kernel is instantiated for
+
+
+def pw_bwd_geometry(M: int):
+    """(G, R): workgroups of a launch over M rows (= fp32 slabs of the workspace; the reduction split linear_wgrad takes
+    for the same gradient) and rows per block of istvt_pw_bwd"""
+    lib = _lib.lib()
+    return int(lib.istvt_pw_bwd_grid(M)), int(lib.istvt_pw_bwd_rows())
+
+
+def pw_bwd_fusable(dz: Tensor, d: Tensor, w: Tensor) -> bool:
+    """whether pw_bwd() takes this unit: bf16, contiguous [M, C] operands, one of the instantiated channel pairs,
+    operands below 2 GiB (the kernel addresses them with 32-bit byte offsets)"""
+    if dz.dtype != torch.bfloat16 or d.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        return False
+    if dz.dim() != 2 or d.dim() != 2 or w.dim() != 2 or not dz.is_contiguous() or not d.is_contiguous():
+        return False
+    M, cout = dz.shape
+    cin = d.shape[1]
+    if d.shape[0] != M or tuple(w.shape) != (cout, cin) or (cin, cout) not in PW_BWD_PAIRS or M < 1:
+        return False
+    return M * cout * 2 < 0x7fffffff and dz.data_ptr() % 16 == 0 and d.data_ptr() % 16 == 0
+
+
+def pw_bwd(dz: Tensor, u: Tensor, bnp: Tensor, gamma: Tensor, stats: Tensor, d: Tensor, w: Tensor, out: Tensor,
+           dgamma: Tensor, dbeta: Tensor, training: bool = True) -> Tensor:
+    """One launch for du = BatchNorm-backward(dz, u), dd = du @ w and out[Cout, Cin] += du.T @ d (du never reaches memory;
+    `out` gets the bits of linear_wgrad(du, d, out=out)).
+    bnp: the BatchNorm's [4][Cout] pack; stats: its reduced backward sums (stem.new_stats layout, replica 0); w [Cout, Cin]
+    in the compute dtype; out float32 [Cout, Cin] and dgamma / dbeta float32 [Cout] are accumulated into.  Only where
+    pw_bwd_fusable() says so: anything else is refused by the library.  -> dd [M, Cin]"""
+    for t in (dz, u, d, w, out, dgamma, dbeta):
+        _req(t)
+    M, cout = dz.shape
+    cin = d.shape[1]
+    if u.shape != dz.shape or not u.is_contiguous() or u.dtype != dz.dtype:
+        raise RuntimeError('pw_bwd: u must match dz (%s %s vs %s %s)' % (tuple(u.shape), u.dtype, tuple(dz.shape), dz.dtype))
+    if out.dtype != torch.float32 or out.numel() != cout * cin or not out.is_contiguous():
+        raise RuntimeError('pw_bwd: the weight gradient must be contiguous float32 [%d, %d]' % (cout, cin))
+    wt, ldwt = rows(_transposed_operand(w))
+    lib = _lib.lib()
+    G = int(lib.istvt_pw_bwd_grid(M))
+    dd = torch.empty((M, cin), dtype=dz.dtype, device=dz.device)
+    ws = torch.empty((G, cout * cin), dtype=torch.float32, device=dz.device)
+    with prof('pw_bwd_fused', (2 * M * cout + 2 * M * cin) * dz.element_size()):
+        _lib.check(lib.istvt_pw_bwd(dz.data_ptr(), u.data_ptr(), bnp.data_ptr(), gamma.data_ptr(), stats[0, 0].data_ptr(),
+                                    stats[0, 1].data_ptr(), d.data_ptr(), d.stride(0), wt.data_ptr(), ldwt, dd.data_ptr(),
+                                    ws.data_ptr(), out.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), M, cin, cout,
+                                    int(training), dtype_code(dz), _stream()), 'istvt_pw_bwd')
+    return dd
+
+
 WGRAD_GROUP_MAX = 8
 
 

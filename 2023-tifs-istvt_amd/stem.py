@@ -145,24 +145,63 @@ def bn_backward(dz: Tensor, u: Tensor, st: BNState, gamma: Tensor, M: int, C: in
     while dgamma / dbeta keep their sums.  `stats` = new_stats() buffer already accumulated (not yet reduced) by a
     fused producer (the depthwise input-gradient kernel).  dg / db: float32 [C] buffers to accumulate into
     (a parameter's .grad); fresh zero tensors otherwise."""
-    L = _lib.lib()
-    if stats is None:
-        stats = new_stats(C, u.device)
-        with ops.prof('bn_bwd_stats', 2 * M * C * u.element_size()):
-            _lib.check(L.istvt_bn_bwd_stats(dz.data_ptr(), u.data_ptr(), st.ptr(),
-                                            stats[0, 0].data_ptr(), stats[0, 1].data_ptr(), M, C, dtype_code(u), _stream()),
-                       'istvt_bn_bwd_stats')
-    reduce_stats(stats, C)
-    du = torch.empty_like(u)
+    stats = _bn_backward_sums(dz, u, st, M, C, stats)
     if dg is None:
         dg = torch.zeros((C,), dtype=torch.float32, device=u.device)
     if db is None:
         db = torch.zeros((C,), dtype=torch.float32, device=u.device)
+    return _bn_backward_apply(dz, u, st, gamma, M, C, stats, dg, db, training), dg, db
+
+
+def _bn_backward_apply(dz: Tensor, u: Tensor, st: BNState, gamma: Tensor, M: int, C: int, stats: Tensor, dg: Tensor,
+                       db: Tensor, training: bool) -> Tensor:
+    du = torch.empty_like(u)
     with ops.prof('bn_bwd_apply', 3 * M * C * u.element_size()):
-        _lib.check(L.istvt_bn_bwd_apply(dz.data_ptr(), u.data_ptr(), st.ptr(), gamma.data_ptr(),
-                                        stats[0, 0].data_ptr(), stats[0, 1].data_ptr(), du.data_ptr(), dg.data_ptr(),
-                                        db.data_ptr(), M, C, int(training), dtype_code(u), _stream()), 'istvt_bn_bwd_apply')
-    return du, dg, db
+        _lib.check(_lib.lib().istvt_bn_bwd_apply(dz.data_ptr(), u.data_ptr(), st.ptr(), gamma.data_ptr(),
+                                                 stats[0, 0].data_ptr(), stats[0, 1].data_ptr(), du.data_ptr(), dg.data_ptr(),
+                                                 db.data_ptr(), M, C, int(training), dtype_code(u), _stream()),
+                   'istvt_bn_bwd_apply')
+    return du
+
+
+def _bn_backward_sums(dz: Tensor, u: Tensor, st: BNState, M: int, C: int, stats: Optional[Tensor]) -> Tensor:
+    """the BatchNorm-backward sums s1 / s2, reduced into replica 0: taken here unless a fused producer accumulated them"""
+    if stats is None:
+        stats = new_stats(C, u.device)
+        with ops.prof('bn_bwd_stats', 2 * M * C * u.element_size()):
+            _lib.check(_lib.lib().istvt_bn_bwd_stats(dz.data_ptr(), u.data_ptr(), st.ptr(), stats[0, 0].data_ptr(),
+                                                     stats[0, 1].data_ptr(), M, C, dtype_code(u), _stream()),
+                       'istvt_bn_bwd_stats')
+    reduce_stats(stats, C)
+    return stats
+
+
+def pointwise_bn_backward(dz: Tensor, u: Tensor, st: BNState, gamma: Tensor, M: int, cout: int, d: Tensor, w: Tensor,
+                          cin: int, stats: Optional[Tensor], dg: Tensor, db: Tensor, wgrad_target: Optional[Tensor],
+                          training: bool, side=None):
+    """Backward of a separable unit's BatchNorm (u -> z) and the 1x1 convolution in front of it (d -> u, weight operand w
+    [cout, cin]): -> (dd, dW), dW None when the weight gradient was added into `wgrad_target` (float32 [cout, cin]).
+    dg / db: float32 [cout] accumulated into.  stats: see bn_backward.
+
+    One launch where ops.pw_bwd_fusable() allows (the 64->128 and 128->128 units in bf16): du stays on the chip.
+    Otherwise, and with ISTVT_STEM_PW_BWD_FUSED=0 (read at call time, for A/B runs), three: the BatchNorm-backward apply,
+    the weight gradient and the input gradient.  side (fallback only): callable(fn, keep) that runs a weight gradient
+    nobody waits for beside the chain (functional.side_launch)."""
+    stats = _bn_backward_sums(dz, u, st, M, cout, stats)
+    if os.environ.get('ISTVT_STEM_PW_BWD_FUSED', '1') != '0' and ops.pw_bwd_fusable(dz, d, w):
+        dW = None
+        if wgrad_target is None:
+            dW = wgrad_target = torch.zeros((cout, cin), dtype=torch.float32, device=dz.device)
+        dd = ops.pw_bwd(dz, u, st.pack, gamma, stats, d, w, wgrad_target, dg, db, training)
+        return dd, dW
+    du = _bn_backward_apply(dz, u, st, gamma, M, cout, stats, dg, db, training)
+    dW = None
+    if wgrad_target is not None and side is not None:
+        side(lambda: ops.linear_wgrad(du, d, out=wgrad_target), (du, d))
+    else:
+        r = ops.linear_wgrad(du, d, out=wgrad_target)
+        dW = r if wgrad_target is None else None
+    return ops.linear_dgrad(du, w, blocked=False), dW
 
 
 def dwconv(x: Tensor, w9: Tensor, Fr: int, H: int, W: int, C: int, *, in_bn: Optional[BNState] = None,
@@ -438,6 +477,26 @@ class StemFn(Function):
             if t is None:
                 grads[n] = r
 
+        def side_wgrad(fn, keep):
+            from . import functional as Fn
+            Fn.side_launch(keep[0].device, fn, keep=keep)
+
+        def pw_bn_bwd(dz, u, st, nbn, M_, C_, d, wp, nw, cin_, stats):
+            """a rep unit's BatchNorm + 1x1 convolution backward (pointwise_bn_backward) -> dd"""
+            q = P[nw]
+            tg, tb, t = tgt(nbn + '.weight', (C_,)), tgt(nbn + '.bias', (C_,)), tgt(nw, (q.shape[0], -1))
+            dg = tg if tg is not None else torch.zeros((C_,), dtype=torch.float32, device=u.device)
+            db = tb if tb is not None else torch.zeros((C_,), dtype=torch.float32, device=u.device)
+            dd, dW = pointwise_bn_backward(dz, u, st, P[nbn + '.weight'], M_, C_, d, wp, cin_, stats, dg, db, t, training,
+                                           side=side_wgrad if side_on else None)
+            if tg is None:
+                grads[nbn + '.weight'] = dg
+            if tb is None:
+                grads[nbn + '.bias'] = db
+            if t is None:
+                grads[nw] = dW
+            return dd
+
         def dw_wgrad(n, xv, dv, H_, C_, bn_, relu_):
             t = tgt(n, (C_, 9))
             if t is not None and side_on:
@@ -466,25 +525,19 @@ class StemFn(Function):
                                             blk['uB'].data_ptr() if training else None, blk['bnB'].ptr() if training else None,
                                             statsB[0, 0].data_ptr() if training else None,
                                             statsB[0, 1].data_ptr() if training else None, dtc, _stream()), 'istvt_pool_bwd')
-            nB = '%s.rep.%d' % (name, i0 + 4)
-            duB = bn_bwd(dzB, blk['uB'], blk['bnB'], nB, M, cout, stats=statsB)
-            del dzB
             sB = '%s.rep.%d' % (name, i0 + 3)
-            lin_wgrad(sB + '.pointwise.weight', duB, blk['d2'])
-            dd2 = ops.linear_dgrad(duB, blk['wpwB'], blocked=False)
-            del duB
+            dd2 = pw_bn_bwd(dzB, blk['uB'], blk['bnB'], '%s.rep.%d' % (name, i0 + 4), M, cout, blk['d2'], blk['wpwB'],
+                            sB + '.pointwise.weight', cout, statsB)
+            del dzB
             dw_wgrad(sB + '.conv1.weight', blk['uA'], dd2, H, cout, blk['bnA'], True)
             statsA = new_stats(cout, dev)
             dzA = dwconv(dd2, blk['wdwB'], Fr, H, H, cout, flip=True, msrc=blk['uA'], m_bn=blk['bnA'], mask_pre=True,
                          stats=statsA)
             del dd2
-            nA = '%s.rep.%d' % (name, i0 + 1)
-            duA = bn_bwd(dzA, blk['uA'], blk['bnA'], nA, M, cout, stats=statsA)
-            del dzA
             sA = '%s.rep.%d' % (name, i0)
-            lin_wgrad(sA + '.pointwise.weight', duA, blk['d1'])
-            dd1 = ops.linear_dgrad(duA, blk['wpwA'], blocked=False)
-            del duA
+            dd1 = pw_bn_bwd(dzA, blk['uA'], blk['bnA'], '%s.rep.%d' % (name, i0 + 1), M, cout, blk['d1'], blk['wpwA'],
+                            sA + '.pointwise.weight', cin, statsA)
+            del dzA
             # (block1: X is u2 -- the convolution's input was relu(bn2(u2)), taken on load as in the forward)
             fused_in = not blk['pre_relu'] and blk['X'] is sv['u2']
             dw_wgrad(sA + '.conv1.weight', blk['X'], dd1, H, cin, sv['bn2'] if fused_in else None, True if fused_in else blk['pre_relu'])

@@ -24,7 +24,8 @@ from torch.autograd.function import once_differentiable
 from . import _lib, ops
 from . import stem as _stem
 from .ops import _c, _req, _stream, dtype_code
-from .stem import bn_apply, bn_backward, bn_forward_stats, dwconv, dwconv_wgrad, new_stats, pointwise_bn
+from .stem import (bn_apply, bn_backward, bn_forward_stats, dwconv, dwconv_wgrad, new_stats, pointwise_bn,
+                   pointwise_bn_backward)
 
 Tensor = torch.Tensor
 
@@ -223,11 +224,16 @@ class RepChainFn(Function):
         for i in reversed(range(nu)):
             un = units[i]
             cin, cout = un['cin'], un['cout']
-            du = bn_bwd(dz, un['u'], un['bn'], 4 * i + 2, M, cout, stats=stats)
+            gq, bq, wq = params[4 * i + 2], params[4 * i + 3], params[4 * i + 1]
+            tg, tb, tw = _fused_target(gq, (cout,)), _fused_target(bq, (cout,)), _fused_target(wq, (wq.shape[0], -1))
+            dg = tg if tg is not None else torch.zeros((cout,), dtype=torch.float32, device=dev)
+            db = tb if tb is not None else torch.zeros((cout,), dtype=torch.float32, device=dev)
+            dd, dW = pointwise_bn_backward(dz, un['u'], un['bn'], gq, M, cout, un['d'], un['wp'], cin, stats, dg, db, tw,
+                                           training)
             del dz
-            lin_wgrad(4 * i + 1, du, un['d'])
-            dd = ops.linear_dgrad(du, un['wp'], blocked=False)
-            del du
+            grads[4 * i + 2] = None if tg is not None else dg
+            grads[4 * i + 3] = None if tb is not None else db
+            grads[4 * i + 1] = None if tw is not None else dW.view(wq.shape)
             q = params[4 * i]
             t = _fused_target(q, (cin, 9))
             r = dwconv_wgrad(un['X'], dd, Fr, H, W, cin, un['in_bn'], un['relu'], out=t)

@@ -253,6 +253,19 @@ int istvt_bn_bwd_stats(const void* dz, const void* u, const float* bnp, double* 
 int istvt_bn_bwd_apply(const void* dz, const void* u, const float* bnp, const float* gamma, const double* s1,
                        const double* s2, void* du, float* dgamma, float* dbeta, long M, int C, int batch_stats,
                        int dtype, istvt_stream_t stream);
+/* The BatchNorm-backward apply above, the 1x1 convolution's input gradient and its weight gradient in one pass (bf16;
+ * (Cin, Cout) = (64, 128) or (128, 128), anything else is ISTVT_ERR_SHAPE and nothing is touched):
+ *   du = bn_bwd_apply(dz, u) [M][Cout] (never stored), dd [M][Cin] = du . W, wgrad_out [Cout][Cin] += du^T . d.
+ * d [M][ldd], wt = W^T [Cin][ldwt], dd contiguous; ws = caller-owned float workspace of istvt_pw_bwd_grid(M) slabs of
+ * Cout * Cin, summed in slab order into wgrad_out (istvt_splitk_reduce): two runs give the same bits, and they are the bits
+ * of the split-K weight gradient istvt_gemm + istvt_splitk_reduce give on the stored du (same chunks of rows, same order).
+ * Operands must be smaller than 2 GiB each.  istvt_pw_bwd_rows(): rows per block of a workgroup's chunk. */
+int istvt_pw_bwd(const void* dz, const void* u, const float* bnp, const float* gamma, const double* s1, const double* s2,
+                 const void* d, long ldd, const void* wt, long ldwt, void* dd, float* ws, float* wgrad_out,
+                 float* dgamma, float* dbeta, long M, int Cin, int Cout, int batch_stats, int dtype,
+                 istvt_stream_t stream);
+int istvt_pw_bwd_grid(long M);
+int istvt_pw_bwd_rows(void);
 /* tail of a stride-1 Block (xception.py:91-100 without the MaxPool): out = bn_x(x) + (bns ? bn_s(skip) : skip) */
 int istvt_bn_add_fwd(const void* x, const float* bnx, const void* skip, const float* bns, void* out, long M, int C,
                      int dtype, istvt_stream_t stream);
