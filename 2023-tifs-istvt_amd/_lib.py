@@ -65,6 +65,7 @@ SIGNATURES = {
     'istvt_warp_similarity_u8': [P, L, I, I, P, P, I, I, P],
     'istvt_warp_similarity_nv12': [P, L, I, I, L, L, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
+    'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],
     'istvt_conv2_wgrad': [P, P, P, P, P, I, I, I, P],

@@ -26,6 +26,11 @@ Aligned crops (DESIGN.md "Aligned crops") are the fifth: ``check_similarities``,
 ops.warp_similarity_u8, float64), ``similarity_of_boxes``, ``similarity_from_landmarks``, ``similarities_of_squares`` and
 ``random_similarities``.  A
 training step with rotation, scale and flip in one table is ``model(ops.warp_similarity_u8(u8, M.to(dev), S))``.
+
+Perturbations (DESIGN.md "Perturbations") are the sixth: ``perturb_host`` (the definition of ops.perturb_u8, integers only:
+brightness, contrast, saturation, Gaussian noise from Philox4x32-10, Gaussian blur with integer taps, pixelation),
+``gaussian_taps``, ``check_perturbations``, ``perturbation``, ``perturbation_table``, ``random_perturbations`` and the ladder
+``PERTURBATION_LEVELS``.  In training ``ops.perturb_u8(u8, table, taps, seed)`` stands where the JPEG round trip stands above.
 """
 import math
 from fractions import Fraction
@@ -766,3 +771,275 @@ def random_similarities(B: int, Hs: int, Ws: int, S: int, scale=(0.5, 1.0), degr
     cx = torch.where(Ws - 2.0 * half > 0, half + u[2] * (Ws - 2.0 * half), torch.full_like(half, 0.5 * Ws))
     cy = torch.where(Hs - 2.0 * half > 0, half + u[3] * (Hs - 2.0 * half), torch.full_like(half, 0.5 * Hs))
     return similarities_of_squares(side, ang, cx, cy, u[4] < flip_p, S)
+
+
+# ------------------------------------------------------------------------------------------ perturbations
+# DESIGN.md "Perturbations": the degradations a robustness table grades a detector by, next to JPEG -- brightness, contrast,
+# saturation, Gaussian noise, Gaussian blur, pixelation -- bytes to bytes in int32 arithmetic with arithmetic shifts and no
+# floating point on the pixel path.  A frame's row of the table is (kind, param, frame_id, stream); ops.perturb_u8 is the
+# device kernel and gives the bits of perturb_host.
+PERTURBATION_KINDS = ('copy', 'brightness', 'contrast', 'saturation', 'noise', 'blur', 'pixelate')
+PERTURB_TAPS = 21                          # taps of a blur row: radius 10 around index 10
+PERTURB_TAPS_SUM = 2048                    # a row sums to 2^11: two passes leave 22 bits to shift out
+PERTURB_MAX_TAPS_ROWS = 16
+PERTURB_PARAM_RANGE = {0: None, 1: (0, 1024), 2: (0, 1024), 3: (0, 1024), 4: (0, 1023), 5: None, 6: (2, 32)}
+# Five steps per kind for a robustness table, mild to severe, in the units clips.perturbation takes.  The steps are this
+# project's choice: the usual protocol names the distortions and that there are five levels of each, not these numbers.
+PERTURBATION_LEVELS = {
+    'brightness': (0.9, 0.8, 0.7, 0.6, 0.5),
+    'contrast': (0.85, 0.725, 0.6, 0.475, 0.35),
+    'saturation': (0.8, 0.6, 0.4, 0.2, 0.0),
+    'noise': (4.0, 8.0, 12.0, 16.0, 20.0),
+    'blur': (0.8, 1.6, 2.4, 3.2, 4.0),
+    'pixelate': (2, 3, 4, 5, 6),
+}
+
+
+def _mulhilo32(m: int, c: Tensor):
+    """(high, low) 32-bit words of m * c for a 32-bit constant m and int64 c in [0, 2^32), without leaving int64"""
+    a, b = m * (c >> 16), m * (c & 0xffff)                         # both below 2^48; m * c = a * 2^16 + b
+    return (a + (b >> 16)) >> 16, (((a & 0xffff) << 16) + b) & 0xffffffff
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon, Moraes, Dror and Shaw, SC'11): counter = four int64 tensors of one shape (or Python ints) holding
+    32-bit words, key = two 32-bit Python ints -> the four output words, int64 tensors in [0, 2^32)."""
+    c0, c1, c2, c3 = torch.broadcast_tensors(*[torch.as_tensor(c, dtype=torch.int64) & 0xffffffff for c in counter])
+    k0, k1 = int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff
+    for _ in range(10):
+        h0, l0 = _mulhilo32(0xD2511F53, c0)
+        h1, l1 = _mulhilo32(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+    return c0, c1, c2, c3
+
+
+def gaussian_taps(sigmas) -> Tensor:
+    """One blur row per sigma in [0.3, 4], int32 (K, 21), K <= 16: w_i = exp(-i^2 / 2 sigma^2) for |i| <= min(10, ceil(3 sigma))
+    and zero outside, in float64; scaled so that the row sums to 2048 and rounded half up; what the rounding leaves of 2048
+    goes to the centre tap.  The kernel reads these integers only."""
+    sigmas = [float(s) for s in (sigmas if isinstance(sigmas, (list, tuple)) else [sigmas])]
+    if not 1 <= len(sigmas) <= PERTURB_MAX_TAPS_ROWS:
+        raise ValueError('gaussian_taps: between 1 and %d sigmas, got %d' % (PERTURB_MAX_TAPS_ROWS, len(sigmas)))
+    rows = []
+    for s in sigmas:
+        if not 0.3 <= s <= 4.0:
+            raise ValueError('gaussian_taps: sigma must lie in [0.3, 4], got %r' % (s,))
+        R = min(PERTURB_TAPS // 2, math.ceil(3.0 * s))
+        w = [math.exp(-(i * i) / (2.0 * s * s)) if abs(i) <= R else 0.0 for i in range(-10, 11)]
+        tot = sum(w)
+        t = [int(math.floor(v * PERTURB_TAPS_SUM / tot + 0.5)) for v in w]
+        t[10] += PERTURB_TAPS_SUM - sum(t)
+        rows.append(t)
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def check_perturbations(table, n: int, taps=None) -> Tensor:
+    """Host validation of a perturbation table before any launch: int32 (n, 4) = (kind, param, frame_id, stream) per frame or
+    clip; kind in 0..6 (PERTURBATION_KINDS); param 0..1024 for the Q8 gains of kinds 1 to 3, 0..1023 for the Q4 sigma of kind
+    4, a row of `taps` for kind 5, 2..32 for the block side of kind 6, anything for kind 0; frame_id and stream >= 0.  taps,
+    whenever it is passed: int32 (K, 21), 1 <= K <= 16, every row symmetric about index 10, non-negative and summing to
+    exactly 2048; a table with a kind 5 row needs it.  Returns the table on the host (a device tensor is copied back, which
+    waits for the device: hand over the loader's host tensor)."""
+    if not torch.is_tensor(table):
+        raise TypeError('perturbations: the table must be an int32 tensor (n, 4), got %s' % type(table).__name__)
+    if table.dtype != torch.int32:
+        raise TypeError('perturbations: the table must be int32, got %s' % table.dtype)
+    if table.dim() != 2 or tuple(table.shape) != (n, 4):
+        raise ValueError('perturbations: the table must have shape (%d, 4) = (kind, param, frame_id, stream) per entry, got %s'
+                         % (n, tuple(table.shape)))
+    K = 0
+    if taps is not None:
+        if not torch.is_tensor(taps):
+            raise TypeError('perturbations: taps must be an int32 tensor (K, 21), got %s' % type(taps).__name__)
+        if taps.dtype != torch.int32:
+            raise TypeError('perturbations: taps must be int32, got %s' % taps.dtype)
+        if taps.dim() != 2 or taps.shape[1] != PERTURB_TAPS or not 1 <= taps.shape[0] <= PERTURB_MAX_TAPS_ROWS:
+            raise ValueError('perturbations: taps must have shape (K, 21) with 1 <= K <= %d, got %s'
+                             % (PERTURB_MAX_TAPS_ROWS, tuple(taps.shape)))
+        tp = taps.detach().cpu()
+        if bool((tp < 0).any()) or not torch.equal(tp, tp.flip(1)) or bool((tp.sum(1) != PERTURB_TAPS_SUM).any()):
+            raise ValueError('perturbations: every row of taps must be non-negative, symmetric about index 10 and sum to %d'
+                             % PERTURB_TAPS_SUM)
+        K = int(tp.shape[0])
+    t = table.detach().cpu()
+    kind, param = t[:, 0], t[:, 1]
+    if bool((kind < 0).any()) or bool((kind >= len(PERTURBATION_KINDS)).any()):
+        raise ValueError('perturbations: kind must lie in [0, %d], got [%d, %d]'
+                         % (len(PERTURBATION_KINDS) - 1, int(kind.min()), int(kind.max())))
+    for k, rng in PERTURB_PARAM_RANGE.items():
+        if rng is not None and bool(((kind == k) & ((param < rng[0]) | (param > rng[1]))).any()):
+            raise ValueError('perturbations: the param of kind %d (%s) must lie in [%d, %d]' % (k, PERTURBATION_KINDS[k], *rng))
+    blur = kind == 5
+    if bool(blur.any()):
+        if taps is None:
+            raise ValueError('perturbations: a blurred frame (kind 5) needs taps (clips.gaussian_taps)')
+        if bool((blur & ((param < 0) | (param >= K))).any()):
+            raise ValueError('perturbations: the param of kind 5 (blur) names a row of taps, 0..%d' % (K - 1))
+    if bool((t[:, 2:] < 0).any()):
+        raise ValueError('perturbations: frame_id and stream must not be negative')
+    return t
+
+
+def perturbation(kind_name: str, value):
+    """A user's (name, strength) -> (kind, param, taps): the gain of 'brightness', 'contrast' and 'saturation' in Q8
+    (round(256 value), 0..4 -> 0..1024), the sigma of 'noise' in grey levels in Q4 (round(16 value), below 64), the sigma
+    of 'blur' (0.3..4) as row 0 of the one-row bank taps = gaussian_taps([value]), the block side of 'pixelate' (an int in
+    2..32) as it is, and 'copy' (the value is ignored).  taps is None for every kind but 'blur'.  ValueError for a name or a
+    value outside these."""
+    if kind_name not in PERTURBATION_KINDS:
+        raise ValueError('perturbation: the kind must be one of %s, got %r' % (', '.join(PERTURBATION_KINDS), kind_name))
+    kind = PERTURBATION_KINDS.index(kind_name)
+    if kind == 0:
+        return 0, 0, None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+        raise ValueError('perturbation: %s takes a finite number, got %r' % (kind_name, value))
+    if kind == 5:
+        return 5, 0, gaussian_taps([value])
+    if kind == 6:
+        if not isinstance(value, int):
+            raise ValueError('perturbation: pixelate takes an int block side, got %r' % (value,))
+        param = value
+    else:
+        param = int(math.floor(value * (16.0 if kind == 4 else 256.0) + 0.5))
+    lo, hi = PERTURB_PARAM_RANGE[kind]
+    if not lo <= param <= hi:
+        raise ValueError('perturbation: %s = %r gives param %d outside [%d, %d]' % (kind_name, value, param, lo, hi))
+    return kind, param, None
+
+
+def perturbation_table(n: int, kind_name: str, value, first_frame: int = 0, stream: int = 0):
+    """"This perturbation on every frame" -> (table int32 (n, 4), taps or None): n rows (kind, param, first_frame + i, stream)
+    for the n frames of one video; what VideoScorer(perturb=(kind_name, value)) applies to a video that is `stream` in its
+    call and whose first frame is `first_frame`."""
+    if n < 1 or first_frame < 0 or stream < 0 or first_frame + n > 2 ** 31:
+        raise ValueError('perturbation_table: need n >= 1, first_frame >= 0 and stream >= 0, got %r, %r, %r' % (n, first_frame, stream))
+    kind, param, taps = perturbation(kind_name, value)
+    table = torch.empty((n, 4), dtype=torch.int32)
+    table[:, 0], table[:, 1], table[:, 3] = kind, param, stream
+    table[:, 2] = torch.arange(first_frame, first_frame + n, dtype=torch.int32)
+    return table, taps
+
+
+def random_perturbations(B: int, p: float = 0.5, kinds=('brightness', 'contrast', 'saturation', 'noise', 'blur', 'pixelate'),
+                         generator: Optional[torch.Generator] = None, brightness=(0.6, 1.4), contrast=(0.6, 1.4),
+                         saturation=(0.0, 1.5), noise=(2.0, 16.0), blur=(0.5, 3.0), pixelate=(2, 6)):
+    """One random perturbation per clip for training -> (table int32 (B, 4), taps int32 (8, 21)), host tensors reproducible
+    from `generator`.  A clip is perturbed with probability p and is kind 0 otherwise; the kind is uniform among `kinds`; the
+    strength is uniform in the kind's range, a keyword each: the gains of brightness and contrast in [0.6, 1.4] and of
+    saturation in [0, 1.5], the noise sigma in [2, 16] grey levels, the blur sigma one of the 8 rows of the bank (sigmas
+    evenly spaced over [0.5, 3]: the bank depends on the range only, so it is uploaded once), the block side an int in
+    [2, 6].  stream = the clip's index and frame_id is drawn from [0, 2^30): the T frames of a clip take frame_id .. frame_id +
+    T - 1, so no two clips of a batch share noise, and two batches do only by a coincidence of 1 in 2^30 per pair.  The step
+    is ``model(ops.perturb_u8(u8, table, taps, seed), view=flips)``, as with random_qualities and ops.jpeg_roundtrip_u8."""
+    if B < 1:
+        raise ValueError('random_perturbations: need B >= 1, got %d' % B)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('random_perturbations: p must be a probability, got %r' % (p,))
+    kinds = tuple(kinds)
+    if not kinds or any(k not in PERTURBATION_KINDS[1:] for k in kinds):
+        raise ValueError('random_perturbations: kinds must name some of %s, got %r' % (', '.join(PERTURBATION_KINDS[1:]), kinds))
+    ranges = {'brightness': brightness, 'contrast': contrast, 'saturation': saturation, 'noise': noise, 'blur': blur,
+              'pixelate': pixelate}
+    for k in kinds:                                                 # both ends must be values perturbation() takes
+        lo, hi = ranges[k]
+        if not lo <= hi:
+            raise ValueError('random_perturbations: the range of %s must be (low, high), got %r' % (k, ranges[k]))
+        perturbation(k, lo), perturbation(k, hi)
+    rows = 8
+    taps = gaussian_taps([blur[0] + (blur[1] - blur[0]) * i / (rows - 1) for i in range(rows)])
+    u = torch.rand((3, B), generator=generator, dtype=torch.float64)
+    fid = torch.randint(0, 2 ** 30, (B,), generator=generator)
+    table = torch.zeros((B, 4), dtype=torch.int32)
+    for b in range(B):
+        table[b, 2], table[b, 3] = int(fid[b]), b
+        if float(u[0, b]) >= p:
+            continue
+        name = kinds[min(int(float(u[1, b]) * len(kinds)), len(kinds) - 1)]
+        lo, hi = ranges[name]
+        if name == 'blur':
+            kind, param = 5, min(int(float(u[2, b]) * rows), rows - 1)
+        elif name == 'pixelate':
+            kind, param = 6, min(int(lo) + int(float(u[2, b]) * (int(hi) - int(lo) + 1)), int(hi))
+        else:
+            kind, param, _ = perturbation(name, lo + (hi - lo) * float(u[2, b]))
+        table[b, 0], table[b, 1] = kind, param
+    return table, taps
+
+
+def _luma(px: Tensor) -> Tensor:
+    """the JPEG path's luma of int32 (..., 3) RGB"""
+    return (19595 * px[..., 0] + 38470 * px[..., 1] + 7471 * px[..., 2] + 32768) >> 16
+
+
+def _perturb_frame(v: Tensor, kind: int, p: int, fid: int, stream: int, taps, key) -> Tensor:
+    """one frame int32 (H, W, 3) through one row of the table -> int32 (H, W, 3) in 0..255"""
+    H, W = v.shape[0], v.shape[1]
+    if kind == 1:
+        return ((v * p + 128) >> 8).clamp_(0, 255)
+    if kind == 2:
+        m = (int(_luma(v).to(torch.int64).sum()) + H * W // 2) // (H * W)
+        return (m + (((v - m) * p + 128) >> 8)).clamp_(0, 255)
+    if kind == 3:
+        Y = _luma(v)[..., None]
+        return (Y + (((v - Y) * p + 128) >> 8)).clamp_(0, 255)
+    if kind == 4:
+        words = philox4x32_10((torch.arange(H * W * 3, dtype=torch.int64), fid, stream, 0), key)
+        z = sum((w >> s) & 0xff for w in words for s in (0, 8, 16, 24)) - 2040
+        d = ((z.to(torch.int32) * p) * 887 + (1 << 21)) >> 22
+        return (v + d.reshape(H, W, 3)).clamp_(0, 255)
+    if kind == 5:
+        t = [int(q) for q in taps[p]]
+        ys, xs = torch.arange(H), torch.arange(W)
+        h = sum(t[i] * v[:, (xs + (i - 10)).clamp_(0, W - 1)] for i in range(PERTURB_TAPS) if t[i])
+        a = sum(t[j] * h[(ys + (j - 10)).clamp_(0, H - 1)] for j in range(PERTURB_TAPS) if t[j])
+        return ((a + (1 << 21)) >> 22).clamp_(0, 255)
+    if kind == 6:
+        by, bx = -(-H // p), -(-W // p)
+        pad = torch.zeros((by * p, bx * p, 3), dtype=torch.int32)
+        pad[:H, :W] = v
+        S = pad.reshape(by, p, bx, p, 3).sum((1, 3))
+        rows = (torch.arange(by) * p + p).clamp_(max=H) - torch.arange(by) * p
+        cols = (torch.arange(bx) * p + p).clamp_(max=W) - torch.arange(bx) * p
+        cnt = (rows[:, None] * cols[None, :]).to(torch.int32)[..., None]
+        q = (S + cnt // 2) // cnt
+        return q[torch.arange(H) // p][:, torch.arange(W) // p]
+    return v
+
+
+def perturb_host(u8: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0) -> Tensor:
+    """The definition on the host: uint8 (n, H, W, 3) or (B, T, H, W, 3), any H, W >= 1, table int32 (n, 4) / (B, 4) =
+    (kind, param, frame_id, stream) per frame, or per clip (frame t of a clip then takes the clip's kind, param and stream and
+    frame_id + t) -> uint8 of the same shape.  int32 arithmetic with arithmetic shifts only; clamp is to 0..255, v is a byte
+    of channel c at pixel (y, x), Y = (19595 R + 38470 G + 7471 B + 32768) >> 16 of its pixel:
+
+      0 copy        v
+      1 brightness  clamp((v p + 128) >> 8), p the gain in Q8
+      2 contrast    clamp(m + (((v - m) p + 128) >> 8)), m = (sum of Y over the frame + H W // 2) // (H W), the sum in 64 bits
+      3 saturation  clamp(Y + (((v - Y) p + 128) >> 8))
+      4 noise       clamp(v + d), d = ((z p) 887 + (1 << 21)) >> 22, p the sigma in Q4 grey levels; z = the sum of the 16 bytes
+                    of Philox4x32-10(counter ((y W + x) 3 + c, frame_id, stream, 0), key (seed & 0xffffffff, seed >> 32)) less
+                    2040: Irwin-Hall, standard deviation 295.6, and 2^22 / (16 * 295.6) = 886.8
+      5 blur        clamp((sum_j t[j] sum_i t[i] v(y + j - 10, x + i - 10) + (1 << 21)) >> 22), t = taps[p], coordinates
+                    clamped into the frame (the border replicates)
+      6 pixelate    (S + cnt // 2) // cnt over the p x p block that holds the pixel, blocks laid from the frame's corner and
+                    cut to the frame: S the block's sum of channel c, cnt its real number of pixels
+
+    With p = 256 kinds 1 to 3 are the identity.  The noise of a byte depends on (seed, stream, frame_id, y, x, c) alone."""
+    if u8.dtype != torch.uint8 or u8.dim() not in (4, 5) or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError('perturb_host expects non-empty uint8 (n, H, W, 3) or (B, T, H, W, 3), got %s %s'
+                         % (u8.dtype, tuple(u8.shape)))
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('perturb_host: the seed must lie in [0, 2^64), got %d' % seed)
+    t = check_perturbations(table, u8.shape[0], taps)
+    T = u8.shape[1] if u8.dim() == 5 else 1
+    H, W = u8.shape[-3], u8.shape[-2]
+    src = u8.reshape((-1, H, W, 3)).cpu()
+    tp = None if taps is None else taps.detach().cpu()
+    key = (seed & 0xffffffff, seed >> 32)
+    out = torch.empty_like(src)
+    for f in range(src.shape[0]):
+        kind, p, fid, stream = (int(q) for q in t[f // T])
+        out[f] = _perturb_frame(src[f].to(torch.int32), kind, p, fid + f % T, stream, tp, key).to(torch.uint8)
+    return out.reshape(u8.shape).to(u8.device)

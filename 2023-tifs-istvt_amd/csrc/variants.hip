@@ -6,6 +6,7 @@
 //   * dropout: nn.Dropout in training mode (module.py:29,31,78,187; models_copy.py:41-44) with a Philox4x32-10 stream
 //     keyed by (seed, element index / 4): the mask is stored (one byte per element) for the backward.
 #include "common.h"
+#include "philox.h"
 
 // ------------------------------------------------------------------------------------------ prepend
 // out[s][0] = tok (+ pos[s % period][0]);  out[s][1+i] = src[s][i] (+ pos[s % period][1+i]);   pos: float [period][pos_rows][D]
@@ -199,17 +200,7 @@ extern "C" int istvt_relu_avgpool_bwd(const void* x, const void* dout, void* dx,
 // Philox4x32-10 (Salmon et al.): counter = (group index, 0, 0, 0), key = seed; four 32-bit outputs per group of four
 // consecutive elements.  keep = u >= p * 2^32 (so P(keep) = 1 - p);  y = keep ? x / (1 - p) : 0.
 __device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long seed, unsigned (&r)[4]) {
-    unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+    philox4x32_10((unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), r);   // philox.h
 }
 
 template <typename T>

@@ -246,20 +246,25 @@ class XceptionVidTr(nn.Module):
         crops as a JPEG codec would hand them back at that quality (ops.jpeg_roundtrip_u8); pixel_format='nv12' (with
         yuv_matrix='bt601' | 'bt709' | 'jfif') takes NV12 frames uint8 (N, 3 * Hs / 2, Ws) and needs boxes; score_videos and
         explain_video take both too.  transforms= stands in the boxes' place (never both): one similarity per frame, float32
-        (N, 2, 3), for aligned crops (ops.warp_similarity_u8; clips.similarity_from_landmarks makes them)."""
+        (N, 2, 3), for aligned crops (ops.warp_similarity_u8; clips.similarity_from_landmarks makes them).
+        perturb=(kind_name, value) -- ('blur', 2.0), ('noise', 10.0), ('saturation', 0.4), ('pixelate', 4), ... as
+        clips.perturbation takes them -- degrades the crops on the device first (ops.perturb_u8, before the JPEG round trip
+        when both are given) and perturb_seed keys the noise; score_videos and explain_video take the two as well."""
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score(frames, boxes=boxes, transforms=transforms)
 
     def score_videos(self, videos, boxes=None, labels=None, transforms=None, **kw):
         """Sliding-window scores of a set of videos in one pass (a list of tensors as score_video takes them, one box table
         per video in `boxes`), with accuracy counts and the AUC over the set when `labels` gives one 0 / 1 per video:
-        istvt_amd.video.VideoScorer(self, **kw).score_videos(videos, boxes, labels)"""
+        istvt_amd.video.VideoScorer(self, **kw).score_videos(videos, boxes, labels).  With perturb=(kind_name, value) among the
+        keywords every video is degraded on the device as score_video describes, video v of the list as noise stream v."""
         from istvt_amd import video
         return video.VideoScorer(self, **kw).score_videos(videos, boxes=boxes, labels=labels, transforms=transforms)
 
     def explain_video(self, frames, index=0, boxes=None, transforms=None, **kw):
         """Per-frame relevance maps of one video (frames and boxes as score_video takes them) for output `index`:
-        istvt_amd.video.VideoScorer(self, **kw).explain(frames, index, boxes)"""
+        istvt_amd.video.VideoScorer(self, **kw).explain(frames, index, boxes); perturb= and perturb_seed= among the keywords
+        explain the degraded video (score_video)."""
         from istvt_amd import video
         return video.VideoScorer(self, **kw).explain(frames, index, boxes=boxes, transforms=transforms)
 

@@ -1301,6 +1301,68 @@ def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Op
     return out
 
 
+def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,
+               checked: bool = False) -> Tensor:
+    """Perturbations (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, table int32 [n,4] = (kind, param,
+    frame_id, stream) per frame or, for clips, [B,4] per clip (frame t of a clip takes its clip's kind, param and stream and
+    frame_id + t), taps int32 [K,21] (clips.gaussian_taps; needed where a row blurs), seed the 64-bit key of the noise -> uint8
+    of the same shape: brightness, contrast, saturation, Gaussian noise, Gaussian blur or pixelation per frame, the bits of
+    clips.perturb_host.  A host table (and host taps) is validated (clips.check_perturbations) before any launch and uploaded
+    without blocking; checked=True takes a device table, and device taps, that the caller has validated already and reads
+    nothing back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.
+    `out` (uint8, contiguous, of the input's shape) is written when given; it may not share memory with the input, whose
+    neighbours blur and pixelation read."""
+    from . import clips
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('perturb_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
+        raise RuntimeError('perturb_u8 expects channels-last (n, H, W, 3) or (B, T, H, W, 3) uint8 input, got %s'
+                           % (tuple(frames.shape),))
+    if frames.numel() == 0:
+        raise RuntimeError('perturb_u8: empty input %s' % (tuple(frames.shape),))
+    if not frames.is_contiguous():
+        raise RuntimeError('perturb_u8: frames must be contiguous, got strides %s for %s'
+                           % (tuple(frames.stride()), tuple(frames.shape)))
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('perturb_u8: the seed must lie in [0, 2^64), got %d' % seed)
+    H, W = frames.shape[-3], frames.shape[-2]
+    if H > 16384 or W > 16384:
+        raise ValueError('perturb_u8: frames of at most 16384 x 16384, got %d x %d' % (H, W))
+    src = frames.view((-1, H, W, 3))
+    n, rows = src.shape[0], frames.shape[0]
+    if checked:
+        if (not torch.is_tensor(table) or table.dtype != torch.int32 or tuple(table.shape) != (rows, 4)
+                or table.device != src.device):
+            raise RuntimeError('perturb_u8: a checked table is int32 (%d, 4) on %s' % (rows, src.device))
+        if taps is not None and (not torch.is_tensor(taps) or taps.dtype != torch.int32 or taps.dim() != 2
+                                 or taps.shape[1] != clips.PERTURB_TAPS
+                                 or not 1 <= taps.shape[0] <= clips.PERTURB_MAX_TAPS_ROWS or taps.device != src.device):
+            raise RuntimeError('perturb_u8: checked taps are int32 (K, 21), K <= %d, on %s'
+                               % (clips.PERTURB_MAX_TAPS_ROWS, src.device))
+        tdev, pdev = _c(table), None if taps is None else _c(taps)
+    else:
+        if (torch.is_tensor(table) and table.is_cuda) or (torch.is_tensor(taps) and taps.is_cuda):
+            raise RuntimeError('perturb_u8: a device table or device taps are taken with checked=True only (validated by the '
+                               'caller); hand over the host tensors otherwise')
+        tdev = clips.check_perturbations(table, rows, taps).contiguous().to(src.device, non_blocking=True)
+        pdev = None if taps is None else taps.detach().contiguous().to(src.device, non_blocking=True)
+    out = _u8_out('perturb_u8', frames, frames.shape, out)
+    nbytes = src.numel()
+    if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
+        raise RuntimeError('perturb_u8: out may not share memory with the input (blur and pixelation read their neighbours)')
+    strips = min(32, -(-(H * W) // 2048))                         # partial sums of Y per frame, for the contrast mean
+    scratch = torch.empty((n * strips,), dtype=torch.int64, device=src.device)
+    with prof('perturb_u8', 2 * nbytes):
+        _lib.check(_lib.lib().istvt_perturb_u8(src.data_ptr(), nbytes, n, H, W, tdev.data_ptr(),
+                                               frames.shape[1] if frames.dim() == 5 else 0,
+                                               0 if pdev is None else pdev.data_ptr(), 0 if pdev is None else pdev.shape[0], seed,
+                                               scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream()),
+                   'istvt_perturb_u8')
+    return out
+
+
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,
                need_dfeats: bool) -> Optional[Tensor]:
     dx, lddx = rows(_req(dx))

@@ -485,6 +485,14 @@ class VideoScorer:
                   just before the stem, after the crop when a call passes `boxes` -- the S x S crops the stem reads are
                   recompressed, not the whole frames.  score(), push(), score_videos() and explain() then give the bits they
                   give on ops.jpeg_roundtrip_u8(crops, jpeg_quality); float frames raise TypeError.
+    perturb       None, or a (kind_name, value) pair as clips.perturbation takes it -- ('blur', 2.0), ('noise', 10.0),
+                  ('saturation', 0.4), ('pixelate', 4), ...: every uint8 stem batch goes through ops.perturb_u8, after the crop
+                  when a call passes `boxes` or `transforms` and before the JPEG round trip when jpeg_quality is set too (a
+                  perturbed video is then compressed).  A frame's row is (kind, param, its index in its video -- counted since
+                  reset() for push() --, its video's index in the call -- 0 for score(), push() and explain()), so with tab,
+                  taps = clips.perturbation_table(N, *perturb) the scorer gives the bits it gives on ops.perturb_u8(crops,
+                  tab, taps, perturb_seed), whatever the batches; float frames raise TypeError.
+    perturb_seed  the 64-bit key of the noise.
     pixel_format  'rgb24' (packed RGB, the default) or 'nv12': every call then takes NV12 frames uint8 (N, 3 * Hs / 2, Ws) and
                   needs `boxes` (ValueError without; frames that already are the crops take identity boxes).  The crop reads
                   the NV12 bytes itself (ops.crop_resize_nv12): the bits of the 'rgb24' scorer on
@@ -500,7 +508,7 @@ class VideoScorer:
     def __init__(self, model, stride: int = 1, frame_batch: int = 64, window_batch: int = 32,
                  capacity: Optional[int] = None, mean: Sequence[float] = DEFAULT_MEAN, std: Sequence[float] = DEFAULT_STD,
                  cover_tail: bool = True, side: Optional[int] = None, jpeg_quality: Optional[int] = None,
-                 pixel_format: str = 'rgb24', yuv_matrix: str = 'bt709'):
+                 pixel_format: str = 'rgb24', yuv_matrix: str = 'bt709', perturb=None, perturb_seed: int = 0):
         vit = getattr(model, 'vit', None)
         if vit is None or not hasattr(model, 'xcep') or not hasattr(vit, 'forward_tokens'):
             raise TypeError('VideoScorer: expected an XceptionVidTr, got %s' % type(model).__name__)
@@ -529,6 +537,15 @@ class VideoScorer:
         if yuv_matrix not in clips.YUV_MATRICES:
             raise ValueError("VideoScorer: yuv_matrix must be 'bt601', 'bt709' or 'jfif', got %r" % (yuv_matrix,))
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
+        self.perturb = None                # (kind, param, host taps or None) of clips.perturbation
+        if perturb is not None:
+            if not isinstance(perturb, (tuple, list)) or len(perturb) != 2:
+                raise ValueError('VideoScorer: perturb must be None or a (kind_name, value) pair, got %r' % (perturb,))
+            self.perturb = clips.perturbation(*perturb)
+        self.perturb_seed = int(perturb_seed)
+        if not 0 <= self.perturb_seed < 2 ** 64:
+            raise ValueError('VideoScorer: perturb_seed must lie in [0, 2^64), got %r' % (perturb_seed,))
+        self._taps = None                  # the perturbation's taps on the device
         self._norm = None                  # (device, mean tensor, std tensor)
         self._jpeg = None                  # the device quality table of a stem batch: jpeg_quality, frame_batch times
         self.reset()
@@ -553,6 +570,8 @@ class VideoScorer:
             if self.jpeg_quality is not None and reads == 'f32':
                 raise TypeError('VideoScorer: jpeg_quality recompresses decoded uint8 frames; normalised float frames cannot '
                                 'take it')
+            if self.perturb is not None and reads == 'f32':
+                raise TypeError('VideoScorer: perturb degrades decoded uint8 frames; normalised float frames cannot take it')
             return VideoInput(reads, False, None, None)
         if boxes is None:
             raise ValueError("VideoScorer: pixel_format='nv12' needs boxes or transforms with every call (one (y0, x0, h, w) or "
@@ -560,14 +579,32 @@ class VideoScorer:
         side = self.side if self.side is not None else getattr(self.model, 'crop_side', None)
         return VideoInput('u8', True, side, check_boxed_frames(frames, boxes, side, self.pixel_format))
 
-    def _fetcher(self, videos, inputs: Sequence[VideoInput], pieces, dev):
+    def _fetcher(self, videos, inputs: Sequence[VideoInput], pieces, dev, frame0: int = 0):
         """-> fetch(first, count), the stem batch of frames [first, first + count) of the executor's steps;
         pieces(first, count) names them as (video, lo, hi).  The tables are uploaded here, once.  The inputs of one call are
         all of one kind (_check_set and _input see to it: boxes for every video, transforms for every video, or neither), so
-        the first one speaks for the set."""
+        the first one speaks for the set.  frame0: the index in its video of frame 0 of `videos[0]` (push(): the frames the
+        stream has seen), which only a perturbation reads."""
         bdev = [i.table.contiguous().to(dev, non_blocking=True) for i in inputs] if inputs[0].boxed else None
-        return lambda first, count: self._frame_batch(videos, pieces(first, count), bdev, inputs[0].side, dev,
-                                                      inputs[0].aligned)
+        if self.perturb is None:
+            return lambda first, count: self._frame_batch(videos, pieces(first, count), bdev, inputs[0].side, dev,
+                                                          inputs[0].aligned)
+
+        def fetch(first, count):
+            ps = pieces(first, count)
+            return self._perturbed(self._frame_batch(videos, ps, bdev, inputs[0].side, dev, inputs[0].aligned), ps, dev, frame0)
+        return fetch
+
+    def _perturbed(self, x: Tensor, pieces, dev, frame0: int) -> Tensor:
+        """the stem batch of (video, lo, hi) pieces through ops.perturb_u8: frame i of video v is (kind, param, frame0 + i, v)"""
+        kind, param, taps = self.perturb
+        if not x.is_cuda:                  # host frames: pinned, then copied on the current stream
+            x = x.contiguous().pin_memory().to(dev, non_blocking=True)
+        table = torch.tensor([(kind, param, frame0 + i, v) for v, lo, hi in pieces for i in range(lo, hi)], dtype=torch.int32)
+        if taps is not None and (self._taps is None or self._taps.device != dev):
+            self._taps = taps.to(dev)
+        return ops.perturb_u8(x.contiguous(), table.pin_memory().to(dev, non_blocking=True),
+                              None if taps is None else self._taps, self.perturb_seed, checked=True)
 
     def _frame_batch(self, videos, pieces, bdev, side, dev, aligned: bool = False) -> Tensor:
         """One stem batch from (video, lo, hi) pieces.  Without boxes a single piece is used where it lies (_stem uploads a
@@ -680,7 +717,7 @@ class VideoScorer:
             self._plan = RingPlan(self.T, self.stride, cap, self.frame_batch, self.window_batch)
         self._kind = inp._replace(table=None)
         base = self._plan.seen
-        fetch = self._fetcher([frames], [inp], lambda first, count: [(0, first - base, first - base + count)], dev)
+        fetch = self._fetcher([frames], [inp], lambda first, count: [(0, first - base, first - base + count)], dev, base)
         self._ring, logits, starts = self._execute(self._plan.push(int(frames.shape[0])), self._ring, self._plan.capacity, dev,
                                                    fetch, inp.reads)
         return logits, torch.tensor(starts, dtype=torch.int64)

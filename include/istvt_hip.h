@@ -357,6 +357,22 @@ int istvt_warp_similarity_nv12(const void* frames, long total, int Hs, int Ws, l
  * (multiples of 8).  Two launches, no synchronisation, no atomics.  H, W <= 16384. */
 int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W, const int* quality, int subsampling,
                             void* scratch, long scratch_bytes, void* out, istvt_stream_t stream);
+/* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
+ * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
+ * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with
+ * frames: ISTVT_ERR_SHAPE).  int32 arithmetic with arithmetic shifts only, the bits of clips.perturb_host; v = a byte, Y = (19595
+ * R + 38470 G + 7471 B + 32768) >> 16 of its pixel, clamp to 0..255.  kind 0: v.  1 (brightness, param = gain in Q8): clamp((v p
+ * + 128) >> 8).  2 (contrast, Q8): clamp(m + (((v - m) p + 128) >> 8)), m = (sum of Y over the frame + H W / 2) / (H W).  3
+ * (saturation, Q8): clamp(Y + (((v - Y) p + 128) >> 8)).  4 (noise, param = sigma in Q4 grey levels, <= 1023): clamp(v + (((z p)
+ * 887 + (1 << 21)) >> 22)), z = the sum of the 16 bytes of Philox4x32-10(counter ((y W + x) 3 + c, frame_id, stream, 0), key
+ * (seed & 0xffffffff, seed >> 32)) less 2040.  5 (blur, param = a row of taps): clamp((sum_j t[j] sum_i t[i] v(y + j - 10, x + i
+ * - 10) + (1 << 21)) >> 22), coordinates clamped into the frame; taps int32 [taps_rows][21] on the device, taps_rows <= 16, every
+ * row symmetric about index 10, non-negative, summing to 2048 (a null taps blurs nothing).  6 (pixelate, param = block side k in
+ * 2..32): (S + cnt / 2) / cnt over the k x k block that holds the pixel, blocks laid from the frame's corner and cut to it.  A
+ * kind outside 0..6 copies; a param outside its range is forced into it for kinds 5 and 6.  scratch: 8-byte aligned, n * min(32,
+ * ceil(H W / 2048)) * 8 bytes.  Three launches, no synchronisation, no atomics, no state.  H, W <= 16384. */
+int istvt_perturb_u8(const void* frames, long total, int n, int H, int W, const int* table, int per_clip_T, const int* taps,
+                     int taps_rows, unsigned long long seed, void* scratch, long scratch_bytes, void* out, istvt_stream_t stream);
 int istvt_conv2_fwd(const void* u1, const float* bnp, const void* w, void* u2, int frames, int H, int W,
                     istvt_stream_t stream);
 int istvt_conv2_dgrad(const void* du2, const void* w, const void* u1, const float* bnp, void* dz1, int frames, int H,
