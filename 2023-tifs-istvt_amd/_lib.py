@@ -64,6 +64,8 @@ SIGNATURES = {
     'istvt_nv12_to_rgb_u8': [P, L, I, I, L, L, P, P, I, P],
     'istvt_warp_similarity_u8': [P, L, I, I, P, P, I, I, P],
     'istvt_warp_similarity_nv12': [P, L, I, I, L, L, P, P, P, I, I, P],
+    'istvt_relevance_paste_u8': [P, L, I, I, P, I, P, P, P, P, I, I, P],
+    'istvt_relevance_paste_nv12': [P, L, I, I, L, L, P, I, P, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
     'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],

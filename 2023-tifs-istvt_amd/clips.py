@@ -31,6 +31,10 @@ Perturbations (DESIGN.md "Perturbations") are the sixth: ``perturb_host`` (the d
 brightness, contrast, saturation, Gaussian noise from Philox4x32-10, Gaussian blur with integer taps, pixelation),
 ``gaussian_taps``, ``check_perturbations``, ``perturbation``, ``perturbation_table``, ``random_perturbations`` and the ladder
 ``PERTURBATION_LEVELS``.  In training ``ops.perturb_u8(u8, table, taps, seed)`` stands where the JPEG round trip stands above.
+
+Pasting maps onto frames (DESIGN.md "Pasting maps onto frames") is the seventh: ``paste_geometry`` (a box or a similarity as
+the map from frame pixels to crop coordinates, and the rectangle to look at), ``paste_maps_host`` (the definition of
+ops.relevance_paste_u8 / ops.relevance_paste_nv12: float64 field, int32 blend), ``paste_field_host`` and ``lut_to_ycc``.
 """
 import math
 from fractions import Fraction
@@ -1043,3 +1047,188 @@ def perturb_host(u8: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed:
         kind, p, fid, stream = (int(q) for q in t[f // T])
         out[f] = _perturb_frame(src[f].to(torch.int32), kind, p, fid + f % T, stream, tp, key).to(torch.uint8)
     return out.reshape(u8.shape).to(u8.device)
+
+
+# ------------------------------------------------------------------------------------------ pasting maps onto frames
+# DESIGN.md "Pasting maps onto frames": a relevance map (g x g, in crop coordinates) blended onto the whole frame it was
+# cut from, through the box or the similarity that cut the crop, in the frame's own format.  Per frame a 2 x 3 float64 map
+# A takes the CENTRE of source pixel (sx, sy) to crop coordinates,
+#
+#     u = (a00 (sx + .5) + a01 (sy + .5)) + a02        v = (a10 (sx + .5) + a11 (sy + .5)) + a12
+#
+# and the crop covers [0, S) x [0, S): a pixel is in the region when 0 <= u < S and 0 <= v < S.  paste_geometry makes A and
+# the rectangle to look at, paste_maps_host is the definition, ops.relevance_paste_u8 / _nv12 are the device kernels.
+PASTE_MAX_GRID = 19
+
+
+def _paste_rect(xlo, xhi, ylo, yhi, Hs: int, Ws: int, even: bool) -> Tensor:
+    """(y0, x0, h, w) int32 of the pixel ranges [xlo, xhi) x [ylo, yhi) (int64 tensors) clamped into the frame, aligned
+    outward to even coordinates for NV12"""
+    x0, x1 = xlo.clamp(0, Ws), xhi.clamp(0, Ws)
+    y0, y1 = ylo.clamp(0, Hs), yhi.clamp(0, Hs)
+    if even:
+        x0, y0 = x0 - x0 % 2, y0 - y0 % 2
+        x1, y1 = (x1 + x1 % 2).clamp(max=Ws), (y1 + y1 % 2).clamp(max=Hs)
+    return torch.stack([y0, x0, (y1 - y0).clamp(min=0), (x1 - x0).clamp(min=0)], dim=1).to(torch.int32).contiguous()
+
+
+def paste_geometry(n: int, Hs: int, Ws: int, S: int, boxes=None, transforms=None, even: bool = False):
+    """The geometry of a paste from the table that cut the crops: exactly one of boxes int32 (n, 4) = (y0, x0, h, w)
+    (check_boxes; h != w is fine) and transforms float32 (n, 2, 3) (check_similarities) -> (A float64 (n, 2, 3), rect int32
+    (n, 4) = (y0, x0, h, w)), both on the host.  A box gives A = [[S / w, 0, -x0 S / w], [0, S / h, -y0 S / h]]; a similarity M
+    gives the closed-form float64 inverse of the float32 table.  rect is the bounding rectangle of the crop square's image in
+    the frame, widened by one pixel and clamped into the frame (even=True, for NV12 frames: aligned outward to even
+    coordinates; Hs and Ws must be even).  It says only where a kernel has to look: whether a pixel is inside is decided by
+    (u, v), so a rectangle that is too large is harmless."""
+    if (boxes is None) == (transforms is None):
+        raise ValueError('paste_geometry: boxes and transforms are two ways to cut the same crop: pass exactly one of them')
+    if even and (Hs % 2 or Ws % 2):
+        raise ValueError('paste_geometry: even=True needs even Hs and Ws, got %d x %d' % (Hs, Ws))
+    A = torch.zeros((n, 2, 3), dtype=torch.float64)
+    if boxes is not None:
+        b = check_boxes(boxes, n, Hs, Ws, S).to(torch.int64)
+        y0, x0, h, w = (b[:, i].to(torch.float64) for i in range(4))
+        A[:, 0, 0], A[:, 1, 1] = S / w, S / h
+        A[:, 0, 2], A[:, 1, 2] = -x0 * S / w, -y0 * S / h
+        return A, _paste_rect(b[:, 1] - 1, b[:, 1] + b[:, 3] + 1, b[:, 0] - 1, b[:, 0] + b[:, 2] + 1, Hs, Ws, even)
+    m = check_similarities(transforms, n, Hs, Ws, S).to(torch.float64)
+    det = m[:, 0, 0] * m[:, 1, 1] - m[:, 0, 1] * m[:, 1, 0]
+    A[:, 0, 0], A[:, 0, 1] = m[:, 1, 1] / det, -m[:, 0, 1] / det
+    A[:, 1, 0], A[:, 1, 1] = -m[:, 1, 0] / det, m[:, 0, 0] / det
+    A[:, 0, 2] = -(A[:, 0, 0] * m[:, 0, 2] + A[:, 0, 1] * m[:, 1, 2])
+    A[:, 1, 2] = -(A[:, 1, 0] * m[:, 0, 2] + A[:, 1, 1] * m[:, 1, 2])
+    corners = torch.tensor([[0.0, 0.0, 1.0], [S, 0.0, 1.0], [0.0, S, 1.0], [S, S, 1.0]], dtype=torch.float64)
+    pts = torch.einsum('nij,kj->nki', m, corners)                 # (n, 4, 2) as (x, y)
+    lo, hi = torch.floor(pts.min(1).values).to(torch.int64), torch.ceil(pts.max(1).values).to(torch.int64)
+    return A, _paste_rect(lo[:, 0] - 1, hi[:, 0] + 1, lo[:, 1] - 1, hi[:, 1] + 1, Hs, Ws, even)
+
+
+def lut_to_ycc(lut: Tensor, matrix: str = 'bt709') -> Tensor:
+    """A colour table uint8 (256, 3) of R'G'B' as (Y, Cb, Cr) uint8 (256, 3) in the space of `matrix`: the float64 forward
+    formulas of rgb_to_nv12_host on every colour, rounded half up, clamped to 0..255.  Where `lut` lives."""
+    if not torch.is_tensor(lut) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError('lut_to_ycc: lut must be uint8 (256, 3)')
+    if matrix not in YUV_MATRICES:
+        raise ValueError("matrix must be 'bt601', 'bt709' or 'jfif', got %r" % (matrix,))
+    kr, kb = (float(v) for v in NV12_MATRICES['bt601' if matrix == 'jfif' else matrix])
+    ys, cs = (1.0, 1.0) if matrix == 'jfif' else (219.0 / 255.0, 224.0 / 255.0)
+    R, G, B = lut.to(torch.float64).unbind(-1)
+    yp = kr * R + (1.0 - kr - kb) * G + kb * B
+    Y = (0.0 if matrix == 'jfif' else 16.0) + ys * yp
+    Cb = 128.0 + cs * ((B - yp) / (2.0 * (1.0 - kb)))
+    Cr = 128.0 + cs * ((R - yp) / (2.0 * (1.0 - kr)))
+    return torch.floor(torch.stack([Y, Cb, Cr], dim=1) + 0.5).clamp_(0, 255).to(torch.uint8)
+
+
+def paste_field_host(grid: Tensor, A: Tensor, rect, S: int):
+    """One frame's field: grid float32 (g, g), A float64 (2, 3), rect = (y0, x0, h, w) already clamped into the frame ->
+    (m float64 (h, w): the normalised map at every pixel of the rectangle, zero outside the region; inside bool (h, w)), or
+    None when the map holds a non-finite entry.  Steps 1 and 2 of paste_maps_host."""
+    g = int(grid.shape[0])
+    if not bool(torch.isfinite(grid).all()):
+        return None
+    mn, mx = grid.min().to(torch.float64), grid.max().to(torch.float64)
+    mhat = torch.zeros((g, g), dtype=torch.float64) if float(mx) == float(mn) else (grid.to(torch.float64) - mn) / (mx - mn)
+    y0, x0, h, w = (int(v) for v in rect)
+    px = (torch.arange(x0, x0 + w, dtype=torch.float64) + 0.5)[None, :]
+    py = (torch.arange(y0, y0 + h, dtype=torch.float64) + 0.5)[:, None]
+    a = A.to(torch.float64)
+    u = (a[0, 0] * px + a[0, 1] * py) + a[0, 2]
+    v = (a[1, 0] * px + a[1, 1] * py) + a[1, 2]
+    inside = (u >= 0) & (u < S) & (v >= 0) & (v < S)
+    r = float(g) / float(S)
+    gu = torch.where(inside, u * r - 0.5, torch.zeros_like(u))
+    gv = torch.where(inside, v * r - 0.5, torch.zeros_like(v))
+    fx0, fy0 = torch.floor(gu), torch.floor(gv)
+    fx, fy = gu - fx0, gv - fy0
+    ix0, iy0 = fx0.to(torch.int64), fy0.to(torch.int64)
+    ix1, iy1 = (ix0 + 1).clamp(0, g - 1), (iy0 + 1).clamp(0, g - 1)
+    ix0, iy0 = ix0.clamp(0, g - 1), iy0.clamp(0, g - 1)
+    m00, m01, m10, m11 = mhat[iy0, ix0], mhat[iy0, ix1], mhat[iy1, ix0], mhat[iy1, ix1]
+    top = m00 + fx * (m01 - m00)                                  # horizontal pairs first, then vertical
+    bot = m10 + fx * (m11 - m10)
+    m = top + fy * (bot - top)
+    return torch.where(inside, m, torch.zeros_like(m)), inside
+
+
+def paste_maps_host(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+                    pixel_format: str = 'rgb24', yuv_matrix: str = 'bt709') -> Tensor:
+    """The definition on the host, in float64 and int32: frames uint8 (n, Hs, Ws, 3) ('rgb24') or NV12 uint8 (n, 3 Hs / 2, Ws)
+    ('nv12'), maps float32 (n, g, g) or (n, g * g), g <= 19, A float64 (n, 2, 3) and rect int32 (n, 4) as paste_geometry makes
+    them, lut uint8 (256, 3) of R'G'B' colours, alpha a float or float32 (n,) -> the frames with the maps pasted on, a new
+    tensor.  Per frame, over the pixels of rect clamped into the frame (NV12: aligned outward to even coordinates):
+
+      1  mhat = (map - min) / (max - min) over the g x g cells, in float64 (a constant map: zeros; a non-finite entry in the
+         map, in A or in alpha: the frame is left untouched)
+      2  in the region (0 <= u < S and 0 <= v < S): gu = u (g / S) - .5, gv likewise; x = floor(gu), f = gu - x; the four cells
+         (clamp(y, 0, g - 1), clamp(x, 0, g - 1)) ... (clamp(y + 1), clamp(x + 1)); a + f (b - a) along x for both rows, then
+         along y: m
+      3  k = clamp(floor(255 m + .5), 0, 255), w = clamp(floor((256 alpha_n) m + .5), 0, 256); outside the region w = 0
+      4  'rgb24': out_c = (frame_c (256 - w) + lut[k][c] w + 128) >> 8
+      5  'nv12', with lut_ycc = lut_to_ycc(lut, yuv_matrix): Y_out = (Y (256 - w) + lutY[k] w + 128) >> 8 per pixel; per 2 x 2
+         block with its four (k_i, w_i): C_out = (C (1024 - sum w_i) + sum w_i lutC[k_i] + 512) >> 10 for Cb and Cr
+
+    alpha = 0, a constant map and every byte outside the region give the input bytes."""
+    if pixel_format not in ('rgb24', 'nv12'):
+        raise ValueError("paste_maps_host: pixel_format must be 'rgb24' or 'nv12', got %r" % (pixel_format,))
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise TypeError('paste_maps_host: frames must be a uint8 tensor')
+    if pixel_format == 'nv12':
+        if frames.dim() != 3:
+            raise ValueError('paste_maps_host: NV12 frames must be (n, 3 * Hs / 2, Ws), got %s' % (tuple(frames.shape),))
+        Hs, Ws = check_nv12(frames)
+    else:
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError('paste_maps_host: frames must be (n, Hs, Ws, 3), got %s' % (tuple(frames.shape),))
+        Hs, Ws = int(frames.shape[1]), int(frames.shape[2])
+    n = int(frames.shape[0])
+    maps = maps.detach().cpu()
+    if maps.dtype != torch.float32 or maps.dim() not in (2, 3) or maps.shape[0] != n:
+        raise ValueError('paste_maps_host: maps must be float32 (%d, g, g) or (%d, g * g), got %s %s'
+                         % (n, n, maps.dtype, tuple(maps.shape)))
+    g = int(maps.shape[1]) if maps.dim() == 3 else int(round(maps.shape[1] ** 0.5))
+    if g < 1 or g > PASTE_MAX_GRID or maps.numel() != n * g * g:
+        raise ValueError('paste_maps_host: a square grid of at most %d x %d cells expected, got %s'
+                         % (PASTE_MAX_GRID, PASTE_MAX_GRID, tuple(maps.shape)))
+    maps = maps.reshape(n, g, g)
+    if tuple(A.shape) != (n, 2, 3) or A.dtype != torch.float64 or tuple(rect.shape) != (n, 4) or rect.dtype != torch.int32:
+        raise ValueError('paste_maps_host: A float64 (%d, 2, 3) and rect int32 (%d, 4) expected' % (n, n))
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError('paste_maps_host: lut must be uint8 (256, 3)')
+    al = alpha.detach().cpu().to(torch.float32) if torch.is_tensor(alpha) else torch.full((n,), float(alpha), dtype=torch.float32)
+    if tuple(al.shape) != (n,):
+        raise ValueError('paste_maps_host: alpha is a float or float32 (%d,)' % n)
+    A, rect = A.detach().cpu(), rect.detach().cpu().to(torch.int64)
+    nv = pixel_format == 'nv12'
+    table = (lut_to_ycc(lut.cpu(), yuv_matrix) if nv else lut.cpu()).to(torch.int32)
+    out = frames.detach().cpu().clone()
+    for f in range(n):
+        if not bool(torch.isfinite(A[f]).all()) or not bool(torch.isfinite(al[f])):
+            continue
+        y0, x0 = int(rect[f, 0].clamp(0, Hs)), int(rect[f, 1].clamp(0, Ws))
+        y1, x1 = int((rect[f, 0] + rect[f, 2]).clamp(y0, Hs)), int((rect[f, 1] + rect[f, 3]).clamp(x0, Ws))
+        if nv:
+            y0, x0, y1, x1 = y0 - y0 % 2, x0 - x0 % 2, y1 + y1 % 2, x1 + x1 % 2
+        if y1 <= y0 or x1 <= x0:
+            continue
+        field = paste_field_host(maps[f], A[f], (y0, x0, y1 - y0, x1 - x0), S)
+        if field is None:
+            continue
+        m, inside = field
+        k = torch.floor(255.0 * m + 0.5).to(torch.int64).clamp_(0, 255)
+        w = torch.floor((256.0 * al[f].to(torch.float64)) * m + 0.5).clamp_(0, 256).to(torch.int32)
+        w = torch.where(inside, w, torch.zeros_like(w))
+        if not nv:
+            px = out[f, y0:y1, x0:x1].to(torch.int32)
+            out[f, y0:y1, x0:x1] = ((px * (256 - w)[:, :, None] + table[k] * w[:, :, None] + 128) >> 8).to(torch.uint8)
+            continue
+        Y = out[f, y0:y1, x0:x1].to(torch.int32)
+        out[f, y0:y1, x0:x1] = ((Y * (256 - w) + table[k][:, :, 0] * w + 128) >> 8).to(torch.uint8)
+        hb, wb = (y1 - y0) // 2, (x1 - x0) // 2
+        sw = w.reshape(hb, 2, wb, 2).sum(dim=(1, 3))
+        cy0, cy1 = Hs + y0 // 2, Hs + y1 // 2
+        for c in (1, 2):
+            sc = (table[k][:, :, c] * w).reshape(hb, 2, wb, 2).sum(dim=(1, 3))
+            C = out[f, cy0:cy1, x0 + c - 1:x1:2].to(torch.int32)
+            out[f, cy0:cy1, x0 + c - 1:x1:2] = ((C * (1024 - sw) + sc + 512) >> 10).to(torch.uint8)
+    return out.to(frames.device)

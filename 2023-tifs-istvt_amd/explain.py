@@ -156,3 +156,39 @@ def overlay(frames_u8, maps, scale: int = 16, lut=None):
     if lut is None:
         lut = jet_lut(frames_u8.device)
     return ops.relevance_overlay_u8(frames_u8, maps, lut, scale)
+
+
+def _paste_setup(n, Hs, Ws, side, boxes, transforms, lut, pixel_format, yuv_matrix):
+    """the host half of a paste: geometry from the table that cut the crops and the colour table in the frames' space, ->
+    (A, rect, lut) on the host, for one upload each.  Every argument error is raised here, before the device is touched."""
+    from . import clips
+    nv = pixel_format == 'nv12'
+    A, rect = clips.paste_geometry(n, Hs, Ws, side, boxes=boxes, transforms=transforms, even=nv)
+    if lut is None:
+        lut = jet_lut()
+    if not torch.is_tensor(lut) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise ValueError('lut must be uint8 (256, 3), got %s' % (tuple(lut.shape) if torch.is_tensor(lut) else type(lut).__name__,))
+    if nv:
+        lut = clips.lut_to_ycc(lut.cpu(), yuv_matrix)
+    return A, rect, lut.cpu().contiguous()
+
+
+def overlay_frames(frames, maps, boxes=None, transforms=None, side=None, alpha=0.5, lut=None, pixel_format: str = 'rgb24',
+                   yuv_matrix: str = 'bt709', inplace: bool = False):
+    """Relevance maps pasted back onto the whole frames their crops were cut from (DESIGN.md "Pasting maps onto frames"):
+    frames uint8 (N, Hs, Ws, 3) -- pixel_format 'nv12': (N, 3 * Hs / 2, Ws) -- on the device, maps (N, g, g) or (N, g * g)
+    float32 in crop coordinates (VideoExplanation.frame_s, say), exactly one of boxes int32 (N, 4) and transforms float32
+    (N, 2, 3): the table that cut the crops of side `side`; alpha a float or float32 (N,); lut uint8 (256, 3) of RGB colours
+    (default jet_lut()) -> frames of the input's format with every map normalised over its cells, coloured through the
+    table and blended over its face (clips.paste_maps_host is the definition).  inplace=True writes into `frames` and costs
+    the faces' area; several faces per frame are several calls in place."""
+    from . import video
+    if pixel_format not in ('rgb24', 'nv12'):
+        raise ValueError("overlay_frames: pixel_format must be 'rgb24' or 'nv12', got %r" % (pixel_format,))
+    if (boxes is None) == (transforms is None):
+        raise ValueError('overlay_frames: boxes and transforms are two ways to cut the same crop: pass exactly one of them')
+    n, Hs, Ws = video._whole_frames(frames, side, pixel_format, 'boxes' if boxes is not None else 'transforms')
+    A, rect, table = (t.to(frames.device) for t in _paste_setup(n, Hs, Ws, int(side), boxes, transforms, lut, pixel_format,
+                                                                yuv_matrix))
+    paste = ops.relevance_paste_nv12 if pixel_format == 'nv12' else ops.relevance_paste_u8
+    return paste(frames, maps, A, rect, table, alpha, int(side), inplace=inplace, checked=True)

@@ -268,6 +268,15 @@ class XceptionVidTr(nn.Module):
         from istvt_amd import video
         return video.VideoScorer(self, **kw).explain(frames, index, boxes=boxes, transforms=transforms)
 
+    def render_explanation(self, frames, explanation, boxes=None, transforms=None, which='s', alpha=0.5, weight_frames=True,
+                           lut=None, **kw):
+        """The frames of explain_video with its maps pasted onto them through the same boxes or transforms, in the frames'
+        own format: istvt_amd.video.VideoScorer(self, **kw).render_explanation(frames, explanation, ...), with the keywords
+        (side, pixel_format, yuv_matrix, frame_batch) explain_video was given."""
+        from istvt_amd import video
+        return video.VideoScorer(self, **kw).render_explanation(frames, explanation, boxes=boxes, transforms=transforms,
+                                                                which=which, alpha=alpha, weight_frames=weight_frames, lut=lut)
+
     def set_crop_side(self, S):
         """The side S of the crops a view cuts out of larger uint8 source frames.  A token grid does not name it (sixteen
         input sides end at the same grid), so it is a setting: 300 for the reference's 19 x 19 grid, otherwise to be

@@ -1247,6 +1247,122 @@ def warp_similarity_nv12(frames: Tensor, M: Tensor, S: int, matrix: str = 'bt709
     return out
 
 
+def _paste_tables(what: str, frames: Tensor, n: int, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+                  checked: bool):
+    """the device tables of the two pastes -> (maps (n, g * g), g, A, rect, lut, alpha (n,), S).  A and rect: checked tables as
+    they are, or host tables validated (shapes, dtypes, every number of A finite, no negative extent) and uploaded."""
+    S = int(S)
+    if S < 1 or S > 480:
+        raise ValueError('%s: the crop side must lie in [1, 480], got %d' % (what, S))
+    if not torch.is_tensor(maps) or maps.dtype != torch.float32 or maps.dim() not in (2, 3) or maps.shape[0] != n:
+        raise RuntimeError('%s: maps must be float32 (%d, g, g) or (%d, g * g), got %s'
+                           % (what, n, n, (maps.dtype, tuple(maps.shape)) if torch.is_tensor(maps) else type(maps).__name__))
+    g = int(maps.shape[1]) if maps.dim() == 3 else int(round(maps.shape[1] ** 0.5))
+    if not 1 <= g <= 19 or maps.numel() != n * g * g:
+        raise RuntimeError('%s: a square grid of at most 19 x 19 cells per map expected, got %s' % (what, tuple(maps.shape)))
+    if not torch.is_tensor(lut) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise RuntimeError('%s: the colour table must be uint8 (256, 3)' % what)
+    if maps.device != frames.device or lut.device != frames.device:
+        raise RuntimeError('%s: frames, maps and the colour table must share one device' % what)
+    if checked:
+        if A.dtype != torch.float64 or tuple(A.shape) != (n, 2, 3) or A.device != frames.device:
+            raise RuntimeError('%s: a checked A is float64 (%d, 2, 3) on %s' % (what, n, frames.device))
+        if rect.dtype != torch.int32 or tuple(rect.shape) != (n, 4) or rect.device != frames.device:
+            raise RuntimeError('%s: a checked rect is int32 (%d, 4) on %s' % (what, n, frames.device))
+    else:
+        if not torch.is_tensor(A) or A.dtype != torch.float64:
+            raise TypeError('%s: A must be a float64 tensor (n, 2, 3) as clips.paste_geometry makes it' % what)
+        if not torch.is_tensor(rect) or rect.dtype != torch.int32:
+            raise TypeError('%s: rect must be an int32 tensor (n, 4) as clips.paste_geometry makes it' % what)
+        if tuple(A.shape) != (n, 2, 3) or tuple(rect.shape) != (n, 4):
+            raise ValueError('%s: A (%d, 2, 3) and rect (%d, 4) expected, got %s and %s'
+                             % (what, n, n, tuple(A.shape), tuple(rect.shape)))
+        A, rect = A.detach().cpu(), rect.detach().cpu()
+        if not bool(torch.isfinite(A).all()):
+            raise ValueError('%s: every entry of A must be finite' % what)
+        if bool((rect[:, 2:] < 0).any()):
+            raise ValueError('%s: rect = (y0, x0, h, w) with h, w >= 0' % what)
+        A, rect = A.contiguous().to(frames.device), rect.contiguous().to(frames.device)
+    if torch.is_tensor(alpha):
+        if alpha.dtype != torch.float32 or tuple(alpha.shape) != (n,):
+            raise RuntimeError('%s: alpha is a float or a float32 tensor (%d,), got %s %s'
+                               % (what, n, alpha.dtype, tuple(alpha.shape)))
+        alpha = alpha.to(frames.device, non_blocking=True)
+    else:
+        alpha = float(alpha)
+        if alpha != alpha or alpha in (float('inf'), float('-inf')):
+            raise ValueError('%s: alpha must be finite, got %r' % (what, alpha))
+        alpha = torch.full((n,), alpha, dtype=torch.float32, device=frames.device)
+    return _c(maps).view(n, g * g), g, _c(A), _c(rect), _c(lut), _c(alpha), S
+
+
+def relevance_paste_u8(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+                       out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
+    """Relevance maps pasted onto whole frames (clips.paste_maps_host is the definition): frames uint8 [n,Hs,Ws,3] on the
+    device, maps float32 [n,g,g] or [n,g*g] (g <= 19, crop coordinates), A float64 [n,2,3] and rect int32 [n,4] as
+    clips.paste_geometry makes them for crops of side S, lut uint8 [256,3], alpha a float or float32 [n] -> the frames with
+    every map coloured through the table and blended over its face.  A and rect are host tables, validated here and
+    uploaded; checked=True takes device tables as they are (the kernel clamps a rectangle into its frame and leaves a frame
+    with a non-finite A, alpha or map untouched).  inplace=True writes into `frames` (contiguous) and costs the rectangles'
+    area; otherwise the frames are copied once, into `out` when given, and the same launch runs on the copy."""
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('relevance_paste_u8: frames must be uint8, got %s' % frames.dtype)
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError('relevance_paste_u8 expects channels-last (n, Hs, Ws, 3) uint8 input, got %s' % (tuple(frames.shape),))
+    if frames.numel() == 0:
+        raise RuntimeError('relevance_paste_u8: empty input %s' % (tuple(frames.shape),))
+    n, Hs, Ws = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('relevance_paste_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
+    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_u8', frames, n, maps, A, rect, lut, alpha, S, checked)
+    if inplace:
+        if out is not None or not frames.is_contiguous():
+            raise RuntimeError('relevance_paste_u8: inplace=True writes into contiguous frames and takes no out')
+        out = frames
+    else:
+        out = _u8_out('relevance_paste_u8', frames, tuple(frames.shape), out)
+        out.copy_(frames)
+    with prof('relevance_paste_u8', n * g * g * 4):    # + twice the rectangles' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_relevance_paste_u8(out.data_ptr(), out.numel(), Hs, Ws, maps.data_ptr(), g, A.data_ptr(),
+                                                       rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S, _stream()),
+                   'istvt_relevance_paste_u8')
+    return out
+
+
+def relevance_paste_nv12(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut_ycc: Tensor, alpha, S: int,
+                         out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
+    """relevance_paste_u8 on NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] on the device, the pitch and the frame
+    stride taken from the tensor's strides; lut_ycc uint8 [256,3] holds (Y, Cb, Cr) per entry (clips.lut_to_ycc of the RGB
+    table in the frames' matrix); A and rect in pixels of the Hs x Ws picture, rect from paste_geometry(even=True).  The blend
+    runs in the frame's own colour space: no pixel is converted.  inplace=True writes the surface where it lies (frames that
+    do not overlap); otherwise -> a contiguous copy with the maps pasted on."""
+    if inplace and (not torch.is_tensor(frames) or frames.dim() != 3 or frames.stride(-1) != 1):
+        raise RuntimeError('relevance_paste_nv12: inplace=True takes (n, 3 * Hs / 2, Ws) frames with contiguous rows')
+    if torch.is_tensor(frames) and frames.dim() != 3:
+        raise RuntimeError('relevance_paste_nv12 expects NV12 (n, 3 * Hs / 2, Ws) uint8 input, got %s' % (tuple(frames.shape),))
+    Hs, Ws, _, _ = _nv12_source('relevance_paste_nv12', frames, 'bt709')
+    n = int(frames.shape[0])
+    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_nv12', frames, n, maps, A, rect, lut_ycc, alpha, S, checked)
+    if inplace:
+        if out is not None:
+            raise RuntimeError('relevance_paste_nv12: inplace=True takes no out')
+        out = frames
+    else:
+        out = _u8_out('relevance_paste_nv12', frames, tuple(frames.shape), out)
+        out.copy_(frames)
+    pitch, fs = int(out.stride(1)), int(out.stride(0)) if n > 1 else 0
+    rows = Hs + Hs // 2
+    total = (n - 1) * fs + (rows - 1) * pitch + Ws
+    if n > 1 and fs < (rows - 1) * pitch + Ws:
+        raise RuntimeError('relevance_paste_nv12: the frames of a batch written in place may not overlap')
+    with prof('relevance_paste_nv12', n * g * g * 4):  # + twice the rectangles' areas * 3 / 2, which live on the device
+        _lib.check(_lib.lib().istvt_relevance_paste_nv12(out.data_ptr(), total, Hs, Ws, pitch, fs, maps.data_ptr(), g,
+                                                         A.data_ptr(), rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S,
+                                                         _stream()), 'istvt_relevance_paste_nv12')
+    return out
+
+
 def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
                       checked: bool = False) -> Tensor:
     """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for

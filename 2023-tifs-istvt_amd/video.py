@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import contextlib
 import heapq
+import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -781,6 +782,60 @@ class VideoScorer:
         res = VideoExplanation(self._video_score(logits, starts, dev), windows, *fused)
         torch.cuda.current_stream(dev).synchronize()
         return res
+
+    def render_explanation(self, frames: Tensor, explanation: VideoExplanation, boxes=None, transforms=None, which: str = 's',
+                           alpha: float = 0.5, weight_frames: bool = True, lut=None) -> Tensor:
+        """The video an analyst was given, with the heat where the face is (DESIGN.md "Pasting maps onto frames"): the frames
+        of explain() -- with the same boxes or transforms -- and its result -> the frames in their own format (packed RGB or
+        NV12, as the scorer's pixel_format says), uint8 on the device, with explanation.frame_s (which='s') or frame_t ('t')
+        pasted onto every frame through the table that cut its crop (explain.overlay_frames, clips.paste_maps_host).  Without
+        boxes or transforms the frames are the crops themselves, (N, S, S, 3), and the maps cover them.  weight_frames: frame n
+        is blended with alpha_n = (frame_weight[n] / max frame_weight).clamp(0, 1) * alpha (float32, on the device, no
+        synchronisation), so frames the verdict did not rest on stay nearly clean; frames no window covers have zero maps and
+        come back untouched.  lut: uint8 (256, 3) RGB colours (default explain.jet_lut()).  Host frames are pinned, uploaded
+        and pasted frame_batch at a time; device frames are pasted out of place.  The model is not touched."""
+        from . import clips, explain as _explain, ops
+        if which not in ('s', 't'):
+            raise ValueError("render_explanation: which must be 's' or 't', got %r" % (which,))
+        if boxes is not None and transforms is not None:
+            raise ValueError('VideoScorer: boxes and transforms are two ways to cut the same crop: pass one of them')
+        nv = self.pixel_format == 'nv12'
+        if boxes is None and transforms is None:
+            if nv:
+                raise ValueError("VideoScorer: pixel_format='nv12' needs boxes or transforms with every call")
+            if check_frames(frames) != 'u8':
+                raise TypeError('render_explanation pastes onto decoded uint8 frames; normalised float frames cannot take it')
+            side = int(frames.shape[1])
+            boxes = torch.tensor([[0, 0, side, side]] * int(frames.shape[0]), dtype=torch.int32)
+        else:
+            side = self.side if self.side is not None else getattr(self.model, 'crop_side', None)
+        n, Hs, Ws = _whole_frames(frames, side, self.pixel_format, 'boxes' if boxes is not None else 'transforms')
+        maps = explanation.frame_s if which == 's' else explanation.frame_t
+        if maps.shape[0] != n or explanation.frame_weight.shape[0] != n:
+            raise ValueError('render_explanation: the explanation covers %d frames, got %d' % (maps.shape[0], n))
+        alpha = float(alpha)
+        if not math.isfinite(alpha):
+            raise ValueError('render_explanation: alpha must be finite, got %r' % (alpha,))
+        tables = _explain._paste_setup(n, Hs, Ws, int(side), boxes, transforms, lut, self.pixel_format, self.yuv_matrix)
+        dev = self._device()
+        A, rect, table = (t.to(dev) for t in tables)
+        if weight_frames:
+            fw = explanation.frame_weight.to(dev)
+            al = (fw / fw.max()).clamp(0, 1) * alpha
+        else:
+            al = torch.full((n,), alpha, dtype=torch.float32, device=dev)
+        maps = maps.to(dev)
+        paste = ops.relevance_paste_nv12 if nv else ops.relevance_paste_u8
+        out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=dev)
+        for lo in range(0, n, self.frame_batch):
+            hi = min(lo + self.frame_batch, n)
+            x = frames[lo:hi]
+            if not x.is_cuda:              # host frames: pinned, then copied on the current stream
+                x = x.contiguous().pin_memory()
+            out[lo:hi].copy_(x, non_blocking=True)
+            paste(out[lo:hi], maps[lo:hi], A[lo:hi], rect[lo:hi], table, al[lo:hi], int(side), inplace=True, checked=True)
+        torch.cuda.current_stream(dev).synchronize()
+        return out
 
     # ---------------------------------------------------------------------------------------- a set of videos
     def _check_set(self, videos, boxes, transforms=None) -> List[VideoInput]:

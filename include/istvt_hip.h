@@ -346,6 +346,24 @@ int istvt_warp_similarity_u8(const void* frames, long total, int Hs, int Ws, con
                              istvt_stream_t stream);
 int istvt_warp_similarity_nv12(const void* frames, long total, int Hs, int Ws, long pitch, long fstride, const int* coef,
                                const float* M, void* out, int n, int S, istvt_stream_t stream);
+/* Pasting relevance maps onto whole frames, IN PLACE: frames uint8 [n][Hs][Ws][3] (istvt_relevance_paste_u8; `total` bytes at
+ * frames, >= n*Hs*Ws*3, no alignment needed) or NV12 as istvt_crop_resize_nv12 takes them (istvt_relevance_paste_nv12; pitch >=
+ * Ws, frames that do not overlap); maps float32 [n][g][g], g <= 19; A double [n][2][3]: u = (a00 (sx + .5) + a01 (sy + .5)) +
+ * a02, v likewise, take the centre of source pixel (sx, sy) to crop coordinates, the crop covering [0, S)^2; rect int32 [n][4] =
+ * (y0, x0, h, w): where to look (clamped into the frame by the kernel, NV12: then aligned outward to even coordinates; nothing
+ * outside it is read or written); lut uint8 [256][3]: R'G'B' for packed frames, (Y, Cb, Cr) for NV12; alpha float32 [n]; all on
+ * the device.  Per frame, in double with one rounding per operation: mhat = (map - min) / (max - min) over the cells; in the
+ * region 0 <= u, v < S: gu = u (g / S) - .5, x = floor(gu), fx = gu - x, cells clamped to [0, g - 1], a + fx (b - a) along x for
+ * both rows and then along y: m; k = clamp(floor(255 m + .5), 0, 255), w = clamp(floor((256 alpha) m + .5), 0, 256), w = 0
+ * outside the region.  Packed: out_c = (frame_c (256 - w) + lut[k][c] w + 128) >> 8.  NV12: Y likewise with lut[k][0]; per 2 x 2
+ * block C_out = (C (1024 - sum w_i) + sum w_i lut[k_i][c] + 512) >> 10 for Cb (c = 1) and Cr (c = 2).  A frame whose map, A or
+ * alpha holds a non-finite number is left untouched, as is one with a constant map or alpha <= 0.  One launch, one writer per
+ * byte, no atomics: the bits of clips.paste_maps_host wherever 255 m and 256 alpha m are not within rounding of n + 1/2. */
+int istvt_relevance_paste_u8(void* frames, long total, int Hs, int Ws, const float* maps, int g, const double* A,
+                             const int* rect, const void* lut, const float* alpha, int n, int S, istvt_stream_t stream);
+int istvt_relevance_paste_nv12(void* frames, long total, int Hs, int Ws, long pitch, long fstride, const float* maps, int g,
+                               const double* A, const int* rect, const void* lut, const float* alpha, int n, int S,
+                               istvt_stream_t stream);
 /* JPEG round trip: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), quality int32 [n] on the device -> out uint8 [n][H][W][3] (no overlap with frames: ISTVT_ERR_SHAPE), the
  * RGB a baseline JPEG encoder and decoder hand back: libjpeg's 16-bit fixed-point colour transforms, edge replication to whole

@@ -9,6 +9,7 @@
     python tools/video_bench.py --nv12              # NV12 frames: the fused crop against convert + crop (DESIGN.md "NV12 frames")
     python tools/video_bench.py --videos            # a set of 64 videos of 32 frames (DESIGN.md "Scoring a set of videos")
     python tools/video_bench.py --align             # one similarity per frame: the warp against the crop (DESIGN.md "Aligned crops")
+    python tools/video_bench.py --paste             # maps pasted back onto whole frames (DESIGN.md "Pasting maps onto frames")
 
 (a) VideoScorer.score on a device-resident uint8 video; (b) the same windows gathered on the device from the normalised
 float32 video into clips and run through model(clips) in eval mode under no_grad, window_batch clips at a time -- the
@@ -43,6 +44,13 @@ as packed RGB and as NV12, one random similarity per frame (source side --box-si
 mirrored, the rotated square inside the frame).  Events around the launches, the legs alternating, median and range of
 --reps: ops.warp_similarity_u8, ops.warp_similarity_nv12, and the yardstick, ops.crop_resize_u8 on the square boxes of the
 same centres and sides; then score(frames, transforms=...) against score on the warps made beforehand.
+
+--paste (DESIGN.md "Pasting maps onto frames"): --frames frames of --full-size on the device, as packed RGB and as NV12 (random
+bytes), one random similarity per frame as --align draws them, one random 14 x 14 map per frame (--size / 16 cells a side).
+Events around the launches, the legs alternating, median and range of --reps, per format: a plain device copy of the frames
+(the yardstick of the out-of-place form), the paste out of place, the paste in place, and for scale on packed RGB
+ops.warp_similarity_u8 followed by explain.overlay on the crops.  The in-place leg is also given as GB/s over the bytes it
+moves: every rectangle read once and every region written once.  No model is built.
 
 --videos (DESIGN.md "Scoring a set of videos"), strides 8 and 1 unless --strides says otherwise: --set-size device-resident
 uint8 videos of --video-frames frames.  Alternating, medians and spread as above: (a) score_videos(videos, labels=...);
@@ -229,6 +237,61 @@ def boxes_bench(a, model):
                         'max_abs_byte_diff': int((res['c'].int() - crops.int()).abs().max())}
     print('host loop (crop_resize_host + upload): %.0f and %.0f ms | %d of %d bytes differ from the kernel, by at most %d'
           % (th[0], th[1], differ, crops.numel(), out['host_loop']['max_abs_byte_diff']), flush=True)
+    return out
+
+
+def paste_bench(a):
+    import math
+    from istvt_amd import clips, explain
+    Hs, Ws = (int(v) for v in a.full_size.split('x'))
+    lo, hi = (int(v) for v in a.box_sides.split('-'))
+    S, n = a.size, a.frames
+    gc = max(1, min(19, S // 16))
+    g = torch.Generator().manual_seed(2)
+    frames = torch.randint(0, 256, (n, Hs, Ws, 3), generator=g, dtype=torch.uint8).cuda()
+    nv = torch.randint(0, 256, (n, Hs + Hs // 2, Ws), generator=g, dtype=torch.uint8).cuda()
+    side = torch.randint(lo, hi + 1, (n,), generator=g).double()
+    u = torch.rand((4, n), generator=g, dtype=torch.float64)
+    ang = (2 * u[0] - 1) * math.radians(a.degrees)
+    half = 0.5 * side * (torch.cos(ang).abs() + torch.sin(ang).abs())
+    cx, cy = half + u[1] * (Ws - 2 * half), half + u[2] * (Hs - 2 * half)
+    M = clips.similarities_of_squares(side, ang, cx, cy, u[3] < 0.5, S)
+    maps = torch.randn((n, gc, gc), generator=g).cuda()
+    lut = explain.jet_lut()
+    alpha = torch.full((n,), 0.5, dtype=torch.float32, device='cuda')
+    out = {'frames': n, 'full_size': [Hs, Ws], 'box_sides': [lo, hi], 'degrees': a.degrees, 'size': S, 'grid': gc}
+    crops = ops.warp_similarity_u8(frames, M, S)
+    mdev = M.cuda()
+    for fmt, src, bpp in (('rgb24', frames, 3.0), ('nv12', nv, 1.5)):
+        A, rect = clips.paste_geometry(n, Hs, Ws, S, transforms=M, even=fmt == 'nv12')
+        paste = ops.relevance_paste_nv12 if fmt == 'nv12' else ops.relevance_paste_u8
+        table = (clips.lut_to_ycc(lut, a.matrix) if fmt == 'nv12' else lut).cuda()
+        Ad, rd = A.cuda(), rect.cuda()
+        dst, work = torch.empty_like(src), src.clone()
+        legs = {'copy': lambda: dst.copy_(src),
+                'paste_out_of_place': lambda: paste(src, maps, Ad, rd, table, alpha, S, out=dst, checked=True),
+                'paste_in_place': lambda: paste(work, maps, Ad, rd, table, alpha, S, inplace=True, checked=True)}
+        if fmt == 'rgb24':
+            legs['warp_then_overlay_on_crops'] = lambda: explain.overlay(
+                ops.warp_similarity_u8(frames, mdev, S, out=crops, checked=True), maps, scale=16, lut=table)
+        ts = {k: [] for k in legs}
+        for r in range(a.warmup + a.reps):
+            for k, fn in legs.items():                      # alternating
+                t = event_ms(fn)
+                if r >= a.warmup:
+                    ts[k].append(t)
+        res = {k: stats(ts[k]) for k in legs}
+        moved = bpp * (float((rect[:, 2].double() * rect[:, 3].double()).sum()) + float((side * side).sum()))
+        res['in_place_bytes'] = moved
+        res['in_place_GB_per_s'] = moved / (res['paste_in_place']['median_ms'] * 1e-3) / 1e9
+        res['frame_bytes'] = float(src.numel())
+        res['in_place_over_copy'] = res['paste_in_place']['median_ms'] / res['copy']['median_ms']
+        for k in legs:
+            print('paste %-5s %-27s %.3f ms (%.3f-%.3f)' % (fmt, k, res[k]['median_ms'], res[k]['min_ms'], res[k]['max_ms']),
+                  flush=True)
+        print('paste %-5s in place moves %.1f MB of %.1f MB of frames: %.0f GB/s; in place / copy x%.3f'
+              % (fmt, moved / 1e6, src.numel() / 1e6, res['in_place_GB_per_s'], res['in_place_over_copy']), flush=True)
+        out[fmt] = res
     return out
 
 
@@ -470,6 +533,7 @@ def main():
     ap.add_argument('--videos', action='store_true')
     ap.add_argument('--nv12', action='store_true')
     ap.add_argument('--align', action='store_true')
+    ap.add_argument('--paste', action='store_true')
     ap.add_argument('--degrees', type=float, default=15.0)
     ap.add_argument('--matrix', default='bt709', choices=['bt601', 'bt709', 'jfif'])
     ap.add_argument('--set-size', type=int, default=64)
@@ -483,6 +547,17 @@ def main():
         raise SystemExit('video_bench.py measures on a GPU; none is visible')
     if a.conv1_only:
         return conv1_only(a)
+    if a.paste:
+        out = dict(paste_bench(a), reps=a.reps, warmup=a.warmup)
+        if a.json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+            with open(a.json, 'w') as f:
+                json.dump(out, f, indent=1)
+        print(json.dumps({'video_paste_bench': {f: {'copy_ms': out[f]['copy']['median_ms'],
+                                                    'out_of_place_ms': out[f]['paste_out_of_place']['median_ms'],
+                                                    'in_place_ms': out[f]['paste_in_place']['median_ms'],
+                                                    'in_place_GB_per_s': out[f]['in_place_GB_per_s']} for f in ('rgb24', 'nv12')}}))
+        return
     from oracle import istvt_ref as R
     grid = R.stem_out_side(a.size)
     dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
