@@ -47,6 +47,8 @@ def _stream() -> int:
 # two lines.  Transformer activations (and the bf16 operand copies of the weights) are therefore
 # allocated with rows padded to a multiple of 64 elements and handed around as [M, D] VIEWS of the
 # [M, ld] buffer; every kernel takes the row stride.  Pad columns are never read and never written.
+# (No kernel writes them on purpose.  Both halves are checked: tests/gpu_checks.py feeds NaN pad columns, and its guarded_*
+# entries run the kernels on outputs whose pad columns and surroundings hold a sentinel that must survive, tests/guard.py.)
 ROW_ALIGN = 64
 
 

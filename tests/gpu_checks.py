@@ -12,6 +12,7 @@ import math
 
 import torch
 
+import guard as G
 import istvt_pkg
 
 istvt_amd = istvt_pkg.load()
@@ -37,20 +38,31 @@ def relerr(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
-def rnd(shape, dtype, seed, scale=1.0):
+# Inputs go through guard.place and declared outputs through guard.expect: both are the identity outside guard.guarded(),
+# so the plain registrations run what they always ran; inside it (the guarded_* entries at the end of this file) every
+# input sits in a guarded buffer that must come back unchanged.  inplace=<key of guard.INPLACE_WAIVERS>: a buffer the
+# kernel is meant to change (an accumulator, a pre-filled output).
+def rnd(shape, dtype, seed, scale=1.0, inplace=None):
     g = torch.Generator(device='cpu').manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(DEV).to(dtype)
+    return G.place((torch.randn(shape, generator=g) * scale).to(DEV).to(dtype), inplace=inplace)
 
 
-def ints(shape, dtype, seed, lo=-2, hi=3):
+def ints(shape, dtype, seed, lo=-2, hi=3, inplace=None):
     g = torch.Generator(device='cpu').manual_seed(seed)
-    return torch.randint(lo, hi, shape, generator=g).to(DEV).to(dtype)
+    return G.place(torch.randint(lo, hi, shape, generator=g).to(DEV).to(dtype), inplace=inplace)
+
+
+def _prefilled(t, key='output.prefilled'):
+    """a buffer the check fills and a kernel then writes or adds to"""
+    return G.place(t, inplace=key)
 
 
 def padded(t):
     """the same values as a [M, D] view of a buffer with line-aligned rows (ops.empty_rows), pad columns = NaN: a
     kernel that reads a pad column as data, or assumes stride == width, fails the check"""
     M, D = t.shape
+    if G.active() is not None:
+        return G.place(t, pad=True, ld=ops.pad_ld(D) + 64)
     buf = torch.full((M, ops.pad_ld(D) + 64), float('nan'), dtype=t.dtype, device=t.device)
     v = buf[:, :D]
     v.copy_(t)
@@ -64,15 +76,15 @@ def gemm_padded(dtype, M=515, N=728, K=1544):
     b = ints((N,), torch.float32, 4)
     xp, wp, rp = padded(x), padded(w), padded(r)
     ref = x.double() @ w.double().t() + b.double() + r.double()
-    y = ops.linear_fwd(xp, wp, b, rp, pad=True)
+    y = G.expect(ops.linear_fwd(xp, wp, b, rp, pad=True))
     assert y.stride(0) == ops.pad_ld(N)
     e = float((y.double() - ref.to(dtype).double()).abs().max())
     dy = ints((M, N), dtype, 5, -1, 2)
-    dx = ops.linear_dgrad(padded(dy), w, pad=True)
+    dx = G.expect(ops.linear_dgrad(padded(dy), w, pad=True))
     e = max(e, float((dx.double() - (dy.double() @ w.double()).to(dtype).double()).abs().max()))
-    dw = ops.linear_wgrad(padded(dy), xp)
+    dw = G.expect(ops.linear_wgrad(padded(dy), xp))
     e = max(e, float((dw.double() - dy.double().t() @ x.double()).abs().max()))
-    u, g = ops.linear_fwd(xp, wp, None, gelu=True, pad=True)
+    u, g = G.expect(*ops.linear_fwd(xp, wp, None, gelu=True, pad=True))
     e = max(e, float((u.double() - (x.double() @ w.double().t()).to(dtype).double()).abs().max()))
     return e, 0.0
 
@@ -82,15 +94,15 @@ def gemm_exact(dtype, mode, M=200, N=136, K=104):
     """integer data -> exact; mode in fwd/dgrad/wgrad; covers M/N/K tails."""
     if mode == 'fwd':
         x, w = ints((M, K), dtype, 1), ints((N, K), dtype, 2)
-        y = ops.linear_fwd(x, w)
+        y = G.expect(ops.linear_fwd(x, w))
         ref = x.double() @ w.double().t()
     elif mode == 'dgrad':
         dy, w = ints((M, N), dtype, 3), ints((N, K), dtype, 4)
-        y = ops.linear_dgrad(dy, w)
+        y = G.expect(ops.linear_dgrad(dy, w))
         ref = dy.double() @ w.double()
     else:
         dy, x = ints((M, N), dtype, 5), ints((M, K), dtype, 6)
-        y = ops.linear_wgrad(dy, x)
+        y = G.expect(ops.linear_wgrad(dy, x))
         ref = dy.double().t() @ x.double()
     if mode != 'wgrad':
         ref = ref.to(dtype)            # the exact sum, rounded once to the storage type
@@ -101,42 +113,42 @@ def gemm_real(dtype, mode):
     M, N, K = 1000, 728, 2912
     if mode == 'fwd_bias_res':
         x, w, b, r = rnd((M, K), dtype, 1), rnd((N, K), dtype, 2, K ** -0.5), rnd((N,), torch.float32, 3), rnd((M, N), dtype, 4)
-        y = ops.linear_fwd(x, w, b, r)
+        y = G.expect(ops.linear_fwd(x, w, b, r))
         ref = x.double() @ w.double().t() + b.double() + r.double()
     elif mode == 'fwd_gelu':
         x, w, b = rnd((M, 728), dtype, 1), rnd((2912, 728), dtype, 2, 728 ** -0.5), rnd((2912,), torch.float32, 3)
-        u, g = ops.linear_fwd(x, w, b, gelu=True)
+        u, g = G.expect(*ops.linear_fwd(x, w, b, gelu=True))
         ru = x.double() @ w.double().t() + b.double()
         rg = torch.nn.functional.gelu(ru)
         return max(relerr(u, ru), relerr(g, rg)), TOL[dtype]
     elif mode == 'fwd_gelu_d':      # istvt_gemm flags bit 4: C = gelu'(u), C2 = gelu(u)
         x, w, b = rnd((M, 728), dtype, 1), rnd((2912, 728), dtype, 2, 728 ** -0.5), rnd((2912,), torch.float32, 3)
-        d, g = ops.linear_fwd(x, w, b, gelu=True, gelu_d=True)
+        d, g = G.expect(*ops.linear_fwd(x, w, b, gelu=True, gelu_d=True))
         ru = (x.double() @ w.double().t() + b.double()).requires_grad_(True)
         rg = torch.nn.functional.gelu(ru)
         rg.sum().backward()
         return max(relerr(d, ru.grad), relerr(g, rg.detach())), TOL[dtype]
     elif mode == 'dgrad_gelu_d':    # ... and C = acc * C2 with the saved derivative
         dy, w, d = rnd((M, 728), dtype, 1), rnd((728, 2912), dtype, 2, 728 ** -0.5), rnd((M, 2912), dtype, 3)
-        y = ops.linear_dgrad(dy, w, gelu_u=d, gelu_d=True)
+        y = G.expect(ops.linear_dgrad(dy, w, gelu_u=d, gelu_d=True))
         ref = (dy.double() @ w.double()) * d.double()
     elif mode == 'dgrad_gelu':
         dy, w, u = rnd((M, 728), dtype, 1), rnd((728, 2912), dtype, 2, 728 ** -0.5), rnd((M, 2912), dtype, 3)
-        y = ops.linear_dgrad(dy, w, gelu_u=u)
+        y = G.expect(ops.linear_dgrad(dy, w, gelu_u=u))
         ud = u.double().requires_grad_(True)
         torch.nn.functional.gelu(ud).backward(dy.double() @ w.double())
         ref = ud.grad
     elif mode == 'wgrad':
         dy, x = rnd((5000, N), dtype, 5), rnd((5000, 512), dtype, 6)
-        y = ops.linear_wgrad(dy, x)
+        y = G.expect(ops.linear_wgrad(dy, x))
         ref = dy.double().t() @ x.double()
     elif mode == 'head':            # N = 1 (Linear(dim, 1)) and its gradients
         x, w, b = rnd((32, 728), dtype, 1), rnd((1, 728), dtype, 2, 0.05), rnd((1,), torch.float32, 3)
-        y = ops.linear_fwd(x, w, b)
+        y = G.expect(ops.linear_fwd(x, w, b))
         dy = rnd((32, 1), dtype, 4)
-        dx = ops.linear_dgrad(dy, w)
-        dw = ops.linear_wgrad(dy, x)
-        db = ops.colsum(dy)
+        dx = G.expect(ops.linear_dgrad(dy, w))
+        dw = G.expect(ops.linear_wgrad(dy, x))
+        db = G.expect(ops.colsum(dy))
         e = max(relerr(y, x.double() @ w.double().t() + b.double()), relerr(dx, dy.double() @ w.double()),
                 relerr(dw, dy.double().t() @ x.double()), relerr(db, dy.double().sum(0)))
         return e, TOL[dtype]
@@ -145,10 +157,10 @@ def gemm_real(dtype, mode):
 
 # ------------------------------------------------------------------------------------------ LayerNorm
 def layernorm(dtype, D=728, M=1003, pad=False):
-    x, g, b = rnd((M, D), dtype, 1, 2.0), rnd((D,), torch.float32, 2, 0.2) + 1, rnd((D,), torch.float32, 3, 0.1)
+    x, g, b = rnd((M, D), dtype, 1, 2.0), G.place(rnd((D,), torch.float32, 2, 0.2) + 1), rnd((D,), torch.float32, 3, 0.1)
     if pad:
         x = padded(x)
-    y, mean, rstd = ops.layernorm_fwd(x, g, b, 1e-5, pad=pad)
+    y, mean, rstd = G.expect(*ops.layernorm_fwd(x, g, b, 1e-5, pad=pad))
     xd = x.double().requires_grad_(True)
     gd, bd = g.double().requires_grad_(True), b.double().requires_grad_(True)
     ref = torch.nn.functional.layer_norm(xd, (D,), gd, bd, 1e-5)
@@ -157,19 +169,20 @@ def layernorm(dtype, D=728, M=1003, pad=False):
     dg, db = torch.zeros_like(g), torch.zeros_like(b)
     if pad:
         dres = padded(dres)                 # dy stays contiguous: the strides are independent
-    dx = ops.layernorm_bwd(dy, x, mean, rstd, g, dg, db, dres=dres, pad=pad)
+    dx = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg, db, dres=dres, pad=pad))
     e = max(relerr(y, ref), relerr(dx, xd.grad + dres.double()), relerr(dg, gd.grad), relerr(db, bd.grad))
     # the same call with the fused column sums of dx (the preceding Linear's bias gradient): dx, dgamma, dbeta
     # unchanged, dcol accumulates on top of what the buffer holds
-    dg2, db2, dcol = torch.zeros_like(g), torch.zeros_like(b), torch.ones((D,), dtype=torch.float32, device=DEV)
-    dx2 = ops.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, pad=pad, dcol=dcol)
+    dg2, db2 = torch.zeros_like(g), torch.zeros_like(b)
+    dcol = _prefilled(torch.ones((D,), dtype=torch.float32, device=DEV), 'accumulator')
+    dx2 = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, pad=pad, dcol=dcol))
     e = max(e, relerr(dx2, dx), relerr(dg2, dg), relerr(db2, db),
             relerr(dcol - 1.0, (xd.grad + dres.double()).sum(0)))
     # without the residual input (the kernel variants that stage two operands), with and without the column sums
     dg3, db3 = torch.zeros_like(g), torch.zeros_like(b)
-    dx3 = ops.layernorm_bwd(dy, x, mean, rstd, g, dg3, db3, pad=pad)
+    dx3 = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg3, db3, pad=pad))
     dg4, db4, dcol4 = torch.zeros_like(g), torch.zeros_like(b), torch.zeros((D,), dtype=torch.float32, device=DEV)
-    dx4 = ops.layernorm_bwd(dy, x, mean, rstd, g, dg4, db4, pad=pad, dcol=dcol4)
+    dx4 = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg4, db4, pad=pad, dcol=dcol4))
     e = max(e, relerr(dx3, xd.grad), relerr(dg3, gd.grad), relerr(db3, bd.grad), relerr(dx4, dx3), relerr(dg4, dg3),
             relerr(dcol4, xd.grad.sum(0)))
     return e, tol_rounding(dtype)
@@ -183,7 +196,7 @@ def _diff_ref(y, B, F, P):
 def layernorm_bwd_reproducible(dtype, D=728, M=20011):
     """two launches on the same inputs give the same BITS in dx, dgamma, dbeta and the fused column sums: the parameter
     gradients are reduced in a fixed order (per-workgroup partial rows + one reduce launch), not with atomics"""
-    x, g = rnd((M, D), dtype, 1, 2.0), rnd((D,), torch.float32, 2, 0.2) + 1
+    x, g = rnd((M, D), dtype, 1, 2.0), G.place(rnd((D,), torch.float32, 2, 0.2) + 1)
     dy, dres = rnd((M, D), dtype, 4), rnd((M, D), dtype, 5)
     _, mean, rstd = ops.layernorm_fwd(x, g, torch.zeros_like(g), 1e-5)
     outs = []
@@ -199,18 +212,19 @@ def layernorm_bwd_reproducible(dtype, D=728, M=20011):
 def layernorm_bwd_deferred(dtype, D=728, M=20011):
     """ops.layernorm_bwd(defer=...) + layernorm_bwd_reduce on ANOTHER stream (how functional runs it: the fold of the
     partial rows rides on the weight-gradient stream) gives the same bits as the one-call form, with and without dcol"""
-    x, g = rnd((M, D), dtype, 1, 2.0), rnd((D,), torch.float32, 2, 0.2) + 1
+    x, g = rnd((M, D), dtype, 1, 2.0), G.place(rnd((D,), torch.float32, 2, 0.2) + 1)
     dy, dres = rnd((M, D), dtype, 4), rnd((M, D), dtype, 5)
     _, mean, rstd = ops.layernorm_fwd(x, g, torch.zeros_like(g), 1e-5)
     side = torch.cuda.Stream()
     worst = 0.0
     for with_dcol in (True, False):
-        dg, db, dc = (torch.full((D,), 0.25, dtype=torch.float32, device=DEV) for _ in range(3))      # accumulate (+=) onto something
-        dx = ops.layernorm_bwd(dy, x, mean, rstd, g, dg, db, dres=dres, dcol=dc if with_dcol else None)
-        dg2, db2, dc2 = (torch.full((D,), 0.25, dtype=torch.float32, device=DEV) for _ in range(3))
+        dg, db, dc = (_prefilled(torch.full((D,), 0.25, dtype=torch.float32, device=DEV), 'accumulator')
+                      for _ in range(3))                                                             # accumulate (+=) onto something
+        dx = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg, db, dres=dres, dcol=dc if with_dcol else None))
+        dg2, db2, dc2 = (_prefilled(torch.full((D,), 0.25, dtype=torch.float32, device=DEV), 'accumulator') for _ in range(3))
         held = []
-        dx2 = ops.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, dcol=dc2 if with_dcol else None,
-                                defer=lambda *a: held.append(a))
+        dx2 = G.expect(ops.layernorm_bwd(dy, x, mean, rstd, g, dg2, db2, dres=dres, dcol=dc2 if with_dcol else None,
+                                         defer=lambda *a: held.append(a)))
         assert len(held) == 1 and torch.equal(dg2, torch.full_like(dg2, 0.25)), 'the deferred call must not touch the gradients'
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -228,7 +242,7 @@ def frame_diff(dtype, B=2, F=7, P=13, D=64):
     ref = _diff_ref(xd, B, F, P)
     g = rnd((B * F * P, D), dtype, 2)
     ref.backward(g.double())
-    e = max(relerr(ops.frame_diff(x, B, F, P), ref), relerr(ops.frame_diff(g, B, F, P, adjoint=True), xd.grad))
+    e = max(relerr(G.expect(ops.frame_diff(x, B, F, P)), ref), relerr(G.expect(ops.frame_diff(g, B, F, P, adjoint=True)), xd.grad))
     return e, TOL[dtype]
 
 
@@ -245,13 +259,13 @@ def attn_spatial(dtype, BF=3, P=197, heads=8, dh=64, pad=False):
     qkv = rnd((BF * P, 3 * inner), dtype, 1)
     if pad:
         qkv = padded(qkv)
-    out, lse = ops.attn_spatial_fwd(qkv, BF, P, heads, dh)
+    out, lse = G.expect(*ops.attn_spatial_fwd(qkv, BF, P, heads, dh))
     qd = qkv.double().requires_grad_(True)
     q, k, v = (t.view(BF, P, heads, dh).transpose(1, 2) for t in qd.chunk(3, dim=-1))
     ref = _attn_ref(q, k, v).transpose(1, 2).reshape(BF * P, inner)
     dout = rnd((BF * P, inner), dtype, 2)
     ref.backward(dout.double())
-    dqkv = ops.attn_spatial_bwd(qkv, out, padded(dout) if pad else dout, lse, BF, P, heads, dh)
+    dqkv = G.expect(ops.attn_spatial_bwd(qkv, out, padded(dout) if pad else dout, lse, BF, P, heads, dh))
     e_f = relerr(out, ref)
     e_b = max(relerr(a, b) for a, b in zip(dqkv.chunk(3, dim=-1), qd.grad.chunk(3, dim=-1)))
     return max(e_f, e_b), tol_rounding(dtype)
@@ -264,17 +278,17 @@ def attn_spatial_fp8(BF=3, P=197, heads=8, dh=64):
     dtype = torch.bfloat16
     inner = heads * dh
     qkv = rnd((BF * P, 3 * inner), dtype, 1)
-    out, lse = ops.attn_spatial_fwd(qkv, BF, P, heads, dh, fp8=True)
+    out, lse = G.expect(*ops.attn_spatial_fwd(qkv, BF, P, heads, dh, fp8=True))
     qd = qkv.double().requires_grad_(True)
     q, k, v = (t.view(BF, P, heads, dh).transpose(1, 2) for t in qd.chunk(3, dim=-1))
     ref = _attn_ref(q, k, v).transpose(1, 2).reshape(BF * P, inner)
     dout = rnd((BF * P, inner), dtype, 2)
     ref.backward(dout.double())
-    dqkv = ops.attn_spatial_bwd(qkv, out, dout, lse, BF, P, heads, dh, fp8=True)
+    dqkv = G.expect(ops.attn_spatial_bwd(qkv, out, dout, lse, BF, P, heads, dh, fp8=True))
     e_f = relerr(out, ref)
     e_b = max(relerr(a, b) for a, b in zip(dqkv.chunk(3, dim=-1), qd.grad.chunk(3, dim=-1)))
     # and against the bf16-operand kernel on the same inputs: the delta the config asks to report
-    out16, _ = ops.attn_spatial_fwd(qkv, BF, P, heads, dh)
+    out16, _ = G.expect(*ops.attn_spatial_fwd(qkv, BF, P, heads, dh))
     print('attn_spatial_fp8: forward rel err vs fp64 %.3e, backward %.3e, forward delta vs bf16 kernel %.3e'
           % (e_f, e_b, relerr(out, out16)))
     return max(e_f, e_b), 8e-2
@@ -295,7 +309,7 @@ def attn_temporal(dtype, B=2, F=9, P=37, heads=8, dh=64, pad=False, diff=False, 
         qk, v = rnd((M, 2 * inner), dtype, 1), rnd((M, inner), dtype, 2)
         if pad:
             qk, v = padded(qk), padded(v)
-    out = ops.attn_temporal_fwd(qk, v, B, F, P, heads, dh, diff=diff)
+    out = G.expect(ops.attn_temporal_fwd(qk, v, B, F, P, heads, dh, diff=diff))
     qkd, vd = qk.double().requires_grad_(True), v.double().requires_grad_(True)
 
     def split(t):                                    # (b f p) (h d) -> b h p f d
@@ -314,6 +328,7 @@ def attn_temporal(dtype, B=2, F=9, P=37, heads=8, dh=64, pad=False, diff=False, 
     dqk, dv = ops.attn_temporal_bwd(qk, v, padded(dout) if pad else dout, B, F, P, heads, dh, diff=diff, packed=packed)
     if packed:
         dqk, dv = dqk[:, :2 * inner], dqk[:, 2 * inner:]
+    G.expect(dqk, dv)
     e = max(relerr(out, ref), relerr(dqk, qkd.grad), relerr(dv, vd.grad))
     # bf16 + diff: the kernel rounds q[f] - q[f-1] to bf16 once more before the MFMA (operand type)
     return e, tol_rounding(dtype)
@@ -324,12 +339,12 @@ def layernorm_diff(dtype, B=3, F=9, P=23, D=728):
     the difference plane must carry the precision of the DIFFERENCE -- checked on frames that differ by 2 %"""
     M = B * F * P
     base = rnd((B, 1, P, D), torch.float32, 1, 2.0)
-    x = (base + 0.02 * rnd((B, F, P, D), torch.float32, 2)).reshape(M, D).to(dtype)
-    g, b = rnd((D,), torch.float32, 3, 0.2) + 1, rnd((D,), torch.float32, 4, 0.1)
-    y, yd, mean, rstd = ops.layernorm_fwd_diff(x, g, b, 1e-5, B, F, P)
+    x = G.place((base + 0.02 * rnd((B, F, P, D), torch.float32, 2)).reshape(M, D).to(dtype))
+    g, b = G.place(rnd((D,), torch.float32, 3, 0.2) + 1), rnd((D,), torch.float32, 4, 0.1)
+    y, yd, mean, rstd = G.expect(*ops.layernorm_fwd_diff(x, g, b, 1e-5, B, F, P))
     ref = torch.nn.functional.layer_norm(x.double(), (D,), g.double(), b.double(), 1e-5)
     dref = _diff_ref(ref, B, F, P)
-    y0, _, _ = ops.layernorm_fwd(x, g, b, 1e-5, pad=True)
+    y0, _, _ = G.expect(*ops.layernorm_fwd(x, g, b, 1e-5, pad=True))
     planes_ok = yd.data_ptr() + M * yd.stride(0) * yd.element_size() == y.data_ptr()
     e = max(relerr(y, ref), relerr(yd, dref), 0.0 if torch.equal(y, y0) else 1.0, 0.0 if planes_ok else 1.0)
     return e, tol_rounding(dtype)
@@ -363,9 +378,10 @@ def gemm_a_select(M=3000, K=728, N=1536, split=1024):
     ld = ops.pad_ld(K)
     planes = torch.full((2, M, ld), float('nan'), dtype=dt, device=DEV)
     planes[:, :, :K] = torch.randint(-3, 4, (2, M, K), generator=g, device=DEV).to(dt)
+    planes = G.place(planes)
     w = ops.empty_rows(N, K, dt, DEV, True)
     w.copy_(torch.randint(-2, 3, (N, K), generator=g, device=DEV).to(dt))
-    y = ops.linear_fwd(planes[0][:, :K], w, pad=True, a_sel_col=split)
+    y = G.expect(ops.linear_fwd(planes[0][:, :K], w, pad=True, a_sel_col=split))
     ref = torch.cat((planes[0][:, :K].double() @ w[:split].double().t(), planes[1][:, :K].double() @ w[split:].double().t()), 1)
     return (0.0 if torch.equal(y.double(), ref.to(dt).double()) else float((y.double() - ref).abs().max())), 0.0
 
@@ -375,7 +391,7 @@ def tokens(dtype, B=3, T=4, hw=36, D=728, pad=False):
     feats = rnd((B, T, hw, D), dtype, 1)
     space, temporal = rnd((1, 1, D), torch.float32, 2), rnd((1, 1, D), torch.float32, 3)
     pos = rnd((1, T, hw + 3, D), torch.float32, 4)          # declared grid larger than the input's
-    x = ops.tokens_fwd(feats, space, temporal, pos, pad=pad)
+    x = G.expect(ops.tokens_fwd(feats, space, temporal, pos, pad=pad))
     fd = feats.double().requires_grad_(True)
     sd, td, pd = (t.double().requires_grad_(True) for t in (space, temporal, pos))
     r = torch.cat((sd.view(1, 1, 1, D).expand(B, T, 1, D), fd), dim=2) + pd[:, :, :hw + 1]
@@ -385,7 +401,7 @@ def tokens(dtype, B=3, T=4, hw=36, D=728, pad=False):
     ds, dt, dp = torch.zeros_like(space), torch.zeros_like(temporal), torch.zeros_like(pos)
     if pad:
         dx = padded(dx.reshape(-1, D)).view(B, -1, D)
-    dfe = ops.tokens_bwd(dx, B, T, hw, D, ds, dt, dp, True)
+    dfe = G.expect(ops.tokens_bwd(dx, B, T, hw, D, ds, dt, dp, True))
     e = max(relerr(x, r), relerr(dfe, fd.grad), relerr(ds, sd.grad), relerr(dt, td.grad), relerr(dp, pd.grad))
     return e, TOL[dtype]
 
@@ -401,8 +417,8 @@ def colsum_cast(dtype):
 def cast_transpose(R=1000, C=728):
     """fp32 weight -> bf16 operand copy + its transpose (both with padded rows) in one pass; exact vs torch's cast"""
     w = torch.nn.Parameter(rnd((R, C), torch.float32, 7))
-    wp = ops.weight_as(w, torch.bfloat16, pad=True)
-    wt = ops._transposed_operand(wp)
+    wp = G.expect(ops.weight_as(w, torch.bfloat16, pad=True))
+    wt = G.expect(ops._transposed_operand(wp))
     ref = w.detach().to(torch.bfloat16)
     assert wp.stride(0) == ops.pad_ld(C) and wt.stride(0) == ops.pad_ld(R)
     e = max(float((wp.float() - ref.float()).abs().max()), float((wt.float() - ref.float().t()).abs().max()))
@@ -459,18 +475,19 @@ def all_checks():
 
 # ------------------------------------------------------------------------------------------ stem kernels
 def _nhwc(t):            # (n,c,h,w) -> [n*h*w, c]
-    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous()
+    return G.place(t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous())
 
 
 def dwconv_check(dtype, Fr=3, H=21, W=37, C=40):
     from istvt_amd import stem as S
     x = rnd((Fr, C, H, W), dtype, 1)
     w = rnd((C, 1, 3, 3), torch.float32, 2, 0.3)
-    sc, sh = rnd((C,), torch.float32, 3, 0.3) + 1, rnd((C,), torch.float32, 4, 0.3)
+    sc, sh = G.place(rnd((C,), torch.float32, 3, 0.3) + 1), rnd((C,), torch.float32, 4, 0.3)
     bn = S.BNState(C, DEV)
     bn.scale.copy_(sc); bn.beta.copy_(sh); bn.mean.zero_(); bn.rstd.fill_(1.0)
     xn = _nhwc(x)
-    y = S.dwconv(xn, w.reshape(C, 9).t().contiguous(), Fr, H, W, C, in_bn=bn, in_relu=True)
+    w9 = G.place(w.reshape(C, 9).t().contiguous())
+    y = G.expect(S.dwconv(xn, w9, Fr, H, W, C, in_bn=bn, in_relu=True))
     xd = x.double().requires_grad_(True)
     wd = w.double().requires_grad_(True)
     a = torch.relu(xd * sc.double().view(1, C, 1, 1) + sh.double().view(1, C, 1, 1))
@@ -481,10 +498,10 @@ def dwconv_check(dtype, Fr=3, H=21, W=37, C=40):
     ref.backward(dout.double())
     e = relerr(y, _nhwc(ref))
     # input gradient w.r.t. a (flipped taps), masked by relu'(affine(x))
-    dz = S.dwconv(_nhwc(dout), w.reshape(C, 9).t().contiguous(), Fr, H, W, C, flip=True, msrc=xn, m_bn=bn, mask_pre=True)
+    dz = G.expect(S.dwconv(_nhwc(dout), w9, Fr, H, W, C, flip=True, msrc=xn, m_bn=bn, mask_pre=True))
     ref_dz = xd.grad / sc.double().view(1, C, 1, 1)           # dL/dz with z = affine(x) pre-ReLU
     e = max(e, relerr(dz, _nhwc(ref_dz)))
-    dw = S.dwconv_wgrad(xn, _nhwc(dout), Fr, H, W, C, bn, True)
+    dw = G.expect(S.dwconv_wgrad(xn, _nhwc(dout), Fr, H, W, C, bn, True))
     e = max(e, relerr(dw, wd.grad.reshape(C, 9)))
     return e, TOL[dtype]
 
@@ -492,17 +509,18 @@ def dwconv_check(dtype, Fr=3, H=21, W=37, C=40):
 def bn_check(dtype, M=5000, C=728):
     from istvt_amd import stem as S
     u = rnd((M, C), dtype, 1, 2.0) + 0.5
-    g, b = rnd((C,), torch.float32, 2, 0.2) + 1, rnd((C,), torch.float32, 3, 0.1)
-    rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+    u = G.place(u)
+    g, b = G.place(rnd((C,), torch.float32, 2, 0.2) + 1), rnd((C,), torch.float32, 3, 0.1)
+    rm, rv = torch.zeros(C, device=DEV), _prefilled(torch.ones(C, device=DEV), 'accumulator')
     st = S.bn_forward_stats(u, M, C, g, b, rm, rv, True)
-    y = S.bn_apply(u, st, M, C, False)
+    y = G.expect(S.bn_apply(u, st, M, C, False))
     ud = u.double().requires_grad_(True)
     gd, bd = g.double().requires_grad_(True), b.double().requires_grad_(True)
     rm2, rv2 = torch.zeros(C, device=DEV, dtype=torch.float64), torch.ones(C, device=DEV, dtype=torch.float64)
     ref = torch.nn.functional.batch_norm(ud, rm2, rv2, gd, bd, True, 0.1, 1e-5)
     dz = rnd((M, C), dtype, 4)
     ref.backward(dz.double())
-    du, dg, db = S.bn_backward(dz, u, st, g, M, C)
+    du, dg, db = G.expect(*S.bn_backward(dz, u, st, g, M, C))
     e = max(relerr(y, ref), relerr(rm, rm2), relerr(rv, rv2), relerr(du, ud.grad), relerr(dg, gd.grad), relerr(db, bd.grad))
     return e, TOL[dtype]
 
@@ -522,6 +540,7 @@ def pool_check(dtype, Fr=2, H=21, W=21, C=24):
     L = _lib.lib()
     _lib.check(L.istvt_pool_add_fwd(xn.data_ptr(), b1.ptr(), sn.data_ptr(), b2.ptr(), out.data_ptr(), am.data_ptr(), Fr, H, W, C,
                                     ops.dtype_code(xn), ops._stream()), 'pool')
+    G.expect(out, am)
     z = (x.float() * b1.scale.view(1, C, 1, 1) + b1.beta.view(1, C, 1, 1)).to(dtype).double().requires_grad_(True)
     ref = torch.nn.functional.max_pool2d(z, 3, 2, 1) + (sk.double() * b2.scale.double().view(1, C, 1, 1) + b2.beta.double().view(1, C, 1, 1))
     dout = rnd((Fr, C, Ho, Ho), dtype, 7)
@@ -529,6 +548,7 @@ def pool_check(dtype, Fr=2, H=21, W=21, C=24):
     dz = torch.empty_like(xn)
     _lib.check(L.istvt_pool_bwd(_nhwc(dout).data_ptr(), am.data_ptr(), dz.data_ptr(), Fr, H, W, C, None, None, None, None,
                                 ops.dtype_code(xn), ops._stream()), 'poolb')
+    G.expect(dz)
     e = max(relerr(out, _nhwc(ref)), relerr(dz, _nhwc(z.grad)))
     # the same with the BatchNorm-backward sums of the pooled BatchNorm taken on the way: dz identical, sums equal to the
     # standalone statistics pass over (dz, u)
@@ -537,6 +557,7 @@ def pool_check(dtype, Fr=2, H=21, W=21, C=24):
     acc = S.new_stats(C, DEV)
     _lib.check(L.istvt_pool_bwd(_nhwc(dout).data_ptr(), am.data_ptr(), dz2.data_ptr(), Fr, H, W, C, xn.data_ptr(), b1.ptr(),
                                 acc[0, 0].data_ptr(), acc[0, 1].data_ptr(), ops.dtype_code(xn), ops._stream()), 'poolb stats')
+    G.expect(dz2, acc)
     S.reduce_stats(acc, C)
     ref_acc = S.new_stats(C, DEV)
     _lib.check(L.istvt_bn_bwd_stats(dz.data_ptr(), xn.data_ptr(), b1.ptr(), ref_acc[0, 0].data_ptr(), ref_acc[0, 1].data_ptr(),
@@ -756,7 +777,7 @@ def dwconv_epilogue_check(dtype, case, Fr=2, H=12, W=12, C=728):
     z = (u.float() - bn.mean.view(1, C, 1, 1)) * bn.scale.view(1, C, 1, 1) + bn.beta.view(1, C, 1, 1)
     v = lambda t: t.view(1, C, 1, 1)  # noqa: E731
     stats = S.new_stats(C, DEV)
-    w9 =w.reshape(C, 9).t().contiguous()          # tap-major [9][C]
+    w9 = G.place(w.reshape(C, 9).t().contiguous())          # tap-major [9][C]
     if case == 'a':
         res = res * (z > 0)
         out = S.dwconv(_nhwc(dd), w9, Fr, H, W, C, flip=True, msrc=_nhwc(u), m_bn=bn, mask_pre=True, stats=stats)
@@ -769,6 +790,7 @@ def dwconv_epilogue_check(dtype, case, Fr=2, H=12, W=12, C=728):
         res = res * (z > 0)
         out = S.dwconv(_nhwc(dd), w9, Fr, H, W, C, flip=True, msrc=_nhwc(u), m_bn=bn, mask_post=True, addsrc=_nhwc(add),
                        stats=stats)
+    G.expect(out)
     e = relerr(out, _nhwc(res))
     if case != 'b':
         S.reduce_stats(stats, C)
@@ -787,16 +809,18 @@ def im2col_check(dtype, Fr=2, S_=33):
     H1 = (S_ - 3) // 2 + 1
     col1 = torch.empty((Fr * H1 * H1, 32), dtype=dtype, device=DEV)
     _lib.check(L.istvt_im2col_conv1(x.data_ptr(), col1.data_ptr(), Fr, S_, ops._DT[dtype], ops._stream()), 'i1')
-    u1 = ops.linear_fwd(col1, S._conv1_weight(w1, dtype))
+    G.expect(col1)
+    u1 = G.expect(ops.linear_fwd(col1, S._conv1_weight(w1, dtype)))
     xd, w1d = x.double().requires_grad_(True), w1.to(dtype).double().requires_grad_(True)
     xq = xd + (xd.detach().to(dtype).double() - xd.detach())
     r1 = torch.nn.functional.conv2d(xq, w1d, None, 2, 0)
     e = relerr(u1, _nhwc(r1))
     g1 = rnd((Fr, 32, H1, H1), dtype, 3)
     r1.backward(g1.double())
-    dcol1 = ops.linear_dgrad(_nhwc(g1), S._conv1_weight(w1, dtype))
+    dcol1 = G.expect(ops.linear_dgrad(_nhwc(g1), S._conv1_weight(w1, dtype)))
     dx = torch.empty_like(x)
     _lib.check(L.istvt_col2im_conv1(dcol1.data_ptr(), dx.data_ptr(), Fr, S_, ops._DT[dtype], ops._stream()), 'c1')
+    G.expect(dx)
     e = max(e, relerr(dx, xd.grad))
     dW1 = ops.linear_wgrad(_nhwc(g1), col1)[:, :27].reshape(32, 3, 3, 3).permute(0, 3, 1, 2)
     e = max(e, relerr(dW1, w1d.grad))
@@ -810,7 +834,8 @@ def im2col_check(dtype, Fr=2, S_=33):
     col2 = torch.empty((Fr * H2 * H2, 9 * C), dtype=dtype, device=DEV)
     un = _nhwc(u)
     _lib.check(L.istvt_im2col3x3(un.data_ptr(), bn.ptr(), 1, col2.data_ptr(), Fr, H1, H1, C, ops._DT[dtype], ops._stream()), 'i2')
-    u2 = ops.linear_fwd(col2, S._conv2_weight(w2, dtype))
+    G.expect(col2)
+    u2 = G.expect(ops.linear_fwd(col2, S._conv2_weight(w2, dtype)))
     zd = (u.float() * bn.scale.view(1, C, 1, 1) + bn.beta.view(1, C, 1, 1)).double().requires_grad_(True)
     ad = torch.relu(zd)
     aq = ad + (ad.detach().to(dtype).double() - ad.detach())
@@ -819,10 +844,11 @@ def im2col_check(dtype, Fr=2, S_=33):
     e = max(e, relerr(u2, _nhwc(r2)))
     g2 = rnd((Fr, 64, H2, H2), dtype, 8)
     r2.backward(g2.double())
-    dcol2 = ops.linear_dgrad(_nhwc(g2), S._conv2_weight(w2, dtype))
+    dcol2 = G.expect(ops.linear_dgrad(_nhwc(g2), S._conv2_weight(w2, dtype)))
     dz = torch.empty_like(un)
     _lib.check(L.istvt_col2im3x3(dcol2.data_ptr(), un.data_ptr(), bn.ptr(), dz.data_ptr(), Fr, H1, H1, C, ops._DT[dtype],
                                  ops._stream()), 'c2')
+    G.expect(dz)
     e = max(e, relerr(dz, _nhwc(zd.grad)))
     dW2 = ops.linear_wgrad(_nhwc(g2), col2).view(64, 3, 3, C).permute(0, 3, 1, 2)
     e = max(e, relerr(dW2, w2d.grad))
@@ -839,6 +865,7 @@ def conv_dense_check(dtype, Fr=2, S_=33):
     H1 = (S_ - 3) // 2 + 1
     u1 = torch.empty((Fr * H1 * H1, 32), dtype=dtype, device=DEV)
     _lib.check(L.istvt_conv1_fwd(x.data_ptr(), w1.data_ptr(), u1.data_ptr(), Fr, S_, ops._DT[dtype], ops._stream()), 'conv1')
+    G.expect(u1)
     r1 = torch.nn.functional.conv2d(x.double(), w1.double(), None, 2, 0)
     e = relerr(u1, _nhwc(r1))
     if dtype != torch.bfloat16:
@@ -847,7 +874,7 @@ def conv_dense_check(dtype, Fr=2, S_=33):
     xq = x.to(dtype).double()                       # the patches are rounded to the storage dtype, as im2col does
     w1d = w1.double().requires_grad_(True)
     torch.nn.functional.conv2d(xq, w1d, None, 2, 0).backward(g1.double())
-    g1n = _nhwc(g1).contiguous()
+    g1n = _nhwc(g1)
     dW1 = torch.zeros((32, 32), dtype=torch.float32, device=DEV)
     slabs1 = torch.empty((L.istvt_conv1_wgrad_slabs(), 1024), dtype=torch.float32, device=DEV)
     _lib.check(L.istvt_conv1_wgrad(g1n.data_ptr(), x.data_ptr(), slabs1.data_ptr(), dW1.data_ptr(), Fr, S_,
@@ -861,10 +888,11 @@ def conv_dense_check(dtype, Fr=2, S_=33):
     bn.mean.copy_(rnd((C,), torch.float32, 19, 0.4))
     w2 = rnd((64, C, 3, 3), torch.float32, 17, 0.1)
     H2 = H1 - 2
-    un = _nhwc(u).contiguous()
+    un = _nhwc(u)
     w2g = S._conv2_weight(w2, dtype)
     u2 = torch.empty((Fr * H2 * H2, 64), dtype=dtype, device=DEV)
     _lib.check(L.istvt_conv2_fwd(un.data_ptr(), bn.ptr(), w2g.data_ptr(), u2.data_ptr(), Fr, H1, H1, ops._stream()), 'conv2')
+    G.expect(u2)
     zd = ((u.float() - bn.mean.view(1, C, 1, 1)) * bn.scale.view(1, C, 1, 1) + bn.beta.view(1, C, 1, 1)).double().requires_grad_(True)
     ad = torch.relu(zd)
     aq = ad + (ad.detach().to(dtype).double() - ad.detach())
@@ -873,10 +901,11 @@ def conv_dense_check(dtype, Fr=2, S_=33):
     e = max(e, relerr(u2, _nhwc(r2)))
     g2 = rnd((Fr, 64, H2, H2), dtype, 18)
     r2.backward(g2.double())
-    g2n = _nhwc(g2).contiguous()
+    g2n = _nhwc(g2)
     dz = torch.empty_like(un)
     _lib.check(L.istvt_conv2_dgrad(g2n.data_ptr(), w2g.data_ptr(), un.data_ptr(), bn.ptr(), dz.data_ptr(), Fr, H1, H1,
                                    ops._stream()), 'conv2 dgrad')
+    G.expect(dz)
     e = max(e, relerr(dz, _nhwc(zd.grad)))
     dW2 = torch.zeros((64, 288), dtype=torch.float32, device=DEV)
     slabs = torch.empty((L.istvt_conv2_wgrad_slabs(), 64 * 288), dtype=torch.float32, device=DEV)
@@ -947,7 +976,7 @@ def gemm_production(mode, N, K, M=M_C2, nsample=2048):
             assert u.stride(0) == ops.pad_ld(N)
             return max(e, 0.0 if eg < 1e-2 else eg), 0.0
         r = padded(ints((M, N), dt, 3)) if mode == 'fwd_bias_res' else None
-        y = ops.linear_fwd(x, w, b, r, pad=True)
+        y = G.expect(ops.linear_fwd(x, w, b, r, pad=True))
         if mode == 'fwd_bias_res':
             ref = ref + cpu(b) + cpu(r[ic])
         return float((cpu(y[ic]) - ref.to(dt).double()).abs().max()), 0.0
@@ -1079,7 +1108,8 @@ def all_checks():  # noqa: F811
     out.append(('attn_temporal_prediff_padded_F17_bf16', lambda: attn_temporal(torch.bfloat16, 2, 17, 19, 8, 64, pad=True, diff=2, packed=True)))
     out.append(('attn_temporal_prediff_F5_h2_d32_bf16', lambda: attn_temporal(torch.bfloat16, 3, 5, 11, 2, 32, diff=2)))
     # every frame count around the boundaries of the row-chunk stores (3 F dh/8 chunks, 64 per instruction), of the 16-row
-    # tiles and of the one- / two-tile kernels, with both head sizes; NaN pad columns catch a chunk stored past a row
+    # tiles and of the one- / two-tile kernels, with both head sizes.  The NaN pad columns are those of the INPUTS (a chunk
+    # read past a row shows); a chunk STORED past a row is caught by the guarded_attn_temporal_store_sweep_* entries below
     for F_ in (1, 2, 3, 7, 8, 10, 15, 16, 17):           # (the host wrappers take at most 17 frames: T <= 16)
         out.append(('attn_temporal_store_sweep_F%d_d64_bf16' % F_,
                     lambda F_=F_: attn_temporal(torch.bfloat16, 2, F_, 5, 2, 64, pad=True, diff=2, packed=True)))
@@ -1111,16 +1141,18 @@ def gemm_stats_check(M, N, K):
     assert ops.stats_fusable(x, w)
     acc = S.new_stats(N, DEV)
     acc[0, 0].fill_(1.0)                                    # accumulates on top of what the buffer holds
-    y = ops.linear_fwd(x, w, stats=acc)
+    y = G.expect(ops.linear_fwd(x, w, stats=acc))
     S.reduce_stats(acc, N)
-    y0 = ops.linear_fwd(x, w)
+    y0 = G.expect(ops.linear_fwd(x, w))
     e = 0.0 if torch.equal(y, y0) else 1.0
     yd = y.double()
     e = max(e, relerr(acc[0, 0] - 1.0, yd.sum(0)), relerr(acc[0, 1], (yd * yd).sum(0)))
     # and through the BatchNorm front end: same pack as the separate statistics pass
-    g, b = rnd((N,), torch.float32, 3, 0.2) + 1, rnd((N,), torch.float32, 4, 0.1)
-    rm1, rv1, rm2, rv2 = (torch.zeros(N, device=DEV), torch.ones(N, device=DEV), torch.zeros(N, device=DEV), torch.ones(N, device=DEV))
+    g, b = G.place(rnd((N,), torch.float32, 3, 0.2) + 1), rnd((N,), torch.float32, 4, 0.1)
+    rm1, rv1, rm2, rv2 = (torch.zeros(N, device=DEV), _prefilled(torch.ones(N, device=DEV), 'accumulator'),
+                          torch.zeros(N, device=DEV), _prefilled(torch.ones(N, device=DEV), 'accumulator'))
     u1, st1 = S.pointwise_bn(x, w, M, N, g, b, rm1, rv1, True)
+    G.expect(u1)
     st2 = S.bn_forward_stats(y0, M, N, g, b, rm2, rv2, True)
     e = max(e, relerr(st1.pack, st2.pack), relerr(rv1, rv2), float((rm1 - rm2).abs().max() / rv2.sqrt().max()))
     return e, 2e-5
@@ -1144,9 +1176,9 @@ def gemm_csum_check(M=5000, N=728, K=2912):
     dy, w, u = rnd((M, N), dt, 1), rnd((N, K), dt, 2, N ** -0.5), rnd((M, K), dt, 3)
     up = ops.empty_rows(M, K, dt, DEV)
     up.copy_(u)
-    out = torch.full((K,), 3.0, dtype=torch.float32, device=DEV)
-    dx = ops.linear_dgrad(padded(dy), w, gelu_u=up, pad=True, csum=out)
-    dx0 = ops.linear_dgrad(padded(dy), w, gelu_u=up, pad=True)
+    out = _prefilled(torch.full((K,), 3.0, dtype=torch.float32, device=DEV), 'accumulator')
+    dx = G.expect(ops.linear_dgrad(padded(dy), w, gelu_u=up, pad=True, csum=out))
+    dx0 = G.expect(ops.linear_dgrad(padded(dy), w, gelu_u=up, pad=True))
     e = 0.0 if torch.equal(dx, dx0) else 1.0
     ref = dx.double().sum(0)
     return max(e, float((out.double() - 3.0 - ref).abs().max() / ref.abs().max())), 2e-5
@@ -1173,7 +1205,7 @@ def wgrad_group_check(M, shapes=LAYER_WGRADS, padded_rows=True):
     items, refs = [], []
     for i, (N, K) in enumerate(shapes):
         dy, x = ints((M, N), dt, 10 + i), ints((M, K), dt, 30 + i)
-        out = torch.full((N, K), float(i + 1), dtype=torch.float32, device=DEV)
+        out = _prefilled(torch.full((N, K), float(i + 1), dtype=torch.float32, device=DEV), 'accumulator')
         refs.append(dy.double().t() @ x.double() + float(i + 1))
         items.append((padded(dy), padded(x), out) if padded_rows else (dy, x, out))
     ops.linear_wgrad_group(items)
@@ -1377,8 +1409,8 @@ def _exact(a, b):
 
 def _fused_param(t, fill):
     """a float32 parameter whose gradient the Functions accumulate into a pre-filled .grad (functional._target)"""
-    p = torch.nn.Parameter(t.clone())
-    p.grad = torch.full_like(p, fill)
+    p = torch.nn.Parameter(G.place(t.clone()))
+    p.grad = _prefilled(torch.full_like(p, fill), 'accumulator')
     p._istvt_fused_grad = True
     return p
 
@@ -1398,7 +1430,7 @@ def prepend_check(dtype, S, n, period=None, pos_rows=None, Ds=(64, 728, 1544)):
         if period is not None:
             pos = ints((period, pos_rows, D), torch.float32, 3, -3, 4)
             pos = _fused_param(pos, -4.0) if pos_grad else pos
-        out = Fn.PrependFn.apply(src, tok, pos, period if period is not None else 1)
+        out = G.expect(Fn.PrependFn.apply(src, tok, pos, period if period is not None else 1))
         sd, td = src.detach().double(), tok.detach().double()
         ref = torch.cat((td.expand(S, 1, D), sd), dim=1)
         if pos is not None:
@@ -1429,7 +1461,7 @@ def seq_mean_check(dtype, S, n, Ds=(64, 728, 1544)):
         for exact in ((False, True) if n & (n - 1) == 0 else (False,)):
             gen = ints if exact else rnd
             x = padded(gen((S * n, D), dtype, 1)).view(S, n, D).requires_grad_(True)
-            y = Fn.SeqMeanFn.apply(x)
+            y = G.expect(Fn.SeqMeanFn.apply(x))
             g = gen((S, D), dtype, 2)
             y.backward(g)
             ry = x.detach().double().mean(1)
@@ -1453,8 +1485,9 @@ def relu_avgpool_check(dtype, Fr, HW, C, relu):
         zpos = torch.arange(0, flat.numel(), 7, device=DEV)
         flat[zpos[0::2]] = 0.0
         flat[zpos[1::2]] = -0.0
+        G.resnap(x)
         x.requires_grad_(True)
-        y = xblocks.ReluAvgPoolFn.apply(x, Fr, HW, relu)
+        y = G.expect(xblocks.ReluAvgPoolFn.apply(x, Fr, HW, relu))
         g = gen((Fr, C), dtype, 2)
         y.backward(g)
         xd = x.detach().double()
@@ -1476,7 +1509,7 @@ def add_check(dtype, M, D):
     from istvt_amd import functional as Fn
     a, b = ints((M, D), dtype, 1), ints((M, D), dtype, 2)
     ap = padded(a)
-    out = Fn.AddFn.apply(ap, b)
+    out = G.expect(Fn.AddFn.apply(ap, b))
     if M > 1:
         assert len({ap.stride(0), b.stride(0), out.stride(0)}) == 3, (ap.stride(0), b.stride(0), out.stride(0))
     return _fold(0.0, _exact(out, a.double() + b.double())), 0.0
@@ -1494,9 +1527,10 @@ def dropout_strided_check(dtype, M, D, p, seed=12345):
     from istvt_amd import functional as Fn
     x = rnd((M, D), dtype, 1)
     x[x == 0] = 1.0                                   # (so that y != 0 reads the mask)
+    G.resnap(x)
     xp = padded(x).requires_grad_(True)
-    y = Fn.DropoutFn.apply(xp, p, seed)
-    y_dense = Fn.DropoutFn.apply(x, p, seed)
+    y = G.expect(Fn.DropoutFn.apply(xp, p, seed))
+    y_dense = G.expect(Fn.DropoutFn.apply(x, p, seed))
     assert y.stride(0) == ops.pad_ld(D) and y_dense.stride(0) == D
     mask = y_dense != 0
     e = 0.0 if torch.equal(y != 0, mask) else 1.0
@@ -1508,6 +1542,7 @@ def dropout_strided_check(dtype, M, D, p, seed=12345):
     e = _fold(e, 0.0 if torch.equal(y, y_dense) and float(y[~mask].abs().max()) == 0.0 else 1.0)
     dy = rnd((M, D), dtype, 2)
     dy[dy == 0] = 1.0
+    G.resnap(dy)
     y.backward(padded(dy))
     dx = xp.grad
     e = _fold(e, 0.0 if torch.equal(dx != 0, mask) else 1.0)
@@ -1558,7 +1593,7 @@ def rows_reduce_check():
     for rows_ in (1, 15, 16, 17, 300):
         for n in (1, 63, 64, 65, 2912 * 3 + 1):
             ws = ints((rows_, n), torch.float32, rows_ + n)
-            out = ints((n,), torch.float32, 7, -9, 10)
+            out = ints((n,), torch.float32, 7, -9, 10, inplace='accumulator')
             ref = out.double() + ws.double().sum(0)
             _lib.check(L.istvt_rows_reduce(ws.data_ptr(), rows_, n, out.data_ptr(), ops._stream()), 'istvt_rows_reduce')
             e = _fold(e, _exact(out, ref))
@@ -1578,7 +1613,7 @@ def cast_check():
         for ti in (torch.float32, torch.bfloat16):
             for to in (torch.float32, torch.bfloat16):
                 x = rnd((n,), torch.float32, n, 37.0).to(ti)
-                out = torch.full((n + 8,), float('nan'), dtype=to, device=DEV)
+                out = _prefilled(torch.full((n + 8,), float('nan'), dtype=to, device=DEV))
                 _lib.check(L.istvt_cast(x.data_ptr(), ops._DT[ti], out.data_ptr(), ops._DT[to], n, ops._stream()), 'istvt_cast')
                 ok = torch.equal(_bits(out[:n]), _bits(x.to(to))) and bool(out[n:].isnan().all())
                 e = _fold(e, 0.0 if ok else 1.0)
@@ -1595,7 +1630,7 @@ def cast2d_check():
         for ti in (torch.float32, torch.bfloat16):
             for to in (torch.float32, torch.bfloat16):
                 x = padded(rnd((R, C), torch.float32, R + C, 37.0).to(ti))
-                buf = torch.full((R, ops.pad_ld(C) + 8), float('nan'), dtype=to, device=DEV)
+                buf = _prefilled(torch.full((R, ops.pad_ld(C) + 8), float('nan'), dtype=to, device=DEV))
                 _lib.check(L.istvt_cast2d(x.data_ptr(), ops._DT[ti], x.stride(0), buf.data_ptr(), ops._DT[to], buf.stride(0),
                                           R, C, ops._stream()), 'istvt_cast2d')
                 ok = torch.equal(_bits(buf[:, :C]), _bits(x.to(to))) and bool(buf[:, C:].isnan().all())
@@ -1615,9 +1650,9 @@ def cast_transpose_group_check(count=40):
         R, Cc = shapes[i % len(shapes)]
         ws.append(rnd((R, Cc), torch.float32, 100 + i, 3.0))
         for lst in (outs, one):
-            lst.append(torch.full((R, ops.pad_ld(Cc)), float('nan'), dtype=torch.bfloat16, device=DEV))
+            lst.append(_prefilled(torch.full((R, ops.pad_ld(Cc)), float('nan'), dtype=torch.bfloat16, device=DEV)))
         for lst in (outts, onet):
-            lst.append(torch.full((Cc, ops.pad_ld(R)), float('nan'), dtype=torch.bfloat16, device=DEV))
+            lst.append(_prefilled(torch.full((Cc, ops.pad_ld(R)), float('nan'), dtype=torch.bfloat16, device=DEV)))
     PA, LA, IA = C.c_void_p * count, C.c_long * count, C.c_int * count
     _lib.check(L.istvt_cast_transpose_group(count, PA(*[w.data_ptr() for w in ws]), LA(*[w.stride(0) for w in ws]),
                                             PA(*[o.data_ptr() for o in outs]), LA(*[o.stride(0) for o in outs]),
@@ -1644,7 +1679,7 @@ def colsum_edges_check(dtype):
     for M in (1, 3, 63, 64, 65, 4099):
         for N in (8, 520, 2912):
             x = ints((M, N), dtype, M + N)
-            out = ints((N,), torch.float32, 5, -9, 10)
+            out = ints((N,), torch.float32, 5, -9, 10, inplace='accumulator')
             ref = out.double() + x.double().sum(0)
             ops.colsum(padded(x) if M > 1 else x, out)
             e = _fold(e, _exact(out, ref))
@@ -1656,9 +1691,9 @@ def _operand(t, ld, off):
     """t [R, C] as a view with row stride ld that starts `off` elements into a NaN-filled buffer"""
     R, Cc = t.shape
     buf = torch.full((off + R * ld + 8,), float('nan'), dtype=t.dtype, device=t.device)
-    v = buf[off:off + R * ld].view(R, ld)[:, :Cc]
-    v.copy_(t)
-    return v
+    buf[off:off + R * ld].view(R, ld)[:, :Cc].copy_(t)
+    buf = G.place(buf)                               # (same offset into a guarded copy: the alignment of the view is kept)
+    return buf[off:off + R * ld].view(R, ld)[:, :Cc]
 
 
 def _splits(K, splitk, dtype):
@@ -1693,23 +1728,23 @@ def gemm_unaligned(dtype, layout, M=129):
             prod = Al.double() @ Bl.double().t()
             kw = dict(M=M, N=N, K=K)
             # mode 0: the storage type
-            C = torch.full((M, N), float('nan'), dtype=dtype, device=DEV)
+            C = _prefilled(torch.full((M, N), float('nan'), dtype=dtype, device=DEV))
             ops.gemm_raw(A, lda, a_kc, B, ldb, b_kc, C, N, **kw)
             e = _fold(e, _exact(C, prod.to(dtype)))
             # mode 1: float store
-            C = torch.full((M, N), float('nan'), dtype=torch.float32, device=DEV)
+            C = _prefilled(torch.full((M, N), float('nan'), dtype=torch.float32, device=DEV))
             ops.gemm_raw(A, lda, a_kc, B, ldb, b_kc, C, N, out_mode=1, **kw)
             e = _fold(e, _exact(C, prod))
             # mode 2: atomic add onto a pre-filled float output
-            C = ints((M, N), torch.float32, 9, -9, 10)
+            C = ints((M, N), torch.float32, 9, -9, 10, inplace='accumulator')
             ref = C.double() + prod
             ops.gemm_raw(A, lda, a_kc, B, ldb, b_kc, C, N, out_mode=2, **kw)
             e = _fold(e, _exact(C, ref))
             # mode 3: split-K partial slabs, summed in slab order by istvt_rows_reduce; slabs past the split count untouched
             ns = _splits(K, 3, dtype)
-            slabs = torch.full((3, M, N), float('nan'), dtype=torch.float32, device=DEV)
+            slabs = _prefilled(torch.full((3, M, N), float('nan'), dtype=torch.float32, device=DEV))
             ops.gemm_raw(A, lda, a_kc, B, ldb, b_kc, slabs, N, out_mode=3, splitk=3, **kw)
-            out = ints((M, N), torch.float32, 10, -9, 10)
+            out = ints((M, N), torch.float32, 10, -9, 10, inplace='accumulator')
             ref = out.double() + prod
             _lib.check(_lib.lib().istvt_rows_reduce(slabs.data_ptr(), ns, M * N, out.data_ptr(), ops._stream()), 'istvt_rows_reduce')
             e = _fold(e, _exact(out, ref))
@@ -1719,7 +1754,7 @@ def gemm_unaligned(dtype, layout, M=129):
             bias = ints((N,), torch.float32, 11, -3, 4)
             ldr = N + 1 + (N % 2)
             res = _operand(ints((M, N), dtype, 12), ldr, 0)
-            C = torch.full((M, N), float('nan'), dtype=dtype, device=DEV)
+            C = _prefilled(torch.full((M, N), float('nan'), dtype=dtype, device=DEV))
             ops.gemm_raw(A2, lda, a_kc, B, ldb, b_kc, C, N, bias=bias, residual=res, ldr=ldr, alpha=0.5, **kw)
             e = _fold(e, _exact(C, (prod + bias.double() + res.double()).to(dtype)))
     return e, 0.0
@@ -1729,13 +1764,13 @@ def gemm_unaligned_gelu(dtype, M=129, N=130, K=75):
     """the two GELU epilogues of the generic kernel through its scalar stores (N = ldc = 130), rows of K = 75 elements:
     real data against float64"""
     x, w, b = rnd((M, K), dtype, 1), rnd((N, K), dtype, 2, K ** -0.5), rnd((N,), torch.float32, 3)
-    u = torch.full((M, N), float('nan'), dtype=dtype, device=DEV)
-    g = torch.full((M, N), float('nan'), dtype=dtype, device=DEV)
+    u = _prefilled(torch.full((M, N), float('nan'), dtype=dtype, device=DEV))
+    g = _prefilled(torch.full((M, N), float('nan'), dtype=dtype, device=DEV))
     ops.gemm_raw(x, K, 1, w, K, 1, u, N, M, N, K, bias=b, C2=g, epi=1)
     ru = x.double() @ w.double().t() + b.double()
     e = _fold(_fold(0.0, relerr(u, ru)), relerr(g, torch.nn.functional.gelu(ru)))
     U = rnd((M, N), dtype, 4)
-    d = torch.full((M, N), float('nan'), dtype=dtype, device=DEV)
+    d = _prefilled(torch.full((M, N), float('nan'), dtype=dtype, device=DEV))
     ops.gemm_raw(x, K, 1, w, K, 1, d, N, M, N, K, C2=U, epi=2)
     ud = U.double().requires_grad_(True)
     torch.nn.functional.gelu(ud).backward(x.double() @ w.double().t())
@@ -1799,4 +1834,619 @@ def all_checks():  # noqa: F811
         for layout in ('nt', 'nn', 'tn'):
             out.append(('gemm_unaligned_%s_%s' % (layout, tag), lambda dt=dt, layout=layout: gemm_unaligned(dt, layout)))
         out.append(('gemm_unaligned_gelu_%s' % tag, lambda dt=dt: gemm_unaligned_gelu(dt)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ guard bands (tests/guard.py)
+# The checks above compare VALUES.  The layer below runs a small-shape subset of them (and the smallest kernel cases of
+# tests/test_relevance_gpu.py, test_loss_gpu.py, test_fused_optim_gpu.py and test_pw_bwd_gpu.py, lifted here) once more inside
+# guard.guarded(): every tensor the wrappers allocate sits between sentinel guards, inputs are placed in guarded buffers
+# that must come back unchanged, declared outputs must be written exactly where the returned view is.  A guarded entry
+# returns the check's own (err, tol) -- parity and placement in one run; a read of a guard or of a pad column would show
+# in err, the sentinel being a NaN -- raises guard.GuardViolation on a misplaced write, and then asserts that the entry
+# points it was chosen for (EXPECTED_CALLS) were really called; the GEMM entries also that every launch took the kernel
+# the same call takes outside the harness (ops.gemm_kernel_name through ops.gemm_profile).
+def _rows_input(t):
+    """t [M, D] in the forward's row-strided layout (ops.empty_rows); under the harness a placed input with sentinel pads"""
+    M, D = t.shape
+    if G.active() is not None:
+        ld = ops.pad_ld(D)
+        return G.place(t, pad=True, ld=ld) if ld != D else G.place(t)
+    v = ops.empty_rows(M, D, t.dtype, t.device)
+    v.copy_(t)
+    return v
+
+
+def relevance_spatial_check(dtype, P=50, heads=2, dh=32, BF=1):
+    """tests/test_relevance_gpu.py::test_spatial_relevance_kernel, its smallest case (same data, restatement and bounds:
+    the error of r_out at TOL, that of the increment at 10 TOL)"""
+    import test_relevance_gpu as TR
+    g = torch.Generator().manual_seed(P * 100 + heads * 10 + dh + BF)
+    inner = heads * dh
+    qkv = _rows_input(TR._rand((BF * P, 3 * inner), g, dtype, 0.6))
+    dout = G.place(TR._rand((BF * P, inner), g, dtype))
+    r = torch.rand((BF, P), generator=g).cuda()
+    r[:, 0] += 1.0
+    r = G.place(r)
+    _, lse = G.expect(*ops.attn_spatial_fwd(qkv, BF, P, heads, dh))
+    out = G.expect(ops.attn_spatial_relevance(qkv, dout, lse, r, BF, P, heads, dh))
+    ref = TR._spatial_ref(qkv, dout, r, BF, P, heads, dh)
+    err = float((out.double() - ref).norm() / ref.norm())
+    inc = float(((out.double() - r.double()) - (ref - r.double())).norm() / (ref - r.double()).norm())
+    again = G.expect(ops.attn_spatial_relevance(qkv, dout, lse, r, BF, P, heads, dh))
+    return _fold(_fold(_fold(0.0, err), inc / 10.0), 0.0 if torch.equal(out, again) else 1.0), TR.TOL[dtype]
+
+
+def relevance_temporal_check(dtype, F=5, diff=1, B=2, P=50, heads=2, dh=32):
+    """tests/test_relevance_gpu.py::test_temporal_relevance_kernel, its smallest case"""
+    import test_relevance_gpu as TR
+    g = torch.Generator().manual_seed(F * 10 + diff)
+    inner = heads * dh
+    M = B * F * P
+    qkv = _rows_input(TR._rand((M, 3 * inner), g, dtype, 0.6))
+    dout = G.place(TR._rand((M, inner), g, dtype))
+    r = torch.rand((B * P, F), generator=g).cuda()
+    r[:, 0] += 1.0
+    r = G.place(r)
+    out = G.expect(ops.attn_temporal_relevance(qkv, dout, r, B, F, P, heads, dh, diff))
+    ref = TR._temporal_ref(qkv, dout, r, B, F, P, heads, dh, diff)
+    err = float((out.double() - ref).norm() / ref.norm())
+    inc = float(((out.double() - r.double()) - (ref - r.double())).norm() / (ref - r.double()).norm())
+    return _fold(_fold(0.0, err), inc / 10.0), TR.TOL[dtype]
+
+
+def relevance_heatmap_check(g_in=14):
+    """tests/test_relevance_gpu.py::test_heatmaps_match_interpolate_and_min_max at the smaller grid: bilinear upsampling
+    and per-map min-max against torch's interpolate, 1e-6 absolute"""
+    cam = torch.rand((2, 3, g_in, g_in), generator=torch.Generator().manual_seed(g_in), dtype=torch.float32) ** 3
+    out = G.expect(ops.relevance_heatmap(G.place(cam.cuda()), scale=16))
+    up = torch.nn.functional.interpolate(cam.view(-1, 1, g_in, g_in), scale_factor=16, mode='bilinear', align_corners=False)
+    up = up.view(2, 3, g_in * 16, g_in * 16)
+    mn, mx = up.amin(dim=(-1, -2), keepdim=True), up.amax(dim=(-1, -2), keepdim=True)
+    return _fold(0.0, (out.cpu() - (up - mn) / (mx - mn)).abs().max()), 1e-6
+
+
+def bce_check(n=65):
+    """tests/test_loss_gpu.py::test_kernel_against_float64_restatement, one configuration (per-sample weights, pos_weight
+    3, label smoothing 0.1, 'mean', float targets) at n = 1 and at 65, one past a 64-sample block: losses, reduced loss and
+    gradient at 2e-5, the meter's counts exact; then istvt_bce_logits_bwd against d * g"""
+    import test_loss_gpu as TL
+    from istvt_amd import loss as loss_mod
+    z, y, w = (G.place(t.contiguous()) for t in TL._inputs(n, 100 + n))
+    ref = loss_mod.bce_logits_ref(z, y, w, 3.0, 0.1, 'mean')
+    meter = torch.zeros(10, dtype=torch.int64, device=DEV)
+    loss, reduced, d = G.expect(*ops.bce_logits(z, y, w, 3.0, 0.1, 'mean', 0.0, want_loss=True, want_reduced=True,
+                                                want_grad=True, meter=meter))
+    e = 0.0
+    for got, want in ((loss, ref['loss']), (reduced, ref['reduced']), (d, ref['grad'])):
+        e = _fold(e, TL.relerr(got, want))
+    _, words = TL._meter_words(meter)
+    if words[:6] != [ref['counts'][k] for k in TL.COUNTS] or words[6:] != [1, 0]:
+        e = _fold(e, 1.0)
+    gvec = rnd((1,), torch.float32, 5)
+    grad = G.expect(ops.bce_logits_bwd(d, gvec))
+    e = _fold(e, relerr(grad, d.double() * gvec.double()))
+    return e, TL.TOL
+
+
+def fused_optim_check(kind):
+    """tests/test_fused_optim_gpu.py::test_one_group_through_groups_entry_is_bit_identical (N = 5503: three elements behind
+    the last whole 16-byte quad): istvt_sgd_momentum / istvt_adamw against their _groups form over three steps, one of them
+    with the fused zero-grad; every buffer equal in every bit, and the gradient zeroed or untouched.  The kernels update
+    in place over a flat length: parameter, gradient and state sit in guarded buffers whose tail guard is the point."""
+    import ctypes
+    import test_fused_optim_gpu as TO
+    from istvt_amd import _lib
+    lib = _lib.lib()
+    N = TO.N
+    gen = torch.Generator().manual_seed(5)
+    p0 = torch.randn(N, generator=gen).cuda()
+    grads = [torch.randn(N, generator=gen).cuda() for _ in range(3)]
+    nstate = 1 if kind == 'sgd' else 2
+
+    def bufs():
+        return [_prefilled(p0.clone(), 'optimizer.param')] + [_prefilled(torch.zeros(N, device=DEV), 'optimizer.state')
+                                                              for _ in range(nstate)]
+    plain, group = bufs(), bufs()
+    seg_end = G.place(torch.tensor([N], dtype=torch.int64, device=DEV))
+    seg_gid = G.place(torch.zeros(1, dtype=torch.int32, device=DEV))
+    lr, wd = (ctypes.c_float * 1)(0.05), (ctypes.c_float * 1)(0.01)
+    ok = True
+    for step, gv in enumerate(grads):
+        ga, gb = _prefilled(gv.clone(), 'optimizer.grad'), _prefilled(gv.clone(), 'optimizer.grad')
+        zero = int(step == 1)
+        if kind == 'sgd':
+            _lib.check(lib.istvt_sgd_momentum(plain[0].data_ptr(), ga.data_ptr(), plain[1].data_ptr(), N, 0.05, 0.9, 0.1, 0.01,
+                                              0, int(step == 0), zero, 0.5, ops._stream()), 'plain')
+            _lib.check(lib.istvt_sgd_momentum_groups(group[0].data_ptr(), gb.data_ptr(), group[1].data_ptr(), N,
+                                                     seg_end.data_ptr(), seg_gid.data_ptr(), 1, lr, wd, 1, 0.9, 0.1, 0,
+                                                     int(step == 0), zero, 0.5, None, 0, ops._stream()), 'groups')
+        else:
+            _lib.check(lib.istvt_adamw(plain[0].data_ptr(), ga.data_ptr(), plain[1].data_ptr(), plain[2].data_ptr(), N, 0.05,
+                                       0.9, 0.999, 1e-8, 0.01, step + 1, zero, 0.5, ops._stream()), 'plain')
+            _lib.check(lib.istvt_adamw_groups(group[0].data_ptr(), gb.data_ptr(), group[1].data_ptr(), group[2].data_ptr(), N,
+                                              seg_end.data_ptr(), seg_gid.data_ptr(), 1, lr, wd, 1, 0.9, 0.999, 1e-8,
+                                              step + 1, zero, 0.5, None, 0, ops._stream()), 'groups')
+        torch.cuda.synchronize()
+        ok = ok and all(torch.equal(a, b) for a, b in zip(plain + [ga], group + [gb]))
+        ok = ok and (float(ga.abs().max()) == 0.0 if zero else torch.equal(ga, gv))
+    ok = ok and not torch.equal(plain[0], p0)
+    return (0.0 if ok else 1.0), 0.0
+
+
+def grad_norm_check():
+    """tests/test_fused_optim_gpu.py::test_grad_norm_repeats_its_bits_and_matches_float64 at its two smallest lengths
+    (255, 1025): two launches give the same step-info block, the norm is within 1e-6 of float64"""
+    import test_fused_optim_gpu as TO
+    from istvt_amd import _lib, parallel
+    lib = _lib.lib()
+    gen = torch.Generator().manual_seed(8)
+    e = 0.0
+    for n in TO._norm_sizes(parallel)[2:4]:
+        g = torch.randn(n, generator=gen)
+        gd = G.place(g.cuda())
+        ws = torch.empty(lib.istvt_grad_norm_ws_elems(n), dtype=torch.float64, device=DEV)
+        infos = [torch.zeros(8, dtype=torch.int32, device=DEV) for _ in range(2)]
+        for info in infos:
+            ws.fill_(float('nan'))
+            _lib.check(lib.istvt_grad_norm(gd.data_ptr(), n, 0.5, 0.0, 0, ws.data_ptr(), ws.numel(), info.data_ptr(),
+                                           ops._stream()), 'istvt_grad_norm')
+        norm, scale = infos[0][:2].view(torch.float32).tolist()
+        want = float((0.5 * g.double()).norm())
+        e = _fold(e, abs(norm - want) / want)
+        if not torch.equal(infos[0], infos[1]) or scale != 0.5 or infos[0][2:].tolist() != [1, 0, 0, 0, 0, 0]:
+            e = _fold(e, 1.0)
+    return e, 1e-6
+
+
+def pw_bwd_check(mkey='one', cin=64, cout=128, training=True):
+    """tests/test_pw_bwd_gpu.py::test_fused_matches_three_launches, the 64 -> 128 unit in training mode on a pre-filled
+    weight gradient: dgamma / dbeta equal in every bit, dd within that file's bound of the three-launch value (returned as
+    error / bound, tolerance 1), dW the bits of ops.linear_wgrad(du, d, out=P)"""
+    import os
+    import test_pw_bwd_gpu as TP
+    from istvt_amd import stem as S
+    c = TP._case(cin, cout, mkey, training)
+    M = c['M']
+    assert ops.pw_bwd_fusable(c['dz'], c['d'], c['w'])
+    P = torch.randn((cout, cin), generator=torch.Generator(device='cuda').manual_seed(7), device=DEV) + 0.5
+    dz, u, d, w, gamma = (G.place(c[k]) for k in ('dz', 'u', 'd', 'w', 'gamma'))
+    st = S.BNState(cout, DEV)
+    st.pack.copy_(c['st'].pack)
+    out = _prefilled(P.clone(), 'accumulator')
+    dg, db = _prefilled(c['dg0'].clone(), 'accumulator'), _prefilled(c['db0'].clone(), 'accumulator')
+    acc = _prefilled(c['acc'].clone(), 'accumulator')
+    saved = os.environ.get('ISTVT_STEM_PW_BWD_FUSED')
+    os.environ['ISTVT_STEM_PW_BWD_FUSED'] = '1'
+    try:
+        dd, dW = S.pointwise_bn_backward(dz, u, st, gamma, M, cout, d, w, cin, acc, dg, db, out, training)
+    finally:
+        if saved is None:
+            del os.environ['ISTVT_STEM_PW_BWD_FUSED']
+        else:
+            os.environ['ISTVT_STEM_PW_BWD_FUSED'] = saved
+    G.expect(dd)
+    assert dW is None and tuple(dd.shape) == (M, cin)
+    old = c['dd_old'].double()
+    lim = 2.0 ** -7 * old.abs() + c['dd_slack']
+    e = _fold(0.0, ((dd.double() - old).abs() / lim.clamp_min(1e-300)).max())
+    bits = (torch.equal(dg, c['dg_old']) and torch.equal(db, c['db_old'])
+            and torch.equal(out, ops.linear_wgrad(c['du'], c['d'], out=P.clone())))
+    return _fold(e, 0.0 if bits else 2.0), 1.0
+
+
+def subsample2_check(dtype, Fr=2, H=7, W=5, C=24):
+    """istvt_subsample2 (the strided skip's input: every second pixel of every second row, odd sizes): a copy, exact"""
+    from istvt_amd import _lib
+    x = ints((Fr * H * W, C), dtype, 1)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    out = torch.empty((Fr * Ho * Wo, C), dtype=dtype, device=DEV)
+    _lib.check(_lib.lib().istvt_subsample2(x.data_ptr(), out.data_ptr(), Fr, H, W, C, ops.dtype_code(x), ops._stream()),
+               'istvt_subsample2')
+    G.expect(out)
+    ref = x.view(Fr, H, W, C)[:, ::2, ::2].reshape(-1, C)
+    return _fold(0.0, _exact(out, ref)), 0.0
+
+
+def bn_add_check(dtype, M=333, C=24, with_skip_bn=True):
+    """istvt_bn_add_fwd (a block's tail without pooling): out = BN(x) rounded to the storage type + BN_s(skip) (or + skip,
+    the identity skip), against float64 with the same storage rounding of BN(x)"""
+    from istvt_amd import _lib, stem as S
+    x, sk = rnd((M, C), dtype, 1), rnd((M, C), dtype, 2)
+    bns = []
+    for k in range(2):
+        bn = S.BNState(C, DEV)
+        bn.scale.copy_(rnd((C,), torch.float32, 3 + 4 * k, 0.5)); bn.beta.copy_(rnd((C,), torch.float32, 4 + 4 * k, 0.3))
+        bn.mean.copy_(rnd((C,), torch.float32, 5 + 4 * k, 0.2)); bn.rstd.fill_(1.0)
+        bns.append(bn)
+    out = torch.empty((M, C), dtype=dtype, device=DEV)
+    _lib.check(_lib.lib().istvt_bn_add_fwd(x.data_ptr(), bns[0].ptr(), sk.data_ptr(), bns[1].ptr() if with_skip_bn else None,
+                                           out.data_ptr(), M, C, ops.dtype_code(x), ops._stream()), 'istvt_bn_add_fwd')
+    G.expect(out)
+
+    def affine(t, bn):
+        return (t.double() - bn.mean.double()) * bn.scale.double() + bn.beta.double()
+    ref = affine(x, bns[0]).to(dtype).double() + (affine(sk, bns[1]) if with_skip_bn else sk.double())
+    return _fold(0.0, relerr(out, ref)), TOL[dtype]
+
+
+def bytes_conv1_check(dtype, side=33):
+    """tests/test_train_bytes_gpu.py at its smallest side (33, the identity view and per-frame views of a larger odd-sized
+    source): conv1 forward, its weight gradient and im2col from uint8 frames, each equal in every bit to the float-input
+    kernel on clips.to_float of the same bytes; and test_video_gpu.py's contiguous entry on the identity case"""
+    import test_train_bytes_gpu as TB
+    from istvt_amd import clips
+    norm = TB.IMAGENET
+    m, s = (G.place(t) for t in TB._norm_dev(norm))
+    w = G.place(torch.randn((32, 3, 3, 3), generator=torch.Generator().manual_seed(side + 1)).cuda())
+    Ho = (side - 3) // 2 + 1
+    ok = True
+    for name, u8, view in TB._cases(side):
+        n = u8.shape[0]
+        x = clips.to_float(u8, norm[0], norm[1], view, side).cuda()
+        dev = G.place(u8.cuda())
+        ok = ok and torch.equal(ops.conv1_fwd_u8_view(dev, view, side, m, s, w, dtype), ops.conv1_fwd(x, w, dtype))
+        if view is None:
+            ok = ok and torch.equal(ops.conv1_fwd_u8(dev, m, s, w, dtype), ops.conv1_fwd(x, w, dtype))
+        du1 = G.place(torch.randn((n * Ho * Ho, 32), generator=torch.Generator().manual_seed(side)).cuda().to(dtype))
+        out = ops.conv1_wgrad_u8(du1, dev, view, side, m, s)
+        ok = ok and torch.equal(out, ops.conv1_wgrad(du1, x)) and float(out[:, 27:].abs().max()) == 0.0 and float(out.abs().max()) > 0
+        col = ops.im2col_conv1_u8(dev, view, side, m, s, dtype)
+        ok = ok and torch.equal(col, ops.im2col_conv1(x, dtype)) and float(col[:, 27:].float().abs().max()) == 0.0
+    return (0.0 if ok else 1.0), 0.0
+
+
+def tokens_gather_check(dtype, T=4):
+    """tests/test_video_gpu.py::test_tokens_gather_bit_identical at T = 4: the gather form against tokens_fwd on the
+    gathered features, dense and padded rows, every bit"""
+    g = torch.Generator().manual_seed(T)
+    cap, hw, D, W = 23, 36, 728, 7
+    bank = G.place(torch.randn((cap, hw, D), generator=g).to(dtype).cuda())
+    idx = torch.randint(0, cap, (W, T), generator=g, dtype=torch.int32)
+    idx[1] = idx[0]
+    idx[2, 1] = idx[2, 0]
+    space, temporal = G.place(torch.randn((1, 1, D), generator=g).cuda()), G.place(torch.randn((1, 1, D), generator=g).cuda())
+    pos = G.place(torch.randn((1, T, hw + 3, D), generator=g).cuda())
+    ok = True
+    for pad in (False, True):
+        ref = ops.tokens_fwd(bank[idx.long().cuda()], space, temporal, pos, pad=pad)
+        out = G.expect(ops.tokens_gather_fwd(bank, idx, space, temporal, pos, pad=pad))
+        ok = ok and tuple(out.shape) == (W, (T + 1) * (hw + 1), D) and torch.equal(out, ref)
+    return (0.0 if ok else 1.0), 0.0
+
+
+def windows_reduce_check(nc=1):
+    """tests/test_video_set_gpu.py::test_windows_reduce: videos of 1, 1, 68, 1 and 329 windows; the logit means within one
+    float32 ulp of float64 (returned in ulps, tolerance 1), the probability means within 1e-6"""
+    from istvt_amd import video
+    off = [0, 1, 2, 70, 71, 400]
+    g = torch.Generator().manual_seed(40 + nc)
+    x = (torch.rand((400, nc), generator=g) * 60 - 30).float()
+    x[5, 0], x[6, 0] = 30.0, -30.0
+    lm64, pm64 = video.windows_reduce_ref(x, off)
+    lm, pm = G.expect(*ops.windows_reduce(G.place(x.cuda()), off))
+    r32 = lm64.float()
+    ulp = (torch.nextafter(r32.abs(), torch.full_like(r32, float('inf'))) - r32.abs()).double()
+    e = _fold(0.0, ((lm.cpu().double() - lm64).abs() / ulp).max())
+    return _fold(e, (pm.cpu().double() - pm64).abs().max() / 1e-6), 1.0
+
+
+def auc_pairs_check():
+    """tests/test_video_set_gpu.py::test_auc_pairs_and_set_metrics, the kernel part: V = 1, 2, 257 and 1000, the host's
+    integer counts and its float64 AUC exactly (same_metrics asserts)"""
+    from istvt_amd import video
+    from test_video_set_cpu import metric_cases, same_metrics
+    for name, s, lab in metric_cases():
+        ref = video.set_metrics_ref(s, lab, 3.0)
+        counts, auc = G.expect(*ops.auc_pairs(G.place(s.cuda()), G.place(lab.to(torch.int32).cuda()), 3.0))
+        same_metrics(dict(zip(ops.AUC_COUNTS, counts.tolist()), auc=float(auc)), ref)
+    return 0.0, 0.0
+
+
+def fuse_windows_check(T=4, g=6):
+    """tests/test_video_explain_gpu.py::test_fuse_kernel_vs_float64 at T = 4, g = 6: five window layouts, the four float
+    outputs at 1e-6 against float64, the counts exact, uncovered frames zero"""
+    from istvt_amd import video
+    from test_video_explain_cpu import fuse_ref
+    P, F, n = g * g + 1, T + 1, 3 * T + 5
+    gen = torch.Generator().manual_seed(100 * T + g)
+    e = 0.0
+    for stride, tail in ((1, True), (3, True), (T, False), (T + 3, True), (T + 3, False)):
+        starts = video.window_starts(n, T, stride, tail)
+        W = len(starts)
+        r_s, r_t = torch.rand((W, F, P), generator=gen), torch.rand((W, P, F), generator=gen)
+        logits = torch.randn((W, 2), generator=gen)
+        out = G.expect(*ops.relevance_fuse_windows(G.place(r_s.cuda()), G.place(r_t.cuda()), G.place(logits.cuda()), starts, n, index=1))
+        ref = fuse_ref(r_s, r_t, logits, starts, n, index=1)
+        for o, r in zip(out[:4], ref[:4]):
+            e = _fold(e, relerr(o.cpu(), r))
+        empty = ref[4] == 0
+        if not torch.equal(out[4].cpu(), ref[4]) or any(float(o.cpu()[empty].abs().sum()) != 0.0 for o in out[:4]):
+            e = _fold(e, 1.0)
+    return e, 1e-6
+
+
+def overlay_check(g=6, S=96):
+    """tests/test_video_explain_gpu.py::test_overlay_kernel_vs_float64 at g = 6, S = 96 (its own byte rule, asserted there)"""
+    import test_video_explain_gpu as TE
+    from istvt_amd import explain
+    gen = torch.Generator().manual_seed(g)
+    N = 3
+    maps = torch.rand((N, g, g), generator=gen)
+    frames = torch.randint(0, 256, (N, S, S, 3), generator=gen, dtype=torch.uint8)
+    out = explain.overlay(G.place(frames.cuda()), G.place(maps.cuda()), scale=16)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (N, g * 16, g * 16, 3)
+    TE._check_overlay(out, frames, maps, explain.jet_lut(), 16, 'guarded g=%d S=%d' % (g, S))
+    return 0.0, 0.0
+
+
+def warp_check(S=16):
+    """tests/test_warp_gpu.py: the first small transform on 3 frames of 37 x 53 against the float64 restatement (its byte
+    rule, asserted there), and the NV12 form against the warp of the converted frames (every bit)"""
+    import test_warp_gpu as TW
+    from istvt_amd import clips
+    frames = TW.frames_of(3, 37, 53, 3753)
+    M = torch.stack([TW.similarity(*TW.SMALL[0], S)] * 3)
+    got = ops.warp_similarity_u8(G.place(frames.cuda()), M, S)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (3, S, S, 3)
+    for i in range(3):
+        v, _ = TW.warp_f64(frames[i].numpy(), M[i], S)
+        TW.check_against_values(got[i].cpu().numpy(), v, 1e-6, 'guarded frame %d' % i)
+    nv = clips.rgb_to_nv12_host(TW.frames_of(2, 38, 54, 1), 'bt709')
+    rgb = ops.nv12_to_rgb_u8(nv.cuda(), 'bt709')
+    want = ops.warp_similarity_u8(rgb, M[:2], S)
+    same = torch.equal(ops.warp_similarity_nv12(G.place(nv.cuda()), M[:2], S, 'bt709'), want)
+    return (0.0 if same else 1.0), 0.0
+
+
+def paste_u8_check(name='boxes'):
+    """tests/test_paste_gpu.py::test_rgb_against_the_definition on its first table (4 frames of 40 x 56, boxes with ragged
+    16-byte edges, the whole frame, one pixel): out of place against the host definition (its byte rule, asserted there),
+    the input unchanged, nothing outside the rectangles written; then in place"""
+    import test_paste_gpu as TP
+    from istvt_amd import clips, explain
+    rgb, maps, lut = TP.frames_of(4, TP.HS, TP.WS, 4056), TP.maps_of(4, TP.G, 44), explain.jet_lut()
+    A, rect = clips.paste_geometry(4, TP.HS, TP.WS, TP.S, even=False, **TP.small_table(name))
+    al = TP.small_alphas(name)
+    want = clips.paste_maps_host(rgb, maps, A, rect, lut, al, TP.S, pixel_format='rgb24', yuv_matrix='bt709')
+    dev, mdev, ldev = G.place(rgb.cuda()), G.place(maps.cuda()), G.place(lut.cuda())
+    got = ops.relevance_paste_u8(dev, mdev, A, rect, ldev, al, TP.S)
+    band, region = TP.band_of(clips, maps, A, rect, al, TP.S, TP.HS, TP.WS, False)
+    TP.check_bytes(got.cpu(), want, band, region, 'rgb24', 'guarded ' + name)
+    TP.outside_rect_untouched(got.cpu(), rgb, rect, 'rgb24', TP.HS)
+    inpl = _prefilled(rgb.cuda())
+    same = ops.relevance_paste_u8(inpl, mdev, A, rect, ldev, al, TP.S, inplace=True) is inpl and torch.equal(inpl, got)
+    return (0.0 if same else 1.0), 0.0
+
+
+def guard_selftest():
+    """the harness on the device: a tail-guard write 200 rows behind the body and a pad write in the last row, planted with
+    fill_ on slices of the harness's own flat buffer (in-bounds torch writes, no project kernel), are both reported at their
+    position -- in bfloat16 and float32, at ld = 192 where a fixed 4 KiB guard would end after ten rows"""
+    M, D, ld = 37, 130, 192
+    for dtype in (torch.bfloat16, torch.float32):
+        for kind in ('tail', 'pad'):
+            try:
+                with G.guarded(DEV):
+                    buf = torch.empty((M, ld), dtype=dtype, device=DEV)
+                    rec = G.active().records[-1]
+                    buf[:, :D].fill_(1.0)
+                    if kind == 'tail':
+                        at = M * ld + 200 * ld + 3
+                        rec.flat[rec.ge + at:rec.ge + at + 8].fill_(2.0)
+                    else:
+                        at = (M - 1) * ld + D
+                        buf[M - 1:, D:D + 8].fill_(2.0)
+            except G.GuardViolation as v:
+                if v.kind != kind or v.index != at or (v.row, v.col) != (at // ld, at % ld):
+                    return 1.0, 0.0
+            else:
+                return 1.0, 0.0
+    with G.guarded(DEV):                                   # and a clean run reports nothing
+        buf = torch.empty((M, ld), dtype=torch.bfloat16, device=DEV)
+        buf[:, :D].fill_(1.0)
+        G.expect(buf[:, :D])
+    return 0.0, 0.0
+
+
+def _guarded_table():
+    """-> [(name, check, entry points it must be seen calling, is a GEMM entry)]"""
+    f32, bf16 = torch.float32, torch.bfloat16
+    T = []
+
+    def add(name, fn, calls, gemm=False):
+        T.append(('guarded_' + name, fn, frozenset(calls), gemm))
+    GEMM = ('istvt_gemm',)
+    LN = ('istvt_layernorm_fwd', 'istvt_layernorm_bwd')
+    SP = ('istvt_attn_spatial_fwd', 'istvt_attn_spatial_bwd')
+    TE = ('istvt_attn_temporal_fwd', 'istvt_attn_temporal_bwd')
+    for dt, tag in ((f32, 'f32'), (bf16, 'bf16')):
+        big = dt == bf16
+        # ---- GEMM
+        for (M, N, K), stag in (((200, 136, 104), ''), ((700, 72, 40), '_k40'), ((1030, 128, 64), '_k64')):
+            for mode in ('fwd', 'dgrad', 'wgrad'):
+                add('gemm_exact%s_%s_%s' % (stag, mode, tag), lambda dt=dt, mode=mode, M=M, N=N, K=K: gemm_exact(dt, mode, M, N, K),
+                    GEMM, True)
+        add('gemm_padded_rows_%s' % tag, lambda dt=dt: gemm_padded(dt), GEMM + (('istvt_splitk_reduce',) if big else ()), True)
+        for mode in ('fwd_bias_res', 'fwd_gelu', 'dgrad_gelu', 'fwd_gelu_d', 'dgrad_gelu_d', 'wgrad', 'head'):
+            add('gemm_%s_%s' % (mode, tag), lambda dt=dt, mode=mode: gemm_real(dt, mode),
+                GEMM + (('istvt_splitk_reduce',) if big and mode == 'wgrad' else ()), True)
+        for layout in ('nt', 'nn', 'tn'):
+            add('gemm_unaligned_%s_%s' % (layout, tag), lambda dt=dt, layout=layout: gemm_unaligned(dt, layout),
+                GEMM + ('istvt_rows_reduce',), True)
+        add('gemm_unaligned_gelu_%s' % tag, lambda dt=dt: gemm_unaligned_gelu(dt), GEMM, True)
+        add('colsum_edges_%s' % tag, lambda dt=dt: colsum_edges_check(dt), ('istvt_colsum',))
+        # ---- LayerNorm
+        add('layernorm_padded_rows_%s' % tag, lambda dt=dt: layernorm(dt, pad=True), LN)
+        for D_, M_ in ((512, 333), (520, 1003), (1024, 129), (728, 3), (64, 77)):
+            add('layernorm_D%d_M%d_%s' % (D_, M_, tag), lambda dt=dt, D_=D_, M_=M_: layernorm(dt, D_, M_), LN)
+        for B_, F_, P_ in ((3, 9, 23), (5, 2, 1), (4, 1, 7)):
+            add('layernorm_diff_B%d_F%d_P%d_%s' % (B_, F_, P_, tag), lambda dt=dt, B_=B_, F_=F_, P_=P_: layernorm_diff(dt, B_, F_, P_),
+                ('istvt_layernorm_fwd_diff', 'istvt_layernorm_fwd'))
+        add('layernorm_bwd_deferred_M1003_%s' % tag, lambda dt=dt: layernorm_bwd_deferred(dt, 728, 1003),
+            ('istvt_layernorm_fwd', 'istvt_layernorm_bwd', 'istvt_layernorm_bwd_partial', 'istvt_layernorm_bwd_reduce'))
+        # ---- spatial attention (lse is a declared output: nothing outside the fp8 layer compares it)
+        for P in (37, 128, 129, 197, 256, 257, 362, 384, 385):
+            add('attn_spatial_padded_rows_P%d_h2_d64_%s' % (P, tag), lambda dt=dt, P=P: attn_spatial(dt, 2, P, 2, 64, pad=True), SP)
+        add('attn_spatial_padded_rows_P50_h2_d32_%s' % tag, lambda dt=dt: attn_spatial(dt, 3, 50, 2, 32, pad=True), SP)
+        # ---- temporal attention
+        add('attn_temporal_padded_rows_F9_%s' % tag, lambda dt=dt: attn_temporal(dt, 2, 9, 37, 8, 64, pad=True), TE)
+        # ---- helpers
+        add('tokens_padded_rows_%s' % tag, lambda dt=dt: tokens(dt, pad=True), ('istvt_tokens_fwd', 'istvt_tokens_bwd'))
+        add('frame_diff_D728_F3_%s' % tag, lambda dt=dt: frame_diff(dt, 2, 3, 197, 728), ('istvt_frame_diff',))
+        for S_, n, period, extra, Ds in ((6, 7, 3, 2, (64, 728, 1544)), (130, 5, 65, 0, (1544, 64, 728))):
+            add('prepend_pos_S%d_n%d_period%d_%s' % (S_, n, period, tag),
+                lambda dt=dt, S_=S_, n=n, period=period, extra=extra, Ds=Ds: prepend_check(dt, S_, n, period, n + 1 + extra, Ds),
+                ('istvt_prepend_fwd', 'istvt_prepend_bwd'))
+        for S_, n in ((5, 1), (70, 9)):
+            add('seq_mean_S%d_n%d_%s' % (S_, n, tag), lambda dt=dt, S_=S_, n=n: seq_mean_check(dt, S_, n),
+                ('istvt_seq_mean_fwd', 'istvt_seq_mean_bwd'))
+        for Fr, HW, C in ((3, 1, 8), (2, 49, 728), (2, 100, 2048)):
+            for relu in (True, False):
+                add('relu_avgpool_Fr%d_HW%d_C%d_%s_%s' % (Fr, HW, C, 'relu' if relu else 'plain', tag),
+                    lambda dt=dt, Fr=Fr, HW=HW, C=C, relu=relu: relu_avgpool_check(dt, Fr, HW, C, relu),
+                    ('istvt_relu_avgpool_fwd', 'istvt_relu_avgpool_bwd'))
+        for M, D in ((1, 8), (3, 728), (3, 2912)):
+            add('add_strided_M%d_D%d_%s' % (M, D, tag), lambda dt=dt, M=M, D=D: add_check(dt, M, D), ('istvt_add',))
+        add('dropout_strided_p0.1_%s' % tag, lambda dt=dt: dropout_strided_check(dt, 301, 728, 0.1),
+            ('istvt_dropout_fwd', 'istvt_dropout_bwd'))
+        # ---- stem
+        add('stem_dwconv_%s' % tag, lambda dt=dt: dwconv_check(dt), ('istvt_dwconv3x3', 'istvt_dwconv3x3_wgrad'))
+        add('stem_dwconv_c728_%s' % tag, lambda dt=dt: dwconv_check(dt, 2, 14, 14, 728), ('istvt_dwconv3x3', 'istvt_dwconv3x3_wgrad'))
+        for case in 'abc':
+            add('stem_dwepi_%s_%s' % (case, tag), lambda dt=dt, case=case: dwconv_epilogue_check(dt, case),
+                ('istvt_dwconv3x3',) + (('istvt_stats_reduce',) if case != 'b' else ()))
+        for M, C in ((1003, 728), (333, 32)):
+            add('stem_bn_M%d_C%d_%s' % (M, C, tag), lambda dt=dt, M=M, C=C: bn_check(dt, M, C),
+                ('istvt_bn_stats', 'istvt_bn_finalize', 'istvt_bn_apply', 'istvt_bn_bwd_stats', 'istvt_bn_bwd_apply', 'istvt_stats_reduce'))
+        add('stem_pool_%s' % tag, lambda dt=dt: pool_check(dt), ('istvt_pool_add_fwd', 'istvt_pool_bwd', 'istvt_bn_bwd_stats'))
+        add('stem_pool_even_%s' % tag, lambda dt=dt: pool_check(dt, 2, 28, 28, 256), ('istvt_pool_add_fwd', 'istvt_pool_bwd'))
+        add('stem_im2col_%s' % tag, lambda dt=dt: im2col_check(dt),
+            ('istvt_im2col_conv1', 'istvt_col2im_conv1', 'istvt_im2col3x3', 'istvt_col2im3x3', 'istvt_gemm'))
+        conv = ('istvt_conv1_fwd',) + (('istvt_conv1_wgrad', 'istvt_conv2_fwd', 'istvt_conv2_dgrad', 'istvt_conv2_wgrad') if big else ())
+        add('stem_convdense_%s' % tag, lambda dt=dt: conv_dense_check(dt), conv)
+        add('stem_convdense_odd_%s' % tag, lambda dt=dt: conv_dense_check(dt, 3, 77), conv)
+        # ---- relevance
+        add('relevance_spatial_P50_%s' % tag, lambda dt=dt: relevance_spatial_check(dt), ('istvt_attn_spatial_fwd', 'istvt_attn_spatial_relevance'))
+        add('relevance_temporal_F5_%s' % tag, lambda dt=dt: relevance_temporal_check(dt), ('istvt_attn_temporal_relevance',))
+    # ---- bfloat16 only / no dtype
+    for P in (37, 197, 362):
+        add('attn_spatial_fp8_P%d_h2_d64' % P, lambda P=P: attn_spatial_fp8(2, P, 2, 64),
+            ('istvt_attn_spatial_fwd_fp8', 'istvt_attn_spatial_bwd_fp8', 'istvt_attn_spatial_fwd'))
+    for F_ in (1, 2, 3, 7, 8, 10, 15, 16, 17):
+        add('attn_temporal_store_sweep_F%d_d64_bf16' % F_, lambda F_=F_: attn_temporal(bf16, 2, F_, 5, 2, 64, pad=True, diff=2, packed=True), TE)
+        add('attn_temporal_store_sweep_F%d_d32_bf16' % F_, lambda F_=F_: attn_temporal(bf16, 2, F_, 3, 4, 32, pad=True, diff=1, packed=True), TE)
+    add('gemm_khalf_edge_fwd_K97', lambda: gemm_production('fwd', 512, 97, M=3000, nsample=3000), GEMM, True)
+    add('gemm_bn_stats_M300_N256_K128', lambda: gemm_stats_check(300, 256, 128), GEMM + ('istvt_stats_reduce', 'istvt_bn_finalize'), True)
+    add('gemm_a_select', lambda: gemm_a_select(3000, 728, 1536, 1024), GEMM, True)
+    # M = 64 (ops.G256_MIN) is the smallest row count at which ops.gemm_kernel_name still reports what it reports at
+    # M = 5000, gemm256q_kernel<2, false, 0, 256, 2, true>: below it the dispatch leaves the 256x256 kernel, and with the
+    # column sums in the epilogue the row tile is always 256 (_run_guarded asserts the two names equal)
+    add('gemm_gelu_bwd_colsum_M%d' % CSUM_SMALLEST_M, lambda: gemm_csum_check(CSUM_SMALLEST_M),
+        GEMM + ('istvt_stats_reduce_add',), True)
+    add('wgrad_group_layer_M130_dense_rows', lambda: wgrad_group_check(130, padded_rows=False), ('istvt_wgrad_group',))
+    add('wgrad_group_three_M1000', lambda: wgrad_group_check(1000, ((72, 264), (728, 728), (256, 64))), ('istvt_wgrad_group',))
+    add('rows_reduce_edges', rows_reduce_check, ('istvt_rows_reduce',))
+    add('cast_tail_all_pairs', cast_check, ('istvt_cast',))
+    add('cast2d_strided_all_pairs', cast2d_check, ('istvt_cast2d',))
+    add('cast_transpose_tail', lambda: cast_transpose(520, 1544), ('istvt_cast_transpose',))
+    add('cast_transpose_group_8', lambda: cast_transpose_group_check(8), ('istvt_cast_transpose_group', 'istvt_cast_transpose'))
+    add('relevance_heatmap_g14', relevance_heatmap_check, ('istvt_relevance_heatmap',))
+    add('bce_logits_n1', lambda: bce_check(1), ('istvt_bce_logits', 'istvt_bce_logits_bwd'))
+    add('bce_logits_n65', lambda: bce_check(65), ('istvt_bce_logits', 'istvt_bce_logits_bwd'))
+    add('fused_optim_sgd_N5503', lambda: fused_optim_check('sgd'), ('istvt_sgd_momentum', 'istvt_sgd_momentum_groups'))
+    add('fused_optim_adamw_N5503', lambda: fused_optim_check('adamw'), ('istvt_adamw', 'istvt_adamw_groups'))
+    add('grad_norm_n255_n1025', grad_norm_check, ('istvt_grad_norm',))
+    add('pw_bwd_64to128_M1', lambda: pw_bwd_check('one'), ('istvt_pw_bwd', 'istvt_bn_bwd_stats'))
+    add('pw_bwd_64to128_M129', lambda: pw_bwd_check('R+1'), ('istvt_pw_bwd', 'istvt_bn_bwd_stats'))
+    for dt, tag in ((f32, 'f32'), (bf16, 'bf16')):
+        add('stem_subsample2_%s' % tag, lambda dt=dt: subsample2_check(dt), ('istvt_subsample2',))
+        add('stem_bn_add_%s' % tag, lambda dt=dt: bn_add_check(dt), ('istvt_bn_add_fwd',))
+        add('stem_bn_add_identity_skip_%s' % tag, lambda dt=dt: bn_add_check(dt, 77, 728, False), ('istvt_bn_add_fwd',))
+        add('bytes_conv1_S33_%s' % tag, lambda dt=dt: bytes_conv1_check(dt),
+            ('istvt_conv1_fwd_u8', 'istvt_conv1_fwd_u8_view', 'istvt_conv1_wgrad_u8', 'istvt_im2col_conv1_u8',
+             'istvt_conv1_fwd', 'istvt_conv1_wgrad', 'istvt_im2col_conv1'))
+        add('tokens_gather_T4_%s' % tag, lambda dt=dt: tokens_gather_check(dt), ('istvt_tokens_gather_fwd', 'istvt_tokens_fwd'))
+    # the smallest cases of the video / explanation kernels: all four can be called under the harness unchanged
+    add('windows_reduce_nc1', windows_reduce_check, ('istvt_windows_reduce',))
+    add('auc_pairs', auc_pairs_check, ('istvt_auc_pairs',))
+    add('relevance_fuse_windows_T4_g6', fuse_windows_check, ('istvt_relevance_fuse_windows',))
+    add('relevance_overlay_g6_S96', overlay_check, ('istvt_relevance_overlay_u8',))
+    # byte-image kernels without guard bytes in their own files (those that have them: GUARDED_ELSEWHERE below)
+    add('warp_similarity_S16', warp_check, ('istvt_warp_similarity_u8', 'istvt_warp_similarity_nv12'))
+    add('relevance_paste_u8_boxes', paste_u8_check, ('istvt_relevance_paste_u8',))
+    return T
+
+
+CSUM_SMALLEST_M = 64
+_GUARDED = _guarded_table()
+EXPECTED_CALLS = {name: calls for name, _, calls, _ in _GUARDED}
+
+# entry points with pointer arguments whose writes an existing test already puts between guard bytes:
+# name -> (file, test function, what it guards)
+GUARDED_ELSEWHERE = {
+    'istvt_crop_resize_u8': ('tests/test_crop_resize_gpu.py', 'test_slices_guard_band_and_determinism',
+                             'sentinel bytes around the source and around an out= at an odd offset'),
+    'istvt_nv12_to_rgb_u8': ('tests/test_nv12_gpu.py', 'test_to_rgb_pitch_slices_offsets_and_guards',
+                             'sentinel bytes around the surfaces and around out='),
+    'istvt_crop_resize_nv12': ('tests/test_nv12_gpu.py', 'test_unvalidated_table_stays_inside',
+                               'sentinel bytes around the surfaces and around out=, with a box table that was not validated'),
+    'istvt_jpeg_roundtrip_u8': ('tests/test_jpeg_gpu.py', 'test_output_bounds', '4096 guard bytes around the output'),
+    'istvt_perturb_u8': ('tests/test_perturb_gpu.py', 'test_output_bounds', '4096 guard bytes around the output'),
+    'istvt_relevance_paste_nv12': ('tests/test_paste_gpu.py', 'test_nv12_against_the_definition',
+                                   'pitched surfaces in a filled store: the bytes between the rows and behind the last stay'),
+}
+
+# entry points with pointer arguments that write no tensor (the pointers are host tables they only read)
+NOT_A_WRITER = {
+    'istvt_wgrad_group_splits': 'returns the reduction split of a grouped weight gradient from two host int arrays; no launch',
+}
+
+
+def _run_guarded(name, fn, expected, gemm):
+    from istvt_amd import _lib, stem as S
+    arena = dict(S._arena)
+    prof = ops.gemm_profile
+    try:
+        S._arena.update(buf=None, off=0)       # statistics accumulators: from torch.zeros, not from the step arena
+        plain = None
+        if gemm:
+            ops.gemm_profile = []
+            fn()
+            plain = [p[-1] for p in ops.gemm_profile]
+            ops.gemm_profile = []
+        with G.guarded(DEV, _lib) as calls:
+            err, tol = fn()
+        under = [p[-1] for p in ops.gemm_profile] if gemm else None
+    finally:
+        ops.gemm_profile = prof
+        S._arena.clear()
+        S._arena.update(arena)
+    assert expected <= calls, '%s: expected entry points %s were not called (seen: %s)' % (name, sorted(expected - calls), sorted(calls))
+    if gemm:
+        assert plain and under == plain, '%s: kernels under the harness %s, outside it %s' % (name, under, plain)
+        if name.startswith('guarded_gemm_gelu_bwd_colsum'):
+            ops.gemm_profile = []
+            try:
+                gemm_csum_check(5000)
+                at5000 = sorted(set(p[-1] for p in ops.gemm_profile))
+            finally:
+                ops.gemm_profile = prof
+            assert sorted(set(plain)) == at5000, (plain, at5000)
+    return err, tol
+
+
+def guarded_entries():
+    """-> [(name, callable)]: the guard-band layer"""
+    return [(name, lambda name=name, fn=fn, calls=calls, gemm=gemm: _run_guarded(name, fn, calls, gemm))
+            for name, fn, calls, gemm in _GUARDED]
+
+
+_base10_all_checks = all_checks
+
+
+def all_checks():  # noqa: F811
+    out = _base10_all_checks()
+    out.append(('guard_selftest', guard_selftest))
+    out.extend(guarded_entries())
     return out
