@@ -9,6 +9,8 @@ Layout
     _common.py     dtype codes, stream handle, row-strided layout, cast: what ops.py and weights.py both stand on
     weights.py     the one cache of every copy derived from a parameter (operands, transposes, stem layouts)
     ops.py         tensor-level launch wrappers (shape checks, stream, dtype codes)
+    frames.py      the launch wrappers of the routines on decoded uint8 frames (crops, warps, NV12, JPEG, perturbations, the
+                   relevance paste) behind one argument front end; ops re-exports them
     functional.py  torch.autograd.Function glue (autograd plumbing only)
     network/       nn.Modules mirroring the reference's constructor/forward signatures
     parallel.py    data-parallel gradient bucket (one RCCL all-reduce per step)

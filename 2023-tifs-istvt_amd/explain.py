@@ -23,6 +23,7 @@ import contextlib
 
 import torch
 
+from . import frames as byte_frames
 from . import functional as Fn
 from . import ops
 
@@ -190,5 +191,4 @@ def overlay_frames(frames, maps, boxes=None, transforms=None, side=None, alpha=0
     n, Hs, Ws = video._whole_frames(frames, side, pixel_format, 'boxes' if boxes is not None else 'transforms')
     A, rect, table = (t.to(frames.device) for t in _paste_setup(n, Hs, Ws, int(side), boxes, transforms, lut, pixel_format,
                                                                 yuv_matrix))
-    paste = ops.relevance_paste_nv12 if pixel_format == 'nv12' else ops.relevance_paste_u8
-    return paste(frames, maps, A, rect, table, alpha, int(side), inplace=inplace, checked=True)
+    return byte_frames.paste_maps(pixel_format, frames, maps, A, rect, table, alpha, int(side), inplace=inplace, checked=True)

@@ -1,0 +1,430 @@
+"""The routines on decoded uint8 frames (clips.py holds their definitions on the host): crops, similarity warps, the NV12
+readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12.
+
+One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
+checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
+_nv12_launches (the launches of an NV12 batch with the per-frame tensors sliced alongside) and _paste_target (in place, `out`
+or a copy).  crop_frames and paste_maps pick the entry for a pixel format.  ops re-exports the public entries, and ops.prof
+records them: ops.kernel_profile stays the one switch.  Nothing here synchronises; with checked=True nothing is read back.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+
+from . import _lib, clips
+from ._common import Tensor, _c, _req, _stream
+
+
+def prof(name, nbytes):
+    """ops.prof (ops imports this module, so the name is looked up at the call)"""
+    from . import ops
+    return ops.prof(name, nbytes)
+
+
+# ---- the argument front end ------------------------------------------------------------------------------------------------
+def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: bool = False):
+    """Packed RGB frames: uint8, channels last, (n, Hs, Ws, 3) or (clips_too) (B, T, Hs, Ws, 3) on the device, not empty, at
+    most 16384 x 16384; contiguous=True refuses what would have to be copied.  -> (n frames, T or None, Hs, Ws); the kernels
+    take a pointer and n, so the flat source is _c(frames)."""
+    _req(frames, 'frames')
+    if frames.dtype != torch.uint8:
+        raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
+    if frames.dim() not in ((4, 5) if clips_too else (4,)) or frames.shape[-1] != 3:
+        hw = 'H, W' if contiguous else 'Hs, Ws'
+        raise RuntimeError('%s expects channels-last (n, %s, 3)%s uint8 input, got %s'
+                           % (what, hw, ' or (B, T, %s, 3)' % hw if clips_too else '', tuple(frames.shape)))
+    if frames.numel() == 0:
+        raise RuntimeError('%s: empty input %s' % (what, tuple(frames.shape)))
+    if contiguous and not frames.is_contiguous():
+        raise RuntimeError('%s: frames must be contiguous, got strides %s for %s'
+                           % (what, tuple(frames.stride()), tuple(frames.shape)))
+    Hs, Ws = int(frames.shape[-3]), int(frames.shape[-2])
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('%s: frames of at most 16384 x 16384, got %d x %d' % (what, Hs, Ws))
+    T = int(frames.shape[1]) if frames.dim() == 5 else None
+    return frames.numel() // (Hs * Ws * 3), T, Hs, Ws
+
+
+def _nv12_launch(t: Tensor, first: int, Hs: int, Ws: int):
+    """t uint8 [n, 3 Hs / 2, Ws] with contiguous rows -> (t, data_ptr, readable bytes, pitch, frame stride, first, n)"""
+    n, pitch, fs = int(t.shape[0]), int(t.stride(1)), int(t.stride(0)) if t.shape[0] > 1 else 0
+    return (t, t.data_ptr(), (n - 1) * fs + (Hs + Hs // 2 - 1) * pitch + Ws, pitch, fs, first, n)
+
+
+def _nv12_source(what: str, frames: Tensor, matrix: str):
+    """Arguments common to the kernels that read NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws]
+    on the device.  The row pitch and the frame stride are the tensor's strides; only a non-contiguous last dimension is
+    copied.  -> (n frames, T or None, Hs, Ws, coefficients as a C array, launches), launches = [(tensor that keeps the memory
+    alive, data_ptr, readable bytes, pitch, frame stride, first frame, frames)]: one launch, or one per clip when the clip
+    stride of a 4-D batch is not T frame strides."""
+    if torch.is_tensor(frames) and frames.dtype != torch.uint8:
+        raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
+    if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
+        raise RuntimeError('%s expects NV12 (n, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws) uint8 input, got %s'
+                           % (what, tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__))
+    if frames.numel() == 0:
+        raise RuntimeError('%s: empty input %s' % (what, tuple(frames.shape)))
+    if frames.stride(-1) != 1:
+        frames = frames.contiguous()
+    Hs, Ws = clips.check_nv12(frames)
+    if Hs > 16384 or Ws > 16384:
+        raise ValueError('%s: frames of at most 16384 x 16384, got %d x %d' % (what, Hs, Ws))
+    coef = (ctypes.c_int * 6)(*clips.nv12_coefficients(matrix))
+    _req(frames, 'frames')             # after the argument errors, which need no device
+    rows, pitch = Hs + Hs // 2, int(frames.stride(-2))
+    if pitch > (1 << 20):
+        raise ValueError('%s: a row pitch of at most 2^20 bytes, got %d' % (what, pitch))
+    n = frames.numel() // (rows * Ws)
+    if frames.dim() == 3:
+        return n, None, Hs, Ws, coef, [_nv12_launch(frames, 0, Hs, Ws)]
+    B, T = int(frames.shape[0]), int(frames.shape[1])
+    if B == 1 or T == 1 or frames.stride(0) == T * frames.stride(1):
+        flat = frames[0] if B == 1 else frames[:, 0] if T == 1 else frames.as_strided((B * T, rows, Ws), (frames.stride(1), pitch, 1))
+        return n, T, Hs, Ws, coef, [_nv12_launch(flat, 0, Hs, Ws)]
+    return n, T, Hs, Ws, coef, [_nv12_launch(frames[b], b * T, Hs, Ws) for b in range(B)]
+
+
+def _nv12_launches(launches, *per_frame):
+    """every launch of _nv12_source -> (data_ptr, readable bytes, pitch, frame stride, frames k, the k rows of each per-frame
+    tensor that belong to it)"""
+    for _, ptr, total, pitch, fs, first, k in launches:
+        yield (ptr, total, pitch, fs, k) + tuple(t[first:first + k] for t in per_frame)
+
+
+def _side(what: str, S, noun: str = 'output side') -> int:
+    S = int(S)
+    if S < 1 or S > 480:
+        raise ValueError('%s: the %s must lie in [1, 480], got %d' % (what, noun, S))
+    return S
+
+
+# the per-frame tables: (what a refusal calls it, dtype, shape of a row)
+_BOXES = ('box table', torch.int32, (4,))
+_SIMILARITIES = ('table of similarities', torch.float32, (2, 3))
+_QUALITIES = ('quality table', torch.int32, ())
+_PERTURBATIONS = ('table', torch.int32, (4,))
+_PASTE_A = ('A', torch.float64, (2, 3))
+_PASTE_RECT = ('rect', torch.int32, (4,))
+
+
+def _frame_table(what: str, kind, table, n: int, T: Optional[int], device, checked: bool, check, host_only: Optional[str] = None):
+    """The device table of a routine, one row for each of the n frames.  checked=True: the caller's device table as it is
+    (dtype, shape and device looked at, nothing read back).  Otherwise check(table, rows) validates the host table
+    (clips.check_*) of n rows or, for clips (T not None), n / T rows spread over the T frames of each clip, and the result is
+    uploaded.  host_only: the refusal of an unchecked device table, whose validation would wait for the device; such a table
+    is uploaded without blocking."""
+    noun, dtype, row = kind
+    if checked:
+        if not torch.is_tensor(table) or table.dtype != dtype or tuple(table.shape) != (n,) + row or table.device != device:
+            raise RuntimeError('%s: a checked %s is %s %s on %s' % (what, noun, str(dtype)[6:], (n,) + row, device))
+        return _c(table)
+    if host_only is not None and torch.is_tensor(table) and table.is_cuda:
+        raise RuntimeError(host_only)
+    t = check(table, n if T is None else n // T)
+    if T is not None:
+        t = t.repeat_interleave(T, dim=0)
+    return t.contiguous().to(device, non_blocking=host_only is not None)
+
+
+def _u8_out(what: str, frames: Tensor, shape, out: Optional[Tensor]) -> Tensor:
+    """the uint8 result of the byte-image routines: a new tensor of `shape` on the frames' device, or the caller's `out`"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device or not out.is_contiguous():
+        raise RuntimeError('%s: out must be contiguous uint8 %s on %s' % (what, tuple(shape), frames.device))
+    return out
+
+
+def _no_overlap(what: str, out: Tensor, ptr: int, nbytes: int, source: str) -> None:
+    """`out` may not share memory with the nbytes the kernel reads at ptr"""
+    if out.data_ptr() < ptr + nbytes and ptr < out.data_ptr() + out.numel():
+        raise RuntimeError('%s: out may not share memory with the %s' % (what, source))
+
+
+# ---- crops and warps ---------------------------------------------------------------------------------------------------------
+def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
+    """Frames and boxes (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, boxes int32 [n,4] = (y0, x0, h,
+    w) per frame or, for clips, [B,4] spread over the T frames of a clip -> uint8 [n,S,S,3] / [B,T,S,S,3]: every box cut out
+    and resized with the antialiased bilinear filter of clips.crop_resize_host.  Boxes are validated on the host
+    (clips.check_boxes) before any launch and then uploaded; checked=True takes a per-frame device table the caller has
+    validated already.  `out` (uint8, contiguous, of the result's shape) is written when given."""
+    n, T, Hs, Ws = _rgb_source('crop_resize_u8', frames)
+    S = _side('crop_resize_u8', S)
+    src = _c(frames)
+    bdev = _frame_table('crop_resize_u8', _BOXES, boxes, n, T, frames.device, checked,
+                        lambda b, rows: clips.check_boxes(b, rows, Hs, Ws, S))
+    out = _u8_out('crop_resize_u8', frames, tuple(frames.shape[:-3]) + (S, S, 3), out)
+    with prof('crop_resize_u8', n * S * S * 3):        # + the boxes' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_crop_resize_u8(src.data_ptr(), src.numel(), Hs, Ws, bdev.data_ptr(), out.data_ptr(), n, S,
+                                                   _stream()), 'istvt_crop_resize_u8')
+    return out
+
+
+def nv12_to_rgb_u8(frames: Tensor, matrix: str = 'bt709', out: Optional[Tensor] = None) -> Tensor:
+    """NV12 frames (clips.py) -> packed RGB: frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device, the row
+    pitch and the frame stride taken from the tensor's strides (a decoder surface wrapped with as_strided is read where it
+    lies) -> uint8 [n, Hs, Ws, 3] / [B, T, Hs, Ws, 3], the bits of clips.nv12_to_rgb_host.  matrix: 'bt601', 'bt709' (limited
+    range) or 'jfif' (full range).  `out` (uint8, contiguous, of the result's shape, no overlap with the frames) is written
+    when given."""
+    n, _, Hs, Ws, coef, launches = _nv12_source('nv12_to_rgb_u8', frames, matrix)
+    out = _u8_out('nv12_to_rgb_u8', frames, tuple(frames.shape[:-2]) + (Hs, Ws, 3), out)
+    for ptr, total, pitch, fs, k, rgb in _nv12_launches(launches, out.view((n, Hs, Ws, 3))):
+        _no_overlap('nv12_to_rgb_u8', out, ptr, total, 'frames')
+        with prof('nv12_to_rgb_u8', k * Hs * Ws * 9 // 2):
+            _lib.check(_lib.lib().istvt_nv12_to_rgb_u8(ptr, total, Hs, Ws, pitch, fs, coef, rgb.data_ptr(), k, _stream()),
+                       'istvt_nv12_to_rgb_u8')
+    return out
+
+
+def crop_resize_nv12(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
+                     checked: bool = False) -> Tensor:
+    """crop_resize_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device (pitch
+    and frame stride from the tensor's strides, nothing copied unless the last dimension is not contiguous), boxes, S, `out`
+    and `checked` as crop_resize_u8 takes them, the boxes in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] /
+    [B, T, S, S, 3]: the bits of crop_resize_u8(nv12_to_rgb_u8(frames, matrix), boxes, S) without the RGB frames -- the colour
+    conversion runs on the rows of the box only, inside the crop kernel."""
+    n, T, Hs, Ws, coef, launches = _nv12_source('crop_resize_nv12', frames, matrix)
+    S = _side('crop_resize_nv12', S)
+    bdev = _frame_table('crop_resize_nv12', _BOXES, boxes, n, T, frames.device, checked,
+                        lambda b, rows: clips.check_boxes(b, rows, Hs, Ws, S))
+    out = _u8_out('crop_resize_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
+    for ptr, total, pitch, fs, k, b, crops in _nv12_launches(launches, bdev, out.view((n, S, S, 3))):
+        with prof('crop_resize_nv12', k * S * S * 3):  # + the boxes' areas * 3 / 2, which live on the device
+            _lib.check(_lib.lib().istvt_crop_resize_nv12(ptr, total, Hs, Ws, pitch, fs, coef, b.data_ptr(), crops.data_ptr(), k, S,
+                                                         _stream()), 'istvt_crop_resize_nv12')
+    return out
+
+
+def warp_similarity_u8(frames: Tensor, M: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
+    """Aligned crops (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, M float32 [n,2,3] per frame or, for
+    clips, [B,2,3] spread over the T frames of a clip: the similarity that takes the centre of an output pixel to source
+    coordinates (pixel j covers [j, j + 1)) -> uint8 [n,S,S,3] / [B,T,S,S,3], every frame resampled through its map with the
+    antialiased triangle of clips.warp_similarity_host, the border replicated.  The table is validated on the host
+    (clips.check_similarities) before any launch and then uploaded; checked=True takes a per-frame device table the caller
+    has validated already (an entry the kernel itself refuses gives a frame of zeros).  `out` (uint8, contiguous, of the
+    result's shape) is written when given."""
+    n, T, Hs, Ws = _rgb_source('warp_similarity_u8', frames)
+    S = _side('warp_similarity_u8', S)
+    src = _c(frames)
+    mdev = _frame_table('warp_similarity_u8', _SIMILARITIES, M, n, T, frames.device, checked,
+                        lambda m, rows: clips.check_similarities(m, rows, Hs, Ws, S))
+    out = _u8_out('warp_similarity_u8', frames, tuple(frames.shape[:-3]) + (S, S, 3), out)
+    with prof('warp_similarity_u8', n * S * S * 3):    # + the footprints' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_warp_similarity_u8(src.data_ptr(), src.numel(), Hs, Ws, mdev.data_ptr(), out.data_ptr(), n,
+                                                       S, _stream()), 'istvt_warp_similarity_u8')
+    return out
+
+
+def warp_similarity_nv12(frames: Tensor, M: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
+                         checked: bool = False) -> Tensor:
+    """warp_similarity_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device
+    (pitch and frame stride from the tensor's strides, as crop_resize_nv12 takes them), M, S, `out` and `checked` as
+    warp_similarity_u8 takes them, the maps in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] / [B, T, S, S, 3]: the bits of
+    warp_similarity_u8(nv12_to_rgb_u8(frames, matrix), M, S) without the RGB frames -- a source pixel is converted once per
+    output tile, inside the warp kernel."""
+    n, T, Hs, Ws, coef, launches = _nv12_source('warp_similarity_nv12', frames, matrix)
+    S = _side('warp_similarity_nv12', S)
+    mdev = _frame_table('warp_similarity_nv12', _SIMILARITIES, M, n, T, frames.device, checked,
+                        lambda m, rows: clips.check_similarities(m, rows, Hs, Ws, S))
+    out = _u8_out('warp_similarity_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
+    for ptr, total, pitch, fs, k, m, crops in _nv12_launches(launches, mdev, out.view((n, S, S, 3))):
+        with prof('warp_similarity_nv12', k * S * S * 3):
+            _lib.check(_lib.lib().istvt_warp_similarity_nv12(ptr, total, Hs, Ws, pitch, fs, coef, m.data_ptr(), crops.data_ptr(),
+                                                             k, S, _stream()), 'istvt_warp_similarity_nv12')
+    return out
+
+
+def crop_frames(pixel_format: str, aligned: bool, frames: Tensor, table: Tensor, S: int, matrix: str = 'bt709',
+                out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
+    """the crop of frames in `pixel_format` ('nv12', or packed RGB): a warp through similarities when `aligned`, boxes cut
+    out and resized otherwise; `matrix` is read for NV12 frames only"""
+    if pixel_format == 'nv12':
+        return (warp_similarity_nv12 if aligned else crop_resize_nv12)(frames, table, S, matrix, out=out, checked=checked)
+    return (warp_similarity_u8 if aligned else crop_resize_u8)(frames, table, S, out=out, checked=checked)
+
+
+# ---- the relevance paste -----------------------------------------------------------------------------------------------------
+def _paste_geometry(what: str, A, rect, n: int):
+    """host A and rect as clips.paste_geometry makes them, validated: dtypes, shapes, every number of A finite, no negative
+    extent -> (A, rect) on the host"""
+    if not torch.is_tensor(A) or A.dtype != torch.float64:
+        raise TypeError('%s: A must be a float64 tensor (n, 2, 3) as clips.paste_geometry makes it' % what)
+    if not torch.is_tensor(rect) or rect.dtype != torch.int32:
+        raise TypeError('%s: rect must be an int32 tensor (n, 4) as clips.paste_geometry makes it' % what)
+    if tuple(A.shape) != (n, 2, 3) or tuple(rect.shape) != (n, 4):
+        raise ValueError('%s: A (%d, 2, 3) and rect (%d, 4) expected, got %s and %s'
+                         % (what, n, n, tuple(A.shape), tuple(rect.shape)))
+    A, rect = A.detach().cpu(), rect.detach().cpu()
+    if not bool(torch.isfinite(A).all()):
+        raise ValueError('%s: every entry of A must be finite' % what)
+    if bool((rect[:, 2:] < 0).any()):
+        raise ValueError('%s: rect = (y0, x0, h, w) with h, w >= 0' % what)
+    return A, rect
+
+
+def _paste_tables(what: str, frames: Tensor, n: int, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+                  checked: bool):
+    """the device tables of the two pastes -> (maps (n, g * g), g, A, rect, lut, alpha (n,), S).  A and rect: checked tables as
+    they are, or host tables validated (_paste_geometry) and uploaded."""
+    S = _side(what, S, 'crop side')
+    if not torch.is_tensor(maps) or maps.dtype != torch.float32 or maps.dim() not in (2, 3) or maps.shape[0] != n:
+        raise RuntimeError('%s: maps must be float32 (%d, g, g) or (%d, g * g), got %s'
+                           % (what, n, n, (maps.dtype, tuple(maps.shape)) if torch.is_tensor(maps) else type(maps).__name__))
+    g = int(maps.shape[1]) if maps.dim() == 3 else int(round(maps.shape[1] ** 0.5))
+    if not 1 <= g <= 19 or maps.numel() != n * g * g:
+        raise RuntimeError('%s: a square grid of at most 19 x 19 cells per map expected, got %s' % (what, tuple(maps.shape)))
+    if not torch.is_tensor(lut) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+        raise RuntimeError('%s: the colour table must be uint8 (256, 3)' % what)
+    if maps.device != frames.device or lut.device != frames.device:
+        raise RuntimeError('%s: frames, maps and the colour table must share one device' % what)
+    if not checked:
+        A, rect = _paste_geometry(what, A, rect, n)
+    A = _frame_table(what, _PASTE_A, A, n, None, frames.device, checked, lambda t, rows: t)
+    rect = _frame_table(what, _PASTE_RECT, rect, n, None, frames.device, checked, lambda t, rows: t)
+    if torch.is_tensor(alpha):
+        if alpha.dtype != torch.float32 or tuple(alpha.shape) != (n,):
+            raise RuntimeError('%s: alpha is a float or a float32 tensor (%d,), got %s %s'
+                               % (what, n, alpha.dtype, tuple(alpha.shape)))
+        alpha = alpha.to(frames.device, non_blocking=True)
+    else:
+        alpha = float(alpha)
+        if alpha != alpha or alpha in (float('inf'), float('-inf')):
+            raise ValueError('%s: alpha must be finite, got %r' % (what, alpha))
+        alpha = torch.full((n,), alpha, dtype=torch.float32, device=frames.device)
+    return _c(maps).view(n, g * g), g, A, rect, _c(lut), _c(alpha), S
+
+
+def _paste_target(what: str, frames: Tensor, out: Optional[Tensor], inplace: bool) -> Tensor:
+    """what a paste writes: the frames themselves (inplace), or a copy of them in `out` or in a new tensor"""
+    if inplace:
+        return frames
+    out = _u8_out(what, frames, tuple(frames.shape), out)
+    out.copy_(frames)
+    return out
+
+
+def relevance_paste_u8(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+                       out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
+    """Relevance maps pasted onto whole frames (clips.paste_maps_host is the definition): frames uint8 [n,Hs,Ws,3] on the
+    device, maps float32 [n,g,g] or [n,g*g] (g <= 19, crop coordinates), A float64 [n,2,3] and rect int32 [n,4] as
+    clips.paste_geometry makes them for crops of side S, lut uint8 [256,3], alpha a float or float32 [n] -> the frames with
+    every map coloured through the table and blended over its face.  A and rect are host tables, validated here and
+    uploaded; checked=True takes device tables as they are (the kernel clamps a rectangle into its frame and leaves a frame
+    with a non-finite A, alpha or map untouched).  inplace=True writes into `frames` (contiguous) and costs the rectangles'
+    area; otherwise the frames are copied once, into `out` when given, and the same launch runs on the copy."""
+    n, _, Hs, Ws = _rgb_source('relevance_paste_u8', frames, clips_too=False)
+    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_u8', frames, n, maps, A, rect, lut, alpha, S, checked)
+    if inplace and (out is not None or not frames.is_contiguous()):
+        raise RuntimeError('relevance_paste_u8: inplace=True writes into contiguous frames and takes no out')
+    out = _paste_target('relevance_paste_u8', frames, out, inplace)
+    with prof('relevance_paste_u8', n * g * g * 4):    # + twice the rectangles' areas * 3, which live on the device
+        _lib.check(_lib.lib().istvt_relevance_paste_u8(out.data_ptr(), out.numel(), Hs, Ws, maps.data_ptr(), g, A.data_ptr(),
+                                                       rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S, _stream()),
+                   'istvt_relevance_paste_u8')
+    return out
+
+
+def relevance_paste_nv12(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut_ycc: Tensor, alpha, S: int,
+                         out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
+    """relevance_paste_u8 on NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] on the device, the pitch and the frame
+    stride taken from the tensor's strides; lut_ycc uint8 [256,3] holds (Y, Cb, Cr) per entry (clips.lut_to_ycc of the RGB
+    table in the frames' matrix); A and rect in pixels of the Hs x Ws picture, rect from paste_geometry(even=True).  The blend
+    runs in the frame's own colour space: no pixel is converted.  inplace=True writes the surface where it lies (frames that
+    do not overlap); otherwise -> a contiguous copy with the maps pasted on."""
+    if inplace and (not torch.is_tensor(frames) or frames.dim() != 3 or frames.stride(-1) != 1):
+        raise RuntimeError('relevance_paste_nv12: inplace=True takes (n, 3 * Hs / 2, Ws) frames with contiguous rows')
+    if torch.is_tensor(frames) and frames.dim() != 3:
+        raise RuntimeError('relevance_paste_nv12 expects NV12 (n, 3 * Hs / 2, Ws) uint8 input, got %s' % (tuple(frames.shape),))
+    n, _, Hs, Ws, _, _ = _nv12_source('relevance_paste_nv12', frames, 'bt709')
+    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_nv12', frames, n, maps, A, rect, lut_ycc, alpha, S, checked)
+    if inplace and out is not None:
+        raise RuntimeError('relevance_paste_nv12: inplace=True takes no out')
+    out = _paste_target('relevance_paste_nv12', frames, out, inplace)
+    _, ptr, total, pitch, fs, _, _ = _nv12_launch(out, 0, Hs, Ws)
+    if n > 1 and fs < total - (n - 1) * fs:            # a frame's own bytes reach into the next frame
+        raise RuntimeError('relevance_paste_nv12: the frames of a batch written in place may not overlap')
+    with prof('relevance_paste_nv12', n * g * g * 4):  # + twice the rectangles' areas * 3 / 2, which live on the device
+        _lib.check(_lib.lib().istvt_relevance_paste_nv12(ptr, total, Hs, Ws, pitch, fs, maps.data_ptr(), g, A.data_ptr(),
+                                                         rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S, _stream()),
+                   'istvt_relevance_paste_nv12')
+    return out
+
+
+def paste_maps(pixel_format: str, frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
+               **kw) -> Tensor:
+    """the paste onto frames in `pixel_format` ('nv12', or packed RGB); lut in the frames' colour space"""
+    return (relevance_paste_nv12 if pixel_format == 'nv12' else relevance_paste_u8)(frames, maps, A, rect, lut, alpha, S, **kw)
+
+
+# ---- degradations ------------------------------------------------------------------------------------------------------------
+def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
+                      checked: bool = False) -> Tensor:
+    """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for
+    clips, [B] shared by the T frames of a clip (or an int for all) -> uint8 of the same shape: what a baseline JPEG encoder
+    and decoder hand back at that quality ('420' or '444' chroma), the bits of clips.jpeg_roundtrip_host.  Entries 1..100
+    compress, an entry <= 0 copies its frame.  A host table is validated (clips.check_qualities) before any launch and
+    uploaded without blocking; checked=True takes a per-frame device table the caller has validated already and reads nothing
+    back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.  `out`
+    (uint8, contiguous, of the input's shape) is written when given; it may not share memory with the input, whose
+    neighbouring blocks the chroma upsample reads."""
+    n, T, H, W = _rgb_source('jpeg_roundtrip_u8', frames, contiguous=True)
+    sub = clips._jpeg_sub(subsampling)
+    qdev = _frame_table('jpeg_roundtrip_u8', _QUALITIES, quality, n, T, frames.device, checked, clips.check_qualities,
+                        'jpeg_roundtrip_u8: a device quality table is taken with checked=True only (int32, one entry per '
+                        'frame, validated by the caller); hand over the host table otherwise')
+    out = _u8_out('jpeg_roundtrip_u8', frames, frames.shape, out)
+    nbytes = frames.numel()
+    _no_overlap('jpeg_roundtrip_u8', out, frames.data_ptr(), nbytes, 'input (the round trip is not done in place)')
+    mcu = 8 * sub
+    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
+    planes = torch.empty((n * Hp * Wp * 3 // (2 if sub == 2 else 1),), dtype=torch.uint8, device=frames.device)
+    with prof('jpeg_roundtrip_u8', 2 * nbytes + 2 * planes.numel()):
+        _lib.check(_lib.lib().istvt_jpeg_roundtrip_u8(frames.data_ptr(), nbytes, n, H, W, qdev.data_ptr(), 2 if sub == 2 else 0,
+                                                      planes.data_ptr(), planes.numel(), out.data_ptr(), _stream()),
+                   'istvt_jpeg_roundtrip_u8')
+    return out
+
+
+def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,
+               checked: bool = False) -> Tensor:
+    """Perturbations (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, table int32 [n,4] = (kind, param,
+    frame_id, stream) per frame or, for clips, [B,4] per clip (frame t of a clip takes its clip's kind, param and stream and
+    frame_id + t), taps int32 [K,21] (clips.gaussian_taps; needed where a row blurs), seed the 64-bit key of the noise -> uint8
+    of the same shape: brightness, contrast, saturation, Gaussian noise, Gaussian blur or pixelation per frame, the bits of
+    clips.perturb_host.  A host table (and host taps) is validated (clips.check_perturbations) before any launch and uploaded
+    without blocking; checked=True takes a device table, and device taps, that the caller has validated already and reads
+    nothing back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.
+    `out` (uint8, contiguous, of the input's shape) is written when given; it may not share memory with the input, whose
+    neighbours blur and pixelation read."""
+    n, T, H, W = _rgb_source('perturb_u8', frames, contiguous=True)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('perturb_u8: the seed must lie in [0, 2^64), got %d' % seed)
+    dev = frames.device
+    host_only = ('perturb_u8: a device table or device taps are taken with checked=True only (validated by the caller); hand '
+                 'over the host tensors otherwise')
+    if checked:
+        if taps is not None and (not torch.is_tensor(taps) or taps.dtype != torch.int32 or taps.dim() != 2
+                                 or taps.shape[1] != clips.PERTURB_TAPS
+                                 or not 1 <= taps.shape[0] <= clips.PERTURB_MAX_TAPS_ROWS or taps.device != dev):
+            raise RuntimeError('perturb_u8: checked taps are int32 (K, 21), K <= %d, on %s' % (clips.PERTURB_MAX_TAPS_ROWS, dev))
+    elif torch.is_tensor(taps) and taps.is_cuda:
+        raise RuntimeError(host_only)
+    # the table keeps one row per clip: the kernel spreads it, frame t of a clip takes frame_id + t
+    tdev = _frame_table('perturb_u8', _PERTURBATIONS, table, frames.shape[0], None, dev, checked,
+                        lambda t, rows: clips.check_perturbations(t, rows, taps), host_only)
+    pdev = None if taps is None else _c(taps) if checked else taps.detach().contiguous().to(dev, non_blocking=True)
+    out = _u8_out('perturb_u8', frames, frames.shape, out)
+    nbytes = frames.numel()
+    _no_overlap('perturb_u8', out, frames.data_ptr(), nbytes, 'input (blur and pixelation read their neighbours)')
+    strips = min(32, -(-(H * W) // 2048))                         # partial sums of Y per frame, for the contrast mean
+    scratch = torch.empty((n * strips,), dtype=torch.int64, device=dev)
+    with prof('perturb_u8', 2 * nbytes):
+        _lib.check(_lib.lib().istvt_perturb_u8(frames.data_ptr(), nbytes, n, H, W, tdev.data_ptr(), 0 if T is None else T,
+                                               0 if pdev is None else pdev.data_ptr(), 0 if pdev is None else pdev.shape[0], seed,
+                                               scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream()),
+                   'istvt_perturb_u8')
+    return out

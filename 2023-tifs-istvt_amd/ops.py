@@ -4,6 +4,10 @@ Every function checks shapes/dtypes in Python *before* launching (so bad geometr
 Python exception like the reference does, SURVEY.md 8(b) "Error convention"), passes raw device
 pointers + the current torch stream, and never synchronises.  Inputs must live on a ROCm
 device: there is deliberately no CPU path.
+
+Here: the GEMMs, the transformer and stem wrappers (the stem's conv1 from decoded bytes included) and the criterion.  The
+routines on whole uint8 frames (crops, warps, NV12, JPEG, perturbations, the relevance paste) live in frames.py and are
+re-exported below: their callers keep saying ``ops.crop_resize_u8`` ..., and ``kernel_profile`` here is their switch too.
 """
 from __future__ import annotations
 
@@ -16,6 +20,9 @@ from . import _lib
 # dtype codes, the stream handle, the row-strided activation layout (pad_ld / empty_rows / rows) and the cast launch
 from ._common import (G256_MIN, ROW_ALIGN, Tensor, _DT, _c, _ptr, _req, _stream, cast, dtype_code,  # noqa: F401
                       empty_rows, pad_ld, rows, zeros_rows)
+# the routines on decoded uint8 frames (frames.py looks prof up here when it launches, so it imports nothing from this module)
+from .frames import (crop_resize_nv12, crop_resize_u8, jpeg_roundtrip_u8, nv12_to_rgb_u8, perturb_u8,  # noqa: F401
+                     relevance_paste_nv12, relevance_paste_u8, warp_similarity_nv12, warp_similarity_u8)
 # Every copy derived from a parameter (the compute-dtype operand, its transpose, the stacked operand, the stem's layouts):
 # cached, refreshed and released by weights.py; the names below are the live cache's.
 from .weights import (_refresh_derived, _refresh_plain_copies, _static_holders, _transposed_operand,  # noqa: F401
@@ -1037,446 +1044,6 @@ def im2col_conv1_u8(src: Tensor, view, S: Optional[int], mean: Tensor, std: Tens
                                                     _c(std).data_ptr(), col.data_ptr(), Fr, S, _DT[dtype], _stream()),
                    'istvt_im2col_conv1_u8')
     return col
-
-
-def _u8_out(what: str, frames: Tensor, shape, out: Optional[Tensor]) -> Tensor:
-    """the uint8 result of the byte-image routines: a new tensor of `shape` on the frames' device, or the caller's `out`"""
-    if out is None:
-        return torch.empty(shape, dtype=torch.uint8, device=frames.device)
-    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or out.device != frames.device or not out.is_contiguous():
-        raise RuntimeError('%s: out must be contiguous uint8 %s on %s' % (what, tuple(shape), frames.device))
-    return out
-
-
-def _frame_boxes(what: str, frames: Tensor, boxes: Tensor, n: int, T: Optional[int], Hs: int, Ws: int, S: int,
-                 checked: bool) -> Tensor:
-    """the device box table of the two crops, one row for each of the n frames: a checked table as it is, or the host table
-    validated (clips.check_boxes), spread over the T frames of a clip (T None: frames, not clips) and uploaded"""
-    from . import clips
-    if checked:
-        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or boxes.device != frames.device:
-            raise RuntimeError('%s: a checked box table is int32 (%d, 4) on %s' % (what, n, frames.device))
-        return _c(boxes)
-    b = clips.check_boxes(boxes, frames.shape[0], Hs, Ws, S)
-    if T is not None:
-        b = clips.per_frame_boxes(b, T)
-    return b.contiguous().to(frames.device)
-
-
-def crop_resize_u8(frames: Tensor, boxes: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
-    """Frames and boxes (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, boxes int32 [n,4] = (y0, x0, h,
-    w) per frame or, for clips, [B,4] spread over the T frames of a clip -> uint8 [n,S,S,3] / [B,T,S,S,3]: every box cut out
-    and resized with the antialiased bilinear filter of clips.crop_resize_host.  Boxes are validated on the host
-    (clips.check_boxes) before any launch and then uploaded; checked=True takes a per-frame device table the caller has
-    validated already.  `out` (uint8, contiguous, of the result's shape) is written when given."""
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('crop_resize_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
-        raise RuntimeError('crop_resize_u8 expects channels-last (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3) uint8 input, got %s'
-                           % (tuple(frames.shape),))
-    if frames.numel() == 0:
-        raise RuntimeError('crop_resize_u8: empty input %s' % (tuple(frames.shape),))
-    S = int(S)
-    lead = tuple(frames.shape[:-3])
-    Hs, Ws = frames.shape[-3], frames.shape[-2]
-    if S < 1 or S > 480:
-        raise ValueError('crop_resize_u8: the output side must lie in [1, 480], got %d' % S)
-    if Hs > 16384 or Ws > 16384:
-        raise ValueError('crop_resize_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
-    src = _c(frames).view((-1, Hs, Ws, 3))
-    n = src.shape[0]
-    bdev = _frame_boxes('crop_resize_u8', frames, boxes, n, frames.shape[1] if frames.dim() == 5 else None, Hs, Ws, S, checked)
-    out = _u8_out('crop_resize_u8', frames, lead + (S, S, 3), out)
-    with prof('crop_resize_u8', n * S * S * 3):        # + the boxes' areas * 3, which live on the device
-        _lib.check(_lib.lib().istvt_crop_resize_u8(src.data_ptr(), src.numel(), Hs, Ws, bdev.data_ptr(), out.data_ptr(), n, S,
-                                                   _stream()), 'istvt_crop_resize_u8')
-    return out
-
-
-def _nv12_source(what: str, frames: Tensor, matrix: str):
-    """Arguments common to the kernels that read NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws]
-    on the device.  The row pitch and the frame stride are the tensor's strides; only a non-contiguous last dimension is
-    copied.  -> (Hs, Ws, coefficients as a C array, launches), launches = [(tensor that keeps the memory alive, data_ptr,
-    readable bytes, pitch, frame stride, first frame, frames)]: one launch, or one per clip when the clip stride of a 4-D
-    batch is not T frame strides."""
-    import ctypes
-    from . import clips
-    if torch.is_tensor(frames) and frames.dtype != torch.uint8:
-        raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
-    if not torch.is_tensor(frames) or frames.dim() not in (3, 4):
-        raise RuntimeError('%s expects NV12 (n, 3 * Hs / 2, Ws) or (B, T, 3 * Hs / 2, Ws) uint8 input, got %s'
-                           % (what, tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__))
-    if frames.numel() == 0:
-        raise RuntimeError('%s: empty input %s' % (what, tuple(frames.shape)))
-    if frames.stride(-1) != 1:
-        frames = frames.contiguous()
-    Hs, Ws = clips.check_nv12(frames)
-    if Hs > 16384 or Ws > 16384:
-        raise ValueError('%s: frames of at most 16384 x 16384, got %d x %d' % (what, Hs, Ws))
-    coef = (ctypes.c_int * 6)(*clips.nv12_coefficients(matrix))
-    _req(frames, 'frames')             # after the argument errors, which need no device
-    rows, pitch = Hs + Hs // 2, int(frames.stride(-2))
-    if pitch > (1 << 20):
-        raise ValueError('%s: a row pitch of at most 2^20 bytes, got %d' % (what, pitch))
-
-    def launch(t, first):              # t: 3-D
-        n, fs = int(t.shape[0]), int(t.stride(0)) if t.shape[0] > 1 else 0
-        return (t, t.data_ptr(), (n - 1) * fs + (rows - 1) * pitch + Ws, pitch, fs, first, n)
-
-    if frames.dim() == 3:
-        return Hs, Ws, coef, [launch(frames, 0)]
-    B, T = int(frames.shape[0]), int(frames.shape[1])
-    if B == 1 or T == 1 or frames.stride(0) == T * frames.stride(1):
-        flat = frames[0] if B == 1 else frames[:, 0] if T == 1 else frames.as_strided((B * T, rows, Ws), (frames.stride(1), pitch, 1))
-        return Hs, Ws, coef, [launch(flat, 0)]
-    return Hs, Ws, coef, [launch(frames[b], b * T) for b in range(B)]
-
-
-def nv12_to_rgb_u8(frames: Tensor, matrix: str = 'bt709', out: Optional[Tensor] = None) -> Tensor:
-    """NV12 frames (clips.py) -> packed RGB: frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device, the row
-    pitch and the frame stride taken from the tensor's strides (a decoder surface wrapped with as_strided is read where it
-    lies) -> uint8 [n, Hs, Ws, 3] / [B, T, Hs, Ws, 3], the bits of clips.nv12_to_rgb_host.  matrix: 'bt601', 'bt709' (limited
-    range) or 'jfif' (full range).  `out` (uint8, contiguous, of the result's shape, no overlap with the frames) is written
-    when given."""
-    Hs, Ws, coef, launches = _nv12_source('nv12_to_rgb_u8', frames, matrix)
-    out = _u8_out('nv12_to_rgb_u8', frames, tuple(frames.shape[:-2]) + (Hs, Ws, 3), out)
-    flat = out.view((-1, Hs, Ws, 3))
-    for t, ptr, total, pitch, fs, first, n in launches:
-        if out.data_ptr() < ptr + total and ptr < out.data_ptr() + out.numel():
-            raise RuntimeError('nv12_to_rgb_u8: out may not share memory with the frames')
-        with prof('nv12_to_rgb_u8', n * Hs * Ws * 9 // 2):
-            _lib.check(_lib.lib().istvt_nv12_to_rgb_u8(ptr, total, Hs, Ws, pitch, fs, coef, flat[first:first + n].data_ptr(), n,
-                                                       _stream()), 'istvt_nv12_to_rgb_u8')
-    return out
-
-
-def crop_resize_nv12(frames: Tensor, boxes: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
-                     checked: bool = False) -> Tensor:
-    """crop_resize_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device (pitch
-    and frame stride from the tensor's strides, nothing copied unless the last dimension is not contiguous), boxes, S, `out`
-    and `checked` as crop_resize_u8 takes them, the boxes in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] /
-    [B, T, S, S, 3]: the bits of crop_resize_u8(nv12_to_rgb_u8(frames, matrix), boxes, S) without the RGB frames -- the colour
-    conversion runs on the rows of the box only, inside the crop kernel."""
-    Hs, Ws, coef, launches = _nv12_source('crop_resize_nv12', frames, matrix)
-    S = int(S)
-    if S < 1 or S > 480:
-        raise ValueError('crop_resize_nv12: the output side must lie in [1, 480], got %d' % S)
-    n = frames.numel() // (frames.shape[-2] * frames.shape[-1])
-    bdev = _frame_boxes('crop_resize_nv12', frames, boxes, n, frames.shape[1] if frames.dim() == 4 else None, Hs, Ws, S, checked)
-    out = _u8_out('crop_resize_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
-    flat = out.view((-1, S, S, 3))
-    for t, ptr, total, pitch, fs, first, k in launches:
-        with prof('crop_resize_nv12', k * S * S * 3):  # + the boxes' areas * 3 / 2, which live on the device
-            _lib.check(_lib.lib().istvt_crop_resize_nv12(ptr, total, Hs, Ws, pitch, fs, coef, bdev[first:first + k].data_ptr(),
-                                                         flat[first:first + k].data_ptr(), k, S, _stream()),
-                       'istvt_crop_resize_nv12')
-    return out
-
-
-def _frame_similarities(what: str, frames: Tensor, M: Tensor, n: int, T: Optional[int], Hs: int, Ws: int, S: int,
-                        checked: bool) -> Tensor:
-    """the device table of the two warps, one 2 x 3 map for each of the n frames: a checked table as it is, or the host table
-    validated (clips.check_similarities), spread over the T frames of a clip (T None: frames, not clips) and uploaded"""
-    from . import clips
-    if checked:
-        if M.dtype != torch.float32 or tuple(M.shape) != (n, 2, 3) or M.device != frames.device:
-            raise RuntimeError('%s: a checked table of similarities is float32 (%d, 2, 3) on %s' % (what, n, frames.device))
-        return _c(M)
-    m = clips.check_similarities(M, frames.shape[0], Hs, Ws, S)
-    if T is not None:
-        m = clips.per_frame_similarities(m, T)
-    return m.contiguous().to(frames.device)
-
-
-def warp_similarity_u8(frames: Tensor, M: Tensor, S: int, out: Optional[Tensor] = None, checked: bool = False) -> Tensor:
-    """Aligned crops (clips.py): frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device, M float32 [n,2,3] per frame or, for
-    clips, [B,2,3] spread over the T frames of a clip: the similarity that takes the centre of an output pixel to source
-    coordinates (pixel j covers [j, j + 1)) -> uint8 [n,S,S,3] / [B,T,S,S,3], every frame resampled through its map with the
-    antialiased triangle of clips.warp_similarity_host, the border replicated.  The table is validated on the host
-    (clips.check_similarities) before any launch and then uploaded; checked=True takes a per-frame device table the caller
-    has validated already (an entry the kernel itself refuses gives a frame of zeros).  `out` (uint8, contiguous, of the
-    result's shape) is written when given."""
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('warp_similarity_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
-        raise RuntimeError('warp_similarity_u8 expects channels-last (n, Hs, Ws, 3) or (B, T, Hs, Ws, 3) uint8 input, got %s'
-                           % (tuple(frames.shape),))
-    if frames.numel() == 0:
-        raise RuntimeError('warp_similarity_u8: empty input %s' % (tuple(frames.shape),))
-    S = int(S)
-    lead = tuple(frames.shape[:-3])
-    Hs, Ws = frames.shape[-3], frames.shape[-2]
-    if S < 1 or S > 480:
-        raise ValueError('warp_similarity_u8: the output side must lie in [1, 480], got %d' % S)
-    if Hs > 16384 or Ws > 16384:
-        raise ValueError('warp_similarity_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
-    src = _c(frames).view((-1, Hs, Ws, 3))
-    n = src.shape[0]
-    mdev = _frame_similarities('warp_similarity_u8', frames, M, n, frames.shape[1] if frames.dim() == 5 else None, Hs, Ws, S,
-                               checked)
-    out = _u8_out('warp_similarity_u8', frames, lead + (S, S, 3), out)
-    with prof('warp_similarity_u8', n * S * S * 3):    # + the footprints' areas * 3, which live on the device
-        _lib.check(_lib.lib().istvt_warp_similarity_u8(src.data_ptr(), src.numel(), Hs, Ws, mdev.data_ptr(), out.data_ptr(), n,
-                                                       S, _stream()), 'istvt_warp_similarity_u8')
-    return out
-
-
-def warp_similarity_nv12(frames: Tensor, M: Tensor, S: int, matrix: str = 'bt709', out: Optional[Tensor] = None,
-                         checked: bool = False) -> Tensor:
-    """warp_similarity_u8 from NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] or [B, T, 3 Hs / 2, Ws] on the device
-    (pitch and frame stride from the tensor's strides, as crop_resize_nv12 takes them), M, S, `out` and `checked` as
-    warp_similarity_u8 takes them, the maps in pixels of the Hs x Ws picture -> uint8 [n, S, S, 3] / [B, T, S, S, 3]: the bits of
-    warp_similarity_u8(nv12_to_rgb_u8(frames, matrix), M, S) without the RGB frames -- a source pixel is converted once per
-    output tile, inside the warp kernel."""
-    Hs, Ws, coef, launches = _nv12_source('warp_similarity_nv12', frames, matrix)
-    S = int(S)
-    if S < 1 or S > 480:
-        raise ValueError('warp_similarity_nv12: the output side must lie in [1, 480], got %d' % S)
-    n = frames.numel() // (frames.shape[-2] * frames.shape[-1])
-    mdev = _frame_similarities('warp_similarity_nv12', frames, M, n, frames.shape[1] if frames.dim() == 4 else None, Hs, Ws, S,
-                               checked)
-    out = _u8_out('warp_similarity_nv12', frames, tuple(frames.shape[:-2]) + (S, S, 3), out)
-    flat = out.view((-1, S, S, 3))
-    for t, ptr, total, pitch, fs, first, k in launches:
-        with prof('warp_similarity_nv12', k * S * S * 3):
-            _lib.check(_lib.lib().istvt_warp_similarity_nv12(ptr, total, Hs, Ws, pitch, fs, coef,
-                                                             mdev[first:first + k].data_ptr(), flat[first:first + k].data_ptr(), k,
-                                                             S, _stream()), 'istvt_warp_similarity_nv12')
-    return out
-
-
-def _paste_tables(what: str, frames: Tensor, n: int, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
-                  checked: bool):
-    """the device tables of the two pastes -> (maps (n, g * g), g, A, rect, lut, alpha (n,), S).  A and rect: checked tables as
-    they are, or host tables validated (shapes, dtypes, every number of A finite, no negative extent) and uploaded."""
-    S = int(S)
-    if S < 1 or S > 480:
-        raise ValueError('%s: the crop side must lie in [1, 480], got %d' % (what, S))
-    if not torch.is_tensor(maps) or maps.dtype != torch.float32 or maps.dim() not in (2, 3) or maps.shape[0] != n:
-        raise RuntimeError('%s: maps must be float32 (%d, g, g) or (%d, g * g), got %s'
-                           % (what, n, n, (maps.dtype, tuple(maps.shape)) if torch.is_tensor(maps) else type(maps).__name__))
-    g = int(maps.shape[1]) if maps.dim() == 3 else int(round(maps.shape[1] ** 0.5))
-    if not 1 <= g <= 19 or maps.numel() != n * g * g:
-        raise RuntimeError('%s: a square grid of at most 19 x 19 cells per map expected, got %s' % (what, tuple(maps.shape)))
-    if not torch.is_tensor(lut) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
-        raise RuntimeError('%s: the colour table must be uint8 (256, 3)' % what)
-    if maps.device != frames.device or lut.device != frames.device:
-        raise RuntimeError('%s: frames, maps and the colour table must share one device' % what)
-    if checked:
-        if A.dtype != torch.float64 or tuple(A.shape) != (n, 2, 3) or A.device != frames.device:
-            raise RuntimeError('%s: a checked A is float64 (%d, 2, 3) on %s' % (what, n, frames.device))
-        if rect.dtype != torch.int32 or tuple(rect.shape) != (n, 4) or rect.device != frames.device:
-            raise RuntimeError('%s: a checked rect is int32 (%d, 4) on %s' % (what, n, frames.device))
-    else:
-        if not torch.is_tensor(A) or A.dtype != torch.float64:
-            raise TypeError('%s: A must be a float64 tensor (n, 2, 3) as clips.paste_geometry makes it' % what)
-        if not torch.is_tensor(rect) or rect.dtype != torch.int32:
-            raise TypeError('%s: rect must be an int32 tensor (n, 4) as clips.paste_geometry makes it' % what)
-        if tuple(A.shape) != (n, 2, 3) or tuple(rect.shape) != (n, 4):
-            raise ValueError('%s: A (%d, 2, 3) and rect (%d, 4) expected, got %s and %s'
-                             % (what, n, n, tuple(A.shape), tuple(rect.shape)))
-        A, rect = A.detach().cpu(), rect.detach().cpu()
-        if not bool(torch.isfinite(A).all()):
-            raise ValueError('%s: every entry of A must be finite' % what)
-        if bool((rect[:, 2:] < 0).any()):
-            raise ValueError('%s: rect = (y0, x0, h, w) with h, w >= 0' % what)
-        A, rect = A.contiguous().to(frames.device), rect.contiguous().to(frames.device)
-    if torch.is_tensor(alpha):
-        if alpha.dtype != torch.float32 or tuple(alpha.shape) != (n,):
-            raise RuntimeError('%s: alpha is a float or a float32 tensor (%d,), got %s %s'
-                               % (what, n, alpha.dtype, tuple(alpha.shape)))
-        alpha = alpha.to(frames.device, non_blocking=True)
-    else:
-        alpha = float(alpha)
-        if alpha != alpha or alpha in (float('inf'), float('-inf')):
-            raise ValueError('%s: alpha must be finite, got %r' % (what, alpha))
-        alpha = torch.full((n,), alpha, dtype=torch.float32, device=frames.device)
-    return _c(maps).view(n, g * g), g, _c(A), _c(rect), _c(lut), _c(alpha), S
-
-
-def relevance_paste_u8(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: Tensor, alpha, S: int,
-                       out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
-    """Relevance maps pasted onto whole frames (clips.paste_maps_host is the definition): frames uint8 [n,Hs,Ws,3] on the
-    device, maps float32 [n,g,g] or [n,g*g] (g <= 19, crop coordinates), A float64 [n,2,3] and rect int32 [n,4] as
-    clips.paste_geometry makes them for crops of side S, lut uint8 [256,3], alpha a float or float32 [n] -> the frames with
-    every map coloured through the table and blended over its face.  A and rect are host tables, validated here and
-    uploaded; checked=True takes device tables as they are (the kernel clamps a rectangle into its frame and leaves a frame
-    with a non-finite A, alpha or map untouched).  inplace=True writes into `frames` (contiguous) and costs the rectangles'
-    area; otherwise the frames are copied once, into `out` when given, and the same launch runs on the copy."""
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('relevance_paste_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() != 4 or frames.shape[-1] != 3:
-        raise RuntimeError('relevance_paste_u8 expects channels-last (n, Hs, Ws, 3) uint8 input, got %s' % (tuple(frames.shape),))
-    if frames.numel() == 0:
-        raise RuntimeError('relevance_paste_u8: empty input %s' % (tuple(frames.shape),))
-    n, Hs, Ws = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    if Hs > 16384 or Ws > 16384:
-        raise ValueError('relevance_paste_u8: frames of at most 16384 x 16384, got %d x %d' % (Hs, Ws))
-    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_u8', frames, n, maps, A, rect, lut, alpha, S, checked)
-    if inplace:
-        if out is not None or not frames.is_contiguous():
-            raise RuntimeError('relevance_paste_u8: inplace=True writes into contiguous frames and takes no out')
-        out = frames
-    else:
-        out = _u8_out('relevance_paste_u8', frames, tuple(frames.shape), out)
-        out.copy_(frames)
-    with prof('relevance_paste_u8', n * g * g * 4):    # + twice the rectangles' areas * 3, which live on the device
-        _lib.check(_lib.lib().istvt_relevance_paste_u8(out.data_ptr(), out.numel(), Hs, Ws, maps.data_ptr(), g, A.data_ptr(),
-                                                       rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S, _stream()),
-                   'istvt_relevance_paste_u8')
-    return out
-
-
-def relevance_paste_nv12(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut_ycc: Tensor, alpha, S: int,
-                         out: Optional[Tensor] = None, inplace: bool = False, checked: bool = False) -> Tensor:
-    """relevance_paste_u8 on NV12 frames (clips.py): frames uint8 [n, 3 Hs / 2, Ws] on the device, the pitch and the frame
-    stride taken from the tensor's strides; lut_ycc uint8 [256,3] holds (Y, Cb, Cr) per entry (clips.lut_to_ycc of the RGB
-    table in the frames' matrix); A and rect in pixels of the Hs x Ws picture, rect from paste_geometry(even=True).  The blend
-    runs in the frame's own colour space: no pixel is converted.  inplace=True writes the surface where it lies (frames that
-    do not overlap); otherwise -> a contiguous copy with the maps pasted on."""
-    if inplace and (not torch.is_tensor(frames) or frames.dim() != 3 or frames.stride(-1) != 1):
-        raise RuntimeError('relevance_paste_nv12: inplace=True takes (n, 3 * Hs / 2, Ws) frames with contiguous rows')
-    if torch.is_tensor(frames) and frames.dim() != 3:
-        raise RuntimeError('relevance_paste_nv12 expects NV12 (n, 3 * Hs / 2, Ws) uint8 input, got %s' % (tuple(frames.shape),))
-    Hs, Ws, _, _ = _nv12_source('relevance_paste_nv12', frames, 'bt709')
-    n = int(frames.shape[0])
-    maps, g, A, rect, lut, alpha, S = _paste_tables('relevance_paste_nv12', frames, n, maps, A, rect, lut_ycc, alpha, S, checked)
-    if inplace:
-        if out is not None:
-            raise RuntimeError('relevance_paste_nv12: inplace=True takes no out')
-        out = frames
-    else:
-        out = _u8_out('relevance_paste_nv12', frames, tuple(frames.shape), out)
-        out.copy_(frames)
-    pitch, fs = int(out.stride(1)), int(out.stride(0)) if n > 1 else 0
-    rows = Hs + Hs // 2
-    total = (n - 1) * fs + (rows - 1) * pitch + Ws
-    if n > 1 and fs < (rows - 1) * pitch + Ws:
-        raise RuntimeError('relevance_paste_nv12: the frames of a batch written in place may not overlap')
-    with prof('relevance_paste_nv12', n * g * g * 4):  # + twice the rectangles' areas * 3 / 2, which live on the device
-        _lib.check(_lib.lib().istvt_relevance_paste_nv12(out.data_ptr(), total, Hs, Ws, pitch, fs, maps.data_ptr(), g,
-                                                         A.data_ptr(), rect.data_ptr(), lut.data_ptr(), alpha.data_ptr(), n, S,
-                                                         _stream()), 'istvt_relevance_paste_nv12')
-    return out
-
-
-def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Optional[Tensor] = None,
-                      checked: bool = False) -> Tensor:
-    """JPEG round trip (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, quality int32 [n] per frame or, for
-    clips, [B] shared by the T frames of a clip (or an int for all) -> uint8 of the same shape: what a baseline JPEG encoder
-    and decoder hand back at that quality ('420' or '444' chroma), the bits of clips.jpeg_roundtrip_host.  Entries 1..100
-    compress, an entry <= 0 copies its frame.  A host table is validated (clips.check_qualities) before any launch and
-    uploaded without blocking; checked=True takes a per-frame device table the caller has validated already and reads nothing
-    back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.  `out` (uint8, contiguous, of the input's shape) is written when given; it may not share memory
-    with the input, whose neighbouring blocks the chroma upsample reads."""
-    from . import clips
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('jpeg_roundtrip_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
-        raise RuntimeError('jpeg_roundtrip_u8 expects channels-last (n, H, W, 3) or (B, T, H, W, 3) uint8 input, got %s'
-                           % (tuple(frames.shape),))
-    if frames.numel() == 0:
-        raise RuntimeError('jpeg_roundtrip_u8: empty input %s' % (tuple(frames.shape),))
-    if not frames.is_contiguous():
-        raise RuntimeError('jpeg_roundtrip_u8: frames must be contiguous, got strides %s for %s'
-                           % (tuple(frames.stride()), tuple(frames.shape)))
-    sub = clips._jpeg_sub(subsampling)
-    H, W = frames.shape[-3], frames.shape[-2]
-    if H > 16384 or W > 16384:
-        raise ValueError('jpeg_roundtrip_u8: frames of at most 16384 x 16384, got %d x %d' % (H, W))
-    src = frames.view((-1, H, W, 3))
-    n = src.shape[0]
-    if checked:
-        if (not torch.is_tensor(quality) or quality.dtype != torch.int32 or tuple(quality.shape) != (n,)
-                or quality.device != src.device):
-            raise RuntimeError('jpeg_roundtrip_u8: a checked quality table is int32 (%d,) on %s' % (n, src.device))
-        qdev = _c(quality)
-    else:
-        if torch.is_tensor(quality) and quality.is_cuda:
-            raise RuntimeError('jpeg_roundtrip_u8: a device quality table is taken with checked=True only (int32, one entry per '
-                               'frame, validated by the caller); hand over the host table otherwise')
-        q = clips.check_qualities(quality, frames.shape[0])
-        if frames.dim() == 5:
-            q = q.repeat_interleave(frames.shape[1])
-        qdev = q.contiguous().to(src.device, non_blocking=True)
-    out = _u8_out('jpeg_roundtrip_u8', frames, frames.shape, out)
-    nbytes = src.numel()
-    if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
-        raise RuntimeError('jpeg_roundtrip_u8: out may not share memory with the input (the round trip is not done in place)')
-    mcu = 8 * sub
-    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
-    planes = torch.empty((n * Hp * Wp * 3 // (2 if sub == 2 else 1),), dtype=torch.uint8, device=src.device)
-    with prof('jpeg_roundtrip_u8', 2 * nbytes + 2 * planes.numel()):
-        _lib.check(_lib.lib().istvt_jpeg_roundtrip_u8(src.data_ptr(), nbytes, n, H, W, qdev.data_ptr(), 2 if sub == 2 else 0,
-                                                      planes.data_ptr(), planes.numel(), out.data_ptr(), _stream()),
-                   'istvt_jpeg_roundtrip_u8')
-    return out
-
-
-def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,
-               checked: bool = False) -> Tensor:
-    """Perturbations (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3] on the device, table int32 [n,4] = (kind, param,
-    frame_id, stream) per frame or, for clips, [B,4] per clip (frame t of a clip takes its clip's kind, param and stream and
-    frame_id + t), taps int32 [K,21] (clips.gaussian_taps; needed where a row blurs), seed the 64-bit key of the noise -> uint8
-    of the same shape: brightness, contrast, saturation, Gaussian noise, Gaussian blur or pixelation per frame, the bits of
-    clips.perturb_host.  A host table (and host taps) is validated (clips.check_perturbations) before any launch and uploaded
-    without blocking; checked=True takes a device table, and device taps, that the caller has validated already and reads
-    nothing back.  A device table without checked=True is refused: validating it would copy it back and wait for the device.
-    `out` (uint8, contiguous, of the input's shape) is written when given; it may not share memory with the input, whose
-    neighbours blur and pixelation read."""
-    from . import clips
-    _req(frames, 'frames')
-    if frames.dtype != torch.uint8:
-        raise TypeError('perturb_u8: frames must be uint8, got %s' % frames.dtype)
-    if frames.dim() not in (4, 5) or frames.shape[-1] != 3:
-        raise RuntimeError('perturb_u8 expects channels-last (n, H, W, 3) or (B, T, H, W, 3) uint8 input, got %s'
-                           % (tuple(frames.shape),))
-    if frames.numel() == 0:
-        raise RuntimeError('perturb_u8: empty input %s' % (tuple(frames.shape),))
-    if not frames.is_contiguous():
-        raise RuntimeError('perturb_u8: frames must be contiguous, got strides %s for %s'
-                           % (tuple(frames.stride()), tuple(frames.shape)))
-    seed = int(seed)
-    if not 0 <= seed < 2 ** 64:
-        raise ValueError('perturb_u8: the seed must lie in [0, 2^64), got %d' % seed)
-    H, W = frames.shape[-3], frames.shape[-2]
-    if H > 16384 or W > 16384:
-        raise ValueError('perturb_u8: frames of at most 16384 x 16384, got %d x %d' % (H, W))
-    src = frames.view((-1, H, W, 3))
-    n, rows = src.shape[0], frames.shape[0]
-    if checked:
-        if (not torch.is_tensor(table) or table.dtype != torch.int32 or tuple(table.shape) != (rows, 4)
-                or table.device != src.device):
-            raise RuntimeError('perturb_u8: a checked table is int32 (%d, 4) on %s' % (rows, src.device))
-        if taps is not None and (not torch.is_tensor(taps) or taps.dtype != torch.int32 or taps.dim() != 2
-                                 or taps.shape[1] != clips.PERTURB_TAPS
-                                 or not 1 <= taps.shape[0] <= clips.PERTURB_MAX_TAPS_ROWS or taps.device != src.device):
-            raise RuntimeError('perturb_u8: checked taps are int32 (K, 21), K <= %d, on %s'
-                               % (clips.PERTURB_MAX_TAPS_ROWS, src.device))
-        tdev, pdev = _c(table), None if taps is None else _c(taps)
-    else:
-        if (torch.is_tensor(table) and table.is_cuda) or (torch.is_tensor(taps) and taps.is_cuda):
-            raise RuntimeError('perturb_u8: a device table or device taps are taken with checked=True only (validated by the '
-                               'caller); hand over the host tensors otherwise')
-        tdev = clips.check_perturbations(table, rows, taps).contiguous().to(src.device, non_blocking=True)
-        pdev = None if taps is None else taps.detach().contiguous().to(src.device, non_blocking=True)
-    out = _u8_out('perturb_u8', frames, frames.shape, out)
-    nbytes = src.numel()
-    if out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes:
-        raise RuntimeError('perturb_u8: out may not share memory with the input (blur and pixelation read their neighbours)')
-    strips = min(32, -(-(H * W) // 2048))                         # partial sums of Y per frame, for the contrast mean
-    scratch = torch.empty((n * strips,), dtype=torch.int64, device=src.device)
-    with prof('perturb_u8', 2 * nbytes):
-        _lib.check(_lib.lib().istvt_perturb_u8(src.data_ptr(), nbytes, n, H, W, tdev.data_ptr(),
-                                               frames.shape[1] if frames.dim() == 5 else 0,
-                                               0 if pdev is None else pdev.data_ptr(), 0 if pdev is None else pdev.shape[0], seed,
-                                               scratch.data_ptr(), scratch.numel() * 8, out.data_ptr(), _stream()),
-                   'istvt_perturb_u8')
-    return out
 
 
 def tokens_bwd(dx: Tensor, B: int, T: int, hw: int, D: int, dspace: Tensor, dtemporal: Tensor, dpos: Tensor,

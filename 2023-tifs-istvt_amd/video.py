@@ -34,6 +34,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
+from . import frames as byte_frames      # (`frames` is every method's argument here)
 from . import ops
 
 Tensor = torch.Tensor
@@ -626,15 +627,9 @@ class VideoScorer:
                 x = x.contiguous().pin_memory()
             if bdev is None:
                 out.copy_(x, non_blocking=True)
-            elif aligned and self.pixel_format == 'nv12':
-                ops.warp_similarity_nv12(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, self.yuv_matrix, out=out,
-                                         checked=True)
-            elif aligned:
-                ops.warp_similarity_u8(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, out=out, checked=True)
-            elif self.pixel_format == 'nv12':
-                ops.crop_resize_nv12(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, self.yuv_matrix, out=out, checked=True)
             else:
-                ops.crop_resize_u8(x.to(dev, non_blocking=True), bdev[v][lo:hi], side, out=out, checked=True)
+                byte_frames.crop_frames(self.pixel_format, aligned, x.to(dev, non_blocking=True), bdev[v][lo:hi], side,
+                                        self.yuv_matrix, out=out, checked=True)
             at += hi - lo
         return batch
 
@@ -825,7 +820,6 @@ class VideoScorer:
         else:
             al = torch.full((n,), alpha, dtype=torch.float32, device=dev)
         maps = maps.to(dev)
-        paste = ops.relevance_paste_nv12 if nv else ops.relevance_paste_u8
         out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=dev)
         for lo in range(0, n, self.frame_batch):
             hi = min(lo + self.frame_batch, n)
@@ -833,7 +827,8 @@ class VideoScorer:
             if not x.is_cuda:              # host frames: pinned, then copied on the current stream
                 x = x.contiguous().pin_memory()
             out[lo:hi].copy_(x, non_blocking=True)
-            paste(out[lo:hi], maps[lo:hi], A[lo:hi], rect[lo:hi], table, al[lo:hi], int(side), inplace=True, checked=True)
+            byte_frames.paste_maps(self.pixel_format, out[lo:hi], maps[lo:hi], A[lo:hi], rect[lo:hi], table, al[lo:hi],
+                                   int(side), inplace=True, checked=True)
         torch.cuda.current_stream(dev).synchronize()
         return out
 

@@ -50,8 +50,8 @@ RECTANGLE_WAIVERS = {
                                       'input has fewer chunks than the library has slabs (declared outputs of that check are '
                                       'held to rule 3 all the same)',
     'ops.py:_conv1_wgrad_ws': 'the same conv1 slab workspace, allocated by the wrapper',
-    'ops.py:_u8_out': 'byte images: every value is legitimate, so a pixel equal to the uint8 sentinel reads as unwritten',
-    'ops.py:relevance_overlay_u8': 'byte image (see ops.py:_u8_out)',
+    'frames.py:_u8_out': 'byte images: every value is legitimate, so a pixel equal to the uint8 sentinel reads as unwritten',
+    'ops.py:relevance_overlay_u8': 'byte image (see frames.py:_u8_out)',
 }
 # (No kernel writes pad columns on purpose, so there is no table of pad-write waivers: the invariant in _common.py holds.)
 # INPLACE_WAIVERS: placed inputs that a kernel overwrites as documented behaviour: place(t, inplace=<key>); the guards
