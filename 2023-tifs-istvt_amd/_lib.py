@@ -13,6 +13,14 @@ LIB_PATH = os.environ.get('ISTVT_LIB') or os.path.join(_HERE, 'libistvt_hip.so')
 
 P, I, L, F = c_void_p, c_int, c_long, c_float
 
+
+class JpegDecodeArgs(ctypes.Structure):
+    """istvt_jpeg_decode_args of include/istvt_hip.h"""
+    _fields_ = [('bytes', P), ('nbytes', L), ('images', P), ('images_host', P), ('segments', P), ('segments_host', P),
+                ('qtabs', P), ('htabs', P), ('scratch', P), ('scratch_bytes', L), ('out', P), ('sizes', P), ('status', P),
+                ('stream', P), ('n', I), ('nseg', I), ('nq', I), ('nh', I), ('Hc', I), ('Wc', I)]
+
+
 # name -> argtypes (all return int).  Mirrors include/istvt_hip.h one to one.
 SIGNATURES = {
     'istvt_gemm': [P, L, I, P, L, I, P, L, I, I, I, P, P, L, P, I, I, I, F, P, P, I, I, P],
@@ -67,6 +75,7 @@ SIGNATURES = {
     'istvt_relevance_paste_u8': [P, L, I, I, P, I, P, P, P, P, I, I, P],
     'istvt_relevance_paste_nv12': [P, L, I, I, L, L, P, I, P, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
+    'istvt_jpeg_decode_u8': [ctypes.POINTER(JpegDecodeArgs)],
     'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],

@@ -35,9 +35,16 @@ brightness, contrast, saturation, Gaussian noise from Philox4x32-10, Gaussian bl
 Pasting maps onto frames (DESIGN.md "Pasting maps onto frames") is the seventh: ``paste_geometry`` (a box or a similarity as
 the map from frame pixels to crop coordinates, and the rectangle to look at), ``paste_maps_host`` (the definition of
 ops.relevance_paste_u8 / ops.relevance_paste_nv12: float64 field, int32 blend), ``paste_field_host`` and ``lut_to_ycc``.
+
+JPEG files (DESIGN.md "JPEG files") are the eighth, next to the round trip whose inverse half they share: ``jpeg_parse`` (the
+markers of a baseline file, and every refusal), ``jpeg_decode_host`` (the definition of ops.jpeg_decode_u8, integers only),
+``jpeg_encode_host`` (files for tests and benchmarks), ``jpeg_batch`` (files packed for one launch), ``whole_boxes`` and
+``check_jpeg_status``.  A loader that yields file bytes runs ``model(ops.decode_frames(files, S, boxes).view(B, T, S, S, 3),
+view=flips)``: the compressed bytes are what crosses the host boundary.
 """
 import math
 from fractions import Fraction
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -366,16 +373,28 @@ def _jpeg_plane(p: Tensor, qt: Tensor) -> Tensor:
     """One component through its 8 x 8 blocks: p int32 (n, Hp, Wp) samples 0..255 with Hp, Wp multiples of 8, qt int32
     (n, 8, 8) -> the reconstructed samples, int32 0..255.  Level shift, rows then columns forward, quantise (half away from
     zero) and multiply back, columns then rows inverse, + 128, clamp."""
+    return _jpeg_samples(_jpeg_quantise(p, qt) * qt[:, None, :, None, :])
+
+
+def _jpeg_quantise(p: Tensor, qt: Tensor) -> Tensor:
+    """the forward half of _jpeg_plane: p int32 (n, Hp, Wp), qt int32 (n, 8, 8) -> the quantised coefficients a file stores,
+    int32 (n, Hp / 8, 8, Wp / 8, 8) = (frame, block row, v, block column, u)"""
     n, Hp, Wp = p.shape
-    b = (p - 128).reshape(n, Hp // 8, 8, Wp // 8, 8)                           # (frame, block row, v, block column, u)
+    b = (p - 128).reshape(n, Hp // 8, 8, Wp // 8, 8)
     b = torch.stack(_fdct8(b.unbind(4), True), dim=4)
     b = torch.stack(_fdct8(b.unbind(2), False), dim=2)                        # 8 x the coefficients
     q = qt[:, None, :, None, :]
     k = (b.abs() + q * 4) // (q * 8)                                          # (|c| + q / 2) / q in the units of the table
-    b = torch.where(b < 0, -k, k) * q
+    return torch.where(b < 0, -k, k)
+
+
+def _jpeg_samples(b: Tensor) -> Tensor:
+    """the inverse half: dequantised coefficients int32 (n, bh, 8, bw, 8) -> samples int32 0..255 (n, 8 bh, 8 bw): columns
+    then rows inverse, + 128, clamp"""
+    n, bh, _, bw, _ = b.shape
     b = torch.stack(_idct8(b.unbind(2), True), dim=2)
     b = torch.stack(_idct8(b.unbind(4), False), dim=4)
-    return (b + 128).clamp_(0, 255).reshape(n, Hp, Wp)
+    return (b + 128).clamp_(0, 255).reshape(n, bh * 8, bw * 8)
 
 
 def _jpeg_upsample(c: Tensor, H: int, W: int) -> Tensor:
@@ -388,6 +407,25 @@ def _jpeg_upsample(c: Tensor, H: int, W: int) -> Tensor:
     col = 3 * c[:, near] + c[:, far]
     this, other = x >> 1, ((x >> 1) + (x & 1) * 2 - 1).clamp_(0, Wc - 1)
     return (3 * col[:, :, this] + col[:, :, other] + (8 - (x & 1)).to(torch.int32)) >> 4
+
+
+def _jpeg_planes_in(src: Tensor, sub: int):
+    """colour in, padding and downsample of jpeg_roundtrip_host: src uint8 (n, H, W, 3) on the host -> Y int32 (n, Hp, Wp)
+    and Cb, Cr int32 (n, Hp / sub, Wp / sub), whole MCUs"""
+    H, W = src.shape[1], src.shape[2]
+    mcu = 8 * sub
+    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
+    rgb = src[:, torch.arange(Hp).clamp_(max=H - 1)][:, :, torch.arange(Wp).clamp_(max=W - 1)].to(torch.int32)
+    R, G, B = rgb.unbind(3)
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    if sub == 2:
+        bias = torch.tensor([1, 2], dtype=torch.int32).repeat(Wp // 4)
+        Cb, Cr = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + bias) >> 2 for c in (Cb, Cr))
+        rows = torch.arange(Hp // 2).clamp_(max=(H + 1) // 2 - 1)              # below the frame: the last chroma row again
+        Cb, Cr = Cb[:, rows], Cr[:, rows]
+    return Y, Cb, Cr
 
 
 def jpeg_roundtrip_host(u8: Tensor, quality, subsampling: str = '420') -> Tensor:
@@ -418,19 +456,8 @@ def jpeg_roundtrip_host(u8: Tensor, quality, subsampling: str = '420') -> Tensor
         q = q.repeat_interleave(u8.shape[1])
     H, W = u8.shape[-3], u8.shape[-2]
     src = u8.reshape((-1, H, W, 3)).cpu()
-    mcu = 8 * sub
-    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
-    rgb = src[:, torch.arange(Hp).clamp_(max=H - 1)][:, :, torch.arange(Wp).clamp_(max=W - 1)].to(torch.int32)
-    R, G, B = rgb.unbind(3)
-    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
-    Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
-    Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    Y, Cb, Cr = _jpeg_planes_in(src, sub)
     tables = torch.stack([jpeg_quant_tables(min(max(int(v), 1), 100)) for v in q])       # (n, 2, 8, 8); unused where q <= 0
-    if sub == 2:
-        bias = torch.tensor([1, 2], dtype=torch.int32).repeat(Wp // 4)
-        Cb, Cr = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + bias) >> 2 for c in (Cb, Cr))
-        rows = torch.arange(Hp // 2).clamp_(max=(H + 1) // 2 - 1)              # below the frame: the last chroma row again
-        Cb, Cr = Cb[:, rows], Cr[:, rows]
     Y = _jpeg_plane(Y, tables[:, 0])[:, :H, :W]
     Cb, Cr = _jpeg_plane(Cb, tables[:, 1]), _jpeg_plane(Cr, tables[:, 1])
     if sub == 2:
@@ -457,6 +484,531 @@ def random_qualities(n: int, p: float = 0.5, lo: int = 30, hi: int = 95, generat
     on = torch.rand((n,), generator=generator) < p
     q = torch.randint(lo, hi + 1, (n,), generator=generator)
     return torch.where(on, q, torch.zeros_like(q)).to(torch.int32).contiguous()
+
+
+# ------------------------------------------------------------------------------------------ JPEG files
+# DESIGN.md "JPEG files": baseline JPEG files decoded on the device.  jpeg_parse reads a file's markers, jpeg_decode_host is
+# the definition of ops.jpeg_decode_u8 (canonical Huffman decoding in front of the inverse half of the round trip above),
+# jpeg_encode_host writes files for tests and benchmarks, jpeg_batch packs files for one launch.
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+               35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
+               62, 63)                                  # natural index of the k-th coefficient of a block (T.81 figure A.6)
+JPEG_MAX_SIDE = 16384
+JPEG_HUFF_INTS = 288                        # a decode table: limit[16], offset[16], values[256] (csrc/jpeg_entropy.h)
+JPEG_IMAGE_INTS = 20                        # a row of the per-image table
+JPEG_IDCT_BLOCKS = 24                       # blocks per workgroup of the IDCT kernel (JP_BLOCKS of csrc/jpeg.hip)
+
+
+def _std_ac(head, runs):
+    """the tail of an Annex K.3 AC value list: after `head`, run r carries sizes lo..10"""
+    return tuple(head) + tuple((r << 4) | s for r, lo in runs for s in range(lo, 11))
+
+
+# ITU-T T.81 Annex K.3: (number of codes of length 1..16, values in code order) of the four typical Huffman tables
+JPEG_STD_HUFFMAN = {
+    (0, 0): ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    (0, 1): ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    (1, 0): ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d), _std_ac(
+        (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32,
+         0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a),
+        ((1, 6), (2, 5), (3, 4), (4, 3), (5, 3), (6, 3), (7, 3), (8, 3), (9, 2), (10, 2), (11, 2), (12, 2), (13, 2), (14, 1),
+         (15, 1)))),
+    (1, 1): ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), _std_ac(
+        (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81,
+         0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34,
+         0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a),
+        ((2, 6), (3, 5), (4, 3), (5, 3), (6, 3), (7, 3), (8, 2), (9, 2), (10, 2), (11, 2), (12, 2), (13, 2), (14, 2), (15, 2)))),
+}
+
+
+class JpegHeader:
+    """What jpeg_parse reads from one baseline file.  H, W; sub: the chroma step (2 at 4:2:0, 1 at 4:4:4); mcus = (rows,
+    columns) of MCUs; quant: per component, the 64 entries of its table in natural order; huffman: per component, ((counts,
+    values) of its DC table, (counts, values) of its AC table); restart_interval (0: none); segments: [(begin, end)] byte
+    ranges of `data` between the restart markers, one per restart interval; eoi: whether the scan ended with EOI."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _jpeg_refuse(text: str):
+    raise ValueError('jpeg_parse: ' + text)
+
+
+def jpeg_parse(data) -> JpegHeader:
+    """The markers of one baseline JPEG file (bytes): SOI, APPn / COM (skipped), DQT, SOF0, DHT, DRI, SOS, and RSTn / EOI
+    inside the scan.  Accepted: 8-bit precision, three components sampled 2x2 / 1x1 / 1x1 or 1x1 / 1x1 / 1x1, one interleaved
+    scan, 8-bit quantisation tables.  Everything else is refused by name (ValueError, 'jpeg_parse: ...').  A scan that ends
+    without EOI runs to the end of the data; restart intervals it no longer holds become empty segments, and decoding
+    reports status 1."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        _jpeg_refuse('the file does not start with SOI (FF D8)')
+    pos = 2
+    quant, huff = {}, {}
+    frame = None
+    ri = 0
+    while True:
+        if pos + 4 > n:
+            _jpeg_refuse('the file has no SOS: it ends at byte %d inside its headers' % n)
+        if data[pos] != 0xFF:
+            _jpeg_refuse('a marker expected at byte %d, got %02X' % (pos, data[pos]))
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos + 3 > n:
+            _jpeg_refuse('the file has no SOS: it ends at byte %d inside its headers' % n)
+        m = data[pos]
+        pos += 1
+        if m == 0xD9:
+            _jpeg_refuse('the file has no SOS: EOI at byte %d' % (pos - 2))
+        length = (data[pos] << 8) | data[pos + 1]
+        if length < 2 or pos + length > n:
+            _jpeg_refuse('segment %02X at byte %d reaches past the end of the file' % (m, pos - 2))
+        seg = data[pos + 2:pos + length]
+        pos += length
+        if m == 0xDA:
+            break
+        if 0xE0 <= m <= 0xEF or m == 0xFE:
+            if m == 0xEE and seg[:5] == b'Adobe' and len(seg) >= 12 and seg[11] == 0:
+                _jpeg_refuse('an Adobe APP14 segment with transform 0 (RGB or CMYK samples, not YCbCr)')
+        elif m == 0xDB:
+            at = 0
+            while at < len(seg):
+                pq, tq = seg[at] >> 4, seg[at] & 15
+                if pq != 0:
+                    _jpeg_refuse('16-bit quantisation table %d' % tq)
+                if tq > 3 or at + 65 > len(seg):
+                    _jpeg_refuse('a malformed DQT segment')
+                t = [0] * 64
+                for k in range(64):
+                    t[JPEG_ZIGZAG[k]] = seg[at + 1 + k]
+                if min(t) < 1:
+                    _jpeg_refuse('quantisation table %d has a zero entry' % tq)
+                quant[tq] = tuple(t)
+                at += 65
+        elif m == 0xC0:
+            if frame is not None:
+                _jpeg_refuse('a second SOF0')
+            if len(seg) < 6:
+                _jpeg_refuse('a malformed SOF0 segment')
+            if seg[0] != 8:
+                _jpeg_refuse('%d-bit precision (8 expected)' % seg[0])
+            H, W, nf = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
+            if nf != 3:
+                _jpeg_refuse('%d component%s (three expected: Y, Cb, Cr)' % (nf, '' if nf == 1 else 's'))
+            if len(seg) != 6 + 3 * nf:
+                _jpeg_refuse('a malformed SOF0 segment')
+            if H < 1 or W < 1:
+                _jpeg_refuse('zero width or height (%d x %d)' % (H, W))
+            if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+                _jpeg_refuse('a side above %d (%d x %d)' % (JPEG_MAX_SIDE, H, W))
+            comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(3)]
+            samp = tuple((h, v) for _, h, v, _ in comps)
+            if samp not in (((2, 2), (1, 1), (1, 1)), ((1, 1), (1, 1), (1, 1))):
+                _jpeg_refuse('sampling %s (2x2/1x1/1x1 or 1x1/1x1/1x1 expected)' % '/'.join('%dx%d' % s for s in samp))
+            frame = (H, W, comps)
+        elif m in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
+            _jpeg_refuse('%s (SOF%d); baseline SOF0 expected'
+                         % ('progressive' if m in (0xC2, 0xC6, 0xCA, 0xCE) else 'not baseline', m - 0xC0))
+        elif m == 0xC4:
+            at = 0
+            while at < len(seg):
+                tc, th = seg[at] >> 4, seg[at] & 15
+                if tc > 1 or th > 3 or at + 17 > len(seg):
+                    _jpeg_refuse('a malformed DHT segment')
+                counts = tuple(seg[at + 1:at + 17])
+                total = sum(counts)
+                space = 1                                 # codes still free at this length
+                for c in counts:
+                    space = 2 * space - c
+                    if space < 0:
+                        _jpeg_refuse('Huffman table %d/%d assigns more codes than its lengths hold' % (tc, th))
+                if total > 256 or at + 17 + total > len(seg):
+                    _jpeg_refuse('a malformed DHT segment')
+                huff[(tc, th)] = (counts, tuple(seg[at + 17:at + 17 + total]))
+                at += 17 + total
+        elif m == 0xDD:
+            if len(seg) != 2:
+                _jpeg_refuse('a malformed DRI segment')
+            ri = (seg[0] << 8) | seg[1]
+        else:
+            _jpeg_refuse('marker %02X at byte %d is not part of a baseline file' % (m, pos - length - 2))
+    if frame is None:
+        _jpeg_refuse('SOS before SOF0')
+    H, W, comps = frame
+    ns = seg[0] if seg else 0
+    if ns != 3:
+        _jpeg_refuse('several scans: the first holds %d of the 3 components (one interleaved scan expected)' % ns)
+    if len(seg) != 1 + 2 * ns + 3:
+        _jpeg_refuse('a malformed SOS segment')
+    if (seg[7], seg[8], seg[9]) != (0, 63, 0):
+        _jpeg_refuse('a scan of coefficients %d..%d, approximation %02X (progressive); 0..63 expected' % (seg[7], seg[8], seg[9]))
+    tables = []
+    for c in range(3):
+        if seg[1 + 2 * c] != comps[c][0]:
+            _jpeg_refuse('the scan lists component %d where the frame has %d' % (seg[1 + 2 * c], comps[c][0]))
+        td, ta = seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15
+        if comps[c][3] not in quant:
+            _jpeg_refuse('component %d refers to quantisation table %d, which the file never defines' % (c, comps[c][3]))
+        if (0, td) not in huff:
+            _jpeg_refuse('component %d refers to DC Huffman table %d, which the file never defines' % (c, td))
+        if (1, ta) not in huff:
+            _jpeg_refuse('component %d refers to AC Huffman table %d, which the file never defines' % (c, ta))
+        tables.append((huff[(0, td)], huff[(1, ta)]))
+    sub = comps[0][1]
+    mcus = (-(-H // (8 * sub)), -(-W // (8 * sub)))
+    # the scan: stuffed FF 00 pairs are data, RSTn splits it, any other marker ends it
+    segments, marks = [], []
+    begin = at = pos
+    eoi, end = False, n
+    while at < n:
+        if data[at] != 0xFF:
+            at += 1
+            continue
+        k = at + 1
+        while k < n and data[k] == 0xFF:                 # fill bytes in front of a marker
+            k += 1
+        if k >= n:
+            break                                         # FF at the very end: the scan runs to the end of the data
+        if data[k] == 0 and k == at + 1:
+            at += 2
+            continue
+        if 0xD0 <= data[k] <= 0xD7:
+            segments.append((begin, at))
+            marks.append(data[k] - 0xD0)
+            begin = at = k + 1
+            continue
+        end, eoi = at, data[k] == 0xD9
+        if not eoi:
+            _jpeg_refuse('several scans: marker %02X follows the first scan at byte %d' % (data[k], at))
+        break
+    segments.append((begin, end))
+    total = mcus[0] * mcus[1]
+    want = -(-total // ri) if ri else 1
+    if marks != [i % 8 for i in range(len(marks))]:
+        _jpeg_refuse('restart markers out of sequence: RST%s' % ', RST'.join(str(v) for v in marks[:16]))
+    if len(segments) > want or (eoi and len(segments) != want):
+        _jpeg_refuse('%d restart intervals in the scan, %d expected (%d MCUs, restart interval %d)'
+                     % (len(segments), want, total, ri))
+    segments += [(end, end)] * (want - len(segments))
+    return JpegHeader(H=H, W=W, sub=sub, mcus=mcus, quant=tuple(quant[c[3]] for c in comps), huffman=tuple(tables),
+                      restart_interval=ri, segments=segments, eoi=eoi, data=data)
+
+
+def jpeg_huffman_table(counts, values):
+    """The decode form of one Huffman table (csrc/jpeg_entropy.h reads the same 288 ints): with c the next 16 bits of the
+    stream, the code has the smallest length l with c < limit[l - 1], and its value is values[(offset[l - 1] + (c >>
+    (16 - l))) & 255].  limit[l - 1] = (first code of length l + number of such codes) << (16 - l): canonical codes of one
+    length are consecutive (T.81 F.2.2.3), so limit does not decrease."""
+    limit, offset = [], []
+    code = at = 0
+    for l in range(1, 17):
+        offset.append(at - code)
+        code += counts[l - 1]
+        at += counts[l - 1]
+        limit.append(code << (16 - l))
+        code <<= 1
+    return limit + offset + list(values) + [0] * (256 - len(values))
+
+
+class _JpegBits:
+    """The bit reader of a segment: bytes [pos, end) of data, FF 00 un-stuffed, zeros fed past the end (status 1 once one of
+    them is consumed).  At most 23 bits wait in buf."""
+
+    def __init__(self, data, pos, end):
+        self.data, self.pos, self.end = data, pos, end
+        self.buf = self.n = self.fake = self.status = 0
+
+    def need(self, k):
+        while self.n < k:
+            b = 0
+            if self.pos < self.end:
+                b = self.data[self.pos]
+                self.pos += 1
+                if b == 0xFF and self.pos < self.end and self.data[self.pos] == 0:
+                    self.pos += 1
+            else:
+                self.fake += 8
+            self.buf = ((self.buf << 8) | b) & 0xFFFFFFFF
+            self.n += 8
+
+    def skip(self, k):
+        self.n -= k
+        if self.n < self.fake:
+            self.status, self.fake = max(self.status, 1), self.n
+
+    def huffman(self, t):
+        self.need(16)
+        c = (self.buf >> (self.n - 16)) & 0xFFFF
+        for l in range(1, 17):
+            if c < t[l - 1]:
+                self.skip(l)
+                return t[32 + ((t[16 + l - 1] + (c >> (16 - l))) & 255)]
+        return -1
+
+    def receive(self, s):
+        """s <= 15 bits, extended to a signed value (T.81 F.2.2.1)"""
+        self.need(s)
+        r = (self.buf >> (self.n - s)) & ((1 << s) - 1)
+        self.skip(s)
+        return r if r >= (1 << (s - 1)) else r - (1 << s) + 1
+
+
+def _jpeg_block(bits: _JpegBits, dc, ac, pred: int, out) -> tuple:
+    """one block into out (64 ints, natural order, zero on entry) -> (error status or 0, the new DC prediction)"""
+    s = bits.huffman(dc)
+    if s < 0 or s > 11:
+        return 2, pred
+    if s:
+        pred = ((pred + bits.receive(s) + 32768) & 65535) - 32768   # the prediction lives in the int16 a coefficient has
+    out[0] = pred
+    k = 1
+    while k < 64:
+        rs = bits.huffman(ac)
+        if rs < 0:
+            return 2, pred
+        r, s = rs >> 4, rs & 15
+        if s == 0:
+            if r != 15:
+                break
+            k += 16
+            if k > 64:
+                return 3, pred
+            continue
+        k += r
+        if k > 63:
+            return 3, pred
+        out[JPEG_ZIGZAG[k]] = bits.receive(s)
+        k += 1
+    return 0, pred
+
+
+def _jpeg_coefficients(hd: JpegHeader):
+    """every segment of a parsed file through the entropy decoder -> (coefficient planes [Y, Cb, Cr], int32 (block rows, 8,
+    block columns, 8) in natural order and whole MCUs, status)"""
+    sub, (my, mx) = hd.sub, hd.mcus
+    planes = [torch.zeros((my * s, mx * s, 64), dtype=torch.int32) for s in (sub, 1, 1)]
+    tabs = [(jpeg_huffman_table(*dc), jpeg_huffman_table(*ac)) for dc, ac in hd.huffman]
+    ri = hd.restart_interval or my * mx
+    status = 0
+    for i, (begin, end) in enumerate(hd.segments):
+        bits = _JpegBits(hd.data, begin, end)
+        pred, dead = [0, 0, 0], 0
+        for mcu in range(i * ri, min((i + 1) * ri, my * mx)):
+            y, x = divmod(mcu, mx)
+            for c in range(3):
+                s = sub if c == 0 else 1
+                for v in range(s):
+                    for h in range(s):
+                        if dead:
+                            continue                      # the rest of the segment's blocks stay zero
+                        blk = [0] * 64
+                        dead, pred[c] = _jpeg_block(bits, tabs[c][0], tabs[c][1], pred[c], blk)
+                        planes[c][y * s + v, x * s + h] = torch.tensor(blk, dtype=torch.int32)
+        status = max(status, dead, bits.status)
+    return [p.reshape(p.shape[0], p.shape[1], 8, 8).permute(0, 2, 1, 3) for p in planes], status
+
+
+def jpeg_decode_host(data, return_status: bool = False):
+    """The definition of ops.jpeg_decode_u8, int32 only: one baseline file (bytes, or a JpegHeader) -> uint8 (H, W, 3), with
+    return_status=True (frame, status).
+
+      entropy      canonical Huffman decoding (T.81 F.2.2) of each restart interval: bytes un-stuffed, the DC prediction
+                   reset at each restart, coefficients de-zigzagged
+      blocks       times the file's own table; _idct8 columns then rows; + 128; clamp
+      chroma       cut to the ceil(H / 2) x ceil(W / 2) samples that belong to the frame, then _jpeg_upsample ('420')
+      colour out   _ycc_to_rgb(..., JFIF_COEFFICIENTS); crop to H x W
+
+    status: 0 fine | 1 bits were needed past the end of a segment (zeros are fed) | 2 a 16-bit prefix with no code, or a DC
+    category above 11 | 3 a run that carries the coefficient index past 63.  After 2 or 3 the rest of that segment's blocks
+    are zero; the largest status of a file's segments is the file's.  The device gives these bytes where the status is 0
+    and the dequantised blocks stay inside libjpeg's 32-bit argument (every file an encoder makes from 8-bit samples)."""
+    hd = data if isinstance(data, JpegHeader) else jpeg_parse(data)
+    coef, status = _jpeg_coefficients(hd)
+    H, W = hd.H, hd.W
+    Y, Cb, Cr = (_jpeg_samples((c * torch.tensor(q, dtype=torch.int32).reshape(8, 1, 8)[None])[None])
+                 for c, q in zip(coef, hd.quant))
+    if hd.sub == 2:
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        Cb, Cr = _jpeg_upsample(Cb[:, :Hc, :Wc], H, W), _jpeg_upsample(Cr[:, :Hc, :Wc], H, W)
+    out = _ycc_to_rgb(Y[:, :H, :W], Cb[:, :H, :W] - 128, Cr[:, :H, :W] - 128, JFIF_COEFFICIENTS)[0]
+    return (out, status) if return_status else out
+
+
+def check_jpeg_status(status) -> None:
+    """reads the status table of ops.jpeg_decode_u8 back (this waits for the device) and raises for the first damaged file"""
+    names = {1: 'its scan ends early', 2: 'a Huffman code or DC category no table holds', 3: 'a run past coefficient 63'}
+    for i, s in enumerate(status.detach().cpu().tolist()):
+        if s != 0:
+            raise ValueError('jpeg_decode: file %d is damaged (status %d: %s)' % (i, s, names.get(s, 'unknown')))
+
+
+def _huffman_codes(counts, values):
+    """value -> (code, length) of a canonical table"""
+    codes, code, at = {}, 0, 0
+    for l in range(1, 17):
+        for _ in range(counts[l - 1]):
+            codes[values[at]] = (code, l)
+            code += 1
+            at += 1
+        code <<= 1
+    return codes
+
+
+def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval: int = 0) -> bytes:
+    """A baseline JFIF file of one frame, for tests and benchmarks: u8 uint8 (H, W, 3) -> bytes.  The front half of
+    jpeg_roundtrip_host (colour in, padding, downsample, _fdct8, quantise with jpeg_quant_tables(quality)), then Huffman
+    coding with the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none).  Its defining property:
+    jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly."""
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError('jpeg_encode_host expects a non-empty uint8 (H, W, 3) frame')
+    sub = _jpeg_sub(subsampling)
+    ri = int(restart_interval)
+    if not 0 <= ri <= 65535:
+        raise ValueError('jpeg_encode_host: the restart interval must lie in [0, 65535], got %d' % ri)
+    H, W = int(u8.shape[0]), int(u8.shape[1])
+    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+        raise ValueError('jpeg_encode_host: frames of at most %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE))
+    qt = jpeg_quant_tables(quality)
+    planes = _jpeg_planes_in(u8[None].cpu(), sub)
+    zz = torch.tensor(JPEG_ZIGZAG)
+    coef = []                                               # per component (block rows, block columns, 64) in zigzag order
+    for c, p in enumerate(planes):
+        k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
+        coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
+    out = bytearray(b'\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
+    for t in range(2):
+        out += b'\xff\xdb\x00\x43' + bytes([t]) + bytes(qt[t].reshape(64)[zz].tolist())
+    out += b'\xff\xc0\x00\x11\x08' + bytes([H >> 8, H & 255, W >> 8, W & 255, 3, 1, (sub << 4) | sub, 0, 2, 0x11, 1, 3, 0x11, 1])
+    for (tc, th), (counts, values) in sorted(JPEG_STD_HUFFMAN.items()):
+        out += b'\xff\xc4' + bytes([(19 + len(values)) >> 8, (19 + len(values)) & 255, (tc << 4) | th]) + bytes(counts) + bytes(values)
+    if ri:
+        out += b'\xff\xdd\x00\x04' + bytes([ri >> 8, ri & 255])
+    out += b'\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00'
+    codes = {k: _huffman_codes(*v) for k, v in JPEG_STD_HUFFMAN.items()}
+    acc = nacc = 0
+
+    def put(code, length):
+        nonlocal acc, nacc
+        acc, nacc = (acc << length) | code, nacc + length
+        while nacc >= 8:
+            b = (acc >> (nacc - 8)) & 255
+            out.append(b)
+            if b == 255:
+                out.append(0)
+            nacc -= 8
+        acc &= (1 << nacc) - 1
+
+    def magnitude(v):
+        s = abs(v).bit_length()
+        return s, (v if v >= 0 else v + (1 << s) - 1)
+
+    my, mx = -(-H // (8 * sub)), -(-W // (8 * sub))
+    pred = [0, 0, 0]
+    for mcu in range(my * mx):
+        if ri and mcu and mcu % ri == 0:
+            if nacc:
+                put((1 << (8 - nacc)) - 1, 8 - nacc)
+            out += bytes([0xFF, 0xD0 + (mcu // ri - 1) % 8])
+            pred = [0, 0, 0]
+        y, x = divmod(mcu, mx)
+        for c in range(3):
+            s = sub if c == 0 else 1
+            dc, ac = codes[(0, min(c, 1))], codes[(1, min(c, 1))]
+            for v in range(s):
+                for h in range(s):
+                    blk = coef[c][y * s + v][x * s + h]
+                    size, bits = magnitude(blk[0] - pred[c])
+                    pred[c] = blk[0]
+                    put(*dc[size])
+                    if size:
+                        put(bits, size)
+                    run = 0
+                    last = max([k for k in range(1, 64) if blk[k]] or [0])
+                    for k in range(1, last + 1):
+                        if blk[k] == 0:
+                            run += 1
+                            continue
+                        while run > 15:
+                            put(*ac[0xF0])
+                            run -= 16
+                        size, bits = magnitude(blk[k])
+                        put(*ac[(run << 4) | size])
+                        put(bits, size)
+                        run = 0
+                    if last < 63:
+                        put(*ac[0])
+    if nacc:
+        put((1 << (8 - nacc)) - 1, 8 - nacc)
+    return bytes(out + b'\xff\xd9')
+
+
+class JpegBatch:
+    """Files packed for one launch of ops.jpeg_decode_u8 (jpeg_batch makes it): host tensors, pinned where a device is there
+    to take them.  data uint8: the scan bytes of every file, end to end | images int32 (n, 20): H, W, chroma step, MCU
+    columns, MCU rows, the quantisation slots of Y, Cb, Cr, the (DC, AC) Huffman slots of Y, Cb, Cr, first block in the
+    scratch, first workgroup of the IDCT, first segment, segments, blocks, 0 | segments int32 (s, 5): image, first byte, end
+    byte, first MCU, MCUs | qtabs int32 (q, 64): the distinct quantisation tables, natural order | htabs int32 (h, 288): the
+    distinct Huffman tables as jpeg_huffman_table makes them | sizes: [(H, W)] | blocks: 8 x 8 blocks of the whole batch."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self._on = {}
+
+    @property
+    def scratch_bytes(self) -> int:
+        """what a launch needs: int16 coefficients and uint8 planes of every block, an int32 status per segment"""
+        return 192 * self.blocks + 4 * int(self.segments.shape[0])
+
+    def on(self, device):
+        """the five tensors on `device`: .data .images .segments .qtabs .htabs.  Uploaded once, without blocking, on the
+        stream that is current at the first call: a caller that decodes on another stream later orders the two itself."""
+        key = str(device)
+        if key not in self._on:
+            names = ('data', 'images', 'segments', 'qtabs', 'htabs')
+            self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in names})
+        return self._on[key]
+
+
+def jpeg_batch(files) -> JpegBatch:
+    """A sequence of baseline JPEG files (bytes) -> the JpegBatch of one launch.  Every file goes through jpeg_parse, so a
+    file the decoder does not take is refused here, before anything is uploaded."""
+    files = list(files)
+    if not files:
+        raise ValueError('jpeg_batch: an empty batch')
+    chunks, images, segments, qtabs, htabs, sizes = [], [], [], {}, {}, []
+    nbytes = blocks = groups = 0
+    for i, f in enumerate(files):
+        hd = f if isinstance(f, JpegHeader) else jpeg_parse(f)
+        my, mx = hd.mcus
+        q = [qtabs.setdefault(t, len(qtabs)) for t in hd.quant]
+        h = [htabs.setdefault(t, len(htabs)) for pair in hd.huffman for t in pair]
+        nb = my * mx * (hd.sub * hd.sub + 2)
+        images.append([hd.H, hd.W, hd.sub, mx, my] + q + h + [blocks, groups, len(segments), len(hd.segments), nb, 0])
+        blocks, groups = blocks + nb, groups + -(-nb // JPEG_IDCT_BLOCKS)
+        lo, hi = hd.segments[0][0], hd.segments[-1][1]
+        ri = hd.restart_interval or my * mx
+        for k, (b, e) in enumerate(hd.segments):
+            segments.append([i, nbytes + b - lo, nbytes + e - lo, k * ri, min(ri, my * mx - k * ri)])
+        chunks.append(hd.data[lo:hi])
+        nbytes += hi - lo
+        sizes.append((hd.H, hd.W))
+    pin = torch.cuda.is_available()
+
+    def host(t):
+        return t.pin_memory() if pin and t.numel() else t
+    data = torch.frombuffer(bytearray(b''.join(chunks) or b'\0'), dtype=torch.uint8)
+    return JpegBatch(data=host(data), nbytes=nbytes, images=host(torch.tensor(images, dtype=torch.int32)),
+                     segments=host(torch.tensor(segments, dtype=torch.int32)),
+                     qtabs=host(torch.tensor(list(qtabs), dtype=torch.int32)),
+                     htabs=host(torch.tensor([jpeg_huffman_table(*t) for t in htabs], dtype=torch.int32)),
+                     sizes=sizes, n=len(files), blocks=blocks, groups=groups)
+
+
+def whole_boxes(sizes) -> Tensor:
+    """[(H, W)] -> int32 (n, 4): the box (0, 0, H, W) of every frame, for crop_resize_u8 on the decoder's canvas"""
+    return torch.tensor([[0, 0, int(h), int(w)] for h, w in sizes], dtype=torch.int32).reshape(-1, 4)
 
 
 # ------------------------------------------------------------------------------------------ NV12 frames

@@ -20,6 +20,13 @@
 // rounded up to whole MCUs).  jpeg_rgb_kernel: a lane takes 4 consecutive pixels of the batch, reads Y and the (up to 4 + 4)
 // chroma samples around each from the planes, and stores their 12 bytes as three dwords.  A frame whose quality is <= 0 is
 // skipped by the first kernel and copied by the second.
+//
+// JPEG files (DESIGN.md "JPEG files") are the second half of this file: istvt_jpeg_decode_u8 decodes a batch of baseline
+// files from their compressed bytes in three launches that share jp_idct8, jp_chroma and the colour-out expression with the
+// round trip.  jpeg_entropy_kernel: one lane per restart interval (jpeg_entropy.h) -> int16 coefficients.
+// jpeg_idct_kernel: the back half of jpeg_planes_kernel with the file's own tables -> the planes.  jpeg_canvas_kernel:
+// jpeg_rgb_kernel over a canvas [n][Hc][Wc][3] that holds images of several sizes.
+#include "jpeg_entropy.h"
 #include "u8_view.h"
 
 namespace {
@@ -317,4 +324,283 @@ extern "C" int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, in
     if (o < a + bytes && a < o + bytes) return ISTVT_ERR_SHAPE;              // in place: the upsample reads its neighbours
     if (subsampling == 2) return jpeg_launch<2>(a, total, n, H, W, quality, (uint8_t*)scratch, scratch_bytes, (uint8_t*)out, stream);
     return jpeg_launch<1>(a, total, n, H, W, quality, (uint8_t*)scratch, scratch_bytes, (uint8_t*)out, stream);
+}
+
+// ---- JPEG files ----------------------------------------------------------------------------------------------------------
+// A row of the per-image table (clips.JpegBatch.images) and of the per-segment table
+enum { JD_H = 0, JD_W, JD_SUB, JD_MCUX, JD_MCUY, JD_QUANT, JD_HUFF = 8, JD_BLOCK0 = 14, JD_GROUP0, JD_SEG0, JD_NSEG, JD_NBLOCKS };
+constexpr int JD_IMAGE_INTS = 20;
+constexpr int JD_SEGMENT_INTS = 5;          // image, first byte, end byte, first MCU, MCUs
+// the scratch, for B blocks in the batch and s segments: int16 coefficients [B][64] | planes, 64 B bytes, per image Y
+// [Hp][Wp], Cb, Cr [Hp / sub][Wp / sub] as the round trip lays them out | int32 status [s]
+constexpr long JD_BLOCK_BYTES = 128 + 64;
+
+/* the argument block of istvt_jpeg_decode_u8 (include/istvt_hip.h) */
+struct istvt_jpeg_decode_args {
+    const void* bytes;
+    long nbytes;
+    const int* images;
+    const int* images_host;
+    const int* segments;
+    const int* segments_host;
+    const int* qtabs;
+    const int* htabs;
+    void* scratch;
+    long scratch_bytes;
+    void* out;
+    int* sizes;
+    int* status;
+    hipStream_t stream;
+    int n, nseg, nq, nh, Hc, Wc;
+};
+
+namespace {
+
+// where the entropy decoder puts the blocks of one image: int16 [block][64] in natural order
+struct JdWriter {
+    short* coef;
+    long block0, total;                     // the image's first block; blocks of the batch
+    int ybw, cbw, ny, nc;                   // blocks per row of Y / of a chroma plane; blocks of Y / of a chroma plane
+    __host__ __device__ long block(int c, int row, int col) const {
+        const long b = block0 + (c == 0 ? (long)row * ybw + col : ny + (long)(c - 1) * nc + (long)row * cbw + col);
+        return b >= 0 && b < total ? b : -1;
+    }
+    __host__ __device__ void clear(long b) const {
+        if (b < 0) return;
+        uint4* p = reinterpret_cast<uint4*>(coef + b * 64);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) p[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __host__ __device__ void put(long b, int at, int v) const {
+        if (b >= 0) coef[b * 64 + at] = (short)v;
+    }
+};
+
+// One lane per restart interval.  The entry has checked the host copies of both tables; the comparisons here keep a device
+// table that differs from them inside the buffers all the same (its segment then reports status 2).
+__global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restrict__ bytes, long nbytes,
+                                                          const int* __restrict__ images, int n,
+                                                          const int* __restrict__ segments, int nseg,
+                                                          const int* __restrict__ htabs, int nh, short* __restrict__ coef,
+                                                          long total_blocks, int* __restrict__ seg_status) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= nseg) return;
+    const int* sg = segments + (long)s * JD_SEGMENT_INTS;
+    const int img = sg[0], first = sg[3], count = sg[4];
+    const long begin = sg[1], end = sg[2];
+    int ok = img >= 0 && img < n && begin >= 0 && begin <= end && end <= nbytes && first >= 0 && count >= 0;
+    const int* im = images + (long)(ok ? img : 0) * JD_IMAGE_INTS;
+    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
+    ok = ok && (long)first + count <= (long)mcux * mcuy;
+    const int* huff[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int slot = im[JD_HUFF + k];
+        ok = ok && slot >= 0 && slot < nh;
+        huff[k] = htabs + (long)(ok ? slot : 0) * JE_HUFF_INTS;
+    }
+    if (!ok) {
+        seg_status[s] = 2;
+        return;
+    }
+    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * sub, mcux, mcux * sub * mcuy * sub, mcux * mcuy};
+    seg_status[s] = je_decode_segment(bytes, begin, end, huff, sub, mcux, first, count, w);
+}
+
+// The back half of jpeg_planes_kernel on decoded coefficients: a workgroup takes JP_BLOCKS consecutive blocks of one image,
+// a lane one 8-point transform of each pass: times the image's table and inverse columns | inverse rows, + 128, clamp, one
+// 8-byte store.  The first workgroup of an image also writes its size and the largest status of its segments.
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const short* __restrict__ coef, const int* __restrict__ images, int n,
+                                                        const int* __restrict__ qtabs, int nq,
+                                                        const int* __restrict__ seg_status, int nseg,
+                                                        uint8_t* __restrict__ planes, int* __restrict__ sizes,
+                                                        int* __restrict__ status) {
+    __shared__ int ws[JP_BLOCKS * JP_BLOCK_LD];
+    __shared__ int qt[3 * 64];
+    __shared__ int worst;
+    const int tid = threadIdx.x, g = blockIdx.x;
+    int lo = 0, hi = n - 1;                                      // the last image whose first workgroup is <= g
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (images[(long)mid * JD_IMAGE_INTS + JD_GROUP0] <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    const int* im = images + (long)lo * JD_IMAGE_INTS;
+    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = im[JD_MCUX], mcuy = im[JD_MCUY];
+    const int ybw = mcux * sub, ny = ybw * mcuy * sub, nc = mcux * mcuy, nb = ny + 2 * nc;
+    const long block0 = im[JD_BLOCK0];
+    const int local0 = (g - im[JD_GROUP0]) * JP_BLOCKS;
+    if (tid < 192) {
+        const int slot = im[JD_QUANT + (tid >> 6)];
+        qt[tid] = slot >= 0 && slot < nq ? qtabs[(long)slot * 64 + (tid & 63)] : 1;
+    }
+    if (tid == 0) worst = 0;
+    __syncthreads();
+    if (local0 == 0) {
+        int m = 0;
+        for (int s = tid; s < im[JD_NSEG]; s += 256) {
+            const long at = (long)im[JD_SEG0] + s;
+            if (at >= 0 && at < nseg) m = max(m, seg_status[at]);
+        }
+        if (m) atomicMax(&worst, m);
+    }
+
+    const int b = tid >> 3, k = tid & 7;                         // block and its column (first pass) or row (second)
+    const int bi = local0 + b;
+    const bool on = tid < JP_BLOCKS * 8 && bi < nb;
+    const int comp = bi < ny ? 0 : bi < ny + nc ? 1 : 2;
+    int d[8];
+    if (on) {
+        const short* src = coef + (block0 + bi) * 64 + k;
+        const int* q = qt + comp * 64 + k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = src[i * 8] * q[i * 8];
+        jp_idct8<true>(d);
+        int* col = ws + b * JP_BLOCK_LD + k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) col[i * 8] = d[i];
+    }
+    __syncthreads();
+    if (on) {
+        const int* row = ws + b * JP_BLOCK_LD + k * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        jp_idct8<false>(d);
+        const int c = comp ? bi - ny - (comp - 1) * nc : bi;     // the block's number in its plane
+        const int bw = comp ? mcux : ybw, brow = c / bw, bcol = c - brow * bw;
+        uint8_t* dst = planes + block0 * 64 + (comp ? (long)ny * 64 + (long)(comp - 1) * nc * 64 : 0) +
+                       (long)(brow * 8 + k) * (bw * 8) + bcol * 8;
+        uint2 v;
+        v.x = jp_byte(d[0] + 128) | jp_byte(d[1] + 128) << 8 | jp_byte(d[2] + 128) << 16 | jp_byte(d[3] + 128) << 24;
+        v.y = jp_byte(d[4] + 128) | jp_byte(d[5] + 128) << 8 | jp_byte(d[6] + 128) << 16 | jp_byte(d[7] + 128) << 24;
+        *reinterpret_cast<uint2*>(dst) = v;
+    }
+    if (local0 == 0 && tid == 0) {                               // `worst` is complete since the barrier between the passes
+        status[lo] = worst;
+        sizes[2 * lo] = im[JD_H], sizes[2 * lo + 1] = im[JD_W];
+    }
+}
+
+// jpeg_rgb_kernel over a canvas [n][Hc][Wc][3]: 4 consecutive pixels of the canvas per lane; inside its image's H x W a pixel
+// is the upsampled, converted sample, outside it is 0, so every byte of the canvas is written
+__global__ __launch_bounds__(256) void jpeg_canvas_kernel(const int* __restrict__ images, const uint8_t* __restrict__ planes,
+                                                          uint8_t* __restrict__ out, long npix, int Hc, int Wc, int out4) {
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= npix) return;
+    const long hw = (long)Hc * Wc;
+    long f = p0 / hw;
+    const int rest = (int)(p0 - f * hw);
+    int y = rest / Wc, xx = rest - y * Wc;
+    unsigned char o[12];
+    const int cnt = (int)min(4L, npix - p0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        o[3 * j] = o[3 * j + 1] = o[3 * j + 2] = 0;
+        if (j < cnt) {
+            const int* im = images + f * JD_IMAGE_INTS;
+            const int H = im[JD_H], W = im[JD_W];
+            if (y < H && xx < W) {
+                const int sub = im[JD_SUB] == 2 ? 2 : 1;
+                const int Wp = im[JD_MCUX] * 8 * sub, Hp = im[JD_MCUY] * 8 * sub;
+                const long plane = (long)Hp * Wp, cplane = plane / (sub * sub);
+                const int pw = Wp / sub, Hs = (H + sub - 1) / sub, Ws = (W + sub - 1) / sub;
+                const uint8_t* fp = planes + (long)im[JD_BLOCK0] * 64;
+                const int yv = fp[(long)y * Wp + xx];
+                int cb, cr;
+                if (sub == 2) {
+                    cb = jp_chroma<2>(fp + plane, pw, Hs, Ws, y, xx) - 128;
+                    cr = jp_chroma<2>(fp + plane + cplane, pw, Hs, Ws, y, xx) - 128;
+                } else {
+                    cb = jp_chroma<1>(fp + plane, pw, Hs, Ws, y, xx) - 128;
+                    cr = jp_chroma<1>(fp + plane + cplane, pw, Hs, Ws, y, xx) - 128;
+                }
+                o[3 * j] = (unsigned char)jp_byte(yv + ((91881 * cr + 32768) >> 16));
+                o[3 * j + 1] = (unsigned char)jp_byte(yv + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+                o[3 * j + 2] = (unsigned char)jp_byte(yv + ((116130 * cb + 32768) >> 16));
+            }
+            if (++xx == Wc) {
+                xx = 0;
+                if (++y == Hc) y = 0, ++f;
+            }
+        }
+    }
+    uint8_t* dst = out + p0 * 3;
+    if (out4 && cnt == 4) {
+        unsigned* d4 = reinterpret_cast<unsigned*>(dst);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) d4[j] = o[4 * j] | o[4 * j + 1] << 8 | o[4 * j + 2] << 16 | (unsigned)o[4 * j + 3] << 24;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j)
+            if (j < 3 * cnt) dst[j] = o[j];
+    }
+}
+
+// the host copies of the two tables against the counts, the byte range, the canvas and each other -> blocks of the batch, or -1
+long jpeg_decode_check(const istvt_jpeg_decode_args* a, long* groups) {
+    long blocks = 0, grp = 0, seg = 0;
+    for (int i = 0; i < a->n; ++i) {
+        const int* im = a->images_host + (long)i * JD_IMAGE_INTS;
+        const int H = im[JD_H], W = im[JD_W], sub = im[JD_SUB];
+        if (H < 1 || W < 1 || H > 16384 || W > 16384 || H > a->Hc || W > a->Wc || (sub != 1 && sub != 2)) return -1;
+        const int mcux = (W + 8 * sub - 1) / (8 * sub), mcuy = (H + 8 * sub - 1) / (8 * sub);
+        if (im[JD_MCUX] != mcux || im[JD_MCUY] != mcuy) return -1;
+        for (int c = 0; c < 3; ++c)
+            if (im[JD_QUANT + c] < 0 || im[JD_QUANT + c] >= a->nq) return -1;
+        for (int k = 0; k < 6; ++k)
+            if (im[JD_HUFF + k] < 0 || im[JD_HUFF + k] >= a->nh) return -1;
+        const long mcus = (long)mcux * mcuy, nb = mcus * (sub * sub + 2);
+        if (im[JD_BLOCK0] != blocks || im[JD_GROUP0] != grp || im[JD_SEG0] != seg || im[JD_NBLOCKS] != nb) return -1;
+        if (im[JD_NSEG] < 1 || seg + im[JD_NSEG] > a->nseg) return -1;
+        long mcu = 0;
+        for (int s = 0; s < im[JD_NSEG]; ++s) {
+            const int* sg = a->segments_host + (seg + s) * JD_SEGMENT_INTS;
+            if (sg[0] != i || sg[1] < 0 || sg[1] > sg[2] || sg[2] > a->nbytes || sg[3] != mcu || sg[4] < 1) return -1;
+            mcu += sg[4];
+        }
+        if (mcu != mcus) return -1;
+        seg += im[JD_NSEG];
+        blocks += nb;
+        grp += (nb + JP_BLOCKS - 1) / JP_BLOCKS;
+        if (blocks > 0x7fffffffL / 64) return -1;                 // block0 * 64 and the group count stay ints
+    }
+    if (seg != a->nseg) return -1;
+    *groups = grp;
+    return blocks;
+}
+
+}  // namespace
+
+// A batch of baseline JPEG files, packed by clips.jpeg_batch, decoded to uint8 RGB on a canvas out [n][Hc][Wc][3]; the
+// argument block is described in include/istvt_hip.h.  Three launches, no synchronisation, no global state.
+extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
+    if (!a || a->n <= 0 || a->nseg < a->n || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0) return ISTVT_ERR_SHAPE;
+    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->segments_host || !a->qtabs || !a->htabs ||
+        !a->scratch || !a->out || !a->sizes || !a->status)
+        return ISTVT_ERR_SHAPE;
+    if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
+    long groups = 0;
+    const long blocks = jpeg_decode_check(a, &groups);
+    if (blocks < 0) return ISTVT_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < blocks * JD_BLOCK_BYTES + 4L * a->nseg)
+        return ISTVT_ERR_SHAPE;
+    const long npix = (long)a->n * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
+    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const uint8_t* src = (const uint8_t*)a->bytes;
+    uint8_t* out = (uint8_t*)a->out;
+    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
+    short* coef = (short*)a->scratch;
+    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
+    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((a->nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes,
+                       a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,
+                       seg_status, a->nseg, planes, a->sizes, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
+                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
 }

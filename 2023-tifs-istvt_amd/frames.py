@@ -1,5 +1,6 @@
 """The routines on decoded uint8 frames (clips.py holds their definitions on the host): crops, similarity warps, the NV12
-readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12.
+readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12; and the JPEG decoder
+that makes such frames from files (jpeg_decode_u8, decode_frames).
 
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
@@ -386,6 +387,72 @@ def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Op
                                                       planes.data_ptr(), planes.numel(), out.data_ptr(), _stream()),
                    'istvt_jpeg_roundtrip_u8')
     return out
+
+
+def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None):
+    """JPEG files (clips.py): a batch of baseline JPEG files goes to the device as compressed bytes -> (frames, sizes,
+    status): frames uint8 [n, Hc, Wc, 3], image i in the top left H_i x W_i of its canvas and 0 elsewhere, the bits of
+    clips.jpeg_decode_host; sizes int32 [n, 2] = (H, W) and status int32 [n] (0: fine; clips.jpeg_decode_host lists the
+    rest) on the device.  Nothing is decoded on the host and nothing synchronises: clips.check_jpeg_status(status) reads
+    back and raises, for callers who want that.  batch: a sequence of bytes, parsed and packed here (clips.jpeg_batch, which
+    refuses what the decoder does not take), or with checked=True a clips.JpegBatch the caller has packed already (the
+    loader's worker); its tables are uploaded once per device and kept on it.  canvas = (Hc, Wc) defaults to the largest
+    H and W of the batch.  `out` (uint8, contiguous, of the result's shape, no overlap with the uploaded bytes) is written
+    when given.  buffers = (scratch uint8 of at least batch.scratch_bytes bytes and 16-byte aligned, sizes, status): the
+    caller's, to decode step after step without an allocation."""
+    if isinstance(batch, clips.JpegBatch):
+        pass
+    elif checked:
+        raise RuntimeError('jpeg_decode_u8: checked=True takes a clips.JpegBatch (clips.jpeg_batch packs and validates the files)')
+    else:
+        if isinstance(batch, (bytes, bytearray)) or not hasattr(batch, '__len__'):
+            raise TypeError('jpeg_decode_u8 expects a sequence of files (bytes) or a clips.JpegBatch, got %s' % type(batch).__name__)
+        if len(batch) == 0:
+            raise RuntimeError('jpeg_decode_u8: empty input (no files)')
+        batch = clips.jpeg_batch(batch)
+    if not torch.cuda.is_available():
+        raise RuntimeError('istvt_amd: jpeg_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
+    device = out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    n = batch.n
+    Hmax, Wmax = max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes)
+    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < Hmax or Wc < Wmax or Hc > 16384 or Wc > 16384:
+        raise ValueError('jpeg_decode_u8: the canvas must hold every image (%d x %d at least, 16384 x 16384 at most), got %d x %d'
+                         % (Hmax, Wmax, Hc, Wc))
+    dev = batch.on(device)
+    out = _u8_out('jpeg_decode_u8', dev.data, (n, Hc, Wc, 3), out)
+    _no_overlap('jpeg_decode_u8', out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
+    if buffers is None:
+        scratch = torch.empty((batch.scratch_bytes,), dtype=torch.uint8, device=device)
+        sizes = torch.empty((n, 2), dtype=torch.int32, device=device)
+        status = torch.empty((n,), dtype=torch.int32, device=device)
+    else:
+        scratch, sizes, status = buffers
+        ok = (t.device == device and t.is_contiguous() for t in buffers)
+        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < batch.scratch_bytes or scratch.data_ptr() % 16
+                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
+                or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
+            raise RuntimeError('jpeg_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
+                               'status (%d,)), contiguous on %s' % (batch.scratch_bytes, n, n, device))
+    args = _lib.JpegDecodeArgs(
+        bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
+        segments=dev.segments.data_ptr(), segments_host=batch.segments.data_ptr(), qtabs=dev.qtabs.data_ptr(),
+        htabs=dev.htabs.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(),
+        sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, nseg=int(batch.segments.shape[0]),
+        nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), Hc=Hc, Wc=Wc)
+    with prof('jpeg_decode_u8', batch.nbytes + 2 * 192 * batch.blocks + out.numel()):
+        _lib.check(_lib.lib().istvt_jpeg_decode_u8(ctypes.byref(args)), 'istvt_jpeg_decode_u8')
+    return out, sizes, status
+
+
+def decode_frames(files, S: int, boxes: Optional[Tensor] = None) -> Tensor:
+    """Face crops from JPEG files: files (a sequence of bytes, or a clips.JpegBatch) are decoded on the device
+    (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
+    whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
+    and the scorers."""
+    batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files)
+    frames, _, _ = jpeg_decode_u8(batch, checked=True)
+    return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)
 
 
 def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,

@@ -375,6 +375,40 @@ int istvt_relevance_paste_nv12(void* frames, long total, int Hs, int Ws, long pi
  * (multiples of 8).  Two launches, no synchronisation, no atomics.  H, W <= 16384. */
 int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W, const int* quality, int subsampling,
                             void* scratch, long scratch_bytes, void* out, istvt_stream_t stream);
+/* JPEG files: a batch of baseline JPEG files, packed on the host by clips.jpeg_batch, decoded from their compressed bytes ->
+ * out uint8 [n][Hc][Wc][3]: image i in the top left H_i x W_i of its canvas, 0 elsewhere; sizes int32 [n][2] = (H, W) and
+ * status int32 [n] (0 fine, 1 the scan ended early, 2 a code or DC category no table holds, 3 a run past coefficient 63) on
+ * the device.  The bits of clips.jpeg_decode_host where the status is 0: canonical Huffman decoding per restart interval
+ * (T.81 F.2.2), the file's own quantisation tables, then the inverse half of the round trip above.  Three launches (entropy:
+ * one lane per restart interval; IDCT; colour onto the canvas), no synchronisation, no global state.
+ *   bytes      uint8 [nbytes]: the scans of all files, end to end
+ *   images     int32 [n][20]: H, W, chroma step (2 or 1), MCU columns, MCU rows, quantisation slot of Y, Cb, Cr, (DC, AC)
+ *              Huffman slots of Y, Cb, Cr, first block, first IDCT workgroup (24 blocks each), first segment, segments,
+ *              blocks, 0.  An image's blocks: those of Y, row by row of the plane padded to whole MCUs, then Cb's, then Cr's.
+ *   segments   int32 [nseg][5]: image, first byte, end byte, first MCU, MCUs; sorted by image, then by MCU
+ *   qtabs      int32 [nq][64], natural order;  htabs int32 [nh][288]: limit[16], offset[16], values[256]
+ *   scratch    16-byte aligned, blocks * 192 + nseg * 4 bytes; nothing is read from it before it is written
+ * images_host / segments_host are host copies of the two tables: the entry checks them against the counts, nbytes, the
+ * canvas and each other before any launch and returns -3 on a null pointer, a bad count, a canvas smaller than an image,
+ * an out that overlaps bytes or an inconsistent table.  Every other pointer is a device pointer. */
+typedef struct istvt_jpeg_decode_args {
+    const void* bytes;
+    long nbytes;
+    const int* images;
+    const int* images_host;
+    const int* segments;
+    const int* segments_host;
+    const int* qtabs;
+    const int* htabs;
+    void* scratch;
+    long scratch_bytes;
+    void* out;
+    int* sizes;
+    int* status;
+    istvt_stream_t stream;
+    int n, nseg, nq, nh, Hc, Wc;
+} istvt_jpeg_decode_args;
+int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with
