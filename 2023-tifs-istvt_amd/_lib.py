@@ -21,6 +21,13 @@ class JpegDecodeArgs(ctypes.Structure):
                 ('stream', P), ('n', I), ('nseg', I), ('nq', I), ('nh', I), ('Hc', I), ('Wc', I)]
 
 
+class JpegEncodeArgs(ctypes.Structure):
+    """istvt_jpeg_encode_args of include/istvt_hip.h"""
+    _fields_ = [('frames', P), ('total', L), ('quality', P), ('header', P), ('header_bytes', L), ('scratch', P),
+                ('scratch_bytes', L), ('data', P), ('capacity', L), ('offsets', P), ('status', P), ('stream', P), ('n', I),
+                ('H', I), ('W', I), ('subsampling', I), ('restart_interval', I), ('dqt0', I), ('dqt1', I)]
+
+
 # name -> argtypes (all return int).  Mirrors include/istvt_hip.h one to one.
 SIGNATURES = {
     'istvt_gemm': [P, L, I, P, L, I, P, L, I, I, I, P, P, L, P, I, I, I, F, P, P, I, I, P],
@@ -76,6 +83,7 @@ SIGNATURES = {
     'istvt_relevance_paste_nv12': [P, L, I, I, L, L, P, I, P, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
     'istvt_jpeg_decode_u8': [ctypes.POINTER(JpegDecodeArgs)],
+    'istvt_jpeg_encode_u8': [ctypes.POINTER(JpegEncodeArgs)],
     'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],

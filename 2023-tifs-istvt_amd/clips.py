@@ -856,27 +856,34 @@ def _huffman_codes(counts, values):
     return codes
 
 
-def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval: int = 0) -> bytes:
-    """A baseline JFIF file of one frame, for tests and benchmarks: u8 uint8 (H, W, 3) -> bytes.  The front half of
-    jpeg_roundtrip_host (colour in, padding, downsample, _fdct8, quantise with jpeg_quant_tables(quality)), then Huffman
-    coding with the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none).  Its defining property:
-    jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly."""
-    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
-        raise ValueError('jpeg_encode_host expects a non-empty uint8 (H, W, 3) frame')
+def jpeg_restart_interval(restart_interval, W: int, subsampling: str = '420') -> int:
+    """The restart interval in MCUs that a file's DRI segment carries: an int in 0..65535 (0: no restart markers) as it is,
+    or 'row' for one MCU row, ceil(W / (8 * sub)) MCUs -- the interval that gives the device decoder one lane per MCU row."""
     sub = _jpeg_sub(subsampling)
+    if isinstance(restart_interval, str):
+        if restart_interval != 'row':
+            raise ValueError("the restart interval is an int in [0, 65535] or 'row', got %r" % (restart_interval,))
+        return -(-int(W) // (8 * sub))
     ri = int(restart_interval)
     if not 0 <= ri <= 65535:
-        raise ValueError('jpeg_encode_host: the restart interval must lie in [0, 65535], got %d' % ri)
-    H, W = int(u8.shape[0]), int(u8.shape[1])
-    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
-        raise ValueError('jpeg_encode_host: frames of at most %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE))
+        raise ValueError('the restart interval must lie in [0, 65535], got %d' % ri)
+    return ri
+
+
+JPEG_HEADER_DQT = (25, 94)                  # where the 64 bytes of the two quantisation tables lie in jpeg_header's bytes
+
+
+def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
+    """SOI through the SOS header of the file jpeg_encode_host writes for an H x W frame: JFIF APP0, the two quantisation
+    tables of `quality` in zig-zag order (at JPEG_HEADER_DQT), SOF0, the four Annex K.3 Huffman tables, DRI where the
+    restart interval is not 0, SOS.  Everything but the 2 x 64 table bytes is shared by the frames of a batch."""
+    sub = _jpeg_sub(subsampling)
+    H, W = int(H), int(W)
+    if not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
+        raise ValueError('jpeg_header: frames of 1 x 1 to %d x %d, got %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE, H, W))
+    ri = jpeg_restart_interval(restart_interval, W, subsampling)
     qt = jpeg_quant_tables(quality)
-    planes = _jpeg_planes_in(u8[None].cpu(), sub)
     zz = torch.tensor(JPEG_ZIGZAG)
-    coef = []                                               # per component (block rows, block columns, 64) in zigzag order
-    for c, p in enumerate(planes):
-        k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
-        coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
     out = bytearray(b'\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
     for t in range(2):
         out += b'\xff\xdb\x00\x43' + bytes([t]) + bytes(qt[t].reshape(64)[zz].tolist())
@@ -886,6 +893,30 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
     if ri:
         out += b'\xff\xdd\x00\x04' + bytes([ri >> 8, ri & 255])
     out += b'\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00'
+    return bytes(out)
+
+
+def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
+    """A baseline JFIF file of one frame, the definition of ops.jpeg_encode_u8: u8 uint8 (H, W, 3) -> bytes.  The front half
+    of jpeg_roundtrip_host (colour in, padding, downsample, _fdct8, quantise with jpeg_quant_tables(quality)), then Huffman
+    coding with the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none; 'row': every MCU row,
+    jpeg_restart_interval).  Its defining property:
+    jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly."""
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError('jpeg_encode_host expects a non-empty uint8 (H, W, 3) frame')
+    sub = _jpeg_sub(subsampling)
+    H, W = int(u8.shape[0]), int(u8.shape[1])
+    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+        raise ValueError('jpeg_encode_host: frames of at most %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE))
+    ri = jpeg_restart_interval(restart_interval, W, subsampling)
+    qt = jpeg_quant_tables(quality)
+    planes = _jpeg_planes_in(u8[None].cpu(), sub)
+    zz = torch.tensor(JPEG_ZIGZAG)
+    coef = []                                               # per component (block rows, block columns, 64) in zigzag order
+    for c, p in enumerate(planes):
+        k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
+        coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
+    out = bytearray(jpeg_header(H, W, quality, subsampling, ri))
     codes = {k: _huffman_codes(*v) for k, v in JPEG_STD_HUFFMAN.items()}
     acc = nacc = 0
 
@@ -944,6 +975,64 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
     return bytes(out + b'\xff\xd9')
 
 
+def check_encode_qualities(quality, n: int) -> Tensor:
+    """check_qualities for an encoder: every entry compresses, so it lies in 1..100"""
+    q = check_qualities(quality, n)
+    if bool((q < 1).any()):
+        raise ValueError('quality: an encoder takes entries in [1, 100], got down to %d' % int(q.min()))
+    return q
+
+
+def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', restart_interval='row') -> list:
+    """The definition of ops.jpeg_encode_u8 for a batch: frames uint8 (n, H, W, 3) or (B, T, H, W, 3), quality an int or
+    int32 (n,) / (B,) as check_qualities takes it, every entry in 1..100 -> [jpeg_encode_host(frame, its quality, ...)]."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (4, 5) or frames.shape[-1] != 3 \
+            or frames.numel() == 0:
+        raise ValueError('jpeg_encode_files_host expects non-empty uint8 (n, H, W, 3) or (B, T, H, W, 3) frames')
+    q = check_encode_qualities(quality, frames.shape[0])
+    if frames.dim() == 5:
+        q = q.repeat_interleave(frames.shape[1])
+    flat = frames.reshape((-1,) + tuple(frames.shape[-3:])).cpu()
+    return [jpeg_encode_host(f, int(v), subsampling, restart_interval) for f, v in zip(flat, q.tolist())]
+
+
+JPEG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capacity a retry needs', 2: 'quality <= 0: no file',
+                      3: 'a coefficient outside the categories of baseline JPEG, coded clamped'}
+
+
+class JpegFiles:
+    """What ops.jpeg_encode_u8 hands back, on the device: data uint8 (capacity,): the files end to end | offsets int64
+    (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, the rest as JPEG_ENCODE_STATUS names
+    them.  Nothing here has waited for the device until files() or nbytes() is called."""
+
+    def __init__(self, data: Tensor, offsets: Tensor, status: Tensor):
+        if data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 \
+                or status.dtype != torch.int32 or tuple(status.shape) != (offsets.shape[0] - 1,) or status.shape[0] < 1:
+            raise ValueError('JpegFiles: data uint8 (capacity,), offsets int64 (n + 1,), status int32 (n,) expected')
+        self.data, self.offsets, self.status = data, offsets, status
+
+    def __len__(self) -> int:
+        return int(self.status.shape[0])
+
+    def nbytes(self) -> int:
+        """the bytes of all files, offsets[n] (this waits for the device); more than the capacity where a status is 1"""
+        return int(self.offsets[-1])
+
+    def files(self, check: bool = True) -> list:
+        """-> [bytes] of every file.  Waits for the device once, for offsets and status, then copies offsets[n] bytes back
+        (at most the capacity).  check: a non-zero status raises ValueError with its name; with check=False such a file is
+        handed over as it is: b'' for status 1 and 2."""
+        table = torch.cat([self.offsets, self.status.to(torch.int64)]).cpu().tolist()
+        n = len(self)
+        offsets, status = table[:n + 1], table[n + 1:]
+        if check:
+            for i, s in enumerate(status):
+                if s != 0:
+                    raise ValueError('jpeg_encode: file %d has status %d (%s)' % (i, s, JPEG_ENCODE_STATUS.get(s, 'unknown')))
+        host = self.data[:max(0, min(offsets[n], int(self.data.shape[0])))].cpu().numpy().tobytes()
+        return [b'' if s in (1, 2) else host[offsets[i]:offsets[i + 1]] for i, s in enumerate(status)]
+
+
 class JpegBatch:
     """Files packed for one launch of ops.jpeg_decode_u8 (jpeg_batch makes it): host tensors, pinned where a device is there
     to take them.  data uint8: the scan bytes of every file, end to end | images int32 (n, 20): H, W, chroma step, MCU
@@ -973,8 +1062,9 @@ class JpegBatch:
 
 def jpeg_batch(files) -> JpegBatch:
     """A sequence of baseline JPEG files (bytes) -> the JpegBatch of one launch.  Every file goes through jpeg_parse, so a
-    file the decoder does not take is refused here, before anything is uploaded."""
-    files = list(files)
+    file the decoder does not take is refused here, before anything is uploaded.  A JpegFiles (the encoder's result) is read
+    back through its files()."""
+    files = files.files() if isinstance(files, JpegFiles) else list(files)
     if not files:
         raise ValueError('jpeg_batch: an empty batch')
     chunks, images, segments, qtabs, htabs, sizes = [], [], [], {}, {}, []

@@ -26,7 +26,13 @@
 // round trip.  jpeg_entropy_kernel: one lane per restart interval (jpeg_entropy.h) -> int16 coefficients.
 // jpeg_idct_kernel: the back half of jpeg_planes_kernel with the file's own tables -> the planes.  jpeg_canvas_kernel:
 // jpeg_rgb_kernel over a canvas [n][Hc][Wc][3] that holds images of several sizes.
+//
+// JPEG files out (DESIGN.md "JPEG files out") are the third part: istvt_jpeg_encode_u8 writes a batch of frames as baseline
+// files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
+// jpeg_count_kernel / jpeg_write_kernel: one lane per restart interval (jpeg_entropy_enc.h), first counting, then storing.
+// jpeg_offsets_kernel between them: the prefix sum that lays the files end to end.
 #include "jpeg_entropy.h"
+#include "jpeg_entropy_enc.h"
 #include "u8_view.h"
 
 namespace {
@@ -111,7 +117,10 @@ template <int SUB> __host__ __device__ __forceinline__ long jp_frame_bytes(int H
 }
 
 // SUB = chroma step per axis: 2 (4:2:0, MCU 16 x 16) or 1 (4:4:4, MCU 8 x 8).  A tile is one MCU row x JP_TILE_W pixels.
-template <int SUB>
+// ENC: the encoder's front half (JPEG files out, below).  The kernel stops behind the quantiser and stores what a file
+// holds: `planes` then takes int16 coefficients, per frame the blocks of Y row by row, then Cb's, then Cr's, 64 per block in
+// zig-zag order, one 16-byte store per lane.
+template <int SUB, bool ENC>
 __global__ __launch_bounds__(256) void jpeg_planes_kernel(const uint8_t* __restrict__ x, long total,
                                                           const int* __restrict__ quality, uint8_t* __restrict__ planes,
                                                           int H, int W, int Hp, int Wp, int tiles_y, int tiles_x) {
@@ -195,13 +204,35 @@ __global__ __launch_bounds__(256) void jpeg_planes_kernel(const uint8_t* __restr
         for (int i = 0; i < 8; ++i) {
             const int qv = qc[i * 8];
             const int n = (abs(d[i]) + 4 * qv) / (8 * qv);
-            d[i] = (d[i] < 0 ? -n : n) * qv;
+            d[i] = (d[i] < 0 ? -n : n) * (ENC ? 1 : qv);
         }
-        jp_idct8<true>(d);
+        if (!ENC) jp_idct8<true>(d);
 #pragma unroll
         for (int i = 0; i < 8; ++i) col[i * 8] = d[i];
     }
     __syncthreads();
+    if (ENC) {                                                   // coefficients 8 k .. 8 k + 7 of the block's zig-zag order
+        if (!on) return;
+        const int bw = Wp / 8, cw = Wp / (8 * SUB);              // blocks per row of Y / of a chroma plane
+        const long ny = (long)bw * (Hp / 8), nc = (long)cw * (Hp / (8 * SUB));
+        long at;
+        int bcol, lim;
+        if (SUB == 2) {
+            if (b < 16) bcol = x0 / 8 + (b & 7), lim = bw, at = (long)(y0 / 8 + (b >> 3)) * bw + bcol;
+            else bcol = x0 / 16 + ((b - 16) & 3), lim = cw, at = ny + ((b - 16) >> 2) * nc + (long)(y0 / 16) * cw + bcol;
+        } else {
+            bcol = x0 / 8 + (b & 7), lim = bw, at = (b >> 3) * nc + (long)(y0 / 8) * bw + bcol;
+        }
+        if (bcol < lim) {                                        // a tile may reach past the last MCU of the row
+            const int* blk = ws + b * JP_BLOCK_LD;
+            unsigned v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[j] = (unsigned)(blk[je_zigzag(8 * k + 2 * j)] & 0xFFFF) | (unsigned)blk[je_zigzag(8 * k + 2 * j + 1)] << 16;
+            *reinterpret_cast<uint4*>(planes + ((f * (ny + 2 * nc) + at) * 64 + 8 * k) * 2) = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        return;
+    }
     if (on) {                                                    // inverse rows -> 8 bytes of a plane
         const int* row = ws + b * JP_BLOCK_LD + k * 8;
 #pragma unroll
@@ -297,7 +328,7 @@ int jpeg_launch(const uint8_t* x, long total, int n, int H, int W, const int* qu
     const long npix = (long)n * H * W;
     const long groups = (npix + 1023) / 1024;
     if (tiles > 0x7fffffffL || groups > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    hipLaunchKernelGGL(jpeg_planes_kernel<SUB>, dim3((unsigned)tiles), dim3(256), 0, stream, x, total, quality, scratch, H, W,
+    hipLaunchKernelGGL((jpeg_planes_kernel<SUB, false>), dim3((unsigned)tiles), dim3(256), 0, stream, x, total, quality, scratch, H, W,
                        Hp, Wp, tiles_y, tiles_x);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
@@ -603,4 +634,220 @@ extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
     hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
                        a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
     return istvt_check_launch();
+}
+
+// ---- JPEG files out ------------------------------------------------------------------------------------------------------
+// istvt_jpeg_encode_u8 (DESIGN.md "JPEG files out"): frames -> baseline files laid end to end in one buffer, the bytes of
+// clips.jpeg_encode_host.  Four launches: jpeg_planes_kernel<SUB, true> (coefficients) | jpeg_count_kernel (one lane per
+// restart interval: its length) | jpeg_offsets_kernel (one workgroup: where every file and segment starts, the statuses) |
+// jpeg_write_kernel (the same lanes store; one workgroup per image copies the header).
+
+/* the argument block of istvt_jpeg_encode_u8 (include/istvt_hip.h) */
+struct istvt_jpeg_encode_args {
+    const void* frames;
+    long total;
+    const int* quality;
+    const void* header;
+    long header_bytes;
+    void* scratch;
+    long scratch_bytes;
+    void* data;
+    long capacity;
+    long* offsets;
+    int* status;
+    hipStream_t stream;
+    int n, H, W, subsampling, restart_interval, dqt0, dqt1;
+};
+
+namespace {
+
+// a row of the per-segment table behind the coefficients in the scratch: where the segment's first byte goes (written by
+// jpeg_offsets_kernel) and its length in the low 56 bits with its status above them (written by jpeg_count_kernel)
+struct JeSegment {
+    long begin;
+    unsigned long size;
+};
+constexpr int JE_STATUS_SHIFT = 56;
+constexpr unsigned long JE_LENGTH_MASK = (1ul << JE_STATUS_SHIFT) - 1;
+
+// what the three kernels behind the coefficients share
+struct JeGeometry {
+    int n, sub, mcux, mcuy, ri, nseg;       // frames; chroma step; MCUs per row / column; MCUs per segment; segments per image
+    long nb;                                // blocks per image
+};
+
+__device__ __forceinline__ void je_stage_codes(uint32_t* codes, int tid, int lanes) {
+    for (int i = tid; i < JE_CODE_WORDS; i += lanes) codes[i] = je_code_word(i);
+    __syncthreads();
+}
+
+// segment s of the batch through je_encode_segment -> its length and status
+template <class Sink>
+__device__ __forceinline__ long je_run_segment(const JeGeometry& g, const short* coef, long s, const uint32_t* codes, Sink& sink,
+                                               int& status) {
+    const long img = s / g.nseg;
+    const int k = (int)(s - img * g.nseg);
+    const long mcus = (long)g.mcux * g.mcuy;
+    const long first = (long)k * g.ri;
+    const int count = (int)min((long)g.ri, mcus - first);
+    const int marker = k == g.nseg - 1 ? 0xD9 : 0xD0 + (k & 7);
+    return je_encode_segment(coef + img * g.nb * 64, g.sub, g.mcux, g.mcuy, (int)first, count, codes, marker, sink, status);
+}
+
+__global__ __launch_bounds__(64) void jpeg_count_kernel(JeGeometry g, const int* __restrict__ quality,
+                                                        const short* __restrict__ coef, JeSegment* __restrict__ seg) {
+    __shared__ uint32_t codes[JE_CODE_WORDS];
+    je_stage_codes(codes, threadIdx.x, 64);
+    const long s = (long)blockIdx.x * 64 + threadIdx.x;
+    if (s >= (long)g.n * g.nseg) return;
+    if (quality[s / g.nseg] <= 0) {                              // no coefficients, an empty file
+        seg[s].size = 2ul << JE_STATUS_SHIFT;
+        return;
+    }
+    JeCount sink = {0};
+    int status = 0;
+    const long len = je_run_segment(g, coef, s, codes, sink, status);
+    seg[s].size = ((unsigned long)len & JE_LENGTH_MASK) | (unsigned long)status << JE_STATUS_SHIFT;
+}
+
+// One workgroup.  The exclusive prefix sum, in one fixed order, of header + segments over the images: lane t sums the t-th
+// run of consecutive segments, the 256 sums are scanned in LDS, lane t walks its run again and writes the places.
+__global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const int* __restrict__ quality, long header_bytes,
+                                                           long capacity, JeSegment* __restrict__ seg, long* __restrict__ offsets,
+                                                           int* __restrict__ status) {
+    __shared__ long part[256];
+    const int tid = threadIdx.x;
+    const long N = (long)g.n * g.nseg, per = (N + 255) / 256;
+    const long lo = min(N, tid * per), hi = min(N, lo + per);
+    for (int i = tid; i < g.n; i += 256) status[i] = 0;
+    long sum = 0;
+    for (long e = lo; e < hi; ++e) {
+        const long img = e / g.nseg;
+        sum += (long)(seg[e].size & JE_LENGTH_MASK) + (e == img * g.nseg && quality[img] > 0 ? header_bytes : 0);
+    }
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {                          // inclusive scan of the 256 sums
+        const long add = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    long at = part[tid] - sum;
+    for (long e = lo; e < hi; ++e) {
+        const long img = e / g.nseg;
+        const unsigned long size = seg[e].size;
+        long head = 0;
+        if (e == img * g.nseg) {
+            offsets[img] = at;
+            head = quality[img] > 0 ? header_bytes : 0;
+        }
+        seg[e].begin = at + head;
+        at += head + (long)(size & JE_LENGTH_MASK);
+        const int st = (int)(size >> JE_STATUS_SHIFT);
+        if (st) atomicMax(status + img, st);
+    }
+    if (tid == 255) offsets[g.n] = part[255];
+    __syncthreads();
+    for (int i = tid; i < g.n; i += 256)
+        if (offsets[i + 1] > capacity) status[i] = 1;            // the file does not fit: nothing of it is written
+}
+
+// Workgroups [0, seg_groups): one lane per segment stores what it counted.  Workgroups behind them: one per image copies
+// the header, with the two quantisation tables of the frame's quality in their places.
+__global__ __launch_bounds__(64) void jpeg_write_kernel(JeGeometry g, int seg_groups, const int* __restrict__ quality,
+                                                        const short* __restrict__ coef, const JeSegment* __restrict__ seg,
+                                                        const uint8_t* __restrict__ header, int header_bytes, int dqt0, int dqt1,
+                                                        const long* __restrict__ offsets, const int* __restrict__ status,
+                                                        uint8_t* __restrict__ data, long capacity) {
+    __shared__ uint32_t codes[JE_CODE_WORDS];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= seg_groups) {
+        const int img = blockIdx.x - seg_groups;
+        const int st = status[img];
+        const long at = offsets[img];
+        if (st == 1 || st == 2 || at < 0 || at + header_bytes > capacity) return;
+        const int q = min(quality[img], 100);
+        const int s = q < 50 ? 5000 / max(q, 1) : 200 - 2 * q;
+        for (int i = tid; i < header_bytes; i += 64) {
+            int v = header[i];
+            const int t = i >= dqt0 && i < dqt0 + 64 ? i - dqt0 : i >= dqt1 && i < dqt1 + 64 ? 64 + i - dqt1 : -1;
+            if (t >= 0)                                           // a table entry: the file holds them in zig-zag order
+                v = min(max((JP_BASE[(t & 64) + je_zigzag(t & 63)] * s + 50) / 100, 1), 255);
+            data[at + i] = (uint8_t)v;
+        }
+        return;
+    }
+    je_stage_codes(codes, tid, 64);
+    const long s = (long)blockIdx.x * 64 + tid;
+    if (s >= (long)g.n * g.nseg) return;
+    const int st = status[s / g.nseg];
+    if (st == 1 || st == 2) return;
+    const long begin = seg[s].begin, len = (long)(seg[s].size & JE_LENGTH_MASK);
+    if (begin < 0 || begin + len > capacity) return;              // cannot be, with status 0 or 3; keeps a store inside data
+    JeStore sink = {data, begin, len, 0};
+    int ignored = 0;
+    je_run_segment(g, coef, s, codes, sink, ignored);
+}
+
+template <int SUB> int jpeg_encode_launch(const istvt_jpeg_encode_args* a) {
+    constexpr int MCU = 8 * SUB;
+    const int H = a->H, W = a->W, n = a->n;
+    const int Hp = (H + MCU - 1) / MCU * MCU, Wp = (W + MCU - 1) / MCU * MCU;
+    JeGeometry g;
+    g.n = n, g.sub = SUB, g.mcux = Wp / MCU, g.mcuy = Hp / MCU;
+    const long mcus = (long)g.mcux * g.mcuy;
+    g.ri = (int)(a->restart_interval ? min((long)a->restart_interval, mcus) : mcus);
+    const long nseg = (mcus + g.ri - 1) / g.ri;
+    g.nb = mcus * (SUB * SUB + 2);
+    const long blocks = g.nb * n, segments = nseg * n;
+    const int tiles_y = Hp / MCU, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
+    const long tiles = (long)n * tiles_y * tiles_x;
+    // a segment's length stays far inside 56 bits: at most 64 symbols of 27 bits per block, each byte stuffed
+    if (tiles > 0x7fffffffL || segments > 0x7fffffffL - 64 - n || blocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    if (a->scratch_bytes < blocks * 128 + segments * (long)sizeof(JeSegment)) return ISTVT_ERR_SHAPE;
+    g.nseg = (int)nseg;
+    uint8_t* coef = (uint8_t*)a->scratch;
+    JeSegment* seg = (JeSegment*)(coef + blocks * 128);
+    const uint8_t* x = (const uint8_t*)a->frames;
+    hipLaunchKernelGGL((jpeg_planes_kernel<SUB, true>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
+                       coef, H, W, Hp, Wp, tiles_y, tiles_x);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    const int seg_groups = (int)((segments + 63) / 64);
+    hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)seg_groups), dim3(64), 0, a->stream, g, a->quality, (const short*)coef, seg);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(256), 0, a->stream, g, a->quality, a->header_bytes, a->capacity, seg,
+                       a->offsets, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_write_kernel, dim3((unsigned)(seg_groups + n)), dim3(64), 0, a->stream, g, seg_groups, a->quality,
+                       (const short*)coef, (const JeSegment*)seg, (const uint8_t*)a->header, (int)a->header_bytes, a->dqt0, a->dqt1,
+                       (const long*)a->offsets, (const int*)a->status, (uint8_t*)a->data, a->capacity);
+    return istvt_check_launch();
+}
+
+}  // namespace
+
+// Frames uint8 [n][H][W][3] -> n baseline JPEG files end to end in data[0 .. capacity), offsets int64 [n + 1] and status
+// int32 [n] on the device; the argument block is described in include/istvt_hip.h.  Four launches, no synchronisation, no
+// global state, nothing allocated.
+extern "C" int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a) {
+    if (!a || a->n <= 0 || !a->frames || !a->quality || !a->header || !a->scratch || !a->data || !a->offsets || !a->status)
+        return ISTVT_ERR_SHAPE;
+    if (a->H < 1 || a->W < 1 || a->H > 16384 || a->W > 16384) return ISTVT_ERR_SHAPE;
+    if (a->subsampling != 0 && a->subsampling != 2) return ISTVT_ERR_SHAPE;
+    if (a->restart_interval < 0 || a->restart_interval > 65535 || a->capacity < 0) return ISTVT_ERR_SHAPE;
+    // the header: both 64-byte tables inside it, one behind the other
+    if (a->header_bytes < 128 || a->header_bytes > 4096 || a->dqt0 < 0 || a->dqt1 < a->dqt0 + 64 || a->dqt1 + 64 > a->header_bytes)
+        return ISTVT_ERR_SHAPE;
+    const long bytes = (long)a->n * a->H * a->W * 3;
+    if (a->total < bytes || (reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->offsets) & 7) ||
+        (reinterpret_cast<uintptr_t>(a->status) & 3))
+        return ISTVT_ERR_SHAPE;
+    const uint8_t* x = (const uint8_t*)a->frames;
+    const uint8_t* d = (const uint8_t*)a->data;
+    if (d < x + bytes && x < d + a->capacity) return ISTVT_ERR_SHAPE;
+    return a->subsampling == 2 ? jpeg_encode_launch<2>(a) : jpeg_encode_launch<1>(a);
 }

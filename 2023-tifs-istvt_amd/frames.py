@@ -1,6 +1,7 @@
 """The routines on decoded uint8 frames (clips.py holds their definitions on the host): crops, similarity warps, the NV12
 readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12; and the JPEG decoder
-that makes such frames from files (jpeg_decode_u8, decode_frames).
+that makes such frames from files (jpeg_decode_u8, decode_frames) and the encoder that makes files from them (jpeg_encode_u8,
+encode_frames).
 
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
@@ -26,11 +27,15 @@ def prof(name, nbytes):
 
 
 # ---- the argument front end ------------------------------------------------------------------------------------------------
-def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: bool = False):
+def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: bool = False, on_device: bool = True):
     """Packed RGB frames: uint8, channels last, (n, Hs, Ws, 3) or (clips_too) (B, T, Hs, Ws, 3) on the device, not empty, at
     most 16384 x 16384; contiguous=True refuses what would have to be copied.  -> (n frames, T or None, Hs, Ws); the kernels
-    take a pointer and n, so the flat source is _c(frames)."""
-    _req(frames, 'frames')
+    take a pointer and n, so the flat source is _c(frames).  on_device=False leaves the device to the caller, who asks for it
+    (_req) behind the argument errors that need none."""
+    if on_device:
+        _req(frames, 'frames')
+    elif not torch.is_tensor(frames):
+        raise TypeError('%s: frames must be a uint8 tensor, got %s' % (what, type(frames).__name__))
     if frames.dtype != torch.uint8:
         raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
     if frames.dim() not in ((4, 5) if clips_too else (4,)) or frames.shape[-1] != 3:
@@ -400,6 +405,8 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     H and W of the batch.  `out` (uint8, contiguous, of the result's shape, no overlap with the uploaded bytes) is written
     when given.  buffers = (scratch uint8 of at least batch.scratch_bytes bytes and 16-byte aligned, sizes, status): the
     caller's, to decode step after step without an allocation."""
+    if isinstance(batch, clips.JpegFiles):                        # the encoder's result: read back, then parsed like any files
+        batch = batch.files()
     if isinstance(batch, clips.JpegBatch):
         pass
     elif checked:
@@ -446,13 +453,95 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
 
 
 def decode_frames(files, S: int, boxes: Optional[Tensor] = None) -> Tensor:
-    """Face crops from JPEG files: files (a sequence of bytes, or a clips.JpegBatch) are decoded on the device
+    """Face crops from JPEG files: files (a sequence of bytes, a clips.JpegBatch or a clips.JpegFiles) are decoded on the device
     (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
     whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
     and the scorers."""
     batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files)
     frames, _, _ = jpeg_decode_u8(batch, checked=True)
     return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)
+
+
+# ---- JPEG files out ----------------------------------------------------------------------------------------------------------
+_JPEG_HEADERS: dict = {}                    # (H, W, subsampling, restart interval, device) -> (header on the device, its length)
+
+
+def _jpeg_header_on(device, H: int, W: int, subsampling: str, ri: int):
+    """the header every file of a call starts with, uploaded once per geometry and device; its table bytes are placeholders"""
+    key = (H, W, subsampling, ri, str(device))
+    if key not in _JPEG_HEADERS:
+        head = clips.jpeg_header(H, W, 50, subsampling, ri)
+        _JPEG_HEADERS[key] = (torch.frombuffer(bytearray(head), dtype=torch.uint8).to(device), len(head))
+    return _JPEG_HEADERS[key]
+
+
+def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', capacity: Optional[int] = None,
+                   out: Optional[Tensor] = None, checked: bool = False) -> 'clips.JpegFiles':
+    """JPEG files out (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3], contiguous, on the device, quality int32 [n] per
+    frame or, for clips, [B] shared by the T frames of a clip (or an int for all), every entry in 1..100 -> a clips.JpegFiles
+    on the device: the baseline JFIF files of clips.jpeg_encode_files_host end to end in `data`, byte for byte, with `offsets`
+    and a `status` per file.  subsampling '420' or '444'; restart_interval in MCUs (0: none, and one lane per image, slow)
+    or 'row': a restart marker every MCU row, the files ops.jpeg_decode_u8 decodes one lane per row.  A host quality table is
+    validated before any launch and uploaded without blocking; checked=True takes a per-frame device table as it is, and an
+    entry <= 0 then gives an empty file with status 2.  capacity: the bytes of `data`, by default n * (H * W * 3 + header); a
+    file that does not fit (noise at quality 100; a frame of a few pixels, whose file still codes a whole MCU) gets status 1,
+    nothing of it is written, and offsets[n] still says what a retry needs.  `out` (uint8, one dimension, contiguous, no
+    overlap with the frames) is used as `data`.  Nothing synchronises."""
+    n, T, H, W = _rgb_source('jpeg_encode_u8', frames, contiguous=True, on_device=False)
+    sub = clips._jpeg_sub(subsampling)
+    ri = clips.jpeg_restart_interval(restart_interval, W, subsampling)
+    host_only = ('jpeg_encode_u8: a device quality table is taken with checked=True only (int32, one entry per frame, validated '
+                 'by the caller); hand over the host table otherwise')
+    if not checked:                        # the argument errors that need no device, before the one that asks for it
+        if torch.is_tensor(quality) and quality.device.type != 'cpu':
+            raise RuntimeError(host_only)
+        clips.check_encode_qualities(quality, n if T is None else n // T)
+    _req(frames, 'frames')
+    qdev = _frame_table('jpeg_encode_u8', _QUALITIES, quality, n, T, frames.device, checked, clips.check_encode_qualities, host_only)
+    header, hlen = _jpeg_header_on(frames.device, H, W, subsampling, ri)
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or out.device != frames.device \
+                or not out.is_contiguous() or out.numel() == 0:
+            raise RuntimeError('jpeg_encode_u8: out must be contiguous uint8 (capacity,) on %s' % frames.device)
+        if capacity is not None and int(capacity) != out.numel():
+            raise ValueError('jpeg_encode_u8: capacity %d and out of %d bytes disagree' % (int(capacity), out.numel()))
+        data = out
+    else:
+        capacity = n * (H * W * 3 + hlen) if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError('jpeg_encode_u8: the capacity must be positive, got %d' % capacity)
+        data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
+    nbytes = frames.numel()
+    _no_overlap('jpeg_encode_u8', data, frames.data_ptr(), nbytes, 'frames')
+    mcus = (-(-H // (8 * sub))) * (-(-W // (8 * sub)))
+    blocks, segments = n * mcus * (sub * sub + 2), n * (-(-mcus // min(ri, mcus)) if ri else 1)
+    scratch = torch.empty((128 * blocks + 16 * segments,), dtype=torch.uint8, device=frames.device)
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=frames.device)
+    status = torch.empty((n,), dtype=torch.int32, device=frames.device)
+    _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri)
+    return clips.JpegFiles(data, offsets, status)
+
+
+def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri) -> None:
+    """the entry on buffers that are all the caller's (tests put sentinels around them)"""
+    args = _lib.JpegEncodeArgs(
+        frames=frames.data_ptr(), total=nbytes, quality=qdev.data_ptr(), header=header.data_ptr(), header_bytes=hlen,
+        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(), capacity=data.numel(),
+        offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W, subsampling=2 if sub == 2 else 0,
+        restart_interval=ri, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+    with prof('jpeg_encode_u8', nbytes + 3 * scratch.numel()):   # + the files' bytes, which live on the device
+        _lib.check(_lib.lib().istvt_jpeg_encode_u8(ctypes.byref(args)), 'istvt_jpeg_encode_u8')
+
+
+def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None, quality=90,
+                  subsampling: str = '420', restart_interval='row') -> 'clips.JpegFiles':
+    """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
+    cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
+    (jpeg_encode_u8) -> a clips.JpegFiles, whose files() ops.decode_frames and clips.jpeg_batch take."""
+    if (boxes is None) == (transforms is None):
+        raise ValueError('encode_frames: boxes and transforms are two ways to cut the same crop: pass one of them')
+    crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
+    return jpeg_encode_u8(crops, quality, subsampling, restart_interval)
 
 
 def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,

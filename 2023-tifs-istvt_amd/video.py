@@ -779,7 +779,7 @@ class VideoScorer:
         return res
 
     def render_explanation(self, frames: Tensor, explanation: VideoExplanation, boxes=None, transforms=None, which: str = 's',
-                           alpha: float = 0.5, weight_frames: bool = True, lut=None) -> Tensor:
+                           alpha: float = 0.5, weight_frames: bool = True, lut=None, jpeg_quality: Optional[int] = None):
         """The video an analyst was given, with the heat where the face is (DESIGN.md "Pasting maps onto frames"): the frames
         of explain() -- with the same boxes or transforms -- and its result -> the frames in their own format (packed RGB or
         NV12, as the scorer's pixel_format says), uint8 on the device, with explanation.frame_s (which='s') or frame_t ('t')
@@ -788,10 +788,18 @@ class VideoScorer:
         is blended with alpha_n = (frame_weight[n] / max frame_weight).clamp(0, 1) * alpha (float32, on the device, no
         synchronisation), so frames the verdict did not rest on stay nearly clean; frames no window covers have zero maps and
         come back untouched.  lut: uint8 (256, 3) RGB colours (default explain.jet_lut()).  Host frames are pinned, uploaded
-        and pasted frame_batch at a time; device frames are pasted out of place.  The model is not touched."""
+        and pasted frame_batch at a time; device frames are pasted out of place.  The model is not touched.  jpeg_quality
+        (1..100): the rendered RGB frames leave as JPEG files instead, a clips.JpegFiles on the device (ops.jpeg_encode_u8,
+        4:2:0, a restart marker every MCU row) -- a tenth of the bytes across the host boundary; not for NV12 frames."""
         from . import clips, explain as _explain, ops
         if which not in ('s', 't'):
             raise ValueError("render_explanation: which must be 's' or 't', got %r" % (which,))
+        if jpeg_quality is not None:
+            if self.pixel_format == 'nv12':
+                raise ValueError("render_explanation: jpeg_quality encodes packed RGB frames; pixel_format='nv12' with "
+                                 'jpeg_quality is not supported')
+            if isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100:
+                raise ValueError('render_explanation: jpeg_quality must be an int in [1, 100], got %r' % (jpeg_quality,))
         if boxes is not None and transforms is not None:
             raise ValueError('VideoScorer: boxes and transforms are two ways to cut the same crop: pass one of them')
         nv = self.pixel_format == 'nv12'
@@ -829,6 +837,8 @@ class VideoScorer:
             out[lo:hi].copy_(x, non_blocking=True)
             byte_frames.paste_maps(self.pixel_format, out[lo:hi], maps[lo:hi], A[lo:hi], rect[lo:hi], table, al[lo:hi],
                                    int(side), inplace=True, checked=True)
+        if jpeg_quality is not None:
+            out = byte_frames.jpeg_encode_u8(out, jpeg_quality, '420', 'row')
         torch.cuda.current_stream(dev).synchronize()
         return out
 

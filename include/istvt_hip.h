@@ -409,6 +409,38 @@ typedef struct istvt_jpeg_decode_args {
     int n, nseg, nq, nh, Hc, Wc;
 } istvt_jpeg_decode_args;
 int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a);
+/* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
+ * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
+ * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
+ * the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none; 0..65535).  All frames of a call share H, W,
+ * subsampling and restart interval; quality int32 [n] on the device is per frame.  Four launches (coefficients; one lane per
+ * restart interval counts; one workgroup takes the prefix sum; the same lanes store), no synchronisation, no global state,
+ * nothing allocated.
+ *   header     the bytes SOI .. SOS header that every file of the call starts with (clips.jpeg_header), on the device; the 64
+ *              bytes at dqt0 and at dqt1 are the two quantisation tables, filled per frame from its quality
+ *   scratch    16-byte aligned, 128 bytes per 8 x 8 block (int16 coefficients in zig-zag order; per frame the blocks of Y row
+ *              by row of the plane padded to whole MCUs, then Cb's, then Cr's) + 16 bytes per restart interval
+ *   data       uint8 [capacity], no overlap with frames;  offsets int64 [n + 1]: file i is data[offsets[i] .. offsets[i + 1])
+ *   status     int32 [n]: 0 fine | 1 the file does not fit in data: nothing of it is written, offsets still hold the true
+ *              sizes, so offsets[n] is the capacity a retry needs | 2 quality <= 0: an empty file | 3 a coefficient outside
+ *              baseline's categories, coded clamped (not reachable from 8-bit samples)
+ * Returns -3 before any launch on a null pointer, a bad count or size, a scratch too small or misaligned, or an overlap. */
+typedef struct istvt_jpeg_encode_args {
+    const void* frames;
+    long total;
+    const int* quality;
+    const void* header;
+    long header_bytes;
+    void* scratch;
+    long scratch_bytes;
+    void* data;
+    long capacity;
+    long* offsets;
+    int* status;
+    istvt_stream_t stream;
+    int n, H, W, subsampling, restart_interval, dqt0, dqt1;
+} istvt_jpeg_encode_args;
+int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

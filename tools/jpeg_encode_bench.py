@@ -1,0 +1,173 @@
+#!/usr/bin/env python3
+"""JPEG files out (DESIGN.md "JPEG files out") on one GPU in one process: ops.jpeg_encode_u8 on one training step's frames.
+
+    python tools/jpeg_encode_bench.py [--frames 256] [--size 224] [--out profiles/NAME.txt]
+
+--frames frames of --size x --size: 8 distinct smooth_image frames (tests/golden/make_jpeg_golden.py's recipe) repeated, on
+the device; quality 75 and 90, 4:2:0, restart interval 'row' and 0.  Per configuration, after checking two distinct files
+against clips.jpeg_encode_host:
+
+encode   ops.jpeg_encode_u8 into the caller's buffer, events around the call (four launches); alternating with
+         ops.jpeg_roundtrip_u8 on the same frames as the yardstick; medians and min-max over the repeats after the warm-up
+download data[:offsets[n]] against the raw frames (3 bytes per pixel), both into pinned memory, host clock around copy +
+         synchronise
+decode   ops.jpeg_decode_u8 on the encoder's own 'row' files (parsed and packed on the host beforehand), checked against
+         ops.jpeg_roundtrip_u8
+
+and last one batch of 1080 x 1920 frames, as VideoScorer.render_explanation(jpeg_quality=75) encodes them: 4:2:0, 'row'.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import istvt_pkg  # noqa: E402
+
+istvt_pkg.load()
+from istvt_amd import clips, ops  # noqa: E402
+
+DISTINCT = 8
+QUALITIES = (75, 90)
+
+
+def smooth_image(h, w, seed):
+    g = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h, 0:w]
+    planes = [128 + 80 * np.sin(x / 5.0 + c) * np.cos(y / 7.0 + 2 * c) for c in range(3)]
+    return np.clip(np.round(np.stack(planes, -1) + g.normal(0.0, 12.0, (h, w, 3))), 0, 255).astype(np.uint8)
+
+
+def event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def stats(ts):
+    return {'median_ms': statistics.median(ts), 'min_ms': min(ts), 'max_ms': max(ts)}
+
+
+def fmt(s):
+    return '%.3f ms (%.3f-%.3f)' % (s['median_ms'], s['min_ms'], s['max_ms'])
+
+
+def say(lines, text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def alternate(a, first, second):
+    ta, tb = [], []
+    for r in range(a.warmup + a.reps):
+        x, y = event_ms(first), event_ms(second)
+        if r >= a.warmup:
+            ta.append(x)
+            tb.append(y)
+    return stats(ta), stats(tb)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--frames', type=int, default=256)
+    ap.add_argument('--size', type=int, default=224)
+    ap.add_argument('--reps', type=int, default=15)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--big', type=int, default=4, help='frames of the 1080 x 1920 batch (0: skip it)')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_encode_bench.py measures on a GPU; none is visible')
+    n, S = a.frames, a.size
+    lines, res = [], {}
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    raw_dev = src.repeat((-(-n // DISTINCT), 1, 1, 1))[:n].contiguous().cuda()
+    raw_host = torch.empty(raw_dev.shape, dtype=torch.uint8).pin_memory()
+    rt_out = torch.empty_like(raw_dev)
+    data = torch.empty((raw_dev.numel(),), dtype=torch.uint8, device=raw_dev.device)
+    for q in QUALITIES:
+        qdev = torch.full((n,), q, dtype=torch.int32, device=raw_dev.device)
+        for ri in ('row', 0):
+            enc = ops.jpeg_encode_u8(raw_dev, qdev, '420', ri, out=data, checked=True)
+            files = enc.files()
+            for i in (0, DISTINCT - 1):
+                if files[i] != clips.jpeg_encode_host(src[i], q, '420', ri) or files[n - DISTINCT + i] != files[i]:
+                    raise SystemExit('q=%d ri=%s: file %d is not the definition' % (q, ri, i))
+            total = enc.nbytes()
+            se, sr = alternate(a, lambda: ops.jpeg_encode_u8(raw_dev, qdev, '420', ri, out=data, checked=True),
+                               lambda: ops.jpeg_roundtrip_u8(raw_dev, qdev, '420', out=rt_out, checked=True))
+            file_host = torch.empty((total,), dtype=torch.uint8).pin_memory()
+            tf, tw = [], []
+            for r in range(a.warmup + a.reps):
+                x = timed(lambda: file_host.copy_(data[:total], non_blocking=True))
+                y = timed(lambda: raw_host.copy_(raw_dev, non_blocking=True))
+                if r >= a.warmup:
+                    tf.append(x)
+                    tw.append(y)
+            sf, sw = stats(tf), stats(tw)
+            key = 'q%d_%s' % (q, ri)
+            res[key] = {'frames': n, 'size': S, 'file_bytes': total, 'raw_bytes': raw_dev.numel(), 'encode': se, 'roundtrip': sr,
+                        'download_files': sf, 'download_raw': sw}
+            say(lines, "jpeg_encode_u8 q=%d, restart interval %s: %d frames of %d x %d | %s = %.2f us per frame | jpeg_roundtrip_u8 on "
+                'the same frames %s | files %.2f MB against %.2f MB raw = 1 / %.1f: to pinned memory %s against %s'
+                % (q, ri, n, S, S, fmt(se), se['median_ms'] * 1e3 / n, fmt(sr), total * 1e-6, raw_dev.numel() * 1e-6,
+                   raw_dev.numel() / total, fmt(sf), fmt(sw)))
+            if ri == 'row':                                       # the decoder on the encoder's own files
+                batch = clips.jpeg_batch(files)
+                dev = raw_dev.device
+                buffers = (torch.empty((batch.scratch_bytes,), dtype=torch.uint8, device=dev),
+                           torch.empty((n, 2), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+                out = torch.empty_like(raw_dev)
+                got, _, status = ops.jpeg_decode_u8(batch, out=out, checked=True, buffers=buffers)
+                clips.check_jpeg_status(status)
+                if not torch.equal(got, ops.jpeg_roundtrip_u8(raw_dev, qdev, '420', checked=True)):
+                    raise SystemExit('q=%d: decoding the encoder\'s files is not the round trip' % q)
+                sd, _ = alternate(a, lambda: ops.jpeg_decode_u8(batch, out=out, checked=True, buffers=buffers),
+                                  lambda: ops.jpeg_roundtrip_u8(raw_dev, qdev, '420', out=rt_out, checked=True))
+                res[key]['decode'] = sd
+                res[key]['segments'] = int(batch.segments.shape[0])
+                say(lines, "jpeg_decode_u8 on these files (%d segments): %s" % (res[key]['segments'], fmt(sd)))
+    if a.big:
+        frame = torch.from_numpy(smooth_image(1080, 1920, 1080))
+        big = frame[None].repeat(a.big, 1, 1, 1).contiguous().cuda()
+        qdev = torch.full((a.big,), 75, dtype=torch.int32, device=big.device)
+        data = torch.empty((big.numel(),), dtype=torch.uint8, device=big.device)
+        rt_out = torch.empty_like(big)
+        enc = ops.jpeg_encode_u8(big, qdev, '420', 'row', out=data, checked=True)
+        files = enc.files()
+        got, _, status = ops.jpeg_decode_u8(files[:1])
+        clips.check_jpeg_status(status)
+        if not torch.equal(got, ops.jpeg_roundtrip_u8(big[:1], 75, '420')) or any(f != files[0] for f in files):
+            raise SystemExit('1080 x 1920: decoding the file is not the round trip')
+        se, sr = alternate(a, lambda: ops.jpeg_encode_u8(big, qdev, '420', 'row', out=data, checked=True),
+                           lambda: ops.jpeg_roundtrip_u8(big, qdev, '420', out=rt_out, checked=True))
+        res['big'] = {'frames': a.big, 'file_bytes': enc.nbytes(), 'raw_bytes': big.numel(), 'encode': se, 'roundtrip': sr}
+        say(lines, "jpeg_encode_u8 q=75, restart interval row: %d frames of 1080 x 1920 | %s = %.3f ms per frame | jpeg_roundtrip_u8 %s "
+            '| files %.2f MB against %.2f MB raw = 1 / %.1f'
+            % (a.big, fmt(se), se['median_ms'] / a.big, fmt(sr), enc.nbytes() * 1e-6, big.numel() * 1e-6, big.numel() / enc.nbytes()))
+    line = json.dumps({'jpeg_encode_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
+if __name__ == '__main__':
+    main()
