@@ -94,7 +94,7 @@ def rows(t: Tensor) -> Tuple[Tensor, int]:
     return t2, t2.stride(0)
 
 
-G256_MIN = 64          # smallest output edge routed to the 256x256 DMA GEMM (mirrors ISTVT_G256_MIN in gemm.hip)
+G256_MIN = 64          # smallest output edge routed to the 256x256 DMA GEMM (ISTVT_G256_MIN of include/istvt_hip.h)
 
 
 def cast(t: Tensor, dtype: torch.dtype) -> Tensor:

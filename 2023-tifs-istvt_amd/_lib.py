@@ -28,7 +28,8 @@ class JpegEncodeArgs(ctypes.Structure):
                 ('H', I), ('W', I), ('subsampling', I), ('restart_interval', I), ('dqt0', I), ('dqt1', I)]
 
 
-# name -> argtypes (all return int).  Mirrors include/istvt_hip.h one to one.
+# name -> argtypes (all return int).  Written by hand, one line per prototype of include/istvt_hip.h;
+# tests/test_abi_cpu.py parses the header and compares the two type by type.
 SIGNATURES = {
     'istvt_gemm': [P, L, I, P, L, I, P, L, I, I, I, P, P, L, P, I, I, I, F, P, P, I, I, P],
     'istvt_layernorm_fwd': [P, L, P, P, P, L, P, P, L, I, F, I, P],

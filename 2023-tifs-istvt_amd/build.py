@@ -3,7 +3,8 @@
     python 2023-tifs-istvt_amd/build.py [--force]
 
 No torch dependency: plain `hipcc --offload-arch=gfx950 -fPIC -shared`.  Object files are
-cached under csrc/build/ and rebuilt when a source or header is newer.
+cached under csrc/build/ and rebuilt when a source or header is newer.  The sources are compiled
+against the public header include/istvt_hip.h, which declares what they define.
 """
 import os
 import subprocess
@@ -14,8 +15,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libistvt_hip.so')
+INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-Wno-inline-asm', '-ffp-contract=fast'] + os.environ.get('ISTVT_EXTRA_HIPCC_FLAGS', '').split()
+FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wno-unused-result', '-Wno-inline-asm', '-ffp-contract=fast', '-I', INCLUDE] + os.environ.get('ISTVT_EXTRA_HIPCC_FLAGS', '').split()
 
 
 def _sources():
@@ -23,7 +25,8 @@ def _sources():
 
 
 def _newest_header():
-    return max([os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith('.h')] + [0.0])
+    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(INCLUDE, 'istvt_hip.h')]
+    return max(os.path.getmtime(h) for h in headers)
 
 
 def _compile(src):

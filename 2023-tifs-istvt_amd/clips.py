@@ -494,9 +494,10 @@ JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 2
                35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
                62, 63)                                  # natural index of the k-th coefficient of a block (T.81 figure A.6)
 JPEG_MAX_SIDE = 16384
+# the ISTVT_JPEG_* sizes of include/istvt_hip.h (tests/test_abi_cpu.py holds the two together)
 JPEG_HUFF_INTS = 288                        # a decode table: limit[16], offset[16], values[256] (csrc/jpeg_entropy.h)
 JPEG_IMAGE_INTS = 20                        # a row of the per-image table
-JPEG_IDCT_BLOCKS = 24                       # blocks per workgroup of the IDCT kernel (JP_BLOCKS of csrc/jpeg.hip)
+JPEG_IDCT_BLOCKS = 24                       # blocks per workgroup of the IDCT kernel
 
 
 def _std_ac(head, runs):

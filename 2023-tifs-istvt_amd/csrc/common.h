@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the declaration of every entry point, argument block and return code: the definitions are compiled against it
+#include "istvt_hip.h"
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -17,11 +19,6 @@ typedef short short4v __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define ISTVT_OK 0
-#define ISTVT_ERR_DTYPE (-2)
-#define ISTVT_ERR_SHAPE (-3)
-#define ISTVT_ERR_LAUNCH (-4)
 
 enum { DT_F32 = 0, DT_BF16 = 1 };
 

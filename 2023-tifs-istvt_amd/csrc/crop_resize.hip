@@ -19,6 +19,7 @@
 // Further down: whole NV12 frames to packed RGB (DESIGN.md "NV12 frames"), and the similarity warp (DESIGN.md "Aligned
 // crops"), a second kernel over the same two sources: one 2 x 3 map per frame instead of a box, the same triangle in the
 // rotated frame of the output, in double.
+#include "istvt_hip.h"
 #include "u8_view.h"
 
 namespace {

@@ -125,11 +125,10 @@ __device__ __forceinline__ gf2 gelu_grad_fast2(gf2 u) {
 #include "gemm256q.h"
 #include "gemm256t.h"
 
-// Smallest output edge sent to the 256x256 DMA kernels.  Narrow outputs (the stem's 64/128-channel
-// pointwise convs over ~3 M pixels, K <= 288) waste MFMA lanes in a 256-wide tile, but those GEMMs
+// ISTVT_G256_MIN (istvt_hip.h): smallest output edge sent to the 256x256 DMA kernels.  Narrow outputs (the stem's
+// 64/128-channel pointwise convs over ~3 M pixels, K <= 288) waste MFMA lanes in a 256-wide tile, but those GEMMs
 // are HBM-bound: what matters is streaming A once with full-line DMA and storing C in 16-byte
 // row segments, which the 128x128 register-staged kernel does not do.
-constexpr int ISTVT_G256_MIN = 64;
 
 template <typename T> struct Tile { static constexpr int BK = 32; };
 template <> struct Tile<bf16_t> { static constexpr int BK = 64; };

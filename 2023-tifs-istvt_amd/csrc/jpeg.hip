@@ -31,6 +31,7 @@
 // files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
 // jpeg_count_kernel / jpeg_write_kernel: one lane per restart interval (jpeg_entropy_enc.h), first counting, then storing.
 // jpeg_offsets_kernel between them: the prefix sum that lays the files end to end.
+#include "istvt_hip.h"
 #include "jpeg_entropy.h"
 #include "jpeg_entropy_enc.h"
 #include "u8_view.h"
@@ -38,7 +39,7 @@
 namespace {
 
 constexpr int JP_TILE_W = 64;               // pixels per tile row: 8 blocks of Y
-constexpr int JP_BLOCKS = 24;               // 8 x 8 blocks of a tile, either subsampling
+constexpr int JP_BLOCKS = ISTVT_JPEG_IDCT_BLOCKS;  // 8 x 8 blocks of a tile, either subsampling
 constexpr int JP_BLOCK_LD = 72;             // ints between blocks in LDS: 64 + 8, so a column pass meets no bank twice
 constexpr int JP_PITCH = 208;               // u8_row_pitch(JP_TILE_W)
 
@@ -360,30 +361,11 @@ extern "C" int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, in
 // ---- JPEG files ----------------------------------------------------------------------------------------------------------
 // A row of the per-image table (clips.JpegBatch.images) and of the per-segment table
 enum { JD_H = 0, JD_W, JD_SUB, JD_MCUX, JD_MCUY, JD_QUANT, JD_HUFF = 8, JD_BLOCK0 = 14, JD_GROUP0, JD_SEG0, JD_NSEG, JD_NBLOCKS };
-constexpr int JD_IMAGE_INTS = 20;
-constexpr int JD_SEGMENT_INTS = 5;          // image, first byte, end byte, first MCU, MCUs
+constexpr int JD_IMAGE_INTS = ISTVT_JPEG_IMAGE_INTS;
+constexpr int JD_SEGMENT_INTS = ISTVT_JPEG_SEGMENT_INTS;  // image, first byte, end byte, first MCU, MCUs
 // the scratch, for B blocks in the batch and s segments: int16 coefficients [B][64] | planes, 64 B bytes, per image Y
 // [Hp][Wp], Cb, Cr [Hp / sub][Wp / sub] as the round trip lays them out | int32 status [s]
 constexpr long JD_BLOCK_BYTES = 128 + 64;
-
-/* the argument block of istvt_jpeg_decode_u8 (include/istvt_hip.h) */
-struct istvt_jpeg_decode_args {
-    const void* bytes;
-    long nbytes;
-    const int* images;
-    const int* images_host;
-    const int* segments;
-    const int* segments_host;
-    const int* qtabs;
-    const int* htabs;
-    void* scratch;
-    long scratch_bytes;
-    void* out;
-    int* sizes;
-    int* status;
-    hipStream_t stream;
-    int n, nseg, nq, nh, Hc, Wc;
-};
 
 namespace {
 
@@ -641,23 +623,6 @@ extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
 // clips.jpeg_encode_host.  Four launches: jpeg_planes_kernel<SUB, true> (coefficients) | jpeg_count_kernel (one lane per
 // restart interval: its length) | jpeg_offsets_kernel (one workgroup: where every file and segment starts, the statuses) |
 // jpeg_write_kernel (the same lanes store; one workgroup per image copies the header).
-
-/* the argument block of istvt_jpeg_encode_u8 (include/istvt_hip.h) */
-struct istvt_jpeg_encode_args {
-    const void* frames;
-    long total;
-    const int* quality;
-    const void* header;
-    long header_bytes;
-    void* scratch;
-    long scratch_bytes;
-    void* data;
-    long capacity;
-    long* offsets;
-    int* status;
-    hipStream_t stream;
-    int n, H, W, subsampling, restart_interval, dqt0, dqt1;
-};
 
 namespace {
 

@@ -14,6 +14,7 @@
 
 #include <stdint.h>
 
+#include "istvt_hip.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define JE_HD __host__ __device__ __forceinline__
@@ -22,7 +23,7 @@
 #endif
 
 // a Huffman table in decode form (clips.jpeg_huffman_table): limit[16], offset[16], values[256]
-constexpr int JE_HUFF_INTS = 288;
+constexpr int JE_HUFF_INTS = ISTVT_JPEG_HUFF_INTS;
 
 struct JeBits {
     const uint8_t* data;

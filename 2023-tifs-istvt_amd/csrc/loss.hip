@@ -24,15 +24,8 @@ namespace {
 
 constexpr int BCE_MAX_THREADS = 1024;
 constexpr long BCE_MAX_N = 1l << 30;        // per-call counts are 32-bit inside the kernel
-enum { Y_F32 = 0, Y_I64 = 1, Y_I32 = 2, Y_U8 = 3 };
-enum { RED_NONE = 0, RED_MEAN = 1, RED_SUM = 2 };
 
-// the meter block of include/istvt_hip.h (istvt_loss_meter): ten 8-byte words
-struct Meter {
-    double loss_sum;
-    double batch_loss_sum;
-    long long seen, correct, tp, tn, fp, fn, calls, reserved;
-};
+using Meter = istvt_loss_meter;
 static_assert(sizeof(Meter) == 80, "istvt_loss_meter is ten 8-byte words");
 
 struct Partial {
@@ -41,9 +34,9 @@ struct Partial {
 };
 
 template <int KIND> __device__ __forceinline__ float load_target(const void* y, long i) {
-    if (KIND == Y_F32) return ((const float*)y)[i];
-    if (KIND == Y_I64) return (float)((const long long*)y)[i];
-    if (KIND == Y_I32) return (float)((const int*)y)[i];
+    if (KIND == ISTVT_TARGET_F32) return ((const float*)y)[i];
+    if (KIND == ISTVT_TARGET_I64) return (float)((const long long*)y)[i];
+    if (KIND == ISTVT_TARGET_I32) return (float)((const int*)y)[i];
     return (float)((const unsigned char*)y)[i];
 }
 
@@ -55,7 +48,7 @@ __global__ __launch_bounds__(BCE_MAX_THREADS) void bce_logits_kernel(const float
                                                                      float* __restrict__ d, Meter* meter) {
     __shared__ Partial part[BCE_MAX_THREADS];
     const int tid = threadIdx.x, T = blockDim.x;
-    const float dscale = reduction == RED_MEAN ? 1.0f / (float)n : 1.0f;
+    const float dscale = reduction == ISTVT_REDUCE_MEAN ? 1.0f / (float)n : 1.0f;
     Partial acc = {0.0, 0u, 0u, 0u, 0u};
 #pragma unroll 4
     for (long i = tid; i < n; i += T) {
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(BCE_MAX_THREADS) void bce_logits_kernel(const float
     if (tid == 0) {
         const Partial tot = part[0];
         // what the caller gets back is what the meter adds up: the value rounded to fp32 once (mean divides by n, as torch)
-        const float out = (float)(reduction == RED_MEAN ? tot.loss / (double)n : tot.loss);
+        const float out = (float)(reduction == ISTVT_REDUCE_MEAN ? tot.loss / (double)n : tot.loss);
         if (reduced) *reduced = out;
         if (meter) {
             meter->loss_sum += tot.loss;
@@ -124,19 +117,19 @@ extern "C" int istvt_bce_logits(const float* z, long stride, const void* y, int 
                                 float label_smoothing, int reduction, float threshold, long n, float* loss, float* reduced,
                                 float* d, void* meter, hipStream_t stream) {
     if (!z || !y || n < 1 || n > BCE_MAX_N || stride < 1) return ISTVT_ERR_SHAPE;
-    if (reduction < RED_NONE || reduction > RED_SUM) return ISTVT_ERR_SHAPE;
+    if (reduction < ISTVT_REDUCE_NONE || reduction > ISTVT_REDUCE_SUM) return ISTVT_ERR_SHAPE;
     if (!(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return ISTVT_ERR_SHAPE;
-    if (y_kind < Y_F32 || y_kind > Y_U8) return ISTVT_ERR_DTYPE;
+    if (y_kind < ISTVT_TARGET_F32 || y_kind > ISTVT_TARGET_U8) return ISTVT_ERR_DTYPE;
     int T = 64;
     while (T < BCE_MAX_THREADS && T < n) T <<= 1;
 #define BCE_LAUNCH(KIND)                                                                                                   \
     hipLaunchKernelGGL(bce_logits_kernel<KIND>, dim3(1), dim3((unsigned)T), 0, stream, z, stride, y, w, pos_weight,         \
                        label_smoothing, reduction, threshold, n, loss, reduced, d, (Meter*)meter)
     switch (y_kind) {
-        case Y_F32: BCE_LAUNCH(Y_F32); break;
-        case Y_I64: BCE_LAUNCH(Y_I64); break;
-        case Y_I32: BCE_LAUNCH(Y_I32); break;
-        default: BCE_LAUNCH(Y_U8); break;
+        case ISTVT_TARGET_F32: BCE_LAUNCH(ISTVT_TARGET_F32); break;
+        case ISTVT_TARGET_I64: BCE_LAUNCH(ISTVT_TARGET_I64); break;
+        case ISTVT_TARGET_I32: BCE_LAUNCH(ISTVT_TARGET_I32); break;
+        default: BCE_LAUNCH(ISTVT_TARGET_U8); break;
     }
 #undef BCE_LAUNCH
     return istvt_check_launch();

@@ -100,15 +100,9 @@ inline int opt_grid(long n, int per_thread) {
     return b < 1 ? 1 : (int)b;
 }
 
-// ---- the step-info block (device memory, 8 x 32-bit words; include/istvt_hip.h) ------------------------------------------
-struct StepInfo {
-    float total_norm;       // || grad_scale * g ||_2 of the last istvt_grad_norm
-    float scale;            // what the update multiplies g by: grad_scale x min(1, max_norm / (total_norm + 1e-6)); 0 when skipped
-    int finite;             // the norm is finite
-    int applied_steps;      // skip mode only: steps whose norm was finite (this one included) ...
-    int skipped_steps;      // ... and steps that were skipped
-    int reserved[3];
-};
+// ---- the step-info block (device memory, 8 x 32-bit words) ---------------------------------------------------------------
+using StepInfo = istvt_step_info;
+static_assert(sizeof(StepInfo) == 32, "istvt_step_info is eight 32-bit words");
 
 // fp64 sum over the workgroup in a fixed order: lanes by a shuffle tree, then the four wavefronts in index order.
 // Valid in thread 0.

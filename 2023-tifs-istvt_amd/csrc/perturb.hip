@@ -19,6 +19,7 @@
 // tile meets (pixelate), cut to the frame, with u8_stage_rows, and works in LDS: blur = horizontal pass bytes -> int32 plane,
 // unrounded, then vertical pass plane -> bytes; pixelate = row sums per block, block values, look-up.  A workgroup whose frame
 // is not of its kernel's kinds returns at once.
+#include "istvt_hip.h"
 #include "philox.h"
 #include "u8_view.h"
 

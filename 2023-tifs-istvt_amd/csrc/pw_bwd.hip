@@ -39,8 +39,6 @@
 #include "common.h"
 #include "bn_bwd.h"
 
-extern "C" int istvt_splitk_reduce(const float* ws, int splits, long n, float* out, hipStream_t stream);
-
 constexpr int PW_R = 128;           // rows per block
 constexpr int PW_THREADS = 512;
 

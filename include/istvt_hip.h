@@ -10,11 +10,14 @@
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch allocates everything);
  *     kernels never allocate, free, or retain pointers, and only enqueue on `stream`
- *     (hipStream_t passed as void*; no host synchronisation).
+ *     (istvt_stream_t is HIP's own hipStream_t, spelled out below so that this header needs no HIP include and stays
+ *     valid C; no host synchronisation).  libistvt_hip.so is compiled against this header: a definition that
+ *     disagrees with its prototype here does not build.
  *   - `dtype`: storage type of activations: 0 = float32 (parity mode), 1 = bfloat16.
  *     Parameters, statistics, parameter gradients and all accumulation are float32.
- *   - return value: 0 = ok; -2 = bad dtype; -3 = bad shape/argument; -(1000+e) = hipError_t e
- *     raised by the launch.  Nothing throws, nothing exits.
+ *   - return value: ISTVT_OK (0); ISTVT_ERR_DTYPE (-2) = bad dtype; ISTVT_ERR_SHAPE (-3) = bad shape/argument;
+ *     ISTVT_ERR_LAUNCH (-4) = the runtime refused to prepare a launch (a kernel's dynamic-LDS limit could not be raised);
+ *     -(1000+e) = hipError_t e raised by the launch.  Nothing throws, nothing exits.
  *   - "accumulate" outputs (parameter gradients) are added to, so the caller zeroes them
  *     (they are the .grad buffers).
  *   - row-major everywhere; activations of the transformer are [M = B*F*P][D] with rows
@@ -35,7 +38,12 @@
 extern "C" {
 #endif
 
-typedef void* istvt_stream_t; /* hipStream_t */
+typedef struct ihipStream_t* istvt_stream_t; /* HIP's definition of hipStream_t */
+
+#define ISTVT_OK 0
+#define ISTVT_ERR_DTYPE (-2)
+#define ISTVT_ERR_SHAPE (-3)
+#define ISTVT_ERR_LAUNCH (-4)
 
 #define ISTVT_F32 0
 #define ISTVT_BF16 1
@@ -77,6 +85,9 @@ typedef void* istvt_stream_t; /* hipStream_t */
  *           the stem backward, train_CNN.py:185-186 -> parallel.GradBucket), so that every persistent workgroup is resident
  *           at once instead of queueing behind a whole tile list.  An argument of each launch: the library keeps no state
  *           (results are bit-identical for every value: one workgroup computes an output tile in one fixed order). */
+/* Smallest output edge (M and N of a bf16 forward, N_i and K_i of a weight gradient) that goes to the 256x256 LDS-DMA
+ * kernels; the host routes by it too (weight copies, grouped weight gradients, workspace sizes). */
+#define ISTVT_G256_MIN 64
 int istvt_gemm(const void* A, long lda, int a_kc, const void* B, long ldb, int b_kc, void* C, long ldc, int M, int N,
                int K, const float* bias, const void* residual, long ldr, void* C2, int epi, int out_mode, int splitk,
                float alpha, double* col_sum, double* col_sumsq, int flags, int dtype, istvt_stream_t stream);
@@ -391,6 +402,10 @@ int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W,
  * images_host / segments_host are host copies of the two tables: the entry checks them against the counts, nbytes, the
  * canvas and each other before any launch and returns -3 on a null pointer, a bad count, a canvas smaller than an image,
  * an out that overlaps bytes or an inconsistent table.  Every other pointer is a device pointer. */
+#define ISTVT_JPEG_IMAGE_INTS 20   /* a row of images */
+#define ISTVT_JPEG_SEGMENT_INTS 5  /* a row of segments */
+#define ISTVT_JPEG_HUFF_INTS 288   /* a table of htabs */
+#define ISTVT_JPEG_IDCT_BLOCKS 24  /* blocks per IDCT workgroup: what "first IDCT workgroup" of an images row counts in */
 typedef struct istvt_jpeg_decode_args {
     const void* bytes;
     long nbytes;
@@ -565,14 +580,17 @@ int istvt_adamw(float* p, float* g, float* m, float* v, long n, float lr, float 
  * order: every workgroup reduces one contiguous chunk (fp32 per lane over 16 elements, fp64 from there on) into one double
  * of ws (>= istvt_grad_norm_ws_elems(n) doubles), one workgroup sums those.  Chunk and grid depend on n alone and there are
  * no atomics: the same bucket gives the same bits on every rank and in every run.  The second stage writes the STEP-INFO
- * BLOCK `info` (device memory, 8 x 32-bit words):
- *   [0] float total_norm
- *   [1] float scale: what the step multiplies g by -- grad_scale x min(1, max_norm / (total_norm + 1e-6)), torch's
- *       clip_grad_norm_ coefficient; just grad_scale with max_norm <= 0; 0 for a skipped step
- *   [2] int finite: total_norm is finite
- *   [3] int applied_steps, [4] int skipped_steps: touched only with skip_nonfinite != 0 -- a non-finite norm counts as a
- *       skipped step, any other as an applied one (the caller zeroes the block once, or sets [3] when it resumes a run)
- *   [5..7] reserved */
+ * BLOCK `info` (device memory, 8 x 32-bit words). */
+typedef struct istvt_step_info {
+    float total_norm;  /* || grad_scale * g ||_2 */
+    float scale;       /* what the step multiplies g by -- grad_scale x min(1, max_norm / (total_norm + 1e-6)), torch's
+                          clip_grad_norm_ coefficient; just grad_scale with max_norm <= 0; 0 for a skipped step */
+    int finite;        /* total_norm is finite */
+    int applied_steps; /* with skipped_steps touched only with skip_nonfinite != 0 -- a non-finite norm counts as a skipped */
+    int skipped_steps; /* step, any other as an applied one (the caller zeroes the block once, or sets applied_steps when it
+                          resumes a run) */
+    int reserved[3];
+} istvt_step_info;
 int istvt_grad_norm(const float* g, long n, float grad_scale, float max_norm, int skip_nonfinite, double* ws,
                     long ws_elems, void* info, istvt_stream_t stream);
 int istvt_grad_norm_ws_elems(long n);

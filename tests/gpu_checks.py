@@ -1390,7 +1390,7 @@ def attn_spatial_fp8_refusals(BF=2, P=37, heads=2, dh=32):
                                         delta.data_ptr(), dqkv.data_ptr(), BF, P, heads, dh, dh ** -0.5,
                                         ops._DT[torch.float32], ops._stream())
     torch.cuda.synchronize()
-    # -2 is ISTVT_ERR_DTYPE (csrc/common.h; the return codes are listed in include/istvt_hip.h)
+    # -2 is ISTVT_ERR_DTYPE (include/istvt_hip.h)
     ok = rc_f == -2 and rc_b == -2 and all(bool((t == 7.0).all()) for t in (out, lse, dqkv, delta))
     return (0.0 if ok else 1.0), 0.0
 

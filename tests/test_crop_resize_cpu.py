@@ -162,14 +162,3 @@ def test_scorer_argument_errors_need_no_device(pkg):
     model.set_crop_side(32)                                                  # the model's side is the default
     with pytest.raises(RuntimeError, match='ROCm'):                          # the arguments pass: the next stop is the device
         video.VideoScorer(model).score(frames, boxes=boxes)
-
-
-def test_symbol_declared_bound_and_exported(pkg):
-    import os
-    from istvt_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, 'include', 'istvt_hip.h')) as fh:
-        assert 'int istvt_crop_resize_u8(' in fh.read()
-    assert 'istvt_crop_resize_u8' in _lib.SIGNATURES
-    if os.path.exists(_lib.LIB_PATH):
-        assert hasattr(_lib.lib(), 'istvt_crop_resize_u8')

@@ -1,11 +1,9 @@
 """Fused optimizers, host side: the segment table of the grouped step kernels and the argument
 checks of parameter groups.  No GPU: the table is plain Python and every check fires before the optimizers ask for one."""
-import os
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(37, 5), (1001,), (8, 3, 3, 3), (3,), (1,), (4097,)]          # 185, 1001, 216, 3, 1, 4097 elements
 
 
@@ -23,10 +21,7 @@ def _params(shapes=SHAPES):
 
 def test_new_entry_points_declared_and_exported(parallel):
     from istvt_amd import _lib
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    lib = _lib.lib()
-    for name in ('istvt_grad_norm', 'istvt_grad_norm_ws_elems', 'istvt_sgd_momentum_groups', 'istvt_adamw_groups'):
-        assert name in _lib.SIGNATURES and 'int ' + name + '(' in header and hasattr(lib, name), name
+    lib = _lib.lib()                                        # (header, table and library: test_abi_cpu.py)
     # the workspace helper: one double per chunk of n, and the chunk is the constant the tests size their cases by
     c = parallel.GRAD_NORM_CHUNK
     assert [lib.istvt_grad_norm_ws_elems(n) for n in (1, c, c + 1, 3 * c + 5)] == [1, 1, 2, 4]

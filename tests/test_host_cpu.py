@@ -1,5 +1,5 @@
-"""CPU-only checks: the C-ABI library loads and exports every symbol include/istvt_hip.h
-declares, the nn.Module mirror keeps the reference's constructor surface and state-dict names,
+"""CPU-only checks: a missing library fails loudly (what it exports against the header: test_abi_cpu.py),
+the nn.Module mirror keeps the reference's constructor surface and state-dict names,
 the product path refuses to run without a GPU (no fallback), and the data-parallel gradient
 bucket is correct across 2 gloo ranks."""
 import json
@@ -19,20 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def pkg():
     import istvt_pkg
     return istvt_pkg.load()
-
-
-def test_library_exports_every_declared_symbol(pkg):
-    from istvt_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    lib = _lib.lib()                                  # resolves all SIGNATURES or raises
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    declared = set(re.findall(r'\bint\s+(istvt_\w+)\s*\(', header))
-    assert declared, 'no declarations parsed'
-    for name in sorted(declared):
-        assert hasattr(lib, name), 'libistvt_hip.so lacks %s declared in include/istvt_hip.h' % name
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
 
 
 def test_missing_library_fails_loudly(pkg, tmp_path, monkeypatch):
@@ -464,8 +450,6 @@ def test_cu_reserve_is_a_launch_argument_not_library_state(pkg):
     rc = lib.istvt_gemm(None, 64, 1, None, 64, 1, None, 256, 256, 256, 64, None, None, 0, None, 0, 0, 1, 1.0, None, None,
                         25 << 8, 1, None)
     assert rc == -3
-
-
 
 
 def test_bench_n1_record_round_trip(tmp_path, monkeypatch):

@@ -6,7 +6,6 @@ import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((16, 16), (24, 40), (17, 33), (48, 48))
 CASES = [(2, q) for q in (30, 50, 75, 90)] + [(0, 75)]         # (PIL's subsampling number, quality)
 NAMES = {2: '420', 0: '444'}
@@ -148,14 +147,8 @@ def test_check_qualities(clips):
 
 
 def test_entry_point_declared_and_exported(clips):
-    import re
-    from istvt_amd import _lib, ops, video
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    name = 'istvt_jpeg_roundtrip_u8'
-    assert name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-    m = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)', header)
-    assert m and len(m.group(1).split(',')) == len(_lib.SIGNATURES[name])                   # same arity in header and table
-    assert callable(ops.jpeg_roundtrip_u8)
+    from istvt_amd import ops, video
+    assert callable(ops.jpeg_roundtrip_u8)                  # (header, table and library: test_abi_cpu.py)
     with pytest.raises(RuntimeError):
         ops.jpeg_roundtrip_u8(torch.zeros((1, 8, 8, 3), dtype=torch.uint8), 50)            # a CPU tensor: no fallback
     import inspect

@@ -2,13 +2,11 @@
 fixture file, the parser's fields and refusals, the statuses of the damaged files, the encode / decode / round-trip identity,
 the tables of a packed batch, and the entry point's declaration."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((1, 1), (8, 8), (16, 16), (17, 33), (24, 40), (33, 70), (48, 48))
 VARIANTS = ('q30', 'q75', 'q95', 'q100', 'q75_opt', 'q75_rb1', 'q75_rr1')
 
@@ -219,13 +217,7 @@ def test_batch_tables_and_whole_boxes(clips, files):
 def test_entry_point_declared_and_exported(clips):
     import ctypes
     from istvt_amd import _lib, frames, ops
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    name = 'istvt_jpeg_decode_u8'
-    assert _lib.SIGNATURES[name] == [ctypes.POINTER(_lib.JpegDecodeArgs)] and hasattr(_lib.lib(), name)
-    assert re.search(r'\bint\s+' + name + r'\s*\(const istvt_jpeg_decode_args\* a\);', header)
-    body = re.search(r'typedef struct istvt_jpeg_decode_args \{(.*?)\} istvt_jpeg_decode_args;', header, re.S).group(1)
-    declared = [w for line in body.split(';') for w in re.findall(r'(\w+)\s*(?:,|$)', line.strip())]
-    assert declared == [f[0] for f in _lib.JpegDecodeArgs._fields_]
+    # (header, table, argument block and library: test_abi_cpu.py)
     assert ops.jpeg_decode_u8 is frames.jpeg_decode_u8 and ops.decode_frames is frames.decode_frames
     assert _lib.lib().istvt_jpeg_decode_u8(None) == -3                                   # no block: refused, nothing launched
     args = _lib.JpegDecodeArgs(n=1, nseg=1, nq=1, nh=1, Hc=8, Wc=8)

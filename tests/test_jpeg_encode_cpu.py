@@ -1,14 +1,11 @@
 """JPEG files out (DESIGN.md "JPEG files out") without a device: the header and the 'row' restart interval factored out of
 clips.jpeg_encode_host, the batch definition, clips.JpegFiles on host tensors, the refusals of ops.jpeg_encode_u8 that need
-no device, and the entry point's declaration."""
-import ctypes
-import os
+no device, and the entry point's aliases."""
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
@@ -168,19 +165,8 @@ def test_render_explanation_refuses_nv12_with_a_quality():
 
 
 def test_entry_point_declared_and_bound(clips):
-    from istvt_amd import _lib, frames, ops
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    name = 'istvt_jpeg_encode_u8'
-    assert 'int ' + name + '(const istvt_jpeg_encode_args* a);' in header and 'typedef struct istvt_jpeg_encode_args {' in header
-    assert _lib.SIGNATURES[name] == [ctypes.POINTER(_lib.JpegEncodeArgs)] and hasattr(_lib.lib(), name)
-    # the fields of the header's struct, in order, are the ctypes structure's
-    body = header.split('typedef struct istvt_jpeg_encode_args {')[1].split('}')[0]
-    fields = []
-    for line in body.split(';'):
-        words = line.replace('*', ' ').replace(',', ' ').split()
-        if words:
-            fields += words[-1:] if line.count(',') == 0 else words[1:]
-    assert fields == [f[0] for f in _lib.JpegEncodeArgs._fields_]
+    from istvt_amd import frames, ops
+    # (header, table, argument block and library: test_abi_cpu.py)
     assert ops.jpeg_encode_u8 is frames.jpeg_encode_u8 and ops.encode_frames is frames.encode_frames
     assert max(len(line) for line in frames.jpeg_encode_u8.__doc__.splitlines()) <= 128
 

@@ -191,16 +191,3 @@ def test_encoder_round_trip_on_flat_blocks(pkg, matrix):
     d = int((back.to(torch.int32) - rgb.to(torch.int32)).abs().max())
     print('%s: max |round trip - image| = %d' % (matrix, d))
     assert d <= 2
-
-
-def test_symbols_declared_bound_and_exported(pkg):
-    import os
-    from istvt_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, 'include', 'istvt_hip.h')) as fh:
-        header = fh.read()
-    for name in ('istvt_nv12_to_rgb_u8', 'istvt_crop_resize_nv12'):
-        assert 'int %s(' % name in header
-        assert name in _lib.SIGNATURES
-        if os.path.exists(_lib.LIB_PATH):
-            assert hasattr(_lib.lib(), name)

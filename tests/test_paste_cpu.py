@@ -2,7 +2,6 @@
 geometry (clips.paste_geometry), the field against torch's bilinear upsampling, and the properties of the definition
 (clips.paste_maps_host) in packed RGB and NV12."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -39,21 +38,6 @@ def _region(clips, A, Hs, Ws, side):
     """bool (Hs, Ws): the pixels whose centre lands in the crop, from the definition's own field over the whole frame"""
     _, inside = clips.paste_field_host(torch.arange(4, dtype=torch.float32).reshape(2, 2), A, (0, 0, Hs, Ws), side)
     return inside
-
-
-def test_symbols_declared_bound_and_exported(pkg):
-    import re
-    from istvt_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, 'include', 'istvt_hip.h')) as fh:
-        header = fh.read()
-    for name in ('istvt_relevance_paste_u8', 'istvt_relevance_paste_nv12'):
-        decl = re.search(r'int %s\(([^;]*)\);' % name, header)
-        assert decl is not None, name
-        assert name in _lib.SIGNATURES
-        assert len(decl.group(1).split(',')) == len(_lib.SIGNATURES[name]), name
-        if os.path.exists(_lib.LIB_PATH):
-            assert hasattr(_lib.lib(), name)
 
 
 def test_argument_errors_need_no_device(pkg):

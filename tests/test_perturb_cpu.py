@@ -2,14 +2,11 @@
 definition clips.perturb_host, the taps, the blur against a float64 convolution, the noise statistics, per-clip tables, the
 helpers and the validation."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIGMAS = (0.5, 1.0, 2.0, 3.5)
 
 
@@ -237,17 +234,6 @@ def test_random_perturbations(clips):
             clips.random_perturbations(4, **kw)
     with pytest.raises(ValueError):
         clips.random_perturbations(0)
-
-
-def test_c_abi_declares_the_entry_point():
-    import istvt_pkg
-    istvt_pkg.load()
-    from istvt_amd import _lib
-    name = 'istvt_perturb_u8'
-    header = open(os.path.join(ROOT, 'include', 'istvt_hip.h')).read()
-    assert name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
-    m = re.search(r'int %s\(([^;]*)\);' % name, header)
-    assert m and len(m.group(1).split(',')) == len(_lib.SIGNATURES[name])
 
 
 def test_scorer_checks_the_keyword():

@@ -105,12 +105,10 @@ def test_starts_validation(pkg):
 
 
 def test_api_surface(pkg):
-    from istvt_amd import _lib, explain, ops, video
+    from istvt_amd import explain, ops, video
     from istvt_amd.network.vivit.vivit import XceptionVidTr
     assert callable(video.VideoScorer.explain) and callable(XceptionVidTr.explain_video) and callable(explain.overlay)
     assert video.VideoExplanation._fields == ('score', 'windows', 'frame_s', 'frame_t', 'frame_weight', 'frame_logit', 'count')
-    for name in ('istvt_relevance_fuse_windows', 'istvt_relevance_overlay_u8'):
-        assert name in _lib.SIGNATURES
     assert callable(ops.relevance_fuse_windows) and callable(ops.relevance_overlay_u8)
 
 

@@ -288,16 +288,3 @@ def test_scorer_argument_errors_need_no_device(pkg):
                  lambda: model.score_video(nv, transforms=M, side=32, pixel_format='nv12')):
         with pytest.raises(RuntimeError, match='ROCm'):
             call()
-
-
-def test_symbols_declared_bound_and_exported(pkg):
-    import os
-    from istvt_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, 'include', 'istvt_hip.h')) as fh:
-        header = fh.read()
-    for name in ('istvt_warp_similarity_u8', 'istvt_warp_similarity_nv12'):
-        assert 'int %s(' % name in header
-        assert name in _lib.SIGNATURES
-        if os.path.exists(_lib.LIB_PATH):
-            assert hasattr(_lib.lib(), name)

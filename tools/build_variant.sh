@@ -8,7 +8,7 @@ CSRC=$ROOT/2023-tifs-istvt_amd/csrc
 out=$1; src=$2; shift 2
 mkdir -p "$(dirname "$out")"
 tmp=$(mktemp -d)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-inline-asm -ffp-contract=fast "$@" -c "$CSRC/$src" -o "$tmp/v.o"
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -Wno-inline-asm -ffp-contract=fast -I "$ROOT/include" "$@" -c "$CSRC/$src" -o "$tmp/v.o"
 objs=""
 for o in "$CSRC"/build/*.o; do
     [ "$(basename "$o")" = "${src%.hip}.o" ] || objs="$objs $o"

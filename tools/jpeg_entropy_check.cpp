@@ -1,7 +1,7 @@
 // The entropy decoder of csrc/jpeg_entropy.h on the host, under sanitizers (DESIGN.md "JPEG files"):
 //
 //     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
-//         -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_check.cpp -o jpeg_entropy_check
+//         -I include -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_check.cpp -o jpeg_entropy_check
 //     python tests/golden/make_jpeg_files_golden.py jpg && ./jpeg_entropy_check jpg/*.jpg
 //
 // For every baseline file named: the markers are read and the segment table rebuilt here (the job of clips.jpeg_parse and

@@ -1,7 +1,7 @@
 // The entropy coder of csrc/jpeg_entropy_enc.h on the host, under sanitizers (DESIGN.md "JPEG files out"):
 //
 //     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
-//         -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_enc_check.cpp -o jpeg_entropy_enc_check
+//         -I include -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_enc_check.cpp -o jpeg_entropy_enc_check
 //     ./jpeg_entropy_enc_check
 //
 // Coefficient arrays from a fixed LCG in four flavours -- sparse and realistic | dense, every coefficient in +-1023 | runs of
