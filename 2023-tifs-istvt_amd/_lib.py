@@ -84,6 +84,7 @@ SIGNATURES = {
     'istvt_relevance_paste_nv12': [P, L, I, I, L, L, P, I, P, P, P, P, I, I, P],
     'istvt_jpeg_roundtrip_u8': [P, L, I, I, I, P, I, P, L, P, P],
     'istvt_jpeg_decode_u8': [ctypes.POINTER(JpegDecodeArgs)],
+    'istvt_jpeg_decode_split_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_jpeg_encode_u8': [ctypes.POINTER(JpegEncodeArgs)],
     'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],

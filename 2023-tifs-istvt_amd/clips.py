@@ -1097,6 +1097,257 @@ def jpeg_batch(files) -> JpegBatch:
                      sizes=sizes, n=len(files), blocks=blocks, groups=groups)
 
 
+# DESIGN.md "JPEG files without restart markers": a restart interval decoded from several start points at once.
+# jpeg_split_plan is the chunk rule, jpeg_split_host the definition of the state table (csrc/jpeg_entropy_split.h has the
+# same steps for the device); the definition of the pixels stays jpeg_decode_host.
+JPEG_SPLIT_LANES = 256                      # chunks of a segment at the most: the lanes of its workgroup
+JPEG_SPLIT_MIN = 16                         # the smallest chunk_bytes
+JPEG_SPLIT_DEFAULT = 128                    # what split='auto' takes (DESIGN.md has the sweep it comes from)
+JPEG_SPLIT_AUTO_BYTES = 12 * 128            # ... where some segment is longer than this: measured to lose at 850, to win at 1700
+JPEG_STATE_INTS = 8                         # a state row: ISTVT_JPEG_STATE_INTS of include/istvt_hip.h
+
+
+def check_split(chunk_bytes) -> int:
+    if isinstance(chunk_bytes, bool) or not isinstance(chunk_bytes, int) or chunk_bytes < JPEG_SPLIT_MIN:
+        raise ValueError('jpeg split: the chunk size is an int of at least %d bytes, got %r' % (JPEG_SPLIT_MIN, chunk_bytes))
+    return chunk_bytes
+
+
+def jpeg_split_plan(batch_or_header, chunk_bytes: int) -> SimpleNamespace:
+    """How ops.jpeg_decode_u8(..., split=chunk_bytes) cuts the segments of a JpegBatch (or of one parsed file, packed alone):
+    a segment of `length` bytes into chunks of max(chunk_bytes, ceil(length / 256)) bytes, at least one and at most 256 of
+    them; the last ends with the segment.  -> chunk, count, row0: per segment, the chunk size, the number of chunks and the
+    first of its rows in the state table (first byte // chunk_bytes + segment: segments lie in order, so rows never meet) |
+    rows: rows of the table | states_at: where the table starts in the scratch | scratch_bytes: what the launch needs."""
+    chunk_bytes = check_split(chunk_bytes)
+    batch = batch_or_header if isinstance(batch_or_header, JpegBatch) else jpeg_batch([batch_or_header])
+    chunk, count, row0 = [], [], []
+    for s, (_, b, e, _, _) in enumerate(batch.segments.tolist()):
+        c = max(chunk_bytes, -(-(e - b) // JPEG_SPLIT_LANES))
+        chunk.append(c)
+        count.append(max(1, -(-(e - b) // c)))
+        row0.append(b // chunk_bytes + s)
+    rows = batch.nbytes // chunk_bytes + len(chunk)
+    at = -(-batch.scratch_bytes // 16) * 16
+    return SimpleNamespace(chunk=chunk, count=count, row0=row0, rows=rows, states_at=at,
+                           scratch_bytes=at + 4 * JPEG_STATE_INTS * rows)
+
+
+class _JpegPosBits:
+    """_JpegBits for the split path: a reader that knows where it is and can be opened at any (pos, bit).  pos: the raw
+    index of the byte that holds the next bit (never a stuffed 00; the zeros fed past `end` count on as bytes end, end + 1,
+    ...), bit: bits of it already taken.  Three bytes wait in win; p[0..2] are their indices, p[3] the next to fetch."""
+
+    def __init__(self, data, end, pos, bit):
+        self.data, self.end, self.bit, self.status = data, end, bit, 0
+        self.p, self.win = [pos], 0
+        for _ in range(3):
+            b, at = self._fetch(self.p[-1])
+            self.win = (self.win << 8) | b
+            self.p.append(at)
+
+    def _fetch(self, at):
+        if at >= self.end:
+            return 0, at + 1
+        b = self.data[at]
+        at += 1
+        if b == 0xFF and at < self.end and self.data[at] == 0:
+            at += 1
+        return b, at
+
+    @property
+    def pos(self):
+        return self.p[0]
+
+    def skip(self, k):
+        last = self.p[0]
+        self.bit += k
+        while self.bit >= 8:
+            last = self.p[0]
+            b, at = self._fetch(self.p[3])
+            self.win = ((self.win << 8) | b) & 0xFFFFFF
+            self.p = self.p[1:] + [at]
+            self.bit -= 8
+        if self.bit > 0:
+            last = self.p[0]
+        if last >= self.end:
+            self.status = 1
+
+    def huffman(self, t):
+        c = (self.win >> (8 - self.bit)) & 0xFFFF
+        for l in range(1, 17):
+            if c < t[l - 1]:
+                self.skip(l)
+                return t[32 + ((t[16 + l - 1] + (c >> (16 - l))) & 255)]
+        return -1
+
+    def receive(self, s):
+        r = (self.win >> (24 - self.bit - s)) & ((1 << s) - 1)
+        self.skip(s)
+        return r if r >= (1 << (s - 1)) else r - (1 << s) + 1
+
+
+def _split_component(sub: int, blk: int) -> int:
+    return (0, 0, 0, 0, 1, 2)[blk] if sub == 2 else blk
+
+
+def _split_chunk(data, end, limit, tabs, sub, state):
+    """The lenient transition of one lane (js_chunk): the symbols from `state` that start before `limit` -> (the exit state,
+    blocks started up to the first error, that error or 0).  A prefix no code matches takes 16 bits and counts as 0, a DC
+    category above 11 counts as 0, a run past 63 ends the block: it cannot die, and up to the first of these it is the
+    decoder of _jpeg_block."""
+    pos, bit, blk, k = state
+    bits = _JpegPosBits(data, end, pos, bit)
+    nblk, blocks, err = (6 if sub == 2 else 3), 0, 0
+    while bits.pos < limit:
+        c = _split_component(sub, blk)
+        done = False
+        if k == 0:
+            s = bits.huffman(tabs[c][0])
+            blocks += 0 if err else 1
+            if s < 0:
+                bits.skip(16)
+            if s < 0 or s > 11:
+                err = err or 2
+            else:
+                bits.skip(s)
+            k = 1
+        else:
+            rs = bits.huffman(tabs[c][1])
+            if rs < 0:
+                bits.skip(16)
+                err, rs = err or 2, 0
+            r, s = rs >> 4, rs & 15
+            if s == 0:
+                k = k + 16 if r == 15 else 64
+                if k > 64:
+                    err = err or 3
+                done = k >= 64
+            else:
+                k += r
+                if k > 63:
+                    err, done = err or 3, True
+                else:
+                    bits.skip(s)
+                    k += 1
+                    done = k == 64
+        if done:
+            k, blk = 0, (blk + 1) % nblk
+    return (bits.pos, bits.bit, blk, k), blocks, err
+
+
+def _split_strict(data, end, limit, last, tabs, sub, total, state, nxt):
+    """The strict decode of one lane (js_write without its stores): _jpeg_block's steps from a converged state on the symbols
+    that start before `limit`, or with last=True until block `total` of the segment would start; nxt: the number of the next
+    block to start -> (status, blocks started)"""
+    pos, bit, _, k = state
+    bits = _JpegPosBits(data, end, pos, bit)
+    started, c = 0, 0
+    if k > 0:
+        if not 1 <= nxt <= total:
+            return 0, 0
+        c = _split_component(sub, (nxt - 1) % (6 if sub == 2 else 3))
+    while last or bits.pos < limit:
+        if k == 0:
+            if nxt >= total:
+                break
+            c = _split_component(sub, nxt % (6 if sub == 2 else 3))
+            nxt, started = nxt + 1, started + 1
+            s = bits.huffman(tabs[c][0])
+            if s < 0 or s > 11:
+                return 2, started
+            if s:
+                bits.receive(s)
+            k = 1
+            continue
+        rs = bits.huffman(tabs[c][1])
+        if rs < 0:
+            return 2, started
+        r, s = rs >> 4, rs & 15
+        if s == 0:
+            if r != 15:
+                k = 0
+                continue
+            k += 16
+            if k > 64:
+                return 3, started
+            k %= 64
+            continue
+        k += r
+        if k > 63:
+            return 3, started
+        bits.receive(s)
+        k = (k + 1) % 64
+    return bits.status, started
+
+
+def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
+    """The host model of the split entropy decode of one parsed file (a JpegHeader, or bytes): per segment, S chunks by
+    jpeg_split_plan's rule and as many lanes.
+
+      guess    lane 0 starts at (begin, 0, 0, 0); lane i at byte begin + i * chunk, bit 0, block 0, k 0, one byte later
+               where that byte is the 00 stuffed behind an FF
+      relax    in every round lane i recomputes its exit state from the exit state lane i - 1 had the round before
+               (_split_chunk); the loop ends when no state changed.  After round r lanes 0..r hold the sequential
+               decoder's states, so there are at most S - 1 rounds and the guesses cannot change the result.
+      strict   every lane decodes its chunk once by the rules of _jpeg_block (_split_strict), up to the first lane that
+               meets an error; the segment stops at its MCU count, and only its last lane reads past the end.
+
+    -> segments: per segment a namespace of states [(pos, bit, blk, k)], the entry state of every lane, pos an index into
+    the file; blocks: blocks started per lane; first: each lane's first block; lane_status; rounds: the rounds in which a
+    state changed; status; rows: the eight ints per lane the device leaves in the scratch | status: the largest of the
+    segments', jpeg_decode_host's | rounds: the largest.  The fixed point is asserted against one walk from lane 0 on."""
+    hd = header if isinstance(header, JpegHeader) else jpeg_parse(header)
+    chunk_bytes = check_split(chunk_bytes)
+    sub, (my, mx) = hd.sub, hd.mcus
+    nblk = 6 if sub == 2 else 3
+    tabs = [(jpeg_huffman_table(*dc), jpeg_huffman_table(*ac)) for dc, ac in hd.huffman]
+    ri = hd.restart_interval or my * mx
+    data, segments = hd.data, []
+    for i, (begin, end) in enumerate(hd.segments):
+        total = nblk * min(ri, my * mx - i * ri)
+        chunk = max(chunk_bytes, -(-(end - begin) // JPEG_SPLIT_LANES))
+        S = max(1, -(-(end - begin) // chunk))
+        limits = [begin + (j + 1) * chunk for j in range(S)]
+        entry = [(begin, 0, 0, 0)]
+        for j in range(1, S):
+            at = begin + j * chunk
+            entry.append((at + 1 if data[at - 1] == 0xFF and data[at] == 0 else at, 0, 0, 0))
+        step = [_split_chunk(data, end, limits[j], tabs, sub, entry[j]) for j in range(S - 1)]
+        rounds = 0
+        for _ in range(1, S):
+            changed = False
+            before = [st[0] for st in step]
+            for j in range(1, S):
+                if before[j - 1] != entry[j]:
+                    entry[j] = before[j - 1]
+                    if j < S - 1:
+                        new = _split_chunk(data, end, limits[j], tabs, sub, entry[j])
+                        changed = changed or new[0] != step[j][0]
+                        step[j] = new
+            if not changed:
+                break
+            rounds += 1
+        walk = [(begin, 0, 0, 0)]
+        for j in range(S - 1):
+            walk.append(_split_chunk(data, end, limits[j], tabs, sub, walk[j])[0])
+        assert entry == walk and rounds <= max(S - 1, 0), 'jpeg_split_host: the relaxation did not reach the sequential states'
+        # a lane's first block: the tallies of the lanes in front; the lanes up to the first whose tally met an error decode
+        dead = min([j for j in range(S - 1) if step[j][2]], default=S)
+        blocks, first, lane_status, nxt = [], [], [], 0
+        for j in range(S):
+            first.append(min(nxt, total))                         # bits behind the last block can look like blocks
+            st, started = _split_strict(data, end, limits[j], j == S - 1, tabs, sub, total, entry[j], nxt) if j <= dead else (0, 0)
+            nxt += step[j][1] if j < S - 1 else 0
+            blocks.append(started)
+            lane_status.append(st)
+        status = max(lane_status)
+        rows = [list(entry[j]) + [blocks[j], first[j], lane_status[j], rounds] for j in range(S)]
+        segments.append(SimpleNamespace(states=entry, blocks=blocks, first=first, lane_status=lane_status, rounds=rounds,
+                                        status=status, chunk=chunk, rows=rows))
+    return SimpleNamespace(segments=segments, status=max(s.status for s in segments), rounds=max(s.rounds for s in segments))
+
+
 def whole_boxes(sizes) -> Tensor:
     """[(H, W)] -> int32 (n, 4): the box (0, 0, H, W) of every frame, for crop_resize_u8 on the decoder's canvas"""
     return torch.tensor([[0, 0, int(h), int(w)] for h, w in sizes], dtype=torch.int32).reshape(-1, 4)

@@ -25,7 +25,9 @@
 // files from their compressed bytes in three launches that share jp_idct8, jp_chroma and the colour-out expression with the
 // round trip.  jpeg_entropy_kernel: one lane per restart interval (jpeg_entropy.h) -> int16 coefficients.
 // jpeg_idct_kernel: the back half of jpeg_planes_kernel with the file's own tables -> the planes.  jpeg_canvas_kernel:
-// jpeg_rgb_kernel over a canvas [n][Hc][Wc][3] that holds images of several sizes.
+// jpeg_rgb_kernel over a canvas [n][Hc][Wc][3] that holds images of several sizes.  istvt_jpeg_decode_split_u8 (DESIGN.md
+// "JPEG files without restart markers") puts jpeg_entropy_split_kernel in front instead: one workgroup per restart interval,
+// one lane per chunk of it (jpeg_entropy_split.h), for files whose intervals are long.
 //
 // JPEG files out (DESIGN.md "JPEG files out") are the third part: istvt_jpeg_encode_u8 writes a batch of frames as baseline
 // files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
@@ -34,6 +36,7 @@
 #include "istvt_hip.h"
 #include "jpeg_entropy.h"
 #include "jpeg_entropy_enc.h"
+#include "jpeg_entropy_split.h"
 #include "u8_view.h"
 
 namespace {
@@ -420,6 +423,131 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     seg_status[s] = je_decode_segment(bytes, begin, end, huff, sub, mcux, first, count, w);
 }
 
+// The state rows of the split path (js_chunk_bytes, js_chunks: the chunk rule): those of segment s start at row begin /
+// chunk_bytes + s of the table behind the statuses.  Segments lie in order in the bytes and a segment has at most length /
+// chunk_bytes + 1 chunks, so the rows of two segments never meet and the table has nbytes / chunk_bytes + nseg rows.
+constexpr int JS_STATE_INTS = ISTVT_JPEG_STATE_INTS;
+
+// One workgroup per restart interval, one lane per chunk (jpeg_entropy_split.h).  All lanes clear the interval's blocks;
+// the lanes relax their entry states until no exit state changes, at most S - 1 rounds; the tallies of the last transition
+// are scanned into each lane's first block and DC predictions; the lanes up to the first that met an error decode once more
+// with stores.  The barriers of the rounds lie between the clears and every put.  A state row: entry pos, bit, blk, k,
+// blocks started, first block, status of the lane's decode, rounds in which a state changed.  LANES: the workgroup's size,
+// 256, or 64 where no interval of the batch has more chunks than that (the entry knows from the host table).
+template <int LANES>
+__global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ bytes, long nbytes,
+                                                                   const int* __restrict__ images, int n,
+                                                                   const int* __restrict__ segments, int nseg,
+                                                                   const int* __restrict__ htabs, int nh,
+                                                                   short* __restrict__ coef, long total_blocks,
+                                                                   int* __restrict__ seg_status, int* __restrict__ rows,
+                                                                   long nrows, int chunk_bytes) {
+    __shared__ int sh_pos[LANES], sh_pk[LANES];
+    __shared__ int sh_scan[2][4][LANES];
+    __shared__ int sh_dead, sh_status;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int* sg = segments + (long)s * JD_SEGMENT_INTS;
+    const int img = sg[0], first = sg[3], count = sg[4];
+    const long begin = sg[1], end = sg[2];
+    int ok = img >= 0 && img < n && begin >= 0 && begin <= end && end <= nbytes && first >= 0 && count >= 0;
+    const int* im = images + (long)(ok ? img : 0) * JD_IMAGE_INTS;
+    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
+    ok = ok && (long)first + count <= (long)mcux * mcuy;
+    const int* huff[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int slot = im[JD_HUFF + k];
+        ok = ok && slot >= 0 && slot < nh;
+        huff[k] = htabs + (long)(ok ? slot : 0) * JE_HUFF_INTS;
+    }
+    const long chunk = ok ? js_chunk_bytes(end - begin, chunk_bytes) : chunk_bytes;
+    const int S = ok ? js_chunks(end - begin, chunk_bytes) : 1;
+    const long row0 = begin / chunk_bytes + s;
+    ok = ok && S <= LANES && row0 >= 0 && row0 + S <= nrows;
+    if (!ok) {                                                   // the same for every lane of the workgroup
+        if (tid == 0) seg_status[s] = 2;
+        return;
+    }
+    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * sub, mcux, mcux * sub * mcuy * sub, mcux * mcuy};
+    const int nblk = js_mcu_blocks(sub);
+    const long total = (long)count * nblk;                       // blocks of the interval
+    for (long at = tid; at < total * 8; at += LANES) {           // a lane clears 16 bytes at a time
+        const long cur = at >> 3;
+        const int mcu = first + (int)(cur / nblk), j = (int)(cur % nblk);
+        const int my = mcu / mcux, mx = mcu - my * mcux;
+        const int c = js_component(sub, j), nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
+        const long b = w.block(c, my * nb + jj / nb, mx * nb + jj % nb);
+        if (b >= 0) reinterpret_cast<uint4*>(coef + b * 64)[at & 7] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (tid == 0) sh_dead = JS_LANES, sh_status = 0;
+
+    const bool lane = tid < S, inner = tid < S - 1;              // inner: a lane whose exit state another lane reads
+    const long limit = begin + (long)(tid + 1) * chunk;          // <= end for an inner lane
+    JsState in = {begin, 0, 0, 0}, out = in;
+    JsTally t = {0, 0, {0, 0, 0}};
+    if (lane && tid > 0) in = js_guess(bytes, begin, end, begin + (long)tid * chunk);
+    if (inner) out = js_chunk(bytes, end, limit, huff, sub, in, t);
+    sh_pos[tid] = (int)out.pos, sh_pk[tid] = out.bit | out.blk << 3 | out.k << 6;
+    __syncthreads();
+    int rounds = 0;
+    for (int r = 1; r < S; ++r) {                                // S is the workgroup's: every lane takes the same trips
+        JsState nin = in;
+        if (lane && tid > 0) {
+            const int pk = sh_pk[tid - 1];
+            nin.pos = sh_pos[tid - 1], nin.bit = pk & 7, nin.blk = (pk >> 3) & 7, nin.k = pk >> 6;
+        }
+        __syncthreads();                                         // every exit state of the last round is read
+        int changed = 0;
+        if (!js_same(nin, in)) {
+            in = nin;
+            if (inner) {
+                const JsState o = js_chunk(bytes, end, limit, huff, sub, in, t);
+                changed = !js_same(o, out);
+                out = o;
+                sh_pos[tid] = (int)out.pos, sh_pk[tid] = out.bit | out.blk << 3 | out.k << 6;
+            }
+        }
+        if (!__syncthreads_or(changed)) break;
+        ++rounds;
+    }
+
+    // each lane's first block and predictions: an inclusive scan of the inner lanes' tallies, read one lane to the left
+    int v[4] = {inner ? t.blocks : 0, inner ? t.pred[0] : 0, inner ? t.pred[1] : 0, inner ? t.pred[2] : 0};
+    if (inner && t.err) atomicMin(&sh_dead, tid);
+    int side = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sh_scan[0][q][tid] = v[q];
+    __syncthreads();
+    for (int d = 1; d < S; d <<= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (tid >= d) v[q] += sh_scan[side][q][tid - d];
+            sh_scan[side ^ 1][q][tid] = v[q];
+        }
+        side ^= 1;
+        __syncthreads();
+    }
+    long next = 0;
+    int pred[3] = {0, 0, 0};
+    if (tid > 0) {
+        next = sh_scan[side][0][tid - 1];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) pred[q] = (int16_t)sh_scan[side][1 + q][tid - 1];
+    }
+    int started = 0, st = 0;
+    if (lane && tid <= sh_dead) {
+        st = js_write(bytes, end, limit, tid == S - 1, huff, sub, mcux, first, total, in, next, pred, w, started);
+        if (st) atomicMax(&sh_status, st);
+    }
+    if (lane) {
+        int* row = rows + (row0 + tid) * JS_STATE_INTS;
+        row[0] = (int)in.pos, row[1] = in.bit, row[2] = in.blk, row[3] = in.k;
+        row[4] = started, row[5] = (int)min(next, total), row[6] = st, row[7] = rounds;
+    }
+    __syncthreads();
+    if (tid == 0) seg_status[s] = sh_status;
+}
+
 // The back half of jpeg_planes_kernel on decoded coefficients: a workgroup takes JP_BLOCKS consecutive blocks of one image,
 // a lane one 8-point transform of each pass: times the image's table and inverse columns | inverse rows, + 128, clamp, one
 // 8-byte store.  The first workgroup of an image also writes its size and the largest status of its segments.
@@ -607,6 +735,60 @@ extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
     int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((a->nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes,
                        a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,
+                       seg_status, a->nseg, planes, a->sizes, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
+                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
+// istvt_jpeg_decode_u8 with the split entropy kernel in front: a workgroup per restart interval, a lane per chunk of
+// chunk_bytes (at least 16) of it, for files whose intervals are long (DESIGN.md "JPEG files without restart markers").  The
+// same checks, the same IDCT and colour launches, the same bytes out.  The scratch keeps the layout above in front; the state
+// rows follow the statuses at the next multiple of 16 bytes.
+extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes) {
+    if (!a || a->n <= 0 || a->nseg < a->n || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || chunk_bytes < 16) return ISTVT_ERR_SHAPE;
+    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->segments_host || !a->qtabs || !a->htabs ||
+        !a->scratch || !a->out || !a->sizes || !a->status)
+        return ISTVT_ERR_SHAPE;
+    if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
+    long groups = 0;
+    const long blocks = jpeg_decode_check(a, &groups);
+    if (blocks < 0) return ISTVT_ERR_SHAPE;
+    long chunks = 0;
+    int most = 0;                                                 // chunks of the longest segment
+    for (int s = 0; s < a->nseg; ++s) {                          // segments in the order of their bytes: what the rows rely on
+        const int* sg = a->segments_host + (long)s * JD_SEGMENT_INTS;
+        if (s > 0 && sg[1] < sg[-JD_SEGMENT_INTS + 2]) return ISTVT_ERR_SHAPE;
+        const int c = js_chunks((long)sg[2] - sg[1], chunk_bytes);
+        chunks += c;
+        most = c > most ? c : most;
+    }
+    const long nrows = a->nbytes / chunk_bytes + a->nseg;         // chunks <= nrows
+    const long front = (blocks * JD_BLOCK_BYTES + 4L * a->nseg + 15) & ~15L;
+    if (chunks > nrows || (reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < front + nrows * JS_STATE_INTS * 4)
+        return ISTVT_ERR_SHAPE;
+    const long npix = (long)a->n * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
+    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const uint8_t* src = (const uint8_t*)a->bytes;
+    uint8_t* out = (uint8_t*)a->out;
+    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
+    short* coef = (short*)a->scratch;
+    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
+    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
+    int* rows = (int*)((uint8_t*)a->scratch + front);
+    if (most <= 64)
+        hipLaunchKernelGGL(jpeg_entropy_split_kernel<64>, dim3((unsigned)a->nseg), dim3(64), 0, a->stream, src, a->nbytes,
+                           a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status, rows, nrows,
+                           chunk_bytes);
+    else
+        hipLaunchKernelGGL(jpeg_entropy_split_kernel<JS_LANES>, dim3((unsigned)a->nseg), dim3(JS_LANES), 0, a->stream, src,
+                           a->nbytes, a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status, rows,
+                           nrows, chunk_bytes);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,

@@ -394,7 +394,21 @@ def jpeg_roundtrip_u8(frames: Tensor, quality, subsampling: str = '420', out: Op
     return out
 
 
-def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None):
+def _jpeg_split(batch, split):
+    """the `split` argument of jpeg_decode_u8 -> the chunk size of the split entropy kernel, or None for the one lane per
+    restart interval"""
+    if split is None:
+        return None
+    if split == 'auto':
+        longest = int((batch.segments[:, 2] - batch.segments[:, 1]).max())
+        return clips.JPEG_SPLIT_DEFAULT if longest > clips.JPEG_SPLIT_AUTO_BYTES else None
+    if isinstance(split, bool) or not isinstance(split, int) or split < clips.JPEG_SPLIT_MIN:
+        raise ValueError("jpeg_decode_u8: split is None, 'auto' or a chunk size in bytes (an int of at least %d), got %r"
+                         % (clips.JPEG_SPLIT_MIN, split))
+    return split
+
+
+def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None, split=None):
     """JPEG files (clips.py): a batch of baseline JPEG files goes to the device as compressed bytes -> (frames, sizes,
     status): frames uint8 [n, Hc, Wc, 3], image i in the top left H_i x W_i of its canvas and 0 elsewhere, the bits of
     clips.jpeg_decode_host; sizes int32 [n, 2] = (H, W) and status int32 [n] (0: fine; clips.jpeg_decode_host lists the
@@ -404,7 +418,13 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     loader's worker); its tables are uploaded once per device and kept on it.  canvas = (Hc, Wc) defaults to the largest
     H and W of the batch.  `out` (uint8, contiguous, of the result's shape, no overlap with the uploaded bytes) is written
     when given.  buffers = (scratch uint8 of at least batch.scratch_bytes bytes and 16-byte aligned, sizes, status): the
-    caller's, to decode step after step without an allocation."""
+    caller's, to decode step after step without an allocation.  split: how a restart interval is decoded.  None: by one
+    lane, which suits files with a restart marker per MCU row.  A chunk size in bytes (an int of at least 16): by one lane
+    per chunk, which start from guessed decoder states and relax them to the sequential decoder's (clips.jpeg_split_host) --
+    for files without restart markers, as cameras and most encoders write them; the same bytes come out.  'auto': chunks
+    of clips.JPEG_SPLIT_DEFAULT bytes where some interval of the batch is longer than clips.JPEG_SPLIT_AUTO_BYTES (the
+    split has a cost: on intervals of one MCU row of a 224-pixel frame it is the slower of the two), else None.  With a split the
+    scratch holds clips.jpeg_split_plan(batch, chunk).scratch_bytes."""
     if isinstance(batch, clips.JpegFiles):                        # the encoder's result: read back, then parsed like any files
         batch = batch.files()
     if isinstance(batch, clips.JpegBatch):
@@ -417,6 +437,8 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
         if len(batch) == 0:
             raise RuntimeError('jpeg_decode_u8: empty input (no files)')
         batch = clips.jpeg_batch(batch)
+    chunk = _jpeg_split(batch, split)
+    need = batch.scratch_bytes if chunk is None else clips.jpeg_split_plan(batch, chunk).scratch_bytes
     if not torch.cuda.is_available():
         raise RuntimeError('istvt_amd: jpeg_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
     device = out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
@@ -430,35 +452,39 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     out = _u8_out('jpeg_decode_u8', dev.data, (n, Hc, Wc, 3), out)
     _no_overlap('jpeg_decode_u8', out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
     if buffers is None:
-        scratch = torch.empty((batch.scratch_bytes,), dtype=torch.uint8, device=device)
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
         sizes = torch.empty((n, 2), dtype=torch.int32, device=device)
         status = torch.empty((n,), dtype=torch.int32, device=device)
     else:
         scratch, sizes, status = buffers
         ok = (t.device == device and t.is_contiguous() for t in buffers)
-        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < batch.scratch_bytes or scratch.data_ptr() % 16
+        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
                 or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
                 or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
             raise RuntimeError('jpeg_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
-                               'status (%d,)), contiguous on %s' % (batch.scratch_bytes, n, n, device))
+                               'status (%d,)), contiguous on %s' % (need, n, n, device))
     args = _lib.JpegDecodeArgs(
         bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
         segments=dev.segments.data_ptr(), segments_host=batch.segments.data_ptr(), qtabs=dev.qtabs.data_ptr(),
         htabs=dev.htabs.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(),
         sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, nseg=int(batch.segments.shape[0]),
         nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), Hc=Hc, Wc=Wc)
+    if chunk is not None:
+        with prof('jpeg_decode_split_u8', batch.nbytes + 2 * 192 * batch.blocks + out.numel()):
+            _lib.check(_lib.lib().istvt_jpeg_decode_split_u8(ctypes.byref(args), chunk), 'istvt_jpeg_decode_split_u8')
+        return out, sizes, status
     with prof('jpeg_decode_u8', batch.nbytes + 2 * 192 * batch.blocks + out.numel()):
         _lib.check(_lib.lib().istvt_jpeg_decode_u8(ctypes.byref(args)), 'istvt_jpeg_decode_u8')
     return out, sizes, status
 
 
-def decode_frames(files, S: int, boxes: Optional[Tensor] = None) -> Tensor:
+def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None) -> Tensor:
     """Face crops from JPEG files: files (a sequence of bytes, a clips.JpegBatch or a clips.JpegFiles) are decoded on the device
     (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
     whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
-    and the scorers."""
+    and the scorers.  split: jpeg_decode_u8's, for files without restart markers."""
     batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files)
-    frames, _, _ = jpeg_decode_u8(batch, checked=True)
+    frames, _, _ = jpeg_decode_u8(batch, checked=True, split=split)
     return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)
 
 

@@ -424,6 +424,19 @@ typedef struct istvt_jpeg_decode_args {
     int n, nseg, nq, nh, Hc, Wc;
 } istvt_jpeg_decode_args;
 int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a);
+/* JPEG files without restart markers: istvt_jpeg_decode_u8 with another entropy kernel, one workgroup per restart interval
+ * and one lane per chunk of it, for intervals that are long (a whole file where there are no markers).  The same argument
+ * block, the same checks and the same bytes in out, sizes and status.  An interval of `length` bytes is cut into chunks of
+ * max(chunk_bytes, ceil(length / 256)) bytes, at least one; the lanes start from guessed decoder states and relax them to the
+ * sequential decoder's (csrc/jpeg_entropy_split.h), then decode their chunks.  chunk_bytes >= 16, and segments lie in the
+ * order of their bytes (first byte >= the end byte of the segment before), or -3.
+ *   scratch    16-byte aligned; the layout above in front, then from the next multiple of 16 bytes int32
+ *              [nbytes / chunk_bytes + nseg][8], the state rows: those of segment s start at row (first byte) / chunk_bytes
+ *              + s.  A row: the lane's entry state (byte index in `bytes`, bits of that byte taken, block within the MCU,
+ *              coefficient index), blocks it started, its first block within the interval, the status of its decode, the
+ *              rounds in which a state of the interval changed.  clips.jpeg_split_plan has the sizes. */
+#define ISTVT_JPEG_STATE_INTS 8    /* a state row */
+int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with

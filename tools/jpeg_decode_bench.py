@@ -12,6 +12,11 @@ clips.jpeg_roundtrip_host:
 decode   ops.jpeg_decode_u8 on the uploaded batch with the caller's buffers, events around the call (three launches);
          alternating with ops.jpeg_roundtrip_u8 on the same decoded frames as context; medians and min-max over the repeats
          after the warm-up.  The three kernels apart come from `rocprofv3 --kernel-trace --stats` on a run with --reps 3.
+--split  adds, on the two restart-less configurations and on the row-restart one at quality 75, ops.jpeg_decode_u8(...,
+         split=chunk) for chunk 64, 128, 256 and 512 (DESIGN.md "JPEG files without restart markers"): checked against the
+         default call's frames, then timed in alternation with the default call, whose code no chunk size changes.  It
+         also adds quality 75 with a restart marker every 2, 4 and 8 MCU rows, at the default chunk size: where between a
+         row and a whole file the split starts to pay, which is what split='auto' decides by.
 upload   the compressed batch (scan bytes and tables) against the decoded clip (3 bytes per pixel), both from pinned memory,
          host clock around copy + synchronise.
 """
@@ -33,6 +38,7 @@ from istvt_amd import clips, ops  # noqa: E402
 
 DISTINCT = 8
 QUALITIES = (75, 90)
+SPLIT_CHUNKS = (64, 128, 256, 512)
 
 
 def smooth_image(h, w, seed):
@@ -81,8 +87,40 @@ def encoded(a, q, ri):
     return files
 
 
+def split_rows(a, lines, res, batch, out, want, buffers, q, ri, chunks):
+    """--split: ops.jpeg_decode_u8(..., split=chunk) for every chunk size of SPLIT_CHUNKS on one configuration, each checked
+    against the default call's frames and timed in alternation with the default call; the rounds come from the state rows"""
+    n = batch.n
+    for chunk in chunks:
+        plan = clips.jpeg_split_plan(batch, chunk)
+        mine = (torch.empty((plan.scratch_bytes,), dtype=torch.uint8, device=out.device), buffers[1], buffers[2])
+        got, _, status = ops.jpeg_decode_u8(batch, out=out, checked=True, buffers=mine, split=chunk)
+        clips.check_jpeg_status(status)
+        if not torch.equal(got, want):
+            raise SystemExit('q=%d ri=%d split=%d: the frames are not the default call\'s' % (q, ri, chunk))
+        table = mine[0][plan.states_at:plan.states_at + 32 * plan.rows].view(torch.int32).view(-1, 8)
+        rounds = [int(table[r0:r0 + c, 7].max()) for r0, c in zip(plan.row0[:len(plan.row0) // n * DISTINCT],
+                                                                  plan.count[:len(plan.count) // n * DISTINCT])]
+        ts, td = [], []
+        for r in range(a.warmup + a.reps):
+            x = event_ms(lambda: ops.jpeg_decode_u8(batch, out=out, checked=True, buffers=mine, split=chunk))
+            y = event_ms(lambda: ops.jpeg_decode_u8(batch, out=out, checked=True, buffers=buffers))
+            if r >= a.warmup:
+                ts.append(x)
+                td.append(y)
+        ss, sd = stats(ts), stats(td)
+        res['split%d' % chunk] = {'decode': ss, 'default_beside': sd, 'chunks': max(plan.count), 'chunk': max(plan.chunk),
+                                  'rounds_max': max(rounds), 'rounds_median': statistics.median(rounds),
+                                  'scratch_bytes': plan.scratch_bytes}
+        say(lines, 'jpeg_decode_u8 q=%d, restart interval %d, split=%d: up to %d chunks of %d bytes, rounds median %g, max %d | '
+            '%.3f ms (%.3f-%.3f) against %.3f ms (%.3f-%.3f) by default beside it = %.2f x'
+            % (q, ri, chunk, max(plan.count), max(plan.chunk), statistics.median(rounds), max(rounds), ss['median_ms'],
+               ss['min_ms'], ss['max_ms'], sd['median_ms'], sd['min_ms'], sd['max_ms'], sd['median_ms'] / ss['median_ms']))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--split', action='store_true')
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--reps', type=int, default=15)
@@ -93,6 +131,8 @@ def main():
     a = ap.parse_args()
     row = -(-a.size // 16)                                        # MCUs of one MCU row at 4:2:0
     configs = [(q, ri) for q in QUALITIES for ri in (0, row)]
+    longer = [(QUALITIES[0], k * row) for k in (2, 4, 8)] if a.split else []     # where between a row and a file it starts to pay
+    configs += longer
     if a.encode_only:
         for q, ri in configs:
             print('q=%d restart interval %d: %d bytes in %d files' % (q, ri, sum(len(f) for f in encoded(a, q, ri)), DISTINCT))
@@ -145,6 +185,9 @@ def main():
                sd['median_ms'] * 1e6 / (n * S * S), sr['median_ms'], sr['min_ms'], sr['max_ms'], up * 1e-6, batch.nbytes * 1e-6,
                raw.numel() * 1e-6, raw.numel() / up, su['median_ms'], su['min_ms'], su['max_ms'], sw['median_ms'], sw['min_ms'],
                sw['max_ms']))
+        if a.split and (ri == 0 or q == QUALITIES[0]):
+            chunks = (clips.JPEG_SPLIT_DEFAULT,) if (q, ri) in longer else SPLIT_CHUNKS
+            split_rows(a, lines, res[key], batch, out, got.clone(), buffers, q, ri, chunks)
     line = json.dumps({'jpeg_decode_bench': res})
     print(line)
     if a.out:

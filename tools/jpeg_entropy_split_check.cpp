@@ -1,0 +1,305 @@
+// The split entropy decode of csrc/jpeg_entropy_split.h on the host, under sanitizers (DESIGN.md "JPEG files without restart
+// markers"):
+//
+//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//         -I include -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_split_check.cpp -o jpeg_entropy_split_check
+//     python tests/golden/make_jpeg_files_golden.py jpg && ./jpeg_entropy_split_check jpg/*.jpg
+//
+// For every baseline file named: the markers are read and the segment table rebuilt as tools/jpeg_entropy_check.cpp does,
+// then (1) the file as it is, (2) the file cut at every byte length of its scan and (3) copies with 1 to 4 bits of the scan
+// flipped by a fixed LCG are decoded twice: by je_decode_segment, and by the split algorithm at chunk sizes 16, 37 and 128
+// with the lanes of the kernel emulated in order (guesses, rounds of js_chunk on the states of the round before, the scan of
+// the tallies, js_write up to the first lane that met an error).  Required: the same coefficients and the same status, every
+// block of the image cleared exactly once, no store outside the image's blocks (the buffer has the exact size, so
+// AddressSanitizer sees one), at most S - 1 rounds and a fixed point at their end.  Prints one line per file, exit status 1
+// on any failure.  A hand tool for a CPU: nothing here touches a GPU.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "jpeg_entropy_split.h"
+
+namespace {
+
+struct Table {
+    int t[JE_HUFF_INTS];
+};
+
+struct File {
+    std::vector<uint8_t> data;
+    int H = 0, W = 0, sub = 0, ri = 0;
+    int dc[3] = {0, 0, 0}, ac[3] = {0, 0, 0};
+    Table huff[2][4];
+    bool have[2][4] = {};
+    long scan = 0, scan_end = 0;
+    std::vector<long> begin, end;          // the restart intervals
+};
+
+// clips.jpeg_huffman_table
+void decode_form(const uint8_t* counts, const uint8_t* values, int total, Table& out) {
+    int code = 0, at = 0;
+    for (int l = 1; l <= 16; ++l) {
+        out.t[16 + l - 1] = at - code;
+        code += counts[l - 1];
+        at += counts[l - 1];
+        out.t[l - 1] = code << (16 - l);
+        code <<= 1;
+    }
+    for (int i = 0; i < 256; ++i) out.t[32 + i] = i < total ? values[i] : 0;
+}
+
+bool parse(File& f) {
+    const std::vector<uint8_t>& d = f.data;
+    const long n = (long)d.size();
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return false;
+    long pos = 2;
+    for (;;) {
+        if (pos + 4 > n || d[pos] != 0xFF) return false;
+        while (pos < n && d[pos] == 0xFF) ++pos;
+        if (pos + 3 > n) return false;
+        const int m = d[pos++];
+        const long len = (d[pos] << 8) | d[pos + 1];
+        if (len < 2 || pos + len > n) return false;
+        const uint8_t* s = d.data() + pos + 2;
+        const long sl = len - 2;
+        pos += len;
+        if (m == 0xC0) {
+            if (sl != 15 || s[0] != 8 || s[5] != 3) return false;
+            f.H = (s[1] << 8) | s[2], f.W = (s[3] << 8) | s[4];
+            f.sub = s[7] >> 4;
+            if (f.H < 1 || f.W < 1 || (s[7] != 0x22 && s[7] != 0x11) || s[10] != 0x11 || s[13] != 0x11) return false;
+        } else if (m == 0xC4) {
+            long at = 0;
+            while (at + 17 <= sl) {
+                const int tc = s[at] >> 4, th = s[at] & 15;
+                int total = 0, space = 1;
+                for (int i = 0; i < 16; ++i) {
+                    total += s[at + 1 + i];
+                    space = 2 * space - s[at + 1 + i];
+                    if (space < 0) return false;
+                }
+                if (tc > 1 || th > 3 || total > 256 || at + 17 + total > sl) return false;
+                decode_form(s + at + 1, s + at + 17, total, f.huff[tc][th]);
+                f.have[tc][th] = true;
+                at += 17 + total;
+            }
+        } else if (m == 0xDD) {
+            if (sl != 2) return false;
+            f.ri = (s[0] << 8) | s[1];
+        } else if (m == 0xDA) {
+            if (sl != 10 || s[0] != 3 || f.sub == 0) return false;
+            for (int c = 0; c < 3; ++c) {
+                f.dc[c] = s[2 + 2 * c] >> 4, f.ac[c] = s[2 + 2 * c] & 15;
+                if (f.dc[c] > 3 || f.ac[c] > 3 || !f.have[0][f.dc[c]] || !f.have[1][f.ac[c]]) return false;
+            }
+            break;
+        } else if (m == 0xC2 || m == 0xD9) {
+            return false;
+        }
+    }
+    f.scan = pos;
+    long begin = pos, at = pos;
+    f.scan_end = n;
+    while (at < n) {
+        if (d[at] != 0xFF) {
+            ++at;
+            continue;
+        }
+        long k = at + 1;
+        while (k < n && d[k] == 0xFF) ++k;
+        if (k >= n) break;
+        if (d[k] == 0 && k == at + 1) {
+            at += 2;
+            continue;
+        }
+        if (d[k] >= 0xD0 && d[k] <= 0xD7) {
+            f.begin.push_back(begin), f.end.push_back(at);
+            begin = at = k + 1;
+            continue;
+        }
+        f.scan_end = at;
+        break;
+    }
+    f.begin.push_back(begin), f.end.push_back(f.scan_end);
+    return true;
+}
+
+struct Writer {
+    std::vector<int16_t> coef;             // exactly the image's blocks
+    std::vector<int> cleared;              // how often each was cleared
+    long blocks = 0, puts = 0;
+    int ybw = 0, cbw = 0, ny = 0, nc = 0;
+    bool bad = false;
+    long block(int c, int row, int col) {
+        const long b = c == 0 ? (long)row * ybw + col : ny + (long)(c - 1) * nc + (long)row * cbw + col;
+        if (b < 0 || b >= blocks) bad = true;
+        return b;                           // handed on as it is: a wrong place is for the sanitizer to see
+    }
+    void clear(long b) {
+        for (int i = 0; i < 64; ++i) coef[b * 64 + i] = 0;
+        ++cleared[b];
+    }
+    void put(long b, int at, int v) {
+        if (at < 0 || at > 63) bad = true;
+        if (cleared[b] != 1) bad = true;    // a put before its block's clear
+        coef[b * 64 + at] = (int16_t)v;
+        ++puts;
+    }
+    void shape(const File& f, int mcux, int mcuy) {
+        ybw = mcux * f.sub, cbw = mcux, ny = mcux * f.sub * mcuy * f.sub, nc = mcux * mcuy;
+        blocks = ny + 2 * nc;
+        coef.assign(blocks * 64, 0x5a5a);
+        cleared.assign(blocks, 0);
+    }
+    bool sound() const {
+        for (long b = 0; b < blocks; ++b)
+            if (cleared[b] != 1) return false;
+        return !bad && puts <= blocks * 64;
+    }
+};
+
+// One restart interval as the kernel's workgroup decodes it, lane after lane -> its status, or -1 on a broken promise
+int split_segment(const uint8_t* data, long begin, long end, const int* const* huff, int sub, int mcux, int first, int count,
+                  int chunk_bytes, Writer& w, long& rounds_seen) {
+    const int nblk = js_mcu_blocks(sub);
+    const long total = (long)count * nblk;
+    for (long cur = 0; cur < total; ++cur) {
+        const int mcu = first + (int)(cur / nblk), j = (int)(cur % nblk);
+        const int my = mcu / mcux, mx = mcu - my * mcux;
+        const int c = js_component(sub, j), nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
+        w.clear(w.block(c, my * nb + jj / nb, mx * nb + jj % nb));
+    }
+    const long chunk = js_chunk_bytes(end - begin, chunk_bytes);
+    const int S = js_chunks(end - begin, chunk_bytes);
+    if (S > JS_LANES || chunk < chunk_bytes || begin + (long)(S - 1) * chunk > end || begin + (long)S * chunk < end) return -1;
+    std::vector<JsState> in(S), out(S), seen(S);
+    std::vector<JsTally> t(S);
+    for (int i = 0; i < S; ++i) {
+        in[i] = i ? js_guess(data, begin, end, begin + (long)i * chunk) : JsState{begin, 0, 0, 0};
+        out[i] = in[i];
+        t[i] = JsTally{0, 0, {0, 0, 0}};
+        if (i < S - 1) out[i] = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, sub, in[i], t[i]);
+    }
+    long rounds = 0;
+    for (int r = 1; r < S; ++r) {
+        seen = out;                         // every lane reads the round before
+        bool changed = false;
+        for (int i = 1; i < S; ++i) {
+            if (js_same(seen[i - 1], in[i])) continue;
+            in[i] = seen[i - 1];
+            if (i < S - 1) {
+                const JsState o = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, sub, in[i], t[i]);
+                changed = changed || !js_same(o, out[i]);
+                out[i] = o;
+            }
+        }
+        if (!changed) break;
+        ++rounds;
+    }
+    if (rounds > (S > 1 ? S - 1 : 0)) return -1;
+    for (int i = 1; i < S; ++i)            // a fixed point: every lane has decoded from what its neighbour now says
+        if (!js_same(in[i], out[i - 1])) return -1;
+    if (rounds > rounds_seen) rounds_seen = rounds;
+    int dead = S;
+    for (int i = S - 2; i >= 0; --i)
+        if (t[i].err) dead = i;
+    long next = 0;
+    int pred[3] = {0, 0, 0}, status = 0;
+    for (int i = 0; i < S && i <= dead; ++i) {
+        int started = 0;
+        const int st = js_write(data, end, begin + (long)(i + 1) * chunk, i == S - 1, huff, sub, mcux, first, total, in[i], next,
+                                pred, w, started);
+        if (st < 0 || st > 3) return -1;
+        if (st > status) status = st;
+        next += t[i].blocks;
+        for (int c = 0; c < 3; ++c) pred[c] = (int16_t)(pred[c] + t[i].pred[c]);
+    }
+    return status;
+}
+
+// all segments of a file whose bytes are `bytes` (cut to `limit`), both ways -> the file's status, or -1
+int decode(const File& f, const std::vector<uint8_t>& bytes, long limit, int chunk_bytes, long& rounds_seen) {
+    const int sub = f.sub, mcux = (f.W + 8 * sub - 1) / (8 * sub), mcuy = (f.H + 8 * sub - 1) / (8 * sub);
+    const long mcus = (long)mcux * mcuy;
+    Writer want, got;
+    want.shape(f, mcux, mcuy), got.shape(f, mcux, mcuy);
+    const int* huff[6];
+    for (int c = 0; c < 3; ++c) huff[2 * c] = f.huff[0][f.dc[c]].t, huff[2 * c + 1] = f.huff[1][f.ac[c]].t;
+    const long ri = f.ri ? f.ri : mcus, segs = (mcus + ri - 1) / ri;
+    int status = 0;
+    for (long i = 0; i < segs; ++i) {
+        long b = i < (long)f.begin.size() ? f.begin[i] : limit, e = i < (long)f.end.size() ? f.end[i] : limit;
+        if (b > limit) b = limit;
+        if (e > limit) e = limit;
+        const long first = i * ri, count = mcus - first < ri ? mcus - first : ri;
+        const int st = je_decode_segment(bytes.data(), b, e, huff, sub, mcux, (int)first, (int)count, want);
+        const int sp = split_segment(bytes.data(), b, e, huff, sub, mcux, (int)first, (int)count, chunk_bytes, got, rounds_seen);
+        if (st < 0 || st > 3 || sp != st) return -1;
+        if (st > status) status = st;
+    }
+    if (!want.sound() || !got.sound() || want.coef != got.coef) return -1;
+    return status;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    const int chunks[3] = {16, 37, 128};
+    int failures = 0;
+    for (int a = 1; a < argc; ++a) {
+        File f;
+        FILE* fh = fopen(argv[a], "rb");
+        if (!fh) {
+            printf("%s: cannot open\n", argv[a]);
+            ++failures;
+            continue;
+        }
+        uint8_t buf[4096];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof buf, fh)) > 0) f.data.insert(f.data.end(), buf, buf + got);
+        fclose(fh);
+        if (!parse(f)) {
+            printf("%s: not a baseline three-component file this tool reads\n", argv[a]);
+            ++failures;
+            continue;
+        }
+        const long n = (long)f.data.size();
+        int hist[4] = {0, 0, 0, 0}, whole = 0;
+        long runs = 0, broken = 0, rounds[3] = {0, 0, 0};
+        for (int ci = 0; ci < 3; ++ci) {
+            const int cb = chunks[ci];
+            whole = decode(f, f.data, n, cb, rounds[ci]);
+            long ignore = 0;                // the rounds reported are those of the file as it is
+            broken += whole < 0;
+            for (long cut = f.scan; cut < f.scan_end; ++cut) {
+                const std::vector<uint8_t> head(f.data.begin(), f.data.begin() + cut);     // exact size: a read past it is seen
+                const int st = decode(f, head, cut, cb, ignore);
+                ++runs;
+                if (st < 0) ++broken;
+                else ++hist[st];
+            }
+            uint32_t lcg = 12345u;
+            std::vector<uint8_t> copy;
+            for (int trial = 0; trial < 400; ++trial) {
+                copy = f.data;
+                const int flips = 1 + trial % 4;
+                for (int k = 0; k < flips; ++k) {
+                    lcg = lcg * 1664525u + 1013904223u;
+                    const long at = f.scan + (long)((lcg >> 8) % (uint32_t)(f.scan_end - f.scan > 0 ? f.scan_end - f.scan : 1));
+                    if (at < n) copy[at] ^= (uint8_t)(1u << (lcg >> 29));
+                }
+                const int st = decode(f, copy, n, cb, ignore);
+                ++runs;
+                if (st < 0) ++broken;
+                else ++hist[st];
+            }
+        }
+        printf("%s: %d x %d, %zu segments, status %d, rounds %ld/%ld/%ld at chunk 16/37/128; %ld damaged runs: status 0/1/2/3 = "
+               "%d/%d/%d/%d, broken %ld\n", argv[a], f.H, f.W, f.begin.size(), whole, rounds[0], rounds[1], rounds[2], runs,
+               hist[0], hist[1], hist[2], hist[3], broken);
+        if (broken) ++failures;
+    }
+    printf("%s\n", failures ? "FAILED" : "ok");
+    return failures ? 1 : 0;
+}
