@@ -40,7 +40,10 @@ JPEG files (DESIGN.md "JPEG files") are the eighth, next to the round trip whose
 markers of a baseline file, and every refusal), ``jpeg_decode_host`` (the definition of ops.jpeg_decode_u8, integers only),
 ``jpeg_encode_host`` (files for tests and benchmarks), ``jpeg_batch`` (files packed for one launch), ``whole_boxes`` and
 ``check_jpeg_status``.  A loader that yields file bytes runs ``model(ops.decode_frames(files, S, boxes).view(B, T, S, S, 3),
-view=flips)``: the compressed bytes are what crosses the host boundary.
+view=flips)``: the compressed bytes are what crosses the host boundary.  Files are 4:2:0 or 4:4:4 unless a call passes
+``layouts`` (DESIGN.md "JPEG layouts"): ``JPEG_LAYOUTS`` names what ``jpeg_parse``, ``jpeg_decode_host``, ``jpeg_batch``,
+``ops.jpeg_decode_u8`` and ``ops.decode_frames`` can be asked to take, 4:2:2 and greyscale files among them, and
+``jpeg_encode_layout_host`` writes such files for tests and benchmarks.
 """
 import math
 from fractions import Fraction
@@ -409,17 +412,25 @@ def _jpeg_upsample(c: Tensor, H: int, W: int) -> Tensor:
     return (3 * col[:, :, this] + col[:, :, other] + (8 - (x & 1)).to(torch.int32)) >> 4
 
 
-def _jpeg_planes_in(src: Tensor, sub: int):
-    """colour in, padding and downsample of jpeg_roundtrip_host: src uint8 (n, H, W, 3) on the host -> Y int32 (n, Hp, Wp)
-    and Cb, Cr int32 (n, Hp / sub, Wp / sub), whole MCUs"""
+def _jpeg_colour_in(src: Tensor, mh: int, mw: int):
+    """src uint8 (n, H, W, 3) padded to whole MCUs of mh x mw pixels by edge replication, colour in -> Y, Cb, Cr int32 (n, Hp,
+    Wp), all at full resolution"""
     H, W = src.shape[1], src.shape[2]
-    mcu = 8 * sub
-    Hp, Wp = -(-H // mcu) * mcu, -(-W // mcu) * mcu
+    Hp, Wp = -(-H // mh) * mh, -(-W // mw) * mw
     rgb = src[:, torch.arange(Hp).clamp_(max=H - 1)][:, :, torch.arange(Wp).clamp_(max=W - 1)].to(torch.int32)
     R, G, B = rgb.unbind(3)
     Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
     Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16
     Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16
+    return Y, Cb, Cr
+
+
+def _jpeg_planes_in(src: Tensor, sub: int):
+    """colour in, padding and downsample of jpeg_roundtrip_host: src uint8 (n, H, W, 3) on the host -> Y int32 (n, Hp, Wp)
+    and Cb, Cr int32 (n, Hp / sub, Wp / sub), whole MCUs"""
+    H = src.shape[1]
+    Y, Cb, Cr = _jpeg_colour_in(src, 8 * sub, 8 * sub)
+    Hp, Wp = Y.shape[1], Y.shape[2]
     if sub == 2:
         bias = torch.tensor([1, 2], dtype=torch.int32).repeat(Wp // 4)
         Cb, Cr = ((c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + bias) >> 2 for c in (Cb, Cr))
@@ -498,6 +509,12 @@ JPEG_MAX_SIDE = 16384
 JPEG_HUFF_INTS = 288                        # a decode table: limit[16], offset[16], values[256] (csrc/jpeg_entropy.h)
 JPEG_IMAGE_INTS = 20                        # a row of the per-image table
 JPEG_IDCT_BLOCKS = 24                       # blocks per workgroup of the IDCT kernel
+# The layouts a file may have: '420' / '444' / '422' are three components sampled 2x2 / 1x1 / 2x1 (Y) and 1x1 (Cb, Cr), 'grey'
+# is Y alone.  What a call accepts is opt-in: without a `layouts` argument it is JPEG_LAYOUTS_DEFAULT.
+JPEG_LAYOUTS = ('420', '444', '422', 'grey')
+JPEG_LAYOUTS_DEFAULT = ('420', '444')
+JPEG_SAMPLINGS = {((2, 2), (1, 1), (1, 1)): '420', ((1, 1), (1, 1), (1, 1)): '444', ((2, 1), (1, 1), (1, 1)): '422'}
+JPEG_LAYOUT_CODES = {'420': 0, '444': 0, '422': 1, 'grey': 2}     # the last int of an images row: ISTVT_JPEG_LAYOUT_*
 
 
 def _std_ac(head, runs):
@@ -523,25 +540,51 @@ JPEG_STD_HUFFMAN = {
 
 
 class JpegHeader:
-    """What jpeg_parse reads from one baseline file.  H, W; sub: the chroma step (2 at 4:2:0, 1 at 4:4:4); mcus = (rows,
-    columns) of MCUs; quant: per component, the 64 entries of its table in natural order; huffman: per component, ((counts,
-    values) of its DC table, (counts, values) of its AC table); restart_interval (0: none); segments: [(begin, end)] byte
-    ranges of `data` between the restart markers, one per restart interval; eoi: whether the scan ended with EOI."""
+    """What jpeg_parse reads from one baseline file.  H, W; layout: one of JPEG_LAYOUTS; factors: (h, v), the luma blocks of
+    an MCU per axis ((1, 1) for 'grey': a one-component scan has one block per MCU whatever the file's factors say); sub: the
+    horizontal chroma step h (2 at 4:2:0, 1 at 4:4:4); mcus = (rows, columns) of MCUs, which are 8 h x 8 v pixels; quant: per
+    component the file has, the 64 entries of its table in natural order; huffman: per component, ((counts, values) of its
+    DC table, (counts, values) of its AC table); restart_interval (0: none); segments: [(begin, end)] byte ranges of `data`
+    between the restart markers, one per restart interval; eoi: whether the scan ended with EOI."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+    @property
+    def mcu_blocks(self) -> tuple:
+        """the component of every block of an MCU, in the order of the scan: (0, 0, 0, 0, 1, 2) at 4:2:0, (0,) for 'grey'"""
+        h, v = self.factors
+        return (0,) * (h * v) + tuple(range(1, len(self.quant)))
+
+    @property
+    def block_factors(self) -> list:
+        """per component, its (h, v) blocks in an MCU"""
+        return [self.factors] + [(1, 1)] * (len(self.quant) - 1)
 
 
 def _jpeg_refuse(text: str):
     raise ValueError('jpeg_parse: ' + text)
 
 
-def jpeg_parse(data) -> JpegHeader:
+def _jpeg_layouts(layouts, who: str = 'jpeg_parse') -> tuple:
+    """the `layouts` argument: a tuple of names from JPEG_LAYOUTS, or 'all'"""
+    if isinstance(layouts, str) and layouts == 'all':
+        return JPEG_LAYOUTS
+    names = layouts if isinstance(layouts, (tuple, list)) else ()
+    if not names or any(not isinstance(v, str) or v not in JPEG_LAYOUTS for v in names):
+        raise ValueError("%s: layouts is 'all' or a tuple of names from %r, got %r" % (who, JPEG_LAYOUTS, layouts))
+    return tuple(layouts)
+
+
+def jpeg_parse(data, layouts=JPEG_LAYOUTS_DEFAULT) -> JpegHeader:
     """The markers of one baseline JPEG file (bytes): SOI, APPn / COM (skipped), DQT, SOF0, DHT, DRI, SOS, and RSTn / EOI
-    inside the scan.  Accepted: 8-bit precision, three components sampled 2x2 / 1x1 / 1x1 or 1x1 / 1x1 / 1x1, one interleaved
-    scan, 8-bit quantisation tables.  Everything else is refused by name (ValueError, 'jpeg_parse: ...').  A scan that ends
-    without EOI runs to the end of the data; restart intervals it no longer holds become empty segments, and decoding
-    reports status 1."""
+    inside the scan.  Accepted: 8-bit precision, one scan of all components, 8-bit quantisation tables, and the layouts named
+    in `layouts` (a tuple of names from JPEG_LAYOUTS, or 'all'): three components sampled 2x2 / 1x1 / 1x1 ('420'), 1x1 / 1x1 /
+    1x1 ('444') or 2x1 / 1x1 / 1x1 ('422'), or one component ('grey', whose sampling factors are read and ignored: T.81
+    A.2.2).  By default '420' and '444' alone.  Everything else is refused by name (ValueError, 'jpeg_parse: ...').  A scan
+    that ends without EOI runs to the end of the data; restart intervals it no longer holds become empty segments, and
+    decoding reports status 1."""
+    layouts = _jpeg_layouts(layouts)
     data = bytes(data)
     n = len(data)
     if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
@@ -596,19 +639,25 @@ def jpeg_parse(data) -> JpegHeader:
             if seg[0] != 8:
                 _jpeg_refuse('%d-bit precision (8 expected)' % seg[0])
             H, W, nf = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
-            if nf != 3:
-                _jpeg_refuse('%d component%s (three expected: Y, Cb, Cr)' % (nf, '' if nf == 1 else 's'))
+            if nf != 3 and not (nf == 1 and 'grey' in layouts):
+                _jpeg_refuse('%d component%s (three expected: Y, Cb, Cr%s)'
+                             % (nf, '' if nf == 1 else 's', '; or one' if 'grey' in layouts else ''))
             if len(seg) != 6 + 3 * nf:
                 _jpeg_refuse('a malformed SOF0 segment')
             if H < 1 or W < 1:
                 _jpeg_refuse('zero width or height (%d x %d)' % (H, W))
             if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
                 _jpeg_refuse('a side above %d (%d x %d)' % (JPEG_MAX_SIDE, H, W))
-            comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(3)]
+            comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(nf)]
             samp = tuple((h, v) for _, h, v, _ in comps)
-            if samp not in (((2, 2), (1, 1), (1, 1)), ((1, 1), (1, 1), (1, 1))):
-                _jpeg_refuse('sampling %s (2x2/1x1/1x1 or 1x1/1x1/1x1 expected)' % '/'.join('%dx%d' % s for s in samp))
-            frame = (H, W, comps)
+            layout = 'grey' if nf == 1 else JPEG_SAMPLINGS.get(samp)
+            if layout not in layouts:
+                # a layout that has a name and was not asked for is refused as it always was
+                names = [k for k, v in JPEG_SAMPLINGS.items() if v in (JPEG_LAYOUTS_DEFAULT if layout else layouts)]
+                names = ['/'.join('%dx%d' % s for s in k) for k in names]
+                _jpeg_refuse('sampling %s (%s expected)' % ('/'.join('%dx%d' % s for s in samp),
+                                                            ' or '.join([', '.join(names[:-1])] * (len(names) > 1) + names[-1:])))
+            frame = (H, W, comps, layout)
         elif m in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF):
             _jpeg_refuse('%s (SOF%d); baseline SOF0 expected'
                          % ('progressive' if m in (0xC2, 0xC6, 0xCA, 0xCE) else 'not baseline', m - 0xC0))
@@ -637,16 +686,18 @@ def jpeg_parse(data) -> JpegHeader:
             _jpeg_refuse('marker %02X at byte %d is not part of a baseline file' % (m, pos - length - 2))
     if frame is None:
         _jpeg_refuse('SOS before SOF0')
-    H, W, comps = frame
+    H, W, comps, layout = frame
+    nf = len(comps)
     ns = seg[0] if seg else 0
-    if ns != 3:
-        _jpeg_refuse('several scans: the first holds %d of the 3 components (one interleaved scan expected)' % ns)
+    if ns != nf:
+        _jpeg_refuse('several scans: the first holds %d of the %d component%s (one %s expected)'
+                     % (ns, nf, 's' if nf > 1 else '', 'interleaved scan' if nf > 1 else 'scan'))
     if len(seg) != 1 + 2 * ns + 3:
         _jpeg_refuse('a malformed SOS segment')
-    if (seg[7], seg[8], seg[9]) != (0, 63, 0):
-        _jpeg_refuse('a scan of coefficients %d..%d, approximation %02X (progressive); 0..63 expected' % (seg[7], seg[8], seg[9]))
+    if tuple(seg[1 + 2 * ns:]) != (0, 63, 0):
+        _jpeg_refuse('a scan of coefficients %d..%d, approximation %02X (progressive); 0..63 expected' % tuple(seg[1 + 2 * ns:]))
     tables = []
-    for c in range(3):
+    for c in range(nf):
         if seg[1 + 2 * c] != comps[c][0]:
             _jpeg_refuse('the scan lists component %d where the frame has %d' % (seg[1 + 2 * c], comps[c][0]))
         td, ta = seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15
@@ -657,8 +708,8 @@ def jpeg_parse(data) -> JpegHeader:
         if (1, ta) not in huff:
             _jpeg_refuse('component %d refers to AC Huffman table %d, which the file never defines' % (c, ta))
         tables.append((huff[(0, td)], huff[(1, ta)]))
-    sub = comps[0][1]
-    mcus = (-(-H // (8 * sub)), -(-W // (8 * sub)))
+    factors = (1, 1) if layout == 'grey' else (comps[0][1], comps[0][2])
+    mcus = (-(-H // (8 * factors[1])), -(-W // (8 * factors[0])))
     # the scan: stuffed FF 00 pairs are data, RSTn splits it, any other marker ends it
     segments, marks = [], []
     begin = at = pos
@@ -693,8 +744,9 @@ def jpeg_parse(data) -> JpegHeader:
         _jpeg_refuse('%d restart intervals in the scan, %d expected (%d MCUs, restart interval %d)'
                      % (len(segments), want, total, ri))
     segments += [(end, end)] * (want - len(segments))
-    return JpegHeader(H=H, W=W, sub=sub, mcus=mcus, quant=tuple(quant[c[3]] for c in comps), huffman=tuple(tables),
-                      restart_interval=ri, segments=segments, eoi=eoi, data=data)
+    return JpegHeader(H=H, W=W, layout=layout, factors=factors, sub=factors[0], mcus=mcus,
+                      quant=tuple(quant[c[3]] for c in comps), huffman=tuple(tables), restart_interval=ri, segments=segments,
+                      eoi=eoi, data=data)
 
 
 def jpeg_huffman_table(counts, values):
@@ -786,53 +838,64 @@ def _jpeg_block(bits: _JpegBits, dc, ac, pred: int, out) -> tuple:
 
 
 def _jpeg_coefficients(hd: JpegHeader):
-    """every segment of a parsed file through the entropy decoder -> (coefficient planes [Y, Cb, Cr], int32 (block rows, 8,
-    block columns, 8) in natural order and whole MCUs, status)"""
-    sub, (my, mx) = hd.sub, hd.mcus
-    planes = [torch.zeros((my * s, mx * s, 64), dtype=torch.int32) for s in (sub, 1, 1)]
+    """every segment of a parsed file through the entropy decoder -> (coefficient planes [Y, Cb, Cr] ([Y] for 'grey'), int32
+    (block rows, 8, block columns, 8) in natural order and whole MCUs, status)"""
+    fac, (my, mx) = hd.block_factors, hd.mcus
+    planes = [torch.zeros((my * v, mx * h, 64), dtype=torch.int32) for h, v in fac]
     tabs = [(jpeg_huffman_table(*dc), jpeg_huffman_table(*ac)) for dc, ac in hd.huffman]
     ri = hd.restart_interval or my * mx
     status = 0
     for i, (begin, end) in enumerate(hd.segments):
         bits = _JpegBits(hd.data, begin, end)
-        pred, dead = [0, 0, 0], 0
+        pred, dead = [0] * len(fac), 0
         for mcu in range(i * ri, min((i + 1) * ri, my * mx)):
             y, x = divmod(mcu, mx)
-            for c in range(3):
-                s = sub if c == 0 else 1
-                for v in range(s):
-                    for h in range(s):
+            for c, (nh, nv) in enumerate(fac):
+                for v in range(nv):
+                    for h in range(nh):
                         if dead:
                             continue                      # the rest of the segment's blocks stay zero
                         blk = [0] * 64
                         dead, pred[c] = _jpeg_block(bits, tabs[c][0], tabs[c][1], pred[c], blk)
-                        planes[c][y * s + v, x * s + h] = torch.tensor(blk, dtype=torch.int32)
+                        planes[c][y * nv + v, x * nh + h] = torch.tensor(blk, dtype=torch.int32)
         status = max(status, dead, bits.status)
     return [p.reshape(p.shape[0], p.shape[1], 8, 8).permute(0, 2, 1, 3) for p in planes], status
 
 
-def jpeg_decode_host(data, return_status: bool = False):
-    """The definition of ops.jpeg_decode_u8, int32 only: one baseline file (bytes, or a JpegHeader) -> uint8 (H, W, 3), with
-    return_status=True (frame, status).
+def _jpeg_upsample_h2v1(c: Tensor, W: int) -> Tensor:
+    """libjpeg's "fancy" h2v1 upsampling of a 4:2:2 chroma plane int32 (n, H, Wc), Wc = ceil(W / 2) -> (n, H, W): 3/4 of the
+    nearer and 1/4 of the farther sample of the row, + 1 (even columns) or + 2 (odd ones), >> 2; the plane's edges replicate"""
+    x = torch.arange(W)
+    this, other = x >> 1, ((x >> 1) + (x & 1) * 2 - 1).clamp_(0, c.shape[2] - 1)
+    return (3 * c[:, :, this] + c[:, :, other] + (1 + (x & 1)).to(torch.int32)) >> 2
+
+
+def jpeg_decode_host(data, return_status: bool = False, layouts=JPEG_LAYOUTS_DEFAULT):
+    """The definition of ops.jpeg_decode_u8, int32 only: one baseline file (bytes, parsed with `layouts`, or a JpegHeader) ->
+    uint8 (H, W, 3), with return_status=True (frame, status).
 
       entropy      canonical Huffman decoding (T.81 F.2.2) of each restart interval: bytes un-stuffed, the DC prediction
                    reset at each restart, coefficients de-zigzagged
       blocks       times the file's own table; _idct8 columns then rows; + 128; clamp
-      chroma       cut to the ceil(H / 2) x ceil(W / 2) samples that belong to the frame, then _jpeg_upsample ('420')
-      colour out   _ycc_to_rgb(..., JFIF_COEFFICIENTS); crop to H x W
+      chroma       cut to the ceil(H / 2) x ceil(W / 2) samples that belong to the frame, then _jpeg_upsample ('420'); cut to
+                   H x ceil(W / 2), then _jpeg_upsample_h2v1, which has no vertical step ('422'); none: Cb = Cr = 128 ('grey')
+      colour out   _ycc_to_rgb(..., JFIF_COEFFICIENTS); crop to H x W.  For 'grey' that is R = G = B = Y
 
     status: 0 fine | 1 bits were needed past the end of a segment (zeros are fed) | 2 a 16-bit prefix with no code, or a DC
     category above 11 | 3 a run that carries the coefficient index past 63.  After 2 or 3 the rest of that segment's blocks
     are zero; the largest status of a file's segments is the file's.  The device gives these bytes where the status is 0
     and the dequantised blocks stay inside libjpeg's 32-bit argument (every file an encoder makes from 8-bit samples)."""
-    hd = data if isinstance(data, JpegHeader) else jpeg_parse(data)
+    hd = data if isinstance(data, JpegHeader) else jpeg_parse(data, layouts)
     coef, status = _jpeg_coefficients(hd)
     H, W = hd.H, hd.W
-    Y, Cb, Cr = (_jpeg_samples((c * torch.tensor(q, dtype=torch.int32).reshape(8, 1, 8)[None])[None])
-                 for c, q in zip(coef, hd.quant))
-    if hd.sub == 2:
-        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    planes = [_jpeg_samples((c * torch.tensor(q, dtype=torch.int32).reshape(8, 1, 8)[None])[None]) for c, q in zip(coef, hd.quant)]
+    Y = planes[0]
+    Cb, Cr = planes[1:] if hd.layout != 'grey' else (torch.full_like(Y, 128),) * 2
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    if hd.layout == '420':
         Cb, Cr = _jpeg_upsample(Cb[:, :Hc, :Wc], H, W), _jpeg_upsample(Cr[:, :Hc, :Wc], H, W)
+    elif hd.layout == '422':
+        Cb, Cr = _jpeg_upsample_h2v1(Cb[:, :H, :Wc], W), _jpeg_upsample_h2v1(Cr[:, :H, :Wc], W)
     out = _ycc_to_rgb(Y[:, :H, :W], Cb[:, :H, :W] - 128, Cr[:, :H, :W] - 128, JFIF_COEFFICIENTS)[0]
     return (out, status) if return_status else out
 
@@ -883,18 +946,28 @@ def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_
     if not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
         raise ValueError('jpeg_header: frames of 1 x 1 to %d x %d, got %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE, H, W))
     ri = jpeg_restart_interval(restart_interval, W, subsampling)
+    return _jpeg_header(H, W, quality, [(sub, sub), (1, 1), (1, 1)], ri)
+
+
+def _jpeg_header(H: int, W: int, quality: int, fac, ri: int) -> bytes:
+    """jpeg_header for components sampled fac = [(h, v)]: Y, or Y, Cb, Cr; component c has id c + 1, and all but Y take the
+    second quantisation table and the second pair of Huffman tables.  All six tables are written whatever the components"""
     qt = jpeg_quant_tables(quality)
     zz = torch.tensor(JPEG_ZIGZAG)
     out = bytearray(b'\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
     for t in range(2):
         out += b'\xff\xdb\x00\x43' + bytes([t]) + bytes(qt[t].reshape(64)[zz].tolist())
-    out += b'\xff\xc0\x00\x11\x08' + bytes([H >> 8, H & 255, W >> 8, W & 255, 3, 1, (sub << 4) | sub, 0, 2, 0x11, 1, 3, 0x11, 1])
+    out += b'\xff\xc0' + bytes([0, 8 + 3 * len(fac), 8, H >> 8, H & 255, W >> 8, W & 255, len(fac)])
+    for c, (h, v) in enumerate(fac):
+        out += bytes([c + 1, (h << 4) | v, min(c, 1)])
     for (tc, th), (counts, values) in sorted(JPEG_STD_HUFFMAN.items()):
         out += b'\xff\xc4' + bytes([(19 + len(values)) >> 8, (19 + len(values)) & 255, (tc << 4) | th]) + bytes(counts) + bytes(values)
     if ri:
         out += b'\xff\xdd\x00\x04' + bytes([ri >> 8, ri & 255])
-    out += b'\xff\xda\x00\x0c\x03\x01\x00\x02\x11\x03\x11\x00\x3f\x00'
-    return bytes(out)
+    out += b'\xff\xda' + bytes([0, 6 + 2 * len(fac), len(fac)])
+    for c in range(len(fac)):
+        out += bytes([c + 1, 0x11 * min(c, 1)])
+    return bytes(out + b'\x00\x3f\x00')
 
 
 def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
@@ -917,7 +990,15 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
     for c, p in enumerate(planes):
         k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
         coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
-    out = bytearray(jpeg_header(H, W, quality, subsampling, ri))
+    my, mx = -(-H // (8 * sub)), -(-W // (8 * sub))
+    return _jpeg_scan(bytearray(jpeg_header(H, W, quality, subsampling, ri)), coef, [(sub, sub), (1, 1), (1, 1)], my, mx, ri)
+
+
+def _jpeg_scan(out: bytearray, coef, fac, my: int, mx: int, ri: int) -> bytes:
+    """The scan writer of the host encoders: behind the header in `out`, my x mx MCUs of components sampled fac = [(h, v)],
+    coef per component [block row][block column][64] in zigzag order; Huffman coding with the Annex K.3 tables (the first
+    pair for Y, the second for the rest), a restart marker and a prediction reset every ri MCUs (0: none), ones to the byte
+    boundary in front of every marker, FF stuffed; EOI -> the file"""
     codes = {k: _huffman_codes(*v) for k, v in JPEG_STD_HUFFMAN.items()}
     acc = nacc = 0
 
@@ -936,21 +1017,19 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
         s = abs(v).bit_length()
         return s, (v if v >= 0 else v + (1 << s) - 1)
 
-    my, mx = -(-H // (8 * sub)), -(-W // (8 * sub))
-    pred = [0, 0, 0]
+    pred = [0] * len(fac)
     for mcu in range(my * mx):
         if ri and mcu and mcu % ri == 0:
             if nacc:
                 put((1 << (8 - nacc)) - 1, 8 - nacc)
             out += bytes([0xFF, 0xD0 + (mcu // ri - 1) % 8])
-            pred = [0, 0, 0]
+            pred = [0] * len(fac)
         y, x = divmod(mcu, mx)
-        for c in range(3):
-            s = sub if c == 0 else 1
+        for c, (nh, nv) in enumerate(fac):
             dc, ac = codes[(0, min(c, 1))], codes[(1, min(c, 1))]
-            for v in range(s):
-                for h in range(s):
-                    blk = coef[c][y * s + v][x * s + h]
+            for v in range(nv):
+                for h in range(nh):
+                    blk = coef[c][y * nv + v][x * nh + h]
                     size, bits = magnitude(blk[0] - pred[c])
                     pred[c] = blk[0]
                     put(*dc[size])
@@ -974,6 +1053,40 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
     if nacc:
         put((1 << (8 - nacc)) - 1, 8 - nacc)
     return bytes(out + b'\xff\xd9')
+
+
+def jpeg_encode_layout_host(u8: Tensor, quality: int, layout: str, restart_interval: int = 0) -> bytes:
+    """jpeg_encode_host for the layouts that have no device encoder, for tests and benchmarks: u8 uint8 (H, W, 3) -> a
+    baseline file in layout '422' or 'grey'.  Colour in is the round trip's; the frame is padded to whole MCUs (16 x 8
+    pixels at '422', 8 x 8 for 'grey') by edge replication; '422' chroma is the mean of horizontal pairs with libjpeg's
+    alternating bias, (a + b + (column & 1)) >> 1 with `column` that of the chroma sample; 'grey' keeps Y alone.  Then
+    _fdct8, quantisation with jpeg_quant_tables(quality) and the scan writer of jpeg_encode_host, with a restart marker every
+    restart_interval MCUs (an int in 0..65535; 0: none)."""
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
+        raise ValueError('jpeg_encode_layout_host expects a non-empty uint8 (H, W, 3) frame')
+    if layout not in ('422', 'grey'):
+        raise ValueError("jpeg_encode_layout_host: the layout is '422' or 'grey' (jpeg_encode_host writes the rest), got %r"
+                         % (layout,))
+    H, W = int(u8.shape[0]), int(u8.shape[1])
+    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+        raise ValueError('jpeg_encode_layout_host: frames of at most %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE))
+    ri = restart_interval
+    if isinstance(ri, bool) or not isinstance(ri, int) or not 0 <= ri <= 65535:
+        raise ValueError('jpeg_encode_layout_host: the restart interval is an int in [0, 65535] MCUs, got %r' % (restart_interval,))
+    qt = jpeg_quant_tables(quality)
+    fac = [(2, 1), (1, 1), (1, 1)] if layout == '422' else [(1, 1)]
+    Y, Cb, Cr = _jpeg_colour_in(u8[None].cpu(), 8, 8 * fac[0][0])
+    planes = [Y]
+    if layout == '422':
+        bias = torch.tensor([0, 1], dtype=torch.int32).repeat(Y.shape[2] // 4)
+        planes += [(c[:, :, 0::2] + c[:, :, 1::2] + bias) >> 1 for c in (Cb, Cr)]
+    zz = torch.tensor(JPEG_ZIGZAG)
+    coef = []
+    for c, p in enumerate(planes):
+        k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
+        coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
+    my, mx = Y.shape[1] // 8, Y.shape[2] // (8 * fac[0][0])
+    return _jpeg_scan(bytearray(_jpeg_header(H, W, quality, fac, ri)), coef, fac, my, mx, ri)
 
 
 def check_encode_qualities(quality, n: int) -> Tensor:
@@ -1038,9 +1151,10 @@ class JpegBatch:
     """Files packed for one launch of ops.jpeg_decode_u8 (jpeg_batch makes it): host tensors, pinned where a device is there
     to take them.  data uint8: the scan bytes of every file, end to end | images int32 (n, 20): H, W, chroma step, MCU
     columns, MCU rows, the quantisation slots of Y, Cb, Cr, the (DC, AC) Huffman slots of Y, Cb, Cr, first block in the
-    scratch, first workgroup of the IDCT, first segment, segments, blocks, 0 | segments int32 (s, 5): image, first byte, end
-    byte, first MCU, MCUs | qtabs int32 (q, 64): the distinct quantisation tables, natural order | htabs int32 (h, 288): the
-    distinct Huffman tables as jpeg_huffman_table makes them | sizes: [(H, W)] | blocks: 8 x 8 blocks of the whole batch."""
+    scratch, first workgroup of the IDCT, first segment, segments, blocks, layout code (JPEG_LAYOUT_CODES) | segments int32
+    (s, 5): image, first byte, end byte, first MCU, MCUs | qtabs int32 (q, 64): the distinct quantisation tables, natural
+    order | htabs int32 (h, 288): the distinct Huffman tables as jpeg_huffman_table makes them | sizes: [(H, W)] | blocks:
+    8 x 8 blocks of the whole batch."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1061,22 +1175,25 @@ class JpegBatch:
         return self._on[key]
 
 
-def jpeg_batch(files) -> JpegBatch:
-    """A sequence of baseline JPEG files (bytes) -> the JpegBatch of one launch.  Every file goes through jpeg_parse, so a
-    file the decoder does not take is refused here, before anything is uploaded.  A JpegFiles (the encoder's result) is read
-    back through its files()."""
+def jpeg_batch(files, layouts=JPEG_LAYOUTS_DEFAULT) -> JpegBatch:
+    """A sequence of baseline JPEG files (bytes) -> the JpegBatch of one launch.  Every file goes through jpeg_parse with
+    `layouts`, so a file the decoder does not take is refused here, before anything is uploaded.  A JpegFiles (the encoder's
+    result) is read back through its files().  A row of a 'grey' image repeats Y's table slots for Cb and Cr."""
+    layouts = _jpeg_layouts(layouts, 'jpeg_batch')
     files = files.files() if isinstance(files, JpegFiles) else list(files)
     if not files:
         raise ValueError('jpeg_batch: an empty batch')
     chunks, images, segments, qtabs, htabs, sizes = [], [], [], {}, {}, []
     nbytes = blocks = groups = 0
     for i, f in enumerate(files):
-        hd = f if isinstance(f, JpegHeader) else jpeg_parse(f)
+        hd = f if isinstance(f, JpegHeader) else jpeg_parse(f, layouts)
         my, mx = hd.mcus
         q = [qtabs.setdefault(t, len(qtabs)) for t in hd.quant]
         h = [htabs.setdefault(t, len(htabs)) for pair in hd.huffman for t in pair]
-        nb = my * mx * (hd.sub * hd.sub + 2)
-        images.append([hd.H, hd.W, hd.sub, mx, my] + q + h + [blocks, groups, len(segments), len(hd.segments), nb, 0])
+        q, h = q + q[:1] * (3 - len(q)), h + h[:2] * (3 - len(hd.huffman))
+        nb = my * mx * len(hd.mcu_blocks)
+        images.append([hd.H, hd.W, hd.sub, mx, my] + q + h + [blocks, groups, len(segments), len(hd.segments), nb,
+                                                              JPEG_LAYOUT_CODES[hd.layout]])
         blocks, groups = blocks + nb, groups + -(-nb // JPEG_IDCT_BLOCKS)
         lo, hi = hd.segments[0][0], hd.segments[-1][1]
         ri = hd.restart_interval or my * mx
@@ -1187,20 +1304,16 @@ class _JpegPosBits:
         return r if r >= (1 << (s - 1)) else r - (1 << s) + 1
 
 
-def _split_component(sub: int, blk: int) -> int:
-    return (0, 0, 0, 0, 1, 2)[blk] if sub == 2 else blk
-
-
-def _split_chunk(data, end, limit, tabs, sub, state):
+def _split_chunk(data, end, limit, tabs, seq, state):
     """The lenient transition of one lane (js_chunk): the symbols from `state` that start before `limit` -> (the exit state,
     blocks started up to the first error, that error or 0).  A prefix no code matches takes 16 bits and counts as 0, a DC
     category above 11 counts as 0, a run past 63 ends the block: it cannot die, and up to the first of these it is the
-    decoder of _jpeg_block."""
+    decoder of _jpeg_block.  seq: the component of every block of an MCU (JpegHeader.mcu_blocks)."""
     pos, bit, blk, k = state
     bits = _JpegPosBits(data, end, pos, bit)
-    nblk, blocks, err = (6 if sub == 2 else 3), 0, 0
+    nblk, blocks, err = len(seq), 0, 0
     while bits.pos < limit:
-        c = _split_component(sub, blk)
+        c = seq[blk]
         done = False
         if k == 0:
             s = bits.huffman(tabs[c][0])
@@ -1236,7 +1349,7 @@ def _split_chunk(data, end, limit, tabs, sub, state):
     return (bits.pos, bits.bit, blk, k), blocks, err
 
 
-def _split_strict(data, end, limit, last, tabs, sub, total, state, nxt):
+def _split_strict(data, end, limit, last, tabs, seq, total, state, nxt):
     """The strict decode of one lane (js_write without its stores): _jpeg_block's steps from a converged state on the symbols
     that start before `limit`, or with last=True until block `total` of the segment would start; nxt: the number of the next
     block to start -> (status, blocks started)"""
@@ -1246,12 +1359,12 @@ def _split_strict(data, end, limit, last, tabs, sub, total, state, nxt):
     if k > 0:
         if not 1 <= nxt <= total:
             return 0, 0
-        c = _split_component(sub, (nxt - 1) % (6 if sub == 2 else 3))
+        c = seq[(nxt - 1) % len(seq)]
     while last or bits.pos < limit:
         if k == 0:
             if nxt >= total:
                 break
-            c = _split_component(sub, nxt % (6 if sub == 2 else 3))
+            c = seq[nxt % len(seq)]
             nxt, started = nxt + 1, started + 1
             s = bits.huffman(tabs[c][0])
             if s < 0 or s > 11:
@@ -1299,8 +1412,8 @@ def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
     segments', jpeg_decode_host's | rounds: the largest.  The fixed point is asserted against one walk from lane 0 on."""
     hd = header if isinstance(header, JpegHeader) else jpeg_parse(header)
     chunk_bytes = check_split(chunk_bytes)
-    sub, (my, mx) = hd.sub, hd.mcus
-    nblk = 6 if sub == 2 else 3
+    seq, (my, mx) = hd.mcu_blocks, hd.mcus
+    nblk = len(seq)
     tabs = [(jpeg_huffman_table(*dc), jpeg_huffman_table(*ac)) for dc, ac in hd.huffman]
     ri = hd.restart_interval or my * mx
     data, segments = hd.data, []
@@ -1313,7 +1426,7 @@ def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
         for j in range(1, S):
             at = begin + j * chunk
             entry.append((at + 1 if data[at - 1] == 0xFF and data[at] == 0 else at, 0, 0, 0))
-        step = [_split_chunk(data, end, limits[j], tabs, sub, entry[j]) for j in range(S - 1)]
+        step = [_split_chunk(data, end, limits[j], tabs, seq, entry[j]) for j in range(S - 1)]
         rounds = 0
         for _ in range(1, S):
             changed = False
@@ -1322,7 +1435,7 @@ def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
                 if before[j - 1] != entry[j]:
                     entry[j] = before[j - 1]
                     if j < S - 1:
-                        new = _split_chunk(data, end, limits[j], tabs, sub, entry[j])
+                        new = _split_chunk(data, end, limits[j], tabs, seq, entry[j])
                         changed = changed or new[0] != step[j][0]
                         step[j] = new
             if not changed:
@@ -1330,14 +1443,14 @@ def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
             rounds += 1
         walk = [(begin, 0, 0, 0)]
         for j in range(S - 1):
-            walk.append(_split_chunk(data, end, limits[j], tabs, sub, walk[j])[0])
+            walk.append(_split_chunk(data, end, limits[j], tabs, seq, walk[j])[0])
         assert entry == walk and rounds <= max(S - 1, 0), 'jpeg_split_host: the relaxation did not reach the sequential states'
         # a lane's first block: the tallies of the lanes in front; the lanes up to the first whose tally met an error decode
         dead = min([j for j in range(S - 1) if step[j][2]], default=S)
         blocks, first, lane_status, nxt = [], [], [], 0
         for j in range(S):
             first.append(min(nxt, total))                         # bits behind the last block can look like blocks
-            st, started = _split_strict(data, end, limits[j], j == S - 1, tabs, sub, total, entry[j], nxt) if j <= dead else (0, 0)
+            st, started = _split_strict(data, end, limits[j], j == S - 1, tabs, seq, total, entry[j], nxt) if j <= dead else (0, 0)
             nxt += step[j][1] if j < S - 1 else 0
             blocks.append(started)
             lane_status.append(st)

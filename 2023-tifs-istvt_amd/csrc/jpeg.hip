@@ -271,6 +271,15 @@ template <int SUB> __device__ __forceinline__ int jp_chroma(const uint8_t* __res
     return (3 * (3 * near[cx] + far[cx]) + 3 * near[ox] + far[ox] + 8 - (x & 1)) >> 4;
 }
 
+// the same at 4:2:2, where the plane has the frame's H x Wc samples and only the columns are interpolated (libjpeg's h2v1
+// "fancy" triangle): 3/4 of the nearer and 1/4 of the farther sample of row y, + 1 (even columns) or + 2 (odd ones), >> 2
+__device__ __forceinline__ int jp_chroma_h2v1(const uint8_t* __restrict__ c, int pw, int Wc, int y, int x) {
+    const int cx = x >> 1;
+    const uint8_t* near = c + (long)y * pw;
+    const int ox = min(max(cx + (x & 1) * 2 - 1, 0), Wc - 1);
+    return (3 * near[cx] + near[ox] + 1 + (x & 1)) >> 2;
+}
+
 // 4 consecutive pixels of the batch per lane; out4 = the output may be written as dwords
 template <int SUB>
 __global__ __launch_bounds__(256) void jpeg_rgb_kernel(const uint8_t* __restrict__ x, const int* __restrict__ quality,
@@ -363,14 +372,18 @@ extern "C" int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, in
 
 // ---- JPEG files ----------------------------------------------------------------------------------------------------------
 // A row of the per-image table (clips.JpegBatch.images) and of the per-segment table
-enum { JD_H = 0, JD_W, JD_SUB, JD_MCUX, JD_MCUY, JD_QUANT, JD_HUFF = 8, JD_BLOCK0 = 14, JD_GROUP0, JD_SEG0, JD_NSEG, JD_NBLOCKS };
+enum { JD_H = 0, JD_W, JD_SUB, JD_MCUX, JD_MCUY, JD_QUANT, JD_HUFF = 8, JD_BLOCK0 = 14, JD_GROUP0, JD_SEG0, JD_NSEG, JD_NBLOCKS,
+       JD_LAYOUT };
 constexpr int JD_IMAGE_INTS = ISTVT_JPEG_IMAGE_INTS;
 constexpr int JD_SEGMENT_INTS = ISTVT_JPEG_SEGMENT_INTS;  // image, first byte, end byte, first MCU, MCUs
 // the scratch, for B blocks in the batch and s segments: int16 coefficients [B][64] | planes, 64 B bytes, per image Y
-// [Hp][Wp], Cb, Cr [Hp / sub][Wp / sub] as the round trip lays them out | int32 status [s]
+// [Hp][Wp], Cb, Cr [Hp / v][Wp / h] as the round trip lays them out (h, v: the luma blocks of an MCU per axis, JeLayout; no
+// Cb, Cr for greyscale) | int32 status [s]
 constexpr long JD_BLOCK_BYTES = 128 + 64;
 
 namespace {
+
+__host__ __device__ __forceinline__ JeLayout jd_layout(const int* im) { return je_layout(im[JD_LAYOUT], im[JD_SUB]); }
 
 // where the entropy decoder puts the blocks of one image: int16 [block][64] in natural order
 struct JdWriter {
@@ -406,7 +419,8 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     const long begin = sg[1], end = sg[2];
     int ok = img >= 0 && img < n && begin >= 0 && begin <= end && end <= nbytes && first >= 0 && count >= 0;
     const int* im = images + (long)(ok ? img : 0) * JD_IMAGE_INTS;
-    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
+    const JeLayout lay = jd_layout(im);
+    const int mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
     ok = ok && (long)first + count <= (long)mcux * mcuy;
     const int* huff[6];
 #pragma unroll
@@ -419,8 +433,8 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
         seg_status[s] = 2;
         return;
     }
-    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * sub, mcux, mcux * sub * mcuy * sub, mcux * mcuy};
-    seg_status[s] = je_decode_segment(bytes, begin, end, huff, sub, mcux, first, count, w);
+    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * lay.h, mcux, mcux * lay.h * mcuy * lay.v, mcux * mcuy};
+    seg_status[s] = je_decode_segment(bytes, begin, end, huff, lay, mcux, first, count, w);
 }
 
 // The state rows of the split path (js_chunk_bytes, js_chunks: the chunk rule): those of segment s start at row begin /
@@ -451,7 +465,8 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
     const long begin = sg[1], end = sg[2];
     int ok = img >= 0 && img < n && begin >= 0 && begin <= end && end <= nbytes && first >= 0 && count >= 0;
     const int* im = images + (long)(ok ? img : 0) * JD_IMAGE_INTS;
-    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
+    const JeLayout lay = jd_layout(im);
+    const int mcux = max(im[JD_MCUX], 1), mcuy = max(im[JD_MCUY], 1);
     ok = ok && (long)first + count <= (long)mcux * mcuy;
     const int* huff[6];
 #pragma unroll
@@ -468,15 +483,11 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
         if (tid == 0) seg_status[s] = 2;
         return;
     }
-    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * sub, mcux, mcux * sub * mcuy * sub, mcux * mcuy};
-    const int nblk = js_mcu_blocks(sub);
-    const long total = (long)count * nblk;                       // blocks of the interval
+    const JdWriter w = {coef, (long)im[JD_BLOCK0], total_blocks, mcux * lay.h, mcux, mcux * lay.h * mcuy * lay.v, mcux * mcuy};
+    const long total = (long)count * js_mcu_blocks(lay);         // blocks of the interval
     for (long at = tid; at < total * 8; at += LANES) {           // a lane clears 16 bytes at a time
-        const long cur = at >> 3;
-        const int mcu = first + (int)(cur / nblk), j = (int)(cur % nblk);
-        const int my = mcu / mcux, mx = mcu - my * mcux;
-        const int c = js_component(sub, j), nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
-        const long b = w.block(c, my * nb + jj / nb, mx * nb + jj % nb);
+        int c;
+        const long b = js_place(lay, mcux, first, at >> 3, w, c);
         if (b >= 0) reinterpret_cast<uint4*>(coef + b * 64)[at & 7] = make_uint4(0u, 0u, 0u, 0u);
     }
     if (tid == 0) sh_dead = JS_LANES, sh_status = 0;
@@ -486,7 +497,7 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
     JsState in = {begin, 0, 0, 0}, out = in;
     JsTally t = {0, 0, {0, 0, 0}};
     if (lane && tid > 0) in = js_guess(bytes, begin, end, begin + (long)tid * chunk);
-    if (inner) out = js_chunk(bytes, end, limit, huff, sub, in, t);
+    if (inner) out = js_chunk(bytes, end, limit, huff, lay, in, t);
     sh_pos[tid] = (int)out.pos, sh_pk[tid] = out.bit | out.blk << 3 | out.k << 6;
     __syncthreads();
     int rounds = 0;
@@ -501,7 +512,7 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
         if (!js_same(nin, in)) {
             in = nin;
             if (inner) {
-                const JsState o = js_chunk(bytes, end, limit, huff, sub, in, t);
+                const JsState o = js_chunk(bytes, end, limit, huff, lay, in, t);
                 changed = !js_same(o, out);
                 out = o;
                 sh_pos[tid] = (int)out.pos, sh_pk[tid] = out.bit | out.blk << 3 | out.k << 6;
@@ -536,7 +547,7 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
     }
     int started = 0, st = 0;
     if (lane && tid <= sh_dead) {
-        st = js_write(bytes, end, limit, tid == S - 1, huff, sub, mcux, first, total, in, next, pred, w, started);
+        st = js_write(bytes, end, limit, tid == S - 1, huff, lay, mcux, first, total, in, next, pred, w, started);
         if (st) atomicMax(&sh_status, st);
     }
     if (lane) {
@@ -567,8 +578,9 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const short* __restrict_
         else hi = mid - 1;
     }
     const int* im = images + (long)lo * JD_IMAGE_INTS;
-    const int sub = im[JD_SUB] == 2 ? 2 : 1, mcux = im[JD_MCUX], mcuy = im[JD_MCUY];
-    const int ybw = mcux * sub, ny = ybw * mcuy * sub, nc = mcux * mcuy, nb = ny + 2 * nc;
+    const JeLayout lay = jd_layout(im);
+    const int mcux = im[JD_MCUX], mcuy = im[JD_MCUY];
+    const int ybw = mcux * lay.h, ny = ybw * mcuy * lay.v, nc = mcux * mcuy, nb = ny + lay.nc * nc;
     const long block0 = im[JD_BLOCK0];
     const int local0 = (g - im[JD_GROUP0]) * JP_BLOCKS;
     if (tid < 192) {
@@ -641,17 +653,20 @@ __global__ __launch_bounds__(256) void jpeg_canvas_kernel(const int* __restrict_
             const int* im = images + f * JD_IMAGE_INTS;
             const int H = im[JD_H], W = im[JD_W];
             if (y < H && xx < W) {
-                const int sub = im[JD_SUB] == 2 ? 2 : 1;
-                const int Wp = im[JD_MCUX] * 8 * sub, Hp = im[JD_MCUY] * 8 * sub;
-                const long plane = (long)Hp * Wp, cplane = plane / (sub * sub);
-                const int pw = Wp / sub, Hs = (H + sub - 1) / sub, Ws = (W + sub - 1) / sub;
+                const JeLayout lay = jd_layout(im);
+                const int pw = im[JD_MCUX] * 8, Wp = pw * lay.h, Hp = im[JD_MCUY] * 8 * lay.v;
+                const long plane = (long)Hp * Wp, cplane = (long)im[JD_MCUY] * 8 * pw;
+                const int Hs = (H + lay.v - 1) / lay.v, Ws = (W + lay.h - 1) / lay.h;
                 const uint8_t* fp = planes + (long)im[JD_BLOCK0] * 64;
                 const int yv = fp[(long)y * Wp + xx];
-                int cb, cr;
-                if (sub == 2) {
+                int cb = 0, cr = 0;                               // greyscale: no chroma is read, R = G = B = Y
+                if (lay.nc != 0 && lay.v == 2) {
                     cb = jp_chroma<2>(fp + plane, pw, Hs, Ws, y, xx) - 128;
                     cr = jp_chroma<2>(fp + plane + cplane, pw, Hs, Ws, y, xx) - 128;
-                } else {
+                } else if (lay.nc != 0 && lay.h == 2) {
+                    cb = jp_chroma_h2v1(fp + plane, pw, Ws, y, xx) - 128;
+                    cr = jp_chroma_h2v1(fp + plane + cplane, pw, Ws, y, xx) - 128;
+                } else if (lay.nc != 0) {
                     cb = jp_chroma<1>(fp + plane, pw, Hs, Ws, y, xx) - 128;
                     cr = jp_chroma<1>(fp + plane + cplane, pw, Hs, Ws, y, xx) - 128;
                 }
@@ -682,15 +697,17 @@ long jpeg_decode_check(const istvt_jpeg_decode_args* a, long* groups) {
     long blocks = 0, grp = 0, seg = 0;
     for (int i = 0; i < a->n; ++i) {
         const int* im = a->images_host + (long)i * JD_IMAGE_INTS;
-        const int H = im[JD_H], W = im[JD_W], sub = im[JD_SUB];
+        const int H = im[JD_H], W = im[JD_W], sub = im[JD_SUB], code = im[JD_LAYOUT];
         if (H < 1 || W < 1 || H > 16384 || W > 16384 || H > a->Hc || W > a->Wc || (sub != 1 && sub != 2)) return -1;
-        const int mcux = (W + 8 * sub - 1) / (8 * sub), mcuy = (H + 8 * sub - 1) / (8 * sub);
+        if (code != 0 && !(code == ISTVT_JPEG_LAYOUT_422 && sub == 2) && !(code == ISTVT_JPEG_LAYOUT_GREY && sub == 1)) return -1;
+        const JeLayout lay = je_layout(code, sub);               // the MCU is 8 h x 8 v pixels
+        const int mcux = (W + 8 * lay.h - 1) / (8 * lay.h), mcuy = (H + 8 * lay.v - 1) / (8 * lay.v);
         if (im[JD_MCUX] != mcux || im[JD_MCUY] != mcuy) return -1;
         for (int c = 0; c < 3; ++c)
             if (im[JD_QUANT + c] < 0 || im[JD_QUANT + c] >= a->nq) return -1;
         for (int k = 0; k < 6; ++k)
             if (im[JD_HUFF + k] < 0 || im[JD_HUFF + k] >= a->nh) return -1;
-        const long mcus = (long)mcux * mcuy, nb = mcus * (sub * sub + 2);
+        const long mcus = (long)mcux * mcuy, nb = mcus * js_mcu_blocks(lay);
         if (im[JD_BLOCK0] != blocks || im[JD_GROUP0] != grp || im[JD_SEG0] != seg || im[JD_NBLOCKS] != nb) return -1;
         if (im[JD_NSEG] < 1 || seg + im[JD_NSEG] > a->nseg) return -1;
         long mcu = 0;

@@ -110,12 +110,28 @@ template <class Writer> JE_HD int je_block(JeBits& s, const int* dc, const int* 
     return 0;
 }
 
+// How an image's blocks lie in its MCUs: v rows of h luma blocks, then nc chroma blocks (Cb, Cr: 2, or 0 for greyscale).
+// The MCU is 8 h x 8 v pixels and a chroma plane has one block per MCU.
+struct JeLayout {
+    int h, v, nc;
+};
+
+// the layout of an images row from its layout code (ISTVT_JPEG_LAYOUT_*) and its chroma step; a code nobody defined reads as 0
+JE_HD JeLayout je_layout(int code, int sub) {
+    const int s = sub == 2 ? 2 : 1;
+    const JeLayout l = {code == ISTVT_JPEG_LAYOUT_GREY ? 1 : code == ISTVT_JPEG_LAYOUT_422 ? 2 : s,
+                        code == ISTVT_JPEG_LAYOUT_GREY || code == ISTVT_JPEG_LAYOUT_422 ? 1 : s,
+                        code == ISTVT_JPEG_LAYOUT_GREY ? 0 : 2};
+    return l;
+}
+
 // One restart interval: bytes [begin, end) of data, MCUs [first_mcu, first_mcu + mcu_count) of an image whose rows hold
-// mcu_cols MCUs and whose chroma step is sub (2: four Y blocks per MCU, 1: one).  huff: the DC and AC tables of Y, Cb, Cr.
+// mcu_cols MCUs of layout lay (4:2:0: four Y blocks per MCU, 4:2:2: two side by side, 4:4:4 and greyscale: one).  huff: the DC
+// and AC tables of Y, Cb, Cr; those of a component the layout does not have are never read, nor is its prediction touched.
 // The writer names a block by component, block row and block column (w.block), clears it (w.clear) and takes its non-zero
 // coefficients (w.put).  Every block of the interval is cleared; after status 2 or 3 the rest stay zero.  -> the status
 template <class Writer>
-JE_HD int je_decode_segment(const uint8_t* data, long begin, long end, const int* const* huff, int sub, int mcu_cols,
+JE_HD int je_decode_segment(const uint8_t* data, long begin, long end, const int* const* huff, const JeLayout& lay, int mcu_cols,
                             int first_mcu, int mcu_count, Writer& w) {
     JeBits s = {data, begin, end, 0u, 0, 0, 0};
     int pred[3] = {0, 0, 0};
@@ -123,11 +139,11 @@ JE_HD int je_decode_segment(const uint8_t* data, long begin, long end, const int
     for (int m = 0; m < mcu_count; ++m) {
         const int mcu = first_mcu + m;
         const int my = mcu / mcu_cols, mx = mcu - my * mcu_cols;
-        for (int c = 0; c < 3; ++c) {
-            const int nb = c == 0 ? sub : 1;
-            for (int v = 0; v < nb; ++v) {
-                for (int h = 0; h < nb; ++h) {
-                    const long block = w.block(c, my * nb + v, mx * nb + h);
+        for (int c = 0; c <= lay.nc; ++c) {
+            const int nv = c == 0 ? lay.v : 1, nh = c == 0 ? lay.h : 1;
+            for (int v = 0; v < nv; ++v) {
+                for (int h = 0; h < nh; ++h) {
+                    const long block = w.block(c, my * nv + v, mx * nh + h);
                     w.clear(block);
                     if (!dead) dead = je_block(s, huff[2 * c], huff[2 * c + 1], pred[c], w, block);
                 }

@@ -8,7 +8,7 @@
 //     pos  the raw index of the byte that holds the next bit (never the stuffed 00 behind an FF; past `end` the zeros that
 //          are fed count on as bytes end, end + 1, ...)
 //     bit  bits of that byte already taken, 0..7
-//     blk  the block within the MCU, 0..5 at 4:2:0 and 0..2 at 4:4:4
+//     blk  the block within the MCU, 0..5 at 4:2:0, 0..2 at 4:4:4, 0..3 at 4:2:2 and 0 for greyscale
 //     k    the coefficient index the next symbol continues at; 0: the next symbol is a DC code
 // Lane 0 knows its state, (begin, 0, 0, 0); every other lane starts from js_guess and the states are relaxed: in every round
 // lane i runs js_chunk from the exit state lane i - 1 had in the round before.  After round r the states of lanes 0..r are
@@ -120,8 +120,20 @@ JE_HD int js_receive(JsBits& s, int size) {
 }
 
 // blocks of an MCU, and the component of block blk of an MCU
-JE_HD int js_mcu_blocks(int sub) { return sub == 2 ? 6 : 3; }
-JE_HD int js_component(int sub, int blk) { return sub == 2 ? (blk < 4 ? 0 : blk < 5 ? 1 : 2) : (blk < 1 ? 0 : blk < 2 ? 1 : 2); }
+JE_HD int js_mcu_blocks(const JeLayout& lay) { return lay.h * lay.v + lay.nc; }
+JE_HD int js_component(const JeLayout& lay, int blk) { return blk < lay.h * lay.v ? 0 : blk - lay.h * lay.v + 1; }
+
+// Where block number cur of an interval that starts at MCU first_mcu lies, as je_decode_segment counts the blocks: the
+// writer's name for it; c: its component
+template <class Writer> JE_HD long js_place(const JeLayout& lay, int mcu_cols, int first_mcu, long cur, Writer& w, int& c) {
+    const int nblk = js_mcu_blocks(lay);     // 6, 3, 4 or 1 (je_layout): no division by a variable
+    const long q = nblk == 6 ? cur / 6 : nblk == 4 ? cur >> 2 : nblk == 3 ? cur / 3 : cur;
+    const int mcu = first_mcu + (int)q, j = (int)(cur - q * nblk);
+    const int my = mcu / mcu_cols, mx = mcu - my * mcu_cols;
+    c = js_component(lay, j);
+    if (c != 0) return w.block(c, my, mx);
+    return lay.h == 2 ? w.block(0, my * lay.v + (j >> 1), mx * 2 + (j & 1)) : w.block(0, my * lay.v + j, mx);
+}
 
 // The guess of lane i >= 1: its boundary, stepped past a stuffed 00, at the start of an MCU
 JE_HD JsState js_guess(const uint8_t* data, long begin, long end, long boundary) {
@@ -132,15 +144,16 @@ JE_HD JsState js_guess(const uint8_t* data, long begin, long end, long boundary)
 
 // The lenient transition of one lane: symbols from state `in` while they start before `limit` (<= end) -> the exit state.
 // t: the strict tallies of the same symbols, frozen at the first error.
-JE_HD JsState js_chunk(const uint8_t* data, long end, long limit, const int* const* huff, int sub, const JsState& in, JsTally& t) {
+JE_HD JsState js_chunk(const uint8_t* data, long end, long limit, const int* const* huff, const JeLayout& lay,
+                       const JsState& in, JsTally& t) {
     JsBits s;
     js_open(s, data, end, in.pos, in.bit);
-    const int nblk = js_mcu_blocks(sub);
+    const int nblk = js_mcu_blocks(lay);
     int blk = in.blk < 0 || in.blk >= nblk ? 0 : in.blk, k = in.k & 63;
     t.blocks = t.err = 0;
     t.pred[0] = t.pred[1] = t.pred[2] = 0;
     while (s.p0 < limit) {
-        const int c = js_component(sub, blk);
+        const int c = js_component(lay, blk);
         bool done = false;                  // the block ends with this symbol
         if (k == 0) {
             int size = js_huffman(s, huff[2 * c]);
@@ -197,35 +210,25 @@ JE_HD JsState js_chunk(const uint8_t* data, long end, long limit, const int* con
 // block's place is counted from first_mcu and its number as je_decode_segment counts it.  The blocks are zero on entry.
 // -> the largest of the error (2, 3) and status 1; started: the blocks this lane started
 template <class Writer>
-JE_HD int js_write(const uint8_t* data, long end, long limit, bool last, const int* const* huff, int sub, int mcu_cols,
-                   int first_mcu, long total, const JsState& in, long next, const int* pred_in, Writer& w, int& started) {
+JE_HD int js_write(const uint8_t* data, long end, long limit, bool last, const int* const* huff, const JeLayout& lay,
+                   int mcu_cols, int first_mcu, long total, const JsState& in, long next, const int* pred_in, Writer& w,
+                   int& started) {
     JsBits s;
     js_open(s, data, end, in.pos, in.bit);
-    const int nblk = js_mcu_blocks(sub);
     int pred[3] = {pred_in[0], pred_in[1], pred_in[2]};
     int k = in.k & 63, c = 0;
     long block = -1;                        // where the block in progress lies; -1: nowhere, its coefficients are dropped
     started = 0;
     if (k > 0 && next >= 1 && next <= total) {
-        const long cur = next - 1;          // the block lane i - 1 left unfinished
-        const int mcu = first_mcu + (int)(cur / nblk), j = (int)(cur % nblk);
-        const int my = mcu / mcu_cols, mx = mcu - my * mcu_cols;
-        c = js_component(sub, j);
-        const int nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
-        block = w.block(c, my * nb + jj / nb, mx * nb + jj % nb);
+        block = js_place(lay, mcu_cols, first_mcu, next - 1, w, c);         // the block lane i - 1 left unfinished
     } else if (k > 0) {
         return 0;                           // no state of a sound walk: nothing in front that a block could continue
     }
     while (last || s.p0 < limit) {
         if (k == 0) {
             if (next >= total) break;
-            const long cur = next++;
+            block = js_place(lay, mcu_cols, first_mcu, next++, w, c);
             ++started;
-            const int mcu = first_mcu + (int)(cur / nblk), j = (int)(cur % nblk);
-            const int my = mcu / mcu_cols, mx = mcu - my * mcu_cols;
-            c = js_component(sub, j);
-            const int nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
-            block = w.block(c, my * nb + jj / nb, mx * nb + jj % nb);
             const int size = js_huffman(s, huff[2 * c]);
             if (size < 0 || size > 11) return 2;
             if (size) pred[c] = (int16_t)(pred[c] + js_receive(s, size));

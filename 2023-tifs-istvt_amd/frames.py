@@ -408,7 +408,8 @@ def _jpeg_split(batch, split):
     return split
 
 
-def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None, split=None):
+def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None, split=None,
+                   layouts=clips.JPEG_LAYOUTS_DEFAULT):
     """JPEG files (clips.py): a batch of baseline JPEG files goes to the device as compressed bytes -> (frames, sizes,
     status): frames uint8 [n, Hc, Wc, 3], image i in the top left H_i x W_i of its canvas and 0 elsewhere, the bits of
     clips.jpeg_decode_host; sizes int32 [n, 2] = (H, W) and status int32 [n] (0: fine; clips.jpeg_decode_host lists the
@@ -424,7 +425,9 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     for files without restart markers, as cameras and most encoders write them; the same bytes come out.  'auto': chunks
     of clips.JPEG_SPLIT_DEFAULT bytes where some interval of the batch is longer than clips.JPEG_SPLIT_AUTO_BYTES (the
     split has a cost: on intervals of one MCU row of a 224-pixel frame it is the slower of the two), else None.  With a split the
-    scratch holds clips.jpeg_split_plan(batch, chunk).scratch_bytes."""
+    scratch holds clips.jpeg_split_plan(batch, chunk).scratch_bytes.  layouts: what clips.jpeg_batch accepts when files are
+    handed over, a tuple of names from clips.JPEG_LAYOUTS or 'all' (4:2:0, 4:4:4, 4:2:2 and greyscale files, mixed as they
+    come); by default 4:2:0 and 4:4:4 alone.  A JpegBatch has been parsed already: the argument is not consulted for it."""
     if isinstance(batch, clips.JpegFiles):                        # the encoder's result: read back, then parsed like any files
         batch = batch.files()
     if isinstance(batch, clips.JpegBatch):
@@ -436,7 +439,7 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
             raise TypeError('jpeg_decode_u8 expects a sequence of files (bytes) or a clips.JpegBatch, got %s' % type(batch).__name__)
         if len(batch) == 0:
             raise RuntimeError('jpeg_decode_u8: empty input (no files)')
-        batch = clips.jpeg_batch(batch)
+        batch = clips.jpeg_batch(batch, layouts)
     chunk = _jpeg_split(batch, split)
     need = batch.scratch_bytes if chunk is None else clips.jpeg_split_plan(batch, chunk).scratch_bytes
     if not torch.cuda.is_available():
@@ -478,12 +481,13 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     return out, sizes, status
 
 
-def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None) -> Tensor:
+def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, layouts=clips.JPEG_LAYOUTS_DEFAULT) -> Tensor:
     """Face crops from JPEG files: files (a sequence of bytes, a clips.JpegBatch or a clips.JpegFiles) are decoded on the device
     (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
     whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
-    and the scorers.  split: jpeg_decode_u8's, for files without restart markers."""
-    batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files)
+    and the scorers.  split: jpeg_decode_u8's, for files without restart markers.  layouts: jpeg_decode_u8's, for files that are
+    not all 4:2:0 or 4:4:4."""
+    batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files, layouts)
     frames, _, _ = jpeg_decode_u8(batch, checked=True, split=split)
     return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)
 

@@ -395,7 +395,12 @@ int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W,
  *   bytes      uint8 [nbytes]: the scans of all files, end to end
  *   images     int32 [n][20]: H, W, chroma step (2 or 1), MCU columns, MCU rows, quantisation slot of Y, Cb, Cr, (DC, AC)
  *              Huffman slots of Y, Cb, Cr, first block, first IDCT workgroup (24 blocks each), first segment, segments,
- *              blocks, 0.  An image's blocks: those of Y, row by row of the plane padded to whole MCUs, then Cb's, then Cr's.
+ *              blocks, layout code.  An image's blocks: those of Y, row by row of the plane padded to whole MCUs, then Cb's,
+ *              then Cr's.  Layout code 0: three components, the chroma step on both axes (4:2:0: MCUs of 16 x 16 pixels and
+ *              2 x 2 Y blocks; 4:4:4: 8 x 8 and one).  ISTVT_JPEG_LAYOUT_422: three components, the chroma step (2) is
+ *              horizontal only, MCUs of 16 x 8 pixels with two Y blocks side by side.  ISTVT_JPEG_LAYOUT_GREY: Y alone, the
+ *              chroma step is 1, MCUs of 8 x 8 pixels and one block, no Cb or Cr blocks; the Cb and Cr slots repeat Y's and
+ *              nothing is read through them.  Any other code, or a chroma step the code does not go with, is -3.
  *   segments   int32 [nseg][5]: image, first byte, end byte, first MCU, MCUs; sorted by image, then by MCU
  *   qtabs      int32 [nq][64], natural order;  htabs int32 [nh][288]: limit[16], offset[16], values[256]
  *   scratch    16-byte aligned, blocks * 192 + nseg * 4 bytes; nothing is read from it before it is written
@@ -406,6 +411,8 @@ int istvt_jpeg_roundtrip_u8(const void* frames, long total, int n, int H, int W,
 #define ISTVT_JPEG_SEGMENT_INTS 5  /* a row of segments */
 #define ISTVT_JPEG_HUFF_INTS 288   /* a table of htabs */
 #define ISTVT_JPEG_IDCT_BLOCKS 24  /* blocks per IDCT workgroup: what "first IDCT workgroup" of an images row counts in */
+#define ISTVT_JPEG_LAYOUT_422 1    /* layout code of an images row: 4:2:2 */
+#define ISTVT_JPEG_LAYOUT_GREY 2   /* ... one component */
 typedef struct istvt_jpeg_decode_args {
     const void* bytes;
     long nbytes;
@@ -432,9 +439,10 @@ int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a);
  * order of their bytes (first byte >= the end byte of the segment before), or -3.
  *   scratch    16-byte aligned; the layout above in front, then from the next multiple of 16 bytes int32
  *              [nbytes / chunk_bytes + nseg][8], the state rows: those of segment s start at row (first byte) / chunk_bytes
- *              + s.  A row: the lane's entry state (byte index in `bytes`, bits of that byte taken, block within the MCU,
- *              coefficient index), blocks it started, its first block within the interval, the status of its decode, the
- *              rounds in which a state of the interval changed.  clips.jpeg_split_plan has the sizes. */
+ *              + s.  A row: the lane's entry state (byte index in `bytes`, bits of that byte taken, block within the MCU
+ *              (0..5 at 4:2:0, 0..2 at 4:4:4, 0..3 at 4:2:2, 0 for greyscale), coefficient index), blocks it started, its
+ *              first block within the interval, the status of its decode, the rounds in which a state of the interval
+ *              changed.  clips.jpeg_split_plan has the sizes. */
 #define ISTVT_JPEG_STATE_INTS 8    /* a state row */
 int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end

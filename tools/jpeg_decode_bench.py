@@ -19,8 +19,15 @@ decode   ops.jpeg_decode_u8 on the uploaded batch with the caller's buffers, eve
          row and a whole file the split starts to pay, which is what split='auto' decides by.
 upload   the compressed batch (scan bytes and tables) against the decoded clip (3 bytes per pixel), both from pinned memory,
          host clock around copy + synchronise.
+--layouts  instead of the above (DESIGN.md "JPEG layouts"): layouts '420' (clips.jpeg_encode_host), '422' and 'grey'
+         (clips.jpeg_encode_layout_host) at quality 75 and 90, restart-less with split=128 and with a marker per MCU row by
+         the default call; the 8 distinct frames are compared with clips.jpeg_decode_host, then the configurations are timed in
+         alternation.  With --against OTHER.so (another build of the library, the parent commit's for instance) the four
+         4:2:0 configurations by the default call, and split=128 on the restart-less ones, are timed through the entry
+         points of both libraries in alternation instead.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -118,8 +125,118 @@ def split_rows(a, lines, res, batch, out, want, buffers, q, ri, chunks):
                ss['min_ms'], ss['max_ms'], sd['median_ms'], sd['min_ms'], sd['max_ms'], sd['median_ms'] / ss['median_ms']))
 
 
+def layout_files(a, layout, q, ri):
+    """the 8 distinct files of a layout and their frames by clips.jpeg_decode_host, from the cache or made here"""
+    path = os.path.join(a.cache, 'jpeg_layouts_bench_%d_%s_q%d_ri%d.npz' % (a.size, layout, q, ri)) if a.cache else None
+    if path and os.path.exists(path):
+        z = np.load(path)
+        return [bytes(z['f%d' % i]) for i in range(DISTINCT)], torch.from_numpy(z['frames'])
+    srcs = [torch.from_numpy(smooth_image(a.size, a.size, 1000 + i)) for i in range(DISTINCT)]
+    files = [clips.jpeg_encode_host(x, q, '420', ri) if layout == '420' else clips.jpeg_encode_layout_host(x, q, layout, ri)
+             for x in srcs]
+    frames = torch.stack([clips.jpeg_decode_host(f, layouts='all') for f in files])
+    if path:
+        os.makedirs(a.cache, exist_ok=True)
+        np.savez(path, frames=frames.numpy(), **{'f%d' % i: np.frombuffer(f, dtype=np.uint8) for i, f in enumerate(files)})
+    return files, frames
+
+
+def entry_call(lib, batch, out, buffers, chunk):
+    """one call of a library's entry point on an uploaded batch, as frames.jpeg_decode_u8 makes it"""
+    from istvt_amd import _lib
+    dev = batch.on(out.device)
+    args = _lib.JpegDecodeArgs(
+        bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
+        segments=dev.segments.data_ptr(), segments_host=batch.segments.data_ptr(), qtabs=dev.qtabs.data_ptr(),
+        htabs=dev.htabs.data_ptr(), scratch=buffers[0].data_ptr(), scratch_bytes=buffers[0].numel(), out=out.data_ptr(),
+        sizes=buffers[1].data_ptr(), status=buffers[2].data_ptr(), stream=None, n=batch.n, nseg=int(batch.segments.shape[0]),
+        nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), Hc=out.shape[1], Wc=out.shape[2])
+    if chunk is None:
+        rc = lib.istvt_jpeg_decode_u8(ctypes.byref(args))
+    else:
+        rc = lib.istvt_jpeg_decode_split_u8(ctypes.byref(args), chunk)
+    if rc != 0:
+        raise SystemExit('the entry point returned %d' % rc)
+
+
+def layouts_main(a):
+    """--layouts: the layout table, or with --against the alternation of two libraries on the 4:2:0 configurations"""
+    from istvt_amd import _lib
+    n, S = a.frames, a.size
+    chunk = clips.JPEG_SPLIT_DEFAULT
+    layouts = ('420',) if a.against else ('420', '422', 'grey')
+    step = {'420': 16, '422': 16, 'grey': 8}
+    configs = [(lay, q, ri, split) for lay in layouts for q in QUALITIES
+               for ri, split in ((0, chunk), (-(-S // step[lay]), None))]
+    if a.against:
+        configs += [(lay, q, 0, None) for lay in layouts for q in QUALITIES]
+    if a.encode_only:
+        for lay, q, ri, _ in configs:
+            nbytes = sum(len(f) for f in layout_files(a, lay, q, ri)[0])
+            print('%s q=%d restart interval %d: %d bytes in %d files' % (lay, q, ri, nbytes, DISTINCT))
+        return
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_decode_bench.py measures on a GPU; none is visible')
+    dev = torch.device('cuda', torch.cuda.current_device())
+    torch.zeros(1, device=dev)
+    libs = [('this', _lib.lib())]
+    if a.against:
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        for name in ('istvt_jpeg_decode_u8', 'istvt_jpeg_decode_split_u8'):
+            getattr(other, name).argtypes, getattr(other, name).restype = _lib.SIGNATURES[name], ctypes.c_int
+        libs.append(('other', other))
+    lines, res, runs = [], {}, []
+    out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
+    for lay, q, ri, split in configs:
+        files, frames = layout_files(a, lay, q, ri)
+        batch = clips.jpeg_batch([files[i % DISTINCT] for i in range(n)], layouts='all')
+        need = batch.scratch_bytes if split is None else clips.jpeg_split_plan(batch, split).scratch_bytes
+        buffers = (torch.empty((need,), dtype=torch.uint8, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                   torch.empty((n,), dtype=torch.int32, device=dev))
+        for name, lib in libs:                                    # the frames before anything is timed
+            out.zero_()
+            entry_call(lib, batch, out, buffers, split)
+            clips.check_jpeg_status(buffers[2])
+            if not torch.equal(out[:DISTINCT].cpu(), frames) or not torch.equal(out[n - DISTINCT:], out[:DISTINCT]):
+                raise SystemExit('%s q=%d ri=%d (%s): the decoded frames are not the definition' % (lay, q, ri, name))
+        runs.append((lay, q, ri, split, batch, buffers))
+    times = {(i, name): [] for i in range(len(runs)) for name, _ in libs}
+    for r in range(a.warmup + a.reps):                            # alternating between configurations and libraries
+        for i, (lay, q, ri, split, batch, buffers) in enumerate(runs):
+            for name, lib in (libs if r % 2 == 0 else libs[::-1]):
+                t = event_ms(lambda: entry_call(lib, batch, out, buffers, split))
+                if r >= a.warmup:
+                    times[(i, name)].append(t)
+    for i, (lay, q, ri, split, batch, buffers) in enumerate(runs):
+        up = sum(t.numel() * t.element_size() for t in (batch.data, batch.images, batch.segments, batch.qtabs, batch.htabs))
+        key = '%s_q%d_ri%d_%s' % (lay, q, ri, 'default' if split is None else 'split%d' % split)
+        res[key] = {'segments': int(batch.segments.shape[0]), 'scan_bytes': batch.nbytes, 'blocks': batch.blocks,
+                    'uploaded_bytes': up, 'decoded_bytes': out.numel()}
+        text = ('%s q=%d, restart interval %d, %s: %d frames of %d x %d, scans %.2f MB, %d blocks, uploaded %.2f MB against '
+                '%.2f MB decoded') \
+            % (lay, q, ri, 'default call' if split is None else 'split=%d' % split, n, S, S, batch.nbytes * 1e-6, batch.blocks,
+               up * 1e-6, out.numel() * 1e-6)
+        for name, _ in libs:
+            st = stats(times[(i, name)])
+            res[key][name] = st
+            text += ' | %s %.3f ms (%.3f-%.3f)' % (name, st['median_ms'], st['min_ms'], st['max_ms'])
+        if a.against:
+            t, o = res[key]['this'], res[key]['other']
+            text += ' | this / other = %.4f, other\'s spread %+.1f %% .. %+.1f %%' % (
+                t['median_ms'] / o['median_ms'], 100 * (o['min_ms'] / o['median_ms'] - 1), 100 * (o['max_ms'] / o['median_ms'] - 1))
+        say(lines, text)
+    line = json.dumps({'jpeg_layouts_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--layouts', action='store_true')
+    ap.add_argument('--against', default=None)
     ap.add_argument('--split', action='store_true')
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--size', type=int, default=224)
@@ -129,6 +246,8 @@ def main():
     ap.add_argument('--encode-only', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.layouts:
+        return layouts_main(a)
     row = -(-a.size // 16)                                        # MCUs of one MCU row at 4:2:0
     configs = [(q, ri) for q in QUALITIES for ri in (0, row)]
     longer = [(QUALITIES[0], k * row) for k in (2, 4, 8)] if a.split else []     # where between a row and a file it starts to pay

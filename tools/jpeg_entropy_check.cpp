@@ -2,13 +2,15 @@
 //
 //     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         -I include -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_check.cpp -o jpeg_entropy_check
-//     python tests/golden/make_jpeg_files_golden.py jpg && ./jpeg_entropy_check jpg/*.jpg
+//     python tests/golden/make_jpeg_files_golden.py jpg && python tests/golden/make_jpeg_layouts_golden.py jpg
+//     ./jpeg_entropy_check jpg/*.jpg
 //
 // For every baseline file named: the markers are read and the segment table rebuilt here (the job of clips.jpeg_parse and
 // clips.jpeg_batch), then je_decode_segment decodes (1) the file as it is, (2) the file cut at every byte length of its scan
 // and (3) copies with bits of the scan flipped by a fixed LCG, the segment table kept.  Each run must come back with a status
 // in 0..3 after clearing exactly the blocks of the image and writing inside them; the coefficient buffer has the exact
 // size, so AddressSanitizer sees any write or read outside.  Prints one line per file, exit status 1 on any failure.
+// The files may be 4:2:0, 4:4:4, 4:2:2 or greyscale.
 // A hand tool for a CPU: it is no test of the suite and nothing here touches a GPU.
 #include <cstdint>
 #include <cstdio>
@@ -25,7 +27,8 @@ struct Table {
 
 struct File {
     std::vector<uint8_t> data;
-    int H = 0, W = 0, sub = 0, ri = 0;
+    int H = 0, W = 0, nf = 0, ri = 0;
+    JeLayout lay = {0, 0, 0};               // h = 0: no SOF0 yet
     int dc[3] = {0, 0, 0}, ac[3] = {0, 0, 0};
     Table huff[2][4];
     bool have[2][4] = {};
@@ -62,10 +65,15 @@ bool parse(File& f) {
         const long sl = len - 2;
         pos += len;
         if (m == 0xC0) {
-            if (sl != 15 || s[0] != 8 || s[5] != 3) return false;
-            f.H = (s[1] << 8) | s[2], f.W = (s[3] << 8) | s[4];
-            f.sub = s[7] >> 4;
-            if (f.H < 1 || f.W < 1 || (s[7] != 0x22 && s[7] != 0x11) || s[10] != 0x11 || s[13] != 0x11) return false;
+            if (sl < 6 || s[0] != 8 || (s[5] != 3 && s[5] != 1) || sl != 6 + 3 * s[5]) return false;
+            f.H = (s[1] << 8) | s[2], f.W = (s[3] << 8) | s[4], f.nf = s[5];
+            if (f.H < 1 || f.W < 1) return false;
+            if (f.nf == 1) {                // one component: one block per MCU whatever its factors say (T.81 A.2.2)
+                f.lay = JeLayout{1, 1, 0};
+            } else {                        // 4:2:0, 4:4:4 or 4:2:2
+                if ((s[7] != 0x22 && s[7] != 0x11 && s[7] != 0x21) || s[10] != 0x11 || s[13] != 0x11) return false;
+                f.lay = JeLayout{s[7] >> 4, s[7] & 15, 2};
+            }
         } else if (m == 0xC4) {
             long at = 0;
             while (at + 17 <= sl) {
@@ -85,9 +93,10 @@ bool parse(File& f) {
             if (sl != 2) return false;
             f.ri = (s[0] << 8) | s[1];
         } else if (m == 0xDA) {
-            if (sl != 10 || s[0] != 3 || f.sub == 0) return false;
-            for (int c = 0; c < 3; ++c) {
-                f.dc[c] = s[2 + 2 * c] >> 4, f.ac[c] = s[2 + 2 * c] & 15;
+            if (f.lay.h == 0 || s[0] != f.nf || sl != 4 + 2 * f.nf) return false;
+            for (int c = 0; c < 3; ++c) {   // the slots of components the file does not have repeat Y's
+                const int at = c < f.nf ? 2 + 2 * c : 2;
+                f.dc[c] = s[at] >> 4, f.ac[c] = s[at] & 15;
                 if (f.dc[c] > 3 || f.ac[c] > 3 || !f.have[0][f.dc[c]] || !f.have[1][f.ac[c]]) return false;
             }
             break;
@@ -145,11 +154,12 @@ struct Writer {
 
 // all segments of a file whose bytes are `bytes` (cut to `limit`) -> the file's status, or -1 on a broken promise
 int decode(const File& f, const std::vector<uint8_t>& bytes, long limit) {
-    const int sub = f.sub, mcux = (f.W + 8 * sub - 1) / (8 * sub), mcuy = (f.H + 8 * sub - 1) / (8 * sub);
+    const JeLayout lay = f.lay;
+    const int mcux = (f.W + 8 * lay.h - 1) / (8 * lay.h), mcuy = (f.H + 8 * lay.v - 1) / (8 * lay.v);
     const long mcus = (long)mcux * mcuy;
     Writer w;
-    w.ybw = mcux * sub, w.cbw = mcux, w.ny = mcux * sub * mcuy * sub, w.nc = mcux * mcuy;
-    w.blocks = w.ny + 2 * w.nc;
+    w.ybw = mcux * lay.h, w.cbw = mcux, w.ny = mcux * lay.h * mcuy * lay.v, w.nc = mcux * mcuy;
+    w.blocks = w.ny + lay.nc * w.nc;
     w.coef.assign(w.blocks * 64, 0x5a5a);
     const int* huff[6];
     for (int c = 0; c < 3; ++c) huff[2 * c] = f.huff[0][f.dc[c]].t, huff[2 * c + 1] = f.huff[1][f.ac[c]].t;
@@ -160,7 +170,7 @@ int decode(const File& f, const std::vector<uint8_t>& bytes, long limit) {
         if (b > limit) b = limit;
         if (e > limit) e = limit;
         const long first = i * ri, count = mcus - first < ri ? mcus - first : ri;
-        const int st = je_decode_segment(bytes.data(), b, e, huff, sub, mcux, (int)first, (int)count, w);
+        const int st = je_decode_segment(bytes.data(), b, e, huff, lay, mcux, (int)first, (int)count, w);
         if (st < 0 || st > 3) return -1;
         if (st > status) status = st;
     }
@@ -186,7 +196,7 @@ int main(int argc, char** argv) {
         while ((got = fread(buf, 1, sizeof buf, fh)) > 0) f.data.insert(f.data.end(), buf, buf + got);
         fclose(fh);
         if (!parse(f)) {
-            printf("%s: not a baseline three-component file this tool reads\n", argv[a]);
+            printf("%s: not a baseline file of a layout this tool reads\n", argv[a]);
             ++failures;
             continue;
         }

@@ -3,7 +3,8 @@
 //
 //     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //         -I include -I 2023-tifs-istvt_amd/csrc tools/jpeg_entropy_split_check.cpp -o jpeg_entropy_split_check
-//     python tests/golden/make_jpeg_files_golden.py jpg && ./jpeg_entropy_split_check jpg/*.jpg
+//     python tests/golden/make_jpeg_files_golden.py jpg && python tests/golden/make_jpeg_layouts_golden.py jpg
+//     ./jpeg_entropy_split_check jpg/*.jpg
 //
 // For every baseline file named: the markers are read and the segment table rebuilt as tools/jpeg_entropy_check.cpp does,
 // then (1) the file as it is, (2) the file cut at every byte length of its scan and (3) copies with 1 to 4 bits of the scan
@@ -12,7 +13,8 @@
 // the tallies, js_write up to the first lane that met an error).  Required: the same coefficients and the same status, every
 // block of the image cleared exactly once, no store outside the image's blocks (the buffer has the exact size, so
 // AddressSanitizer sees one), at most S - 1 rounds and a fixed point at their end.  Prints one line per file, exit status 1
-// on any failure.  A hand tool for a CPU: nothing here touches a GPU.
+// on any failure.  The files may be 4:2:0, 4:4:4, 4:2:2 or greyscale.  A hand tool for a CPU: nothing here touches a
+// GPU.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +30,8 @@ struct Table {
 
 struct File {
     std::vector<uint8_t> data;
-    int H = 0, W = 0, sub = 0, ri = 0;
+    int H = 0, W = 0, nf = 0, ri = 0;
+    JeLayout lay = {0, 0, 0};               // h = 0: no SOF0 yet
     int dc[3] = {0, 0, 0}, ac[3] = {0, 0, 0};
     Table huff[2][4];
     bool have[2][4] = {};
@@ -65,10 +68,15 @@ bool parse(File& f) {
         const long sl = len - 2;
         pos += len;
         if (m == 0xC0) {
-            if (sl != 15 || s[0] != 8 || s[5] != 3) return false;
-            f.H = (s[1] << 8) | s[2], f.W = (s[3] << 8) | s[4];
-            f.sub = s[7] >> 4;
-            if (f.H < 1 || f.W < 1 || (s[7] != 0x22 && s[7] != 0x11) || s[10] != 0x11 || s[13] != 0x11) return false;
+            if (sl < 6 || s[0] != 8 || (s[5] != 3 && s[5] != 1) || sl != 6 + 3 * s[5]) return false;
+            f.H = (s[1] << 8) | s[2], f.W = (s[3] << 8) | s[4], f.nf = s[5];
+            if (f.H < 1 || f.W < 1) return false;
+            if (f.nf == 1) {                // one component: one block per MCU whatever its factors say (T.81 A.2.2)
+                f.lay = JeLayout{1, 1, 0};
+            } else {                        // 4:2:0, 4:4:4 or 4:2:2
+                if ((s[7] != 0x22 && s[7] != 0x11 && s[7] != 0x21) || s[10] != 0x11 || s[13] != 0x11) return false;
+                f.lay = JeLayout{s[7] >> 4, s[7] & 15, 2};
+            }
         } else if (m == 0xC4) {
             long at = 0;
             while (at + 17 <= sl) {
@@ -88,9 +96,10 @@ bool parse(File& f) {
             if (sl != 2) return false;
             f.ri = (s[0] << 8) | s[1];
         } else if (m == 0xDA) {
-            if (sl != 10 || s[0] != 3 || f.sub == 0) return false;
-            for (int c = 0; c < 3; ++c) {
-                f.dc[c] = s[2 + 2 * c] >> 4, f.ac[c] = s[2 + 2 * c] & 15;
+            if (f.lay.h == 0 || s[0] != f.nf || sl != 4 + 2 * f.nf) return false;
+            for (int c = 0; c < 3; ++c) {   // the slots of components the file does not have repeat Y's
+                const int at = c < f.nf ? 2 + 2 * c : 2;
+                f.dc[c] = s[at] >> 4, f.ac[c] = s[at] & 15;
                 if (f.dc[c] > 3 || f.ac[c] > 3 || !f.have[0][f.dc[c]] || !f.have[1][f.ac[c]]) return false;
             }
             break;
@@ -147,8 +156,8 @@ struct Writer {
         ++puts;
     }
     void shape(const File& f, int mcux, int mcuy) {
-        ybw = mcux * f.sub, cbw = mcux, ny = mcux * f.sub * mcuy * f.sub, nc = mcux * mcuy;
-        blocks = ny + 2 * nc;
+        ybw = mcux * f.lay.h, cbw = mcux, ny = mcux * f.lay.h * mcuy * f.lay.v, nc = mcux * mcuy;
+        blocks = ny + f.lay.nc * nc;
         coef.assign(blocks * 64, 0x5a5a);
         cleared.assign(blocks, 0);
     }
@@ -160,15 +169,12 @@ struct Writer {
 };
 
 // One restart interval as the kernel's workgroup decodes it, lane after lane -> its status, or -1 on a broken promise
-int split_segment(const uint8_t* data, long begin, long end, const int* const* huff, int sub, int mcux, int first, int count,
-                  int chunk_bytes, Writer& w, long& rounds_seen) {
-    const int nblk = js_mcu_blocks(sub);
-    const long total = (long)count * nblk;
+int split_segment(const uint8_t* data, long begin, long end, const int* const* huff, const JeLayout& lay, int mcux, int first,
+                  int count, int chunk_bytes, Writer& w, long& rounds_seen) {
+    const long total = (long)count * js_mcu_blocks(lay);
     for (long cur = 0; cur < total; ++cur) {
-        const int mcu = first + (int)(cur / nblk), j = (int)(cur % nblk);
-        const int my = mcu / mcux, mx = mcu - my * mcux;
-        const int c = js_component(sub, j), nb = c == 0 ? sub : 1, jj = c == 0 ? j : 0;
-        w.clear(w.block(c, my * nb + jj / nb, mx * nb + jj % nb));
+        int c;
+        w.clear(js_place(lay, mcux, first, cur, w, c));
     }
     const long chunk = js_chunk_bytes(end - begin, chunk_bytes);
     const int S = js_chunks(end - begin, chunk_bytes);
@@ -179,7 +185,7 @@ int split_segment(const uint8_t* data, long begin, long end, const int* const* h
         in[i] = i ? js_guess(data, begin, end, begin + (long)i * chunk) : JsState{begin, 0, 0, 0};
         out[i] = in[i];
         t[i] = JsTally{0, 0, {0, 0, 0}};
-        if (i < S - 1) out[i] = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, sub, in[i], t[i]);
+        if (i < S - 1) out[i] = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, lay, in[i], t[i]);
     }
     long rounds = 0;
     for (int r = 1; r < S; ++r) {
@@ -189,7 +195,7 @@ int split_segment(const uint8_t* data, long begin, long end, const int* const* h
             if (js_same(seen[i - 1], in[i])) continue;
             in[i] = seen[i - 1];
             if (i < S - 1) {
-                const JsState o = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, sub, in[i], t[i]);
+                const JsState o = js_chunk(data, end, begin + (long)(i + 1) * chunk, huff, lay, in[i], t[i]);
                 changed = changed || !js_same(o, out[i]);
                 out[i] = o;
             }
@@ -208,7 +214,7 @@ int split_segment(const uint8_t* data, long begin, long end, const int* const* h
     int pred[3] = {0, 0, 0}, status = 0;
     for (int i = 0; i < S && i <= dead; ++i) {
         int started = 0;
-        const int st = js_write(data, end, begin + (long)(i + 1) * chunk, i == S - 1, huff, sub, mcux, first, total, in[i], next,
+        const int st = js_write(data, end, begin + (long)(i + 1) * chunk, i == S - 1, huff, lay, mcux, first, total, in[i], next,
                                 pred, w, started);
         if (st < 0 || st > 3) return -1;
         if (st > status) status = st;
@@ -220,7 +226,8 @@ int split_segment(const uint8_t* data, long begin, long end, const int* const* h
 
 // all segments of a file whose bytes are `bytes` (cut to `limit`), both ways -> the file's status, or -1
 int decode(const File& f, const std::vector<uint8_t>& bytes, long limit, int chunk_bytes, long& rounds_seen) {
-    const int sub = f.sub, mcux = (f.W + 8 * sub - 1) / (8 * sub), mcuy = (f.H + 8 * sub - 1) / (8 * sub);
+    const JeLayout lay = f.lay;
+    const int mcux = (f.W + 8 * lay.h - 1) / (8 * lay.h), mcuy = (f.H + 8 * lay.v - 1) / (8 * lay.v);
     const long mcus = (long)mcux * mcuy;
     Writer want, got;
     want.shape(f, mcux, mcuy), got.shape(f, mcux, mcuy);
@@ -233,8 +240,8 @@ int decode(const File& f, const std::vector<uint8_t>& bytes, long limit, int chu
         if (b > limit) b = limit;
         if (e > limit) e = limit;
         const long first = i * ri, count = mcus - first < ri ? mcus - first : ri;
-        const int st = je_decode_segment(bytes.data(), b, e, huff, sub, mcux, (int)first, (int)count, want);
-        const int sp = split_segment(bytes.data(), b, e, huff, sub, mcux, (int)first, (int)count, chunk_bytes, got, rounds_seen);
+        const int st = je_decode_segment(bytes.data(), b, e, huff, lay, mcux, (int)first, (int)count, want);
+        const int sp = split_segment(bytes.data(), b, e, huff, lay, mcux, (int)first, (int)count, chunk_bytes, got, rounds_seen);
         if (st < 0 || st > 3 || sp != st) return -1;
         if (st > status) status = st;
     }
@@ -260,7 +267,7 @@ int main(int argc, char** argv) {
         while ((got = fread(buf, 1, sizeof buf, fh)) > 0) f.data.insert(f.data.end(), buf, buf + got);
         fclose(fh);
         if (!parse(f)) {
-            printf("%s: not a baseline three-component file this tool reads\n", argv[a]);
+            printf("%s: not a baseline file of a layout this tool reads\n", argv[a]);
             ++failures;
             continue;
         }
