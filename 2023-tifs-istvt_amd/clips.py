@@ -43,7 +43,9 @@ markers of a baseline file, and every refusal), ``jpeg_decode_host`` (the defini
 view=flips)``: the compressed bytes are what crosses the host boundary.  Files are 4:2:0 or 4:4:4 unless a call passes
 ``layouts`` (DESIGN.md "JPEG layouts"): ``JPEG_LAYOUTS`` names what ``jpeg_parse``, ``jpeg_decode_host``, ``jpeg_batch``,
 ``ops.jpeg_decode_u8`` and ``ops.decode_frames`` can be asked to take, 4:2:2 and greyscale files among them, and
-``jpeg_encode_layout_host`` writes such files for tests and benchmarks.
+``jpeg_encode_layout_host`` writes such files for tests and benchmarks.  ``jpeg_encode_host(optimize=True)`` (DESIGN.md "JPEG
+files out, optimised tables") codes a file with its own Huffman tables: ``jpeg_symbol_counts``, ``jpeg_optimal_table``
+(libjpeg's, so PIL's ``optimize=True``) and ``jpeg_header_bound``; ``ops.jpeg_encode_u8(optimize=True)`` gives its bytes.
 """
 import math
 from fractions import Fraction
@@ -935,6 +937,7 @@ def jpeg_restart_interval(restart_interval, W: int, subsampling: str = '420') ->
 
 
 JPEG_HEADER_DQT = (25, 94)                  # where the 64 bytes of the two quantisation tables lie in jpeg_header's bytes
+JPEG_HEADER_DHT = (177, 609)                # where the four Huffman table segments of jpeg_header's bytes begin and end
 
 
 def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
@@ -949,9 +952,11 @@ def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_
     return _jpeg_header(H, W, quality, [(sub, sub), (1, 1), (1, 1)], ri)
 
 
-def _jpeg_header(H: int, W: int, quality: int, fac, ri: int) -> bytes:
+def _jpeg_header(H: int, W: int, quality: int, fac, ri: int, tables=None) -> bytes:
     """jpeg_header for components sampled fac = [(h, v)]: Y, or Y, Cb, Cr; component c has id c + 1, and all but Y take the
-    second quantisation table and the second pair of Huffman tables.  All six tables are written whatever the components"""
+    second quantisation table and the second pair of Huffman tables.  All six tables are written whatever the components.
+    tables: {(class, id): (counts, values)} of the four Huffman tables, JPEG_STD_HUFFMAN by default"""
+    tables = JPEG_STD_HUFFMAN if tables is None else tables
     qt = jpeg_quant_tables(quality)
     zz = torch.tensor(JPEG_ZIGZAG)
     out = bytearray(b'\xff\xd8\xff\xe0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')
@@ -960,7 +965,7 @@ def _jpeg_header(H: int, W: int, quality: int, fac, ri: int) -> bytes:
     out += b'\xff\xc0' + bytes([0, 8 + 3 * len(fac), 8, H >> 8, H & 255, W >> 8, W & 255, len(fac)])
     for c, (h, v) in enumerate(fac):
         out += bytes([c + 1, (h << 4) | v, min(c, 1)])
-    for (tc, th), (counts, values) in sorted(JPEG_STD_HUFFMAN.items()):
+    for (tc, th), (counts, values) in sorted(tables.items()):
         out += b'\xff\xc4' + bytes([(19 + len(values)) >> 8, (19 + len(values)) & 255, (tc << 4) | th]) + bytes(counts) + bytes(values)
     if ri:
         out += b'\xff\xdd\x00\x04' + bytes([ri >> 8, ri & 255])
@@ -970,14 +975,138 @@ def _jpeg_header(H: int, W: int, quality: int, fac, ri: int) -> bytes:
     return bytes(out + b'\x00\x3f\x00')
 
 
-def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
+def jpeg_symbol_counts(coef, fac, my: int, mx: int, ri: int) -> list:
+    """How often the scan of _jpeg_scan(out, coef, fac, my, mx, ri) uses every Huffman symbol -> four lists of 256 counts: DC
+    and AC of table id 0 (Y), then DC and AC of table id 1 (the rest).  The walk is _jpeg_scan's: the DC prediction starts
+    at 0 and again every ri MCUs (0: never again), a ZRL per 16 zeros in front of a coded coefficient, an EOB where zeros
+    end the block.  Values are clamped as the device coder clamps them: a DC difference to +-2047, an AC value to +-1023."""
+    counts = [[0] * 256 for _ in range(4)]
+    pred = [0] * len(fac)
+    for mcu in range(my * mx):
+        if ri and mcu and mcu % ri == 0:
+            pred = [0] * len(fac)
+        y, x = divmod(mcu, mx)
+        for c, (nh, nv) in enumerate(fac):
+            dc, ac = counts[2 * min(c, 1)], counts[2 * min(c, 1) + 1]
+            for v in range(nv):
+                for h in range(nh):
+                    blk = coef[c][y * nv + v][x * nh + h]
+                    diff = max(-2047, min(2047, blk[0] - pred[c]))
+                    pred[c] = blk[0]
+                    dc[abs(diff).bit_length()] += 1
+                    run = 0
+                    for k in range(1, 64):
+                        if blk[k] == 0:
+                            run += 1
+                            continue
+                        ac[0xF0] += run >> 4
+                        ac[((run & 15) << 4) | abs(max(-1023, min(1023, blk[k]))).bit_length()] += 1
+                        run = 0
+                    if run:
+                        ac[0] += 1
+    return counts
+
+
+def jpeg_code_lengths(counts):
+    """The first half of jpeg_optimal_table: 256 symbol counts -> (lengths of the 257 symbols before any limiting, 0 for a
+    symbol without a count; the symbols with one, ascending).  No length is above 32."""
+    counts = [int(c) for c in counts]
+    if len(counts) != 256 or min(counts) < 0:
+        raise ValueError('jpeg_optimal_table: 256 non-negative counts expected')
+    if not any(counts):
+        return [0] * 257, []
+    for shift in range(33):
+        freq = [(c + (1 << shift) - 1) >> shift for c in counts] + [1]
+        live = [s for s in range(257) if freq[s]]
+        size, others = [0] * 257, [-1] * 257
+        while True:
+            c1 = c2 = -1
+            for s in live:
+                if freq[s] and (c1 < 0 or freq[s] <= freq[c1]):
+                    c1 = s
+            for s in live:
+                if freq[s] and s != c1 and (c2 < 0 or freq[s] <= freq[c2]):
+                    c2 = s
+            if c2 < 0:
+                break
+            freq[c1] += freq[c2]
+            freq[c2] = 0
+            size[c1] += 1
+            while others[c1] >= 0:
+                c1 = others[c1]
+                size[c1] += 1
+            others[c1] = c2                                       # the chain of c2 behind the chain of c1
+            size[c2] += 1
+            while others[c2] >= 0:
+                c2 = others[c2]
+                size[c2] += 1
+        if max(size) <= 32:
+            break
+    return size, live
+
+
+def jpeg_optimal_table(counts):
+    """256 symbol counts -> (counts16, values): the Huffman table libjpeg's jpeg_gen_optimal_table makes of them, which is
+    what PIL writes with optimize=True.  A reserved symbol 256 with count 1 joins the counted ones, so that no code is all
+    ones.  The two smallest non-zero counts are merged until one is left; among equal counts the larger symbol is taken, for
+    the first and for the second.  A symbol's code length is the number of merges its chain of `others` went through.
+    Lengths above 16 are folded down by the loop of T.81 K.2 from length 32: two codes of length i become one of length
+    i - 1, and a code of the longest shorter length j becomes two of length j + 1.  One code of the longest length is taken
+    out, the reserved symbol's.  Values are ordered by length, then by symbol.  Where a length would pass 32 (libjpeg stops
+    there; the counts of no image of JPEG_MAX_SIDE do it unless they grow like Fibonacci numbers) every count is halved,
+    rounding up, and the merging starts again: at most 32 times, after which all counts are 1.
+    All-zero counts give an empty table, 16 zero counts and no values: no scan symbol refers to such a table, since a
+    component that is coded counts a DC symbol and an AC symbol (a coefficient or EOB) in every block.
+    csrc/jpeg_entropy_opt.h (jo_optimal_table) is the same steps for the device."""
+    size, live = jpeg_code_lengths(counts)
+    if not live:
+        return (0,) * 16, ()
+    bits = [0] * 33
+    for s in live:
+        bits[size[s]] += 1
+    for i in range(32, 16, -1):
+        while bits[i] > 0:
+            j = i - 2
+            while j > 0 and bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while bits[i] == 0:
+        i -= 1
+    bits[i] -= 1
+    values = tuple(s for l in range(1, 33) for s in live if s < 256 and size[s] == l)
+    return tuple(bits[1:17]), values
+
+
+def jpeg_optimal_tables(coef, fac, my: int, mx: int, ri: int) -> dict:
+    """{(class, id): (counts, values)} as _jpeg_header and _jpeg_scan take it: jpeg_optimal_table of jpeg_symbol_counts"""
+    dc0, ac0, dc1, ac1 = (jpeg_optimal_table(c) for c in jpeg_symbol_counts(coef, fac, my, mx, ri))
+    return {(0, 0): dc0, (0, 1): dc1, (1, 0): ac0, (1, 1): ac1}
+
+
+def jpeg_header_bound(H: int, W: int, subsampling: str = '420', restart_interval=0) -> int:
+    """The largest header a file of jpeg_encode_host(optimize=True) can have.  A DC table holds at most the 12 categories
+    0..11 and an AC table at most 160 (run, size) pairs, EOB and ZRL, since the coder clamps a DC difference to +-2047 and an
+    AC value to +-1023: as many values as the Annex K.3 tables list, so the bound is the length of jpeg_header."""
+    return len(jpeg_header(H, W, 50, subsampling, restart_interval))
+
+
+def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0, optimize: bool = False) -> bytes:
     """A baseline JFIF file of one frame, the definition of ops.jpeg_encode_u8: u8 uint8 (H, W, 3) -> bytes.  The front half
     of jpeg_roundtrip_host (colour in, padding, downsample, _fdct8, quantise with jpeg_quant_tables(quality)), then Huffman
     coding with the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none; 'row': every MCU row,
     jpeg_restart_interval).  Its defining property:
-    jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly."""
+    jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly.
+    optimize=True (DESIGN.md "JPEG files out, optimised tables") codes the same coefficients with the frame's own four
+    tables, jpeg_optimal_table of jpeg_symbol_counts, written in the places of the Annex K.3 ones: the header's length then
+    varies with the frame, the scan is never longer, and the file decodes to the same pixels."""
     if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
         raise ValueError('jpeg_encode_host expects a non-empty uint8 (H, W, 3) frame')
+    if not isinstance(optimize, bool):
+        raise ValueError('jpeg_encode_host: optimize is True or False, got %r' % (optimize,))
     sub = _jpeg_sub(subsampling)
     H, W = int(u8.shape[0]), int(u8.shape[1])
     if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
@@ -991,15 +1120,17 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
         k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
         coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
     my, mx = -(-H // (8 * sub)), -(-W // (8 * sub))
-    return _jpeg_scan(bytearray(jpeg_header(H, W, quality, subsampling, ri)), coef, [(sub, sub), (1, 1), (1, 1)], my, mx, ri)
+    fac = [(sub, sub), (1, 1), (1, 1)]
+    tables = jpeg_optimal_tables(coef, fac, my, mx, ri) if optimize else None
+    return _jpeg_scan(bytearray(_jpeg_header(H, W, quality, fac, ri, tables)), coef, fac, my, mx, ri, tables)
 
 
-def _jpeg_scan(out: bytearray, coef, fac, my: int, mx: int, ri: int) -> bytes:
+def _jpeg_scan(out: bytearray, coef, fac, my: int, mx: int, ri: int, tables=None) -> bytes:
     """The scan writer of the host encoders: behind the header in `out`, my x mx MCUs of components sampled fac = [(h, v)],
-    coef per component [block row][block column][64] in zigzag order; Huffman coding with the Annex K.3 tables (the first
-    pair for Y, the second for the rest), a restart marker and a prediction reset every ri MCUs (0: none), ones to the byte
-    boundary in front of every marker, FF stuffed; EOI -> the file"""
-    codes = {k: _huffman_codes(*v) for k, v in JPEG_STD_HUFFMAN.items()}
+    coef per component [block row][block column][64] in zigzag order; Huffman coding with `tables` ({(class, id): (counts,
+    values)}, the Annex K.3 tables by default; the first pair for Y, the second for the rest), a restart marker and a
+    prediction reset every ri MCUs (0: none), ones to the byte boundary in front of every marker, FF stuffed; EOI -> the file"""
+    codes = {k: _huffman_codes(*v) for k, v in (JPEG_STD_HUFFMAN if tables is None else tables).items()}
     acc = nacc = 0
 
     def put(code, length):
@@ -1097,9 +1228,10 @@ def check_encode_qualities(quality, n: int) -> Tensor:
     return q
 
 
-def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', restart_interval='row') -> list:
+def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', optimize: bool = False) -> list:
     """The definition of ops.jpeg_encode_u8 for a batch: frames uint8 (n, H, W, 3) or (B, T, H, W, 3), quality an int or
-    int32 (n,) / (B,) as check_qualities takes it, every entry in 1..100 -> [jpeg_encode_host(frame, its quality, ...)]."""
+    int32 (n,) / (B,) as check_qualities takes it, every entry in 1..100 -> [jpeg_encode_host(frame, its quality, ...)];
+    optimize=True: every file with its own Huffman tables."""
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (4, 5) or frames.shape[-1] != 3 \
             or frames.numel() == 0:
         raise ValueError('jpeg_encode_files_host expects non-empty uint8 (n, H, W, 3) or (B, T, H, W, 3) frames')
@@ -1107,7 +1239,7 @@ def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', re
     if frames.dim() == 5:
         q = q.repeat_interleave(frames.shape[1])
     flat = frames.reshape((-1,) + tuple(frames.shape[-3:])).cpu()
-    return [jpeg_encode_host(f, int(v), subsampling, restart_interval) for f, v in zip(flat, q.tolist())]
+    return [jpeg_encode_host(f, int(v), subsampling, restart_interval, optimize) for f, v in zip(flat, q.tolist())]
 
 
 JPEG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capacity a retry needs', 2: 'quality <= 0: no file',

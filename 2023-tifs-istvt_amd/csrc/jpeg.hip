@@ -32,10 +32,13 @@
 // JPEG files out (DESIGN.md "JPEG files out") are the third part: istvt_jpeg_encode_u8 writes a batch of frames as baseline
 // files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
 // jpeg_count_kernel / jpeg_write_kernel: one lane per restart interval (jpeg_entropy_enc.h), first counting, then storing.
-// jpeg_offsets_kernel between them: the prefix sum that lays the files end to end.
+// jpeg_offsets_kernel between them: the prefix sum that lays the files end to end.  istvt_jpeg_encode_opt_u8 (DESIGN.md
+// "JPEG files out, optimised tables") codes every file with its own Huffman tables: jpeg_tables_kernel counts an image's
+// symbols in LDS and builds the four tables (jpeg_entropy_opt.h), then count, offsets and write with the image's codes.
 #include "istvt_hip.h"
 #include "jpeg_entropy.h"
 #include "jpeg_entropy_enc.h"
+#include "jpeg_entropy_opt.h"
 #include "jpeg_entropy_split.h"
 #include "u8_view.h"
 
@@ -876,9 +879,10 @@ __global__ __launch_bounds__(64) void jpeg_count_kernel(JeGeometry g, const int*
 
 // One workgroup.  The exclusive prefix sum, in one fixed order, of header + segments over the images: lane t sums the t-th
 // run of consecutive segments, the 256 sums are scanned in LDS, lane t walks its run again and writes the places.
-__global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const int* __restrict__ quality, long header_bytes,
-                                                           long capacity, JeSegment* __restrict__ seg, long* __restrict__ offsets,
-                                                           int* __restrict__ status) {
+// header_of(img): the bytes in front of the first segment of a file that has one
+template <class HeaderOf>
+__device__ __forceinline__ void je_offsets(const JeGeometry& g, const int* __restrict__ quality, HeaderOf header_of, long capacity,
+                                           JeSegment* __restrict__ seg, long* __restrict__ offsets, int* __restrict__ status) {
     __shared__ long part[256];
     const int tid = threadIdx.x;
     const long N = (long)g.n * g.nseg, per = (N + 255) / 256;
@@ -887,7 +891,7 @@ __global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const i
     long sum = 0;
     for (long e = lo; e < hi; ++e) {
         const long img = e / g.nseg;
-        sum += (long)(seg[e].size & JE_LENGTH_MASK) + (e == img * g.nseg && quality[img] > 0 ? header_bytes : 0);
+        sum += (long)(seg[e].size & JE_LENGTH_MASK) + (e == img * g.nseg && quality[img] > 0 ? header_of(img) : 0);
     }
     part[tid] = sum;
     __syncthreads();
@@ -904,7 +908,7 @@ __global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const i
         long head = 0;
         if (e == img * g.nseg) {
             offsets[img] = at;
-            head = quality[img] > 0 ? header_bytes : 0;
+            head = quality[img] > 0 ? header_of(img) : 0;
         }
         seg[e].begin = at + head;
         at += head + (long)(size & JE_LENGTH_MASK);
@@ -915,6 +919,20 @@ __global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const i
     __syncthreads();
     for (int i = tid; i < g.n; i += 256)
         if (offsets[i + 1] > capacity) status[i] = 1;            // the file does not fit: nothing of it is written
+}
+
+__global__ __launch_bounds__(256) void jpeg_offsets_kernel(JeGeometry g, const int* __restrict__ quality, long header_bytes,
+                                                           long capacity, JeSegment* __restrict__ seg, long* __restrict__ offsets,
+                                                           int* __restrict__ status) {
+    je_offsets(g, quality, [header_bytes](long) { return header_bytes; }, capacity, seg, offsets, status);
+}
+
+// byte i of the shared header for a frame whose quality scales the Annex K tables by s: the two quantisation tables at dqt0
+// and dqt1 are filled in, in zig-zag order as the file holds them
+__device__ __forceinline__ uint8_t je_header_byte(const uint8_t* __restrict__ header, int i, int dqt0, int dqt1, int s) {
+    const int t = i >= dqt0 && i < dqt0 + 64 ? i - dqt0 : i >= dqt1 && i < dqt1 + 64 ? 64 + i - dqt1 : -1;
+    if (t < 0) return header[i];
+    return (uint8_t)min(max((JP_BASE[(t & 64) + je_zigzag(t & 63)] * s + 50) / 100, 1), 255);
 }
 
 // Workgroups [0, seg_groups): one lane per segment stores what it counted.  Workgroups behind them: one per image copies
@@ -933,13 +951,7 @@ __global__ __launch_bounds__(64) void jpeg_write_kernel(JeGeometry g, int seg_gr
         if (st == 1 || st == 2 || at < 0 || at + header_bytes > capacity) return;
         const int q = min(quality[img], 100);
         const int s = q < 50 ? 5000 / max(q, 1) : 200 - 2 * q;
-        for (int i = tid; i < header_bytes; i += 64) {
-            int v = header[i];
-            const int t = i >= dqt0 && i < dqt0 + 64 ? i - dqt0 : i >= dqt1 && i < dqt1 + 64 ? 64 + i - dqt1 : -1;
-            if (t >= 0)                                           // a table entry: the file holds them in zig-zag order
-                v = min(max((JP_BASE[(t & 64) + je_zigzag(t & 63)] * s + 50) / 100, 1), 255);
-            data[at + i] = (uint8_t)v;
-        }
+        for (int i = tid; i < header_bytes; i += 64) data[at + i] = je_header_byte(header, i, dqt0, dqt1, s);
         return;
     }
     je_stage_codes(codes, tid, 64);
@@ -992,12 +1004,192 @@ template <int SUB> int jpeg_encode_launch(const istvt_jpeg_encode_args* a) {
     return istvt_check_launch();
 }
 
-}  // namespace
+// ---- JPEG files out, optimised tables ------------------------------------------------------------------------------------
+// istvt_jpeg_encode_opt_u8 (DESIGN.md "JPEG files out, optimised tables"): the files above, each coded with its own four
+// Huffman tables.  Five launches: jpeg_planes_kernel<SUB, true> | jpeg_tables_kernel (one workgroup per image: symbol counts
+// in LDS, jo_optimal_table, the image's row of the scratch) | jpeg_count_opt_kernel (one workgroup per image, its code
+// words staged in LDS, one lane per restart interval) | jpeg_offsets_opt_kernel | jpeg_write_opt_kernel.
 
-// Frames uint8 [n][H][W][3] -> n baseline JPEG files end to end in data[0 .. capacity), offsets int64 [n + 1] and status
-// int32 [n] on the device; the argument block is described in include/istvt_hip.h.  Four launches, no synchronisation, no
-// global state, nothing allocated.
-extern "C" int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a) {
+// an image's row behind the segment table: int32 header length | 4 DHT segments JO_DHT_STRIDE apart | JE_CODE_WORDS words
+constexpr int JO_DHT_STRIDE = 288, JO_DHT_MAX = 21 + 256;
+constexpr int JO_ROW_DHT = 16, JO_ROW_CODES = JO_ROW_DHT + 4 * JO_DHT_STRIDE;
+constexpr int JO_ROW_BYTES = ISTVT_JPEG_OPT_ROW_BYTES;
+static_assert(JO_ROW_BYTES == JO_ROW_CODES + 4 * JE_CODE_WORDS && JO_ROW_BYTES % 16 == 0 && JO_ROW_CODES % 16 == 0 &&
+              JO_DHT_MAX <= JO_DHT_STRIDE, "the row of include/istvt_hip.h");
+
+// the sink of jo_count_block on four LDS histograms (JoHistogram's order); integer adds, so the order does not matter
+struct JoLdsHistogram {
+    uint32_t* counts;
+    __device__ __forceinline__ void dc(int id, int sym) { atomicAdd(counts + (id & 1) * 256 + (sym & 255), 1u); }
+    __device__ __forceinline__ void ac(int id, int sym, uint32_t times) { atomicAdd(counts + (2 + (id & 1)) * 256 + (sym & 255), times); }
+};
+
+// the bytes of image img's table segment t as the file holds it: FF C4, length, class and id, 16 counts, the values
+__device__ __forceinline__ int jo_dht_length(const uint8_t* dht) { return min(2 + ((dht[2] << 8) | dht[3]), JO_DHT_MAX); }
+
+// One workgroup per image.  fixed_bytes: the header's bytes outside its table segments
+__global__ __launch_bounds__(256) void jpeg_tables_kernel(JeGeometry g, const int* __restrict__ quality, const short* __restrict__ coef,
+                                                          uint8_t* __restrict__ rows, int fixed_bytes) {
+    __shared__ uint32_t hist[4 * 256];
+    __shared__ JoWork work[4];
+    __shared__ uint32_t words[JE_CODE_WORDS];
+    __shared__ uint8_t dht[4][JO_DHT_STRIDE];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    if (quality[img] <= 0) return;                                // no coefficients, no file: its row stays unwritten
+    for (int i = tid; i < 4 * 256; i += 256) hist[i] = 0;
+    __syncthreads();
+    const JeQuad* blocks = reinterpret_cast<const JeQuad*>(coef + (long)img * g.nb * 64);
+    JoLdsHistogram sink = {hist};
+    for (long b = tid; b < g.nb; b += 256) {
+        int id = 0;
+        const long p = jo_previous_block(b, g.sub, g.mcux, g.mcuy, g.ri, id);
+        const int pred = p < 0 || p >= g.nb ? 0 : (int16_t)(blocks[p * 8].lo & 0xFFFF);
+        jo_count_block(sink, blocks + b * 8, pred, id);
+    }
+    __syncthreads();
+    if ((tid & 63) == 0) {                                        // one table per wave
+        const int t = tid >> 6;
+        uint8_t* d = dht[t];
+        int total = 0;
+        jo_optimal_table(hist + t * 256, d + 5, d + 21, &total, work[t]);
+        total = min(max(total, 0), 256);
+        d[0] = 0xFF, d[1] = 0xC4, d[2] = (uint8_t)((19 + total) >> 8), d[3] = (uint8_t)((19 + total) & 255);
+        d[4] = (uint8_t)(((t >> 1) << 4) | (t & 1));
+        jo_code_words(d + 5, d + 21, total, words + (t < 2 ? JE_CODE_DC + 16 * t : JE_CODE_AC + 256 * (t - 2)), t < 2 ? 16 : 256);
+    }
+    __syncthreads();
+    uint8_t* row = rows + (long)img * JO_ROW_BYTES;
+    if (tid == 0) {
+        int head = fixed_bytes;
+        for (int t = 0; t < 4; ++t) head += jo_dht_length(dht[t]);
+        *reinterpret_cast<int*>(row) = head;
+    }
+    for (int t = 0; t < 4; ++t) {
+        const int len = jo_dht_length(dht[t]);
+        for (int i = tid; i < len; i += 256) row[JO_ROW_DHT + t * JO_DHT_STRIDE + i] = dht[t][i];
+    }
+    uint32_t* codes = reinterpret_cast<uint32_t*>(row + JO_ROW_CODES);
+    for (int i = tid; i < JE_CODE_WORDS; i += 256) codes[i] = words[i];
+}
+
+__device__ __forceinline__ void jo_stage_codes(uint32_t* codes, const uint8_t* rows, int img, int tid, int lanes) {
+    const uint32_t* from = reinterpret_cast<const uint32_t*>(rows + (long)img * JO_ROW_BYTES + JO_ROW_CODES);
+    for (int i = tid; i < JE_CODE_WORDS; i += lanes) codes[i] = from[i];
+    __syncthreads();
+}
+
+// One workgroup per image: lane t takes the image's restart intervals t, t + 64, ...
+__global__ __launch_bounds__(64) void jpeg_count_opt_kernel(JeGeometry g, const int* __restrict__ quality, const short* __restrict__ coef,
+                                                            const uint8_t* __restrict__ rows, JeSegment* __restrict__ seg) {
+    __shared__ uint32_t codes[JE_CODE_WORDS];
+    const int tid = threadIdx.x, img = blockIdx.x;
+    if (quality[img] <= 0) {                                      // no coefficients, an empty file
+        for (int k = tid; k < g.nseg; k += 64) seg[(long)img * g.nseg + k].size = 2ul << JE_STATUS_SHIFT;
+        return;
+    }
+    jo_stage_codes(codes, rows, img, tid, 64);
+    for (int k = tid; k < g.nseg; k += 64) {
+        const long s = (long)img * g.nseg + k;
+        JeCount sink = {0};
+        int status = 0;
+        const long len = je_run_segment(g, coef, s, codes, sink, status);
+        seg[s].size = ((unsigned long)len & JE_LENGTH_MASK) | (unsigned long)status << JE_STATUS_SHIFT;
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_offsets_opt_kernel(JeGeometry g, const int* __restrict__ quality,
+                                                               const uint8_t* __restrict__ rows, long capacity,
+                                                               JeSegment* __restrict__ seg, long* __restrict__ offsets,
+                                                               int* __restrict__ status) {
+    je_offsets(g, quality, [rows](long img) { return (long)*reinterpret_cast<const int*>(rows + img * JO_ROW_BYTES); }, capacity,
+               seg, offsets, status);
+}
+
+// Workgroups [0, n): the lanes of jpeg_count_opt_kernel store what they counted.  Workgroups [n, 2 n): one per image writes
+// the header: the shared bytes in front of dht0 with the quality's two quantisation tables, the image's four table
+// segments, the shared bytes from dht1 on (DRI, SOS)
+__global__ __launch_bounds__(64) void jpeg_write_opt_kernel(JeGeometry g, const int* __restrict__ quality, const short* __restrict__ coef,
+                                                            const JeSegment* __restrict__ seg, const uint8_t* __restrict__ rows,
+                                                            const uint8_t* __restrict__ header, int header_bytes, int dqt0, int dqt1,
+                                                            int dht0, int dht1, const long* __restrict__ offsets,
+                                                            const int* __restrict__ status, uint8_t* __restrict__ data, long capacity) {
+    __shared__ uint32_t codes[JE_CODE_WORDS];
+    const int tid = threadIdx.x;
+    const int img = (int)blockIdx.x < g.n ? blockIdx.x : blockIdx.x - g.n;
+    const int st = status[img];
+    if (st == 1 || st == 2) return;
+    if ((int)blockIdx.x >= g.n) {
+        const uint8_t* row = rows + (long)img * JO_ROW_BYTES;
+        const long at = offsets[img];
+        int len[4], head = header_bytes - (dht1 - dht0);
+        for (int t = 0; t < 4; ++t) head += len[t] = jo_dht_length(row + JO_ROW_DHT + t * JO_DHT_STRIDE);
+        if (at < 0 || at + head > capacity || offsets[img + 1] - at < head) return;
+        const int q = min(quality[img], 100);
+        const int s = q < 50 ? 5000 / max(q, 1) : 200 - 2 * q;
+        for (int i = tid; i < dht0; i += 64) data[at + i] = je_header_byte(header, i, dqt0, dqt1, s);
+        long to = at + dht0;
+        for (int t = 0; t < 4; ++t) {
+            for (int i = tid; i < len[t]; i += 64) data[to + i] = row[JO_ROW_DHT + t * JO_DHT_STRIDE + i];
+            to += len[t];
+        }
+        for (int i = dht1 + tid; i < header_bytes; i += 64) data[to + i - dht1] = header[i];
+        return;
+    }
+    jo_stage_codes(codes, rows, img, tid, 64);
+    for (int k = tid; k < g.nseg; k += 64) {
+        const long s = (long)img * g.nseg + k;
+        const long begin = seg[s].begin, len = (long)(seg[s].size & JE_LENGTH_MASK);
+        if (begin < 0 || begin + len > capacity) continue;        // cannot be, with status 0 or 3; keeps a store inside data
+        JeStore sink = {data, begin, len, 0};
+        int ignored = 0;
+        je_run_segment(g, coef, s, codes, sink, ignored);
+    }
+}
+
+template <int SUB> int jpeg_encode_opt_launch(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
+    constexpr int MCU = 8 * SUB;
+    const int H = a->H, W = a->W, n = a->n;
+    const int Hp = (H + MCU - 1) / MCU * MCU, Wp = (W + MCU - 1) / MCU * MCU;
+    JeGeometry g;
+    g.n = n, g.sub = SUB, g.mcux = Wp / MCU, g.mcuy = Hp / MCU;
+    const long mcus = (long)g.mcux * g.mcuy;
+    g.ri = (int)(a->restart_interval ? min((long)a->restart_interval, mcus) : mcus);
+    const long nseg = (mcus + g.ri - 1) / g.ri;
+    g.nb = mcus * (SUB * SUB + 2);
+    const long blocks = g.nb * n, segments = nseg * n;
+    const int tiles_y = Hp / MCU, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
+    const long tiles = (long)n * tiles_y * tiles_x;
+    if (tiles > 0x7fffffffL || segments > 0x7fffffffL - 64 - n || blocks > 0x7fffffffL || 2L * n > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    if (a->scratch_bytes < blocks * 128 + segments * (long)sizeof(JeSegment) + (long)n * JO_ROW_BYTES) return ISTVT_ERR_SHAPE;
+    g.nseg = (int)nseg;
+    uint8_t* coef = (uint8_t*)a->scratch;
+    JeSegment* seg = (JeSegment*)(coef + blocks * 128);
+    uint8_t* rows = (uint8_t*)(seg + segments);
+    const uint8_t* x = (const uint8_t*)a->frames;
+    hipLaunchKernelGGL((jpeg_planes_kernel<SUB, true>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
+                       coef, H, W, Hp, Wp, tiles_y, tiles_x);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)n), dim3(256), 0, a->stream, g, a->quality, (const short*)coef, rows,
+                       (int)a->header_bytes - (dht1 - dht0));
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_count_opt_kernel, dim3((unsigned)n), dim3(64), 0, a->stream, g, a->quality, (const short*)coef,
+                       (const uint8_t*)rows, seg);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_offsets_opt_kernel, dim3(1), dim3(256), 0, a->stream, g, a->quality, (const uint8_t*)rows, a->capacity,
+                       seg, a->offsets, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_write_opt_kernel, dim3(2u * (unsigned)n), dim3(64), 0, a->stream, g, a->quality, (const short*)coef,
+                       (const JeSegment*)seg, (const uint8_t*)rows, (const uint8_t*)a->header, (int)a->header_bytes, a->dqt0, a->dqt1,
+                       dht0, dht1, (const long*)a->offsets, (const int*)a->status, (uint8_t*)a->data, a->capacity);
+    return istvt_check_launch();
+}
+
+// what both encoder entries refuse before any launch, but for the size of the scratch
+int jpeg_encode_refusal(const istvt_jpeg_encode_args* a) {
     if (!a || a->n <= 0 || !a->frames || !a->quality || !a->header || !a->scratch || !a->data || !a->offsets || !a->status)
         return ISTVT_ERR_SHAPE;
     if (a->H < 1 || a->W < 1 || a->H > 16384 || a->W > 16384) return ISTVT_ERR_SHAPE;
@@ -1013,5 +1205,24 @@ extern "C" int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a) {
     const uint8_t* x = (const uint8_t*)a->frames;
     const uint8_t* d = (const uint8_t*)a->data;
     if (d < x + bytes && x < d + a->capacity) return ISTVT_ERR_SHAPE;
+    return ISTVT_OK;
+}
+
+}  // namespace
+
+// Frames uint8 [n][H][W][3] -> n baseline JPEG files end to end in data[0 .. capacity), offsets int64 [n + 1] and status
+// int32 [n] on the device; the argument block is described in include/istvt_hip.h.  Four launches, no synchronisation, no
+// global state, nothing allocated.
+extern "C" int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a) {
+    const int rc = jpeg_encode_refusal(a);
+    if (rc != ISTVT_OK) return rc;
     return a->subsampling == 2 ? jpeg_encode_launch<2>(a) : jpeg_encode_launch<1>(a);
+}
+
+// The same with every file's own Huffman tables in the place of header[dht0 .. dht1): five launches
+extern "C" int istvt_jpeg_encode_opt_u8(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
+    const int rc = jpeg_encode_refusal(a);
+    if (rc != ISTVT_OK) return rc;
+    if (dht0 < a->dqt1 + 64 || dht1 <= dht0 || dht1 > a->header_bytes) return ISTVT_ERR_SHAPE;
+    return a->subsampling == 2 ? jpeg_encode_opt_launch<2>(a, dht0, dht1) : jpeg_encode_opt_launch<1>(a, dht0, dht1);
 }

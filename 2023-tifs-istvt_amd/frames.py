@@ -506,7 +506,7 @@ def _jpeg_header_on(device, H: int, W: int, subsampling: str, ri: int):
 
 
 def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', capacity: Optional[int] = None,
-                   out: Optional[Tensor] = None, checked: bool = False) -> 'clips.JpegFiles':
+                   out: Optional[Tensor] = None, checked: bool = False, optimize: bool = False) -> 'clips.JpegFiles':
     """JPEG files out (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3], contiguous, on the device, quality int32 [n] per
     frame or, for clips, [B] shared by the T frames of a clip (or an int for all), every entry in 1..100 -> a clips.JpegFiles
     on the device: the baseline JFIF files of clips.jpeg_encode_files_host end to end in `data`, byte for byte, with `offsets`
@@ -516,7 +516,13 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
     entry <= 0 then gives an empty file with status 2.  capacity: the bytes of `data`, by default n * (H * W * 3 + header); a
     file that does not fit (noise at quality 100; a frame of a few pixels, whose file still codes a whole MCU) gets status 1,
     nothing of it is written, and offsets[n] still says what a retry needs.  `out` (uint8, one dimension, contiguous, no
-    overlap with the frames) is used as `data`.  Nothing synchronises."""
+    overlap with the frames) is used as `data`.  Nothing synchronises.
+    optimize=True (PIL's word for it): every file is coded with its own four Huffman tables, the bytes of
+    clips.jpeg_encode_files_host(optimize=True): fewer scan bytes for every later decode, for one more launch now.  Its header
+    is at most the standard one's (clips.jpeg_header_bound), so the default capacity is the same.  The scratch of that entry
+    is 128 bytes per block + 16 per restart interval + 3344 per frame."""
+    if not isinstance(optimize, bool):
+        raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     n, T, H, W = _rgb_source('jpeg_encode_u8', frames, contiguous=True, on_device=False)
     sub = clips._jpeg_sub(subsampling)
     ri = clips.jpeg_restart_interval(restart_interval, W, subsampling)
@@ -537,6 +543,7 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
             raise ValueError('jpeg_encode_u8: capacity %d and out of %d bytes disagree' % (int(capacity), out.numel()))
         data = out
     else:
+        # (hlen is clips.jpeg_header_bound(H, W, subsampling, ri): no optimised header is longer than the standard one)
         capacity = n * (H * W * 3 + hlen) if capacity is None else int(capacity)
         if capacity < 1:
             raise ValueError('jpeg_encode_u8: the capacity must be positive, got %d' % capacity)
@@ -545,33 +552,49 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
     _no_overlap('jpeg_encode_u8', data, frames.data_ptr(), nbytes, 'frames')
     mcus = (-(-H // (8 * sub))) * (-(-W // (8 * sub)))
     blocks, segments = n * mcus * (sub * sub + 2), n * (-(-mcus // min(ri, mcus)) if ri else 1)
-    scratch = torch.empty((128 * blocks + 16 * segments,), dtype=torch.uint8, device=frames.device)
+    scratch = torch.empty((jpeg_encode_scratch_bytes(blocks, segments, n, optimize),), dtype=torch.uint8, device=frames.device)
     offsets = torch.empty((n + 1,), dtype=torch.int64, device=frames.device)
     status = torch.empty((n,), dtype=torch.int32, device=frames.device)
-    _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri)
+    _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri, optimize)
     return clips.JpegFiles(data, offsets, status)
 
 
-def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri) -> None:
+JPEG_OPT_ROW_BYTES = 3344                   # ISTVT_JPEG_OPT_ROW_BYTES of include/istvt_hip.h: an image's tables in the scratch
+
+
+def jpeg_encode_scratch_bytes(blocks: int, segments: int, n: int, optimize: bool = False) -> int:
+    """the scratch of istvt_jpeg_encode_u8: 128 bytes per 8 x 8 block of the batch + 16 per restart interval; of
+    istvt_jpeg_encode_opt_u8 (optimize=True): + JPEG_OPT_ROW_BYTES per frame"""
+    return 128 * blocks + 16 * segments + (JPEG_OPT_ROW_BYTES * n if optimize else 0)
+
+
+def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri, optimize=False) -> None:
     """the entry on buffers that are all the caller's (tests put sentinels around them)"""
     args = _lib.JpegEncodeArgs(
         frames=frames.data_ptr(), total=nbytes, quality=qdev.data_ptr(), header=header.data_ptr(), header_bytes=hlen,
         scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(), capacity=data.numel(),
         offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W, subsampling=2 if sub == 2 else 0,
         restart_interval=ri, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+    if optimize:
+        with prof('jpeg_encode_opt_u8', nbytes + 4 * scratch.numel()):
+            _lib.check(_lib.lib().istvt_jpeg_encode_opt_u8(ctypes.byref(args), *clips.JPEG_HEADER_DHT), 'istvt_jpeg_encode_opt_u8')
+        return
     with prof('jpeg_encode_u8', nbytes + 3 * scratch.numel()):   # + the files' bytes, which live on the device
         _lib.check(_lib.lib().istvt_jpeg_encode_u8(ctypes.byref(args)), 'istvt_jpeg_encode_u8')
 
 
 def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None, quality=90,
-                  subsampling: str = '420', restart_interval='row') -> 'clips.JpegFiles':
+                  subsampling: str = '420', restart_interval='row', optimize: bool = False) -> 'clips.JpegFiles':
     """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
     cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
-    (jpeg_encode_u8) -> a clips.JpegFiles, whose files() ops.decode_frames and clips.jpeg_batch take."""
+    (jpeg_encode_u8; optimize=True: with their own Huffman tables) -> a clips.JpegFiles, whose files() ops.decode_frames and
+    clips.jpeg_batch take."""
     if (boxes is None) == (transforms is None):
         raise ValueError('encode_frames: boxes and transforms are two ways to cut the same crop: pass one of them')
+    if not isinstance(optimize, bool):
+        raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
-    return jpeg_encode_u8(crops, quality, subsampling, restart_interval)
+    return jpeg_encode_u8(crops, quality, subsampling, restart_interval, optimize=optimize)
 
 
 def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,

@@ -477,6 +477,20 @@ typedef struct istvt_jpeg_encode_args {
     int n, H, W, subsampling, restart_interval, dqt0, dqt1;
 } istvt_jpeg_encode_args;
 int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a);
+/* JPEG files out with optimised Huffman tables: istvt_jpeg_encode_u8 with every file coded by its own four tables, those
+ * libjpeg's jpeg_gen_optimal_table makes of the file's symbol counts -> the bytes of clips.jpeg_encode_host(optimize=True).
+ * The same argument block, the same checks, and offsets and status as above.  `header` is the same standard header;
+ * [dht0, dht1) are the bytes of its four Huffman table segments (dqt1 + 64 <= dht0 < dht1 <= header_bytes), which every file
+ * replaces by its own, so a file's header is at most header_bytes long.  Five launches on the stream (coefficients; one
+ * workgroup per image counts symbols in LDS and builds the tables; one workgroup per image counts the bytes of its restart
+ * intervals; one workgroup takes the prefix sum with the per-image header lengths; the same lanes store), no
+ * synchronisation, no global atomics, nothing allocated, nothing that has to be zeroed.
+ *   scratch    16-byte aligned, 128 bytes per 8 x 8 block + 16 bytes per restart interval as above, then
+ *              ISTVT_JPEG_OPT_ROW_BYTES per image: int32 header length (16 bytes), four Huffman table segments of up to 277
+ *              bytes 288 bytes apart (DC 0, DC 1, AC 0, AC 1), then 544 code words (code << 8 | length; 16 + 16 DC, 256 + 256
+ *              AC).  A row of an image whose quality is <= 0 is not written. */
+#define ISTVT_JPEG_OPT_ROW_BYTES 3344
+int istvt_jpeg_encode_opt_u8(const istvt_jpeg_encode_args* a, int dht0, int dht1);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

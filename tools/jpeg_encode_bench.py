@@ -15,8 +15,17 @@ decode   ops.jpeg_decode_u8 on the encoder's own 'row' files (parsed and packed 
          ops.jpeg_roundtrip_u8
 
 and last one batch of 1080 x 1920 frames, as VideoScorer.render_explanation(jpeg_quality=75) encodes them: 4:2:0, 'row'.
+
+--optimize  instead of the above (DESIGN.md "JPEG files out, optimised tables"): per configuration, after checking two
+         distinct files of ops.jpeg_encode_u8(optimize=True) against clips.jpeg_encode_host(optimize=True), the optimised
+         call and the standard call in alternation (encode time, file bytes, scan bytes), then ops.jpeg_decode_u8 on the
+         optimised files and on the standard files in alternation: the default call on 'row' files, split=128 on
+         restart-less ones; both decodes must give the same frames.  With --against OTHER.so (another build of the library,
+         the parent commit's) the standard entry of both libraries is also called in alternation on the same argument block:
+         whether this commit's median lies inside the other's own min-max spread.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -83,8 +92,93 @@ def alternate(a, first, second):
     return stats(ta), stats(tb)
 
 
+def optimize_main(a):
+    from istvt_amd import _lib, frames as F
+    n, S = a.frames, a.size
+    lines, res = [], {}
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    raw_dev = src.repeat((-(-n // DISTINCT), 1, 1, 1))[:n].contiguous().cuda()
+    dev = raw_dev.device
+    data = [torch.empty((raw_dev.numel(),), dtype=torch.uint8, device=dev) for _ in range(2)]
+    out = [torch.empty_like(raw_dev) for _ in range(2)]
+    other = None
+    if a.against:
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        other.istvt_jpeg_encode_u8.argtypes, other.istvt_jpeg_encode_u8.restype = _lib.SIGNATURES['istvt_jpeg_encode_u8'], ctypes.c_int
+    for q in QUALITIES:
+        qdev = torch.full((n,), q, dtype=torch.int32, device=dev)
+        for ri in ('row', 0):
+            if a.only and a.only != 'q%d_%s' % (q, ri):
+                continue
+
+            def encode(optimize):
+                return ops.jpeg_encode_u8(raw_dev, qdev, '420', ri, out=data[optimize], checked=True, optimize=bool(optimize))
+            files = [encode(0).files(), encode(1).files()]
+            for i in (0, DISTINCT - 1):
+                if files[1][i] != clips.jpeg_encode_host(src[i], q, '420', ri, optimize=True) or files[1][n - DISTINCT + i] != files[1][i]:
+                    raise SystemExit('q=%d ri=%s: optimised file %d is not the definition' % (q, ri, i))
+            so, ss = alternate(a, lambda: encode(1), lambda: encode(0))
+            batches = [clips.jpeg_batch(f) for f in files]
+            split = None if ri == 'row' else clips.JPEG_SPLIT_DEFAULT
+
+            def decode(k):
+                return ops.jpeg_decode_u8(batches[k], out=out[k], checked=True, split=split)
+            for k in range(2):
+                clips.check_jpeg_status(decode(k)[2])
+            if not torch.equal(out[0], out[1]):
+                raise SystemExit('q=%d ri=%s: the optimised files do not decode to the frames of the standard files' % (q, ri))
+            do, ds = alternate(a, lambda: decode(1), lambda: decode(0))
+            key = 'q%d_%s' % (q, ri)
+            nb = [sum(len(f) for f in fs) for fs in files]
+            res[key] = {'frames': n, 'size': S, 'file_bytes': nb[0], 'file_bytes_opt': nb[1], 'scan_bytes': batches[0].nbytes,
+                        'scan_bytes_opt': batches[1].nbytes, 'encode': ss, 'encode_opt': so, 'decode': ds, 'decode_opt': do,
+                        'decode_call': 'default' if split is None else 'split=%d' % split}
+            say(lines, 'q=%d, restart interval %s, %d frames of %d x %d | encode optimised %s against standard %s beside it = %.2f x | '
+                'files %.3f MB against %.3f MB = %.3f, scans %.3f MB against %.3f MB = %.3f | jpeg_decode_u8 (%s) on the optimised '
+                'files %s against %s on the standard ones = %.3f'
+                % (q, ri, n, S, S, fmt(so), fmt(ss), so['median_ms'] / ss['median_ms'], nb[1] * 1e-6, nb[0] * 1e-6, nb[1] / nb[0],
+                   batches[1].nbytes * 1e-6, batches[0].nbytes * 1e-6, batches[1].nbytes / batches[0].nbytes,
+                   res[key]['decode_call'], fmt(do), fmt(ds), do['median_ms'] / ds['median_ms']))
+            if other is not None:
+                r = clips.jpeg_restart_interval(ri, S, '420')
+                mcus = (-(-S // 16)) ** 2
+                blocks, segments = n * mcus * 6, n * (-(-mcus // min(r, mcus)) if r else 1)
+                header, hlen = F._jpeg_header_on(dev, S, S, '420', r)
+                scratch = torch.empty((F.jpeg_encode_scratch_bytes(blocks, segments, n),), dtype=torch.uint8, device=dev)
+                offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+                status = torch.empty((n,), dtype=torch.int32, device=dev)
+                args = _lib.JpegEncodeArgs(
+                    frames=raw_dev.data_ptr(), total=raw_dev.numel(), quality=qdev.data_ptr(), header=header.data_ptr(),
+                    header_bytes=hlen, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data[0].data_ptr(),
+                    capacity=data[0].numel(), offsets=offsets.data_ptr(), status=status.data_ptr(), stream=F._stream(), n=n, H=S, W=S,
+                    subsampling=2, restart_interval=r, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+                got = []
+                for lib in (_lib.lib(), other):
+                    data[0].zero_()
+                    _lib.check(lib.istvt_jpeg_encode_u8(ctypes.byref(args)), 'istvt_jpeg_encode_u8')
+                    got.append(data[0][:nb[0]].clone())
+                if not torch.equal(got[0], got[1]) or bytes(got[0].cpu().numpy()) != b''.join(files[0]):
+                    raise SystemExit('q=%d ri=%s: the two libraries write different standard files' % (q, ri))
+                st, sp = alternate(a, lambda: _lib.lib().istvt_jpeg_encode_u8(ctypes.byref(args)),
+                                   lambda: other.istvt_jpeg_encode_u8(ctypes.byref(args)))
+                inside = sp['min_ms'] <= st['median_ms'] <= sp['max_ms']
+                res[key].update({'entry_this': st, 'entry_other': sp, 'this_inside_others_spread': inside})
+                say(lines, '    istvt_jpeg_encode_u8, this library %s against the other %s in alternation: this / other = %.4f; this '
+                    "median %s the other's min-max" % (fmt(st), fmt(sp), st['median_ms'] / sp['median_ms'],
+                                                       'inside' if inside else 'below' if st['median_ms'] < sp['min_ms'] else 'ABOVE'))
+    line = json.dumps({'jpeg_encode_bench_optimize': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--optimize', action='store_true')
+    ap.add_argument('--against', default=None)
+    ap.add_argument('--only', default=None, help='with --optimize: one configuration, q75_row | q75_0 | q90_row | q90_0 (for a kernel trace)')
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--reps', type=int, default=15)
@@ -94,6 +188,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('jpeg_encode_bench.py measures on a GPU; none is visible')
+    if a.optimize:
+        return optimize_main(a)
     n, S = a.frames, a.size
     lines, res = [], {}
     src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
