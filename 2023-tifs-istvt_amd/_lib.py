@@ -87,6 +87,7 @@ SIGNATURES = {
     'istvt_jpeg_decode_split_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_jpeg_encode_u8': [ctypes.POINTER(JpegEncodeArgs)],
     'istvt_jpeg_encode_opt_u8': [ctypes.POINTER(JpegEncodeArgs), I, I],
+    'istvt_jpeg_encode_layout_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I],
     'istvt_perturb_u8': [P, L, I, I, I, P, I, P, I, ctypes.c_ulonglong, P, L, P, P],
     'istvt_conv2_fwd': [P, P, P, P, I, I, I, P],
     'istvt_conv2_dgrad': [P, P, P, P, P, I, I, I, P],

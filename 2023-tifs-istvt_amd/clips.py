@@ -922,10 +922,29 @@ def _huffman_codes(counts, values):
     return codes
 
 
-def jpeg_restart_interval(restart_interval, W: int, subsampling: str = '420') -> int:
+JPEG_LAYOUT_FACTORS = {'420': ((2, 2), (1, 1), (1, 1)), '444': ((1, 1), (1, 1), (1, 1)), '422': ((2, 1), (1, 1), (1, 1)),
+                       'grey': ((1, 1),)}      # (h, v) of a layout's components: the MCU is 8 h x 8 v pixels of Y
+
+
+def _jpeg_encode_layout(subsampling, layout, who: str) -> str:
+    """The layout an encoder call names: subsampling ('420' or '444') where layout is None, else layout, one of JPEG_LAYOUTS,
+    which then stands alone: '420' and '444' are the subsampling of that name."""
+    if layout is None:
+        _jpeg_sub(subsampling)
+        return subsampling
+    if layout not in JPEG_LAYOUTS:
+        raise ValueError("%s: layout must be one of '420', '444', '422', 'grey', got %r" % (who, layout))
+    if subsampling != '420':
+        raise ValueError('%s: layout=%r takes the place of subsampling: leave subsampling at its default, got %r'
+                         % (who, layout, subsampling))
+    return layout
+
+
+def jpeg_restart_interval(restart_interval, W: int, subsampling: str = '420', layout=None) -> int:
     """The restart interval in MCUs that a file's DRI segment carries: an int in 0..65535 (0: no restart markers) as it is,
-    or 'row' for one MCU row, ceil(W / (8 * sub)) MCUs -- the interval that gives the device decoder one lane per MCU row."""
-    sub = _jpeg_sub(subsampling)
+    or 'row' for one MCU row, ceil(W / (8 * sub)) MCUs -- the interval that gives the device decoder one lane per MCU row.
+    layout (one of JPEG_LAYOUTS, in the place of subsampling): a row is ceil(W / 16) MCUs at '422' and ceil(W / 8) at 'grey'."""
+    sub = JPEG_LAYOUT_FACTORS[_jpeg_encode_layout(subsampling, layout, 'jpeg_restart_interval')][0][0]
     if isinstance(restart_interval, str):
         if restart_interval != 'row':
             raise ValueError("the restart interval is an int in [0, 65535] or 'row', got %r" % (restart_interval,))
@@ -938,18 +957,26 @@ def jpeg_restart_interval(restart_interval, W: int, subsampling: str = '420') ->
 
 JPEG_HEADER_DQT = (25, 94)                  # where the 64 bytes of the two quantisation tables lie in jpeg_header's bytes
 JPEG_HEADER_DHT = (177, 609)                # where the four Huffman table segments of jpeg_header's bytes begin and end
+JPEG_HEADER_DHT_GREY = (171, 603)           # ... in a one-component header: its SOF0 is 6 bytes shorter (and its SOS 4)
 
 
-def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_interval=0) -> bytes:
+def jpeg_header_dht(layout: str) -> tuple:
+    """JPEG_HEADER_DHT for a layout of JPEG_LAYOUTS: the quantisation tables lie in front of SOF0, at JPEG_HEADER_DQT always"""
+    return JPEG_HEADER_DHT_GREY if layout == 'grey' else JPEG_HEADER_DHT
+
+
+def jpeg_header(H: int, W: int, quality: int, subsampling: str = '420', restart_interval=0, layout=None) -> bytes:
     """SOI through the SOS header of the file jpeg_encode_host writes for an H x W frame: JFIF APP0, the two quantisation
     tables of `quality` in zig-zag order (at JPEG_HEADER_DQT), SOF0, the four Annex K.3 Huffman tables, DRI where the
-    restart interval is not 0, SOS.  Everything but the 2 x 64 table bytes is shared by the frames of a batch."""
-    sub = _jpeg_sub(subsampling)
+    restart interval is not 0, SOS.  Everything but the 2 x 64 table bytes is shared by the frames of a batch.
+    layout (one of JPEG_LAYOUTS, in the place of subsampling): 'grey' names one component in SOF0 and SOS and still holds all
+    six tables, the Huffman ones at JPEG_HEADER_DHT_GREY."""
+    word = _jpeg_encode_layout(subsampling, layout, 'jpeg_header')
     H, W = int(H), int(W)
     if not (1 <= H <= JPEG_MAX_SIDE and 1 <= W <= JPEG_MAX_SIDE):
         raise ValueError('jpeg_header: frames of 1 x 1 to %d x %d, got %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE, H, W))
-    ri = jpeg_restart_interval(restart_interval, W, subsampling)
-    return _jpeg_header(H, W, quality, [(sub, sub), (1, 1), (1, 1)], ri)
+    ri = jpeg_restart_interval(restart_interval, W, subsampling, layout)
+    return _jpeg_header(H, W, quality, list(JPEG_LAYOUT_FACTORS[word]), ri)
 
 
 def _jpeg_header(H: int, W: int, quality: int, fac, ri: int, tables=None) -> bytes:
@@ -1087,14 +1114,16 @@ def jpeg_optimal_tables(coef, fac, my: int, mx: int, ri: int) -> dict:
     return {(0, 0): dc0, (0, 1): dc1, (1, 0): ac0, (1, 1): ac1}
 
 
-def jpeg_header_bound(H: int, W: int, subsampling: str = '420', restart_interval=0) -> int:
+def jpeg_header_bound(H: int, W: int, subsampling: str = '420', restart_interval=0, layout=None) -> int:
     """The largest header a file of jpeg_encode_host(optimize=True) can have.  A DC table holds at most the 12 categories
     0..11 and an AC table at most 160 (run, size) pairs, EOB and ZRL, since the coder clamps a DC difference to +-2047 and an
-    AC value to +-1023: as many values as the Annex K.3 tables list, so the bound is the length of jpeg_header."""
-    return len(jpeg_header(H, W, 50, subsampling, restart_interval))
+    AC value to +-1023: as many values as the Annex K.3 tables list, so the bound is the length of jpeg_header -- in every
+    layout, since the argument counts symbols, not components."""
+    return len(jpeg_header(H, W, 50, subsampling, restart_interval, layout))
 
 
-def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0, optimize: bool = False) -> bytes:
+def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart_interval=0, optimize: bool = False,
+                     layout=None) -> bytes:
     """A baseline JFIF file of one frame, the definition of ops.jpeg_encode_u8: u8 uint8 (H, W, 3) -> bytes.  The front half
     of jpeg_roundtrip_host (colour in, padding, downsample, _fdct8, quantise with jpeg_quant_tables(quality)), then Huffman
     coding with the Annex K.3 tables, a restart marker every restart_interval MCUs (0: none; 'row': every MCU row,
@@ -1102,25 +1131,39 @@ def jpeg_encode_host(u8: Tensor, quality: int, subsampling: str = '420', restart
     jpeg_decode_host(jpeg_encode_host(x, q, s)) == jpeg_roundtrip_host(x[None], q, s)[0], exactly.
     optimize=True (DESIGN.md "JPEG files out, optimised tables") codes the same coefficients with the frame's own four
     tables, jpeg_optimal_table of jpeg_symbol_counts, written in the places of the Annex K.3 ones: the header's length then
-    varies with the frame, the scan is never longer, and the file decodes to the same pixels."""
+    varies with the frame, the scan is never longer, and the file decodes to the same pixels.
+    layout (DESIGN.md "JPEG files out, 4:2:2 and greyscale"): one of JPEG_LAYOUTS in the place of subsampling, which then
+    keeps its default.  '420' and '444' are the subsampling of that name.  '422' pads to MCUs of 16 x 8 pixels and takes
+    chroma as the mean of horizontal pairs with libjpeg's alternating bias, (a + b + (chroma column & 1)) >> 1; 'grey' pads
+    to 8 x 8 and keeps Y of the colour transform alone, coded with the first pair of tables: with optimize=False the bytes
+    of jpeg_encode_layout_host.  The header holds all six tables in every layout, so an optimised 'grey' file has two empty
+    tables of id 1, which no scan symbol refers to."""
     if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[-1] != 3 or u8.numel() == 0:
         raise ValueError('jpeg_encode_host expects a non-empty uint8 (H, W, 3) frame')
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_host: optimize is True or False, got %r' % (optimize,))
-    sub = _jpeg_sub(subsampling)
+    word = _jpeg_encode_layout(subsampling, layout, 'jpeg_encode_host')
     H, W = int(u8.shape[0]), int(u8.shape[1])
     if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
         raise ValueError('jpeg_encode_host: frames of at most %d x %d' % (JPEG_MAX_SIDE, JPEG_MAX_SIDE))
-    ri = jpeg_restart_interval(restart_interval, W, subsampling)
+    ri = jpeg_restart_interval(restart_interval, W, subsampling, layout)
     qt = jpeg_quant_tables(quality)
-    planes = _jpeg_planes_in(u8[None].cpu(), sub)
+    fac = list(JPEG_LAYOUT_FACTORS[word])
+    mh, mv = fac[0]
+    if word in JPEG_SUBSAMPLINGS:
+        planes = _jpeg_planes_in(u8[None].cpu(), mh)
+    else:
+        Y, Cb, Cr = _jpeg_colour_in(u8[None].cpu(), 8 * mv, 8 * mh)
+        planes = [Y]
+        if word == '422':
+            bias = torch.tensor([0, 1], dtype=torch.int32).repeat(Y.shape[2] // 4)
+            planes += [(c[:, :, 0::2] + c[:, :, 1::2] + bias) >> 1 for c in (Cb, Cr)]
     zz = torch.tensor(JPEG_ZIGZAG)
     coef = []                                               # per component (block rows, block columns, 64) in zigzag order
     for c, p in enumerate(planes):
         k = _jpeg_quantise(p, qt[min(c, 1)][None])[0].permute(0, 2, 1, 3)
         coef.append(k.reshape(k.shape[0], k.shape[1], 64)[:, :, zz].tolist())
-    my, mx = -(-H // (8 * sub)), -(-W // (8 * sub))
-    fac = [(sub, sub), (1, 1), (1, 1)]
+    my, mx = -(-H // (8 * mv)), -(-W // (8 * mh))
     tables = jpeg_optimal_tables(coef, fac, my, mx, ri) if optimize else None
     return _jpeg_scan(bytearray(_jpeg_header(H, W, quality, fac, ri, tables)), coef, fac, my, mx, ri, tables)
 
@@ -1228,10 +1271,11 @@ def check_encode_qualities(quality, n: int) -> Tensor:
     return q
 
 
-def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', optimize: bool = False) -> list:
+def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', optimize: bool = False,
+                           layout=None) -> list:
     """The definition of ops.jpeg_encode_u8 for a batch: frames uint8 (n, H, W, 3) or (B, T, H, W, 3), quality an int or
     int32 (n,) / (B,) as check_qualities takes it, every entry in 1..100 -> [jpeg_encode_host(frame, its quality, ...)];
-    optimize=True: every file with its own Huffman tables."""
+    optimize=True: every file with its own Huffman tables; layout: one of JPEG_LAYOUTS in the place of subsampling."""
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() not in (4, 5) or frames.shape[-1] != 3 \
             or frames.numel() == 0:
         raise ValueError('jpeg_encode_files_host expects non-empty uint8 (n, H, W, 3) or (B, T, H, W, 3) frames')
@@ -1239,7 +1283,7 @@ def jpeg_encode_files_host(frames: Tensor, quality, subsampling: str = '420', re
     if frames.dim() == 5:
         q = q.repeat_interleave(frames.shape[1])
     flat = frames.reshape((-1,) + tuple(frames.shape[-3:])).cpu()
-    return [jpeg_encode_host(f, int(v), subsampling, restart_interval, optimize) for f, v in zip(flat, q.tolist())]
+    return [jpeg_encode_host(f, int(v), subsampling, restart_interval, optimize, layout) for f, v in zip(flat, q.tolist())]
 
 
 JPEG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capacity a retry needs', 2: 'quality <= 0: no file',

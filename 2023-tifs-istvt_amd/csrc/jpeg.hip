@@ -35,6 +35,8 @@
 // jpeg_offsets_kernel between them: the prefix sum that lays the files end to end.  istvt_jpeg_encode_opt_u8 (DESIGN.md
 // "JPEG files out, optimised tables") codes every file with its own Huffman tables: jpeg_tables_kernel counts an image's
 // symbols in LDS and builds the four tables (jpeg_entropy_opt.h), then count, offsets and write with the image's codes.
+// istvt_jpeg_encode_layout_u8 (DESIGN.md "JPEG files out, 4:2:2 and greyscale") is both of them in the decoder's other two
+// layouts: jpeg_coef_kernel in front, whose MCUs are 16 x 8 or 8 x 8 pixels, and the same entropy kernels on a JeLayout.
 #include "istvt_hip.h"
 #include "jpeg_entropy.h"
 #include "jpeg_entropy_enc.h"
@@ -261,6 +263,106 @@ __global__ __launch_bounds__(256) void jpeg_planes_kernel(const uint8_t* __restr
             v.y = jp_byte(d[4] + 128) | jp_byte(d[5] + 128) << 8 | jp_byte(d[6] + 128) << 16 | jp_byte(d[7] + 128) << 24;
             *reinterpret_cast<uint2*>(dst) = v;
         }
+    }
+}
+
+// jpeg_planes_kernel<SUB, true> for the two layouts whose MCU is 8 rows high (DESIGN.md "JPEG files out, 4:2:2 and
+// greyscale"): GREY = false is 4:2:2, MCUs of 16 x 8 pixels, chroma halved along a row as libjpeg's h2v1_downsample does it,
+// (a + b + (chroma column & 1)) >> 1; GREY = true keeps Y alone, MCUs of 8 x 8.  A tile is one MCU row (8 pixel rows) x
+// JP_TILE_W pixels: 8 Y blocks, then at 4:2:2 4 Cb and 4 Cr.  Hp, Wp: H, W rounded up to whole MCUs; pixels past the frame
+// replicate its edge, so the pair at an odd W's last column averages the last pixel with itself.  -> int16 coefficients,
+// per frame the blocks of Y row by row, then Cb's, then Cr's, 64 per block in zig-zag order, one 16-byte store per lane.
+template <bool GREY>
+__global__ __launch_bounds__(256) void jpeg_coef_kernel(const uint8_t* __restrict__ x, long total, const int* __restrict__ quality,
+                                                        uint8_t* __restrict__ coef, int H, int W, int Hp, int Wp, int tiles_y,
+                                                        int tiles_x) {
+    constexpr int NB = GREY ? 8 : 16;                            // live blocks of a tile
+    __shared__ int ws[NB * JP_BLOCK_LD];
+    __shared__ int qt[128];
+    __shared__ __align__(16) unsigned char stage[8 * JP_PITCH];
+
+    const int tid = threadIdx.x;
+    const int per = tiles_y * tiles_x;
+    const long f = blockIdx.x / per;
+    const int rem = (int)(blockIdx.x - f * per);
+    const int y0 = (rem / tiles_x) * 8, x0 = (rem % tiles_x) * JP_TILE_W;
+    const int q = min(quality[f], 100);
+    if (q <= 0) return;                                          // the whole workgroup: no coefficients, an empty file
+
+    if (tid < 128) {
+        const int s = q < 50 ? 5000 / q : 200 - 2 * q;
+        qt[tid] = min(max((JP_BASE[tid] * s + 50) / 100, 1), 255);
+    }
+    // the tile's part of the frame (y0 < H and x0 < W: padding adds less than one MCU); pixels past it replicate its edge
+    const int rows = min(8, H - y0), cols = min(JP_TILE_W, W - x0);
+    const int rstride = W * 3;
+    const int lead0 = u8_stage_rows(x, total, ((f * H + y0) * (long)W + x0) * 3, rstride, rows, cols, stage, JP_PITCH, tid, 256);
+    __syncthreads();
+
+    auto pixel = [&](int r, int c) -> const unsigned char* {
+        r = min(r, rows - 1);
+        return stage + r * JP_PITCH + u8_row_lead(lead0, r, rstride) + min(c, cols - 1) * 3;
+    };
+    if (GREY) {                                                  // 8 x 64 pixels, two per lane
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int p = tid + 256 * j;
+            const int ty = p >> 6, tx = p & 63;
+            ws[(tx >> 3) * JP_BLOCK_LD + ty * 8 + (tx & 7)] = jp_ycc(pixel(ty, tx)).y - 128;
+        }
+    } else {                                                     // one horizontal pair per lane: 8 x 32 pairs
+        const int ty = tid >> 5, px = tid & 31;
+        const JpYcc a = jp_ycc(pixel(ty, 2 * px)), b = jp_ycc(pixel(ty, 2 * px + 1));
+        const int at = (px >> 2) * JP_BLOCK_LD + ty * 8 + 2 * (px & 3);
+        ws[at] = a.y - 128;
+        ws[at + 1] = b.y - 128;
+        const int bias = px & 1;                                 // x0 / 2 is even: the chroma column's parity is the lane's
+        const int cat = (8 + (px >> 3)) * JP_BLOCK_LD + ty * 8 + (px & 7);
+        ws[cat] = ((a.cb + b.cb + bias) >> 1) - 128;
+        ws[cat + 4 * JP_BLOCK_LD] = ((a.cr + b.cr + bias) >> 1) - 128;
+    }
+    __syncthreads();
+
+    const int b = tid >> 3, k = tid & 7;                         // block and its row (first pass) or column (second)
+    const bool on = tid < NB * 8;
+    int d[8];
+    if (on) {                                                    // forward, rows
+        int* row = ws + b * JP_BLOCK_LD + k * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        jp_fdct8<true>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[i] = d[i];
+    }
+    __syncthreads();
+    if (on) {                                                    // forward columns, quantise
+        int* col = ws + b * JP_BLOCK_LD + k;
+        const int* qc = qt + (b < 8 ? 0 : 64) + k;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = col[i * 8];
+        jp_fdct8<false>(d);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int qv = qc[i * 8];
+            const int n = (abs(d[i]) + 4 * qv) / (8 * qv);
+            col[i * 8] = d[i] < 0 ? -n : n;
+        }
+    }
+    __syncthreads();
+    if (!on) return;
+    const int bw = Wp / 8, cw = Wp / 16;                         // blocks per row of Y / of a 4:2:2 chroma plane
+    const long ny = (long)bw * (Hp / 8), nc = GREY ? 0 : (long)cw * (Hp / 8);
+    long at;
+    int bcol, lim;
+    if (b < 8) bcol = x0 / 8 + b, lim = bw, at = (long)(y0 / 8) * bw + bcol;
+    else bcol = x0 / 16 + ((b - 8) & 3), lim = cw, at = ny + ((b - 8) >> 2) * nc + (long)(y0 / 8) * cw + bcol;
+    if (bcol < lim) {                                            // a tile may reach past the last MCU of the row
+        const int* blk = ws + b * JP_BLOCK_LD;
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v[j] = (unsigned)(blk[je_zigzag(8 * k + 2 * j)] & 0xFFFF) | (unsigned)blk[je_zigzag(8 * k + 2 * j + 1)] << 16;
+        *reinterpret_cast<uint4*>(coef + ((f * (ny + 2 * nc) + at) * 64 + 8 * k) * 2) = make_uint4(v[0], v[1], v[2], v[3]);
     }
 }
 
@@ -839,7 +941,8 @@ constexpr unsigned long JE_LENGTH_MASK = (1ul << JE_STATUS_SHIFT) - 1;
 
 // what the three kernels behind the coefficients share
 struct JeGeometry {
-    int n, sub, mcux, mcuy, ri, nseg;       // frames; chroma step; MCUs per row / column; MCUs per segment; segments per image
+    int n, mcux, mcuy, ri, nseg;            // frames; MCUs per row / column; MCUs per segment; segments per image
+    JeLayout lay;                           // the blocks of an MCU: (sub, sub, 2) for the chroma step of the first two entries
     long nb;                                // blocks per image
 };
 
@@ -858,7 +961,7 @@ __device__ __forceinline__ long je_run_segment(const JeGeometry& g, const short*
     const long first = (long)k * g.ri;
     const int count = (int)min((long)g.ri, mcus - first);
     const int marker = k == g.nseg - 1 ? 0xD9 : 0xD0 + (k & 7);
-    return je_encode_segment(coef + img * g.nb * 64, g.sub, g.mcux, g.mcuy, (int)first, count, codes, marker, sink, status);
+    return je_encode_segment(coef + img * g.nb * 64, g.lay, g.mcux, g.mcuy, (int)first, count, codes, marker, sink, status);
 }
 
 __global__ __launch_bounds__(64) void jpeg_count_kernel(JeGeometry g, const int* __restrict__ quality,
@@ -966,30 +1069,46 @@ __global__ __launch_bounds__(64) void jpeg_write_kernel(JeGeometry g, int seg_gr
     je_run_segment(g, coef, s, codes, sink, ignored);
 }
 
-template <int SUB> int jpeg_encode_launch(const istvt_jpeg_encode_args* a) {
-    constexpr int MCU = 8 * SUB;
+// The geometry of a call whose MCUs hold LV rows of LH Y blocks and LNC chroma blocks (JeLayout) and its first launch, the
+// coefficients: jpeg_planes_kernel<SUB, true> where the chroma step SUB is that of both axes, jpeg_coef_kernel otherwise.
+// row_bytes: what an image adds to the scratch behind the segment table.  -> blocks of the batch in `blocks`
+template <int LH, int LV, int LNC> int jpeg_encode_front(const istvt_jpeg_encode_args* a, long row_bytes, JeGeometry& g, long& blocks) {
+    constexpr int MW = 8 * LH, MH = 8 * LV;
     const int H = a->H, W = a->W, n = a->n;
-    const int Hp = (H + MCU - 1) / MCU * MCU, Wp = (W + MCU - 1) / MCU * MCU;
-    JeGeometry g;
-    g.n = n, g.sub = SUB, g.mcux = Wp / MCU, g.mcuy = Hp / MCU;
+    const int Hp = (H + MH - 1) / MH * MH, Wp = (W + MW - 1) / MW * MW;
+    g.n = n, g.lay = JeLayout{LH, LV, LNC}, g.mcux = Wp / MW, g.mcuy = Hp / MH;
     const long mcus = (long)g.mcux * g.mcuy;
     g.ri = (int)(a->restart_interval ? min((long)a->restart_interval, mcus) : mcus);
     const long nseg = (mcus + g.ri - 1) / g.ri;
-    g.nb = mcus * (SUB * SUB + 2);
-    const long blocks = g.nb * n, segments = nseg * n;
-    const int tiles_y = Hp / MCU, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
+    g.nb = mcus * (LH * LV + LNC);
+    blocks = g.nb * n;
+    const long segments = nseg * n;
+    const int tiles_y = Hp / MH, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
     const long tiles = (long)n * tiles_y * tiles_x;
     // a segment's length stays far inside 56 bits: at most 64 symbols of 27 bits per block, each byte stuffed
-    if (tiles > 0x7fffffffL || segments > 0x7fffffffL - 64 - n || blocks > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    if (a->scratch_bytes < blocks * 128 + segments * (long)sizeof(JeSegment)) return ISTVT_ERR_SHAPE;
+    if (tiles > 0x7fffffffL || segments > 0x7fffffffL - 64 - n || blocks > 0x7fffffffL || 2L * n > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    if (a->scratch_bytes < blocks * 128 + segments * (long)sizeof(JeSegment) + n * row_bytes) return ISTVT_ERR_SHAPE;
     g.nseg = (int)nseg;
     uint8_t* coef = (uint8_t*)a->scratch;
-    JeSegment* seg = (JeSegment*)(coef + blocks * 128);
     const uint8_t* x = (const uint8_t*)a->frames;
-    hipLaunchKernelGGL((jpeg_planes_kernel<SUB, true>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
-                       coef, H, W, Hp, Wp, tiles_y, tiles_x);
-    int rc = istvt_check_launch();
+    if constexpr (LH == LV && LNC == 2)
+        hipLaunchKernelGGL((jpeg_planes_kernel<LH, true>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
+                           coef, H, W, Hp, Wp, tiles_y, tiles_x);
+    else
+        hipLaunchKernelGGL((jpeg_coef_kernel<LNC == 0>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
+                           coef, H, W, Hp, Wp, tiles_y, tiles_x);
+    return istvt_check_launch();
+}
+
+template <int LH, int LV, int LNC> int jpeg_encode_launch(const istvt_jpeg_encode_args* a) {
+    JeGeometry g;
+    long blocks = 0;
+    int rc = jpeg_encode_front<LH, LV, LNC>(a, 0, g, blocks);
     if (rc != ISTVT_OK) return rc;
+    const int n = a->n;
+    const long segments = (long)g.nseg * n;
+    uint8_t* coef = (uint8_t*)a->scratch;
+    JeSegment* seg = (JeSegment*)(coef + blocks * 128);
     const int seg_groups = (int)((segments + 63) / 64);
     hipLaunchKernelGGL(jpeg_count_kernel, dim3((unsigned)seg_groups), dim3(64), 0, a->stream, g, a->quality, (const short*)coef, seg);
     rc = istvt_check_launch();
@@ -1042,7 +1161,7 @@ __global__ __launch_bounds__(256) void jpeg_tables_kernel(JeGeometry g, const in
     JoLdsHistogram sink = {hist};
     for (long b = tid; b < g.nb; b += 256) {
         int id = 0;
-        const long p = jo_previous_block(b, g.sub, g.mcux, g.mcuy, g.ri, id);
+        const long p = jo_previous_block(b, g.lay, g.mcux, g.mcuy, g.ri, id);
         const int pred = p < 0 || p >= g.nb ? 0 : (int16_t)(blocks[p * 8].lo & 0xFFFF);
         jo_count_block(sink, blocks + b * 8, pred, id);
     }
@@ -1146,30 +1265,16 @@ __global__ __launch_bounds__(64) void jpeg_write_opt_kernel(JeGeometry g, const 
     }
 }
 
-template <int SUB> int jpeg_encode_opt_launch(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
-    constexpr int MCU = 8 * SUB;
-    const int H = a->H, W = a->W, n = a->n;
-    const int Hp = (H + MCU - 1) / MCU * MCU, Wp = (W + MCU - 1) / MCU * MCU;
+template <int LH, int LV, int LNC> int jpeg_encode_opt_launch(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
     JeGeometry g;
-    g.n = n, g.sub = SUB, g.mcux = Wp / MCU, g.mcuy = Hp / MCU;
-    const long mcus = (long)g.mcux * g.mcuy;
-    g.ri = (int)(a->restart_interval ? min((long)a->restart_interval, mcus) : mcus);
-    const long nseg = (mcus + g.ri - 1) / g.ri;
-    g.nb = mcus * (SUB * SUB + 2);
-    const long blocks = g.nb * n, segments = nseg * n;
-    const int tiles_y = Hp / MCU, tiles_x = (Wp + JP_TILE_W - 1) / JP_TILE_W;
-    const long tiles = (long)n * tiles_y * tiles_x;
-    if (tiles > 0x7fffffffL || segments > 0x7fffffffL - 64 - n || blocks > 0x7fffffffL || 2L * n > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    if (a->scratch_bytes < blocks * 128 + segments * (long)sizeof(JeSegment) + (long)n * JO_ROW_BYTES) return ISTVT_ERR_SHAPE;
-    g.nseg = (int)nseg;
+    long blocks = 0;
+    int rc = jpeg_encode_front<LH, LV, LNC>(a, JO_ROW_BYTES, g, blocks);
+    if (rc != ISTVT_OK) return rc;
+    const int n = a->n;
+    const long segments = (long)g.nseg * n;
     uint8_t* coef = (uint8_t*)a->scratch;
     JeSegment* seg = (JeSegment*)(coef + blocks * 128);
     uint8_t* rows = (uint8_t*)(seg + segments);
-    const uint8_t* x = (const uint8_t*)a->frames;
-    hipLaunchKernelGGL((jpeg_planes_kernel<SUB, true>), dim3((unsigned)tiles), dim3(256), 0, a->stream, x, a->total, a->quality,
-                       coef, H, W, Hp, Wp, tiles_y, tiles_x);
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_tables_kernel, dim3((unsigned)n), dim3(256), 0, a->stream, g, a->quality, (const short*)coef, rows,
                        (int)a->header_bytes - (dht1 - dht0));
     rc = istvt_check_launch();
@@ -1189,6 +1294,10 @@ template <int SUB> int jpeg_encode_opt_launch(const istvt_jpeg_encode_args* a, i
 }
 
 // what both encoder entries refuse before any launch, but for the size of the scratch
+bool jpeg_encode_dht_refused(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
+    return dht0 < a->dqt1 + 64 || dht1 <= dht0 || dht1 > a->header_bytes;
+}
+
 int jpeg_encode_refusal(const istvt_jpeg_encode_args* a) {
     if (!a || a->n <= 0 || !a->frames || !a->quality || !a->header || !a->scratch || !a->data || !a->offsets || !a->status)
         return ISTVT_ERR_SHAPE;
@@ -1216,13 +1325,26 @@ int jpeg_encode_refusal(const istvt_jpeg_encode_args* a) {
 extern "C" int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a) {
     const int rc = jpeg_encode_refusal(a);
     if (rc != ISTVT_OK) return rc;
-    return a->subsampling == 2 ? jpeg_encode_launch<2>(a) : jpeg_encode_launch<1>(a);
+    return a->subsampling == 2 ? jpeg_encode_launch<2, 2, 2>(a) : jpeg_encode_launch<1, 1, 2>(a);
 }
 
 // The same with every file's own Huffman tables in the place of header[dht0 .. dht1): five launches
 extern "C" int istvt_jpeg_encode_opt_u8(const istvt_jpeg_encode_args* a, int dht0, int dht1) {
     const int rc = jpeg_encode_refusal(a);
     if (rc != ISTVT_OK) return rc;
-    if (dht0 < a->dqt1 + 64 || dht1 <= dht0 || dht1 > a->header_bytes) return ISTVT_ERR_SHAPE;
-    return a->subsampling == 2 ? jpeg_encode_opt_launch<2>(a, dht0, dht1) : jpeg_encode_opt_launch<1>(a, dht0, dht1);
+    if (jpeg_encode_dht_refused(a, dht0, dht1)) return ISTVT_ERR_SHAPE;
+    return a->subsampling == 2 ? jpeg_encode_opt_launch<2, 2, 2>(a, dht0, dht1) : jpeg_encode_opt_launch<1, 1, 2>(a, dht0, dht1);
+}
+
+// Both of the above in the layouts 4:2:2 (MCUs of 16 x 8 pixels, 4 blocks) and greyscale (8 x 8, one block, Y of the colour
+// transform alone): the bytes of clips.jpeg_encode_host(layout=).  dht0 == dht1 == 0: the Annex K.3 tables, four launches;
+// otherwise every file's own tables in the place of header[dht0 .. dht1), five launches
+extern "C" int istvt_jpeg_encode_layout_u8(const istvt_jpeg_encode_args* a, int layout, int dht0, int dht1) {
+    const int rc = jpeg_encode_refusal(a);
+    if (rc != ISTVT_OK) return rc;
+    if (a->subsampling != 0 || (layout != ISTVT_JPEG_LAYOUT_422 && layout != ISTVT_JPEG_LAYOUT_GREY)) return ISTVT_ERR_SHAPE;
+    if (dht0 == 0 && dht1 == 0) return layout == ISTVT_JPEG_LAYOUT_422 ? jpeg_encode_launch<2, 1, 2>(a) : jpeg_encode_launch<1, 1, 0>(a);
+    if (jpeg_encode_dht_refused(a, dht0, dht1)) return ISTVT_ERR_SHAPE;
+    return layout == ISTVT_JPEG_LAYOUT_422 ? jpeg_encode_opt_launch<2, 1, 2>(a, dht0, dht1)
+                                           : jpeg_encode_opt_launch<1, 1, 0>(a, dht0, dht1);
 }

@@ -15,6 +15,7 @@
 
 #include <stdint.h>
 
+#include "jpeg_entropy.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define JEE_HD __host__ __device__ __forceinline__
@@ -219,31 +220,33 @@ template <class Sink> JEE_HD void je_encode_block(JeEnc& e, Sink& s, const JeQua
     }
 }
 
-// One restart interval: MCUs [first_mcu, first_mcu + mcu_count) of an image of mcu_rows x mcu_cols MCUs whose chroma step is
-// sub (2: four Y blocks per MCU, 1: one).  coef: the image's blocks, int16 [block][64] in zig-zag order, 16-byte aligned:
-// those of Y row by row of the plane padded to whole MCUs, then Cb's, then Cr's.  codes: je_code_word's words (JE_CODE_WORDS
-// of them).  The DC prediction starts at 0 and is the DC of the previous block of the component, read from coef.  After the
-// last MCU the bits are padded with ones to a whole byte and FF `marker` follows (RSTm, or EOI after the last interval).
+// One restart interval: MCUs [first_mcu, first_mcu + mcu_count) of an image of mcu_rows x mcu_cols MCUs of layout lay
+// (JeLayout of jpeg_entropy.h; 4:2:0: four Y blocks per MCU, 4:2:2: two side by side, 4:4:4 and greyscale: one; greyscale has
+// no Cb or Cr and codes with table id 0 only).  coef: the image's blocks, int16 [block][64] in zig-zag order, 16-byte
+// aligned: those of Y row by row of the plane padded to whole MCUs, then Cb's, then Cr's.  codes: je_code_word's words
+// (JE_CODE_WORDS of them).  The DC prediction starts at 0 and is the DC of the previous block of the component, read from
+// coef.  After the last MCU the bits are padded with ones to a whole byte and FF `marker` follows (RSTm, or EOI after the
+// last interval).
 // -> the bytes handed to the sink, stuffed bytes, pad and marker included; status: 0, or 3 where a coefficient was clamped
 template <class Sink>
-JEE_HD long je_encode_segment(const int16_t* coef, int sub, int mcu_cols, int mcu_rows, int first_mcu, int mcu_count,
+JEE_HD long je_encode_segment(const int16_t* coef, const JeLayout& lay, int mcu_cols, int mcu_rows, int first_mcu, int mcu_count,
                               const uint32_t* codes, int marker, Sink& sink, int& status) {
     JeEnc e = {0u, 0, 0};
     int pred[3] = {0, 0, 0};
     const JeQuad* blocks = reinterpret_cast<const JeQuad*>(coef);
-    const long ybw = (long)mcu_cols * sub, ny = ybw * mcu_rows * sub, nc = (long)mcu_cols * mcu_rows;
+    const long ybw = (long)mcu_cols * lay.h, ny = ybw * mcu_rows * lay.v, nc = (long)mcu_cols * mcu_rows;
     const long mcus = nc;
     for (int m = 0; m < mcu_count; ++m) {
         const long mcu = (long)first_mcu + m;
         if (mcu < 0 || mcu >= mcus) break;
         const int my = (int)(mcu / mcu_cols), mx = (int)(mcu - (long)my * mcu_cols);
-        for (int c = 0; c < 3; ++c) {
-            const int nb = c == 0 ? sub : 1;
+        for (int c = 0; c <= lay.nc && c < 3; ++c) {
+            const int nv = c == 0 ? lay.v : 1, nh = c == 0 ? lay.h : 1;
             const uint32_t* dc = codes + JE_CODE_DC + (c ? 16 : 0);
             const uint32_t* ac = codes + JE_CODE_AC + (c ? 256 : 0);
-            for (int v = 0; v < nb; ++v) {
-                for (int h = 0; h < nb; ++h) {
-                    const long b = c == 0 ? ((long)my * sub + v) * ybw + (long)mx * sub + h : ny + (c - 1) * nc + mcu;
+            for (int v = 0; v < nv; ++v) {
+                for (int h = 0; h < nh; ++h) {
+                    const long b = c == 0 ? ((long)my * lay.v + v) * ybw + (long)mx * lay.h + h : ny + (c - 1) * nc + mcu;
                     je_encode_block(e, sink, blocks + b * 8, pred[c], dc, ac);
                 }
             }

@@ -191,9 +191,9 @@ template <class Sink> JEE_HD void jo_count_block(Sink& s, const JeQuad* blk, int
 
 // Block b of an image in the order of its coefficients (Y row by row of the padded plane, then Cb, then Cr) -> the block
 // whose DC predicts it in the scan, or -1 where the prediction is 0: the first block of its component in a restart interval
-// of ri >= 1 MCUs.  sub, mcu_cols, mcu_rows as je_encode_segment takes them
-JEE_HD long jo_previous_block(long b, int sub, int mcu_cols, int mcu_rows, int ri, int& id) {
-    const long ybw = (long)mcu_cols * sub, ny = ybw * mcu_rows * sub, nc = (long)mcu_cols * mcu_rows;
+// of ri >= 1 MCUs.  lay, mcu_cols, mcu_rows as je_encode_segment takes them; a greyscale image has Y blocks only
+JEE_HD long jo_previous_block(long b, const JeLayout& lay, int mcu_cols, int mcu_rows, int ri, int& id) {
+    const long ybw = (long)mcu_cols * lay.h, ny = ybw * mcu_rows * lay.v, nc = (long)mcu_cols * mcu_rows;
     if (b >= ny) {                                                // chroma: one block per MCU
         id = 1;
         const long mcu = (b - ny) % nc;
@@ -201,32 +201,33 @@ JEE_HD long jo_previous_block(long b, int sub, int mcu_cols, int mcu_rows, int r
     }
     id = 0;
     const long row = b / ybw, col = b - row * ybw;
-    const int v = (int)(row % sub), h = (int)(col % sub);
+    const int v = (int)(row % lay.v), h = (int)(col % lay.h);
     if (h > 0) return b - 1;
-    if (v > 0) return b - ybw + (sub - 1);                        // the last block of the MCU's row above
-    const long my = row / sub, mx = col / sub, mcu = my * mcu_cols + mx;
+    if (v > 0) return b - ybw + (lay.h - 1);                      // the last block of the MCU's row above
+    const long my = row / lay.v, mx = col / lay.h, mcu = my * mcu_cols + mx;
     if (mcu % ri == 0) return -1;
     const long py = mx > 0 ? my : my - 1, px = mx > 0 ? mx - 1 : mcu_cols - 1;    // the MCU before: its last block
-    return (py * sub + (sub - 1)) * ybw + px * sub + (sub - 1);
+    return (py * lay.v + (lay.v - 1)) * ybw + px * lay.h + (lay.h - 1);
 }
 
 // The counts of one restart interval, MCUs [first_mcu, first_mcu + mcu_count), block by block through jo_previous_block:
 // what je_encode_segment codes of the same arguments
 template <class Sink>
-JEE_HD void jo_count_segment(const int16_t* coef, int sub, int mcu_cols, int mcu_rows, int ri, int first_mcu, int mcu_count, Sink& sink) {
+JEE_HD void jo_count_segment(const int16_t* coef, const JeLayout& lay, int mcu_cols, int mcu_rows, int ri, int first_mcu,
+                             int mcu_count, Sink& sink) {
     const JeQuad* blocks = reinterpret_cast<const JeQuad*>(coef);
-    const long ybw = (long)mcu_cols * sub, ny = ybw * mcu_rows * sub, nc = (long)mcu_cols * mcu_rows;
+    const long ybw = (long)mcu_cols * lay.h, ny = ybw * mcu_rows * lay.v, nc = (long)mcu_cols * mcu_rows;
     for (int m = 0; m < mcu_count; ++m) {
         const long mcu = (long)first_mcu + m;
         if (mcu < 0 || mcu >= nc) break;
         const long my = mcu / mcu_cols, mx = mcu - my * mcu_cols;
-        for (int c = 0; c < 3; ++c) {
-            const int nb = c == 0 ? sub : 1;
-            for (int v = 0; v < nb; ++v)
-                for (int h = 0; h < nb; ++h) {
-                    const long b = c == 0 ? (my * sub + v) * ybw + mx * sub + h : ny + (c - 1) * nc + mcu;
+        for (int c = 0; c <= lay.nc && c < 3; ++c) {
+            const int nv = c == 0 ? lay.v : 1, nh = c == 0 ? lay.h : 1;
+            for (int v = 0; v < nv; ++v)
+                for (int h = 0; h < nh; ++h) {
+                    const long b = c == 0 ? (my * lay.v + v) * ybw + mx * lay.h + h : ny + (c - 1) * nc + mcu;
                     int id = 0;
-                    const long p = jo_previous_block(b, sub, mcu_cols, mcu_rows, ri, id);
+                    const long p = jo_previous_block(b, lay, mcu_cols, mcu_rows, ri, id);
                     const int pred = p < 0 ? 0 : (int16_t)(blocks[p * 8].lo & 0xFFFF);
                     jo_count_block(sink, blocks + b * 8, pred, id);
                 }

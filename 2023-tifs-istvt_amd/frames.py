@@ -493,20 +493,20 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
 
 
 # ---- JPEG files out ----------------------------------------------------------------------------------------------------------
-_JPEG_HEADERS: dict = {}                    # (H, W, subsampling, restart interval, device) -> (header on the device, its length)
+_JPEG_HEADERS: dict = {}          # (H, W, subsampling, restart interval, device, layout) -> (header on the device, its length)
 
 
-def _jpeg_header_on(device, H: int, W: int, subsampling: str, ri: int):
+def _jpeg_header_on(device, H: int, W: int, subsampling: str, ri: int, layout=None):
     """the header every file of a call starts with, uploaded once per geometry and device; its table bytes are placeholders"""
-    key = (H, W, subsampling, ri, str(device))
+    key = (H, W, subsampling, ri, str(device), layout)
     if key not in _JPEG_HEADERS:
-        head = clips.jpeg_header(H, W, 50, subsampling, ri)
+        head = clips.jpeg_header(H, W, 50, subsampling, ri, layout)
         _JPEG_HEADERS[key] = (torch.frombuffer(bytearray(head), dtype=torch.uint8).to(device), len(head))
     return _JPEG_HEADERS[key]
 
 
 def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_interval='row', capacity: Optional[int] = None,
-                   out: Optional[Tensor] = None, checked: bool = False, optimize: bool = False) -> 'clips.JpegFiles':
+                   out: Optional[Tensor] = None, checked: bool = False, optimize: bool = False, layout=None) -> 'clips.JpegFiles':
     """JPEG files out (clips.py): frames uint8 [n,H,W,3] or [B,T,H,W,3], contiguous, on the device, quality int32 [n] per
     frame or, for clips, [B] shared by the T frames of a clip (or an int for all), every entry in 1..100 -> a clips.JpegFiles
     on the device: the baseline JFIF files of clips.jpeg_encode_files_host end to end in `data`, byte for byte, with `offsets`
@@ -520,12 +520,19 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
     optimize=True (PIL's word for it): every file is coded with its own four Huffman tables, the bytes of
     clips.jpeg_encode_files_host(optimize=True): fewer scan bytes for every later decode, for one more launch now.  Its header
     is at most the standard one's (clips.jpeg_header_bound), so the default capacity is the same.  The scratch of that entry
-    is 128 bytes per block + 16 per restart interval + 3344 per frame."""
+    is 128 bytes per block + 16 per restart interval + 3344 per frame.
+    layout: one of clips.JPEG_LAYOUTS in the place of subsampling, which then keeps its default: the bytes of
+    clips.jpeg_encode_files_host(layout=).  '420' and '444' are the subsampling of that name, by the same entry.  '422' (MCUs
+    of 16 x 8 pixels, 4 blocks) and 'grey' (8 x 8, one block: Y of the colour transform, the frames stay RGB) go through
+    istvt_jpeg_encode_layout_u8, standard or optimised; restart_interval counts those MCUs."""
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     n, T, H, W = _rgb_source('jpeg_encode_u8', frames, contiguous=True, on_device=False)
-    sub = clips._jpeg_sub(subsampling)
-    ri = clips.jpeg_restart_interval(restart_interval, W, subsampling)
+    word = clips._jpeg_encode_layout(subsampling, layout, 'jpeg_encode_u8')
+    if word in clips.JPEG_SUBSAMPLINGS:    # the subsampling of that name: the same header, entry and profile record
+        subsampling, layout = word, None
+    mh, mv = clips.JPEG_LAYOUT_FACTORS[word][0]
+    ri = clips.jpeg_restart_interval(restart_interval, W, subsampling, layout)
     host_only = ('jpeg_encode_u8: a device quality table is taken with checked=True only (int32, one entry per frame, validated '
                  'by the caller); hand over the host table otherwise')
     if not checked:                        # the argument errors that need no device, before the one that asks for it
@@ -534,7 +541,7 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
         clips.check_encode_qualities(quality, n if T is None else n // T)
     _req(frames, 'frames')
     qdev = _frame_table('jpeg_encode_u8', _QUALITIES, quality, n, T, frames.device, checked, clips.check_encode_qualities, host_only)
-    header, hlen = _jpeg_header_on(frames.device, H, W, subsampling, ri)
+    header, hlen = _jpeg_header_on(frames.device, H, W, subsampling, ri, layout)
     if out is not None:
         if not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or out.device != frames.device \
                 or not out.is_contiguous() or out.numel() == 0:
@@ -550,12 +557,13 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
         data = torch.empty((capacity,), dtype=torch.uint8, device=frames.device)
     nbytes = frames.numel()
     _no_overlap('jpeg_encode_u8', data, frames.data_ptr(), nbytes, 'frames')
-    mcus = (-(-H // (8 * sub))) * (-(-W // (8 * sub)))
-    blocks, segments = n * mcus * (sub * sub + 2), n * (-(-mcus // min(ri, mcus)) if ri else 1)
+    mcus = (-(-H // (8 * mv))) * (-(-W // (8 * mh)))
+    blocks = n * mcus * (mh * mv + len(clips.JPEG_LAYOUT_FACTORS[word]) - 1)
+    segments = n * (-(-mcus // min(ri, mcus)) if ri else 1)
     scratch = torch.empty((jpeg_encode_scratch_bytes(blocks, segments, n, optimize),), dtype=torch.uint8, device=frames.device)
     offsets = torch.empty((n + 1,), dtype=torch.int64, device=frames.device)
     status = torch.empty((n,), dtype=torch.int32, device=frames.device)
-    _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri, optimize)
+    _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, mh, ri, optimize, layout)
     return clips.JpegFiles(data, offsets, status)
 
 
@@ -568,13 +576,21 @@ def jpeg_encode_scratch_bytes(blocks: int, segments: int, n: int, optimize: bool
     return 128 * blocks + 16 * segments + (JPEG_OPT_ROW_BYTES * n if optimize else 0)
 
 
-def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri, optimize=False) -> None:
-    """the entry on buffers that are all the caller's (tests put sentinels around them)"""
+def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, sub, ri, optimize=False,
+                        layout=None) -> None:
+    """the entry on buffers that are all the caller's (tests put sentinels around them); layout: None, '422' or 'grey'"""
     args = _lib.JpegEncodeArgs(
         frames=frames.data_ptr(), total=nbytes, quality=qdev.data_ptr(), header=header.data_ptr(), header_bytes=hlen,
         scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(), capacity=data.numel(),
-        offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W, subsampling=2 if sub == 2 else 0,
+        offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W,
+        subsampling=2 if sub == 2 and layout is None else 0,
         restart_interval=ri, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+    if layout is not None:
+        dht = clips.jpeg_header_dht(layout) if optimize else (0, 0)
+        with prof('jpeg_encode_layout_u8', nbytes + (4 if optimize else 3) * scratch.numel()):
+            _lib.check(_lib.lib().istvt_jpeg_encode_layout_u8(ctypes.byref(args), clips.JPEG_LAYOUT_CODES[layout], *dht),
+                       'istvt_jpeg_encode_layout_u8')
+        return
     if optimize:
         with prof('jpeg_encode_opt_u8', nbytes + 4 * scratch.numel()):
             _lib.check(_lib.lib().istvt_jpeg_encode_opt_u8(ctypes.byref(args), *clips.JPEG_HEADER_DHT), 'istvt_jpeg_encode_opt_u8')
@@ -584,17 +600,19 @@ def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offse
 
 
 def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None, quality=90,
-                  subsampling: str = '420', restart_interval='row', optimize: bool = False) -> 'clips.JpegFiles':
+                  subsampling: str = '420', restart_interval='row', optimize: bool = False, layout=None) -> 'clips.JpegFiles':
     """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
     cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
-    (jpeg_encode_u8; optimize=True: with their own Huffman tables) -> a clips.JpegFiles, whose files() ops.decode_frames and
-    clips.jpeg_batch take."""
+    (jpeg_encode_u8; optimize=True: with their own Huffman tables; layout: one of clips.JPEG_LAYOUTS in the place of
+    subsampling) -> a clips.JpegFiles, whose files() ops.decode_frames and clips.jpeg_batch take (with layouts='all' for '422'
+    and 'grey')."""
     if (boxes is None) == (transforms is None):
         raise ValueError('encode_frames: boxes and transforms are two ways to cut the same crop: pass one of them')
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
+    clips._jpeg_encode_layout(subsampling, layout, 'jpeg_encode_u8')
     crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
-    return jpeg_encode_u8(crops, quality, subsampling, restart_interval, optimize=optimize)
+    return jpeg_encode_u8(crops, quality, subsampling, restart_interval, optimize=optimize, layout=layout)
 
 
 def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,

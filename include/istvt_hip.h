@@ -491,6 +491,18 @@ int istvt_jpeg_encode_u8(const istvt_jpeg_encode_args* a);
  *              AC).  A row of an image whose quality is <= 0 is not written. */
 #define ISTVT_JPEG_OPT_ROW_BYTES 3344
 int istvt_jpeg_encode_opt_u8(const istvt_jpeg_encode_args* a, int dht0, int dht1);
+/* JPEG files out in the layouts 4:2:2 and greyscale: the two entries above for layout = ISTVT_JPEG_LAYOUT_422 (MCUs of 16 x
+ * 8 pixels: two Y blocks side by side, Cb, Cr; chroma is the mean of horizontal pairs, (a + b + (chroma column & 1)) >> 1) or
+ * ISTVT_JPEG_LAYOUT_GREY (MCUs of 8 x 8 pixels and one block: Y of the colour transform alone, coded with table id 0) -> the
+ * bytes of clips.jpeg_encode_host(layout=).  The same argument block with subsampling = 0, the same checks, and offsets and
+ * status as above; any other layout or subsampling is -3.  restart_interval counts the layout's MCUs.  `header` is
+ * clips.jpeg_header(layout=); it holds both quantisation tables and all four Huffman tables in either layout.
+ * dht0 == dht1 == 0: the Annex K.3 tables, the four launches and the scratch of istvt_jpeg_encode_u8.  Otherwise [dht0, dht1)
+ * are the header's four Huffman table segments, checked as istvt_jpeg_encode_opt_u8 checks them, and every file is coded with
+ * its own tables in that entry's five launches and scratch; a greyscale file's two id-1 tables are empty (19 bytes each).
+ * Blocks per frame: 4 per MCU at 4:2:2, 1 for greyscale.  No synchronisation, no global atomics, nothing allocated, nothing
+ * that has to be zeroed. */
+int istvt_jpeg_encode_layout_u8(const istvt_jpeg_encode_args* a, int layout, int dht0, int dht1);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

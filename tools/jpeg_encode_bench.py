@@ -23,6 +23,14 @@ and last one batch of 1080 x 1920 frames, as VideoScorer.render_explanation(jpeg
          restart-less ones; both decodes must give the same frames.  With --against OTHER.so (another build of the library,
          the parent commit's) the standard entry of both libraries is also called in alternation on the same argument block:
          whether this commit's median lies inside the other's own min-max spread.
+
+--layouts  instead of the above (DESIGN.md "JPEG files out, 4:2:2 and greyscale"): per configuration (quality, restart
+         interval, standard or optimised tables) ops.jpeg_encode_u8(layout='422') and (layout='grey'), each in alternation
+         with the 4:2:0 call of the same configuration (encode time, file bytes), after checking one file of each new
+         layout against clips.jpeg_encode_host(layout=) once; then ops.jpeg_decode_u8 on each kind of file in alternation
+         with the 4:2:0 files (the default call on 'row' files, split=128 on restart-less ones).  With --against OTHER.so
+         istvt_jpeg_encode_u8 and istvt_jpeg_encode_opt_u8 of both libraries are called in alternation on one 4:2:0 argument
+         block: whether this commit's median lies inside the other's own min-max spread.
 """
 import argparse
 import ctypes
@@ -174,11 +182,104 @@ def optimize_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def layouts_main(a):
+    from istvt_amd import _lib, frames as F
+    n, S = a.frames, a.size
+    lines, res = [], {}
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    raw_dev = src.repeat((-(-n // DISTINCT), 1, 1, 1))[:n].contiguous().cuda()
+    dev = raw_dev.device
+    names = ('420', '422', 'grey')
+    data = {k: torch.empty((raw_dev.numel(),), dtype=torch.uint8, device=dev) for k in names}
+    out = {k: torch.empty_like(raw_dev) for k in names}
+    other = None
+    if a.against:
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        for entry in ('istvt_jpeg_encode_u8', 'istvt_jpeg_encode_opt_u8'):
+            getattr(other, entry).argtypes, getattr(other, entry).restype = _lib.SIGNATURES[entry], ctypes.c_int
+    checked = set()
+    for q in QUALITIES:
+        qdev = torch.full((n,), q, dtype=torch.int32, device=dev)
+        for ri in ('row', 0):
+            for optimize in (False, True):
+                key = 'q%d_%s_%s' % (q, ri, 'opt' if optimize else 'std')
+                if a.only and a.only != key:
+                    continue
+
+                def encode(layout):
+                    return ops.jpeg_encode_u8(raw_dev, qdev, restart_interval=ri, out=data[layout], checked=True, optimize=optimize,
+                                              layout=layout)
+                files = {k: encode(k).files() for k in names}
+                for k in names[1:]:
+                    if (k, optimize) not in checked:              # the definition takes seconds per frame of this size: once
+                        checked.add((k, optimize))
+                        want = clips.jpeg_encode_host(src[DISTINCT - 1], q, restart_interval=ri, optimize=optimize, layout=k)
+                        if files[k][DISTINCT - 1] != want or files[k][n - 1] != files[k][(n - 1) % DISTINCT]:
+                            raise SystemExit('%s: the %s file is not the definition' % (key, k))
+                batches = {k: clips.jpeg_batch(files[k], 'all') for k in names}
+                split = None if ri == 'row' else clips.JPEG_SPLIT_DEFAULT
+
+                def decode(k):
+                    return ops.jpeg_decode_u8(batches[k], out=out[k], checked=True, split=split)
+                for k in names:
+                    clips.check_jpeg_status(decode(k)[2])
+                nb = {k: sum(len(f) for f in files[k]) for k in names}
+                res[key] = {'frames': n, 'size': S, 'decode_call': 'default' if split is None else 'split=%d' % split}
+                for k in names[1:]:
+                    se, sb = alternate(a, lambda: encode(k), lambda: encode('420'))
+                    sd, sdb = alternate(a, lambda: decode(k), lambda: decode('420'))
+                    res[key][k] = {'file_bytes': nb[k], 'file_bytes_420': nb['420'], 'encode': se, 'encode_420': sb, 'decode': sd,
+                                   'decode_420': sdb}
+                    say(lines, '%s, %d frames of %d x %d | %s: encode %s against 4:2:0 %s beside it = %.3f | files %.3f MB against %.3f MB '
+                        '= %.3f | jpeg_decode_u8 (%s) %s against %s on the 4:2:0 files = %.3f'
+                        % (key, n, S, S, k, fmt(se), fmt(sb), se['median_ms'] / sb['median_ms'], nb[k] * 1e-6, nb['420'] * 1e-6,
+                           nb[k] / nb['420'], res[key]['decode_call'], fmt(sd), fmt(sdb), sd['median_ms'] / sdb['median_ms']))
+                if other is not None:
+                    r = clips.jpeg_restart_interval(ri, S, '420')
+                    mcus = (-(-S // 16)) ** 2
+                    blocks, segments = n * mcus * 6, n * (-(-mcus // min(r, mcus)) if r else 1)
+                    header, hlen = F._jpeg_header_on(dev, S, S, '420', r)
+                    scratch = torch.empty((F.jpeg_encode_scratch_bytes(blocks, segments, n, optimize),), dtype=torch.uint8, device=dev)
+                    offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+                    status = torch.empty((n,), dtype=torch.int32, device=dev)
+                    args = _lib.JpegEncodeArgs(
+                        frames=raw_dev.data_ptr(), total=raw_dev.numel(), quality=qdev.data_ptr(), header=header.data_ptr(),
+                        header_bytes=hlen, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data['420'].data_ptr(),
+                        capacity=data['420'].numel(), offsets=offsets.data_ptr(), status=status.data_ptr(), stream=F._stream(), n=n,
+                        H=S, W=S, subsampling=2, restart_interval=r, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+                    entry = 'istvt_jpeg_encode_opt_u8' if optimize else 'istvt_jpeg_encode_u8'
+                    rest = clips.JPEG_HEADER_DHT if optimize else ()
+
+                    def call(lib):
+                        return getattr(lib, entry)(ctypes.byref(args), *rest)
+                    got = []
+                    for lib in (_lib.lib(), other):
+                        data['420'].zero_()
+                        _lib.check(call(lib), entry)
+                        got.append(data['420'][:nb['420']].clone())
+                    if not torch.equal(got[0], got[1]) or bytes(got[0].cpu().numpy()) != b''.join(files['420']):
+                        raise SystemExit('%s: the two libraries write different 4:2:0 files' % key)
+                    st, sp = alternate(a, lambda: call(_lib.lib()), lambda: call(other))
+                    inside = sp['min_ms'] <= st['median_ms'] <= sp['max_ms']
+                    res[key].update({'entry': entry, 'entry_this': st, 'entry_other': sp, 'this_inside_others_spread': inside})
+                    say(lines, '    %s at 4:2:0, this library %s against the other %s in alternation: this / other = %.4f; this median '
+                        "%s the other's min-max" % (entry, fmt(st), fmt(sp), st['median_ms'] / sp['median_ms'],
+                                                    'inside' if inside else 'below' if st['median_ms'] < sp['min_ms'] else 'ABOVE'))
+    line = json.dumps({'jpeg_encode_bench_layouts': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--optimize', action='store_true')
+    ap.add_argument('--layouts', action='store_true')
     ap.add_argument('--against', default=None)
-    ap.add_argument('--only', default=None, help='with --optimize: one configuration, q75_row | q75_0 | q90_row | q90_0 (for a kernel trace)')
+    ap.add_argument('--only', default=None, help='one configuration (for a kernel trace): with --optimize q75_row | q75_0 | q90_row | '
+                    'q90_0, with --layouts the same with _std or _opt behind it')
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--reps', type=int, default=15)
@@ -190,6 +291,8 @@ def main():
         raise SystemExit('jpeg_encode_bench.py measures on a GPU; none is visible')
     if a.optimize:
         return optimize_main(a)
+    if a.layouts:
+        return layouts_main(a)
     n, S = a.frames, a.size
     lines, res = [], {}
     src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])

@@ -132,14 +132,14 @@ int main() {
                         const int marker = s == nseg - 1 ? 0xD9 : 0xD0 + (s & 7);
                         JeCount counter = {0};
                         int st0 = -1, st1 = -1;
-                        const long len = je_encode_segment(coef, sub, mx, my, first, count, codes, marker, counter, st0);
+                        const long len = je_encode_segment(coef, je_layout(0, sub), mx, my, first, count, codes, marker, counter, st0);
                         if (len < 2) {
                             fail("a segment holds its marker at least", f, sub, mx, my, ri, s);
                             continue;
                         }
                         std::vector<uint8_t> out((size_t)len, 0xAA);       // exactly the counted size
                         JeStore store = {out.data(), 0, len, 0};
-                        const long wrote = je_encode_segment(coef, sub, mx, my, first, count, codes, marker, store, st1);
+                        const long wrote = je_encode_segment(coef, je_layout(0, sub), mx, my, first, count, codes, marker, store, st1);
                         if (wrote != len || store.n != len) fail("the stored length equals the counted one", f, sub, mx, my, ri, s);
                         if (st0 != st1 || (st0 != 0 && st0 != 3)) fail("one status, 0 or 3, from both passes", f, sub, mx, my, ri, s);
                         if (out[len - 2] != 0xFF || out[len - 1] != marker) fail("FF and the marker end the segment", f, sub, mx, my, ri, s);
@@ -151,7 +151,7 @@ int main() {
                         if (st0 > image_status) image_status = st0;
                         ++segments, bytes += len;
                         if (f < 3) {
-                            const int st = je_decode_segment(out.data(), 0L, len - 2, tabs, sub, mx, first, count, w);
+                            const int st = je_decode_segment(out.data(), 0L, len - 2, tabs, je_layout(0, sub), mx, first, count, w);
                             if (st != 0) fail("the segment decodes with status 0", f, sub, mx, my, ri, s);
                         }
                     }

@@ -104,6 +104,7 @@ void round_trip(const uint32_t* dc_counts, const uint32_t* ac_counts, const char
     if (dc_sizes.empty()) dc_sizes.push_back(0);
     for (int sub = 2; sub >= 1; --sub) {
         const int mx = 3, my = 2, mcus = mx * my;
+        const JeLayout lay = je_layout(0, sub);
         const long ybw = (long)mx * sub, ny = ybw * my * sub, nc = mcus, nb = ny + 2 * nc;
         std::vector<JeQuad> backing(nb * 8);                     // 16-byte aligned, exactly the image's blocks
         int16_t* coef = reinterpret_cast<int16_t*>(backing.data());
@@ -127,7 +128,7 @@ void round_trip(const uint32_t* dc_counts, const uint32_t* ac_counts, const char
                         for (int h = 0; h < (c ? 1 : sub); ++h) {
                             const long b = c == 0 ? ((long)(mcu / mx) * sub + v) * ybw + (long)(mcu % mx) * sub + h : ny + (c - 1) * nc + mcu;
                             int id = 0;
-                            const long p = jo_previous_block(b, sub, mx, my, per, id);
+                            const long p = jo_previous_block(b, lay, mx, my, per, id);
                             const int pred = p < 0 ? 0 : coef[p * 64];
                             int d = of_size(dc_sizes[lcg() % dc_sizes.size()]);
                             if (pred + d > 1023 || pred + d < -1023) d = -d;
@@ -136,7 +137,7 @@ void round_trip(const uint32_t* dc_counts, const uint32_t* ac_counts, const char
                         }
             uint32_t hist[4 * 256] = {};
             JoHistogram sink = {hist};
-            for (int s = 0; s < nseg; ++s) jo_count_segment(coef, sub, mx, my, per, s * per, mcus - s * per < per ? mcus - s * per : per, sink);
+            for (int s = 0; s < nseg; ++s) jo_count_segment(coef, lay, mx, my, per, s * per, mcus - s * per < per ? mcus - s * per : per, sink);
             // the tables of the blocks' own counts, then (where they hold EOB and category 0, which any block may need) the
             // tables of the family's counts themselves
             for (int variant = 0; variant < 2; ++variant) {
@@ -160,16 +161,16 @@ void round_trip(const uint32_t* dc_counts, const uint32_t* ac_counts, const char
                 const int marker = s == nseg - 1 ? 0xD9 : 0xD0 + (s & 7);
                 JeCount counter = {0};
                 int st0 = -1, st1 = -1;
-                const long len = je_encode_segment(coef, sub, mx, my, first, count, codes, marker, counter, st0);
+                const long len = je_encode_segment(coef, lay, mx, my, first, count, codes, marker, counter, st0);
                 if (len < 2) {
                     fail("a segment holds its marker at least", family, item);
                     continue;
                 }
                 std::vector<uint8_t> out((size_t)len, 0xAA);     // exactly the counted size
                 JeStore store = {out.data(), 0, len, 0};
-                const long wrote = je_encode_segment(coef, sub, mx, my, first, count, codes, marker, store, st1);
+                const long wrote = je_encode_segment(coef, lay, mx, my, first, count, codes, marker, store, st1);
                 if (wrote != len || st0 != 0 || st1 != 0) fail("the stored length equals the counted one, status 0", family, item);
-                if (je_decode_segment(out.data(), 0L, len - 2, tabs, je_layout(0, sub), mx, first, count, w) != 0)
+                if (je_decode_segment(out.data(), 0L, len - 2, tabs, lay, mx, first, count, w) != 0)
                     fail("the segment decodes with status 0", family, item);
             }
             for (long b = 0; b < nb; ++b)
