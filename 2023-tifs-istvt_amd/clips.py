@@ -46,6 +46,10 @@ view=flips)``: the compressed bytes are what crosses the host boundary.  Files a
 ``jpeg_encode_layout_host`` writes such files for tests and benchmarks.  ``jpeg_encode_host(optimize=True)`` (DESIGN.md "JPEG
 files out, optimised tables") codes a file with its own Huffman tables: ``jpeg_symbol_counts``, ``jpeg_optimal_table``
 (libjpeg's, so PIL's ``optimize=True``) and ``jpeg_header_bound``; ``ops.jpeg_encode_u8(optimize=True)`` gives its bytes.
+A ``JpegBank`` (DESIGN.md "JPEG bank") keeps the files of a whole set on the device: ``jpeg_bank`` packs host files,
+``JpegBank.from_encoded`` takes the encoder's result where it lies, ``jpeg_bank_decode_host`` is the definition of
+``ops.jpeg_decode_indexed_u8(bank, index)``, ``jpeg_scan_segments_host`` that of the device's marker scan, and
+``check_jpeg_bank_status`` names the two statuses an index adds.
 """
 import math
 from fractions import Fraction
@@ -1293,7 +1297,10 @@ JPEG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capac
 class JpegFiles:
     """What ops.jpeg_encode_u8 hands back, on the device: data uint8 (capacity,): the files end to end | offsets int64
     (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, the rest as JPEG_ENCODE_STATUS names
-    them.  Nothing here has waited for the device until files() or nbytes() is called."""
+    them.  Nothing here has waited for the device until files() or nbytes() is called.  geometry: what the files of one
+    encoder call share (H, W, layout, restart_interval in MCUs, optimize), left here by ops.jpeg_encode_u8 for
+    JpegBank.from_encoded; None for a JpegFiles put together by hand."""
+    geometry = None
 
     def __init__(self, data: Tensor, offsets: Tensor, status: Tensor):
         if data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 \
@@ -1640,6 +1647,217 @@ def jpeg_split_host(header, chunk_bytes: int) -> SimpleNamespace:
 def whole_boxes(sizes) -> Tensor:
     """[(H, W)] -> int32 (n, 4): the box (0, 0, H, W) of every frame, for crop_resize_u8 on the decoder's canvas"""
     return torch.tensor([[0, 0, int(h), int(w)] for h, w in sizes], dtype=torch.int32).reshape(-1, 4)
+
+
+# ------------------------------------------------------------------------------------------ JPEG bank
+# DESIGN.md "JPEG bank": the files of a whole set parsed once and kept on the device, then decoded in any order and any
+# number of times through an index that lives on the device too (ops.jpeg_decode_indexed_u8).  jpeg_bank packs host files,
+# JpegBank.from_encoded takes the encoder's result without leaving the device, jpeg_bank_decode_host is the definition of the
+# indexed decode and jpeg_scan_segments_host that of the device's marker scan.
+JPEG_BANK_MAX_BYTES = 2 ** 31 - 1           # segment rows are int32 byte offsets
+JPEG_BANK_STATUS = {4: 'the index is outside the bank', 5: 'the bank holds no decodable file at that place'}
+JPEG_SCAN_LANE_BYTES = 16                   # JB_LANE_BYTES of csrc/jpeg_bank_scan.h: the bytes of a lane of the marker scan
+JPEG_SCAN_TILE_BYTES = 256 * 16             # ... and of a workgroup's trip
+
+
+def _bank_bytes(nbytes: int, who: str) -> int:
+    if nbytes > JPEG_BANK_MAX_BYTES:
+        raise ValueError('%s: %d bytes; a bank holds fewer than 2^31 (its segment rows are int32 byte offsets): use several banks'
+                         % (who, nbytes))
+    return nbytes
+
+
+class JpegBank:
+    """A set of files ready for ops.jpeg_decode_indexed_u8: what a JpegBatch of the whole set holds -- data, images (n, 20),
+    segments, qtabs, htabs, sizes, as JpegBatch describes them -- and the two numbers that make a call's geometry independent
+    of which files it draws: seg_max, the most segments of any file, and block_stride, the most 8 x 8 blocks of any, rounded
+    up to a multiple of JPEG_IDCT_BLOCKS.  Hmax, Wmax: the largest height and width.  An images row with 0 segments is an
+    empty place (the device ingest marks files so): drawing it gives status 5.
+
+    jpeg_bank builds one from host files: the tensors are host tensors (pinned where a device is there to take them),
+    `headers` keeps the parsed files for jpeg_bank_decode_host, and on(device) uploads once.  from_encoded and extend build
+    one on a device: data .. htabs are None, `device` says where it lives, and on(device) hands those tensors back."""
+
+    def __init__(self, **kw):
+        self.device = self.headers = None
+        self.__dict__.update(kw)
+        self._on = {}
+
+    def __len__(self) -> int:
+        return self.n
+
+    def on(self, device):
+        """the five tensors on `device`: .data .images .segments .qtabs .htabs, uploaded once without blocking (JpegBatch.on)"""
+        key = str(torch.device(device))
+        if key not in self._on:
+            if self.data is None:
+                raise RuntimeError('JpegBank: this bank was built on %s and has no host copy to upload to %s' % (self.device, key))
+            names = ('data', 'images', 'segments', 'qtabs', 'htabs')
+            self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in names})
+        return self._on[key]
+
+    def release_host(self) -> None:
+        """drops the host copies (the bytes, the tables, the parsed files) of a bank that has been uploaded: the device
+        copies are what a decode reads"""
+        if not self._on:
+            raise RuntimeError('JpegBank.release_host: upload the bank first (on(device))')
+        self.device = self.device or next(iter(self._on))
+        self.data = self.images = self.segments = self.qtabs = self.htabs = self.headers = None
+
+    @classmethod
+    def from_encoded(cls, jf, H=None, W=None, layout=None, restart_interval=None) -> 'JpegBank':
+        """The result of ops.jpeg_encode_u8 / ops.encode_frames (a JpegFiles) -> a bank over the same bytes, on their device:
+        no files(), no readback, no synchronisation (frames.jpeg_bank_ingest has the launches).  The geometry all files of
+        the call share comes from jf.geometry, which the encoder call leaves there; H, W, layout (one of JPEG_LAYOUTS) and
+        restart_interval name it for a JpegFiles put together by hand.  Files with optimised tables are refused."""
+        from . import frames
+        return frames.jpeg_bank_ingest(jf, H, W, layout, restart_interval)
+
+    def extend(self, other: 'JpegBank', device=None) -> 'JpegBank':
+        """Appends the files of `other` (another encode call's bank, say) behind this bank's, on the device both live on (or
+        `device` for two host banks): the bytes are joined, and offsets, table slots and first segments of `other` are
+        rebased with tensor expressions there.  Nothing is read back.  Afterwards this bank lives on that device alone."""
+        if not isinstance(other, JpegBank):
+            raise TypeError('JpegBank.extend takes a JpegBank, got %s' % type(other).__name__)
+        device = device or self.device or other.device
+        if device is None:
+            raise ValueError('JpegBank.extend: two host banks are joined on the `device` the call names')
+        for b in (self, other):
+            if b.device is not None and str(torch.device(b.device)) != str(torch.device(device)):
+                raise RuntimeError('JpegBank.extend: the banks live on %s and %s' % (b.device, device))
+        _bank_bytes(self.nbytes + other.nbytes, 'JpegBank.extend')
+        a, b = self.on(device), other.on(device)
+        I = JPEG_IMAGE_INTS
+        add = torch.zeros(I, dtype=torch.int32)
+        add[5:8], add[8:14], add[14], add[15], add[16] = self.nq, self.nh, self.blocks, self.groups, self.nseg
+        seg_add = torch.tensor([self.n, self.nbytes, self.nbytes, 0, 0], dtype=torch.int32)
+        joined = SimpleNamespace(
+            data=torch.cat([a.data[:self.nbytes], b.data[:other.nbytes]]),
+            images=torch.cat([a.images, b.images + add.to(device)]),
+            segments=torch.cat([a.segments, b.segments + seg_add.to(device)]),
+            qtabs=torch.cat([a.qtabs, b.qtabs]), htabs=torch.cat([a.htabs, b.htabs]))
+        self.n, self.nbytes, self.nseg = self.n + other.n, self.nbytes + other.nbytes, self.nseg + other.nseg
+        self.nq, self.nh = self.nq + other.nq, self.nh + other.nh
+        self.blocks, self.groups = self.blocks + other.blocks, self.groups + other.groups
+        self.sizes = list(self.sizes) + list(other.sizes)
+        self.seg_max, self.block_stride = max(self.seg_max, other.seg_max), max(self.block_stride, other.block_stride)
+        self.Hmax, self.Wmax = max(self.Hmax, other.Hmax), max(self.Wmax, other.Wmax)
+        self.data = self.images = self.segments = self.qtabs = self.htabs = self.headers = None
+        self.device, self._on = torch.device(device), {str(torch.device(device)): joined}
+        return self
+
+
+def jpeg_bank(files, layouts=JPEG_LAYOUTS_DEFAULT) -> JpegBank:
+    """A sequence of baseline JPEG files (bytes, or parsed JpegHeaders) -> the JpegBank of the set, on the host.  Every file
+    goes through jpeg_parse with `layouts`, which refuses what the decoder does not take, and jpeg_batch packs the tables:
+    the rows are those of jpeg_batch(files).  A set of 2^31 scan bytes or more is refused."""
+    layouts = _jpeg_layouts(layouts, 'jpeg_bank')
+    if isinstance(files, (bytes, bytearray, JpegFiles)) or not hasattr(files, '__len__'):
+        raise TypeError('jpeg_bank expects a sequence of files (bytes); JpegBank.from_encoded takes a JpegFiles, got %s'
+                        % type(files).__name__)
+    if len(files) == 0:
+        raise ValueError('jpeg_bank: an empty bank')
+    headers = [f if isinstance(f, JpegHeader) else jpeg_parse(f, layouts) for f in files]
+    _bank_bytes(sum(hd.segments[-1][1] - hd.segments[0][0] for hd in headers), 'jpeg_bank')
+    batch = jpeg_batch(headers, layouts)
+    return JpegBank(data=batch.data, nbytes=batch.nbytes, images=batch.images, segments=batch.segments, qtabs=batch.qtabs,
+                    htabs=batch.htabs, sizes=batch.sizes, n=batch.n, nseg=int(batch.segments.shape[0]),
+                    nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), blocks=batch.blocks, groups=batch.groups,
+                    seg_max=int(batch.images[:, 17].max()),
+                    block_stride=-(-int(batch.images[:, 18].max()) // JPEG_IDCT_BLOCKS) * JPEG_IDCT_BLOCKS,
+                    Hmax=max(h for h, _ in batch.sizes), Wmax=max(w for _, w in batch.sizes), headers=headers)
+
+
+def jpeg_bank_scratch_bytes(bank: JpegBank, m: int) -> int:
+    """The scratch of ops.jpeg_decode_indexed_u8 for m places: coefficients and planes of m * block_stride blocks | an int32
+    status per segment row and one more per place | from the next multiple of 16 bytes, the planned images (m, 20) and
+    segments (m * seg_max, 5)"""
+    m = int(m)
+    front = 192 * m * bank.block_stride + 4 * (m * bank.seg_max + m)
+    return -(-front // 16) * 16 + 4 * JPEG_IMAGE_INTS * m + 20 * m * bank.seg_max
+
+
+def check_bank_index(index, who: str = 'jpeg_bank_decode_host') -> Tensor:
+    """the `index` argument of an indexed decode: a list of ints, or a contiguous int32 / int64 tensor of one dimension, not
+    empty; values are not looked at (a value outside the bank is status 4, not an error)"""
+    if not torch.is_tensor(index):
+        if isinstance(index, (str, bytes)) or not hasattr(index, '__len__') or \
+                any(isinstance(v, bool) or not isinstance(v, int) for v in index):
+            raise TypeError('%s: index is a list of ints or an int32 / int64 tensor, got %s' % (who, type(index).__name__))
+        index = torch.tensor(list(index), dtype=torch.int64)
+    if index.dtype not in (torch.int32, torch.int64) or index.dim() != 1:
+        raise TypeError('%s: index is int32 or int64 of one dimension, got %s %s' % (who, index.dtype, tuple(index.shape)))
+    if index.numel() == 0:
+        raise ValueError('%s: an empty index' % who)
+    if not index.is_contiguous():
+        raise ValueError('%s: index must be contiguous, got stride %d' % (who, index.stride(0)))
+    return index
+
+
+def jpeg_bank_decode_host(bank_or_files, index, canvas=None, layouts=JPEG_LAYOUTS_DEFAULT):
+    """The definition of ops.jpeg_decode_indexed_u8: -> (frames, sizes, status), frames uint8 (m, Hc, Wc, 3) with place j
+    holding jpeg_decode_host(files[index[j]]) in its top left corner and 0 elsewhere, sizes int32 (m, 2) = (H, W), status
+    int32 (m,).  bank_or_files: a JpegBank that jpeg_bank built, or a sequence of files (parsed with `layouts`) in which b''
+    or None stands for an empty place.  Beside the statuses of jpeg_decode_host: 4 where index[j] is outside [0, n), 5 for an
+    empty place; both with size (0, 0) and a frame of zeros.  canvas = (Hc, Wc) defaults to the largest H and W of the set."""
+    if isinstance(bank_or_files, JpegBank):
+        if bank_or_files.headers is None:
+            raise ValueError('jpeg_bank_decode_host: this bank has no host copy of its files: pass the files')
+        files = bank_or_files.headers
+    else:
+        files = list(bank_or_files)
+    index = check_bank_index(index).tolist()
+    drawn = {}
+    for i in set(index):
+        if 0 <= i < len(files) and files[i] is not None and not (isinstance(files[i], (bytes, bytearray)) and len(files[i]) == 0):
+            drawn[i] = jpeg_decode_host(files[i], return_status=True, layouts=layouts)
+    if isinstance(bank_or_files, JpegBank):
+        Hmax, Wmax = bank_or_files.Hmax, bank_or_files.Wmax
+    else:
+        Hmax, Wmax = max([1] + [f.shape[0] for f, _ in drawn.values()]), max([1] + [f.shape[1] for f, _ in drawn.values()])
+    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if any(f.shape[0] > Hc or f.shape[1] > Wc for f, _ in drawn.values()):
+        raise ValueError('jpeg_bank_decode_host: the canvas %d x %d does not hold every image drawn' % (Hc, Wc))
+    frames = torch.zeros((len(index), Hc, Wc, 3), dtype=torch.uint8)
+    sizes = torch.zeros((len(index), 2), dtype=torch.int32)
+    status = torch.zeros((len(index),), dtype=torch.int32)
+    for j, i in enumerate(index):
+        if i in drawn:
+            f, s = drawn[i]
+            frames[j, :f.shape[0], :f.shape[1]] = f.to(torch.uint8)
+            sizes[j, 0], sizes[j, 1], status[j] = f.shape[0], f.shape[1], s
+        else:
+            status[j] = 5 if 0 <= i < len(files) else 4
+    return frames, sizes, status
+
+
+def check_jpeg_bank_status(status) -> None:
+    """check_jpeg_status for an indexed decode: reads the status table back (this waits for the device) and raises for the
+    first place that is not fine, statuses 4 and 5 (JPEG_BANK_STATUS) included"""
+    names = {1: 'its scan ends early', 2: 'a Huffman code or DC category no table holds', 3: 'a run past coefficient 63'}
+    names.update(JPEG_BANK_STATUS)
+    for j, s in enumerate(status.detach().cpu().tolist()):
+        if s in JPEG_BANK_STATUS:
+            raise ValueError('jpeg_decode_indexed: place %d has status %d (%s)' % (j, s, names[s]))
+        if s != 0:
+            raise ValueError('jpeg_decode_indexed: the file of place %d is damaged (status %d: %s)' % (j, s, names.get(s, 'unknown')))
+
+
+def jpeg_scan_segments_host(data, begin: int, end: int, expected: int):
+    """The definition of the device's marker scan (jpeg_bank_scan_kernel): data[begin:end] are the entropy-coded bytes of one
+    file whose EOI stands at `end` -> [(first byte, end byte)] of its restart intervals, cut at every pair FF D0..D7 (inside
+    a scan an FF is followed by 00, an RSTn or EOI alone, so such a pair is a marker wherever it stands), or None where
+    they are not `expected` many.  For a file of jpeg_encode_host these are jpeg_parse(file).segments."""
+    data = bytes(data)
+    out, first, at = [], begin, begin
+    while at + 1 < end:
+        if data[at] == 0xFF and 0xD0 <= data[at + 1] <= 0xD7:
+            out.append((first, at))
+            first = at = at + 2
+        else:
+            at += 1
+    out.append((first, end))
+    return out if len(out) == expected else None
 
 
 # ------------------------------------------------------------------------------------------ NV12 frames

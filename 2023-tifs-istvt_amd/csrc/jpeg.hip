@@ -27,7 +27,9 @@
 // jpeg_idct_kernel: the back half of jpeg_planes_kernel with the file's own tables -> the planes.  jpeg_canvas_kernel:
 // jpeg_rgb_kernel over a canvas [n][Hc][Wc][3] that holds images of several sizes.  istvt_jpeg_decode_split_u8 (DESIGN.md
 // "JPEG files without restart markers") puts jpeg_entropy_split_kernel in front instead: one workgroup per restart interval,
-// one lane per chunk of it (jpeg_entropy_split.h), for files whose intervals are long.
+// one lane per chunk of it (jpeg_entropy_split.h), for files whose intervals are long.  istvt_jpeg_decode_indexed_u8 (DESIGN.md
+// "JPEG bank") puts jpeg_bank_plan_kernel in front of the three kernels: files that stay on the device, drawn by an index
+// that lives there; istvt_jpeg_bank_ingest builds such a bank from the encoder's result (jpeg_bank_scan.h).
 //
 // JPEG files out (DESIGN.md "JPEG files out") are the third part: istvt_jpeg_encode_u8 writes a batch of frames as baseline
 // files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
@@ -38,6 +40,7 @@
 // istvt_jpeg_encode_layout_u8 (DESIGN.md "JPEG files out, 4:2:2 and greyscale") is both of them in the decoder's other two
 // layouts: jpeg_coef_kernel in front, whose MCUs are 16 x 8 or 8 x 8 pixels, and the same entropy kernels on a JeLayout.
 #include "istvt_hip.h"
+#include "jpeg_bank_scan.h"
 #include "jpeg_entropy.h"
 #include "jpeg_entropy_enc.h"
 #include "jpeg_entropy_opt.h"
@@ -919,6 +922,230 @@ extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int c
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
                        a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
+// ---- JPEG bank -------------------------------------------------------------------------------------------------------------
+// DESIGN.md "JPEG bank": files parsed once and kept on the device, decoded through an index that lives there too.  The plan
+// kernel turns the index into the two tables the three kernels above read, at uniform strides (seg_max segment rows and
+// block_stride blocks per place), so every grid is known on the host; the ingest builds a bank's tables from the encoder's
+// files without a host parse.  csrc/jpeg_bank_scan.h has the arithmetic both share with tools/jpeg_bank_check.cpp.
+
+namespace {
+
+// One workgroup per place j of the index: its images row, its seg_max segment rows and its word behind the segment
+// statuses (jb_plan_image says what that word is for).
+__global__ __launch_bounds__(64) void jpeg_bank_plan_kernel(const int* __restrict__ bank_images, int n,
+                                                            const int* __restrict__ bank_segments, int bank_nseg,
+                                                            const int* __restrict__ index, int m, int seg_max, int block_stride,
+                                                            int Hc, int Wc, int* __restrict__ images, int* __restrict__ segments,
+                                                            int* __restrict__ place_status) {
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int idx = index[j];
+    const int st = jb_plan_status(bank_images, n, bank_nseg, idx, seg_max, block_stride, Hc, Wc);
+    if (tid == 0) {
+        int row[JB_IMAGE_INTS];
+        jb_plan_image(bank_images, idx, st, j, m, seg_max, block_stride, row);
+#pragma unroll
+        for (int f = 0; f < JB_IMAGE_INTS; ++f) images[(long)j * JB_IMAGE_INTS + f] = row[f];
+        place_status[j] = st;
+    }
+    for (int k = tid; k < seg_max; k += 64) {
+        int row[JB_SEGMENT_INTS];
+        jb_plan_segment(bank_images, bank_segments, idx, st, j, k, row);
+        int* dst = segments + ((long)j * seg_max + k) * JB_SEGMENT_INTS;
+#pragma unroll
+        for (int f = 0; f < JB_SEGMENT_INTS; ++f) dst[f] = row[f];
+    }
+}
+
+// what all files of one encoder call share
+struct JbGeometry {
+    int H, W, sub, mcux, mcuy, layout, blocks, ri, seg_max;    // ri: MCUs per restart interval, never 0
+};
+
+// whether file i of the encoder's result can be read: fine by the encoder, inside data, long enough for a header and EOI
+__device__ __forceinline__ bool jb_file_ok(const long* __restrict__ offsets, const int* __restrict__ enc_status, int i,
+                                           long capacity, int header_bytes) {
+    const long start = offsets[i], stop = offsets[i + 1];
+    return enc_status[i] == 0 && start >= 0 && stop <= capacity && stop <= 0x7fffffffL && stop - start >= header_bytes + 2;
+}
+
+// One lane per table entry: the 2 x 64 bytes at dqt0 / dqt1 of file i, zig-zag order -> qtabs rows 2 i, 2 i + 1, natural
+// order; all 1 for a file that cannot be read
+__global__ __launch_bounds__(256) void jpeg_bank_qtabs_kernel(const uint8_t* __restrict__ data, long capacity,
+                                                              const long* __restrict__ offsets,
+                                                              const int* __restrict__ enc_status, int n, int header_bytes,
+                                                              int dqt0, int dqt1, int* __restrict__ qtabs) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)n * 128) return;
+    const int i = (int)(e >> 7), t = (int)(e >> 6) & 1, k = (int)e & 63;
+    int v = 1;
+    if (jb_file_ok(offsets, enc_status, i, capacity, header_bytes)) v = data[offsets[i] + (t ? dqt1 : dqt0) + k];
+    qtabs[((long)2 * i + t) * 64 + je_zigzag(k)] = v;
+}
+
+// One workgroup per file: the restart markers of its scan -> its seg_max segment rows, and its images row.  The lanes walk
+// the scan in tiles of 256 x 16 bytes; a lane finds the pairs that start in its bytes (jb_markers), an inclusive scan of
+// the counts in LDS plus the count of the tiles before orders them, and marker r ends interval r and starts interval r +
+// 1.  A file the encoder did not finish, one too short for its header, one that does not end with EOI or whose marker count
+// is not seg_max - 1 gets 0 segments in its images row: an empty place, status 5 when it is drawn.
+__global__ __launch_bounds__(256) void jpeg_bank_scan_kernel(const uint8_t* __restrict__ data, long capacity,
+                                                             const long* __restrict__ offsets,
+                                                             const int* __restrict__ enc_status, int header_bytes, JbGeometry g,
+                                                             int* __restrict__ segments, int* __restrict__ images) {
+    __shared__ int counts[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    bool ok = jb_file_ok(offsets, enc_status, i, capacity, header_bytes);        // the same for every lane
+    const long begin = ok ? offsets[i] + header_bytes : 0, end = ok ? offsets[i + 1] - 2 : 0;   // end: where EOI stands
+    ok = ok && data[end] == 0xFF && data[end + 1] == 0xD9;
+    int* seg = segments + (long)i * g.seg_max * JB_SEGMENT_INTS;
+    const int mcus = g.mcux * g.mcuy;
+    for (int k = tid; k < g.seg_max; k += 256) {
+        int* row = seg + (long)k * JB_SEGMENT_INTS;
+        row[0] = i, row[3] = k * g.ri, row[4] = min(g.ri, mcus - k * g.ri);
+        if (!ok) row[1] = row[2] = 0;
+    }
+    int found = 0;                                               // markers in the tiles before this one
+    if (ok) {
+        if (tid == 0) seg[1] = (int)begin, seg[(long)(g.seg_max - 1) * JB_SEGMENT_INTS + 2] = (int)end;
+        for (long tile = begin; tile < end; tile += JB_TILE_BYTES) {
+            const long lo = tile + (long)tid * JB_LANE_BYTES, hi = min(lo + JB_LANE_BYTES, end);
+            uint32_t mask = jb_markers(data, lo, hi, end);
+            const int mine = __popc(mask);
+            int sum = mine;
+            counts[tid] = sum;
+            __syncthreads();
+            for (int d = 1; d < 256; d <<= 1) {
+                const int add = tid >= d ? counts[tid - d] : 0;
+                __syncthreads();
+                sum += add;
+                counts[tid] = sum;
+                __syncthreads();
+            }
+            int r = found + sum - mine;
+            while (mask) {
+                const long p = lo + __ffs(mask) - 1;
+                mask &= mask - 1;
+                if (r < g.seg_max - 1) {
+                    seg[(long)r * JB_SEGMENT_INTS + 2] = (int)p;
+                    seg[(long)(r + 1) * JB_SEGMENT_INTS + 1] = (int)p + 2;
+                }
+                ++r;
+            }
+            found += counts[255];
+            __syncthreads();                                     // counts[255] is read before the next tile writes it
+        }
+    }
+    const bool whole = ok && found == g.seg_max - 1;
+    __syncthreads();                                             // the marker stores of other lanes lie before the next ones
+    if (ok && !whole)
+        for (int k = tid; k < g.seg_max; k += 256) seg[(long)k * JB_SEGMENT_INTS + 1] = seg[(long)k * JB_SEGMENT_INTS + 2] = 0;
+    if (tid < JB_IMAGE_INTS) {
+        const bool grey = g.layout == ISTVT_JPEG_LAYOUT_GREY;
+        int v = 0;
+        if (tid == JB_H) v = g.H;
+        else if (tid == JB_W) v = g.W;
+        else if (tid == JB_SUB) v = g.sub;
+        else if (tid == JB_MCUX) v = g.mcux;
+        else if (tid == JB_MCUY) v = g.mcuy;
+        else if (tid < JB_HUFF) v = 2 * i + (tid > JB_QUANT && !grey);        // Y: the file's first table; Cb, Cr: its second
+        else if (tid < JB_BLOCK0) v = grey ? (tid - JB_HUFF) & 1 : tid < JB_HUFF + 2 ? tid - JB_HUFF : 2 + ((tid - JB_HUFF) & 1);
+        else if (tid == JB_BLOCK0) v = i * g.blocks;
+        else if (tid == JB_GROUP0) v = i * ((g.blocks + JP_BLOCKS - 1) / JP_BLOCKS);
+        else if (tid == JB_SEG0) v = i * g.seg_max;
+        else if (tid == JB_NSEG) v = whole ? g.seg_max : 0;
+        else if (tid == JB_NBLOCKS) v = g.blocks;
+        else v = g.layout;
+        images[(long)i * JB_IMAGE_INTS + tid] = v;
+    }
+}
+
+}  // namespace
+
+// A bank decoded through an index; the argument block is described in include/istvt_hip.h.  Four launches: the plan, then
+// the three kernels of istvt_jpeg_decode_u8 on the planned tables.  No synchronisation, no global state, no atomics of its
+// own, nothing allocated.  The checks here are on scalars alone: the bank's tables were checked when it was built.
+extern "C" int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax,
+                                            int Wmax) {
+    if (!a || a->n <= 0 || a->nseg <= 0 || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || a->nbytes > 0x7fffffffL)
+        return ISTVT_ERR_SHAPE;
+    if (m <= 0 || seg_max < 1 || block_stride < JP_BLOCKS || block_stride % JP_BLOCKS != 0) return ISTVT_ERR_SHAPE;
+    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->qtabs || !a->htabs || !a->scratch || !a->out ||
+        !a->sizes || !a->status)
+        return ISTVT_ERR_SHAPE;
+    if (Hmax < 1 || Wmax < 1 || a->Hc < Hmax || a->Wc < Wmax || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
+    const long blocks = (long)m * block_stride, nseg = (long)m * seg_max, words = nseg + m;
+    if (blocks > 0x7fffffffL / 64 || words > 0x7fffffffL / JD_SEGMENT_INTS) return ISTVT_ERR_SHAPE;
+    const long tables = (blocks * JD_BLOCK_BYTES + 4 * words + 15) & ~15L;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) ||
+        a->scratch_bytes < tables + 4L * m * JD_IMAGE_INTS + 4 * nseg * JD_SEGMENT_INTS)
+        return ISTVT_ERR_SHAPE;
+    const long npix = (long)m * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
+    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const uint8_t* src = (const uint8_t*)a->bytes;
+    uint8_t* out = (uint8_t*)a->out;
+    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
+    const int* index = a->images_host;                           // this entry's reading of the field: on the device
+    short* coef = (short*)a->scratch;
+    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
+    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
+    int* images = (int*)((uint8_t*)a->scratch + tables);
+    int* segments = images + (long)m * JD_IMAGE_INTS;
+    hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
+                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes, images, m,
+                       segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(blocks / JP_BLOCKS)), dim3(256), 0, a->stream, coef, images, m, a->qtabs,
+                       a->nq, seg_status, (int)words, planes, a->sizes, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, images, planes, out, npix, a->Hc,
+                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
+// The encoder's files -> the tables of a bank, on the device; the argument block is described in include/istvt_hip.h.  Two
+// launches, no synchronisation, no atomics, nothing allocated.
+extern "C" int istvt_jpeg_bank_ingest(const istvt_jpeg_encode_args* a, int layout) {
+    if (!a || a->n <= 0 || a->H < 1 || a->W < 1 || a->H > 16384 || a->W > 16384) return ISTVT_ERR_SHAPE;
+    if (!a->data || !a->offsets || !a->status || !a->scratch) return ISTVT_ERR_SHAPE;
+    if (a->capacity < 1 || a->capacity > 0x7fffffffL || a->restart_interval < 0 || a->restart_interval > 65535)
+        return ISTVT_ERR_SHAPE;
+    if (a->dqt0 < 0 || a->dqt1 < a->dqt0 + 64 || a->header_bytes < a->dqt1 + 64 || a->header_bytes > 0x7fffffffL)
+        return ISTVT_ERR_SHAPE;
+    int sub;
+    if (layout == 0 && (a->subsampling == 2 || a->subsampling == 0)) sub = a->subsampling == 2 ? 2 : 1;
+    else if (layout == ISTVT_JPEG_LAYOUT_422 && a->subsampling == 0) sub = 2;
+    else if (layout == ISTVT_JPEG_LAYOUT_GREY && a->subsampling == 0) sub = 1;
+    else return ISTVT_ERR_SHAPE;
+    const JeLayout lay = je_layout(layout, sub);
+    JbGeometry g;
+    g.H = a->H, g.W = a->W, g.sub = sub, g.layout = layout;
+    g.mcux = (a->W + 8 * lay.h - 1) / (8 * lay.h), g.mcuy = (a->H + 8 * lay.v - 1) / (8 * lay.v);
+    const int mcus = g.mcux * g.mcuy;
+    g.blocks = mcus * js_mcu_blocks(lay);
+    g.ri = a->restart_interval > 0 && a->restart_interval < mcus ? a->restart_interval : mcus;
+    g.seg_max = (mcus + g.ri - 1) / g.ri;
+    const long rows = (long)a->n * g.seg_max;
+    if (rows > 0x7fffffffL / JD_SEGMENT_INTS || (long)a->n * g.blocks > 0x7fffffffL / 64) return ISTVT_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) ||
+        a->scratch_bytes < 4 * (rows * JD_SEGMENT_INTS + (long)a->n * (128 + JD_IMAGE_INTS)))
+        return ISTVT_ERR_SHAPE;
+    const uint8_t* data = (const uint8_t*)a->data;
+    int* segments = (int*)a->scratch;
+    int* qtabs = segments + rows * JD_SEGMENT_INTS;
+    int* images = qtabs + (long)a->n * 128;
+    hipLaunchKernelGGL(jpeg_bank_qtabs_kernel, dim3((unsigned)(((long)a->n * 128 + 255) / 256)), dim3(256), 0, a->stream, data,
+                       a->capacity, a->offsets, a->status, a->n, (int)a->header_bytes, a->dqt0, a->dqt1, qtabs);
+    const int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_bank_scan_kernel, dim3((unsigned)a->n), dim3(256), 0, a->stream, data, a->capacity, a->offsets,
+                       a->status, (int)a->header_bytes, g, segments, images);
     return istvt_check_launch();
 }
 

@@ -12,6 +12,7 @@ records them: ops.kernel_profile stays the one switch.  Nothing here synchronise
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -481,12 +482,147 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     return out, sizes, status
 
 
-def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, layouts=clips.JPEG_LAYOUTS_DEFAULT) -> Tensor:
+def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = None, buffers=None, split=None):
+    """JPEG bank (clips.py): the files of a clips.JpegBank stay on the device, and the m of them that `index` names are
+    decoded, in that order and with repeats -> (frames, sizes, status) as jpeg_decode_u8 hands them back, the bits of
+    clips.jpeg_bank_decode_host: frames uint8 [m, Hc, Wc, 3], sizes int32 [m, 2], status int32 [m]; a place whose index is
+    outside the bank has status 4, one whose file the device ingest could not read status 5, both with size (0, 0) and a
+    frame of zeros.  index: int32 or int64, one dimension, contiguous, on the device (torch.randint there) -- then no host
+    data is part of the call, nothing synchronises, and the call can be captured in a graph with `out` and `buffers` -- or
+    a host tensor or list, which is uploaded.  int64 is narrowed on the device.  The bank is uploaded at the first call
+    (bank.on).  canvas = (Hc, Wc) defaults to the bank's largest H and W, whatever is drawn.  buffers = (scratch uint8 of
+    clips.jpeg_bank_scratch_bytes(bank, m) bytes and 16-byte aligned, sizes, status).  split= is refused: the split kernel's
+    state rows are laid out over the whole byte range of a call, which for a bank is the whole set."""
+    if not isinstance(bank, clips.JpegBank):
+        raise TypeError('jpeg_decode_indexed_u8 expects a clips.JpegBank (clips.jpeg_bank, clips.JpegBank.from_encoded), got %s'
+                        % type(bank).__name__)
+    if split is not None:
+        raise ValueError('jpeg_decode_indexed_u8: split= is not available for a bank (the state rows of the split kernel are '
+                         'addressed over the whole byte range, which here is the whole set): long intervals decode with one '
+                         'lane each; pass such files to jpeg_decode_u8(split=)')
+    index = clips.check_bank_index(index, 'jpeg_decode_indexed_u8')
+    if not torch.cuda.is_available():
+        raise RuntimeError('istvt_amd: jpeg_decode_indexed_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
+    device = torch.device(bank.device) if bank.device is not None else index.device if index.is_cuda else \
+        out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    m = int(index.numel())
+    Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < bank.Hmax or Wc < bank.Wmax or Hc > 16384 or Wc > 16384:
+        raise ValueError('jpeg_decode_indexed_u8: the canvas must hold every image of the bank (%d x %d at least, 16384 x 16384 '
+                         'at most), got %d x %d' % (bank.Hmax, bank.Wmax, Hc, Wc))
+    dev = bank.on(device)
+    if index.device != dev.data.device:
+        index = index.to(dev.data.device, non_blocking=True)
+    if index.dtype != torch.int32:                                # -1 and n are outside the bank as everything beyond them is
+        index = index.clamp(-1, bank.n).to(torch.int32)
+    out = _u8_out('jpeg_decode_indexed_u8', dev.data, (m, Hc, Wc, 3), out)
+    _no_overlap('jpeg_decode_indexed_u8', out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
+    need = clips.jpeg_bank_scratch_bytes(bank, m)
+    device = dev.data.device
+    if buffers is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
+        sizes = torch.empty((m, 2), dtype=torch.int32, device=device)
+        status = torch.empty((m,), dtype=torch.int32, device=device)
+    else:
+        scratch, sizes, status = buffers
+        ok = (t.device == device and t.is_contiguous() for t in buffers)
+        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
+                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (m, 2)
+                or status.dtype != torch.int32 or tuple(status.shape) != (m,)):
+            raise RuntimeError('jpeg_decode_indexed_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes '
+                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (need, m, m, device))
+    args = _lib.JpegDecodeArgs(
+        bytes=dev.data.data_ptr(), nbytes=bank.nbytes, images=dev.images.data_ptr(), images_host=index.data_ptr(),
+        segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
+        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
+        status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
+    with prof('jpeg_decode_indexed_u8', 2 * 192 * m * bank.block_stride + out.numel()):   # + the bytes drawn, known on the device
+        _lib.check(_lib.lib().istvt_jpeg_decode_indexed_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
+                                                           bank.Wmax), 'istvt_jpeg_decode_indexed_u8')
+    return out, sizes, status
+
+
+_JPEG_STD_HTABS: dict = {}        # (device, tables) -> the Annex K.3 Huffman tables in decode form on the device
+
+
+def jpeg_bank_ingest(jf, H=None, W=None, layout=None, restart_interval=None) -> 'clips.JpegBank':
+    """clips.JpegBank.from_encoded: the encoder's result -> a bank over the same bytes, where they lie.  What the host knows
+    without waiting -- the number of files, the geometry they share, the header's length, seg_max = ceil(MCUs / restart
+    interval), the Annex K.3 Huffman tables -- it fills in; istvt_jpeg_bank_ingest reads the rest on the device: every
+    file's two quantisation tables and where its restart intervals lie.  A file the encoder did not finish (a status that is
+    not 0) becomes an empty place.  Two launches; no files(), no readback, no synchronisation."""
+    if not isinstance(jf, clips.JpegFiles):
+        raise TypeError('JpegBank.from_encoded expects a clips.JpegFiles, got %s' % type(jf).__name__)
+    g = jf.geometry
+    if g is not None and g.optimize:
+        raise ValueError('JpegBank.from_encoded: files with optimised Huffman tables (optimize=True) carry their own tables behind a '
+                         'header of their own length, which the device ingest does not read: encode with optimize=False, or '
+                         'hand files() to clips.jpeg_bank')
+    if g is None and (H is None or W is None or layout is None or restart_interval is None):
+        raise ValueError('JpegBank.from_encoded: a JpegFiles that no encoder call made needs H, W, layout and restart_interval')
+    H, W = int(g.H if H is None else H), int(g.W if W is None else W)
+    layout = g.layout if layout is None else layout
+    if layout not in clips.JPEG_LAYOUTS:
+        raise ValueError("JpegBank.from_encoded: layout must be one of '420', '444', '422', 'grey', got %r" % (layout,))
+    if not (1 <= H <= clips.JPEG_MAX_SIDE and 1 <= W <= clips.JPEG_MAX_SIDE):
+        raise ValueError('JpegBank.from_encoded: frames of 1 x 1 to 16384 x 16384, got %d x %d' % (H, W))
+    ri = clips.jpeg_restart_interval(g.restart_interval if restart_interval is None else restart_interval, W, layout=layout)
+    if not jf.data.is_cuda or jf.offsets.device != jf.data.device or jf.status.device != jf.data.device \
+            or not (jf.data.is_contiguous() and jf.offsets.is_contiguous() and jf.status.is_contiguous()):
+        raise RuntimeError('JpegBank.from_encoded: data, offsets and status of the JpegFiles are contiguous on one ROCm device')
+    device, n = jf.data.device, len(jf)
+    capacity = clips._bank_bytes(int(jf.data.numel()), 'JpegBank.from_encoded')
+    hlen = len(clips.jpeg_header(H, W, 50, restart_interval=ri, layout=layout))
+    fac = clips.JPEG_LAYOUT_FACTORS[layout]
+    (mh, mv), grey = fac[0], len(fac) == 1
+    mcus = (-(-H // (8 * mv))) * (-(-W // (8 * mh)))
+    seg_max = -(-mcus // min(ri, mcus)) if ri else 1
+    nb = mcus * (mh * mv + len(fac) - 1)
+    key = (str(device), grey)
+    if key not in _JPEG_STD_HTABS:
+        order = ((0, 0), (1, 0)) if grey else ((0, 0), (1, 0), (0, 1), (1, 1))
+        tabs = [clips.jpeg_huffman_table(*clips.JPEG_STD_HUFFMAN[k]) for k in order]
+        _JPEG_STD_HTABS[key] = torch.tensor(tabs, dtype=torch.int32).to(device)
+    tables = torch.empty((n * (5 * seg_max + 128 + clips.JPEG_IMAGE_INTS),), dtype=torch.int32, device=device)
+    args = _lib.JpegEncodeArgs(
+        frames=None, total=0, quality=None, header=None, header_bytes=hlen, scratch=tables.data_ptr(),
+        scratch_bytes=4 * tables.numel(), data=jf.data.data_ptr(), capacity=capacity, offsets=jf.offsets.data_ptr(),
+        status=jf.status.data_ptr(), stream=_stream(), n=n, H=H, W=W, subsampling=2 if layout == '420' else 0,
+        restart_interval=ri, dqt0=clips.JPEG_HEADER_DQT[0], dqt1=clips.JPEG_HEADER_DQT[1])
+    with prof('jpeg_bank_ingest', capacity + 4 * tables.numel()):
+        _lib.check(_lib.lib().istvt_jpeg_bank_ingest(ctypes.byref(args), clips.JPEG_LAYOUT_CODES[layout]), 'istvt_jpeg_bank_ingest')
+    at = 5 * n * seg_max
+    bank = clips.JpegBank(data=None, images=None, segments=None, qtabs=None, htabs=None, nbytes=capacity, sizes=[(H, W)] * n, n=n,
+                          nseg=n * seg_max, nq=2 * n, nh=2 if grey else 4, blocks=n * nb,
+                          groups=n * -(-nb // clips.JPEG_IDCT_BLOCKS), seg_max=seg_max,
+                          block_stride=-(-nb // clips.JPEG_IDCT_BLOCKS) * clips.JPEG_IDCT_BLOCKS, Hmax=H, Wmax=W, device=device)
+    bank._on[str(device)] = SimpleNamespace(data=jf.data, images=tables[at + 128 * n:].view(n, clips.JPEG_IMAGE_INTS),
+                                            segments=tables[:at].view(n * seg_max, 5),
+                                            qtabs=tables[at:at + 128 * n].view(2 * n, 64), htabs=_JPEG_STD_HTABS[key])
+    return bank
+
+
+def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, layouts=clips.JPEG_LAYOUTS_DEFAULT,
+                  index=None) -> Tensor:
     """Face crops from JPEG files: files (a sequence of bytes, a clips.JpegBatch or a clips.JpegFiles) are decoded on the device
     (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
     whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
     and the scorers.  split: jpeg_decode_u8's, for files without restart markers.  layouts: jpeg_decode_u8's, for files that are
-    not all 4:2:0 or 4:4:4."""
+    not all 4:2:0 or 4:4:4.  files may be a clips.JpegBank with `index` (jpeg_decode_indexed_u8): the places the index names
+    are decoded and cut; without `boxes` each is cut whole through boxes made from the decoder's sizes on the device, and a
+    place with status 4 or 5 comes out black."""
+    if isinstance(files, clips.JpegBank):
+        if index is None:
+            raise ValueError('decode_frames: a clips.JpegBank is decoded through index=')
+        frames, sizes, _ = jpeg_decode_indexed_u8(files, index, split=split)
+        if boxes is not None:
+            return crop_resize_u8(frames, boxes, S)
+        S = _side('crop_resize_u8', S)
+        clips.check_boxes(clips.whole_boxes([(files.Hmax, files.Wmax)]), 1, files.Hmax, files.Wmax, S)   # the largest there is
+        whole = torch.cat([torch.zeros_like(sizes), sizes.clamp(min=1)], dim=1)        # (0, 0, H, W); (0, 0, 1, 1) of a black place
+        return crop_resize_u8(frames, whole, S, checked=True)
+    if index is not None:
+        raise ValueError('decode_frames: index= goes with a clips.JpegBank')
     batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files, layouts)
     frames, _, _ = jpeg_decode_u8(batch, checked=True, split=split)
     return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)
@@ -564,7 +700,10 @@ def jpeg_encode_u8(frames: Tensor, quality, subsampling: str = '420', restart_in
     offsets = torch.empty((n + 1,), dtype=torch.int64, device=frames.device)
     status = torch.empty((n,), dtype=torch.int32, device=frames.device)
     _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offsets, status, n, H, W, mh, ri, optimize, layout)
-    return clips.JpegFiles(data, offsets, status)
+    files = clips.JpegFiles(data, offsets, status)
+    # what all files of the call share, for clips.JpegBank.from_encoded: known here, and nowhere else without a parse
+    files.geometry = SimpleNamespace(H=H, W=W, layout=word, restart_interval=ri, optimize=optimize)
+    return files
 
 
 JPEG_OPT_ROW_BYTES = 3344                   # ISTVT_JPEG_OPT_ROW_BYTES of include/istvt_hip.h: an image's tables in the scratch

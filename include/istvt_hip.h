@@ -445,6 +445,28 @@ int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a);
  *              changed.  clips.jpeg_split_plan has the sizes. */
 #define ISTVT_JPEG_STATE_INTS 8    /* a state row */
 int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes);
+/* JPEG bank: the files of a whole set stay on the device with their tables (clips.jpeg_bank), and a call decodes the m of them
+ * that `index` names, in that order and with repeats -> out uint8 [m][Hc][Wc][3], sizes int32 [m][2], status int32 [m] as
+ * above, and two more statuses: 4 the index is outside [0, n), 5 the bank's row holds no decodable file (its segment count
+ * is 0: istvt_jpeg_bank_ingest marks files so); either leaves size (0, 0) and a frame of zeros.  The bits of
+ * clips.jpeg_bank_decode_host.  Four launches: jpeg_bank_plan_kernel writes batch-local images and segments tables into the
+ * scratch, then the three kernels of istvt_jpeg_decode_u8 read those.  Place j gets first block j * block_stride, first IDCT
+ * workgroup j * block_stride / 24 and first segment j * seg_max, so every grid is known from m alone; segment rows behind an
+ * image's real count name image -1, which the entropy kernel rejects, and are not part of the image's status.  No
+ * synchronisation, no global state, nothing allocated.  The argument block is istvt_jpeg_decode_args, read as follows:
+ *   bytes, nbytes, images, segments, qtabs, htabs, n, nseg, nq, nh    the bank, on the device; nbytes < 2^31
+ *   images_host    NOT a host pointer here: the index, int32 [m] on the device.  segments_host is not read.
+ *   scratch        16-byte aligned; nothing is read from it before it is written.  m * block_stride * 192 bytes of
+ *                  coefficients and planes | int32 [m * seg_max + m]: the segment statuses, then a word per place (0, 4 or 5),
+ *                  which a place that cannot be decoded names as its one segment | from the next multiple of 16 bytes the
+ *                  planned images int32 [m][20] | the planned segments int32 [m * seg_max][5].
+ *                  clips.jpeg_bank_scratch_bytes has the sum.
+ *   out, sizes, status, Hc, Wc, stream    as above, with m in the place of n
+ * seg_max: the most segments of any file of the bank; block_stride: the most blocks of any, a multiple of 24; Hmax, Wmax: the
+ * largest height and width.  The entry looks at scalars alone and returns -3 on a null pointer, a bad count or stride, a
+ * canvas smaller than Hmax x Wmax, a scratch too small or misaligned, or an out that overlaps bytes; the bank's tables were
+ * checked when it was built, and the plan kernel turns a row that does not fit the strides or the canvas into status 5. */
+int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax, int Wmax);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
@@ -503,6 +525,20 @@ int istvt_jpeg_encode_opt_u8(const istvt_jpeg_encode_args* a, int dht0, int dht1
  * Blocks per frame: 4 per MCU at 4:2:2, 1 for greyscale.  No synchronisation, no global atomics, nothing allocated, nothing
  * that has to be zeroed. */
 int istvt_jpeg_encode_layout_u8(const istvt_jpeg_encode_args* a, int layout, int dht0, int dht1);
+/* JPEG bank, ingest: the result of one istvt_jpeg_encode_u8 / istvt_jpeg_encode_layout_u8 call with the Annex K.3 tables
+ * (dht0 == dht1 == 0) -> the tables of a bank over the same `data`, without a host parse.  Two launches:
+ * jpeg_bank_qtabs_kernel de-zigzags the 2 x 64 bytes at dqt0 / dqt1 of every file; jpeg_bank_scan_kernel, one workgroup per
+ * file, finds the FF D0..D7 pairs of its scan in tiles of 256 lanes x 16 bytes and writes its segment rows and its images
+ * row.  No synchronisation, no atomics, nothing allocated.  The argument block is istvt_jpeg_encode_args as the encoder call
+ * had it -- data, capacity (< 2^31), offsets, status (read here), header_bytes, dqt0, dqt1, n, H, W, subsampling,
+ * restart_interval, stream -- except that frames, quality and header are not read and
+ *   scratch        is the result, 16-byte aligned: segments int32 [n * seg_max][5] with byte offsets into data (seg_max =
+ *                  ceil(MCUs / restart_interval), 1 where that is 0) | qtabs int32 [2 n][64], file i's at rows 2 i, 2 i + 1 |
+ *                  images int32 [n][20], whose Huffman slots are 0..3 in the order DC 0, AC 0, DC 1, AC 1 (0, 1 for greyscale).
+ * layout: 0 with the call's subsampling, or ISTVT_JPEG_LAYOUT_422 / ISTVT_JPEG_LAYOUT_GREY with subsampling 0.  A file whose
+ * status is not 0, that is shorter than header_bytes + 2, does not end with EOI or does not hold seg_max - 1 restart markers
+ * gets 0 segments in its images row: istvt_jpeg_decode_indexed_u8 reports status 5 for it.  -3 as above. */
+int istvt_jpeg_bank_ingest(const istvt_jpeg_encode_args* a, int layout);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

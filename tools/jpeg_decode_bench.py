@@ -25,6 +25,15 @@ upload   the compressed batch (scan bytes and tables) against the decoded clip (
          alternation.  With --against OTHER.so (another build of the library, the parent commit's for instance) the four
          4:2:0 configurations by the default call, and split=128 on the restart-less ones, are timed through the entry
          points of both libraries in alternation instead.
+--bank   instead of the above (DESIGN.md "JPEG bank"): at quality 75 and 90 with a marker per MCU row, a clips.JpegBank of
+         --bank-files files (4096; the 8 distinct files repeated), of which every call draws --frames (256).  The same draw is
+         decoded (a) from bytes by ops.jpeg_decode_u8(files): parse, pack, upload, decode; (b) from a prepacked JpegBatch with
+         checked=True and the caller's buffers, the fastest path without a bank; (c) by ops.jpeg_decode_indexed_u8 through a
+         device index with the caller's buffers; (d) as (c) with a fresh torch.randint index on the device per call.  (c)'s
+         frames are compared with (b)'s first.  Per path the device time by events and the host's wall time per call with the
+         stream drained; (b) and (c) alternate.  Then the ingest: clips.JpegBank.from_encoded on --frames files of
+         ops.jpeg_encode_u8 against files() + clips.jpeg_batch + upload.  The plan kernel's own time comes from `rocprofv3
+         --kernel-trace --stats` on a run with --reps 3.
 """
 import argparse
 import ctypes
@@ -233,8 +242,102 @@ def layouts_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def bank_main(a):
+    """--bank: the indexed decode from a resident bank against the two ways of decoding the same files without one"""
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_decode_bench.py measures on a GPU; none is visible')
+    n, S, N = a.frames, a.size, a.bank_files
+    dev = torch.device('cuda', torch.cuda.current_device())
+    torch.zeros(1, device=dev)
+    lines, res = [], {}
+    row = -(-S // 16)
+    out, out_b = (torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    raw_dev = src.repeat((-(-n // DISTINCT), 1, 1, 1))[:n].contiguous().to(dev)
+
+    def both(fn, reps, warmup=a.warmup):
+        """(device ms by events, host ms with the stream drained) per call, after the warm-up"""
+        td, th = [], []
+        for r in range(warmup + reps):
+            x, y = event_ms(fn), timed(fn)
+            if r >= warmup:
+                td.append(x)
+                th.append(y)
+        return stats(td), stats(th)
+
+    def small(n_):
+        return (torch.empty((n_, 2), dtype=torch.int32, device=dev), torch.empty((n_,), dtype=torch.int32, device=dev))
+    for q in QUALITIES:
+        files = encoded(a, q, row)
+        headers = [clips.jpeg_parse(f) for f in files]            # parsed once: the bank's 4096 files are these 8, repeated
+        bank = clips.jpeg_bank([headers[i % DISTINCT] for i in range(N)])
+        bank.on(dev)
+        g = torch.Generator().manual_seed(q)
+        draw = torch.randint(0, N, (n,), generator=g)
+        index = draw.to(torch.int32).to(dev)
+        drawn = [files[i % DISTINCT] for i in draw.tolist()]
+        batch = clips.jpeg_batch(drawn)
+        buf_b = (torch.empty((batch.scratch_bytes,), dtype=torch.uint8, device=dev),) + small(n)
+        buf_c = (torch.empty((clips.jpeg_bank_scratch_bytes(bank, n),), dtype=torch.uint8, device=dev),) + small(n)
+        want, _, st_b = ops.jpeg_decode_u8(batch, out=out_b, checked=True, buffers=buf_b)
+        got, _, st_c = ops.jpeg_decode_indexed_u8(bank, index, out=out, buffers=buf_c)
+        clips.check_jpeg_status(st_b)
+        clips.check_jpeg_bank_status(st_c)
+        if not torch.equal(got, want):
+            raise SystemExit('q=%d: the indexed decode is not the default call on the same files' % q)
+        sa = both(lambda: ops.jpeg_decode_u8(drawn, out=out_b), max(2, a.reps // 5), 1)     # a second per call: the host parse
+        tb, tc, hb, hc = [], [], [], []
+
+        def by_batch():
+            return ops.jpeg_decode_u8(batch, out=out_b, checked=True, buffers=buf_b)
+
+        def by_bank():
+            return ops.jpeg_decode_indexed_u8(bank, index, out=out, buffers=buf_c)
+        for r in range(a.warmup + a.reps):                        # (b) and (c) in alternation, either first in turn
+            order = ((by_batch, tb, hb), (by_bank, tc, hc))[::1 if r % 2 == 0 else -1]
+            for clock, which in ((event_ms, 1), (timed, 2)):
+                for entry in order:
+                    t = clock(entry[0])
+                    if r >= a.warmup:
+                        entry[which].append(t)
+        sd = both(lambda: ops.jpeg_decode_indexed_u8(bank, torch.randint(0, N, (n,), device=dev), out=out, buffers=buf_c), a.reps)
+        # the ingest, on the same frames at this quality
+        jf = ops.jpeg_encode_u8(raw_dev, q, '420', 'row')
+        si = both(lambda: clips.JpegBank.from_encoded(jf), a.reps)
+        sh = both(lambda: clips.jpeg_batch(jf.files()).on(dev), max(2, a.reps // 5), 1)
+        ingested = clips.JpegBank.from_encoded(jf)
+        again, _, st_i = ops.jpeg_decode_indexed_u8(ingested, torch.arange(n, device=dev))
+        clips.check_jpeg_bank_status(st_i)
+        if not torch.equal(again, ops.jpeg_decode_u8(jf.files())[0]):
+            raise SystemExit('q=%d: the ingested bank does not decode to the files\' frames' % q)
+        res['q%d' % q] = {'bank_files': N, 'frames': n, 'size': S, 'bank_scan_bytes': bank.nbytes, 'drawn_scan_bytes': batch.nbytes,
+                          'seg_max': bank.seg_max, 'block_stride': bank.block_stride,
+                          'scratch_bytes': {'batch': batch.scratch_bytes, 'bank': clips.jpeg_bank_scratch_bytes(bank, n)},
+                          'a_files': {'device': sa[0], 'host': sa[1]}, 'b_batch': {'device': stats(tb), 'host': stats(hb)},
+                          'c_bank': {'device': stats(tc), 'host': stats(hc)}, 'd_bank_randint': {'device': sd[0], 'host': sd[1]},
+                          'ingest_device': {'device': si[0], 'host': si[1]}, 'ingest_host': {'device': sh[0], 'host': sh[1]}}
+        fmt = '%.3f ms (%.3f-%.3f)'
+        say(lines, 'bank q=%d: %d of %d files of %d x %d per call, bank scans %.2f MB, drawn %.2f MB, seg_max %d, block_stride %d'
+            % (q, n, N, S, S, bank.nbytes * 1e-6, batch.nbytes * 1e-6, bank.seg_max, bank.block_stride))
+        for name, key in (('(a) files: parse, pack, upload, decode', 'a_files'), ('(b) prepacked JpegBatch, checked', 'b_batch'),
+                          ('(c) bank, device index', 'c_bank'), ('(d) bank, torch.randint per call', 'd_bank_randint'),
+                          ('ingest: JpegBank.from_encoded', 'ingest_device'),
+                          ('ingest: files() + jpeg_batch + upload', 'ingest_host')):
+            d, h = res['q%d' % q][key]['device'], res['q%d' % q][key]['host']
+            say(lines, ('  %-42s device ' + fmt + ' | host, drained ' + fmt)
+                % (name, d['median_ms'], d['min_ms'], d['max_ms'], h['median_ms'], h['min_ms'], h['max_ms']))
+    line = json.dumps({'jpeg_bank_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--bank', action='store_true')
+    ap.add_argument('--bank-files', type=int, default=4096)
     ap.add_argument('--layouts', action='store_true')
     ap.add_argument('--against', default=None)
     ap.add_argument('--split', action='store_true')
@@ -248,6 +351,8 @@ def main():
     a = ap.parse_args()
     if a.layouts:
         return layouts_main(a)
+    if a.bank:
+        return bank_main(a)
     row = -(-a.size // 16)                                        # MCUs of one MCU row at 4:2:0
     configs = [(q, ri) for q in QUALITIES for ri in (0, row)]
     longer = [(QUALITIES[0], k * row) for k in (2, 4, 8)] if a.split else []     # where between a row and a file it starts to pay
