@@ -50,6 +50,12 @@ A ``JpegBank`` (DESIGN.md "JPEG bank") keeps the files of a whole set on the dev
 ``JpegBank.from_encoded`` takes the encoder's result where it lies, ``jpeg_bank_decode_host`` is the definition of
 ``ops.jpeg_decode_indexed_u8(bank, index)``, ``jpeg_scan_segments_host`` that of the device's marker scan, and
 ``check_jpeg_bank_status`` names the two statuses an index adds.
+
+The batch draw (DESIGN.md "Batch draw") is the ninth: ``BatchPlan`` (which videos a run draws its clips from, the base boxes,
+the shape bank of ``draw_shapes``, the probabilities as 32-bit thresholds, the seed; built and validated on the host once) and
+``batch_draw_host`` (the definition of ops.batch_draw and ops.draw_clips, integers only: the file index, boxes, flips,
+qualities, perturbation rows and labels of a batch as a pure function of the seed and the step).  A step that reads no host
+data is ``u8, view, label, _ = ops.draw_clips(bank, plan, S)`` and ``model(u8, view=view, view_checked=True, crop=S)``.
 """
 import math
 from fractions import Fraction
@@ -2633,3 +2639,277 @@ def paste_maps_host(frames: Tensor, maps: Tensor, A: Tensor, rect: Tensor, lut: 
             C = out[f, cy0:cy1, x0 + c - 1:x1:2].to(torch.int32)
             out[f, cy0:cy1, x0 + c - 1:x1:2] = ((C * (1024 - sw) + sc + 512) >> 10).to(torch.uint8)
     return out.to(frames.device)
+
+
+# ------------------------------------------------------------------------------------------ batch draw
+# DESIGN.md "Batch draw": which clips of which videos a training step takes from a JpegBank, and each clip's box, flip, JPEG
+# quality and perturbation, as a pure function of (seed, step) in integer arithmetic.  BatchPlan is built and validated on the
+# host once per run, batch_draw_host is the definition, and ops.batch_draw / ops.draw_clips give its tables on the device
+# (csrc/batch_draw.h), where the step counter lives too: a captured graph draws a new batch on every replay.
+DRAW_HEADER_INTS = 36                       # BD_HEADER_INTS of csrc/batch_draw.h: the index of a draw block starts here
+DRAW_MAGIC = 0x57524442                     # 'BDRW'
+DRAW_PARTS = ('videos', 'base', 'shapes', 'kinds', 'boxes', 'quality', 'view', 'perturb', 'label')     # in the block's order
+DRAW_STEP_WORD, DRAW_STATUS_WORD, DRAW_DRAWN_WORD, DRAW_OFFSET_WORD = 20, 22, 24, 26
+DRAW_STATUS = {1: 'the header disagrees with the call or a part leaves the block',
+               2: 'a row of videos leaves the base table or is shorter than a clip'}
+DRAW_PERTURB_RANGES = {'brightness': (0.6, 1.4), 'contrast': (0.6, 1.4), 'saturation': (0.0, 1.5), 'noise': (2.0, 16.0),
+                       'blur': (0.5, 3.0), 'pixelate': (2, 6)}          # random_perturbations' defaults
+DRAW_BLUR_ROWS = 8                          # the blur bank of random_perturbations
+
+
+def _i32(v: int) -> int:
+    """the 32-bit word v as the int32 that holds its bits"""
+    v &= 0xffffffff
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+def _threshold(p, what: str) -> int:
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+        raise ValueError('BatchPlan: %s must be a probability in [0, 1], got %r' % (what, p))
+    return int(math.floor(float(p) * 2.0 ** 32 + 0.5))
+
+
+def draw_shapes(K: int = 1024, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3)) -> Tensor:
+    """The shape bank of a BatchPlan, int32 (K, 2): row i holds the Q16 factors (rh, rw) by which the shorter side of a base
+    box gives a box's height and width.  random_boxes' float64 formulas on a stratified set of K points (Hammersley: the area
+    fraction at (i + 1/2) / K of `scale`, the aspect at the bit-reversed i, plus half a cell, of log `ratio`): h = sqrt(area /
+    aspect), w = sqrt(area * aspect), so log, exp and sqrt run here and never on the device."""
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 1 << 20:
+        raise ValueError('BatchPlan: the shape bank needs 1 <= K <= 2^20 rows, got %r' % (K,))
+    if not (0.0 < scale[0] <= scale[1] <= 1.0) or not (0.0 < ratio[0] <= ratio[1]):
+        raise ValueError('BatchPlan: need 0 < scale[0] <= scale[1] <= 1 and 0 < ratio[0] <= ratio[1], got %r %r' % (scale, ratio))
+    bits = max(1, (K - 1).bit_length())
+    l0, l1 = math.log(ratio[0]), math.log(ratio[1])
+    rows = []
+    for i in range(K):
+        rev = int(format(i, '0%db' % bits)[::-1], 2)
+        area = scale[0] + (scale[1] - scale[0]) * (i + 0.5) / K
+        asp = math.exp(l0 + (l1 - l0) * (rev + 0.5) / (1 << bits))
+        rows.append([int(math.floor(math.sqrt(area / asp) * 65536.0 + 0.5)), int(math.floor(math.sqrt(area * asp) * 65536.0 + 0.5))])
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def draw_block_layout(B: int, T: int, V: int, N: int, K: int, nk: int, gap: int = 0):
+    """Where the parts of a draw block lie -> ({name: (offset, length)} in ints, block_ints): the header, the index at
+    DRAW_HEADER_INTS, then DRAW_PARTS in order, each at the next multiple of 4 ints with `gap` more ints in front of it and
+    behind the last (tests put sentinels there)."""
+    n = B * T
+    lengths = dict(videos=3 * V, base=4 * N, shapes=2 * K, kinds=3 * nk, boxes=4 * n, quality=n, view=3 * B, perturb=4 * B, label=B)
+    parts, at = {'index': (DRAW_HEADER_INTS, n)}, DRAW_HEADER_INTS + n
+    for name in DRAW_PARTS:
+        at = -(-(at + gap) // 4) * 4
+        parts[name] = (at, lengths[name])
+        at += lengths[name]
+    return parts, at + gap
+
+
+class BatchPlan:
+    """What a training run draws its batches from, built and validated on the host once:
+
+    bank      a JpegBank, or the [(H, W)] of its places: the frames of the whole set, video after video
+    videos    int32 (V, 3) rows (first place, frame count, label), or a list of such triples: a video is a run of consecutive
+              places.  Class balance is the caller's: a video listed twice is drawn twice as often.
+    T, B, stride    a clip is T frames `stride` apart, a batch B clips; a video shorter than (T - 1) * stride + 1 is refused
+    base      int32 (N, 4), one (y0, x0, h, w) per place: the face box with its margin, inside its image; None: whole images
+    scale, ratio, K    the shape bank (draw_shapes): the box area as a fraction of the base box's largest square, its aspect
+    flip_p    the probability of a horizontal flip
+    jpeg      (p, lo, hi): with probability p a clip is recompressed at a quality uniform in [lo, hi]; None: never
+    perturb   (p, kinds, ranges): with probability p a clip takes one of `kinds`, uniform, at a strength uniform in the kind's
+              range; ranges: {name: (low, high)} over DRAW_PERTURB_RANGES, in the units clips.perturbation takes, stored as
+              the integer params of both ends.  'blur' draws a row of the 8-row bank gaussian_taps spans over its range, as
+              random_perturbations does (plan.taps).  None: never.
+    seed      in [0, 2^64): the Philox key of the draw, and the noise key draw_clips hands to perturb_u8.  Ranks that share a
+              bank draw different batches from different seeds: fold the rank into it.
+    step      where the run starts; a resumed run passes the step it stopped at, or calls seek().
+
+    batch_draw_host(plan, step) is the draw.  on(device) uploads the plan as a draw block, once; from then on the step lives
+    on the device: ops.batch_draw(plan) advances it, `step` reads it back (HostScalar: without draining the stream) and
+    seek(step) writes it."""
+
+    def __init__(self, bank, videos, T: int, B: int, stride: int = 1, base=None, scale=(0.5, 1.0), ratio=(3 / 4, 4 / 3),
+                 K: int = 1024, flip_p: float = 0.5, jpeg=(0.5, 30, 95),
+                 perturb=(0.5, ('brightness', 'contrast', 'saturation', 'noise', 'blur', 'pixelate'), None), seed: int = 0,
+                 step: int = 0):
+        sizes = list(bank.sizes if hasattr(bank, 'sizes') else bank)
+        N = len(sizes)
+        if N < 1 or any(len(s) != 2 or int(s[0]) < 1 or int(s[1]) < 1 for s in sizes):
+            raise ValueError('BatchPlan: the bank is a JpegBank or a list of (H, W), not empty')
+        for name, v in (('T', T), ('B', B), ('stride', stride)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError('BatchPlan: %s must be an int >= 1, got %r' % (name, v))
+        if B * T > (2 ** 31 - 1) // 8:
+            raise ValueError('BatchPlan: B * T = %d frames are too many for one draw' % (B * T))
+        videos = torch.as_tensor(videos)
+        if videos.dtype not in (torch.int32, torch.int64) or videos.dim() != 2 or videos.shape[1] != 3 or videos.shape[0] < 1:
+            raise ValueError('BatchPlan: videos must be an integer table (V, 3) = (first place, frame count, label), V >= 1, got %s %s'
+                             % (videos.dtype, tuple(videos.shape)))
+        span = (T - 1) * stride + 1
+        for v, (first, count, label) in enumerate(videos.tolist()):
+            if first < 0 or count < 1 or first + count > N:
+                raise IndexError('BatchPlan: video %d = places [%d, %d) leaves the bank of %d places' % (v, first, first + count, N))
+            if count < span:
+                raise ValueError('BatchPlan: video %d has %d frames, a clip of T=%d at stride %d spans %d' % (v, count, T, stride, span))
+            if not -2 ** 31 <= label < 2 ** 31:
+                raise ValueError('BatchPlan: the label of video %d does not fit an int32' % v)
+        whole = torch.tensor([[0, 0, int(h), int(w)] for h, w in sizes], dtype=torch.int32)
+        if base is None:
+            base = whole
+        else:
+            if not torch.is_tensor(base) or base.dtype != torch.int32 or tuple(base.shape) != (N, 4):
+                raise ValueError('BatchPlan: base must be int32 (%d, 4) = (y0, x0, h, w) per place of the bank' % N)
+            base = base.detach().cpu().contiguous()
+            bad = (base[:, 0] < 0) | (base[:, 1] < 0) | (base[:, 2] < 1) | (base[:, 3] < 1) | \
+                (base[:, 0].long() + base[:, 2] > whole[:, 2]) | (base[:, 1].long() + base[:, 3] > whole[:, 3])
+            if bool(bad.any()):
+                i = int(bad.nonzero()[0])
+                raise IndexError('BatchPlan: the base box %s of place %d lies outside its %d x %d image'
+                                 % (base[i].tolist(), i, int(whole[i, 2]), int(whole[i, 3])))
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError('BatchPlan: the seed must lie in [0, 2^64), got %r' % (seed,))
+        if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError('BatchPlan: the step must lie in [0, 2^64), got %r' % (step,))
+        self.thr_flip = _threshold(flip_p, 'flip_p')
+        self.thr_jpeg, self.jpeg_lo, self.jpeg_hi = 0, 1, 1
+        if jpeg is not None:
+            p, lo, hi = jpeg
+            self.thr_jpeg = _threshold(p, 'the p of jpeg')
+            if any(isinstance(q, bool) or not isinstance(q, int) for q in (lo, hi)) or not 1 <= lo <= hi <= 100:
+                raise ValueError('BatchPlan: jpeg = (p, lo, hi) needs ints 1 <= lo <= hi <= 100, got lo=%r hi=%r' % (lo, hi))
+            self.jpeg_lo, self.jpeg_hi = lo, hi
+        self.thr_perturb, self.taps, rows = 0, None, []
+        if perturb is not None:
+            p, kinds, ranges = perturb
+            self.thr_perturb = _threshold(p, 'the p of perturb')
+            kinds = tuple(kinds)
+            if not kinds or any(k not in PERTURBATION_KINDS[1:] for k in kinds):
+                raise ValueError('BatchPlan: the kinds of perturb must name some of %s, got %r' % (', '.join(PERTURBATION_KINDS[1:]), kinds))
+            ranges = dict(DRAW_PERTURB_RANGES, **(ranges or {}))
+            for k in kinds:
+                lo, hi = ranges[k]
+                if not lo <= hi:
+                    raise ValueError('BatchPlan: the range of %s must be (low, high) with low <= high, got %r' % (k, ranges[k]))
+                (kind, plo, _), (_, phi, _) = perturbation(k, lo), perturbation(k, hi)      # both ends are values it takes
+                if k == 'blur':
+                    plo, phi = 0, DRAW_BLUR_ROWS - 1
+                    self.taps = gaussian_taps([lo + (hi - lo) * i / (DRAW_BLUR_ROWS - 1) for i in range(DRAW_BLUR_ROWS)])
+                rows.append([kind, plo, phi])
+        self.kinds = torch.tensor(rows, dtype=torch.int32).reshape(-1, 3)
+        self.shapes = draw_shapes(K, scale, ratio)
+        self.videos, self.base = videos.to(torch.int32).contiguous(), base
+        self.T, self.B, self.stride, self.N, self.seed, self._step = T, B, stride, N, seed, step
+        self.Hmax, self.Wmax = int(whole[:, 2].max()), int(whole[:, 3].max())
+        self.max_side = int(base[:, 2:].max())                     # no drawn box is larger: draw_clips asks max_side <= 8 S
+        self.block = self.storage = self.draw = self.taps_dev = self.parts = None
+
+    # ---- the draw block
+    def block_host(self, gap: int = 0, fill: int = 0):
+        """-> (the draw block as an int32 host tensor, {name: (offset, length)}): the header and the four input tables in
+        place, every other int `fill`"""
+        V, K, nk = int(self.videos.shape[0]), int(self.shapes.shape[0]), int(self.kinds.shape[0])
+        parts, ints = draw_block_layout(self.B, self.T, V, self.N, K, nk, gap)
+        if ints > 2 ** 31 - 1:
+            raise ValueError('BatchPlan: a draw block of %d ints is too large' % ints)
+        block = torch.full((ints,), fill, dtype=torch.int32)
+        pair = lambda v: [_i32(v), _i32(v >> 32)]
+        head = [_i32(DRAW_MAGIC), ints, self.B, self.T, self.stride, V, self.N, K, nk, self.jpeg_lo, self.jpeg_hi, 0] + \
+            pair(self.thr_flip) + pair(self.thr_jpeg) + pair(self.thr_perturb) + pair(self.seed) + pair(self._step) + \
+            [0, 0, 0, 0] + [parts[name][0] for name in DRAW_PARTS] + [0]
+        assert len(head) == DRAW_HEADER_INTS
+        block[:DRAW_HEADER_INTS] = torch.tensor(head, dtype=torch.int32)
+        for name in ('videos', 'base', 'shapes', 'kinds'):
+            off, length = parts[name]
+            block[off:off + length] = getattr(self, name).reshape(-1)
+        return block, parts
+
+    def on(self, device, gap: int = 0, tail: int = 0, fill: int = 0) -> 'BatchPlan':
+        """Uploads the plan as its draw block, once (a second call is a no-op): .block the int32 device tensor, .draw its
+        parts as views -- index (B*T,), boxes (B*T, 4), quality (B*T,), view (B, 3), perturb (B, 4), label (B,), status (1,),
+        drawn (2,) -- and .taps_dev.  gap, tail, fill: ints left between the parts and behind the block, and what they
+        hold (for tests)."""
+        if self.block is not None:
+            asked = torch.device(device)
+            if asked.type != self.block.device.type or asked.index not in (None, self.block.device.index):
+                raise RuntimeError('BatchPlan: this plan lives on %s' % self.block.device)
+            return self
+        host, parts = self.block_host(gap, fill)
+        ints = int(host.numel())
+        self.storage = torch.cat([host, torch.full((tail,), fill, dtype=torch.int32)]).to(device)
+        self.block, self.parts = self.storage[:ints], parts
+        n, B = self.B * self.T, self.B
+        part = lambda name: self.block[parts[name][0]:parts[name][0] + parts[name][1]]
+        self.draw = SimpleNamespace(
+            index=part('index'), boxes=part('boxes').view(n, 4), quality=part('quality'), view=part('view').view(B, 3),
+            perturb=part('perturb').view(B, 4), label=part('label'), status=self.block[DRAW_STATUS_WORD:DRAW_STATUS_WORD + 1],
+            drawn=self.block[DRAW_DRAWN_WORD:DRAW_DRAWN_WORD + 2])
+        self.taps_dev = None if self.taps is None else self.taps.to(device)
+        return self
+
+    @property
+    def step(self) -> int:
+        """the step the next draw takes: on the device once on() has run, read back without draining the stream"""
+        if self.block is None:
+            return self._step
+        from .parallel import HostScalar
+        return int(HostScalar(self.block[DRAW_STEP_WORD:DRAW_STEP_WORD + 2].view(torch.int64)).item()) & (2 ** 64 - 1)
+
+    def seek(self, step: int) -> 'BatchPlan':
+        """the next draw takes `step`: a resumed run, or a batch drawn again"""
+        if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+            raise ValueError('BatchPlan: the step must lie in [0, 2^64), got %r' % (step,))
+        self._step = step
+        if self.block is not None:
+            self.block[DRAW_STEP_WORD:DRAW_STEP_WORD + 2].copy_(torch.tensor([_i32(step), _i32(step >> 32)], dtype=torch.int32))
+        return self
+
+
+def batch_draw_host(plan: BatchPlan, step: int) -> SimpleNamespace:
+    """The definition of ops.batch_draw: the batch of `step`, int32 host tensors -- index (B*T,) the place of the bank every
+    frame is, boxes (B*T, 4), quality (B*T,), view (B, 3), perturb (B, 4), label (B,) -- in the shapes crop_resize_u8,
+    jpeg_roundtrip_u8 and perturb_u8 take with checked=True.  Integer arithmetic only.  Clip b takes the twelve words w0..w11
+    of philox4x32_10((step & 0xffffffff, step >> 32, b, j), (seed & 0xffffffff, seed >> 32)), j = 0, 1, 2, and with
+    u(w, n) = (w * n) >> 32 and on(w, thr) = w < thr:
+
+        video v = u(w0, V);  start = u(w1, count_v - (T - 1) * stride);  index[b, t] = first_v + start + t * stride
+        label[b] = label_v;  view[b] = (0, 0, on(w2, thr_flip));  shape row k = u(w3, K)
+        per frame, with the base box (by, bx, bh, bw) of its place:
+            h = clamp((min(bh, bw) * rh_k + 32768) >> 16, 1, bh),  w likewise with rw_k and bw
+            box = (by + u(w4, bh - h + 1), bx + u(w5, bw - w + 1), h, w)
+        quality[b] = lo + u(w7, hi - lo + 1) if on(w6, thr_jpeg) else 0
+        perturb[b] = (kind_i, lo_i + u(w10, hi_i - lo_i + 1), w11 & (2^30 - 1), b) with i = u(w9, nk) if on(w8, thr_perturb),
+                     else (0, 0, w11 & (2^30 - 1), b)
+
+    One draw per clip is applied to each frame's own base box, so a crop follows the face through its clip.  The tables pass
+    check_boxes (for S with plan.max_side <= 8 S), check_views, check_qualities and check_perturbations by construction."""
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+        raise ValueError('batch_draw_host: the step must lie in [0, 2^64), got %r' % (step,))
+    B, T, stride = plan.B, plan.T, plan.stride
+    b = torch.arange(B, dtype=torch.int64)
+    key = (plan.seed & 0xffffffff, plan.seed >> 32)
+    w = []
+    for j in range(3):
+        w += list(philox4x32_10((step & 0xffffffff, step >> 32, b, j), key))
+    u = lambda word, n: (word * n) >> 32
+    vid = plan.videos.long()[u(w[0], plan.videos.shape[0])]
+    start = u(w[1], vid[:, 1] - (T - 1) * stride)
+    index = (vid[:, 0] + start)[:, None] + torch.arange(T, dtype=torch.int64)[None, :] * stride
+    flip = (w[2] < plan.thr_flip).long()
+    shape = plan.shapes.long()[u(w[3], plan.shapes.shape[0])]
+    bb = plan.base.long()[index]                                    # (B, T, 4)
+    by, bx, bh, bw = bb.unbind(-1)
+    m = torch.minimum(bh, bw)
+    h = torch.minimum(((m * shape[:, 0:1] + 32768) >> 16).clamp(min=1), bh)
+    wd = torch.minimum(((m * shape[:, 1:2] + 32768) >> 16).clamp(min=1), bw)
+    boxes = torch.stack([by + u(w[4][:, None], bh - h + 1), bx + u(w[5][:, None], bw - wd + 1), h, wd], dim=-1)
+    quality = torch.where(w[6] < plan.thr_jpeg, plan.jpeg_lo + u(w[7], plan.jpeg_hi - plan.jpeg_lo + 1), torch.zeros_like(b))
+    perturb = torch.zeros((B, 4), dtype=torch.int64)
+    perturb[:, 2], perturb[:, 3] = w[11] & (2 ** 30 - 1), b
+    if plan.thr_perturb > 0:
+        row = plan.kinds.long()[u(w[9], plan.kinds.shape[0])]
+        hit = w[8] < plan.thr_perturb
+        perturb[:, 0] = torch.where(hit, row[:, 0], torch.zeros_like(b))
+        perturb[:, 1] = torch.where(hit, row[:, 1] + u(w[10], row[:, 2] - row[:, 1] + 1), torch.zeros_like(b))
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return SimpleNamespace(index=i32(index.reshape(-1)), boxes=i32(boxes.reshape(-1, 4)),
+                           quality=i32(quality[:, None].expand(B, T).reshape(-1)),
+                           view=i32(torch.stack([torch.zeros_like(flip), torch.zeros_like(flip), flip], dim=1)),
+                           perturb=i32(perturb), label=i32(vid[:, 2]), step=step)

@@ -1,12 +1,18 @@
 // Philox4x32-10 (Salmon, Moraes, Dror and Shaw, "Parallel random numbers: as easy as 1, 2, 3", SC'11): a four-word counter
 // and a two-word key -> four 32-bit words.  Ten rounds of two 32 x 32 -> 64-bit products; the key words grow by the Weyl
 // constants between rounds.  Known answers (counter and key all zero -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8) are held by
-// clips.philox4x32_10, the host restatement the kernels' bytes are compared with.
+// clips.philox4x32_10, the host restatement the kernels' bytes are compared with.  A host program compiles it too
+// (csrc/batch_draw.h, tools/batch_draw_check.cpp): plain integer arithmetic, the same words on either side.
 #pragma once
+#if defined(__HIPCC__)
 #include "common.h"
+#define PHILOX_HD __host__ __device__ __forceinline__
+#else
+#define PHILOX_HD inline
+#endif
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&r)[4]) {
+PHILOX_HD void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                             unsigned (&r)[4]) {
 #pragma unroll
     for (int i = 0; i < 10; ++i) {
         const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;

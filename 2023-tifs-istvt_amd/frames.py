@@ -1,7 +1,8 @@
 """The routines on decoded uint8 frames (clips.py holds their definitions on the host): crops, similarity warps, the NV12
 readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12; and the JPEG decoder
 that makes such frames from files (jpeg_decode_u8, decode_frames) and the encoder that makes files from them (jpeg_encode_u8,
-encode_frames).
+encode_frames); and the batch draw, which makes the index and the tables of a training batch on the device (batch_draw,
+jpeg_decode_drawn_u8, draw_clips).
 
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
@@ -482,6 +483,33 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     return out, sizes, status
 
 
+def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], buffers):
+    """What a decode of m places of a bank needs beside the index: the canvas, the uploaded bank, `out` and `buffers` checked
+    or made -> (the bank on its device, Hc, Wc, out, scratch, sizes, status)"""
+    Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < bank.Hmax or Wc < bank.Wmax or Hc > 16384 or Wc > 16384:
+        raise ValueError('%s: the canvas must hold every image of the bank (%d x %d at least, 16384 x 16384 '
+                         'at most), got %d x %d' % (what, bank.Hmax, bank.Wmax, Hc, Wc))
+    dev = bank.on(device)
+    out = _u8_out(what, dev.data, (m, Hc, Wc, 3), out)
+    _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
+    need = clips.jpeg_bank_scratch_bytes(bank, m)
+    device = dev.data.device
+    if buffers is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
+        sizes = torch.empty((m, 2), dtype=torch.int32, device=device)
+        status = torch.empty((m,), dtype=torch.int32, device=device)
+    else:
+        scratch, sizes, status = buffers
+        ok = (t.device == device and t.is_contiguous() for t in buffers)
+        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
+                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (m, 2)
+                or status.dtype != torch.int32 or tuple(status.shape) != (m,)):
+            raise RuntimeError('%s: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes '
+                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (what, need, m, m, device))
+    return dev, Hc, Wc, out, scratch, sizes, status
+
+
 def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = None, buffers=None, split=None):
     """JPEG bank (clips.py): the files of a clips.JpegBank stay on the device, and the m of them that `index` names are
     decoded, in that order and with repeats -> (frames, sizes, status) as jpeg_decode_u8 hands them back, the bits of
@@ -506,31 +534,11 @@ def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = Non
     device = torch.device(bank.device) if bank.device is not None else index.device if index.is_cuda else \
         out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
     m = int(index.numel())
-    Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
-    if Hc < bank.Hmax or Wc < bank.Wmax or Hc > 16384 or Wc > 16384:
-        raise ValueError('jpeg_decode_indexed_u8: the canvas must hold every image of the bank (%d x %d at least, 16384 x 16384 '
-                         'at most), got %d x %d' % (bank.Hmax, bank.Wmax, Hc, Wc))
-    dev = bank.on(device)
+    dev, Hc, Wc, out, scratch, sizes, status = _bank_call('jpeg_decode_indexed_u8', bank, m, device, canvas, out, buffers)
     if index.device != dev.data.device:
         index = index.to(dev.data.device, non_blocking=True)
     if index.dtype != torch.int32:                                # -1 and n are outside the bank as everything beyond them is
         index = index.clamp(-1, bank.n).to(torch.int32)
-    out = _u8_out('jpeg_decode_indexed_u8', dev.data, (m, Hc, Wc, 3), out)
-    _no_overlap('jpeg_decode_indexed_u8', out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
-    need = clips.jpeg_bank_scratch_bytes(bank, m)
-    device = dev.data.device
-    if buffers is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
-        sizes = torch.empty((m, 2), dtype=torch.int32, device=device)
-        status = torch.empty((m,), dtype=torch.int32, device=device)
-    else:
-        scratch, sizes, status = buffers
-        ok = (t.device == device and t.is_contiguous() for t in buffers)
-        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
-                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (m, 2)
-                or status.dtype != torch.int32 or tuple(status.shape) != (m,)):
-            raise RuntimeError('jpeg_decode_indexed_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes '
-                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (need, m, m, device))
     args = _lib.JpegDecodeArgs(
         bytes=dev.data.data_ptr(), nbytes=bank.nbytes, images=dev.images.data_ptr(), images_host=index.data_ptr(),
         segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
@@ -540,6 +548,84 @@ def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = Non
         _lib.check(_lib.lib().istvt_jpeg_decode_indexed_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
                                                            bank.Wmax), 'istvt_jpeg_decode_indexed_u8')
     return out, sizes, status
+
+
+# ---- batch draw ----------------------------------------------------------------------------------------------------------------
+def _drawn_plan(what: str, plan) -> 'clips.BatchPlan':
+    if not isinstance(plan, clips.BatchPlan):
+        raise TypeError('%s expects a clips.BatchPlan, got %s' % (what, type(plan).__name__))
+    if plan.block is None or not plan.block.is_cuda:
+        raise RuntimeError('%s: the plan is drawn from where its draw block lives: upload it first, plan.on(device)' % what)
+    return plan
+
+
+def batch_draw(plan):
+    """Batch draw (clips.py): the tables of the batch of the plan's current step, drawn on the device into the plan's draw
+    block, and the step advanced there -> plan.draw, the namespace of int32 device views index (B*T,), boxes (B*T, 4), quality
+    (B*T,), view (B, 3), perturb (B, 4), label (B,), status (1,) (0: drawn; clips.DRAW_STATUS names the refusals, which leave
+    tables and step as they were) and drawn (2,), the step as two words.  The bits of clips.batch_draw_host(plan, step).  One
+    launch of one workgroup; no synchronisation, no allocation and no host read, so the call can be captured in a graph, and
+    every replay draws the next step.  The views are the same tensors at every call: crop_resize_u8, jpeg_roundtrip_u8 and
+    perturb_u8 take them with checked=True, jpeg_decode_indexed_u8 takes the index, and a source of raw uint8 clips can be
+    gathered through it just as well."""
+    plan = _drawn_plan('batch_draw', plan)
+    args = _lib.JpegDecodeArgs(images_host=plan.block.data_ptr(), stream=_stream())
+    with prof('batch_draw', 4 * plan.block.numel()):
+        _lib.check(_lib.lib().istvt_batch_draw(ctypes.byref(args), plan.B, plan.T, plan.block.numel()), 'istvt_batch_draw')
+    return plan.draw
+
+
+def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, buffers=None):
+    """batch_draw(plan) and jpeg_decode_indexed_u8(bank, the index just drawn) as one call of five launches -> (frames, sizes,
+    status, draw): frames uint8 [B*T, Hc, Wc, 3], sizes and status as the indexed decode hands them back, draw as batch_draw
+    does.  The plan was built for this bank (as many places) and lives on its device.  canvas, out and buffers are
+    jpeg_decode_indexed_u8's, for m = B * T; with out and buffers the call can be captured in a graph."""
+    if not isinstance(bank, clips.JpegBank):
+        raise TypeError('jpeg_decode_drawn_u8 expects a clips.JpegBank, got %s' % type(bank).__name__)
+    plan = _drawn_plan('jpeg_decode_drawn_u8', plan)
+    if plan.N != bank.n:
+        raise ValueError('jpeg_decode_drawn_u8: the plan was built for a bank of %d places, this one has %d' % (plan.N, bank.n))
+    m = plan.B * plan.T
+    dev, Hc, Wc, out, scratch, sizes, status = _bank_call('jpeg_decode_drawn_u8', bank, m, plan.block.device, canvas, out, buffers)
+    if dev.data.device != plan.block.device:
+        raise RuntimeError('jpeg_decode_drawn_u8: the bank lives on %s, the plan on %s' % (dev.data.device, plan.block.device))
+    args = _lib.JpegDecodeArgs(
+        bytes=dev.data.data_ptr(), nbytes=bank.nbytes, images=dev.images.data_ptr(), images_host=plan.block.data_ptr(),
+        segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
+        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
+        status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
+    with prof('jpeg_decode_drawn_u8', 2 * 192 * m * bank.block_stride + out.numel()):
+        _lib.check(_lib.lib().istvt_jpeg_decode_drawn_u8(ctypes.byref(args), plan.B, plan.T, plan.block.numel(), bank.seg_max,
+                                                         bank.block_stride, bank.Hmax, bank.Wmax), 'istvt_jpeg_decode_drawn_u8')
+    return out, sizes, status, plan.draw
+
+
+def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
+    """The whole input side of a training step on the device: the batch of the plan's current step is drawn and decoded
+    (jpeg_decode_drawn_u8), every frame cut and resized through its drawn box (crop_resize_u8), recompressed at its clip's
+    drawn quality (jpeg_roundtrip_u8; left out when the plan's jpeg is off) and perturbed by its clip's drawn row (perturb_u8
+    with the plan's taps and its seed as the noise key; left out when the plan's perturb is off) -> (u8 [B, T, S, S, 3], view
+    int32 [B, 3], label int32 [B], status int32 [B*T]), all on the device: the bytes of the same calls on the host tables of
+    clips.batch_draw_host(plan, step).  The step is model(u8, view=view, view_checked=True, crop=S).  No host table, no
+    upload, no synchronisation: with `out` (uint8, contiguous, of the result's shape) the call can be captured in a graph,
+    and every replay gives the next batch.  view, label and the draw behind them are views of the plan's draw block, which
+    the next draw overwrites."""
+    plan = _drawn_plan('draw_clips', plan)
+    S = _side('draw_clips', S)
+    if plan.max_side > clips.MAX_BOX_SCALE * S:
+        raise ValueError('draw_clips: the largest base box of the plan has a side of %d; boxes of at most %d (8 x the output side '
+                         '%d) are resized' % (plan.max_side, clips.MAX_BOX_SCALE * S, S))
+    B, T = plan.B, plan.T
+    out = _u8_out('draw_clips', plan.block, (B, T, S, S, 3), out)
+    frames, _, status, draw = jpeg_decode_drawn_u8(bank, plan)
+    stages = ['crop'] + ['jpeg'] * (plan.thr_jpeg > 0) + ['perturb'] * (plan.thr_perturb > 0)
+    flat = lambda stage: out.view(B * T, S, S, 3) if stages[-1] == stage else None      # the last stage writes `out`
+    u8 = crop_resize_u8(frames, draw.boxes, S, out=flat('crop'), checked=True)
+    if 'jpeg' in stages:
+        u8 = jpeg_roundtrip_u8(u8, draw.quality, out=flat('jpeg'), checked=True)
+    if 'perturb' in stages:
+        u8 = perturb_u8(u8.view(B, T, S, S, 3), draw.perturb, plan.taps_dev, plan.seed, out=out, checked=True)
+    return u8.view(B, T, S, S, 3), draw.view, draw.label, status
 
 
 _JPEG_STD_HTABS: dict = {}        # (device, tables) -> the Annex K.3 Huffman tables in decode form on the device

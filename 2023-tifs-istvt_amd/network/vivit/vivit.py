@@ -216,18 +216,20 @@ class XceptionVidTr(nn.Module):
             self._step_graphs = None
         return self
 
-    def forward(self, x, view=None, crop=None):
+    def forward(self, x, view=None, crop=None, view_checked=False):
         """x float32 (b, t, 3, S, S), already normalised: the reference's call.  x uint8 (b, t, Hs, Ws, 3), the clips as
         decoded (istvt_amd.clips): conv1 normalises the bytes (set_input_normalisation) and reads them through `view`,
         int32 (b, 3) = one (y0, x0, flip) per clip shared by its t frames -- a host tensor, validated before any launch --,
         with crop side `crop` (default: the side the model's token grid stands for).  Without a view the frames must
-        already be crop-sized.  A uint8 step runs launch by launch also with step graphs on."""
+        already be crop-sized.  A uint8 step runs launch by launch also with step graphs on.  view_checked=True takes a view
+        that lives on the device as validated by whoever made it (ops.draw_clips): its dtype, shape and device are looked
+        at and nothing is copied back."""
         if x.dtype == torch.uint8:
             g = self._step_graphs
             if g is not None:
                 g.note_eager('uint8 input: the byte path is not captured')
-            return self._forward_eager(x, view, crop)
-        if view is not None or crop is not None:
+            return self._forward_eager(x, view, crop, view_checked)
+        if view is not None or crop is not None or view_checked:
             raise RuntimeError('view / crop apply to uint8 clips; float input is taken as already cropped and normalised')
         g = self._step_graphs
         if g is not None:
@@ -289,7 +291,7 @@ class XceptionVidTr(nn.Module):
             raise ValueError('a view needs the crop side: model(x, view=view, crop=S) or model.set_crop_side(S)')
         return self.crop_side
 
-    def _forward_eager(self, x, view=None, crop=None):
+    def _forward_eager(self, x, view=None, crop=None, view_checked=False):
         b, t = x.shape[:2]
         if x.dtype == torch.uint8:
             from istvt_amd import clips
@@ -299,9 +301,16 @@ class XceptionVidTr(nn.Module):
             Hs, Ws = x.shape[2], x.shape[3]
             if crop is None:
                 crop = self._crop_side() if view is not None else Hs
-            v = clips.check_views(view, b, Hs, Ws, crop)
-            if v is not None:               # one small upload, expanded to the per-frame table on the device
-                v = clips.per_frame_views(v.contiguous().to(x.device, non_blocking=True), t)
+            if view_checked:                # the caller's device table as it is: nothing is read back
+                if not torch.is_tensor(view) or view.dtype != torch.int32 or tuple(view.shape) != (b, 3) or view.device != x.device:
+                    raise RuntimeError('a checked view is int32 (%d, 3) on %s' % (b, x.device))
+                if not 3 <= crop <= min(Hs, Ws):
+                    raise ValueError('the crop side must satisfy 3 <= S <= min(Hs, Ws), got S=%d for %d x %d frames' % (crop, Hs, Ws))
+                v = clips.per_frame_views(view, t)
+            else:
+                v = clips.check_views(view, b, Hs, Ws, crop)
+                if v is not None:           # one small upload, expanded to the per-frame table on the device
+                    v = clips.per_frame_views(v.contiguous().to(x.device, non_blocking=True), t)
             mean, std = self._input_norm_on(x.device)
             feats = self.xcep.model.low_level_features_nhwc(x.flatten(0, 1), self.compute_dtype, mean, std,
                                                             train_bytes=True, view=v, crop=crop)

@@ -467,6 +467,30 @@ int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes)
  * canvas smaller than Hmax x Wmax, a scratch too small or misaligned, or an out that overlaps bytes; the bank's tables were
  * checked when it was built, and the plan kernel turns a row that does not fit the strides or the canvas into status 5. */
 int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax, int Wmax);
+/* Batch draw: which B clips of T frames a training step takes from a bank and how each is augmented, drawn on the device as a
+ * pure function of (seed, step); the bits of clips.batch_draw_host.  The plan, the step counter and the drawn tables live in
+ * one int32 tensor on the device, the draw block of block_ints ints (csrc/batch_draw.h names the words):
+ *   [0, 36)   header: magic 'BDRW', block_ints, B, T, stride, V, N, K, nk, jpeg lo, jpeg hi, 0 | as (low, high) pairs the
+ *             thresholds round(p * 2^32) of flip, jpeg and perturb, the seed and the step | status, 0, the step that was
+ *             drawn (low, high) | the offsets in ints of videos, base, shapes, kinds, boxes, quality, view, perturb, label | 0
+ *   [36, 36 + B*T)   index: the place of the bank every frame is
+ *   the nine parts at their offsets, in that order, each behind the one before: videos [V][3] = (first place, frames, label),
+ *   base [N][4] = (y0, x0, h, w) per place, shapes [K][2] = Q16 (rh, rw), kinds [nk][3] = (kind, lo, hi), which are read, and
+ *   boxes [B*T][4], quality [B*T], view [B][3], perturb [B][4], label [B], which are written.
+ * The argument block is istvt_jpeg_decode_args, as the bank's entries take it; istvt_batch_draw reads two fields:
+ *   images_host    NOT a host pointer here: the draw block, int32 [block_ints] on the device
+ *   stream
+ * One launch of ONE workgroup: every lane reads the step, and behind a barrier lane 0 stores step + 1, the step drawn and
+ * status 0.  A block whose header disagrees with B, T or block_ints, or names a part outside the block or in front of the part
+ * before it, gets status 1; one whose videos rows leave the base table or are shorter than (T - 1) * stride + 1 frames gets
+ * status 2; either way no other word is written and the step stays.  Nothing outside the block is read or written.  No
+ * synchronisation, nothing allocated.  -3 for a null block, B or T < 1, or block_ints < 36 + B * T. */
+int istvt_batch_draw(const istvt_jpeg_decode_args* a, int B, int T, int block_ints);
+/* The draw followed by istvt_jpeg_decode_indexed_u8 with m = B * T on the index it wrote: five launches.  images_host is the
+ * draw block as above; every other field, and seg_max, block_stride, Hmax and Wmax, are the indexed decode's.  Statuses 4
+ * and 5 are what they were; a refused block leaves its index as it was, which the plan kernel checks like any other. */
+int istvt_jpeg_decode_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max, int block_stride,
+                               int Hmax, int Wmax);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
