@@ -1419,6 +1419,13 @@ def check_split(chunk_bytes) -> int:
     return chunk_bytes
 
 
+def jpeg_split_chunks(length: int, chunk_bytes: int):
+    """the chunk rule for one segment of `length` bytes -> (chunk size, number of chunks): js_chunk_bytes and js_chunks of
+    csrc/jpeg_entropy_split.h"""
+    c = max(chunk_bytes, -(-length // JPEG_SPLIT_LANES))
+    return c, max(1, -(-length // c))
+
+
 def jpeg_split_plan(batch_or_header, chunk_bytes: int) -> SimpleNamespace:
     """How ops.jpeg_decode_u8(..., split=chunk_bytes) cuts the segments of a JpegBatch (or of one parsed file, packed alone):
     a segment of `length` bytes into chunks of max(chunk_bytes, ceil(length / 256)) bytes, at least one and at most 256 of
@@ -1429,9 +1436,9 @@ def jpeg_split_plan(batch_or_header, chunk_bytes: int) -> SimpleNamespace:
     batch = batch_or_header if isinstance(batch_or_header, JpegBatch) else jpeg_batch([batch_or_header])
     chunk, count, row0 = [], [], []
     for s, (_, b, e, _, _) in enumerate(batch.segments.tolist()):
-        c = max(chunk_bytes, -(-(e - b) // JPEG_SPLIT_LANES))
+        c, k = jpeg_split_chunks(e - b, chunk_bytes)
         chunk.append(c)
-        count.append(max(1, -(-(e - b) // c)))
+        count.append(k)
         row0.append(b // chunk_bytes + s)
     rows = batch.nbytes // chunk_bytes + len(chunk)
     at = -(-batch.scratch_bytes // 16) * 16
@@ -1673,6 +1680,16 @@ def _bank_bytes(nbytes: int, who: str) -> int:
     return nbytes
 
 
+def _bank_split(split, who: str):
+    """the `split` argument of a bank, checked: None, 'auto' or a chunk size that check_split accepts"""
+    if split is None or (isinstance(split, str) and split == 'auto'):
+        return split
+    if isinstance(split, bool) or not isinstance(split, int) or split < JPEG_SPLIT_MIN:
+        raise ValueError("%s: split is None, 'auto' or a chunk size in bytes (an int of at least %d), got %r"
+                         % (who, JPEG_SPLIT_MIN, split))
+    return split
+
+
 class JpegBank:
     """A set of files ready for ops.jpeg_decode_indexed_u8: what a JpegBatch of the whole set holds -- data, images (n, 20),
     segments, qtabs, htabs, sizes, as JpegBatch describes them -- and the two numbers that make a call's geometry independent
@@ -1682,15 +1699,52 @@ class JpegBank:
 
     jpeg_bank builds one from host files: the tensors are host tensors (pinned where a device is there to take them),
     `headers` keeps the parsed files for jpeg_bank_decode_host, and on(device) uploads once.  from_encoded and extend build
-    one on a device: data .. htabs are None, `device` says where it lives, and on(device) hands those tensors back."""
+    one on a device: data .. htabs are None, `device` says where it lives, and on(device) hands those tensors back.
+
+    How the bank's restart intervals are decoded is a property of the bank (DESIGN.md "JPEG bank, split"), not of a call,
+    because it fixes a call's scratch layout and workgroup size.  split: None, one lane per interval, or the chunk size in
+    bytes of the split entropy kernel, one lane per chunk (ops.jpeg_decode_u8 describes both; files without restart markers
+    want the second).  seg_bytes_max: the longest interval of the set in bytes, or None where the host has not seen the
+    lengths (an ingested bank whose caller named none).  chunk_rows: the state rows a split bank reserves per segment."""
 
     def __init__(self, **kw):
-        self.device = self.headers = None
+        self.device = self.headers = self.split = self.seg_bytes_max = None
         self.__dict__.update(kw)
         self._on = {}
 
     def __len__(self) -> int:
         return self.n
+
+    @property
+    def chunk_rows(self):
+        """min(256, max(1, ceil(seg_bytes_max / split))): an upper bound of jpeg_split_plan's chunk count for every length up
+        to seg_bytes_max (ceil(L / max(split, ceil(L / 256))) <= ceil(L / split), which grows with L, and <= 256) -- not
+        the count at seg_bytes_max itself, which is not monotone once the 256-lane cap raises the chunk size.  256 where
+        seg_bytes_max is not known: no interval has more chunks.  None for a bank without a split."""
+        if self.split is None:
+            return None
+        if self.seg_bytes_max is None:
+            return JPEG_SPLIT_LANES
+        return min(JPEG_SPLIT_LANES, max(1, -(-self.seg_bytes_max // self.split)))
+
+    def _resolve_split(self, split, who: str):
+        """the `split` argument of jpeg_bank / with_split -> None or a chunk size: JPEG_SPLIT_DEFAULT for 'auto' where the
+        longest interval exceeds JPEG_SPLIT_AUTO_BYTES (ops.jpeg_decode_u8's rule, decided once per bank)"""
+        if _bank_split(split, who) != 'auto':
+            return split
+        if self.seg_bytes_max is None:
+            raise ValueError("%s: split='auto' needs the longest interval of the bank, which the host has not seen for an "
+                             "ingested bank: name seg_bytes_max= in JpegBank.from_encoded, or a chunk size" % who)
+        return JPEG_SPLIT_DEFAULT if self.seg_bytes_max > JPEG_SPLIT_AUTO_BYTES else None
+
+    def with_split(self, split) -> 'JpegBank':
+        """A second JpegBank over the same files with another `split` (None, 'auto' or a chunk size): the same tensors and
+        the same uploaded copies, nothing copied or uploaded again.  with_split(None) is the bank of one lane per interval.
+        The two share what on() has uploaded; extend() and release_host() act on the bank they are called on alone."""
+        other = JpegBank.__new__(JpegBank)
+        other.__dict__.update(self.__dict__)                     # _on included: one cache
+        other.split = self._resolve_split(split, 'JpegBank.with_split')
+        return other
 
     def on(self, device):
         """the five tensors on `device`: .data .images .segments .qtabs .htabs, uploaded once without blocking (JpegBatch.on)"""
@@ -1711,18 +1765,22 @@ class JpegBank:
         self.data = self.images = self.segments = self.qtabs = self.htabs = self.headers = None
 
     @classmethod
-    def from_encoded(cls, jf, H=None, W=None, layout=None, restart_interval=None) -> 'JpegBank':
+    def from_encoded(cls, jf, H=None, W=None, layout=None, restart_interval=None, seg_bytes_max=None) -> 'JpegBank':
         """The result of ops.jpeg_encode_u8 / ops.encode_frames (a JpegFiles) -> a bank over the same bytes, on their device:
         no files(), no readback, no synchronisation (frames.jpeg_bank_ingest has the launches).  The geometry all files of
         the call share comes from jf.geometry, which the encoder call leaves there; H, W, layout (one of JPEG_LAYOUTS) and
-        restart_interval name it for a JpegFiles put together by hand.  Files with optimised tables are refused."""
+        restart_interval name it for a JpegFiles put together by hand.  Files with optimised tables are refused.
+        seg_bytes_max: the longest restart interval in bytes, where the caller knows a bound -- the host does not read the
+        lengths here.  A split decode then reserves chunk_rows for it instead of 256 per segment, and a file with a longer
+        interval decodes to status 5; without it split='auto' is refused."""
         from . import frames
-        return frames.jpeg_bank_ingest(jf, H, W, layout, restart_interval)
+        return frames.jpeg_bank_ingest(jf, H, W, layout, restart_interval, seg_bytes_max)
 
     def extend(self, other: 'JpegBank', device=None) -> 'JpegBank':
         """Appends the files of `other` (another encode call's bank, say) behind this bank's, on the device both live on (or
         `device` for two host banks): the bytes are joined, and offsets, table slots and first segments of `other` are
-        rebased with tensor expressions there.  Nothing is read back.  Afterwards this bank lives on that device alone."""
+        rebased with tensor expressions there.  Nothing is read back.  Afterwards this bank lives on that device alone.
+        seg_bytes_max becomes the larger of the two, or None where either is; split stays this bank's."""
         if not isinstance(other, JpegBank):
             raise TypeError('JpegBank.extend takes a JpegBank, got %s' % type(other).__name__)
         device = device or self.device or other.device
@@ -1748,16 +1806,22 @@ class JpegBank:
         self.sizes = list(self.sizes) + list(other.sizes)
         self.seg_max, self.block_stride = max(self.seg_max, other.seg_max), max(self.block_stride, other.block_stride)
         self.Hmax, self.Wmax = max(self.Hmax, other.Hmax), max(self.Wmax, other.Wmax)
+        known = self.seg_bytes_max is not None and other.seg_bytes_max is not None
+        self.seg_bytes_max = max(self.seg_bytes_max, other.seg_bytes_max) if known else None
         self.data = self.images = self.segments = self.qtabs = self.htabs = self.headers = None
         self.device, self._on = torch.device(device), {str(torch.device(device)): joined}
         return self
 
 
-def jpeg_bank(files, layouts=JPEG_LAYOUTS_DEFAULT) -> JpegBank:
+def jpeg_bank(files, layouts=JPEG_LAYOUTS_DEFAULT, split=None) -> JpegBank:
     """A sequence of baseline JPEG files (bytes, or parsed JpegHeaders) -> the JpegBank of the set, on the host.  Every file
     goes through jpeg_parse with `layouts`, which refuses what the decoder does not take, and jpeg_batch packs the tables:
-    the rows are those of jpeg_batch(files).  A set of 2^31 scan bytes or more is refused."""
+    the rows are those of jpeg_batch(files).  A set of 2^31 scan bytes or more is refused.  split: how the bank's restart
+    intervals are decoded (JpegBank): None, by one lane each; a chunk size in bytes, by one lane per chunk, for files
+    without restart markers; 'auto', JPEG_SPLIT_DEFAULT where the longest interval of the set (bank.seg_bytes_max) exceeds
+    JPEG_SPLIT_AUTO_BYTES, else None."""
     layouts = _jpeg_layouts(layouts, 'jpeg_bank')
+    _bank_split(split, 'jpeg_bank')                               # said before anything is parsed
     if isinstance(files, (bytes, bytearray, JpegFiles)) or not hasattr(files, '__len__'):
         raise TypeError('jpeg_bank expects a sequence of files (bytes); JpegBank.from_encoded takes a JpegFiles, got %s'
                         % type(files).__name__)
@@ -1766,21 +1830,28 @@ def jpeg_bank(files, layouts=JPEG_LAYOUTS_DEFAULT) -> JpegBank:
     headers = [f if isinstance(f, JpegHeader) else jpeg_parse(f, layouts) for f in files]
     _bank_bytes(sum(hd.segments[-1][1] - hd.segments[0][0] for hd in headers), 'jpeg_bank')
     batch = jpeg_batch(headers, layouts)
-    return JpegBank(data=batch.data, nbytes=batch.nbytes, images=batch.images, segments=batch.segments, qtabs=batch.qtabs,
+    bank = JpegBank(data=batch.data, nbytes=batch.nbytes, images=batch.images, segments=batch.segments, qtabs=batch.qtabs,
                     htabs=batch.htabs, sizes=batch.sizes, n=batch.n, nseg=int(batch.segments.shape[0]),
                     nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), blocks=batch.blocks, groups=batch.groups,
                     seg_max=int(batch.images[:, 17].max()),
                     block_stride=-(-int(batch.images[:, 18].max()) // JPEG_IDCT_BLOCKS) * JPEG_IDCT_BLOCKS,
-                    Hmax=max(h for h, _ in batch.sizes), Wmax=max(w for _, w in batch.sizes), headers=headers)
+                    Hmax=max(h for h, _ in batch.sizes), Wmax=max(w for _, w in batch.sizes), headers=headers,
+                    seg_bytes_max=int((batch.segments[:, 2] - batch.segments[:, 1]).max()))
+    bank.split = bank._resolve_split(split, 'jpeg_bank')
+    return bank
 
 
 def jpeg_bank_scratch_bytes(bank: JpegBank, m: int) -> int:
     """The scratch of ops.jpeg_decode_indexed_u8 for m places: coefficients and planes of m * block_stride blocks | an int32
     status per segment row and one more per place | from the next multiple of 16 bytes, the planned images (m, 20) and
-    segments (m * seg_max, 5)"""
+    segments (m * seg_max, 5).  For a bank with a split, from the next multiple of 16 bytes behind those the state rows of the
+    split kernel, int32 (m * seg_max * chunk_rows, 8): planned segment row s owns rows [s * chunk_rows, (s + 1) * chunk_rows)."""
     m = int(m)
     front = 192 * m * bank.block_stride + 4 * (m * bank.seg_max + m)
-    return -(-front // 16) * 16 + 4 * JPEG_IMAGE_INTS * m + 20 * m * bank.seg_max
+    need = -(-front // 16) * 16 + 4 * JPEG_IMAGE_INTS * m + 20 * m * bank.seg_max
+    if bank.split is None:
+        return need
+    return -(-need // 16) * 16 + 4 * JPEG_STATE_INTS * m * bank.seg_max * bank.chunk_rows
 
 
 def check_bank_index(index, who: str = 'jpeg_bank_decode_host') -> Tensor:

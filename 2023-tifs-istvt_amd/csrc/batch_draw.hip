@@ -69,3 +69,16 @@ extern "C" int istvt_jpeg_decode_drawn_u8(const istvt_jpeg_decode_args* a, int B
     indexed.images_host = a->images_host + BD_HEADER_INTS;
     return istvt_jpeg_decode_indexed_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax);
 }
+
+// The same with the split decode of the bank behind the draw (istvt_jpeg_decode_indexed_split_u8): five launches.
+extern "C" int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max,
+                                                int block_stride, int Hmax, int Wmax, int chunk_bytes, int chunk_rows,
+                                                int seg_bytes_max) {
+    if (!bd_scalars_ok(a, B, T, block_ints)) return ISTVT_ERR_SHAPE;
+    const int rc = istvt_batch_draw(a, B, T, block_ints);
+    if (rc != ISTVT_OK) return rc;
+    istvt_jpeg_decode_args indexed = *a;
+    indexed.images_host = a->images_host + BD_HEADER_INTS;
+    return istvt_jpeg_decode_indexed_split_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax, chunk_bytes, chunk_rows,
+                                              seg_bytes_max);
+}

@@ -30,6 +30,8 @@
 // one lane per chunk of it (jpeg_entropy_split.h), for files whose intervals are long.  istvt_jpeg_decode_indexed_u8 (DESIGN.md
 // "JPEG bank") puts jpeg_bank_plan_kernel in front of the three kernels: files that stay on the device, drawn by an index
 // that lives there; istvt_jpeg_bank_ingest builds such a bank from the encoder's result (jpeg_bank_scan.h).
+// istvt_jpeg_decode_indexed_split_u8 (DESIGN.md "JPEG bank, split") is the indexed decode with the split kernel behind the
+// plan, its state rows at a stride per planned segment.
 //
 // JPEG files out (DESIGN.md "JPEG files out") are the third part: istvt_jpeg_encode_u8 writes a batch of frames as baseline
 // files in four launches.  jpeg_planes_kernel<SUB, true>: the front half of the round trip -> int16 coefficients.
@@ -545,9 +547,9 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     seg_status[s] = je_decode_segment(bytes, begin, end, huff, lay, mcux, first, count, w);
 }
 
-// The state rows of the split path (js_chunk_bytes, js_chunks: the chunk rule): those of segment s start at row begin /
-// chunk_bytes + s of the table behind the statuses.  Segments lie in order in the bytes and a segment has at most length /
-// chunk_bytes + 1 chunks, so the rows of two segments never meet and the table has nbytes / chunk_bytes + nseg rows.
+// The state rows of the split path (js_chunk_bytes, js_chunks: the chunk rule): js_row0 says where those of segment s lie in
+// the table behind the statuses, by the segment's byte offset (the batch call: a table of nbytes / chunk_bytes + nseg rows) or
+// at a stride per segment (the bank's calls: segment s owns rows [s * R, (s + 1) * R)).
 constexpr int JS_STATE_INTS = ISTVT_JPEG_STATE_INTS;
 
 // One workgroup per restart interval, one lane per chunk (jpeg_entropy_split.h).  All lanes clear the interval's blocks;
@@ -555,8 +557,10 @@ constexpr int JS_STATE_INTS = ISTVT_JPEG_STATE_INTS;
 // are scanned into each lane's first block and DC predictions; the lanes up to the first that met an error decode once more
 // with stores.  The barriers of the rounds lie between the clears and every put.  A state row: entry pos, bit, blk, k,
 // blocks started, first block, status of the lane's decode, rounds in which a state changed.  LANES: the workgroup's size,
-// 256, or 64 where no interval of the batch has more chunks than that (the entry knows from the host table).
-template <int LANES>
+// 256, or 64 where no interval of the batch has more chunks than that (the entry knows from the host table, or from the
+// bank's row stride).  STRIDED: the row addressing; `nrows` is then the row stride R, not the table's size, and an interval of
+// more than R chunks is refused with status 2 like one that fails the other comparisons: nothing of it is written.
+template <int LANES, bool STRIDED>
 __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t* __restrict__ bytes, long nbytes,
                                                                    const int* __restrict__ images, int n,
                                                                    const int* __restrict__ segments, int nseg,
@@ -585,8 +589,8 @@ __global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(const uint8_t
     }
     const long chunk = ok ? js_chunk_bytes(end - begin, chunk_bytes) : chunk_bytes;
     const int S = ok ? js_chunks(end - begin, chunk_bytes) : 1;
-    const long row0 = begin / chunk_bytes + s;
-    ok = ok && S <= LANES && row0 >= 0 && row0 + S <= nrows;
+    const long row0 = js_row0<STRIDED>(begin, chunk_bytes, s, S, nrows);
+    ok = ok && S <= LANES && row0 >= 0;
     if (!ok) {                                                   // the same for every lane of the workgroup
         if (tid == 0) seg_status[s] = 2;
         return;
@@ -907,13 +911,13 @@ extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int c
     int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
     int* rows = (int*)((uint8_t*)a->scratch + front);
     if (most <= 64)
-        hipLaunchKernelGGL(jpeg_entropy_split_kernel<64>, dim3((unsigned)a->nseg), dim3(64), 0, a->stream, src, a->nbytes,
-                           a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status, rows, nrows,
-                           chunk_bytes);
-    else
-        hipLaunchKernelGGL(jpeg_entropy_split_kernel<JS_LANES>, dim3((unsigned)a->nseg), dim3(JS_LANES), 0, a->stream, src,
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<64, false>), dim3((unsigned)a->nseg), dim3(64), 0, a->stream, src,
                            a->nbytes, a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status, rows,
                            nrows, chunk_bytes);
+    else
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<JS_LANES, false>), dim3((unsigned)a->nseg), dim3(JS_LANES), 0, a->stream,
+                           src, a->nbytes, a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status,
+                           rows, nrows, chunk_bytes);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,
@@ -934,15 +938,16 @@ extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int c
 namespace {
 
 // One workgroup per place j of the index: its images row, its seg_max segment rows and its word behind the segment
-// statuses (jb_plan_image says what that word is for).
+// statuses (jb_plan_image says what that word is for).  seg_bytes_max: the longest segment a place may have, which the split
+// entries name (their state rows are reserved for it); -1: no limit.
 __global__ __launch_bounds__(64) void jpeg_bank_plan_kernel(const int* __restrict__ bank_images, int n,
                                                             const int* __restrict__ bank_segments, int bank_nseg,
                                                             const int* __restrict__ index, int m, int seg_max, int block_stride,
                                                             int Hc, int Wc, int* __restrict__ images, int* __restrict__ segments,
-                                                            int* __restrict__ place_status) {
+                                                            int* __restrict__ place_status, int seg_bytes_max) {
     const int j = blockIdx.x, tid = threadIdx.x;
     const int idx = index[j];
-    const int st = jb_plan_status(bank_images, n, bank_nseg, idx, seg_max, block_stride, Hc, Wc);
+    const int st = jb_plan_status(bank_images, n, bank_segments, bank_nseg, idx, seg_max, block_stride, Hc, Wc, seg_bytes_max);
     if (tid == 0) {
         int row[JB_IMAGE_INTS];
         jb_plan_image(bank_images, idx, st, j, m, seg_max, block_stride, row);
@@ -1093,11 +1098,69 @@ extern "C" int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int
     int* images = (int*)((uint8_t*)a->scratch + tables);
     int* segments = images + (long)m * JD_IMAGE_INTS;
     hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
-                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg);
+                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg, -1);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes, images, m,
                        segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(blocks / JP_BLOCKS)), dim3(256), 0, a->stream, coef, images, m, a->qtabs,
+                       a->nq, seg_status, (int)words, planes, a->sizes, a->status);
+    rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, images, planes, out, npix, a->Hc,
+                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
+// istvt_jpeg_decode_indexed_u8 with the split entropy kernel behind the plan, for a bank of files whose restart intervals are
+// long (DESIGN.md "JPEG bank, split"): four launches, the same checks on scalars alone, the same bytes out.  A workgroup per
+// planned segment row, m * seg_max of them; segment s keeps its state rows at [s * chunk_rows, (s + 1) * chunk_rows) behind the
+// layout above, from the next multiple of 16 bytes, so the table's size comes from m alone and not from where the drawn
+// files lie in the bank.  chunk_rows >= the chunks of any segment of up to seg_bytes_max bytes (the bank knows both); the plan
+// turns a place with a longer segment into status 5, and the kernel refuses more than chunk_rows chunks by itself.
+extern "C" int istvt_jpeg_decode_indexed_split_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax,
+                                                  int Wmax, int chunk_bytes, int chunk_rows, int seg_bytes_max) {
+    if (!a || a->n <= 0 || a->nseg <= 0 || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || a->nbytes > 0x7fffffffL)
+        return ISTVT_ERR_SHAPE;
+    if (m <= 0 || seg_max < 1 || block_stride < JP_BLOCKS || block_stride % JP_BLOCKS != 0) return ISTVT_ERR_SHAPE;
+    if (chunk_bytes < 16 || chunk_rows < 1 || chunk_rows > JS_LANES) return ISTVT_ERR_SHAPE;
+    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->qtabs || !a->htabs || !a->scratch || !a->out ||
+        !a->sizes || !a->status)
+        return ISTVT_ERR_SHAPE;
+    if (Hmax < 1 || Wmax < 1 || a->Hc < Hmax || a->Wc < Wmax || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
+    const long blocks = (long)m * block_stride, nseg = (long)m * seg_max, words = nseg + m;
+    if (blocks > 0x7fffffffL / 64 || words > 0x7fffffffL / JD_SEGMENT_INTS) return ISTVT_ERR_SHAPE;
+    const long tables = (blocks * JD_BLOCK_BYTES + 4 * words + 15) & ~15L;
+    const long front = (tables + 4L * m * JD_IMAGE_INTS + 4 * nseg * JD_SEGMENT_INTS + 15) & ~15L;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < front + 4L * JS_STATE_INTS * nseg * chunk_rows)
+        return ISTVT_ERR_SHAPE;
+    const long npix = (long)m * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
+    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
+    const uint8_t* src = (const uint8_t*)a->bytes;
+    uint8_t* out = (uint8_t*)a->out;
+    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
+    const int* index = a->images_host;                           // this entry's reading of the field: on the device
+    short* coef = (short*)a->scratch;
+    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
+    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
+    int* images = (int*)((uint8_t*)a->scratch + tables);
+    int* segments = images + (long)m * JD_IMAGE_INTS;
+    int* rows = (int*)((uint8_t*)a->scratch + front);
+    hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
+                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg,
+                       seg_bytes_max < 0 ? -1 : seg_bytes_max);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    if (chunk_rows <= 64)
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<64, true>), dim3((unsigned)nseg), dim3(64), 0, a->stream, src, a->nbytes,
+                           images, m, segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status, rows, (long)chunk_rows,
+                           chunk_bytes);
+    else
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<JS_LANES, true>), dim3((unsigned)nseg), dim3(JS_LANES), 0, a->stream, src,
+                           a->nbytes, images, m, segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status, rows,
+                           (long)chunk_rows, chunk_bytes);
     rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(blocks / JP_BLOCKS)), dim3(256), 0, a->stream, coef, images, m, a->qtabs,

@@ -4,7 +4,7 @@
 //
 //   jb_markers        a lane's share of the marker scan of the device ingest: which of its 16 bytes start an RSTn pair
 //   jb_plan_status    what place j of an indexed decode is: decodable (0), an index outside the bank (4), a bank row that
-//                     holds no decodable file (5)
+//                     holds no decodable file (5); for the split decode also a row with a segment longer than the bank says (5)
 //   jb_plan_image     the batch-local images row of place j;  jb_plan_segment: row k of its seg_max segment rows
 //
 // clips.jpeg_scan_segments_host and clips.jpeg_bank_decode_host are the definitions on the host.
@@ -52,6 +52,21 @@ JE_HD int jb_plan_status(const int* bank_images, int n, int bank_nseg, int index
                     (long)mcux * mcuy * (lay.h * lay.v + lay.nc) <= block_stride && H >= 1 && W >= 1 && H <= Hc && W <= Wc &&
                     H <= mcuy * 8 * lay.v && W <= mcux * 8 * lay.h;
     return ok ? 0 : JB_STATUS_EMPTY;
+}
+
+// The same for the split decode of a bank (DESIGN.md "JPEG bank, split"), whose state rows are reserved for segments of at
+// most seg_bytes_max bytes: a row with a longer segment is not decodable either, by the same rule -- the bound is the host's
+// number, and a device table that exceeds it is kept inside the scratch.  seg_bytes_max < 0: no limit, the function above.
+JE_HD int jb_plan_status(const int* bank_images, int n, const int* bank_segments, int bank_nseg, int index, int seg_max,
+                         int block_stride, int Hc, int Wc, int seg_bytes_max) {
+    const int st = jb_plan_status(bank_images, n, bank_nseg, index, seg_max, block_stride, Hc, Wc);
+    if (st != 0 || seg_bytes_max < 0) return st;
+    const int* b = bank_images + (long)index * JB_IMAGE_INTS;
+    for (int k = 0; k < b[JB_NSEG]; ++k) {                       // 1 <= segments <= seg_max, all inside the table: checked above
+        const int* s = bank_segments + ((long)b[JB_SEG0] + k) * JB_SEGMENT_INTS;
+        if ((long)s[2] - s[1] > seg_bytes_max) return JB_STATUS_EMPTY;
+    }
+    return 0;
 }
 
 // The images row of place j of m.  Decodable: the bank's row with the first block, first IDCT workgroup and first segment of

@@ -62,6 +62,20 @@ JE_HD int js_chunks(long length, int chunk_bytes) {
     return n < 1 ? 1 : (int)n;
 }
 
+// Where the S state rows of segment s, whose bytes start at `begin`, lie in the table behind the statuses -> its first
+// row, or -1 where they do not fit.  Two addressings:
+//   by byte offset (STRIDED = false)  row begin / chunk_bytes + s of a table of `rows` rows.  Segments lie in order in the
+//       bytes and a segment has at most length / chunk_bytes + 1 chunks, so the rows of two segments never meet and the
+//       table of a call over nbytes has nbytes / chunk_bytes + nseg rows: the batch call (istvt_jpeg_decode_split_u8).
+//   per segment (STRIDED = true)  `rows` is the row stride R, and segment s owns rows [s * R, (s + 1) * R) of a table of
+//       nseg * R rows whatever its bytes' place: the bank's calls, whose bytes are a whole set but whose segments are the few
+//       drawn.  A segment of more than R chunks does not fit.
+template <bool STRIDED> JE_HD long js_row0(long begin, int chunk_bytes, int s, int S, long rows) {
+    if (STRIDED) return s >= 0 && S >= 1 && S <= rows ? (long)s * rows : -1;
+    const long row0 = begin / chunk_bytes + s;
+    return row0 >= 0 && row0 + S <= rows ? row0 : -1;
+}
+
 JE_HD bool js_same(const JsState& a, const JsState& b) { return a.pos == b.pos && a.bit == b.bit && a.blk == b.blk && a.k == b.k; }
 
 // the byte at p (FF 00 is the byte FF, zeros past the end) and p moved behind it

@@ -505,9 +505,16 @@ def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], b
         if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
                 or sizes.dtype != torch.int32 or tuple(sizes.shape) != (m, 2)
                 or status.dtype != torch.int32 or tuple(status.shape) != (m,)):
-            raise RuntimeError('%s: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes '
-                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (what, need, m, m, device))
+            layout = '' if bank.split is None else ' for the split layout (bank.split = %d: %d state rows per segment)' \
+                % (bank.split, bank.chunk_rows)
+            raise RuntimeError('%s: buffers = (uint8 scratch of %d bytes%s, 16-byte aligned; int32 sizes '
+                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (what, need, layout, m, m, device))
     return dev, Hc, Wc, out, scratch, sizes, status
+
+
+def _bank_split_scalars(bank):
+    """chunk_bytes, chunk_rows, seg_bytes_max as the split entries of a bank take them; -1: no limit on a segment's length"""
+    return bank.split, bank.chunk_rows, -1 if bank.seg_bytes_max is None else min(int(bank.seg_bytes_max), 2 ** 31 - 1)
 
 
 def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = None, buffers=None, split=None):
@@ -519,15 +526,18 @@ def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = Non
     data is part of the call, nothing synchronises, and the call can be captured in a graph with `out` and `buffers` -- or
     a host tensor or list, which is uploaded.  int64 is narrowed on the device.  The bank is uploaded at the first call
     (bank.on).  canvas = (Hc, Wc) defaults to the bank's largest H and W, whatever is drawn.  buffers = (scratch uint8 of
-    clips.jpeg_bank_scratch_bytes(bank, m) bytes and 16-byte aligned, sizes, status).  split= is refused: the split kernel's
-    state rows are laid out over the whole byte range of a call, which for a bank is the whole set."""
+    clips.jpeg_bank_scratch_bytes(bank, m) bytes and 16-byte aligned, sizes, status).  How the intervals are decoded is the
+    bank's property: with bank.split set (clips.jpeg_bank(files, split=), bank.with_split) the split entropy kernel runs, one
+    lane per chunk with its state rows at a stride per drawn segment, for files without restart markers; the same bytes come
+    out, and the scratch is larger.  The call's own split= is refused: the chunk size fixes the scratch layout and the
+    workgroup size, which must not change from call to call."""
     if not isinstance(bank, clips.JpegBank):
         raise TypeError('jpeg_decode_indexed_u8 expects a clips.JpegBank (clips.jpeg_bank, clips.JpegBank.from_encoded), got %s'
                         % type(bank).__name__)
     if split is not None:
         raise ValueError('jpeg_decode_indexed_u8: split= is not available for a bank (the state rows of the split kernel are '
-                         'addressed over the whole byte range, which here is the whole set): long intervals decode with one '
-                         'lane each; pass such files to jpeg_decode_u8(split=)')
+                         'addressed over the whole byte range, which here is the whole set): the split is a property of the '
+                         'bank, clips.jpeg_bank(files, split=) or bank.with_split(split)')
     index = clips.check_bank_index(index, 'jpeg_decode_indexed_u8')
     if not torch.cuda.is_available():
         raise RuntimeError('istvt_amd: jpeg_decode_indexed_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
@@ -544,6 +554,12 @@ def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = Non
         segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
         scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
         status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
+    if bank.split is not None:
+        with prof('jpeg_decode_indexed_split_u8', 2 * 192 * m * bank.block_stride + out.numel()):
+            _lib.check(_lib.lib().istvt_jpeg_decode_indexed_split_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
+                                                                     bank.Wmax, *_bank_split_scalars(bank)),
+                       'istvt_jpeg_decode_indexed_split_u8')
+        return out, sizes, status
     with prof('jpeg_decode_indexed_u8', 2 * 192 * m * bank.block_stride + out.numel()):   # + the bytes drawn, known on the device
         _lib.check(_lib.lib().istvt_jpeg_decode_indexed_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
                                                            bank.Wmax), 'istvt_jpeg_decode_indexed_u8')
@@ -579,7 +595,8 @@ def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, 
     """batch_draw(plan) and jpeg_decode_indexed_u8(bank, the index just drawn) as one call of five launches -> (frames, sizes,
     status, draw): frames uint8 [B*T, Hc, Wc, 3], sizes and status as the indexed decode hands them back, draw as batch_draw
     does.  The plan was built for this bank (as many places) and lives on its device.  canvas, out and buffers are
-    jpeg_decode_indexed_u8's, for m = B * T; with out and buffers the call can be captured in a graph."""
+    jpeg_decode_indexed_u8's, for m = B * T; with out and buffers the call can be captured in a graph.  A bank with a split
+    decodes through the split entropy kernel, as there."""
     if not isinstance(bank, clips.JpegBank):
         raise TypeError('jpeg_decode_drawn_u8 expects a clips.JpegBank, got %s' % type(bank).__name__)
     plan = _drawn_plan('jpeg_decode_drawn_u8', plan)
@@ -594,6 +611,12 @@ def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, 
         segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
         scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
         status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
+    if bank.split is not None:
+        with prof('jpeg_decode_drawn_split_u8', 2 * 192 * m * bank.block_stride + out.numel()):
+            _lib.check(_lib.lib().istvt_jpeg_decode_drawn_split_u8(ctypes.byref(args), plan.B, plan.T, plan.block.numel(), bank.seg_max,
+                                                                   bank.block_stride, bank.Hmax, bank.Wmax,
+                                                                   *_bank_split_scalars(bank)), 'istvt_jpeg_decode_drawn_split_u8')
+        return out, sizes, status, plan.draw
     with prof('jpeg_decode_drawn_u8', 2 * 192 * m * bank.block_stride + out.numel()):
         _lib.check(_lib.lib().istvt_jpeg_decode_drawn_u8(ctypes.byref(args), plan.B, plan.T, plan.block.numel(), bank.seg_max,
                                                          bank.block_stride, bank.Hmax, bank.Wmax), 'istvt_jpeg_decode_drawn_u8')
@@ -631,14 +654,18 @@ def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
 _JPEG_STD_HTABS: dict = {}        # (device, tables) -> the Annex K.3 Huffman tables in decode form on the device
 
 
-def jpeg_bank_ingest(jf, H=None, W=None, layout=None, restart_interval=None) -> 'clips.JpegBank':
+def jpeg_bank_ingest(jf, H=None, W=None, layout=None, restart_interval=None, seg_bytes_max=None) -> 'clips.JpegBank':
     """clips.JpegBank.from_encoded: the encoder's result -> a bank over the same bytes, where they lie.  What the host knows
     without waiting -- the number of files, the geometry they share, the header's length, seg_max = ceil(MCUs / restart
     interval), the Annex K.3 Huffman tables -- it fills in; istvt_jpeg_bank_ingest reads the rest on the device: every
     file's two quantisation tables and where its restart intervals lie.  A file the encoder did not finish (a status that is
-    not 0) becomes an empty place.  Two launches; no files(), no readback, no synchronisation."""
+    not 0) becomes an empty place.  Two launches; no files(), no readback, no synchronisation.  seg_bytes_max: the caller's
+    bound on a restart interval's bytes, kept as bank.seg_bytes_max (the lengths are not read here)."""
     if not isinstance(jf, clips.JpegFiles):
         raise TypeError('JpegBank.from_encoded expects a clips.JpegFiles, got %s' % type(jf).__name__)
+    if seg_bytes_max is not None and (isinstance(seg_bytes_max, bool) or not isinstance(seg_bytes_max, int) or seg_bytes_max < 1):
+        raise ValueError('JpegBank.from_encoded: seg_bytes_max is None or a positive int (bytes of the longest restart interval), '
+                         'got %r' % (seg_bytes_max,))
     g = jf.geometry
     if g is not None and g.optimize:
         raise ValueError('JpegBank.from_encoded: files with optimised Huffman tables (optimize=True) carry their own tables behind a '
@@ -681,7 +708,8 @@ def jpeg_bank_ingest(jf, H=None, W=None, layout=None, restart_interval=None) -> 
     bank = clips.JpegBank(data=None, images=None, segments=None, qtabs=None, htabs=None, nbytes=capacity, sizes=[(H, W)] * n, n=n,
                           nseg=n * seg_max, nq=2 * n, nh=2 if grey else 4, blocks=n * nb,
                           groups=n * -(-nb // clips.JPEG_IDCT_BLOCKS), seg_max=seg_max,
-                          block_stride=-(-nb // clips.JPEG_IDCT_BLOCKS) * clips.JPEG_IDCT_BLOCKS, Hmax=H, Wmax=W, device=device)
+                          block_stride=-(-nb // clips.JPEG_IDCT_BLOCKS) * clips.JPEG_IDCT_BLOCKS, Hmax=H, Wmax=W, device=device,
+                          seg_bytes_max=seg_bytes_max)
     bank._on[str(device)] = SimpleNamespace(data=jf.data, images=tables[at + 128 * n:].view(n, clips.JPEG_IMAGE_INTS),
                                             segments=tables[:at].view(n * seg_max, 5),
                                             qtabs=tables[at:at + 128 * n].view(2 * n, 64), htabs=_JPEG_STD_HTABS[key])
@@ -696,7 +724,7 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
     and the scorers.  split: jpeg_decode_u8's, for files without restart markers.  layouts: jpeg_decode_u8's, for files that are
     not all 4:2:0 or 4:4:4.  files may be a clips.JpegBank with `index` (jpeg_decode_indexed_u8): the places the index names
     are decoded and cut; without `boxes` each is cut whole through boxes made from the decoder's sizes on the device, and a
-    place with status 4 or 5 comes out black."""
+    place with status 4 or 5 comes out black.  A bank brings its own split (bank.split); split= is refused for it."""
     if isinstance(files, clips.JpegBank):
         if index is None:
             raise ValueError('decode_frames: a clips.JpegBank is decoded through index=')

@@ -467,6 +467,28 @@ int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes)
  * canvas smaller than Hmax x Wmax, a scratch too small or misaligned, or an out that overlaps bytes; the bank's tables were
  * checked when it was built, and the plan kernel turns a row that does not fit the strides or the canvas into status 5. */
 int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax, int Wmax);
+/* JPEG bank, split: istvt_jpeg_decode_indexed_u8 for a bank whose files have long restart intervals (no markers at all, as
+ * cameras and most encoders write them).  Four launches: the plan, then the split entropy kernel of
+ * istvt_jpeg_decode_split_u8 on m * seg_max workgroups -- of 64 lanes where chunk_rows <= 64, else 256 -- then the IDCT and
+ * canvas kernels.  The same argument block, the same bytes in out, sizes and status.  The split is a property of the bank:
+ *   chunk_bytes    >= 16: an interval of `length` bytes is cut into chunks of max(chunk_bytes, ceil(length / 256)) bytes
+ *   chunk_rows     1..256: the state rows reserved per planned segment row, at least the chunks of any interval of up to
+ *                  seg_bytes_max bytes: min(256, max(1, ceil(seg_bytes_max / chunk_bytes))).  This is the second row addressing
+ *                  of the split kernel: planned segment s = j * seg_max + k (place j, its segment k) owns rows [s * chunk_rows,
+ *                  (s + 1) * chunk_rows), whatever the place of its bytes in the bank (the batch call addresses rows by byte
+ *                  offset over the call's bytes, which for a bank are the whole set).  An interval of more chunks than
+ *                  chunk_rows gets segment status 2 and nothing of it is written.
+ *   seg_bytes_max  the longest interval of the bank in bytes, as its builder knows it: the plan kernel turns a place whose
+ *                  file has a longer one into status 5, so a device table that differs from the host's number stays inside
+ *                  the scratch.  Negative: no limit (chunk_rows = 256 then holds any interval).
+ *   scratch        the layout of istvt_jpeg_decode_indexed_u8 in front, then from the next multiple of 16 bytes the state
+ *                  rows int32 [m * seg_max * chunk_rows][8], a row as istvt_jpeg_decode_split_u8 describes it with byte
+ *                  indices into the bank.  Rows behind an interval's chunks are not written.  clips.jpeg_bank_scratch_bytes
+ *                  has the sum.
+ * Checks on scalars alone, -3 as above and for chunk_bytes < 16 or chunk_rows outside 1..256.  No synchronisation, no
+ * allocation, no global state. */
+int istvt_jpeg_decode_indexed_split_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax, int Wmax,
+                                       int chunk_bytes, int chunk_rows, int seg_bytes_max);
 /* Batch draw: which B clips of T frames a training step takes from a bank and how each is augmented, drawn on the device as a
  * pure function of (seed, step); the bits of clips.batch_draw_host.  The plan, the step counter and the drawn tables live in
  * one int32 tensor on the device, the draw block of block_ints ints (csrc/batch_draw.h names the words):
@@ -491,6 +513,10 @@ int istvt_batch_draw(const istvt_jpeg_decode_args* a, int B, int T, int block_in
  * and 5 are what they were; a refused block leaves its index as it was, which the plan kernel checks like any other. */
 int istvt_jpeg_decode_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max, int block_stride,
                                int Hmax, int Wmax);
+/* The draw followed by istvt_jpeg_decode_indexed_split_u8 with m = B * T on the index it wrote: five launches.  chunk_bytes,
+ * chunk_rows and seg_bytes_max are that entry's, everything else is istvt_jpeg_decode_drawn_u8's. */
+int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max, int block_stride,
+                                     int Hmax, int Wmax, int chunk_bytes, int chunk_rows, int seg_bytes_max);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with

@@ -15,7 +15,13 @@ For each: the host's wall time until the call has returned (the stream drained b
 spends per batch), and the device time between two events around it.  The draw kernel alone is timed as a captured graph of
 --chain launches of ops.batch_draw, replayed: device time per launch, the gaps between graph nodes included; its kernel time
 without them is rocprofv3's (`rocprofv3 --kernel-trace --stats -d DIR -- python tools/batch_draw_bench.py --reps 3`).
-Before anything is timed the draw side's bytes are compared with the existing calls on clips.batch_draw_host's tables."""
+Before anything is timed the draw side's bytes are compared with the existing calls on clips.batch_draw_host's tables.
+
+    python tools/batch_draw_bench.py --restartless [...]
+
+instead (DESIGN.md "JPEG bank, split"): the same bank from files WITHOUT restart markers, and ops.draw_clips on it with
+with_split(128) and with with_split(None), eager and as replayed graphs, in alternation; the two give the same bytes, which
+is checked at two steps first."""
 import argparse
 import json
 import os
@@ -60,6 +66,65 @@ def measure(fn):
     return host, e0.elapsed_time(e1)
 
 
+def restartless_main(a):
+    """--restartless: draw_clips on a bank of restart-less files, with and without the bank's split"""
+    B, T, S, N = a.clips, a.frames, a.size, a.bank_files
+    dev = torch.device('cuda', torch.cuda.current_device())
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)]).to(dev)
+    headers = [clips.jpeg_parse(f) for f in ops.jpeg_encode_u8(src, 90, '420', 0).files()]
+    plain = clips.jpeg_bank([headers[i % DISTINCT] for i in range(N)])
+    split = plain.with_split(clips.JPEG_SPLIT_DEFAULT)
+    plain.on(dev)
+    V = N // VIDEO_FRAMES
+    videos = torch.tensor([[v * VIDEO_FRAMES, VIDEO_FRAMES, v & 1] for v in range(V)], dtype=torch.int32)
+    banks = {'one_lane': plain, 'split': split}
+    plans = {k: clips.BatchPlan(plain, videos, T=T, B=B, seed=2023).on(dev) for k in banks}
+    outs = {k: torch.empty((B, T, S, S, 3), dtype=torch.uint8, device=dev) for k in banks}
+    for step in (0, 1):                                             # the bytes first
+        got = {k: ops.draw_clips(banks[k], plans[k], S, out=outs[k]) for k in banks}
+        clips.check_jpeg_bank_status(got['split'][3])
+        if not all(torch.equal(x, y) for x, y in zip(got['split'], got['one_lane'])):
+            raise SystemExit('step %d: draw_clips on the split bank is not draw_clips on the bank without a split' % step)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for k in banks:
+            ops.draw_clips(banks[k], plans[k], S, out=outs[k])
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graphs = {}
+    for k in banks:
+        graphs[k] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[k], capture_error_mode='thread_local'):
+            ops.draw_clips(banks[k], plans[k], S, out=outs[k])
+    torch.cuda.synchronize()
+    sides = [(k + '_eager', (lambda k=k: ops.draw_clips(banks[k], plans[k], S, out=outs[k]))) for k in banks]
+    sides += [(k + '_graph', graphs[k].replay) for k in banks]
+    times = {name: ([], []) for name, _ in sides}
+    for r in range(a.warmup + a.reps):
+        for name, fn in sides[::1 if r % 2 == 0 else -1]:
+            host, device = measure(fn)
+            if r >= a.warmup:
+                times[name][0].append(host)
+                times[name][1].append(device)
+    res = {'clips': B, 'frames': T, 'size': S, 'bank_files': N, 'chunk_bytes': split.split, 'chunk_rows': split.chunk_rows,
+           'seg_bytes_max': split.seg_bytes_max}
+    lines = ['batch draw, restart-less bank: %d clips of %d frames at %d x %d from %d files, longest scan %d bytes, split %d with %d '
+             'state rows per segment' % (B, T, S, S, N, split.seg_bytes_max, split.split, split.chunk_rows)]
+    for name, _ in sides:
+        res[name] = {'host': stats(times[name][0]), 'device': stats(times[name][1])}
+        h, d = res[name]['host'], res[name]['device']
+        lines.append('  %-18s host %.3f ms (%.3f-%.3f) | device %.3f ms (%.3f-%.3f)'
+                     % (name, h['median_ms'], h['min_ms'], h['max_ms'], d['median_ms'], d['min_ms'], d['max_ms']))
+    print('\n'.join(lines), flush=True)
+    line = json.dumps({'batch_draw_restartless_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--clips', type=int, default=32)
@@ -70,9 +135,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--chain', type=int, default=200)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--restartless', action='store_true')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('batch_draw_bench.py measures on a GPU; none is visible')
+    if a.restartless:
+        return restartless_main(a)
     B, T, S, N = a.clips, a.frames, a.size, a.bank_files
     dev = torch.device('cuda', torch.cuda.current_device())
     src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)]).to(dev)

@@ -34,6 +34,12 @@ upload   the compressed batch (scan bytes and tables) against the decoded clip (
          stream drained; (b) and (c) alternate.  Then the ingest: clips.JpegBank.from_encoded on --frames files of
          ops.jpeg_encode_u8 against files() + clips.jpeg_batch + upload.  The plan kernel's own time comes from `rocprofv3
          --kernel-trace --stats` on a run with --reps 3.
+--bank --split  (DESIGN.md "JPEG bank, split") the bank of files WITHOUT restart markers, at quality 75 and 90, the same
+         --bank-files and --frames, through a device index with the caller's buffers: (a) the bank with split=128
+         (clips.JPEG_SPLIT_DEFAULT), (b) the same bank through with_split(None), one lane per file, which is the code of a
+         bank before it had a split, (c) ops.jpeg_decode_u8 on a prepacked JpegBatch of the drawn files with split=128,
+         checked=True and the caller's buffers.  The three give the same frames, which is checked first; then they are timed
+         by events in alternation, each first in turn.
 """
 import argparse
 import ctypes
@@ -334,6 +340,73 @@ def bank_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def bank_split_main(a):
+    """--bank --split: a bank of restart-less files with and without its split, beside the split call on a prepacked batch"""
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_decode_bench.py measures on a GPU; none is visible')
+    n, S, N = a.frames, a.size, a.bank_files
+    chunk = clips.JPEG_SPLIT_DEFAULT
+    dev = torch.device('cuda', torch.cuda.current_device())
+    torch.zeros(1, device=dev)
+    lines, res = [], {}
+    outs = [torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) for _ in range(3)]
+
+    def small():
+        return (torch.empty((n, 2), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+    for q in QUALITIES:
+        files = encoded(a, q, 0)
+        headers = [clips.jpeg_parse(f) for f in files]
+        bank = clips.jpeg_bank([headers[i % DISTINCT] for i in range(N)], split=chunk)
+        plain = bank.with_split(None)
+        bank.on(dev)
+        g = torch.Generator().manual_seed(q)
+        draw = torch.randint(0, N, (n,), generator=g)
+        index = draw.to(torch.int32).to(dev)
+        batch = clips.jpeg_batch([headers[i % DISTINCT] for i in draw.tolist()])
+        need = {'a_bank_split': clips.jpeg_bank_scratch_bytes(bank, n), 'b_bank_one_lane': clips.jpeg_bank_scratch_bytes(plain, n),
+                'c_batch_split': clips.jpeg_split_plan(batch, chunk).scratch_bytes}
+        bufs = {k: (torch.empty((v,), dtype=torch.uint8, device=dev),) + small() for k, v in need.items()}
+        calls = {'a_bank_split': lambda: ops.jpeg_decode_indexed_u8(bank, index, out=outs[0], buffers=bufs['a_bank_split']),
+                 'b_bank_one_lane': lambda: ops.jpeg_decode_indexed_u8(plain, index, out=outs[1], buffers=bufs['b_bank_one_lane']),
+                 'c_batch_split': lambda: ops.jpeg_decode_u8(batch, out=outs[2], checked=True, buffers=bufs['c_batch_split'],
+                                                             split=chunk)}
+        first = {k: fn() for k, fn in calls.items()}
+        clips.check_jpeg_bank_status(first['a_bank_split'][2])
+        clips.check_jpeg_bank_status(first['b_bank_one_lane'][2])
+        clips.check_jpeg_status(first['c_batch_split'][2])
+        if not (torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[2])):
+            raise SystemExit('q=%d: the three decodes of the same draw differ' % q)
+        names = list(calls)
+        times = {k: [] for k in names}
+        for r in range(a.warmup + a.reps):                        # in alternation, each first in turn
+            for k in names[r % 3:] + names[:r % 3]:
+                t = event_ms(calls[k])
+                if r >= a.warmup:
+                    times[k].append(t)
+        st = {k: stats(v) for k, v in times.items()}
+        res['q%d' % q] = dict(st, bank_files=N, frames=n, size=S, chunk_bytes=chunk, chunk_rows=bank.chunk_rows,
+                              seg_bytes_max=bank.seg_bytes_max, bank_scan_bytes=bank.nbytes, drawn_scan_bytes=batch.nbytes,
+                              scratch_bytes=need)
+        say(lines, 'bank, split q=%d: %d of %d restart-less files of %d x %d per call, bank scans %.2f MB, drawn %.2f MB, longest scan '
+            '%d bytes, chunk %d, %d state rows per segment' % (q, n, N, S, S, bank.nbytes * 1e-6, batch.nbytes * 1e-6,
+                                                               bank.seg_bytes_max, chunk, bank.chunk_rows))
+        for name, key in (('(a) bank with split=%d, device index' % chunk, 'a_bank_split'),
+                          ('(b) the same bank, with_split(None)', 'b_bank_one_lane'),
+                          ('(c) prepacked JpegBatch, split=%d, checked' % chunk, 'c_batch_split')):
+            say(lines, '  %-44s %.3f ms (%.3f-%.3f), scratch %.2f MB' % (name, st[key]['median_ms'], st[key]['min_ms'],
+                                                                         st[key]['max_ms'], need[key] * 1e-6))
+        c = st['c_batch_split']
+        say(lines, '  (a) - (c) = %+.3f ms; (c)\'s own spread is %.3f ms; (b) / (a) = %.2f x'
+            % (st['a_bank_split']['median_ms'] - c['median_ms'], c['max_ms'] - c['min_ms'],
+               st['b_bank_one_lane']['median_ms'] / st['a_bank_split']['median_ms']))
+    line = json.dumps({'jpeg_bank_split_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--bank', action='store_true')
@@ -352,7 +425,7 @@ def main():
     if a.layouts:
         return layouts_main(a)
     if a.bank:
-        return bank_main(a)
+        return bank_split_main(a) if a.split else bank_main(a)
     row = -(-a.size // 16)                                        # MCUs of one MCU row at 4:2:0
     configs = [(q, ri) for q in QUALITIES for ri in (0, row)]
     longer = [(QUALITIES[0], k * row) for k in (2, 4, 8)] if a.split else []     # where between a row and a file it starts to pay
