@@ -26,7 +26,8 @@ def _target(p):
     """(buffer to accumulate this parameter's gradient into, value to return to autograd)"""
     if p is None:
         return None, None
-    if getattr(p, '_istvt_fused_grad', False) and p.grad is not None:
+    # (a frozen parameter keeps its view of the bucket: a Function that computes its gradient anyway must not add there)
+    if getattr(p, '_istvt_fused_grad', False) and p.grad is not None and p.requires_grad:
         return p.grad, None
     z = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
     return z, z
@@ -654,8 +655,14 @@ class TakeClsFn(Function):
         return dx.view(B, F * P, D), None, None, None
 
 
+seed_draws = [0]        # _new_seed() calls so far: a forward that moves it took a host value no captured graph can replay
+
+
 def _new_seed() -> int:
-    """63-bit Philox key from torch's default CPU generator (torch.manual_seed makes a run reproducible)"""
+    """63-bit Philox key from torch's default CPU generator (torch.manual_seed makes a run reproducible).  The key reaches
+    the dropout kernels as a launch argument: parallel.StepGraphs watches ``seed_draws`` across its launch-by-launch warm-up
+    forwards and never captures a configuration that draws."""
+    seed_draws[0] += 1
     return int(torch.empty((), dtype=torch.int64).random_()) & 0x7fffffffffffffff
 
 

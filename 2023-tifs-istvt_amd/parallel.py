@@ -12,6 +12,8 @@ parameters (block4..fc) that ``low_level_features`` never touches.
 """
 from __future__ import annotations
 
+import itertools
+import operator
 import os
 import weakref
 from typing import Iterable, List, Tuple
@@ -650,7 +652,73 @@ class _ReplayBackward(torch.autograd.Function):
 
 
 class _GraphEntry:
-    __slots__ = ('static_x', 'static_out', 'static_gout', 'g_fwd', 'g_bwd', 'keep', 'fingerprint', 'calls', 'pool')
+    __slots__ = ('static_x', 'static_out', 'static_gout', 'g_fwd', 'g_bwd', 'keep', 'fingerprint', 'live', 'calls', 'pool')
+
+
+def env_switches() -> tuple:
+    """The switches stem.py and functional.py read from the environment on EVERY call and that select launch sequences,
+    each as its reader sees it (so a value that means the default is the default): ISTVT_STEM_MATERIALISE_A2 (stem forward),
+    ISTVT_STEM_WGRAD_SIDE and ISTVT_STEM_PW_BWD_FUSED (stem backward), ISTVT_BGRAD_SIDE (functional._bgrad)."""
+    env = os.environ.get
+    return (env('ISTVT_STEM_MATERIALISE_A2', '0') == '1', env('ISTVT_STEM_WGRAD_SIDE', '1') != '0',
+            env('ISTVT_STEM_PW_BWD_FUSED', '1') != '0', env('ISTVT_BGRAD_SIDE', '0') == '1')
+
+
+_training_of = operator.attrgetter('training')
+
+
+class ModuleIndex:
+    """One walk over a model's module tree, kept: what StepGraphs reads on the host at every call -- the mode flags that
+    select launch sequences and the parameters the backward differentiates -- comes from these lists instead of a new
+    ``modules()`` / ``named_parameters()`` walk per step.  No device work: it is built and read on a host model as well.
+
+    ``stale()`` says whether the tree has changed since (a submodule replaced, added or removed, a parameter registered or
+    deleted); the owner then builds a new index.  A parameter REPLACED in its module, or frozen, needs no new index:
+    ``live()`` reads every slot and ``requires_grad`` anew."""
+
+    def __init__(self, model: torch.nn.Module):
+        keep = set('xcep.model.' + n for n in _stem.param_names())
+        mods, self.slots = [], []                       # slots: (the owner's _parameters dict, leaf name), in model order
+        for prefix, mod in model.named_modules():
+            mods.append(mod)
+            for leaf in mod._parameters:
+                name = prefix + '.' + leaf if prefix else leaf
+                if name.startswith('xcep.') and name not in keep:       # the never-executed Xception tail
+                    continue
+                self.slots.append((mod._parameters, leaf))
+        self._child_dicts = [mod._modules for mod in mods]
+        self._param_dicts = [mod._parameters for mod in mods]
+        self._children = self._walk()
+        self._param_count = sum(map(len, self._param_dicts))
+        # The model itself is held weakly: it owns the StepGraphs that owns this index, and a cycle through it would keep the
+        # graphs' memory pools and static-address mode alive until the garbage collector runs (submodules do not point back).
+        self._root = weakref.ref(model)
+        self.modules = mods[1:]
+        self.dropouts = [mod for mod in self.modules if isinstance(mod, torch.nn.Dropout)]
+        self.fp8 = [mod for mod in self.modules if hasattr(mod, 'attn_fp8')]
+        self.dre = [mod for mod in self.modules if hasattr(mod, 'dead_row_elimination')]
+
+    def _walk(self):
+        return list(itertools.chain.from_iterable(map(dict.values, self._child_dicts)))
+
+    def stale(self) -> bool:
+        # (list equality compares by identity first; nn.Module defines no __eq__)
+        return self._walk() != self._children or sum(map(len, self._param_dicts)) != self._param_count
+
+    def flags(self) -> tuple:
+        """every module's train / eval flag, every nn.Dropout's ``p > 0``, every attn_fp8 and dead_row_elimination flag"""
+        root = self._root()
+        return ((root.training, bool(getattr(root, 'attn_fp8', False)), bool(getattr(root, 'dead_row_elimination', False))),
+                tuple(map(_training_of, self.modules)), tuple([d.p > 0 for d in self.dropouts]),
+                tuple([bool(q.attn_fp8) for q in self.fp8]), tuple([bool(q.dead_row_elimination) for q in self.dre]))
+
+    def live(self) -> List[torch.nn.Parameter]:
+        """the parameters ``live_named_parameters(model)`` names, in its order, from the slots' current contents"""
+        out = [p for p in [params[leaf] for params, leaf in self.slots] if p is not None and p.requires_grad]
+        if len(set(map(id, out))) != len(out):          # a tied parameter once, as named_parameters() lists it
+            seen = set()
+            out = [p for p in out if not (id(p) in seen or seen.add(id(p)))]
+        return out
 
 
 class StepGraphs:
@@ -669,29 +737,43 @@ class StepGraphs:
         kernels write the bucket directly; a torch optimizer's ``zero_grad(set_to_none=True)`` breaks that and is detected);
       * no early all-reduce hook (N > 1 with the overlapped schedule stays launch-by-launch: the collective's handle is host state);
       * no per-kernel instrumentation (bench.py's profiled step);
-      * the switches that change the launch sequence (compute dtype, fp8 attention operands, dead-row elimination, the
-        weight-gradient stream / grouping) are part of an entry's key: a toggle captures a new entry, it never replays the old one;
+      * the forward draws no dropout seed: an applied ``nn.Dropout`` with ``p > 0`` in train mode takes a Philox key from
+        torch's CPU generator at every forward (functional._new_seed), a host value a graph would freeze.  Seen on the
+        warm-up forwards (functional.seed_draws); such a key is never captured, ``last_reason`` says so.  The same model in
+        eval mode, or with every ``p`` back at 0, is another key and is captured;
       * the previous graphed forward of this entry has had its backward (or was dropped): an entry owns ONE set of saved
         activations.
-    Addresses: parameters, gradients and every cached operand copy must stay where they were at capture; the cached copies are
-    refreshed in place (the static-address mode of weights.py), parameters and gradients are fingerprinted (data_ptr of each) and a change
-    drops the graphs and captures again.  The first ``warmup`` calls of an entry run launch by launch (they fill the operand
-    caches, the statistics arena, the side stream, the kernels' one-time attribute calls).  Every entry has a memory pool of
-    its own: replaying one never touches what another saved for its backward."""
+    Everything else the launch-by-launch path reads on the host at every call is in an entry's KEY (``key()``): the input's
+    shape / dtype / device, grad / no_grad, the compute dtype, the train / eval flag of EVERY module (the stem goes by
+    ``xcep``'s, each block and transformer module by its own: ``model.xcep.eval()`` for frozen BatchNorm statistics is
+    another launch sequence), every ``nn.Dropout``'s ``p > 0``, every ``attn_fp8`` and ``dead_row_elimination`` flag, the
+    weight-gradient stream / grouping, the GELU backward form, ISTVT_GEMM_TM and the four environment switches stem.py and
+    functional.py read per call (``env_switches()``).  A toggle captures a new entry, it never replays the old one; undoing
+    it finds the old entry again.  The flags are read in one pass over a cached module list (``ModuleIndex``); a changed
+    module tree (a new head) is noticed at the next call, drops the graphs and rebuilds the list.
+    The FINGERPRINT covers what an entry's graphs hold by address: the set of differentiated parameters -- recomputed at every
+    call, so ``requires_grad_()`` after a capture and a parameter swapped in are seen --, the identity and ``data_ptr`` of each and
+    of its gradient view.  A change (a new bucket, staged unfreezing) drops the graphs and captures again.  Every cached
+    operand copy is refreshed in place (the static-address mode of weights.py).  The first ``warmup`` calls of an entry (at
+    least one) run launch by launch (they fill the operand caches, the statistics arena, the side stream, the kernels'
+    one-time attribute calls).  Every entry has a memory pool of its own: replaying one never touches what another saved
+    for its backward."""
 
     def __init__(self, model: torch.nn.Module, forward_eager, warmup: int = 2, max_entries: int = 4):
         self.model = weakref.ref(model)
         # (a bound method of the model would make model -> StepGraphs -> model a cycle only the garbage collector breaks:
         #  the graphs' memory pools, and static-address mode, would outlive the model for as long as that takes)
         self._fwd = weakref.WeakMethod(forward_eager) if hasattr(forward_eager, '__self__') else (lambda f=forward_eager: f)
-        self.warmup = int(warmup)
+        # at least one launch-by-launch forward per key: it shows whether the configuration draws dropout seeds on the host
+        self.warmup = max(int(warmup), 1)
         self.max_entries = int(max_entries)
         self.entries = {}
         self.seen = {}
+        self.nocapture = {}             # entry key -> why this configuration is never captured (its forward draws seeds)
         self.pending = {}               # entry key -> weakref to the token of a graphed forward whose backward has not run
         self.anchor = None
-        self.live = None
-        self._probe = None
+        self.live = None                # the differentiated parameters as of the last call
+        self._tree = None               # ModuleIndex of the model, rebuilt when the module tree changes
         self.stats = {'captures': 0, 'replays': 0, 'eager': 0, 'recaptures': 0}
         self.last_reason = None
         from . import ops
@@ -705,28 +787,51 @@ class StepGraphs:
         self.last_reason = reason
         self.stats['eager'] += 1
 
+    # -- host side: the entry key, the live set, the fingerprint (no device work; they run on a host model too) ---------
+    def index(self) -> ModuleIndex:
+        """the model's ModuleIndex; a changed module tree (a swapped head) drops every graph and every warm-up count --
+        they belong to another model -- and builds a new one"""
+        idx = self._tree
+        if idx is None or idx.stale():
+            if idx is not None:
+                if self.entries:
+                    self.stats['recaptures'] += 1
+                self.drop()
+            idx = self._tree = ModuleIndex(self.model())
+        return idx
+
     def _config(self, m):
         from . import functional as Fn
         if m is None:
             return None
-        if self._probe is None:
-            fp8 = [mod for mod in m.modules() if hasattr(mod, 'attn_fp8')]
-            dre = [mod for mod in m.modules() if hasattr(mod, 'dead_row_elimination')]
-            self._probe = (fp8, dre)
-        fp8, dre = self._probe
-        return (str(getattr(m, 'compute_dtype', None)), tuple(bool(q.attn_fp8) for q in fp8[:1]) + tuple(bool(q.attn_fp8) for q in fp8[-1:]),
-                tuple(bool(q.dead_row_elimination) for q in dre), bool(Fn._overlap['on']), int(Fn._overlap['group']),
-                bool(Fn.GELU_SAVE_DERIV[0]), os.environ.get('ISTVT_GEMM_TM', ''))
+        return (str(getattr(m, 'compute_dtype', None)), self.index().flags(), env_switches(), bool(Fn._overlap['on']),
+                int(Fn._overlap['group']), bool(Fn.GELU_SAVE_DERIV[0]), os.environ.get('ISTVT_GEMM_TM', ''))
 
-    # -- preconditions -----------------------------------------------------------------------------------------------
-    def _live(self):
-        if self.live is None:
-            self.live = [p for _, p in live_named_parameters(self.model())]
+    def key(self, x, grads: bool):
+        """The key of the entry ``model(x)`` belongs to.  It names everything that selects a launch sequence: the input,
+        grad / no_grad, the compute dtype, EVERY module's train / eval flag (the stem and each block branch on their own),
+        every nn.Dropout's ``p > 0``, every attn_fp8 and dead_row_elimination flag, the weight-gradient stream / grouping and
+        the environment switches read per call.  A toggle after a capture is another key, never a replay of the old sequence;
+        undoing it finds the old entry again."""
+        m = self.model()
+        return (tuple(x.shape), x.dtype, x.device.index, self._config(m), bool(m is not None and m.training), bool(grads))
+
+    def live_parameters(self):
+        """the parameters the backward differentiates NOW: read at every call (requires_grad_() after a capture, a parameter
+        or submodule swapped in), in the order of live_named_parameters()"""
+        self.live = self.index().live()
         return self.live
 
-    def _fingerprint(self, grads: bool):
+    def _live(self):
+        return self.live if self.live is not None else self.live_parameters()
+
+    def _fingerprint(self, grads: bool, live=None):
+        """identity and address of every live parameter (and, with gradients, the address of its fused gradient view); None
+        when a live gradient is not a view of a fused bucket.  An entry keeps its parameters alive, so an identity in its
+        fingerprint cannot come back as another tensor's."""
         fp = []
-        for p in self._live():
+        for p in (self._live() if live is None else live):
+            fp.append(id(p))
             fp.append(p.data_ptr())
             if grads:
                 g = p.grad
@@ -756,38 +861,52 @@ class StepGraphs:
 
     # -- the call ----------------------------------------------------------------------------------------------------
     def __call__(self, x):
+        from . import functional as Fn
         from . import ops
-        m = self.model()
         grads = torch.is_grad_enabled()
-        # the key names everything that selects a launch sequence: the input, the mode, and the switches that change which
-        # kernels a forward / backward issues (a toggle after a capture must not replay the old sequence)
-        key = (tuple(x.shape), x.dtype, x.device.index, self._config(m), bool(m is not None and m.training), grads)
+        key = self.key(x, grads)
         reason = self.why_not(x, key)
-        fp = None
+        fp = live = None
         if reason is None:
-            fp = self._fingerprint(grads)
+            live = self.live_parameters()
+            fp = self._fingerprint(grads, live)
             if fp is None:
                 reason = 'a live gradient is not a fused-bucket view'
+        if reason is None:
+            reason = self.nocapture.get(key)
+        warming = False
         if reason is None:
             n = self.seen.get(key, 0)
             self.seen[key] = n + 1
             if n < self.warmup:
-                reason = 'warm-up'
+                reason, warming = 'warm-up', True
             elif key not in self.entries and len(self.entries) >= self.max_entries:
                 reason = 'more (shape, mode) entries than max_entries'
         if reason is not None:
             self.last_reason = reason
             self.stats['eager'] += 1
-            return self.forward_eager(x)
+            if not warming:
+                return self.forward_eager(x)
+            # A forward that draws a dropout seed (functional._new_seed: a host integer from torch's CPU generator, handed to
+            # the kernel by value) would replay the masks of its capture for ever.  The warm-up forwards run launch by launch
+            # anyway: if the draw counter moves across one, this key is never captured.  Nothing is captured and thrown away,
+            # and the generator sees exactly the draws of the launch-by-launch loop.
+            draws = Fn.seed_draws[0]
+            out = self.forward_eager(x)
+            if Fn.seed_draws[0] != draws:
+                self.nocapture[key] = self.last_reason = \
+                    'dropout is active: its seeds are drawn on the host at every forward (not captured)'
+            return out
         ent = self.entries.get(key)
         if ent is not None and ent.fingerprint != fp:
-            # a parameter or gradient moved (a new bucket, load_state_dict into new storage, .to()): the captured pointers
-            # are dead -- drop every graph and start over
+            # a parameter or gradient moved (a new bucket, load_state_dict into new storage, .to()), or the set of
+            # differentiated parameters changed (requires_grad_(), a parameter swapped in): the captured pointers are dead,
+            # or the captured backward differentiates the wrong set -- drop every graph and start over
             self.drop()
             self.stats['recaptures'] += 1
             ent = None
         if ent is None:
-            ent = self._capture(x, key, fp, grads)
+            ent = self._capture(x, key, fp, grads, live)
         # operand copies the optimizer step (or a load_state_dict) made stale: in place, before the graph reads them
         ops.refresh_stale_operands()
         if ent.static_x.data_ptr() != x.data_ptr():
@@ -804,7 +923,7 @@ class StepGraphs:
         self.pending[key] = weakref.ref(token)
         return _ReplayBackward.apply(self.anchor, ent, token)
 
-    def _capture(self, x, key, fp, grads):
+    def _capture(self, x, key, fp, grads, live):
         from . import functional as Fn
         from . import ops
         from . import stem as stem_mod
@@ -815,6 +934,7 @@ class StepGraphs:
         ent = _GraphEntry()
         ent.calls = 0
         ent.fingerprint = fp
+        ent.live = live                 # the captured backward differentiates these; alive as long as the entry is
         ent.static_x = x.detach().clone()
         ent.static_gout = ent.g_bwd = None
         self.entries[key] = ent         # from here on ops.static_addresses() is true: every refresh is in place
@@ -855,10 +975,10 @@ class StepGraphs:
                     # default stream, and the engine's stream hand-over to them is illegal inside a capture -- it crashed
                     # the process); the kernels write the fused bucket themselves and the Functions return None for their
                     # parameters
-                    got = torch.autograd.grad(out, self._live(), grad_outputs=ent.static_gout, allow_unused=True)
+                    got = torch.autograd.grad(out, ent.live, grad_outputs=ent.static_gout, allow_unused=True)
                     # a Function that does hand a gradient tensor back is accumulated here, inside the capture, as
                     # AccumulateGrad would have done
-                    for p, g in zip(self._live(), got):
+                    for p, g in zip(ent.live, got):
                         if g is not None:
                             p.grad.add_(g)
                 del got
@@ -867,5 +987,6 @@ class StepGraphs:
         """forget every captured graph (each entry's pool is released once the last reference is gone)"""
         self.entries.clear()
         self.seen.clear()
+        self.nocapture.clear()
         self.pending.clear()
         self.live = None

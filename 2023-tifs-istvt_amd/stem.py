@@ -445,9 +445,14 @@ class StemFn(Function):
 
         # A parameter registered with GradBucket(fuse_accumulate=True) receives its gradient straight in .grad (the
         # kernels accumulate) and autograd gets None for it: no zero fill, no add pass, no copy per parameter.
+        # A frozen parameter (requires_grad False, staged unfreezing) keeps its .grad view of the bucket: nothing may be
+        # added there -- its gradient goes to a fresh tensor that autograd drops, as for any input that needs none.
+        def fused(q):
+            return getattr(q, '_istvt_fused_grad', False) and q.grad is not None and q.requires_grad
+
         def tgt(n, shape):
             q = P[n]
-            if getattr(q, '_istvt_fused_grad', False) and q.grad is not None and q.grad.is_contiguous():
+            if fused(q) and q.grad.is_contiguous():
                 grads[n] = None
                 return q.grad.view(shape)
             return None
@@ -566,7 +571,7 @@ class StemFn(Function):
                 _lib.check(L.istvt_conv2_wgrad(du.data_ptr(), u1.data_ptr(), bn1.ptr(), slabs.data_ptr(), dW.data_ptr(),
                                                Fr, H1, H1, _stream()), 'istvt_conv2_wgrad')
                 return dW.view(64, 3, 3, 32).permute(0, 3, 1, 2)
-            if side_on and getattr(q2, '_istvt_fused_grad', False) and q2.grad is not None:
+            if side_on and fused(q2):
                 # nothing later reads it: beside the input gradient, on the side stream, added into .grad there
                 from . import functional as Fn
                 Fn.side_launch(du2.device, lambda: q2.grad.add_(conv2_wgrad()), keep=(du2, sv['u1'], sv['bn1']))
@@ -610,7 +615,7 @@ class StemFn(Function):
         # launch-by-launch step on the default stream is illegal -- parallel.StepGraphs).
         for n in ('conv1.weight', 'conv2.weight'):
             q = P[n]
-            if grads[n] is not None and getattr(q, '_istvt_fused_grad', False) and q.grad is not None:
+            if grads[n] is not None and fused(q):
                 q.grad.add_(grads[n].view(q.shape))
                 grads[n] = None
         out = [None if grads[n] is None else grads[n].view(P[n].shape) for n in param_names()]
