@@ -56,6 +56,11 @@ the shape bank of ``draw_shapes``, the probabilities as 32-bit thresholds, the s
 ``batch_draw_host`` (the definition of ops.batch_draw and ops.draw_clips, integers only: the file index, boxes, flips,
 qualities, perturbation rows and labels of a batch as a pure function of the seed and the step).  A step that reads no host
 data is ``u8, view, label, _ = ops.draw_clips(bank, plan, S)`` and ``model(u8, view=view, view_checked=True, crop=S)``.
+
+PNG files (DESIGN.md "PNG files") are the tenth, at the end of this file: ``png_parse`` (the chunks of a file, and every
+refusal), ``png_decode_host`` (the definition of ops.png_decode_u8: zlib's inflate, the five row filters, integers only),
+``png_encode_host`` (files for tests and users), ``png_batch`` (files packed for one launch) and ``check_png_status``.  Frames
+kept lossless on purpose run ``model(ops.decode_frames(clips.png_batch(files), S, boxes).view(B, T, S, S, 3), view=flips)``.
 """
 import math
 from fractions import Fraction
@@ -2984,3 +2989,440 @@ def batch_draw_host(plan: BatchPlan, step: int) -> SimpleNamespace:
                            quality=i32(quality[:, None].expand(B, T).reshape(-1)),
                            view=i32(torch.stack([torch.zeros_like(flip), torch.zeros_like(flip), flip], dim=1)),
                            perturb=i32(perturb), label=i32(vid[:, 2]), step=step)
+
+
+# ---- PNG files (DESIGN.md "PNG files") ---------------------------------------------------------------------------------------
+# png_parse (the chunks of a file, and every refusal), png_decode_host (the definition of ops.png_decode_u8, integers only:
+# zlib's inflate, or _png_inflate where zlib raises; the five row filters in numpy), png_encode_host (files for tests and
+# users), png_batch (files packed for one launch) and check_png_status.  _png_inflate is RFC 1951 step by step, in the order of
+# csrc/png_inflate.h: the specification the C++ decoder is compared against, and what decides a damaged stream's status.
+PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
+PNG_MAX_SIDE = 16384
+PNG_IMAGE_INTS = 8                          # a row of PngBatch.images: ISTVT_PNG_IMAGE_INTS of include/istvt_hip.h
+PNG_MAX_BYTES = 2 ** 31 - 4096              # the streams of a batch at the most: ISTVT_PNG_MAX_BYTES
+PNG_BPP = {0: 1, 2: 3, 6: 4}                # bytes per pixel of the colour types the decoder takes
+PNG_STATUS = {1: 'the stream ends early', 2: 'a reserved block type, or a stored block whose length and complement disagree',
+              3: 'code lengths that are over-subscribed or incomplete, or a code no table holds',
+              4: 'a distance beyond the bytes produced', 5: 'more, or fewer, bytes than H (1 + W bpp)',
+              6: 'a filter byte above 4'}
+_PNG_LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_PNG_LEXT = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+_PNG_DBASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
+              8193, 12289, 16385, 24577)
+_PNG_DEXT = (0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13)
+_PNG_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+
+
+class PngHeader:
+    """What png_parse reads from one file: H, W, colour_type (0 grey, 2 RGB, 6 RGBA), bpp (1, 3 or 4 bytes per pixel) and
+    data, the raw DEFLATE bytes of the joined IDAT chunks without the zlib header and the Adler-32."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def raw_bytes(self) -> int:
+        """the filtered rows: a filter byte and W bpp bytes per row"""
+        return self.H * (1 + self.W * self.bpp)
+
+
+def _png_refuse(text: str):
+    raise ValueError('png_parse: ' + text)
+
+
+def png_parse(data) -> PngHeader:
+    """The chunks of one PNG file (bytes): the signature, IHDR, IDAT (joined), IEND; ancillary chunks are skipped, and so is a
+    PLTE in a colour type 2 or 6 file (in a grey file it is refused); IDAT chunks follow one another, or the file is refused;
+    every chunk's CRC-32 is checked.  Accepted: bit depth 8, no interlace, colour type 0
+    (grey), 2 (RGB) or 6 (RGBA; the decoder drops alpha), sides of 1..16384, a zlib header of method 8, a window of at most
+    32 KiB and no preset dictionary.  Everything else is refused by name (ValueError, 'png_parse: ...')."""
+    import zlib
+    data = bytes(data)
+    if data[:8] != PNG_SIGNATURE:
+        _png_refuse('the file does not start with the PNG signature')
+    pos, ihdr, idat, ended, run = 8, None, [], False, False
+    while pos < len(data):
+        if pos + 12 > len(data):
+            _png_refuse('a chunk header at byte %d reaches past the end of the file' % pos)
+        length, kind = int.from_bytes(data[pos:pos + 4], 'big'), data[pos + 4:pos + 8]
+        if pos + 12 + length > len(data):
+            _png_refuse('chunk %s at byte %d reaches past the end of the file' % (kind.decode('latin-1'), pos))
+        body = data[pos + 8:pos + 8 + length]
+        if zlib.crc32(data[pos + 4:pos + 8 + length]) != int.from_bytes(data[pos + 8 + length:pos + 12 + length], 'big'):
+            _png_refuse('chunk %s at byte %d has a bad CRC-32' % (kind.decode('latin-1'), pos))
+        pos += 12 + length
+        if ihdr is None and kind != b'IHDR':
+            _png_refuse('the first chunk is %s, not IHDR' % kind.decode('latin-1'))
+        if kind == b'IHDR':
+            if ihdr is not None or length != 13:
+                _png_refuse('a second IHDR, or one that is not 13 bytes long')
+            ihdr = body
+            W, H = int.from_bytes(body[0:4], 'big'), int.from_bytes(body[4:8], 'big')
+            depth, ct, comp, flt, lace = body[8:13]
+            if ct not in (0, 2, 3, 4, 6) or depth not in (1, 2, 4, 8, 16):
+                _png_refuse('colour type %d with bit depth %d is not a PNG image type' % (ct, depth))
+            if depth == 16:
+                _png_refuse('16-bit samples are not decoded (bit depth 8 only)')
+            if depth < 8:
+                _png_refuse('%d-bit samples are not decoded (bit depth 8 only)' % depth)
+            if ct == 3:
+                _png_refuse('palette images (colour type 3) are not decoded')
+            if ct == 4:
+                _png_refuse('grey + alpha images (colour type 4) are not decoded')
+            if comp != 0 or flt != 0:
+                _png_refuse('compression method %d / filter method %d are not PNG' % (comp, flt))
+            if lace != 0:
+                _png_refuse('Adam7 interlaced files are not decoded')
+            if not (1 <= H <= PNG_MAX_SIDE and 1 <= W <= PNG_MAX_SIDE):
+                _png_refuse('sides of 1..%d, got %d x %d' % (PNG_MAX_SIDE, H, W))
+        elif kind == b'IDAT':
+            if idat and not run:
+                _png_refuse('IDAT chunks at byte %d that do not follow one another' % (pos - 12 - length))
+            idat.append(body)
+        elif kind == b'IEND':
+            ended = True
+            break
+        elif kind == b'PLTE':
+            if ct == 0:
+                _png_refuse('a PLTE chunk in a grey file (colour type 0)')
+        elif not kind[0] & 0x20:
+            _png_refuse('critical chunk %s is not known' % kind.decode('latin-1'))
+        run = kind == b'IDAT'
+    if ihdr is None:
+        _png_refuse('the file has no IHDR')
+    if not ended:
+        _png_refuse('the file has no IEND')
+    if not idat:
+        _png_refuse('the file has no IDAT')
+    z = b''.join(idat)
+    if len(z) < 6 or (z[0] & 15) != 8 or (z[0] >> 4) > 7 or (z[1] & 0x20) or ((z[0] << 8) | z[1]) % 31:
+        _png_refuse('a bad zlib header (method 8, a window of at most 32 KiB and no preset dictionary are taken)')
+    return PngHeader(H=H, W=W, colour_type=ct, bpp=PNG_BPP[ct], data=z[2:-4])
+
+
+class _PngBits:
+    """bits of a DEFLATE stream, least significant first"""
+
+    def __init__(self, data):
+        self.data, self.pos, self.buf, self.cnt = data, 0, 0, 0
+
+    def refill(self):
+        while self.cnt <= 32 and self.pos < len(self.data):
+            self.buf |= self.data[self.pos] << self.cnt
+            self.cnt += 8
+            self.pos += 1
+
+    def take(self, n):
+        v = self.buf & ((1 << n) - 1)
+        self.buf >>= n
+        self.cnt -= n
+        return v
+
+
+def _png_code(lens, single_ok=False):
+    """code lengths -> (limit[16], offset[16], symbols) of the canonical code, or None where the set is over-subscribed or
+    incomplete (but for the distance code of no symbol, or of one symbol of one bit)"""
+    count = [0] * 16
+    for v in lens:
+        count[v] += 1
+    left, used = 1, 0
+    for n in range(1, 16):
+        left = 2 * left - count[n]
+        if left < 0:
+            return None
+        used += count[n]
+    if left and not (single_ok and (used == 0 or (used == 1 and count[1] == 1))):
+        return None
+    limit, offset, code, index = [0] * 16, [0] * 16, 0, 0
+    for n in range(1, 16):
+        code <<= 1
+        offset[n] = index - code
+        code += count[n]
+        index += count[n]
+        limit[n] = code << (15 - n)
+    return limit, offset, sorted((i for i, v in enumerate(lens) if v), key=lambda i: (lens[i], i))
+
+
+def _png_symbol(bits: _PngBits, code):
+    """the next symbol, or -1 (the stream ends early) / -3 (no code); the peek is padded with zeros, as the device's is"""
+    limit, offset, syms = code
+    c15 = int('{:015b}'.format(bits.buf & 0x7fff)[::-1], 2)
+    for n in range(1, 16):
+        if c15 < limit[n]:
+            if n > bits.cnt:
+                return -1
+            bits.take(n)
+            return syms[offset[n] + (c15 >> (15 - n))]
+    return -3
+
+
+def _png_inflate(raw, expected: int):
+    """RFC 1951 on one raw stream whose output length is known -> (bytes, status 0..5 of PNG_STATUS); the first fault in stream
+    order decides, and a stored block checks its complement, then the room, then the bytes it has."""
+    bits, out = _PngBits(bytes(raw)), bytearray()
+    while True:
+        bits.refill()
+        if bits.cnt < 3:
+            return out, 1
+        last, kind = bits.take(1), bits.take(2)
+        if kind == 3:
+            return out, 2
+        if kind == 0:
+            bits.take(bits.cnt & 7)
+            bits.refill()
+            if bits.cnt < 32:
+                return out, 1
+            n, c = bits.take(16), bits.take(16)
+            if n ^ 0xffff != c:
+                return out, 2
+            if len(out) + n > expected:
+                return out, 5
+            if n > bits.cnt // 8 + len(bits.data) - bits.pos:
+                return out, 1
+            for _ in range(n):
+                bits.refill()
+                out.append(bits.take(8))
+        else:
+            if kind == 1:
+                lit, dist = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 32
+            else:
+                bits.refill()
+                if bits.cnt < 14:
+                    return out, 1
+                hlit, hdist, hclen = bits.take(5) + 257, bits.take(5) + 1, bits.take(4) + 4
+                if hlit > 286 or hdist > 30:
+                    return out, 3
+                cl = [0] * 19
+                for i in range(hclen):
+                    bits.refill()
+                    if bits.cnt < 3:
+                        return out, 1
+                    cl[_PNG_CL_ORDER[i]] = bits.take(3)
+                cl = _png_code(cl)
+                if cl is None:
+                    return out, 3
+                lens = []
+                while len(lens) < hlit + hdist:
+                    bits.refill()
+                    s = _png_symbol(bits, cl)
+                    if s < 0:
+                        return out, -s
+                    if s < 16:
+                        lens.append(s)
+                        continue
+                    if s == 16 and not lens:
+                        return out, 3
+                    need, base, val = {16: (2, 3, lens[-1] if lens else 0), 17: (3, 3, 0), 18: (7, 11, 0)}[s]
+                    if bits.cnt < need:
+                        return out, 1
+                    rep = base + bits.take(need)
+                    if len(lens) + rep > hlit + hdist:
+                        return out, 3
+                    lens += [val] * rep
+                lit, dist = lens[:hlit], lens[hlit:]
+                if lit[256] == 0:
+                    return out, 3
+            lit, dist = _png_code(lit), _png_code(dist, single_ok=True)
+            if lit is None or dist is None:
+                return out, 3
+            while True:
+                bits.refill()
+                s = _png_symbol(bits, lit)
+                if s < 0:
+                    return out, -s
+                if s < 256:
+                    if len(out) >= expected:
+                        return out, 5
+                    out.append(s)
+                    continue
+                if s == 256:
+                    break
+                if s > 285:
+                    return out, 3
+                if bits.cnt < _PNG_LEXT[s - 257]:
+                    return out, 1
+                L = _PNG_LBASE[s - 257] + bits.take(_PNG_LEXT[s - 257])
+                bits.refill()
+                d = _png_symbol(bits, dist)
+                if d < 0:
+                    return out, -d
+                if d > 29:
+                    return out, 3
+                if bits.cnt < _PNG_DEXT[d]:
+                    return out, 1
+                D = _PNG_DBASE[d] + bits.take(_PNG_DEXT[d])
+                if D > len(out):
+                    return out, 4
+                if len(out) + L > expected:
+                    return out, 5
+                for _ in range(L):
+                    out.append(out[-D])
+        if last:
+            break
+    return out, 0 if len(out) == expected else 5
+
+
+def _png_paeth(a, b, c):
+    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
+    return a if pa <= pb and pa <= pc else (b if pb <= pc else c)
+
+
+def _png_unfilter(rows, bpp: int):
+    """rows uint8 numpy (H, 1 + W bpp): the filter byte and the filtered bytes -> the reconstructed (H, W bpp), int arithmetic
+    mod 256 (PNG specification, 9.2)"""
+    import numpy as np
+    H, n = rows.shape[0], rows.shape[1] - 1
+    out = np.zeros((H, n), dtype=np.uint8)
+    zero = np.zeros(n, dtype=np.int64)
+    for y in range(H):
+        ft, x = int(rows[y, 0]), rows[y, 1:].astype(np.int64)
+        up = out[y - 1].astype(np.int64) if y else zero
+        if ft == 0:
+            cur = x
+        elif ft == 2:
+            cur = x + up
+        elif ft == 1:
+            cur = x.copy()
+            for i in range(bpp, n):
+                cur[i] = (cur[i] + cur[i - bpp]) & 255
+        else:
+            cur = x.copy()
+            for i in range(n):
+                a = int(cur[i - bpp]) if i >= bpp else 0
+                b = int(up[i])
+                c = int(up[i - bpp]) if i >= bpp else 0
+                cur[i] = (cur[i] + ((a + b) >> 1 if ft == 3 else _png_paeth(a, b, c))) & 255
+        out[y] = (cur & 255).astype(np.uint8)
+    return out
+
+
+def png_decode_host(data, return_status: bool = False):
+    """The definition of ops.png_decode_u8, integers only: one file (bytes, or a PngHeader) -> uint8 (H, W, 3), with
+    return_status=True (frame, status).  png_parse; the inflate; the row filters; grey replicated to three channels, alpha
+    dropped.  status: 0 fine, else PNG_STATUS, and the frame is all zeros.  The status is _png_inflate's, always: zlib is more
+    lenient than RFC 1951 in one place (it takes an incomplete literal/length set whose only code is one bit long, which the
+    decoders here refuse with status 3), so it never decides.  Where _png_inflate decodes a stream, zlib.decompress(raw, -15)
+    must give the same bytes, and this raises if it does not."""
+    import zlib
+
+    import numpy as np
+    hd = data if isinstance(data, PngHeader) else png_parse(data)
+    raw, status = _png_inflate(hd.data, hd.raw_bytes)
+    if status == 0:
+        z = zlib.decompressobj(-15)
+        if z.decompress(hd.data) != bytes(raw) or not z.eof:
+            raise RuntimeError('png_decode_host: zlib and _png_inflate disagree on a stream both decode')
+    rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(hd.H, -1) if status == 0 else None
+    if status == 0 and int(rows[:, 0].max()) > 4:
+        status = 6
+    if status:
+        out = torch.zeros((hd.H, hd.W, 3), dtype=torch.uint8)
+    else:
+        px = torch.from_numpy(_png_unfilter(rows, hd.bpp)).reshape(hd.H, hd.W, hd.bpp)
+        out = px.expand(hd.H, hd.W, 3).contiguous() if hd.bpp == 1 else px[:, :, :3].contiguous()
+    return (out, status) if return_status else out
+
+
+def png_encode_host(frame, filters=None, level: int = 6, strategy: int = 0, idat: Optional[int] = None) -> bytes:
+    """A PNG file of `frame`, uint8 (H, W) grey, (H, W, 3) RGB or (H, W, 4) RGBA (a tensor or an array): host only, for tests
+    and users.  filters: one filter type 0..4 per row (None: 0 on every row).  zlib.compressobj(level, DEFLATED, 15, 9,
+    strategy): level 0 writes stored blocks, strategy 4 (Z_FIXED) fixed ones.  idat=k splits the stream into IDAT chunks of k
+    bytes."""
+    import zlib
+
+    import numpy as np
+    px = np.ascontiguousarray(frame.numpy() if torch.is_tensor(frame) else frame)
+    if px.dtype != np.uint8 or px.ndim not in (2, 3) or (px.ndim == 3 and px.shape[2] not in (3, 4)) or 0 in px.shape:
+        raise ValueError('png_encode_host: a uint8 (H, W), (H, W, 3) or (H, W, 4) frame, got %s %s' % (px.dtype, px.shape))
+    H, W = px.shape[:2]
+    bpp = 1 if px.ndim == 2 else px.shape[2]
+    ct = {1: 0, 3: 2, 4: 6}[bpp]
+    filters = [0] * H if filters is None else [int(v) for v in filters]
+    if len(filters) != H or any(not 0 <= v <= 4 for v in filters):
+        raise ValueError('png_encode_host: filters holds one type 0..4 per row (%d rows)' % H)
+    cur = px.reshape(H, W * bpp).astype(np.int64)
+    a = np.concatenate([np.zeros((H, bpp), np.int64), cur[:, :-bpp]], axis=1) if W > 1 else np.zeros_like(cur)
+    b = np.concatenate([np.zeros((1, W * bpp), np.int64), cur[:-1]], axis=0)
+    c = np.concatenate([np.zeros((H, bpp), np.int64), b[:, :-bpp]], axis=1) if W > 1 else np.zeros_like(cur)
+    pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    pred = np.stack([np.zeros_like(cur), a, b, (a + b) >> 1, paeth])
+    ft = np.array(filters, dtype=np.int64)
+    rows = np.empty((H, 1 + W * bpp), dtype=np.uint8)
+    rows[:, 0] = ft
+    rows[:, 1:] = ((cur - pred[ft, np.arange(H)]) & 255).astype(np.uint8)
+    z = zlib.compressobj(level, zlib.DEFLATED, 15, 9, strategy)
+    stream = z.compress(rows.tobytes()) + z.flush()
+    return png_wrap(H, W, ct, stream, idat)
+
+
+def png_wrap(H: int, W: int, colour_type: int, stream: bytes, idat: Optional[int] = None) -> bytes:
+    """the file of a zlib stream (header, DEFLATE bytes, Adler-32): signature, IHDR, IDAT chunks of `idat` bytes (None: one),
+    IEND"""
+    import zlib
+
+    def chunk(kind, body):
+        return len(body).to_bytes(4, 'big') + kind + body + zlib.crc32(kind + body).to_bytes(4, 'big')
+    k = len(stream) if idat is None else int(idat)
+    if k < 1:
+        raise ValueError('png_wrap: idat is a chunk size of at least 1 byte')
+    head = W.to_bytes(4, 'big') + H.to_bytes(4, 'big') + bytes([8, colour_type, 0, 0, 0])
+    return (PNG_SIGNATURE + chunk(b'IHDR', head) + b''.join(chunk(b'IDAT', stream[i:i + k]) for i in range(0, len(stream), k))
+            + chunk(b'IEND', b''))
+
+
+class PngBatch:
+    """Files packed for one launch of ops.png_decode_u8 (png_batch makes it): host tensors, pinned where a device is there to
+    take them.  data uint8: the raw DEFLATE streams end to end, each starting at a multiple of 16 bytes | images int32 (n, 8):
+    H, W, colour type, bpp, begin, end, 0, 0 | sizes: [(H, W)] | raw_stride: the largest H (1 + W bpp) of the batch, rounded up
+    to 16 | raw_bytes: the filtered bytes of all files."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+        self._on = {}
+
+    @property
+    def scratch_bytes(self) -> int:
+        """what a launch needs: a row of raw_stride bytes per file for its filtered rows"""
+        return self.n * self.raw_stride
+
+    def on(self, device):
+        """.data and .images on `device`: uploaded once, without blocking, on the stream that is current at the first call"""
+        key = str(device)
+        if key not in self._on:
+            self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in ('data', 'images')})
+        return self._on[key]
+
+
+def png_batch(files) -> PngBatch:
+    """A sequence of PNG files (bytes, or PngHeaders) -> the PngBatch of one launch.  Every file goes through png_parse, so a
+    file the decoder does not take is refused here, before anything is uploaded."""
+    files = list(files)
+    if not files:
+        raise ValueError('png_batch: an empty batch')
+    parts, images, sizes, nbytes, stride, raw = [], [], [], 0, 16, 0
+    for f in files:
+        hd = f if isinstance(f, PngHeader) else png_parse(f)
+        images.append([hd.H, hd.W, hd.colour_type, hd.bpp, nbytes, nbytes + len(hd.data), 0, 0])
+        pad = -len(hd.data) % 16
+        parts.append(hd.data + bytes(pad))
+        nbytes += len(hd.data) + pad
+        sizes.append((hd.H, hd.W))
+        stride = max(stride, -(-hd.raw_bytes // 16) * 16)
+        raw += hd.raw_bytes
+    if nbytes > PNG_MAX_BYTES:
+        raise ValueError('png_batch: the streams of a batch hold at most %d bytes, got %d' % (PNG_MAX_BYTES, nbytes))
+    pin = torch.cuda.is_available()
+
+    def host(t):
+        return t.pin_memory() if pin and t.numel() else t
+    data = torch.frombuffer(bytearray(b''.join(parts) or bytes(16)), dtype=torch.uint8)
+    return PngBatch(data=host(data), nbytes=nbytes, images=host(torch.tensor(images, dtype=torch.int32)), sizes=sizes,
+                    n=len(files), raw_stride=stride, raw_bytes=raw)
+
+
+def check_png_status(status) -> None:
+    """reads the status table of ops.png_decode_u8 back (this waits for the device) and raises for the first damaged file"""
+    for i, s in enumerate(status.detach().cpu().tolist()):
+        if s != 0:
+            raise ValueError('png_decode: file %d is damaged (status %d: %s)' % (i, s, PNG_STATUS.get(s, 'unknown')))

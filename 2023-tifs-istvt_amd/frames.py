@@ -2,7 +2,7 @@
 readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12; and the JPEG decoder
 that makes such frames from files (jpeg_decode_u8, decode_frames) and the encoder that makes files from them (jpeg_encode_u8,
 encode_frames); and the batch draw, which makes the index and the tables of a training batch on the device (batch_draw,
-jpeg_decode_drawn_u8, draw_clips).
+jpeg_decode_drawn_u8, draw_clips); and the PNG decoder (png_decode_u8), which decode_frames takes packed files of too.
 
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
@@ -483,6 +483,61 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     return out, sizes, status
 
 
+def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None):
+    """PNG files (clips.py): a batch of 8-bit grey, RGB or RGBA PNG files goes to the device as its DEFLATE streams ->
+    (frames, sizes, status): frames uint8 [n, Hc, Wc, 3], image i in the top left H_i x W_i of its canvas and 0 elsewhere
+    (grey replicated, alpha dropped), the bytes of clips.png_decode_host; sizes int32 [n, 2] = (H, W) and status int32 [n]
+    (0: fine; clips.PNG_STATUS lists the rest, and such a file's canvas is all zeros) on the device.  Nothing is inflated on the
+    host and nothing synchronises: clips.check_png_status(status) reads back and raises, for callers who want that.  batch: a
+    sequence of bytes, parsed and packed here (clips.png_batch, which refuses what the decoder does not take), or with
+    checked=True a clips.PngBatch the caller has packed already; its tensors are uploaded once per device and kept on it.
+    canvas = (Hc, Wc) defaults to the largest H and W of the batch.  `out` (uint8, contiguous, of the result's shape, no
+    overlap with the uploaded bytes) is written when given.  buffers = (scratch uint8 of at least batch.scratch_bytes bytes
+    and 16-byte aligned, sizes, status): the caller's, to decode step after step without an allocation."""
+    if isinstance(batch, clips.PngBatch):
+        pass
+    elif checked:
+        raise RuntimeError('png_decode_u8: checked=True takes a clips.PngBatch (clips.png_batch packs and validates the files)')
+    else:
+        if isinstance(batch, (bytes, bytearray)) or not hasattr(batch, '__len__'):
+            raise TypeError('png_decode_u8 expects a sequence of files (bytes) or a clips.PngBatch, got %s' % type(batch).__name__)
+        if len(batch) == 0:
+            raise RuntimeError('png_decode_u8: empty input (no files)')
+        batch = clips.png_batch(batch)
+    need = batch.scratch_bytes
+    if not torch.cuda.is_available():
+        raise RuntimeError('istvt_amd: png_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
+    device = out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    n = batch.n
+    Hmax, Wmax = max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes)
+    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < Hmax or Wc < Wmax or Hc > 16384 or Wc > 16384:
+        raise ValueError('png_decode_u8: the canvas must hold every image (%d x %d at least, 16384 x 16384 at most), got %d x %d'
+                         % (Hmax, Wmax, Hc, Wc))
+    dev = batch.on(device)
+    out = _u8_out('png_decode_u8', dev.data, (n, Hc, Wc, 3), out)
+    _no_overlap('png_decode_u8', out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
+    if buffers is None:
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
+        sizes = torch.empty((n, 2), dtype=torch.int32, device=device)
+        status = torch.empty((n,), dtype=torch.int32, device=device)
+    else:
+        scratch, sizes, status = buffers
+        ok = (t.device == device and t.is_contiguous() for t in buffers)
+        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
+                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
+                or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
+            raise RuntimeError('png_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
+                               'status (%d,)), contiguous on %s' % (need, n, n, device))
+    args = _lib.JpegDecodeArgs(
+        bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
+        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
+        status=status.data_ptr(), stream=_stream(), n=n, Hc=Hc, Wc=Wc)
+    with prof('png_decode_u8', batch.nbytes + 2 * batch.raw_bytes + out.numel()):
+        _lib.check(_lib.lib().istvt_png_decode_u8(ctypes.byref(args), batch.raw_stride), 'istvt_png_decode_u8')
+    return out, sizes, status
+
+
 def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], buffers):
     """What a decode of m places of a bank needs beside the index: the canvas, the uploaded bank, `out` and `buffers` checked
     or made -> (the bank on its device, Hc, Wc, out, scratch, sizes, status)"""
@@ -724,7 +779,8 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
     and the scorers.  split: jpeg_decode_u8's, for files without restart markers.  layouts: jpeg_decode_u8's, for files that are
     not all 4:2:0 or 4:4:4.  files may be a clips.JpegBank with `index` (jpeg_decode_indexed_u8): the places the index names
     are decoded and cut; without `boxes` each is cut whole through boxes made from the decoder's sizes on the device, and a
-    place with status 4 or 5 comes out black.  A bank brings its own split (bank.split); split= is refused for it."""
+    place with status 4 or 5 comes out black.  A bank brings its own split (bank.split); split= is refused for it.  A
+    clips.PngBatch (clips.png_batch) is decoded by png_decode_u8 and cut the same way; split= and layouts= are refused for it."""
     if isinstance(files, clips.JpegBank):
         if index is None:
             raise ValueError('decode_frames: a clips.JpegBank is decoded through index=')
@@ -737,6 +793,11 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
         return crop_resize_u8(frames, whole, S, checked=True)
     if index is not None:
         raise ValueError('decode_frames: index= goes with a clips.JpegBank')
+    if isinstance(files, clips.PngBatch):                         # PNG files come packed: a sequence of bytes stays JPEG
+        if split is not None or layouts is not clips.JPEG_LAYOUTS_DEFAULT:
+            raise ValueError('decode_frames: split= and layouts= go with JPEG files; a clips.PngBatch takes neither')
+        frames, _, _ = png_decode_u8(files, checked=True)
+        return crop_resize_u8(frames, clips.whole_boxes(files.sizes) if boxes is None else boxes, S)
     batch = files if isinstance(files, clips.JpegBatch) else clips.jpeg_batch(files, layouts)
     frames, _, _ = jpeg_decode_u8(batch, checked=True, split=split)
     return crop_resize_u8(frames, clips.whole_boxes(batch.sizes) if boxes is None else boxes, S)

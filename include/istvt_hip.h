@@ -517,6 +517,26 @@ int istvt_jpeg_decode_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, in
  * chunk_rows and seg_bytes_max are that entry's, everything else is istvt_jpeg_decode_drawn_u8's. */
 int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max, int block_stride,
                                      int Hmax, int Wmax, int chunk_bytes, int chunk_rows, int seg_bytes_max);
+/* PNG files: a batch of 8-bit, non-interlaced PNG files of colour type 0 (grey), 2 (RGB) or 6 (RGBA), packed on the host by
+ * clips.png_batch, decoded from their raw DEFLATE streams -> out uint8 [n][Hc][Wc][3]: image i in the top left H_i x W_i of its
+ * canvas (grey replicated, alpha dropped), 0 elsewhere; sizes int32 [n][2] = (H, W) and status int32 [n] on the device.  The
+ * bytes of clips.png_decode_host.  Status: 0 fine, 1 the stream ends early, 2 a reserved block type or a stored block whose
+ * length and complement disagree, 3 code lengths over-subscribed or incomplete or a code no table holds, 4 a distance beyond
+ * the bytes produced, 5 more or fewer bytes than H (1 + W bpp), 6 a filter byte above 4; a file whose status is not 0 gets an
+ * all-zero canvas.  Two launches of n workgroups of one wave (inflate into the scratch; unfilter and colour onto the canvas),
+ * no synchronisation, no global state, nothing allocated.  The argument block is istvt_jpeg_decode_args, as istvt_batch_draw
+ * takes it; the entry reads
+ *   bytes, nbytes  uint8 [nbytes], 16-byte aligned, nbytes <= ISTVT_PNG_MAX_BYTES: the DEFLATE streams end to end, each starting at a multiple of 16 bytes;
+ *                  no byte outside a file's [begin, end) is read for it
+ *   images         int32 [n][8]: H, W, colour type, bytes per pixel (1, 3 or 4), begin, end, 0, 0;  images_host: its host copy
+ *   scratch        16-byte aligned, n * raw_stride bytes; file i's H (1 + W bpp) filtered bytes go to scratch + i * raw_stride and
+ *                  nothing else of the scratch is written
+ *   out, sizes, status, stream, n, Hc, Wc
+ * and no other field.  raw_stride: a multiple of 16, at least every file's H (1 + W bpp).  -3 on a null pointer, a bad count,
+ * a canvas smaller than an image, an out that overlaps bytes or a table row that disagrees with any of this. */
+#define ISTVT_PNG_IMAGE_INTS 8     /* a row of a PNG batch's images */
+#define ISTVT_PNG_MAX_BYTES 2147479552   /* nbytes at the most, 2^31 - 4096: byte offsets and a 256-byte window stay ints */
+int istvt_png_decode_u8(const istvt_jpeg_decode_args* a, int raw_stride);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
