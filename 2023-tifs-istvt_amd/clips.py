@@ -1305,18 +1305,16 @@ JPEG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capac
                       3: 'a coefficient outside the categories of baseline JPEG, coded clamped'}
 
 
-class JpegFiles:
-    """What ops.jpeg_encode_u8 hands back, on the device: data uint8 (capacity,): the files end to end | offsets int64
-    (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, the rest as JPEG_ENCODE_STATUS names
-    them.  Nothing here has waited for the device until files() or nbytes() is called.  geometry: what the files of one
-    encoder call share (H, W, layout, restart_interval in MCUs, optimize), left here by ops.jpeg_encode_u8 for
-    JpegBank.from_encoded; None for a JpegFiles put together by hand."""
+class _EncodedFiles:
+    """data, offsets, status of an encoder call on the device and the way back to the host, shared by JpegFiles and PngFiles;
+    a subclass names itself, its status words and the statuses whose file is empty"""
     geometry = None
+    _name, _who, _status, _empty = '', '', {}, ()
 
     def __init__(self, data: Tensor, offsets: Tensor, status: Tensor):
         if data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 \
                 or status.dtype != torch.int32 or tuple(status.shape) != (offsets.shape[0] - 1,) or status.shape[0] < 1:
-            raise ValueError('JpegFiles: data uint8 (capacity,), offsets int64 (n + 1,), status int32 (n,) expected')
+            raise ValueError('%s: data uint8 (capacity,), offsets int64 (n + 1,), status int32 (n,) expected' % self._name)
         self.data, self.offsets, self.status = data, offsets, status
 
     def __len__(self) -> int:
@@ -1329,16 +1327,25 @@ class JpegFiles:
     def files(self, check: bool = True) -> list:
         """-> [bytes] of every file.  Waits for the device once, for offsets and status, then copies offsets[n] bytes back
         (at most the capacity).  check: a non-zero status raises ValueError with its name; with check=False such a file is
-        handed over as it is: b'' for status 1 and 2."""
+        handed over as it is: b'' for a status that writes no file."""
         table = torch.cat([self.offsets, self.status.to(torch.int64)]).cpu().tolist()
         n = len(self)
         offsets, status = table[:n + 1], table[n + 1:]
         if check:
             for i, s in enumerate(status):
                 if s != 0:
-                    raise ValueError('jpeg_encode: file %d has status %d (%s)' % (i, s, JPEG_ENCODE_STATUS.get(s, 'unknown')))
+                    raise ValueError('%s: file %d has status %d (%s)' % (self._who, i, s, self._status.get(s, 'unknown')))
         host = self.data[:max(0, min(offsets[n], int(self.data.shape[0])))].cpu().numpy().tobytes()
-        return [b'' if s in (1, 2) else host[offsets[i]:offsets[i + 1]] for i, s in enumerate(status)]
+        return [b'' if s in self._empty else host[offsets[i]:offsets[i + 1]] for i, s in enumerate(status)]
+
+
+class JpegFiles(_EncodedFiles):
+    """What ops.jpeg_encode_u8 hands back, on the device: data uint8 (capacity,): the files end to end | offsets int64
+    (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, the rest as JPEG_ENCODE_STATUS names
+    them.  Nothing here has waited for the device until files() or nbytes() is called (b'' for status 1 and 2).  geometry:
+    what the files of one encoder call share (H, W, layout, restart_interval in MCUs, optimize), left here by
+    ops.jpeg_encode_u8 for JpegBank.from_encoded; None for a JpegFiles put together by hand."""
+    _name, _who, _status, _empty = 'JpegFiles', 'jpeg_encode', JPEG_ENCODE_STATUS, (1, 2)
 
 
 class JpegBatch:
@@ -3426,3 +3433,334 @@ def check_png_status(status) -> None:
     for i, s in enumerate(status.detach().cpu().tolist()):
         if s != 0:
             raise ValueError('png_decode: file %d is damaged (status %d: %s)' % (i, s, PNG_STATUS.get(s, 'unknown')))
+
+
+# ---- PNG files out (DESIGN.md "PNG files out") ---------------------------------------------------------------------------------
+# png_encode_banded_host is the definition of ops.png_encode_u8, byte for byte: row filters chosen from the source pixels, bands
+# of band_rows rows coded on their own (one dynamic-Huffman block and an empty stored block each, so every band starts and ends
+# on a byte), literals and matches at distance 1 only.  csrc/png_deflate.h is the same steps in C++ for the device and for
+# tools/png_deflate_check.cpp.
+PNG_ENCODE_STATUS = {1: 'the file does not fit in data: offsets[n] is the capacity a retry needs'}
+PNG_BAND_HEADER_BITS = 17 + 3 * 19 + 7 * 287    # BFINAL, BTYPE, HLIT, HDIST, HCLEN; 19 lengths of 3 bits; 286 + 1 lengths of <= 7 bits
+PNG_CONTAINER_BYTES = 57 + 6                # signature 8, IHDR 25, IDAT 12, IEND 12; the zlib header 2 and the Adler-32 4
+
+
+def _png_code_lengths(counts, limit: int) -> list:
+    """Counts -> the code length of every symbol (0 where the count is 0), at most `limit` bits, a complete set where two or
+    more symbols have a count.  The rule, fixed so that two programs make the same table:
+      1. merge the two smallest live counts until one is left; of equal counts the larger symbol is the smaller one; the
+         first pick c1 keeps the sum and c2's chain of symbols is hung behind c1's; every symbol of both chains gets one bit
+         more (libjpeg's jpeg_gen_optimal_table without its reserved symbol);
+      2. bits[l] = how many symbols have length l; for i from the longest length down to limit + 1, while bits[i] > 0: take
+         the largest j < i - 1 with bits[j] > 0 and do bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1 (ITU T.81
+         K.2, which keeps the Kraft sum at 1);
+      3. the symbols sorted by (length of step 1, symbol) take the lengths of bits[] in ascending order.
+    One live symbol gets length 1 (an incomplete code; no band makes one)."""
+    n = len(counts)
+    live = [s for s in range(n) if counts[s]]
+    lens = [0] * n
+    if len(live) < 2:
+        for s in live:
+            lens[s] = 1
+        return lens
+    freq, others, size = list(counts), [-1] * n, [0] * n
+    while True:
+        c1, v = -1, None
+        for s in live:
+            if freq[s] and (v is None or freq[s] <= v):
+                v, c1 = freq[s], s
+        c2, v = -1, None
+        for s in live:
+            if freq[s] and s != c1 and (v is None or freq[s] <= v):
+                v, c2 = freq[s], s
+        if c2 < 0:
+            break
+        freq[c1] += freq[c2]
+        freq[c2] = 0
+        for c in (c1, c2):
+            size[c] += 1
+            while others[c] >= 0:
+                c = others[c]
+                size[c] += 1
+        c = c1                                 # the chain of c2 goes behind the chain of c1
+        while others[c] >= 0:
+            c = others[c]
+        others[c] = c2
+    bits = [0] * (n + 2)
+    for s in live:
+        bits[size[s]] += 1
+    for i in range(n, limit, -1):
+        while bits[i] > 0:
+            j = i - 2
+            while j > 0 and bits[j] == 0:
+                j -= 1
+            if j == 0:
+                raise ValueError('_png_code_lengths: %d symbols do not fit in %d bits' % (len(live), limit))
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    order = sorted(live, key=lambda s: (size[s], s))
+    at = 0
+    for l in range(1, min(limit, n) + 1):
+        for _ in range(bits[l]):
+            lens[order[at]] = l
+            at += 1
+    return lens
+
+
+def _png_canonical(lens) -> list:
+    """RFC 1951 3.2.2: lengths -> the code of every symbol, most significant bit first"""
+    count = [0] * 16
+    for v in lens:
+        count[v] += 1
+    count[0] = 0
+    nxt, code = [0] * 16, 0
+    for n in range(1, 16):
+        code = (code + count[n - 1]) << 1
+        nxt[n] = code
+    codes = [0] * len(lens)
+    for s, v in enumerate(lens):
+        if v:
+            codes[s] = nxt[v]
+            nxt[v] += 1
+    return codes
+
+
+def _png_band_tokens(band) -> list:
+    """The tokens of one band's bytes (rows with their filter bytes, one sequence): a literal is its byte 0..255, a match of
+    length L at distance 1 is -L.  Per maximal run of n equal bytes: its first byte is a literal; of the other m = n - 1, m //
+    258 matches of 258, then one match of m % 258 where that is at least 3, else that many literals."""
+    out, i, n = [], 0, len(band)
+    while i < n:
+        j = i
+        while j < n and band[j] == band[i]:
+            j += 1
+        m = j - i - 1
+        out.append(band[i])
+        out += [-258] * (m // 258)
+        r = m % 258
+        out += [-r] if r >= 3 else [band[i]] * r
+        i = j
+    return out
+
+
+def _png_length_symbol(L: int):
+    """a match length 3..258 -> (symbol 257..285, extra bits, their count); 258 is symbol 285"""
+    k = 28
+    while _PNG_LBASE[k] > L:
+        k -= 1
+    return 257 + k, L - _PNG_LBASE[k], _PNG_LEXT[k]
+
+
+def _png_length_tokens(lens) -> list:
+    """The lengths of a block's two codes, one sequence, as code-length symbols [(symbol, extra, extra bits)], greedy from the
+    left.  A run of r zeros: 18 with min(r, 138) while r >= 11, then 17 with r where r >= 3, else r times 0.  A run of r equal
+    lengths v > 0: v once, then 16 with min(rest, 6) while the rest is >= 3, then the rest (0..2) as v."""
+    out, i, n = [], 0, len(lens)
+    while i < n:
+        j = i
+        while j < n and lens[j] == lens[i]:
+            j += 1
+        v, r = lens[i], j - i
+        if v == 0:
+            while r >= 11:
+                k = min(r, 138)
+                out.append((18, k - 11, 7))
+                r -= k
+            if r >= 3:
+                out.append((17, r - 3, 3))
+                r = 0
+        else:
+            out.append((v, 0, 0))
+            r -= 1
+            while r >= 3:
+                k = min(r, 6)
+                out.append((16, k - 3, 2))
+                r -= k
+        out += [(v, 0, 0)] * r
+        i = j
+    return out
+
+
+class _PngBitsOut:
+    """bits of a DEFLATE stream, least significant first; a Huffman code goes in most significant bit first"""
+
+    def __init__(self):
+        self.acc, self.n = 0, 0
+
+    def put(self, v: int, k: int):
+        self.acc |= v << self.n
+        self.n += k
+
+    def code(self, c: int, k: int):
+        self.put(int('{:0{}b}'.format(c, k)[::-1], 2) if k else 0, k)
+
+    def bytes(self) -> bytes:
+        return self.acc.to_bytes(-(-self.n // 8), 'little')
+
+
+def _png_band_tables(tokens):
+    """tokens -> (literal/length lengths [286], HLIT, code-length tokens, code-length code's lengths [19], HCLEN)"""
+    counts = [0] * 286
+    for t in tokens:
+        counts[t if t >= 0 else _png_length_symbol(-t)[0]] += 1
+    counts[256] = 1
+    lit = _png_code_lengths(counts, 15)
+    hlit = max(i for i in range(286) if lit[i]) + 1             # >= 257: the end-of-block has a code
+    cltok = _png_length_tokens(lit[:hlit] + [1])                # and the distance code: symbol 0, one bit
+    clcounts = [0] * 19
+    for s, _, _ in cltok:
+        clcounts[s] += 1
+    cl = _png_code_lengths(clcounts, 7)
+    hclen = max(4, max(i for i in range(19) if cl[_PNG_CL_ORDER[i]]) + 1)
+    return lit, hlit, cltok, cl, hclen
+
+
+def _png_encode_band(band, final: bool) -> bytes:
+    """one band: a dynamic-Huffman block (BFINAL = 0) and an empty stored block, which carries BFINAL on the last band"""
+    tokens = _png_band_tokens(band)
+    lit, hlit, cltok, cl, hclen = _png_band_tables(tokens)
+    if _png_code(lit) is None or _png_code(cl) is None:
+        raise RuntimeError('png_encode_banded_host: an incomplete code')
+    w = _PngBitsOut()
+    w.put(0, 1)
+    w.put(2, 2)
+    w.put(hlit - 257, 5)
+    w.put(0, 5)
+    w.put(hclen - 4, 4)
+    for i in range(hclen):
+        w.put(cl[_PNG_CL_ORDER[i]], 3)
+    clcode, litcode = _png_canonical(cl), _png_canonical(lit)
+    for s, extra, k in cltok:
+        w.code(clcode[s], cl[s])
+        w.put(extra, k)
+    for t in tokens:
+        if t >= 0:
+            w.code(litcode[t], lit[t])
+        else:
+            s, extra, k = _png_length_symbol(-t)
+            w.code(litcode[s], lit[s])
+            w.put(extra, k)
+            w.put(0, 1)                                           # distance 1: code 0 of one bit
+    w.code(litcode[256], lit[256])
+    w.put(1 if final else 0, 1)
+    w.put(0, 2)
+    w.put(0, -w.n % 8)
+    return w.bytes() + b'\x00\x00\xff\xff'
+
+
+def _png_frame(frame, who: str):
+    import numpy as np
+    px = np.ascontiguousarray(frame.detach().cpu().numpy() if torch.is_tensor(frame) else frame)
+    if px.ndim == 3 and px.shape[2] == 1:
+        px = px[:, :, 0]
+    if px.dtype != np.uint8 or px.ndim not in (2, 3) or (px.ndim == 3 and px.shape[2] not in (3, 4)) or 0 in px.shape:
+        raise ValueError('%s: a uint8 (H, W), (H, W, 1), (H, W, 3) or (H, W, 4) frame, got %s %s' % (who, px.dtype, px.shape))
+    if px.shape[0] > PNG_MAX_SIDE or px.shape[1] > PNG_MAX_SIDE:
+        raise ValueError('%s: sides of at most %d, got %d x %d' % (who, PNG_MAX_SIDE, px.shape[0], px.shape[1]))
+    return px, (1 if px.ndim == 2 else px.shape[2])
+
+
+def check_png_filters(filters, who: str = 'png_encode_banded_host') -> int:
+    """'adaptive' -> 5, a fixed type 0..4 -> itself; anything else is refused"""
+    if filters == 'adaptive':
+        return 5
+    if isinstance(filters, int) and not isinstance(filters, bool) and 0 <= filters <= 4:
+        return int(filters)
+    raise ValueError("%s: filters is 'adaptive' or one type 0..4 for every row, got %r" % (who, filters))
+
+
+def check_png_band_rows(band_rows, who: str = 'png_encode_banded_host') -> int:
+    if isinstance(band_rows, bool) or not isinstance(band_rows, int) or band_rows < 1:
+        raise ValueError('%s: band_rows is a count of rows of at least 1, got %r' % (who, band_rows))
+    return min(int(band_rows), PNG_MAX_SIDE)
+
+
+def png_filter_rows_host(frame, filters='adaptive'):
+    """frame -> the filtered rows uint8 (H, 1 + W bpp) with their filter bytes.  The predictors are png_encode_host's: a and c
+    are zero at the row's start, b and c on the image's first row, and the row above is the source's.  'adaptive': per row the
+    type whose residuals r have the smallest sum of min(r, 256 - r); of equal sums the lowest type."""
+    import numpy as np
+    px, bpp = _png_frame(frame, 'png_encode_banded_host')
+    mode = check_png_filters(filters)
+    H, W = px.shape[:2]
+    cur = px.reshape(H, W * bpp).astype(np.int64)
+    a = np.concatenate([np.zeros((H, bpp), np.int64), cur[:, :-bpp]], axis=1) if W > 1 else np.zeros_like(cur)
+    b = np.concatenate([np.zeros((1, W * bpp), np.int64), cur[:-1]], axis=0)
+    c = np.concatenate([np.zeros((H, bpp), np.int64), b[:, :-bpp]], axis=1) if W > 1 else np.zeros_like(cur)
+    pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+    paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+    res = (cur[None] - np.stack([np.zeros_like(cur), a, b, (a + b) >> 1, paeth])) & 255
+    if mode == 5:
+        ft = np.argmin(np.minimum(res, 256 - res).sum(axis=2), axis=0)
+    else:
+        ft = np.full(H, mode, dtype=np.int64)
+    rows = np.empty((H, 1 + W * bpp), dtype=np.uint8)
+    rows[:, 0] = ft
+    rows[:, 1:] = res[ft, np.arange(H)].astype(np.uint8)
+    return rows
+
+
+def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', return_bands: bool = False):
+    """The definition of ops.png_encode_u8, integers only: frame uint8 (H, W) / (H, W, 1) grey, (H, W, 3) RGB or (H, W, 4) RGBA
+    -> a complete PNG file: signature, IHDR, one IDAT, IEND.  Rows [k R, min(H, (k + 1) R)) with their filter bytes
+    (png_filter_rows_host) are band k, R = band_rows, coded on its own by _png_encode_band: tokens by _png_band_tokens, both
+    code tables by _png_code_lengths (15 and 7 bits), the lengths sent by _png_length_tokens, HLIT and HCLEN trimmed of
+    trailing zeros, HDIST = 0 with one distance code of one bit, canonical codes, then an empty stored block (000 or, on the
+    last band, 100; zeros to the byte; 00 00 FF FF).  So every band starts and ends on a byte and refers to no byte outside
+    itself.  The stream is 78 01, the bands, the Adler-32 of the filtered rows.  return_bands=True: (file, [(begin, end)] of
+    every band in the stream, whose first band begins at 2, the filter type of every row)."""
+    import zlib
+    R = check_png_band_rows(band_rows)
+    rows = png_filter_rows_host(frame, filters)
+    H, bpp = rows.shape[0], _png_frame(frame, 'png_encode_banded_host')[1]
+    W = (rows.shape[1] - 1) // bpp
+    stream, bands = bytearray(b'\x78\x01'), []
+    for r0 in range(0, H, R):
+        part = _png_encode_band(rows[r0:r0 + R].tobytes(), r0 + R >= H)
+        bands.append((len(stream), len(stream) + len(part)))
+        stream += part
+    stream += zlib.adler32(rows.tobytes()).to_bytes(4, 'big')
+    data = png_wrap(H, W, {1: 0, 3: 2, 4: 6}[bpp], bytes(stream))
+    return (data, bands, rows[:, 0].tolist()) if return_bands else data
+
+
+def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive') -> list:
+    """the files of a batch: frames uint8 (n, H, W), (n, H, W, 1 | 3 | 4) or clips (B, T, H, W, C) -> [bytes], one
+    png_encode_banded_host each"""
+    import numpy as np
+    px = np.asarray(frames.detach().cpu().numpy() if torch.is_tensor(frames) else frames)
+    if px.ndim == 5:
+        px = px.reshape((-1,) + px.shape[2:])
+    if px.ndim not in (3, 4):
+        raise ValueError('png_encode_files_host: frames (n, H, W), (n, H, W, C) or (B, T, H, W, C), got %s' % (px.shape,))
+    return [png_encode_banded_host(f, band_rows, filters) for f in px]
+
+
+def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16) -> int:
+    """The bytes one file of png_encode_banded_host needs at the most.  A band of nb bytes (rows (1 + W bpp)) is at most nb
+    tokens and the end-of-block.  The code `256 literals of 9 bits, the end-of-block and the 29 length symbols of 6` is a
+    prefix code (256 / 512 + 30 / 64 < 1), and under it a literal costs 9 bits and a match 6 + 5 extra + 1 distance = 12 for
+    at least 3 bytes, so a band's tokens cost at most 9 nb bits and the end-of-block at most 15; a Huffman code costs no more
+    than any prefix code.  (The covering code is not the issue's sketch, 255 literals of 8 bits and two symbols of 9, which
+    has no room for the length symbols the tokens use.)  The limit of 15 bits only acts where a code would be longer, which
+    takes counts that grow like 1, 1, 2, 3, 5, ... (2584 bytes at least); the adjustment that shortens such a code is not
+    an optimal one, so for those bands the 9 bits are measured (tests/test_png_encode_cpu.py: far inside), not proven.
+    Nothing rests on it but the default capacity: the kernels check the capacity themselves and report status 1.  The block
+    header is at most PNG_BAND_HEADER_BITS = 17
+    + 19 * 3 + 287 * 7 bits.  The empty stored block is 3 bits, the pad to the byte and 4 bytes.  Bands of a file: ceil(H /
+    R).  The container is 57 + 6 bytes."""
+    H, W, bpp, R = int(H), int(W), int(bpp), check_png_band_rows(band_rows, 'png_encoded_bound')
+    stride, total = 1 + W * bpp, PNG_CONTAINER_BYTES
+    for r0 in range(0, H, R):
+        nb = (min(H, r0 + R) - r0) * stride
+        total += -(-(PNG_BAND_HEADER_BITS + 9 * nb + 15 + 3) // 8) + 4
+    return total
+
+
+class PngFiles(_EncodedFiles):
+    """What ops.png_encode_u8 hands back, on the device, with JpegFiles' semantics: data uint8 (capacity,): the files end to
+    end | offsets int64 (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, 1 as
+    PNG_ENCODE_STATUS words it (files() hands b'' over for it with check=False).  geometry: H, W, bpp, band_rows, filters."""
+    _name, _who, _status, _empty = 'PngFiles', 'png_encode', PNG_ENCODE_STATUS, (1,)

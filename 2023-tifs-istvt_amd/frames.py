@@ -2,7 +2,8 @@
 readers, the JPEG round trip, the perturbations and the relevance paste, in packed RGB and in NV12; and the JPEG decoder
 that makes such frames from files (jpeg_decode_u8, decode_frames) and the encoder that makes files from them (jpeg_encode_u8,
 encode_frames); and the batch draw, which makes the index and the tables of a training batch on the device (batch_draw,
-jpeg_decode_drawn_u8, draw_clips); and the PNG decoder (png_decode_u8), which decode_frames takes packed files of too.
+jpeg_decode_drawn_u8, draw_clips); and the PNG decoder (png_decode_u8), which decode_frames takes packed files of too, and
+the PNG writer (png_encode_u8), which encode_frames(format='png') ends in.
 
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
@@ -29,18 +30,23 @@ def prof(name, nbytes):
 
 
 # ---- the argument front end ------------------------------------------------------------------------------------------------
-def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: bool = False, on_device: bool = True):
+def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: bool = False, on_device: bool = True,
+                channels=(3,)):
     """Packed RGB frames: uint8, channels last, (n, Hs, Ws, 3) or (clips_too) (B, T, Hs, Ws, 3) on the device, not empty, at
     most 16384 x 16384; contiguous=True refuses what would have to be copied.  -> (n frames, T or None, Hs, Ws); the kernels
     take a pointer and n, so the flat source is _c(frames).  on_device=False leaves the device to the caller, who asks for it
-    (_req) behind the argument errors that need none."""
+    (_req) behind the argument errors that need none.  channels: the channel counts taken in the place of 3 (the PNG writer:
+    1, 3 or 4); the caller reads the count from the shape."""
     if on_device:
         _req(frames, 'frames')
     elif not torch.is_tensor(frames):
         raise TypeError('%s: frames must be a uint8 tensor, got %s' % (what, type(frames).__name__))
     if frames.dtype != torch.uint8:
         raise TypeError('%s: frames must be uint8, got %s' % (what, frames.dtype))
-    if frames.dim() not in ((4, 5) if clips_too else (4,)) or frames.shape[-1] != 3:
+    if tuple(channels) != (3,) and (frames.dim() not in (4, 5) or frames.shape[-1] not in channels):
+        raise RuntimeError('%s expects channels-last (n, H, W, C) or (B, T, H, W, C) uint8 input with C in %s (grey also as (n, H, W)), '
+                           'got %s' % (what, tuple(channels), tuple(frames.shape)))
+    if frames.dim() not in ((4, 5) if clips_too else (4,)) or frames.shape[-1] not in channels:
         hw = 'H, W' if contiguous else 'Hs, Ws'
         raise RuntimeError('%s expects channels-last (n, %s, 3)%s uint8 input, got %s'
                            % (what, hw, ' or (B, T, %s, 3)' % hw if clips_too else '', tuple(frames.shape)))
@@ -53,7 +59,7 @@ def _rgb_source(what: str, frames: Tensor, clips_too: bool = True, contiguous: b
     if Hs > 16384 or Ws > 16384:
         raise ValueError('%s: frames of at most 16384 x 16384, got %d x %d' % (what, Hs, Ws))
     T = int(frames.shape[1]) if frames.dim() == 5 else None
-    return frames.numel() // (Hs * Ws * 3), T, Hs, Ws
+    return frames.numel() // (Hs * Ws * int(frames.shape[-1])), T, Hs, Ws
 
 
 def _nv12_launch(t: Tensor, first: int, Hs: int, Ws: int):
@@ -913,20 +919,123 @@ def _jpeg_encode_launch(frames, nbytes, qdev, header, hlen, scratch, data, offse
         _lib.check(_lib.lib().istvt_jpeg_encode_u8(ctypes.byref(args)), 'istvt_jpeg_encode_u8')
 
 
-def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None, quality=90,
-                  subsampling: str = '420', restart_interval='row', optimize: bool = False, layout=None) -> 'clips.JpegFiles':
+class _NotGiven:
+    """the default of encode_frames' JPEG-only arguments: tells `not given` from a value that happens to be the default"""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __repr__(self):
+        return repr(self.value)
+
+
+_JPEG_ONLY = dict(quality=_NotGiven(90), subsampling=_NotGiven('420'), restart_interval=_NotGiven('row'), optimize=_NotGiven(False),
+                  layout=None)       # layout's own word for `not given` is None, as in every other signature that has it
+
+
+def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
+                  quality=_JPEG_ONLY['quality'], subsampling=_JPEG_ONLY['subsampling'],
+                  restart_interval=_JPEG_ONLY['restart_interval'], optimize=_JPEG_ONLY['optimize'], layout=_JPEG_ONLY['layout'],
+                  format: str = 'jpeg', band_rows=None, filters=None):
     """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
     cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
     (jpeg_encode_u8; optimize=True: with their own Huffman tables; layout: one of clips.JPEG_LAYOUTS in the place of
     subsampling) -> a clips.JpegFiles, whose files() ops.decode_frames and clips.jpeg_batch take (with layouts='all' for '422'
-    and 'grey')."""
+    and 'grey').  format='png': the crops leave lossless, as PNG files (png_encode_u8 with band_rows and filters, 16 and
+    'adaptive' where not given) -> a clips.PngFiles; the JPEG-only arguments (quality 90, subsampling '420', restart_interval
+    'row' and optimize False where not given) are then refused if given, whatever their value, and so is a layout."""
+    if format not in ('jpeg', 'png'):
+        raise ValueError("encode_frames: format is 'jpeg' or 'png', got %r" % (format,))
+    if format == 'png':
+        given = dict(quality=quality, subsampling=subsampling, restart_interval=restart_interval, optimize=optimize, layout=layout)
+        for name, default in _JPEG_ONLY.items():
+            if given[name] is not default:
+                raise ValueError("encode_frames: %s= goes with format='jpeg'; format='png' takes band_rows= and filters=" % name)
+    elif band_rows is not None or filters is not None:
+        raise ValueError("encode_frames: band_rows= and filters= go with format='png'")
+    quality, subsampling, restart_interval, optimize, layout = (v.value if isinstance(v, _NotGiven) else v for v in
+                                                                (quality, subsampling, restart_interval, optimize, layout))
     if (boxes is None) == (transforms is None):
         raise ValueError('encode_frames: boxes and transforms are two ways to cut the same crop: pass one of them')
+    if format == 'png':
+        band_rows = clips.check_png_band_rows(16 if band_rows is None else band_rows, 'png_encode_u8')
+        filters = 'adaptive' if filters is None else filters
+        clips.check_png_filters(filters, 'png_encode_u8')
+        crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
+        return png_encode_u8(crops, band_rows, filters)
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     clips._jpeg_encode_layout(subsampling, layout, 'jpeg_encode_u8')
     crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
     return jpeg_encode_u8(crops, quality, subsampling, restart_interval, optimize=optimize, layout=layout)
+
+
+# ---- PNG files out -----------------------------------------------------------------------------------------------------------
+PNG_BAND_ROW_BYTES = 1728                   # ISTVT_PNG_BAND_ROW_BYTES of include/istvt_hip.h: a band's tables in the scratch
+
+
+def png_encode_scratch(n: int, H: int, W: int, bpp: int, band_rows: int):
+    """-> (raw_stride, scratch bytes) of istvt_png_encode_u8: a file's filtered rows, rounded up to 16 bytes, and
+    PNG_BAND_ROW_BYTES per band"""
+    R = min(band_rows, H)
+    raw_stride = -(-(H * (1 + W * bpp)) // 16) * 16
+    return raw_stride, n * raw_stride + n * (-(-H // R)) * PNG_BAND_ROW_BYTES
+
+
+def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capacity: Optional[int] = None,
+                  buffers=None) -> 'clips.PngFiles':
+    """PNG files out (clips.py): frames uint8 [n,H,W] or [n,H,W,1] (grey), [n,H,W,3] (RGB), [n,H,W,4] (RGBA) or clips
+    [B,T,H,W,C], contiguous, on the device -> a clips.PngFiles on the device: the files of clips.png_encode_files_host end to
+    end in `data`, byte for byte, with `offsets` and a `status` per file.  Lossless, for frame sets whose compression traces a
+    JPEG re-encode would overwrite.  band_rows: the rows that are coded together; every band is a DEFLATE block of its own
+    that starts and ends on a byte and refers to nothing outside itself.  filters: 'adaptive' (per row the type with the
+    smallest sum of absolute residuals) or one type 0..4 for every row.  capacity: the bytes of `data`, by default n *
+    clips.png_encoded_bound(H, W, bpp, band_rows); a file that does not fit gets status 1, nothing of it is written, and
+    offsets[n] says what a retry needs.  buffers = (data uint8 (capacity,), scratch uint8 of at least png_encode_scratch(...)[1]
+    bytes and 16-byte aligned, offsets int64 (n + 1,), status int32 (n,)): the caller's, to encode step after step without an
+    allocation; data may not overlap the frames.  Four launches, nothing synchronises."""
+    what = 'png_encode_u8'
+    if torch.is_tensor(frames) and frames.dim() == 3:
+        frames = frames.unsqueeze(-1)
+    n, T, H, W = _rgb_source(what, frames, contiguous=True, on_device=False, channels=(1, 3, 4))
+    bpp = int(frames.shape[-1])
+    R = clips.check_png_band_rows(band_rows, what)
+    mode = clips.check_png_filters(filters, what)
+    bound = n * clips.png_encoded_bound(H, W, bpp, R)
+    if bound > clips.PNG_MAX_BYTES:
+        raise ValueError('%s: the files of a batch hold at most %d bytes, %d frames of %d x %d x %d can need %d'
+                         % (what, clips.PNG_MAX_BYTES, n, H, W, bpp, bound))
+    _req(frames, 'frames')
+    device = frames.device
+    raw_stride, need = png_encode_scratch(n, H, W, bpp, R)
+    if buffers is None:
+        capacity = bound if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError('%s: the capacity must be positive, got %d' % (what, capacity))
+        data = torch.empty((capacity,), dtype=torch.uint8, device=device)
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=device)
+        status = torch.empty((n,), dtype=torch.int32, device=device)
+    else:
+        data, scratch, offsets, status = buffers
+        ok = (torch.is_tensor(t) and t.device == device and t.is_contiguous() for t in buffers)
+        if (not all(ok) or data.dtype != torch.uint8 or data.dim() != 1 or data.numel() < 1 or scratch.dtype != torch.uint8
+                or scratch.numel() < need or scratch.data_ptr() % 16 or offsets.dtype != torch.int64
+                or tuple(offsets.shape) != (n + 1,) or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
+            raise RuntimeError('%s: buffers = (uint8 data (capacity,); uint8 scratch of %d bytes, 16-byte aligned; int64 offsets '
+                               '(%d,); int32 status (%d,)), contiguous on %s' % (what, need, n + 1, n, device))
+        if capacity is not None and int(capacity) != data.numel():
+            raise ValueError('%s: capacity %d and data of %d bytes disagree' % (what, int(capacity), data.numel()))
+    nbytes = frames.numel()
+    _no_overlap(what, data, frames.data_ptr(), nbytes, 'frames')
+    args = _lib.JpegEncodeArgs(
+        frames=frames.data_ptr(), total=nbytes, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(),
+        capacity=data.numel(), offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W)
+    with prof(what, nbytes + 3 * n * H * (1 + W * bpp)):          # the pixels; the filtered rows written once and read twice
+        _lib.check(_lib.lib().istvt_png_encode_u8(ctypes.byref(args), bpp, R, mode, raw_stride), 'istvt_png_encode_u8')
+    files = clips.PngFiles(data, offsets, status)
+    files.geometry = SimpleNamespace(H=H, W=W, bpp=bpp, band_rows=R, filters=filters)
+    return files
 
 
 def perturb_u8(frames: Tensor, table: Tensor, taps: Optional[Tensor] = None, seed: int = 0, out: Optional[Tensor] = None,

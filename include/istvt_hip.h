@@ -609,6 +609,29 @@ int istvt_jpeg_encode_layout_u8(const istvt_jpeg_encode_args* a, int layout, int
  * status is not 0, that is shorter than header_bytes + 2, does not end with EOI or does not hold seg_max - 1 restart markers
  * gets 0 segments in its images row: istvt_jpeg_decode_indexed_u8 reports status 5 for it.  -3 as above. */
 int istvt_jpeg_bank_ingest(const istvt_jpeg_encode_args* a, int layout);
+/* PNG files out: a batch of frames uint8 [n][H][W][bpp], bpp = 1 (grey), 3 (RGB) or 4 (RGBA) -> n complete PNG files (signature,
+ * IHDR, one IDAT, IEND) end to end in `data`, the bytes of clips.png_encode_banded_host.  Rows [k R, min(H, (k + 1) R)) with
+ * their filter bytes are band k, R = min(band_rows, H): one dynamic-Huffman block of literals and distance-1 matches and an
+ * empty stored block, so every band starts and ends on a byte and can be inflated alone.  filter: 0..4 on every row, or 5: per
+ * row the type with the smallest sum of min(r, 256 - r) over its residuals, the lowest on a tie; the row above is the source's.
+ * The block is istvt_jpeg_encode_args, of which this entry reads
+ *   frames, total  the pixels, total >= n H W bpp bytes readable; no alignment needed
+ *   scratch        16-byte aligned, scratch_bytes >= n * raw_stride + n * ceil(H / R) * ISTVT_PNG_BAND_ROW_BYTES: file i's
+ *                  filtered rows at i * raw_stride (raw_stride >= H (1 + W bpp), a multiple of 16), then one row of 432 ints per
+ *                  band: 288 literal/length code words (bit-reversed code << 8 | length), 136 dwords of block-header bits, then
+ *                  header bits, the band's bytes in the stream, Adler-32 parts a, b, the band's filtered bytes, the distance
+ *                  code's word, the band's offset in the stream, 0
+ *   data, capacity the files; data may not overlap frames
+ *   offsets        long [n + 1]: file i is data[offsets[i] .. offsets[i + 1])
+ *   status         int [n]: 0 fine, 1 the file does not fit: nothing of it is written, offsets still hold true sizes and
+ *                  offsets[n] is the capacity a retry needs
+ *   stream, n, H, W (H, W <= 16384)
+ * and no other field.  Four launches (filter and count, one wave per band; prefix sum, one workgroup; store, the same waves;
+ * container with Adler-32 and CRC-32s, one workgroup of 512 threads per file), no synchronisation, no global atomics, nothing allocated, nothing
+ * that has to be zeroed.  -3 before any launch: a null pointer, a bad count, size, bpp, band_rows or filter, a misaligned or
+ * short scratch, data overlapping frames. */
+#define ISTVT_PNG_BAND_ROW_BYTES 1728
+int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with
