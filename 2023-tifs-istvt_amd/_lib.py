@@ -91,7 +91,9 @@ SIGNATURES = {
     'istvt_jpeg_decode_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I, I, I],
     'istvt_jpeg_decode_drawn_split_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I, I, I, I, I, I],
     'istvt_png_decode_u8': [ctypes.POINTER(JpegDecodeArgs), I],
+    'istvt_png_decode_bands_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_png_encode_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
+    'istvt_png_encode_indexed_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_jpeg_bank_ingest': [ctypes.POINTER(JpegEncodeArgs), I],
     'istvt_jpeg_encode_u8': [ctypes.POINTER(JpegEncodeArgs)],
     'istvt_jpeg_encode_opt_u8': [ctypes.POINTER(JpegEncodeArgs), I, I],

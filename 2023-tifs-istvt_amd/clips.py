@@ -3012,6 +3012,11 @@ PNG_STATUS = {1: 'the stream ends early', 2: 'a reserved block type, or a stored
               3: 'code lengths that are over-subscribed or incomplete, or a code no table holds',
               4: 'a distance beyond the bytes produced', 5: 'more, or fewer, bytes than H (1 + W bpp)',
               6: 'a filter byte above 4'}
+# the status only a band-wise decode gives (png_decode_bands_host, ops.png_decode_u8 on a batch with bands); check_png_status
+# words it too.  A table of its own, as JPEG_BANK_STATUS is: PNG_STATUS lists what the sequential decoder can give.
+PNG_BAND_STATUS = {7: 'the band index disagrees with the stream'}
+PNG_BAND_CHUNK = b'baND'                    # ancillary, private, reserved bit clear, not safe to copy: it describes the IDAT bytes
+PNG_BAND_INTS = 5                           # a row of PngBatch.bands: ISTVT_PNG_BAND_INTS of include/istvt_hip.h
 _PNG_LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 _PNG_LEXT = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
 _PNG_DBASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
@@ -3022,7 +3027,8 @@ _PNG_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 1
 
 class PngHeader:
     """What png_parse reads from one file: H, W, colour_type (0 grey, 2 RGB, 6 RGBA), bpp (1, 3 or 4 bytes per pixel) and
-    data, the raw DEFLATE bytes of the joined IDAT chunks without the zlib header and the Adler-32."""
+    data, the raw DEFLATE bytes of the joined IDAT chunks without the zlib header and the Adler-32.  bands: (R, offsets) of a
+    usable baND chunk (_png_band_index), else None."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -3047,7 +3053,7 @@ def png_parse(data) -> PngHeader:
     data = bytes(data)
     if data[:8] != PNG_SIGNATURE:
         _png_refuse('the file does not start with the PNG signature')
-    pos, ihdr, idat, ended, run = 8, None, [], False, False
+    pos, ihdr, idat, ended, run, index = 8, None, [], False, False, []
     while pos < len(data):
         if pos + 12 > len(data):
             _png_refuse('a chunk header at byte %d reaches past the end of the file' % pos)
@@ -3092,6 +3098,8 @@ def png_parse(data) -> PngHeader:
         elif kind == b'PLTE':
             if ct == 0:
                 _png_refuse('a PLTE chunk in a grey file (colour type 0)')
+        elif kind == PNG_BAND_CHUNK:
+            index.append((body, not idat))
         elif not kind[0] & 0x20:
             _png_refuse('critical chunk %s is not known' % kind.decode('latin-1'))
         run = kind == b'IDAT'
@@ -3104,7 +3112,41 @@ def png_parse(data) -> PngHeader:
     z = b''.join(idat)
     if len(z) < 6 or (z[0] & 15) != 8 or (z[0] >> 4) > 7 or (z[1] & 0x20) or ((z[0] << 8) | z[1]) % 31:
         _png_refuse('a bad zlib header (method 8, a window of at most 32 KiB and no preset dictionary are taken)')
-    return PngHeader(H=H, W=W, colour_type=ct, bpp=PNG_BPP[ct], data=z[2:-4])
+    return PngHeader(H=H, W=W, colour_type=ct, bpp=PNG_BPP[ct], data=z[2:-4], bands=_png_band_index(index, H, len(z)))
+
+
+def png_band_chunk_bytes(H: int, band_rows: int) -> int:
+    """the bytes a baND chunk adds to a file: length, type and CRC-32 12, R and nb 8, nb + 1 offsets"""
+    return 12 + 8 + 4 * (-(-int(H) // int(band_rows)) + 1)
+
+
+def _png_band_chunk(R: int, offsets) -> bytes:
+    """The band index of one file, the chunk that stands between IHDR and IDAT.  The body is big-endian uint32 words: R, the
+    band rows; nb = ceil(H / R); nb + 1 offsets into the zlib stream (the joined IDAT bodies), off[0] = 2 behind the zlib
+    header, off[nb] = the stream's length - 4 in front of the Adler-32.  Band k is stream bytes [off[k], off[k + 1]) and holds
+    rows [k R, min(H, (k + 1) R)) with their filter bytes."""
+    import zlib
+    body = b''.join(int(v).to_bytes(4, 'big') for v in [R, len(offsets) - 1] + list(offsets))
+    return len(body).to_bytes(4, 'big') + PNG_BAND_CHUNK + body + zlib.crc32(PNG_BAND_CHUNK + body).to_bytes(4, 'big')
+
+
+def _png_band_index(chunks, H: int, stream_bytes: int):
+    """[(body, stands before the first IDAT)] of a file's baND chunks -> (R, [off[0] .. off[nb]]), or None where the index is
+    not taken: not exactly one chunk, one behind an IDAT, a length that is not 8 + 4 (nb + 1) for the nb = ceil(H / R) of its
+    own R >= 1, an nb that is not that, off[0] != 2, offsets that do not increase strictly, or off[nb] != the stream's length
+    - 4.  Never a refusal: the chunk is ancillary, and a decoder that ignores it is a correct one."""
+    if len(chunks) != 1 or not chunks[0][1]:
+        return None
+    body = chunks[0][0]
+    if len(body) < 16 or len(body) % 4:
+        return None
+    words = [int.from_bytes(body[i:i + 4], 'big') for i in range(0, len(body), 4)]
+    R, nb, off = words[0], words[1], words[2:]
+    if R < 1 or nb != -(-H // R) or len(off) != nb + 1:
+        return None
+    if off[0] != 2 or off[-1] != stream_bytes - 4 or any(a >= b for a, b in zip(off, off[1:])):
+        return None
+    return R, off
 
 
 class _PngBits:
@@ -3163,15 +3205,20 @@ def _png_symbol(bits: _PngBits, code):
     return -3
 
 
-def _png_inflate(raw, expected: int):
+def _png_inflate(raw, expected: int, middle: bool = False):
     """RFC 1951 on one raw stream whose output length is known -> (bytes, status 0..5 of PNG_STATUS); the first fault in stream
-    order decides, and a stored block checks its complement, then the room, then the bytes it has."""
+    order decides, and a stored block checks its complement, then the room, then the bytes it has.  middle=True is the band
+    mode of png_decode_bands_host for a band that is not its file's last: `raw` is the band's bytes alone; a block header
+    with BFINAL set is status 7, whatever its type; the band stops behind a stored block that ends on the last byte of
+    `raw`, and then checks the count as the end of a stream does."""
     bits, out = _PngBits(bytes(raw)), bytearray()
     while True:
         bits.refill()
         if bits.cnt < 3:
             return out, 1
         last, kind = bits.take(1), bits.take(2)
+        if middle and last:
+            return out, 7
         if kind == 3:
             return out, 2
         if kind == 0:
@@ -3189,6 +3236,8 @@ def _png_inflate(raw, expected: int):
             for _ in range(n):
                 bits.refill()
                 out.append(bits.take(8))
+            if middle and bits.pos - bits.cnt // 8 == len(bits.data):
+                break
         else:
             if kind == 1:
                 lit, dist = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 32
@@ -3330,6 +3379,70 @@ def png_decode_host(data, return_status: bool = False):
     return (out, status) if return_status else out
 
 
+def png_band_table(hd: PngHeader, file: int = 0, base: int = 0) -> list:
+    """The bands of one parsed file as rows of PngBatch.bands: [file, first byte, end byte, first output byte within the
+    file's filtered rows, output bytes], the byte positions counted from `base` + the start of hd.data.  A file without a
+    usable index is one band over its whole stream."""
+    if hd.bands is None:
+        return [[file, base, base + len(hd.data), 0, hd.raw_bytes]]
+    R, off = hd.bands
+    stride = 1 + hd.W * hd.bpp
+    return [[file, base + off[k] - 2, base + off[k + 1] - 2, k * R * stride, (min(hd.H, (k + 1) * R) - k * R) * stride]
+            for k in range(len(off) - 1)]
+
+
+def png_inflate_bands_host(hd: PngHeader):
+    """-> (the filtered rows as far as they were decoded, bytearray of hd.raw_bytes; [status of every band])"""
+    rows = png_band_table(hd)
+    raw, statuses = bytearray(hd.raw_bytes), []
+    for k, (_, begin, end, at, nbytes) in enumerate(rows):
+        out, status = _png_inflate(hd.data[begin:end], nbytes, middle=k < len(rows) - 1)
+        raw[at:at + len(out)] = out
+        statuses.append(status)
+    return raw, statuses
+
+
+def png_decode_bands_host(data, return_status: bool = False):
+    """The definition of ops.png_decode_u8 on a batch that carries bands, integers only: one file (bytes, or a PngHeader) ->
+    uint8 (H, W, 3), with return_status=True (frame, status).  Every band of the file's index (png_parse: .bands) is decoded
+    alone, by _png_inflate's rules with two changes.
+      The window starts at the band's first output byte: a distance beyond the bytes THIS band has produced is status 4.  The
+        output is bounded by the band's rows (1 + W bpp) bytes and the input by the band's [begin, end).
+      The stop rule.  A band that is not the file's last stops when a stored block ends with the byte position equal to `end`;
+        the file's last band stops at its BFINAL block, whatever its type, as the sequential decoder does.
+    The order of precedence, which the device follows: the faults of a block are _png_inflate's, in its order, and the first in
+    stream order decides.  In a band that is not the last, BFINAL is looked at before the block's type: a set BFINAL is status
+    7 (PNG_BAND_STATUS) even on a reserved type, and nothing of that block is decoded.  Bits or bytes wanted at or past `end` are
+    status 1, wherever that happens -- so a band whose last block is not a stored one ending on `end` runs into status 1 at
+    the next block header, and a stored block that reaches past `end` is 1 after its complement (2) and its room (5) were
+    checked.  More bytes than the band's rows hold is status 5 where the symbol or the stored block that brings them stands;
+    fewer is status 5 at the stop, so of a band that stops in the right place with the wrong count 5 is the status.
+    The file's status is the status of its first failing band, in band order; then 6 for a filter byte above 4, as in
+    png_decode_host.  A file whose bands is None is one last band over its whole stream: the sequential decoder, the same
+    bytes and the same status as png_decode_host.
+    Why a file whose bands all have status 0 decodes to png_decode_host's frame: by induction over the bands.  Say the
+    sequential decoder stands at byte off[k] on a byte boundary in front of a block header, with exactly the rows in front of
+    band k produced (true for k = 0).  The band decoder read non-final blocks from there to a stored block that ended at
+    off[k + 1]; the sequential decoder reads the same bits, for every symbol the band decoder took had all of its bits inside
+    the band; every distance lay inside the band's own output, so inside the sequential window, and copied the same bytes;
+    no count check fires sooner, for the file's room is no smaller than the band's; no block has BFINAL, so it goes on; behind
+    the stored block it stands at off[k + 1] on a byte boundary with band k's rows produced.  The last band ends with its
+    BFINAL block in both, and the counts sum to H (1 + W bpp): status 0, the same filtered rows, the same frame."""
+    import numpy as np
+    hd = data if isinstance(data, PngHeader) else png_parse(data)
+    raw, statuses = png_inflate_bands_host(hd)
+    status = next((s for s in statuses if s), 0)
+    rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(hd.H, -1) if status == 0 else None
+    if status == 0 and int(rows[:, 0].max()) > 4:
+        status = 6
+    if status:
+        out = torch.zeros((hd.H, hd.W, 3), dtype=torch.uint8)
+    else:
+        px = torch.from_numpy(_png_unfilter(rows, hd.bpp)).reshape(hd.H, hd.W, hd.bpp)
+        out = px.expand(hd.H, hd.W, 3).contiguous() if hd.bpp == 1 else px[:, :, :3].contiguous()
+    return (out, status) if return_status else out
+
+
 def png_encode_host(frame, filters=None, level: int = 6, strategy: int = 0, idat: Optional[int] = None) -> bytes:
     """A PNG file of `frame`, uint8 (H, W) grey, (H, W, 3) RGB or (H, W, 4) RGBA (a tensor or an array): host only, for tests
     and users.  filters: one filter type 0..4 per row (None: 0 on every row).  zlib.compressobj(level, DEFLATED, 15, 9,
@@ -3363,9 +3476,9 @@ def png_encode_host(frame, filters=None, level: int = 6, strategy: int = 0, idat
     return png_wrap(H, W, ct, stream, idat)
 
 
-def png_wrap(H: int, W: int, colour_type: int, stream: bytes, idat: Optional[int] = None) -> bytes:
-    """the file of a zlib stream (header, DEFLATE bytes, Adler-32): signature, IHDR, IDAT chunks of `idat` bytes (None: one),
-    IEND"""
+def png_wrap(H: int, W: int, colour_type: int, stream: bytes, idat: Optional[int] = None, extra: bytes = b'') -> bytes:
+    """the file of a zlib stream (header, DEFLATE bytes, Adler-32): signature, IHDR, `extra` (whole chunks, as they are),
+    IDAT chunks of `idat` bytes (None: one), IEND"""
     import zlib
 
     def chunk(kind, body):
@@ -3374,7 +3487,7 @@ def png_wrap(H: int, W: int, colour_type: int, stream: bytes, idat: Optional[int
     if k < 1:
         raise ValueError('png_wrap: idat is a chunk size of at least 1 byte')
     head = W.to_bytes(4, 'big') + H.to_bytes(4, 'big') + bytes([8, colour_type, 0, 0, 0])
-    return (PNG_SIGNATURE + chunk(b'IHDR', head) + b''.join(chunk(b'IDAT', stream[i:i + k]) for i in range(0, len(stream), k))
+    return (PNG_SIGNATURE + chunk(b'IHDR', head) + extra + b''.join(chunk(b'IDAT', stream[i:i + k]) for i in range(0, len(stream), k))
             + chunk(b'IEND', b''))
 
 
@@ -3382,35 +3495,55 @@ class PngBatch:
     """Files packed for one launch of ops.png_decode_u8 (png_batch makes it): host tensors, pinned where a device is there to
     take them.  data uint8: the raw DEFLATE streams end to end, each starting at a multiple of 16 bytes | images int32 (n, 8):
     H, W, colour type, bpp, begin, end, 0, 0 | sizes: [(H, W)] | raw_stride: the largest H (1 + W bpp) of the batch, rounded up
-    to 16 | raw_bytes: the filtered bytes of all files."""
+    to 16 | raw_bytes: the filtered bytes of all files.  bands: None, or with png_batch(bands='index') int32 (nband, 5), the
+    bands of all files sorted by file, then by band: file, first byte in data, end byte, first output byte within the file's
+    filtered rows, output bytes; images[:, 6:8] are then a file's first row of `bands` and its count of them."""
 
     def __init__(self, **kw):
+        self.bands = None
         self.__dict__.update(kw)
         self._on = {}
 
     @property
     def scratch_bytes(self) -> int:
-        """what a launch needs: a row of raw_stride bytes per file for its filtered rows"""
-        return self.n * self.raw_stride
+        """what a launch needs: a row of raw_stride bytes per file for its filtered rows; with bands, behind them a status
+        word per band"""
+        return self.n * self.raw_stride + (0 if self.bands is None else 4 * int(self.bands.shape[0]))
 
     def on(self, device):
-        """.data and .images on `device`: uploaded once, without blocking, on the stream that is current at the first call"""
+        """.data and .images (and .bands, where the batch has them) on `device`: uploaded once, without blocking, on the
+        stream that is current at the first call"""
         key = str(device)
         if key not in self._on:
-            self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in ('data', 'images')})
+            names = ('data', 'images') + (() if self.bands is None else ('bands',))
+            self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in names})
         return self._on[key]
 
 
-def png_batch(files) -> PngBatch:
+def check_png_bands(bands, who: str = 'png_batch'):
+    """None (the sequential decoder) or 'index' (one wave per band of every file's baND chunk); anything else is refused"""
+    if bands is None or bands == 'index':
+        return bands
+    raise ValueError("%s: bands is None or 'index', got %r" % (who, bands))
+
+
+def png_batch(files, bands=None) -> PngBatch:
     """A sequence of PNG files (bytes, or PngHeaders) -> the PngBatch of one launch.  Every file goes through png_parse, so a
-    file the decoder does not take is refused here, before anything is uploaded."""
+    file the decoder does not take is refused here, before anything is uploaded.  bands='index': the batch carries the band
+    table of the files' baND chunks (png_band_table), one band for a file without a usable chunk, and ops.png_decode_u8
+    decodes it one wave per band; bands=None: the batch of the sequential decoder, whatever chunks the files have."""
+    check_png_bands(bands)
     files = list(files)
     if not files:
         raise ValueError('png_batch: an empty batch')
-    parts, images, sizes, nbytes, stride, raw = [], [], [], 0, 16, 0
+    parts, images, sizes, nbytes, stride, raw, table = [], [], [], 0, 16, 0, []
     for f in files:
         hd = f if isinstance(f, PngHeader) else png_parse(f)
         images.append([hd.H, hd.W, hd.colour_type, hd.bpp, nbytes, nbytes + len(hd.data), 0, 0])
+        if bands is not None:
+            rows = png_band_table(hd, len(images) - 1, nbytes)
+            images[-1][6:8] = [len(table), len(rows)]
+            table += rows
         pad = -len(hd.data) % 16
         parts.append(hd.data + bytes(pad))
         nbytes += len(hd.data) + pad
@@ -3425,14 +3558,16 @@ def png_batch(files) -> PngBatch:
         return t.pin_memory() if pin and t.numel() else t
     data = torch.frombuffer(bytearray(b''.join(parts) or bytes(16)), dtype=torch.uint8)
     return PngBatch(data=host(data), nbytes=nbytes, images=host(torch.tensor(images, dtype=torch.int32)), sizes=sizes,
-                    n=len(files), raw_stride=stride, raw_bytes=raw)
+                    n=len(files), raw_stride=stride, raw_bytes=raw,
+                    bands=None if bands is None else host(torch.tensor(table, dtype=torch.int32).reshape(-1, PNG_BAND_INTS)))
 
 
 def check_png_status(status) -> None:
     """reads the status table of ops.png_decode_u8 back (this waits for the device) and raises for the first damaged file"""
     for i, s in enumerate(status.detach().cpu().tolist()):
         if s != 0:
-            raise ValueError('png_decode: file %d is damaged (status %d: %s)' % (i, s, PNG_STATUS.get(s, 'unknown')))
+            raise ValueError('png_decode: file %d is damaged (status %d: %s)'
+                             % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s, 'unknown')))
 
 
 # ---- PNG files out (DESIGN.md "PNG files out") ---------------------------------------------------------------------------------
@@ -3702,7 +3837,7 @@ def png_filter_rows_host(frame, filters='adaptive'):
     return rows
 
 
-def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', return_bands: bool = False):
+def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', return_bands: bool = False, index: bool = False):
     """The definition of ops.png_encode_u8, integers only: frame uint8 (H, W) / (H, W, 1) grey, (H, W, 3) RGB or (H, W, 4) RGBA
     -> a complete PNG file: signature, IHDR, one IDAT, IEND.  Rows [k R, min(H, (k + 1) R)) with their filter bytes
     (png_filter_rows_host) are band k, R = band_rows, coded on its own by _png_encode_band: tokens by _png_band_tokens, both
@@ -3710,8 +3845,12 @@ def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', retur
     trailing zeros, HDIST = 0 with one distance code of one bit, canonical codes, then an empty stored block (000 or, on the
     last band, 100; zeros to the byte; 00 00 FF FF).  So every band starts and ends on a byte and refers to no byte outside
     itself.  The stream is 78 01, the bands, the Adler-32 of the filtered rows.  return_bands=True: (file, [(begin, end)] of
-    every band in the stream, whose first band begins at 2, the filter type of every row)."""
+    every band in the stream, whose first band begins at 2, the filter type of every row).  index=True (the definition of
+    ops.png_encode_u8(index=True)): the file carries the bands' offsets in a baND chunk (_png_band_chunk, with R =
+    min(band_rows, H)) between IHDR and IDAT, for a decoder that takes the bands apart; every other byte is the same."""
     import zlib
+    if not isinstance(index, bool):
+        raise ValueError('png_encode_banded_host: index is True or False, got %r' % (index,))
     R = check_png_band_rows(band_rows)
     rows = png_filter_rows_host(frame, filters)
     H, bpp = rows.shape[0], _png_frame(frame, 'png_encode_banded_host')[1]
@@ -3722,11 +3861,12 @@ def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', retur
         bands.append((len(stream), len(stream) + len(part)))
         stream += part
     stream += zlib.adler32(rows.tobytes()).to_bytes(4, 'big')
-    data = png_wrap(H, W, {1: 0, 3: 2, 4: 6}[bpp], bytes(stream))
+    extra = _png_band_chunk(min(R, H), [b for b, _ in bands] + [bands[-1][1]]) if index else b''
+    data = png_wrap(H, W, {1: 0, 3: 2, 4: 6}[bpp], bytes(stream), extra=extra)
     return (data, bands, rows[:, 0].tolist()) if return_bands else data
 
 
-def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive') -> list:
+def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive', index: bool = False) -> list:
     """the files of a batch: frames uint8 (n, H, W), (n, H, W, 1 | 3 | 4) or clips (B, T, H, W, C) -> [bytes], one
     png_encode_banded_host each"""
     import numpy as np
@@ -3735,10 +3875,10 @@ def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive') -> li
         px = px.reshape((-1,) + px.shape[2:])
     if px.ndim not in (3, 4):
         raise ValueError('png_encode_files_host: frames (n, H, W), (n, H, W, C) or (B, T, H, W, C), got %s' % (px.shape,))
-    return [png_encode_banded_host(f, band_rows, filters) for f in px]
+    return [png_encode_banded_host(f, band_rows, filters, index=index) for f in px]
 
 
-def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16) -> int:
+def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16, index: bool = False) -> int:
     """The bytes one file of png_encode_banded_host needs at the most.  A band of nb bytes (rows (1 + W bpp)) is at most nb
     tokens and the end-of-block.  The code `256 literals of 9 bits, the end-of-block and the 29 length symbols of 6` is a
     prefix code (256 / 512 + 30 / 64 < 1), and under it a literal costs 9 bits and a match 6 + 5 extra + 1 distance = 12 for
@@ -3750,9 +3890,9 @@ def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16) -> int:
     Nothing rests on it but the default capacity: the kernels check the capacity themselves and report status 1.  The block
     header is at most PNG_BAND_HEADER_BITS = 17
     + 19 * 3 + 287 * 7 bits.  The empty stored block is 3 bits, the pad to the byte and 4 bytes.  Bands of a file: ceil(H /
-    R).  The container is 57 + 6 bytes."""
+    R).  The container is 57 + 6 bytes; index=True adds the baND chunk's png_band_chunk_bytes(H, R)."""
     H, W, bpp, R = int(H), int(W), int(bpp), check_png_band_rows(band_rows, 'png_encoded_bound')
-    stride, total = 1 + W * bpp, PNG_CONTAINER_BYTES
+    stride, total = 1 + W * bpp, PNG_CONTAINER_BYTES + (png_band_chunk_bytes(H, R) if index else 0)
     for r0 in range(0, H, R):
         nb = (min(H, r0 + R) - r0) * stride
         total += -(-(PNG_BAND_HEADER_BITS + 9 * nb + 15 + 3) // 8) + 4
@@ -3762,5 +3902,6 @@ def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16) -> int:
 class PngFiles(_EncodedFiles):
     """What ops.png_encode_u8 hands back, on the device, with JpegFiles' semantics: data uint8 (capacity,): the files end to
     end | offsets int64 (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, 1 as
-    PNG_ENCODE_STATUS words it (files() hands b'' over for it with check=False).  geometry: H, W, bpp, band_rows, filters."""
+    PNG_ENCODE_STATUS words it (files() hands b'' over for it with check=False).  geometry: H, W, bpp, band_rows, filters,
+    index."""
     _name, _who, _status, _empty = 'PngFiles', 'png_encode', PNG_ENCODE_STATUS, (1,)

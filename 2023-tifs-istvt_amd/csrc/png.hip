@@ -8,11 +8,9 @@
 #include "common.h"
 #include "istvt_hip.h"
 #include "png_inflate.h"
+#include "png_unfilter.h"
 
 namespace {
-
-constexpr int PG_H = 0, PG_W = 1, PG_TYPE = 2, PG_BPP = 3, PG_BEGIN = 4, PG_END = 5;
-constexpr int PG_FILTER = 6;               // the status of a filter byte above 4
 
 __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restrict__ bytes, const int* __restrict__ images,
                                                          uint8_t* __restrict__ scratch, long raw_stride, int* __restrict__ status) {
@@ -24,108 +22,11 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const uint8_t* __restri
     if (lane == 0) status[f] = st;
 }
 
-__device__ __forceinline__ int png_paeth(int a, int b, int c) {
-    const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-
-// n zero bytes at p, by the wave: single bytes up to the first multiple of 4 and behind the last, dwords between
-__device__ __forceinline__ void png_zero(uint8_t* p, long n, int lane) {
-    long head = (long)((4 - (reinterpret_cast<uintptr_t>(p) & 3)) & 3);
-    if (head > n) head = n;
-    const long words = (n - head) >> 2, tail = head + 4 * words;
-    if (lane < head) p[lane] = 0;
-    uint32_t* q = reinterpret_cast<uint32_t*>(p + head);
-    for (long i = lane; i < words; i += 64) q[i] = 0u;
-    if (tail + lane < n) p[tail + lane] = 0;
-}
-
-// Lane l of band k holds row 64 k + l and reconstructs pixel x = t - l at step t: its `b` is what lane l - 1 made one step
-// earlier (one cross-lane move), its `c` the `b` of its last step, its `a` its own last pixel; a pixel is one dword, bpp <= 4.
-// The last row of a band is written back over its filtered bytes, all bpp channels, and lane 0 of the next band reads it there.
 __global__ __launch_bounds__(64) void png_unfilter_kernel(const int* __restrict__ images, uint8_t* scratch, long raw_stride,
                                                           uint8_t* __restrict__ out, int Hc, int Wc, int* __restrict__ sizes,
                                                           int* status) {
     const int f = blockIdx.x, lane = threadIdx.x;
-    const int* im = images + (long)f * ISTVT_PNG_IMAGE_INTS;
-    const int H = im[PG_H], W = im[PG_W], bpp = im[PG_BPP];
-    const long stride = 1 + (long)W * bpp;
-    uint8_t* raw = scratch + (long)f * raw_stride;
-    uint8_t* canvas = out + (long)f * Hc * Wc * 3;
-    int st = status[f];
-    if (st == 0) {
-        int bad = 0;
-        for (int r = lane; r < H; r += 64) bad |= raw[r * stride] > 4;
-        if (__any(bad)) st = PG_FILTER;
-    }
-    if (lane == 0) {
-        status[f] = st;
-        sizes[2 * f] = H;
-        sizes[2 * f + 1] = W;
-    }
-    if (st != 0) {
-        png_zero(canvas, (long)Hc * Wc * 3, lane);
-        return;
-    }
-    const int right = (Wc - W) * 3;                              // the margin beside the image, row by row; then the rows below
-    if (right > 0)
-        for (int y = 0; y < H; ++y) png_zero(canvas + ((long)y * Wc + W) * 3, right, lane);
-    png_zero(canvas + (long)H * Wc * 3, (long)(Hc - H) * Wc * 3, lane);
-    for (int band = 0; band * 64 < H; ++band) {
-        const int r = band * 64 + lane;
-        const bool active = r < H;
-        const uint8_t* row = raw + (active ? r : 0) * stride;
-        const int ft = active ? row[0] : 0;
-        const uint8_t* above = row - stride + 1;                 // read by lane 0 of the bands after the first
-        const bool keep = lane == 63 && r + 1 < H;
-        uint32_t last = 0, c = 0;
-        for (int t = 0; t < W + 63; ++t) {
-            const int x = t - lane;
-            uint32_t b = __shfl_up(last, 1);
-            if (!active || x < 0 || x >= W) continue;
-            const uint8_t* src = row + 1 + (long)x * bpp;
-            if (lane == 0) {
-                b = 0;
-                if (band > 0)
-                    for (int k = 0; k < bpp; ++k) b |= (uint32_t)above[(long)x * bpp + k] << (8 * k);
-            }
-            const uint32_t a = x > 0 ? last : 0;
-            if (x == 0) c = 0;
-            uint32_t px = 0;
-            for (int k = 0; k < bpp; ++k) {
-                const int v = src[k], ak = (a >> (8 * k)) & 255, bk = (b >> (8 * k)) & 255, ck = (c >> (8 * k)) & 255;
-                const int pred = ft == 0 ? 0 : ft == 1 ? ak : ft == 2 ? bk : ft == 3 ? (ak + bk) >> 1 : png_paeth(ak, bk, ck);
-                px |= (uint32_t)((v + pred) & 255) << (8 * k);
-            }
-            last = px;
-            c = b;
-            uint8_t* dst = canvas + ((long)r * Wc + x) * 3;
-            if (bpp == 1) {
-                dst[0] = dst[1] = dst[2] = (uint8_t)px;
-            } else {
-                dst[0] = (uint8_t)px;
-                dst[1] = (uint8_t)(px >> 8);
-                dst[2] = (uint8_t)(px >> 16);
-            }
-            if (keep)
-                for (int k = 0; k < bpp; ++k) raw[r * stride + 1 + (long)x * bpp + k] = (uint8_t)(px >> (8 * k));
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                         // lane 63's row has landed before lane 0 reads it
-    }
-}
-
-// the host copy of the image table against the byte range, the canvas and the scratch
-bool png_decode_check(const istvt_jpeg_decode_args* a, long raw_stride) {
-    for (int i = 0; i < a->n; ++i) {
-        const int* im = a->images_host + (long)i * ISTVT_PNG_IMAGE_INTS;
-        const int H = im[PG_H], W = im[PG_W], ct = im[PG_TYPE], bpp = im[PG_BPP];
-        if (H < 1 || W < 1 || H > 16384 || W > 16384 || H > a->Hc || W > a->Wc) return false;
-        if (!((ct == 0 && bpp == 1) || (ct == 2 && bpp == 3) || (ct == 6 && bpp == 4))) return false;
-        if (im[PG_BEGIN] < 0 || (im[PG_BEGIN] & 15) || im[PG_BEGIN] > im[PG_END] || im[PG_END] > a->nbytes) return false;
-        if ((long)H * (1 + (long)W * bpp) > raw_stride) return false;
-    }
-    return true;
+    png_unfilter_file<false>(images, nullptr, scratch, raw_stride, out, Hc, Wc, sizes, status, f, lane);
 }
 
 }  // namespace
@@ -133,17 +34,9 @@ bool png_decode_check(const istvt_jpeg_decode_args* a, long raw_stride) {
 // A batch of PNG files, packed by clips.png_batch, decoded to uint8 RGB on a canvas out [n][Hc][Wc][3]; include/istvt_hip.h
 // describes the arguments.  Two launches, no synchronisation, no global state.
 extern "C" int istvt_png_decode_u8(const istvt_jpeg_decode_args* a, int raw_stride) {
-    if (!a || a->n <= 0 || a->nbytes < 0 || a->nbytes > ISTVT_PNG_MAX_BYTES || raw_stride < 16 || (raw_stride & 15)) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->images_host || !a->scratch || !a->out || !a->sizes || !a->status) return ISTVT_ERR_SHAPE;
-    if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
-    if (!png_decode_check(a, raw_stride)) return ISTVT_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->bytes) & 15) ||
-        a->scratch_bytes < (long)a->n * raw_stride)
-        return ISTVT_ERR_SHAPE;
+    if (!png_decode_args_ok(a, raw_stride) || a->scratch_bytes < (long)a->n * raw_stride) return ISTVT_ERR_SHAPE;
     const uint8_t* src = (const uint8_t*)a->bytes;
     uint8_t* out = (uint8_t*)a->out;
-    const long nout = (long)a->n * a->Hc * a->Wc * 3;
-    if (out < src + a->nbytes && src < out + nout) return ISTVT_ERR_SHAPE;
     hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)a->n), dim3(64), 0, a->stream, src, a->images, (uint8_t*)a->scratch,
                        (long)raw_stride, a->status);
     int rc = istvt_check_launch();

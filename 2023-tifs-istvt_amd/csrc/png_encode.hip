@@ -4,6 +4,8 @@
 // (csrc/png_deflate.h); png_prefix_kernel, one workgroup, places bands in files and files in data; png_store_kernel, the same
 // waves, codes the bands; png_container_kernel, one workgroup per file, writes the chunks around the stream with the Adler-32 and
 // the CRC-32s.  No synchronisation with the host, no global atomics, nothing allocated, nothing that has to be zeroed.
+// istvt_png_encode_indexed_u8 is the same four launches with `extra` > 0: the bytes of the baND chunk that every file then
+// carries between IHDR and IDAT (clips._png_band_chunk), which the container kernel writes from the bands' offsets.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -14,7 +16,8 @@
 namespace {
 
 constexpr int PE_ADAPTIVE = 5;
-constexpr int PE_STREAM = 41;              // signature 8, IHDR 25, the IDAT's length and type 8: where the zlib stream begins
+constexpr int PE_IHDR_END = 33;            // signature 8, IHDR 25: where the band index stands, if there is one
+constexpr int PE_STREAM = 41;              // + the IDAT's length and type 8: where the zlib stream begins (+ the index's bytes)
 constexpr int PE_CONTAINER = 57 + 6;       // + the IDAT's CRC 4 and IEND 12; the zlib header 2 and the Adler-32 4
 
 __device__ __forceinline__ int pe_paeth(int a, int b, int c) {
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(64) void png_filter_count_kernel(const uint8_t* __r
 
 // bands in their file's stream, files in data; 256 files at a time
 __global__ __launch_bounds__(256) void png_prefix_kernel(int* __restrict__ rows, int bands, int n, long capacity, long* __restrict__ offsets,
-                                                         int* __restrict__ status) {
+                                                         int* __restrict__ status, int extra) {
     __shared__ long sizes[256];
     __shared__ long carry;
     const int tid = threadIdx.x;
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(256) void png_prefix_kernel(int* __restrict__ rows,
                 meta[PD_META_OFFSET] = (int)at;
                 at += meta[PD_META_BYTES];
             }
-            sizes[tid] = at + 4 + (PE_CONTAINER - 6);
+            sizes[tid] = at + 4 + (PE_CONTAINER - 6) + extra;
         }
         __syncthreads();
         if (tid == 0) {
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(256) void png_prefix_kernel(int* __restrict__ rows,
 
 __global__ __launch_bounds__(64) void png_store_kernel(const uint8_t* __restrict__ scratch, long raw_stride, const int* __restrict__ rows,
                                                        int H, int W, int bpp, int band_rows, int bands, uint8_t* data,
-                                                       const long* __restrict__ offsets, const int* __restrict__ status) {
+                                                       const long* __restrict__ offsets, const int* __restrict__ status, int extra) {
     __shared__ PdStage s;
     const int f = blockIdx.x / bands, k = blockIdx.x % bands, lane = threadIdx.x;
     if (status[f] != 0) return;
@@ -138,18 +141,51 @@ __global__ __launch_bounds__(64) void png_store_kernel(const uint8_t* __restrict
     const long stride = 1 + (long)W * bpp;
     const int r0 = k * band_rows, r1 = min(H, r0 + band_rows);
     const int* meta = row + PD_ROW_META;
-    uint8_t* dst = data + offsets[f] + PE_STREAM + meta[PD_META_OFFSET];
+    uint8_t* dst = data + offsets[f] + PE_STREAM + extra + meta[PD_META_OFFSET];
     pd_store_band(scratch + (long)f * raw_stride + (long)r0 * stride, (int)((r1 - r0) * stride), k == bands - 1 ? 1 : 0, s.words,
                   reinterpret_cast<const uint32_t*>(row + PD_ROW_HEADER), meta[PD_META_HEADER_BITS], dst, s.stage, lane);
 }
 
-// byte i of what the IDAT's CRC-32 covers lies at file[37 + i]; the type, the zlib header and the Adler-32 are this kernel's
-// own stores and are taken from registers.  One workgroup of PE_CRC_THREADS per file: a contiguous slice per thread, the first
-// wave folds them, eight neighbours per lane and then the 64 lanes, with x^(8 length) mod P.
+// The CRC-32 of `total` bytes, byte(i) the i-th, by the PE_CRC_THREADS threads of a workgroup together: a contiguous slice per
+// thread, equal lengths but for the last; the first wave folds them, eight neighbours per lane and then the 64 lanes, with
+// x^(8 length) mod P.  -> the CRC in the threads of the first wave; part is free again behind the call.
 constexpr int PE_CRC_THREADS = 512;
 
-__global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int* __restrict__ rows, int H, int W, int bpp, int bands, uint8_t* data,
-                                                           const long* __restrict__ offsets, const int* __restrict__ status) {
+template <class Byte>
+__device__ __forceinline__ uint32_t pe_crc_fold(long total, Byte byte, const uint32_t* table, uint32_t* part, int lane) {
+    const long slice = (total + PE_CRC_THREADS - 1) / PE_CRC_THREADS;
+    const long lo = min(total, lane * slice), hi = min(total, lo + slice);
+    uint32_t crc = 0xffffffffu;
+    for (long i = lo; i < hi; ++i) crc = table[(crc ^ byte(i)) & 255] ^ (crc >> 8);
+    part[lane] = hi > lo ? ~crc : 0u;
+    __syncthreads();
+    uint32_t all = 0;
+    if (lane < 64) {
+        constexpr int group = PE_CRC_THREADS / 64;
+        const uint32_t full = pd_crc_shift((uint64_t)slice);
+        uint32_t mine_crc = 0;
+        long mine_len = 0;
+        for (int j = 0; j < group; ++j) {                         // the slices of threads [group lane, group (lane + 1))
+            const int t = group * lane + j;
+            const long tlo = min(total, t * slice), len = min(total, tlo + slice) - tlo;
+            mine_crc = j == 0 ? part[t] : pd_crc_combine(mine_crc, part[t], len == slice ? full : pd_crc_shift((uint64_t)len));
+            mine_len += len;
+        }
+        const uint32_t mine = pd_crc_shift((uint64_t)mine_len);
+        all = __shfl(mine_crc, 0);
+        for (int l = 1; l < 64; ++l) all = pd_crc_combine(all, __shfl(mine_crc, l), __shfl(mine, l));
+    }
+    __syncthreads();
+    return all;
+}
+
+// Byte i of what the IDAT's CRC-32 covers lies at file[37 + extra + i]; the type, the zlib header and the Adler-32 are this
+// kernel's own stores and are taken from registers.  One workgroup of PE_CRC_THREADS per file.  extra > 0: the band index,
+// `extra` bytes at file[33]: words of 4 bytes, most significant first -- the body's length, 'baND', R, the band count, the
+// bands' offsets in the stream (the scratch rows have them), the stream's length - 4, the CRC-32 of all but the first.
+__global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int* __restrict__ rows, int H, int W, int bpp, int band_rows,
+                                                                       int bands, uint8_t* data, const long* __restrict__ offsets,
+                                                                       const int* __restrict__ status, int extra) {
     __shared__ uint32_t table[256];
     __shared__ uint8_t head[48];
     __shared__ uint32_t part[PE_CRC_THREADS];
@@ -158,7 +194,7 @@ __global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int
     for (int i = lane; i < 256; i += PE_CRC_THREADS) table[i] = pd_crc_entry((uint32_t)i);
     uint8_t* file = data + offsets[f];
     const long size = offsets[f + 1] - offsets[f];
-    const long stream = size - (PE_CONTAINER - 6);                // the IDAT's body
+    const long stream = size - (PE_CONTAINER - 6) - extra;        // the IDAT's body
     uint32_t A = 1, B = 0;
     for (int k = 0; k < bands; ++k) {                             // uniform: every lane holds the sum
         const int* meta = rows + ((long)f * bands + k) * PD_ROW_INTS + PD_ROW_META;
@@ -184,38 +220,33 @@ __global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int
         for (int i = 0; i < 14; ++i) head[29 + i] = rest[i];
     }
     __syncthreads();
-    if (lane < 43) file[lane] = head[lane];
-    // the CRC-32 of type + body: a contiguous slice per thread, equal lengths but for the last
+    if (lane < PE_IHDR_END) file[lane] = head[lane];
+    if (lane >= PE_IHDR_END && lane < 43) file[extra + lane] = head[lane];
+    if (extra > 0) {
+        // word j of the chunk, j = 0 .. bands + 4; the CRC-32 covers words 1 .. bands + 4 and is word bands + 5
+        const auto word = [&](int j) -> uint32_t {
+            if (j == 0) return (uint32_t)(extra - 12);
+            if (j == 1) return 0x62614e44u;                       // 'baND'
+            if (j == 2) return (uint32_t)band_rows;
+            if (j == 3) return (uint32_t)bands;
+            if (j - 4 < bands) return (uint32_t)rows[((long)f * bands + (j - 4)) * PD_ROW_INTS + PD_ROW_META + PD_META_OFFSET];
+            return (uint32_t)(stream - 4);
+        };
+        uint8_t* chunk = file + PE_IHDR_END;
+        for (int j = lane; j < bands + 5; j += PE_CRC_THREADS) {
+            const uint32_t v = word(j);
+            chunk[4 * j] = (uint8_t)(v >> 24), chunk[4 * j + 1] = (uint8_t)(v >> 16), chunk[4 * j + 2] = (uint8_t)(v >> 8), chunk[4 * j + 3] = (uint8_t)v;
+        }
+        const uint32_t crc = pe_crc_fold(4L * (bands + 4), [&](long i) -> uint32_t { return (word(1 + (int)(i >> 2)) >> (8 * (3 - (i & 3)))) & 255u; },
+                                         table, part, lane);
+        if (lane < 4) chunk[4 * (bands + 5) + lane] = (uint8_t)(crc >> (8 * (3 - lane)));
+    }
+    // the CRC-32 of type + body
     const long total = 4 + stream;
-    const long slice = (total + PE_CRC_THREADS - 1) / PE_CRC_THREADS;
-    const long lo = min(total, lane * slice), hi = min(total, lo + slice);
-    uint32_t crc = 0xffffffffu;
-    for (long i = lo; i < hi; ++i) {
-        uint32_t b;
-        if (i < 6)
-            b = head[37 + i];
-        else if (i >= total - 4)
-            b = (adler >> (8 * (total - 1 - i))) & 255u;
-        else
-            b = file[37 + i];
-        crc = table[(crc ^ b) & 255] ^ (crc >> 8);
-    }
-    part[lane] = hi > lo ? ~crc : 0u;
-    __syncthreads();
-    if (lane >= 64) return;
-    constexpr int group = PE_CRC_THREADS / 64;
-    const uint32_t full = pd_crc_shift((uint64_t)slice);
-    uint32_t mine_crc = 0;
-    long mine_len = 0;
-    for (int j = 0; j < group; ++j) {                             // the slices of threads [group lane, group (lane + 1))
-        const int t = group * lane + j;
-        const long tlo = min(total, t * slice), len = min(total, tlo + slice) - tlo;
-        mine_crc = j == 0 ? part[t] : pd_crc_combine(mine_crc, part[t], len == slice ? full : pd_crc_shift((uint64_t)len));
-        mine_len += len;
-    }
-    const uint32_t mine = pd_crc_shift((uint64_t)mine_len);
-    uint32_t all = __shfl(mine_crc, 0);
-    for (int l = 1; l < 64; ++l) all = pd_crc_combine(all, __shfl(mine_crc, l), __shfl(mine, l));
+    const uint8_t* body = file + 37 + extra;
+    const uint32_t all = pe_crc_fold(total, [&](long i) -> uint32_t {
+        return i < 6 ? head[37 + i] : i >= total - 4 ? (adler >> (8 * (total - 1 - i))) & 255u : body[i];
+    }, table, part, lane);
     if (lane < 20) {
         const uint8_t tail[20] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler,
                                   (uint8_t)(all >> 24), (uint8_t)(all >> 16), (uint8_t)(all >> 8), (uint8_t)all,
@@ -224,10 +255,8 @@ __global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int
     }
 }
 
-}  // namespace
-
-// A batch of frames -> PNG files; include/istvt_hip.h describes the arguments and the scratch.
-extern "C" int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride) {
+// the checks and the four launches of both entries; extra: the bytes of a file's band index, 0 for none
+int pe_encode(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride, bool index) {
     if (!a || a->n <= 0 || a->H < 1 || a->W < 1 || a->H > 16384 || a->W > 16384) return ISTVT_ERR_SHAPE;
     if ((bpp != 1 && bpp != 3 && bpp != 4) || band_rows < 1 || filter < 0 || filter > PE_ADAPTIVE) return ISTVT_ERR_SHAPE;
     if (!a->frames || !a->scratch || !a->data || !a->offsets || !a->status || a->capacity < 1) return ISTVT_ERR_SHAPE;
@@ -235,6 +264,7 @@ extern "C" int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int
     if (a->total < pixels || raw_stride < raw || (raw_stride & 15)) return ISTVT_ERR_SHAPE;
     const int R = band_rows < a->H ? band_rows : a->H;
     const int bands = (a->H + R - 1) / R;
+    const int extra = index ? 12 + 8 + 4 * (bands + 1) : 0;
     const long waves = (long)a->n * bands;
     if (waves > 0x7fffffffL) return ISTVT_ERR_SHAPE;
     const long need = (long)a->n * raw_stride + waves * PD_ROW_INTS * (long)sizeof(int);
@@ -248,14 +278,26 @@ extern "C" int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int
                        scratch, (long)raw_stride, rows);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(png_prefix_kernel, dim3(1), dim3(256), 0, a->stream, rows, bands, a->n, a->capacity, a->offsets, a->status);
+    hipLaunchKernelGGL(png_prefix_kernel, dim3(1), dim3(256), 0, a->stream, rows, bands, a->n, a->capacity, a->offsets, a->status, extra);
     rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(png_store_kernel, dim3((unsigned)waves), dim3(64), 0, a->stream, (const uint8_t*)scratch, (long)raw_stride,
-                       (const int*)rows, a->H, a->W, bpp, R, bands, data, (const long*)a->offsets, (const int*)a->status);
+                       (const int*)rows, a->H, a->W, bpp, R, bands, data, (const long*)a->offsets, (const int*)a->status, extra);
     rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(png_container_kernel, dim3((unsigned)a->n), dim3(PE_CRC_THREADS), 0, a->stream, (const int*)rows, a->H, a->W, bpp, bands, data,
-                       (const long*)a->offsets, (const int*)a->status);
+    hipLaunchKernelGGL(png_container_kernel, dim3((unsigned)a->n), dim3(PE_CRC_THREADS), 0, a->stream, (const int*)rows, a->H, a->W, bpp, R,
+                       bands, data, (const long*)a->offsets, (const int*)a->status, extra);
     return istvt_check_launch();
+}
+
+}  // namespace
+
+// A batch of frames -> PNG files; include/istvt_hip.h describes the arguments and the scratch.
+extern "C" int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride) {
+    return pe_encode(a, bpp, band_rows, filter, raw_stride, false);
+}
+
+// ... and every file with its band index
+extern "C" int istvt_png_encode_indexed_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride) {
+    return pe_encode(a, bpp, band_rows, filter, raw_stride, true);
 }

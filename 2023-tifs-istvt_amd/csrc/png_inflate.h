@@ -11,6 +11,12 @@
 // Status (the first fault in stream order decides; clips.PNG_STATUS words them): 0 fine | 1 the stream ends early | 2 a
 // reserved block type, or LEN != ~NLEN | 3 code lengths over-subscribed or incomplete, or a code no table holds | 4 a distance
 // beyond the bytes produced | 5 more, or fewer, bytes than expected.  A stored block checks 2, then 5, then 1.
+//
+// The band mode (pi_inflate<true>, clips.png_decode_bands_host is its definition): [begin, end) is one band of a file whose
+// index names its bands, begin any byte, out the band's first output byte and expected its rows' bytes -- so the window, the
+// count and the fence bookkeeping are the band's own with no further code.  A band that is not its file's last (middle) gives
+// status 7 for a block header with BFINAL set, before the block's type is looked at, and stops behind a stored block that ends
+// at byte `end`; the last band stops at its BFINAL block.  Both are tests per block: the symbol loop is the sequential one.
 #pragma once
 #include <stdint.h>
 
@@ -34,6 +40,7 @@
 #define PI_CODES 3
 #define PI_DISTANCE 4
 #define PI_LENGTH 5
+#define PI_BAND 7                          // 6 is the unfilter's
 
 #define PI_LIT_FAST 10                     // bits of the literal/length lookup; longer codes take the limit scan
 #define PI_DIST_FAST 8
@@ -55,8 +62,8 @@ struct PiTables {
 };
 
 struct PiBits {
-    const uint8_t* data;                   // the base the byte offsets count from; 4-byte aligned
-    int begin, p, end;                     // bytes [begin, end) may be read, begin is a multiple of 4; a batch holds < 2^31
+    const uint8_t* data;                   // the base the byte offsets count from; 4-byte aligned on the device
+    int begin, p, end;                     // bytes [begin, end) may be read (a band begins at any byte); a batch holds < 2^31
     uint64_t buf;
     int cnt;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -87,7 +94,9 @@ PI_HD uint32_t pi_word(PiBits& r) {
     }
     return (uint32_t)__builtin_amdgcn_readlane((int)r.chunk, __builtin_amdgcn_readfirstlane((int)((r.p >> 2) & 63)));
 #else
-    return *reinterpret_cast<const uint32_t*>(r.data + r.p);
+    uint32_t w;                            // the host's base need not be aligned: a checker gives a band a block of its own
+    __builtin_memcpy(&w, r.data + r.p, 4);
+    return w;
 #endif
 }
 
@@ -336,8 +345,10 @@ PI_HD int pi_pair(PiBits& r, PiOut& o, const PiTables* T, int s, int lane) {
 }
 
 // One stream: bytes [begin, end) of data -> out[0 .. expected), by the PI_LANES lanes of the caller together.  Nothing outside
-// out[0, expected) is written and no byte outside [begin, end) is read.  -> the status
-PI_HD int pi_inflate(const uint8_t* data, int begin, int end, uint8_t* out, int expected, PiTables* T, int lane) {
+// out[0, expected) is written and no byte outside [begin, end) is read.  -> the status.  BAND: the band mode above; middle is
+// read with BAND only.  pi_inflate(...) without either is the sequential decoder.
+template <bool BAND = false>
+PI_HD int pi_inflate(const uint8_t* data, int begin, int end, uint8_t* out, int expected, PiTables* T, int lane, bool middle = false) {
     PiBits r;
     r.data = data;
     r.begin = begin;
@@ -362,6 +373,8 @@ PI_HD int pi_inflate(const uint8_t* data, int begin, int end, uint8_t* out, int 
         pi_refill(r);
         if (r.cnt < 3) return PI_EARLY;
         const int last = (int)pi_take(r, 1), type = (int)pi_take(r, 2);
+        if constexpr (BAND)
+            if (middle && last) return PI_BAND;
         if (type == 3) return PI_BLOCK;
         if (type == 0) {
             pi_take(r, r.cnt & 7);
@@ -382,6 +395,8 @@ PI_HD int pi_inflate(const uint8_t* data, int begin, int end, uint8_t* out, int 
             for (int i = lane; i < rest; i += PI_LANES) out[o.produced + done + i] = data[r.p + i];
             r.p += rest;
             o.produced += (int)len;
+            if constexpr (BAND)
+                if (middle && r.p - (r.cnt >> 3) == end) break;
         } else {
             int hlit = 288, hdist = 32;
             if (type == 1) {

@@ -489,7 +489,7 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     return out, sizes, status
 
 
-def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None):
+def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bool = False, buffers=None, bands=None):
     """PNG files (clips.py): a batch of 8-bit grey, RGB or RGBA PNG files goes to the device as its DEFLATE streams ->
     (frames, sizes, status): frames uint8 [n, Hc, Wc, 3], image i in the top left H_i x W_i of its canvas and 0 elsewhere
     (grey replicated, alpha dropped), the bytes of clips.png_decode_host; sizes int32 [n, 2] = (H, W) and status int32 [n]
@@ -499,9 +499,16 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
     checked=True a clips.PngBatch the caller has packed already; its tensors are uploaded once per device and kept on it.
     canvas = (Hc, Wc) defaults to the largest H and W of the batch.  `out` (uint8, contiguous, of the result's shape, no
     overlap with the uploaded bytes) is written when given.  buffers = (scratch uint8 of at least batch.scratch_bytes bytes
-    and 16-byte aligned, sizes, status): the caller's, to decode step after step without an allocation."""
+    and 16-byte aligned, sizes, status): the caller's, to decode step after step without an allocation.
+    bands='index' with a sequence of bytes packs it with clips.png_batch(bands='index'); a batch that carries bands, packed
+    here or by the caller, is decoded one wave per band of the files' baND chunks (istvt_png_decode_bands_u8, the bytes and
+    statuses of clips.png_decode_bands_host; status 7 is clips.PNG_BAND_STATUS's) and its scratch holds a status word per band
+    behind the filtered rows.  A PngBatch is decoded as it was packed: bands= given with one must agree with it."""
+    clips.check_png_bands(bands, 'png_decode_u8')
     if isinstance(batch, clips.PngBatch):
-        pass
+        if bands is not None and batch.bands is None:
+            raise ValueError("png_decode_u8: bands='index' with a clips.PngBatch that was packed without bands "
+                             "(clips.png_batch(files, bands='index') packs them)")
     elif checked:
         raise RuntimeError('png_decode_u8: checked=True takes a clips.PngBatch (clips.png_batch packs and validates the files)')
     else:
@@ -509,7 +516,7 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
             raise TypeError('png_decode_u8 expects a sequence of files (bytes) or a clips.PngBatch, got %s' % type(batch).__name__)
         if len(batch) == 0:
             raise RuntimeError('png_decode_u8: empty input (no files)')
-        batch = clips.png_batch(batch)
+        batch = clips.png_batch(batch, bands)
     need = batch.scratch_bytes
     if not torch.cuda.is_available():
         raise RuntimeError('istvt_amd: png_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
@@ -533,8 +540,22 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
         if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
                 or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
                 or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
+            if batch.bands is not None and torch.is_tensor(scratch) and n * batch.raw_stride <= scratch.numel() < need:
+                raise RuntimeError('png_decode_u8: a batch with bands needs a scratch of %d bytes: %d of filtered rows and a status '
+                                   'word for each of its %d bands, got %d' % (need, n * batch.raw_stride, batch.bands.shape[0],
+                                                                              scratch.numel()))
             raise RuntimeError('png_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
                                'status (%d,)), contiguous on %s' % (need, n, n, device))
+    if batch.bands is not None:
+        nband = int(batch.bands.shape[0])
+        args = _lib.JpegDecodeArgs(
+            bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
+            segments=dev.bands.data_ptr(), segments_host=batch.bands.data_ptr(), scratch=scratch.data_ptr(),
+            scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(),
+            n=n, nseg=nband, Hc=Hc, Wc=Wc)
+        with prof('png_decode_bands_u8', batch.nbytes + 2 * batch.raw_bytes + out.numel()):
+            _lib.check(_lib.lib().istvt_png_decode_bands_u8(ctypes.byref(args), batch.raw_stride), 'istvt_png_decode_bands_u8')
+        return out, sizes, status
     args = _lib.JpegDecodeArgs(
         bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
         scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
@@ -786,7 +807,8 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
     not all 4:2:0 or 4:4:4.  files may be a clips.JpegBank with `index` (jpeg_decode_indexed_u8): the places the index names
     are decoded and cut; without `boxes` each is cut whole through boxes made from the decoder's sizes on the device, and a
     place with status 4 or 5 comes out black.  A bank brings its own split (bank.split); split= is refused for it.  A
-    clips.PngBatch (clips.png_batch) is decoded by png_decode_u8 and cut the same way; split= and layouts= are refused for it."""
+    clips.PngBatch (clips.png_batch) is decoded by png_decode_u8 and cut the same way, by its bands where it carries them;
+    split= and layouts= are refused for it."""
     if isinstance(files, clips.JpegBank):
         if index is None:
             raise ValueError('decode_frames: a clips.JpegBank is decoded through index=')
@@ -936,16 +958,19 @@ _JPEG_ONLY = dict(quality=_NotGiven(90), subsampling=_NotGiven('420'), restart_i
 def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
                   quality=_JPEG_ONLY['quality'], subsampling=_JPEG_ONLY['subsampling'],
                   restart_interval=_JPEG_ONLY['restart_interval'], optimize=_JPEG_ONLY['optimize'], layout=_JPEG_ONLY['layout'],
-                  format: str = 'jpeg', band_rows=None, filters=None):
+                  format: str = 'jpeg', band_rows=None, filters=None, index=None):
     """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
     cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
     (jpeg_encode_u8; optimize=True: with their own Huffman tables; layout: one of clips.JPEG_LAYOUTS in the place of
     subsampling) -> a clips.JpegFiles, whose files() ops.decode_frames and clips.jpeg_batch take (with layouts='all' for '422'
     and 'grey').  format='png': the crops leave lossless, as PNG files (png_encode_u8 with band_rows and filters, 16 and
     'adaptive' where not given) -> a clips.PngFiles; the JPEG-only arguments (quality 90, subsampling '420', restart_interval
-    'row' and optimize False where not given) are then refused if given, whatever their value, and so is a layout."""
+    'row' and optimize False where not given) are then refused if given, whatever their value, and so is a layout.
+    index=True (format='png' only): the files carry their band index (png_encode_u8(index=True))."""
     if format not in ('jpeg', 'png'):
         raise ValueError("encode_frames: format is 'jpeg' or 'png', got %r" % (format,))
+    if index is not None and format != 'png':
+        raise ValueError("encode_frames: index= goes with format='png' (the band index of a PNG file); JPEG files have none")
     if format == 'png':
         given = dict(quality=quality, subsampling=subsampling, restart_interval=restart_interval, optimize=optimize, layout=layout)
         for name, default in _JPEG_ONLY.items():
@@ -961,8 +986,10 @@ def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transf
         band_rows = clips.check_png_band_rows(16 if band_rows is None else band_rows, 'png_encode_u8')
         filters = 'adaptive' if filters is None else filters
         clips.check_png_filters(filters, 'png_encode_u8')
+        if index is not None and not isinstance(index, bool):
+            raise ValueError('png_encode_u8: index is True or False, got %r' % (index,))
         crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
-        return png_encode_u8(crops, band_rows, filters)
+        return png_encode_u8(crops, band_rows, filters, index=False if index is None else index)
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     clips._jpeg_encode_layout(subsampling, layout, 'jpeg_encode_u8')
@@ -983,7 +1010,7 @@ def png_encode_scratch(n: int, H: int, W: int, bpp: int, band_rows: int):
 
 
 def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capacity: Optional[int] = None,
-                  buffers=None) -> 'clips.PngFiles':
+                  buffers=None, index: bool = False) -> 'clips.PngFiles':
     """PNG files out (clips.py): frames uint8 [n,H,W] or [n,H,W,1] (grey), [n,H,W,3] (RGB), [n,H,W,4] (RGBA) or clips
     [B,T,H,W,C], contiguous, on the device -> a clips.PngFiles on the device: the files of clips.png_encode_files_host end to
     end in `data`, byte for byte, with `offsets` and a `status` per file.  Lossless, for frame sets whose compression traces a
@@ -993,15 +1020,20 @@ def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capac
     clips.png_encoded_bound(H, W, bpp, band_rows); a file that does not fit gets status 1, nothing of it is written, and
     offsets[n] says what a retry needs.  buffers = (data uint8 (capacity,), scratch uint8 of at least png_encode_scratch(...)[1]
     bytes and 16-byte aligned, offsets int64 (n + 1,), status int32 (n,)): the caller's, to encode step after step without an
-    allocation; data may not overlap the frames.  Four launches, nothing synchronises."""
+    allocation; data may not overlap the frames.  Four launches, nothing synchronises.
+    index=True: every file carries its bands' offsets in a baND chunk between IHDR and IDAT, the bytes of
+    clips.png_encode_files_host(index=True), which ops.png_decode_u8(files, bands='index') decodes one wave per band; the
+    default capacity grows by the chunks (clips.png_encoded_bound(index=True))."""
     what = 'png_encode_u8'
+    if not isinstance(index, bool):
+        raise ValueError('%s: index is True or False, got %r' % (what, index))
     if torch.is_tensor(frames) and frames.dim() == 3:
         frames = frames.unsqueeze(-1)
     n, T, H, W = _rgb_source(what, frames, contiguous=True, on_device=False, channels=(1, 3, 4))
     bpp = int(frames.shape[-1])
     R = clips.check_png_band_rows(band_rows, what)
     mode = clips.check_png_filters(filters, what)
-    bound = n * clips.png_encoded_bound(H, W, bpp, R)
+    bound = n * clips.png_encoded_bound(H, W, bpp, R, index)
     if bound > clips.PNG_MAX_BYTES:
         raise ValueError('%s: the files of a batch hold at most %d bytes, %d frames of %d x %d x %d can need %d'
                          % (what, clips.PNG_MAX_BYTES, n, H, W, bpp, bound))
@@ -1031,10 +1063,11 @@ def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capac
     args = _lib.JpegEncodeArgs(
         frames=frames.data_ptr(), total=nbytes, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(),
         capacity=data.numel(), offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W)
-    with prof(what, nbytes + 3 * n * H * (1 + W * bpp)):          # the pixels; the filtered rows written once and read twice
-        _lib.check(_lib.lib().istvt_png_encode_u8(ctypes.byref(args), bpp, R, mode, raw_stride), 'istvt_png_encode_u8')
+    name = 'png_encode_indexed_u8' if index else what
+    with prof(name, nbytes + 3 * n * H * (1 + W * bpp)):          # the pixels; the filtered rows written once and read twice
+        _lib.check(getattr(_lib.lib(), 'istvt_' + name)(ctypes.byref(args), bpp, R, mode, raw_stride), 'istvt_' + name)
     files = clips.PngFiles(data, offsets, status)
-    files.geometry = SimpleNamespace(H=H, W=W, bpp=bpp, band_rows=R, filters=filters)
+    files.geometry = SimpleNamespace(H=H, W=W, bpp=bpp, band_rows=R, filters=filters, index=index)
     return files
 
 

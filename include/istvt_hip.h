@@ -537,6 +537,23 @@ int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a, int B, int
 #define ISTVT_PNG_IMAGE_INTS 8     /* a row of a PNG batch's images */
 #define ISTVT_PNG_MAX_BYTES 2147479552   /* nbytes at the most, 2^31 - 4096: byte offsets and a 256-byte window stay ints */
 int istvt_png_decode_u8(const istvt_jpeg_decode_args* a, int raw_stride);
+/* PNG files by their bands: the batch of istvt_png_decode_u8 packed with clips.png_batch(bands='index'), every file's stream
+ * taken apart where its `baND` chunk says a band begins (a file without a usable chunk is one band), one wave per band in
+ * place of one per file.  The bytes and statuses of clips.png_decode_bands_host: a band's window starts at its own first
+ * output byte, a band that is not its file's last stops behind the stored block that ends at its end byte, and status 7 says
+ * that the index disagrees with the stream (BFINAL in such a band); the file's status is that of its first failing band.
+ * The entry reads what istvt_png_decode_u8 reads, and
+ *   segments, segments_host, nseg   int32 [nseg][ISTVT_PNG_BAND_INTS]: file, first byte in `bytes`, end byte, first output byte
+ *                  within the file's filtered rows, output bytes; sorted by file, then by band
+ *   images[i][6], images[i][7]      file i's first row of segments and its count of them
+ *   scratch        n * raw_stride bytes of filtered rows as above, then int32 [nseg] band statuses; scratch_bytes >= n *
+ *                  raw_stride + 4 nseg.  Nothing else of it is written.
+ * Two launches (inflate, nseg workgroups of one wave; unfilter and colour, n workgroups of one wave: the rows of a file stay
+ * serial, since a band's first row may be filtered against the row above it), no synchronisation, nothing allocated.  -3
+ * before any launch as above, and where the host tables disagree: a band outside its file's [begin, end), rows that are not
+ * in file order, a file's output ranges that do not follow one another from 0 to H (1 + W bpp). */
+#define ISTVT_PNG_BAND_INTS 5      /* a row of a PNG batch's bands */
+int istvt_png_decode_bands_u8(const istvt_jpeg_decode_args* a, int raw_stride);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
@@ -632,6 +649,13 @@ int istvt_jpeg_bank_ingest(const istvt_jpeg_encode_args* a, int layout);
  * short scratch, data overlapping frames. */
 #define ISTVT_PNG_BAND_ROW_BYTES 1728
 int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride);
+/* PNG files out with their band index: istvt_png_encode_u8 in every argument, check, scratch row and launch, and every file
+ * carries between IHDR and IDAT the private ancillary chunk `baND` of 12 + 8 + 4 (nb + 1) bytes, nb = ceil(H / R): big-endian
+ * uint32 words R, nb and nb + 1 offsets into the zlib stream, off[0] = 2, off[nb] = the stream's length - 4; band k is stream
+ * bytes [off[k], off[k + 1]).  The bytes of clips.png_encode_banded_host(index=True).  The prefix kernel adds the chunk's
+ * length to every file; the container kernel writes it from the bands' offsets in the scratch rows and folds its CRC-32 as it
+ * folds the IDAT's.  Status 1 and offsets as above. */
+int istvt_png_encode_indexed_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

@@ -13,12 +13,30 @@ host     what a user does without it: PIL decodes the same files on the host, th
 jpeg     for context, ops.jpeg_decode_u8 on the same frames at quality 90, as tools/jpeg_decode_bench.py measures it
 upload   the bytes each route sends to the device
 large    one batch of 8 frames of 1080 x 1920 at level 6, the same legs without the JPEG one
+
+--bands [--against PARENT.so] [--bench-py K [--parent-tree DIR]]  instead of the above (DESIGN.md "PNG files by their bands"): the same frames, 256
+of 224 x 224 and 8 of 1080 x 1920, as our own files with their band index (ops.png_encode_u8(index=True), whose bytes the tests
+pin to the definition) at band_rows 8, 16 and 32.  Per size and band_rows, after the decoded frames are compared with the
+source pixels, in alternation:
+
+bands    ops.png_decode_u8 on the batch packed with bands='index': one wave per band; each kernel's share from a
+         torch.profiler trace of ten more calls
+seq      the same files packed without bands: one wave per file, this tree
+parent   with --against, the sequential entry of that library (the parent commit's build, made as tools/build_variant.sh makes
+         a variant: the same flags) on the same arguments: the speed-up is stated against this leg
+host     PIL decodes the same files on the host, the decoded bytes go up
+encode   ops.png_encode_u8 with and without the index on the same frames
+--bench-py K   bench.py at its defaults K times on this tree and, with --parent-tree DIR, on that checkout of the parent commit
+         (built: this tree's Python does not load a library without the new entry points), in alternation, each in a fresh
+         process (--only-bench-py: nothing else)
 """
 import argparse
 import io
+import ctypes
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -45,7 +63,7 @@ def fmt(s):
     return '%.3f ms (%.3f-%.3f)' % (s['median_ms'], s['min_ms'], s['max_ms'])
 
 
-def kernel_shares(call, reps=10):
+def kernel_shares(call, reps=10, frags=('png_inflate_kernel', 'png_unfilter_kernel')):
     """device time per kernel of `reps` calls -> {kernel name fragment: mean us per call}; a trace without the two kernels is
     an error, not a gap in the table"""
     from torch.profiler import ProfilerActivity, profile
@@ -55,12 +73,12 @@ def kernel_shares(call, reps=10):
         torch.cuda.synchronize()
     out = {}
     for ev in prof.key_averages():
-        for frag in ('png_inflate_kernel', 'png_unfilter_kernel'):
+        for frag in frags:
             if frag in ev.key:
                 total = getattr(ev, 'device_time_total', None) or getattr(ev, 'cuda_time_total', 0)
                 out[frag] = out.get(frag, 0.0) + total / reps
     if len(out) != 2:
-        raise SystemExit('the profiler trace holds no png_inflate_kernel / png_unfilter_kernel: %r' % (out,))
+        raise SystemExit('the profiler trace does not hold %s: %r' % (' / '.join(frags), out))
     return out
 
 
@@ -139,6 +157,136 @@ def measure(a, lines, res, key, src, n, levels, jpeg_quality, host_reps):
             % (jpeg_quality, fmt(stats(ts[k])), up * 1e-6))
 
 
+def bands_size(a, lines, res, key, src, n, other):
+    """--bands, one size: src uint8 [DISTINCT, H, W, 3] -> the legs in alternation for every band_rows"""
+    from istvt_amd import _lib
+    dev = torch.device('cuda', torch.cuda.current_device())
+    H, W = src.shape[1:3]
+    pick = [i % DISTINCT for i in range(n)]
+    src_dev = src.to(dev)
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+    staging = torch.empty((n, H, W, 3), dtype=torch.uint8).pin_memory()
+    view = staging.numpy()
+    res[key] = {'frames': n, 'H': H, 'W': W}
+    say(lines, '%s: %d frames of %d x %d' % (key, n, H, W))
+    for R in a.band_rows:
+        distinct = ops.png_encode_u8(src_dev, R, index=True).files()       # files() raises where a status is not 0
+        plain_bytes = sum(len(f) for f in ops.png_encode_u8(src_dev, R).files())
+        files = [distinct[i] for i in pick]
+        bb, bs = clips.png_batch(files, bands='index'), clips.png_batch(files)
+        bufs = {}
+        for name, b in (('bands', bb), ('seq', bs)):
+            b.on(dev)
+            bufs[name] = (torch.empty((b.scratch_bytes,), dtype=torch.uint8, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                          torch.empty((n,), dtype=torch.int32, device=dev))
+        calls = {'bands': lambda: ops.png_decode_u8(bb, out=out, checked=True, buffers=bufs['bands']),
+                 'seq': lambda: ops.png_decode_u8(bs, out=out, checked=True, buffers=bufs['seq'])}
+        if other is not None:
+            d, (scratch, sizes, status) = bs.on(dev), bufs['seq']
+            args = _lib.JpegDecodeArgs(
+                bytes=d.data.data_ptr(), nbytes=bs.nbytes, images=d.images.data_ptr(), images_host=bs.images.data_ptr(),
+                scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
+                status=status.data_ptr(), stream=torch.cuda.current_stream().cuda_stream, n=n, Hc=H, Wc=W)
+            calls['parent'] = lambda: (_lib.check(other.istvt_png_decode_u8(ctypes.byref(args), bs.raw_stride), 'parent istvt_png_decode_u8'),
+                                       (out, sizes, status))[1]
+        for name, fn in calls.items():                            # the frames before anything is timed
+            out.fill_(7)
+            got, _, status = fn()
+            clips.check_png_status(status)
+            if not torch.equal(got[:DISTINCT], src_dev) or not torch.equal(got[n - DISTINCT:].cpu(), src[torch.tensor(pick[n - DISTINCT:])]):
+                raise SystemExit('%s band_rows %d, %s: the decoded frames are not the source pixels' % (key, R, name))
+        ts = {k: [] for k in calls}
+        for r in range(a.warmup + a.reps):
+            order = list(calls.items())
+            for k, fn in order[r % len(order):] + order[:r % len(order)]:      # each leg first in turn
+                t = event_ms(fn)
+                if r >= a.warmup:
+                    ts[k].append(t)
+
+        def host_route():
+            for j, i in enumerate(pick):
+                view[j] = np.asarray(Image.open(io.BytesIO(distinct[i])).convert('RGB'))
+            return staging.to(dev, non_blocking=True)
+        th = [timed(host_route) for _ in range(1 + a.host_reps)][1:]
+        if not torch.equal(host_route()[:DISTINCT], src_dev):
+            raise SystemExit('%s: PIL does not give the source pixels of an indexed file' % key)
+        te = {False: [], True: []}
+        for r in range(a.warmup + a.reps):
+            for index in ((False, True) if r % 2 else (True, False)):
+                t = event_ms(lambda: ops.png_encode_u8(src_dev, R, index=index))
+                if r >= a.warmup:
+                    te[index].append(t)
+        shares = kernel_shares(calls['bands'], frags=('png_inflate_bands_kernel', 'png_unfilter_bands_kernel'))
+        st = {k: stats(v) for k, v in ts.items()}
+        row = {'bands_per_file': int(bb.bands.shape[0]) // n, 'waves': int(bb.bands.shape[0]), 'stream_bytes': bb.nbytes,
+               'index_bytes': sum(len(f) for f in distinct) - plain_bytes, 'file_bytes': sum(len(f) for f in distinct),
+               'host_route': stats(th), 'kernel_us': shares, 'encode': stats(te[False]), 'encode_indexed': stats(te[True])}
+        row.update(st)
+        res[key]['band_rows_%d' % R] = row
+        text = ('  band_rows %d: %d bands per file, %d waves in place of %d | by bands %s (inflate %.0f us, unfilter %.0f us per call = %.0f %% '
+                'and %.0f %%) | sequential, this tree %s'
+                % (R, row['bands_per_file'], row['waves'], n, fmt(st['bands']), shares['png_inflate_bands_kernel'],
+                   shares['png_unfilter_bands_kernel'], 100 * shares['png_inflate_bands_kernel'] / sum(shares.values()),
+                   100 * shares['png_unfilter_bands_kernel'] / sum(shares.values()), fmt(st['seq'])))
+        if other is not None:
+            p_ = st['parent']
+            text += (' | sequential, the parent\'s library %s, its spread %.3f ms | parent / bands = %.2f x, parent - bands = %.3f ms = %.1f '
+                     'spreads | this tree\'s sequential / the parent\'s = %.4f'
+                     % (fmt(p_), p_['max_ms'] - p_['min_ms'], p_['median_ms'] / st['bands']['median_ms'],
+                        p_['median_ms'] - st['bands']['median_ms'],
+                        (p_['median_ms'] - st['bands']['median_ms']) / max(p_['max_ms'] - p_['min_ms'], 1e-9),
+                        st['seq']['median_ms'] / p_['median_ms']))
+        text += (' | the host route (PIL decode + upload of the pixels) %s = %.2f x the call by bands | files %.2f MB, of which the index '
+                 '%.1f kB | encode %s, with the index %s'
+                 % (fmt(stats(th)), stats(th)['median_ms'] / st['bands']['median_ms'], row['file_bytes'] * 1e-6 * n / DISTINCT,
+                    row['index_bytes'] * 1e-3 * n / DISTINCT, fmt(stats(te[False])), fmt(stats(te[True]))))
+        say(lines, text)
+
+
+def bench_py(a, lines, res):
+    """bench.py at its defaults in fresh processes, this tree and the parent's checkout in alternation -> its result lines"""
+    legs = [('this', ROOT)] + ([('parent', os.path.abspath(a.parent_tree))] if a.parent_tree else [])
+    res['bench_py'] = {k: [] for k, _ in legs}
+    for r in range(a.bench_py):
+        for name, tree in (legs if r % 2 == 0 else legs[::-1]):
+            env = dict(os.environ)
+            env.pop('ISTVT_LIB', None)
+            p = subprocess.run([sys.executable, os.path.join(tree, 'bench.py'), '--gpus', '1'], env=env, cwd=tree, capture_output=True,
+                               text=True, timeout=600)
+            if p.returncode != 0:
+                raise SystemExit('bench.py (%s) failed:\n%s' % (name, p.stderr[-2000:]))
+            line = [l for l in p.stdout.splitlines() if l.startswith('{')][-1]
+            res['bench_py'][name].append(json.loads(line))
+            say(lines, 'bench.py, %s, run %d: %s' % (name, r, line[:400]))
+
+
+def bands_main(a):
+    if not torch.cuda.is_available():
+        raise SystemExit('png_decode_bench.py measures on a GPU; none is visible')
+    from istvt_amd import _lib
+    torch.zeros(1, device='cuda')
+    other = None
+    if a.against:
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        other.istvt_png_decode_u8.argtypes, other.istvt_png_decode_u8.restype = _lib.SIGNATURES['istvt_png_decode_u8'], ctypes.c_int
+    lines, res = [], {}
+    S = a.size
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    if not a.only_bench_py:
+        bands_size(a, lines, res, 'step', src, a.frames, other)
+    if not a.no_large and not a.only_bench_py:
+        big = torch.stack([torch.from_numpy(smooth_image(1080, 1920, 2000 + i)) for i in range(DISTINCT)])
+        bands_size(a, lines, res, 'large', big, DISTINCT, other)
+    if a.bench_py:
+        bench_py(a, lines, res)
+    line = json.dumps({'png_bands_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--frames', type=int, default=256)
@@ -148,7 +296,15 @@ def main():
     p.add_argument('--host-reps', type=int, default=3)
     p.add_argument('--no-large', action='store_true')
     p.add_argument('--out', default=None)
+    p.add_argument('--bands', action='store_true')
+    p.add_argument('--band-rows', type=int, nargs='+', default=[8, 16, 32])
+    p.add_argument('--against', default=None, help='another build of the library (the parent commit\'s) for the sequential leg')
+    p.add_argument('--bench-py', type=int, default=0, help='runs of bench.py per library, in alternation')
+    p.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit, for --bench-py')
+    p.add_argument('--only-bench-py', action='store_true', help='with --bands --bench-py: skip the decode legs')
     a = p.parse_args()
+    if a.bands:
+        return bands_main(a)
     if not torch.cuda.is_available():
         raise SystemExit('png_decode_bench.py measures on a GPU; none is visible')
     lines, res = [], {}
