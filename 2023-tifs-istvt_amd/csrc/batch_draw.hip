@@ -47,6 +47,16 @@ bool bd_scalars_ok(const istvt_jpeg_decode_args* a, int B, int T, int block_ints
     return (long)block_ints >= BD_HEADER_INTS + (long)B * T;
 }
 
+// The front of both drawn entries: the draw (istvt_batch_draw, which asks the scalars first) -> its return code, and the
+// caller's block with images_host moved on to the index
+int bd_draw_then(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, istvt_jpeg_decode_args& indexed) {
+    const int rc = istvt_batch_draw(a, B, T, block_ints);
+    if (rc != ISTVT_OK) return rc;
+    indexed = *a;
+    indexed.images_host = a->images_host + BD_HEADER_INTS;
+    return ISTVT_OK;
+}
+
 }  // namespace
 
 // The draw alone; include/istvt_hip.h describes the block.  One launch, no synchronisation, nothing allocated.
@@ -59,26 +69,21 @@ extern "C" int istvt_batch_draw(const istvt_jpeg_decode_args* a, int B, int T, i
 
 // The draw, then the indexed decode of the bank on the index the draw has just written: five launches.  A block that the
 // draw refuses keeps the index it held, which the plan kernel of the bank checks like any other (status 4 outside the
-// bank), so nothing outside the block or the bank is read either way.
+// bank), so nothing outside the block or the bank is read either way.  The draw is launched before the indexed entry looks at
+// its own scalars: a call that entry then refuses has drawn, and advanced the step, all the same.
 extern "C" int istvt_jpeg_decode_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max,
                                           int block_stride, int Hmax, int Wmax) {
-    if (!bd_scalars_ok(a, B, T, block_ints)) return ISTVT_ERR_SHAPE;
-    const int rc = istvt_batch_draw(a, B, T, block_ints);
-    if (rc != ISTVT_OK) return rc;
-    istvt_jpeg_decode_args indexed = *a;
-    indexed.images_host = a->images_host + BD_HEADER_INTS;
-    return istvt_jpeg_decode_indexed_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax);
+    istvt_jpeg_decode_args indexed;
+    const int rc = bd_draw_then(a, B, T, block_ints, indexed);
+    return rc != ISTVT_OK ? rc : istvt_jpeg_decode_indexed_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax);
 }
 
 // The same with the split decode of the bank behind the draw (istvt_jpeg_decode_indexed_split_u8): five launches.
 extern "C" int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int seg_max,
                                                 int block_stride, int Hmax, int Wmax, int chunk_bytes, int chunk_rows,
                                                 int seg_bytes_max) {
-    if (!bd_scalars_ok(a, B, T, block_ints)) return ISTVT_ERR_SHAPE;
-    const int rc = istvt_batch_draw(a, B, T, block_ints);
-    if (rc != ISTVT_OK) return rc;
-    istvt_jpeg_decode_args indexed = *a;
-    indexed.images_host = a->images_host + BD_HEADER_INTS;
-    return istvt_jpeg_decode_indexed_split_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax, chunk_bytes, chunk_rows,
-                                              seg_bytes_max);
+    istvt_jpeg_decode_args indexed;
+    const int rc = bd_draw_then(a, B, T, block_ints, indexed);
+    return rc != ISTVT_OK ? rc : istvt_jpeg_decode_indexed_split_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax, chunk_bytes,
+                                                                    chunk_rows, seg_bytes_max);
 }

@@ -839,40 +839,100 @@ long jpeg_decode_check(const istvt_jpeg_decode_args* a, long* groups) {
     return blocks;
 }
 
+// ---- what the four decode entries share: they check, lay the scratch out, (plan,) decode the entropy, finish ------------------
+// The argument checks: the block, its pointers, the counts, the canvas -> blocks of the batch, or -1.  A direct call names
+// host copies of both tables, which jpeg_decode_check reads.  A bank's call (bank: the largest image Hmax x Wmax lies against
+// the canvas) checks scalars alone -- the bank's tables were checked when it was built -- and reads images_host as the index,
+// on the device; segments_host is not used, nbytes stays an int, and the blocks follow from the entry's own scalars: 0 here.
+long jd_args_check(const istvt_jpeg_decode_args* a, bool bank, int Hmax, int Wmax, long* groups) {
+    if (!a || a->n <= 0 || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0) return -1;
+    if (bank ? a->nseg <= 0 || a->nbytes > 0x7fffffffL : a->nseg < a->n) return -1;
+    if (!a->bytes || !a->images || !a->images_host || !a->segments || (!bank && !a->segments_host) || !a->qtabs || !a->htabs ||
+        !a->scratch || !a->out || !a->sizes || !a->status)
+        return -1;
+    if (Hmax < 1 || Wmax < 1 || a->Hc < Hmax || a->Wc < Wmax || a->Hc > 16384 || a->Wc > 16384) return -1;
+    return bank ? 0 : jpeg_decode_check(a, groups);
+}
+
+// The scratch of a call (the layout above JD_BLOCK_BYTES) and what follows it: for a bank's m places of seg_max segment rows,
+// from the next multiple of 16 bytes, the planned images and segments; for the split kernel, from the next multiple of 16
+// bytes again, nrows state rows.  clips.py and tools/jpeg_bank_split_check.cpp compute the same offsets.
+struct JdScratch {
+    short* coef;
+    uint8_t* planes;
+    int *seg_status, *images, *segments, *rows;                  // images, segments: planned (m > 0); rows: the states (nrows > 0)
+};
+
+// -> whether the caller's scratch is aligned and holds the layout for `words` status words
+bool jd_scratch(const istvt_jpeg_decode_args* a, long blocks, long words, long m, long seg_max, long nrows, JdScratch& s) {
+    uint8_t* base = (uint8_t*)a->scratch;
+    long at = blocks * JD_BLOCK_BYTES + 4 * words;
+    s.coef = (short*)base, s.planes = base + blocks * 128, s.seg_status = (int*)(base + blocks * JD_BLOCK_BYTES);
+    s.images = s.segments = s.rows = nullptr;
+    if (m > 0) {
+        at = (at + 15) & ~15L;
+        s.images = (int*)(base + at), s.segments = s.images + m * JD_IMAGE_INTS;
+        at += 4 * m * JD_IMAGE_INTS + 4 * m * seg_max * JD_SEGMENT_INTS;
+    }
+    if (nrows > 0) {
+        at = (at + 15) & ~15L;
+        s.rows = (int*)(base + at);
+        at += nrows * JS_STATE_INTS * 4;
+    }
+    return (reinterpret_cast<uintptr_t>(base) & 15) == 0 && a->scratch_bytes >= at;
+}
+
+// The output side, a canvas of n images: its pixels, which the colour kernel takes 1024 per workgroup, and `out` clear of
+// the bytes the call reads
+bool jd_out_ok(const istvt_jpeg_decode_args* a, long n, long& npix) {
+    npix = n * a->Hc * a->Wc;
+    const uint8_t *src = (const uint8_t*)a->bytes, *out = (const uint8_t*)a->out;
+    return (npix + 1023) / 1024 <= 0x7fffffffL && !(out < src + a->nbytes && src < out + npix * 3);
+}
+
+// The entropy stage on the tables (images [n], segments [nseg]): one lane per segment, or where the scratch has state rows
+// the split kernel, in workgroups of 64 where no segment has more chunks (`most`) and of JS_LANES elsewhere.  STRIDED, nrows:
+// how the rows are addressed (jpeg_entropy_split_kernel).
+template <bool STRIDED>
+int jd_entropy(const istvt_jpeg_decode_args* a, const int* images, int n, const int* segments, int nseg, long blocks,
+               const JdScratch& s, int most = 0, long nrows = 0, int chunk_bytes = 0) {
+    const uint8_t* src = (const uint8_t*)a->bytes;
+    if (!s.rows)
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes, images,
+                           n, segments, nseg, a->htabs, a->nh, s.coef, blocks, s.seg_status);
+    else if (most <= 64)
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<64, STRIDED>), dim3((unsigned)nseg), dim3(64), 0, a->stream, src, a->nbytes,
+                           images, n, segments, nseg, a->htabs, a->nh, s.coef, blocks, s.seg_status, s.rows, nrows, chunk_bytes);
+    else
+        hipLaunchKernelGGL((jpeg_entropy_split_kernel<JS_LANES, STRIDED>), dim3((unsigned)nseg), dim3(JS_LANES), 0, a->stream, src,
+                           a->nbytes, images, n, segments, nseg, a->htabs, a->nh, s.coef, blocks, s.seg_status, s.rows, nrows,
+                           chunk_bytes);
+    return istvt_check_launch();
+}
+
+// The IDCT in `groups` workgroups, which also folds the `words` status words into the statuses, then the colour kernel
+int jd_finish(const istvt_jpeg_decode_args* a, const int* images, int n, int words, long groups, const JdScratch& s, long npix) {
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, s.coef, images, n, a->qtabs, a->nq,
+                       s.seg_status, words, s.planes, a->sizes, a->status);
+    const int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    uint8_t* out = (uint8_t*)a->out;
+    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)((npix + 1023) / 1024)), dim3(256), 0, a->stream, images, s.planes, out,
+                       npix, a->Hc, a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
+    return istvt_check_launch();
+}
+
 }  // namespace
 
 // A batch of baseline JPEG files, packed by clips.jpeg_batch, decoded to uint8 RGB on a canvas out [n][Hc][Wc][3]; the
 // argument block is described in include/istvt_hip.h.  Three launches, no synchronisation, no global state.
 extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
-    if (!a || a->n <= 0 || a->nseg < a->n || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->segments_host || !a->qtabs || !a->htabs ||
-        !a->scratch || !a->out || !a->sizes || !a->status)
-        return ISTVT_ERR_SHAPE;
-    if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
-    long groups = 0;
-    const long blocks = jpeg_decode_check(a, &groups);
-    if (blocks < 0) return ISTVT_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < blocks * JD_BLOCK_BYTES + 4L * a->nseg)
-        return ISTVT_ERR_SHAPE;
-    const long npix = (long)a->n * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
-    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const uint8_t* src = (const uint8_t*)a->bytes;
-    uint8_t* out = (uint8_t*)a->out;
-    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
-    short* coef = (short*)a->scratch;
-    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
-    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((a->nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes,
-                       a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status);
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,
-                       seg_status, a->nseg, planes, a->sizes, a->status);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
-                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
-    return istvt_check_launch();
+    long groups = 0, npix;
+    JdScratch s;
+    const long blocks = jd_args_check(a, false, 1, 1, &groups);
+    if (blocks < 0 || !jd_scratch(a, blocks, a->nseg, 0, 0, 0, s) || !jd_out_ok(a, a->n, npix)) return ISTVT_ERR_SHAPE;
+    const int rc = jd_entropy<false>(a, a->images, a->n, a->segments, a->nseg, blocks, s);
+    return rc != ISTVT_OK ? rc : jd_finish(a, a->images, a->n, a->nseg, groups, s, npix);
 }
 
 // istvt_jpeg_decode_u8 with the split entropy kernel in front: a workgroup per restart interval, a lane per chunk of
@@ -880,13 +940,9 @@ extern "C" int istvt_jpeg_decode_u8(const istvt_jpeg_decode_args* a) {
 // same checks, the same IDCT and colour launches, the same bytes out.  The scratch keeps the layout above in front; the state
 // rows follow the statuses at the next multiple of 16 bytes.
 extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int chunk_bytes) {
-    if (!a || a->n <= 0 || a->nseg < a->n || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || chunk_bytes < 16) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->segments_host || !a->qtabs || !a->htabs ||
-        !a->scratch || !a->out || !a->sizes || !a->status)
-        return ISTVT_ERR_SHAPE;
-    if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
-    long groups = 0;
-    const long blocks = jpeg_decode_check(a, &groups);
+    long groups = 0, npix;
+    JdScratch s;
+    const long blocks = chunk_bytes < 16 ? -1 : jd_args_check(a, false, 1, 1, &groups);
     if (blocks < 0) return ISTVT_ERR_SHAPE;
     long chunks = 0;
     int most = 0;                                                 // chunks of the longest segment
@@ -898,35 +954,9 @@ extern "C" int istvt_jpeg_decode_split_u8(const istvt_jpeg_decode_args* a, int c
         most = c > most ? c : most;
     }
     const long nrows = a->nbytes / chunk_bytes + a->nseg;         // chunks <= nrows
-    const long front = (blocks * JD_BLOCK_BYTES + 4L * a->nseg + 15) & ~15L;
-    if (chunks > nrows || (reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < front + nrows * JS_STATE_INTS * 4)
-        return ISTVT_ERR_SHAPE;
-    const long npix = (long)a->n * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
-    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const uint8_t* src = (const uint8_t*)a->bytes;
-    uint8_t* out = (uint8_t*)a->out;
-    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
-    short* coef = (short*)a->scratch;
-    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
-    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
-    int* rows = (int*)((uint8_t*)a->scratch + front);
-    if (most <= 64)
-        hipLaunchKernelGGL((jpeg_entropy_split_kernel<64, false>), dim3((unsigned)a->nseg), dim3(64), 0, a->stream, src,
-                           a->nbytes, a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status, rows,
-                           nrows, chunk_bytes);
-    else
-        hipLaunchKernelGGL((jpeg_entropy_split_kernel<JS_LANES, false>), dim3((unsigned)a->nseg), dim3(JS_LANES), 0, a->stream,
-                           src, a->nbytes, a->images, a->n, a->segments, a->nseg, a->htabs, a->nh, coef, blocks, seg_status,
-                           rows, nrows, chunk_bytes);
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)groups), dim3(256), 0, a->stream, coef, a->images, a->n, a->qtabs, a->nq,
-                       seg_status, a->nseg, planes, a->sizes, a->status);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, a->images, planes, out, npix, a->Hc,
-                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
-    return istvt_check_launch();
+    if (chunks > nrows || !jd_scratch(a, blocks, a->nseg, 0, 0, nrows, s) || !jd_out_ok(a, a->n, npix)) return ISTVT_ERR_SHAPE;
+    const int rc = jd_entropy<false>(a, a->images, a->n, a->segments, a->nseg, blocks, s, most, nrows, chunk_bytes);
+    return rc != ISTVT_OK ? rc : jd_finish(a, a->images, a->n, a->nseg, groups, s, npix);
 }
 
 // ---- JPEG bank -------------------------------------------------------------------------------------------------------------
@@ -1066,6 +1096,28 @@ __global__ __launch_bounds__(256) void jpeg_bank_scan_kernel(const uint8_t* __re
     }
 }
 
+// Both bank entries behind their own scalars: m places planned at seg_max segment rows and block_stride blocks each, then
+// the kernels of the direct entries on the planned tables, with one status word per planned segment row and one per place.
+// chunk_bytes = 0: one lane per segment; else the split kernel with chunk_rows state rows per segment.
+int jb_decode(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax, int Wmax, int chunk_bytes,
+              int chunk_rows, int seg_bytes_max) {
+    if (jd_args_check(a, true, Hmax, Wmax, nullptr) < 0) return ISTVT_ERR_SHAPE;
+    if (m <= 0 || seg_max < 1 || block_stride < JP_BLOCKS || block_stride % JP_BLOCKS != 0) return ISTVT_ERR_SHAPE;
+    const long blocks = (long)m * block_stride, nseg = (long)m * seg_max, words = nseg + m;
+    if (blocks > 0x7fffffffL / 64 || words > 0x7fffffffL / JD_SEGMENT_INTS) return ISTVT_ERR_SHAPE;
+    long npix;
+    JdScratch s;
+    if (!jd_scratch(a, blocks, words, m, seg_max, chunk_bytes ? nseg * chunk_rows : 0, s) || !jd_out_ok(a, m, npix))
+        return ISTVT_ERR_SHAPE;
+    const int* index = a->images_host;                           // these entries' reading of the field: on the device
+    hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
+                       index, m, seg_max, block_stride, a->Hc, a->Wc, s.images, s.segments, s.seg_status + nseg, seg_bytes_max);
+    int rc = istvt_check_launch();
+    if (rc != ISTVT_OK) return rc;
+    rc = jd_entropy<true>(a, s.images, m, s.segments, (int)nseg, blocks, s, chunk_rows, (long)chunk_rows, chunk_bytes);
+    return rc != ISTVT_OK ? rc : jd_finish(a, s.images, m, (int)words, blocks / JP_BLOCKS, s, npix);
+}
+
 }  // namespace
 
 // A bank decoded through an index; the argument block is described in include/istvt_hip.h.  Four launches: the plan, then
@@ -1073,45 +1125,7 @@ __global__ __launch_bounds__(256) void jpeg_bank_scan_kernel(const uint8_t* __re
 // own, nothing allocated.  The checks here are on scalars alone: the bank's tables were checked when it was built.
 extern "C" int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax,
                                             int Wmax) {
-    if (!a || a->n <= 0 || a->nseg <= 0 || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || a->nbytes > 0x7fffffffL)
-        return ISTVT_ERR_SHAPE;
-    if (m <= 0 || seg_max < 1 || block_stride < JP_BLOCKS || block_stride % JP_BLOCKS != 0) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->qtabs || !a->htabs || !a->scratch || !a->out ||
-        !a->sizes || !a->status)
-        return ISTVT_ERR_SHAPE;
-    if (Hmax < 1 || Wmax < 1 || a->Hc < Hmax || a->Wc < Wmax || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
-    const long blocks = (long)m * block_stride, nseg = (long)m * seg_max, words = nseg + m;
-    if (blocks > 0x7fffffffL / 64 || words > 0x7fffffffL / JD_SEGMENT_INTS) return ISTVT_ERR_SHAPE;
-    const long tables = (blocks * JD_BLOCK_BYTES + 4 * words + 15) & ~15L;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) ||
-        a->scratch_bytes < tables + 4L * m * JD_IMAGE_INTS + 4 * nseg * JD_SEGMENT_INTS)
-        return ISTVT_ERR_SHAPE;
-    const long npix = (long)m * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
-    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const uint8_t* src = (const uint8_t*)a->bytes;
-    uint8_t* out = (uint8_t*)a->out;
-    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
-    const int* index = a->images_host;                           // this entry's reading of the field: on the device
-    short* coef = (short*)a->scratch;
-    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
-    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
-    int* images = (int*)((uint8_t*)a->scratch + tables);
-    int* segments = images + (long)m * JD_IMAGE_INTS;
-    hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
-                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg, -1);
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, a->stream, src, a->nbytes, images, m,
-                       segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(blocks / JP_BLOCKS)), dim3(256), 0, a->stream, coef, images, m, a->qtabs,
-                       a->nq, seg_status, (int)words, planes, a->sizes, a->status);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, images, planes, out, npix, a->Hc,
-                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
-    return istvt_check_launch();
+    return jb_decode(a, m, seg_max, block_stride, Hmax, Wmax, 0, 0, -1);
 }
 
 // istvt_jpeg_decode_indexed_u8 with the split entropy kernel behind the plan, for a bank of files whose restart intervals are
@@ -1122,54 +1136,8 @@ extern "C" int istvt_jpeg_decode_indexed_u8(const istvt_jpeg_decode_args* a, int
 // turns a place with a longer segment into status 5, and the kernel refuses more than chunk_rows chunks by itself.
 extern "C" int istvt_jpeg_decode_indexed_split_u8(const istvt_jpeg_decode_args* a, int m, int seg_max, int block_stride, int Hmax,
                                                   int Wmax, int chunk_bytes, int chunk_rows, int seg_bytes_max) {
-    if (!a || a->n <= 0 || a->nseg <= 0 || a->nq <= 0 || a->nh <= 0 || a->nbytes < 0 || a->nbytes > 0x7fffffffL)
-        return ISTVT_ERR_SHAPE;
-    if (m <= 0 || seg_max < 1 || block_stride < JP_BLOCKS || block_stride % JP_BLOCKS != 0) return ISTVT_ERR_SHAPE;
     if (chunk_bytes < 16 || chunk_rows < 1 || chunk_rows > JS_LANES) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->images_host || !a->segments || !a->qtabs || !a->htabs || !a->scratch || !a->out ||
-        !a->sizes || !a->status)
-        return ISTVT_ERR_SHAPE;
-    if (Hmax < 1 || Wmax < 1 || a->Hc < Hmax || a->Wc < Wmax || a->Hc > 16384 || a->Wc > 16384) return ISTVT_ERR_SHAPE;
-    const long blocks = (long)m * block_stride, nseg = (long)m * seg_max, words = nseg + m;
-    if (blocks > 0x7fffffffL / 64 || words > 0x7fffffffL / JD_SEGMENT_INTS) return ISTVT_ERR_SHAPE;
-    const long tables = (blocks * JD_BLOCK_BYTES + 4 * words + 15) & ~15L;
-    const long front = (tables + 4L * m * JD_IMAGE_INTS + 4 * nseg * JD_SEGMENT_INTS + 15) & ~15L;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || a->scratch_bytes < front + 4L * JS_STATE_INTS * nseg * chunk_rows)
-        return ISTVT_ERR_SHAPE;
-    const long npix = (long)m * a->Hc * a->Wc, lanes = (npix + 1023) / 1024;
-    if (lanes > 0x7fffffffL) return ISTVT_ERR_SHAPE;
-    const uint8_t* src = (const uint8_t*)a->bytes;
-    uint8_t* out = (uint8_t*)a->out;
-    if (out < src + a->nbytes && src < out + npix * 3) return ISTVT_ERR_SHAPE;
-    const int* index = a->images_host;                           // this entry's reading of the field: on the device
-    short* coef = (short*)a->scratch;
-    uint8_t* planes = (uint8_t*)a->scratch + blocks * 128;
-    int* seg_status = (int*)((uint8_t*)a->scratch + blocks * JD_BLOCK_BYTES);
-    int* images = (int*)((uint8_t*)a->scratch + tables);
-    int* segments = images + (long)m * JD_IMAGE_INTS;
-    int* rows = (int*)((uint8_t*)a->scratch + front);
-    hipLaunchKernelGGL(jpeg_bank_plan_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->n, a->segments, a->nseg,
-                       index, m, seg_max, block_stride, a->Hc, a->Wc, images, segments, seg_status + nseg,
-                       seg_bytes_max < 0 ? -1 : seg_bytes_max);
-    int rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    if (chunk_rows <= 64)
-        hipLaunchKernelGGL((jpeg_entropy_split_kernel<64, true>), dim3((unsigned)nseg), dim3(64), 0, a->stream, src, a->nbytes,
-                           images, m, segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status, rows, (long)chunk_rows,
-                           chunk_bytes);
-    else
-        hipLaunchKernelGGL((jpeg_entropy_split_kernel<JS_LANES, true>), dim3((unsigned)nseg), dim3(JS_LANES), 0, a->stream, src,
-                           a->nbytes, images, m, segments, (int)nseg, a->htabs, a->nh, coef, blocks, seg_status, rows,
-                           (long)chunk_rows, chunk_bytes);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(blocks / JP_BLOCKS)), dim3(256), 0, a->stream, coef, images, m, a->qtabs,
-                       a->nq, seg_status, (int)words, planes, a->sizes, a->status);
-    rc = istvt_check_launch();
-    if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(jpeg_canvas_kernel, dim3((unsigned)lanes), dim3(256), 0, a->stream, images, planes, out, npix, a->Hc,
-                       a->Wc, (int)((reinterpret_cast<uintptr_t>(out) & 3) == 0));
-    return istvt_check_launch();
+    return jb_decode(a, m, seg_max, block_stride, Hmax, Wmax, chunk_bytes, chunk_rows, seg_bytes_max < 0 ? -1 : seg_bytes_max);
 }
 
 // The encoder's files -> the tables of a bank, on the device; the argument block is described in include/istvt_hip.h.  Two

@@ -8,7 +8,8 @@ the PNG writer (png_encode_u8), which encode_frames(format='png') ends in.
 One argument front end serves them all: _rgb_source / _nv12_source (the frames), _side, _frame_table (a per-frame table:
 checked as it is, or validated on the host, spread over a clip's frames and uploaded), _u8_out and _no_overlap (the result),
 _nv12_launches (the launches of an NV12 batch with the per-frame tensors sliced alongside) and _paste_target (in place, `out`
-or a copy).  crop_frames and paste_maps pick the entry for a pixel format.  ops re-exports the public entries, and ops.prof
+or a copy); for the file decoders _packed (files or a packed batch), _canvas, _decode_buffers ((scratch, sizes, status) made
+or checked), _decode_args (their argument block) and _call (the entry called, recorded and its return code read).  crop_frames and paste_maps pick the entry for a pixel format.  ops re-exports the public entries, and ops.prof
 records them: ops.kernel_profile stays the one switch.  Nothing here synchronises; with checked=True nothing is read back.
 """
 from __future__ import annotations
@@ -156,6 +157,74 @@ def _no_overlap(what: str, out: Tensor, ptr: int, nbytes: int, source: str) -> N
     """`out` may not share memory with the nbytes the kernel reads at ptr"""
     if out.data_ptr() < ptr + nbytes and ptr < out.data_ptr() + out.numel():
         raise RuntimeError('%s: out may not share memory with the %s' % (what, source))
+
+
+# the file decoders' share of the front end (jpeg_decode_u8, png_decode_u8, jpeg_decode_indexed_u8, jpeg_decode_drawn_u8)
+def _packed(what: str, batch, checked: bool, cls, pack, *how):
+    """The `batch` of a file decoder -> a packed batch: a `cls` as it is; with checked=True nothing else is taken; a sequence
+    of files (bytes), not empty, is packed here by pack(files, *how)."""
+    if isinstance(batch, cls):
+        return batch
+    if checked:
+        raise RuntimeError('%s: checked=True takes a clips.%s (clips.%s packs and validates the files)' % (what, cls.__name__, pack.__name__))
+    if isinstance(batch, (bytes, bytearray)) or not hasattr(batch, '__len__'):
+        raise TypeError('%s expects a sequence of files (bytes) or a clips.%s, got %s' % (what, cls.__name__, type(batch).__name__))
+    if len(batch) == 0:
+        raise RuntimeError('%s: empty input (no files)' % what)
+    return pack(batch, *how)
+
+
+def _decode_device(what: str, out: Optional[Tensor]):
+    """where a batch of files is decoded: on the device of a given `out`, else on the current one"""
+    if not torch.cuda.is_available():
+        raise RuntimeError('istvt_amd: %s needs a ROCm device (no CPU fallback exists for the ISTVT hot path)' % what)
+    return out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+
+
+def _canvas(what: str, Hmax: int, Wmax: int, canvas, whose: str = ''):
+    """canvas = (Hc, Wc), by default Hmax x Wmax: it holds every image (`whose`: ' of the bank') and is at most 16384 x 16384"""
+    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < Hmax or Wc < Wmax or Hc > 16384 or Wc > 16384:
+        raise ValueError('%s: the canvas must hold every image%s (%d x %d at least, 16384 x 16384 at most), got %d x %d'
+                         % (what, whose, Hmax, Wmax, Hc, Wc))
+    return Hc, Wc
+
+
+def _decode_buffers(what: str, device, n: int, need: int, buffers, hint: str = '', short=None):
+    """(scratch, sizes, status) of a decode of n images: made here, or the caller's `buffers` checked -- contiguous on
+    `device`, a uint8 scratch of `need` bytes (`hint` says more about them) at a multiple of 16, int32 sizes (n, 2) and status
+    (n,).  short = (bytes, message with a %d): what a refused scratch of at least that many bytes is told instead."""
+    if buffers is None:
+        return (torch.empty((need,), dtype=torch.uint8, device=device), torch.empty((n, 2), dtype=torch.int32, device=device),
+                torch.empty((n,), dtype=torch.int32, device=device))
+    scratch, sizes, status = buffers
+    ok = (t.device == device and t.is_contiguous() for t in buffers)
+    if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
+            or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
+            or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
+        if short is not None and torch.is_tensor(scratch) and short[0] <= scratch.numel() < need:
+            raise RuntimeError(short[1] % scratch.numel())
+        raise RuntimeError('%s: buffers = (uint8 scratch of %d bytes%s, 16-byte aligned; int32 sizes (%d, 2); int32 '
+                           'status (%d,)), contiguous on %s' % (what, need, hint, n, n, device))
+    return scratch, sizes, status
+
+
+def _decode_args(dev, host_or_index: Tensor, scratch: Tensor, out: Tensor, sizes: Tensor, status: Tensor, n: int, nseg: int,
+                 nq: int, nh: int, nbytes: int, Hc: int, Wc: int, segments_host: Optional[Tensor] = None):
+    """The argument block of a decode.  dev: the uploaded tensors, .data and whichever of .images .segments .qtabs .htabs the
+    entry reads; host_or_index: what the entry reads through images_host (include/istvt_hip.h)."""
+    at = lambda name: getattr(dev, name).data_ptr() if hasattr(dev, name) else None
+    return _lib.JpegDecodeArgs(bytes=dev.data.data_ptr(), nbytes=nbytes, images=at('images'), images_host=host_or_index.data_ptr(),
+                               segments=at('segments'), segments_host=None if segments_host is None else segments_host.data_ptr(),
+                               qtabs=at('qtabs'), htabs=at('htabs'), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(),
+                               out=out.data_ptr(), sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n,
+                               nseg=nseg, nq=nq, nh=nh, Hc=Hc, Wc=Wc)
+
+
+def _call(name: str, nbytes: int, *cargs) -> None:
+    """one call of the library's entry `name` (istvt_...), recorded under its name without the prefix"""
+    with prof(name[6:], nbytes):
+        _lib.check(getattr(_lib.lib(), name)(*cargs), name)
 
 
 # ---- crops and warps ---------------------------------------------------------------------------------------------------------
@@ -438,54 +507,21 @@ def jpeg_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: bo
     come); by default 4:2:0 and 4:4:4 alone.  A JpegBatch has been parsed already: the argument is not consulted for it."""
     if isinstance(batch, clips.JpegFiles):                        # the encoder's result: read back, then parsed like any files
         batch = batch.files()
-    if isinstance(batch, clips.JpegBatch):
-        pass
-    elif checked:
-        raise RuntimeError('jpeg_decode_u8: checked=True takes a clips.JpegBatch (clips.jpeg_batch packs and validates the files)')
-    else:
-        if isinstance(batch, (bytes, bytearray)) or not hasattr(batch, '__len__'):
-            raise TypeError('jpeg_decode_u8 expects a sequence of files (bytes) or a clips.JpegBatch, got %s' % type(batch).__name__)
-        if len(batch) == 0:
-            raise RuntimeError('jpeg_decode_u8: empty input (no files)')
-        batch = clips.jpeg_batch(batch, layouts)
+    what = 'jpeg_decode_u8'
+    batch = _packed(what, batch, checked, clips.JpegBatch, clips.jpeg_batch, layouts)
     chunk = _jpeg_split(batch, split)
     need = batch.scratch_bytes if chunk is None else clips.jpeg_split_plan(batch, chunk).scratch_bytes
-    if not torch.cuda.is_available():
-        raise RuntimeError('istvt_amd: jpeg_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
-    device = out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    device = _decode_device(what, out)
     n = batch.n
-    Hmax, Wmax = max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes)
-    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
-    if Hc < Hmax or Wc < Wmax or Hc > 16384 or Wc > 16384:
-        raise ValueError('jpeg_decode_u8: the canvas must hold every image (%d x %d at least, 16384 x 16384 at most), got %d x %d'
-                         % (Hmax, Wmax, Hc, Wc))
+    Hc, Wc = _canvas(what, max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes), canvas)
     dev = batch.on(device)
-    out = _u8_out('jpeg_decode_u8', dev.data, (n, Hc, Wc, 3), out)
-    _no_overlap('jpeg_decode_u8', out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
-    if buffers is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
-        sizes = torch.empty((n, 2), dtype=torch.int32, device=device)
-        status = torch.empty((n,), dtype=torch.int32, device=device)
-    else:
-        scratch, sizes, status = buffers
-        ok = (t.device == device and t.is_contiguous() for t in buffers)
-        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
-                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
-                or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
-            raise RuntimeError('jpeg_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
-                               'status (%d,)), contiguous on %s' % (need, n, n, device))
-    args = _lib.JpegDecodeArgs(
-        bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
-        segments=dev.segments.data_ptr(), segments_host=batch.segments.data_ptr(), qtabs=dev.qtabs.data_ptr(),
-        htabs=dev.htabs.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(),
-        sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, nseg=int(batch.segments.shape[0]),
-        nq=int(batch.qtabs.shape[0]), nh=int(batch.htabs.shape[0]), Hc=Hc, Wc=Wc)
-    if chunk is not None:
-        with prof('jpeg_decode_split_u8', batch.nbytes + 2 * 192 * batch.blocks + out.numel()):
-            _lib.check(_lib.lib().istvt_jpeg_decode_split_u8(ctypes.byref(args), chunk), 'istvt_jpeg_decode_split_u8')
-        return out, sizes, status
-    with prof('jpeg_decode_u8', batch.nbytes + 2 * 192 * batch.blocks + out.numel()):
-        _lib.check(_lib.lib().istvt_jpeg_decode_u8(ctypes.byref(args)), 'istvt_jpeg_decode_u8')
+    out = _u8_out(what, dev.data, (n, Hc, Wc, 3), out)
+    _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
+    scratch, sizes, status = _decode_buffers(what, device, n, need, buffers)
+    args = _decode_args(dev, batch.images, scratch, out, sizes, status, n, int(batch.segments.shape[0]), int(batch.qtabs.shape[0]),
+                        int(batch.htabs.shape[0]), batch.nbytes, Hc, Wc, segments_host=batch.segments)
+    name, extra = ('istvt_jpeg_decode_u8', ()) if chunk is None else ('istvt_jpeg_decode_split_u8', (chunk,))
+    _call(name, batch.nbytes + 2 * 192 * batch.blocks + out.numel(), ctypes.byref(args), *extra)
     return out, sizes, status
 
 
@@ -504,99 +540,59 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
     here or by the caller, is decoded one wave per band of the files' baND chunks (istvt_png_decode_bands_u8, the bytes and
     statuses of clips.png_decode_bands_host; status 7 is clips.PNG_BAND_STATUS's) and its scratch holds a status word per band
     behind the filtered rows.  A PngBatch is decoded as it was packed: bands= given with one must agree with it."""
-    clips.check_png_bands(bands, 'png_decode_u8')
-    if isinstance(batch, clips.PngBatch):
-        if bands is not None and batch.bands is None:
-            raise ValueError("png_decode_u8: bands='index' with a clips.PngBatch that was packed without bands "
-                             "(clips.png_batch(files, bands='index') packs them)")
-    elif checked:
-        raise RuntimeError('png_decode_u8: checked=True takes a clips.PngBatch (clips.png_batch packs and validates the files)')
-    else:
-        if isinstance(batch, (bytes, bytearray)) or not hasattr(batch, '__len__'):
-            raise TypeError('png_decode_u8 expects a sequence of files (bytes) or a clips.PngBatch, got %s' % type(batch).__name__)
-        if len(batch) == 0:
-            raise RuntimeError('png_decode_u8: empty input (no files)')
-        batch = clips.png_batch(batch, bands)
+    what = 'png_decode_u8'
+    clips.check_png_bands(bands, what)
+    if isinstance(batch, clips.PngBatch) and bands is not None and batch.bands is None:
+        raise ValueError("png_decode_u8: bands='index' with a clips.PngBatch that was packed without bands "
+                         "(clips.png_batch(files, bands='index') packs them)")
+    batch = _packed(what, batch, checked, clips.PngBatch, clips.png_batch, bands)
     need = batch.scratch_bytes
-    if not torch.cuda.is_available():
-        raise RuntimeError('istvt_amd: png_decode_u8 needs a ROCm device (no CPU fallback exists for the ISTVT hot path)')
-    device = out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    device = _decode_device(what, out)
     n = batch.n
-    Hmax, Wmax = max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes)
-    Hc, Wc = (Hmax, Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
-    if Hc < Hmax or Wc < Wmax or Hc > 16384 or Wc > 16384:
-        raise ValueError('png_decode_u8: the canvas must hold every image (%d x %d at least, 16384 x 16384 at most), got %d x %d'
-                         % (Hmax, Wmax, Hc, Wc))
+    Hc, Wc = _canvas(what, max(h for h, _ in batch.sizes), max(w for _, w in batch.sizes), canvas)
     dev = batch.on(device)
-    out = _u8_out('png_decode_u8', dev.data, (n, Hc, Wc, 3), out)
-    _no_overlap('png_decode_u8', out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
-    if buffers is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
-        sizes = torch.empty((n, 2), dtype=torch.int32, device=device)
-        status = torch.empty((n,), dtype=torch.int32, device=device)
-    else:
-        scratch, sizes, status = buffers
-        ok = (t.device == device and t.is_contiguous() for t in buffers)
-        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
-                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (n, 2)
-                or status.dtype != torch.int32 or tuple(status.shape) != (n,)):
-            if batch.bands is not None and torch.is_tensor(scratch) and n * batch.raw_stride <= scratch.numel() < need:
-                raise RuntimeError('png_decode_u8: a batch with bands needs a scratch of %d bytes: %d of filtered rows and a status '
-                                   'word for each of its %d bands, got %d' % (need, n * batch.raw_stride, batch.bands.shape[0],
-                                                                              scratch.numel()))
-            raise RuntimeError('png_decode_u8: buffers = (uint8 scratch of %d bytes, 16-byte aligned; int32 sizes (%d, 2); int32 '
-                               'status (%d,)), contiguous on %s' % (need, n, n, device))
+    out = _u8_out(what, dev.data, (n, Hc, Wc, 3), out)
+    _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
+    name, nband, short = 'istvt_png_decode_u8', 0, None
     if batch.bands is not None:
-        nband = int(batch.bands.shape[0])
-        args = _lib.JpegDecodeArgs(
-            bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
-            segments=dev.bands.data_ptr(), segments_host=batch.bands.data_ptr(), scratch=scratch.data_ptr(),
-            scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(), status=status.data_ptr(), stream=_stream(),
-            n=n, nseg=nband, Hc=Hc, Wc=Wc)
-        with prof('png_decode_bands_u8', batch.nbytes + 2 * batch.raw_bytes + out.numel()):
-            _lib.check(_lib.lib().istvt_png_decode_bands_u8(ctypes.byref(args), batch.raw_stride), 'istvt_png_decode_bands_u8')
-        return out, sizes, status
-    args = _lib.JpegDecodeArgs(
-        bytes=dev.data.data_ptr(), nbytes=batch.nbytes, images=dev.images.data_ptr(), images_host=batch.images.data_ptr(),
-        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
-        status=status.data_ptr(), stream=_stream(), n=n, Hc=Hc, Wc=Wc)
-    with prof('png_decode_u8', batch.nbytes + 2 * batch.raw_bytes + out.numel()):
-        _lib.check(_lib.lib().istvt_png_decode_u8(ctypes.byref(args), batch.raw_stride), 'istvt_png_decode_u8')
+        name, nband = 'istvt_png_decode_bands_u8', int(batch.bands.shape[0])
+        dev = SimpleNamespace(data=dev.data, images=dev.images, segments=dev.bands)     # the band table goes where segments do
+        # said to a scratch that holds the rows but not the band status words
+        short = (n * batch.raw_stride, 'png_decode_u8: a batch with bands needs a scratch of %d bytes: %d of filtered rows and a '
+                 'status word for each of its %d bands, got %%d' % (need, n * batch.raw_stride, nband))
+    scratch, sizes, status = _decode_buffers(what, device, n, need, buffers, short=short)
+    args = _decode_args(dev, batch.images, scratch, out, sizes, status, n, nband, 0, 0, batch.nbytes, Hc, Wc,
+                        segments_host=batch.bands)
+    _call(name, batch.nbytes + 2 * batch.raw_bytes + out.numel(), ctypes.byref(args), batch.raw_stride)
     return out, sizes, status
 
 
 def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], buffers):
     """What a decode of m places of a bank needs beside the index: the canvas, the uploaded bank, `out` and `buffers` checked
     or made -> (the bank on its device, Hc, Wc, out, scratch, sizes, status)"""
-    Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
-    if Hc < bank.Hmax or Wc < bank.Wmax or Hc > 16384 or Wc > 16384:
-        raise ValueError('%s: the canvas must hold every image of the bank (%d x %d at least, 16384 x 16384 '
-                         'at most), got %d x %d' % (what, bank.Hmax, bank.Wmax, Hc, Wc))
+    Hc, Wc = _canvas(what, bank.Hmax, bank.Wmax, canvas, ' of the bank')
     dev = bank.on(device)
     out = _u8_out(what, dev.data, (m, Hc, Wc, 3), out)
     _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
-    need = clips.jpeg_bank_scratch_bytes(bank, m)
-    device = dev.data.device
-    if buffers is None:
-        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
-        sizes = torch.empty((m, 2), dtype=torch.int32, device=device)
-        status = torch.empty((m,), dtype=torch.int32, device=device)
-    else:
-        scratch, sizes, status = buffers
-        ok = (t.device == device and t.is_contiguous() for t in buffers)
-        if (not all(ok) or scratch.dtype != torch.uint8 or scratch.numel() < need or scratch.data_ptr() % 16
-                or sizes.dtype != torch.int32 or tuple(sizes.shape) != (m, 2)
-                or status.dtype != torch.int32 or tuple(status.shape) != (m,)):
-            layout = '' if bank.split is None else ' for the split layout (bank.split = %d: %d state rows per segment)' \
-                % (bank.split, bank.chunk_rows)
-            raise RuntimeError('%s: buffers = (uint8 scratch of %d bytes%s, 16-byte aligned; int32 sizes '
-                               '(%d, 2); int32 status (%d,)), contiguous on %s' % (what, need, layout, m, m, device))
+    layout = '' if bank.split is None else ' for the split layout (bank.split = %d: %d state rows per segment)' \
+        % (bank.split, bank.chunk_rows)
+    scratch, sizes, status = _decode_buffers(what, dev.data.device, m, clips.jpeg_bank_scratch_bytes(bank, m), buffers, layout)
     return dev, Hc, Wc, out, scratch, sizes, status
 
 
-def _bank_split_scalars(bank):
-    """chunk_bytes, chunk_rows, seg_bytes_max as the split entries of a bank take them; -1: no limit on a segment's length"""
-    return bank.split, bank.chunk_rows, -1 if bank.seg_bytes_max is None else min(int(bank.seg_bytes_max), 2 ** 31 - 1)
+def _bank_decode(name: str, bank, index: Tensor, head, dev, Hc: int, Wc: int, out: Tensor, scratch: Tensor, sizes: Tensor,
+                 status: Tensor):
+    """The call behind _bank_call: the bank's entry istvt_jpeg_decode_<name>_u8, which reads the index at `index` and takes the
+    scalars `head` in front of the bank's, or for a bank with a split its _split sibling, which takes chunk_bytes,
+    chunk_rows and seg_bytes_max (-1: no limit on a segment's length) behind them -> (out, sizes, status)"""
+    args = _decode_args(dev, index, scratch, out, sizes, status, bank.n, bank.nseg, bank.nq, bank.nh, bank.nbytes, Hc, Wc)
+    tail = (bank.seg_max, bank.block_stride, bank.Hmax, bank.Wmax)
+    if bank.split is not None:
+        name += '_split'
+        tail += (bank.split, bank.chunk_rows, -1 if bank.seg_bytes_max is None else min(int(bank.seg_bytes_max), 2 ** 31 - 1))
+    # the bytes: + those drawn, known on the device
+    _call('istvt_jpeg_decode_%s_u8' % name, 2 * 192 * out.shape[0] * bank.block_stride + out.numel(), ctypes.byref(args), *head, *tail)
+    return out, sizes, status
 
 
 def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = None, buffers=None, split=None):
@@ -626,26 +622,13 @@ def jpeg_decode_indexed_u8(bank, index, canvas=None, out: Optional[Tensor] = Non
     device = torch.device(bank.device) if bank.device is not None else index.device if index.is_cuda else \
         out.device if out is not None and out.is_cuda else torch.device('cuda', torch.cuda.current_device())
     m = int(index.numel())
-    dev, Hc, Wc, out, scratch, sizes, status = _bank_call('jpeg_decode_indexed_u8', bank, m, device, canvas, out, buffers)
-    if index.device != dev.data.device:
-        index = index.to(dev.data.device, non_blocking=True)
+    front = _bank_call('jpeg_decode_indexed_u8', bank, m, device, canvas, out, buffers)
+    on = front[0].data.device
+    if index.device != on:
+        index = index.to(on, non_blocking=True)
     if index.dtype != torch.int32:                                # -1 and n are outside the bank as everything beyond them is
         index = index.clamp(-1, bank.n).to(torch.int32)
-    args = _lib.JpegDecodeArgs(
-        bytes=dev.data.data_ptr(), nbytes=bank.nbytes, images=dev.images.data_ptr(), images_host=index.data_ptr(),
-        segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
-        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
-        status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
-    if bank.split is not None:
-        with prof('jpeg_decode_indexed_split_u8', 2 * 192 * m * bank.block_stride + out.numel()):
-            _lib.check(_lib.lib().istvt_jpeg_decode_indexed_split_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
-                                                                     bank.Wmax, *_bank_split_scalars(bank)),
-                       'istvt_jpeg_decode_indexed_split_u8')
-        return out, sizes, status
-    with prof('jpeg_decode_indexed_u8', 2 * 192 * m * bank.block_stride + out.numel()):   # + the bytes drawn, known on the device
-        _lib.check(_lib.lib().istvt_jpeg_decode_indexed_u8(ctypes.byref(args), m, bank.seg_max, bank.block_stride, bank.Hmax,
-                                                           bank.Wmax), 'istvt_jpeg_decode_indexed_u8')
-    return out, sizes, status
+    return _bank_decode('indexed', bank, index, (m,), *front)
 
 
 # ---- batch draw ----------------------------------------------------------------------------------------------------------------
@@ -684,25 +667,10 @@ def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, 
     plan = _drawn_plan('jpeg_decode_drawn_u8', plan)
     if plan.N != bank.n:
         raise ValueError('jpeg_decode_drawn_u8: the plan was built for a bank of %d places, this one has %d' % (plan.N, bank.n))
-    m = plan.B * plan.T
-    dev, Hc, Wc, out, scratch, sizes, status = _bank_call('jpeg_decode_drawn_u8', bank, m, plan.block.device, canvas, out, buffers)
-    if dev.data.device != plan.block.device:
-        raise RuntimeError('jpeg_decode_drawn_u8: the bank lives on %s, the plan on %s' % (dev.data.device, plan.block.device))
-    args = _lib.JpegDecodeArgs(
-        bytes=dev.data.data_ptr(), nbytes=bank.nbytes, images=dev.images.data_ptr(), images_host=plan.block.data_ptr(),
-        segments=dev.segments.data_ptr(), segments_host=None, qtabs=dev.qtabs.data_ptr(), htabs=dev.htabs.data_ptr(),
-        scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), out=out.data_ptr(), sizes=sizes.data_ptr(),
-        status=status.data_ptr(), stream=_stream(), n=bank.n, nseg=bank.nseg, nq=bank.nq, nh=bank.nh, Hc=Hc, Wc=Wc)
-    if bank.split is not None:
-        with prof('jpeg_decode_drawn_split_u8', 2 * 192 * m * bank.block_stride + out.numel()):
-            _lib.check(_lib.lib().istvt_jpeg_decode_drawn_split_u8(ctypes.byref(args), plan.B, plan.T, plan.block.numel(), bank.seg_max,
-                                                                   bank.block_stride, bank.Hmax, bank.Wmax,
-                                                                   *_bank_split_scalars(bank)), 'istvt_jpeg_decode_drawn_split_u8')
-        return out, sizes, status, plan.draw
-    with prof('jpeg_decode_drawn_u8', 2 * 192 * m * bank.block_stride + out.numel()):
-        _lib.check(_lib.lib().istvt_jpeg_decode_drawn_u8(ctypes.byref(args), plan.B, plan.T, plan.block.numel(), bank.seg_max,
-                                                         bank.block_stride, bank.Hmax, bank.Wmax), 'istvt_jpeg_decode_drawn_u8')
-    return out, sizes, status, plan.draw
+    front = _bank_call('jpeg_decode_drawn_u8', bank, plan.B * plan.T, plan.block.device, canvas, out, buffers)
+    if front[0].data.device != plan.block.device:
+        raise RuntimeError('jpeg_decode_drawn_u8: the bank lives on %s, the plan on %s' % (front[0].data.device, plan.block.device))
+    return _bank_decode('drawn', bank, plan.block, (plan.B, plan.T, plan.block.numel()), *front) + (plan.draw,)
 
 
 def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
