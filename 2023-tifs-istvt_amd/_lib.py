@@ -92,6 +92,8 @@ SIGNATURES = {
     'istvt_jpeg_decode_drawn_split_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I, I, I, I, I, I],
     'istvt_png_decode_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_png_decode_bands_u8': [ctypes.POINTER(JpegDecodeArgs), I],
+    'istvt_png_decode_bank_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I],
+    'istvt_png_decode_bank_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I],
     'istvt_png_encode_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_png_encode_indexed_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_jpeg_bank_ingest': [ctypes.POINTER(JpegEncodeArgs), I],

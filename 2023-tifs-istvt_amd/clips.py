@@ -61,6 +61,9 @@ PNG files (DESIGN.md "PNG files") are the tenth, at the end of this file: ``png_
 refusal), ``png_decode_host`` (the definition of ops.png_decode_u8: zlib's inflate, the five row filters, integers only),
 ``png_encode_host`` (files for tests and users), ``png_batch`` (files packed for one launch) and ``check_png_status``.  Frames
 kept lossless on purpose run ``model(ops.decode_frames(clips.png_batch(files), S, boxes).view(B, T, S, S, 3), view=flips)``.
+A whole set of them stays on the device as a ``PngBank`` (DESIGN.md "PNG bank"; ``png_bank``, ``png_bank_scratch_bytes``,
+``png_bank_decode_host``, the definition of ops.png_decode_bank_u8), and ``ops.draw_clips(bank, plan, S)`` takes it as it takes
+a JpegBank.
 """
 import math
 from fractions import Fraction
@@ -2789,7 +2792,8 @@ def draw_block_layout(B: int, T: int, V: int, N: int, K: int, nk: int, gap: int 
 class BatchPlan:
     """What a training run draws its batches from, built and validated on the host once:
 
-    bank      a JpegBank, or the [(H, W)] of its places: the frames of the whole set, video after video
+    bank      a JpegBank or a PngBank (either is read through its .sizes alone), or the [(H, W)] of its places: the frames of
+              the whole set, video after video
     videos    int32 (V, 3) rows (first place, frame count, label), or a list of such triples: a video is a run of consecutive
               places.  Class balance is the caller's: a video listed twice is drawn twice as often.
     T, B, stride    a clip is T frames `stride` apart, a batch B clips; a video shorter than (T - 1) * stride + 1 is refused
@@ -3567,7 +3571,164 @@ def check_png_status(status) -> None:
     for i, s in enumerate(status.detach().cpu().tolist()):
         if s != 0:
             raise ValueError('png_decode: file %d is damaged (status %d: %s)'
-                             % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s, 'unknown')))
+                             % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s) or PNG_BANK_STATUS.get(s, 'unknown')))
+
+
+# ---- PNG bank (DESIGN.md "PNG bank") --------------------------------------------------------------------------------------------
+# The files of a whole set packed once for ops.png_decode_bank_u8, which decodes those a device index names.  A file is
+# addressed by a 64-bit base into the bank's bytes and everything inside it by 32-bit offsets from that base, so a bank is not
+# bound by 2^31 bytes; csrc/png_bank.h is the same arithmetic in C++.  png_bank_decode_host is the definition, computed from
+# the bank's own rows and bytes.
+PNG_BANK_IMAGE_INTS = 10                    # a row of PngBank.images: ISTVT_PNG_BANK_IMAGE_INTS of include/istvt_hip.h
+# the statuses only a bank's decode gives (png_bank_decode_host, ops.png_decode_bank_u8); check_png_status words them too
+PNG_BANK_STATUS = {8: 'the index is outside the bank', 9: "the bank's row for this place, or one of its band rows, does not fit the call"}
+
+
+class PngBank:
+    """A set of PNG files ready for ops.png_decode_bank_u8 (png_bank makes it): host tensors, pinned where a device is there to
+    take them.  data uint8: the raw DEFLATE streams end to end, each starting at a multiple of 16 bytes | images int32 (n, 10):
+    H, W, colour type, bpp, base low word, base high word, stream bytes, first band row, band count, 0; the base is the 64-bit
+    byte offset of the file's stream on the device, first_byte included, and a multiple of 16 | bands int32 (nband, 5), rows
+    of png_band_table sorted by file, then by band, with begin and end counted from the file's base | sizes: [(H, W)] | n,
+    nband | nbytes: the streams' bytes with their padding, a Python int that may exceed 2^31 | Hmax, Wmax | raw_stride: the
+    largest H (1 + W bpp), rounded up to 16 | band_max: the most bands of any file | first_byte: where the first stream
+    starts on the device | headers: the parsed files."""
+
+    def __init__(self, **kw):
+        self.device = None                                        # ops.png_decode_bank_u8 reads it as it does a JpegBank's
+        self.__dict__.update(kw)
+        self._on = {}
+
+    def __len__(self) -> int:
+        return self.n
+
+    def on(self, device):
+        """.data .images .bands on `device`, uploaded once without blocking: .data is torch.empty of first_byte + nbytes bytes
+        with the streams copied behind first_byte; the bytes in front are never written and never read"""
+        key = str(device)
+        if key not in self._on:
+            data = torch.empty((self.first_byte + self.nbytes,), dtype=torch.uint8, device=device)
+            data[self.first_byte:].copy_(self.data, non_blocking=True)
+            self._on[key] = SimpleNamespace(data=data, images=self.images.to(device, non_blocking=True),
+                                            segments=self.bands.to(device, non_blocking=True))
+            self._on[key].bands = self._on[key].segments           # the band table goes where segments do
+        return self._on[key]
+
+
+def png_bank(files, bands='index', first_byte: int = 0) -> PngBank:
+    """A sequence of PNG files (bytes, or PngHeaders) -> the PngBank of the set, on the host.  Every file goes through
+    png_parse, which refuses what the decoder does not take.  bands='index' (the default): a file's bands are those of its
+    baND chunk where png_parse accepts it, and a file without a usable chunk is one band; bands=None: every file is one band.
+    first_byte (a multiple of 16, for tests): the first stream starts there on the device, and the bytes in front are
+    allocated and never read.  A single stream of PNG_MAX_BYTES or more is refused; the set as a whole has no such bound."""
+    check_png_bands(bands, 'png_bank')
+    if isinstance(first_byte, bool) or not isinstance(first_byte, int) or first_byte < 0 or first_byte % 16:
+        raise ValueError('png_bank: first_byte is a multiple of 16 and not negative, got %r' % (first_byte,))
+    if isinstance(files, (bytes, bytearray)) or not hasattr(files, '__len__'):
+        raise TypeError('png_bank expects a sequence of files (bytes), got %s' % type(files).__name__)
+    if len(files) == 0:
+        raise ValueError('png_bank: an empty bank')
+    headers = [f if isinstance(f, PngHeader) else png_parse(f) for f in files]
+    parts, images, table, nbytes, stride, band_max = [], [], [], 0, 16, 1
+    for i, hd in enumerate(headers):
+        if len(hd.data) >= PNG_MAX_BYTES:
+            raise ValueError('png_bank: the stream of file %d holds %d bytes; one file holds fewer than %d (offsets inside a '
+                             'file are int32)' % (i, len(hd.data), PNG_MAX_BYTES))
+        one = hd if bands == 'index' or hd.bands is None else PngHeader(H=hd.H, W=hd.W, colour_type=hd.colour_type, bpp=hd.bpp,
+                                                                         data=hd.data, bands=None)
+        rows = png_band_table(one, i, 0)
+        base = first_byte + nbytes
+        images.append([hd.H, hd.W, hd.colour_type, hd.bpp, base & 0xffffffff, base >> 32, len(hd.data), len(table), len(rows), 0])
+        table += rows
+        band_max = max(band_max, len(rows))
+        pad = -len(hd.data) % 16
+        parts.append(hd.data + bytes(pad))
+        nbytes += len(hd.data) + pad
+        stride = max(stride, -(-hd.raw_bytes // 16) * 16)
+    pin = torch.cuda.is_available()
+
+    def host(t):
+        return t.pin_memory() if pin and t.numel() else t
+    words = torch.tensor(images, dtype=torch.int64)
+    words[:, 4:6] = (words[:, 4:6] + 2 ** 31) % 2 ** 32 - 2 ** 31   # the two words of the base as int32 holds them
+    data = torch.frombuffer(bytearray(b''.join(parts) or bytes(16)), dtype=torch.uint8)
+    return PngBank(data=host(data), nbytes=int(data.numel()), images=host(words.to(torch.int32)),
+                   bands=host(torch.tensor(table, dtype=torch.int32).reshape(-1, PNG_BAND_INTS)),
+                   sizes=[(hd.H, hd.W) for hd in headers], n=len(headers), nband=len(table), Hmax=max(hd.H for hd in headers),
+                   Wmax=max(hd.W for hd in headers), raw_stride=stride, band_max=band_max, first_byte=first_byte, headers=headers)
+
+
+def png_bank_scratch_bytes(bank: PngBank, m: int) -> int:
+    """The scratch of ops.png_decode_bank_u8 for m places: a row of raw_stride bytes per place for its filtered rows, then an
+    int32 status per band, band_max of them per place"""
+    m = int(m)
+    return m * bank.raw_stride + 4 * m * bank.band_max
+
+
+def _png_bank_place(bank: PngBank, i: int, Hc: int, Wc: int):
+    """Place i of the bank from its own rows and bytes, as csrc/png_bank.h reads them -> (frame uint8 (H, W, 3) or None, H, W,
+    status).  Status 9 and no frame where the image row or a band row does not fit the bank."""
+    import numpy as np
+    im = bank.images[i].tolist()
+    H, W, ct, bpp, lo, hi, nstream, first, count = im[:9]
+    base = ((hi & 0xffffffff) << 32) | (lo & 0xffffffff)
+    if base >= 2 ** 63:
+        base -= 2 ** 64
+    total = bank.first_byte + bank.nbytes
+    if not (1 <= H <= PNG_MAX_SIDE and 1 <= W <= PNG_MAX_SIDE and H <= Hc and W <= Wc) or PNG_BPP.get(ct) != bpp \
+            or H * (1 + W * bpp) > bank.raw_stride or not (1 <= count <= bank.band_max) or base < 0 or base % 16 or nstream < 0 \
+            or base > total or nstream > total - base or base < bank.first_byte:
+        return None, 0, 0, 9
+    stream = bytes(bank.data[base - bank.first_byte:base - bank.first_byte + nstream].numpy())
+    raw, statuses = bytearray(H * (1 + W * bpp)), []
+    for k in range(count):
+        if first < 0 or first + k >= bank.nband:
+            statuses.append(9)
+            continue
+        f, begin, end, at, nout = bank.bands[first + k].tolist()
+        if f != i or not (0 <= begin <= end <= nstream) or at < 0 or nout < 0 or at + nout > len(raw):
+            statuses.append(9)
+            continue
+        out, status = _png_inflate(stream[begin:end], nout, middle=k < count - 1)
+        raw[at:at + len(out)] = out
+        statuses.append(status)
+    status = next((s for s in statuses if s), 0)
+    rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(H, -1) if status == 0 else None
+    if status == 0 and int(rows[:, 0].max()) > 4:
+        status = 6
+    if status:
+        return torch.zeros((H, W, 3), dtype=torch.uint8), H, W, status
+    px = torch.from_numpy(_png_unfilter(rows, bpp)).reshape(H, W, bpp)
+    return (px.expand(H, W, 3).contiguous() if bpp == 1 else px[:, :, :3].contiguous()), H, W, 0
+
+
+def png_bank_decode_host(bank_or_files, index, canvas=None):
+    """The definition of ops.png_decode_bank_u8, integers only: -> (frames, sizes, status), frames uint8 (m, Hc, Wc, 3) with
+    place j holding png_decode_bands_host(files[index[j]]) in its top left corner and 0 elsewhere, sizes int32 (m, 2) =
+    (H, W), status int32 (m,).  Computed from the bank's own rows and bytes (a sequence of files is packed by png_bank
+    first), so it says what the tables mean: a file packed as one band gives png_decode_host's result.  Beside the statuses of
+    png_decode_bands_host: 8 where index[j] is outside [0, n), 9 where the bank's row for the place or one of its band rows
+    does not fit (PNG_BANK_STATUS); both with size (0, 0) and a frame of zeros.  canvas = (Hc, Wc) defaults to the bank's
+    Hmax x Wmax, whatever is drawn."""
+    bank = bank_or_files if isinstance(bank_or_files, PngBank) else png_bank(bank_or_files)
+    index = check_bank_index(index, 'png_bank_decode_host').tolist()
+    Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if Hc < bank.Hmax or Wc < bank.Wmax:
+        raise ValueError('png_bank_decode_host: the canvas %d x %d does not hold every image of the bank' % (Hc, Wc))
+    drawn = {i: _png_bank_place(bank, i, Hc, Wc) for i in set(index) if 0 <= i < bank.n}
+    frames = torch.zeros((len(index), Hc, Wc, 3), dtype=torch.uint8)
+    sizes = torch.zeros((len(index), 2), dtype=torch.int32)
+    status = torch.zeros((len(index),), dtype=torch.int32)
+    for j, i in enumerate(index):
+        if i not in drawn:
+            status[j] = 8
+            continue
+        f, H, W, s = drawn[i]
+        status[j] = s
+        if s != 9:
+            frames[j, :H, :W] = f
+            sizes[j, 0], sizes[j, 1] = H, W
+    return frames, sizes, status
 
 
 # ---- PNG files out (DESIGN.md "PNG files out") ---------------------------------------------------------------------------------

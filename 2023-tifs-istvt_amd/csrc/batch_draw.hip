@@ -87,3 +87,12 @@ extern "C" int istvt_jpeg_decode_drawn_split_u8(const istvt_jpeg_decode_args* a,
     return rc != ISTVT_OK ? rc : istvt_jpeg_decode_indexed_split_u8(&indexed, B * T, seg_max, block_stride, Hmax, Wmax, chunk_bytes,
                                                                     chunk_rows, seg_bytes_max);
 }
+
+// The draw, then the indexed decode of a PNG bank (csrc/png_bank.hip) on the index the draw has just written: three launches.
+// A refused block keeps the index it held, which the bank's kernels check like any other (status 8 outside the bank).
+extern "C" int istvt_png_decode_bank_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max,
+                                              int raw_stride) {
+    istvt_jpeg_decode_args indexed;
+    const int rc = bd_draw_then(a, B, T, block_ints, indexed);
+    return rc != ISTVT_OK ? rc : istvt_png_decode_bank_u8(&indexed, B * T, band_max, raw_stride);
+}

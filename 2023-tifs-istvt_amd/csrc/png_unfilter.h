@@ -1,5 +1,6 @@
-// What the two PNG decoders (csrc/png.hip, csrc/png_bands.hip) share behind the inflate: the rows of the image table, the
-// unfilter of one file by one wave, and the checks of the host tables that both entries make before any launch.
+// What the PNG decoders (csrc/png.hip, csrc/png_bands.hip, csrc/png_bank.hip) share behind the inflate: the unfilter of one file
+// by one wave; and for the two batch decoders the rows of the image table and the checks of the host tables that both entries
+// make before any launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,21 +35,21 @@ __device__ __forceinline__ void png_zero(uint8_t* p, long n, int lane) {
 // The last row of a band is written back over its filtered bytes, all bpp channels, and lane 0 of the next band reads it there.
 // BANDS: the inflate's status of the file is that of its first band that failed, in band order (band_status, read with BANDS
 // only); else it is status[f]
+// The form with the file's fields apart from the tables: H, W and bpp of the file, first_status its first band status word and
+// count its bands (read with BANDS only), place its row of the scratch, of `out`, of sizes and of status.  csrc/png_bank.hip
+// takes the fields from the bank's row of the drawn file and the place from the wave.
 template <bool BANDS>
-__device__ __forceinline__ void png_unfilter_file(const int* __restrict__ images, const int* __restrict__ band_status, uint8_t* scratch,
+__device__ __forceinline__ void png_unfilter_file(int H, int W, int bpp, const int* __restrict__ first_status, int count, uint8_t* scratch,
                                                   long raw_stride, uint8_t* __restrict__ out, int Hc, int Wc, int* __restrict__ sizes,
                                                   int* status, int f, int lane) {
-    const int* im = images + (long)f * ISTVT_PNG_IMAGE_INTS;
-    const int H = im[PG_H], W = im[PG_W], bpp = im[PG_BPP];
     const long stride = 1 + (long)W * bpp;
     uint8_t* raw = scratch + (long)f * raw_stride;
     uint8_t* canvas = out + (long)f * Hc * Wc * 3;
     int st;
     if constexpr (BANDS) {
-        const int first = im[PG_FIRST_BAND], count = im[PG_BANDS];
         st = 0;
         for (int k0 = 0; k0 < count && st == 0; k0 += 64) {
-            const int mine = k0 + lane < count ? band_status[first + k0 + lane] : 0;
+            const int mine = k0 + lane < count ? first_status[k0 + lane] : 0;
             const unsigned long long failed = __ballot(mine != 0);
             if (failed) st = __shfl(mine, __ffsll((long long)failed) - 1);
         }
@@ -115,6 +116,19 @@ __device__ __forceinline__ void png_unfilter_file(const int* __restrict__ images
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                         // lane 63's row has landed before lane 0 reads it
     }
+}
+
+// The form of the two batch decoders: file f's fields are row f of `images`, its band statuses start at its first band row
+template <bool BANDS>
+__device__ __forceinline__ void png_unfilter_file(const int* __restrict__ images, const int* __restrict__ band_status, uint8_t* scratch,
+                                                  long raw_stride, uint8_t* __restrict__ out, int Hc, int Wc, int* __restrict__ sizes,
+                                                  int* status, int f, int lane) {
+    const int* im = images + (long)f * ISTVT_PNG_IMAGE_INTS;
+    if constexpr (BANDS)
+        png_unfilter_file<true>(im[PG_H], im[PG_W], im[PG_BPP], band_status + im[PG_FIRST_BAND], im[PG_BANDS], scratch, raw_stride, out, Hc,
+                                Wc, sizes, status, f, lane);
+    else
+        png_unfilter_file<false>(im[PG_H], im[PG_W], im[PG_BPP], nullptr, 0, scratch, raw_stride, out, Hc, Wc, sizes, status, f, lane);
 }
 
 // the host copy of the image table against the byte range, the canvas and the scratch

@@ -574,9 +574,13 @@ def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], b
     dev = bank.on(device)
     out = _u8_out(what, dev.data, (m, Hc, Wc, 3), out)
     _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
-    layout = '' if bank.split is None else ' for the split layout (bank.split = %d: %d state rows per segment)' \
-        % (bank.split, bank.chunk_rows)
-    scratch, sizes, status = _decode_buffers(what, dev.data.device, m, clips.jpeg_bank_scratch_bytes(bank, m), buffers, layout)
+    if isinstance(bank, clips.PngBank):
+        need, layout = clips.png_bank_scratch_bytes(bank, m), ' (clips.png_bank_scratch_bytes: filtered rows and a status word per band)'
+    else:
+        need = clips.jpeg_bank_scratch_bytes(bank, m)
+        layout = '' if bank.split is None else ' for the split layout (bank.split = %d: %d state rows per segment)' \
+            % (bank.split, bank.chunk_rows)
+    scratch, sizes, status = _decode_buffers(what, dev.data.device, m, need, buffers, layout)
     return dev, Hc, Wc, out, scratch, sizes, status
 
 
@@ -673,9 +677,64 @@ def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, 
     return _bank_decode('drawn', bank, plan.block, (plan.B, plan.T, plan.block.numel()), *front) + (plan.draw,)
 
 
+def _png_bank_decode(name: str, bank, index: Tensor, head, dev, Hc: int, Wc: int, out: Tensor, scratch: Tensor, sizes: Tensor,
+                     status: Tensor):
+    """The call behind _bank_call for a clips.PngBank: the entry istvt_png_decode_<name>_u8, which reads the index at `index` and
+    takes the scalars `head` in front of the bank's band_max and raw_stride -> (out, sizes, status)"""
+    args = _decode_args(dev, index, scratch, out, sizes, status, bank.n, bank.nband, 0, 0, bank.first_byte + bank.nbytes, Hc, Wc)
+    # the bytes: + the streams drawn, known on the device
+    _call('istvt_png_decode_%s_u8' % name, 2 * out.shape[0] * bank.raw_stride + out.numel(), ctypes.byref(args), *head, bank.band_max,
+          bank.raw_stride)
+    return out, sizes, status
+
+
+def png_decode_bank_u8(bank, index, canvas=None, out: Optional[Tensor] = None, buffers=None):
+    """PNG bank (clips.py): the files of a clips.PngBank stay on the device, and the m of them that `index` names are decoded
+    by their bands, in that order and with repeats -> (frames, sizes, status) as png_decode_u8 hands them back, the bytes of
+    clips.png_bank_decode_host: frames uint8 [m, Hc, Wc, 3], sizes int32 [m, 2], status int32 [m]; a place whose index is
+    outside the bank has status 8, one whose rows on the device do not fit the call status 9 (clips.PNG_BANK_STATUS), both
+    with size (0, 0) and a frame of zeros.  index: int32 or int64, one dimension, contiguous, on the device -- then no host
+    data is part of the call, nothing synchronises, and the call can be captured in a graph with `out` and `buffers` -- or a
+    host tensor or list, which is uploaded.  int64 is clamped to [-1, n] and narrowed on the device.  The bank is uploaded at
+    the first call (bank.on); it may hold more than 2^31 bytes.  canvas = (Hc, Wc) defaults to the bank's largest H and W,
+    whatever is drawn.  buffers = (scratch uint8 of clips.png_bank_scratch_bytes(bank, m) bytes and 16-byte aligned, sizes,
+    status).  Two launches."""
+    what = 'png_decode_bank_u8'
+    if not isinstance(bank, clips.PngBank):
+        raise TypeError('%s expects a clips.PngBank (clips.png_bank), got %s' % (what, type(bank).__name__))
+    index = clips.check_bank_index(index, what)
+    if not torch.cuda.is_available():
+        raise RuntimeError('istvt_amd: %s needs a ROCm device (no CPU fallback exists for the ISTVT hot path)' % what)
+    device = index.device if index.is_cuda else out.device if out is not None and out.is_cuda else \
+        torch.device('cuda', torch.cuda.current_device())
+    m = int(index.numel())
+    front = _bank_call(what, bank, m, device, canvas, out, buffers)
+    on = front[0].data.device
+    if index.device != on:
+        index = index.to(on, non_blocking=True)
+    if index.dtype != torch.int32:                                # -1 and n are outside the bank as everything beyond them is
+        index = index.clamp(-1, bank.n).to(torch.int32)
+    return _png_bank_decode('bank', bank, index, (m,), *front)
+
+
+def png_decode_bank_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, buffers=None):
+    """batch_draw(plan) and png_decode_bank_u8(bank, the index just drawn) as one call of three launches -> (frames, sizes,
+    status, draw): frames uint8 [B*T, Hc, Wc, 3], sizes and status as the bank decode hands them back, draw as batch_draw
+    does.  The plan was built for this bank (as many places) and lives on its device.  canvas, out and buffers are
+    png_decode_bank_u8's, for m = B * T; with out and buffers the call can be captured in a graph."""
+    what = 'png_decode_bank_drawn_u8'
+    if not isinstance(bank, clips.PngBank):
+        raise TypeError('%s expects a clips.PngBank, got %s' % (what, type(bank).__name__))
+    plan = _drawn_plan(what, plan)
+    if plan.N != bank.n:
+        raise ValueError('%s: the plan was built for a bank of %d places, this one has %d' % (what, plan.N, bank.n))
+    front = _bank_call(what, bank, plan.B * plan.T, plan.block.device, canvas, out, buffers)
+    return _png_bank_decode('bank_drawn', bank, plan.block, (plan.B, plan.T, plan.block.numel()), *front) + (plan.draw,)
+
+
 def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
     """The whole input side of a training step on the device: the batch of the plan's current step is drawn and decoded
-    (jpeg_decode_drawn_u8), every frame cut and resized through its drawn box (crop_resize_u8), recompressed at its clip's
+    (jpeg_decode_drawn_u8; png_decode_bank_drawn_u8 for a clips.PngBank), every frame cut and resized through its drawn box (crop_resize_u8), recompressed at its clip's
     drawn quality (jpeg_roundtrip_u8; left out when the plan's jpeg is off) and perturbed by its clip's drawn row (perturb_u8
     with the plan's taps and its seed as the noise key; left out when the plan's perturb is off) -> (u8 [B, T, S, S, 3], view
     int32 [B, 3], label int32 [B], status int32 [B*T]), all on the device: the bytes of the same calls on the host tables of
@@ -690,7 +749,7 @@ def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
                          '%d) are resized' % (plan.max_side, clips.MAX_BOX_SCALE * S, S))
     B, T = plan.B, plan.T
     out = _u8_out('draw_clips', plan.block, (B, T, S, S, 3), out)
-    frames, _, status, draw = jpeg_decode_drawn_u8(bank, plan)
+    frames, _, status, draw = (png_decode_bank_drawn_u8 if isinstance(bank, clips.PngBank) else jpeg_decode_drawn_u8)(bank, plan)
     stages = ['crop'] + ['jpeg'] * (plan.thr_jpeg > 0) + ['perturb'] * (plan.thr_perturb > 0)
     flat = lambda stage: out.view(B * T, S, S, 3) if stages[-1] == stage else None      # the last stage writes `out`
     u8 = crop_resize_u8(frames, draw.boxes, S, out=flat('crop'), checked=True)
@@ -776,11 +835,18 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
     are decoded and cut; without `boxes` each is cut whole through boxes made from the decoder's sizes on the device, and a
     place with status 4 or 5 comes out black.  A bank brings its own split (bank.split); split= is refused for it.  A
     clips.PngBatch (clips.png_batch) is decoded by png_decode_u8 and cut the same way, by its bands where it carries them;
-    split= and layouts= are refused for it."""
-    if isinstance(files, clips.JpegBank):
+    split= and layouts= are refused for it.  A clips.PngBank (clips.png_bank) with `index` goes through png_decode_bank_u8 as a
+    JpegBank goes through its decoder: whole-image boxes from the decoder's sizes, a place with status 8 or 9 black; split= and
+    layouts= are refused for it too."""
+    if isinstance(files, (clips.JpegBank, clips.PngBank)):
         if index is None:
-            raise ValueError('decode_frames: a clips.JpegBank is decoded through index=')
-        frames, sizes, _ = jpeg_decode_indexed_u8(files, index, split=split)
+            raise ValueError('decode_frames: a clips.%s is decoded through index=' % type(files).__name__)
+        if isinstance(files, clips.JpegBank):
+            frames, sizes, _ = jpeg_decode_indexed_u8(files, index, split=split)
+        elif split is not None or layouts is not clips.JPEG_LAYOUTS_DEFAULT:
+            raise ValueError('decode_frames: split= and layouts= go with JPEG files; a clips.PngBank takes neither')
+        else:
+            frames, sizes, _ = png_decode_bank_u8(files, index)
         if boxes is not None:
             return crop_resize_u8(frames, boxes, S)
         S = _side('crop_resize_u8', S)

@@ -554,6 +554,35 @@ int istvt_png_decode_u8(const istvt_jpeg_decode_args* a, int raw_stride);
  * in file order, a file's output ranges that do not follow one another from 0 to H (1 + W bpp). */
 #define ISTVT_PNG_BAND_INTS 5      /* a row of a PNG batch's bands */
 int istvt_png_decode_bands_u8(const istvt_jpeg_decode_args* a, int raw_stride);
+/* PNG bank: the files of a whole set stay on the device with their tables (clips.png_bank), and a call decodes the m of them
+ * that `index` names by their bands, in that order and with repeats -> out uint8 [m][Hc][Wc][3], sizes int32 [m][2], status
+ * int32 [m] as istvt_png_decode_bands_u8 writes them, and two more statuses: 8 the index is outside [0, n), 9 the bank's row
+ * for the place, or one of its band rows, does not fit the call (only a device table that differs from what clips.png_bank
+ * built gives it); either leaves size (0, 0) and a frame of zeros.  The bytes of clips.png_bank_decode_host.  The bank may
+ * hold more than 2^31 bytes: a file is addressed by a 64-bit base, everything inside it by 32-bit offsets from that base.
+ * Two launches and no plan kernel: png_bank_inflate_kernel, m * band_max workgroups of one wave, wave b being band b % band_max
+ * of place b / band_max (a wave whose file has fewer bands leaves at once), and png_bank_unfilter_kernel, m workgroups of one
+ * wave; both look the index up themselves and check the rows they use (csrc/png_bank.h).  No synchronisation, no global
+ * state, no atomics, nothing allocated.  The argument block is istvt_jpeg_decode_args, read as follows:
+ *   bytes, nbytes  uint8 [nbytes], 16-byte aligned: the bank's DEFLATE streams, each starting at a multiple of 16 bytes; nbytes
+ *                  is a long and may exceed 2^31.  No byte outside a drawn file's [base, base + stream bytes) is read
+ *   images, n      int32 [n][ISTVT_PNG_BANK_IMAGE_INTS]: H, W, colour type, bytes per pixel, base low word, base high word,
+ *                  stream bytes, first band row, band count, 0
+ *   segments, nseg int32 [nseg][ISTVT_PNG_BAND_INTS] as above, with the first byte and the end byte counted from the file's base
+ *   images_host    NOT a host pointer here: the index, int32 [m] on the device.  segments_host is not read.
+ *   scratch        16-byte aligned; m * raw_stride bytes of filtered rows, place j's at scratch + j * raw_stride, then int32
+ *                  [m * band_max] band statuses, band k of place j at word j * band_max + k; scratch_bytes >= m * raw_stride +
+ *                  4 m band_max (clips.png_bank_scratch_bytes).  Nothing is read from it before it is written.
+ *   out, sizes, status, Hc, Wc, stream    as above, with m in the place of n
+ * band_max: the most bands of any file of the bank; raw_stride: a multiple of 16, at least every file's H (1 + W bpp).  The
+ * entry looks at scalars alone and returns -3 on a null pointer, a count below 1, a raw_stride below 16 or not a multiple of
+ * 16, m * band_max beyond an int, a canvas outside 1..16384, a scratch too small or misaligned, or an out that overlaps bytes. */
+#define ISTVT_PNG_BANK_IMAGE_INTS 10   /* a row of a PNG bank's images */
+int istvt_png_decode_bank_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride);
+/* The draw followed by istvt_png_decode_bank_u8 with m = B * T on the index it wrote: three launches.  images_host is the
+ * draw block as istvt_batch_draw reads it; every other field, and band_max and raw_stride, are the bank decode's.  A refused
+ * block leaves its index as it was, which the bank's kernels check like any other (status 8 outside the bank). */
+int istvt_png_decode_bank_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max, int raw_stride);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with

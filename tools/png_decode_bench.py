@@ -29,6 +29,16 @@ encode   ops.png_encode_u8 with and without the index on the same frames
 --bench-py K   bench.py at its defaults K times on this tree and, with --parent-tree DIR, on that checkout of the parent commit
          (built: this tree's Python does not load a library without the new entry points), in alternation, each in a fresh
          process (--only-bench-py: nothing else)
+
+--bank [--bench-py K [--parent-tree DIR]]  instead of the above (DESIGN.md "PNG bank"): the 224 x 224 frames as our own indexed files at
+band_rows 16 and 8, repeated to a bank of --bank-files (4096) places, 256 drawn per call by a fixed device index, with the
+caller's buffers.  After the frames of both routes are compared with each other and with the source pixels:
+
+b        the prepacked PngBatch of the drawn files with bands through ops.png_decode_u8: what the parent commit has
+c        ops.png_decode_bank_u8 on the bank with the device index; b and c in alternation, each first in turn; each kernel's
+         share of both from a torch.profiler trace of ten more calls
+a        ops.png_decode_u8 from the drawn files' bytes, clips.png_batch and the upload in every call: 3 repeats
+d        ops.draw_clips from the PNG bank beside ops.draw_clips from a JPEG bank of the same frames at quality 90
 """
 import argparse
 import io
@@ -287,6 +297,96 @@ def bands_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def bank_main(a):
+    if not torch.cuda.is_available():
+        raise SystemExit('png_decode_bench.py measures on a GPU; none is visible')
+    dev = torch.device('cuda', torch.cuda.current_device())
+    torch.zeros(1, device=dev)
+    lines, res = [], {}
+    S, n, N = a.size, a.frames, a.bank_files
+    src = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)])
+    src_dev = src.to(dev)
+    g = torch.Generator().manual_seed(31)
+    index = torch.randint(0, N, (n,), generator=g, dtype=torch.int32)
+    idx = index.to(dev)
+    drawn = [i % DISTINCT for i in index.tolist()]
+    want = src_dev[torch.tensor(drawn, device=dev)]
+    out_b, out_c = (torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+    say(lines, 'bank: %d places of %d x %d (%d distinct files repeated), %d drawn per call by a device index' % (N, S, S, DISTINCT, n))
+    for R in a.band_rows:
+        if a.only_bench_py:
+            break
+        distinct = ops.png_encode_u8(src_dev, R, index=True).files()
+        headers = [clips.png_parse(f) for f in distinct]
+        bank = clips.png_bank([headers[i % DISTINCT] for i in range(N)])
+        bank.on(dev)
+        files = [distinct[i] for i in drawn]
+        batch = clips.png_batch([headers[i] for i in drawn], bands='index')
+        batch.on(dev)
+        mk = lambda need: (torch.empty((need,), dtype=torch.uint8, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                           torch.empty((n,), dtype=torch.int32, device=dev))
+        buf_b, buf_c = mk(batch.scratch_bytes), mk(clips.png_bank_scratch_bytes(bank, n))
+        calls = {'b': lambda: ops.png_decode_u8(batch, out=out_b, checked=True, buffers=buf_b),
+                 'c': lambda: ops.png_decode_bank_u8(bank, idx, out=out_c, buffers=buf_c)}
+        for k, fn in calls.items():
+            got, _, status = fn()
+            clips.check_png_status(status)
+            if not torch.equal(got, want):
+                raise SystemExit('band_rows %d, leg %s: the decoded frames are not the source pixels' % (R, k))
+        ts = {k: [] for k in calls}
+        for r in range(a.warmup + a.reps):
+            order = list(calls.items())
+            for k, fn in order[r % 2:] + order[:r % 2]:               # each leg first in turn
+                t = event_ms(fn)
+                if r >= a.warmup:
+                    ts[k].append(t)
+        ta = [timed(lambda: ops.png_decode_u8(files, bands='index')) for _ in range(1 + 3)][1:]
+        sb = kernel_shares(calls['b'], frags=('png_inflate_bands_kernel', 'png_unfilter_bands_kernel'))
+        sc = kernel_shares(calls['c'], frags=('png_bank_inflate_kernel', 'png_bank_unfilter_kernel'))
+        st = {k: stats(v) for k, v in ts.items()}
+        inside = st['b']['min_ms'] <= st['c']['median_ms'] <= st['b']['max_ms']
+        row = {'bands_per_file': bank.band_max, 'waves_b': int(batch.bands.shape[0]), 'waves_c': n * bank.band_max, 'bank_bytes': bank.nbytes,
+               'b': st['b'], 'c': st['c'], 'a': stats(ta), 'kernel_us_b': sb, 'kernel_us_c': sc, 'c_inside_b_range': inside}
+        res['band_rows_%d' % R] = row
+        say(lines, '  band_rows %d: %d bands per file, bank of %.1f MB | (b) prepacked PngBatch with bands %s (inflate %.0f us, unfilter %.0f us '
+            'per call) | (c) the bank by a device index %s (inflate %.0f us, unfilter %.0f us per call) | c / b = %.4f, c - b = %.3f ms, the '
+            'range of b %.3f ms: c is %s it | (a) from bytes, png_batch and upload every call %s = %.1f x c'
+            % (R, bank.band_max, bank.nbytes * 1e-6, fmt(st['b']), sb['png_inflate_bands_kernel'], sb['png_unfilter_bands_kernel'], fmt(st['c']),
+               sc['png_bank_inflate_kernel'], sc['png_bank_unfilter_kernel'], st['c']['median_ms'] / st['b']['median_ms'],
+               st['c']['median_ms'] - st['b']['median_ms'], st['b']['max_ms'] - st['b']['min_ms'], 'inside' if inside else 'OUTSIDE',
+               fmt(stats(ta)), stats(ta)['median_ms'] / st['c']['median_ms']))
+        if R == a.band_rows[0]:                                     # (d) the whole input side from either bank
+            T = 8
+            B = n // T
+            jh = [clips.jpeg_parse(f) for f in ops.jpeg_encode_u8(src_dev, 90, '420', 'row').files()]
+            jbank = clips.jpeg_bank([jh[i % DISTINCT] for i in range(N)])
+            jbank.on(dev)
+            out_d = torch.empty((B, T, S, S, 3), dtype=torch.uint8, device=dev)
+            plans = {k: clips.BatchPlan(bk, [(0, N, 0)], T=T, B=B, seed=5).on(dev) for k, bk in (('png', bank), ('jpeg', jbank))}
+            dcalls = {'png': lambda: ops.draw_clips(bank, plans['png'], S, out=out_d),
+                      'jpeg': lambda: ops.draw_clips(jbank, plans['jpeg'], S, out=out_d)}
+            td = {k: [] for k in dcalls}
+            for r in range(a.warmup + a.reps):
+                order = list(dcalls.items())
+                for k, fn in order[r % 2:] + order[:r % 2]:
+                    t = event_ms(fn)
+                    if r >= a.warmup:
+                        td[k].append(t)
+            row['draw_clips_png'], row['draw_clips_jpeg'] = stats(td['png']), stats(td['jpeg'])
+            say(lines, '  (d) draw_clips, B = %d clips of T = %d at %d x %d, all stages: from the PNG bank %s | from a JPEG bank of the same '
+                'frames at quality 90 %s' % (B, T, S, S, fmt(stats(td['png'])), fmt(stats(td['jpeg']))))
+            del jbank, plans
+        bank._on.clear()
+    if a.bench_py:
+        bench_py(a, lines, res)
+    line = json.dumps({'png_bank_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--frames', type=int, default=256)
@@ -302,7 +402,12 @@ def main():
     p.add_argument('--bench-py', type=int, default=0, help='runs of bench.py per library, in alternation')
     p.add_argument('--parent-tree', default=None, help='a built checkout of the parent commit, for --bench-py')
     p.add_argument('--only-bench-py', action='store_true', help='with --bands --bench-py: skip the decode legs')
+    p.add_argument('--bank', action='store_true')
+    p.add_argument('--bank-files', type=int, default=4096)
     a = p.parse_args()
+    if a.bank:
+        a.band_rows = [16, 8] if a.band_rows == [8, 16, 32] else a.band_rows
+        return bank_main(a)
     if a.bands:
         return bands_main(a)
     if not torch.cuda.is_available():
