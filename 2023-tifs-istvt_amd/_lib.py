@@ -94,8 +94,12 @@ SIGNATURES = {
     'istvt_png_decode_bands_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_png_decode_bank_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I],
     'istvt_png_decode_bank_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I],
+    'istvt_png_decode_alone_u8': [ctypes.POINTER(JpegDecodeArgs), I],
+    'istvt_png_decode_bank_alone_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I],
+    'istvt_png_decode_bank_alone_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I],
     'istvt_png_encode_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_png_encode_indexed_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
+    'istvt_png_encode_alone_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_jpeg_bank_ingest': [ctypes.POINTER(JpegEncodeArgs), I],
     'istvt_jpeg_encode_u8': [ctypes.POINTER(JpegEncodeArgs)],
     'istvt_jpeg_encode_opt_u8': [ctypes.POINTER(JpegEncodeArgs), I, I],

@@ -3021,6 +3021,10 @@ PNG_STATUS = {1: 'the stream ends early', 2: 'a reserved block type, or a stored
 PNG_BAND_STATUS = {7: 'the band index disagrees with the stream'}
 PNG_BAND_CHUNK = b'baND'                    # ancillary, private, reserved bit clear, not safe to copy: it describes the IDAT bytes
 PNG_BAND_INTS = 5                           # a row of PngBatch.bands: ISTVT_PNG_BAND_INTS of include/istvt_hip.h
+PNG_BAND_ALONE = 0x80000000                 # bit 31 of the R word of a baND chunk: ISTVT_PNG_BAND_ALONE of include/istvt_hip.h
+# the status only a decode of bands that stand alone gives (png_decode_alone_host, ops.png_decode_u8 on a batch packed with
+# alone=True, the bank's decode of an alone bank); check_png_status words it too
+PNG_ALONE_STATUS = {10: "the index says its bands stand alone, and a band's first row is filtered against the row above"}
 _PNG_LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 _PNG_LEXT = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
 _PNG_DBASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
@@ -3032,7 +3036,10 @@ _PNG_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 1
 class PngHeader:
     """What png_parse reads from one file: H, W, colour_type (0 grey, 2 RGB, 6 RGBA), bpp (1, 3 or 4 bytes per pixel) and
     data, the raw DEFLATE bytes of the joined IDAT chunks without the zlib header and the Adler-32.  bands: (R, offsets) of a
-    usable baND chunk (_png_band_index), else None."""
+    usable baND chunk (_png_band_index), else None.  alone: True where that chunk is usable and its R word carries
+    PNG_BAND_ALONE, the writer's word that no band's first row is filtered against the row above (png_decode_alone_host
+    checks it); bands holds R without the bit."""
+    alone = False
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -3116,7 +3123,8 @@ def png_parse(data) -> PngHeader:
     z = b''.join(idat)
     if len(z) < 6 or (z[0] & 15) != 8 or (z[0] >> 4) > 7 or (z[1] & 0x20) or ((z[0] << 8) | z[1]) % 31:
         _png_refuse('a bad zlib header (method 8, a window of at most 32 KiB and no preset dictionary are taken)')
-    return PngHeader(H=H, W=W, colour_type=ct, bpp=PNG_BPP[ct], data=z[2:-4], bands=_png_band_index(index, H, len(z)))
+    bands, alone = _png_band_index(index, H, len(z), flag=True)
+    return PngHeader(H=H, W=W, colour_type=ct, bpp=PNG_BPP[ct], data=z[2:-4], bands=bands, alone=alone)
 
 
 def png_band_chunk_bytes(H: int, band_rows: int) -> int:
@@ -3124,21 +3132,31 @@ def png_band_chunk_bytes(H: int, band_rows: int) -> int:
     return 12 + 8 + 4 * (-(-int(H) // int(band_rows)) + 1)
 
 
-def _png_band_chunk(R: int, offsets) -> bytes:
+def _png_band_chunk(R: int, offsets, alone: bool = False) -> bytes:
     """The band index of one file, the chunk that stands between IHDR and IDAT.  The body is big-endian uint32 words: R, the
     band rows; nb = ceil(H / R); nb + 1 offsets into the zlib stream (the joined IDAT bodies), off[0] = 2 behind the zlib
     header, off[nb] = the stream's length - 4 in front of the Adler-32.  Band k is stream bytes [off[k], off[k + 1]) and holds
-    rows [k R, min(H, (k + 1) R)) with their filter bytes."""
+    rows [k R, min(H, (k + 1) R)) with their filter bytes.  alone: the R word carries PNG_BAND_ALONE (R <= 16384, so the
+    bit is free); nothing else of the chunk differs."""
     import zlib
-    body = b''.join(int(v).to_bytes(4, 'big') for v in [R, len(offsets) - 1] + list(offsets))
+    body = b''.join(int(v).to_bytes(4, 'big') for v in [R | (PNG_BAND_ALONE if alone else 0), len(offsets) - 1] + list(offsets))
     return len(body).to_bytes(4, 'big') + PNG_BAND_CHUNK + body + zlib.crc32(PNG_BAND_CHUNK + body).to_bytes(4, 'big')
 
 
-def _png_band_index(chunks, H: int, stream_bytes: int):
+def _png_band_index(chunks, H: int, stream_bytes: int, flag: bool = False):
     """[(body, stands before the first IDAT)] of a file's baND chunks -> (R, [off[0] .. off[nb]]), or None where the index is
     not taken: not exactly one chunk, one behind an IDAT, a length that is not 8 + 4 (nb + 1) for the nb = ceil(H / R) of its
     own R >= 1, an nb that is not that, off[0] != 2, offsets that do not increase strictly, or off[nb] != the stream's length
-    - 4.  Never a refusal: the chunk is ancillary, and a decoder that ignores it is a correct one."""
+    - 4.  Never a refusal: the chunk is ancillary, and a decoder that ignores it is a correct one.  flag=True (png_parse):
+    PNG_BAND_ALONE is taken off the R word before these checks -> ((R, offsets) or None, the bit where the index is taken);
+    without it the word is R as it stands, and one with the bit matches no nb."""
+    if flag:
+        if len(chunks) != 1 or len(chunks[0][0]) < 4:
+            return None, False
+        word = int.from_bytes(chunks[0][0][:4], 'big')
+        body = (word & ~PNG_BAND_ALONE).to_bytes(4, 'big') + chunks[0][0][4:]
+        bands = _png_band_index([(body, chunks[0][1])], H, stream_bytes)
+        return bands, bands is not None and bool(word & PNG_BAND_ALONE)
     if len(chunks) != 1 or not chunks[0][1]:
         return None
     body = chunks[0][0]
@@ -3447,6 +3465,46 @@ def png_decode_bands_host(data, return_status: bool = False):
     return (out, status) if return_status else out
 
 
+def _png_alone_rows(raw, statuses, H: int, W: int, bpp: int, R: int):
+    """The filtered rows of a file whose index says its bands of R rows stand alone, with its band statuses -> (frame uint8
+    (H, W, 3), status) by the precedence of png_decode_alone_host.  The bands are unfiltered one by one, each from a zero row."""
+    import numpy as np
+    status = next((s for s in statuses if s), 0)
+    rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(H, -1) if status == 0 else None
+    if status == 0 and int(rows[:, 0].max()) > 4:
+        status = 6
+    if status == 0 and any(int(rows[r, 0]) >= 2 for r in range(R, H, R)):
+        status = 10
+    if status:
+        return torch.zeros((H, W, 3), dtype=torch.uint8), status
+    px = np.concatenate([_png_unfilter(rows[r0:r0 + R], bpp) for r0 in range(0, H, R)], axis=0)
+    px = torch.from_numpy(px).reshape(H, W, bpp)
+    return (px.expand(H, W, 3).contiguous() if bpp == 1 else px[:, :, :3].contiguous()), 0
+
+
+def png_decode_alone_host(data, return_status: bool = False):
+    """The definition of ops.png_decode_u8 on a batch packed with alone=True, integers only: one file (bytes, or a PngHeader)
+    -> uint8 (H, W, 3), with return_status=True (frame, status).  A file whose header has alone == False is
+    png_decode_bands_host, bytes and status.  A file with alone == True inflates every band as png_inflate_bands_host does and
+    is then unfiltered band by band, each band on its own: rows [k R, min(H, (k + 1) R)) by _png_unfilter with a zero row above
+    the band's first.  Status 10 (PNG_ALONE_STATUS): a row k R, k >= 1, has filter type 2, 3 or 4 -- the file lies; row 0 may
+    have any type, PNG defines it with a zero row above.  Precedence for the whole file: the inflate status of the first
+    failing band in band order; then 6, a filter byte above 4 anywhere; then 10.  Any status other than 0 gives a frame of
+    zeros.
+    Why status 0 gives png_decode_host's frame: by induction over the bands.  png_decode_bands_host's induction gives the
+    same filtered rows as the sequential inflate.  Say rows [0, k R) are reconstructed as _png_unfilter of the whole file
+    reconstructs them (nothing to show for k = 0).  Row k R has type 0 or 1 (status 10 is absent; for k = 0 the row above
+    is zero in both), so its reconstruction reads the row's own bytes only and is the same with a zero row above as with row
+    k R - 1 above.  Every later row of the band reads its own bytes and the row above, which lies in the band and is the same
+    by the step before.  So band k's rows agree, and with them rows [0, (k + 1) R)."""
+    hd = data if isinstance(data, PngHeader) else png_parse(data)
+    if not hd.alone:
+        return png_decode_bands_host(hd, return_status)
+    raw, statuses = png_inflate_bands_host(hd)
+    out, status = _png_alone_rows(raw, statuses, hd.H, hd.W, hd.bpp, hd.bands[0])
+    return (out, status) if return_status else out
+
+
 def png_encode_host(frame, filters=None, level: int = 6, strategy: int = 0, idat: Optional[int] = None) -> bytes:
     """A PNG file of `frame`, uint8 (H, W) grey, (H, W, 3) RGB or (H, W, 4) RGBA (a tensor or an array): host only, for tests
     and users.  filters: one filter type 0..4 per row (None: 0 on every row).  zlib.compressobj(level, DEFLATED, 15, 9,
@@ -3501,10 +3559,13 @@ class PngBatch:
     H, W, colour type, bpp, begin, end, 0, 0 | sizes: [(H, W)] | raw_stride: the largest H (1 + W bpp) of the batch, rounded up
     to 16 | raw_bytes: the filtered bytes of all files.  bands: None, or with png_batch(bands='index') int32 (nband, 5), the
     bands of all files sorted by file, then by band: file, first byte in data, end byte, first output byte within the file's
-    filtered rows, output bytes; images[:, 6:8] are then a file's first row of `bands` and its count of them."""
+    filtered rows, output bytes; images[:, 6:8] are then a file's first row of `bands` and its count of them.  alone: None, or
+    with png_batch(bands='index', alone=True) int32 (n,): 1 where the file's header says its bands stand alone, else 0; such a
+    batch is decoded by istvt_png_decode_alone_u8, the flagged files one wave per band in the unfilter too."""
 
     def __init__(self, **kw):
         self.bands = None
+        self.alone = None
         self.__dict__.update(kw)
         self._on = {}
 
@@ -3519,7 +3580,7 @@ class PngBatch:
         stream that is current at the first call"""
         key = str(device)
         if key not in self._on:
-            names = ('data', 'images') + (() if self.bands is None else ('bands',))
+            names = ('data', 'images') + (() if self.bands is None else ('bands',)) + (() if self.alone is None else ('alone',))
             self._on[key] = SimpleNamespace(**{k: getattr(self, k).to(device, non_blocking=True) for k in names})
         return self._on[key]
 
@@ -3531,19 +3592,27 @@ def check_png_bands(bands, who: str = 'png_batch'):
     raise ValueError("%s: bands is None or 'index', got %r" % (who, bands))
 
 
-def png_batch(files, bands=None) -> PngBatch:
+def png_batch(files, bands=None, alone: bool = False) -> PngBatch:
     """A sequence of PNG files (bytes, or PngHeaders) -> the PngBatch of one launch.  Every file goes through png_parse, so a
     file the decoder does not take is refused here, before anything is uploaded.  bands='index': the batch carries the band
     table of the files' baND chunks (png_band_table), one band for a file without a usable chunk, and ops.png_decode_u8
-    decodes it one wave per band; bands=None: the batch of the sequential decoder, whatever chunks the files have."""
+    decodes it one wave per band; bands=None: the batch of the sequential decoder, whatever chunks the files have.
+    alone=True (needs bands='index'): the batch carries .alone, every file's flag, and the files whose index says their bands
+    stand alone are unfiltered one wave per band as well (png_decode_alone_host); a file without the flag is decoded as
+    without the keyword.  Without alone=True the flag is not looked at: the serial unfilter gives the right pixels either way."""
     check_png_bands(bands)
+    if not isinstance(alone, bool):
+        raise ValueError('png_batch: alone is True or False, got %r' % (alone,))
+    if alone and bands != 'index':
+        raise ValueError("png_batch: alone=True needs bands='index' (the flag lives in the band index)")
     files = list(files)
     if not files:
         raise ValueError('png_batch: an empty batch')
-    parts, images, sizes, nbytes, stride, raw, table = [], [], [], 0, 16, 0, []
+    parts, images, sizes, nbytes, stride, raw, table, flags = [], [], [], 0, 16, 0, [], []
     for f in files:
         hd = f if isinstance(f, PngHeader) else png_parse(f)
         images.append([hd.H, hd.W, hd.colour_type, hd.bpp, nbytes, nbytes + len(hd.data), 0, 0])
+        flags.append(int(bool(hd.alone)))
         if bands is not None:
             rows = png_band_table(hd, len(images) - 1, nbytes)
             images[-1][6:8] = [len(table), len(rows)]
@@ -3562,7 +3631,7 @@ def png_batch(files, bands=None) -> PngBatch:
         return t.pin_memory() if pin and t.numel() else t
     data = torch.frombuffer(bytearray(b''.join(parts) or bytes(16)), dtype=torch.uint8)
     return PngBatch(data=host(data), nbytes=nbytes, images=host(torch.tensor(images, dtype=torch.int32)), sizes=sizes,
-                    n=len(files), raw_stride=stride, raw_bytes=raw,
+                    n=len(files), raw_stride=stride, raw_bytes=raw, alone=host(torch.tensor(flags, dtype=torch.int32)) if alone else None,
                     bands=None if bands is None else host(torch.tensor(table, dtype=torch.int32).reshape(-1, PNG_BAND_INTS)))
 
 
@@ -3571,7 +3640,8 @@ def check_png_status(status) -> None:
     for i, s in enumerate(status.detach().cpu().tolist()):
         if s != 0:
             raise ValueError('png_decode: file %d is damaged (status %d: %s)'
-                             % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s) or PNG_BANK_STATUS.get(s, 'unknown')))
+                             % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s) or PNG_BANK_STATUS.get(s)
+                                or PNG_ALONE_STATUS.get(s, 'unknown')))
 
 
 # ---- PNG bank (DESIGN.md "PNG bank") --------------------------------------------------------------------------------------------
@@ -3587,15 +3657,18 @@ PNG_BANK_STATUS = {8: 'the index is outside the bank', 9: "the bank's row for th
 class PngBank:
     """A set of PNG files ready for ops.png_decode_bank_u8 (png_bank makes it): host tensors, pinned where a device is there to
     take them.  data uint8: the raw DEFLATE streams end to end, each starting at a multiple of 16 bytes | images int32 (n, 10):
-    H, W, colour type, bpp, base low word, base high word, stream bytes, first band row, band count, 0; the base is the 64-bit
+    H, W, colour type, bpp, base low word, base high word, stream bytes, first band row, band count, flags (bit 0 in a bank
+    packed with alone=True: the file's bands stand alone; else 0); the base is the 64-bit
     byte offset of the file's stream on the device, first_byte included, and a multiple of 16 | bands int32 (nband, 5), rows
     of png_band_table sorted by file, then by band, with begin and end counted from the file's base | sizes: [(H, W)] | n,
     nband | nbytes: the streams' bytes with their padding, a Python int that may exceed 2^31 | Hmax, Wmax | raw_stride: the
     largest H (1 + W bpp), rounded up to 16 | band_max: the most bands of any file | first_byte: where the first stream
-    starts on the device | headers: the parsed files."""
+    starts on the device | headers: the parsed files | alone: True for png_bank(alone=True), whose decode unfilters the
+    flagged files one wave per band (istvt_png_decode_bank_alone_u8)."""
 
     def __init__(self, **kw):
         self.device = None                                        # ops.png_decode_bank_u8 reads it as it does a JpegBank's
+        self.alone = False
         self.__dict__.update(kw)
         self._on = {}
 
@@ -3615,13 +3688,19 @@ class PngBank:
         return self._on[key]
 
 
-def png_bank(files, bands='index', first_byte: int = 0) -> PngBank:
+def png_bank(files, bands='index', first_byte: int = 0, alone: bool = False) -> PngBank:
     """A sequence of PNG files (bytes, or PngHeaders) -> the PngBank of the set, on the host.  Every file goes through
     png_parse, which refuses what the decoder does not take.  bands='index' (the default): a file's bands are those of its
     baND chunk where png_parse accepts it, and a file without a usable chunk is one band; bands=None: every file is one band.
     first_byte (a multiple of 16, for tests): the first stream starts there on the device, and the bytes in front are
-    allocated and never read.  A single stream of PNG_MAX_BYTES or more is refused; the set as a whole has no such bound."""
+    allocated and never read.  A single stream of PNG_MAX_BYTES or more is refused; the set as a whole has no such bound.
+    alone=True (needs bands='index'): bit 0 of images[:, 9] is the file's flag (PngHeader.alone), and the bank's decode
+    unfilters the flagged files one wave per band; a file without the flag is decoded as in any other bank."""
     check_png_bands(bands, 'png_bank')
+    if not isinstance(alone, bool):
+        raise ValueError('png_bank: alone is True or False, got %r' % (alone,))
+    if alone and bands != 'index':
+        raise ValueError("png_bank: alone=True needs bands='index' (the flag lives in the band index)")
     if isinstance(first_byte, bool) or not isinstance(first_byte, int) or first_byte < 0 or first_byte % 16:
         raise ValueError('png_bank: first_byte is a multiple of 16 and not negative, got %r' % (first_byte,))
     if isinstance(files, (bytes, bytearray)) or not hasattr(files, '__len__'):
@@ -3638,7 +3717,8 @@ def png_bank(files, bands='index', first_byte: int = 0) -> PngBank:
                                                                          data=hd.data, bands=None)
         rows = png_band_table(one, i, 0)
         base = first_byte + nbytes
-        images.append([hd.H, hd.W, hd.colour_type, hd.bpp, base & 0xffffffff, base >> 32, len(hd.data), len(table), len(rows), 0])
+        images.append([hd.H, hd.W, hd.colour_type, hd.bpp, base & 0xffffffff, base >> 32, len(hd.data), len(table), len(rows),
+                       int(alone and bool(hd.alone))])
         table += rows
         band_max = max(band_max, len(rows))
         pad = -len(hd.data) % 16
@@ -3655,7 +3735,8 @@ def png_bank(files, bands='index', first_byte: int = 0) -> PngBank:
     return PngBank(data=host(data), nbytes=int(data.numel()), images=host(words.to(torch.int32)),
                    bands=host(torch.tensor(table, dtype=torch.int32).reshape(-1, PNG_BAND_INTS)),
                    sizes=[(hd.H, hd.W) for hd in headers], n=len(headers), nband=len(table), Hmax=max(hd.H for hd in headers),
-                   Wmax=max(hd.W for hd in headers), raw_stride=stride, band_max=band_max, first_byte=first_byte, headers=headers)
+                   Wmax=max(hd.W for hd in headers), raw_stride=stride, band_max=band_max, first_byte=first_byte, headers=headers,
+                   alone=alone)
 
 
 def png_bank_scratch_bytes(bank: PngBank, m: int) -> int:
@@ -3665,12 +3746,29 @@ def png_bank_scratch_bytes(bank: PngBank, m: int) -> int:
     return m * bank.raw_stride + 4 * m * bank.band_max
 
 
+def _png_alone_band_rows(H: int, stride: int, rows) -> int:
+    """The band rows of a file that says its bands stand alone -> R, the rows of a band, where they are the R-row bands of an
+    index, else 0 (pa_alone_rows and pa_band_row_fits of csrc/png_alone.h): R = out_bytes of band row 0 / stride, a whole
+    number of at least 1; count == ceil(H / R); band k writes out == k R stride and out_bytes == rows_k stride.  A row that
+    is not inside the table (None) fails."""
+    if not rows or rows[0] is None or rows[0][4] < stride or rows[0][4] % stride:
+        return 0
+    R = rows[0][4] // stride
+    if len(rows) != -(-H // R):
+        return 0
+    for k, row in enumerate(rows):
+        if row is None or row[3] != k * R * stride or row[4] != (min(H, (k + 1) * R) - k * R) * stride:
+            return 0
+    return R
+
+
 def _png_bank_place(bank: PngBank, i: int, Hc: int, Wc: int):
     """Place i of the bank from its own rows and bytes, as csrc/png_bank.h reads them -> (frame uint8 (H, W, 3) or None, H, W,
     status).  Status 9 and no frame where the image row or a band row does not fit the bank."""
     import numpy as np
     im = bank.images[i].tolist()
     H, W, ct, bpp, lo, hi, nstream, first, count = im[:9]
+    alone = bool(bank.alone and im[9] & 1)
     base = ((hi & 0xffffffff) << 32) | (lo & 0xffffffff)
     if base >= 2 ** 63:
         base -= 2 ** 64
@@ -3692,6 +3790,13 @@ def _png_bank_place(bank: PngBank, i: int, Hc: int, Wc: int):
         out, status = _png_inflate(stream[begin:end], nout, middle=k < count - 1)
         raw[at:at + len(out)] = out
         statuses.append(status)
+    if alone:
+        R = _png_alone_band_rows(H, 1 + W * bpp, [bank.bands[first + k].tolist() if 0 <= first and first + k < bank.nband else None
+                                                  for k in range(count)])
+        if R == 0:
+            return None, 0, 0, 9
+        frame, status = _png_alone_rows(raw, statuses, H, W, bpp, R)
+        return (None, 0, 0, 9) if status == 9 else (frame, H, W, status)
     status = next((s for s in statuses if s), 0)
     rows = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(H, -1) if status == 0 else None
     if status == 0 and int(rows[:, 0].max()) > 4:
@@ -3709,7 +3814,9 @@ def png_bank_decode_host(bank_or_files, index, canvas=None):
     first), so it says what the tables mean: a file packed as one band gives png_decode_host's result.  Beside the statuses of
     png_decode_bands_host: 8 where index[j] is outside [0, n), 9 where the bank's row for the place or one of its band rows
     does not fit (PNG_BANK_STATUS); both with size (0, 0) and a frame of zeros.  canvas = (Hc, Wc) defaults to the bank's
-    Hmax x Wmax, whatever is drawn."""
+    Hmax x Wmax, whatever is drawn.  A bank packed with alone=True places png_decode_alone_host for its flagged files: status
+    10 (PNG_ALONE_STATUS) keeps the file's size and zeroes the frame, like statuses 1 to 7; a flagged file whose band rows
+    are not the R-row bands of an index (_png_alone_band_rows) is status 9."""
     bank = bank_or_files if isinstance(bank_or_files, PngBank) else png_bank(bank_or_files)
     index = check_bank_index(index, 'png_bank_decode_host').tolist()
     Hc, Wc = (bank.Hmax, bank.Wmax) if canvas is None else (int(canvas[0]), int(canvas[1]))
@@ -3973,13 +4080,20 @@ def check_png_band_rows(band_rows, who: str = 'png_encode_banded_host') -> int:
     return min(int(band_rows), PNG_MAX_SIDE)
 
 
-def png_filter_rows_host(frame, filters='adaptive'):
+def png_filter_rows_host(frame, filters='adaptive', alone_rows=None):
     """frame -> the filtered rows uint8 (H, 1 + W bpp) with their filter bytes.  The predictors are png_encode_host's: a and c
     are zero at the row's start, b and c on the image's first row, and the row above is the source's.  'adaptive': per row the
-    type whose residuals r have the smallest sum of min(r, 256 - r); of equal sums the lowest type."""
+    type whose residuals r have the smallest sum of min(r, 256 - r); of equal sums the lowest type.
+    alone_rows = R: every row r with r % R == 0, row 0 included, is restricted to the types that do not read the row above.
+    'adaptive' takes the cheaper of 0 and 1 by the same cost, of equal sums 0; a fixed 0 or 1 stays; a fixed 2 becomes 0 (Up
+    against a zero row is None); a fixed 3 or 4 becomes 1 (Paeth with b = c = 0 is Sub; Average has no equal, Sub is the
+    choice).  Every other row is byte for byte what it is without alone_rows: a row's filtered bytes depend on the source
+    rows only."""
     import numpy as np
     px, bpp = _png_frame(frame, 'png_encode_banded_host')
     mode = check_png_filters(filters)
+    if alone_rows is not None:
+        alone_rows = check_png_band_rows(alone_rows)
     H, W = px.shape[:2]
     cur = px.reshape(H, W * bpp).astype(np.int64)
     a = np.concatenate([np.zeros((H, bpp), np.int64), cur[:, :-bpp]], axis=1) if W > 1 else np.zeros_like(cur)
@@ -3992,13 +4106,28 @@ def png_filter_rows_host(frame, filters='adaptive'):
         ft = np.argmin(np.minimum(res, 256 - res).sum(axis=2), axis=0)
     else:
         ft = np.full(H, mode, dtype=np.int64)
+    if alone_rows is not None:
+        first = np.arange(0, H, alone_rows)
+        if mode == 5:
+            ft[first] = np.argmin(np.minimum(res[:2, first], 256 - res[:2, first]).sum(axis=2), axis=0)
+        else:
+            ft[first] = (0, 1, 0, 1, 1)[mode]
     rows = np.empty((H, 1 + W * bpp), dtype=np.uint8)
     rows[:, 0] = ft
     rows[:, 1:] = res[ft, np.arange(H)].astype(np.uint8)
     return rows
 
 
-def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', return_bands: bool = False, index: bool = False):
+def _check_png_alone(alone, index, who: str) -> bool:
+    if not isinstance(alone, bool):
+        raise ValueError('%s: alone is True or False, got %r' % (who, alone))
+    if alone and not index:
+        raise ValueError('%s: alone=True needs index=True (the flag lives in the band index)' % who)
+    return alone
+
+
+def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', return_bands: bool = False, index: bool = False,
+                           alone: bool = False):
     """The definition of ops.png_encode_u8, integers only: frame uint8 (H, W) / (H, W, 1) grey, (H, W, 3) RGB or (H, W, 4) RGBA
     -> a complete PNG file: signature, IHDR, one IDAT, IEND.  Rows [k R, min(H, (k + 1) R)) with their filter bytes
     (png_filter_rows_host) are band k, R = band_rows, coded on its own by _png_encode_band: tokens by _png_band_tokens, both
@@ -4008,12 +4137,16 @@ def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', retur
     itself.  The stream is 78 01, the bands, the Adler-32 of the filtered rows.  return_bands=True: (file, [(begin, end)] of
     every band in the stream, whose first band begins at 2, the filter type of every row).  index=True (the definition of
     ops.png_encode_u8(index=True)): the file carries the bands' offsets in a baND chunk (_png_band_chunk, with R =
-    min(band_rows, H)) between IHDR and IDAT, for a decoder that takes the bands apart; every other byte is the same."""
+    min(band_rows, H)) between IHDR and IDAT, for a decoder that takes the bands apart; every other byte is the same.
+    alone=True (the definition of ops.png_encode_u8(alone=True); needs index=True): every band's first row is filtered without
+    the row above (png_filter_rows_host(alone_rows=R)) and the chunk's R word carries PNG_BAND_ALONE, so a band decodes to
+    pixels with no other band (png_decode_alone_host)."""
     import zlib
     if not isinstance(index, bool):
         raise ValueError('png_encode_banded_host: index is True or False, got %r' % (index,))
+    _check_png_alone(alone, index, 'png_encode_banded_host')
     R = check_png_band_rows(band_rows)
-    rows = png_filter_rows_host(frame, filters)
+    rows = png_filter_rows_host(frame, filters, R if alone else None)
     H, bpp = rows.shape[0], _png_frame(frame, 'png_encode_banded_host')[1]
     W = (rows.shape[1] - 1) // bpp
     stream, bands = bytearray(b'\x78\x01'), []
@@ -4022,12 +4155,12 @@ def png_encode_banded_host(frame, band_rows: int = 16, filters='adaptive', retur
         bands.append((len(stream), len(stream) + len(part)))
         stream += part
     stream += zlib.adler32(rows.tobytes()).to_bytes(4, 'big')
-    extra = _png_band_chunk(min(R, H), [b for b, _ in bands] + [bands[-1][1]]) if index else b''
+    extra = _png_band_chunk(min(R, H), [b for b, _ in bands] + [bands[-1][1]], alone) if index else b''
     data = png_wrap(H, W, {1: 0, 3: 2, 4: 6}[bpp], bytes(stream), extra=extra)
     return (data, bands, rows[:, 0].tolist()) if return_bands else data
 
 
-def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive', index: bool = False) -> list:
+def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive', index: bool = False, alone: bool = False) -> list:
     """the files of a batch: frames uint8 (n, H, W), (n, H, W, 1 | 3 | 4) or clips (B, T, H, W, C) -> [bytes], one
     png_encode_banded_host each"""
     import numpy as np
@@ -4036,10 +4169,10 @@ def png_encode_files_host(frames, band_rows: int = 16, filters='adaptive', index
         px = px.reshape((-1,) + px.shape[2:])
     if px.ndim not in (3, 4):
         raise ValueError('png_encode_files_host: frames (n, H, W), (n, H, W, C) or (B, T, H, W, C), got %s' % (px.shape,))
-    return [png_encode_banded_host(f, band_rows, filters, index=index) for f in px]
+    return [png_encode_banded_host(f, band_rows, filters, index=index, alone=alone) for f in px]
 
 
-def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16, index: bool = False) -> int:
+def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16, index: bool = False, alone: bool = False) -> int:
     """The bytes one file of png_encode_banded_host needs at the most.  A band of nb bytes (rows (1 + W bpp)) is at most nb
     tokens and the end-of-block.  The code `256 literals of 9 bits, the end-of-block and the 29 length symbols of 6` is a
     prefix code (256 / 512 + 30 / 64 < 1), and under it a literal costs 9 bits and a match 6 + 5 extra + 1 distance = 12 for
@@ -4051,7 +4184,9 @@ def png_encoded_bound(H: int, W: int, bpp: int, band_rows: int = 16, index: bool
     Nothing rests on it but the default capacity: the kernels check the capacity themselves and report status 1.  The block
     header is at most PNG_BAND_HEADER_BITS = 17
     + 19 * 3 + 287 * 7 bits.  The empty stored block is 3 bits, the pad to the byte and 4 bytes.  Bands of a file: ceil(H /
-    R).  The container is 57 + 6 bytes; index=True adds the baND chunk's png_band_chunk_bytes(H, R)."""
+    R).  The container is 57 + 6 bytes; index=True adds the baND chunk's png_band_chunk_bytes(H, R).  alone=True (needs
+    index=True) changes filter types only: the indexed bound, unchanged."""
+    _check_png_alone(alone, index, 'png_encoded_bound')
     H, W, bpp, R = int(H), int(W), int(bpp), check_png_band_rows(band_rows, 'png_encoded_bound')
     stride, total = 1 + W * bpp, PNG_CONTAINER_BYTES + (png_band_chunk_bytes(H, R) if index else 0)
     for r0 in range(0, H, R):
@@ -4064,5 +4199,5 @@ class PngFiles(_EncodedFiles):
     """What ops.png_encode_u8 hands back, on the device, with JpegFiles' semantics: data uint8 (capacity,): the files end to
     end | offsets int64 (n + 1,): file i is data[offsets[i]:offsets[i + 1]] | status int32 (n,): 0 fine, 1 as
     PNG_ENCODE_STATUS words it (files() hands b'' over for it with check=False).  geometry: H, W, bpp, band_rows, filters,
-    index."""
+    index, alone."""
     _name, _who, _status, _empty = 'PngFiles', 'png_encode', PNG_ENCODE_STATUS, (1,)

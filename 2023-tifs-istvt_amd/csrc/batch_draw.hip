@@ -96,3 +96,11 @@ extern "C" int istvt_png_decode_bank_drawn_u8(const istvt_jpeg_decode_args* a, i
     const int rc = bd_draw_then(a, B, T, block_ints, indexed);
     return rc != ISTVT_OK ? rc : istvt_png_decode_bank_u8(&indexed, B * T, band_max, raw_stride);
 }
+
+// The same in front of istvt_png_decode_bank_alone_u8 (csrc/png_alone.hip), for a bank packed with clips.png_bank(alone=True)
+extern "C" int istvt_png_decode_bank_alone_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max,
+                                                    int raw_stride) {
+    istvt_jpeg_decode_args indexed;
+    const int rc = bd_draw_then(a, B, T, block_ints, indexed);
+    return rc != ISTVT_OK ? rc : istvt_png_decode_bank_alone_u8(&indexed, B * T, band_max, raw_stride);
+}

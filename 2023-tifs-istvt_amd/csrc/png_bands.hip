@@ -9,6 +9,7 @@
 #include "common.h"
 #include "istvt_hip.h"
 #include "png_inflate.h"
+#include "png_launch.h"
 #include "png_unfilter.h"
 
 namespace {
@@ -64,19 +65,30 @@ bool png_bands_check(const istvt_jpeg_decode_args* a) {
 
 }  // namespace
 
+// What istvt_png_decode_bands_u8 refuses, and its first launch: csrc/png_alone.hip puts its own unfilter behind the same two
+// (csrc/png_launch.h declares them)
+bool png_bands_args_ok(const istvt_jpeg_decode_args* a, int raw_stride) {
+    if (!png_decode_args_ok(a, raw_stride) || !png_bands_check(a)) return false;
+    return a->scratch_bytes >= (long)a->n * raw_stride + (long)a->nseg * (long)sizeof(int);
+}
+
+int png_bands_inflate_launch(const istvt_jpeg_decode_args* a, int raw_stride) {
+    uint8_t* scratch = (uint8_t*)a->scratch;
+    int* band_status = reinterpret_cast<int*>(scratch + (long)a->n * raw_stride);    // a multiple of 16: the status words start there
+    hipLaunchKernelGGL(png_inflate_bands_kernel, dim3((unsigned)a->nseg), dim3(64), 0, a->stream, (const uint8_t*)a->bytes, a->images,
+                       a->segments, scratch, (long)raw_stride, band_status);
+    return istvt_check_launch();
+}
+
 // The same batch with a band table (clips.png_batch(bands='index')): one wave per band inflates, one wave per file unfilters.
 // Two launches, no synchronisation, no global state; the band statuses live in the scratch behind the filtered rows.
 extern "C" int istvt_png_decode_bands_u8(const istvt_jpeg_decode_args* a, int raw_stride) {
-    if (!png_decode_args_ok(a, raw_stride) || !png_bands_check(a)) return ISTVT_ERR_SHAPE;
-    const long rows = (long)a->n * raw_stride;                   // a multiple of 16: the status words start there
-    if (a->scratch_bytes < rows + (long)a->nseg * (long)sizeof(int)) return ISTVT_ERR_SHAPE;
-    uint8_t* scratch = (uint8_t*)a->scratch;
-    int* band_status = reinterpret_cast<int*>(scratch + rows);
-    hipLaunchKernelGGL(png_inflate_bands_kernel, dim3((unsigned)a->nseg), dim3(64), 0, a->stream, (const uint8_t*)a->bytes, a->images,
-                       a->segments, scratch, (long)raw_stride, band_status);
-    int rc = istvt_check_launch();
+    if (!png_bands_args_ok(a, raw_stride)) return ISTVT_ERR_SHAPE;
+    const int rc = png_bands_inflate_launch(a, raw_stride);
     if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(png_unfilter_bands_kernel, dim3((unsigned)a->n), dim3(64), 0, a->stream, a->images, (const int*)band_status, scratch,
+    uint8_t* scratch = (uint8_t*)a->scratch;
+    const int* band_status = reinterpret_cast<const int*>(scratch + (long)a->n * raw_stride);
+    hipLaunchKernelGGL(png_unfilter_bands_kernel, dim3((unsigned)a->n), dim3(64), 0, a->stream, a->images, band_status, scratch,
                        (long)raw_stride, (uint8_t*)a->out, a->Hc, a->Wc, a->sizes, a->status);
     return istvt_check_launch();
 }

@@ -23,7 +23,8 @@
 #define PK_OUTSIDE 8                       // index[j] is outside [0, n)
 #define PK_ROW 9                           // the bank's row for the place, or one of its band rows, does not fit the call
 
-enum { PK_H = 0, PK_W = 1, PK_TYPE = 2, PK_BPP = 3, PK_BASE_LO = 4, PK_BASE_HI = 5, PK_BYTES = 6, PK_FIRST_BAND = 7, PK_BANDS = 8 };
+enum { PK_H = 0, PK_W = 1, PK_TYPE = 2, PK_BPP = 3, PK_BASE_LO = 4, PK_BASE_HI = 5, PK_BYTES = 6, PK_FIRST_BAND = 7, PK_BANDS = 8,
+       PK_FLAGS = 9 };                      // read by csrc/png_alone.hip only: bit 0, the file's bands stand alone
 enum { PKB_FILE = 0, PKB_BEGIN = 1, PKB_END = 2, PKB_OUT = 3, PKB_OUT_BYTES = 4 };
 
 // what the checks of a call compare the rows with: the call's scalars, the same for every wave

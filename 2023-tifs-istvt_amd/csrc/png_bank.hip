@@ -11,6 +11,7 @@
 #include "istvt_hip.h"
 #include "png_bank.h"
 #include "png_inflate.h"
+#include "png_launch.h"
 #include "png_unfilter.h"
 
 static_assert(PK_IMAGE_INTS == ISTVT_PNG_BANK_IMAGE_INTS && PK_BAND_INTS == ISTVT_PNG_BAND_INTS, "csrc/png_bank.h and the header disagree");
@@ -65,27 +66,41 @@ __global__ __launch_bounds__(64) void png_bank_unfilter_kernel(const int* __rest
 
 }  // namespace
 
-// The indexed decode of a PNG bank; include/istvt_hip.h describes the arguments.  The checks are on scalars alone, once per
-// call: the tables are on the device, and the kernels check the rows they use.  Two launches, no synchronisation, no global
-// state, no atomics, nothing allocated; the band statuses live in the scratch behind the filtered rows.
-extern "C" int istvt_png_decode_bank_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride) {
-    if (!a) return ISTVT_ERR_SHAPE;
+// What istvt_png_decode_bank_u8 refuses, and its first launch: csrc/png_alone.hip puts its own unfilter behind the same two
+// (csrc/png_launch.h declares them).  The checks are on scalars alone, once per call: the tables are on the device, and the
+// kernels check the rows they use.
+bool png_bank_args_ok(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride, PkCall* call) {
+    if (!a) return false;
     const PkCall c = {a->nbytes, a->n, a->nseg, band_max, raw_stride, a->Hc, a->Wc};
-    if (!pk_scalars_ok(c, m, a->scratch_bytes)) return ISTVT_ERR_SHAPE;
-    if (!a->bytes || !a->images || !a->segments || !a->images_host || !a->scratch || !a->out || !a->sizes || !a->status)
-        return ISTVT_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->bytes) & 15)) return ISTVT_ERR_SHAPE;
+    if (!pk_scalars_ok(c, m, a->scratch_bytes)) return false;
+    if (!a->bytes || !a->images || !a->segments || !a->images_host || !a->scratch || !a->out || !a->sizes || !a->status) return false;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->bytes) & 15)) return false;
     const uint8_t* src = (const uint8_t*)a->bytes;
     const uint8_t* dst = (const uint8_t*)a->out;
-    if (dst < src + a->nbytes && src < dst + (long)m * a->Hc * a->Wc * 3) return ISTVT_ERR_SHAPE;
+    if (dst < src + a->nbytes && src < dst + (long)m * a->Hc * a->Wc * 3) return false;
+    *call = c;
+    return true;
+}
+
+int png_bank_inflate_launch(const istvt_jpeg_decode_args* a, int m, const PkCall& c) {
     uint8_t* scratch = (uint8_t*)a->scratch;
-    int* band_status = reinterpret_cast<int*>(scratch + (long)m * raw_stride);       // a multiple of 16 behind the rows
+    int* band_status = reinterpret_cast<int*>(scratch + (long)m * c.raw_stride);     // a multiple of 16 behind the rows
     const int* index = a->images_host;                           // this entry's reading of the field: the index, on the device
-    hipLaunchKernelGGL(png_bank_inflate_kernel, dim3((unsigned)(m * band_max)), dim3(64), 0, a->stream, (const uint8_t*)a->bytes,
+    hipLaunchKernelGGL(png_bank_inflate_kernel, dim3((unsigned)(m * c.band_max)), dim3(64), 0, a->stream, (const uint8_t*)a->bytes,
                        a->images, a->segments, index, c, scratch, band_status);
-    const int rc = istvt_check_launch();
+    return istvt_check_launch();
+}
+
+// The indexed decode of a PNG bank; include/istvt_hip.h describes the arguments.  Two launches, no synchronisation, no global
+// state, no atomics, nothing allocated; the band statuses live in the scratch behind the filtered rows.
+extern "C" int istvt_png_decode_bank_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride) {
+    PkCall c;
+    if (!png_bank_args_ok(a, m, band_max, raw_stride, &c)) return ISTVT_ERR_SHAPE;
+    const int rc = png_bank_inflate_launch(a, m, c);
     if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(png_bank_unfilter_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, index, c,
-                       (const int*)band_status, scratch, (uint8_t*)a->out, a->sizes, a->status);
+    uint8_t* scratch = (uint8_t*)a->scratch;
+    const int* band_status = reinterpret_cast<const int*>(scratch + (long)m * raw_stride);
+    hipLaunchKernelGGL(png_bank_unfilter_kernel, dim3((unsigned)m), dim3(64), 0, a->stream, a->images, a->images_host, c, band_status,
+                       scratch, (uint8_t*)a->out, a->sizes, a->status);
     return istvt_check_launch();
 }

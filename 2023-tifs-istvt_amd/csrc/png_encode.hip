@@ -40,6 +40,9 @@ __device__ __forceinline__ void pe_fence() {
     __syncthreads();
 }
 
+// ALONE: the band's first row takes a type that does not read the row above (clips.png_filter_rows_host(alone_rows=)): the
+// cheaper of 0 and 1 where the filter is adaptive, of equal sums 0; else 0 for a fixed 0 or 2 and 1 for a fixed 1, 3 or 4
+template <bool ALONE>
 __global__ __launch_bounds__(64) void png_filter_count_kernel(const uint8_t* __restrict__ frames, int H, int W, int bpp, int band_rows,
                                                               int filter, int bands, uint8_t* scratch, long raw_stride,
                                                               int* __restrict__ rows) {
@@ -71,7 +74,9 @@ __global__ __launch_bounds__(64) void png_filter_count_kernel(const uint8_t* __r
             if (s2 < best) best = s2, ft = 2;
             if (s3 < best) best = s3, ft = 3;
             if (s4 < best) best = s4, ft = 4;
+            if (ALONE && r == r0) ft = s1 < s0 ? 1 : 0;
         }
+        if (ALONE && r == r0 && filter != PE_ADAPTIVE) ft = (filter == 0 || filter == 2) ? 0 : 1;
         uint8_t* dst = raw + (long)r * stride;
         if (lane == 0) dst[0] = (uint8_t)ft;
         for (int x = lane; x < rowbytes; x += 64) {
@@ -255,8 +260,9 @@ __global__ __launch_bounds__(PE_CRC_THREADS) void png_container_kernel(const int
     }
 }
 
-// the checks and the four launches of both entries; extra: the bytes of a file's band index, 0 for none
-int pe_encode(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride, bool index) {
+// the checks and the four launches of the three entries; extra: the bytes of a file's band index, 0 for none; alone (with
+// an index only): the filter kernel's restriction, and ISTVT_PNG_BAND_ALONE in the word the container kernel writes as R
+int pe_encode(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride, bool index, bool alone = false) {
     if (!a || a->n <= 0 || a->H < 1 || a->W < 1 || a->H > 16384 || a->W > 16384) return ISTVT_ERR_SHAPE;
     if ((bpp != 1 && bpp != 3 && bpp != 4) || band_rows < 1 || filter < 0 || filter > PE_ADAPTIVE) return ISTVT_ERR_SHAPE;
     if (!a->frames || !a->scratch || !a->data || !a->offsets || !a->status || a->capacity < 1) return ISTVT_ERR_SHAPE;
@@ -274,8 +280,12 @@ int pe_encode(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filte
     if (data < src + a->total && src < data + a->capacity) return ISTVT_ERR_SHAPE;
     uint8_t* scratch = (uint8_t*)a->scratch;
     int* rows = reinterpret_cast<int*>(scratch + (long)a->n * raw_stride);
-    hipLaunchKernelGGL(png_filter_count_kernel, dim3((unsigned)waves), dim3(64), 0, a->stream, src, a->H, a->W, bpp, R, filter, bands,
-                       scratch, (long)raw_stride, rows);
+    if (alone)
+        hipLaunchKernelGGL(png_filter_count_kernel<true>, dim3((unsigned)waves), dim3(64), 0, a->stream, src, a->H, a->W, bpp, R, filter,
+                           bands, scratch, (long)raw_stride, rows);
+    else
+        hipLaunchKernelGGL(png_filter_count_kernel<false>, dim3((unsigned)waves), dim3(64), 0, a->stream, src, a->H, a->W, bpp, R, filter,
+                           bands, scratch, (long)raw_stride, rows);
     int rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
     hipLaunchKernelGGL(png_prefix_kernel, dim3(1), dim3(256), 0, a->stream, rows, bands, a->n, a->capacity, a->offsets, a->status, extra);
@@ -285,7 +295,8 @@ int pe_encode(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filte
                        (const int*)rows, a->H, a->W, bpp, R, bands, data, (const long*)a->offsets, (const int*)a->status, extra);
     rc = istvt_check_launch();
     if (rc != ISTVT_OK) return rc;
-    hipLaunchKernelGGL(png_container_kernel, dim3((unsigned)a->n), dim3(PE_CRC_THREADS), 0, a->stream, (const int*)rows, a->H, a->W, bpp, R,
+    const int word = alone ? (int)((unsigned)R | ISTVT_PNG_BAND_ALONE) : R;       // the kernel reads it for the chunk's R word alone
+    hipLaunchKernelGGL(png_container_kernel, dim3((unsigned)a->n), dim3(PE_CRC_THREADS), 0, a->stream, (const int*)rows, a->H, a->W, bpp, word,
                        bands, data, (const long*)a->offsets, (const int*)a->status, extra);
     return istvt_check_launch();
 }
@@ -300,4 +311,9 @@ extern "C" int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int
 // ... and every file with its band index
 extern "C" int istvt_png_encode_indexed_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride) {
     return pe_encode(a, bpp, band_rows, filter, raw_stride, true);
+}
+
+// ... and every band's first row filtered without the row above, the index saying so
+extern "C" int istvt_png_encode_alone_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride) {
+    return pe_encode(a, bpp, band_rows, filter, raw_stride, true, true);
 }

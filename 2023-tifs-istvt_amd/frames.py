@@ -539,7 +539,11 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
     bands='index' with a sequence of bytes packs it with clips.png_batch(bands='index'); a batch that carries bands, packed
     here or by the caller, is decoded one wave per band of the files' baND chunks (istvt_png_decode_bands_u8, the bytes and
     statuses of clips.png_decode_bands_host; status 7 is clips.PNG_BAND_STATUS's) and its scratch holds a status word per band
-    behind the filtered rows.  A PngBatch is decoded as it was packed: bands= given with one must agree with it."""
+    behind the filtered rows.  A PngBatch is decoded as it was packed: bands= given with one must agree with it.
+    A batch packed with clips.png_batch(bands='index', alone=True) (batch.alone is not None) goes to
+    istvt_png_decode_alone_u8: the files whose index says their bands stand alone are unfiltered one wave per band too, the
+    bytes and statuses of clips.png_decode_alone_host (status 10 is clips.PNG_ALONE_STATUS's); its flags are uploaded with the
+    other tables, and the promises about `out` and `buffers` hold as before."""
     what = 'png_decode_u8'
     clips.check_png_bands(bands, what)
     if isinstance(batch, clips.PngBatch) and bands is not None and batch.bands is None:
@@ -556,12 +560,16 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
     name, nband, short = 'istvt_png_decode_u8', 0, None
     if batch.bands is not None:
         name, nband = 'istvt_png_decode_bands_u8', int(batch.bands.shape[0])
-        dev = SimpleNamespace(data=dev.data, images=dev.images, segments=dev.bands)     # the band table goes where segments do
+        extra = {}
+        if batch.alone is not None:                               # the flags go where qtabs do, their host copy where htabs do
+            name, extra = 'istvt_png_decode_alone_u8', dict(qtabs=dev.alone, htabs=batch.alone)
+        dev = SimpleNamespace(data=dev.data, images=dev.images, segments=dev.bands, **extra)   # the band table goes where segments do
         # said to a scratch that holds the rows but not the band status words
         short = (n * batch.raw_stride, 'png_decode_u8: a batch with bands needs a scratch of %d bytes: %d of filtered rows and a '
                  'status word for each of its %d bands, got %%d' % (need, n * batch.raw_stride, nband))
     scratch, sizes, status = _decode_buffers(what, device, n, need, buffers, short=short)
-    args = _decode_args(dev, batch.images, scratch, out, sizes, status, n, nband, 0, 0, batch.nbytes, Hc, Wc,
+    nflags = 0 if batch.alone is None else n
+    args = _decode_args(dev, batch.images, scratch, out, sizes, status, n, nband, nflags, nflags, batch.nbytes, Hc, Wc,
                         segments_host=batch.bands)
     _call(name, batch.nbytes + 2 * batch.raw_bytes + out.numel(), ctypes.byref(args), batch.raw_stride)
     return out, sizes, status
@@ -680,7 +688,10 @@ def jpeg_decode_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = None, 
 def _png_bank_decode(name: str, bank, index: Tensor, head, dev, Hc: int, Wc: int, out: Tensor, scratch: Tensor, sizes: Tensor,
                      status: Tensor):
     """The call behind _bank_call for a clips.PngBank: the entry istvt_png_decode_<name>_u8, which reads the index at `index` and
-    takes the scalars `head` in front of the bank's band_max and raw_stride -> (out, sizes, status)"""
+    takes the scalars `head` in front of the bank's band_max and raw_stride -> (out, sizes, status).  A bank packed with
+    clips.png_bank(alone=True) goes to the entry's _alone sibling (istvt_png_decode_bank_alone_u8, ..._bank_alone_drawn_u8)."""
+    if bank.alone:
+        name = name.replace('bank', 'bank_alone')
     args = _decode_args(dev, index, scratch, out, sizes, status, bank.n, bank.nband, 0, 0, bank.first_byte + bank.nbytes, Hc, Wc)
     # the bytes: + the streams drawn, known on the device
     _call('istvt_png_decode_%s_u8' % name, 2 * out.shape[0] * bank.raw_stride + out.numel(), ctypes.byref(args), *head, bank.band_max,
@@ -698,7 +709,8 @@ def png_decode_bank_u8(bank, index, canvas=None, out: Optional[Tensor] = None, b
     host tensor or list, which is uploaded.  int64 is clamped to [-1, n] and narrowed on the device.  The bank is uploaded at
     the first call (bank.on); it may hold more than 2^31 bytes.  canvas = (Hc, Wc) defaults to the bank's largest H and W,
     whatever is drawn.  buffers = (scratch uint8 of clips.png_bank_scratch_bytes(bank, m) bytes and 16-byte aligned, sizes,
-    status).  Two launches."""
+    status).  Two launches.  A bank packed with clips.png_bank(alone=True) is decoded by istvt_png_decode_bank_alone_u8: its
+    flagged files are unfiltered one wave per band too (status 10 is clips.PNG_ALONE_STATUS's)."""
     what = 'png_decode_bank_u8'
     if not isinstance(bank, clips.PngBank):
         raise TypeError('%s expects a clips.PngBank (clips.png_bank), got %s' % (what, type(bank).__name__))
@@ -992,7 +1004,7 @@ _JPEG_ONLY = dict(quality=_NotGiven(90), subsampling=_NotGiven('420'), restart_i
 def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transforms: Optional[Tensor] = None,
                   quality=_JPEG_ONLY['quality'], subsampling=_JPEG_ONLY['subsampling'],
                   restart_interval=_JPEG_ONLY['restart_interval'], optimize=_JPEG_ONLY['optimize'], layout=_JPEG_ONLY['layout'],
-                  format: str = 'jpeg', band_rows=None, filters=None, index=None):
+                  format: str = 'jpeg', band_rows=None, filters=None, index=None, alone=None):
     """Dataset preparation, the mirror of decode_frames: whole frames uint8 [n,Hs,Ws,3] or [B,T,Hs,Ws,3] on the device are
     cut to S x S through `boxes` (crop_resize_u8) or `transforms` (warp_similarity_u8) and the crops leave as JPEG files
     (jpeg_encode_u8; optimize=True: with their own Huffman tables; layout: one of clips.JPEG_LAYOUTS in the place of
@@ -1000,11 +1012,14 @@ def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transf
     and 'grey').  format='png': the crops leave lossless, as PNG files (png_encode_u8 with band_rows and filters, 16 and
     'adaptive' where not given) -> a clips.PngFiles; the JPEG-only arguments (quality 90, subsampling '420', restart_interval
     'row' and optimize False where not given) are then refused if given, whatever their value, and so is a layout.
-    index=True (format='png' only): the files carry their band index (png_encode_u8(index=True))."""
+    index=True (format='png' only): the files carry their band index (png_encode_u8(index=True)); alone=True with it: the
+    bands stand alone (png_encode_u8(alone=True))."""
     if format not in ('jpeg', 'png'):
         raise ValueError("encode_frames: format is 'jpeg' or 'png', got %r" % (format,))
     if index is not None and format != 'png':
         raise ValueError("encode_frames: index= goes with format='png' (the band index of a PNG file); JPEG files have none")
+    if alone is not None and format != 'png':
+        raise ValueError("encode_frames: alone= goes with format='png' (bands of a PNG file that stand alone); JPEG files have none")
     if format == 'png':
         given = dict(quality=quality, subsampling=subsampling, restart_interval=restart_interval, optimize=optimize, layout=layout)
         for name, default in _JPEG_ONLY.items():
@@ -1022,8 +1037,10 @@ def encode_frames(frames: Tensor, S: int, boxes: Optional[Tensor] = None, transf
         clips.check_png_filters(filters, 'png_encode_u8')
         if index is not None and not isinstance(index, bool):
             raise ValueError('png_encode_u8: index is True or False, got %r' % (index,))
+        index, alone = False if index is None else index, False if alone is None else alone
+        clips._check_png_alone(alone, index, 'png_encode_u8')
         crops = crop_resize_u8(frames, boxes, S) if boxes is not None else warp_similarity_u8(frames, transforms, S)
-        return png_encode_u8(crops, band_rows, filters, index=False if index is None else index)
+        return png_encode_u8(crops, band_rows, filters, index=index, alone=alone)
     if not isinstance(optimize, bool):
         raise ValueError('jpeg_encode_u8: optimize is True or False, got %r' % (optimize,))
     clips._jpeg_encode_layout(subsampling, layout, 'jpeg_encode_u8')
@@ -1044,7 +1061,7 @@ def png_encode_scratch(n: int, H: int, W: int, bpp: int, band_rows: int):
 
 
 def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capacity: Optional[int] = None,
-                  buffers=None, index: bool = False) -> 'clips.PngFiles':
+                  buffers=None, index: bool = False, alone: bool = False) -> 'clips.PngFiles':
     """PNG files out (clips.py): frames uint8 [n,H,W] or [n,H,W,1] (grey), [n,H,W,3] (RGB), [n,H,W,4] (RGBA) or clips
     [B,T,H,W,C], contiguous, on the device -> a clips.PngFiles on the device: the files of clips.png_encode_files_host end to
     end in `data`, byte for byte, with `offsets` and a `status` per file.  Lossless, for frame sets whose compression traces a
@@ -1057,10 +1074,14 @@ def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capac
     allocation; data may not overlap the frames.  Four launches, nothing synchronises.
     index=True: every file carries its bands' offsets in a baND chunk between IHDR and IDAT, the bytes of
     clips.png_encode_files_host(index=True), which ops.png_decode_u8(files, bands='index') decodes one wave per band; the
-    default capacity grows by the chunks (clips.png_encoded_bound(index=True))."""
+    default capacity grows by the chunks (clips.png_encoded_bound(index=True)).
+    alone=True (needs index=True): every band's first row is filtered without the row above and the index says so, the bytes
+    of clips.png_encode_files_host(index=True, alone=True) (istvt_png_encode_alone_u8); a batch or bank packed with alone=True
+    then unfilters such files one wave per band."""
     what = 'png_encode_u8'
     if not isinstance(index, bool):
         raise ValueError('%s: index is True or False, got %r' % (what, index))
+    clips._check_png_alone(alone, index, what)
     if torch.is_tensor(frames) and frames.dim() == 3:
         frames = frames.unsqueeze(-1)
     n, T, H, W = _rgb_source(what, frames, contiguous=True, on_device=False, channels=(1, 3, 4))
@@ -1097,11 +1118,11 @@ def png_encode_u8(frames: Tensor, band_rows: int = 16, filters='adaptive', capac
     args = _lib.JpegEncodeArgs(
         frames=frames.data_ptr(), total=nbytes, scratch=scratch.data_ptr(), scratch_bytes=scratch.numel(), data=data.data_ptr(),
         capacity=data.numel(), offsets=offsets.data_ptr(), status=status.data_ptr(), stream=_stream(), n=n, H=H, W=W)
-    name = 'png_encode_indexed_u8' if index else what
+    name = 'png_encode_alone_u8' if alone else 'png_encode_indexed_u8' if index else what
     with prof(name, nbytes + 3 * n * H * (1 + W * bpp)):          # the pixels; the filtered rows written once and read twice
         _lib.check(getattr(_lib.lib(), 'istvt_' + name)(ctypes.byref(args), bpp, R, mode, raw_stride), 'istvt_' + name)
     files = clips.PngFiles(data, offsets, status)
-    files.geometry = SimpleNamespace(H=H, W=W, bpp=bpp, band_rows=R, filters=filters, index=index)
+    files.geometry = SimpleNamespace(H=H, W=W, bpp=bpp, band_rows=R, filters=filters, index=index, alone=alone)
     return files
 
 

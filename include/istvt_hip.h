@@ -567,7 +567,7 @@ int istvt_png_decode_bands_u8(const istvt_jpeg_decode_args* a, int raw_stride);
  *   bytes, nbytes  uint8 [nbytes], 16-byte aligned: the bank's DEFLATE streams, each starting at a multiple of 16 bytes; nbytes
  *                  is a long and may exceed 2^31.  No byte outside a drawn file's [base, base + stream bytes) is read
  *   images, n      int32 [n][ISTVT_PNG_BANK_IMAGE_INTS]: H, W, colour type, bytes per pixel, base low word, base high word,
- *                  stream bytes, first band row, band count, 0
+ *                  stream bytes, first band row, band count, flags (not read by this entry)
  *   segments, nseg int32 [nseg][ISTVT_PNG_BAND_INTS] as above, with the first byte and the end byte counted from the file's base
  *   images_host    NOT a host pointer here: the index, int32 [m] on the device.  segments_host is not read.
  *   scratch        16-byte aligned; m * raw_stride bytes of filtered rows, place j's at scratch + j * raw_stride, then int32
@@ -583,6 +583,29 @@ int istvt_png_decode_bank_u8(const istvt_jpeg_decode_args* a, int m, int band_ma
  * draw block as istvt_batch_draw reads it; every other field, and band_max and raw_stride, are the bank decode's.  A refused
  * block leaves its index as it was, which the bank's kernels check like any other (status 8 outside the bank). */
 int istvt_png_decode_bank_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max, int raw_stride);
+/* PNG bands that stand alone.  A file whose `baND` chunk carries ISTVT_PNG_BAND_ALONE in its R word says that no band's first
+ * row is filtered against the row above (types 2, 3, 4 on a row k R, k >= 1), so a band is decoded to pixels with no other
+ * band.  istvt_png_decode_alone_u8 takes the block of istvt_png_decode_bands_u8 (clips.png_batch(bands='index', alone=True))
+ * with its checks and its inflate launch, and
+ *   qtabs, htabs, nq, nh   int32 [n] on the device and its host copy: file i's flag, 1 where its bands stand alone, else 0;
+ *                  nq == nh == n
+ * The unfilter launch has nseg workgroups of one wave, one per band row.  The waves of a flagged file each settle the file's
+ * status for themselves -- the first failing band status in band order, then 6 for a filter byte above 4, then 10: the file
+ * lies, a band's first row reads the row above -- and then reconstruct, or zero, rows [k R, min(H, (k + 1) R)) of the canvas
+ * with the margin right of them; the wave of band 0 writes status and sizes and zeroes the margin below.  A file without the
+ * flag is unfiltered whole by one wave as istvt_png_decode_bands_u8 does it: wave f of the launch for file f, so that the
+ * long serial jobs start first; its own waves leave.  The bytes and statuses of clips.png_decode_alone_host.  -3 before any launch as there, and on a null qtabs or htabs, another nq or nh,
+ * a flag word with bits other than bit 0, or a flagged file whose band rows are not the R-row bands of an index, R = the
+ * output bytes of its band row 0 / (1 + W bpp): count == ceil(H / R), row k writes k R (1 + W bpp) and on for rows_k (1 + W
+ * bpp) bytes (csrc/png_alone.h) -- so no canvas row is written twice or left unwritten.
+ * istvt_png_decode_bank_alone_u8 is istvt_png_decode_bank_u8 in every argument, check and its inflate launch, for a bank
+ * packed with clips.png_bank(alone=True): bit 0 of images[i][9] is file i's flag.  Its unfilter launch has m * band_max
+ * workgroups, mapped as the inflate's; a flagged file whose band rows fail the check above has status 9.  The bytes of
+ * clips.png_bank_decode_host.  istvt_png_decode_bank_alone_drawn_u8 is the draw in front of it, as above. */
+#define ISTVT_PNG_BAND_ALONE 0x80000000u   /* bit 31 of the R word of a baND chunk: the bands stand alone */
+int istvt_png_decode_alone_u8(const istvt_jpeg_decode_args* a, int raw_stride);
+int istvt_png_decode_bank_alone_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride);
+int istvt_png_decode_bank_alone_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max, int raw_stride);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with
@@ -685,6 +708,11 @@ int istvt_png_encode_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows,
  * length to every file; the container kernel writes it from the bands' offsets in the scratch rows and folds its CRC-32 as it
  * folds the IDAT's.  Status 1 and offsets as above. */
 int istvt_png_encode_indexed_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride);
+/* ... with bands that stand alone: istvt_png_encode_indexed_u8 in checks, scratch and its four launches.  The filter kernel
+ * restricts every band's first row to the types that do not read the row above -- 'adaptive' takes the cheaper of 0 and 1, of
+ * equal sums 0; a fixed 2 becomes 0, a fixed 3 or 4 becomes 1 -- and the container kernel writes R | ISTVT_PNG_BAND_ALONE as
+ * the chunk's first word.  The bytes of clips.png_encode_banded_host(index=True, alone=True). */
+int istvt_png_encode_alone_u8(const istvt_jpeg_encode_args* a, int bpp, int band_rows, int filter, int raw_stride);
 /* Perturbations: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3; nothing outside is read, no
  * alignment needed), table int32 [n][4] = (kind, param, frame_id, stream) per frame on the device -- or, with per_clip_T = T >
  * 0, [n / T][4] per clip: frame f reads row f / T and adds f % T to its frame_id -> out uint8 [n][H][W][3] (no overlap with

@@ -39,6 +39,20 @@ c        ops.png_decode_bank_u8 on the bank with the device index; b and c in al
          share of both from a torch.profiler trace of ten more calls
 a        ops.png_decode_u8 from the drawn files' bytes, clips.png_batch and the upload in every call: 3 repeats
 d        ops.draw_clips from the PNG bank beside ops.draw_clips from a JPEG bank of the same frames at quality 90
+
+--alone --against PARENT.so [--bench-py K [--parent-tree DIR]]  instead of the above (DESIGN.md "PNG bands that stand alone"): 256
+frames of 224 x 224 and 8 of 1080 x 1920 at band_rows 8 and 16, written by ops.png_encode_u8 with their index (indexed) and
+with bands that stand alone (alone).  After the frames of every route are compared with the source pixels, in alternation, each
+leg first in turn:
+
+b        the parent commit's istvt_png_decode_bands_u8 (the library given with --against) on the indexed files
+c        this tree's ops.png_decode_u8 on the alone files packed with alone=True: one wave per band in the unfilter too
+n        this tree's ops.png_decode_u8 on the indexed files packed with alone=True, on the same buffers: no file has the flag
+         and every one takes the serial unfilter, which must cost what (b) costs
+each kernel's share of b and c from a torch.profiler trace of ten more calls; the files' bytes either way, and how many
+band-first rows changed their type (clips.png_filter_rows_host on the distinct frames).  Then the 224 x 224 frames as a bank
+of --bank-files places, 256 drawn per call: ops.png_decode_bank_u8 and ops.draw_clips from the indexed bank and from the alone
+bank.
 """
 import argparse
 import io
@@ -387,6 +401,157 @@ def bank_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def alone_size(a, lines, res, key, src, n, other):
+    """--alone, one size: src uint8 [DISTINCT, H, W, 3] -> legs b, c and n in alternation for every band_rows"""
+    from istvt_amd import _lib
+    dev = torch.device('cuda', torch.cuda.current_device())
+    H, W = src.shape[1:3]
+    pick = [i % DISTINCT for i in range(n)]
+    src_dev = src.to(dev)
+    want_tail = src[torch.tensor(pick[n - DISTINCT:])]
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+    res[key] = {'frames': n, 'H': H, 'W': W}
+    say(lines, '%s: %d frames of %d x %d' % (key, n, H, W))
+    for R in a.band_rows:
+        indexed = ops.png_encode_u8(src_dev, R, index=True).files()
+        alone = ops.png_encode_u8(src_dev, R, index=True, alone=True).files()
+        changed = rows = 0
+        for f in src.numpy():                                     # on the host: the types of the band-first rows either way
+            free, kept = clips.png_filter_rows_host(f)[::R, 0], clips.png_filter_rows_host(f, alone_rows=R)[::R, 0]
+            changed, rows = changed + int((free != kept).sum()), rows + len(free)
+        bi = clips.png_batch([indexed[i] for i in pick], bands='index')
+        bc = clips.png_batch([alone[i] for i in pick], bands='index', alone=True)
+        bn = clips.png_batch([indexed[i] for i in pick], bands='index', alone=True)
+        assert sum(bc.alone.tolist()) == n and sum(bn.alone.tolist()) == 0 and bc.scratch_bytes == bi.scratch_bytes == bn.scratch_bytes
+        for b in (bi, bc, bn):
+            b.on(dev)
+        bufs = (torch.empty((bi.scratch_bytes,), dtype=torch.uint8, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev),
+                torch.empty((n,), dtype=torch.int32, device=dev))
+        d = bi.on(dev)
+        args = _lib.JpegDecodeArgs(
+            bytes=d.data.data_ptr(), nbytes=bi.nbytes, images=d.images.data_ptr(), images_host=bi.images.data_ptr(),
+            segments=d.bands.data_ptr(), segments_host=bi.bands.data_ptr(), scratch=bufs[0].data_ptr(), scratch_bytes=bufs[0].numel(),
+            out=out.data_ptr(), sizes=bufs[1].data_ptr(), status=bufs[2].data_ptr(), stream=torch.cuda.current_stream().cuda_stream, n=n,
+            nseg=int(bi.bands.shape[0]), Hc=H, Wc=W)
+        calls = {'b': lambda: (_lib.check(other.istvt_png_decode_bands_u8(ctypes.byref(args), bi.raw_stride), 'parent istvt_png_decode_bands_u8'),
+                               (out, bufs[1], bufs[2]))[1],
+                 'c': lambda: ops.png_decode_u8(bc, out=out, checked=True, buffers=bufs),
+                 'n': lambda: ops.png_decode_u8(bn, out=out, checked=True, buffers=bufs)}
+        for name, fn in calls.items():                            # the frames before anything is timed
+            out.fill_(7)
+            got, _, status = fn()
+            clips.check_png_status(status)
+            if not torch.equal(got[:DISTINCT], src_dev) or not torch.equal(got[n - DISTINCT:].cpu(), want_tail):
+                raise SystemExit('%s band_rows %d, leg %s: the decoded frames are not the source pixels' % (key, R, name))
+        ts = {k: [] for k in calls}
+        for r in range(a.warmup + a.reps):
+            order = list(calls.items())
+            for k, fn in order[r % len(order):] + order[:r % len(order)]:      # each leg first in turn
+                t = event_ms(fn)
+                if r >= a.warmup:
+                    ts[k].append(t)
+        sb = kernel_shares(calls['b'], frags=('png_inflate_bands_kernel', 'png_unfilter_bands_kernel'))
+        sc = kernel_shares(calls['c'], frags=('png_inflate_bands_kernel', 'png_unfilter_alone_kernel'))
+        st = {k: stats(v) for k, v in ts.items()}
+        spread = max(st['b']['max_ms'] - st['b']['min_ms'], 1e-9)
+        inside = st['b']['min_ms'] <= st['n']['median_ms'] <= st['b']['max_ms']
+        bytes_i, bytes_a = sum(len(f) for f in indexed), sum(len(f) for f in alone)
+        res[key]['band_rows_%d' % R] = dict(st, kernel_us_b=sb, kernel_us_c=sc, waves=int(bi.bands.shape[0]), bytes_indexed=bytes_i,
+                                            bytes_alone=bytes_a, band_first_rows=rows, band_first_rows_changed=changed, n_inside_b_range=inside)
+        say(lines, '  band_rows %d, %d waves: (b) the parent\'s banded call on the indexed files %s, its range %.3f ms (inflate %.0f us, unfilter '
+            '%.0f us per call) | (c) this tree on the alone files %s (inflate %.0f us, unfilter %.0f us per call) | b / c = %.2f x, b - c = '
+            '%.3f ms = %.1f ranges of b | (n) this tree on the indexed files packed with alone=True %s: n - b = %.3f ms, n is %s the range '
+            'of b | the %d distinct files: indexed %d bytes, alone %d bytes = %+.3f %%; %d of %d band-first rows changed their type'
+            % (R, int(bi.bands.shape[0]), fmt(st['b']), spread, sb['png_inflate_bands_kernel'], sb['png_unfilter_bands_kernel'], fmt(st['c']),
+               sc['png_inflate_bands_kernel'], sc['png_unfilter_alone_kernel'], st['b']['median_ms'] / st['c']['median_ms'],
+               st['b']['median_ms'] - st['c']['median_ms'], (st['b']['median_ms'] - st['c']['median_ms']) / spread, fmt(st['n']),
+               st['n']['median_ms'] - st['b']['median_ms'], 'inside' if inside else 'OUTSIDE', DISTINCT, bytes_i, bytes_a,
+               100.0 * (bytes_a - bytes_i) / bytes_i, changed, rows))
+
+
+def alone_bank(a, lines, res, src):
+    """--alone, the bank: ops.png_decode_bank_u8 and ops.draw_clips from the indexed bank and from the alone bank"""
+    dev = torch.device('cuda', torch.cuda.current_device())
+    S, n, N = a.size, a.frames, a.bank_files
+    src_dev = src.to(dev)
+    g = torch.Generator().manual_seed(31)
+    index = torch.randint(0, N, (n,), generator=g, dtype=torch.int32)
+    idx = index.to(dev)
+    want = src_dev[torch.tensor([i % DISTINCT for i in index.tolist()], device=dev)]
+    out = torch.empty((n, S, S, 3), dtype=torch.uint8, device=dev)
+    say(lines, 'bank: %d places of %d x %d (%d distinct files repeated), %d drawn per call by a device index' % (N, S, S, DISTINCT, n))
+    for R in a.band_rows:
+        banks = {}
+        for k, alone in (('b', False), ('c', True)):
+            hs = [clips.png_parse(f) for f in ops.png_encode_u8(src_dev, R, index=True, alone=alone).files()]
+            banks[k] = clips.png_bank([hs[i % DISTINCT] for i in range(N)], alone=alone)
+            banks[k].on(dev)
+        buf = (torch.empty((clips.png_bank_scratch_bytes(banks['b'], n),), dtype=torch.uint8, device=dev),
+               torch.empty((n, 2), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+        T = 8
+        B = n // T
+        out_d = torch.empty((B, T, S, S, 3), dtype=torch.uint8, device=dev)
+        plans = {k: clips.BatchPlan(bk, [(0, N, 0)], T=T, B=B, seed=5).on(dev) for k, bk in banks.items()}
+        calls = {k: (lambda k=k: ops.png_decode_bank_u8(banks[k], idx, out=out, buffers=buf)) for k in banks}
+        dcalls = {k: (lambda k=k: ops.draw_clips(banks[k], plans[k], S, out=out_d)) for k in banks}
+        for k, fn in calls.items():
+            got, _, status = fn()
+            clips.check_png_status(status)
+            if not torch.equal(got, want):
+                raise SystemExit('bank, band_rows %d, leg %s: the decoded frames are not the source pixels' % (R, k))
+        row = {}
+        for tag, legs in (('decode', calls), ('draw_clips', dcalls)):
+            ts = {k: [] for k in legs}
+            for r in range(a.warmup + a.reps):
+                order = list(legs.items())
+                for k, fn in order[r % 2:] + order[:r % 2]:
+                    t = event_ms(fn)
+                    if r >= a.warmup:
+                        ts[k].append(t)
+            row[tag] = {k: stats(v) for k, v in ts.items()}
+        sb = kernel_shares(calls['b'], frags=('png_bank_inflate_kernel', 'png_bank_unfilter_kernel'))
+        sc = kernel_shares(calls['c'], frags=('png_bank_inflate_kernel', 'png_bank_unfilter_alone_kernel'))
+        row.update(kernel_us_b=sb, kernel_us_c=sc)
+        res['bank_band_rows_%d' % R] = row
+        db, dc = row['decode']['b'], row['decode']['c']
+        say(lines, '  band_rows %d: png_decode_bank_u8, the indexed bank %s, its range %.3f ms (inflate %.0f us, unfilter %.0f us per call) | the '
+            'alone bank %s (inflate %.0f us, unfilter %.0f us per call) | b - c = %.3f ms = %.1f ranges of b | draw_clips, B = %d clips of T = '
+            '%d, all stages: from the indexed bank %s, from the alone bank %s'
+            % (R, fmt(db), db['max_ms'] - db['min_ms'], sb['png_bank_inflate_kernel'], sb['png_bank_unfilter_kernel'], fmt(dc),
+               sc['png_bank_inflate_kernel'], sc['png_bank_unfilter_alone_kernel'], db['median_ms'] - dc['median_ms'],
+               (db['median_ms'] - dc['median_ms']) / max(db['max_ms'] - db['min_ms'], 1e-9), B, T, fmt(row['draw_clips']['b']),
+               fmt(row['draw_clips']['c'])))
+        for bk in banks.values():
+            bk._on.clear()
+
+
+def alone_main(a):
+    if not torch.cuda.is_available():
+        raise SystemExit('png_decode_bench.py measures on a GPU; none is visible')
+    from istvt_amd import _lib
+    torch.zeros(1, device='cuda')
+    lines, res = [], {}
+    if not a.only_bench_py:
+        if not a.against:
+            raise SystemExit('--alone measures against the parent commit\'s library: --against PARENT.so')
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        other.istvt_png_decode_bands_u8.argtypes, other.istvt_png_decode_bands_u8.restype = _lib.SIGNATURES['istvt_png_decode_bands_u8'], ctypes.c_int
+        src = torch.stack([torch.from_numpy(smooth_image(a.size, a.size, 1000 + i)) for i in range(DISTINCT)])
+        alone_size(a, lines, res, 'step', src, a.frames, other)
+        if not a.no_large:
+            big = torch.stack([torch.from_numpy(smooth_image(1080, 1920, 2000 + i)) for i in range(DISTINCT)])
+            alone_size(a, lines, res, 'large', big, DISTINCT, other)
+        alone_bank(a, lines, res, src)
+    if a.bench_py:
+        bench_py(a, lines, res)
+    line = json.dumps({'png_alone_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--frames', type=int, default=256)
@@ -404,7 +569,11 @@ def main():
     p.add_argument('--only-bench-py', action='store_true', help='with --bands --bench-py: skip the decode legs')
     p.add_argument('--bank', action='store_true')
     p.add_argument('--bank-files', type=int, default=4096)
+    p.add_argument('--alone', action='store_true')
     a = p.parse_args()
+    if a.alone:
+        a.band_rows = [8, 16] if a.band_rows == [8, 16, 32] else a.band_rows
+        return alone_main(a)
     if a.bank:
         a.band_rows = [16, 8] if a.band_rows == [8, 16, 32] else a.band_rows
         return bank_main(a)
