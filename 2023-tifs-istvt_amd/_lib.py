@@ -97,6 +97,9 @@ SIGNATURES = {
     'istvt_png_decode_alone_u8': [ctypes.POINTER(JpegDecodeArgs), I],
     'istvt_png_decode_bank_alone_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I],
     'istvt_png_decode_bank_alone_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I],
+    'istvt_png_decode_window_u8': [ctypes.POINTER(JpegDecodeArgs), I, I],
+    'istvt_png_decode_bank_window_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I],
+    'istvt_png_decode_bank_window_drawn_u8': [ctypes.POINTER(JpegDecodeArgs), I, I, I, I, I, I, I],
     'istvt_png_encode_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_png_encode_indexed_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],
     'istvt_png_encode_alone_u8': [ctypes.POINTER(JpegEncodeArgs), I, I, I, I],

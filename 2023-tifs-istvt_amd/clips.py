@@ -63,7 +63,9 @@ refusal), ``png_decode_host`` (the definition of ops.png_decode_u8: zlib's infla
 kept lossless on purpose run ``model(ops.decode_frames(clips.png_batch(files), S, boxes).view(B, T, S, S, 3), view=flips)``.
 A whole set of them stays on the device as a ``PngBank`` (DESIGN.md "PNG bank"; ``png_bank``, ``png_bank_scratch_bytes``,
 ``png_bank_decode_host``, the definition of ops.png_decode_bank_u8), and ``ops.draw_clips(bank, plan, S)`` takes it as it takes
-a JpegBank.
+a JpegBank.  Whole video frames whose bands stand alone are decoded through their face boxes (DESIGN.md "PNG windows";
+``png_window_plan``, ``png_window_rows``, ``png_bank_window_host``, the definition of ops.png_decode_window_u8): only the bands a
+box touches, ``ops.decode_frames(..., window=True)`` and ``ops.draw_clips(bank, plan, S, window=True)``.
 """
 import math
 from fractions import Fraction
@@ -3025,6 +3027,9 @@ PNG_BAND_ALONE = 0x80000000                 # bit 31 of the R word of a baND chu
 # the status only a decode of bands that stand alone gives (png_decode_alone_host, ops.png_decode_u8 on a batch packed with
 # alone=True, the bank's decode of an alone bank); check_png_status words it too
 PNG_ALONE_STATUS = {10: "the index says its bands stand alone, and a band's first row is filtered against the row above"}
+# the statuses only a windowed decode gives (png_bank_window_host, ops.png_decode_window_u8); check_png_status words them too
+PNG_WINDOW_STATUS = {11: "the file's index does not say its bands stand alone: it is decoded whole, not by a box",
+                     12: 'the box does not lie in the image, or its bands do not fit the window'}
 _PNG_LBASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 _PNG_LEXT = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
 _PNG_DBASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
@@ -3641,7 +3646,7 @@ def check_png_status(status) -> None:
         if s != 0:
             raise ValueError('png_decode: file %d is damaged (status %d: %s)'
                              % (i, s, PNG_STATUS.get(s) or PNG_BAND_STATUS.get(s) or PNG_BANK_STATUS.get(s)
-                                or PNG_ALONE_STATUS.get(s, 'unknown')))
+                                or PNG_ALONE_STATUS.get(s) or PNG_WINDOW_STATUS.get(s, 'unknown')))
 
 
 # ---- PNG bank (DESIGN.md "PNG bank") --------------------------------------------------------------------------------------------
@@ -3836,6 +3841,281 @@ def png_bank_decode_host(bank_or_files, index, canvas=None):
             frames[j, :H, :W] = f
             sizes[j, 0], sizes[j, 1] = H, W
     return frames, sizes, status
+
+
+# ---- PNG windows (DESIGN.md "PNG windows") ------------------------------------------------------------------------------------
+# A face box needs a fraction of a whole frame's rows.  Of a file whose bands stand alone, ops.png_decode_window_u8 inflates and
+# unfilters only the bands the box touches, into a canvas that is a window of `rows` rows, and hands the crop the box moved into
+# that window.  png_window_plan is the window, png_bank_window_host the definition; csrc/png_window.h is the same arithmetic in
+# C++ for the device and for tools/png_window_check.cpp.
+def png_window_plan(H: int, R: int, count: int, box, rows: int, win_bands: int, W: Optional[int] = None):
+    """The window of box (y0, x0, h, w) in a file of H rows in `count` bands of R rows that stand alone -> (kfirst, klast, w0,
+    w1), or status 12 (PNG_WINDOW_STATUS).  kfirst = y0 // R and klast = (y0 + h - 1) // R are the bands the box touches; w0 =
+    kfirst R and w1 = min(H, (klast + 1) R) the rows they hold.  12: h < 1, w < 1, y0 < 0, x0 < 0, y0 + h > H, x0 + w > W
+    (looked at where W is given), w1 - w0 > rows, or more than win_bands bands.  The one place these steps are written in
+    Python; pw_window of csrc/png_window.h is the same in C++."""
+    y0, x0, h, w = (int(v) for v in box)
+    if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or (W is not None and x0 + w > W):
+        return 12
+    kfirst, klast = y0 // R, (y0 + h - 1) // R
+    w0, w1 = kfirst * R, min(H, (klast + 1) * R)
+    if klast >= count or w1 - w0 > rows or klast - kfirst + 1 > win_bands:
+        return 12
+    return kfirst, klast, w0, w1
+
+
+def _png_window_files(src) -> list:
+    """[(H, W, bpp, R, count, flagged)] of a PngBank's or a PngBatch's files from its own tables; R is 0 for a file without the
+    flag.  Kept with the tensors it was read from, so that a decode step after step does not read the tables again and an
+    object given other tables is read anew."""
+    if not isinstance(src, (PngBank, PngBatch)):
+        raise TypeError('a clips.PngBank or a clips.PngBatch is expected, got %s' % type(src).__name__)
+    kept = src.__dict__.get('_window_files')
+    if kept is None or kept[0] is not src.images or kept[1] is not src.bands or kept[2] is not src.alone:
+        src._window_files = kept = (src.images, src.bands, src.alone, _png_window_files_read(src))
+    return kept[3]
+
+
+def _png_window_files_read(src) -> list:
+    if src.bands is None:
+        return [(r[0], r[1], r[3], 0, 1, False) for r in src.images.tolist()]
+    bands, out = src.bands.tolist(), []
+    bank = isinstance(src, PngBank)
+    flags = src.images[:, 9].tolist() if bank else [0] * src.n if src.alone is None else src.alone.tolist()
+    for r, flag in zip(src.images.tolist(), flags):
+        first, count = (r[7], r[8]) if bank else (r[6], r[7])
+        flagged = bool(flag & 1) and (not bank or bool(src.alone))
+        out.append((r[0], r[1], r[3], bands[first][4] // (1 + r[1] * r[3]) if flagged else 0, count, flagged))
+    return out
+
+
+def png_window_rows(bank_or_batch, h_max: int) -> int:
+    """The window height `rows` that fits any box of height at most h_max in any flagged file of a PngBank or a PngBatch: the
+    largest of min(H_i, R_i (1 + (h_max + R_i - 2) // R_i)).  A box of height h at y0 = k R + a, 0 <= a < R, touches bands k to
+    (k R + a + h - 1) // R = k + (a + h - 1) // R, so 1 + (a + h - 1) // R bands: most for a = R - 1, the box that starts in a
+    band's last row, which touches 1 + (h + R - 2) // R bands, and for h = h_max.  Their rows are R each, and never more than
+    the image has.  1 where no file is flagged."""
+    h_max = int(h_max)
+    if h_max < 1:
+        raise ValueError('png_window_rows: h_max is at least 1, got %d' % h_max)
+    return max([min(H, R * (1 + (h_max + R - 2) // R)) for H, _, _, R, _, flagged in _png_window_files(bank_or_batch) if flagged] or [1])
+
+
+def png_window_bands(bank_or_batch, rows: int) -> int:
+    """win_bands for a window of `rows` rows, the slots a place gets: the largest min(count_i, ceil(rows / R_i)) over the flagged
+    files; 1 where none is"""
+    rows = int(rows)
+    return max([min(count, -(-rows // R)) for _, _, _, R, count, flagged in _png_window_files(bank_or_batch) if flagged] or [1])
+
+
+def png_window_stride(bank_or_batch, rows: int) -> int:
+    """win_stride, the bytes of a place's filtered rows in the scratch: rows * the largest 1 + W_i bpp_i, rounded up to 16"""
+    return -(-int(rows) * max(1 + W * bpp for _, W, bpp, _, _, _ in _png_window_files(bank_or_batch)) // 16) * 16
+
+
+def png_window_scratch_bytes(bank_or_batch, m: int, rows: int) -> int:
+    """The scratch of ops.png_decode_window_u8 for m places: m * win_stride bytes of filtered rows, an int32 status per slot
+    (m * win_bands), then from the next multiple of 16 the moved boxes int32 (m, 4) and the origins int32 (m,)"""
+    return png_window_boxes_at(bank_or_batch, m, rows) + 4 * int(m) * 5
+
+
+def png_window_boxes_at(bank_or_batch, m: int, rows: int) -> int:
+    """Where the moved boxes stand in that scratch, in bytes (pw_boxes_at of csrc/png_window.h): behind the filtered rows and
+    the status words, at the next multiple of 16; the m origins follow the 4 m words of the boxes"""
+    m = int(m)
+    at = m * png_window_stride(bank_or_batch, rows) + 4 * m * png_window_bands(bank_or_batch, rows)
+    return -(-at // 16) * 16
+
+
+def _png_window_place(bank: PngBank, i: int, box, rows: int, Wc: int, win_bands: int, win_stride: int, inflated: dict):
+    """Place i of the bank through `box`, from the bank's own rows and bytes as csrc/png_window.h reads them -> (window uint8
+    (w1 - w0, W, 3) or None, H, W, status, origin, moved box).  inflated: {(i, k): (bytes, status)}, the bands inflated so far."""
+    import numpy as np
+    none = lambda H, W, status: (None, H, W, status, 0, (0, 0, 1, 1))
+    im = bank.images[i].tolist()
+    H, W, ct, bpp, lo, hi, nstream, first, count = im[:9]
+    base = ((hi & 0xffffffff) << 32) | (lo & 0xffffffff)
+    if base >= 2 ** 63:
+        base -= 2 ** 64
+    total = bank.first_byte + bank.nbytes
+    if not (1 <= H <= PNG_MAX_SIDE and 1 <= W <= PNG_MAX_SIDE and W <= Wc) or PNG_BPP.get(ct) != bpp \
+            or H * (1 + W * bpp) > bank.raw_stride or not (1 <= count <= bank.band_max) or base < 0 or base % 16 or nstream < 0 \
+            or base > total or nstream > total - base or base < bank.first_byte:
+        return none(0, 0, 9)
+    stride = 1 + W * bpp
+    if min(H, rows) * stride > win_stride:
+        return none(0, 0, 9)
+    if not (bank.alone and im[9] & 1):
+        return none(H, W, 11)
+    if first < 0 or first + count > bank.nband:
+        return none(0, 0, 9)
+    table = [bank.bands[first + k].tolist() for k in range(count)]
+    R = _png_alone_band_rows(H, stride, table)
+    if R == 0:
+        return none(0, 0, 9)
+    plan = png_window_plan(H, R, count, box, rows, win_bands, W)
+    if plan == 12:
+        return none(H, W, 12)
+    kfirst, klast, w0, w1 = plan
+    raw, statuses = bytearray((w1 - w0) * stride), []
+    for k in range(kfirst, klast + 1):
+        f, begin, end, at, nout = table[k]
+        if f != i or not (0 <= begin <= end <= nstream):
+            statuses.append(9)
+            continue
+        if (i, k) not in inflated:
+            stream = bytes(bank.data[base - bank.first_byte + begin:base - bank.first_byte + end].numpy())
+            inflated[(i, k)] = _png_inflate(stream, nout, middle=k < count - 1)
+        out, status = inflated[(i, k)]
+        raw[at - w0 * stride:at - w0 * stride + len(out)] = out
+        statuses.append(status)
+    status = next((s for s in statuses if s), 0)
+    if status == 9:
+        return none(0, 0, 9)
+    filt = np.frombuffer(bytes(raw), dtype=np.uint8).reshape(w1 - w0, stride)
+    if status == 0 and int(filt[:, 0].max()) > 4:
+        status = 6
+    if status == 0 and any(int(filt[r - w0, 0]) >= 2 for r in range(w0, w1) if r > 0 and r % R == 0):
+        status = 10
+    if status:
+        return none(H, W, status)
+    px = np.concatenate([_png_unfilter(filt[r0 - w0:min(r0 + R, w1) - w0], bpp) for r0 in range(w0, w1, R)], axis=0)
+    px = torch.from_numpy(px).reshape(w1 - w0, W, bpp)
+    y0, x0, h, w = (int(v) for v in box)
+    return (px.expand(w1 - w0, W, 3).contiguous() if bpp == 1 else px[:, :, :3].contiguous()), H, W, 0, w0, (y0 - w0, x0, h, w)
+
+
+def png_bank_window_host(bank_or_files, index, boxes, rows: int, Wc: Optional[int] = None):
+    """The definition of ops.png_decode_window_u8, integers only: place j is files[index[j]] through boxes[j] = (y0, x0, h, w)
+    -> (windows uint8 (m, rows, Wc, 3), sizes int32 (m, 2), status int32 (m,), origin int32 (m,), moved_boxes int32 (m, 4)).
+    bank_or_files: a PngBank packed with alone=True, or a sequence of files, which png_bank(files, alone=True) packs.  Wc
+    defaults to the bank's Wmax.  Of a file of H rows whose index says its count bands of R rows stand alone only the bands
+    the box touches are inflated and unfiltered (png_window_plan): rows [w0, w1) of the image stand in rows [0, w1 - w0) and
+    columns [0, W) of the place's window and everything else of it is zero; origin is w0 and the moved box (y0 - w0, x0, h, w).
+    The status of a place, by precedence:
+      8   index[j] is outside the bank;
+      9   the bank's row does not fit the call (as png_bank_decode_host decides it, but that the file's H is not compared with
+          `rows`: its W is compared with Wc, and min(H, rows) of its filtered rows with the bytes a place has in the scratch);
+      11  the file's index does not say its bands stand alone (PNG_WINDOW_STATUS): such a file is decoded whole, not by a box;
+      9   the band rows of a flagged file are not the R-row bands of an index (_png_alone_band_rows);
+      12  the box does not lie in the image, or its bands do not fit the window (png_window_plan, with win_bands =
+          png_window_bands(bank, rows));
+      then the status of the first failing TOUCHED band in band order: its inflate's, or 9 for a band row that does not name the
+          file or lies outside its stream;
+      6   a filter byte above 4 in a touched row;
+      10  a touched row k R, k >= 1, of type 2, 3 or 4 -- the first row of the window's own first band where kfirst >= 1.
+    Any status but 0 leaves a window of zeros, origin 0 and the moved box (0, 0, 1, 1), so that the crop behind it is black;
+    sizes are (H, W), or (0, 0) with 8 and 9.
+    A deliberate difference from png_decode_alone_host: damage in a band the box does not touch is not seen.  A flipped bit, a
+    filter byte 5 or a lying first row in a band outside [kfirst, klast] leaves status 0 and the right pixels here, where the
+    whole decode gives the file's status and zeros.
+    Why status 0 gives the crop of the whole frame.  The touched bands inflated to the filtered rows the sequential inflate has
+    (png_decode_bands_host's induction, band by band).  No touched row k R, k >= 1, has type 2, 3 or 4 (status 10 is absent), and
+    row 0 is defined with a zero row above: so no touched band's first row reads the row above it, and unfiltering each touched
+    band from a zero row gives rows [w0, w1) of png_decode_host (png_decode_alone_host's induction, started at kfirst in place
+    of 0).  The box lies inside rows [w0, w1) and columns [0, W), and crop_resize_host reads src[y0:y0 + h, x0:x0 + w] and
+    nothing else: crop_resize_host(window, moved_box) is crop_resize_host(whole frame, box), byte for byte."""
+    bank = bank_or_files if isinstance(bank_or_files, PngBank) else png_bank(bank_or_files, alone=True)
+    index = check_bank_index(index, 'png_bank_window_host').tolist()
+    boxes = [[int(v) for v in b] for b in (boxes.tolist() if torch.is_tensor(boxes) else boxes)]
+    rows = int(rows)
+    Wc = bank.Wmax if Wc is None else int(Wc)
+    if len(boxes) != len(index) or any(len(b) != 4 for b in boxes):
+        raise ValueError('png_bank_window_host: one box (y0, x0, h, w) per place, %d of them' % len(index))
+    if not (1 <= rows <= PNG_MAX_SIDE and 1 <= Wc <= PNG_MAX_SIDE):
+        raise ValueError('png_bank_window_host: rows and Wc lie in 1..%d, got %d and %d' % (PNG_MAX_SIDE, rows, Wc))
+    win_bands, win_stride = png_window_bands(bank, rows), png_window_stride(bank, rows)
+    m, inflated = len(index), {}
+    windows = torch.zeros((m, rows, Wc, 3), dtype=torch.uint8)
+    sizes, status = torch.zeros((m, 2), dtype=torch.int32), torch.zeros((m,), dtype=torch.int32)
+    origin, moved = torch.zeros((m,), dtype=torch.int32), torch.tensor([[0, 0, 1, 1]] * m, dtype=torch.int32)
+    for j, i in enumerate(index):
+        if not 0 <= i < bank.n:
+            status[j] = 8
+            continue
+        win, H, W, s, w0, box = _png_window_place(bank, i, boxes[j], rows, Wc, win_bands, win_stride, inflated)
+        status[j], origin[j] = s, w0
+        sizes[j, 0], sizes[j, 1] = H, W
+        moved[j] = torch.tensor(box, dtype=torch.int32)
+        if win is not None:
+            windows[j, :win.shape[0], :W] = win
+    return windows, sizes, status, origin, moved
+
+
+def png_decode_window_host(data, box, rows: Optional[int] = None, Wc: Optional[int] = None, return_status: bool = False):
+    """One file (bytes, or a PngHeader) through one box (y0, x0, h, w) -> (window uint8 (rows, Wc, 3), origin, moved_box), with
+    return_status=True (window, origin, moved_box, status): png_bank_window_host of the file alone, which has the statuses,
+    their precedence and the argument.  rows defaults to the window the box needs, w1 - w0 of png_window_plan (1 where the box
+    has none), Wc to the file's W."""
+    hd = data if isinstance(data, PngHeader) else png_parse(data)
+    bank = png_bank([hd], alone=True)
+    if rows is None:
+        plan = png_window_plan(hd.H, hd.bands[0], len(hd.bands[1]) - 1, box, hd.H, PNG_MAX_SIDE, hd.W) if hd.alone else 12
+        rows = 1 if plan == 12 else plan[3] - plan[2]
+    windows, _, status, origin, moved = png_bank_window_host(bank, [0], [box], rows, Wc)
+    out = (windows[0], int(origin[0]), tuple(moved[0].tolist()))
+    return out + (int(status[0]),) if return_status else out
+
+
+def check_png_window(src, boxes, index=None, rows: Optional[int] = None, canvas_w: Optional[int] = None,
+                     who: str = 'png_decode_window_u8'):
+    """What ops.png_decode_window_u8 refuses by name before a device is asked for -> (boxes, rows, Wc).  src: a PngBatch packed
+    with png_batch(bands='index', alone=True) whose files all carry the flag, or a PngBank packed with png_bank(alone=True).
+    boxes: int32 (m, 4) = (y0, x0, h, w), one per place (a list is made one).  Where the boxes and, for a bank, the index are
+    on the host, every box of a flagged file is looked at: it lies in its image, and its window (png_window_plan) has at most
+    `rows` rows, or with rows=None `rows` becomes the smallest that fits them all.  Boxes or an index on the device are not
+    read: a bank then needs `rows`, and a batch takes its tallest image.  rows and canvas_w (default: the widest image) lie
+    in 1..16384."""
+    if isinstance(src, PngBatch):
+        if src.alone is None:
+            raise ValueError("%s: the batch was not packed with alone=True (clips.png_batch(files, bands='index', alone=True)): only "
+                             'bands that stand alone are decoded by a box' % who)
+        flags = src.alone.tolist()
+        if 0 in flags:
+            raise ValueError("%s: file %d of the batch does not say its bands stand alone (ops.png_encode_u8(alone=True) and "
+                             'clips.png_encode_banded_host(index=True, alone=True) write files that do)' % (who, flags.index(0)))
+        if index is not None:
+            raise ValueError('%s: index= goes with a clips.PngBank' % who)
+        which, Wmax = list(range(src.n)), max(w for _, w in src.sizes)
+    elif isinstance(src, PngBank):
+        if not src.alone:
+            raise ValueError('%s: the bank was not packed with alone=True (clips.png_bank(files, alone=True)): only bands that '
+                             'stand alone are decoded by a box' % who)
+        if index is None:
+            raise ValueError('%s: a clips.PngBank is decoded through index=' % who)
+        index = check_bank_index(index, who)
+        which, Wmax = None if index.is_cuda else index.tolist(), src.Wmax
+    else:
+        raise TypeError('%s expects a clips.PngBatch or a clips.PngBank packed with alone=True, got %s' % (who, type(src).__name__))
+    m = src.n if index is None else int(index.numel())
+    if not torch.is_tensor(boxes):
+        boxes = torch.tensor(boxes, dtype=torch.int32).reshape(-1, 4)
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (m, 4):
+        raise ValueError('%s: boxes are int32 (%d, 4) = (y0, x0, h, w), one per place, got %s %s' % (who, m, boxes.dtype, tuple(boxes.shape)))
+    for name, v in (('rows', rows), ('canvas_w', canvas_w)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= PNG_MAX_SIDE):
+            raise ValueError('%s: %s lies in 1..%d, got %r' % (who, name, PNG_MAX_SIDE, v))
+    Wc = Wmax if canvas_w is None else canvas_w
+    if Wc < Wmax:
+        raise ValueError('%s: canvas_w holds the widest image (%d), got %d' % (who, Wmax, Wc))
+    if boxes.is_cuda or which is None:
+        if rows is None and isinstance(src, PngBank):
+            raise ValueError('%s: boxes or an index on the device are not read here: say rows= (clips.png_window_rows(bank, h_max) '
+                             'fits any box of height at most h_max)' % who)
+        return boxes, (max(h for h, _ in src.sizes) if rows is None else rows), Wc
+    files, need = _png_window_files(src), 1
+    for j, (i, box) in enumerate(zip(which, boxes.tolist())):
+        if not 0 <= i < src.n or not files[i][5]:
+            continue
+        H, W, _, R, count, _ = files[i]
+        plan = png_window_plan(H, R, count, box, H, count, W)
+        if plan == 12:
+            raise IndexError('%s: box %d, (y0, x0, h, w) = %s, does not lie in its image of %d x %d' % (who, j, tuple(box), H, W))
+        if rows is not None and plan[3] - plan[2] > rows:
+            raise ValueError('%s: box %d, (y0, x0, h, w) = %s, needs a window of %d rows (its bands of %d rows), rows is %d'
+                             % (who, j, tuple(box), plan[3] - plan[2], R, rows))
+        need = max(need, plan[3] - plan[2])
+    return boxes, (need if rows is None else rows), Wc
 
 
 # ---- PNG files out (DESIGN.md "PNG files out") ---------------------------------------------------------------------------------

@@ -104,3 +104,12 @@ extern "C" int istvt_png_decode_bank_alone_drawn_u8(const istvt_jpeg_decode_args
     const int rc = bd_draw_then(a, B, T, block_ints, indexed);
     return rc != ISTVT_OK ? rc : istvt_png_decode_bank_alone_u8(&indexed, B * T, band_max, raw_stride);
 }
+
+// The same in front of istvt_png_decode_bank_window_u8 (csrc/png_window.hip): the caller's qtabs points at the boxes of the
+// block, which the draw has written when the decode's kernels read them
+extern "C" int istvt_png_decode_bank_window_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max,
+                                                     int raw_stride, int win_bands, int win_stride) {
+    istvt_jpeg_decode_args indexed;
+    const int rc = bd_draw_then(a, B, T, block_ints, indexed);
+    return rc != ISTVT_OK ? rc : istvt_png_decode_bank_window_u8(&indexed, B * T, band_max, raw_stride, win_bands, win_stride);
+}

@@ -72,6 +72,9 @@ bool png_bands_args_ok(const istvt_jpeg_decode_args* a, int raw_stride) {
     return a->scratch_bytes >= (long)a->n * raw_stride + (long)a->nseg * (long)sizeof(int);
 }
 
+// ... and the part of it that knows no canvas and no scratch row: the block and the host tables alone, for csrc/png_window.hip
+bool png_bands_tables_ok(const istvt_jpeg_decode_args* a) { return png_decode_block_ok(a) && png_bands_check(a); }
+
 int png_bands_inflate_launch(const istvt_jpeg_decode_args* a, int raw_stride) {
     uint8_t* scratch = (uint8_t*)a->scratch;
     int* band_status = reinterpret_cast<int*>(scratch + (long)a->n * raw_stride);    // a multiple of 16: the status words start there

@@ -7,6 +7,9 @@
 
 // istvt_png_decode_bands_u8: every check of the block and of its host tables, the scratch included
 bool png_bands_args_ok(const istvt_jpeg_decode_args* a, int raw_stride);
+// ... and of them those that ask nothing of the canvas or the scratch: the pointers, counts and alignment of the block, every
+// image row against the bytes, the band rows against the image rows (csrc/png_window.hip decodes into a canvas of its own)
+bool png_bands_tables_ok(const istvt_jpeg_decode_args* a);
 // ... and png_inflate_bands_kernel, one wave per band row; the band statuses are nseg ints behind n * raw_stride bytes of scratch
 int png_bands_inflate_launch(const istvt_jpeg_decode_args* a, int raw_stride);
 

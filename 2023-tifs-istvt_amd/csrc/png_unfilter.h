@@ -131,26 +131,41 @@ __device__ __forceinline__ void png_unfilter_file(const int* __restrict__ images
         png_unfilter_file<false>(im[PG_H], im[PG_W], im[PG_BPP], nullptr, 0, scratch, raw_stride, out, Hc, Wc, sizes, status, f, lane);
 }
 
-// the host copy of the image table against the byte range, the canvas and the scratch
+// one row of the host copy of the image table against the byte range: sides, a colour type with its bpp, a stream at a
+// multiple of 16 inside the bytes
+bool png_image_row_ok(const int* im, long nbytes) {
+    const int H = im[PG_H], W = im[PG_W], ct = im[PG_TYPE], bpp = im[PG_BPP];
+    if (H < 1 || W < 1 || H > 16384 || W > 16384) return false;
+    if (!((ct == 0 && bpp == 1) || (ct == 2 && bpp == 3) || (ct == 6 && bpp == 4))) return false;
+    return !(im[PG_BEGIN] < 0 || (im[PG_BEGIN] & 15) || im[PG_BEGIN] > im[PG_END] || im[PG_END] > nbytes);
+}
+
+// The block without its canvas and its scratch row: the pointers, the counts, the alignment and every image row.  What any
+// decoder of a batch asks, whatever it decodes into (csrc/png_window.hip brings a canvas and a scratch of its own).
+bool png_decode_block_ok(const istvt_jpeg_decode_args* a) {
+    if (!a || a->n <= 0 || a->nbytes < 0 || a->nbytes > ISTVT_PNG_MAX_BYTES) return false;
+    if (!a->bytes || !a->images || !a->images_host || !a->scratch || !a->out || !a->sizes || !a->status) return false;
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->bytes) & 15)) return false;
+    for (int i = 0; i < a->n; ++i)
+        if (!png_image_row_ok(a->images_host + (long)i * ISTVT_PNG_IMAGE_INTS, a->nbytes)) return false;
+    return true;
+}
+
+// the host copy of the image table against the canvas and the scratch
 bool png_decode_check(const istvt_jpeg_decode_args* a, long raw_stride) {
     for (int i = 0; i < a->n; ++i) {
         const int* im = a->images_host + (long)i * ISTVT_PNG_IMAGE_INTS;
-        const int H = im[PG_H], W = im[PG_W], ct = im[PG_TYPE], bpp = im[PG_BPP];
-        if (H < 1 || W < 1 || H > 16384 || W > 16384 || H > a->Hc || W > a->Wc) return false;
-        if (!((ct == 0 && bpp == 1) || (ct == 2 && bpp == 3) || (ct == 6 && bpp == 4))) return false;
-        if (im[PG_BEGIN] < 0 || (im[PG_BEGIN] & 15) || im[PG_BEGIN] > im[PG_END] || im[PG_END] > a->nbytes) return false;
-        if ((long)H * (1 + (long)W * bpp) > raw_stride) return false;
+        if (im[PG_H] > a->Hc || im[PG_W] > a->Wc) return false;
+        if ((long)im[PG_H] * (1 + (long)im[PG_W] * im[PG_BPP]) > raw_stride) return false;
     }
     return true;
 }
 
 // what both entries refuse before they look at the scratch
 bool png_decode_args_ok(const istvt_jpeg_decode_args* a, int raw_stride) {
-    if (!a || a->n <= 0 || a->nbytes < 0 || a->nbytes > ISTVT_PNG_MAX_BYTES || raw_stride < 16 || (raw_stride & 15)) return false;
-    if (!a->bytes || !a->images || !a->images_host || !a->scratch || !a->out || !a->sizes || !a->status) return false;
+    if (!png_decode_block_ok(a) || raw_stride < 16 || (raw_stride & 15)) return false;
     if (a->Hc < 1 || a->Wc < 1 || a->Hc > 16384 || a->Wc > 16384) return false;
     if (!png_decode_check(a, raw_stride)) return false;
-    if ((reinterpret_cast<uintptr_t>(a->scratch) & 15) || (reinterpret_cast<uintptr_t>(a->bytes) & 15)) return false;
     const uint8_t* src = (const uint8_t*)a->bytes;
     const uint8_t* out = (const uint8_t*)a->out;
     const long nout = (long)a->n * a->Hc * a->Wc * 3;

@@ -575,14 +575,20 @@ def png_decode_u8(batch, canvas=None, out: Optional[Tensor] = None, checked: boo
     return out, sizes, status
 
 
-def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], buffers):
+def _bank_call(what: str, bank, m: int, device, canvas, out: Optional[Tensor], buffers, rows: Optional[int] = None):
     """What a decode of m places of a bank needs beside the index: the canvas, the uploaded bank, `out` and `buffers` checked
-    or made -> (the bank on its device, Hc, Wc, out, scratch, sizes, status)"""
+    or made -> (the bank on its device, Hc, Wc, out, scratch, sizes, status).  rows: the window height of a windowed decode of a
+    clips.PngBank, whose canvas is rows x Wc and whose scratch is the window's (clips.png_window_scratch_bytes)."""
     Hc, Wc = _canvas(what, bank.Hmax, bank.Wmax, canvas, ' of the bank')
+    if rows is not None:
+        Hc = rows
     dev = bank.on(device)
     out = _u8_out(what, dev.data, (m, Hc, Wc, 3), out)
     _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), "bank's files")
-    if isinstance(bank, clips.PngBank):
+    if rows is not None:
+        need = clips.png_window_scratch_bytes(bank, m, rows)
+        layout = ' (clips.png_window_scratch_bytes: filtered rows, a status word per slot, moved boxes and origins)'
+    elif isinstance(bank, clips.PngBank):
         need, layout = clips.png_bank_scratch_bytes(bank, m), ' (clips.png_bank_scratch_bytes: filtered rows and a status word per band)'
     else:
         need = clips.jpeg_bank_scratch_bytes(bank, m)
@@ -744,7 +750,99 @@ def png_decode_bank_drawn_u8(bank, plan, canvas=None, out: Optional[Tensor] = No
     return _png_bank_decode('bank_drawn', bank, plan.block, (plan.B, plan.T, plan.block.numel()), *front) + (plan.draw,)
 
 
-def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
+# ---- PNG windows ---------------------------------------------------------------------------------------------------------------
+def _png_window_call(name: str, src, reads, head, boxes: Tensor, m: int, rows: int, dev, Hc: int, Wc: int, out: Tensor, scratch: Tensor,
+                     sizes: Tensor, status: Tensor):
+    """The call of a windowed decode of m places behind the front end: the entry istvt_png_decode_<name>_u8 with the boxes where
+    qtabs go and `reads` (a batch's image table, a bank's index, a plan's draw block) where images_host goes -> (out, moved boxes,
+    sizes, status, origin), the boxes and origins being views of the scratch"""
+    win_bands, win_stride = clips.png_window_bands(src, rows), clips.png_window_stride(src, rows)
+    if isinstance(src, clips.PngBank):
+        tabs = SimpleNamespace(data=dev.data, images=dev.images, segments=dev.segments, qtabs=boxes)
+        args = _decode_args(tabs, reads, scratch, out, sizes, status, src.n, src.nband, m, 0, src.first_byte + src.nbytes, Hc, Wc)
+        tail = (src.band_max, src.raw_stride, win_bands, win_stride)
+    else:                                                         # the flags' host copy goes where htabs do
+        tabs = SimpleNamespace(data=dev.data, images=dev.images, segments=dev.bands, qtabs=boxes, htabs=src.alone)
+        args = _decode_args(tabs, reads, scratch, out, sizes, status, m, int(src.bands.shape[0]), m, m, src.nbytes, Hc, Wc,
+                            segments_host=src.bands)
+        tail = (win_bands, win_stride)
+    # the bytes: + the streams of the touched bands, known on the device
+    _call('istvt_png_decode_%s_u8' % name, 2 * m * win_stride + out.numel(), ctypes.byref(args), *head, *tail)
+    at = clips.png_window_boxes_at(src, m, rows)
+    words = scratch[at:at + 20 * m].view(torch.int32)
+    return out, words[:4 * m].view(m, 4), sizes, status, words[4 * m:]
+
+
+def png_decode_window_u8(batch_or_bank, boxes, index=None, rows: Optional[int] = None, canvas_w: Optional[int] = None,
+                         out: Optional[Tensor] = None, buffers=None):
+    """PNG windows (clips.py): files whose bands stand alone are decoded through one box (y0, x0, h, w) per place, and only the
+    bands a box touches are inflated and unfiltered -> (windows uint8 [m, rows, Wc, 3], moved_boxes int32 [m, 4], sizes int32
+    [m, 2], status int32 [m], origin int32 [m]), the bytes of clips.png_bank_window_host: place j holds rows [origin, origin +
+    the window's rows) of its image at its top, 0 elsewhere, and moved_boxes[j] is the box within it, so that
+    crop_resize_u8(windows, moved_boxes, S, checked=True) is the crop of the whole frame through the box.  A place with a status
+    (clips.PNG_STATUS and its siblings; 11 and 12 are clips.PNG_WINDOW_STATUS's) has a window of zeros and the box (0, 0, 1, 1):
+    a black crop.  Damage in a band the box does not touch is not seen.  moved_boxes and origin are views of the scratch.
+    batch_or_bank: a clips.PngBatch packed with clips.png_batch(files, bands='index', alone=True) whose files all carry the
+    flag -- place j is file j, and boxes int32 [n, 4] live on the host or on the device -- or a clips.PngBank packed with
+    clips.png_bank(files, alone=True) with `index` as png_decode_bank_u8 takes it; index and boxes may both live on the device,
+    and `rows` is then required.  Host boxes (with a host index) are checked by name first (clips.check_png_window) and
+    uploaded; rows=None then takes the smallest window that fits them.  canvas_w defaults to the widest image.  buffers =
+    (scratch uint8 of clips.png_window_scratch_bytes(batch_or_bank, m, rows) bytes and 16-byte aligned, sizes, status): with
+    `out`, `buffers`, and boxes and index on the device, nothing is allocated and nothing synchronises, and the call can be
+    captured in a graph.  Two launches (istvt_png_decode_window_u8, istvt_png_decode_bank_window_u8)."""
+    what = 'png_decode_window_u8'
+    src = batch_or_bank
+    boxes, rows, Wc = clips.check_png_window(src, boxes, index, rows, canvas_w, what)
+    if isinstance(src, clips.PngBank):
+        index = clips.check_bank_index(index, what)
+        if not torch.cuda.is_available():
+            raise RuntimeError('istvt_amd: %s needs a ROCm device (no CPU fallback exists for the ISTVT hot path)' % what)
+        device = index.device if index.is_cuda else boxes.device if boxes.is_cuda else out.device if out is not None and out.is_cuda \
+            else torch.device('cuda', torch.cuda.current_device())
+        m = int(index.numel())
+        front = _bank_call(what, src, m, device, (src.Hmax, Wc), out, buffers, rows=rows)
+        on = front[0].data.device
+        if index.device != on:
+            index = index.to(on, non_blocking=True)
+        if index.dtype != torch.int32:                            # -1 and n are outside the bank as everything beyond them is
+            index = index.clamp(-1, src.n).to(torch.int32)
+        boxes = _frame_table(what, _BOXES, boxes, m, None, on, boxes.is_cuda, lambda b, k: b)
+        return _png_window_call('bank_window', src, index, (m,), boxes, m, rows, *front)
+    device = boxes.device if boxes.is_cuda else _decode_device(what, out)
+    n = src.n
+    dev = src.on(device)
+    out = _u8_out(what, dev.data, (n, rows, Wc, 3), out)
+    _no_overlap(what, out, dev.data.data_ptr(), dev.data.numel(), 'uploaded files')
+    scratch, sizes, status = _decode_buffers(what, device, n, clips.png_window_scratch_bytes(src, n, rows), buffers,
+                                             ' (clips.png_window_scratch_bytes: filtered rows, a status word per slot, moved boxes '
+                                             'and origins)')
+    boxes = _frame_table(what, _BOXES, boxes, n, None, device, boxes.is_cuda, lambda b, k: b)
+    return _png_window_call('window', src, src.images, (), boxes, n, rows, dev, rows, Wc, out, scratch, sizes, status)
+
+
+def png_decode_bank_window_drawn_u8(bank, plan, rows: Optional[int] = None, canvas_w: Optional[int] = None,
+                                    out: Optional[Tensor] = None, buffers=None):
+    """batch_draw(plan) and png_decode_window_u8(bank, the boxes just drawn, the index just drawn) as one call of three launches
+    -> (windows, moved_boxes, sizes, status, origin, draw): the first five as png_decode_window_u8 hands them back for m = B *
+    T, draw as batch_draw does.  The bank was packed with clips.png_bank(files, alone=True); the plan was built for it and lives
+    on its device.  rows defaults to clips.png_window_rows(bank, plan.max_side), which fits every box the plan draws; canvas_w,
+    out and buffers are png_decode_window_u8's.  With out and buffers the call can be captured in a graph."""
+    what = 'png_decode_bank_window_drawn_u8'
+    if not isinstance(bank, clips.PngBank):
+        raise TypeError('%s expects a clips.PngBank, got %s' % (what, type(bank).__name__))
+    plan = _drawn_plan(what, plan)
+    if plan.N != bank.n:
+        raise ValueError('%s: the plan was built for a bank of %d places, this one has %d' % (what, plan.N, bank.n))
+    if rows is None and bank.alone:
+        rows = clips.png_window_rows(bank, plan.max_side)
+    boxes, rows, Wc = clips.check_png_window(bank, plan.draw.boxes, plan.draw.index, rows, canvas_w, what)
+    m = plan.B * plan.T
+    front = _bank_call(what, bank, m, plan.block.device, (bank.Hmax, Wc), out, buffers, rows=rows)
+    return _png_window_call('bank_window_drawn', bank, plan.block, (plan.B, plan.T, plan.block.numel()), boxes, m, rows, *front) \
+        + (plan.draw,)
+
+
+def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None, window: bool = False):
     """The whole input side of a training step on the device: the batch of the plan's current step is drawn and decoded
     (jpeg_decode_drawn_u8; png_decode_bank_drawn_u8 for a clips.PngBank), every frame cut and resized through its drawn box (crop_resize_u8), recompressed at its clip's
     drawn quality (jpeg_roundtrip_u8; left out when the plan's jpeg is off) and perturbed by its clip's drawn row (perturb_u8
@@ -753,7 +851,17 @@ def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
     clips.batch_draw_host(plan, step).  The step is model(u8, view=view, view_checked=True, crop=S).  No host table, no
     upload, no synchronisation: with `out` (uint8, contiguous, of the result's shape) the call can be captured in a graph,
     and every replay gives the next batch.  view, label and the draw behind them are views of the plan's draw block, which
-    the next draw overwrites."""
+    the next draw overwrites.  window=True (a clips.PngBank packed with alone=True): the decode is
+    png_decode_bank_window_drawn_u8, which inflates and unfilters only the bands each drawn box touches into a window of
+    clips.png_window_rows(bank, plan.max_side) rows, and the crop reads the windows through the boxes moved into them: the
+    same bytes, from a fraction of the canvas and of the scratch."""
+    if not isinstance(window, bool):
+        raise ValueError('draw_clips: window is True or False, got %r' % (window,))
+    if window and not isinstance(bank, clips.PngBank):
+        raise ValueError('draw_clips: window=True goes with a clips.PngBank packed with alone=True, got %s' % type(bank).__name__)
+    if window and not bank.alone:
+        raise ValueError('draw_clips: the bank was not packed with alone=True (clips.png_bank(files, alone=True)): only bands that '
+                         'stand alone are decoded by a box')
     plan = _drawn_plan('draw_clips', plan)
     S = _side('draw_clips', S)
     if plan.max_side > clips.MAX_BOX_SCALE * S:
@@ -761,10 +869,14 @@ def draw_clips(bank, plan, S: int, out: Optional[Tensor] = None):
                          '%d) are resized' % (plan.max_side, clips.MAX_BOX_SCALE * S, S))
     B, T = plan.B, plan.T
     out = _u8_out('draw_clips', plan.block, (B, T, S, S, 3), out)
-    frames, _, status, draw = (png_decode_bank_drawn_u8 if isinstance(bank, clips.PngBank) else jpeg_decode_drawn_u8)(bank, plan)
+    if window:
+        frames, boxes, _, status, _, draw = png_decode_bank_window_drawn_u8(bank, plan)
+    else:
+        frames, _, status, draw = (png_decode_bank_drawn_u8 if isinstance(bank, clips.PngBank) else jpeg_decode_drawn_u8)(bank, plan)
+        boxes = draw.boxes
     stages = ['crop'] + ['jpeg'] * (plan.thr_jpeg > 0) + ['perturb'] * (plan.thr_perturb > 0)
     flat = lambda stage: out.view(B * T, S, S, 3) if stages[-1] == stage else None      # the last stage writes `out`
-    u8 = crop_resize_u8(frames, draw.boxes, S, out=flat('crop'), checked=True)
+    u8 = crop_resize_u8(frames, boxes, S, out=flat('crop'), checked=True)
     if 'jpeg' in stages:
         u8 = jpeg_roundtrip_u8(u8, draw.quality, out=flat('jpeg'), checked=True)
     if 'perturb' in stages:
@@ -838,7 +950,7 @@ def jpeg_bank_ingest(jf, H=None, W=None, layout=None, restart_interval=None, seg
 
 
 def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, layouts=clips.JPEG_LAYOUTS_DEFAULT,
-                  index=None) -> Tensor:
+                  index=None, window: bool = False) -> Tensor:
     """Face crops from JPEG files: files (a sequence of bytes, a clips.JpegBatch or a clips.JpegFiles) are decoded on the device
     (jpeg_decode_u8) and every frame is cut and resized to S x S through `boxes` (int32 [n, 4], crop_resize_u8), or as a
     whole (clips.whole_boxes) where none are given -> uint8 [n, S, S, 3], ready for model(u8.view(B, T, S, S, 3), view=...)
@@ -849,7 +961,30 @@ def decode_frames(files, S: int, boxes: Optional[Tensor] = None, split=None, lay
     clips.PngBatch (clips.png_batch) is decoded by png_decode_u8 and cut the same way, by its bands where it carries them;
     split= and layouts= are refused for it.  A clips.PngBank (clips.png_bank) with `index` goes through png_decode_bank_u8 as a
     JpegBank goes through its decoder: whole-image boxes from the decoder's sizes, a place with status 8 or 9 black; split= and
-    layouts= are refused for it too."""
+    layouts= are refused for it too.  window=True (a clips.PngBatch or clips.PngBank packed with alone=True, and `boxes`): only
+    the bands each box touches are decoded (png_decode_window_u8) and the crop reads the windows through the moved boxes -- the
+    same bytes; host boxes are checked as crop_resize_u8 checks them, boxes on the device are the caller's, with h and w of at
+    most 8 S, and for a bank with boxes or an index on the device the window fits any such box."""
+    if not isinstance(window, bool):
+        raise ValueError('decode_frames: window is True or False, got %r' % (window,))
+    if window:
+        if not isinstance(files, (clips.PngBatch, clips.PngBank)):
+            raise ValueError('decode_frames: window=True goes with a clips.PngBatch or a clips.PngBank packed with alone=True; JPEG '
+                             'files are decoded whole')
+        if boxes is None:
+            raise ValueError('decode_frames: window=True decodes through boxes=, one per frame')
+        if split is not None or layouts is not clips.JPEG_LAYOUTS_DEFAULT:
+            raise ValueError('decode_frames: split= and layouts= go with JPEG files; a clips.%s takes neither' % type(files).__name__)
+        S = _side('crop_resize_u8', S)
+        rows = None
+        if not torch.is_tensor(boxes):                            # a list is a host table like any other
+            boxes = torch.tensor(boxes, dtype=torch.int32).reshape(-1, 4)
+        if not boxes.is_cuda:
+            clips.check_boxes(boxes, int(boxes.shape[0]) if boxes.dim() else 0, clips.PNG_MAX_SIDE, clips.PNG_MAX_SIDE, S)
+        if isinstance(files, clips.PngBank) and files.alone and (boxes.is_cuda or (torch.is_tensor(index) and index.is_cuda)):
+            rows = clips.png_window_rows(files, clips.MAX_BOX_SCALE * S)
+        windows, moved, _, _, _ = png_decode_window_u8(files, boxes, index=index, rows=rows)
+        return crop_resize_u8(windows, moved, S, checked=True)
     if isinstance(files, (clips.JpegBank, clips.PngBank)):
         if index is None:
             raise ValueError('decode_frames: a clips.%s is decoded through index=' % type(files).__name__)

@@ -24,7 +24,8 @@ from ._common import (G256_MIN, ROW_ALIGN, Tensor, _DT, _c, _ptr, _req, _stream,
 from .frames import (batch_draw, crop_resize_nv12, crop_resize_u8, decode_frames, draw_clips, encode_frames,  # noqa: F401
                      jpeg_bank_ingest, jpeg_decode_drawn_u8, jpeg_decode_indexed_u8, jpeg_decode_u8, jpeg_encode_u8,
                      jpeg_roundtrip_u8, nv12_to_rgb_u8, perturb_u8, png_decode_bank_drawn_u8, png_decode_bank_u8, png_decode_u8,
-                     png_encode_u8, relevance_paste_nv12, relevance_paste_u8, warp_similarity_nv12, warp_similarity_u8)
+                     png_decode_bank_window_drawn_u8, png_decode_window_u8, png_encode_u8, relevance_paste_nv12,
+                     relevance_paste_u8, warp_similarity_nv12, warp_similarity_u8)
 # Every copy derived from a parameter (the compute-dtype operand, its transpose, the stacked operand, the stem's layouts):
 # cached, refreshed and released by weights.py; the names below are the live cache's.
 from .weights import (_refresh_derived, _refresh_plain_copies, _static_holders, _transposed_operand,  # noqa: F401

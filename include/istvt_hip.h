@@ -606,6 +606,43 @@ int istvt_png_decode_bank_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T
 int istvt_png_decode_alone_u8(const istvt_jpeg_decode_args* a, int raw_stride);
 int istvt_png_decode_bank_alone_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride);
 int istvt_png_decode_bank_alone_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max, int raw_stride);
+/* PNG windows: files whose bands stand alone, decoded through one box (y0, x0, h, w) per place.  Only the bands the box touches
+ * are inflated and unfiltered, kfirst = y0 / R to klast = (y0 + h - 1) / R, into out uint8 [m][Hc][Wc][3] whose place j is a
+ * window: rows [w0, w1) = [kfirst R, min(H, (klast + 1) R)) of the image in its rows [0, w1 - w0) and columns [0, W), 0
+ * elsewhere.  The bytes of clips.png_bank_window_host.  Status int32 [m]: 8 and 9 as the bank has them; 11 the file's index does
+ * not say its bands stand alone; 12 the box does not lie in the image (h < 1, w < 1, y0 < 0, x0 < 0, y0 + h > H, x0 + w > W),
+ * its window has more than Hc rows or more than win_bands bands; then the first status that is not 0 of the touched bands in
+ * band order, 6 for a filter byte above 4 in rows [w0, w1), 10 for a row k R, k >= 1, of type 2, 3 or 4 among them, in that
+ * order.  Damage in a band the box does not touch is not seen.  A place with a status has a window of zeros, origin 0 and the
+ * moved box (0, 0, 1, 1); sizes int32 [m][2] are (H, W), or (0, 0) with 8 and 9.  Two launches of m * win_bands workgroups of
+ * one wave, wave b being slot b % win_bands of place b / win_bands and taking band kfirst + slot (a wave whose window has no
+ * such band, or whose place has a status, leaves at once); every wave checks the rows it uses (csrc/png_window.h).  No
+ * synchronisation, no global state, no atomics, nothing allocated.  The argument block is istvt_jpeg_decode_args.
+ * istvt_png_decode_bank_window_u8 reads the bank's fields as istvt_png_decode_bank_alone_u8 does, and
+ *   qtabs, nq      int32 [m][4] on the device: the boxes; nq == m
+ *   Hc, Wc         the window height `rows` and the canvas width: a file's W is compared with Wc, its H is not compared with Hc
+ *   scratch        16-byte aligned; m * win_stride bytes of filtered rows, the window of place j at scratch + j * win_stride |
+ *                  int32 [m * win_bands] band statuses, slot t of place j at word j * win_bands + t; a slot without a band is
+ *                  not written | from the next multiple of 16 bytes int32 [m][4], the boxes moved into their windows, (y0 - w0,
+ *                  x0, h, w) | int32 [m], the origins w0.  clips.png_window_scratch_bytes has the sum.
+ *   out, sizes, status, stream, images_host (the index, on the device)    as there
+ * win_bands: 1..band_max, the slots of a place; win_stride: a multiple of 16, at least min(H, Hc) (1 + W bpp) of every file
+ * (a file of more gets status 9).  The entry looks at scalars alone and returns -3 on what istvt_png_decode_bank_u8 refuses,
+ * asked with win_bands and win_stride in the place of band_max and raw_stride, on a band_max below 1, a raw_stride below 16 or
+ * not a multiple of 16, a null qtabs, nq != m, win_bands outside 1..band_max, a win_stride below 16 or not a multiple of 16, m *
+ * win_bands beyond an int, a scratch smaller than the layout, or an out that overlaps bytes.
+ * istvt_png_decode_window_u8 is the batch of istvt_png_decode_alone_u8 (clips.png_batch(bands='index', alone=True)): m == n and
+ * place j is file j.  It reads the fields of istvt_png_decode_bands_u8 and makes its checks of the host tables, with
+ *   qtabs, nq      the boxes, as above; nq == n
+ *   htabs, nh      int32 [n] on the HOST: file i's flag; nh == n.  -3 unless every flag is 1 and every file's band rows are the
+ *                  R-row bands of an index, as istvt_png_decode_alone_u8 asks of a flagged file
+ *   Hc, Wc, scratch    as above, with n in the place of m
+ * istvt_png_decode_bank_window_drawn_u8 is the draw in front of the bank's entry with m = B * T: three launches.  images_host
+ * is the draw block as istvt_batch_draw reads it, and qtabs points at the boxes inside it, which the draw has just written. */
+int istvt_png_decode_window_u8(const istvt_jpeg_decode_args* a, int win_bands, int win_stride);
+int istvt_png_decode_bank_window_u8(const istvt_jpeg_decode_args* a, int m, int band_max, int raw_stride, int win_bands, int win_stride);
+int istvt_png_decode_bank_window_drawn_u8(const istvt_jpeg_decode_args* a, int B, int T, int block_ints, int band_max, int raw_stride,
+                                          int win_bands, int win_stride);
 /* JPEG files out: frames uint8 [n][H][W][3] (`total` bytes readable at frames, >= n*H*W*3) -> n baseline JFIF files laid end
  * to end in data, the bytes of clips.jpeg_encode_host: the forward half of the round trip above (colour in, padding, 4:2:0
  * downsample at subsampling = 2 or none at 0, the slow-integer DCT, the quantiser of the frame's quality), Huffman coding with

@@ -53,6 +53,10 @@ each kernel's share of b and c from a torch.profiler trace of ten more calls; th
 band-first rows changed their type (clips.png_filter_rows_host on the distinct frames).  Then the 224 x 224 frames as a bank
 of --bank-files places, 256 drawn per call: ops.png_decode_bank_u8 and ops.draw_clips from the indexed bank and from the alone
 bank.
+
+--window --against PARENT.so [--bench-py K [--parent-tree DIR]]  instead of the above (DESIGN.md "PNG windows"): window_main's
+docstring has the cases.  b: the parent commit's whole decode of an alone bank and its crop; w: this tree's windowed decode and
+the crop of the windows through the moved boxes.
 """
 import argparse
 import io
@@ -552,6 +556,151 @@ def alone_main(a):
             f.write('\n'.join(lines) + '\n' + line + '\n')
 
 
+def window_case(a, lines, res, key, bank, src_dev, index, boxes, S, other):
+    """--window, one case: m places of `bank` through `boxes` -> (b) the parent's whole decode and the crop, (w) this tree's
+    windowed decode and the crop, in alternation, each first in turn"""
+    from istvt_amd import _lib
+    dev = src_dev.device
+    m, H, W = len(index), bank.Hmax, bank.Wmax
+    idx, bx = torch.tensor(index, dtype=torch.int32, device=dev), torch.tensor(boxes, dtype=torch.int32, device=dev)
+    rows = clips.check_png_window(bank, torch.tensor(boxes, dtype=torch.int32), index)[1]      # the smallest window that fits them
+    d = bank.on(dev)
+    whole = torch.empty((m, H, W, 3), dtype=torch.uint8, device=dev)
+    bbuf = (torch.empty((clips.png_bank_scratch_bytes(bank, m),), dtype=torch.uint8, device=dev),
+            torch.empty((m, 2), dtype=torch.int32, device=dev), torch.empty((m,), dtype=torch.int32, device=dev))
+    wins = torch.empty((m, rows, W, 3), dtype=torch.uint8, device=dev)
+    wbuf = (torch.empty((clips.png_window_scratch_bytes(bank, m, rows),), dtype=torch.uint8, device=dev),
+            torch.empty((m, 2), dtype=torch.int32, device=dev), torch.empty((m,), dtype=torch.int32, device=dev))
+    cut_b, cut_w = (torch.empty((m, S, S, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+    stream = torch.cuda.current_stream().cuda_stream
+    args = _lib.JpegDecodeArgs(bytes=d.data.data_ptr(), nbytes=bank.first_byte + bank.nbytes, images=d.images.data_ptr(),
+                               images_host=idx.data_ptr(), segments=d.segments.data_ptr(), scratch=bbuf[0].data_ptr(),
+                               scratch_bytes=bbuf[0].numel(), out=whole.data_ptr(), sizes=bbuf[1].data_ptr(), status=bbuf[2].data_ptr(),
+                               stream=stream, n=bank.n, nseg=bank.nband, Hc=H, Wc=W)
+
+    def leg_b():
+        _lib.check(other.istvt_png_decode_bank_alone_u8(ctypes.byref(args), m, bank.band_max, bank.raw_stride), 'parent istvt_png_decode_bank_alone_u8')
+        _lib.check(other.istvt_crop_resize_u8(whole.data_ptr(), whole.numel(), H, W, bx.data_ptr(), cut_b.data_ptr(), m, S, stream),
+                   'parent istvt_crop_resize_u8')
+        return cut_b, bbuf[2]
+
+    def leg_w():
+        got = ops.png_decode_window_u8(bank, bx, index=idx, rows=rows, out=wins, buffers=wbuf)
+        return ops.crop_resize_u8(got[0], got[1], S, out=cut_w, checked=True), got[3]
+
+    for name, fn in (('b', leg_b), ('w', leg_w)):                 # the pixels before anything is timed
+        for t in ((whole, cut_b) if name == 'b' else (wins, cut_w)):
+            t.fill_(7)
+        cut, status = fn()
+        clips.check_png_status(status)
+        torch.cuda.synchronize()
+        for j in (0, m // 2, m - 1):
+            y0, x0, h, w = boxes[j]
+            frame = src_dev[index[j] % DISTINCT]
+            if name == 'b' and not torch.equal(whole[j], frame):
+                raise SystemExit('%s, leg b: the decoded frames are not the source pixels' % key)
+            if name == 'w':
+                at = clips.png_window_boxes_at(bank, m, rows)
+                w0 = int(wbuf[0][at:at + 20 * m].view(torch.int32)[4 * m + j])                    # the origins stand behind the boxes
+                R = clips._png_window_files(bank)[index[j]][3]
+                w1 = min(H, ((y0 + h - 1) // R + 1) * R)
+                if w0 != y0 // R * R or not torch.equal(wins[j, :w1 - w0], frame[w0:w1]):
+                    raise SystemExit('%s, leg w: the windows are not the source pixels' % key)
+    if not torch.equal(cut_b, cut_w):
+        raise SystemExit('%s: the crops of the two routes differ' % key)
+    legs = {'b': leg_b, 'w': leg_w}
+    ts = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        order = list(legs.items())
+        for k, fn in order[r % 2:] + order[:r % 2]:
+            t = event_ms(fn)
+            if r >= a.warmup:
+                ts[k].append(t)
+    st = {k: stats(v) for k, v in ts.items()}
+    sb = kernel_shares(leg_b, frags=('png_bank_inflate_kernel', 'png_bank_unfilter_alone_kernel'))
+    sw = kernel_shares(leg_w, frags=('png_window_inflate_kernel', 'png_window_unfilter_kernel'))
+    spread = max(st['b']['max_ms'] - st['b']['min_ms'], 1e-9)
+    diff = st['b']['median_ms'] - st['w']['median_ms']
+    inside = st['b']['min_ms'] <= st['w']['median_ms'] <= st['b']['max_ms']
+    bytes_b, bytes_w = whole.numel() + bbuf[0].numel(), wins.numel() + wbuf[0].numel()
+    res[key] = dict(st, kernel_us_b=sb, kernel_us_w=sw, places=m, rows=rows, bytes_b=bytes_b, bytes_w=bytes_w, w_inside_b_range=inside,
+                    waves_b=m * bank.band_max, waves_w=m * clips.png_window_bands(bank, rows))
+    say(lines, '  %s: %d places, window of %d rows, %d waves against %d | (b) the parent\'s whole decode and the crop %s, its range %.3f ms '
+        '(inflate %.0f us, unfilter %.0f us per call) | (w) the windowed decode and the crop %s (inflate %.0f us, unfilter %.0f us per call) | '
+        'b - w = %.3f ms = %.1f ranges of b, b / w = %.2f x, w is %s the range of b | out + scratch: %.1f MB against %.1f MB'
+        % (key, m, rows, m * clips.png_window_bands(bank, rows), m * bank.band_max, fmt(st['b']), spread, sb['png_bank_inflate_kernel'],
+           sb['png_bank_unfilter_alone_kernel'], fmt(st['w']), sw['png_window_inflate_kernel'], sw['png_window_unfilter_kernel'], diff,
+           diff / spread, st['b']['median_ms'] / st['w']['median_ms'], 'inside' if inside else 'OUTSIDE', bytes_w / 1e6, bytes_b / 1e6))
+
+
+def window_main(a):
+    """--window --against PARENT.so (DESIGN.md "PNG windows"): frames of 1080 x 1920 at band_rows 8 and 16, written by
+    ops.png_encode_u8(alone=True), as a bank of 32 places (8 distinct frames); 8 and 256 places drawn by a device index through
+    boxes of 360 x 360 at a fixed and at a random y0 and through the degenerate box of all 1080 rows; 256 places of 224 x 224
+    through whole-image boxes; ops.draw_clips with and without window=True at 32 clips of 8 frames.  (b) is the parent commit's
+    istvt_png_decode_bank_alone_u8 and istvt_crop_resize_u8 from the library given with --against, (w) this tree's
+    ops.png_decode_window_u8 and ops.crop_resize_u8; caller's buffers, the legs in alternation, each first in turn."""
+    if not torch.cuda.is_available():
+        raise SystemExit('png_decode_bench.py measures on a GPU; none is visible')
+    from istvt_amd import _lib
+    torch.zeros(1, device='cuda')
+    dev = torch.device('cuda', torch.cuda.current_device())
+    lines, res = [], {}
+    if not a.only_bench_py:
+        if not a.against:
+            raise SystemExit('--window measures against the parent commit\'s library: --against PARENT.so')
+        other = ctypes.CDLL(os.path.abspath(a.against))
+        for name in ('istvt_png_decode_bank_alone_u8', 'istvt_crop_resize_u8'):
+            getattr(other, name).argtypes, getattr(other, name).restype = _lib.SIGNATURES[name], ctypes.c_int
+        S, N = a.size, 32
+        g = torch.Generator().manual_seed(41)
+        big = torch.stack([torch.from_numpy(smooth_image(1080, 1920, 2000 + i)) for i in range(DISTINCT)]).to(dev)
+        small = torch.stack([torch.from_numpy(smooth_image(S, S, 1000 + i)) for i in range(DISTINCT)]).to(dev)
+        for R in a.band_rows:
+            hs = [clips.png_parse(f) for f in ops.png_encode_u8(big, R, index=True, alone=True).files()]
+            bank = clips.png_bank([hs[i % DISTINCT] for i in range(N)], alone=True)
+            say(lines, 'band_rows %d: a bank of %d places of 1080 x 1920 (%d distinct frames), crops of %d x %d' % (R, N, DISTINCT, S, S))
+            for m in (8, a.frames):
+                index = torch.randint(0, N, (m,), generator=g).tolist()
+                ys = torch.randint(0, 1080 - 360 + 1, (m,), generator=g).tolist()
+                for tag, boxes in (('fixed_y0', [[360, 780, 360, 360]] * m), ('random_y0', [[y, 780, 360, 360] for y in ys]),
+                                   ('all_rows', [[0, 420, 1080, 1080]] * m)):
+                    window_case(a, lines, res, 'r%d_%d_places_%s' % (R, m, tag), bank, big, index, boxes, S, other)
+            T, B = 8, 32
+            base = torch.tensor([[360, 780, 360, 360]] * N, dtype=torch.int32)
+            out_d = torch.empty((B, T, S, S, 3), dtype=torch.uint8, device=dev)
+            plans = {k: clips.BatchPlan(bank, [(0, N, 0)], T=T, B=B, base=base, seed=5).on(dev) for k in ('whole', 'window')}
+            legs = {k: (lambda k=k: ops.draw_clips(bank, plans[k], S, out=out_d, window=k == 'window')) for k in plans}
+            first = {k: fn()[0].clone() for k, fn in legs.items()}
+            if not torch.equal(first['whole'], first['window']):
+                raise SystemExit('draw_clips: the two routes differ')
+            ts = {k: [] for k in legs}
+            for r in range(a.warmup + a.reps):
+                order = list(legs.items())
+                for k, fn in order[r % 2:] + order[:r % 2]:
+                    t = event_ms(fn)
+                    if r >= a.warmup:
+                        ts[k].append(t)
+            st = {k: stats(v) for k, v in ts.items()}
+            res['r%d_draw_clips' % R] = st
+            say(lines, '  draw_clips, %d clips of %d frames, base boxes of 360 x 360, all stages: %s without window=True, %s with it (this tree both)'
+                % (B, T, fmt(st['whole']), fmt(st['window'])))
+            bank._on.clear()
+            hs = [clips.png_parse(f) for f in ops.png_encode_u8(small, R, index=True, alone=True).files()]
+            bank = clips.png_bank([hs[i % DISTINCT] for i in range(N)], alone=True)
+            index = torch.randint(0, N, (a.frames,), generator=g).tolist()
+            window_case(a, lines, res, 'r%d_%d_places_of_%d_whole_image' % (R, a.frames, S), bank, small, index, [[0, 0, S, S]] * a.frames, S, other)
+            bank._on.clear()
+    if a.bench_py:
+        bench_py(a, lines, res)
+    line = json.dumps({'png_window_bench': res})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n' + line + '\n')
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--frames', type=int, default=256)
@@ -570,7 +719,11 @@ def main():
     p.add_argument('--bank', action='store_true')
     p.add_argument('--bank-files', type=int, default=4096)
     p.add_argument('--alone', action='store_true')
+    p.add_argument('--window', action='store_true')
     a = p.parse_args()
+    if a.window:
+        a.band_rows = [8, 16] if a.band_rows == [8, 16, 32] else a.band_rows
+        return window_main(a)
     if a.alone:
         a.band_rows = [8, 16] if a.band_rows == [8, 16, 32] else a.band_rows
         return alone_main(a)
